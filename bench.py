@@ -5,14 +5,21 @@
     one step = one pass of the hot path over a batch of 1024 synthetic 1 s utterances
                -> [1024*99, 39] = MFCC | delta | delta-delta   (dsp_mfcc_delta_batch, C ABI: ONE fused kernel)
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Inputs are resident in HBM before the timed region; successive steps rotate over distinct input
 batches whose total size exceeds the 256 MiB Infinity Cache, so reads come from HBM.  Utterances
-shard across ranks with no data-path collective (weak scaling: every rank owns its own batches);
-configs[2] (12 500 utterances per GPU in one launch, then the RCCL gather of the [12500*99, 39] result to rank 0)
-is timed separately and reported under "gather" -- it is not part of `value`.
+shard across ranks with no data-path collective (weak scaling: every rank owns its own batches).
+The timed region is exactly K steps; `ms_per_step` is its wall time / K.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the dump of the
+last step's output (--dump-outputs DIR: rank 0's [1024*99, 39] fp32 rows -> DIR/features.npy; the
+inputs are seeded, so two builds can be compared output for output) and the result line.  --full
+adds everything else, each timed on its own and never part of `value`: the single-stream kernel
+time and the roofline, the parity guard against the CPU oracle, configs[2] (N > 1: 12 500
+utterances per GPU in one launch, then the RCCL gather of the [12500*99, 39] result to rank 0,
+under "gather"), the other paths (N = 1) and the CPU baseline.
 
 rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).
 """
@@ -69,6 +76,47 @@ def compute_roof(kernel_ms):
         out.update({'clock_ghz_measured': clock, 'peak_at_measured_clock': VALU_LANES * clock * 1e9 / 1e12,
                     'frac_at_measured_clock': ach / (VALU_LANES * clock * 1e9)})
     return out
+
+
+def roofline(kernel_ms, mfcc_only_ms, spans, steps, frames_per_s):
+    """--full: the step's ONE kernel against the HBM roof (kernel_ms: single-stream event time per launch; spans:
+    device-side span of every timed block; frames_per_s: the headline rate of one GPU) and against compute_roof's."""
+    # HBM traffic per launch measured with rocprofv3 PMC passes (cannot be collected inside this process)
+    traffic, step_traffic, traffic_source = None, None, None
+    for name in ('r4_traffic.json', 'r3_traffic.json'):     # FETCH / WRITE passes of THIS kernel (the fused one); older files describe the round-2 kernel
+        try:
+            with open(os.path.join(ROOT, 'profiles', name)) as fh:
+                tj = json.load(fh)
+            if tj.get('frames_per_launch') == B * T:
+                traffic = tj['traffic_bytes_per_launch']
+                step_traffic = tj.get('step_traffic_bytes')
+                traffic_source = (f'profiles/{name}: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this '
+                                  f'workload (FETCH doubled per the gfx950 guide); a constant read from that file, '
+                                  f'not measured in this run')
+                break
+        except (OSError, ValueError, KeyError):
+            continue
+    achieved = BYTES_PER_FRAME_ALL * B * T / (kernel_ms * 1e-3) / 1e9
+    return {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
+            'frac': achieved / HBM_PEAK_GBPS, 'traffic': traffic, 'traffic_source': traffic_source,
+            'step_traffic': step_traffic,
+            'frac_of_measured_copy_ceiling': achieved / 6290.0,   # MI355X_MICROARCH.md: 6.29 TB/s copy
+            'algorithmic_bytes_per_launch': BYTES_PER_FRAME_ALL * B * T,
+            'kernel': 'fused MFCC + delta + delta-delta kernel (dsp_mfcc_delta_batch: the whole step is this one '
+                      'launch; reads 4 B x 16000 per utterance, writes 156 B per frame)',
+            'kernel_ms': kernel_ms, 'kernel_ms_note': 'one launch stream, back to back, HIP events',
+            'kernel_ms_overlapped': float(np.median(spans)) / steps,
+            'kernel_ms_overlapped_note': 'device-side span of a timed block (HIP events on every launch '
+                                         'stream, max over streams) / K: the same kernel under the stream '
+                                         'overlap of the timed region; <= ms_per_step',
+            'bytes_per_frame': BYTES_PER_FRAME_ALL, 'frames_per_launch': B * T,
+            'mfcc_only_kernel': {'kernel': 'MFCC-only kernel (dsp_features_batch, DSP_OUT_MFCC -> [sum T, 13]), the '
+                                           'kernel rounds 1-2 reported', 'kernel_ms': mfcc_only_ms,
+                                 'bytes_per_frame': BYTES_PER_FRAME_MFCC,
+                                 'achieved': BYTES_PER_FRAME_MFCC * B * T / (mfcc_only_ms * 1e-3) / 1e9,
+                                 'frac': BYTES_PER_FRAME_MFCC * B * T / (mfcc_only_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS},
+            'whole_step_GBps': BYTES_PER_FRAME_ALL * frames_per_s / 1e9,
+            'compute': compute_roof(kernel_ms)}
 
 
 def synth_batch(seed):
@@ -431,11 +479,17 @@ def main():
     ap.add_argument('--warmup', type=int, default=200)
     ap.add_argument('--buffers', type=int, default=8, help='distinct input batches rotated over (x65.5 MB)')
     ap.add_argument('--streams', type=int, default=3, help='HIP streams the independent steps alternate over')
-    ap.add_argument('--min-time', type=float, default=0.6,
-                    help='the K-step timed block is repeated until this many seconds have been timed')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-gather', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the NFFT=1536 / configs[3] side timings')
+    ap.add_argument('--min-time', type=float, default=0.0,
+                    help='repeat the K-step timed block (at least 3 times) until this many seconds have been timed; '
+                         'default 0: ONE block of exactly --steps steps')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's output (rank 0) to DIR/features.npy")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what is not the headline: kernel time + roofline, parity guard, gather (N > 1), '
+                         'other paths (N = 1), CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-gather', action='store_true', help='with --full: skip the configs[2] gather (N > 1)')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the NFFT=1536 / configs[3] side timings')
     args = ap.parse_args()
     if args.gpus < 1 or args.steps < 1:
         raise SystemExit('bench.py: --gpus and --steps must be >= 1')
@@ -494,10 +548,12 @@ def main():
     ns = len(streams)
     outs = [[torch.empty((B * T, D), dtype=torch.float32, device=dev) for _ in range(2)] for _ in range(ns)]
 
+    def out_of(i):
+        return outs[i % ns][(i // ns) & 1]
+
     def step(i):
-        k = i % ns
-        plan.run_raw(waves[i % len(waves)].data_ptr(), nat.WAVE_F32, layout, outs[k][(i // ns) & 1].data_ptr(),
-                     DELTA_N, streams[k].cuda_stream)
+        plan.run_raw(waves[i % len(waves)].data_ptr(), nat.WAVE_F32, layout, out_of(i).data_ptr(),
+                     DELTA_N, streams[i % ns].cuda_stream)
 
     def sync_all():
         torch.cuda.synchronize(dev)
@@ -542,19 +598,28 @@ def main():
         torch.cuda.synchronize(dev)
     for i in range(args.warmup):
         step(i)
-    # The K-step block is timed R times (R from the first block, identical on all ranks) so that the
-    # timed region covers >= --min-time seconds even when K is small; the line reports the median.
+    # ONE block of exactly K steps.  --min-time > 0 repeats the block R times (R from the first block, identical
+    # on all ranks) so that the timed region covers that many seconds even when K is small; the line then
+    # reports the median block.
     blocks = [timed_block(0)]
-    n_blocks = int(min(1000, max(3, np.ceil(args.min_time / max(blocks[0][0], 1e-6)))))
+    n_blocks = 1
+    if args.min_time > 0:
+        n_blocks = int(min(1000, max(3, np.ceil(args.min_time / max(blocks[0][0], 1e-6)))))
     for r in range(1, n_blocks):
         blocks.append(timed_block(r * args.steps))
     walls = np.array([b[0] for b in blocks])
     spans = np.array([b[1] for b in blocks])
     dt = float(np.median(walls))
 
-    # --- dominant kernel: the step's ONE kernel (fused MFCC + delta + delta-delta, dsp_mfcc_delta_batch) timed alone,
-    #     launches back to back on ONE stream, HIP events on that stream, same input rotation; and, for the record,
-    #     the MFCC-only kernel of dsp_features_batch (what rounds 1-2 reported) ---
+    # --- what the last timed step computed (the timed block ended with a synchronize; nothing has written that
+    #     buffer since) ---
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'features.npy'), out_of(n_blocks * args.steps - 1).cpu().numpy())
+
+    # --- dominant kernel (--full): the step's ONE kernel (fused MFCC + delta + delta-delta, dsp_mfcc_delta_batch)
+    #     timed alone, launches back to back on ONE stream, HIP events on that stream, same input rotation; and,
+    #     for the record, the MFCC-only kernel of dsp_features_batch (what rounds 1-2 reported) ---
     lib = nat.load()
     cep = [torch.empty((B * T, plan.C), dtype=torch.float32, device=dev) for _ in range(2)]
 
@@ -581,12 +646,14 @@ def main():
             ktimes.append(kev0.elapsed_time(kev1) / ksteps)
         return float(np.median(ktimes))
 
-    kernel_ms = event_timed(step_one_stream)
-    mfcc_only_ms = event_timed(mfcc_only)
+    kernel_ms = mfcc_only_ms = None
+    if args.full:
+        kernel_ms = event_timed(step_one_stream)
+        mfcc_only_ms = event_timed(mfcc_only)
 
-    # --- parity guard on batch 0 (outside the timed region): HIP path vs the CPU oracle ---
+    # --- parity guard on batch 0 (--full, outside the timed region): HIP path vs the CPU oracle ---
     parity = None
-    if rank == 0:
+    if args.full and rank == 0:
         from oracle import dsp_oracle
         step(0)
         torch.cuda.synchronize(dev)
@@ -596,12 +663,12 @@ def main():
             ref = dsp_oracle.mfcc_delta(host0[b].astype(np.float64), delta_n=DELTA_N, winfunc=np.hamming, **CFG)
             parity = max(parity, float(np.max(np.abs(got[b] - ref)) / np.max(np.abs(ref))))
 
-    # --- configs[2]: every rank runs its 12 500-utterance share in ONE launch, then the [12500*99, 39] results are
-    #     gathered to rank 0 over RCCL (features/distributed.py: grouped send/recv, other ranks receive nothing).
-    #     Timed on its own, never part of `value`. ---
+    # --- configs[2] (--full): every rank runs its 12 500-utterance share in ONE launch, then the [12500*99, 39]
+    #     results are gathered to rank 0 over RCCL (features/distributed.py: grouped send/recv, other ranks receive
+    #     nothing).  Timed on its own, never part of `value`. ---
     gather = None
     gather_failed = False
-    if world > 1 and not args.no_gather:
+    if args.full and world > 1 and not args.no_gather:
         from features.distributed import gather_features
         share_out, share = share_launch(dev, plan, reps=3 if REHEARSE else 10)
         share_ms = max_over_ranks(share['ms_per_launch'])
@@ -645,25 +712,8 @@ def main():
         dist.all_gather(parts, mine)
         per_rank_ms = [float(x.item()) for x in parts]
 
-    # HBM traffic per launch measured with rocprofv3 PMC passes (cannot be collected inside this process)
-    traffic, step_traffic, traffic_source = None, None, None
-    for name in ('r4_traffic.json', 'r3_traffic.json'):     # FETCH / WRITE passes of THIS kernel (the fused one); older files describe the round-2 kernel
-        try:
-            with open(os.path.join(ROOT, 'profiles', name)) as fh:
-                tj = json.load(fh)
-            if tj.get('frames_per_launch') == B * T:
-                traffic = tj['traffic_bytes_per_launch']
-                step_traffic = tj.get('step_traffic_bytes')
-                traffic_source = (f'profiles/{name}: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this '
-                                  f'workload (FETCH doubled per the gfx950 guide); a constant read from that file, '
-                                  f'not measured in this run')
-                break
-        except (OSError, ValueError, KeyError):
-            continue
-
     frames_total = float(world) * B * T * args.steps
     value = frames_total / dt
-    achieved = BYTES_PER_FRAME_ALL * B * T / (kernel_ms * 1e-3) / 1e9
     res = {
         'metric': 'MFCC frames/sec at 16 kHz, 25 ms/10 ms, nfft=512, 40 mel, 13 cep',
         'value': value, 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -680,28 +730,10 @@ def main():
                    'frames_per_utterance': T, 'delta_n': DELTA_N, 'input_buffers_rotated': len(waves),
                    'hip_streams': ns,
                    'sharding': f'{world} ranks x independent batches, no data-path collective'},
-        'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
-                     'frac': achieved / HBM_PEAK_GBPS, 'traffic': traffic, 'traffic_source': traffic_source,
-                     'step_traffic': step_traffic,
-                     'frac_of_measured_copy_ceiling': achieved / 6290.0,   # MI355X_MICROARCH.md: 6.29 TB/s copy
-                     'algorithmic_bytes_per_launch': BYTES_PER_FRAME_ALL * B * T,
-                     'kernel': 'fused MFCC + delta + delta-delta kernel (dsp_mfcc_delta_batch: the whole step is this one '
-                               'launch; reads 4 B x 16000 per utterance, writes 156 B per frame)',
-                     'kernel_ms': kernel_ms, 'kernel_ms_note': 'one launch stream, back to back, HIP events',
-                     'kernel_ms_overlapped': float(np.median(spans)) / args.steps,
-                     'kernel_ms_overlapped_note': 'device-side span of a timed block (HIP events on every launch '
-                                                  'stream, max over streams) / K: the same kernel under the stream '
-                                                  'overlap of the timed region; <= ms_per_step',
-                     'bytes_per_frame': BYTES_PER_FRAME_ALL, 'frames_per_launch': B * T,
-                     'mfcc_only_kernel': {'kernel': 'MFCC-only kernel (dsp_features_batch, DSP_OUT_MFCC -> [sum T, 13]), the '
-                                                    'kernel rounds 1-2 reported', 'kernel_ms': mfcc_only_ms,
-                                          'bytes_per_frame': BYTES_PER_FRAME_MFCC,
-                                          'achieved': BYTES_PER_FRAME_MFCC * B * T / (mfcc_only_ms * 1e-3) / 1e9,
-                                          'frac': BYTES_PER_FRAME_MFCC * B * T / (mfcc_only_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS},
-                     'whole_step_GBps': BYTES_PER_FRAME_ALL * value / world / 1e9,
-                     'compute': compute_roof(kernel_ms)},
-        'parity_normwise_vs_oracle': parity,
     }
+    if args.full:
+        res['roofline'] = roofline(kernel_ms, mfcc_only_ms, spans, args.steps, value / world)
+        res['parity_normwise_vs_oracle'] = parity
     if REHEARSE:
         res['rehearsal'] = True
     if per_rank_ms is not None:
@@ -709,9 +741,9 @@ def main():
     if gather is not None:
         res['gather'] = gather
         res['gather_failed'] = bool(gather_failed)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         res['other_paths'] = other_paths(dev)
-    if rank == 0 and not args.no_cpu_baseline:      # rank 0's host cores, at every N (the other ranks wait at the final barrier)
+    if args.full and rank == 0 and not args.no_cpu_baseline:      # rank 0's host cores, at every N (the other ranks wait at the final barrier)
         res['cpu_baseline'] = cpu_baseline()
     if rank == 0:
         print(json.dumps(res), flush=True)

@@ -122,7 +122,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
     env = dict(os.environ, BENCH_REHEARSE_GLOO='1')
     env.pop('WORLD_SIZE', None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '10', '--warmup', '2',
-                        '--min-time', '0.05', '--buffers', '2', '--no-cpu-baseline', '--no-extras'],
+                        '--min-time', '0.05', '--buffers', '2', '--full', '--no-cpu-baseline', '--no-extras'],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -144,7 +144,7 @@ def test_bench_gather_failure_sets_the_flag_and_the_exit_code():
     env = dict(os.environ, BENCH_REHEARSE_GLOO='1', BENCH_FAIL_GATHER='1')
     env.pop('WORLD_SIZE', None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '1',
-                        '--min-time', '0.05', '--buffers', '2', '--no-cpu-baseline', '--no-extras'],
+                        '--min-time', '0.05', '--buffers', '2', '--full', '--no-cpu-baseline', '--no-extras'],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode != 0
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

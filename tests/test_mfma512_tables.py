@@ -13,16 +13,16 @@ from conftest import ROOT, normwise
 from oracle import dsp_oracle
 import golden_cases as gc
 
-SO = '/tmp/m512_tab.so'
-
 
 @pytest.fixture(scope='module')
-def emul():
+def emul(tmp_path_factory):
     if shutil.which('g++') is None:
         pytest.skip('no g++')
-    subprocess.run(['g++', '-O2', '-shared', '-fPIC', '-o', SO, os.path.join(ROOT, 'tools', 'mfma512_tables_c.cpp')], check=True)
+    so = str(tmp_path_factory.mktemp('m512') / 'm512_tab.so')     # a fresh path per session, never shared
+    subprocess.run(['g++', '-O2', '-shared', '-fPIC', '-o', so, os.path.join(ROOT, 'tools', 'mfma512_tables_c.cpp')], check=True)
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import mfma512_emul
+    mfma512_emul.SO = so
     return mfma512_emul
 
 
@@ -42,7 +42,7 @@ def test_tables_reproduce_the_oracle(emul, nfilt, L, win):
 def test_plans_the_kernel_does_not_serve_are_refused(emul):
     import ctypes as C
     from features import _plan as P
-    lib = C.CDLL(SO)
+    lib = C.CDLL(emul.SO)
 
     def rc(L=400, S=160, nfilt=40, lowfreq=0, numcep=13):
         window = np.ascontiguousarray(np.hamming(L), np.float32)
@@ -64,7 +64,7 @@ def test_host_fp16_rounding_is_ieee(emul):
     """The table builder's own fp32 -> fp16 conversion (round to nearest even, subnormals kept) against NumPy's, over
     normals, subnormals, ties, the overflow edge and signed zeros."""
     import ctypes as C
-    lib = C.CDLL(SO)
+    lib = C.CDLL(emul.SO)
     lib.m512_half.restype = C.c_uint16
     lib.m512_half.argtypes = [C.c_float]
     rng = np.random.default_rng(1)

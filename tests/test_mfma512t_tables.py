@@ -16,13 +16,17 @@ import golden_cases as gc
 
 
 @pytest.fixture(scope='module')
-def emul():
+def emul(tmp_path_factory):
     if shutil.which('g++') is None:
         pytest.skip('no g++')
-    for src, so in (('mfma512_tables_c.cpp', '/tmp/m512_tab.so'), ('mfma512t_tables_c.cpp', '/tmp/m512t_tab.so')):
-        subprocess.run(['g++', '-O2', '-shared', '-fPIC', '-o', so, os.path.join(ROOT, 'tools', src)], check=True)
+    d = tmp_path_factory.mktemp('m512t')     # a fresh path per session, never shared
+    for src, so in (('mfma512_tables_c.cpp', d / 'm512_tab.so'), ('mfma512t_tables_c.cpp', d / 'm512t_tab.so')):
+        subprocess.run(['g++', '-O2', '-shared', '-fPIC', '-o', str(so), os.path.join(ROOT, 'tools', src)], check=True)
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    import mfma512_emul
     import mfma512t_emul
+    mfma512_emul.SO = str(d / 'm512_tab.so')
+    mfma512t_emul.SO = str(d / 'm512t_tab.so')
     return mfma512t_emul
 
 

@@ -23,6 +23,7 @@ from features import _plan as P  # noqa: E402
 
 KAP = np.array([[0, 2, 4, 6], [15, 13, 11, 9], [1, 3, 5, 7], [14, 12, 10, 8]])
 XBITS, WSH = 10, 16
+SO = '/tmp/m512_tab.so'
 
 
 def mbin(s, kr):
@@ -32,7 +33,7 @@ def mbin(s, kr):
 
 
 def build(L=400, S=160, nfilt=40, numcep=13, lifter=22, append_energy=True, rate=16000, win=np.hamming):
-    lib = C.CDLL('/tmp/m512_tab.so')
+    lib = C.CDLL(SO)
     window = np.ascontiguousarray(win(L), np.float32)
     fb = P.filterbank_matrix(nfilt, 512, rate, 0, None)
     st, cnt, w = P.mel_csr(fb)

@@ -5,8 +5,8 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/prof_r3
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B1="$R/bench.py --steps 200 --warmup 20 --streams 1 --no-cpu-baseline --no-extras"
-B3="$R/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extras"
+B1="$R/bench.py --steps 200 --warmup 20 --streams 1 --full --no-cpu-baseline --no-extras"
+B3="$R/bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --no-extras"
 KB="$R/tools/kbench.py --reps 10 --rounds 1"
 K15="$R/tools/kbench_cfg.py --reps 4"
 run() { tag=$1; shift; "$@" > $O/$tag.log 2>&1 || echo "$tag: rc=$?" >> $O/errors.txt; }
