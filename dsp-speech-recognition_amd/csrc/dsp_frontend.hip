@@ -17,6 +17,7 @@
 #include "kernels_mfma512t.h"
 #include "kernels_vad.h"
 #include "kernels_pitch.h"
+#include "kernels_cepstrum.h"
 
 thread_local int g_host_dry_run = 0;   // dsp_debug_host_dry_run: plan tables in host memory (sanitizer build, no GPU)
 
@@ -1112,6 +1113,86 @@ int dsp_pitch_rows_batch(double* d_rows, const int64_t* d_frame_offsets, int32_t
     if ((flags & 4) && !(flags & 2)) return fail(DSP_EINVAL, "dsp_pitch_rows_batch: the repair sweeps (4) need the arg-max (2)");
     if ((flags & 2) && !d_pitch) return fail(DSP_EINVAL, "dsp_pitch_rows_batch: d_pitch is NULL");
     pitch_rows_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_rows, d_frame_offsets, n_lags, bias, degree, flags, d_pitch);
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+int dsp_pitch_cepstrum_batch(const float* d_sig, const int64_t* d_sample_offsets, const int64_t* d_frame_offsets,
+                             int32_t n_utt, int64_t n_frames_total, int64_t uniform_samples, int32_t frame_len,
+                             int32_t frame_step, const float* d_taps, int32_t center_clip, float* d_rows, double* d_amp,
+                             void* stream) {
+    if (!d_taps || !d_rows) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_batch: NULL taps/output");
+    if (frame_len < 128 || frame_len > 1024 || (frame_len & (frame_len - 1)) != 0)
+        return fail(DSP_EINVAL, "dsp_pitch_cepstrum_batch: frame_len %d is not a power of two in [128, 1024]", frame_len);
+    if (frame_step <= 0) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_batch: frame_step must be > 0");
+    int rc = check_geom(d_sig, DSP_WAVE_F32, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples);
+    if (rc != DSP_OK) return rc;
+    if (n_frames_total > 0x7fffffff) return fail(DSP_EINVAL, "too many frames for one launch");
+    BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, frame_len, frame_step);
+    if (uniform_samples > 0 && bg.uniform_frames * n_utt != n_frames_total)
+        return fail(DSP_EINVAL, "n_frames_total %lld != n_utt*T (%d*%lld)", (long long)n_frames_total, n_utt, (long long)bg.uniform_frames);
+    const float2* tp = reinterpret_cast<const float2*>(d_taps);
+    const int grid = (int)n_frames_total, clip = center_clip ? 1 : 0;
+    hipStream_t st = (hipStream_t)stream;
+    switch (frame_len) {
+        case 128: pitch_cepstrum_kernel<128><<<grid, 64, 0, st>>>(d_sig, bg, frame_step, tp, clip, d_rows, d_amp); break;
+        case 256: pitch_cepstrum_kernel<256><<<grid, 64, 0, st>>>(d_sig, bg, frame_step, tp, clip, d_rows, d_amp); break;
+        case 512: pitch_cepstrum_kernel<512><<<grid, 64, 0, st>>>(d_sig, bg, frame_step, tp, clip, d_rows, d_amp); break;
+        default: pitch_cepstrum_kernel<1024><<<grid, 64, 0, st>>>(d_sig, bg, frame_step, tp, clip, d_rows, d_amp); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+template <typename RT>
+void launch_cepstrum_track(const void* d_rows, const int64_t* d_frame_offsets, int32_t n_utt, int32_t frame_len,
+                                  int32_t flags, double* d_pitch, int32_t* d_scores, hipStream_t st) {
+    const RT* r = reinterpret_cast<const RT*>(d_rows);
+    switch (frame_len) {
+        case 128: pitch_cepstrum_track_kernel<RT, 128><<<n_utt, 64, 0, st>>>(r, d_frame_offsets, flags, d_pitch, d_scores); break;
+        case 256: pitch_cepstrum_track_kernel<RT, 256><<<n_utt, 64, 0, st>>>(r, d_frame_offsets, flags, d_pitch, d_scores); break;
+        case 512: pitch_cepstrum_track_kernel<RT, 512><<<n_utt, 64, 0, st>>>(r, d_frame_offsets, flags, d_pitch, d_scores); break;
+        default: pitch_cepstrum_track_kernel<RT, 1024><<<n_utt, 64, 0, st>>>(r, d_frame_offsets, flags, d_pitch, d_scores); break;
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int dsp_pitch_cepstrum_track_batch(const void* d_rows, int32_t rows_f64, const int64_t* d_frame_offsets, int32_t n_utt,
+                                   int32_t frame_len, int32_t flags, double* d_pitch, int32_t* d_scores, void* stream) {
+    if (!d_rows || !d_frame_offsets || n_utt <= 0) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: bad arguments");
+    if (frame_len < 128 || frame_len > 1024 || (frame_len & (frame_len - 1)) != 0)
+        return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: frame_len %d is not a power of two in [128, 1024]", frame_len);
+    if ((flags & ~3) != 0) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: unknown flags %d", flags);
+    if ((flags & 2) && !d_pitch) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: d_pitch is NULL");
+    if (!(flags & 2) && !d_scores) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: nothing to write (no arg-max, d_scores is NULL)");
+    if (rows_f64)
+        launch_cepstrum_track<double>(d_rows, d_frame_offsets, n_utt, frame_len, flags, d_pitch, d_scores, (hipStream_t)stream);
+    else
+        launch_cepstrum_track<float>(d_rows, d_frame_offsets, n_utt, frame_len, flags, d_pitch, d_scores, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+int dsp_pitch_feature_batch(const double* d_pitch, const double* d_amp, const int64_t* d_frame_offsets, int32_t n_utt,
+                            double* d_seg, double* d_feat, int32_t* d_aux, void* stream) {
+    if (!d_amp || !d_frame_offsets || !d_aux || n_utt <= 0) return fail(DSP_EINVAL, "dsp_pitch_feature_batch: bad arguments");
+    if (d_pitch && (!d_seg || !d_feat)) return fail(DSP_EINVAL, "dsp_pitch_feature_batch: d_pitch needs d_seg and d_feat");
+    pitch_feature_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_pitch, d_amp, d_frame_offsets, d_seg, d_feat, d_aux);
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+int dsp_pitch_smooth_subseq_batch(const double* d_values, const int64_t* d_offsets, int32_t n_utt, int32_t tor,
+                                  double thres, double* d_seg, int32_t* d_info, void* stream) {
+    if (!d_values || !d_offsets || !d_seg || !d_info || n_utt <= 0)
+        return fail(DSP_EINVAL, "dsp_pitch_smooth_subseq_batch: bad arguments");
+    if (tor < 1) return fail(DSP_EINVAL, "dsp_pitch_smooth_subseq_batch: tor must be >= 1 (got %d)", tor);
+    pitch_subseq_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_values, d_offsets, tor, thres, d_seg, d_info);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }

@@ -1,0 +1,487 @@
+// Cepstral pitch path of the reference: pitch.pitch_detect (pitch.py:83-94) and pitch.pitch_feature (pitch.py:26-81,
+// 227-279), batched.  Three launches behind the decimation to 10 kHz:
+//   pitch_cepstrum_kernel        per frame: centre clip, complex band-pass FIR, FFT, log|.|, inverse FFT, |.|
+//   pitch_cepstrum_track_kernel  per utterance: smoothing in place, peak-width scores, arg-max, octave repair
+//   pitch_feature_kernel         per utterance: sub-endpoint, the two smooth subsequences, slopes, quadratic terms, shift
+// The first half of the frame kernel (median by bisection, register-blocked FIR) is the arithmetic of
+// pitch_scores_kernel_v2 (kernels_pitch.h), restated here for a compile-time frame length; that kernel is untouched.
+#pragma once
+
+#include "dsp_common.h"
+
+#define PITCH_CEP_MIN_I 20        // pitch.py:232: candidates 20 .. 99 on the 10 kHz quefrency grid
+#define PITCH_CEP_NSCORE 80
+#define PITCH_CEP_LDS_FRAMES 2048 // pitch values of an utterance kept in LDS (global memory beyond)
+
+__device__ __forceinline__ float2 cep_cmul(float2 a, float2 w) {
+    return make_float2(fmaf(a.x, w.x, -a.y * w.y), fmaf(a.x, w.y, a.y * w.x));
+}
+
+// One wavefront per rectangular frame of L samples (L = 128 .. 1024, a power of two), zero padded as to_frames does.
+//   1. centre clip at the median of the non-negative samples, non-binary form      pitch.py:145-155
+//   2. y = convolve(clipped, taps)[:L], kept complex                                sigproc.py:22-46 as pitch.py:137 calls it
+//   3. row = |IFFT_L(log|FFT_L(y)|)|                                                pitch.py:138-143
+//   4. amp = sum |x| of the unclipped frame (fp64)                                  pitch.py:65
+// Lane q owns W = L / 128 consecutive FIR outputs at the bottom of the frame and W at the top, so every lane does the
+// same L + W tap products per output pair.  The transforms run in place in LDS on the buffer the clipped frame used:
+// a decimation-in-frequency forward pass leaves the spectrum bit-reversed, log|.| is pointwise, and a
+// decimation-in-time inverse pass takes bit-reversed input back to natural order, so nothing is ever permuted.
+// A twiddle of exactly one is never multiplied: a silent frame (log 0 = -inf in every bin) then gives
+// [inf, nan, nan, ...] as NumPy does.  Only rows and amp reach global memory.
+template <int L>
+__global__ __launch_bounds__(64) void pitch_cepstrum_kernel(
+    const float* __restrict__ sig, BatchGeom bg, int32_t S, const float2* __restrict__ taps, int32_t do_clip,
+    float* __restrict__ rows, double* __restrict__ amp) {
+    static_assert(L >= 128 && L <= 1024 && (L & (L - 1)) == 0, "frame length: a power of two in [128, 1024]");
+    constexpr int W = L / 128, NR = L / 64;
+    __shared__ __attribute__((aligned(16))) float s_cl0[2 * L];   // [L zeros][L samples]; later the L complex points
+    __shared__ __attribute__((aligned(16))) float2 s_h[L];        // taps; later the L / 2 twiddles
+    const int lane = threadIdx.x;
+    const int64_t g = blockIdx.x;
+    int32_t utt;
+    int64_t t, s0, nsamp;
+    if (bg.uniform_frames <= 0 && g >= bg.frame_off[bg.n_utt]) return;   // the grid may be sized by an upper bound of the frame count
+    dsp_locate(bg, g, utt, t, s0, nsamp);
+    const int64_t first = t * (int64_t)S;
+    float* cl = s_cl0 + L;
+    // lane owns samples lane + 64 r; order statistics are found on the bit patterns (non-negative floats order like
+    // unsigned integers), everything else is 0xffffffff
+    float xr[NR];
+    uint32_t kb[NR];
+    double asum = 0.0;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const int i = lane + 64 * r;
+        float x = 0.f;
+        if (first + i < nsamp) x = sig[s0 + first + i];
+        xr[r] = x;
+        asum += (double)fabsf(x);
+        kb[r] = x >= 0.f ? __float_as_uint(x + 0.f) : 0xffffffffu;       // x + 0 turns -0 into +0
+        s_cl0[i] = 0.f;                                                  // guard band: samples before the frame
+        s_h[i] = taps[i];
+    }
+    if (amp) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) asum += __shfl_xor(asum, o, 64);
+        if (lane == 0) amp[g] = asum;
+    }
+    float med = 0.f;
+    if (do_clip) {
+        auto count_below = [&](uint32_t cand) {
+            int c = 0;
+#pragma unroll
+            for (int r = 0; r < NR; ++r) c += __popcll(__ballot(kb[r] < cand));
+            return c;
+        };
+        int m = 0;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) m += __popcll(__ballot(kb[r] != 0xffffffffu));
+        if (m > 0) {
+            // k-th smallest (0-based): the largest v with fewer than k + 1 keys below it, bit by bit
+            const int k1 = (m - 1) >> 1, k2 = m >> 1;
+            uint32_t v1 = 0;
+            for (int bit = 30; bit >= 0; --bit) {
+                const uint32_t cand = v1 | (1u << bit);
+                if (count_below(cand) <= k1) v1 = cand;
+            }
+            uint32_t v2 = v1;
+            if (k2 != k1 && count_below(v1 + 1) < k2 + 1) {
+                uint32_t mn = 0xffffffffu;                               // the next distinct key above v1
+#pragma unroll
+                for (int r = 0; r < NR; ++r) mn = (kb[r] > v1 && kb[r] < mn) ? kb[r] : mn;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const uint32_t other = (uint32_t)__shfl_xor((int)mn, o, 64);
+                    mn = other < mn ? other : mn;
+                }
+                v2 = mn;
+            }
+            med = 0.5f * (__uint_as_float(v1) + __uint_as_float(v2));    // numpy.median
+        } else {
+            med = __int_as_float(0x7fc00000);                            // no non-negative sample: NaN level, all zeros
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const float x = xr[r];
+        cl[lane + 64 * r] = do_clip ? (x > med ? x - med : (x < -med ? x + med : 0.f)) : x;
+    }
+    __syncthreads();
+    // ---- FIR: y[k] = sum_m h[m] c[k - m]; lane q owns outputs [W q, W q + W) and [L - W q - W, L - W q) ----
+    const int kl = W * lane, kh = L - W * (lane + 1);
+    float alr[W], ali[W], ahr[W], ahi[W];
+    {
+        float wl[W], wh[W];                                // ring: the sample at position p sits in slot p % W
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            wl[e] = cl[kl + e];
+            wh[e] = cl[kh + e];
+            alr[e] = ali[e] = ahr[e] = ahi[e] = 0.f;
+        }
+        for (int m0 = 0; m0 < L; m0 += W) {
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                const int m = m0 + j;
+                if (m > 0) {                               // position k0 - m enters slot (-m) % W == (W - j) % W
+                    wl[(W - j) % W] = cl[kl - m];
+                    wh[(W - j) % W] = cl[kh - m];
+                }
+                const float2 hm = s_h[m];
+#pragma unroll
+                for (int e = 0; e < W; ++e) {
+                    const float vl = wl[(e - j + W) % W], vh = wh[(e - j + W) % W];
+                    alr[e] = fmaf(hm.x, vl, alr[e]); ali[e] = fmaf(hm.y, vl, ali[e]);
+                    ahr[e] = fmaf(hm.x, vh, ahr[e]); ahi[e] = fmaf(hm.y, vh, ahi[e]);
+                }
+            }
+        }
+    }
+    __syncthreads();                                       // the clipped frame and the taps are dead from here
+    float2* buf = reinterpret_cast<float2*>(s_cl0);        // [L] complex points
+    float2* tw = s_h;                                      // [L / 2] exp(-2 pi i k / L)
+#pragma unroll
+    for (int e = 0; e < W; ++e) {
+        buf[kl + e] = make_float2(alr[e], ali[e]);
+        buf[kh + e] = make_float2(ahr[e], ahi[e]);
+    }
+    for (int k = lane; k < L / 2; k += 64) {
+        float sn, cs;
+        sincospif((float)(2 * k) / (float)L, &sn, &cs);
+        tw[k] = make_float2(cs, -sn);
+    }
+    __syncthreads();
+    // ---- forward transform, decimation in frequency: natural order in, bit-reversed out ----
+    for (int half = L / 2; half >= 1; half >>= 1) {
+        const int tstep = (L / 2) / half;
+        for (int b = lane; b < L / 2; b += 64) {
+            const int j = b & (half - 1), i0 = ((b - j) << 1) + j, i1 = i0 + half;
+            const float2 u = buf[i0], v = buf[i1];
+            float2 d = make_float2(u.x - v.x, u.y - v.y);
+            if (j) d = cep_cmul(d, tw[j * tstep]);
+            buf[i0] = make_float2(u.x + v.x, u.y + v.y);
+            buf[i1] = d;
+        }
+        __syncthreads();
+    }
+    for (int i = lane; i < L; i += 64) {                   // log|X|; a zero bin is -inf, as NumPy
+        const float2 v = buf[i];
+        buf[i] = make_float2(logf(sqrtf(fmaf(v.x, v.x, v.y * v.y))), 0.f);
+    }
+    __syncthreads();
+    // ---- inverse transform, decimation in time with conjugate twiddles: bit-reversed in, natural order out ----
+    for (int half = 1; half <= L / 2; half <<= 1) {
+        const int tstep = (L / 2) / half;
+        for (int b = lane; b < L / 2; b += 64) {
+            const int j = b & (half - 1), i0 = ((b - j) << 1) + j, i1 = i0 + half;
+            const float2 u = buf[i0];
+            float2 v = buf[i1];
+            if (j) {
+                const float2 w = tw[j * tstep];
+                v = cep_cmul(v, make_float2(w.x, -w.y));
+            }
+            buf[i0] = make_float2(u.x + v.x, u.y + v.y);
+            buf[i1] = make_float2(u.x - v.x, u.y - v.y);
+        }
+        __syncthreads();
+    }
+    float* out = rows + g * (int64_t)L;
+    for (int i = lane; i < L; i += 64) {
+        const float2 v = buf[i];
+        out[i] = sqrtf(fmaf(v.x, v.x, v.y * v.y)) * (1.0f / (float)L);
+    }
+}
+
+// The tracker behind the cepstrum rows, one wavefront per utterance, fp64, sequential over the frames:
+//   flags bit 0  pitch.smooth(rows, 2) with the habits kernels_pitch.h documents for pitch_track_kernel: rows below i are
+//                already smoothed (they are carried in registers; d_rows is not written), the window [i - 2, right) has
+//                right = i + 2 if i + 2 < T else T - 1, a one-frame utterance averages nothing (NaN), rows are added
+//                in order and divided once                                               pitch.py:157-164
+//   always       pitch.peak_score of the (smoothed) row: for i in [20, 100) p walks down from i while p > 0 and
+//                row[p] <= row[i], q walks up while q < L and row[q] <= row[i]; score = min(i - p, q - i).  row[0] is
+//                never compared; a NaN row scores 0 everywhere.  i - p <= 99 and a walk up longer than the walk down
+//                cannot change the minimum, so positions 1 .. 198 decide every score       pitch.py:227-242
+//   flags bit 1  first arg-max of the 80 integers -> 1 / (1e-4 (20 + idx)), then the two octave-repair sweeps
+//                                                                                        pitch.py:166-172,191-206
+template <typename RT, int L>
+__global__ __launch_bounds__(64) void pitch_cepstrum_track_kernel(const RT* __restrict__ rows,
+                                                                  const int64_t* __restrict__ frame_off, int32_t flags,
+                                                                  double* __restrict__ pitch, int32_t* __restrict__ scores) {
+    constexpr int NR = L / 64;
+    __shared__ double s_pitch[PITCH_CEP_LDS_FRAMES];
+    const int u = blockIdx.x, lane = threadIdx.x;
+    const int64_t base = frame_off[u];
+    const int T = (int)(frame_off[u + 1] - base);
+    if (T <= 0) return;
+    const RT* rw = rows + base * L;
+    double* out = (flags & 2) ? pitch + base : nullptr;
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    double p2[NR], p1[NR];                  // smoothed rows i - 2 and i - 1 (columns lane, lane + 64, ...)
+#pragma unroll
+    for (int k = 0; k < NR; ++k) p2[k] = p1[k] = 0.0;
+    // raw rows i and i + 1 live in registers and row i + 2 is fetched while frame i is scored: one batch of loads per
+    // frame, off the critical path (a load per window row and column inside the sum costs a memory round trip each)
+    double ra[NR], rb[NR];
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        ra[k] = (double)rw[lane + 64 * k];
+        rb[k] = T > 1 ? (double)rw[(int64_t)L + lane + 64 * k] : 0.0;
+    }
+    for (int i = 0; i < T; ++i) {
+        double cur[NR], rc[NR];
+#pragma unroll
+        for (int k = 0; k < NR; ++k) rc[k] = i + 2 < T ? (double)rw[(int64_t)(i + 2) * L + lane + 64 * k] : 0.0;
+        if (flags & 1) {
+            const int left = i - 2 >= 0 ? i - 2 : 0;
+            const int right = i + 2 < T ? i + 2 : T - 1;          // exclusive, <= i + 2
+            const int cnt = right - left;
+#pragma unroll
+            for (int k = 0; k < NR; ++k) {
+                double acc = qnan;
+                if (cnt > 0) {
+                    bool have = false;
+                    acc = 0.0;
+                    for (int r = left; r < right; ++r) {          // rows in order, as numpy's add.reduce over axis 0
+                        const double v = r == i - 2 ? p2[k] : (r == i - 1 ? p1[k] : (r == i ? ra[k] : rb[k]));
+                        acc = have ? acc + v : v;
+                        have = true;
+                    }
+                    acc = acc / (double)cnt;
+                }
+                cur[k] = acc;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NR; ++k) cur[k] = ra[k];
+        }
+        // peak widths.  Only positions 1 .. 198 can matter (i <= 99, and a walk up longer than the walk down cannot change
+        // the minimum), and lane l already holds positions l, l + 64, l + 128, l + 192 of the row in registers.  The
+        // candidate is uniform: its value is read from its lane, one compare per register gives a 64-bit mask of the
+        // positions that end a walk, and the nearest one either side is a count of leading / trailing zeros.  No LDS,
+        // no barrier.  Positions at and beyond L end the walk up.
+        constexpr int NW = NR < 4 ? NR : 4;
+        int bv = -1, bi = 0, mine[2] = {0, 0};
+#pragma unroll 4
+        for (int c = 0; c < PITCH_CEP_NSCORE; ++c) {
+            const int ii = PITCH_CEP_MIN_I + c, w = ii >> 6, bit = ii & 63;
+            const double src = w == 0 ? cur[0] : cur[1];
+            const double vi = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(src), bit),
+                                               __builtin_amdgcn_readlane(__double2loint(src), bit));
+            uint64_t m[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) m[k] = k < NW ? __ballot(!(cur[k < NW ? k : 0] <= vi)) : ~0ull;
+            const uint64_t below = (1ull << bit) - 1;                           // positions of word w below the candidate
+            const uint64_t l0 = (w == 0 ? m[0] & below : m[0]) & ~1ull;            // position 0 is never compared
+            const uint64_t l1 = w == 0 ? 0ull : m[1] & below;
+            const int p = l1 ? 127 - __builtin_clzll(l1) : (l0 ? 63 - __builtin_clzll(l0) : 0);
+            const int dl = !(vi <= vi) ? 0 : ii - p;
+            const uint64_t above = bit == 63 ? 0ull : ~0ull << (bit + 1);
+            const uint64_t r0 = (w == 0 ? m[0] : m[1]) & above, r1 = w == 0 ? m[1] : m[2], r2 = w == 0 ? m[2] : m[3];
+            const int q = r0 ? 64 * w + __builtin_ctzll(r0)
+                             : (r1 ? 64 * (w + 1) + __builtin_ctzll(r1) : (r2 ? 64 * (w + 2) + __builtin_ctzll(r2) : ii + 129));
+            const int sc = min(dl, q - ii);
+            if (lane == (c & 63)) mine[c >> 6] = sc;
+            if (sc > bv) { bv = sc; bi = c; }                      // c ascends: the first maximum stays
+        }
+        if (scores) {
+            scores[(base + i) * PITCH_CEP_NSCORE + lane] = mine[0];
+            if (lane + 64 < PITCH_CEP_NSCORE) scores[(base + i) * PITCH_CEP_NSCORE + 64 + lane] = mine[1];
+        }
+        if ((flags & 2) && lane == 0) {
+            const double p = 1.0 / (0.0001 * (double)(PITCH_CEP_MIN_I + bi));         // pitch.py:169-170
+            if (i < PITCH_CEP_LDS_FRAMES) s_pitch[i] = p; else out[i] = p;
+        }
+#pragma unroll
+        for (int k = 0; k < NR; ++k) { p2[k] = p1[k]; p1[k] = cur[k]; ra[k] = rb[k]; rb[k] = rc[k]; }
+    }
+    if (!(flags & 2)) return;
+    if (lane == 0) {
+        auto get = [&](int i) { return i < PITCH_CEP_LDS_FRAMES ? s_pitch[i] : out[i]; };
+        auto put = [&](int i, double v) { if (i < PITCH_CEP_LDS_FRAMES) s_pitch[i] = v; else out[i] = v; };
+        const double C = 50.0;
+        for (int i = 1; i < T; ++i) {                              // pitch.py:199-201
+            const double p = get(i);
+            if (fabs(2.0 * p - get(i - 1)) < C && p < 170.0) put(i, 2.0 * p);
+        }
+        for (int i = T - 2; i > 0; --i) {                          // pitch.py:202-204
+            const double p = get(i);
+            if (fabs(2.0 * p - get(i + 1)) < C && p < 170.0) put(i, 2.0 * p);
+        }
+    }
+    __syncthreads();
+    for (int i = lane; i < T && i < PITCH_CEP_LDS_FRAMES; i += 64) out[i] = s_pitch[i];
+}
+
+// ------------------------------------------------------------------------------------------------
+// pitch.find_smooth_subsequence (pitch.py:245-279): from every start i collect the values that stay within `thres` of
+// the last accepted one, until `tor` values were rejected (the segment is then (i, j), j the index of the last
+// rejection, and the next start is j - tor + 1) or the sequence ends (segment (i, n), the search stops).  Returned is
+// the longest collected segment, the first one on a tie.  A comparison against a NaN accepts, as in the reference.
+// ------------------------------------------------------------------------------------------------
+struct PitchSubseq {
+    int start, end, count;
+};
+
+template <typename Get>
+__device__ __forceinline__ PitchSubseq pitch_subseq_best(Get get, int n, int tor, double thres) {
+    PitchSubseq best = {0, 0, 0};
+    int i = 0;
+    while (i < n) {
+        int j = i + 1, k = tor, cnt = 1;
+        double prev = get(i);
+        while (j < n) {
+            const double v = get(j);
+            if (fabs(v - prev) > thres) --k; else { ++cnt; prev = v; }
+            if (!k) break;
+            ++j;
+        }
+        if (cnt > best.count) best = {i, j, cnt};
+        if (j == n) break;
+        i = j - tor + 1;
+    }
+    return best;
+}
+
+// the accepted values of the segment that starts at s.start, in order, handed to put(idx, value)
+template <typename Get, typename Put>
+__device__ __forceinline__ void pitch_subseq_collect(Get get, PitchSubseq s, double thres, Put put) {
+    if (s.count <= 0) return;
+    double prev = get(s.start);
+    int idx = 0;
+    put(idx++, prev);
+    for (int j = s.start + 1; j < s.end && idx < s.count; ++j) {
+        const double v = get(j);
+        if (!(fabs(v - prev) > thres)) { put(idx++, v); prev = v; }
+    }
+}
+
+// values [sum n_b] fp64 -> accepted values at seg[off[b] ..], info[b] = (start, end, count).  One wave per sequence; the
+// search is one dependency chain, so lane 0 walks it.
+__global__ __launch_bounds__(64) void pitch_subseq_kernel(const double* __restrict__ values, const int64_t* __restrict__ off,
+                                                          int32_t tor, double thres, double* __restrict__ seg,
+                                                          int32_t* __restrict__ info) {
+    if (threadIdx.x != 0) return;
+    const int u = blockIdx.x;
+    const int64_t base = off[u];
+    const int n = (int)(off[u + 1] - base);
+    const double* v = values + base;
+    auto get = [&](int i) { return v[i]; };
+    const PitchSubseq s = pitch_subseq_best(get, n, tor, thres);
+    pitch_subseq_collect(get, s, thres, [&](int idx, double x) { seg[base + idx] = x; });
+    info[3 * u + 0] = s.start;
+    info[3 * u + 1] = s.end;
+    info[3 * u + 2] = s.count;
+}
+
+// Median of m values (m >= 1, none NaN) by rank counting across the wave: the k-th order statistic is the value with
+// at most k values below it and more than k values not above it.  numpy.median: mean of the two middle ones.
+__device__ __forceinline__ double pitch_wave_median(const double* __restrict__ v, int m, double* s_two) {
+    const int lane = threadIdx.x, k1 = (m - 1) >> 1, k2 = m >> 1;
+    for (int e = lane; e < m; e += 64) {
+        const double x = v[e];
+        int lt = 0, eq = 0;
+        for (int r = 0; r < m; ++r) {
+            const double y = v[r];
+            lt += y < x ? 1 : 0;
+            eq += y == x ? 1 : 0;
+        }
+        if (lt <= k1 && k1 < lt + eq) s_two[0] = x;
+        if (lt <= k2 && k2 < lt + eq) s_two[1] = x;
+    }
+    __syncthreads();
+    const double r = (s_two[0] + s_two[1]) / 2.0;
+    __syncthreads();
+    return r;
+}
+
+// The tail of pitch.pitch_feature (pitch.py:26-81), one wavefront per utterance, fp64:
+//   p      = sub_endpoint_detect: among i in [10, T - 10) with no amp[i-2 .. i+2] below amp[i], the first i with the
+//            largest sum_{j = i-10 .. i+10} (amp[j] - amp[i]) (strictly greater, from -1000); none: T // 2   pitch.py:64-81
+//   p_bias = 5 if p > 15 else 0                                                                              pitch.py:36
+//   seg1, seg2 = find_smooth_subsequence(pitch[p_bias:p]), (pitch[p:]), tor 3, thres 30                      pitch.py:39-40
+//   feat   = slope(seg1), slope(seg2), quad(seg1), quad(seg2), median(seg2) - median(seg1)                   pitch.py:44-62
+// The least-squares leading coefficients over x = 0 .. m - 1 use the centred orthogonal basis: sum (x - xm) y /
+// sum (x - xm)^2 and sum q y / sum q^2 with q = (x - xm)^2 - (m^2 - 1) / 12.  The reference raises for an empty slice
+// and for m < 2, and is rank deficient for m = 2 at degree 2: any segment with m < 3 gives valid = 0 and a NaN row.
+// aux[b] = (p, p_bias, start1, end1, start2, end2, m1, m2, valid), indices counted from the utterance's first frame.
+// seg receives the accepted values: seg1 at seg[base + p_bias ..], seg2 at seg[base + p ..].  pitch == NULL: only p.
+__global__ __launch_bounds__(64) void pitch_feature_kernel(const double* __restrict__ pitch, const double* __restrict__ amp,
+                                                           const int64_t* __restrict__ frame_off, double* __restrict__ seg,
+                                                           double* __restrict__ feat, int32_t* __restrict__ aux) {
+    __shared__ double s_pitch[PITCH_CEP_LDS_FRAMES];
+    __shared__ double s_fit[4], s_two[2];
+    __shared__ int s_seg[6];
+    const int u = blockIdx.x, lane = threadIdx.x;
+    const int64_t base = frame_off[u];
+    const int T = (int)(frame_off[u + 1] - base);
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    const double* a = amp + base;
+    double bs = -1000.0;
+    int bi = 0x7fffffff;
+    for (int i = 10 + lane; i < T - 10; i += 64) {
+        const double ai = a[i];
+        bool low = true;
+#pragma unroll
+        for (int d = -2; d <= 2; ++d) low = low && !(a[i + d] < ai);
+        if (!low) continue;
+        double s = 0.0;
+        for (int j = i - 10; j <= i + 10; ++j) s += a[j] - ai;     // in order, as Python's sum
+        if (s > bs) { bs = s; bi = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double os = __shfl_xor(bs, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (os > bs || (os == bs && oi < bi)) { bs = os; bi = oi; }
+    }
+    const int p = bi == 0x7fffffff ? (T > 0 ? T / 2 : 0) : bi;
+    int32_t* ax = aux + 9 * (int64_t)u;
+    if (!pitch) {
+        if (lane == 0) ax[0] = p;
+        return;
+    }
+    const int p_bias = p > 15 ? 5 : 0;
+    const double* pg = pitch + base;
+    for (int i = lane; i < T && i < PITCH_CEP_LDS_FRAMES; i += 64) s_pitch[i] = pg[i];
+    __syncthreads();
+    if (lane == 0) {
+        for (int h = 0; h < 2; ++h) {
+            const int lo = h == 0 ? p_bias : p, n = h == 0 ? p - p_bias : T - p;
+            auto get = [&](int i) { return lo + i < PITCH_CEP_LDS_FRAMES ? s_pitch[lo + i] : pg[lo + i]; };
+            const PitchSubseq s = pitch_subseq_best(get, n > 0 ? n : 0, 3, 30.0);
+            const int m = s.count;
+            const double xm = 0.5 * (double)(m - 1), c2 = ((double)m * (double)m - 1.0) / 12.0;
+            double n1 = 0.0, d1 = 0.0, n2 = 0.0, d2 = 0.0;
+            pitch_subseq_collect(get, s, 30.0, [&](int idx, double y) {
+                seg[base + lo + idx] = y;
+                const double x = (double)idx - xm, q = x * x - c2;
+                n1 += x * y; d1 += x * x;
+                n2 += q * y; d2 += q * q;
+            });
+            s_fit[h] = m >= 3 ? n1 / d1 : qnan;
+            s_fit[2 + h] = m >= 3 ? n2 / d2 : qnan;
+            s_seg[3 * h + 0] = lo + s.start;
+            s_seg[3 * h + 1] = lo + s.end;
+            s_seg[3 * h + 2] = m;
+        }
+    }
+    __syncthreads();                                               // seg[] written by lane 0 is read by the whole wave below
+    const int m1 = s_seg[2], m2 = s_seg[5];
+    const bool valid = m1 >= 3 && m2 >= 3;
+    double shift = qnan;
+    if (valid) {
+        const double med1 = pitch_wave_median(seg + base + p_bias, m1, s_two);
+        const double med2 = pitch_wave_median(seg + base + p, m2, s_two);
+        shift = med2 - med1;
+    }
+    if (lane == 0) {
+        double* f = feat + 5 * (int64_t)u;
+        f[0] = valid ? s_fit[0] : qnan;
+        f[1] = valid ? s_fit[1] : qnan;
+        f[2] = valid ? s_fit[2] : qnan;
+        f[3] = valid ? s_fit[3] : qnan;
+        f[4] = shift;
+        ax[0] = p; ax[1] = p_bias;
+        ax[2] = s_seg[0]; ax[3] = s_seg[1]; ax[4] = s_seg[3]; ax[5] = s_seg[4];
+        ax[6] = m1; ax[7] = m2; ax[8] = valid ? 1 : 0;
+    }
+}

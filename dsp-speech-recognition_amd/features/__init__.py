@@ -7,7 +7,8 @@ and return types as features/{sigproc,base,endpoint,preprocess}.py; the arithmet
 hand-written HIP kernels (gfx950) behind a ctypes C ABI (include/dsp_frontend.h).
 
 Unlike the reference's ``features/__init__.py`` this import has no side effects (no ./log/
-directory, no matplotlib / sklearn import); of the pitch module only the score path is here.
+directory, no matplotlib / sklearn import).  Both pitch trackers (``pitch_detect_sr``, ``pitch_detect``) and
+``pitch_feature`` are here; the SVM half of the reference's pitch module is not.
 There is no CPU fallback: without the built library or without a GPU every compute call raises.
 """
 from .base import *  # noqa: F401,F403
@@ -15,7 +16,9 @@ from .sigproc import *  # noqa: F401,F403
 from .endpoint import *  # noqa: F401,F403
 from .preprocess import *  # noqa: F401,F403
 from .pitch import (center_clip, max_pitch, pitch_detect_frame_sr, pitch_detect_sr,  # noqa: F401
-                    robust_max_pitch, smooth, window)
+                    robust_max_pitch, smooth, window, pitch_detect, pitch_detect_frame, peak_score,
+                    sub_endpoint_detect, find_smooth_subsequence, slope, quad_params, peakshift, pitch_feature,
+                    pitch_feature_batch, pitch_features_device)
 from . import base, sigproc, endpoint, preprocess, pitch, batch, pipeline  # noqa: F401
 from .batch import FeaturePlan, EndpointPlan  # noqa: F401
 from .pipeline import VadMfccPipeline  # noqa: F401

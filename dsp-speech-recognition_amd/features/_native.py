@@ -82,6 +82,10 @@ SIGNATURES = {
                                          c_i32, c_i32, c_vp, c_vp]),
     'dsp_pitch_track_batch': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'dsp_pitch_rows_batch': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    'dsp_pitch_cepstrum_batch': (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    'dsp_pitch_cepstrum_track_batch': (C.c_int, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'dsp_pitch_feature_batch': (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'dsp_pitch_smooth_subseq_batch': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_f64, c_vp, c_vp, c_vp]),
     'dsp_resample_layout_batch': (C.c_int, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'dsp_decimate_batch': (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp]),
     'dsp_model_pitchfeat_batch': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),

@@ -1,20 +1,35 @@
-"""Drop-in for the pitch-score path of the reference's ``features/pitch.py``:
-``pitch_detect_sr`` as ``model.py:92`` calls it when ``cfg.use_pitch`` is set.
+"""Drop-in for the reference's ``features/pitch.py``: both pitch trackers and the five pitch features.
 
-Per frame of the 10 kHz signal the reference clips at the median (pitch.py:145-155), band-passes with
-a complex FIR built from an ideal band (sigproc.py:22-46), takes the magnitude and evaluates 180
-autocorrelation lags (pitch.py:112-132) -- ~80 k multiply-adds per frame in Python loops.  Here that
-is one kernel launch for all frames (``dsp_pitch_scores_batch``); the sequential O(T * 180) tail
-(in-place smoothing, arg-max, octave repair) stays host logic, as in the reference.  The SVM /
-plotting side of the reference's module (``pitch_feature``, ``pitch_model.py``) is out of scope.
+* ``pitch_detect_sr``, the autocorrelation tracker ``model.py:92`` calls when ``cfg.use_pitch``
+  is set.  Per frame of the 10 kHz signal the reference clips at the median (pitch.py:145-155), band-passes with a
+  complex FIR built from an ideal band (sigproc.py:22-46), takes the magnitude and evaluates 180 autocorrelation lags
+  (pitch.py:112-132).  Here that is one launch for all frames (``dsp_pitch_scores_batch``) and one for the sequential
+  tail (``dsp_pitch_track_batch``).
+* ``pitch_detect`` (pitch.py:83-94), the cepstral tracker, and ``pitch_feature`` (pitch.py:26-81, 227-279) built on it,
+  which ``pitch_model.py`` calls once per clip.  Three launches: ``dsp_pitch_cepstrum_batch`` (clip, complex FIR at
+  50 - 1000 Hz, FFT, log|.|, inverse FFT per frame), ``dsp_pitch_cepstrum_track_batch`` (in-place smoothing,
+  peak-width scores, arg-max, octave repair per utterance) and ``dsp_pitch_feature_batch`` (sub-endpoint, the two
+  smooth subsequences, slopes, quadratic terms, median shift).  ``pitch_feature_batch`` / ``pitch_features_device``
+  are the batched forms.
+
+``from features.pitch import *`` also yields what the reference's module re-exports through its own imports and
+``pitch_model.py`` relies on (``basic_endpoint_detection``, ``preemphasis``, ``to_frames``, ``pickle``, ...).
+
+Out of scope: ``greedy_max_pitch`` and ``dp_max_pitch`` (no caller anywhere), the SVM / ``__main__`` half of the
+reference's module (no sklearn, no matplotlib here), and frame lengths that are not a power of two in [128, 1024] on the
+cepstral path (``winlen = 0.0512`` gives 512, the only size a reference caller uses): those raise ``ValueError``.
 """
 from __future__ import annotations
+
+import pickle  # noqa: F401  (re-exported: pitch.py:23, pitch_model.py:46-47)
+import types
 
 import numpy as np
 
 from . import _native as nat
-from .preprocess import downsampling
-from .sigproc import to_frames
+from .endpoint import basic_endpoint_detection, get_amplitude, robust_endpoint_detection  # noqa: F401  (pitch.py:17)
+from .preprocess import downsampling, preemphasis  # noqa: F401  (pitch.py:13,24)
+from .sigproc import acr, to_frames  # noqa: F401  (pitch.py:14)
 
 MIN_SHIFT, MAX_SHIFT = 20, 200        # pitch.py:126-127: 50 .. 500 Hz on the 10 kHz lag grid
 _taps_cache = {}
@@ -46,11 +61,11 @@ def center_clip(frame, binary=True):
     return np.where(up, frame - med, np.where(dn, frame + med, 0.0))
 
 
-def _device_taps(L, rate):
-    key = (nat.current_device(), int(L), int(rate))
+def _device_taps(L, rate, high_freq=900):
+    key = (nat.current_device(), int(L), int(rate), int(high_freq))
     buf = _taps_cache.get(key)
     if buf is None:
-        h = bandpass_taps(L, rate, 50, 900, 'hamming')
+        h = bandpass_taps(L, rate, 50, high_freq, 'hamming')
         arr = np.stack([h.real, h.imag], axis=1).astype(np.float32)
         buf = nat.DeviceBuffer(arr.nbytes).upload(arr)
         _taps_cache[key] = buf
@@ -170,3 +185,230 @@ def pitch_detect_sr(sig, rate, winlen=0.0512, step=0.01):
     pitch, _ = pitch_tracks_batch(s, [0, len(s)], L, S)
     frames = to_frames(s, 10000, winlen, step)
     return list(pitch), frames
+
+
+# ---- the cepstral tracker (pitch.py:83-94, 135-143, 227-242) and the pitch features (pitch.py:26-81, 245-279) ----
+
+CEP_MIN, CEP_MAX = 20, 100            # pitch.py:232: peak-score candidates on the 10 kHz quefrency grid
+N_AUX = 9                             # p, p_bias, start1, end1, start2, end2, len1, len2, valid
+
+
+def _check(rc):
+    """nat.check, but a rejected argument (a frame length the kernels do not serve) is the caller's ValueError."""
+    if rc == nat.EINVAL:
+        msg = nat.load().dsp_last_error()
+        raise ValueError(msg.decode() if msg else 'invalid argument')
+    nat.check(rc)
+
+
+def _cepstrum_chain(p_x, p_so, p_fo, n_utt, frames_bound, L, S, stream=None, clip=True, want_scores=False, flags=3,
+                    tail=True):
+    """The three launches behind the 10 kHz signal, on library scratch buffers (nothing is allocated once they exist,
+    so the chain can be captured in a graph after one eager call)."""
+    lib = nat.load()
+    frames_bound = max(int(frames_bound), 1)
+    out = types.SimpleNamespace(scores=None, feat=None, aux=None, seg=None)
+    out.rows = nat.SCRATCH.get('cep_rows', frames_bound * int(L) * 4)
+    out.amp = nat.SCRATCH.get('cep_amp', frames_bound * 8)
+    out.pitch = nat.SCRATCH.get('cep_pitch', frames_bound * 8)
+    if want_scores:
+        out.scores = nat.SCRATCH.get('cep_scores', frames_bound * (CEP_MAX - CEP_MIN) * 4)
+    _check(lib.dsp_pitch_cepstrum_batch(p_x, p_so, p_fo, n_utt, frames_bound, 0, int(L), int(S),
+                                        _device_taps(L, 10000, 1000).ptr, 1 if clip else 0, out.rows.ptr, out.amp.ptr, stream))
+    _check(lib.dsp_pitch_cepstrum_track_batch(out.rows.ptr, 0, p_fo, n_utt, int(L), int(flags), out.pitch.ptr,
+                                              out.scores.ptr if want_scores else None, stream))
+    if tail:
+        out.seg = nat.SCRATCH.get('cep_seg', frames_bound * 8)
+        out.feat = nat.SCRATCH.get('cep_feat', n_utt * 5 * 8)
+        out.aux = nat.SCRATCH.get('cep_aux', n_utt * N_AUX * 4)
+        _check(lib.dsp_pitch_feature_batch(out.pitch.ptr, out.amp.ptr, p_fo, n_utt, out.seg.ptr, out.feat.ptr, out.aux.ptr, stream))
+    return out
+
+
+def _upload_10k(sig10k, sample_offsets, L, S):
+    so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
+    fo = nat.frame_offsets(so, L, S)
+    x = np.ascontiguousarray(sig10k, dtype=np.float32).reshape(-1)
+    d_x = nat.device_array('pitch_sig', x if x.size else np.zeros(1, dtype=np.float32))
+    return d_x, nat.device_array('pitch_so', so), nat.device_array('pitch_fo', fo), so, fo
+
+
+def cepstrum_rows_batch(sig10k, sample_offsets, L, S, clip=True):
+    """|cepstrum| rows [sum T_b, L] (fp64 copies of the kernel's fp32) and the per-frame sums of |x| for concatenated
+    10 kHz signals; returns (rows, amp, frame_offsets)."""
+    nat.require_device()
+    d_x, d_so, d_fo, so, fo = _upload_10k(sig10k, sample_offsets, L, S)
+    n = int(fo[-1])
+    r = _cepstrum_chain(d_x.ptr, d_so.ptr, d_fo.ptr, len(so) - 1, n, L, S, clip=clip, want_scores=True, flags=0, tail=False)
+    return r.rows.download((n, int(L)), np.float32).astype(np.float64), r.amp.download((n,), np.float64), fo
+
+
+def pitch_detect_frame(frame, rate, gender='male'):
+    """pitch.py:135-143 for one (already clipped) frame -> |cepstrum|, float64 [len(frame)]: a batch of one, clipping off."""
+    frame = np.asarray(frame, dtype=np.float64).reshape(-1)
+    L = len(frame)
+    nat.require_device()
+    d_x, d_so, d_fo, so, fo = _upload_10k(frame, [0, L], max(L, 1), max(L, 1))
+    d_rows = nat.SCRATCH.get('cep_rows', max(L, 1) * 4)
+    d_taps = nat.DeviceBuffer(max(L, 1) * 8)
+    h = bandpass_taps(L, rate, 50, 1000, 'hamming') if L else np.zeros(0, dtype=complex)
+    d_taps.upload(np.stack([h.real, h.imag], axis=1).astype(np.float32))
+    try:
+        _check(nat.load().dsp_pitch_cepstrum_batch(d_x.ptr, d_so.ptr, d_fo.ptr, 1, 1, 0, L, L, d_taps.ptr, 0, d_rows.ptr, None, None))
+        return d_rows.download((L,), np.float32).astype(np.float64)
+    finally:
+        d_taps.free()
+
+
+def _scores_on_device(rows, flags):
+    """fp64 rows [T, n] through dsp_pitch_cepstrum_track_batch as a batch of one -> (scores [T, 80] int32, pitch or None).
+    A row that is not a served length is padded with +inf: the walk up stops there exactly as it stops at the row's end."""
+    nat.require_device()
+    rows = np.asarray(rows, dtype=np.float64)
+    T, n = rows.shape
+    if n < CEP_MAX:
+        raise IndexError(f'a row of {n} values has no candidate {CEP_MAX - 1}')          # as the reference's sig[i]
+    L = 128
+    while L < n:
+        L <<= 1
+    if L > 1024:
+        raise ValueError(f'rows of {n} values are not served on the device (<= 1024)')
+    if L != n:
+        rows = np.concatenate([rows, np.full((T, L - n), np.inf)], axis=1)
+    d_rows = nat.device_array('cep_rows64', np.ascontiguousarray(rows))
+    d_fo = nat.device_array('pitch_rows_fo', np.array([0, T], dtype=np.int64))
+    d_scores = nat.SCRATCH.get('cep_scores', T * (CEP_MAX - CEP_MIN) * 4)
+    d_pitch = nat.SCRATCH.get('cep_pitch', T * 8)
+    _check(nat.load().dsp_pitch_cepstrum_track_batch(d_rows.ptr, 1, d_fo.ptr, 1, L, int(flags), d_pitch.ptr, d_scores.ptr, None))
+    return (d_scores.download((T, CEP_MAX - CEP_MIN), np.int32),
+            d_pitch.download((T,), np.float64) if flags & 2 else None)
+
+
+def peak_score(sig, gender='male'):
+    """pitch.py:227-242: for i in [20, 100) the distance to the nearest larger value on either side -> list of 80 ints."""
+    scores, _ = _scores_on_device(np.asarray(sig, dtype=np.float64).reshape(1, -1), 0)
+    return [int(v) for v in scores[0]]
+
+
+def _so_of(clips):
+    return np.concatenate([[0], np.cumsum([len(c) for c in clips])]).astype(np.int64)
+
+
+def pitch_cepstrum_tracks_batch(sig10k, sample_offsets, L, S):
+    """pitch.pitch_detect's chain behind the decimation for concatenated 10 kHz signals.  Returns (pitch [sum T_b] in Hz,
+    scores [sum T_b, 80] int32, frame_offsets)."""
+    nat.require_device()
+    d_x, d_so, d_fo, so, fo = _upload_10k(sig10k, sample_offsets, L, S)
+    n = int(fo[-1])
+    r = _cepstrum_chain(d_x.ptr, d_so.ptr, d_fo.ptr, len(so) - 1, n, L, S, want_scores=True, tail=False)
+    return r.pitch.download((n,), np.float64), r.scores.download((n, CEP_MAX - CEP_MIN), np.int32), fo
+
+
+def pitch_detect(sig, rate, winlen=0.0512, step=0.01, gender='male'):
+    """pitch.py:83-94 -> (pitch per frame in Hz, frames of the 10 kHz signal)."""
+    s = downsampling(np.asarray(sig).reshape(-1), rate, 10000)
+    L, S = int(10000 * winlen), int(step * 10000)          # to_frames truncates (sigproc.py:19)
+    pitch, _, _ = pitch_cepstrum_tracks_batch(s, [0, len(s)], L, S)
+    return list(pitch), to_frames(s, 10000, winlen, step)
+
+
+def sub_endpoint_detect(frames):
+    """pitch.py:64-81: the frame where the amplitude dips most between two syllables (len // 2 when there is none);
+    the search is dsp_pitch_feature_batch without a pitch track, as a batch of one."""
+    amp = np.array([np.abs(f).sum() for f in frames], dtype=np.float64)
+    T = len(amp)
+    if T == 0:
+        return 0
+    nat.require_device()
+    d_amp = nat.device_array('cep_amp', amp)
+    d_fo = nat.device_array('pitch_rows_fo', np.array([0, T], dtype=np.int64))
+    d_aux = nat.SCRATCH.get('cep_aux', N_AUX * 4)
+    _check(nat.load().dsp_pitch_feature_batch(None, d_amp.ptr, d_fo.ptr, 1, None, None, d_aux.ptr, None))
+    return int(d_aux.download((1,), np.int32)[0])
+
+
+def find_smooth_subsequence(pitch, base_tor=3, base_thres=30, bias=0):
+    """pitch.py:245-279 -> (accepted values of the longest smooth run, (start + bias, end + bias)), on the device."""
+    v = np.ascontiguousarray(np.asarray(pitch, dtype=np.float64).reshape(-1))
+    if len(v) == 0:
+        raise ValueError('not enough values to unpack (expected 2, got 0)')           # what the reference's zip(*[]) raises
+    nat.require_device()
+    d_v = nat.device_array('cep_pitch', v)
+    d_off = nat.device_array('pitch_rows_fo', np.array([0, len(v)], dtype=np.int64))
+    d_seg = nat.SCRATCH.get('cep_seg', len(v) * 8)
+    d_info = nat.SCRATCH.get('cep_aux', N_AUX * 4)
+    _check(nat.load().dsp_pitch_smooth_subseq_batch(d_v.ptr, d_off.ptr, 1, int(base_tor), float(base_thres), d_seg.ptr, d_info.ptr, None))
+    start, end, count = (int(x) for x in d_info.download((3,), np.int32))
+    return list(d_seg.download((count,), np.float64)), (start + bias, end + bias)
+
+
+def slope(seq):
+    """pitch.py:49-52"""
+    return np.polyfit(np.arange(0, len(seq)), seq, 1)[0]
+
+
+def quad_params(seq):
+    """pitch.py:54-57"""
+    return np.polyfit(np.arange(0, len(seq)), seq, 2)[0]
+
+
+def peakshift(seq1, seq2):
+    """pitch.py:59-62"""
+    return np.median(seq2) - np.median(seq1)
+
+
+def pitch_features_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, stream=None, L=512, S=100):
+    """pitch.pitch_feature for clips that are already on the device (fp32, concatenated, `rate` Hz): decimation to 10 kHz
+    (dsp_resample_layout_batch + dsp_decimate_batch), then the three launches of the cepstral path; nothing leaves the
+    device.  Returns library scratch buffers as attributes: feat [B, 5] fp64, aux [B, 9] int32 (p, p_bias, start1,
+    end1, start2, end2, len1, len2, valid), pitch and seg [one per frame] fp64, frame_off [B + 1] int64."""
+    lib = nat.load()
+    stream = None if stream is None else int(getattr(stream, 'cuda_stream', stream))
+    d_fo = nat.SCRATCH.get('pitch_fo10', (n_utt + 1) * 8)
+    if rate > 10000:
+        d_so10 = nat.SCRATCH.get('pitch_so10', (n_utt + 1) * 8)
+        d_x10 = nat.SCRATCH.get('pitch_x10', max(4, int(n_samples_bound) * 4))
+        nat.check(lib.dsp_resample_layout_batch(d_src_off, n_utt, int(rate), 10000, int(L), int(S), d_so10.ptr, d_fo.ptr, stream))
+        nat.check(lib.dsp_decimate_batch(d_clips, d_src_off, d_so10.ptr, n_utt, int(n_samples_bound), int(rate), 10000, d_x10.ptr, stream))
+        p_x, p_so = d_x10.ptr, d_so10.ptr
+    else:                       # downsampling keeps every sample when the clip is at 10 kHz or below (preprocess.py:21-28)
+        nat.check(lib.dsp_resample_layout_batch(d_src_off, n_utt, int(rate), 0, int(L), int(S), None, d_fo.ptr, stream))
+        p_x, p_so = d_clips, d_src_off
+    # a clip of n samples keeps at most n * 10000 / rate + 2 of them and has at most 2 + kept / S frames
+    kept_bound = int(n_samples_bound) if rate <= 10000 else int(n_samples_bound) * 10000 // int(rate) + 2 * n_utt
+    frames_bound = kept_bound // int(S) + 2 * n_utt + 1
+    out = _cepstrum_chain(p_x, p_so, d_fo.ptr, n_utt, frames_bound, L, S, stream=stream)
+    out.frame_off = d_fo
+    return out
+
+
+def pitch_feature_batch(clips, sample_offsets, rate, details=False):
+    """pitch.pitch_feature for a batch of host clips (concatenated, `rate` Hz, offsets [B + 1]) -> (feat [B, 5] fp64,
+    valid [B] bool); rows of clips the reference raises on (a segment too short for the fits) are NaN with valid False.
+    The clips are uploaded as fp32 and go through pitch_features_device.  details=True adds a dict with the per-frame
+    pitch, the frame offsets, aux [B, 9] and the accepted values `seg`."""
+    nat.require_device()
+    so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
+    B = len(so) - 1
+    x = np.ascontiguousarray(np.asarray(clips).reshape(-1), dtype=np.float32)
+    d_x = nat.device_array('cep_clips', x if x.size else np.zeros(1, dtype=np.float32))
+    d_so = nat.device_array('cep_clips_so', so)
+    r = pitch_features_device(d_x.ptr, d_so.ptr, B, int(so[-1]), rate)
+    feat = r.feat.download((B, 5), np.float64)
+    aux = r.aux.download((B, N_AUX), np.int32)
+    valid = aux[:, 8] != 0
+    if not details:
+        return feat, valid
+    fo = r.frame_off.download((B + 1,), np.int64)
+    n = int(fo[-1])
+    return feat, valid, dict(pitch=r.pitch.download((n,), np.float64), frame_off=fo, aux=aux,
+                             seg=r.seg.download((n,), np.float64))
+
+
+def pitch_feature(sig, rate, gender='male'):
+    """pitch.py:26-47 -> (slope1, slope2, quad1, quad2, peakshift), five numpy.float64."""
+    sig = np.asarray(sig).reshape(-1)
+    feat, valid = pitch_feature_batch(sig, [0, len(sig)], rate)
+    if not valid[0]:
+        raise ValueError('pitch_feature: a smooth pitch segment shorter than 3 frames cannot be fitted')
+    return tuple(feat[0])

@@ -385,6 +385,56 @@ int dsp_decimate_batch(const float* d_in, const int64_t* d_src_offsets, const in
 int dsp_model_pitchfeat_batch(const double* d_pitch, const int64_t* d_frame_offsets, int32_t n_utt, int32_t max_len,
                               float* d_out, void* stream);
 
+/* ---- cepstral pitch and the five pitch features (pitch.pitch_detect, pitch.pitch_feature) --- */
+/*
+ * Per frame of the (already 10 kHz) signal, rectangular frames as sigproc.to_frames cuts them, one launch:
+ *   centre clipping at the median of the non-negative samples, non-binary (if center_clip != 0)
+ *                                                                    pitch.center_clip       pitch.py:145-155
+ *   y = convolve(frame, taps)[:frame_len], kept complex              sigproc.window          sigproc.py:22-46
+ *   d_rows[t] = |ifft(log|fft(y)|)|                                  pitch.pitch_detect_frame pitch.py:135-143
+ *   d_amp[t]  = sum |x| of the unclipped frame (fp64, optional)      pitch.sub_endpoint_detect pitch.py:65
+ * i.e. the loop body of pitch.pitch_detect (pitch.py:86-90).  Geometry arguments as dsp_pitch_scores_batch; d_taps:
+ * frame_len complex taps (re, im interleaved) of the 50 - 1000 Hz band (pitch.py:137); d_rows: [sum T_b, frame_len]
+ * fp32.  frame_len must be a power of two in [128, 1024] (0.0512 s at 10 kHz is 512); anything else is DSP_EINVAL.
+ * A silent frame gives [inf, nan, nan, ...], as the reference.
+ */
+int dsp_pitch_cepstrum_batch(const float* d_sig, const int64_t* d_sample_offsets, const int64_t* d_frame_offsets,
+                             int32_t n_utt, int64_t n_frames_total, int64_t uniform_samples, int32_t frame_len,
+                             int32_t frame_step, const float* d_taps, int32_t center_clip, float* d_rows, double* d_amp,
+                             void* stream);
+
+/*
+ * The tracker behind those rows (one wavefront per utterance, fp64; pitch.py:91-93).  flags bit 0 = pitch.smooth(rows, 2)
+ * with the reference's in-place habits (pitch.py:157-164; d_rows itself is not written); the peak-width scores of
+ * pitch.peak_score (pitch.py:227-242: 80 integers per frame, candidates 20 .. 99) are always formed and written to
+ * d_scores [sum T_b, 80] when it is not NULL; flags bit 1 = pitch.robust_max_pitch(scores, 20) (pitch.py:166-172,
+ * 191-206) into d_pitch [sum T_b] fp64.  With both bits clear only the scores of the rows as given are written.
+ * d_rows: [sum T_b, frame_len], fp32 as dsp_pitch_cepstrum_batch writes them, or fp64 when rows_f64 != 0.
+ */
+int dsp_pitch_cepstrum_track_batch(const void* d_rows, int32_t rows_f64, const int64_t* d_frame_offsets, int32_t n_utt,
+                                   int32_t frame_len, int32_t flags, double* d_pitch, int32_t* d_scores, void* stream);
+
+/*
+ * The tail of pitch.pitch_feature (pitch.py:34-47), one wavefront per utterance, fp64: p = sub_endpoint_detect
+ * (pitch.py:64-81) from d_amp, p_bias = 5 if p > 15 else 0, find_smooth_subsequence (pitch.py:245-279, tor 3, thres 30)
+ * on pitch[p_bias:p] and pitch[p:], then slope, quad_params and peakshift (pitch.py:49-62).
+ *   d_feat [n_utt, 5] fp64   slope1, slope2, quad1, quad2, peakshift
+ *   d_aux  [n_utt, 9] int32  p, p_bias, start1, end1, start2, end2, len1, len2, valid
+ *   d_seg  [sum T_b]  fp64   the accepted values: segment 1 from frame p_bias of the utterance, segment 2 from frame p
+ * A segment shorter than 3 values (the reference raises, or fits a rank-deficient system) gives valid = 0 and a NaN row.
+ * d_pitch == NULL: only p is computed and written (d_aux[b, 0]); d_seg and d_feat may then be NULL.
+ */
+int dsp_pitch_feature_batch(const double* d_pitch, const double* d_amp, const int64_t* d_frame_offsets, int32_t n_utt,
+                            double* d_seg, double* d_feat, int32_t* d_aux, void* stream);
+
+/*
+ * pitch.find_smooth_subsequence (pitch.py:245-279) on its own: d_values [sum n_b] fp64 with offsets d_offsets [B+1];
+ * the accepted values of the longest segment (the first one on a tie) go to d_seg[d_offsets[b] ..], and
+ * d_info[b] = (start, end, count), indices within the sequence.  An empty sequence has count 0.  tor >= 1.
+ */
+int dsp_pitch_smooth_subseq_batch(const double* d_values, const int64_t* d_offsets, int32_t n_utt, int32_t tor,
+                                  double thres, double* d_seg, int32_t* d_info, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
