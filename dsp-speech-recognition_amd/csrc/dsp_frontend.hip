@@ -21,6 +21,17 @@
 
 thread_local int g_host_dry_run = 0;   // dsp_debug_host_dry_run: plan tables in host memory (sanitizer build, no GPU)
 
+// A batch shape's index tables, built once (include/dsp_frontend.h: dsp_layout).
+struct dsp_layout {
+    int32_t n_utt, frame_len, frame_step, shift;
+    int64_t n_frames_total;
+    int32_t* group_off;
+    int32_t* group_utt;
+    int32_t* group_off2;   // tables of the int16 VAD kernel's 8-frame groups, where it uses them (vad_scan_frames8)
+    int32_t* group_utt2;
+    int device;
+};
+
 namespace {
 
 thread_local std::string g_err;
@@ -121,10 +132,31 @@ __global__ void offsets_view_kernel(const int64_t* __restrict__ src_sample, cons
     }
 }
 
-// The dense instantiations of the fused kernels need N % 4 == 0 (their 16-byte vectors must not
-// straddle utterances) and every fused kernel needs a 16-byte aligned buffer (8 for int16).  A batch
-// that violates either is still a perfectly good ragged batch of a buffer that starts a few samples
-// earlier: write offset tables (arithmetic for dense input, shifted copies otherwise) into a pooled
+// Can the vector kernels (the NFFT = 512 and 1536 MFCC kernels, the VAD tile kernels) read this batch where it lies?
+// They load 16-byte vectors of four samples (8 bytes for int16), so the buffer must start on one; the dense
+// instantiations also need N % 4 == 0 (a vector must not straddle two utterances; ragged batches take any lengths and
+// offsets); and the group counters are 32-bit.  `frames_per_group`: the frames one wave takes at a time.
+bool vector_kernels_can_read(const BatchGeom& bg, const void* d_wave, int dtype, int64_t frames_per_group) {
+    if ((reinterpret_cast<uintptr_t>(d_wave) % (dtype == DSP_WAVE_I16 ? 8 : 16)) != 0) return false;
+    if (bg.uniform_samples > 0) {
+        if ((bg.uniform_samples % 4) != 0) return false;
+        return bg.uniform_samples <= 0x3fffffff &&
+               ((bg.uniform_frames + frames_per_group - 1) / frames_per_group) * bg.n_utt <= 0x3fffffff;
+    }
+    return bg.total_frames / frames_per_group + bg.n_utt <= 0x3fffffff;
+}
+bool fast512_applicable(const dsp_plan* p, const BatchGeom& bg, const void* d_wave, int dtype) {
+    return p->d_fast && vector_kernels_can_read(bg, d_wave, dtype, 8);
+}
+bool fast1536_applicable(const dsp_plan* p, const BatchGeom& bg, const void* d_wave, int dtype) {
+    return p->d_fast1536 && vector_kernels_can_read(bg, d_wave, dtype, 4);
+}
+bool vad_tile_applicable(const BatchGeom& bg, const void* d_wave, int dtype, int FR) {
+    return FR != 0 && vector_kernels_can_read(bg, d_wave, dtype, FR);
+}
+
+// A batch that fails the alignment or the N % 4 rule above is still a perfectly good ragged batch of a buffer that
+// starts a few samples earlier: write offset tables (arithmetic for dense input, shifted copies otherwise) into a pooled
 // workspace and describe it that way.  `d_wave` is moved down to the aligned address.
 // Returns nullptr and changes nothing if no view is needed or the workspace cannot be had.
 DspWorkspace* fused_kernel_view(BatchGeom& bg, const void*& d_wave, int wave_dtype, hipStream_t st) {
@@ -147,6 +179,349 @@ DspWorkspace* fused_kernel_view(BatchGeom& bg, const void*& d_wave, int wave_dty
     bg.uniform_frames = 0;
     d_wave = reinterpret_cast<const void*>(addr - mis);
     return w;
+}
+
+// A plan's (a layout's) tables live on the device it was created on.
+int check_owner_device(int owner, bool is_plan) {
+    int dev = -1;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev == owner) return DSP_OK;
+    return is_plan ? fail(DSP_EINVAL, "plan belongs to device %d, current device is %d", owner, dev)
+                   : fail(DSP_EINVAL, "layout belongs to device %d, current device is %d", owner, dev);
+}
+
+// dense batches: the caller's frame count must be n_utt utterances of T frames
+int check_dense_frames(int64_t n_frames_total, int32_t n_utt, int64_t T) {
+    if (T * n_utt != n_frames_total)
+        return fail(DSP_EINVAL, "n_frames_total %lld != n_utt*T (%d*%lld)", (long long)n_frames_total, n_utt, (long long)T);
+    return DSP_OK;
+}
+
+size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
+
+// The opt-in matrix-pipe kernels of dense NFFT = 512 batches: the frame-per-product form first, then the other.
+// DSP_OK: launched; 1: neither took the batch; < 0: HIP error (the caller reports it).
+int try_matrix_pipe(const dsp_plan* plan, const void* d_wave, int wave_dtype, const BatchGeom& bg, int delta_n,
+                    float* d_out, int64_t ld_out, hipStream_t st) {
+    if (mfma512t_applicable(plan, bg, wave_dtype, delta_n)) {
+        const int rc = mfma512t_launch(plan, d_wave, wave_dtype, bg, delta_n, d_out, ld_out, st);
+        if (rc <= 0) return rc;
+    }
+    if (mfma512_applicable(plan, bg, wave_dtype, delta_n)) {
+        const int rc = mfma512_launch(plan, d_wave, wave_dtype, bg, delta_n, d_out, ld_out, st);
+        if (rc <= 0) return rc;
+    }
+    return 1;
+}
+
+// ---- the delta pass: delta_tiled_kernel / delta_rows_kernel, one workgroup per DT_TILE frames of one utterance ----
+static_assert(DT_TILE == (1 << DT_SHIFT), "tile tables are built with shifts");
+
+// dynamic LDS of a workgroup: DT_TILE + 4 N input rows and DT_TILE + 2 N delta rows of D floats
+size_t delta_tile_lds(int N, int D) { return ((size_t)(DT_TILE + 4 * N) + (size_t)(DT_TILE + 2 * N)) * D * sizeof(float); }
+
+// geometry of a pass over finished rows: frames only (uniform_frames <= 0: ragged)
+BatchGeom frames_geom(const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_frames_total, int64_t uniform_frames) {
+    BatchGeom bg;
+    memset(&bg, 0, sizeof(bg));
+    bg.frame_off = d_frame_offsets;
+    bg.uniform_frames = uniform_frames > 0 ? uniform_frames : 0;
+    bg.total_frames = n_frames_total;
+    bg.n_utt = n_utt;
+    return bg;
+}
+
+// workgroups of a pass: tiles per utterance (left in `tiles`) x utterances for a uniform batch (the tile table is
+// arithmetic); for a ragged one a bound on sum ceil(T_b / DT_TILE), `tiles` = 0.  The caller holds it against INT_MAX.
+int64_t delta_tile_blocks(int64_t uniform_frames, int64_t n_frames_total, int32_t n_utt, int64_t* tiles) {
+    *tiles = uniform_frames > 0 ? (uniform_frames + DT_TILE - 1) / DT_TILE : 0;
+    return uniform_frames > 0 ? *tiles * n_utt : n_frames_total / DT_TILE + n_utt;
+}
+
+void launch_delta_tiled(int64_t blocks, hipStream_t st, const float* d_in, int64_t ld_in, const BatchGeom& bg, int32_t D,
+                        int32_t N, float* d_out, int64_t ld_out, float* d_out_dd, int64_t ld_out_dd, int64_t tiles,
+                        const int64_t* tile_off) {
+    const size_t lds = delta_tile_lds(N, D);
+    const float inv_den = dsp_delta_inv_den(N);
+    if (D == 13)
+        delta_tiled_kernel<13><<<(int)blocks, 256, lds, st>>>(d_in, ld_in, bg, D, N, inv_den, d_out, ld_out, d_out_dd, ld_out_dd, (int32_t)tiles, tile_off);
+    else
+        delta_tiled_kernel<0><<<(int)blocks, 256, lds, st>>>(d_in, ld_in, bg, D, N, inv_den, d_out, ld_out, d_out_dd, ld_out_dd, (int32_t)tiles, tile_off);
+}
+
+void launch_delta_rows(int64_t blocks, hipStream_t st, const float* cep, const BatchGeom& bg, int32_t C, int32_t N,
+                       float* d_out, int64_t tiles, const int64_t* tile_off, const int64_t* seg = nullptr,
+                       const double* stats = nullptr, const int32_t* tile_utt = nullptr) {
+    const size_t lds = delta_tile_lds(N, C);
+    const float inv_den = dsp_delta_inv_den(N);
+    if (C == 13)
+        delta_rows_kernel<13><<<(int)blocks, 256, lds, st>>>(cep, bg, C, N, inv_den, d_out, (int32_t)tiles, tile_off, seg, stats, tile_utt);
+    else
+        delta_rows_kernel<0><<<(int)blocks, 256, lds, st>>>(cep, bg, C, N, inv_den, d_out, (int32_t)tiles, tile_off, seg, stats, tile_utt);
+}
+
+int launch_generic(const dsp_plan* plan, const void* d_wave, int wave_dtype, const BatchGeom& bg,
+                   int out_kind, float* d_out, int64_t ld_out, float* d_out2, hipStream_t st) {
+    GenericParams P = generic_params(plan);
+    const size_t lds = (size_t)DSP_GEN_WAVES * 2 * (plan->nfft / 2) * sizeof(float2);
+    const int grid = grid_for(bg.total_frames, DSP_GEN_WAVES);
+    return dsp_dispatch_wave(wave_dtype, [&](auto dt) {
+        auto k = features_generic_kernel<decltype(dt)::value>;
+        if (lds > 48 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        k<<<grid, 64 * DSP_GEN_WAVES, lds, st>>>(P, bg, d_wave, out_kind, d_out, ld_out, d_out2);
+        HIP_TRY(hipGetLastError());
+        return (int)DSP_OK;
+    });
+}
+
+int features_batch_impl(const dsp_plan* plan, const void* d_wave, int wave_dtype,
+                        const int64_t* d_sample_offsets, const int64_t* d_frame_offsets, int32_t n_utt,
+                        int64_t n_frames_total, int64_t uniform_samples, int out_kind, float* d_out,
+                        int64_t ld_out, float* d_out2, void* stream, const DspRaggedTables* pre) {
+    if (!plan || !d_out) return fail(DSP_EINVAL, "plan/d_out is NULL");
+    int rc = check_owner_device(plan->device, true);
+    if (rc != DSP_OK) return rc;
+    rc = check_geom(d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples);
+    if (rc != DSP_OK) return rc;
+    int width;
+    switch (out_kind) {
+        case DSP_OUT_FRAMES: width = plan->L; break;
+        case DSP_OUT_MAGSPEC:
+        case DSP_OUT_POWSPEC: width = plan->K; break;
+        case DSP_OUT_FBANK:
+            width = plan->M;
+            if (plan->M <= 0) return fail(DSP_EINVAL, "plan has no mel filterbank");
+            if (!d_out2) return fail(DSP_EINVAL, "DSP_OUT_FBANK needs d_out2 (energy)");
+            break;
+        case DSP_OUT_MFCC:
+            width = plan->C;
+            if (plan->M <= 0 || plan->C <= 0) return fail(DSP_EINVAL, "plan has no mel/DCT tables");
+            break;
+        default: return fail(DSP_EINVAL, "unknown out_kind %d", out_kind);
+    }
+    if (ld_out == 0) ld_out = width;
+    if (ld_out < width) return fail(DSP_EINVAL, "ld_out %lld < row width %d", (long long)ld_out, width);
+    BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, plan->L, plan->S);
+    if (uniform_samples > 0 && (rc = check_dense_frames(n_frames_total, n_utt, bg.uniform_frames)) != DSP_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (out_kind == DSP_OUT_MFCC && !g_force_generic && !pre) {
+        const int mrc = try_matrix_pipe(plan, d_wave, wave_dtype, bg, 0, d_out, ld_out, st);
+        if (mrc == DSP_OK) return DSP_OK;
+        if (mrc < 0) return fail(mrc, "matrix-pipe MFCC kernel launch failed");
+    }
+    if (out_kind == DSP_OUT_MFCC && !g_force_generic && (plan->d_fast || plan->d_fast1536)) {
+        BatchGeom fg = bg;
+        const void* fw = d_wave;
+        DspWorkspace* view = fused_kernel_view(fg, fw, wave_dtype, st);
+        int frc = 1;   // 1 = no fused kernel took it
+        if (fast512_applicable(plan, fg, fw, wave_dtype))
+            frc = fast512_launch(plan, fw, wave_dtype, fg, d_out, ld_out, st, pre);
+        else if (fast1536_applicable(plan, fg, fw, wave_dtype))
+            frc = fast1536_launch(plan, fw, wave_dtype, fg, d_out, ld_out, st, pre);
+        if (view && dsp_workspace_pool().release(view, st) != 0 && frc == DSP_OK) frc = DSP_EHIP;
+        if (frc == DSP_OK) return DSP_OK;
+        if (frc < 0) return fail(frc, "fused kernel launch failed");
+    }
+    return launch_generic(plan, d_wave, wave_dtype, bg, out_kind, d_out, ld_out, d_out2, st);
+}
+
+// ---- the three routes of dsp_mfcc_delta_batch.  Each returns 1 where it does not serve the batch: the next one does. ----
+
+// Dense batches of the NFFT = 512 plans: ONE kernel writes the finished rows (kernels_fast512.h, "Fused delta").
+int mfcc_delta_one_launch(const dsp_plan* plan, const void* d_wave, int wave_dtype, int32_t n_utt, int64_t n_frames_total,
+                          int64_t uniform_samples, int64_t uniform_frames, int32_t delta_n, float* d_out, hipStream_t st) {
+    int rc = check_owner_device(plan->device, true);
+    if (rc != DSP_OK) return rc;
+    rc = check_dense_frames(n_frames_total, n_utt, uniform_frames);
+    if (rc != DSP_OK) return rc;
+    const BatchGeom fbg = make_geom(nullptr, nullptr, n_utt, n_frames_total, uniform_samples, plan->L, plan->S);
+    const int mrc = try_matrix_pipe(plan, d_wave, wave_dtype, fbg, delta_n, d_out, 3 * (int64_t)plan->C, st);
+    if (mrc == DSP_OK) return DSP_OK;
+    if (mrc < 0) return fail(mrc, "matrix-pipe MFCC + delta kernel launch failed");
+    if (!fast512_applicable(plan, fbg, d_wave, wave_dtype)) return 1;
+    const int frc = fast512_launch_fused(plan, d_wave, wave_dtype, fbg, delta_n, d_out, st);
+    if (frc < 0) return fail(frc, "fused MFCC + delta kernel launch failed");
+    return frc;
+}
+
+// Two passes, every byte written once as part of a full line: the MFCC kernel writes DENSE cepstra
+// [sum T, C] into a pooled scratch buffer, delta_rows_kernel turns them into whole 3C-float rows.
+// (Writing the 52-byte cepstra straight into the 156-byte rows cost 1.5x write amplification and a
+// strided re-read.)  Scratch above 256 MiB is left to the in-place form.
+int mfcc_delta_via_scratch(const dsp_plan* plan, const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets,
+                           const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_frames_total, int64_t uniform_samples,
+                           int64_t uniform_frames, int32_t delta_n, float* d_out, void* stream) {
+    const int C = plan->C;
+    const size_t scratch_bytes = (size_t)n_frames_total * C * sizeof(float);
+    if (delta_tile_lds(delta_n, C) > 64 * 1024 || scratch_bytes > ((size_t)256 << 20)) return 1;
+    const bool ragged = uniform_frames <= 0;
+    int64_t tiles;
+    const int64_t blocks = delta_tile_blocks(uniform_frames, n_frames_total, n_utt, &tiles);
+    if (blocks > 0x7fffffff) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    // ragged: the delta tile table and the fused MFCC kernel's group tables come from ONE small launch
+    const int gshift = plan->d_fast ? 3 : (plan->d_fast1536 ? 2 : 0);
+    const int64_t gbound = gshift ? (n_frames_total >> gshift) + n_utt : 0;
+    const size_t tile_bytes = ragged ? pad256(((size_t)n_utt + 1) * sizeof(int64_t)) : 0;
+    const size_t goff_bytes = ragged && gshift ? pad256(((size_t)n_utt + 1) * sizeof(int32_t)) : 0;
+    const size_t gutt_bytes = ragged && gshift ? pad256((size_t)gbound * sizeof(int32_t)) : 0;
+    DspWorkspace* w = dsp_workspace_pool().acquire(tile_bytes + goff_bytes + gutt_bytes + scratch_bytes, st);
+    // no scratch to be had (device memory exhausted, or `stream` is being captured into a HIP graph): the
+    // in-place form needs none -- same values, 52-byte partial row writes instead of whole lines
+    if (!w) return 1;
+    char* wp = static_cast<char*>(w->ptr);
+    int64_t* tile_off = ragged ? reinterpret_cast<int64_t*>(wp) : nullptr;
+    DspRaggedTables pre;
+    pre.shift = gshift;
+    pre.group_off = reinterpret_cast<int32_t*>(wp + tile_bytes);
+    pre.group_utt = reinterpret_cast<int32_t*>(wp + tile_bytes + goff_bytes);
+    float* cep = reinterpret_cast<float*>(wp + tile_bytes + goff_bytes + gutt_bytes);
+    const bool have_pre = ragged && gshift != 0 && gbound <= 0x3fffffff;
+    if (have_pre) f512_build_group_tables(d_frame_offsets, n_utt, gshift, pre.group_off, pre.group_utt, st, tile_off);
+    int rc = features_batch_impl(plan, d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt,
+                                 n_frames_total, uniform_samples, DSP_OUT_MFCC, cep, (int64_t)C, nullptr, stream,
+                                 have_pre ? &pre : nullptr);
+    if (rc == DSP_OK) {
+        if (ragged && !have_pre) prefix_ceil_kernel<<<1, 1024, 0, st>>>(d_frame_offsets, n_utt, DT_SHIFT, tile_off);
+        launch_delta_rows(blocks, st, cep, frames_geom(d_frame_offsets, n_utt, n_frames_total, uniform_frames), C, delta_n,
+                          d_out, tiles, tile_off);
+        if (hipGetLastError() != hipSuccess) rc = fail(DSP_EHIP, "delta_rows_kernel launch failed");
+    }
+    if (dsp_workspace_pool().release(w, st) != 0 && rc == DSP_OK) rc = fail(DSP_EHIP, "workspace release failed");
+    return rc;
+}
+
+// In place, no workspace: the cepstra go straight into the first C columns of the 3C-float rows, the delta pass reads
+// them back from there.
+int mfcc_delta_in_place(const dsp_plan* plan, const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets,
+                        const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_frames_total, int64_t uniform_samples,
+                        int64_t uniform_frames, int32_t delta_n, float* d_out, void* stream) {
+    const int C = plan->C;
+    int rc = dsp_features_batch(plan, d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt,
+                                n_frames_total, uniform_samples, DSP_OUT_MFCC, d_out, 3 * (int64_t)C, nullptr, stream);
+    if (rc != DSP_OK) return rc;
+    return dsp_delta_batch(d_out, 3 * (int64_t)C, d_frame_offsets, n_utt, n_frames_total, uniform_frames, C,
+                           delta_n, d_out + C, 3 * (int64_t)C, d_out + 2 * C, 3 * (int64_t)C, stream);
+}
+
+int vad_features_impl(const dsp_layout* layout, const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets,
+                      const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_frames_total,
+                      int64_t uniform_samples, int32_t frame_len, int32_t frame_step, int32_t use_sq,
+                      double* d_amp_sum, int32_t* d_zcr, void* stream) {
+    if (!d_amp_sum || !d_zcr) return fail(DSP_EINVAL, "dsp_vad_features_batch: NULL output");
+    if (frame_len <= 0 || frame_step <= 0) return fail(DSP_EINVAL, "frame_len/frame_step must be > 0");
+    int rc = check_geom(d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples);
+    if (rc != DSP_OK) return rc;
+    BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, frame_len, frame_step);
+    hipStream_t st = (hipStream_t)stream;
+    const int tile = vad_tile_frames(frame_len, frame_step);
+    if (!g_force_generic && tile != 0) {
+        BatchGeom fg = bg;
+        const void* fw = d_wave;
+        DspWorkspace* view = fused_kernel_view(fg, fw, wave_dtype, st);
+        const bool ok = vad_tile_applicable(fg, fw, wave_dtype, tile);
+        DspRaggedTables pre;
+        const bool have_pre = layout != nullptr && layout->group_off != nullptr && view == nullptr;
+        if (have_pre) {
+            pre.shift = layout->shift; pre.group_off = layout->group_off; pre.group_utt = layout->group_utt;
+            if (layout->group_off2 != nullptr) { pre.shift2 = 3; pre.group_off2 = layout->group_off2; pre.group_utt2 = layout->group_utt2; }
+        }
+        if (ok) rc = vad_tile_launch(tile, frame_len, frame_step, use_sq, fg, fw, wave_dtype, d_amp_sum, d_zcr, st,
+                                     have_pre ? &pre : nullptr);
+        if (view && dsp_workspace_pool().release(view, st) != 0 && ok && rc == DSP_OK) rc = DSP_EHIP;
+        if (ok) {
+            if (rc != DSP_OK) return fail(rc, "vad tile kernel launch failed");
+            return DSP_OK;
+        }
+    }
+    const int grid = grid_for(n_frames_total, 4);
+    dsp_dispatch_wave(wave_dtype, [&](auto dt) {
+        vad_features_kernel<decltype(dt)::value><<<grid, 256, 0, st>>>(d_wave, bg, frame_len, frame_step, use_sq, d_amp_sum, d_zcr);
+    });
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+struct SegWork {
+    size_t stats, tile, goff, gutt, tutt, cep, total;
+};
+// layout of the caller-owned work buffer of dsp_mfcc_delta_segments_batch (every part 256-byte aligned)
+SegWork seg_work_layout(int32_t n_utt, int64_t n_frames_bound, int32_t C) {
+    SegWork w;
+    w.stats = 0;
+    w.tile = w.stats + pad256((size_t)n_utt * 2 * sizeof(double));
+    w.goff = w.tile + pad256(((size_t)n_utt + 1) * sizeof(int64_t));
+    w.gutt = w.goff + pad256(((size_t)n_utt + 1) * sizeof(int32_t));
+    w.tutt = w.gutt + pad256(((size_t)(n_frames_bound >> 2) + (size_t)n_utt) * sizeof(int32_t));   // 4-frame groups (NFFT = 1536) at most
+    w.cep = w.tutt + pad256(((size_t)(n_frames_bound >> DT_SHIFT) + (size_t)n_utt) * sizeof(int32_t));
+    w.total = w.cep + pad256((size_t)n_frames_bound * (size_t)C * sizeof(float));
+    return w;
+}
+
+// The argument checks the two model-finalize entry points share (behind their own), and the launch.
+int model_finalize_impl(const float* d_mfcc, int64_t ld_in, const int64_t* d_frame_offsets, int32_t n_utt, int32_t C,
+                        int32_t N, int32_t max_len, float* d_out, int32_t* d_len0, const int64_t* d_segments,
+                        const double* d_stats, void* stream) {
+    if (N < 1) return fail(DSP_EINVAL, "N must be an integer >= 1");  // base.py:71-72
+    if (C <= 0 || C > 32 || max_len <= 0) return fail(DSP_EINVAL, "need 0 < C <= 32 and max_len > 0");
+    if (ld_in == 0) ld_in = C;
+    if (ld_in < C) return fail(DSP_EINVAL, "ld_in %lld < C %d", (long long)ld_in, C);
+    const size_t lds = ((size_t)(max_len + 2 * N) + (size_t)(max_len + N)) * C * sizeof(float);
+    if (lds > 64 * 1024) return fail(DSP_EINVAL, "max_len * C too large for the LDS tile (%zu bytes)", lds);
+    model_finalize_kernel<<<n_utt, 256, lds, (hipStream_t)stream>>>(d_mfcc, ld_in, d_frame_offsets, n_utt, C, N, max_len,
+                                                                   d_out, d_len0, d_segments, d_stats);
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+// The same for the two endpoint-rule entry points (d_voiced: the autocorrelation gate's verdicts, or NULL).
+int endpoint_rule_impl(const double* d_amp_sum, const int32_t* d_zcr, const uint8_t* d_voiced, const int64_t* d_frame_offsets,
+                       int32_t n_utt, int32_t frame_len, double cfg_frame, double cfg_step, int32_t* d_endpoints,
+                       void* stream) {
+    if (!(cfg_frame > 0.0) || !(cfg_step > 0.0)) return fail(DSP_EINVAL, "cfg.frame / cfg.step must be > 0");
+    if (2 * (int)(0.100 / cfg_step) > DSP_MAX_SIL)
+        return fail(DSP_EINVAL, "cfg.step %g gives a silence window > %d frames", cfg_step, DSP_MAX_SIL);
+    endpoint_rule_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(
+        d_amp_sum, d_zcr, d_frame_offsets, n_utt, frame_len, cfg_frame, cfg_step, d_endpoints, d_voiced);
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+// what both endpoint-layout entry points ask of their shared arguments
+bool endpoint_layout_args_ok(const int32_t* d_endpoints, const int64_t* d_sample_offsets, const int64_t* d_segments,
+                             const int64_t* d_dst_offsets, const int64_t* d_frame_offsets, int32_t n_utt) {
+    return d_endpoints && d_sample_offsets && d_segments && d_dst_offsets && d_frame_offsets && n_utt > 0;
+}
+
+// The cepstrum kernels are instantiated for power-of-two frame lengths in [128, 1024]: f(std::integral_constant<int, L>).
+bool cepstrum_frame_len_ok(int32_t frame_len) {
+    return frame_len >= 128 && frame_len <= 1024 && (frame_len & (frame_len - 1)) == 0;
+}
+template <class F>
+void dispatch_cepstrum_frame_len(int32_t frame_len, F&& f) {
+    switch (frame_len) {
+        case 128: f(std::integral_constant<int, 128>{}); break;
+        case 256: f(std::integral_constant<int, 256>{}); break;
+        case 512: f(std::integral_constant<int, 512>{}); break;
+        default: f(std::integral_constant<int, 1024>{}); break;
+    }
+}
+
+// diagnostic builds only: sums a kernel's per-phase shader-clock stamps (`sym`: [slots][n_stamp] on the device) over the
+// slots into out[0 .. min(n, n_stamp)) and zeroes them
+template <class Sym>
+int read_stamps(const Sym& sym, int n_stamp, int slots, unsigned long long* out, int n) {
+    std::vector<unsigned int> h((size_t)n_stamp * slots);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(sym), h.size() * 4));
+    for (int i = 0; i < n && i < n_stamp; ++i) {
+        out[i] = 0;
+        for (int w = 0; w < slots; ++w) out[i] += h[(size_t)w * n_stamp + i];
+    }
+    h.assign(h.size(), 0u);
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(sym), h.data(), h.size() * 4));
+    return DSP_OK;
 }
 
 }  // namespace
@@ -177,52 +552,16 @@ int dsp_debug_pool_stats(long long* n_buffers, long long* bytes) {
     return DSP_OK;
 }
 
+// diagnostic builds only (not declared in the public header): per-phase shader-clock sums of mfcc512_kernel,
+// mfcc512t_kernel and mfcc512m_kernel
 #ifdef F512_STAMPS
-// diagnostic builds only: per-phase shader-clock sums of mfcc512_kernel (not declared in the public header)
-int dsp_debug_read_stamps(unsigned long long* out, int n) {
-    static std::vector<unsigned int> h(F512_NSTAMP * 8192);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(f512_stamp_sum), h.size() * 4));
-    for (int i = 0; i < n && i < F512_NSTAMP; ++i) {
-        out[i] = 0;
-        for (int w = 0; w < 8192; ++w) out[i] += h[(size_t)w * F512_NSTAMP + i];
-    }
-    std::fill(h.begin(), h.end(), 0u);
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(f512_stamp_sum), h.data(), h.size() * 4));
-    return DSP_OK;
-}
+int dsp_debug_read_stamps(unsigned long long* out, int n) { return read_stamps(f512_stamp_sum, F512_NSTAMP, 8192, out, n); }
 #endif
-
 #ifdef M512T_STAMPS
-// diagnostic builds only: per-phase shader-clock sums of mfcc512t_kernel (not declared in the public header)
-int dsp_debug_read_stamps_m512t(unsigned long long* out, int n) {
-    static std::vector<unsigned int> h(M512T_NSTAMP * 4096);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(m512t_stamp_sum), h.size() * 4));
-    for (int i = 0; i < n && i < M512T_NSTAMP; ++i) {
-        out[i] = 0;
-        for (int w = 0; w < 4096; ++w) out[i] += h[(size_t)w * M512T_NSTAMP + i];
-    }
-    std::fill(h.begin(), h.end(), 0u);
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(m512t_stamp_sum), h.data(), h.size() * 4));
-    return DSP_OK;
-}
+int dsp_debug_read_stamps_m512t(unsigned long long* out, int n) { return read_stamps(m512t_stamp_sum, M512T_NSTAMP, 4096, out, n); }
 #endif
-
 #ifdef M512_STAMPS
-// diagnostic builds only: per-phase shader-clock sums of mfcc512m_kernel (not declared in the public header)
-int dsp_debug_read_stamps_m512(unsigned long long* out, int n) {
-    static std::vector<unsigned int> h(M512_NSTAMP * 2048);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(m512_stamp_sum), h.size() * 4));
-    for (int i = 0; i < n && i < M512_NSTAMP; ++i) {
-        out[i] = 0;
-        for (int w = 0; w < 2048; ++w) out[i] += h[(size_t)w * M512_NSTAMP + i];
-    }
-    std::fill(h.begin(), h.end(), 0u);
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(m512_stamp_sum), h.data(), h.size() * 4));
-    return DSP_OK;
-}
+int dsp_debug_read_stamps_m512(unsigned long long* out, int n) { return read_stamps(m512_stamp_sum, M512_NSTAMP, 2048, out, n); }
 #endif
 
 int dsp_plan_has_fast_path(const dsp_plan* plan) { return plan && (plan->d_fast || plan->d_fast1536) ? 1 : 0; }
@@ -380,97 +719,13 @@ int dsp_preemphasis_batch(const void* d_wave, int wave_dtype, const int64_t* d_s
                           int32_t n_utt, int64_t n_samples_total, float coeff, float* d_out, void* stream) {
     if (!d_wave || !d_out || !d_sample_offsets || n_utt <= 0 || n_samples_total <= 0)
         return fail(DSP_EINVAL, "dsp_preemphasis_batch: bad arguments");
+    if (wave_dtype != DSP_WAVE_I16 && wave_dtype != DSP_WAVE_F32) return fail(DSP_EINVAL, "unsupported wave_dtype %d", wave_dtype);
     const int grid = grid_for(n_samples_total, 256);
-    hipStream_t st = (hipStream_t)stream;
-    if (wave_dtype == DSP_WAVE_I16)
-        preemphasis_kernel<DSP_WAVE_I16><<<grid, 256, 0, st>>>(d_wave, d_sample_offsets, n_utt, n_samples_total, coeff, d_out);
-    else if (wave_dtype == DSP_WAVE_F32)
-        preemphasis_kernel<DSP_WAVE_F32><<<grid, 256, 0, st>>>(d_wave, d_sample_offsets, n_utt, n_samples_total, coeff, d_out);
-    else
-        return fail(DSP_EINVAL, "unsupported wave_dtype %d", wave_dtype);
+    dsp_dispatch_wave(wave_dtype, [&](auto dt) {
+        preemphasis_kernel<decltype(dt)::value><<<grid, 256, 0, (hipStream_t)stream>>>(d_wave, d_sample_offsets, n_utt, n_samples_total, coeff, d_out);
+    });
     HIP_TRY(hipGetLastError());
     return DSP_OK;
-}
-
-static int launch_generic(const dsp_plan* plan, const void* d_wave, int wave_dtype, const BatchGeom& bg,
-                          int out_kind, float* d_out, int64_t ld_out, float* d_out2, hipStream_t st) {
-    GenericParams P = generic_params(plan);
-    const size_t lds = (size_t)DSP_GEN_WAVES * 2 * (plan->nfft / 2) * sizeof(float2);
-    const int grid = grid_for(bg.total_frames, DSP_GEN_WAVES);
-    if (wave_dtype == DSP_WAVE_I16) {
-        if (lds > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute((const void*)features_generic_kernel<DSP_WAVE_I16>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        features_generic_kernel<DSP_WAVE_I16><<<grid, 64 * DSP_GEN_WAVES, lds, st>>>(P, bg, d_wave, out_kind, d_out, ld_out, d_out2);
-    } else {
-        if (lds > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute((const void*)features_generic_kernel<DSP_WAVE_F32>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        features_generic_kernel<DSP_WAVE_F32><<<grid, 64 * DSP_GEN_WAVES, lds, st>>>(P, bg, d_wave, out_kind, d_out, ld_out, d_out2);
-    }
-    HIP_TRY(hipGetLastError());
-    return DSP_OK;
-}
-
-static int features_batch_impl(const dsp_plan* plan, const void* d_wave, int wave_dtype,
-                               const int64_t* d_sample_offsets, const int64_t* d_frame_offsets, int32_t n_utt,
-                               int64_t n_frames_total, int64_t uniform_samples, int out_kind, float* d_out,
-                               int64_t ld_out, float* d_out2, void* stream, const DspRaggedTables* pre) {
-    if (!plan || !d_out) return fail(DSP_EINVAL, "plan/d_out is NULL");
-    {
-        int dev = -1;
-        HIP_TRY(hipGetDevice(&dev));
-        if (dev != plan->device)   // the plan's tables live on the device it was created on
-            return fail(DSP_EINVAL, "plan belongs to device %d, current device is %d", plan->device, dev);
-    }
-    int rc = check_geom(d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples);
-    if (rc != DSP_OK) return rc;
-    int width;
-    switch (out_kind) {
-        case DSP_OUT_FRAMES: width = plan->L; break;
-        case DSP_OUT_MAGSPEC:
-        case DSP_OUT_POWSPEC: width = plan->K; break;
-        case DSP_OUT_FBANK:
-            width = plan->M;
-            if (plan->M <= 0) return fail(DSP_EINVAL, "plan has no mel filterbank");
-            if (!d_out2) return fail(DSP_EINVAL, "DSP_OUT_FBANK needs d_out2 (energy)");
-            break;
-        case DSP_OUT_MFCC:
-            width = plan->C;
-            if (plan->M <= 0 || plan->C <= 0) return fail(DSP_EINVAL, "plan has no mel/DCT tables");
-            break;
-        default: return fail(DSP_EINVAL, "unknown out_kind %d", out_kind);
-    }
-    if (ld_out == 0) ld_out = width;
-    if (ld_out < width) return fail(DSP_EINVAL, "ld_out %lld < row width %d", (long long)ld_out, width);
-    BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, plan->L, plan->S);
-    if (uniform_samples > 0 && bg.uniform_frames * n_utt != n_frames_total)
-        return fail(DSP_EINVAL, "n_frames_total %lld != n_utt*T (%d*%lld)", (long long)n_frames_total, n_utt, (long long)bg.uniform_frames);
-    hipStream_t st = (hipStream_t)stream;
-    if (out_kind == DSP_OUT_MFCC && !g_force_generic && !pre && mfma512t_applicable(plan, bg, wave_dtype, 0)) {
-        const int mrc = mfma512t_launch(plan, d_wave, wave_dtype, bg, 0, d_out, ld_out, st);   // dense batches: matrix-pipe kernel, frame per product
-        if (mrc == DSP_OK) return DSP_OK;
-        if (mrc < 0) return fail(mrc, "matrix-pipe MFCC kernel launch failed");
-    }
-    if (out_kind == DSP_OUT_MFCC && !g_force_generic && !pre && mfma512_applicable(plan, bg, wave_dtype, 0)) {
-        const int mrc = mfma512_launch(plan, d_wave, wave_dtype, bg, 0, d_out, ld_out, st);   // dense batches: matrix-pipe kernel
-        if (mrc == DSP_OK) return DSP_OK;
-        if (mrc < 0) return fail(mrc, "matrix-pipe MFCC kernel launch failed");
-    }
-    if (out_kind == DSP_OUT_MFCC && !g_force_generic && (plan->d_fast || plan->d_fast1536)) {
-        BatchGeom fg = bg;
-        const void* fw = d_wave;
-        DspWorkspace* view = fused_kernel_view(fg, fw, wave_dtype, st);
-        int frc = 1;   // 1 = no fused kernel took it
-        if (fast512_applicable(plan, fg, fw, wave_dtype))
-            frc = fast512_launch(plan, fw, wave_dtype, fg, d_out, ld_out, st, pre);
-        else if (fast1536_applicable(plan, fg, fw, wave_dtype))
-            frc = fast1536_launch(plan, fw, wave_dtype, fg, d_out, ld_out, st, pre);
-        if (view && dsp_workspace_pool().release(view, st) != 0 && frc == DSP_OK) frc = DSP_EHIP;
-        if (frc == DSP_OK) return DSP_OK;
-        if (frc < 0) return fail(frc, "fused kernel launch failed");
-    }
-    return launch_generic(plan, d_wave, wave_dtype, bg, out_kind, d_out, ld_out, d_out2, st);
 }
 
 int dsp_features_batch(const dsp_plan* plan, const void* d_wave, int wave_dtype,
@@ -491,48 +746,28 @@ int dsp_delta_batch(const float* d_in, int64_t ld_in, const int64_t* d_frame_off
     if (ld_in == 0) ld_in = D;
     if (ld_out == 0) ld_out = D;
     if (ld_out_dd == 0) ld_out_dd = D;
-    BatchGeom bg;
-    memset(&bg, 0, sizeof(bg));
-    bg.frame_off = d_frame_offsets;
-    bg.uniform_frames = uniform_frames > 0 ? uniform_frames : 0;
-    bg.total_frames = n_frames_total;
-    bg.n_utt = n_utt;
-    int den = 0;
-    for (int i = 1; i <= N; ++i) den += i * i;
-    const float inv_den = (float)(1.0 / (2.0 * den));
-    // tiled LDS kernel for uniform batches (tile table is arithmetic); per-element kernel otherwise
-    const size_t lds = ((size_t)(DT_TILE + 4 * N) + (size_t)(DT_TILE + 2 * N)) * D * sizeof(float);
-    if (uniform_frames > 0 && lds <= 64 * 1024) {
-        const int64_t tiles = (uniform_frames + DT_TILE - 1) / DT_TILE;
-        const int64_t blocks = tiles * n_utt;
+    const BatchGeom bg = frames_geom(d_frame_offsets, n_utt, n_frames_total, uniform_frames);
+    hipStream_t st = (hipStream_t)stream;
+    const bool strides_ok = ld_in <= 0x7fffff && ld_out <= 0x7fffff && ld_out_dd <= 0x7fffff;
+    int64_t tiles;
+    const int64_t blocks = delta_tile_blocks(uniform_frames, n_frames_total, n_utt, &tiles);
+    // tiled LDS kernel where a tile fits (the tile table of a uniform batch is arithmetic); per-element kernel otherwise
+    if (uniform_frames > 0 && delta_tile_lds(N, D) <= 64 * 1024) {
         if (blocks > 0x7fffffff) return fail(DSP_EINVAL, "too many delta tiles");
-        if (ld_in > 0x7fffff || ld_out > 0x7fffff || ld_out_dd > 0x7fffff) return fail(DSP_EINVAL, "row stride too large");
-        if (D == 13)
-            delta_tiled_kernel<13><<<(int)blocks, 256, lds, (hipStream_t)stream>>>(
-                d_in, ld_in, bg, D, N, inv_den, d_out, ld_out, d_out_dd, ld_out_dd, (int32_t)tiles, nullptr);
-        else
-            delta_tiled_kernel<0><<<(int)blocks, 256, lds, (hipStream_t)stream>>>(
-                d_in, ld_in, bg, D, N, inv_den, d_out, ld_out, d_out_dd, ld_out_dd, (int32_t)tiles, nullptr);
-    } else if (uniform_frames <= 0 && lds <= 64 * 1024 && ld_in <= 0x7fffff && ld_out <= 0x7fffff && ld_out_dd <= 0x7fffff) {
+        if (!strides_ok) return fail(DSP_EINVAL, "row stride too large");
+        launch_delta_tiled(blocks, st, d_in, ld_in, bg, D, N, d_out, ld_out, d_out_dd, ld_out_dd, tiles, nullptr);
+    } else if (uniform_frames <= 0 && delta_tile_lds(N, D) <= 64 * 1024 && strides_ok) {
         // ragged: per-utterance tile prefix in a pooled, event-guarded workspace, grid sized by a bound
-        static_assert(DT_TILE == (1 << DT_SHIFT), "tile tables are built with shifts");
-        const int64_t bound = n_frames_total / DT_TILE + n_utt;
-        if (bound > 0x7fffffff) return fail(DSP_EINVAL, "too many delta tiles");
-        hipStream_t st = (hipStream_t)stream;
+        if (blocks > 0x7fffffff) return fail(DSP_EINVAL, "too many delta tiles");
         DspWorkspace* w = dsp_workspace_pool().acquire(((size_t)n_utt + 1) * sizeof(int64_t), st);
         if (!w) return fail(DSP_EHIP, "workspace allocation failed");
         int64_t* tile_off = static_cast<int64_t*>(w->ptr);
         prefix_ceil_kernel<<<1, 1024, 0, st>>>(d_frame_offsets, n_utt, DT_SHIFT, tile_off);
-        if (D == 13)
-            delta_tiled_kernel<13><<<(int)bound, 256, lds, st>>>(d_in, ld_in, bg, D, N, inv_den, d_out, ld_out,
-                                                                 d_out_dd, ld_out_dd, 0, tile_off);
-        else
-            delta_tiled_kernel<0><<<(int)bound, 256, lds, st>>>(d_in, ld_in, bg, D, N, inv_den, d_out, ld_out,
-                                                                d_out_dd, ld_out_dd, 0, tile_off);
+        launch_delta_tiled(blocks, st, d_in, ld_in, bg, D, N, d_out, ld_out, d_out_dd, ld_out_dd, 0, tile_off);
         if (dsp_workspace_pool().release(w, st) != 0) return fail(DSP_EHIP, "workspace release failed");
     } else {
-        delta_kernel<<<grid_for(n_frames_total * D, 256), 256, 0, (hipStream_t)stream>>>(
-            d_in, ld_in, bg, D, N, inv_den, d_out, ld_out, d_out_dd, ld_out_dd);
+        delta_kernel<<<grid_for(n_frames_total * D, 256), 256, 0, st>>>(
+            d_in, ld_in, bg, D, N, dsp_delta_inv_den(N), d_out, ld_out, d_out_dd, ld_out_dd);
     }
     HIP_TRY(hipGetLastError());
     return DSP_OK;
@@ -557,95 +792,16 @@ int dsp_mfcc_delta_batch(const dsp_plan* plan, const void* d_wave, int wave_dtyp
     int64_t uniform_frames = 0;
     if (uniform_samples > 0) dsp_frame_count(uniform_samples, plan->L, plan->S, &uniform_frames);
     hipStream_t st = (hipStream_t)stream;
-    // Dense batches of the NFFT = 512 plans: ONE kernel writes the finished rows (kernels_fast512.h, "Fused delta").
     if (uniform_samples > 0 && !g_force_generic && plan->d_fast) {
-        int dev = -1;
-        HIP_TRY(hipGetDevice(&dev));
-        if (dev != plan->device) return fail(DSP_EINVAL, "plan belongs to device %d, current device is %d", plan->device, dev);
-        if (uniform_frames * n_utt != n_frames_total)
-            return fail(DSP_EINVAL, "n_frames_total %lld != n_utt*T (%d*%lld)", (long long)n_frames_total, n_utt, (long long)uniform_frames);
-        const BatchGeom fbg = make_geom(nullptr, nullptr, n_utt, n_frames_total, uniform_samples, plan->L, plan->S);
-        if (mfma512t_applicable(plan, fbg, wave_dtype, delta_n)) {
-            const int mrc = mfma512t_launch(plan, d_wave, wave_dtype, fbg, delta_n, d_out, 3 * (int64_t)C, st);
-            if (mrc == DSP_OK) return DSP_OK;
-            if (mrc < 0) return fail(mrc, "matrix-pipe MFCC + delta kernel launch failed");
-        }
-        if (mfma512_applicable(plan, fbg, wave_dtype, delta_n)) {
-            const int mrc = mfma512_launch(plan, d_wave, wave_dtype, fbg, delta_n, d_out, 3 * (int64_t)C, st);
-            if (mrc == DSP_OK) return DSP_OK;
-            if (mrc < 0) return fail(mrc, "matrix-pipe MFCC + delta kernel launch failed");
-        }
-        const int frc = fast512_launch_fused(plan, d_wave, wave_dtype, fbg, delta_n, d_out, st);
-        if (frc == DSP_OK) return DSP_OK;
-        if (frc < 0) return fail(frc, "fused MFCC + delta kernel launch failed");
+        const int rc = mfcc_delta_one_launch(plan, d_wave, wave_dtype, n_utt, n_frames_total, uniform_samples, uniform_frames,
+                                             delta_n, d_out, st);
+        if (rc != 1) return rc;
     }
-    // Two passes, every byte written once as part of a full line: the MFCC kernel writes DENSE cepstra
-    // [sum T, C] into a pooled scratch buffer, delta_rows_kernel turns them into whole 3C-float rows.
-    // (Writing the 52-byte cepstra straight into the 156-byte rows cost 1.5x write amplification and a
-    // strided re-read.)  Scratch above 256 MiB falls back to the in-place form.
-    const size_t lds = ((size_t)(DT_TILE + 4 * delta_n) + (size_t)(DT_TILE + 2 * delta_n)) * C * sizeof(float);
-    const size_t scratch_bytes = (size_t)n_frames_total * C * sizeof(float);
-    if (n_frames_total > 0 && n_utt > 0 && lds <= 64 * 1024 && scratch_bytes <= ((size_t)256 << 20)) {
-        const bool ragged = uniform_frames <= 0;
-        int64_t tiles = 0, blocks = 0;
-        if (!ragged) {
-            tiles = (uniform_frames + DT_TILE - 1) / DT_TILE;
-            blocks = tiles * n_utt;
-        } else {
-            if (!d_frame_offsets) return fail(DSP_EINVAL, "ragged batch needs d_frame_offsets");
-            blocks = n_frames_total / DT_TILE + n_utt;
-        }
-        if (blocks <= 0x7fffffff) {
-            // ragged: the delta tile table and the fused MFCC kernel's group tables come from ONE small launch
-            const int gshift = plan->d_fast ? 3 : (plan->d_fast1536 ? 2 : 0);
-            const int64_t gbound = gshift ? (n_frames_total >> gshift) + n_utt : 0;
-            auto pad256 = [](size_t b) { return (b + 255) / 256 * 256; };
-            const size_t tile_bytes = ragged ? pad256(((size_t)n_utt + 1) * sizeof(int64_t)) : 0;
-            const size_t goff_bytes = ragged && gshift ? pad256(((size_t)n_utt + 1) * sizeof(int32_t)) : 0;
-            const size_t gutt_bytes = ragged && gshift ? pad256((size_t)gbound * sizeof(int32_t)) : 0;
-            DspWorkspace* w = dsp_workspace_pool().acquire(tile_bytes + goff_bytes + gutt_bytes + scratch_bytes, st);
-            if (w) {
-            char* wp = static_cast<char*>(w->ptr);
-            int64_t* tile_off = ragged ? reinterpret_cast<int64_t*>(wp) : nullptr;
-            DspRaggedTables pre;
-            pre.shift = gshift;
-            pre.group_off = reinterpret_cast<int32_t*>(wp + tile_bytes);
-            pre.group_utt = reinterpret_cast<int32_t*>(wp + tile_bytes + goff_bytes);
-            float* cep = reinterpret_cast<float*>(wp + tile_bytes + goff_bytes + gutt_bytes);
-            const bool have_pre = ragged && gshift != 0 && gbound <= 0x3fffffff;
-            if (have_pre) f512_build_group_tables(d_frame_offsets, n_utt, gshift, pre.group_off, pre.group_utt, st, tile_off);
-            int rc = features_batch_impl(plan, d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt,
-                                         n_frames_total, uniform_samples, DSP_OUT_MFCC, cep, (int64_t)C, nullptr, stream,
-                                         have_pre ? &pre : nullptr);
-            if (rc == DSP_OK) {
-                BatchGeom bg;
-                memset(&bg, 0, sizeof(bg));
-                bg.frame_off = d_frame_offsets;
-                bg.uniform_frames = uniform_frames > 0 ? uniform_frames : 0;
-                bg.total_frames = n_frames_total;
-                bg.n_utt = n_utt;
-                int den = 0;
-                for (int i = 1; i <= delta_n; ++i) den += i * i;
-                const float inv_den = (float)(1.0 / (2.0 * den));
-                if (ragged && !have_pre) prefix_ceil_kernel<<<1, 1024, 0, st>>>(d_frame_offsets, n_utt, DT_SHIFT, tile_off);
-                if (C == 13)
-                    delta_rows_kernel<13><<<(int)blocks, 256, lds, st>>>(cep, bg, C, delta_n, inv_den, d_out, (int32_t)tiles, tile_off);
-                else
-                    delta_rows_kernel<0><<<(int)blocks, 256, lds, st>>>(cep, bg, C, delta_n, inv_den, d_out, (int32_t)tiles, tile_off);
-                if (hipGetLastError() != hipSuccess) rc = fail(DSP_EHIP, "delta_rows_kernel launch failed");
-            }
-            if (dsp_workspace_pool().release(w, st) != 0 && rc == DSP_OK) rc = fail(DSP_EHIP, "workspace release failed");
-            return rc;
-            }
-            // no scratch to be had (device memory exhausted, or `stream` is being captured into a HIP graph): the
-            // in-place form below needs none -- same values, 52-byte partial row writes instead of whole lines
-        }
-    }
-    int rc = dsp_features_batch(plan, d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt,
-                                n_frames_total, uniform_samples, DSP_OUT_MFCC, d_out, 3 * (int64_t)C, nullptr, stream);
-    if (rc != DSP_OK) return rc;
-    return dsp_delta_batch(d_out, 3 * (int64_t)C, d_frame_offsets, n_utt, n_frames_total, uniform_frames, C,
-                           delta_n, d_out + C, 3 * (int64_t)C, d_out + 2 * C, 3 * (int64_t)C, stream);
+    const int rc = mfcc_delta_via_scratch(plan, d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total,
+                                          uniform_samples, uniform_frames, delta_n, d_out, stream);
+    if (rc != 1) return rc;
+    return mfcc_delta_in_place(plan, d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total,
+                               uniform_samples, uniform_frames, delta_n, d_out, stream);
 }
 
 int dsp_scale_columns(float* d_x, int64_t rows, int32_t cols, const float* d_scale, void* stream) {
@@ -654,26 +810,6 @@ int dsp_scale_columns(float* d_x, int64_t rows, int32_t cols, const float* d_sca
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }
-
-}  // extern "C"
-
-// A batch shape's index tables, built once (include/dsp_frontend.h: dsp_layout).
-struct dsp_layout {
-    int32_t n_utt, frame_len, frame_step, shift;
-    int64_t n_frames_total;
-    int32_t* group_off;
-    int32_t* group_utt;
-    int32_t* group_off2;   // tables of the int16 VAD kernel's 8-frame groups, where it uses them (vad_scan_frames8)
-    int32_t* group_utt2;
-    int device;
-};
-
-static int vad_features_impl(const dsp_layout* layout, const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets,
-                             const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_frames_total,
-                             int64_t uniform_samples, int32_t frame_len, int32_t frame_step, int32_t use_sq,
-                             double* d_amp_sum, int32_t* d_zcr, void* stream);
-
-extern "C" {
 
 int dsp_layout_create(const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_frames_total, int32_t frame_len,
                       int32_t frame_step, void* stream, dsp_layout** out) {
@@ -721,9 +857,8 @@ int dsp_vad_features_layout_batch(const dsp_layout* layout, const void* d_wave, 
                                   const int64_t* d_sample_offsets, const int64_t* d_frame_offsets, int32_t use_sq,
                                   double* d_amp_sum, int32_t* d_zcr, void* stream) {
     if (!layout) return fail(DSP_EINVAL, "dsp_vad_features_layout_batch: layout is NULL");
-    int dev = -1;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev != layout->device) return fail(DSP_EINVAL, "layout belongs to device %d, current device is %d", layout->device, dev);
+    const int rc = check_owner_device(layout->device, false);
+    if (rc != DSP_OK) return rc;
     return vad_features_impl(layout, d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, layout->n_utt,
                              layout->n_frames_total, 0, layout->frame_len, layout->frame_step, use_sq, d_amp_sum, d_zcr,
                              stream);
@@ -737,83 +872,18 @@ int dsp_vad_features_batch(const void* d_wave, int wave_dtype, const int64_t* d_
                              uniform_samples, frame_len, frame_step, use_sq, d_amp_sum, d_zcr, stream);
 }
 
-}  // extern "C"
-
-static int vad_features_impl(const dsp_layout* layout, const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets,
-                             const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_frames_total,
-                             int64_t uniform_samples, int32_t frame_len, int32_t frame_step, int32_t use_sq,
-                             double* d_amp_sum, int32_t* d_zcr, void* stream) {
-    if (!d_amp_sum || !d_zcr) return fail(DSP_EINVAL, "dsp_vad_features_batch: NULL output");
-    if (frame_len <= 0 || frame_step <= 0) return fail(DSP_EINVAL, "frame_len/frame_step must be > 0");
-    int rc = check_geom(d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples);
-    if (rc != DSP_OK) return rc;
-    BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, frame_len, frame_step);
-    hipStream_t st = (hipStream_t)stream;
-    const int tile = vad_tile_frames(frame_len, frame_step);
-    if (!g_force_generic && tile != 0) {
-        BatchGeom fg = bg;
-        const void* fw = d_wave;
-        DspWorkspace* view = fused_kernel_view(fg, fw, wave_dtype, st);
-        const bool ok = vad_tile_applicable(fg, fw, wave_dtype, tile);
-        DspRaggedTables pre;
-        const bool have_pre = layout != nullptr && layout->group_off != nullptr && view == nullptr;
-        if (have_pre) {
-            pre.shift = layout->shift; pre.group_off = layout->group_off; pre.group_utt = layout->group_utt;
-            if (layout->group_off2 != nullptr) { pre.shift2 = 3; pre.group_off2 = layout->group_off2; pre.group_utt2 = layout->group_utt2; }
-        }
-        if (ok) rc = vad_tile_launch(tile, frame_len, frame_step, use_sq, fg, fw, wave_dtype, d_amp_sum, d_zcr, st,
-                                     have_pre ? &pre : nullptr);
-        if (view && dsp_workspace_pool().release(view, st) != 0 && ok && rc == DSP_OK) rc = DSP_EHIP;
-        if (ok) {
-            if (rc != DSP_OK) return fail(rc, "vad tile kernel launch failed");
-            return DSP_OK;
-        }
-    }
-    const int grid = grid_for(n_frames_total, 4);
-    if (wave_dtype == DSP_WAVE_I16)
-        vad_features_kernel<DSP_WAVE_I16><<<grid, 256, 0, st>>>(d_wave, bg, frame_len, frame_step, use_sq, d_amp_sum, d_zcr);
-    else
-        vad_features_kernel<DSP_WAVE_F32><<<grid, 256, 0, st>>>(d_wave, bg, frame_len, frame_step, use_sq, d_amp_sum, d_zcr);
-    HIP_TRY(hipGetLastError());
-    return DSP_OK;
-}
-
-extern "C" {
-
 int dsp_trim_scale_batch(const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets,
                          const int64_t* d_segments, const int64_t* d_dst_offsets, int32_t n_utt,
                          int32_t unit_variance, float* d_out, void* stream) {
     if (!d_wave || !d_sample_offsets || !d_segments || !d_dst_offsets || !d_out || n_utt <= 0)
         return fail(DSP_EINVAL, "dsp_trim_scale_batch: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    if (wave_dtype == DSP_WAVE_I16)
-        trim_scale_kernel<DSP_WAVE_I16><<<n_utt, 256, 0, st>>>(d_wave, d_sample_offsets, d_segments, d_dst_offsets, unit_variance, d_out);
-    else if (wave_dtype == DSP_WAVE_F32)
-        trim_scale_kernel<DSP_WAVE_F32><<<n_utt, 256, 0, st>>>(d_wave, d_sample_offsets, d_segments, d_dst_offsets, unit_variance, d_out);
-    else
-        return fail(DSP_EINVAL, "unsupported wave_dtype %d", wave_dtype);
+    if (wave_dtype != DSP_WAVE_I16 && wave_dtype != DSP_WAVE_F32) return fail(DSP_EINVAL, "unsupported wave_dtype %d", wave_dtype);
+    dsp_dispatch_wave(wave_dtype, [&](auto dt) {
+        trim_scale_kernel<decltype(dt)::value><<<n_utt, 256, 0, (hipStream_t)stream>>>(d_wave, d_sample_offsets, d_segments, d_dst_offsets, unit_variance, d_out);
+    });
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }
-
-namespace {
-struct SegWork {
-    size_t stats, tile, goff, gutt, tutt, cep, total;
-};
-// layout of the caller-owned work buffer of dsp_mfcc_delta_segments_batch (every part 256-byte aligned)
-SegWork seg_work_layout(int32_t n_utt, int64_t n_frames_bound, int32_t C) {
-    auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
-    SegWork w;
-    w.stats = 0;
-    w.tile = w.stats + pad((size_t)n_utt * 2 * sizeof(double));
-    w.goff = w.tile + pad(((size_t)n_utt + 1) * sizeof(int64_t));
-    w.gutt = w.goff + pad(((size_t)n_utt + 1) * sizeof(int32_t));
-    w.tutt = w.gutt + pad(((size_t)(n_frames_bound >> 2) + (size_t)n_utt) * sizeof(int32_t));   // 4-frame groups (NFFT = 1536) at most
-    w.cep = w.tutt + pad(((size_t)(n_frames_bound >> DT_SHIFT) + (size_t)n_utt) * sizeof(int32_t));
-    w.total = w.cep + pad((size_t)n_frames_bound * (size_t)C * sizeof(float));
-    return w;
-}
-}  // namespace
 
 int dsp_segments_workspace_bytes(const dsp_plan* plan, int32_t n_utt, int64_t n_frames_bound, size_t* bytes) {
     if (!plan || !bytes || n_utt <= 0 || n_frames_bound <= 0) return fail(DSP_EINVAL, "dsp_segments_workspace_bytes: bad arguments");
@@ -831,20 +901,16 @@ int dsp_mfcc_delta_segments_batch(const dsp_plan* plan, const void* d_wave, int 
     if (delta_n < 0) return fail(DSP_EINVAL, "N must be an integer >= 1 (or 0: cepstra only)");  // base.py:71-72
     int rc = check_geom(d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt, n_frames_bound, 0);
     if (rc != DSP_OK) return rc;
-    {
-        int dev = -1;
-        HIP_TRY(hipGetDevice(&dev));
-        if (dev != plan->device) return fail(DSP_EINVAL, "plan belongs to device %d, current device is %d", plan->device, dev);
-    }
+    rc = check_owner_device(plan->device, true);
+    if (rc != DSP_OK) return rc;
     const int C = plan->C;
-    const size_t lds = ((size_t)(DT_TILE + 4 * delta_n) + (size_t)(DT_TILE + 2 * delta_n)) * C * sizeof(float);
     BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_bound, 0, plan->L, plan->S);
     // Served by the NFFT = 512 and NFFT = 1536 kernels on buffers they can read in place; everything else (and unit
     // variance without appendEnergy, where the scaling does not reduce to a shift of c0) reports 1: "use the
     // trimmed-copy path".
     const bool k512 = plan->d_fast && fast512_applicable(plan, bg, d_wave, wave_dtype);
     const bool k1536 = !k512 && plan->d_fast1536 && fast1536_applicable(plan, bg, d_wave, wave_dtype);
-    if (g_force_generic || (!k512 && !k1536) || C <= 0 || lds > 64 * 1024 ||
+    if (g_force_generic || (!k512 && !k1536) || C <= 0 || delta_tile_lds(delta_n, C) > 64 * 1024 ||
         (unit_variance && !plan->append_energy) || (n_frames_bound >> 2) + n_utt > 0x3fffffff)
         return 1;
     const SegWork w = seg_work_layout(n_utt, n_frames_bound, C);
@@ -868,22 +934,13 @@ int dsp_mfcc_delta_segments_batch(const dsp_plan* plan, const void* d_wave, int 
               : fast1536_launch(plan, d_wave, wave_dtype, bg, cep, (int64_t)C, st, &pre);
     if (rc != DSP_OK) return fail(rc < 0 ? rc : DSP_EHIP, "fused kernel launch failed");
     if (delta_n == 0) return DSP_OK;    // (unit variance: c0 still lacks -ln(var); dsp_model_finalize_segments_batch applies it)
-    BatchGeom dg;
-    memset(&dg, 0, sizeof(dg));
-    dg.frame_off = d_frame_offsets;
-    dg.total_frames = n_frames_bound;
-    dg.n_utt = n_utt;
-    int den = 0;
-    for (int i = 1; i <= delta_n; ++i) den += i * i;
-    const float inv_den = (float)(1.0 / (2.0 * den));
-    const int64_t blocks = n_frames_bound / DT_TILE + n_utt;
+    int64_t tiles;
+    const int64_t blocks = delta_tile_blocks(0, n_frames_bound, n_utt, &tiles);
     if (blocks > 0x7fffffff) return fail(DSP_EINVAL, "too many delta tiles");
     // (the tile -> utterance table exists only when the layout kernel built the tables)
     const int32_t* tile_utt = (flags & DSP_SEG_TABLES_READY) ? reinterpret_cast<const int32_t*>(wp + w.tutt) : nullptr;
-    if (C == 13)
-        delta_rows_kernel<13><<<(int)blocks, 256, lds, st>>>(cep, dg, C, delta_n, inv_den, d_out, 0, tile_off, d_segments, stats, tile_utt);
-    else
-        delta_rows_kernel<0><<<(int)blocks, 256, lds, st>>>(cep, dg, C, delta_n, inv_den, d_out, 0, tile_off, d_segments, stats, tile_utt);
+    launch_delta_rows(blocks, st, cep, frames_geom(d_frame_offsets, n_utt, n_frames_bound, 0), C, delta_n, d_out, tiles, tile_off,
+                      d_segments, stats, tile_utt);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }
@@ -892,7 +949,7 @@ int dsp_endpoint_layout_batch(const int32_t* d_endpoints, const int64_t* d_sampl
                               double cfg_step, double rate, int32_t frame_len, int32_t frame_step,
                               const int64_t* d_jitter, int64_t* d_segments, int64_t* d_dst_offsets,
                               int64_t* d_frame_offsets, void* stream) {
-    if (!d_endpoints || !d_sample_offsets || !d_segments || !d_dst_offsets || !d_frame_offsets || n_utt <= 0)
+    if (!endpoint_layout_args_ok(d_endpoints, d_sample_offsets, d_segments, d_dst_offsets, d_frame_offsets, n_utt))
         return fail(DSP_EINVAL, "dsp_endpoint_layout_batch: bad arguments");
     if (!(cfg_step > 0.0) || !(rate > 0.0) || frame_len <= 0 || frame_step <= 0)
         return fail(DSP_EINVAL, "dsp_endpoint_layout_batch: step, rate, frame_len, frame_step must be > 0");
@@ -907,7 +964,7 @@ int dsp_endpoint_layout_segments_batch(const int32_t* d_endpoints, const int64_t
                                        double cfg_step, double rate, const int64_t* d_jitter, int64_t* d_segments,
                                        int64_t* d_dst_offsets, int64_t* d_frame_offsets, const dsp_plan* plan,
                                        int64_t n_frames_bound, void* d_work, size_t work_bytes, void* stream) {
-    if (!d_endpoints || !d_sample_offsets || !d_segments || !d_dst_offsets || !d_frame_offsets || !plan || !d_work || n_utt <= 0)
+    if (!endpoint_layout_args_ok(d_endpoints, d_sample_offsets, d_segments, d_dst_offsets, d_frame_offsets, n_utt) || !plan || !d_work)
         return fail(DSP_EINVAL, "dsp_endpoint_layout_segments_batch: bad arguments");
     if (!(cfg_step > 0.0) || !(rate > 0.0) || n_frames_bound <= 0)
         return fail(DSP_EINVAL, "dsp_endpoint_layout_segments_batch: step, rate, n_frames_bound must be > 0");
@@ -930,16 +987,7 @@ int dsp_model_finalize_batch(const float* d_mfcc, int64_t ld_in, const int64_t* 
                              int32_t C, int32_t N, int32_t max_len, float* d_out, int32_t* d_len0, void* stream) {
     if (!d_mfcc || !d_frame_offsets || !d_out || !d_len0 || n_utt <= 0)
         return fail(DSP_EINVAL, "dsp_model_finalize_batch: bad arguments");
-    if (N < 1) return fail(DSP_EINVAL, "N must be an integer >= 1");  // base.py:71-72
-    if (C <= 0 || C > 32 || max_len <= 0) return fail(DSP_EINVAL, "need 0 < C <= 32 and max_len > 0");
-    if (ld_in == 0) ld_in = C;
-    if (ld_in < C) return fail(DSP_EINVAL, "ld_in %lld < C %d", (long long)ld_in, C);
-    const size_t lds = ((size_t)(max_len + 2 * N) + (size_t)(max_len + N)) * C * sizeof(float);
-    if (lds > 64 * 1024) return fail(DSP_EINVAL, "max_len * C too large for the LDS tile (%zu bytes)", lds);
-    model_finalize_kernel<<<n_utt, 256, lds, (hipStream_t)stream>>>(d_mfcc, ld_in, d_frame_offsets, n_utt, C, N,
-                                                                   max_len, d_out, d_len0);
-    HIP_TRY(hipGetLastError());
-    return DSP_OK;
+    return model_finalize_impl(d_mfcc, ld_in, d_frame_offsets, n_utt, C, N, max_len, d_out, d_len0, nullptr, nullptr, stream);
 }
 
 int dsp_model_finalize_segments_batch(const float* d_mfcc, int64_t ld_in, const int64_t* d_frame_offsets,
@@ -947,17 +995,9 @@ int dsp_model_finalize_segments_batch(const float* d_mfcc, int64_t ld_in, const 
                                       int32_t max_len, float* d_out, int32_t* d_len0, void* stream) {
     if (!d_mfcc || !d_frame_offsets || !d_segments || !d_work || !d_out || !d_len0 || n_utt <= 0)
         return fail(DSP_EINVAL, "dsp_model_finalize_segments_batch: bad arguments");
-    if (N < 1) return fail(DSP_EINVAL, "N must be an integer >= 1");  // base.py:71-72
-    if (C <= 0 || C > 32 || max_len <= 0) return fail(DSP_EINVAL, "need 0 < C <= 32 and max_len > 0");
-    if (ld_in == 0) ld_in = C;
-    if (ld_in < C) return fail(DSP_EINVAL, "ld_in %lld < C %d", (long long)ld_in, C);
-    const size_t lds = ((size_t)(max_len + 2 * N) + (size_t)(max_len + N)) * C * sizeof(float);
-    if (lds > 64 * 1024) return fail(DSP_EINVAL, "max_len * C too large for the LDS tile (%zu bytes)", lds);
     // the statistics sit at the start of the work buffer of dsp_mfcc_delta_segments_batch (seg_work_layout)
-    model_finalize_kernel<<<n_utt, 256, lds, (hipStream_t)stream>>>(d_mfcc, ld_in, d_frame_offsets, n_utt, C, N, max_len, d_out, d_len0,
-                                                                   d_segments, static_cast<const double*>(d_work));
-    HIP_TRY(hipGetLastError());
-    return DSP_OK;
+    return model_finalize_impl(d_mfcc, ld_in, d_frame_offsets, n_utt, C, N, max_len, d_out, d_len0, d_segments,
+                               static_cast<const double*>(d_work), stream);
 }
 
 int dsp_model_timefeat_batch(const double* d_amp_sum, const int64_t* d_frame_offsets, int32_t n_utt,
@@ -1022,13 +1062,7 @@ int dsp_endpoint_rule_batch(const double* d_amp_sum, const int32_t* d_zcr, const
                             int32_t* d_endpoints, void* stream) {
     if (!d_amp_sum || !d_zcr || !d_frame_offsets || !d_endpoints || n_utt <= 0 || frame_len <= 0)
         return fail(DSP_EINVAL, "dsp_endpoint_rule_batch: bad arguments");
-    if (!(cfg_frame > 0.0) || !(cfg_step > 0.0)) return fail(DSP_EINVAL, "cfg.frame / cfg.step must be > 0");
-    if (2 * (int)(0.100 / cfg_step) > DSP_MAX_SIL)
-        return fail(DSP_EINVAL, "cfg.step %g gives a silence window > %d frames", cfg_step, DSP_MAX_SIL);
-    endpoint_rule_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(
-        d_amp_sum, d_zcr, d_frame_offsets, n_utt, frame_len, cfg_frame, cfg_step, d_endpoints);
-    HIP_TRY(hipGetLastError());
-    return DSP_OK;
+    return endpoint_rule_impl(d_amp_sum, d_zcr, nullptr, d_frame_offsets, n_utt, frame_len, cfg_frame, cfg_step, d_endpoints, stream);
 }
 
 int dsp_acr_gate_batch(const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets,
@@ -1044,16 +1078,14 @@ int dsp_acr_gate_batch(const void* d_wave, int wave_dtype, const int64_t* d_samp
     int rc = check_geom(d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples);
     if (rc != DSP_OK) return rc;
     BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, frame_len, frame_step);
-    if (uniform_samples > 0 && bg.uniform_frames * n_utt != n_frames_total)
-        return fail(DSP_EINVAL, "n_frames_total %lld != n_utt*T (%d*%lld)", (long long)n_frames_total, n_utt, (long long)bg.uniform_frames);
+    if (uniform_samples > 0 && (rc = check_dense_frames(n_frames_total, n_utt, bg.uniform_frames)) != DSP_OK) return rc;
     if (n_frames_total <= 0) return DSP_OK;
     const int64_t blocks = (n_frames_total + 3) / 4;
     if (blocks > 0x7fffffff) return fail(DSP_EINVAL, "too many frames");
     hipStream_t st = (hipStream_t)stream;
-    if (wave_dtype == DSP_WAVE_I16)
-        acr_gate_kernel<DSP_WAVE_I16><<<(int)blocks, 256, lds, st>>>(d_wave, bg, frame_len, frame_step, lag_lo, lag_hi, thresh, d_voiced);
-    else
-        acr_gate_kernel<DSP_WAVE_F32><<<(int)blocks, 256, lds, st>>>(d_wave, bg, frame_len, frame_step, lag_lo, lag_hi, thresh, d_voiced);
+    dsp_dispatch_wave(wave_dtype, [&](auto dt) {
+        acr_gate_kernel<decltype(dt)::value><<<(int)blocks, 256, lds, st>>>(d_wave, bg, frame_len, frame_step, lag_lo, lag_hi, thresh, d_voiced);
+    });
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }
@@ -1063,13 +1095,7 @@ int dsp_endpoint_rule_acr_batch(const double* d_amp_sum, const int32_t* d_zcr, c
                                 double cfg_step, int32_t* d_endpoints, void* stream) {
     if (!d_amp_sum || !d_zcr || !d_voiced || !d_frame_offsets || !d_endpoints || n_utt <= 0 || frame_len <= 0)
         return fail(DSP_EINVAL, "dsp_endpoint_rule_acr_batch: bad arguments");
-    if (!(cfg_frame > 0.0) || !(cfg_step > 0.0)) return fail(DSP_EINVAL, "cfg.frame / cfg.step must be > 0");
-    if (2 * (int)(0.100 / cfg_step) > DSP_MAX_SIL)
-        return fail(DSP_EINVAL, "cfg.step %g gives a silence window > %d frames", cfg_step, DSP_MAX_SIL);
-    endpoint_rule_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(
-        d_amp_sum, d_zcr, d_frame_offsets, n_utt, frame_len, cfg_frame, cfg_step, d_endpoints, d_voiced);
-    HIP_TRY(hipGetLastError());
-    return DSP_OK;
+    return endpoint_rule_impl(d_amp_sum, d_zcr, d_voiced, d_frame_offsets, n_utt, frame_len, cfg_frame, cfg_step, d_endpoints, stream);
 }
 
 int dsp_resample_layout_batch(const int64_t* d_src_offsets, int32_t n_utt, int64_t src_rate, int64_t dst_rate,
@@ -1122,58 +1148,39 @@ int dsp_pitch_cepstrum_batch(const float* d_sig, const int64_t* d_sample_offsets
                              int32_t frame_step, const float* d_taps, int32_t center_clip, float* d_rows, double* d_amp,
                              void* stream) {
     if (!d_taps || !d_rows) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_batch: NULL taps/output");
-    if (frame_len < 128 || frame_len > 1024 || (frame_len & (frame_len - 1)) != 0)
+    if (!cepstrum_frame_len_ok(frame_len))
         return fail(DSP_EINVAL, "dsp_pitch_cepstrum_batch: frame_len %d is not a power of two in [128, 1024]", frame_len);
     if (frame_step <= 0) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_batch: frame_step must be > 0");
     int rc = check_geom(d_sig, DSP_WAVE_F32, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples);
     if (rc != DSP_OK) return rc;
     if (n_frames_total > 0x7fffffff) return fail(DSP_EINVAL, "too many frames for one launch");
     BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, frame_len, frame_step);
-    if (uniform_samples > 0 && bg.uniform_frames * n_utt != n_frames_total)
-        return fail(DSP_EINVAL, "n_frames_total %lld != n_utt*T (%d*%lld)", (long long)n_frames_total, n_utt, (long long)bg.uniform_frames);
+    if (uniform_samples > 0 && (rc = check_dense_frames(n_frames_total, n_utt, bg.uniform_frames)) != DSP_OK) return rc;
     const float2* tp = reinterpret_cast<const float2*>(d_taps);
     const int grid = (int)n_frames_total, clip = center_clip ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
-    switch (frame_len) {
-        case 128: pitch_cepstrum_kernel<128><<<grid, 64, 0, st>>>(d_sig, bg, frame_step, tp, clip, d_rows, d_amp); break;
-        case 256: pitch_cepstrum_kernel<256><<<grid, 64, 0, st>>>(d_sig, bg, frame_step, tp, clip, d_rows, d_amp); break;
-        case 512: pitch_cepstrum_kernel<512><<<grid, 64, 0, st>>>(d_sig, bg, frame_step, tp, clip, d_rows, d_amp); break;
-        default: pitch_cepstrum_kernel<1024><<<grid, 64, 0, st>>>(d_sig, bg, frame_step, tp, clip, d_rows, d_amp); break;
-    }
+    dispatch_cepstrum_frame_len(frame_len, [&](auto len) {
+        pitch_cepstrum_kernel<decltype(len)::value><<<grid, 64, 0, st>>>(d_sig, bg, frame_step, tp, clip, d_rows, d_amp);
+    });
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }
 
-}  // extern "C"
-
-namespace {
-template <typename RT>
-void launch_cepstrum_track(const void* d_rows, const int64_t* d_frame_offsets, int32_t n_utt, int32_t frame_len,
-                                  int32_t flags, double* d_pitch, int32_t* d_scores, hipStream_t st) {
-    const RT* r = reinterpret_cast<const RT*>(d_rows);
-    switch (frame_len) {
-        case 128: pitch_cepstrum_track_kernel<RT, 128><<<n_utt, 64, 0, st>>>(r, d_frame_offsets, flags, d_pitch, d_scores); break;
-        case 256: pitch_cepstrum_track_kernel<RT, 256><<<n_utt, 64, 0, st>>>(r, d_frame_offsets, flags, d_pitch, d_scores); break;
-        case 512: pitch_cepstrum_track_kernel<RT, 512><<<n_utt, 64, 0, st>>>(r, d_frame_offsets, flags, d_pitch, d_scores); break;
-        default: pitch_cepstrum_track_kernel<RT, 1024><<<n_utt, 64, 0, st>>>(r, d_frame_offsets, flags, d_pitch, d_scores); break;
-    }
-}
-}  // namespace
-
-extern "C" {
-
 int dsp_pitch_cepstrum_track_batch(const void* d_rows, int32_t rows_f64, const int64_t* d_frame_offsets, int32_t n_utt,
                                    int32_t frame_len, int32_t flags, double* d_pitch, int32_t* d_scores, void* stream) {
     if (!d_rows || !d_frame_offsets || n_utt <= 0) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: bad arguments");
-    if (frame_len < 128 || frame_len > 1024 || (frame_len & (frame_len - 1)) != 0)
+    if (!cepstrum_frame_len_ok(frame_len))
         return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: frame_len %d is not a power of two in [128, 1024]", frame_len);
     if ((flags & ~3) != 0) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: unknown flags %d", flags);
     if ((flags & 2) && !d_pitch) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: d_pitch is NULL");
     if (!(flags & 2) && !d_scores) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: nothing to write (no arg-max, d_scores is NULL)");
-    if (rows_f64)
-        launch_cepstrum_track<double>(d_rows, d_frame_offsets, n_utt, frame_len, flags, d_pitch, d_scores, (hipStream_t)stream);
-    else
-        launch_cepstrum_track<float>(d_rows, d_frame_offsets, n_utt, frame_len, flags, d_pitch, d_scores, (hipStream_t)stream);
+    dispatch_cepstrum_frame_len(frame_len, [&](auto len) {
+        auto launch = [&](auto row) {   // row: a value of the rows' element type
+            pitch_cepstrum_track_kernel<decltype(row), decltype(len)::value><<<n_utt, 64, 0, (hipStream_t)stream>>>(
+                static_cast<const decltype(row)*>(d_rows), d_frame_offsets, flags, d_pitch, d_scores);
+        };
+        if (rows_f64) launch(double()); else launch(float());
+    });
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }

@@ -761,17 +761,7 @@ static inline void fast1536_plan_free(dsp_plan* p) {
     p->d_fast1536 = nullptr;
 }
 
-static inline bool fast1536_applicable(const dsp_plan* p, const BatchGeom& bg, const void* d_wave, int dtype) {
-    if (!p->d_fast1536) return false;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_wave);
-    if ((a % (dtype == DSP_WAVE_I16 ? 8 : 16)) != 0) return false;
-    if (bg.uniform_samples > 0) {
-        if ((bg.uniform_samples % 4) != 0) return false;
-        return bg.uniform_samples <= 0x3fffffff && ((bg.uniform_frames + 3) / 4) * bg.n_utt <= 0x3fffffff;
-    }
-    return bg.total_frames / 4 + bg.n_utt <= 0x3fffffff;
-}
-
+// (which batches the kernel can read: fast1536_applicable, dsp_frontend.hip)
 template <int NI, int NC, int NSTAGE, int DTYPE, bool RAGGED>
 static int fast1536_launch_k(const F1536Params& P, const void* d_wave, const BatchGeom& bg, float* d_out,
                              int64_t ld_out, int64_t groups_bound, hipStream_t st) {
@@ -792,32 +782,17 @@ static int fast1536_launch_t(F1536Params P, const void* d_wave, int dtype, const
     if (bg.uniform_samples > 0) {
         P.groups_per_utt = (bg.uniform_frames + 3) / 4;
         P.total_groups = P.groups_per_utt * bg.n_utt;
-        if (dtype == DSP_WAVE_I16)
-            return fast1536_launch_k<NI, NC, NSTAGE, DSP_WAVE_I16, false>(P, d_wave, bg, d_out, ld_out, P.total_groups, st);
-        return fast1536_launch_k<NI, NC, NSTAGE, DSP_WAVE_F32, false>(P, d_wave, bg, d_out, ld_out, P.total_groups, st);
+        return dsp_dispatch_wave(dtype, [&](auto dt) {
+            return fast1536_launch_k<NI, NC, NSTAGE, decltype(dt)::value, false>(P, d_wave, bg, d_out, ld_out, P.total_groups, st);
+        });
     }
     const int64_t bound = bg.total_frames / 4 + bg.n_utt;  // >= sum ceil(T_b / 4)
-    DspWorkspace* w = nullptr;
-    if (pre != nullptr && pre->shift == 2) {
-        P.group_off = pre->group_off;
-        P.group_utt = pre->group_utt;
-    } else {
-        const size_t ws_bytes = ((size_t)bg.n_utt + 1 + (size_t)bound) * sizeof(int32_t);
-        w = dsp_workspace_pool().acquire(ws_bytes, st);
-        if (!w) return DSP_EHIP;
-        int32_t* group_off = static_cast<int32_t*>(w->ptr);
-        int32_t* group_utt = group_off + bg.n_utt + 1;
-        f512_build_group_tables(bg.frame_off, bg.n_utt, 2, group_off, group_utt, st);
-        P.group_off = group_off;
-        P.group_utt = group_utt;
-    }
-    int rc;
-    if (dtype == DSP_WAVE_I16)
-        rc = fast1536_launch_k<NI, NC, NSTAGE, DSP_WAVE_I16, true>(P, d_wave, bg, d_out, ld_out, bound, st);
-    else
-        rc = fast1536_launch_k<NI, NC, NSTAGE, DSP_WAVE_F32, true>(P, d_wave, bg, d_out, ld_out, bound, st);
-    if (w != nullptr && dsp_workspace_pool().release(w, st) != 0 && rc == DSP_OK) rc = DSP_EHIP;
-    return rc;
+    DspWorkspace* w;
+    if (!dsp_ragged_tables_acquire(P, pre, 2, bg, bound, st, w)) return DSP_EHIP;
+    const int rc = dsp_dispatch_wave(dtype, [&](auto dt) {
+        return fast1536_launch_k<NI, NC, NSTAGE, decltype(dt)::value, true>(P, d_wave, bg, d_out, ld_out, bound, st);
+    });
+    return dsp_ragged_tables_release(w, st, rc);
 }
 
 static inline int fast1536_launch(const dsp_plan* p, const void* d_wave, int dtype, const BatchGeom& bg,

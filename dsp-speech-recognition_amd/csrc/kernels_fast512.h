@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "dsp_common.h"
-#include "workspace.h"
+#include "launch_common.h"
 #include "fft_inreg.h"
 
 #define F512_WAVE_FLOATS 2112  // per-wave LDS: 8 frames x 264 floats (staging / exchange alias it)
@@ -1175,90 +1175,6 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
 #endif
 }
 
-// Ragged batches: group_off[b] = sum_{i<b} ceil(T_i / 2^shift) (exclusive prefix, single block), then the
-// utterance of every group.  Both are tiny next to the main kernel and run on the same stream.
-__global__ __launch_bounds__(1024) void f512_group_prefix_kernel(const int64_t* __restrict__ frame_off, int32_t n_utt,
-                                                                 int32_t shift, int32_t* __restrict__ group_off,
-                                                                 int32_t* __restrict__ group_utt = nullptr,
-                                                                 int32_t tile_shift = 0,
-                                                                 int64_t* __restrict__ tile_off = nullptr,
-                                                                 double* __restrict__ zero_stats = nullptr) {
-    // optional second table in the same launch: tile_off[b] = sum_{i<b} ceil(T_i / 2^tile_shift) (the delta pass)
-    __shared__ int32_t wsum[16], wsum_t[16];
-    const int tid = threadIdx.x;
-    const int per = (n_utt + 1023) / 1024;
-    const int lo = tid * per, hi = min(lo + per, n_utt);
-    const int64_t rnd = ((int64_t)1 << shift) - 1, rnd_t = ((int64_t)1 << tile_shift) - 1;
-    int32_t sum = 0, sum_t = 0;
-    for (int b = lo; b < hi; ++b) {
-        const int64_t T = frame_off[b + 1] - frame_off[b];
-        sum += (int32_t)((T + rnd) >> shift);
-        sum_t += (int32_t)((T + rnd_t) >> tile_shift);
-        if (zero_stats != nullptr) { zero_stats[2 * b] = 0.0; zero_stats[2 * b + 1] = 0.0; }
-    }
-    // inclusive scan of the per-thread sums: inside each wave with shuffles, across the 16 waves through LDS
-    int32_t inc = sum, inc_t = sum_t;
-    const int lane = tid & 63, w = tid >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int32_t v = __shfl_up(inc, off, 64), vt = __shfl_up(inc_t, off, 64);
-        if (lane >= off) { inc += v; inc_t += vt; }
-    }
-    if (lane == 63) { wsum[w] = inc; wsum_t[w] = inc_t; }
-    __syncthreads();
-    int32_t before = 0, before_t = 0, total = 0, total_t = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int32_t a = wsum[k], at = wsum_t[k];
-        if (k < w) { before += a; before_t += at; }
-        total += a;
-        total_t += at;
-    }
-    inc += before;
-    inc_t += before_t;
-    int32_t run = inc - sum;
-    int64_t run_t = inc_t - sum_t;
-    for (int b = lo; b < hi; ++b) {
-        group_off[b] = run;
-        const int64_t T = frame_off[b + 1] - frame_off[b];
-        const int32_t n = (int32_t)((T + rnd) >> shift);
-        if (group_utt != nullptr)   // small batches: fill the group -> utterance table in the same launch
-            for (int32_t g = 0; g < n; ++g) group_utt[run + g] = b;
-        run += n;
-        if (tile_off != nullptr) {
-            tile_off[b] = run_t;
-            run_t += (T + rnd_t) >> tile_shift;
-        }
-    }
-    if (tid == 1023) {
-        group_off[n_utt] = total;
-        if (tile_off != nullptr) tile_off[n_utt] = total_t;
-    }
-}
-
-// Builds both ragged index tables on `st`: one launch for small batches, prefix + parallel fill otherwise.
-static inline void f512_build_group_tables(const int64_t* frame_off, int32_t n_utt, int32_t shift,
-                                           int32_t* group_off, int32_t* group_utt, hipStream_t st,
-                                           int64_t* tile_off = nullptr, double* zero_stats = nullptr);
-
-__global__ __launch_bounds__(256) void f512_group_fill_kernel(const int32_t* __restrict__ group_off, int32_t n_utt,
-                                                              int32_t* __restrict__ group_utt) {
-    for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < n_utt; b += gridDim.x * blockDim.x)
-        for (int g = group_off[b]; g < group_off[b + 1]; ++g) group_utt[g] = b;
-}
-
-static inline void f512_build_group_tables(const int64_t* frame_off, int32_t n_utt, int32_t shift,
-                                           int32_t* group_off, int32_t* group_utt, hipStream_t st,
-                                           int64_t* tile_off, double* zero_stats) {
-    if (n_utt <= 4096) {
-        f512_group_prefix_kernel<<<1, 1024, 0, st>>>(frame_off, n_utt, shift, group_off, group_utt, DT_SHIFT, tile_off, zero_stats);
-        return;
-    }
-    f512_group_prefix_kernel<<<1, 1024, 0, st>>>(frame_off, n_utt, shift, group_off, nullptr, DT_SHIFT, tile_off, zero_stats);
-    const int fill_blocks = (int)((n_utt + 255) / 256 < 1024 ? (n_utt + 255) / 256 : 1024);
-    f512_group_fill_kernel<<<fill_blocks, 256, 0, st>>>(group_off, n_utt, group_utt);
-}
-
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
@@ -1298,9 +1214,6 @@ static inline int fast512_plan_init(dsp_plan* p, const dsp_plan_desc* d, const i
     if (nrows <= 25 && ni_real <= 4 && nstage <= 6) { variant = 0; NI = 4; }
     else if (nrows <= 25 && ni_real <= 5 && nstage <= 6) { variant = 1; NI = 5; }
     else { variant = 2; NI = F512_MAX_NI; }
-    if (const char* fv = getenv("DSP_F512_FORCE_CATCHALL")) {  // debugging aid: run any plan on the catch-all instantiation
-        if (fv[0] == '1') { variant = 2; NI = F512_MAX_NI; }
-    }
     std::vector<float> win(512, 0.f);
     for (int n = 0; n < L; ++n) win[n] = d->h_window[n];
 #ifdef F512_COOP
@@ -1392,9 +1305,6 @@ static inline int fast512_plan_init(dsp_plan* p, const dsp_plan_desc* d, const i
         fp->P.nb4[i] = (len + 3) / 4;
         if (caps != 0 && fp->P.nb4[i] > f512_cap(caps, i)) caps = 0;
     }
-    if (const char* fc = getenv("DSP_F512_NOCAPS")) {  // A/B aid: run-time block counts for every plan
-        if (fc[0] == '1') caps = 0;
-    }
     for (int i = 0; i < NI; ++i) {
         if (caps != 0) fp->P.nb4[i] = f512_cap(caps, i);
         row_blocks += fp->P.nb4[i];
@@ -1463,53 +1373,21 @@ static inline void fast512_plan_free(dsp_plan* p) {
     p->d_fast = nullptr;
 }
 
-// The fast kernel serves (a) dense batches with N % 4 == 0 and (b) ragged batches (any lengths and
-// offsets); the buffer itself must start 16-byte aligned (8 for int16) either way.
-static inline bool fast512_applicable(const dsp_plan* p, const BatchGeom& bg, const void* d_wave, int dtype) {
-    if (!p->d_fast) return false;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_wave);
-    if ((a % (dtype == DSP_WAVE_I16 ? 8 : 16)) != 0) return false;
-    if (bg.uniform_samples > 0) {
-        if ((bg.uniform_samples % 4) != 0) return false;
-        return bg.uniform_samples <= 0x3fffffff && ((bg.uniform_frames + 7) / 8) * bg.n_utt <= 0x3fffffff;  // 32-bit indexing
-    }
-    return bg.total_frames / 8 + bg.n_utt <= 0x3fffffff;
-}
-
+// (which batches the kernel can read: fast512_applicable, dsp_frontend.hip)
 template <int NROWS, int NI, int CAPS, int NSTAGE, int DTYPE, bool RAGGED>
 static int fast512_launch_k(const F512Params& P, const void* d_wave, const BatchGeom& bg, float* d_out,
                             int64_t ld_out, int64_t groups_bound, hipStream_t st) {
     const size_t lds = ((size_t)P.tab_floats + (size_t)F512_WAVES * F512_WAVE_FLOATS) * sizeof(float);
-    // balanced persistent grid: every wave runs the same number of groups (no ragged last round)
+    // persistent grid
     const int64_t cap = (int64_t)dsp_cu_count() * (16 / F512_WAVES);  // CUs x resident workgroups (<= 16 waves per CU)
     int64_t blocks = (groups_bound + F512_WAVES - 1) / F512_WAVES;
-    static const int grid_mode = [] { const char* e = getenv("DSP_F512_GRID"); return e ? atoi(e) : 1; }();
-    if (blocks > cap) {
-        if (grid_mode == 0) {   // every wave the same number of groups (fewer, fuller workgroups)
-            const int64_t rounds = (blocks + cap - 1) / cap;
-            blocks = (blocks + rounds - 1) / rounds;
-        } else {
-            blocks = cap;       // every CU fully occupied; the partial last round is dealt wave-major
-        }
-    }
+    if (blocks > cap) blocks = cap;       // every CU fully occupied; the partial last round is dealt wave-major
     auto k = mfcc512_kernel<NROWS, NI, CAPS, NSTAGE, DTYPE, F512_WAVES, RAGGED>;
     static size_t granted[DSP_MAX_DEVICES] = {};  // dynamic-LDS limit already raised, per device
     if (dsp_ensure_dynamic_lds((const void*)k, lds, granted) != 0) return DSP_EHIP;
     k<<<(int)blocks, 64 * F512_WAVES, lds, st>>>(P, bg, d_wave, d_out, ld_out);
     return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
 }
-
-// Ragged index tables built by the caller in one launch together with its own (dsp_mfcc_delta_batch).
-struct DspRaggedTables {
-    int32_t* group_off = nullptr;   // [n_utt + 1] prefix of ceil(T_b / 2^shift)
-    int32_t* group_utt = nullptr;   // utterance of every group
-    int shift = 0;                  // 3: NFFT=512 kernel (8 frames per wave), 2: NFFT=1536 kernel
-    // a second set for another group size (a dsp_layout holds the tables of the int16 VAD kernel's 8-frame groups beside
-    // those of the 4-frame groups the other VAD kernels use, when the two differ)
-    int32_t* group_off2 = nullptr;
-    int32_t* group_utt2 = nullptr;
-    int shift2 = 0;
-};
 
 template <int NROWS, int NI, int CAPS, int NSTAGE>
 static int fast512_launch_t(F512Params P, const void* d_wave, int dtype, const BatchGeom& bg, float* d_out,
@@ -1525,41 +1403,24 @@ static int fast512_launch_t(F512Params P, const void* d_wave, int dtype, const B
         // (the seam is as long as the samples pass 1 READS per frame, 16 x NROWS >= L: a frame's rows beyond L meet a
         // zero window, but 0 x NaN of the next utterance's samples would still poison the frame)
         const int seam = (16 * NROWS - P.S + 3) / 4 * 4;
-        static const bool no_flat = getenv("DSP_F512_NOFLAT") != nullptr;   // A/B switch for tools/kbench.py
-        if (!no_flat && (P.S % 4) == 0 && P.L > P.S && 16 * NROWS > P.S && bg.uniform_frames >= 8 && (bg.uniform_frames % 8) != 0 &&
+        if ((P.S % 4) == 0 && P.L > P.S && 16 * NROWS > P.S && bg.uniform_frames >= 8 && (bg.uniform_frames % 8) != 0 &&
             7 * P.S + 16 * NROWS + seam + 4 <= F512_WAVE_FLOATS && 7 * P.S + 16 * NROWS + seam <= 256 * (NSTAGE + 1) &&
             bg.total_frames + 8 <= 0x3fffffff) {
             P.flat = 1;
             P.seam_off = seam;
             P.total_groups = (bg.total_frames + 7) / 8;
         }
-        if (dtype == DSP_WAVE_I16)
-            return fast512_launch_k<NROWS, NI, CAPS, NSTAGE, DSP_WAVE_I16, false>(P, d_wave, bg, d_out, ld_out, P.total_groups, st);
-        return fast512_launch_k<NROWS, NI, CAPS, NSTAGE, DSP_WAVE_F32, false>(P, d_wave, bg, d_out, ld_out, P.total_groups, st);
+        return dsp_dispatch_wave(dtype, [&](auto dt) {
+            return fast512_launch_k<NROWS, NI, CAPS, NSTAGE, decltype(dt)::value, false>(P, d_wave, bg, d_out, ld_out, P.total_groups, st);
+        });
     }
-    // ragged: build the group tables in a pooled, event-guarded workspace (no host sync)
     const int64_t bound = bg.total_frames / 8 + bg.n_utt;  // >= sum ceil(T_b / 8)
-    DspWorkspace* w = nullptr;
-    if (pre != nullptr && pre->shift == 3) {
-        P.group_off = pre->group_off;
-        P.group_utt = pre->group_utt;
-    } else {
-        const size_t ws_bytes = ((size_t)bg.n_utt + 1 + (size_t)bound) * sizeof(int32_t);
-        w = dsp_workspace_pool().acquire(ws_bytes, st);
-        if (!w) return DSP_EHIP;
-        int32_t* group_off = static_cast<int32_t*>(w->ptr);
-        int32_t* group_utt = group_off + bg.n_utt + 1;
-        f512_build_group_tables(bg.frame_off, bg.n_utt, 3, group_off, group_utt, st);
-        P.group_off = group_off;
-        P.group_utt = group_utt;
-    }
-    int rc;
-    if (dtype == DSP_WAVE_I16)
-        rc = fast512_launch_k<NROWS, NI, CAPS, NSTAGE, DSP_WAVE_I16, true>(P, d_wave, bg, d_out, ld_out, bound, st);
-    else
-        rc = fast512_launch_k<NROWS, NI, CAPS, NSTAGE, DSP_WAVE_F32, true>(P, d_wave, bg, d_out, ld_out, bound, st);
-    if (w != nullptr && dsp_workspace_pool().release(w, st) != 0 && rc == DSP_OK) rc = DSP_EHIP;
-    return rc;
+    DspWorkspace* w;
+    if (!dsp_ragged_tables_acquire(P, pre, 3, bg, bound, st, w)) return DSP_EHIP;
+    const int rc = dsp_dispatch_wave(dtype, [&](auto dt) {
+        return fast512_launch_k<NROWS, NI, CAPS, NSTAGE, decltype(dt)::value, true>(P, d_wave, bg, d_out, ld_out, bound, st);
+    });
+    return dsp_ragged_tables_release(w, st, rc);
 }
 
 static inline int fast512_launch(const dsp_plan* p, const void* d_wave, int dtype, const BatchGeom& bg,
@@ -1597,9 +1458,7 @@ static int fast512_launch_fused_t(F512Params P, const void* d_wave, int dtype, c
     f512_magic((uint32_t)T, P.t_magic, P.t_shift);
     f512_magic((uint32_t)P.groups_per_utt, P.g_magic, P.g_shift);
     P.fd_n = delta_n;
-    int den = 0;
-    for (int i = 1; i <= delta_n; ++i) den += i * i;
-    P.fd_inv_den = (float)(1.0 / (2.0 * den));
+    P.fd_inv_den = dsp_delta_inv_den(delta_n);
     const size_t lds = ((size_t)P.tab_floats + (size_t)F512_WAVES * F512_WAVE_FLOATS + F512_FD_HALO_FLOATS) * sizeof(float);
     if (lds > 80 * 1024) return 1;   // two workgroups per CU
     const int64_t ld = 3 * (int64_t)P.C;
@@ -1621,10 +1480,10 @@ static int fast512_launch_fused_t(F512Params P, const void* d_wave, int dtype, c
 }
 
 // DSP_OK: launched; 1: this batch is not one the fused form serves (the caller takes the two-kernel path); < 0: HIP error.
+// For a batch that is fast512_applicable.
 static inline int fast512_launch_fused(const dsp_plan* p, const void* d_wave, int dtype, const BatchGeom& bg, int delta_n,
                                        float* d_out, hipStream_t st) {
-    static const bool off = getenv("DSP_F512_NOFUSE") != nullptr;   // A/B switch
-    if (off || !fast512_applicable(p, bg, d_wave, dtype) || bg.uniform_samples <= 0) return 1;
+    if (bg.uniform_samples <= 0) return 1;
     const Fast512Plan* fp = static_cast<const Fast512Plan*>(p->d_fast);
     if (fp->variant == 0 && fp->caps == 2) return fast512_launch_fused_t<25, 4, 2, 6>(fp->P, d_wave, dtype, bg, delta_n, d_out, st);
     if (fp->variant == 0) return fast512_launch_fused_t<25, 4, 0, 6>(fp->P, d_wave, dtype, bg, delta_n, d_out, st);

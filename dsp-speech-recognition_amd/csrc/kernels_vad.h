@@ -21,13 +21,14 @@ struct VadParams {
     int32_t L, S, use_sq;
     int32_t span_vec;       // ceil(((FR - 1) S + L) / 4)
     int32_t wave_floats;    // per-wave LDS region (floats)
-    int32_t off_a4, off_e;  // vad_vec_kernel: per-vector |x| sums / sign-change bits behind the samples
+    int32_t off_a4, off_e;  // vad_sum_kernel: the sign-change bits sit off_e floats behind the per-vector sums (off_a4: unused)
     int64_t groups_per_utt, total_groups;   // uniform batches
     const int32_t* group_off;               // ragged: [B+1] prefix of ceil(T_b / FR)
     const int32_t* group_utt;
 };
 
 // ACC: 0 = fp32 partial sums of |x| (exact for int16 input), 1 = fp64 sums of |x|, 2 = fp64 sums of x^2
+// (the host launches 1 and 2 only: int16 sums of |x| all go to vad_scan_kernel)
 template <int DTYPE, int FR, bool RAGGED, int ACC>
 __global__ __launch_bounds__(64 * VAD_WAVES) void vad_tile_kernel(VadParams P, BatchGeom bg,
                                                                   const void* __restrict__ wave,
@@ -145,148 +146,16 @@ __global__ __launch_bounds__(64 * VAD_WAVES) void vad_tile_kernel(VadParams P, B
     }
 }
 
-
-// int16 input, sum |x|: every sample is visited ONCE.  While a vector of four samples is being staged
-// its lane also forms a4 = |x0|+|x1|+|x2|+|x3| (exact in fp32) and four sign-change bits e_i for the
-// pairs (i-1, i); a frame is then the sum of the ~L/4 vector totals strictly inside it plus two edge
-// vectors resolved from the staged samples and a bit mask.  Same results as the walk above, ~3.5x
-// fewer instructions.
-template <int FR, bool RAGGED>
-__global__ __launch_bounds__(64 * VAD_WAVES) void vad_vec_kernel(VadParams P, BatchGeom bg,
-                                                                 const void* __restrict__ wave,
-                                                                 double* __restrict__ amp_sum,
-                                                                 int32_t* __restrict__ zcr) {
-    constexpr int LPF = 64 / FR;
-    constexpr int SHIFT = FR == 16 ? 4 : (FR == 8 ? 3 : 2);
-    extern __shared__ __attribute__((aligned(256))) float smem_f[];
-    const int tid = threadIdx.x;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63;
-    float* xs = smem_f + wid * P.wave_floats;
-    float* a4s = xs + P.off_a4;
-    int32_t* es = reinterpret_cast<int32_t*>(xs + P.off_e);
-    const int total_groups = RAGGED ? P.group_off[bg.n_utt] : (int)P.total_groups;
-    const int gstride = (int)gridDim.x * VAD_WAVES;
-    const int f = lane / LPF, q = lane % LPF;
-    const int L = P.L, S = P.S;
-
-    for (int G = __builtin_amdgcn_readfirstlane((int)blockIdx.x * VAD_WAVES + wid); G < total_groups; G += gstride) {
-        int utt, t0, T, nsamp;
-        int64_t s0, row0;
-        if constexpr (RAGGED) {
-            utt = P.group_utt[G];
-            t0 = (G - P.group_off[utt]) << SHIFT;
-            s0 = bg.sample_off[utt];
-            nsamp = (int)(bg.sample_off[utt + 1] - s0);
-            row0 = bg.frame_off[utt];
-            T = (int)(bg.frame_off[utt + 1] - row0);
-        } else {
-            const int gpu = (int)P.groups_per_utt;
-            utt = G / gpu;
-            t0 = (G - utt * gpu) << SHIFT;
-            nsamp = (int)bg.uniform_samples;
-            T = (int)bg.uniform_frames;
-            s0 = (int64_t)utt * bg.uniform_samples;
-            row0 = (int64_t)utt * bg.uniform_frames;
-        }
-        const int base = t0 * S;
-        const int64_t g0 = s0 + base;
-        const int d = RAGGED ? (int)(g0 & 3) : 0;
-        {
-            const int64_t a0 = g0 - d;
-            const int span_vec = RAGGED ? P.span_vec + 1 : P.span_vec;
-            F512Raw<DSP_WAVE_I16> raw[VAD_NSTAGE];
-#pragma unroll
-            for (int r = 0; r < VAD_NSTAGE; ++r) {
-                const int v = lane + 64 * r;
-                const int rel = base - d + 4 * v;
-                const bool touch = v < span_vec && rel + 3 >= 0 && rel < nsamp;
-                raw[r] = f512_load_raw<DSP_WAVE_I16>(wave, touch ? a0 + 4 * v : 0);
-            }
-            float left = 0.f;   // the pair (first staged sample - 1, first staged sample) is never inside a frame
-#pragma unroll
-            for (int r = 0; r < VAD_NSTAGE; ++r) {
-                const int v = lane + 64 * r;
-                const int rel = base - d + 4 * v;
-                float x[4];
-                f512_unpack<DSP_WAVE_I16>(raw[r], x);
-                float4 y = make_float4(x[0], x[1], x[2], x[3]);
-                if (rel + 0 < 0 || rel + 0 >= nsamp) y.x = 0.f;   // zero padding (sigproc.py:84-87)
-                if (rel + 1 < 0 || rel + 1 >= nsamp) y.y = 0.f;
-                if (rel + 2 < 0 || rel + 2 >= nsamp) y.z = 0.f;
-                if (rel + 3 < 0 || rel + 3 >= nsamp) y.w = 0.f;
-                const float prev = f512_shift_in(y.w, left);
-                left = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(y.w), 63));
-                // int16 products cannot underflow: x[i-1] * x[i] < 0 is the exact sign-pair test
-                const uint32_t b0 = prev * y.x < 0.f, b1 = y.x * y.y < 0.f, b2 = y.y * y.z < 0.f, b3 = y.z * y.w < 0.f;
-                const uint32_t bits = b0 | (b1 << 1) | (b2 << 2) | (b3 << 3);
-                if (v < span_vec) {
-                    *reinterpret_cast<float4*>(xs + 4 * v) = y;
-                    a4s[v] = (fabsf(y.x) + fabsf(y.y)) + (fabsf(y.z) + fabsf(y.w));
-                    es[v] = (int32_t)(bits | ((b0 + b1 + b2 + b3) << 8));
-                }
-            }
-        }
-        F512_FENCE();
-
-        // frame f = samples [s, e) of the LDS image; vectors vL and vR hold its two ends
-        const int s = d + f * S, e = s + L;
-        const int vL = s >> 2, vR = e >> 2;
-        float accf = 0.f;
-        int32_t cnt = 0;
-        for (int v0 = vL + 1 + q; v0 < vR; v0 += 8 * LPF) {
-            float av[8];
-            int32_t ev[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int v = min(v0 + u * LPF, vR - 1);
-                av[u] = a4s[v];
-                ev[u] = es[v];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const bool in = v0 + u * LPF < vR;
-                accf += in ? av[u] : 0.f;
-                cnt += in ? (ev[u] >> 8) : 0;
-            }
-        }
-        if (q == 0) {
-            // left edge: offsets k..3 of vector vL, pairs (i-1, i) only for i >= s + 1
-            const int k = s & 3;
-            const float4 xl = *reinterpret_cast<const float4*>(xs + 4 * vL);
-            accf += (k <= 0 ? fabsf(xl.x) : 0.f) + (k <= 1 ? fabsf(xl.y) : 0.f) + (k <= 2 ? fabsf(xl.z) : 0.f) + fabsf(xl.w);
-            cnt += __builtin_popcount((uint32_t)es[vL] & (0xFu << (k + 1)) & 0xFu);
-            // right edge: offsets 0..m-1 of vector vR (absent when the frame ends on a vector boundary)
-            const int m = e & 3;
-            const float4 xr = *reinterpret_cast<const float4*>(xs + 4 * vR);
-            accf += (m > 0 ? fabsf(xr.x) : 0.f) + (m > 1 ? fabsf(xr.y) : 0.f) + (m > 2 ? fabsf(xr.z) : 0.f);
-            cnt += __builtin_popcount((uint32_t)es[vR] & ((1u << m) - 1u));
-        }
-        double acc = (double)accf;    // lane partials are exact integers below 2^24
-#pragma unroll
-        for (int o = LPF / 2; o > 0; o >>= 1) {
-            acc += __shfl_xor(acc, o, 64);
-            cnt += __shfl_xor(cnt, o, 64);
-        }
-        const int t = t0 + f;
-        if (q == 0 && t < T) {
-            amp_sum[row0 + t] = acc;
-            zcr[row0 + t] = cnt;
-        }
-        F512_FENCE();
-    }
-}
-
 // Vector-aligned frames (L % 4 == 0 and S % 4 == 0 -- every framing the endpoint path uses at 16 / 44.1 /
 // 48 kHz): the wave loads its samples from the group's FIRST sample as it stands (vector loads at the
 // element's own alignment), so every frame is a whole number of 4-sample vectors and nothing but two
 // numbers per vector has to be staged: a4 = sum of |x| (or x^2) over the vector and the sign-change bits
 // of its four (i - 1, i) pairs.  Every sample is visited once, for int16 AND fp32 input (SURVEY 8a-12/13:
 // endpoint.py:109-126, 182-198); 8 bytes (12 with fp64 sums) of LDS per vector instead of 24, so three
-// times as many waves fit a CU as with vad_vec_kernel.  A frame = its L / 4 vector totals; its count
+// times as many waves fit a CU.  A frame = its L / 4 vector totals; its count
 // drops the first vector's pair (s - 1, s), which lies outside the frame.
 //   sums: fp32 when exact (int16 input, |x|: a lane's partial stays below 2^24), fp64 otherwise.
+//   (the host launches the fp64 form only: int16 sums of |x| all go to vad_scan_kernel)
 template <int DTYPE, int FR, bool RAGGED, bool F32SUM>
 __global__ __launch_bounds__(64 * VAD_WAVES) void vad_sum_kernel(VadParams P, BatchGeom bg,
                                                                  const void* __restrict__ wave,
@@ -650,17 +519,7 @@ static inline bool vad_scan_frames8(int32_t L, int32_t S, int dtype, int32_t use
     return (7 * (int64_t)S + L + 3) / 4 <= 64 * 20 && (3 * (int64_t)S + L + 3) / 4 + 1 <= 64 * VAD_NSTAGE;
 }
 
-static inline bool vad_tile_applicable(const BatchGeom& bg, const void* d_wave, int dtype, int FR) {
-    if (FR == 0) return false;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_wave);
-    if ((a % (dtype == DSP_WAVE_I16 ? 8 : 16)) != 0) return false;
-    if (bg.uniform_samples > 0) {
-        if ((bg.uniform_samples % 4) != 0) return false;
-        return bg.uniform_samples <= 0x3fffffff && ((bg.uniform_frames + FR - 1) / FR) * bg.n_utt <= 0x3fffffff;
-    }
-    return bg.total_frames / FR + bg.n_utt <= 0x3fffffff;
-}
-
+// (which batches the kernels can read: vad_tile_applicable, dsp_frontend.hip)
 template <int DTYPE, int FR, bool RAGGED>
 static int vad_tile_launch_k(const VadParams& P, const BatchGeom& bg, const void* d_wave, double* d_amp,
                              int32_t* d_zcr, int64_t groups_bound, hipStream_t st) {
@@ -671,31 +530,23 @@ static int vad_tile_launch_k(const VadParams& P, const BatchGeom& bg, const void
         const int64_t rounds = (blocks + cap - 1) / cap;
         blocks = (blocks + rounds - 1) / rounds;
     }
-    // int16 samples: the |x| sum of one lane stays below 2^24, so fp32 partial sums are exact
-    const bool f32_exact = DTYPE == DSP_WAVE_I16 && !P.use_sq && (P.L + 64 / FR - 1) / (64 / FR) < 512;
-    static const bool force_walk = getenv("DSP_VAD_WALK") != nullptr;   // A/B aid: keep the per-frame walk
-    static const bool no_sum = getenv("DSP_VAD_NOSUM") != nullptr;       // A/B aid: skip vad_sum_kernel
-    static const bool no_scan = getenv("DSP_VAD_NOSCAN") != nullptr;   // A/B aid: keep the round-3 kernels for int16 input
     if constexpr (DTYPE == DSP_WAVE_I16) {
         // int16, sum |x|, any frame length and hop: integer partials and prefix sums (a vector's sum stays below 2^17, a
-        // group's below 2^27)
-        VadParams Q = P;
-        Q.span_vec = ((FR - 1) * P.S + P.L + 3) / 4;
-        if (!P.use_sq && !no_scan && !force_walk && !no_sum && Q.span_vec <= 64 * VAD_NSTAGE && P.L >= 8) {
+        // group's below 2^27).  vad_tile_frames has seen to it that the span fits the staging rounds, and L >= 64.
+        if (!P.use_sq) {
             const size_t ldss = (size_t)VAD_WAVES * 2 * 64 * VAD_SCAN_CH * sizeof(int32_t);
             int64_t blockss = (groups_bound + VAD_WAVES - 1) / VAD_WAVES;
             const int64_t caps = (int64_t)dsp_cu_count() * 6;          // 24.6 KB per workgroup: six per CU
             if (blockss > caps) blockss = caps;
-            vad_scan_kernel<FR, RAGGED><<<(int)blockss, 64 * VAD_WAVES, ldss, st>>>(Q, bg, static_cast<const int16_t*>(d_wave), d_amp, d_zcr);
+            vad_scan_kernel<FR, RAGGED><<<(int)blockss, 64 * VAD_WAVES, ldss, st>>>(P, bg, static_cast<const int16_t*>(d_wave), d_amp, d_zcr);
             return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
         }
     }
-    if ((P.L % 4) == 0 && (P.S % 4) == 0 && !force_walk && !no_sum) {
-        // vector-aligned frames: visit-once kernel with 8 (12) bytes of LDS per vector, both input types
+    if ((P.L % 4) == 0 && (P.S % 4) == 0) {
+        // vector-aligned frames: visit-once kernel with 12 bytes of LDS per vector, both input types
         VadParams Q = P;
         Q.span_vec = ((FR - 1) * P.S + P.L) / 4;
-        const size_t sum_bytes = f32_exact ? 4 : 8;
-        Q.off_e = (int32_t)((((size_t)Q.span_vec * sum_bytes + 15) / 16 * 16) / 4);       // floats
+        Q.off_e = (int32_t)((((size_t)Q.span_vec * 8 + 15) / 16 * 16) / 4);       // floats
         Q.wave_floats = (int32_t)(((size_t)Q.off_e + Q.span_vec + 63) / 64 * 64);
         if (Q.span_vec <= 64 * VAD_NSTAGE) {
             const size_t lds3 = (size_t)VAD_WAVES * Q.wave_floats * sizeof(float);
@@ -705,45 +556,21 @@ static int vad_tile_launch_k(const VadParams& P, const BatchGeom& bg, const void
             if (per_cu < 1) per_cu = 1;
             const int64_t cap3 = (int64_t)dsp_cu_count() * per_cu;
             if (blocks3 > cap3) blocks3 = cap3;
-            if (f32_exact) {
-                auto k = vad_sum_kernel<DTYPE, FR, RAGGED, true>;
-                static size_t granted[DSP_MAX_DEVICES] = {};
-                if (lds3 > 48 * 1024 && dsp_ensure_dynamic_lds((const void*)k, lds3, granted) != 0) return DSP_EHIP;
-                k<<<(int)blocks3, 64 * VAD_WAVES, lds3, st>>>(Q, bg, d_wave, d_amp, d_zcr);
-            } else {
-                auto k = vad_sum_kernel<DTYPE, FR, RAGGED, false>;
-                static size_t granted[DSP_MAX_DEVICES] = {};
-                if (lds3 > 48 * 1024 && dsp_ensure_dynamic_lds((const void*)k, lds3, granted) != 0) return DSP_EHIP;
-                k<<<(int)blocks3, 64 * VAD_WAVES, lds3, st>>>(Q, bg, d_wave, d_amp, d_zcr);
-            }
+            auto k = vad_sum_kernel<DTYPE, FR, RAGGED, false>;
+            static size_t granted[DSP_MAX_DEVICES] = {};
+            if (lds3 > 48 * 1024 && dsp_ensure_dynamic_lds((const void*)k, lds3, granted) != 0) return DSP_EHIP;
+            k<<<(int)blocks3, 64 * VAD_WAVES, lds3, st>>>(Q, bg, d_wave, d_amp, d_zcr);
             return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
         }
     }
-    if (f32_exact && !force_walk) {
-        // visit-once kernel: samples + per-vector sums + sign bits per wave (6 floats per staged vector)
-        VadParams Q = P;
-        Q.off_a4 = 4 * (P.span_vec + 1);
-        Q.off_e = 5 * (P.span_vec + 1);
-        Q.wave_floats = (6 * (P.span_vec + 1) + 63) / 64 * 64;
-        const size_t lds2 = (size_t)VAD_WAVES * Q.wave_floats * sizeof(float);
-        auto k = vad_vec_kernel<FR, RAGGED>;
-        static size_t granted[DSP_MAX_DEVICES] = {};
-        if (lds2 > 48 * 1024 && dsp_ensure_dynamic_lds((const void*)k, lds2, granted) != 0) return DSP_EHIP;
-        int64_t blocks2 = (groups_bound + VAD_WAVES - 1) / VAD_WAVES;
-        const int64_t cap2 = (int64_t)dsp_cu_count() * 2;
-        if (blocks2 > cap2) {
-            const int64_t rounds = (blocks2 + cap2 - 1) / cap2;
-            blocks2 = (blocks2 + rounds - 1) / rounds;
+    // what is left walks every frame: sum x^2 of either type, float sum |x|
+    if constexpr (DTYPE == DSP_WAVE_F32) {
+        if (!P.use_sq) {
+            vad_tile_kernel<DTYPE, FR, RAGGED, 1><<<(int)blocks, 64 * VAD_WAVES, lds, st>>>(P, bg, d_wave, d_amp, d_zcr);
+            return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
         }
-        k<<<(int)blocks2, 64 * VAD_WAVES, lds2, st>>>(Q, bg, d_wave, d_amp, d_zcr);
-        return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
     }
-    if (f32_exact)
-        vad_tile_kernel<DTYPE, FR, RAGGED, 0><<<(int)blocks, 64 * VAD_WAVES, lds, st>>>(P, bg, d_wave, d_amp, d_zcr);
-    else if (!P.use_sq)
-        vad_tile_kernel<DTYPE, FR, RAGGED, 1><<<(int)blocks, 64 * VAD_WAVES, lds, st>>>(P, bg, d_wave, d_amp, d_zcr);
-    else
-        vad_tile_kernel<DTYPE, FR, RAGGED, 2><<<(int)blocks, 64 * VAD_WAVES, lds, st>>>(P, bg, d_wave, d_amp, d_zcr);
+    vad_tile_kernel<DTYPE, FR, RAGGED, 2><<<(int)blocks, 64 * VAD_WAVES, lds, st>>>(P, bg, d_wave, d_amp, d_zcr);
     return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
 }
 
@@ -756,32 +583,17 @@ static int vad_tile_launch_t(VadParams P, const BatchGeom& bg, const void* d_wav
     if (bg.uniform_samples > 0) {
         P.groups_per_utt = (bg.uniform_frames + FR - 1) / FR;
         P.total_groups = P.groups_per_utt * bg.n_utt;
-        if (dtype == DSP_WAVE_I16)
-            return vad_tile_launch_k<DSP_WAVE_I16, FR, false>(P, bg, d_wave, d_amp, d_zcr, P.total_groups, st);
-        return vad_tile_launch_k<DSP_WAVE_F32, FR, false>(P, bg, d_wave, d_amp, d_zcr, P.total_groups, st);
+        return dsp_dispatch_wave(dtype, [&](auto dt) {
+            return vad_tile_launch_k<decltype(dt)::value, FR, false>(P, bg, d_wave, d_amp, d_zcr, P.total_groups, st);
+        });
     }
     const int64_t bound = bg.total_frames / FR + bg.n_utt;
-    DspWorkspace* w = nullptr;
-    if (pre != nullptr && pre->shift == SHIFT) {   // tables of a dsp_layout: built once per batch shape
-        P.group_off = pre->group_off;
-        P.group_utt = pre->group_utt;
-    } else {
-        const size_t ws_bytes = ((size_t)bg.n_utt + 1 + (size_t)bound) * sizeof(int32_t);
-        w = dsp_workspace_pool().acquire(ws_bytes, st);
-        if (!w) return DSP_EHIP;
-        int32_t* group_off = static_cast<int32_t*>(w->ptr);
-        int32_t* group_utt = group_off + bg.n_utt + 1;
-        f512_build_group_tables(bg.frame_off, bg.n_utt, SHIFT, group_off, group_utt, st);
-        P.group_off = group_off;
-        P.group_utt = group_utt;
-    }
-    int rc;
-    if (dtype == DSP_WAVE_I16)
-        rc = vad_tile_launch_k<DSP_WAVE_I16, FR, true>(P, bg, d_wave, d_amp, d_zcr, bound, st);
-    else
-        rc = vad_tile_launch_k<DSP_WAVE_F32, FR, true>(P, bg, d_wave, d_amp, d_zcr, bound, st);
-    if (w != nullptr && dsp_workspace_pool().release(w, st) != 0 && rc == DSP_OK) rc = DSP_EHIP;
-    return rc;
+    DspWorkspace* w;   // (prebuilt tables: those of a dsp_layout, built once per batch shape)
+    if (!dsp_ragged_tables_acquire(P, pre, SHIFT, bg, bound, st, w)) return DSP_EHIP;
+    const int rc = dsp_dispatch_wave(dtype, [&](auto dt) {
+        return vad_tile_launch_k<decltype(dt)::value, FR, true>(P, bg, d_wave, d_amp, d_zcr, bound, st);
+    });
+    return dsp_ragged_tables_release(w, st, rc);
 }
 
 static inline int vad_tile_launch(int FR, int32_t L, int32_t S, int32_t use_sq, const BatchGeom& bg, const void* d_wave,
@@ -795,44 +607,24 @@ static inline int vad_tile_launch(int FR, int32_t L, int32_t S, int32_t use_sq, 
     // (1103 of 1280 staged vectors; 1200 at 48 kHz) instead of four -- 1.25 x instead of 1.5 x of the samples read, half the prefix-scan
     // work per frame: 23.4 vs 30.0 us per 69 MB (same-job A/B)
     if (vad_scan_frames8(L, S, dtype, use_sq)) {
-        static const bool no_scan = getenv("DSP_VAD_NOSCAN") != nullptr;
-        static const bool force_walk = getenv("DSP_VAD_WALK") != nullptr, no_sum = getenv("DSP_VAD_NOSUM") != nullptr;
-        if (!no_scan && !force_walk && !no_sum) {
-            P.span_vec = (int32_t)((7 * (int64_t)S + L + 3) / 4);
-            const size_t ldss = (size_t)VAD_WAVES * 2 * 64 * 20 * sizeof(int32_t);     // CH = 20 dwords per lane and array
-            const int64_t cap = (int64_t)dsp_cu_count() * 3;                             // 40 KB per workgroup: three per CU
-            if (bg.uniform_samples > 0) {
-                P.groups_per_utt = (bg.uniform_frames + 7) / 8;
-                P.total_groups = P.groups_per_utt * bg.n_utt;
-                int64_t blocks = (P.total_groups + VAD_WAVES - 1) / VAD_WAVES;
-                if (blocks > cap) blocks = cap;
-                vad_scan_kernel<8, false><<<(int)blocks, 64 * VAD_WAVES, ldss, st>>>(P, bg, static_cast<const int16_t*>(d_wave), d_amp, d_zcr);
-                return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
-            }
-            const int64_t bound = bg.total_frames / 8 + bg.n_utt;
-            DspWorkspace* w = nullptr;
-            if (pre != nullptr && pre->shift == 3) {
-                P.group_off = pre->group_off;
-                P.group_utt = pre->group_utt;
-            } else if (pre != nullptr && pre->shift2 == 3) {
-                P.group_off = pre->group_off2;
-                P.group_utt = pre->group_utt2;
-            } else {
-                const size_t ws_bytes = ((size_t)bg.n_utt + 1 + (size_t)bound) * sizeof(int32_t);
-                w = dsp_workspace_pool().acquire(ws_bytes, st);
-                if (!w) return DSP_EHIP;
-                int32_t* group_off = static_cast<int32_t*>(w->ptr);
-                f512_build_group_tables(bg.frame_off, bg.n_utt, 3, group_off, group_off + bg.n_utt + 1, st);
-                P.group_off = group_off;
-                P.group_utt = group_off + bg.n_utt + 1;
-            }
-            int64_t blocks = (bound + VAD_WAVES - 1) / VAD_WAVES;
+        P.span_vec = (int32_t)((7 * (int64_t)S + L + 3) / 4);
+        const size_t ldss = (size_t)VAD_WAVES * 2 * 64 * 20 * sizeof(int32_t);     // CH = 20 dwords per lane and array
+        const int64_t cap = (int64_t)dsp_cu_count() * 3;                             // 40 KB per workgroup: three per CU
+        if (bg.uniform_samples > 0) {
+            P.groups_per_utt = (bg.uniform_frames + 7) / 8;
+            P.total_groups = P.groups_per_utt * bg.n_utt;
+            int64_t blocks = (P.total_groups + VAD_WAVES - 1) / VAD_WAVES;
             if (blocks > cap) blocks = cap;
-            vad_scan_kernel<8, true><<<(int)blocks, 64 * VAD_WAVES, ldss, st>>>(P, bg, static_cast<const int16_t*>(d_wave), d_amp, d_zcr);
-            int rc = hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
-            if (w != nullptr && dsp_workspace_pool().release(w, st) != 0 && rc == DSP_OK) rc = DSP_EHIP;
-            return rc;
+            vad_scan_kernel<8, false><<<(int)blocks, 64 * VAD_WAVES, ldss, st>>>(P, bg, static_cast<const int16_t*>(d_wave), d_amp, d_zcr);
+            return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
         }
+        const int64_t bound = bg.total_frames / 8 + bg.n_utt;
+        DspWorkspace* w;
+        if (!dsp_ragged_tables_acquire(P, pre, 3, bg, bound, st, w)) return DSP_EHIP;
+        int64_t blocks = (bound + VAD_WAVES - 1) / VAD_WAVES;
+        if (blocks > cap) blocks = cap;
+        vad_scan_kernel<8, true><<<(int)blocks, 64 * VAD_WAVES, ldss, st>>>(P, bg, static_cast<const int16_t*>(d_wave), d_amp, d_zcr);
+        return dsp_ragged_tables_release(w, st, hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP);
     }
     return vad_tile_launch_t<4>(P, bg, d_wave, dtype, d_amp, d_zcr, st, pre);
 }
