@@ -18,6 +18,7 @@
 #include "kernels_vad.h"
 #include "kernels_pitch.h"
 #include "kernels_cepstrum.h"
+#include "kernels_hmlstm.h"
 
 thread_local int g_host_dry_run = 0;   // dsp_debug_host_dry_run: plan tables in host memory (sanitizer build, no GPU)
 
@@ -29,6 +30,14 @@ struct dsp_layout {
     int32_t* group_utt;
     int32_t* group_off2;   // tables of the int16 VAD kernel's 8-frame groups, where it uses them (vad_scan_frames8)
     int32_t* group_utt2;
+    int device;
+};
+
+// Packed parameters of one HM-LSTM (include/dsp_frontend.h: dsp_hmlstm); immutable after dsp_hmlstm_create.
+struct dsp_hmlstm {
+    int32_t I, H1, H2;
+    float* d_packed;       // one allocation: cell 1 W_01 | U_21 | U_11 | bias, cell 2 W_01 | U_11 | bias (kernels_hmlstm.h layout)
+    HmCell c1, c2;
     int device;
 };
 
@@ -1200,6 +1209,82 @@ int dsp_pitch_smooth_subseq_batch(const double* d_values, const int64_t* d_offse
         return fail(DSP_EINVAL, "dsp_pitch_smooth_subseq_batch: bad arguments");
     if (tor < 1) return fail(DSP_EINVAL, "dsp_pitch_smooth_subseq_batch: tor must be >= 1 (got %d)", tor);
     pitch_subseq_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_values, d_offsets, tor, thres, d_seg, d_info);
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+int dsp_hmlstm_create(const dsp_hmlstm_desc* d, dsp_hmlstm** out) {
+    if (!d || !out) return fail(DSP_EINVAL, "dsp_hmlstm_create: NULL argument");
+    *out = nullptr;
+    if (!hm_size_ok(d->input_size) || !hm_size_ok(d->hidden1) || !hm_size_ok(d->hidden2))
+        return fail(DSP_EINVAL, "dsp_hmlstm_create: input_size %d, hidden1 %d, hidden2 %d must be multiples of 4 in [4, %d]",
+                    d->input_size, d->hidden1, d->hidden2, HM_MAX_SIZE);
+    if (!d->d_c1_U11 || !d->d_c1_U21 || !d->d_c1_W01 || !d->d_c1_bias || !d->d_c2_U11 || !d->d_c2_W01 || !d->d_c2_bias)
+        return fail(DSP_EINVAL, "dsp_hmlstm_create: NULL parameter tensor");
+    const int32_t I = d->input_size, H1 = d->hidden1, H2 = d->hidden2;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    // segments in packing order: (source, H of the cell, K)
+    struct Seg { const float* src; int32_t H, K; };
+    const Seg segs[5] = {{d->d_c1_W01, H1, I}, {d->d_c1_U21, H1, H2}, {d->d_c1_U11, H1, H1}, {d->d_c2_W01, H2, H1}, {d->d_c2_U11, H2, H2}};
+    size_t off[8], total = 0;
+    for (int i = 0; i < 5; ++i) { off[i] = total; total += (size_t)hm_kgroups(segs[i].K) * hm_tiles(segs[i].H) * 256; }
+    off[5] = total; total += (size_t)hm_tiles(H1) * 16;
+    off[6] = total; total += (size_t)hm_tiles(H2) * 16;
+    float* buf = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), total * sizeof(float)));
+    // the parameters may have been written on any stream of the caller: create is rare, so it simply waits for the device
+    hipError_t e = hipDeviceSynchronize();
+    for (int i = 0; i < 5 && e == hipSuccess; ++i) {
+        const int64_t n = (int64_t)hm_kgroups(segs[i].K) * hm_tiles(segs[i].H) * 256;
+        hm_pack_kernel<<<(int)((n + 255) / 256), 256, 0, 0>>>(segs[i].src, segs[i].H, segs[i].K, hm_kgroups(segs[i].K), buf + off[i]);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) { hm_pack_bias_kernel<<<(hm_tiles(H1) * 16 + 255) / 256, 256, 0, 0>>>(d->d_c1_bias, H1, buf + off[5]); e = hipGetLastError(); }
+    if (e == hipSuccess) { hm_pack_bias_kernel<<<(hm_tiles(H2) * 16 + 255) / 256, 256, 0, 0>>>(d->d_c2_bias, H2, buf + off[6]); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(buf);
+        return fail(DSP_EHIP, "dsp_hmlstm_create: %s", hipGetErrorString(e));
+    }
+    dsp_hmlstm* h = new dsp_hmlstm();
+    h->I = I; h->H1 = H1; h->H2 = H2; h->d_packed = buf; h->device = dev;
+    auto f4 = [&](int i) { return reinterpret_cast<const float4*>(buf + off[i]); };
+    h->c1 = HmCell{{f4(0), f4(1), f4(2)}, buf + off[5], {hm_kgroups(I), hm_kgroups(H2), hm_kgroups(H1)}, H1, hm_tiles(H1)};
+    h->c2 = HmCell{{f4(3), nullptr, f4(4)}, buf + off[6], {hm_kgroups(H1), 0, hm_kgroups(H2)}, H2, hm_tiles(H2)};
+    *out = h;
+    return DSP_OK;
+}
+
+int dsp_hmlstm_destroy(dsp_hmlstm* h) {
+    if (!h) return DSP_OK;
+    hipError_t e = hipFree(h->d_packed);
+    delete h;
+    if (e != hipSuccess) return fail(DSP_EHIP, "dsp_hmlstm_destroy: %s", hipGetErrorString(e));
+    return DSP_OK;
+}
+
+int dsp_hmlstm_forward(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
+                       const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1, uint8_t* d_z2,
+                       float* d_zhat, float* d_last_h2, void* stream) {
+    if (!h || !d_x) return fail(DSP_EINVAL, "dsp_hmlstm_forward: NULL handle / input");
+    if (T < 1 || B < 1) return fail(DSP_EINVAL, "dsp_hmlstm_forward: T %d and B %d must be >= 1", T, B);
+    if (!std::isfinite(a)) return fail(DSP_EINVAL, "dsp_hmlstm_forward: the slope a is not finite");
+    if ((reinterpret_cast<uintptr_t>(d_x) & 15) != 0) return fail(DSP_EINVAL, "dsp_hmlstm_forward: d_x must be 16-byte aligned");
+    if (!d_state_out && !d_h1 && !d_h2 && !d_z1 && !d_z2 && !d_zhat && !d_last_h2)
+        return fail(DSP_EINVAL, "dsp_hmlstm_forward: nothing to write (every output is NULL)");
+    HmParams P;
+    P.c1 = h->c1; P.c2 = h->c2;
+    P.I = h->I; P.T = T; P.B = B; P.a = a;
+    P.x = d_x; P.len = d_len; P.state_in = d_state_in; P.state_out = d_state_out;
+    P.h1 = d_h1; P.h2 = d_h2; P.z1 = d_z1; P.z2 = d_z2; P.zhat = d_zhat; P.last_h2 = d_last_h2;
+    const int grid = (B + HM_COLS - 1) / HM_COLS;
+    const int nt = h->c1.n_tiles > h->c2.n_tiles ? h->c1.n_tiles : h->c2.n_tiles;   // tiles per wave: ceil(nt / 8)
+    hipStream_t st = (hipStream_t)stream;
+    if (nt <= 2 * HM_WAVES) hmlstm_forward_kernel<2><<<grid, HM_THREADS, 0, st>>>(P);
+    else if (nt <= 4 * HM_WAVES) hmlstm_forward_kernel<4><<<grid, HM_THREADS, 0, st>>>(P);
+    else if (nt <= 7 * HM_WAVES) hmlstm_forward_kernel<7><<<grid, HM_THREADS, 0, st>>>(P);
+    else hmlstm_forward_kernel<9><<<grid, HM_THREADS, 0, st>>>(P);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }

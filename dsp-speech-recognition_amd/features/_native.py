@@ -31,6 +31,14 @@ class PlanDesc(C.Structure):
     ]
 
 
+class HmlstmDesc(C.Structure):
+    _fields_ = [
+        ('input_size', c_i32), ('hidden1', c_i32), ('hidden2', c_i32), ('reserved', c_i32),
+        ('d_c1_U11', c_vp), ('d_c1_U21', c_vp), ('d_c1_W01', c_vp), ('d_c1_bias', c_vp),
+        ('d_c2_U11', c_vp), ('d_c2_W01', c_vp), ('d_c2_bias', c_vp),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/dsp_frontend.h one to one.
 SIGNATURES = {
     'dsp_abi_version': (C.c_int, []),
@@ -91,6 +99,9 @@ SIGNATURES = {
     'dsp_model_pitchfeat_batch': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     'dsp_model_finalize_batch': (C.c_int, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'dsp_model_finalize_segments_batch': (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'dsp_hmlstm_create': (C.c_int, [C.POINTER(HmlstmDesc), C.POINTER(c_vp)]),
+    'dsp_hmlstm_destroy': (C.c_int, [c_vp]),
+    'dsp_hmlstm_forward': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-"""PyTorch-ROCm stand-ins of the reference's recurrent classifiers (RNN, HRNN, HRNN_Att, Transformer), for SURVEY row f-3 (device-resident
+"""PyTorch-ROCm stand-ins of the reference's recurrent classifiers (RNN, HRNN, HRNN_Att, Transformer, HMRNN), for SURVEY row f-3 (device-resident
 features feed the RNN without a host round trip) and for the configs[4] throughput figure of bench.py.
 
 The reference's own classes (rnn_clf.py, layers.py) run unchanged on PyTorch-ROCm; they are not part of this
@@ -226,6 +226,235 @@ class TransformerHead(nn.Module):
         y2 = self.rnn_enc_2(y[0::self.hir], len1)
         out, feat = _pool_head(y2, len1, self.out)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat, attn_out
+
+
+class _HMCell(nn.Module):
+    """The parameters of hmrnn.HM_LSTMCell (hmrnn.py:60-71), same names, shapes, order and initial distribution."""
+
+    def __init__(self, bottom_size, hidden_size, top_size, last_layer):
+        super().__init__()
+        self.hidden_size, self.last_layer = hidden_size, last_layer
+        rows = 4 * hidden_size + 1
+        self.U_11 = nn.Parameter(torch.empty(rows, hidden_size))
+        if not last_layer:
+            self.U_21 = nn.Parameter(torch.empty(rows, top_size))
+        self.W_01 = nn.Parameter(torch.empty(rows, bottom_size))
+        self.bias = nn.Parameter(torch.empty(rows))
+        stdv = 1.0 / float(np.sqrt(hidden_size))
+        for p in self.parameters():
+            nn.init.uniform_(p, -stdv, stdv)
+
+    def forward(self, a, c, h_bottom, h, h_top, z, z_bottom):
+        """hmrnn.py:73-111, everything [rows, B].  Returns (h_new, c_new, z_new, z_hat); z_new carries the reference's
+        straight-through gradient (``bound.backward`` hands the gradient on unchanged, hmrnn.py:37-45)."""
+        H = self.hidden_size
+        f_s = torch.mm(self.W_01, h_bottom)
+        if not self.last_layer:
+            f_s = f_s + z * torch.mm(self.U_21, h_top)
+        else:
+            f_s = f_s + torch.zeros_like(f_s)
+        f_s = f_s + z_bottom * torch.mm(self.U_11, h) + self.bias.unsqueeze(1)
+        f, i, o = torch.sigmoid(f_s[0:H]), torch.sigmoid(f_s[H:2 * H]), torch.sigmoid(f_s[2 * H:3 * H])
+        g = torch.tanh(f_s[3 * H:4 * H])
+        z_hat = torch.clamp((f_s[4 * H:4 * H + 1] * a + 1) / 2.0, min=0, max=1)                    # hard_sigm, hmrnn.py:25-28
+        c_new = z * (i * g) + (1 - z) * (1 - z_bottom) * c + (1 - z) * z_bottom * (f * c + i * g)
+        t = torch.tanh(c_new)
+        h_new = z * o * t + (1 - z) * (1 - z_bottom) * h + (1 - z) * z_bottom * o * t
+        z_new = (z_hat > 0.5).to(z_hat.dtype) + (z_hat - z_hat.detach())
+        return h_new, c_new, z_new, z_hat
+
+
+class HMLSTMResult:
+    """h_1 [B, T, H1], h_2 [B, T, H2], z_1 / z_2 [B, T, 1] (0. / 1.), hidden = (h1, c1, z1, h2, c2, z2) as [H, B] / [1, B]
+    (hmrnn.py:153-154), z_hat [T, 2, B] (hard_sigm in front of the threshold: cell 1, cell 2) and, when lengths were given,
+    last_h2 [B, H2] = h_2[b, len[b] - 1] (rnn_clf.py:140-143)."""
+    __slots__ = ('h_1', 'h_2', 'z_1', 'z_2', 'hidden', 'z_hat', 'last_h2')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+class HMLSTM(nn.Module):
+    """hmrnn.HM_LSTM (hmrnn.py:114-154): two hierarchical-multiscale LSTM cells over a [T, B, input_size] sequence.
+    Parameter names, shapes and order equal the reference's (``cell_1.U_11, cell_1.U_21, cell_1.W_01, cell_1.bias,
+    cell_2.U_11, cell_2.W_01, cell_2.bias``): its state_dict loads.
+
+    Two paths compute the same thing:
+      * the torch step loop -- the restatement, on any device, with the reference's straight-through gradient; taken
+        whenever a gradient is required;
+      * the native one -- ``dsp_hmlstm_forward`` (csrc/kernels_hmlstm.h: one persistent HIP launch), on the tensors in
+        place on the current stream; the default for CUDA/ROCm tensors when no gradient is required.  ``native=True``
+        insists on it (and raises where it cannot run), ``native=False`` keeps the loop.
+
+    ``a`` is the slope of hard_sigm and is read at every call.  (The reference's cells copy ``a`` at construction,
+    hmrnn.py:53,121-122, so its ``HMRNN.adjust_param`` -- which adds to ``HM_LSTM.a`` only -- never reaches them; here the
+    one attribute is what both cells use.)"""
+
+    def __init__(self, a, input_size, size_list):
+        super().__init__()
+        self.a, self.input_size, self.size_list = float(a), int(input_size), [int(v) for v in size_list]
+        self.cell_1 = _HMCell(self.input_size, self.size_list[0], self.size_list[1], False)
+        self.cell_2 = _HMCell(self.size_list[0], self.size_list[1], None, True)
+        self._handle, self._handle_key = None, None
+
+    # ---- native path ------------------------------------------------------------------------------------------------
+    def _params(self):
+        c1, c2 = self.cell_1, self.cell_2
+        return [c1.U_11, c1.U_21, c1.W_01, c1.bias, c2.U_11, c2.W_01, c2.bias]
+
+    def native_supported(self, x):
+        """Why the native path cannot serve ``x`` (a string), or None when it can."""
+        from . import _native as nat
+        import os
+        if not x.is_cuda:
+            return 'the input is not on a GPU'
+        if x.dtype != torch.float32 or any(p.dtype != torch.float32 or p.device != x.device for p in self._params()):
+            return 'input and parameters must be float32 on one device'
+        if any(v < 4 or v > 256 or v % 4 for v in [self.input_size] + self.size_list):
+            return 'sizes must be multiples of 4 in [4, 256]'
+        if not os.path.exists(nat.LIB_PATH):
+            return f'{nat.LIB_PATH} is not built'
+        return None
+
+    def _drop_handle(self):
+        if self._handle is not None:
+            from . import _native as nat
+            try:
+                nat.load().dsp_hmlstm_destroy(self._handle)
+            except Exception:
+                pass
+            self._handle, self._handle_key = None, None
+
+    def __del__(self):
+        self._drop_handle()
+
+    def __getstate__(self):
+        """Copies (copy.deepcopy, pickling) do not share the native handle: each builds its own on first use."""
+        d = self.__dict__.copy()
+        d['_handle'], d['_handle_key'] = None, None
+        return d
+
+    def _native_handle(self, dev):
+        """The packed copy of the parameters; rebuilt when one of them moved or was written (data_ptr / _version)."""
+        from . import _native as nat
+        ps = [p.detach() for p in self._params()]
+        if any(not p.is_contiguous() for p in ps):
+            raise nat.DspError('HMLSTM: parameters must be contiguous')
+        key = (dev.index,) + tuple((p.data_ptr(), p._version) for p in self._params())
+        if self._handle is None or key != self._handle_key:
+            self._drop_handle()
+            d = nat.HmlstmDesc(self.input_size, self.size_list[0], self.size_list[1], 0, *[p.data_ptr() for p in ps])
+            h = nat.c_vp(0)
+            nat.check(nat.load().dsp_hmlstm_create(nat.C.byref(d), nat.C.byref(h)))
+            self._handle, self._handle_key = h.value, key
+        return self._handle
+
+    def _run_native(self, x, hidden, lens, want_seq=True):
+        from . import _native as nat
+        T, B, _ = x.shape
+        H1, H2 = self.size_list
+        dev = x.device
+        x = x.detach().contiguous()
+        with torch.cuda.device(dev):
+            handle = self._native_handle(dev)
+            f32 = dict(dtype=torch.float32, device=dev)
+            state_in = None
+            if hidden is not None:
+                state_in = torch.cat([v.detach().to(**f32).reshape(-1) for v in hidden])
+                assert state_in.numel() == (2 * H1 + 2 * H2 + 2) * B, 'hidden does not fit (h1, c1, z1, h2, c2, z2) of this batch'
+            state_out = torch.empty((2 * H1 + 2 * H2 + 2) * B, **f32)
+            h_1 = torch.empty(B, T, H1, **f32) if want_seq else None
+            h_2 = torch.empty(B, T, H2, **f32) if want_seq else None
+            z_1 = torch.empty(B, T, dtype=torch.uint8, device=dev) if want_seq else None
+            z_2 = torch.empty(B, T, dtype=torch.uint8, device=dev) if want_seq else None
+            z_hat = torch.empty(T, 2, B, **f32)
+            d_len = last = None
+            if lens is not None:
+                d_len = torch.as_tensor(np.asarray(lens.cpu() if torch.is_tensor(lens) else lens), dtype=torch.int32).to(dev)
+                last = torch.empty(B, H2, **f32)
+            ptr = lambda t: None if t is None else t.data_ptr()
+            nat.check(nat.load().dsp_hmlstm_forward(handle, x.data_ptr(), T, B, float(self.a), ptr(d_len), ptr(state_in),
+                                                    state_out.data_ptr(), ptr(h_1), ptr(h_2), ptr(z_1), ptr(z_2), z_hat.data_ptr(),
+                                                    ptr(last), torch.cuda.current_stream(dev).cuda_stream))
+        sizes = [H1 * B, H1 * B, B, H2 * B, H2 * B, B]
+        parts = torch.split(state_out, sizes)
+        hid = (parts[0].view(H1, B), parts[1].view(H1, B), parts[2].view(1, B), parts[3].view(H2, B), parts[4].view(H2, B), parts[5].view(1, B))
+        zf = lambda z: None if z is None else z.to(torch.float32).unsqueeze(2)
+        return HMLSTMResult(h_1=h_1, h_2=h_2, z_1=zf(z_1), z_2=zf(z_2), hidden=hid, z_hat=z_hat, last_h2=last)
+
+    # ---- torch step loop (hmrnn.py:124-154) -------------------------------------------------------------------------------
+    def _run_torch(self, x, hidden, lens):
+        T, B, _ = x.shape
+        H1, H2 = self.size_list
+        zeros = lambda n: torch.zeros(n, B, dtype=x.dtype, device=x.device)
+        if hidden is None:
+            h1, c1, z1, h2, c2, z2 = zeros(H1), zeros(H1), zeros(1), zeros(H2), zeros(H2), zeros(1)
+        else:
+            h1, c1, z1, h2, c2, z2 = hidden
+        one = torch.ones(1, B, dtype=x.dtype, device=x.device)
+        hs1, hs2, zs1, zs2, zh = [], [], [], [], []
+        for t in range(T):
+            h1, c1, z1, zh1 = self.cell_1(self.a, c1, x[t].t(), h1, h2, z1, one)
+            h2, c2, z2, zh2 = self.cell_2(self.a, c2, h1, h2, None, z2, z1)
+            hs1.append(h1.t()); hs2.append(h2.t()); zs1.append(z1.t()); zs2.append(z2.t())
+            zh.append(torch.cat([zh1, zh2], 0))
+        h_2 = torch.stack(hs2, dim=1)
+        last = None
+        if lens is not None:
+            idx = torch.as_tensor(np.asarray(lens.cpu() if torch.is_tensor(lens) else lens), dtype=torch.int64).clamp(1, T) - 1
+            last = h_2[torch.arange(B, device=x.device), idx.to(x.device)]
+        return HMLSTMResult(h_1=torch.stack(hs1, dim=1), h_2=h_2, z_1=torch.stack(zs1, dim=1), z_2=torch.stack(zs2, dim=1),
+                            hidden=(h1, c1, z1, h2, c2, z2), z_hat=torch.stack(zh).detach(), last_h2=last)
+
+    def run(self, x, hidden=None, lens=None, native=None):
+        """Everything the forward pass yields, as an HMLSTMResult.  x: [T, B, input_size]."""
+        needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())
+                                                  or (hidden is not None and any(v.requires_grad for v in hidden)))
+        why = 'a gradient is required' if needs_grad else self.native_supported(x)
+        if native is None:
+            native = why is None
+        if native:
+            if why is not None:
+                raise RuntimeError(f'HMLSTM: the native path cannot run: {why}')
+            return self._run_native(x, hidden, lens)
+        return self._run_torch(x, hidden, lens)
+
+    def forward(self, x, hidden=None, lens=None, native=None):
+        """-> (h_1, h_2, z_1, z_2, hidden), the reference's return value (hmrnn.py:154)."""
+        r = self.run(x, hidden, lens, native)
+        return r.h_1, r.h_2, r.z_1, r.z_2, r.hidden
+
+
+class HMRNNHead(nn.Module):
+    """rnn_clf.HMRNN (rnn_clf.py:122-164), the classifier model.py:110 ships: a 2-layer bidirectional GRU (halves summed, 200
+    wide), F.dropout(.., 0.2) on its output in EVERY mode (rnn_clf.py:138), the HM-LSTM over the max(len0) rows of it, and
+    feat = [sum / len | max over those rows, zero rows included | h_2 at len - 1] -> Linear(600, 20) -> F.dropout(.., 0.2).
+    ``dropout=False`` returns the values in front of both dropouts.  forward -> (logits, feat).  Parameter names and order
+    equal the real class's ``named_parameters()``."""
+    hir = 5
+
+    def __init__(self, feat_size=39):
+        super().__init__()
+        self.hidden_size = 200
+        self.enc1 = _DynEnc(feat_size, 200, 2)
+        self.enc2 = HMLSTM(1.0, 200, [200, 200])
+        self.out = nn.Linear(600, 20)
+
+    def forward(self, inp, len0, dropout=True, native=None):
+        len0 = np.asarray(len0.cpu() if torch.is_tensor(len0) else len0)
+        enc = self.enc1(inp, len0)                                                    # [max(len0), B, 200]
+        if dropout:
+            enc = torch.nn.functional.dropout(enc, 0.2)
+        last = self.enc2.run(enc, None, lens=len0, native=native).last_h2             # rnn_clf.py:139-143
+        n = torch.as_tensor(len0, dtype=enc.dtype, device=enc.device)
+        feat = torch.cat([enc.sum(0) / n.unsqueeze(1), enc.max(0).values, last], dim=1)
+        out = self.out(feat)
+        return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
+
+    def adjust_param(self):
+        """rnn_clf.py:163-164: the slope schedule, +0.5 per call (see HMLSTM on what the reference's own cells read)."""
+        self.enc2.a += 0.5
 
 
 def fill_parameters(module, seed):

@@ -435,6 +435,51 @@ int dsp_pitch_feature_batch(const double* d_pitch, const double* d_amp, const in
 int dsp_pitch_smooth_subseq_batch(const double* d_values, const int64_t* d_offsets, int32_t n_utt, int32_t tor,
                                   double thres, double* d_seg, int32_t* d_info, void* stream);
 
+/* ---- the HMRNN classifier's recurrence (hmrnn.HM_LSTM, the `enc2` of rnn_clf.HMRNN) --------- */
+/*
+ * Forward pass of hmrnn.HM_LSTM (hmrnn.py:114-154) over its two hmrnn.HM_LSTMCell (hmrnn.py:73-111), fp32, for a whole
+ * batch in ONE persistent launch (csrc/kernels_hmlstm.h): a workgroup owns 16 batch columns for all T steps and never
+ * waits on another one.
+ *
+ * The desc carries DEVICE pointers to the seven parameters in the reference's own row-major layout (hmrnn.py:60-64):
+ *   cell_1: U_11 [4 H1 + 1, H1], U_21 [4 H1 + 1, H2], W_01 [4 H1 + 1, input_size], bias [4 H1 + 1]
+ *   cell_2: U_11 [4 H2 + 1, H2],                      W_01 [4 H2 + 1, H1],         bias [4 H2 + 1]
+ * (rows f | i | o | g | z, hmrnn.py:86-90).  input_size, hidden1 and hidden2 are independent, each a multiple of 4 in
+ * [4, 256]; anything else is DSP_EINVAL, checked before any device call.  Create repacks the parameters into the
+ * kernel's layout on the current device (it waits for the device before and after, so it must not run inside a stream
+ * capture); the handle holds its own copy, is immutable afterwards and may be used from several streams.
+ */
+typedef struct dsp_hmlstm dsp_hmlstm;
+typedef struct dsp_hmlstm_desc {
+    int32_t input_size, hidden1, hidden2;
+    int32_t reserved;
+    const float* d_c1_U11;
+    const float* d_c1_U21;
+    const float* d_c1_W01;
+    const float* d_c1_bias;
+    const float* d_c2_U11;
+    const float* d_c2_W01;
+    const float* d_c2_bias;
+} dsp_hmlstm_desc;
+int dsp_hmlstm_create(const dsp_hmlstm_desc* desc, dsp_hmlstm** out);
+int dsp_hmlstm_destroy(dsp_hmlstm* h);
+/*
+ * d_x [T, B, input_size] fp32, 16-byte aligned.  a: the slope of hard_sigm (hmrnn.py:25-28,90), per call because
+ * rnn_clf.HMRNN.adjust_param (rnn_clf.py:163-164) changes it between epochs.  d_len [B] int32 or NULL (= T everywhere;
+ * values are clamped to [1, T]).  d_state_in / d_state_out: the reference's `hidden` tuple (hmrnn.py:130-138,153) as one
+ * fp32 buffer  h1 [H1, B] | c1 [H1, B] | z1 [B] | h2 [H2, B] | c2 [H2, B] | z2 [B];  d_state_in == NULL means zeros, and
+ * the two may be the same buffer.  Every output may be NULL (not all of them):
+ *   d_h1 [B, T, H1], d_h2 [B, T, H2]   hmrnn.py:148-149,154
+ *   d_z1, d_z2 [B, T] uint8            the boundary bits, hmrnn.py:150-151
+ *   d_zhat [T, 2, B] fp32              hard_sigm in front of the threshold (cell 1, cell 2), hmrnn.py:90
+ *   d_last_h2 [B, H2]                  h_2[b, len[b] - 1], rnn_clf.py:140-143
+ * All T steps are run for every column.  One launch on `stream`, no workspace, no allocation: the call can be captured
+ * into a HIP graph.
+ */
+int dsp_hmlstm_forward(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
+                       const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1,
+                       uint8_t* d_z2, float* d_zhat, float* d_last_h2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
