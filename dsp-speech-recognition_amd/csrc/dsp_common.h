@@ -104,6 +104,10 @@ __device__ __forceinline__ float dsp_load_sample(const void* __restrict__ wave, 
     }
 }
 
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
+    return make_float2(fmaf(a.x, b.x, -a.y * b.y), fmaf(a.x, b.y, a.y * b.x));
+}
+
 __device__ __forceinline__ float dsp_wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

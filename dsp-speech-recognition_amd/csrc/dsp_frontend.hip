@@ -517,6 +517,12 @@ void dispatch_cepstrum_frame_len(int32_t frame_len, F&& f) {
     }
 }
 
+// pitch_scores_kernel_v2 is instantiated for W = 3 and 4 outputs per lane and half: f(std::integral_constant<int, W>).
+template <class F>
+void dispatch_pitch_v2_width(int W, F&& f) {
+    if (W == 3) f(std::integral_constant<int, 3>{}); else f(std::integral_constant<int, 4>{});
+}
+
 // diagnostic builds only: sums a kernel's per-phase shader-clock stamps (`sym`: [slots][n_stamp] on the device) over the
 // slots into out[0 .. min(n, n_stamp)) and zeroes them
 template <class Sym>
@@ -1035,23 +1041,18 @@ int dsp_pitch_scores_batch(const float* d_sig, const int64_t* d_sample_offsets, 
     // register-blocked kernel (one wave per frame) where its shape constraints hold
     const int n_lags = lag_max - lag_min;
     const int W = frame_len <= 384 ? 3 : (frame_len <= 512 ? 4 : 0);
+    const float2* tp = reinterpret_cast<const float2*>(d_taps);
     if (W != 0 && (lag_min % 4) == 0 && n_lags <= 256 && lag_max + 8 <= PITCH2_GUARD && !g_force_generic) {
-        const int Lp = (frame_len + W - 1) / W * W;
-        const size_t lds2 = (2 * (size_t)Lp + 2 * (size_t)Lp + (size_t)Lp + PITCH2_GUARD) * sizeof(float);
-        const float2* tp = reinterpret_cast<const float2*>(d_taps);
-        if (W == 3)
-            pitch_scores_kernel_v2<3><<<(int)n_frames_total, 64, lds2, (hipStream_t)stream>>>(
+        dispatch_pitch_v2_width(W, [&](auto w) {
+            constexpr int Wc = decltype(w)::value;
+            pitch_scores_kernel_v2<Wc><<<(int)n_frames_total, 64, pitch_scores_v2_lds_bytes<Wc>(frame_len), (hipStream_t)stream>>>(
                 d_sig, bg, frame_len, frame_step, P, tp, center_clip ? 1 : 0, lag_min, n_lags, d_scores);
-        else
-            pitch_scores_kernel_v2<4><<<(int)n_frames_total, 64, lds2, (hipStream_t)stream>>>(
-                d_sig, bg, frame_len, frame_step, P, tp, center_clip ? 1 : 0, lag_min, n_lags, d_scores);
+        });
         HIP_TRY(hipGetLastError());
         return DSP_OK;
     }
-    const size_t lds = ((size_t)P + (size_t)((frame_len + 3) & ~3) + 3 * (size_t)frame_len) * sizeof(float);
-    pitch_scores_kernel<<<(int)n_frames_total, PITCH_THREADS, lds, (hipStream_t)stream>>>(
-        d_sig, bg, frame_len, frame_step, P, reinterpret_cast<const float2*>(d_taps), center_clip ? 1 : 0, lag_min,
-        lag_max - lag_min, d_scores);
+    pitch_scores_kernel<<<(int)n_frames_total, PITCH_THREADS, pitch_scores_lds_bytes(frame_len, P), (hipStream_t)stream>>>(
+        d_sig, bg, frame_len, frame_step, P, tp, center_clip ? 1 : 0, lag_min, n_lags, d_scores);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }

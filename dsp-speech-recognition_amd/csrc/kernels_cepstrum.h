@@ -3,19 +3,12 @@
 //   pitch_cepstrum_kernel        per frame: centre clip, complex band-pass FIR, FFT, log|.|, inverse FFT, |.|
 //   pitch_cepstrum_track_kernel  per utterance: smoothing in place, peak-width scores, arg-max, octave repair
 //   pitch_feature_kernel         per utterance: sub-endpoint, the two smooth subsequences, slopes, quadratic terms, shift
-// The first half of the frame kernel (median by bisection, register-blocked FIR) is the arithmetic of
-// pitch_scores_kernel_v2 (kernels_pitch.h), restated here for a compile-time frame length; that kernel is untouched.
 #pragma once
 
-#include "dsp_common.h"
+#include "pitch_common.h"
 
 #define PITCH_CEP_MIN_I 20        // pitch.py:232: candidates 20 .. 99 on the 10 kHz quefrency grid
 #define PITCH_CEP_NSCORE 80
-#define PITCH_CEP_LDS_FRAMES 2048 // pitch values of an utterance kept in LDS (global memory beyond)
-
-__device__ __forceinline__ float2 cep_cmul(float2 a, float2 w) {
-    return make_float2(fmaf(a.x, w.x, -a.y * w.y), fmaf(a.x, w.y, a.y * w.x));
-}
 
 // One wavefront per rectangular frame of L samples (L = 128 .. 1024, a power of two), zero padded as to_frames does.
 //   1. centre clip at the median of the non-negative samples, non-binary form      pitch.py:145-155
@@ -24,10 +17,8 @@ __device__ __forceinline__ float2 cep_cmul(float2 a, float2 w) {
 //   4. amp = sum |x| of the unclipped frame (fp64)                                  pitch.py:65
 // Lane q owns W = L / 128 consecutive FIR outputs at the bottom of the frame and W at the top, so every lane does the
 // same L + W tap products per output pair.  The transforms run in place in LDS on the buffer the clipped frame used:
-// a decimation-in-frequency forward pass leaves the spectrum bit-reversed, log|.| is pointwise, and a
-// decimation-in-time inverse pass takes bit-reversed input back to natural order, so nothing is ever permuted.
-// A twiddle of exactly one is never multiplied: a silent frame (log 0 = -inf in every bin) then gives
-// [inf, nan, nan, ...] as NumPy does.  Only rows and amp reach global memory.
+// the forward pass leaves the spectrum bit-reversed, log|.| is pointwise, and the inverse pass takes bit-reversed
+// input back to natural order, so nothing is ever permuted.  Only rows and amp reach global memory.
 template <int L>
 __global__ __launch_bounds__(64) void pitch_cepstrum_kernel(
     const float* __restrict__ sig, BatchGeom bg, int32_t S, const float2* __restrict__ taps, int32_t do_clip,
@@ -38,14 +29,10 @@ __global__ __launch_bounds__(64) void pitch_cepstrum_kernel(
     __shared__ __attribute__((aligned(16))) float2 s_h[L];        // taps; later the L / 2 twiddles
     const int lane = threadIdx.x;
     const int64_t g = blockIdx.x;
-    int32_t utt;
-    int64_t t, s0, nsamp;
-    if (bg.uniform_frames <= 0 && g >= bg.frame_off[bg.n_utt]) return;   // the grid may be sized by an upper bound of the frame count
-    dsp_locate(bg, g, utt, t, s0, nsamp);
-    const int64_t first = t * (int64_t)S;
+    int64_t first, s0, nsamp;
+    if (!pitch_frame_locate(bg, g, S, first, s0, nsamp)) return;
     float* cl = s_cl0 + L;
-    // lane owns samples lane + 64 r; order statistics are found on the bit patterns (non-negative floats order like
-    // unsigned integers), everything else is 0xffffffff
+    // lane owns samples lane + 64 r
     float xr[NR];
     uint32_t kb[NR];
     double asum = 0.0;
@@ -56,7 +43,7 @@ __global__ __launch_bounds__(64) void pitch_cepstrum_kernel(
         if (first + i < nsamp) x = sig[s0 + first + i];
         xr[r] = x;
         asum += (double)fabsf(x);
-        kb[r] = x >= 0.f ? __float_as_uint(x + 0.f) : 0xffffffffu;       // x + 0 turns -0 into +0
+        kb[r] = pitch_clip_key(x);
         s_cl0[i] = 0.f;                                                  // guard band: samples before the frame
         s_h[i] = taps[i];
     }
@@ -65,77 +52,17 @@ __global__ __launch_bounds__(64) void pitch_cepstrum_kernel(
         for (int o = 32; o > 0; o >>= 1) asum += __shfl_xor(asum, o, 64);
         if (lane == 0) amp[g] = asum;
     }
-    float med = 0.f;
-    if (do_clip) {
-        auto count_below = [&](uint32_t cand) {
-            int c = 0;
-#pragma unroll
-            for (int r = 0; r < NR; ++r) c += __popcll(__ballot(kb[r] < cand));
-            return c;
-        };
-        int m = 0;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) m += __popcll(__ballot(kb[r] != 0xffffffffu));
-        if (m > 0) {
-            // k-th smallest (0-based): the largest v with fewer than k + 1 keys below it, bit by bit
-            const int k1 = (m - 1) >> 1, k2 = m >> 1;
-            uint32_t v1 = 0;
-            for (int bit = 30; bit >= 0; --bit) {
-                const uint32_t cand = v1 | (1u << bit);
-                if (count_below(cand) <= k1) v1 = cand;
-            }
-            uint32_t v2 = v1;
-            if (k2 != k1 && count_below(v1 + 1) < k2 + 1) {
-                uint32_t mn = 0xffffffffu;                               // the next distinct key above v1
-#pragma unroll
-                for (int r = 0; r < NR; ++r) mn = (kb[r] > v1 && kb[r] < mn) ? kb[r] : mn;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const uint32_t other = (uint32_t)__shfl_xor((int)mn, o, 64);
-                    mn = other < mn ? other : mn;
-                }
-                v2 = mn;
-            }
-            med = 0.5f * (__uint_as_float(v1) + __uint_as_float(v2));    // numpy.median
-        } else {
-            med = __int_as_float(0x7fc00000);                            // no non-negative sample: NaN level, all zeros
-        }
-    }
+    const float med = do_clip ? pitch_clip_level(kb) : 0.f;
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
         const float x = xr[r];
-        cl[lane + 64 * r] = do_clip ? (x > med ? x - med : (x < -med ? x + med : 0.f)) : x;
+        cl[lane + 64 * r] = do_clip ? pitch_center_clip(x, med) : x;
     }
     __syncthreads();
     // ---- FIR: y[k] = sum_m h[m] c[k - m]; lane q owns outputs [W q, W q + W) and [L - W q - W, L - W q) ----
     const int kl = W * lane, kh = L - W * (lane + 1);
     float alr[W], ali[W], ahr[W], ahi[W];
-    {
-        float wl[W], wh[W];                                // ring: the sample at position p sits in slot p % W
-#pragma unroll
-        for (int e = 0; e < W; ++e) {
-            wl[e] = cl[kl + e];
-            wh[e] = cl[kh + e];
-            alr[e] = ali[e] = ahr[e] = ahi[e] = 0.f;
-        }
-        for (int m0 = 0; m0 < L; m0 += W) {
-#pragma unroll
-            for (int j = 0; j < W; ++j) {
-                const int m = m0 + j;
-                if (m > 0) {                               // position k0 - m enters slot (-m) % W == (W - j) % W
-                    wl[(W - j) % W] = cl[kl - m];
-                    wh[(W - j) % W] = cl[kh - m];
-                }
-                const float2 hm = s_h[m];
-#pragma unroll
-                for (int e = 0; e < W; ++e) {
-                    const float vl = wl[(e - j + W) % W], vh = wh[(e - j + W) % W];
-                    alr[e] = fmaf(hm.x, vl, alr[e]); ali[e] = fmaf(hm.y, vl, ali[e]);
-                    ahr[e] = fmaf(hm.x, vh, ahr[e]); ahi[e] = fmaf(hm.y, vh, ahi[e]);
-                }
-            }
-        }
-    }
+    pitch_fir_pair<W>(cl, s_h, kl, kh, L, alr, ali, ahr, ahi);
     __syncthreads();                                       // the clipped frame and the taps are dead from here
     float2* buf = reinterpret_cast<float2*>(s_cl0);        // [L] complex points
     float2* tw = s_h;                                      // [L / 2] exp(-2 pi i k / L)
@@ -150,40 +77,13 @@ __global__ __launch_bounds__(64) void pitch_cepstrum_kernel(
         tw[k] = make_float2(cs, -sn);
     }
     __syncthreads();
-    // ---- forward transform, decimation in frequency: natural order in, bit-reversed out ----
-    for (int half = L / 2; half >= 1; half >>= 1) {
-        const int tstep = (L / 2) / half;
-        for (int b = lane; b < L / 2; b += 64) {
-            const int j = b & (half - 1), i0 = ((b - j) << 1) + j, i1 = i0 + half;
-            const float2 u = buf[i0], v = buf[i1];
-            float2 d = make_float2(u.x - v.x, u.y - v.y);
-            if (j) d = cep_cmul(d, tw[j * tstep]);
-            buf[i0] = make_float2(u.x + v.x, u.y + v.y);
-            buf[i1] = d;
-        }
-        __syncthreads();
-    }
+    pitch_fft_dif<L>(buf, tw, lane);
     for (int i = lane; i < L; i += 64) {                   // log|X|; a zero bin is -inf, as NumPy
         const float2 v = buf[i];
         buf[i] = make_float2(logf(sqrtf(fmaf(v.x, v.x, v.y * v.y))), 0.f);
     }
     __syncthreads();
-    // ---- inverse transform, decimation in time with conjugate twiddles: bit-reversed in, natural order out ----
-    for (int half = 1; half <= L / 2; half <<= 1) {
-        const int tstep = (L / 2) / half;
-        for (int b = lane; b < L / 2; b += 64) {
-            const int j = b & (half - 1), i0 = ((b - j) << 1) + j, i1 = i0 + half;
-            const float2 u = buf[i0];
-            float2 v = buf[i1];
-            if (j) {
-                const float2 w = tw[j * tstep];
-                v = cep_cmul(v, make_float2(w.x, -w.y));
-            }
-            buf[i0] = make_float2(u.x + v.x, u.y + v.y);
-            buf[i1] = make_float2(u.x - v.x, u.y - v.y);
-        }
-        __syncthreads();
-    }
+    pitch_ifft_dit<L>(buf, tw, lane);
     float* out = rows + g * (int64_t)L;
     for (int i = lane; i < L; i += 64) {
         const float2 v = buf[i];
@@ -192,10 +92,8 @@ __global__ __launch_bounds__(64) void pitch_cepstrum_kernel(
 }
 
 // The tracker behind the cepstrum rows, one wavefront per utterance, fp64, sequential over the frames:
-//   flags bit 0  pitch.smooth(rows, 2) with the habits kernels_pitch.h documents for pitch_track_kernel: rows below i are
-//                already smoothed (they are carried in registers; d_rows is not written), the window [i - 2, right) has
-//                right = i + 2 if i + 2 < T else T - 1, a one-frame utterance averages nothing (NaN), rows are added
-//                in order and divided once                                               pitch.py:157-164
+//   flags bit 0  pitch.smooth(rows, 2); the smoothed rows below i are carried in registers, d_rows is not written
+//                                                                                        pitch.py:157-164
 //   always       pitch.peak_score of the (smoothed) row: for i in [20, 100) p walks down from i while p > 0 and
 //                row[p] <= row[i], q walks up while q < L and row[q] <= row[i]; score = min(i - p, q - i).  row[0] is
 //                never compared; a NaN row scores 0 everywhere.  i - p <= 99 and a walk up longer than the walk down
@@ -207,14 +105,13 @@ __global__ __launch_bounds__(64) void pitch_cepstrum_track_kernel(const RT* __re
                                                                   const int64_t* __restrict__ frame_off, int32_t flags,
                                                                   double* __restrict__ pitch, int32_t* __restrict__ scores) {
     constexpr int NR = L / 64;
-    __shared__ double s_pitch[PITCH_CEP_LDS_FRAMES];
+    __shared__ double s_pitch[PITCH_LDS_FRAMES];
     const int u = blockIdx.x, lane = threadIdx.x;
     const int64_t base = frame_off[u];
     const int T = (int)(frame_off[u + 1] - base);
     if (T <= 0) return;
     const RT* rw = rows + base * L;
-    double* out = (flags & 2) ? pitch + base : nullptr;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    const PitchTrackStore<double> track{s_pitch, (flags & 2) ? pitch + base : nullptr};
     double p2[NR], p1[NR];                  // smoothed rows i - 2 and i - 1 (columns lane, lane + 64, ...)
 #pragma unroll
     for (int k = 0; k < NR; ++k) p2[k] = p1[k] = 0.0;
@@ -231,23 +128,13 @@ __global__ __launch_bounds__(64) void pitch_cepstrum_track_kernel(const RT* __re
 #pragma unroll
         for (int k = 0; k < NR; ++k) rc[k] = i + 2 < T ? (double)rw[(int64_t)(i + 2) * L + lane + 64 * k] : 0.0;
         if (flags & 1) {
-            const int left = i - 2 >= 0 ? i - 2 : 0;
-            const int right = i + 2 < T ? i + 2 : T - 1;          // exclusive, <= i + 2
-            const int cnt = right - left;
+            int left, right;                                      // right <= i + 2
+            pitch_window_bounds(i, 2, T, left, right);
 #pragma unroll
             for (int k = 0; k < NR; ++k) {
-                double acc = qnan;
-                if (cnt > 0) {
-                    bool have = false;
-                    acc = 0.0;
-                    for (int r = left; r < right; ++r) {          // rows in order, as numpy's add.reduce over axis 0
-                        const double v = r == i - 2 ? p2[k] : (r == i - 1 ? p1[k] : (r == i ? ra[k] : rb[k]));
-                        acc = have ? acc + v : v;
-                        have = true;
-                    }
-                    acc = acc / (double)cnt;
-                }
-                cur[k] = acc;
+                cur[k] = pitch_window_mean(left, right, [&](int r) {
+                    return r == i - 2 ? p2[k] : (r == i - 1 ? p1[k] : (r == i ? ra[k] : rb[k]));
+                });
             }
         } else {
 #pragma unroll
@@ -286,29 +173,14 @@ __global__ __launch_bounds__(64) void pitch_cepstrum_track_kernel(const RT* __re
             scores[(base + i) * PITCH_CEP_NSCORE + lane] = mine[0];
             if (lane + 64 < PITCH_CEP_NSCORE) scores[(base + i) * PITCH_CEP_NSCORE + 64 + lane] = mine[1];
         }
-        if ((flags & 2) && lane == 0) {
-            const double p = 1.0 / (0.0001 * (double)(PITCH_CEP_MIN_I + bi));         // pitch.py:169-170
-            if (i < PITCH_CEP_LDS_FRAMES) s_pitch[i] = p; else out[i] = p;
-        }
+        if ((flags & 2) && lane == 0) track.put(i, pitch_hz(PITCH_CEP_MIN_I, bi));
 #pragma unroll
         for (int k = 0; k < NR; ++k) { p2[k] = p1[k]; p1[k] = cur[k]; ra[k] = rb[k]; rb[k] = rc[k]; }
     }
     if (!(flags & 2)) return;
-    if (lane == 0) {
-        auto get = [&](int i) { return i < PITCH_CEP_LDS_FRAMES ? s_pitch[i] : out[i]; };
-        auto put = [&](int i, double v) { if (i < PITCH_CEP_LDS_FRAMES) s_pitch[i] = v; else out[i] = v; };
-        const double C = 50.0;
-        for (int i = 1; i < T; ++i) {                              // pitch.py:199-201
-            const double p = get(i);
-            if (fabs(2.0 * p - get(i - 1)) < C && p < 170.0) put(i, 2.0 * p);
-        }
-        for (int i = T - 2; i > 0; --i) {                          // pitch.py:202-204
-            const double p = get(i);
-            if (fabs(2.0 * p - get(i + 1)) < C && p < 170.0) put(i, 2.0 * p);
-        }
-    }
+    if (lane == 0) pitch_octave_repair([&](int i) { return track.get(i); }, [&](int i, double v) { track.put(i, v); }, T);
     __syncthreads();
-    for (int i = lane; i < T && i < PITCH_CEP_LDS_FRAMES; i += 64) out[i] = s_pitch[i];
+    track.flush(T, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -407,7 +279,7 @@ __device__ __forceinline__ double pitch_wave_median(const double* __restrict__ v
 __global__ __launch_bounds__(64) void pitch_feature_kernel(const double* __restrict__ pitch, const double* __restrict__ amp,
                                                            const int64_t* __restrict__ frame_off, double* __restrict__ seg,
                                                            double* __restrict__ feat, int32_t* __restrict__ aux) {
-    __shared__ double s_pitch[PITCH_CEP_LDS_FRAMES];
+    __shared__ double s_pitch[PITCH_LDS_FRAMES];
     __shared__ double s_fit[4], s_two[2];
     __shared__ int s_seg[6];
     const int u = blockIdx.x, lane = threadIdx.x;
@@ -440,13 +312,13 @@ __global__ __launch_bounds__(64) void pitch_feature_kernel(const double* __restr
         return;
     }
     const int p_bias = p > 15 ? 5 : 0;
-    const double* pg = pitch + base;
-    for (int i = lane; i < T && i < PITCH_CEP_LDS_FRAMES; i += 64) s_pitch[i] = pg[i];
+    const PitchTrackStore<const double> track{s_pitch, pitch + base};
+    track.load(T, lane);
     __syncthreads();
     if (lane == 0) {
         for (int h = 0; h < 2; ++h) {
             const int lo = h == 0 ? p_bias : p, n = h == 0 ? p - p_bias : T - p;
-            auto get = [&](int i) { return lo + i < PITCH_CEP_LDS_FRAMES ? s_pitch[lo + i] : pg[lo + i]; };
+            auto get = [&](int i) { return track.get(lo + i); };
             const PitchSubseq s = pitch_subseq_best(get, n > 0 ? n : 0, 3, 30.0);
             const int m = s.count;
             const double xm = 0.5 * (double)(m - 1), c2 = ((double)m * (double)m - 1.0) / 12.0;

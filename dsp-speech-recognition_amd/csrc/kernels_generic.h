@@ -25,10 +25,6 @@ struct GenericParams {
     int32_t radix[DSP_MAX_RADIX_PASSES];
 };
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-    return make_float2(fmaf(a.x, b.x, -a.y * b.y), fmaf(a.x, b.y, a.y * b.x));
-}
-
 // One Stockham pass of radix R over n complex points held in LDS (in -> out), executed by one wave.
 // p = product of the radices of the previous passes.  Thread j handles inputs j + r*n/R.
 template <int R>

@@ -8,10 +8,15 @@
 // repair) is O(T * lags) sequential host logic in the Python mirror, as in the reference.
 #pragma once
 
-#include "dsp_common.h"
+#include "pitch_common.h"
 
 #define PITCH_THREADS 256
 #define PITCH_MAX_L 1024
+
+// dynamic LDS of pitch_scores_kernel: the carve-up at its top, in bytes
+inline size_t pitch_scores_lds_bytes(int L, int P) {
+    return ((size_t)P + (size_t)((L + 3) & ~3) + 2 * (size_t)L + (size_t)L) * sizeof(float);
+}
 
 // frames: rectangular, frame t = samples [t S, t S + L) of the utterance, zero padded (to_frames).
 __global__ __launch_bounds__(PITCH_THREADS) void pitch_scores_kernel(
@@ -26,11 +31,8 @@ __global__ __launch_bounds__(PITCH_THREADS) void pitch_scores_kernel(
     __shared__ int s_m;
     const int tid = threadIdx.x;
     const int64_t g = blockIdx.x;
-    int32_t utt;
-    int64_t t, s0, nsamp;
-    if (bg.uniform_frames <= 0 && g >= bg.frame_off[bg.n_utt]) return;   // the grid may be sized by an upper bound of the frame count
-    dsp_locate(bg, g, utt, t, s0, nsamp);
-    const int64_t first = t * (int64_t)S;
+    int64_t first, s0, nsamp;
+    if (!pitch_frame_locate(bg, g, S, first, s0, nsamp)) return;
     if (tid == 0) s_m = 0;
     __syncthreads();
     // ---- load the frame; sort keys: non-negative samples, everything else +inf ----
@@ -109,14 +111,20 @@ __global__ __launch_bounds__(PITCH_THREADS) void pitch_scores_kernel(
 }
 
 // Register-blocked variant, one wavefront per frame.  Every lane owns W consecutive FIR outputs at
-// the bottom of the frame and W at the top (so all lanes do the same work), keeps the 2 W samples it
-// needs in a register ring and reads one new sample per chunk and tap: 3 LDS reads per 4 W
-// multiply-adds instead of 3 per 4.  Indices below zero fall into a zeroed guard band, so the tap
-// loop is uniform and branch free.  The autocorrelation is blocked the same way (4 lags per lane).
-// The clip level (median of the non-negative samples) comes from a 31-step bisection on the float bit
-// patterns held in registers (ballot + popcount per step): no sort, no LDS, no barrier.
+// the bottom of the frame and W at the top, so all lanes do the same work in pitch_fir_pair: 3 LDS
+// reads per 4 W multiply-adds instead of 3 per 4.  The frame length is a run-time value here, so
+// outputs and taps are padded to Lp, the next multiple of W.  The autocorrelation is blocked the same
+// way (4 lags per lane).  The clip level comes from the frame's bit patterns held in registers
+// (pitch_clip_level): no sort, no LDS, no barrier.
 // Requires lag_min % 4 == 0, n_lags <= 256, ceil(L / (2 W)) <= 64 (so L <= 512).
 #define PITCH2_GUARD 256   // zeros behind f[] (>= lag_max + 4)
+
+// dynamic LDS of pitch_scores_kernel_v2<W>: the carve-up at its top, in bytes
+template <int W>
+inline size_t pitch_scores_v2_lds_bytes(int L) {
+    const size_t Lp = (size_t)((L + W - 1) / W * W);
+    return (2 * Lp + 2 * Lp + Lp + PITCH2_GUARD) * sizeof(float);
+}
 
 template <int W>
 __global__ __launch_bounds__(64) void pitch_scores_kernel_v2(
@@ -130,14 +138,10 @@ __global__ __launch_bounds__(64) void pitch_scores_kernel_v2(
     (void)P;
     const int lane = threadIdx.x;
     const int64_t g = blockIdx.x;
-    int32_t utt;
-    int64_t t, s0, nsamp;
-    if (bg.uniform_frames <= 0 && g >= bg.frame_off[bg.n_utt]) return;   // the grid may be sized by an upper bound of the frame count
-    dsp_locate(bg, g, utt, t, s0, nsamp);
-    const int64_t first = t * (int64_t)S;
+    int64_t first, s0, nsamp;
+    if (!pitch_frame_locate(bg, g, S, first, s0, nsamp)) return;
     float* cl = cl0 + Lp;
-    // frame samples: lane owns elements lane + 64 r (r < 8, L <= 512); order statistics are found on
-    // the bit patterns (non-negative floats order like unsigned integers), everything else is 0xffffffff
+    // frame samples: lane owns elements lane + 64 r (r < 8, L <= 512)
     float xr[8];
     uint32_t kb[8];
 #pragma unroll
@@ -147,8 +151,7 @@ __global__ __launch_bounds__(64) void pitch_scores_kernel_v2(
         const bool in = i < L;
         if (in && first + i < nsamp) x = sig[s0 + first + i];
         xr[r] = x;
-        const bool nn = in && x >= 0.f;
-        kb[r] = nn ? __float_as_uint(x + 0.f) : 0xffffffffu;        // x + 0 turns -0 into +0
+        kb[r] = in ? pitch_clip_key(x) : 0xffffffffu;
     }
     for (int i = lane; i < Lp; i += 64) {
         cl0[i] = 0.f;                                      // guard band: samples before the frame
@@ -156,50 +159,13 @@ __global__ __launch_bounds__(64) void pitch_scores_kernel_v2(
         h[i] = i < L ? taps[i] : make_float2(0.f, 0.f);
     }
     for (int i = lane; i < Lp + PITCH2_GUARD; i += 64) f[i] = 0.f;
-    float med = 0.f;
-    if (do_clip) {
-        // wave-wide count of keys below a candidate: one v_cmp per register, popcount of the masks
-        auto count_below = [&](uint32_t cand) {
-            int c = 0;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) c += __popcll(__ballot(kb[r] < cand));
-            return c;
-        };
-        int m = 0;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) m += __popcll(__ballot(kb[r] != 0xffffffffu));
-        if (m > 0) {
-            // k-th smallest (0-based): the largest v with fewer than k + 1 keys below it, bit by bit
-            const int k1 = (m - 1) >> 1, k2 = m >> 1;
-            uint32_t v1 = 0;
-            for (int bit = 30; bit >= 0; --bit) {
-                const uint32_t cand = v1 | (1u << bit);
-                if (count_below(cand) <= k1) v1 = cand;
-            }
-            uint32_t v2 = v1;
-            if (k2 != k1 && count_below(v1 + 1) < k2 + 1) {
-                // the next distinct key above v1
-                uint32_t mn = 0xffffffffu;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) mn = (kb[r] > v1 && kb[r] < mn) ? kb[r] : mn;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const uint32_t other = (uint32_t)__shfl_xor((int)mn, o, 64);
-                    mn = other < mn ? other : mn;
-                }
-                v2 = mn;
-            }
-            med = 0.5f * (__uint_as_float(v1) + __uint_as_float(v2));     // numpy.median
-        } else {
-            med = __int_as_float(0x7fc00000);              // no non-negative sample: NaN clip level
-        }
-    }
+    const float med = do_clip ? pitch_clip_level(kb) : 0.f;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const int i = lane + 64 * r;
         if (i < L) {
             const float x = xr[r];
-            cl[i] = do_clip ? (x > med ? x - med : (x < -med ? x + med : 0.f)) : x;
+            cl[i] = do_clip ? pitch_center_clip(x, med) : x;
         }
     }
     __syncthreads();
@@ -207,31 +173,8 @@ __global__ __launch_bounds__(64) void pitch_scores_kernel_v2(
     const int nchunk = (Lp / W + 1) / 2;
     if (lane < nchunk) {
         const int kl = W * lane, kh = Lp - W * (lane + 1);
-        float wl[W], wh[W];                                // ring: the sample at position p sits in slot p % W
         float alr[W], ali[W], ahr[W], ahi[W];
-#pragma unroll
-        for (int e = 0; e < W; ++e) {
-            wl[e] = cl[kl + e];
-            wh[e] = cl[kh + e];
-            alr[e] = ali[e] = ahr[e] = ahi[e] = 0.f;
-        }
-        for (int m0 = 0; m0 < Lp; m0 += W) {
-#pragma unroll
-            for (int j = 0; j < W; ++j) {
-                const int m = m0 + j;
-                if (m > 0) {                               // position k0 - m enters slot (-m) % W == (W - j) % W
-                    wl[(W - j) % W] = cl[kl - m];
-                    wh[(W - j) % W] = cl[kh - m];
-                }
-                const float2 hm = h[m];
-#pragma unroll
-                for (int e = 0; e < W; ++e) {
-                    const float vl = wl[(e - j + W) % W], vh = wh[(e - j + W) % W];
-                    alr[e] = fmaf(hm.x, vl, alr[e]); ali[e] = fmaf(hm.y, vl, ali[e]);
-                    ahr[e] = fmaf(hm.x, vh, ahr[e]); ahi[e] = fmaf(hm.y, vh, ahi[e]);
-                }
-            }
-        }
+        pitch_fir_pair<W>(cl, h, kl, kh, Lp, alr, ali, ahr, ahi);
 #pragma unroll
         for (int e = 0; e < W; ++e) {
             if (kl + e < L) f[kl + e] = sqrtf(fmaf(alr[e], alr[e], ali[e] * ali[e]));
@@ -272,89 +215,49 @@ __global__ __launch_bounds__(64) void pitch_scores_kernel_v2(
 // ------------------------------------------------------------------------------------------------
 // The tracker behind the scores: pitch.smooth (pitch.py:157-164), pitch.max_pitch (pitch.py:166-172) and the two
 // octave-repair sweeps of pitch.robust_max_pitch (pitch.py:191-206) for a whole batch, one wavefront per utterance.
-// Everything is sequential over the frames of an utterance in the reference, and two of its habits must be kept:
-//   * smooth() works IN PLACE: row i becomes the mean of rows [max(i - 2, 0), right) where rows below i are already
-//     smoothed and `right = i + 2 if i + 2 < T else T - 1` (so the last rows average over a window that EXCLUDES
-//     the last row, and a one-frame utterance averages over nothing: NaN, whose arg-max is index 0);
-//   * numpy's mean adds the rows in order and divides once; arg-max takes the first maximum (the first NaN if any).
-// fp64 throughout, as the reference (its scores are this library's fp32 scores promoted to double).
+// The pieces, and the habits of the reference they keep, are pitch_common.h's; here the two smoothed rows below row i
+// are carried in registers and the raw rows come from global memory.  fp64 throughout, as the reference (its scores are
+// this library's fp32 scores promoted to double).
 // ------------------------------------------------------------------------------------------------
-#define PITCH_TRACK_LDS_FRAMES 2048   // pitch values of an utterance kept in LDS for the repair sweeps (global memory beyond)
-
-__device__ __forceinline__ void pitch_argmax_combine(double& v, int& ix, double ov, int oix) {
-    // numpy.argmax order: a NaN beats everything, then the larger value, then the smaller index
-    const bool vn = v != v, on = ov != ov;
-    const bool take = (on && !vn) || (on == vn && (ov > v || (ov == v && oix < ix))) || (on && vn && oix < ix);
-    if (take) { v = ov; ix = oix; }
-}
-
 __global__ __launch_bounds__(64) void pitch_track_kernel(const float* __restrict__ scores,
                                                          const int64_t* __restrict__ frame_off, int32_t n_lags,
                                                          int32_t bias, double* __restrict__ pitch) {
-    __shared__ double s_pitch[PITCH_TRACK_LDS_FRAMES];
+    __shared__ double s_pitch[PITCH_LDS_FRAMES];
     const int u = blockIdx.x, lane = threadIdx.x;
     const int64_t base = frame_off[u];
     const int T = (int)(frame_off[u + 1] - base);
     if (T <= 0) return;
     const float* sc = scores + base * n_lags;
-    double* out = pitch + base;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    const PitchTrackStore<double> track{s_pitch, pitch + base};
     double p2[4], p1[4];                    // smoothed rows i - 2 and i - 1 (lags lane, lane + 64, ...)
 #pragma unroll
     for (int k = 0; k < 4; ++k) p2[k] = p1[k] = 0.0;
     for (int i = 0; i < T; ++i) {
-        const int left = i - 2 >= 0 ? i - 2 : 0;
-        const int right = i + 2 < T ? i + 2 : T - 1;          // exclusive
-        const int cnt = right - left;
+        int left, right;
+        pitch_window_bounds(i, 2, T, left, right);
         double cur[4];
         double bv = -__longlong_as_double(0x7ff0000000000000ll);   // -inf, index "none": loses to every real candidate
         int bi = 0x7fffffff;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int lag = lane + 64 * k;
-            double acc = qnan;
-            if (lag < n_lags && cnt > 0) {
-                bool have = false;
-                acc = 0.0;
-                for (int r = left; r < right; ++r) {          // rows in order, as numpy's add.reduce over axis 0
-                    const double v = r == i - 2 ? p2[k] : (r == i - 1 ? p1[k] : (double)sc[(int64_t)r * n_lags + lag]);
-                    acc = have ? acc + v : v;
-                    have = true;
-                }
-                acc = acc / (double)cnt;
+            cur[k] = 0.0;
+            if (lag < n_lags) {
+                cur[k] = pitch_window_mean(left, right, [&](int r) {
+                    return r == i - 2 ? p2[k] : (r == i - 1 ? p1[k] : (double)sc[(int64_t)r * n_lags + lag]);
+                });
+                pitch_argmax_combine(bv, bi, cur[k], lag);
             }
-            cur[k] = acc;
-            if (lag < n_lags) pitch_argmax_combine(bv, bi, acc, lag);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            pitch_argmax_combine(bv, bi, ov, oi);
-        }
-        if (lane == 0) {
-            const double p = 1.0 / (0.0001 * (double)(bias + bi));        // pitch.py:169-170
-            if (i < PITCH_TRACK_LDS_FRAMES) s_pitch[i] = p; else out[i] = p;
-        }
+        pitch_wave_argmax(bv, bi);
+        if (lane == 0) track.put(i, pitch_hz(bias, bi));
 #pragma unroll
         for (int k = 0; k < 4; ++k) { p2[k] = p1[k]; p1[k] = cur[k]; }
     }
     __syncthreads();
-    if (lane == 0) {
-        auto get = [&](int i) { return i < PITCH_TRACK_LDS_FRAMES ? s_pitch[i] : out[i]; };
-        auto put = [&](int i, double v) { if (i < PITCH_TRACK_LDS_FRAMES) s_pitch[i] = v; else out[i] = v; };
-        const double C = 50.0;
-        for (int i = 1; i < T; ++i) {                          // pitch.py:199-201
-            const double p = get(i);
-            if (fabs(2.0 * p - get(i - 1)) < C && p < 170.0) put(i, 2.0 * p);
-        }
-        for (int i = T - 2; i > 0; --i) {                      // pitch.py:202-204
-            const double p = get(i);
-            if (fabs(2.0 * p - get(i + 1)) < C && p < 170.0) put(i, 2.0 * p);
-        }
-    }
+    if (lane == 0) pitch_octave_repair([&](int i) { return track.get(i); }, [&](int i, double v) { track.put(i, v); }, T);
     __syncthreads();
-    for (int i = lane; i < T && i < PITCH_TRACK_LDS_FRAMES; i += 64) out[i] = s_pitch[i];
+    track.flush(T, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -467,46 +370,24 @@ __global__ __launch_bounds__(64) void pitch_rows_kernel(double* __restrict__ row
     if (T <= 0) return;
     double* g = rows + base * n_lags;
     double* out = pitch ? pitch + base : nullptr;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
     for (int i = 0; i < T; ++i) {
         double bv = -__longlong_as_double(0x7ff0000000000000ll);
         int bi = 0x7fffffff;
         for (int lag = lane; lag < n_lags; lag += 64) {
             double cur = g[(int64_t)i * n_lags + lag];
             if (flags & 1) {
-                const int left = i - degree >= 0 ? i - degree : 0;
-                const int right = i + degree < T ? i + degree : T - 1;      // exclusive
-                double acc = qnan;
-                bool have = false;
-                for (int r = left; r < right; ++r) {                         // rows in order (rows < i: already smoothed, same lane wrote them)
-                    const double v = g[(int64_t)r * n_lags + lag];
-                    acc = have ? acc + v : v;
-                    have = true;
-                }
-                cur = have ? acc / (double)(right - left) : qnan;
+                int left, right;
+                pitch_window_bounds(i, degree, T, left, right);
+                // rows below i are already smoothed: the same lane wrote them
+                cur = pitch_window_mean(left, right, [&](int r) { return g[(int64_t)r * n_lags + lag]; });
                 g[(int64_t)i * n_lags + lag] = cur;
             }
             pitch_argmax_combine(bv, bi, cur, lag);
         }
         if (flags & 2) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double ov = __shfl_xor(bv, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                pitch_argmax_combine(bv, bi, ov, oi);
-            }
-            if (lane == 0) out[i] = 1.0 / (0.0001 * (double)(bias + bi));
+            pitch_wave_argmax(bv, bi);
+            if (lane == 0) out[i] = pitch_hz(bias, bi);
         }
     }
-    if ((flags & 4) && lane == 0) {
-        const double C = 50.0;
-        for (int i = 1; i < T; ++i) {
-            const double p = out[i];
-            if (fabs(2.0 * p - out[i - 1]) < C && p < 170.0) out[i] = 2.0 * p;
-        }
-        for (int i = T - 2; i > 0; --i) {
-            const double p = out[i];
-            if (fabs(2.0 * p - out[i + 1]) < C && p < 170.0) out[i] = 2.0 * p;
-        }
-    }
+    if ((flags & 4) && lane == 0) pitch_octave_repair([&](int i) { return out[i]; }, [&](int i, double v) { out[i] = v; }, T);
 }

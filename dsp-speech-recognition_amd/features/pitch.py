@@ -27,6 +27,7 @@ import types
 import numpy as np
 
 from . import _native as nat
+from .batch import _stream_ptr
 from .endpoint import basic_endpoint_detection, get_amplitude, robust_endpoint_detection  # noqa: F401  (pitch.py:17)
 from .preprocess import downsampling, preemphasis  # noqa: F401  (pitch.py:13,24)
 from .sigproc import acr, to_frames  # noqa: F401  (pitch.py:14)
@@ -72,16 +73,19 @@ def _device_taps(L, rate, high_freq=900):
     return buf
 
 
-def frame_scores_batch(sig10k, sample_offsets, L, S, rate=10000, clip=True):
-    """[sum T_b, 180] fp32 scores for concatenated 10 kHz signals; returns (scores, frame_offsets)."""
-    nat.require_device()
-    lib = nat.load()
+def _upload_10k(sig10k, sample_offsets, L, S):
     so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
     fo = nat.frame_offsets(so, L, S)
     x = np.ascontiguousarray(sig10k, dtype=np.float32).reshape(-1)
     d_x = nat.device_array('pitch_sig', x if x.size else np.zeros(1, dtype=np.float32))
-    d_so = nat.device_array('pitch_so', so)
-    d_fo = nat.device_array('pitch_fo', fo)
+    return d_x, nat.device_array('pitch_so', so), nat.device_array('pitch_fo', fo), so, fo
+
+
+def frame_scores_batch(sig10k, sample_offsets, L, S, rate=10000, clip=True):
+    """[sum T_b, 180] fp32 scores for concatenated 10 kHz signals; returns (scores, frame_offsets)."""
+    nat.require_device()
+    lib = nat.load()
+    d_x, d_so, d_fo, so, fo = _upload_10k(sig10k, sample_offsets, L, S)
     n_lags = MAX_SHIFT - MIN_SHIFT
     d_out = nat.SCRATCH.get('pitch_scores', int(fo[-1]) * n_lags * 4)
     nat.check(lib.dsp_pitch_scores_batch(d_x.ptr, d_so.ptr, d_fo.ptr, len(so) - 1, int(fo[-1]), 0, int(L), int(S),
@@ -137,12 +141,7 @@ def pitch_tracks_batch(sig10k, sample_offsets, L, S, rate=10000):
     (dsp_pitch_track_batch; pitch.py:157-206).  Returns (pitch [sum T_b] in Hz, fp64, frame_offsets)."""
     nat.require_device()
     lib = nat.load()
-    so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
-    fo = nat.frame_offsets(so, L, S)
-    x = np.ascontiguousarray(sig10k, dtype=np.float32).reshape(-1)
-    d_x = nat.device_array('pitch_sig', x if x.size else np.zeros(1, dtype=np.float32))
-    d_so = nat.device_array('pitch_so', so)
-    d_fo = nat.device_array('pitch_fo', fo)
+    d_x, d_so, d_fo, so, fo = _upload_10k(sig10k, sample_offsets, L, S)
     n_lags = MAX_SHIFT - MIN_SHIFT
     d_scores = nat.SCRATCH.get('pitch_scores', int(fo[-1]) * n_lags * 4)
     d_pitch = nat.SCRATCH.get('pitch_track', int(fo[-1]) * 8)
@@ -152,22 +151,29 @@ def pitch_tracks_batch(sig10k, sample_offsets, L, S, rate=10000):
     return d_pitch.download((int(fo[-1]),), np.float64), fo
 
 
+def _to_10k_on_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, L, S, stream):
+    """preprocess.downsampling to 10 kHz for clips on the device (dsp_resample_layout_batch + dsp_decimate_batch) and the
+    frame offsets of the result at (L, S) -> (p_x, p_so, d_fo): signal and sample offsets as pointers, frame offsets as
+    a scratch buffer."""
+    lib = nat.load()
+    d_fo = nat.SCRATCH.get('pitch_fo10', (n_utt + 1) * 8)
+    if rate <= 10000:           # downsampling keeps every sample when the clip is at 10 kHz or below (preprocess.py:21-28)
+        nat.check(lib.dsp_resample_layout_batch(d_src_off, n_utt, int(rate), 0, int(L), int(S), None, d_fo.ptr, stream))
+        return d_clips, d_src_off, d_fo
+    d_so10 = nat.SCRATCH.get('pitch_so10', (n_utt + 1) * 8)
+    d_x10 = nat.SCRATCH.get('pitch_x10', max(4, int(n_samples_bound) * 4))
+    nat.check(lib.dsp_resample_layout_batch(d_src_off, n_utt, int(rate), 10000, int(L), int(S), d_so10.ptr, d_fo.ptr, stream))
+    nat.check(lib.dsp_decimate_batch(d_clips, d_src_off, d_so10.ptr, n_utt, int(n_samples_bound), int(rate), 10000, d_x10.ptr, stream))
+    return d_x10.ptr, d_so10.ptr, d_fo
+
+
 def pitch_tracks_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, L, S, stream=None):
     """pitch.pitch_detect_sr for clips that are already on the device (fp32, concatenated, `rate` Hz): decimation to
-    10 kHz (dsp_resample_layout_batch + dsp_decimate_batch), scores, smoothing, arg-max and octave repair, nothing
-    leaves the device.  Returns (d_pitch [fp64, one per frame], d_frame_off [B+1]) as library scratch buffers."""
+    10 kHz, scores, smoothing, arg-max and octave repair, nothing leaves the device.  `stream` is None, a raw handle or
+    a torch stream.  Returns (d_pitch [fp64, one per frame], d_frame_off [B+1]) as library scratch buffers."""
     lib = nat.load()
-    if rate > 10000:
-        d_so10 = nat.SCRATCH.get('pitch_so10', (n_utt + 1) * 8)
-        d_fo = nat.SCRATCH.get('pitch_fo10', (n_utt + 1) * 8)
-        d_x10 = nat.SCRATCH.get('pitch_x10', max(4, int(n_samples_bound) * 4))
-        nat.check(lib.dsp_resample_layout_batch(d_src_off, n_utt, int(rate), 10000, int(L), int(S), d_so10.ptr, d_fo.ptr, stream))
-        nat.check(lib.dsp_decimate_batch(d_clips, d_src_off, d_so10.ptr, n_utt, int(n_samples_bound), int(rate), 10000, d_x10.ptr, stream))
-        p_x, p_so = d_x10.ptr, d_so10.ptr
-    else:                       # downsampling keeps every sample when the clip is at 10 kHz or below (preprocess.py:21-28)
-        d_fo = nat.SCRATCH.get('pitch_fo10', (n_utt + 1) * 8)
-        nat.check(lib.dsp_resample_layout_batch(d_src_off, n_utt, int(rate), 0, int(L), int(S), None, d_fo.ptr, stream))
-        p_x, p_so = d_clips, d_src_off
+    stream = _stream_ptr(stream)
+    p_x, p_so, d_fo = _to_10k_on_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, L, S, stream)
     frames_bound = int(n_samples_bound) // int(S) + n_utt + 1
     n_lags = MAX_SHIFT - MIN_SHIFT
     d_scores = nat.SCRATCH.get('pitch_scores', frames_bound * n_lags * 4)
@@ -223,14 +229,6 @@ def _cepstrum_chain(p_x, p_so, p_fo, n_utt, frames_bound, L, S, stream=None, cli
         out.aux = nat.SCRATCH.get('cep_aux', n_utt * N_AUX * 4)
         _check(lib.dsp_pitch_feature_batch(out.pitch.ptr, out.amp.ptr, p_fo, n_utt, out.seg.ptr, out.feat.ptr, out.aux.ptr, stream))
     return out
-
-
-def _upload_10k(sig10k, sample_offsets, L, S):
-    so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
-    fo = nat.frame_offsets(so, L, S)
-    x = np.ascontiguousarray(sig10k, dtype=np.float32).reshape(-1)
-    d_x = nat.device_array('pitch_sig', x if x.size else np.zeros(1, dtype=np.float32))
-    return d_x, nat.device_array('pitch_so', so), nat.device_array('pitch_fo', fo), so, fo
 
 
 def cepstrum_rows_batch(sig10k, sample_offsets, L, S, clip=True):
@@ -358,22 +356,12 @@ def peakshift(seq1, seq2):
 
 
 def pitch_features_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, stream=None, L=512, S=100):
-    """pitch.pitch_feature for clips that are already on the device (fp32, concatenated, `rate` Hz): decimation to 10 kHz
-    (dsp_resample_layout_batch + dsp_decimate_batch), then the three launches of the cepstral path; nothing leaves the
-    device.  Returns library scratch buffers as attributes: feat [B, 5] fp64, aux [B, 9] int32 (p, p_bias, start1,
+    """pitch.pitch_feature for clips that are already on the device (fp32, concatenated, `rate` Hz): decimation to 10 kHz,
+    then the three launches of the cepstral path; nothing leaves the device.  `stream` is None, a raw handle or a torch
+    stream.  Returns library scratch buffers as attributes: feat [B, 5] fp64, aux [B, 9] int32 (p, p_bias, start1,
     end1, start2, end2, len1, len2, valid), pitch and seg [one per frame] fp64, frame_off [B + 1] int64."""
-    lib = nat.load()
-    stream = None if stream is None else int(getattr(stream, 'cuda_stream', stream))
-    d_fo = nat.SCRATCH.get('pitch_fo10', (n_utt + 1) * 8)
-    if rate > 10000:
-        d_so10 = nat.SCRATCH.get('pitch_so10', (n_utt + 1) * 8)
-        d_x10 = nat.SCRATCH.get('pitch_x10', max(4, int(n_samples_bound) * 4))
-        nat.check(lib.dsp_resample_layout_batch(d_src_off, n_utt, int(rate), 10000, int(L), int(S), d_so10.ptr, d_fo.ptr, stream))
-        nat.check(lib.dsp_decimate_batch(d_clips, d_src_off, d_so10.ptr, n_utt, int(n_samples_bound), int(rate), 10000, d_x10.ptr, stream))
-        p_x, p_so = d_x10.ptr, d_so10.ptr
-    else:                       # downsampling keeps every sample when the clip is at 10 kHz or below (preprocess.py:21-28)
-        nat.check(lib.dsp_resample_layout_batch(d_src_off, n_utt, int(rate), 0, int(L), int(S), None, d_fo.ptr, stream))
-        p_x, p_so = d_clips, d_src_off
+    stream = _stream_ptr(stream)
+    p_x, p_so, d_fo = _to_10k_on_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, L, S, stream)
     # a clip of n samples keeps at most n * 10000 / rate + 2 of them and has at most 2 + kept / S frames
     kept_bound = int(n_samples_bound) if rate <= 10000 else int(n_samples_bound) * 10000 // int(rate) + 2 * n_utt
     frames_bound = kept_bound // int(S) + 2 * n_utt + 1

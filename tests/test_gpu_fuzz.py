@@ -248,6 +248,48 @@ def test_pitch_scores_batch_and_tracks_vs_oracle():
         assert same.all(), (rate, same.mean())     # measured: every frame identical (parity_measured.json)
 
 
+@pytest.mark.parametrize('L', [301, 390, 511])
+def test_pitch_scores_at_frame_lengths_off_the_register_block(L):
+    """The register-blocked scores kernel produces FIR outputs W at a time: W = 3 up to L = 384, 4 up to 512.  301
+    (padded to 303), 390 and 511 are no multiple of their W, so the last group of outputs and the taps beyond L are
+    padding.  Clips: the first three of test_pitch_scores_batch_and_tracks_vs_oracle (same seed) and its three edge
+    cases.  Against the one-workgroup-per-frame kernel at that test's 1e-5, against the oracle at its 1e-4."""
+    from features import _native as nat
+    from features import pitch as gp
+    from oracle import dsp_oracle
+    rng = np.random.default_rng(61)
+    clips = []
+    for i in range(3):
+        n = int(rng.integers(2000, 9000))
+        t = np.arange(n) / 10000.0
+        f0 = rng.uniform(80, 400)
+        x = sum(np.sin(2 * np.pi * f0 * h * t + rng.uniform(0, 6)) / h for h in range(1, 6))
+        clips.append(np.round(4000 * x * np.hanning(n) + 30 * rng.standard_normal(n)))
+    clips.append(np.zeros(700))                       # all zero: median 0, every score 0
+    clips.append(-np.abs(clips[0][:900]) - 1.0)       # no non-negative sample: NaN clip level -> zeros
+    clips.append(clips[1][:150])                      # shorter than one frame (zero padded)
+    so = np.concatenate(([0], np.cumsum([len(c) for c in clips]))).astype(np.int64)
+    try:
+        nat.check(nat.load().dsp_debug_force_generic(1))
+        slow, _ = gp.frame_scores_batch(np.concatenate(clips), so, L, 100)
+    finally:
+        nat.check(nat.load().dsp_debug_force_generic(0))
+    fast, fo = gp.frame_scores_batch(np.concatenate(clips), so, L, 100)
+    assert fast.shape == slow.shape == (fo[-1], 180)
+    print(f'L = {L}: fast against generic kernel {normwise(fast, slow):.3e}')
+    assert normwise(fast, slow) <= 1e-5, (L, normwise(fast, slow))
+    for b, c in enumerate(clips):
+        frames = dsp_oracle.framesig(c, L, 100)
+        assert fo[b + 1] - fo[b] == len(frames)
+        ref = np.stack([dsp_oracle.pitch_frame_scores(dsp_oracle.center_clip(fr, False), 10000) for fr in frames])
+        got = fast[fo[b]:fo[b + 1]]
+        if np.max(np.abs(ref)) == 0:
+            assert np.max(np.abs(got)) == 0, (L, b)
+        else:
+            print(f'L = {L} clip {b}: against the oracle {normwise(got, ref):.3e}')
+            assert normwise(got, ref) <= 1e-4, (L, b, normwise(got, ref))
+
+
 def test_pitch_helpers_on_the_device_equal_the_oracle():
     """features.pitch.smooth / max_pitch / robust_max_pitch are batches of one through dsp_pitch_rows_batch: exact
     against the oracle's restatement of pitch.py:157-206 on random score rows (ties, a one-row input, other degrees)."""

@@ -46,6 +46,10 @@ def _gold(pgold, name):
     return {k.split('/', 1)[1]: v for k, v in pgold.items() if k.startswith(name + '/')}
 
 
+def _so(clips):
+    return np.concatenate([[0], np.cumsum([len(c) for c in clips])]).astype(np.int64)
+
+
 def _feat_close(got, want):
     return bool(np.all(np.abs(np.asarray(got) - want) <= 1e-9 * np.maximum(1.0, np.abs(want))))
 
@@ -98,6 +102,44 @@ def test_rows_match_the_stored_fp64_rows(name, fp, pgold):
     one = fp.pitch_detect_frame(fp.center_clip(F[t], False), 10000, 'male')
     assert one.dtype == np.float64 and one.shape == (L10,)
     assert np.max(np.abs(one[1:] - want[t, 1:])) / np.max(np.abs(want[t, 1:])) <= 1e-4
+
+
+# ---- 1b ----
+@pytest.mark.parametrize('L', [128, 256, 1024])
+def test_rows_scores_and_tracks_at_the_other_frame_lengths(L, fp):
+    """The kernels at the served frame lengths no caller of the reference uses: L = 128, 256 and 1024 give 1, 2 and 8 FIR
+    outputs per lane and half and 2, 4 and 16 registers per row.  Two 10 kHz chirps of 0.3 s, a clip of 100 samples
+    and a silent clip, hop 100.  Rows of the voiced frames (the restatement's row is finite) against the restatement
+    at the project's 1e-4, per frame as in test 1; scores and Hz values exactly against the restatement's tracker on
+    the device's own rows."""
+    from pitch_cepstrum_cases import chirp
+    rng = np.random.default_rng(300 + L)
+    clips = [chirp(rng, 10000, 0.3), chirp(rng, 10000, 0.3), chirp(rng, 10000, 0.3)[1400:1500], np.zeros(1500)]
+    so = _so(clips)
+    flat = np.concatenate(clips)
+    rows, amp, fo = fp.cepstrum_rows_batch(flat, so, L, S10)
+    pitch, scores, fo2 = fp.pitch_cepstrum_tracks_batch(flat, so, L, S10)
+    assert rows.shape == (fo[-1], L) and np.array_equal(fo, fo2)
+    voiced = 0
+    for b, c in enumerate(clips):
+        want = ref.cepstrum_rows(ref.frames_of(c, L, S10))
+        got = rows[fo[b]:fo[b + 1]]
+        assert got.shape == want.shape, b
+        for t in range(len(want)):
+            if not np.isfinite(want[t]).all():
+                continue
+            voiced += 1
+            full = np.max(np.abs(got[t] - want[t])) / np.max(np.abs(want[t]))
+            tail = np.max(np.abs(got[t, 1:] - want[t, 1:])) / np.max(np.abs(want[t, 1:]))
+            print(f'L = {L} clip {b} frame {t}: normwise {full:.3e}, columns 1.. {tail:.3e}')
+            record(f'pitch_cepstrum_rows_normwise_L{L}', full)
+            record(f'pitch_cepstrum_rows_normwise_cols1_L{L}', tail)
+            assert full <= 1e-4 and tail <= 1e-4, (L, b, t, full, tail)
+        scores_b = ref.peak_scores(ref.smooth_rows(got))
+        assert np.array_equal(scores[fo[b]:fo[b + 1]], scores_b), (L, b)
+        assert np.array_equal(pitch[fo[b]:fo[b + 1]], ref.robust_track(scores_b)), (L, b)
+    assert voiced >= 2 * (1 + (3000 - L) // S10)                             # every frame of the two chirps
+    assert fo[4] - fo[3] > 1 and np.all(pitch[fo[3]:fo[4]] == 500.0)         # the silent clip
 
 
 # ---- 2 ----

@@ -7,7 +7,8 @@ device-resident 44.1 kHz clips at 512-sample frames:
 The clips are SURVEY 8d's class C as bench.py's model_path builds them (noise background, one Hann-shaped tone burst,
 1 - 2 s), from a fixed seed, whole and untrimmed.  Reported: the median of hipEvent-timed calls of
 pitch_features_device and of pitch_tracks_device, and -- on the same decimated frames, with the launch grid at the exact
-frame count -- the two per-frame kernels alone (dsp_pitch_cepstrum_batch, dsp_pitch_scores_batch) and the two trackers.
+frame count -- the two per-frame kernels alone (dsp_pitch_cepstrum_batch, dsp_pitch_scores_batch) and the two trackers,
+and dsp_pitch_scores_batch at 300-sample frames of the same decimated clips, the kernel the model path runs.
 Per-kernel times: one `rocprofv3 --kernel-trace --stats -- python tools/kbench_pitch_cepstrum.py` run.
 """
 import argparse
@@ -102,6 +103,13 @@ def main():
     us['dsp_pitch_feature_batch (pitch_feature_kernel)'] = median_us(lambda: ck(lib.dsp_pitch_feature_batch(
         pitch.data_ptr(), amp.data_ptr(), d_fo, B, seg.data_ptr(), feat.data_ptr(), aux.data_ptr(), st)), args.iters)
     k_cep, k_sr = list(us.values())[0], list(us.values())[1]
+    # the model path's frame length on the same decimated clips, with frame offsets of its own
+    fo300 = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    ck(lib.dsp_resample_layout_batch(d_so10, B, 10000, 0, 300, S, None, fo300.data_ptr(), st))
+    frames300 = int(fo300[-1])
+    scores300, t_sr300 = torch.empty((frames300, 180), device=dev), gp._device_taps(300, 10000).ptr
+    us300 = median_us(lambda: ck(lib.dsp_pitch_scores_batch(
+        d_x10, d_so10, fo300.data_ptr(), B, frames300, 0, 300, S, t_sr300, 1, 20, 200, scores300.data_ptr(), st)), args.iters)
     lines = [
         f'{B} class-C clips at {rate} Hz ({n} samples, device resident) -> {frames} frames of {L} at 10 kHz; '
         f'median of {args.iters} hipEvent-timed calls',
@@ -110,6 +118,8 @@ def main():
         f'pitch_tracks_device   (decimate + autocorrelation scores + tracker)     : {us_sr:9.1f} us per call '
         f'= {us_sr / B:.2f} us per clip',
     ] + [f'{k:76s}: {v:9.1f} us = {v / frames * 1e3:8.2f} ns per frame' for k, v in us.items()] + [
+        f"{'dsp_pitch_scores_batch at L = 300 (pitch_scores_kernel_v2<3>)':76s}: {us300:9.1f} us = "
+        f'{us300 / frames300 * 1e3:8.2f} ns per frame ({frames300} frames)',
         f'cepstrum rows kernel / autocorrelation scores kernel, per frame: {k_cep / k_sr:.3f} x (margin 1.5 x)']
     text = '\n'.join(lines)
     print(text)
