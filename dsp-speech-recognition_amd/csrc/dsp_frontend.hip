@@ -19,6 +19,7 @@
 #include "kernels_pitch.h"
 #include "kernels_cepstrum.h"
 #include "kernels_hmlstm.h"
+#include "kernels_bigru.h"
 
 thread_local int g_host_dry_run = 0;   // dsp_debug_host_dry_run: plan tables in host memory (sanitizer build, no GPU)
 
@@ -38,6 +39,15 @@ struct dsp_hmlstm {
     int32_t I, H1, H2;
     float* d_packed;       // one allocation: cell 1 W_01 | U_21 | U_11 | bias, cell 2 W_01 | U_11 | bias (kernels_hmlstm.h layout)
     HmCell c1, c2;
+    int device;
+};
+
+// Packed parameters of one bidirectional GRU encoder (include/dsp_frontend.h: dsp_bigru); immutable after dsp_bigru_create.
+struct dsp_bigru {
+    int32_t I, H, L;
+    float* d_packed;       // one allocation: per layer and direction the concatenated [W_ih | W_hh] tiles, then the bias (kernels_bigru.h layout)
+    GruDir dir[GRU_MAX_LAYERS][2];
+    int32_t ngx[GRU_MAX_LAYERS], ng[GRU_MAX_LAYERS];
     int device;
 };
 
@@ -1287,6 +1297,110 @@ int dsp_hmlstm_forward(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t
     else if (nt <= 7 * HM_WAVES) hmlstm_forward_kernel<7><<<grid, HM_THREADS, 0, st>>>(P);
     else hmlstm_forward_kernel<9><<<grid, HM_THREADS, 0, st>>>(P);
     HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+static int64_t bigru_buffer_floats(const dsp_bigru* h, int32_t T, int32_t B) { return (int64_t)T * B * 2 * h->H; }
+
+int dsp_bigru_create(const dsp_bigru_desc* d, dsp_bigru** out) {
+    if (!d || !out) return fail(DSP_EINVAL, "dsp_bigru_create: NULL argument");
+    *out = nullptr;
+    const int32_t I = d->input_size, H = d->hidden, L = d->n_layers;
+    if (I < 1 || I > GRU_MAX_IN) return fail(DSP_EINVAL, "dsp_bigru_create: input_size %d must be in [1, %d]", I, GRU_MAX_IN);
+    if (H < 4 || H > GRU_MAX_H || (H & 3) != 0)
+        return fail(DSP_EINVAL, "dsp_bigru_create: hidden %d must be a multiple of 4 in [4, %d]", H, GRU_MAX_H);
+    if (L < 1 || L > GRU_MAX_LAYERS) return fail(DSP_EINVAL, "dsp_bigru_create: n_layers %d must be in [1, %d]", L, GRU_MAX_LAYERS);
+    for (int i = 0; i < 8 * L; ++i)
+        if (!d->d_params[i]) return fail(DSP_EINVAL, "dsp_bigru_create: NULL parameter tensor (index %d)", i);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const int32_t nt = H / 4;
+    size_t woff[GRU_MAX_LAYERS][2], boff[GRU_MAX_LAYERS][2], total = 0;
+    int32_t ngx[GRU_MAX_LAYERS], ng[GRU_MAX_LAYERS];
+    for (int l = 0; l < L; ++l) {
+        ngx[l] = hm_kgroups(l == 0 ? I : 2 * H);
+        ng[l] = ngx[l] + hm_kgroups(H);
+        for (int dr = 0; dr < 2; ++dr) { woff[l][dr] = total; total += (size_t)ng[l] * nt * 256; }
+    }
+    for (int l = 0; l < L; ++l)
+        for (int dr = 0; dr < 2; ++dr) { boff[l][dr] = total; total += (size_t)4 * H; }
+    float* buf = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), total * sizeof(float)));
+    // the parameters may have been written on any stream of the caller: create is rare, so it simply waits for the device
+    hipError_t e = hipDeviceSynchronize();
+    for (int l = 0; l < L && e == hipSuccess; ++l) {
+        for (int dr = 0; dr < 2 && e == hipSuccess; ++dr) {
+            const float* const* p = d->d_params + 8 * l + 4 * dr;      // weight_ih, weight_hh, bias_ih, bias_hh
+            const int64_t n = (int64_t)ng[l] * nt * 256;
+            gru_pack_kernel<<<(int)((n + 255) / 256), 256, 0, 0>>>(p[0], p[1], H, l == 0 ? I : 2 * H, ngx[l], ng[l], buf + woff[l][dr]);
+            gru_pack_bias_kernel<<<(4 * H + 255) / 256, 256, 0, 0>>>(p[2], p[3], H, buf + boff[l][dr]);
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(buf);
+        return fail(DSP_EHIP, "dsp_bigru_create: %s", hipGetErrorString(e));
+    }
+    dsp_bigru* h = new dsp_bigru();
+    h->I = I; h->H = H; h->L = L; h->d_packed = buf; h->device = dev;
+    for (int l = 0; l < L; ++l) {
+        h->ngx[l] = ngx[l]; h->ng[l] = ng[l];
+        for (int dr = 0; dr < 2; ++dr) h->dir[l][dr] = GruDir{reinterpret_cast<const float4*>(buf + woff[l][dr]), buf + boff[l][dr]};
+    }
+    *out = h;
+    return DSP_OK;
+}
+
+int dsp_bigru_destroy(dsp_bigru* h) {
+    if (!h) return DSP_OK;
+    hipError_t e = hipFree(h->d_packed);
+    delete h;
+    if (e != hipSuccess) return fail(DSP_EHIP, "dsp_bigru_destroy: %s", hipGetErrorString(e));
+    return DSP_OK;
+}
+
+int dsp_bigru_workspace_bytes(const dsp_bigru* h, int32_t T, int32_t B, int64_t* bytes) {
+    if (!h || !bytes) return fail(DSP_EINVAL, "dsp_bigru_workspace_bytes: NULL argument");
+    if (T < 1 || B < 1) return fail(DSP_EINVAL, "dsp_bigru_workspace_bytes: T %d and B %d must be >= 1", T, B);
+    *bytes = (h->L > 1 ? 2 : 1) * bigru_buffer_floats(h, T, B) * (int64_t)sizeof(float);
+    return DSP_OK;
+}
+
+int dsp_bigru_forward(const dsp_bigru* h, const float* d_x, int32_t T, int32_t B, const int32_t* d_len, float* d_y,
+                      float* d_hn, void* d_work, int64_t work_bytes, void* stream) {
+    if (!h || !d_x) return fail(DSP_EINVAL, "dsp_bigru_forward: NULL handle / input");
+    if (T < 1 || B < 1) return fail(DSP_EINVAL, "dsp_bigru_forward: T %d and B %d must be >= 1", T, B);
+    if (!d_y && !d_hn) return fail(DSP_EINVAL, "dsp_bigru_forward: nothing to write (d_y and d_hn are NULL)");
+    const int64_t per = bigru_buffer_floats(h, T, B), need = (h->L > 1 ? 2 : 1) * per * (int64_t)sizeof(float);
+    if (!d_work || work_bytes < need)
+        return fail(DSP_EINVAL, "dsp_bigru_forward: the workspace holds %lld bytes, %lld are needed", (long long)(d_work ? work_bytes : 0),
+                    (long long)need);
+    if ((reinterpret_cast<uintptr_t>(d_work) & 3) != 0) return fail(DSP_EINVAL, "dsp_bigru_forward: d_work must be 4-byte aligned");
+    float* bufs[2] = {static_cast<float*>(d_work), static_cast<float*>(d_work) + (h->L > 1 ? per : 0)};
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((B + HM_COLS - 1) / HM_COLS, 2);
+    const int nt = h->H / 4;                                                    // tiles per wave: ceil(nt / 8)
+    for (int l = 0; l < h->L; ++l) {
+        const bool last = l == h->L - 1;
+        GruParams P;
+        P.d[0] = h->dir[l][0]; P.d[1] = h->dir[l][1];
+        P.I = l == 0 ? h->I : 2 * h->H; P.H = h->H; P.ngx = h->ngx[l]; P.ng = h->ng[l];
+        P.T = T; P.B = B;
+        P.x = l == 0 ? d_x : bufs[(l - 1) & 1];
+        P.len = d_len;
+        P.out = (last && !d_y) ? nullptr : bufs[l & 1];
+        P.hn = d_hn ? d_hn + (int64_t)2 * l * B * h->H : nullptr;
+        if (nt <= 2 * HM_WAVES) bigru_layer_kernel<2><<<grid, HM_THREADS, 0, st>>>(P);
+        else if (nt <= 4 * HM_WAVES) bigru_layer_kernel<4><<<grid, HM_THREADS, 0, st>>>(P);
+        else if (nt <= 7 * HM_WAVES) bigru_layer_kernel<7><<<grid, HM_THREADS, 0, st>>>(P);
+        else bigru_layer_kernel<8><<<grid, HM_THREADS, 0, st>>>(P);
+        HIP_TRY(hipGetLastError());
+    }
+    if (d_y) {
+        bigru_sum_kernel<<<grid_for((int64_t)T * B * h->H, 256), 256, 0, st>>>(bufs[(h->L - 1) & 1], d_len, T, B, h->H, d_y);
+        HIP_TRY(hipGetLastError());
+    }
     return DSP_OK;
 }
 

@@ -39,6 +39,13 @@ class HmlstmDesc(C.Structure):
     ]
 
 
+class BigruDesc(C.Structure):
+    _fields_ = [
+        ('input_size', c_i32), ('hidden', c_i32), ('n_layers', c_i32), ('reserved', c_i32),
+        ('d_params', c_vp * 32),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/dsp_frontend.h one to one.
 SIGNATURES = {
     'dsp_abi_version': (C.c_int, []),
@@ -102,6 +109,10 @@ SIGNATURES = {
     'dsp_hmlstm_create': (C.c_int, [C.POINTER(HmlstmDesc), C.POINTER(c_vp)]),
     'dsp_hmlstm_destroy': (C.c_int, [c_vp]),
     'dsp_hmlstm_forward': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'dsp_bigru_create': (C.c_int, [C.POINTER(BigruDesc), C.POINTER(c_vp)]),
+    'dsp_bigru_destroy': (C.c_int, [c_vp]),
+    'dsp_bigru_workspace_bytes': (C.c_int, [c_vp, c_i32, c_i32, C.POINTER(c_i64)]),
+    'dsp_bigru_forward': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
 }
 
 _lib = None

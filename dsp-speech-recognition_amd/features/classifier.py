@@ -12,59 +12,157 @@ REAL reference class produced (tests/golden/make_rnn_golden.py -> tests/golden/r
 Two details of the reference that a "masked pooling" rewrite would get wrong, kept here on purpose:
 the time axis of the GRU output is max(len0), not the padded 200, and the max pooling runs over the zero rows
 ``pad_packed_sequence`` leaves behind shorter utterances (an utterance whose activations are all negative pools to 0).
+
+The encoder in front of every head (``_DynEnc``) has a native forward pass (csrc/kernels_bigru.h) beside the ``nn.GRU`` route;
+both yield max(len0) rows with zero rows behind each end, so the pooling above is the same on either.
 """
 import numpy as np
 import torch
 from torch import nn
 
 
-class RNNHead(nn.Module):
-    """Same parameter names, shapes and forward pass as the reference's ``RNN`` (``enc.gru.*``, ``out.*``)."""
-
-    class _Enc(nn.Module):
-        def __init__(self, input_size, hidden_size, n_layers):
-            super().__init__()
-            self.hidden_size = hidden_size
-            self.gru = nn.GRU(input_size, hidden_size, n_layers, dropout=0.0, bidirectional=True)
-
-    def __init__(self, feat_size=39, hidden=200, layers=3, classes=20):
-        super().__init__()
-        self.enc = RNNHead._Enc(feat_size, hidden, layers)
-        self.out = nn.Linear(2 * hidden, classes)
-
-    def forward(self, inp, len0):
-        """inp: [T, B, 39] (zero beyond each utterance's length), len0: lengths (numpy / list / tensor) -> [B, 20]."""
-        lens = torch.as_tensor(np.asarray(len0.cpu() if torch.is_tensor(len0) else len0), dtype=torch.int64)
-        order = torch.argsort(lens, descending=True, stable=True)          # layers.py:64 np.argsort(-input_lens)
-        unsort = torch.argsort(order).to(inp.device)
-        packed = nn.utils.rnn.pack_padded_sequence(inp[:, order.to(inp.device)], lens[order])     # layers.py:70
-        y, _ = self.enc.gru(packed)
-        y, _ = nn.utils.rnn.pad_packed_sequence(y)                          # [max(len0), B, 2H], zeros behind each end
-        h = self.enc.hidden_size
-        y = (y[:, :, :h] + y[:, :, h:])[:, unsort]                          # layers.py:73-74
-        avg = y.sum(0) / lens.to(inp.device, inp.dtype).unsqueeze(1)        # rnn_clf.py:29-30
-        mx = y.max(0).values                                                # rnn_clf.py:31 (over the padded rows too)
-        return self.out(torch.cat([avg, mx], dim=1))
-
-
 class _DynEnc(nn.Module):
-    """layers.DynamicEncoder (layers.py:42-76): sort by length (np.argsort(-lens): stable), pack, bidirectional GRU, pad back
-    to max(lens) rows (zeros behind each end), forward + backward halves SUMMED, unsort.  Parameter names ``gru.*``."""
+    """layers.DynamicEncoder (layers.py:42-76): bidirectional GRU over ragged lengths, output padded to max(lens) rows (zeros
+    behind each end), forward + backward halves SUMMED.  Parameter names ``gru.*``.
+
+    Two paths compute the same thing:
+      * the ``nn.GRU`` one -- the reference's own route: sort by length (np.argsort(-lens): stable), pack, GRU, pad back,
+        unsort; on any device, with gradients, with inter-layer dropout in training mode;
+      * the native one -- ``dsp_bigru_forward`` (csrc/kernels_bigru.h), forward only, fp32, on the tensors in place on the
+        current stream.  Nothing is sorted or packed: a column depends on no other column, so the kernel masks on
+        ``t < len``.  Runs for CUDA/ROCm tensors when no gradient is required and inter-layer dropout is inactive;
+        ``native=None`` picks it only where ``native_default`` says so.
+        ``native=True`` insists on it (and raises where it cannot run), ``native=False`` keeps ``nn.GRU``."""
+    native_default = False         # what ``native=None`` picks where the native path can run: opt-in until DESIGN 7.3's timing shows it ahead
 
     def __init__(self, input_size, hidden_size, n_layers, dropout=0.0):
         super().__init__()
         self.hidden_size = hidden_size
         self.gru = nn.GRU(input_size, hidden_size, n_layers, dropout=dropout, bidirectional=True)
+        self._handle, self._handle_key = None, None
 
-    def forward(self, x, lens):
-        lens = torch.as_tensor(np.asarray(lens.cpu() if torch.is_tensor(lens) else lens), dtype=torch.int64)
+    # ---- native path ------------------------------------------------------------------------------------------------
+    def _params(self):
+        """nn.GRU's order: per layer weight_ih, weight_hh, bias_ih, bias_hh, then the same four of the reverse direction."""
+        g = self.gru
+        return [getattr(g, f'{n}_l{l}{sfx}') for l in range(g.num_layers) for sfx in ('', '_reverse')
+                for n in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh')]
+
+    def native_supported(self, x):
+        """Why the native path cannot serve ``x`` (a string), or None when it can."""
+        from . import _native as nat
+        import os
+        g = self.gru
+        if not x.is_cuda:
+            return 'the input is not on a GPU'
+        if x.dtype != torch.float32 or any(p.dtype != torch.float32 or p.device != x.device for p in self._params()):
+            return 'input and parameters must be float32 on one device'
+        if any(not p.is_contiguous() for p in self._params()):
+            return 'parameters must be contiguous'
+        if not (1 <= g.input_size <= 512 and 4 <= g.hidden_size <= 256 and g.hidden_size % 4 == 0 and 1 <= g.num_layers <= 4):
+            return 'sizes out of range: input_size in [1, 512], hidden a multiple of 4 in [4, 256], 1 to 4 layers'
+        if self.training and g.dropout > 0 and g.num_layers > 1:
+            return 'inter-layer dropout is active (training mode)'
+        if not os.path.exists(nat.LIB_PATH):
+            return f'{nat.LIB_PATH} is not built'
+        return None
+
+    def _drop_handle(self):
+        if getattr(self, '_handle', None) is not None:
+            try:                                    # (at interpreter shutdown even the import may fail)
+                from . import _native as nat
+                nat.load().dsp_bigru_destroy(self._handle)
+            except Exception:
+                pass
+            self._handle, self._handle_key = None, None
+
+    def __del__(self):
+        self._drop_handle()
+
+    def __getstate__(self):
+        """Copies (copy.deepcopy, pickling) do not share the native handle: each builds its own on first use."""
+        d = self.__dict__.copy()
+        d['_handle'], d['_handle_key'] = None, None
+        return d
+
+    def _native_handle(self, dev):
+        """The packed copy of the parameters; rebuilt when one of them moved or was written (data_ptr / _version)."""
+        from . import _native as nat
+        ps = self._params()
+        key = (dev.index,) + tuple((p.data_ptr(), p._version) for p in ps)
+        if self._handle is None or key != self._handle_key:
+            self._drop_handle()
+            d = nat.BigruDesc(self.gru.input_size, self.gru.hidden_size, self.gru.num_layers, 0)
+            for i, p in enumerate(ps):
+                d.d_params[i] = p.data_ptr()
+            h = nat.c_vp(0)
+            nat.check(nat.load().dsp_bigru_create(nat.C.byref(d), nat.C.byref(h)))
+            self._handle, self._handle_key = h.value, key
+        return self._handle
+
+    def _run_native(self, x, lens):
+        from . import _native as nat
+        B, H, dev = x.shape[1], self.hidden_size, x.device
+        T = int(lens.max())
+        assert lens.numel() == B and int(lens.min()) >= 1 and T <= x.shape[0], 'lengths do not fit the input'
+        x = x.detach().contiguous()
+        with torch.cuda.device(dev):
+            handle = self._native_handle(dev)
+            lib = nat.load()
+            d_len = lens.to(torch.int32).to(dev)
+            nbytes = nat.c_i64(0)
+            nat.check(lib.dsp_bigru_workspace_bytes(handle, T, B, nat.C.byref(nbytes)))
+            work = torch.empty(nbytes.value // 4, dtype=torch.float32, device=dev)
+            y = torch.empty(T, B, H, dtype=torch.float32, device=dev)
+            hn = torch.empty(2 * self.gru.num_layers, B, H, dtype=torch.float32, device=dev)
+            nat.check(lib.dsp_bigru_forward(handle, x.data_ptr(), T, B, d_len.data_ptr(), y.data_ptr(), hn.data_ptr(),
+                                            work.data_ptr(), nbytes.value, torch.cuda.current_stream(dev).cuda_stream))
+        return y, hn
+
+    # ---- nn.GRU path (layers.py:63-76) -----------------------------------------------------------------------------------
+    def _run_torch(self, x, lens):
         order = torch.argsort(lens, descending=True, stable=True)
         unsort = torch.argsort(order).to(x.device)
         packed = nn.utils.rnn.pack_padded_sequence(x[:, order.to(x.device)], lens[order])
-        y, _ = self.gru(packed)
+        y, hn = self.gru(packed)
         y, _ = nn.utils.rnn.pad_packed_sequence(y)
         h = self.hidden_size
-        return (y[:, :, :h] + y[:, :, h:])[:, unsort].contiguous()
+        return (y[:, :, :h] + y[:, :, h:])[:, unsort].contiguous(), hn[:, unsort].contiguous()
+
+    def run(self, x, lens, native=None):
+        """-> (y [max(lens), B, H], h_n [2 n_layers, B, H]), the reference's return value (layers.py:76)."""
+        lens = torch.as_tensor(np.asarray(lens.cpu() if torch.is_tensor(lens) else lens), dtype=torch.int64)
+        if native is False or (native is None and not self.native_default):
+            return self._run_torch(x, lens)                                     # (nothing to find out about the native path)
+        needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        why = 'a gradient is required' if needs_grad else self.native_supported(x)
+        if native is None:
+            native = why is None
+        if native:
+            if why is not None:
+                raise RuntimeError(f'_DynEnc: the native path cannot run: {why}')
+            return self._run_native(x, lens)
+        return self._run_torch(x, lens)
+
+    def forward(self, x, lens, native=None):
+        return self.run(x, lens, native)[0]
+
+
+class RNNHead(nn.Module):
+    """Same parameter names, shapes and forward pass as the reference's ``RNN`` (``enc.gru.*``, ``out.*``)."""
+
+    def __init__(self, feat_size=39, hidden=200, layers=3, classes=20):
+        super().__init__()
+        self.enc = _DynEnc(feat_size, hidden, layers)
+        self.out = nn.Linear(2 * hidden, classes)
+
+    def forward(self, inp, len0, native_enc=None):
+        """inp: [T, B, 39] (zero beyond each utterance's length), len0: lengths (numpy / list / tensor) -> [B, 20]."""
+        lens = torch.as_tensor(np.asarray(len0.cpu() if torch.is_tensor(len0) else len0), dtype=torch.int64)
+        y = self.enc(inp, lens, native=native_enc)                          # [max(len0), B, H], zeros behind each end
+        avg = y.sum(0) / lens.to(inp.device, inp.dtype).unsqueeze(1)        # rnn_clf.py:29-30
+        mx = y.max(0).values                                                # rnn_clf.py:31 (over the padded rows too)
+        return self.out(torch.cat([avg, mx], dim=1))
 
 
 def _pool_head(y, lens, out, attn=None):
@@ -90,14 +188,14 @@ class HRNNHead(nn.Module):
         self.enc2 = _DynEnc(200, 200, 1)
         self.out = nn.Linear(400, 20)
 
-    def _levels(self, inp, len0):
+    def _levels(self, inp, len0, native_enc=None):
         len0 = np.asarray(len0.cpu() if torch.is_tensor(len0) else len0)
         len1 = (len0 + self.hir - 1) // self.hir                      # rnn_clf.py:52
-        y = self.enc1(inp, len0)[:, :, -self.hidden_size:]            # rnn_clf.py:58
-        return self.enc2(y[0::self.hir], len1), len1                  # rnn_clf.py:61-65
+        y = self.enc1(inp, len0, native=native_enc)[:, :, -self.hidden_size:]            # rnn_clf.py:58
+        return self.enc2(y[0::self.hir], len1, native=native_enc), len1                  # rnn_clf.py:61-65
 
-    def forward(self, inp, len0, dropout=True):
-        y2, len1 = self._levels(inp, len0)
+    def forward(self, inp, len0, dropout=True, native_enc=None):
+        y2, len1 = self._levels(inp, len0, native_enc)
         out, feat = _pool_head(y2, len1, self.out)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
 
@@ -125,8 +223,8 @@ class HRNNAttHead(HRNNHead):
         super().__init__(feat_size)
         self.attn = _SelfAttn(200)
 
-    def forward(self, inp, len0, dropout=True):
-        y2, len1 = self._levels(inp, len0)
+    def forward(self, inp, len0, dropout=True, native_enc=None):
+        y2, len1 = self._levels(inp, len0, native_enc)
         out, feat = _pool_head(y2, len1, self.out, self.attn)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
 
@@ -216,14 +314,14 @@ class TransformerHead(nn.Module):
         self.out = nn.Linear(400, 20)
         self.hidden_size = 200
 
-    def forward(self, inp, len0, dropout=True):
+    def forward(self, inp, len0, dropout=True, native_enc=None):
         len0 = np.asarray(len0.cpu() if torch.is_tensor(len0) else len0)
         len1 = (len0 + self.hir - 1) // self.hir
         attn_out = self.attn_enc(inp)
         a = torch.nn.functional.dropout(attn_out, 0.5) if dropout else attn_out
         # (the reference concatenates all 200 padded rows; the packed GRU then reads max(len0) of them)
-        y = self.rnn_enc_1(torch.cat([inp, a], 2), len0)[:, :, -self.hidden_size:]
-        y2 = self.rnn_enc_2(y[0::self.hir], len1)
+        y = self.rnn_enc_1(torch.cat([inp, a], 2), len0, native=native_enc)[:, :, -self.hidden_size:]
+        y2 = self.rnn_enc_2(y[0::self.hir], len1, native=native_enc)
         out, feat = _pool_head(y2, len1, self.out)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat, attn_out
 
@@ -441,9 +539,9 @@ class HMRNNHead(nn.Module):
         self.enc2 = HMLSTM(1.0, 200, [200, 200])
         self.out = nn.Linear(600, 20)
 
-    def forward(self, inp, len0, dropout=True, native=None):
+    def forward(self, inp, len0, dropout=True, native=None, native_enc=None):
         len0 = np.asarray(len0.cpu() if torch.is_tensor(len0) else len0)
-        enc = self.enc1(inp, len0)                                                    # [max(len0), B, 200]
+        enc = self.enc1(inp, len0, native=native_enc)                                                    # [max(len0), B, 200]
         if dropout:
             enc = torch.nn.functional.dropout(enc, 0.2)
         last = self.enc2.run(enc, None, lens=len0, native=native).last_h2             # rnn_clf.py:139-143

@@ -480,6 +480,48 @@ int dsp_hmlstm_forward(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t
                        const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1,
                        uint8_t* d_z2, float* d_zhat, float* d_last_h2, void* stream);
 
+/* ---- the classifiers' encoder (layers.DynamicEncoder, the first stage of every head in rnn_clf.py) --------- */
+/*
+ * Forward pass of layers.DynamicEncoder (layers.py:42-76), fp32: n_layers bidirectional GRU layers over ragged lengths, the
+ * two directions of the last layer summed, zero rows behind each utterance's end (csrc/kernels_bigru.h: one launch per layer,
+ * a workgroup owns 16 batch columns of one direction for all steps and never waits on another one, plus one summing launch).
+ * Per layer and direction, nn.GRU's parameters weight_ih [3 H, in], weight_hh [3 H, H], bias_ih, bias_hh [3 H], rows r | z | n,
+ * in = input_size for layer 0 and 2 H above it:
+ *   r = sigmoid(W_ir x + b_ir + W_hr h + b_hr),  z = sigmoid(W_iz x + b_iz + W_hz h + b_hz),
+ *   n = tanh(W_in x + b_in + r * (W_hn h + b_hn)),  h' = (1 - z) * n + z * h.
+ * Both directions start from h = 0; column b is active at step t iff t < len[b]; an inactive column keeps its h and emits a
+ * zero row, so the reverse direction starts its recurrence at len[b] - 1.  No column depends on another one: nothing is
+ * sorted or packed.
+ *
+ * d_params holds 8 DEVICE pointers per layer in nn.GRU's order: weight_ih, weight_hh, bias_ih, bias_hh of the forward
+ * direction, then the same four of the reverse direction; row-major as torch holds them.  Sizes out of range or a NULL
+ * parameter are DSP_EINVAL, checked before any device call.  Create repacks the parameters on the current device (it waits for
+ * the device before and after, so it must not run inside a stream capture); the handle holds its own copy, is immutable
+ * afterwards and may be used from several streams.
+ */
+typedef struct dsp_bigru dsp_bigru;
+typedef struct dsp_bigru_desc {
+    int32_t input_size;   /* 1 .. 512 */
+    int32_t hidden;       /* multiple of 4 in [4, 256] */
+    int32_t n_layers;     /* 1 .. 4 */
+    int32_t reserved;
+    const float* d_params[32];
+} dsp_bigru_desc;
+int dsp_bigru_create(const dsp_bigru_desc* desc, dsp_bigru** out);
+int dsp_bigru_destroy(dsp_bigru* h);
+/* bytes of the workspace dsp_bigru_forward needs at (T, B): the [T, B, 2 H] rows between the layers */
+int dsp_bigru_workspace_bytes(const dsp_bigru* h, int32_t T, int32_t B, int64_t* bytes);
+/*
+ * d_x [>= T, B, input_size] fp32 (the first T rows are read; no alignment beyond a float's).  d_len [B] int32 or NULL (= T
+ * everywhere; values are clamped to [1, T]).  d_y [T, B, hidden] = forward + reverse of the last layer with exact zero rows at
+ * t >= len[b]: every element is written on every call.  d_hn [2 n_layers, B, hidden] in nn.GRU's order (layer-major, forward
+ * then reverse): the forward direction's h at len - 1 and the reverse direction's at t = 0.  d_y or d_hn may be NULL, not
+ * both.  d_work: the caller's buffer of at least dsp_bigru_workspace_bytes bytes, so that the call allocates nothing and can be
+ * captured into a HIP graph.  The same arguments give the same bits on every call.
+ */
+int dsp_bigru_forward(const dsp_bigru* h, const float* d_x, int32_t T, int32_t B, const int32_t* d_len, float* d_y,
+                      float* d_hn, void* d_work, int64_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
