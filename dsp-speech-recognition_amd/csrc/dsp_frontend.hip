@@ -19,6 +19,7 @@
 #include "kernels_pitch.h"
 #include "kernels_cepstrum.h"
 #include "kernels_hmlstm.h"
+#include "kernels_hmlstm_bwd.h"
 #include "kernels_bigru.h"
 
 thread_local int g_host_dry_run = 0;   // dsp_debug_host_dry_run: plan tables in host memory (sanitizer build, no GPU)
@@ -39,6 +40,7 @@ struct dsp_hmlstm {
     int32_t I, H1, H2;
     float* d_packed;       // one allocation: cell 1 W_01 | U_21 | U_11 | bias, cell 2 W_01 | U_11 | bias (kernels_hmlstm.h layout)
     HmCell c1, c2;
+    const float4* wt[4];   // in the same allocation: U_11(2)^T, W_01(2)^T, U_21^T, U_11(1)^T (kernels_hmlstm_bwd.h layout)
     int device;
 };
 
@@ -1242,6 +1244,10 @@ int dsp_hmlstm_create(const dsp_hmlstm_desc* d, dsp_hmlstm** out) {
     for (int i = 0; i < 5; ++i) { off[i] = total; total += (size_t)hm_kgroups(segs[i].K) * hm_tiles(segs[i].H) * 256; }
     off[5] = total; total += (size_t)hm_tiles(H1) * 16;
     off[6] = total; total += (size_t)hm_tiles(H2) * 16;
+    // the transposed copies of the backward recurrence: (source, H of the cell, columns = hidden index of the product)
+    const Seg tsegs[4] = {{d->d_c2_U11, H2, H2}, {d->d_c2_W01, H2, H1}, {d->d_c1_U21, H1, H2}, {d->d_c1_U11, H1, H1}};
+    size_t toff[4];
+    for (int i = 0; i < 4; ++i) { toff[i] = total; total += (size_t)hm_bwd_packed_floats(tsegs[i].H, tsegs[i].K); }
     float* buf = nullptr;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), total * sizeof(float)));
     // the parameters may have been written on any stream of the caller: create is rare, so it simply waits for the device
@@ -1253,6 +1259,11 @@ int dsp_hmlstm_create(const dsp_hmlstm_desc* d, dsp_hmlstm** out) {
     }
     if (e == hipSuccess) { hm_pack_bias_kernel<<<(hm_tiles(H1) * 16 + 255) / 256, 256, 0, 0>>>(d->d_c1_bias, H1, buf + off[5]); e = hipGetLastError(); }
     if (e == hipSuccess) { hm_pack_bias_kernel<<<(hm_tiles(H2) * 16 + 255) / 256, 256, 0, 0>>>(d->d_c2_bias, H2, buf + off[6]); e = hipGetLastError(); }
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) {
+        const int64_t n = hm_bwd_packed_floats(tsegs[i].H, tsegs[i].K);
+        hm_pack_t_kernel<<<(int)((n + 255) / 256), 256, 0, 0>>>(tsegs[i].src, tsegs[i].H, tsegs[i].K, HM_WAVES * hm_bwd_chunks(tsegs[i].K), buf + toff[i]);
+        e = hipGetLastError();
+    }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         (void)hipFree(buf);
@@ -1263,6 +1274,7 @@ int dsp_hmlstm_create(const dsp_hmlstm_desc* d, dsp_hmlstm** out) {
     auto f4 = [&](int i) { return reinterpret_cast<const float4*>(buf + off[i]); };
     h->c1 = HmCell{{f4(0), f4(1), f4(2)}, buf + off[5], {hm_kgroups(I), hm_kgroups(H2), hm_kgroups(H1)}, H1, hm_tiles(H1)};
     h->c2 = HmCell{{f4(3), nullptr, f4(4)}, buf + off[6], {hm_kgroups(H1), 0, hm_kgroups(H2)}, H2, hm_tiles(H2)};
+    for (int i = 0; i < 4; ++i) h->wt[i] = reinterpret_cast<const float4*>(buf + toff[i]);
     *out = h;
     return DSP_OK;
 }
@@ -1275,27 +1287,110 @@ int dsp_hmlstm_destroy(dsp_hmlstm* h) {
     return DSP_OK;
 }
 
-int dsp_hmlstm_forward(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
-                       const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1, uint8_t* d_z2,
-                       float* d_zhat, float* d_last_h2, void* stream) {
-    if (!h || !d_x) return fail(DSP_EINVAL, "dsp_hmlstm_forward: NULL handle / input");
-    if (T < 1 || B < 1) return fail(DSP_EINVAL, "dsp_hmlstm_forward: T %d and B %d must be >= 1", T, B);
-    if (!std::isfinite(a)) return fail(DSP_EINVAL, "dsp_hmlstm_forward: the slope a is not finite");
-    if ((reinterpret_cast<uintptr_t>(d_x) & 15) != 0) return fail(DSP_EINVAL, "dsp_hmlstm_forward: d_x must be 16-byte aligned");
+// The checks and the launch behind dsp_hmlstm_forward (d_tape == NULL) and dsp_hmlstm_forward_train.
+static int hmlstm_forward_launch(const char* who, const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a,
+                                 const int32_t* d_len, const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2,
+                                 uint8_t* d_z1, uint8_t* d_z2, float* d_zhat, float* d_last_h2, float* d_tape, void* stream) {
+    if (!h || !d_x) return fail(DSP_EINVAL, "%s: NULL handle / input", who);
+    if (T < 1 || B < 1) return fail(DSP_EINVAL, "%s: T %d and B %d must be >= 1", who, T, B);
+    if (!std::isfinite(a)) return fail(DSP_EINVAL, "%s: the slope a is not finite", who);
+    if ((reinterpret_cast<uintptr_t>(d_x) & 15) != 0) return fail(DSP_EINVAL, "%s: d_x must be 16-byte aligned", who);
     if (!d_state_out && !d_h1 && !d_h2 && !d_z1 && !d_z2 && !d_zhat && !d_last_h2)
-        return fail(DSP_EINVAL, "dsp_hmlstm_forward: nothing to write (every output is NULL)");
+        return fail(DSP_EINVAL, "%s: nothing to write (every output is NULL)", who);
     HmParams P;
     P.c1 = h->c1; P.c2 = h->c2;
     P.I = h->I; P.T = T; P.B = B; P.a = a;
     P.x = d_x; P.len = d_len; P.state_in = d_state_in; P.state_out = d_state_out;
-    P.h1 = d_h1; P.h2 = d_h2; P.z1 = d_z1; P.z2 = d_z2; P.zhat = d_zhat; P.last_h2 = d_last_h2;
+    P.h1 = d_h1; P.h2 = d_h2; P.z1 = d_z1; P.z2 = d_z2; P.zhat = d_zhat; P.last_h2 = d_last_h2; P.tape = d_tape;
     const int grid = (B + HM_COLS - 1) / HM_COLS;
     const int nt = h->c1.n_tiles > h->c2.n_tiles ? h->c1.n_tiles : h->c2.n_tiles;   // tiles per wave: ceil(nt / 8)
     hipStream_t st = (hipStream_t)stream;
-    if (nt <= 2 * HM_WAVES) hmlstm_forward_kernel<2><<<grid, HM_THREADS, 0, st>>>(P);
-    else if (nt <= 4 * HM_WAVES) hmlstm_forward_kernel<4><<<grid, HM_THREADS, 0, st>>>(P);
-    else if (nt <= 7 * HM_WAVES) hmlstm_forward_kernel<7><<<grid, HM_THREADS, 0, st>>>(P);
-    else hmlstm_forward_kernel<9><<<grid, HM_THREADS, 0, st>>>(P);
+    if (d_tape) {
+        if (nt <= 2 * HM_WAVES) hmlstm_forward_kernel<2, true><<<grid, HM_THREADS, 0, st>>>(P);
+        else if (nt <= 4 * HM_WAVES) hmlstm_forward_kernel<4, true><<<grid, HM_THREADS, 0, st>>>(P);
+        else if (nt <= 7 * HM_WAVES) hmlstm_forward_kernel<7, true><<<grid, HM_THREADS, 0, st>>>(P);
+        else hmlstm_forward_kernel<9, true><<<grid, HM_THREADS, 0, st>>>(P);
+    } else {
+        if (nt <= 2 * HM_WAVES) hmlstm_forward_kernel<2><<<grid, HM_THREADS, 0, st>>>(P);
+        else if (nt <= 4 * HM_WAVES) hmlstm_forward_kernel<4><<<grid, HM_THREADS, 0, st>>>(P);
+        else if (nt <= 7 * HM_WAVES) hmlstm_forward_kernel<7><<<grid, HM_THREADS, 0, st>>>(P);
+        else hmlstm_forward_kernel<9><<<grid, HM_THREADS, 0, st>>>(P);
+    }
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+int dsp_hmlstm_forward(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
+                       const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1, uint8_t* d_z2,
+                       float* d_zhat, float* d_last_h2, void* stream) {
+    return hmlstm_forward_launch("dsp_hmlstm_forward", h, d_x, T, B, a, d_len, d_state_in, d_state_out, d_h1, d_h2, d_z1, d_z2,
+                                 d_zhat, d_last_h2, nullptr, stream);
+}
+
+int dsp_hmlstm_tape_bytes(const dsp_hmlstm* h, int32_t T, int32_t B, int64_t* bytes) {
+    if (!h || !bytes) return fail(DSP_EINVAL, "dsp_hmlstm_tape_bytes: NULL argument");
+    if (T < 1 || B < 1) return fail(DSP_EINVAL, "dsp_hmlstm_tape_bytes: T %d and B %d must be >= 1", T, B);
+    *bytes = hm_tape_floats(h->H1, h->H2, T, B) * (int64_t)sizeof(float);
+    return DSP_OK;
+}
+
+// The tape argument of the two training entry points.  Without a handle (h == NULL: the caller reports that next) the size is
+// held against the smallest tape any handle asks for at (T, B).
+static int hmlstm_check_tape(const char* who, const dsp_hmlstm* h, int32_t T, int32_t B, const void* d_tape, int64_t tape_bytes) {
+    if (!d_tape) return fail(DSP_EINVAL, "%s: NULL tape", who);
+    if ((reinterpret_cast<uintptr_t>(d_tape) & 15) != 0) return fail(DSP_EINVAL, "%s: d_tape must be 16-byte aligned", who);
+    const int64_t need = hm_tape_floats(h ? h->H1 : 4, h ? h->H2 : 4, T, B) * (int64_t)sizeof(float);
+    if (tape_bytes < need)
+        return fail(DSP_EINVAL, "%s: the tape is short (%lld bytes, dsp_hmlstm_tape_bytes asks for %lld)", who, (long long)tape_bytes, (long long)need);
+    return DSP_OK;
+}
+
+int dsp_hmlstm_forward_train(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
+                             const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1, uint8_t* d_z2,
+                             float* d_zhat, float* d_last_h2, void* d_tape, int64_t tape_bytes, void* stream) {
+    const char* who = "dsp_hmlstm_forward_train";
+    if (T < 1 || B < 1) return fail(DSP_EINVAL, "%s: T %d and B %d must be >= 1", who, T, B);
+    if (int rc = hmlstm_check_tape(who, h, T, B, d_tape, tape_bytes)) return rc;
+    if (!d_h1 || !d_h2 || !d_z1 || !d_z2) return fail(DSP_EINVAL, "%s: h1, h2, z1 and z2 are mandatory (the backward pass reads them)", who);
+    if (!d_x) return fail(DSP_EINVAL, "%s: NULL input", who);
+    if (!h) return fail(DSP_EINVAL, "%s: NULL handle", who);
+    return hmlstm_forward_launch(who, h, d_x, T, B, a, d_len, d_state_in, d_state_out, d_h1, d_h2, d_z1, d_z2, d_zhat,
+                                 d_last_h2, static_cast<float*>(d_tape), stream);
+}
+
+int dsp_hmlstm_backward(const dsp_hmlstm* h, int32_t T, int32_t B, float a, const int32_t* d_len, const float* d_state_in,
+                        const void* d_tape, int64_t tape_bytes, const float* d_h1, const float* d_h2, const uint8_t* d_z1,
+                        const uint8_t* d_z2, const float* d_g_h1, const float* d_g_h2, const float* d_g_last, float* d_dfs1,
+                        float* d_dfs2, void* stream) {
+    const char* who = "dsp_hmlstm_backward";
+    if (T < 1 || B < 1) return fail(DSP_EINVAL, "%s: T %d and B %d must be >= 1", who, T, B);
+    if (!std::isfinite(a)) return fail(DSP_EINVAL, "%s: the slope a is not finite", who);
+    if (int rc = hmlstm_check_tape(who, h, T, B, d_tape, tape_bytes)) return rc;
+    if (!d_h1 || !d_h2 || !d_z1 || !d_z2) return fail(DSP_EINVAL, "%s: NULL forward output (h1, h2, z1, z2)", who);
+    if (!d_g_h1 && !d_g_h2 && !d_g_last) return fail(DSP_EINVAL, "%s: no gradient to propagate (g_h1, g_h2 and g_last are all NULL)", who);
+    if (!d_dfs1 || !d_dfs2) return fail(DSP_EINVAL, "%s: NULL output (dfs1, dfs2)", who);
+    if (!h) return fail(DSP_EINVAL, "%s: NULL handle", who);
+    HmBwdParams P;
+    for (int i = 0; i < 4; ++i) P.wt[i] = h->wt[i];
+    P.H1 = h->H1; P.H2 = h->H2; P.T = T; P.B = B; P.a = a;
+    P.len = d_len; P.state_in = d_state_in; P.tape = static_cast<const float*>(d_tape);
+    P.h1 = d_h1; P.h2 = d_h2; P.z1 = d_z1; P.z2 = d_z2;
+    P.g_h1 = d_g_h1; P.g_h2 = d_g_h2; P.g_last = d_g_last; P.dfs1 = d_dfs1; P.dfs2 = d_dfs2;
+    const int grid = (B + HM_COLS - 1) / HM_COLS;
+    const size_t lds = hm_bwd_lds_bytes(h->H1, h->H2);       // up to 67.5 KB: above the static limit
+    hipStream_t st = (hipStream_t)stream;
+    const int nc = hm_bwd_chunks(h->H1 > h->H2 ? h->H1 : h->H2);
+    if (nc <= 1) {
+        static size_t granted[DSP_MAX_DEVICES] = {};
+        if (dsp_ensure_dynamic_lds((const void*)hmlstm_backward_kernel<1>, lds, granted) != 0)
+            return fail(DSP_EHIP, "%s: %zu bytes of LDS were not granted", who, lds);
+        hmlstm_backward_kernel<1><<<grid, HM_THREADS, lds, st>>>(P);
+    } else {
+        static size_t granted[DSP_MAX_DEVICES] = {};
+        if (dsp_ensure_dynamic_lds((const void*)hmlstm_backward_kernel<2>, lds, granted) != 0)
+            return fail(DSP_EHIP, "%s: %zu bytes of LDS were not granted", who, lds);
+        hmlstm_backward_kernel<2><<<grid, HM_THREADS, lds, st>>>(P);
+    }
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }

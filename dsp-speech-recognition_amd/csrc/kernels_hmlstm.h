@@ -52,7 +52,21 @@ struct HmParams {
     uint8_t* z2;
     float* zhat;                // [T, 2, B]
     float* last_h2;             // [B, H2]
+    float* tape;                // training mode (the TAPE instantiations) only: hm_tape_* below
 };
+
+// The tape of the training mode: what the backward recurrence (kernels_hmlstm_bwd.h) reads beside the outputs h1 / h2 / z1 / z2.
+// Per slice of 16 columns and step, hm_tape_step floats:
+//   cell 1: the gates (f, i, o, g) behind their non-linearities as one float4 per owner lane, [H1 / 4 tiles][64 lanes] -- lane
+//           l of tile t is (hidden unit 4 t + (l >> 4), column l & 15), so a wave stores a contiguous 1 KiB per tile -- then
+//           c' as one float per owner lane in the same order;
+//   cell 2: the same;
+//   m1 [16], m2 [16]: 1.0f where 0 <= (f_s[4H] a + 1) / 2 <= 1 (the clamp of hard_sigm passes the gradient), else 0.
+// Slice s, step t starts at ((s * T) + t) * hm_tape_step: every column of the last slice is written, b >= B included.
+__host__ __device__ static inline int64_t hm_tape_step(int32_t H1, int32_t H2) { return 80 * (int64_t)(H1 + H2) + 32; }
+static inline int64_t hm_tape_floats(int32_t H1, int32_t H2, int32_t T, int32_t B) {
+    return (int64_t)((B + HM_COLS - 1) / HM_COLS) * T * hm_tape_step(H1, H2);
+}
 
 // row of the reference's [4H + 1, K] matrix behind row r of tile t; -1: padding
 __host__ __device__ static inline int32_t hm_row(int32_t t, int32_t r, int32_t H) {
@@ -86,6 +100,16 @@ __global__ __launch_bounds__(256) void hm_pack_bias_kernel(const float* __restri
 __device__ __forceinline__ int hm_idx(int k, int col) { return (((k >> 2) * HM_COLS + col) << 2) + (k & 3); }
 
 __device__ __forceinline__ float hm_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+
+// A wave-uniform address, taken through readfirstlane and so held in scalar registers: the loads below are then "scalar base
+// + the lane's own offset", and the per-slot addresses are not carried in vector registers across the step loop (which
+// spills; see hm_product).  Used by the training mode and by kernels_hmlstm_bwd.h.
+template <class Tp>
+__device__ __forceinline__ Tp* hm_uniform(Tp* p) {
+    const uint64_t a = reinterpret_cast<uint64_t>(p);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    return reinterpret_cast<Tp*>(((uint64_t)hi << 32) | lo);
+}
 
 #define HM_CHUNK 4          // tiles a wave accumulates side by side: independent accumulators, one read of the LDS operand
 
@@ -155,9 +179,11 @@ __device__ __forceinline__ void hm_products(hm_f32x4 (&fs)[HM_CHUNK], hm_f32x4 (
 // (hmrnn.py:75-84) and the blend of hmrnn.py:86-97 into the owner lane's registers c, h.  Nothing is written to LDS here
 // (other waves still read the operands): hm_publish does that behind the barrier.  Returns z_hat (boundary tile, q = 0).
 // w is wave-uniform (the caller passes it through readfirstlane), so the tile counts below are scalar branches.
-template <int MAXS>
+// TAPE: tape points at this cell's gates of this step, mask at its 16 mask words (see hm_tape_step).
+template <int MAXS, bool TAPE = false>
 __device__ __forceinline__ float hm_cell(const HmCell& cp, const float* lds_bottom, const float* lds_top, const float* lds_h,
-                                         float (&c)[MAXS], float (&h)[MAXS], float z, float zb, float a, int w, int lane) {
+                                         float (&c)[MAXS], float (&h)[MAXS], float z, float zb, float a, int w, int lane,
+                                         float* tape = nullptr, float* mask = nullptr) {
     const int q = lane >> 4, nt = cp.n_tiles;
     const float nz = 1.0f - z, keep = nz * (1.0f - zb), upd = nz * zb;
     float zh = 0.f;
@@ -180,14 +206,22 @@ __device__ __forceinline__ float hm_cell(const HmCell& cp, const float* lds_bott
                 hm_f32x4 f4 = fs[i] + zb * acc[i];
                 f4 += hm_f32x4{bv.x, bv.y, bv.z, bv.w};
                 if (t < nt - 1) {
-                    const float f = hm_sigmoid(f4.x), ig = hm_sigmoid(f4.y) * tanhf(f4.w), o = hm_sigmoid(f4.z);
+                    const float f = hm_sigmoid(f4.x), gi = hm_sigmoid(f4.y), gg = tanhf(f4.w), ig = gi * gg, o = hm_sigmoid(f4.z);
                     const float cn = z * ig + keep * c[s] + upd * (f * c[s] + ig);
+                    if (TAPE) {
+                        typedef __attribute__((address_space(1))) hm_f32x4 gw4;
+                        typedef __attribute__((address_space(1))) float gw;
+                        ((gw4*)hm_uniform(tape + t * 256))[lane] = hm_f32x4{f, gi, o, gg};
+                        ((gw*)hm_uniform(tape + (nt - 1) * 256 + t * 64))[lane] = cn;
+                    }
                     const float ot = o * tanhf(cn);
                     h[s] = z * ot + keep * h[s] + upd * ot;
                     c[s] = cn;
                 } else {
                     // hard_sigm (hmrnn.py:25-28) in the reference's own rounding steps
-                    zh = fminf(fmaxf(__fmul_rn(__fadd_rn(__fmul_rn(f4.x, a), 1.0f), 0.5f), 0.0f), 1.0f);
+                    const float pre = __fmul_rn(__fadd_rn(__fmul_rn(f4.x, a), 1.0f), 0.5f);
+                    zh = fminf(fmaxf(pre, 0.0f), 1.0f);
+                    if (TAPE && q == 0) ((__attribute__((address_space(1))) float*)hm_uniform(mask))[lane & 15] = (pre >= 0.0f && pre <= 1.0f) ? 1.0f : 0.0f;
                 }
             }
         }
@@ -228,7 +262,7 @@ __device__ __forceinline__ void hm_store_rows(const float* lds_h, int H, int b0,
     }
 }
 
-template <int MAXS>
+template <int MAXS, bool TAPE = false>
 __global__ __launch_bounds__(HM_THREADS) void hmlstm_forward_kernel(const HmParams P) {
     __shared__ __attribute__((aligned(16))) float xbuf[HM_BUF_FLOATS];
     __shared__ __attribute__((aligned(16))) float h1buf[HM_BUF_FLOATS];
@@ -310,10 +344,13 @@ __global__ __launch_bounds__(HM_THREADS) void hmlstm_forward_kernel(const HmPara
     put_x();
     __syncthreads();
 
+    float* tp = nullptr;                    // this slice's tape rows of step t
+    if (TAPE) tp = P.tape + (int64_t)blockIdx.x * T * hm_tape_step(H1, H2);
     for (int t = 0; t < T; ++t) {
         if (t + 1 < T) load_x(t + 1);
         // ---- cell 1: bottom = x_t with z_bottom = 1, top = h2 of the previous step (hmrnn.py:146)
-        const float zh1 = hm_cell<MAXS>(P.c1, xbuf, h2buf, h1buf, c1, h1, z1s[col], 1.0f, P.a, w, lane);
+        const float zh1 = hm_cell<MAXS, TAPE>(P.c1, xbuf, h2buf, h1buf, c1, h1, z1s[col], 1.0f, P.a, w, lane, tp,
+                                              TAPE ? tp + 80 * (H1 + H2) : nullptr);
         __syncthreads();                    // every wave has read xbuf, h1buf and z1s
         if (t + 1 < T) put_x();
         hm_publish<MAXS>(h1, nt1, zh1, h1buf, z1s, w, lane, P.zhat ? P.zhat + ((int64_t)t * 2) * B + b : nullptr,
@@ -321,12 +358,14 @@ __global__ __launch_bounds__(HM_THREADS) void hmlstm_forward_kernel(const HmPara
         __syncthreads();                    // h1buf / z1s hold step t
         if (P.h1) hm_store_rows(h1buf, H1, b0, B, T, t, P.h1, nullptr, lens);
         // ---- cell 2: bottom = h1 and z1 of THIS step, no top-down term (hmrnn.py:147)
-        const float zh2 = hm_cell<MAXS>(P.c2, h1buf, nullptr, h2buf, c2, h2, z2s[col], z1s[col], P.a, w, lane);
+        const float zh2 = hm_cell<MAXS, TAPE>(P.c2, h1buf, nullptr, h2buf, c2, h2, z2s[col], z1s[col], P.a, w, lane,
+                                              TAPE ? tp + 80 * H1 : nullptr, TAPE ? tp + 80 * (H1 + H2) + 16 : nullptr);
         __syncthreads();                    // every wave has read h2buf and z2s
         hm_publish<MAXS>(h2, nt2, zh2, h2buf, z2s, w, lane, P.zhat ? P.zhat + ((int64_t)t * 2 + 1) * B + b : nullptr,
                          P.z2 ? P.z2 + (int64_t)b * T + t : nullptr, col_ok);
         __syncthreads();                    // h2buf / z2s hold step t
         if (P.h2 || P.last_h2) hm_store_rows(h2buf, H2, b0, B, T, t, P.h2, P.last_h2, lens);
+        if (TAPE) tp += hm_tape_step(H1, H2);
     }
 
     if (P.state_out && col_ok) {

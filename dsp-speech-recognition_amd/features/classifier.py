@@ -362,6 +362,106 @@ class _HMCell(nn.Module):
         return h_new, c_new, z_new, z_hat
 
 
+def hm_param_grads(params, x, state_in, h_1, h_2, z_1, dfs1, dfs2, need=None):
+    """The GEMMs behind the backward recurrence (include/dsp_frontend.h: dsp_hmlstm_backward).  params: (U_11, U_21, W_01,
+    bias of cell 1, U_11, W_01, bias of cell 2); x [T, B, I]; state_in: the flat h1 | c1 | z1 | h2 | c2 | z2 buffer or
+    None (zeros); h_1 [B, T, H1], h_2 [B, T, H2], z_1 [B, T] (0 / 1, any dtype); dfs1 [T, B, 4 H1 + 1] and dfs2
+    [T, B, 4 H2 + 1]: the gradients of the pre-activations f_s of every step.  -> (dx, then the seven parameter gradients
+    in the order of ``params``); ``need`` (8 booleans) leaves out what is not wanted."""
+    T, B, _ = x.shape
+    H1, H2 = h_1.shape[2], h_2.shape[2]
+    need = [True] * 8 if need is None else need
+    dt = dfs1.dtype
+    z1 = z_1.to(dt).t()                                                          # [T, B]
+    if state_in is None:
+        h1_0, h2_0, z1_0 = dfs1.new_zeros(1, B, H1), dfs1.new_zeros(1, B, H2), dfs1.new_zeros(1, B)
+    else:
+        h1_0 = state_in[:H1 * B].view(H1, B).t().unsqueeze(0)
+        z1_0 = state_in[2 * H1 * B:(2 * H1 + 1) * B].view(1, B)
+        h2_0 = state_in[(2 * H1 + 1) * B:(2 * H1 + 1 + H2) * B].view(H2, B).t().unsqueeze(0)
+    h1t, h2t = h_1.transpose(0, 1), h_2.transpose(0, 1)                          # [T, B, H]
+    h1p = torch.cat([h1_0.to(dt), h1t[:-1]], 0).reshape(T * B, H1)
+    h2p = torch.cat([h2_0.to(dt), h2t[:-1]], 0).reshape(T * B, H2)
+    z1p = torch.cat([z1_0.to(dt), z1[:-1]], 0).reshape(T * B, 1)
+    d1, d2 = dfs1.reshape(T * B, -1), dfs2.reshape(T * B, -1)
+    U11_1, U21, W01_1, _, U11_2, W01_2, _ = params
+    out = [None] * 8
+    if need[0]: out[0] = torch.matmul(dfs1, W01_1)
+    if need[1]: out[1] = d1.t() @ h1p
+    if need[2]: out[2] = (d1 * z1p).t() @ h2p
+    if need[3]: out[3] = d1.t() @ x.reshape(T * B, -1)
+    if need[4]: out[4] = d1.sum(0)
+    if need[5]: out[5] = (d2 * z1.reshape(T * B, 1)).t() @ h2p
+    if need[6]: out[6] = d2.t() @ h1t.reshape(T * B, H1)
+    if need[7]: out[7] = d2.sum(0)
+    return tuple(out)
+
+
+class _HMLSTMTrain(torch.autograd.Function):
+    """HMLSTM's native training path.  forward: dsp_hmlstm_forward_train (the forward kernel, which also saves the tape);
+    backward: dsp_hmlstm_backward (the recurrence, one launch) and ``hm_param_grads``.  Inputs: (module, a, d_len int32 [B],
+    state_in or None, x, the seven parameters); outputs: h_1, h_2, last_h2 (differentiable) and z_1, z_2 (uint8 [B, T]),
+    z_hat, state_out (marked non-differentiable)."""
+
+    @staticmethod
+    def forward(ctx, mod, a, d_len, state_in, x, *params):
+        from . import _native as nat
+        ctx.set_materialize_grads(False)                     # an unused output hands None to backward, not a tensor of zeros
+        T, B, _ = x.shape
+        H1, H2 = mod.size_list
+        dev = x.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        xc = x.detach().contiguous()
+        handle, lib = mod._native_handle(dev), nat.load()
+        nbytes = nat.c_i64(0)
+        nat.check(lib.dsp_hmlstm_tape_bytes(handle, T, B, nat.C.byref(nbytes)))
+        tape = torch.empty(nbytes.value // 4, **f32)
+        state_out = torch.empty((2 * H1 + 2 * H2 + 2) * B, **f32)
+        h_1, h_2 = torch.empty(B, T, H1, **f32), torch.empty(B, T, H2, **f32)
+        z_1, z_2 = torch.empty(B, T, dtype=torch.uint8, device=dev), torch.empty(B, T, dtype=torch.uint8, device=dev)
+        z_hat, last = torch.empty(T, 2, B, **f32), torch.empty(B, H2, **f32)
+        nat.check(lib.dsp_hmlstm_forward_train(handle, xc.data_ptr(), T, B, a, d_len.data_ptr(),
+                                               None if state_in is None else state_in.data_ptr(), state_out.data_ptr(),
+                                               h_1.data_ptr(), h_2.data_ptr(), z_1.data_ptr(), z_2.data_ptr(), z_hat.data_ptr(),
+                                               last.data_ptr(), tape.data_ptr(), nbytes.value,
+                                               torch.cuda.current_stream(dev).cuda_stream))
+        ctx.mod, ctx.a, ctx.tape_bytes = mod, a, nbytes.value
+        ctx.handle_key = mod._handle_key
+        ctx.has_state = state_in is not None
+        ctx.save_for_backward(xc, d_len, tape, h_1, h_2, z_1, z_2, *([state_in] if state_in is not None else []), *params)
+        ctx.mark_non_differentiable(z_1, z_2, z_hat, state_out)
+        return h_1, h_2, last, z_1, z_2, z_hat, state_out
+
+    @staticmethod
+    def backward(ctx, g_h1, g_h2, g_last, *_):
+        from . import _native as nat
+        saved = ctx.saved_tensors
+        xc, d_len, tape, h_1, h_2, z_1, z_2 = saved[:7]
+        state_in = saved[7] if ctx.has_state else None
+        params = saved[8 if ctx.has_state else 7:]
+        mod = ctx.mod
+        T, B, _ = xc.shape
+        H1, H2 = mod.size_list
+        dev = xc.device
+        if mod._handle is None or mod._handle_key != ctx.handle_key:
+            raise RuntimeError('HMLSTM: a parameter was modified between the native forward and its backward')
+        need = [ctx.needs_input_grad[4]] + list(ctx.needs_input_grad[5:12])
+        if g_h1 is None and g_h2 is None and g_last is None:
+            return (None,) * 12
+        gp = lambda g: None if g is None else g.to(torch.float32).contiguous()
+        g_h1, g_h2, g_last = gp(g_h1), gp(g_h2), gp(g_last)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(dev):
+            dfs1 = torch.empty(T, B, 4 * H1 + 1, dtype=torch.float32, device=dev)
+            dfs2 = torch.empty(T, B, 4 * H2 + 1, dtype=torch.float32, device=dev)
+            nat.check(nat.load().dsp_hmlstm_backward(mod._handle, T, B, ctx.a, d_len.data_ptr(), ptr(state_in), tape.data_ptr(),
+                                                     ctx.tape_bytes, h_1.data_ptr(), h_2.data_ptr(), z_1.data_ptr(), z_2.data_ptr(),
+                                                     ptr(g_h1), ptr(g_h2), ptr(g_last), dfs1.data_ptr(), dfs2.data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream))
+            grads = hm_param_grads([p.detach() for p in params], xc, state_in, h_1, h_2, z_1, dfs1, dfs2, need)
+        return (None, None, None, None) + grads
+
+
 class HMLSTMResult:
     """h_1 [B, T, H1], h_2 [B, T, H2], z_1 / z_2 [B, T, 1] (0. / 1.), hidden = (h1, c1, z1, h2, c2, z2) as [H, B] / [1, B]
     (hmrnn.py:153-154), z_hat [T, 2, B] (hard_sigm in front of the threshold: cell 1, cell 2) and, when lengths were given,
@@ -379,15 +479,23 @@ class HMLSTM(nn.Module):
     cell_2.U_11, cell_2.W_01, cell_2.bias``): its state_dict loads.
 
     Two paths compute the same thing:
-      * the torch step loop -- the restatement, on any device, with the reference's straight-through gradient; taken
-        whenever a gradient is required;
+      * the torch step loop -- the restatement, on any device, with the reference's straight-through gradient; what
+        ``native=None`` takes when a gradient is required (unless ``native_train_default`` is set);
       * the native one -- ``dsp_hmlstm_forward`` (csrc/kernels_hmlstm.h: one persistent HIP launch), on the tensors in
         place on the current stream; the default for CUDA/ROCm tensors when no gradient is required.  ``native=True``
         insists on it (and raises where it cannot run), ``native=False`` keeps the loop.
+        With a gradient required, ``native=True`` takes the native TRAINING path (``_HMLSTMTrain``): the forward saves a
+        tape (``dsp_hmlstm_forward_train``), the backward recurrence is one more persistent launch
+        (``dsp_hmlstm_backward``, csrc/kernels_hmlstm_bwd.h) and the parameter gradients are GEMMs over what it leaves
+        (``hm_param_grads``).  On that path h_1, h_2 and last_h2 carry the gradient to x and the seven parameters;
+        z_1, z_2, z_hat and the final ``hidden`` are NOT differentiable (the loop's z carries the straight-through gradient
+        to its consumers; nothing in this package consumes it), and an initial ``hidden`` that requires a gradient is a
+        reason the native path cannot run.
 
     ``a`` is the slope of hard_sigm and is read at every call.  (The reference's cells copy ``a`` at construction,
     hmrnn.py:53,121-122, so its ``HMRNN.adjust_param`` -- which adds to ``HM_LSTM.a`` only -- never reaches them; here the
     one attribute is what both cells use.)"""
+    native_train_default = False   # what ``native=None`` picks when a gradient is required: the loop, until DESIGN 7.4's timing shows the native path ahead
 
     def __init__(self, a, input_size, size_list):
         super().__init__()
@@ -481,6 +589,29 @@ class HMLSTM(nn.Module):
         zf = lambda z: None if z is None else z.to(torch.float32).unsqueeze(2)
         return HMLSTMResult(h_1=h_1, h_2=h_2, z_1=zf(z_1), z_2=zf(z_2), hidden=hid, z_hat=z_hat, last_h2=last)
 
+    def _run_native_train(self, x, hidden, lens):
+        """The native training path: the same HMLSTMResult, h_1 / h_2 / last_h2 attached to the autograd graph."""
+        T, B, _ = x.shape
+        H1, H2 = self.size_list
+        dev = x.device
+        with torch.cuda.device(dev):
+            self._native_handle(dev)
+            f32 = dict(dtype=torch.float32, device=dev)
+            state_in = None
+            if hidden is not None:
+                state_in = torch.cat([v.detach().to(**f32).reshape(-1) for v in hidden])
+                assert state_in.numel() == (2 * H1 + 2 * H2 + 2) * B, 'hidden does not fit (h1, c1, z1, h2, c2, z2) of this batch'
+            if lens is not None:
+                d_len = torch.as_tensor(np.asarray(lens.cpu() if torch.is_tensor(lens) else lens), dtype=torch.int32).to(dev)
+            else:
+                d_len = torch.full((B,), T, dtype=torch.int32, device=dev)
+            h_1, h_2, last, z_1, z_2, z_hat, state_out = _HMLSTMTrain.apply(self, float(self.a), d_len, state_in, x, *self._params())
+        sizes = [H1 * B, H1 * B, B, H2 * B, H2 * B, B]
+        parts = torch.split(state_out, sizes)
+        hid = (parts[0].view(H1, B), parts[1].view(H1, B), parts[2].view(1, B), parts[3].view(H2, B), parts[4].view(H2, B), parts[5].view(1, B))
+        zf = lambda z: z.to(torch.float32).unsqueeze(2)
+        return HMLSTMResult(h_1=h_1, h_2=h_2, z_1=zf(z_1), z_2=zf(z_2), hidden=hid, z_hat=z_hat, last_h2=last if lens is not None else None)
+
     # ---- torch step loop (hmrnn.py:124-154) -------------------------------------------------------------------------------
     def _run_torch(self, x, hidden, lens):
         T, B, _ = x.shape
@@ -507,15 +638,17 @@ class HMLSTM(nn.Module):
 
     def run(self, x, hidden=None, lens=None, native=None):
         """Everything the forward pass yields, as an HMLSTMResult.  x: [T, B, input_size]."""
-        needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())
-                                                  or (hidden is not None and any(v.requires_grad for v in hidden)))
-        why = 'a gradient is required' if needs_grad else self.native_supported(x)
+        hidden_grad = torch.is_grad_enabled() and hidden is not None and any(v.requires_grad for v in hidden)
+        needs_grad = hidden_grad or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))
+        if needs_grad and native is None and not self.native_train_default:
+            return self._run_torch(x, hidden, lens)
+        why = 'the initial hidden requires a gradient' if hidden_grad else self.native_supported(x)
         if native is None:
             native = why is None
         if native:
             if why is not None:
                 raise RuntimeError(f'HMLSTM: the native path cannot run: {why}')
-            return self._run_native(x, hidden, lens)
+            return self._run_native_train(x, hidden, lens) if needs_grad else self._run_native(x, hidden, lens)
         return self._run_torch(x, hidden, lens)
 
     def forward(self, x, hidden=None, lens=None, native=None):

@@ -480,6 +480,46 @@ int dsp_hmlstm_forward(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t
                        const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1,
                        uint8_t* d_z2, float* d_zhat, float* d_last_h2, void* stream);
 
+/*
+ * Training mode of the same recurrence: a forward that also saves what the backward pass needs (the "tape"), and the
+ * backward recurrence (csrc/kernels_hmlstm_bwd.h, one persistent launch of the same shape).  dsp_hmlstm_create packs a
+ * second, transposed copy of the four recurrent / bottom-up matrices for it, so a handle holds about
+ * 4 (4 H1 + 1) (input_size + H2 + H1) + 4 (4 H2 + 1) (H1 + H2) bytes for the forward plus, rounded up to whole tiles,
+ * 4 (4 H1 + 1) (H1 + H2) + 4 (4 H2 + 1) (H1 + H2) bytes for the backward (1.3 MB + 1.7 MB padded at 200 / 200 / 200).
+ *
+ * dsp_hmlstm_tape_bytes: the size of the caller's tape buffer at (T, B): ceil(B / 16) T (320 (H1 + H2) + 128) bytes
+ * (0.82 GB at T 200, B 512, H 200 / 200).  It holds, per step, cell and (hidden unit, column), the four gates behind
+ * their non-linearities and c', and per step, cell and column whether the clamp of hard_sigm passed the gradient.
+ *
+ * dsp_hmlstm_forward_train: dsp_hmlstm_forward with d_tape (16-byte aligned, at least dsp_hmlstm_tape_bytes; the caller
+ * owns it and keeps it and d_h1, d_h2, d_z1, d_z2 -- all four mandatory here -- unchanged until the backward call).
+ * Every output is bit for bit what dsp_hmlstm_forward writes.
+ *
+ * dsp_hmlstm_backward: given the gradients of a loss with respect to h_1 (d_g_h1 [B, T, H1]), h_2 (d_g_h2 [B, T, H2]) and
+ * last_h2 (d_g_last [B, H2], added at t = clamp(len[b], 1, T) - 1) -- each may be NULL, not all three -- it runs the steps
+ * t = T - 1 .. 0 and writes the gradients of the two cells' pre-activations f_s (hmrnn.py:84, rows f | i | o | g | z):
+ *   d_dfs1 [T, B, 4 H1 + 1], d_dfs2 [T, B, 4 H2 + 1]      every element is written; the same bits on every call.
+ * T, B, a, d_len and d_state_in must be those of the forward call.  The boundary z = [z_hat > 0.5] hands the gradient
+ * through unchanged (hmrnn.py:37-45) and hard_sigm's clamp passes it where 0 <= (a f_s[4H] + 1) / 2 <= 1.  The
+ * gradients of x and of the parameters are GEMMs over dfs, left to the caller (K = T B; features/classifier.py::
+ * hm_param_grads does them with torch.matmul).  With d1 = dfs1 and d2 = dfs2 as [T B, rows], x as [T B, input_size],
+ * h1 / h2 / z1 the forward's outputs of step t and h1' / h2' / z1' those of step t - 1 (d_state_in or zeros at t = 0):
+ *   dx       = d1 W_01(1)                                     [T B, input_size]
+ *   dW_01(1) = d1^T x          dU_11(1) = d1^T h1'            dU_21    = (z1' d1)^T h2'        dbias(1) = sum of d1's rows
+ *   dW_01(2) = d2^T h1         dU_11(2) = (z1 d2)^T h2'                                        dbias(2) = sum of d2's rows
+ * Neither call differentiates with respect to the initial state, and z_1 / z_2 / z_hat / state_out are outputs only.
+ * Both are one launch on `stream` without allocation (capturable); bad sizes, NULL or misaligned pointers and a short
+ * tape are DSP_EINVAL, checked before any device call.
+ */
+int dsp_hmlstm_tape_bytes(const dsp_hmlstm* h, int32_t T, int32_t B, int64_t* bytes);
+int dsp_hmlstm_forward_train(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
+                             const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1,
+                             uint8_t* d_z2, float* d_zhat, float* d_last_h2, void* d_tape, int64_t tape_bytes, void* stream);
+int dsp_hmlstm_backward(const dsp_hmlstm* h, int32_t T, int32_t B, float a, const int32_t* d_len, const float* d_state_in,
+                        const void* d_tape, int64_t tape_bytes, const float* d_h1, const float* d_h2, const uint8_t* d_z1,
+                        const uint8_t* d_z2, const float* d_g_h1, const float* d_g_h2, const float* d_g_last, float* d_dfs1,
+                        float* d_dfs2, void* stream);
+
 /* ---- the classifiers' encoder (layers.DynamicEncoder, the first stage of every head in rnn_clf.py) --------- */
 /*
  * Forward pass of layers.DynamicEncoder (layers.py:42-76), fp32: n_layers bidirectional GRU layers over ragged lengths, the

@@ -6,6 +6,10 @@ launch) against the torch step loop on the same device in the same process, alte
     python tools/kbench_hmlstm.py [--out profiles/hmlstm_kbench.json] [--rounds 5]
     python tools/kbench_hmlstm.py --kernel-only B      # one warm-up and ten native calls, for a rocprofv3 --kernel-trace run
     python tools/kbench_hmlstm.py --scan-seeds          # CPU only: the seeds of tests/test_gpu_hmlstm.py::LOOP_CASES
+    python tools/kbench_hmlstm.py --train [--parent-lib LIB] [--out profiles/hmlstm_train_kbench.json]
+                                                        # the training step: native forward_train / backward / GEMMs
+                                                        # against the torch loop, the head, and the guard on the plain forward
+    python tools/kbench_hmlstm.py --scan-train-seeds    # CPU only: the seeds of tests/test_gpu_hmlstm_train.py
 
 Times are device-event times around calls on one stream, median over the rounds (min and max are kept beside it); every
 shape is warmed up first.  The operation count is 2 (4H+1) (I + H2 + H1 + H1 + H2) per column and step.
@@ -59,15 +63,187 @@ def scan_seeds():
                 break
 
 
+def scan_train_seeds():
+    """CPU only: the seed tables of tests/test_gpu_hmlstm_train.py -- for every gradient case the first seed from 20260900 at
+    which the fp64 loop drops no column (in any variant the tests use), and the head's seed: no decision of the fp32 loop
+    within 1e-3 of 0.5 or of the clamp's ends."""
+    import hmrnn_cases as hc
+    import test_gpu_hmlstm_train as tt
+    for B, T, shape, _ in tt.GRAD_CASES:
+        variants = [dict()] + ([dict(with_state=True), dict(lens_kind='edges')] if (B, T, shape) == (19, 7, 'c') else [])
+        for seed in range(20260900, 20260900 + 200):
+            cases = [tt.truth(B, T, shape, seed, **kw) for kw in variants]
+            if all(c['keep'].all() for c in cases):
+                print(f"    ({B}, {T}, '{shape}', {seed}),   # dropped 0, boundary rates {cases[0]['rates'][0]:.2f} / {cases[0]['rates'][1]:.2f}", flush=True)
+                break
+    for seed in range(20260900, 20260900 + 200):
+        head, inp, len0, _ = tt._head_case(seed)
+        with torch.no_grad():
+            enc = head.enc1(torch.from_numpy(inp), len0)
+            zh = head.enc2.run(enc, None, lens=len0, native=False).z_hat.numpy()
+        if tt.kept_columns(zh, 1e-3).all():
+            print(f'HEAD_SEED = {seed}   # boundary rates {(zh[:, 0] > 0.5).mean():.2f} / {(zh[:, 1] > 0.5).mean():.2f}', flush=True)
+            break
+
+
+def _forward_ms_in_child(lib, rounds):
+    """dsp_hmlstm_forward at B 512 in a fresh process on the given library -> the rounds' times (this process keeps its own)."""
+    import subprocess
+    env = dict(os.environ, DSP_FRONTEND_LIB=lib)
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), '--forward-rounds', str(rounds)], env=env, check=True,
+                         stdout=subprocess.PIPE, text=True, timeout=300).stdout
+    return json.loads(out.strip().splitlines()[-1])
+
+
+def forward_rounds(rounds):
+    import ctypes
+    from features import _native as nat
+    from features.classifier import HMLSTM, fill_parameters
+    probe = ctypes.CDLL(nat.LIB_PATH)
+    for name in [n for n in nat.SIGNATURES if not hasattr(probe, name)]:     # a build of an older commit: the forward needs none of them
+        del nat.SIGNATURES[name]
+    dev = torch.device('cuda', 0)
+    torch.manual_seed(0)
+    m = HMLSTM(1.0, 200, [200, 200]).eval()
+    fill_parameters(m, 1)
+    m = m.to(dev)
+    x = torch.from_numpy(np.random.default_rng(2).standard_normal((200, 512, 200)).astype(np.float32)).to(dev)
+    with torch.no_grad():
+        m.run(x, native=True)
+        torch.cuda.synchronize()
+        print(json.dumps([_time(lambda: m.run(x, native=True), 5) for _ in range(rounds)]))
+
+
+def train(args):
+    """The training step: native forward_train, backward and the GEMMs (separately and as one autograd step) against the torch
+    loop's forward + backward, alternating; the whole HMRNNHead at B 512; and the guard on dsp_hmlstm_forward against a build
+    of the parent commit (--parent-lib, e.g. from tools/build_variants.sh), each library in a process of its own, alternating."""
+    from features import _native as nat
+    from features.classifier import HMLSTM, HMRNNHead, fill_parameters, hm_param_grads
+    dev = torch.device('cuda', 0)
+    I, sizes, T = 200, [200, 200], 200
+    H1, H2 = sizes
+    torch.manual_seed(0)
+    m = HMLSTM(1.0, I, sizes)
+    fill_parameters(m, 1)
+    m = m.to(dev)
+    rng = np.random.default_rng(2)
+    res = {'shape': {'input_size': I, 'sizes': sizes, 'T': T}, 'hmlstm_train': {}, 'heads_train': {}, 'forward_guard': {}}
+    lib = nat.load()
+    for B in (8, 64, 512):
+        new = lambda *s: torch.from_numpy(rng.standard_normal(s).astype(np.float32)).to(dev)
+        x, g1, g2, gl = new(T, B, I), new(B, T, H1), new(B, T, H2), new(B, H2)
+        xg = x.clone().requires_grad_(True)
+        lens = torch.full((B,), T, dtype=torch.int32, device=dev)
+
+        def step(native):
+            r = m.run(xg, None, lens=lens.cpu().numpy(), native=native)
+            torch.autograd.backward([r.h_1, r.h_2, r.last_h2], [g1, g2, gl])
+            m.zero_grad(set_to_none=True); xg.grad = None
+        # the three parts of the native step on raw buffers
+        handle = m._native_handle(dev)
+        n = nat.c_i64(0)
+        nat.check(lib.dsp_hmlstm_tape_bytes(handle, T, B, nat.C.byref(n)))
+        f32 = dict(dtype=torch.float32, device=dev)
+        tape = torch.empty(n.value // 4, **f32)
+        h1, h2 = torch.empty(B, T, H1, **f32), torch.empty(B, T, H2, **f32)
+        z1, z2 = torch.empty(B, T, dtype=torch.uint8, device=dev), torch.empty(B, T, dtype=torch.uint8, device=dev)
+        zhat, last, state = torch.empty(T, 2, B, **f32), torch.empty(B, H2, **f32), torch.empty((2 * H1 + 2 * H2 + 2) * B, **f32)
+        d1, d2 = torch.empty(T, B, 4 * H1 + 1, **f32), torch.empty(T, B, 4 * H2 + 1, **f32)
+        st = lambda: torch.cuda.current_stream(dev).cuda_stream
+        fwd = lambda: nat.check(lib.dsp_hmlstm_forward_train(handle, x.data_ptr(), T, B, 1.0, lens.data_ptr(), None, state.data_ptr(),
+                                                             h1.data_ptr(), h2.data_ptr(), z1.data_ptr(), z2.data_ptr(), zhat.data_ptr(),
+                                                             last.data_ptr(), tape.data_ptr(), n.value, st()))
+        bwd = lambda: nat.check(lib.dsp_hmlstm_backward(handle, T, B, 1.0, lens.data_ptr(), None, tape.data_ptr(), n.value, h1.data_ptr(),
+                                                        h2.data_ptr(), z1.data_ptr(), z2.data_ptr(), g1.data_ptr(), g2.data_ptr(),
+                                                        gl.data_ptr(), d1.data_ptr(), d2.data_ptr(), st()))
+        params = [p.detach() for p in m._params()]
+        gemms = lambda: hm_param_grads(params, x, None, h1, h2, z1, d1, d2)
+        runs = {'forward_train': (fwd, 5), 'backward': (bwd, 5), 'gemms': (gemms, 5), 'native_step': (lambda: step(True), 3),
+                'torch_loop_step': (lambda: step(False), 1)}
+        for f, _ in runs.values():
+            f()
+        torch.cuda.synchronize()
+        ts = {k: [] for k in runs}
+        for _ in range(args.rounds):
+            for k, (f, reps) in runs.items():
+                ts[k].append(_time(f, reps))
+        r = {k: _stats(v) for k, v in ts.items()}
+        r['tape_bytes'] = n.value
+        r['sum_of_parts_ms'] = sum(r[k]['median_ms'] for k in ('forward_train', 'backward', 'gemms'))
+        r['speedup'] = r['torch_loop_step']['median_ms'] / r['native_step']['median_ms']
+        res['hmlstm_train'][str(B)] = r
+        print(f"B {B:4d}: forward_train {r['forward_train']['median_ms']:.2f} + backward {r['backward']['median_ms']:.2f} + GEMMs "
+              f"{r['gemms']['median_ms']:.2f} = {r['sum_of_parts_ms']:.2f} ms; autograd step native {r['native_step']['median_ms']:.2f} ms, "
+              f"torch loop {r['torch_loop_step']['median_ms']:.1f} ms -> x{r['speedup']:.1f}; tape {n.value / 2**20:.0f} MiB", flush=True)
+        del tape, d1, d2
+    B = 512
+    inp = torch.from_numpy(rng.standard_normal((T, B, 39)).astype(np.float32)).to(dev)
+    len0 = rng.integers(20, T + 1, B)
+    len0[0] = T
+    wl = torch.from_numpy(rng.standard_normal((B, 20)).astype(np.float32)).to(dev)
+    torch.manual_seed(0)
+    hm = HMRNNHead().to(dev)
+
+    def head_step(native):
+        lo, _ = hm(inp, len0, dropout=True, native=native)
+        (lo * wl).sum().backward()
+        hm.zero_grad(set_to_none=True)
+    for nv in (True, False):
+        head_step(nv)
+    torch.cuda.synchronize()
+    ts = {True: [], False: []}
+    for _ in range(args.rounds):
+        for nv in (True, False):
+            ts[nv].append(_time(lambda: head_step(nv), 1))
+    res['heads_train'] = {'HMRNNHead_native': _stats(ts[True]), 'HMRNNHead_torch_loop': _stats(ts[False])}
+    print(f"HMRNNHead forward + backward (B = 512): native {res['heads_train']['HMRNNHead_native']['median_ms']:.1f} ms, torch loop "
+          f"{res['heads_train']['HMRNNHead_torch_loop']['median_ms']:.1f} ms", flush=True)
+    def write():
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'w') as fh:
+                json.dump(res, fh, indent=1)
+    write()
+    if args.parent_lib:
+        del hm, inp
+        torch.cuda.empty_cache()
+        t_par, t_new = [], []
+        for _ in range(2):                                                    # alternating processes
+            t_par += _forward_ms_in_child(os.path.abspath(args.parent_lib), args.rounds)
+            t_new += _forward_ms_in_child(nat.LIB_PATH, args.rounds)
+        g = {'B': 512, 'parent': _stats(t_par), 'this_tree': _stats(t_new)}
+        # the margin: the parent's own min-max spread of rounds as profiles/hmlstm_kbench.json records it (this job's is kept beside it)
+        with open(os.path.join(ROOT, 'profiles', 'hmlstm_kbench.json')) as fh:
+            rec = json.load(fh)['hmlstm']['512']['native']
+        g['margin_ms'] = rec['max_ms'] - rec['min_ms']
+        g['parent_spread_this_job_ms'] = g['parent']['max_ms'] - g['parent']['min_ms']
+        g['no_slower'] = g['this_tree']['median_ms'] <= g['parent']['median_ms'] + g['margin_ms']
+        res['forward_guard'] = g
+        print(f"dsp_hmlstm_forward (B = 512): parent {g['parent']['median_ms']:.3f} ms (min {g['parent']['min_ms']:.3f}, max "
+              f"{g['parent']['max_ms']:.3f}), this tree {g['this_tree']['median_ms']:.3f} ms -> no slower: {g['no_slower']}", flush=True)
+    write()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--kernel-only', type=int, default=0, metavar='B')
     ap.add_argument('--scan-seeds', action='store_true')
+    ap.add_argument('--scan-train-seeds', action='store_true')
+    ap.add_argument('--train', action='store_true')
+    ap.add_argument('--parent-lib', default=None, help='with --train: a build of the parent commit, for the forward guard')
+    ap.add_argument('--forward-rounds', type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.forward_rounds:
+        return forward_rounds(args.forward_rounds)
     if args.scan_seeds:
         return scan_seeds()
+    if args.scan_train_seeds:
+        return scan_train_seeds()
+    if args.train:
+        return train(args)
     from features.classifier import HMLSTM, HMRNNHead, RNNHead, fill_parameters
     dev = torch.device('cuda', 0)
     I, sizes, T = 200, [200, 200], 200
