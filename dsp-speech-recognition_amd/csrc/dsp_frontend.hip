@@ -21,6 +21,7 @@
 #include "kernels_hmlstm.h"
 #include "kernels_hmlstm_bwd.h"
 #include "kernels_bigru.h"
+#include "kernels_bigru_bwd.h"
 
 thread_local int g_host_dry_run = 0;   // dsp_debug_host_dry_run: plan tables in host memory (sanitizer build, no GPU)
 
@@ -49,6 +50,7 @@ struct dsp_bigru {
     int32_t I, H, L;
     float* d_packed;       // one allocation: per layer and direction the concatenated [W_ih | W_hh] tiles, then the bias (kernels_bigru.h layout)
     GruDir dir[GRU_MAX_LAYERS][2];
+    const float4* wt[GRU_MAX_LAYERS][2];   // in the same allocation: weight_hh^T per layer and direction (kernels_bigru_bwd.h layout)
     int32_t ngx[GRU_MAX_LAYERS], ng[GRU_MAX_LAYERS];
     int device;
 };
@@ -1419,6 +1421,10 @@ int dsp_bigru_create(const dsp_bigru_desc* d, dsp_bigru** out) {
     }
     for (int l = 0; l < L; ++l)
         for (int dr = 0; dr < 2; ++dr) { boff[l][dr] = total; total += (size_t)4 * H; }
+    // the transposed copies of the backward recurrence
+    size_t toff[GRU_MAX_LAYERS][2];
+    for (int l = 0; l < L; ++l)
+        for (int dr = 0; dr < 2; ++dr) { toff[l][dr] = total; total += (size_t)gru_bwd_packed_floats(H); }
     float* buf = nullptr;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), total * sizeof(float)));
     // the parameters may have been written on any stream of the caller: create is rare, so it simply waits for the device
@@ -1429,6 +1435,8 @@ int dsp_bigru_create(const dsp_bigru_desc* d, dsp_bigru** out) {
             const int64_t n = (int64_t)ng[l] * nt * 256;
             gru_pack_kernel<<<(int)((n + 255) / 256), 256, 0, 0>>>(p[0], p[1], H, l == 0 ? I : 2 * H, ngx[l], ng[l], buf + woff[l][dr]);
             gru_pack_bias_kernel<<<(4 * H + 255) / 256, 256, 0, 0>>>(p[2], p[3], H, buf + boff[l][dr]);
+            const int64_t nb = gru_bwd_packed_floats(H);
+            gru_pack_t_kernel<<<(int)((nb + 255) / 256), 256, 0, 0>>>(p[1], H, HM_WAVES * hm_bwd_chunks(H), buf + toff[l][dr]);
             e = hipGetLastError();
         }
     }
@@ -1441,7 +1449,10 @@ int dsp_bigru_create(const dsp_bigru_desc* d, dsp_bigru** out) {
     h->I = I; h->H = H; h->L = L; h->d_packed = buf; h->device = dev;
     for (int l = 0; l < L; ++l) {
         h->ngx[l] = ngx[l]; h->ng[l] = ng[l];
-        for (int dr = 0; dr < 2; ++dr) h->dir[l][dr] = GruDir{reinterpret_cast<const float4*>(buf + woff[l][dr]), buf + boff[l][dr]};
+        for (int dr = 0; dr < 2; ++dr) {
+            h->dir[l][dr] = GruDir{reinterpret_cast<const float4*>(buf + woff[l][dr]), buf + boff[l][dr]};
+            h->wt[l][dr] = reinterpret_cast<const float4*>(buf + toff[l][dr]);
+        }
     }
     *out = h;
     return DSP_OK;
@@ -1462,6 +1473,25 @@ int dsp_bigru_workspace_bytes(const dsp_bigru* h, int32_t T, int32_t B, int64_t*
     return DSP_OK;
 }
 
+// One layer of the forward pass: the plain instantiations, or (tape != NULL) those that also save the gates.
+static void bigru_launch_layer(const dsp_bigru* h, int l, GruParams& P, float* tape, const float* drop, dim3 grid, hipStream_t st) {
+    P.d[0] = h->dir[l][0]; P.d[1] = h->dir[l][1];
+    P.I = l == 0 ? h->I : 2 * h->H; P.H = h->H; P.ngx = h->ngx[l]; P.ng = h->ng[l];
+    P.tape = tape; P.drop = drop;
+    const int nt = h->H / 4;                                                    // tiles per wave: ceil(nt / 8)
+    if (tape) {
+        if (nt <= 2 * HM_WAVES) bigru_layer_kernel<2, true><<<grid, HM_THREADS, 0, st>>>(P);
+        else if (nt <= 4 * HM_WAVES) bigru_layer_kernel<4, true><<<grid, HM_THREADS, 0, st>>>(P);
+        else if (nt <= 7 * HM_WAVES) bigru_layer_kernel<7, true><<<grid, HM_THREADS, 0, st>>>(P);
+        else bigru_layer_kernel<8, true><<<grid, HM_THREADS, 0, st>>>(P);
+    } else {
+        if (nt <= 2 * HM_WAVES) bigru_layer_kernel<2><<<grid, HM_THREADS, 0, st>>>(P);
+        else if (nt <= 4 * HM_WAVES) bigru_layer_kernel<4><<<grid, HM_THREADS, 0, st>>>(P);
+        else if (nt <= 7 * HM_WAVES) bigru_layer_kernel<7><<<grid, HM_THREADS, 0, st>>>(P);
+        else bigru_layer_kernel<8><<<grid, HM_THREADS, 0, st>>>(P);
+    }
+}
+
 int dsp_bigru_forward(const dsp_bigru* h, const float* d_x, int32_t T, int32_t B, const int32_t* d_len, float* d_y,
                       float* d_hn, void* d_work, int64_t work_bytes, void* stream) {
     if (!h || !d_x) return fail(DSP_EINVAL, "dsp_bigru_forward: NULL handle / input");
@@ -1475,27 +1505,120 @@ int dsp_bigru_forward(const dsp_bigru* h, const float* d_x, int32_t T, int32_t B
     float* bufs[2] = {static_cast<float*>(d_work), static_cast<float*>(d_work) + (h->L > 1 ? per : 0)};
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((B + HM_COLS - 1) / HM_COLS, 2);
-    const int nt = h->H / 4;                                                    // tiles per wave: ceil(nt / 8)
     for (int l = 0; l < h->L; ++l) {
         const bool last = l == h->L - 1;
         GruParams P;
-        P.d[0] = h->dir[l][0]; P.d[1] = h->dir[l][1];
-        P.I = l == 0 ? h->I : 2 * h->H; P.H = h->H; P.ngx = h->ngx[l]; P.ng = h->ng[l];
         P.T = T; P.B = B;
         P.x = l == 0 ? d_x : bufs[(l - 1) & 1];
         P.len = d_len;
         P.out = (last && !d_y) ? nullptr : bufs[l & 1];
         P.hn = d_hn ? d_hn + (int64_t)2 * l * B * h->H : nullptr;
-        if (nt <= 2 * HM_WAVES) bigru_layer_kernel<2><<<grid, HM_THREADS, 0, st>>>(P);
-        else if (nt <= 4 * HM_WAVES) bigru_layer_kernel<4><<<grid, HM_THREADS, 0, st>>>(P);
-        else if (nt <= 7 * HM_WAVES) bigru_layer_kernel<7><<<grid, HM_THREADS, 0, st>>>(P);
-        else bigru_layer_kernel<8><<<grid, HM_THREADS, 0, st>>>(P);
+        bigru_launch_layer(h, l, P, nullptr, nullptr, grid, st);
         HIP_TRY(hipGetLastError());
     }
     if (d_y) {
         bigru_sum_kernel<<<grid_for((int64_t)T * B * h->H, 256), 256, 0, st>>>(bufs[(h->L - 1) & 1], d_len, T, B, h->H, d_y);
         HIP_TRY(hipGetLastError());
     }
+    return DSP_OK;
+}
+
+int dsp_bigru_tape_bytes(const dsp_bigru* h, int32_t T, int32_t B, int64_t* bytes) {
+    if (!h || !bytes) return fail(DSP_EINVAL, "dsp_bigru_tape_bytes: NULL argument");
+    if (T < 1 || B < 1) return fail(DSP_EINVAL, "dsp_bigru_tape_bytes: T %d and B %d must be >= 1", T, B);
+    *bytes = gru_tape_floats(h->H, h->L, T, B) * (int64_t)sizeof(float);
+    return DSP_OK;
+}
+
+int dsp_bigru_tape_rows(const dsp_bigru* h, int32_t layer, int32_t T, int32_t B, int64_t* offset_bytes) {
+    if (!h || !offset_bytes) return fail(DSP_EINVAL, "dsp_bigru_tape_rows: NULL argument");
+    if (T < 1 || B < 1) return fail(DSP_EINVAL, "dsp_bigru_tape_rows: T %d and B %d must be >= 1", T, B);
+    if (layer < 0 || layer >= h->L) return fail(DSP_EINVAL, "dsp_bigru_tape_rows: layer %d out of range [0, %d)", layer, h->L);
+    *offset_bytes = layer * gru_tape_rows_floats(h->H, T, B) * (int64_t)sizeof(float);
+    return DSP_OK;
+}
+
+// The tape argument of the two training entry points.  Without a handle (h == NULL: the caller reports that next) the size is
+// held against the smallest tape any handle asks for at (T, B).
+static int bigru_check_tape(const char* who, const dsp_bigru* h, int32_t T, int32_t B, const void* d_tape, int64_t tape_bytes) {
+    if (!d_tape) return fail(DSP_EINVAL, "%s: NULL tape", who);
+    if ((reinterpret_cast<uintptr_t>(d_tape) & 15) != 0) return fail(DSP_EINVAL, "%s: d_tape must be 16-byte aligned", who);
+    const int64_t need = gru_tape_floats(h ? h->H : 4, h ? h->L : 1, T, B) * (int64_t)sizeof(float);
+    if (tape_bytes < need)
+        return fail(DSP_EINVAL, "%s: the tape is short (%lld bytes, dsp_bigru_tape_bytes asks for %lld)", who, (long long)tape_bytes, (long long)need);
+    return DSP_OK;
+}
+
+// where layer l's output rows and gates start in the tape
+static float* bigru_tape_rows(const dsp_bigru* h, void* tape, int l, int32_t T, int32_t B) {
+    return static_cast<float*>(tape) + l * gru_tape_rows_floats(h->H, T, B);
+}
+static float* bigru_tape_gates(const dsp_bigru* h, void* tape, int l, int32_t T, int32_t B) {
+    return static_cast<float*>(tape) + h->L * gru_tape_rows_floats(h->H, T, B) + l * gru_tape_layer_gates_floats(h->H, T, B);
+}
+
+int dsp_bigru_forward_train(const dsp_bigru* h, const float* d_x, int32_t T, int32_t B, const int32_t* d_len, const float* d_drop,
+                            float* d_y, float* d_hn, void* d_tape, int64_t tape_bytes, void* stream) {
+    const char* who = "dsp_bigru_forward_train";
+    if (T < 1 || B < 1) return fail(DSP_EINVAL, "%s: T %d and B %d must be >= 1", who, T, B);
+    if (int rc = bigru_check_tape(who, h, T, B, d_tape, tape_bytes)) return rc;
+    if (!d_x) return fail(DSP_EINVAL, "%s: NULL input", who);
+    if (!h) return fail(DSP_EINVAL, "%s: NULL handle", who);
+    if ((reinterpret_cast<uintptr_t>(d_drop) & 3) != 0) return fail(DSP_EINVAL, "%s: d_drop must be 4-byte aligned", who);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((B + HM_COLS - 1) / HM_COLS, 2);
+    for (int l = 0; l < h->L; ++l) {
+        GruParams P;
+        P.T = T; P.B = B;
+        P.x = l == 0 ? d_x : bigru_tape_rows(h, d_tape, l - 1, T, B);
+        P.len = d_len;
+        P.out = bigru_tape_rows(h, d_tape, l, T, B);
+        P.hn = d_hn ? d_hn + (int64_t)2 * l * B * h->H : nullptr;
+        bigru_launch_layer(h, l, P, bigru_tape_gates(h, d_tape, l, T, B),
+                           (l > 0 && d_drop) ? d_drop + (int64_t)(l - 1) * gru_tape_rows_floats(h->H, T, B) : nullptr, grid, st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (d_y) {
+        bigru_sum_kernel<<<grid_for((int64_t)T * B * h->H, 256), 256, 0, st>>>(bigru_tape_rows(h, d_tape, h->L - 1, T, B), d_len, T, B, h->H, d_y);
+        HIP_TRY(hipGetLastError());
+    }
+    return DSP_OK;
+}
+
+int dsp_bigru_backward(const dsp_bigru* h, int32_t layer, int32_t T, int32_t B, const int32_t* d_len, const void* d_tape,
+                       int64_t tape_bytes, const float* d_g, const float* d_g_hn, float* d_da, void* stream) {
+    const char* who = "dsp_bigru_backward";
+    if (T < 1 || B < 1) return fail(DSP_EINVAL, "%s: T %d and B %d must be >= 1", who, T, B);
+    if (int rc = bigru_check_tape(who, h, T, B, d_tape, tape_bytes)) return rc;
+    if (!d_g && !d_g_hn) return fail(DSP_EINVAL, "%s: no gradient to propagate (g and g_hn are both NULL)", who);
+    if (!d_da) return fail(DSP_EINVAL, "%s: NULL output (da)", who);
+    if (((reinterpret_cast<uintptr_t>(d_g) | reinterpret_cast<uintptr_t>(d_g_hn) | reinterpret_cast<uintptr_t>(d_da)) & 3) != 0)
+        return fail(DSP_EINVAL, "%s: g, g_hn and da must be 4-byte aligned", who);
+    if (!h) return fail(DSP_EINVAL, "%s: NULL handle", who);
+    if (layer < 0 || layer >= h->L) return fail(DSP_EINVAL, "%s: layer %d out of range [0, %d)", who, layer, h->L);
+    GruBwdParams P;
+    P.wt[0] = h->wt[layer][0]; P.wt[1] = h->wt[layer][1];
+    P.H = h->H; P.T = T; P.B = B;
+    P.g_stride = layer == h->L - 1 ? h->H : 2 * h->H;
+    P.len = d_len;
+    P.gates = bigru_tape_gates(h, const_cast<void*>(d_tape), layer, T, B);
+    P.out = bigru_tape_rows(h, const_cast<void*>(d_tape), layer, T, B);
+    P.g = d_g; P.g_hn = d_g_hn; P.da = d_da;
+    const dim3 grid((B + HM_COLS - 1) / HM_COLS, 2);
+    const size_t lds = gru_bwd_lds_bytes(h->H);                // up to 64 KiB: above the static limit
+    hipStream_t st = (hipStream_t)stream;
+    if (hm_bwd_chunks(h->H) <= 1) {
+        static size_t granted[DSP_MAX_DEVICES] = {};
+        if (dsp_ensure_dynamic_lds((const void*)bigru_backward_kernel<1>, lds, granted) != 0)
+            return fail(DSP_EHIP, "%s: %zu bytes of LDS were not granted", who, lds);
+        bigru_backward_kernel<1><<<grid, HM_THREADS, lds, st>>>(P);
+    } else {
+        static size_t granted[DSP_MAX_DEVICES] = {};
+        if (dsp_ensure_dynamic_lds((const void*)bigru_backward_kernel<2>, lds, granted) != 0)
+            return fail(DSP_EHIP, "%s: %zu bytes of LDS were not granted", who, lds);
+        bigru_backward_kernel<2><<<grid, HM_THREADS, lds, st>>>(P);
+    }
+    HIP_TRY(hipGetLastError());
     return DSP_OK;
 }
 

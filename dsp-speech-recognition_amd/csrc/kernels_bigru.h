@@ -37,7 +37,25 @@ struct GruParams {
     const int32_t* len;         // [B] or nullptr
     float* out;                 // [T, B, 2 H]: forward | reverse, or nullptr
     float* hn;                  // [2, B, H] of this layer, or nullptr
+    float* tape;                // training mode (the TAPE instantiations) only: this layer's gates, gru_tape_* below
+    const float* drop;          // training mode only: [T, B, I] multipliers of x (inter-layer dropout), or nullptr
 };
+
+// The tape of the training mode (dsp_bigru_forward_train): what the backward recurrence (kernels_bigru_bwd.h) reads.
+//   rows:  per layer the [T, B, 2 H] output rows (forward | reverse), EVERY row written: exact zeros at t >= len[b], also
+//          behind a slice's last step -- layer l at float l * T * B * 2 H;
+//   gates: behind the rows of all layers, per layer, direction, slice of 16 columns and step gru_tape_step floats: the owner
+//          lane's float4 (r, z, n behind their non-linearities, n_h = W_hn h + b_hn), [H / 4 tiles][64 lanes] -- lane l of tile t
+//          is (hidden unit 4 t + (l >> 4), column l & 15), so a wave stores a contiguous 1 KiB per tile.  Only the steps a
+//          slice visits (t < max len of its columns) are stored; every column of the last slice is, b >= B included.
+__host__ __device__ static inline int64_t gru_tape_step(int32_t H) { return 64 * (int64_t)H; }
+static inline int64_t gru_tape_rows_floats(int32_t H, int32_t T, int32_t B) { return (int64_t)T * B * 2 * H; }
+static inline int64_t gru_tape_layer_gates_floats(int32_t H, int32_t T, int32_t B) {
+    return 2 * (int64_t)((B + HM_COLS - 1) / HM_COLS) * T * gru_tape_step(H);
+}
+static inline int64_t gru_tape_floats(int32_t H, int32_t L, int32_t T, int32_t B) {
+    return L * (gru_tape_rows_floats(H, T, B) + gru_tape_layer_gates_floats(H, T, B));
+}
 
 // dst[((g * nt + t) * 64 + l) * 4 + e]; one thread per float.  w_ih [3H, I], w_hh [3H, H], rows r | z | n.
 __global__ __launch_bounds__(256) void gru_pack_kernel(const float* __restrict__ w_ih, const float* __restrict__ w_hh, int32_t H,
@@ -70,9 +88,10 @@ __global__ __launch_bounds__(256) void gru_pack_bias_kernel(const float* __restr
 
 // One step for this wave's tiles w, w + 8, ..: the gates of (hidden unit 4 t + q, column col) into the owner lane's h.
 // Nothing is written to LDS here (other waves still read the operand).  w is wave-uniform.
-template <int MAXS>
+// TAPE: tape points at this slice's gates of this step (see gru_tape_step).
+template <int MAXS, bool TAPE = false>
 __device__ __forceinline__ void gru_cell(const GruDir& dp, int ng, int nt, const float* lds, float (&h)[MAXS], bool active,
-                                         int w, int lane) {
+                                         int w, int lane, float* tape = nullptr) {
     const int q = lane >> 4;
 #pragma unroll
     for (int s0 = 0; s0 < MAXS; s0 += HM_CHUNK) {
@@ -92,6 +111,10 @@ __device__ __forceinline__ void gru_cell(const GruDir& dp, int ng, int nt, const
                 const float4 bv = *reinterpret_cast<const float4*>(dp.bias + t * 16 + 4 * q);
                 const hm_f32x4 f4 = acc[i] + hm_f32x4{bv.x, bv.y, bv.z, bv.w};
                 const float r = hm_sigmoid(f4.x), z = hm_sigmoid(f4.y), n = tanhf(f4.z + r * f4.w);
+                if (TAPE) {
+                    typedef __attribute__((address_space(1))) hm_f32x4 gw4;
+                    ((gw4*)hm_uniform(tape + t * 256))[lane] = hm_f32x4{r, z, n, f4.w};
+                }
                 const float hn = (1.0f - z) * n + z * h[s];
                 h[s] = active ? hn : h[s];                                      // a column behind its end keeps its h
             }
@@ -99,7 +122,7 @@ __device__ __forceinline__ void gru_cell(const GruDir& dp, int ng, int nt, const
     }
 }
 
-template <int MAXS>
+template <int MAXS, bool TAPE = false>
 __global__ __launch_bounds__(HM_THREADS) void bigru_layer_kernel(const GruParams P) {
     __shared__ __attribute__((aligned(16))) float buf[GRU_BUF_FLOATS];       // [x_t, K padded to 16 | h] of the slice
     __shared__ int lens[HM_COLS];
@@ -136,6 +159,14 @@ __global__ __launch_bounds__(HM_THREADS) void bigru_layer_kernel(const GruParams
             xr[r] = 0.f;
             if (idx < nx) xr[r] = src[idx];
         }
+        if (TAPE && P.drop) {                   // the same layout as x: a second load with the same index
+            const float* dsrc = P.drop + ((int64_t)t * B + b0) * I;
+#pragma unroll
+            for (int r = 0; r < GRU_X_ROUNDS; ++r) {
+                const int idx = tid + r * HM_THREADS;
+                if (idx < nx) xr[r] *= dsrc[idx];
+            }
+        }
     };
     auto put_x = [&]() {
 #pragma unroll
@@ -159,10 +190,12 @@ __global__ __launch_bounds__(HM_THREADS) void bigru_layer_kernel(const GruParams
     }
     __syncthreads();
 
+    float* tp = nullptr;                    // this slice's gates of step 0
+    if (TAPE) tp = P.tape + ((int64_t)dir * gridDim.x + blockIdx.x) * T * gru_tape_step(H);
     for (int s = 0; s < steps; ++s) {
         const int t = step_t(s);
         if (s + 1 < steps) load_x(step_t(s + 1));
-        gru_cell<MAXS>(dp, ng, nt, buf, h, t < mylen, w, lane);
+        gru_cell<MAXS, TAPE>(dp, ng, nt, buf, h, t < mylen, w, lane, TAPE ? tp + t * gru_tape_step(H) : nullptr);
         __syncthreads();                    // every wave has read x_t and h
         if (s + 1 < steps) put_x();
 #pragma unroll
@@ -179,6 +212,15 @@ __global__ __launch_bounds__(HM_THREADS) void bigru_layer_kernel(const GruParams
                 P.out[((int64_t)t * B + b0 + c) * (2 * H) + dir * H + j] = v;
             }
         }
+    }
+
+    if (TAPE && P.out) {                    // the rows no step visited: the backward's GEMMs read every row of a layer
+        const int n = min(HM_COLS, B - b0) * H;
+        for (int t = steps; t < T; ++t)
+            for (int idx = tid; idx < n; idx += HM_THREADS) {
+                const int c = idx / H, j = idx - c * H;
+                P.out[((int64_t)t * B + b0 + c) * (2 * H) + dir * H + j] = 0.f;
+            }
     }
 
     if (P.hn && b < B) {

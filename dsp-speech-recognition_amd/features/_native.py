@@ -118,6 +118,10 @@ SIGNATURES = {
     'dsp_bigru_destroy': (C.c_int, [c_vp]),
     'dsp_bigru_workspace_bytes': (C.c_int, [c_vp, c_i32, c_i32, C.POINTER(c_i64)]),
     'dsp_bigru_forward': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'dsp_bigru_tape_bytes': (C.c_int, [c_vp, c_i32, c_i32, C.POINTER(c_i64)]),
+    'dsp_bigru_tape_rows': (C.c_int, [c_vp, c_i32, c_i32, c_i32, C.POINTER(c_i64)]),
+    'dsp_bigru_forward_train': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'dsp_bigru_backward': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

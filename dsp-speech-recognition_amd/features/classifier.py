@@ -14,7 +14,8 @@ the time axis of the GRU output is max(len0), not the padded 200, and the max po
 ``pad_packed_sequence`` leaves behind shorter utterances (an utterance whose activations are all negative pools to 0).
 
 The encoder in front of every head (``_DynEnc``) has a native forward pass (csrc/kernels_bigru.h) beside the ``nn.GRU`` route;
-both yield max(len0) rows with zero rows behind each end, so the pooling above is the same on either.
+both yield max(len0) rows with zero rows behind each end, so the pooling above is the same on either.  With a gradient
+required, ``native_enc=True`` takes the native training path (``_DynEncTrain``, csrc/kernels_bigru_bwd.h).
 """
 import numpy as np
 import torch
@@ -32,8 +33,16 @@ class _DynEnc(nn.Module):
         current stream.  Nothing is sorted or packed: a column depends on no other column, so the kernel masks on
         ``t < len``.  Runs for CUDA/ROCm tensors when no gradient is required and inter-layer dropout is inactive;
         ``native=None`` picks it only where ``native_default`` says so.
-        ``native=True`` insists on it (and raises where it cannot run), ``native=False`` keeps ``nn.GRU``."""
+        ``native=True`` insists on it (and raises where it cannot run), ``native=False`` keeps ``nn.GRU``.
+        With a gradient required, ``native=True`` takes the native TRAINING path (``_DynEncTrain``): the forward saves a tape
+        (``dsp_bigru_forward_train``), the backward recurrence is one launch per layer (``dsp_bigru_backward``,
+        csrc/kernels_bigru_bwd.h) and the gradients of the parameters and of x are GEMMs over what it leaves
+        (``gru_param_grads``).  y and h_n both carry the gradient; inter-layer dropout in training mode is drawn with torch
+        and handed to the kernel as multipliers.  The training path serves modules in TRAINING mode (``.train()``): in eval
+        mode a required gradient stays a reason the native path cannot run, as it was before that path existed.
+        ``native=None`` keeps ``nn.GRU`` whenever a gradient is required, unless ``native_train_default`` is set."""
     native_default = False         # what ``native=None`` picks where the native path can run: opt-in until DESIGN 7.3's timing shows it ahead
+    native_train_default = False   # what ``native=None`` picks when a gradient is required: nn.GRU, until DESIGN 7.5's timing decides
 
     def __init__(self, input_size, hidden_size, n_layers, dropout=0.0):
         super().__init__()
@@ -48,8 +57,9 @@ class _DynEnc(nn.Module):
         return [getattr(g, f'{n}_l{l}{sfx}') for l in range(g.num_layers) for sfx in ('', '_reverse')
                 for n in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh')]
 
-    def native_supported(self, x):
-        """Why the native path cannot serve ``x`` (a string), or None when it can."""
+    def native_supported(self, x, train=False):
+        """Why the native path cannot serve ``x`` (a string), or None when it can.  ``train``: the training path, which
+        applies inter-layer dropout itself."""
         from . import _native as nat
         import os
         g = self.gru
@@ -61,7 +71,7 @@ class _DynEnc(nn.Module):
             return 'parameters must be contiguous'
         if not (1 <= g.input_size <= 512 and 4 <= g.hidden_size <= 256 and g.hidden_size % 4 == 0 and 1 <= g.num_layers <= 4):
             return 'sizes out of range: input_size in [1, 512], hidden a multiple of 4 in [4, 256], 1 to 4 layers'
-        if self.training and g.dropout > 0 and g.num_layers > 1:
+        if not train and self.training and g.dropout > 0 and g.num_layers > 1:
             return 'inter-layer dropout is active (training mode)'
         if not os.path.exists(nat.LIB_PATH):
             return f'{nat.LIB_PATH} is not built'
@@ -119,6 +129,24 @@ class _DynEnc(nn.Module):
                                             work.data_ptr(), nbytes.value, torch.cuda.current_stream(dev).cuda_stream))
         return y, hn
 
+    def _run_native_train(self, x, lens, drop=None):
+        """The native training path: y and h_n attached to the autograd graph.  ``drop``: the inter-layer multipliers
+        [n_layers - 1, max(lens), B, 2 H] (0 or 1 / (1 - p)); drawn here in training mode when None."""
+        B, H, dev, g = x.shape[1], self.hidden_size, x.device, self.gru
+        T = int(lens.max())
+        assert lens.numel() == B and int(lens.min()) >= 1 and T <= x.shape[0], 'lengths do not fit the input'
+        x = x[:T]                                                               # (autograd pads the gradient of the rows behind)
+        with torch.cuda.device(dev):
+            self._native_handle(dev)
+            d_len = lens.to(torch.int32).to(dev)
+            if drop is None and self.training and g.dropout > 0 and g.num_layers > 1:
+                keep = 1.0 - g.dropout
+                drop = (torch.rand(g.num_layers - 1, T, B, 2 * H, device=dev) < keep).to(torch.float32) / keep
+            if drop is not None:
+                drop = drop.detach().to(torch.float32).contiguous()
+                assert tuple(drop.shape) == (g.num_layers - 1, T, B, 2 * H), 'drop does not fit [n_layers - 1, T, B, 2 H]'
+            return _DynEncTrain.apply(self, T, d_len, drop, x, *self._params())
+
     # ---- nn.GRU path (layers.py:63-76) -----------------------------------------------------------------------------------
     def _run_torch(self, x, lens):
         order = torch.argsort(lens, descending=True, stable=True)
@@ -132,20 +160,125 @@ class _DynEnc(nn.Module):
     def run(self, x, lens, native=None):
         """-> (y [max(lens), B, H], h_n [2 n_layers, B, H]), the reference's return value (layers.py:76)."""
         lens = torch.as_tensor(np.asarray(lens.cpu() if torch.is_tensor(lens) else lens), dtype=torch.int64)
-        if native is False or (native is None and not self.native_default):
-            return self._run_torch(x, lens)                                     # (nothing to find out about the native path)
+        if native is False:
+            return self._run_torch(x, lens)
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
-        why = 'a gradient is required' if needs_grad else self.native_supported(x)
+        if native is None and not (self.native_train_default if needs_grad else self.native_default):
+            return self._run_torch(x, lens)                                     # (nothing to find out about the native path)
+        if needs_grad and not self.training:                                    # eval mode keeps what it always did: no native gradient
+            why = 'a gradient is required and the module is in eval mode (the native training path serves training mode)'
+        else:
+            why = self.native_supported(x, train=needs_grad)
         if native is None:
             native = why is None
         if native:
             if why is not None:
-                raise RuntimeError(f'_DynEnc: the native path cannot run: {why}')
-            return self._run_native(x, lens)
+                raise RuntimeError(f"_DynEnc: the native {'training path (a gradient is required)' if needs_grad else 'path'} cannot run: {why}")
+            return self._run_native_train(x, lens) if needs_grad else self._run_native(x, lens)
         return self._run_torch(x, lens)
 
     def forward(self, x, lens, native=None):
         return self.run(x, lens, native)[0]
+
+
+def gru_param_grads(params, x, out, da, drop=None, need=None):
+    """The GEMMs behind one layer of the backward recurrence (include/dsp_frontend.h: dsp_bigru_backward).  params: the
+    layer's weight_ih, weight_hh, bias_ih, bias_hh of the forward direction, then of the reverse one; x [T, B, in]: the
+    layer's input as the kernel read it (dropout multipliers applied); out [T, B, 2 H]: the layer's output rows, forward |
+    reverse, zero rows behind each column's end; da [T, B, 2, 4 H]: the gradients of the pre-activations, n_x | r | z | n_h;
+    drop [T, B, in]: the multipliers of x, or None.  -> (dx -- the gradient of the layer's input in front of the
+    multipliers -- then the eight parameter gradients in the order of ``params``); ``need`` (9 booleans) leaves out what is
+    not wanted."""
+    T, B, I = x.shape
+    H = out.shape[2] // 2
+    need = [True] * 9 if need is None else need
+    d2, x2 = da.reshape(T * B, 2, 4 * H), x.reshape(T * B, I)
+    rzn = lambda v: torch.cat([v[H:], v[:H]], 0)            # rows n | r | z -> nn.GRU's r | z | n
+    res = [None] * 9
+    dx = None
+    zero = out.new_zeros(1, B, H)
+    for d in (0, 1):
+        w_ih = params[4 * d]
+        a_ih, a_hh = d2[:, d, :3 * H], d2[:, d, H:]          # [T B, 3 H]: (n_x | r | z) and (r | z | n_h)
+        if need[0]:
+            part = a_ih @ torch.cat([w_ih[2 * H:], w_ih[:2 * H]], 0)
+            dx = part if dx is None else dx + part
+        if need[1 + 4 * d]: res[1 + 4 * d] = rzn(a_ih.t() @ x2)
+        if need[2 + 4 * d]:
+            hp = torch.cat([zero, out[:-1, :, :H]], 0) if d == 0 else torch.cat([out[1:, :, H:], zero], 0)
+            res[2 + 4 * d] = a_hh.t() @ hp.reshape(T * B, H)
+        if need[3 + 4 * d]: res[3 + 4 * d] = rzn(a_ih.sum(0))
+        if need[4 + 4 * d]: res[4 + 4 * d] = a_hh.sum(0)
+    if need[0]:
+        dx = dx.view(T, B, I)
+        res[0] = dx * drop if drop is not None else dx
+    return tuple(res)
+
+
+class _DynEncTrain(torch.autograd.Function):
+    """_DynEnc's native training path.  forward: dsp_bigru_forward_train (the forward kernels, which also save the tape and keep
+    every layer's output rows); backward: per layer, top down, dsp_bigru_backward (the recurrence, one launch) and
+    ``gru_param_grads``, whose dx is the next layer's incoming gradient.  Inputs: (module, T, d_len int32 [B], drop or None, x,
+    the 8 n_layers parameters in nn.GRU's order); outputs: y [T, B, H] and h_n [2 n_layers, B, H], both differentiable."""
+
+    @staticmethod
+    def forward(ctx, mod, T, d_len, drop, x, *params):
+        from . import _native as nat
+        ctx.set_materialize_grads(False)                     # an unused output hands None to backward, not a tensor of zeros
+        B, H, L, dev = x.shape[1], mod.hidden_size, mod.gru.num_layers, x.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        xc = x.detach().contiguous()
+        handle, lib = mod._native_handle(dev), nat.load()
+        nbytes = nat.c_i64(0)
+        nat.check(lib.dsp_bigru_tape_bytes(handle, T, B, nat.C.byref(nbytes)))
+        tape = torch.empty(nbytes.value // 4, **f32)
+        y, hn = torch.empty(T, B, H, **f32), torch.empty(2 * L, B, H, **f32)
+        nat.check(lib.dsp_bigru_forward_train(handle, xc.data_ptr(), T, B, d_len.data_ptr(), None if drop is None else drop.data_ptr(),
+                                              y.data_ptr(), hn.data_ptr(), tape.data_ptr(), nbytes.value,
+                                              torch.cuda.current_stream(dev).cuda_stream))
+        ctx.mod, ctx.tape_bytes, ctx.handle_key, ctx.has_drop = mod, nbytes.value, mod._handle_key, drop is not None
+        ctx.save_for_backward(xc, d_len, tape, *([drop] if drop is not None else []), *params)
+        return y, hn
+
+    @staticmethod
+    def backward(ctx, g_y, g_hn):
+        from . import _native as nat
+        mod = ctx.mod
+        now = ctx.handle_key[:1] + tuple((p.data_ptr(), p._version) for p in mod._params())
+        if mod._handle is None or mod._handle_key != ctx.handle_key or now != ctx.handle_key:
+            raise RuntimeError('_DynEnc: a parameter was modified between the native forward and its backward')
+        saved = ctx.saved_tensors
+        xc, d_len, tape = saved[:3]
+        drop = saved[3] if ctx.has_drop else None
+        params = [p.detach() for p in saved[4 if ctx.has_drop else 3:]]
+        T, B, _ = xc.shape
+        H, L, dev = mod.hidden_size, mod.gru.num_layers, xc.device
+        grads = [None] * (1 + 8 * L)
+        if g_y is None and g_hn is None:
+            return (None,) * 4 + tuple(grads)
+        gp = lambda g: None if g is None else g.to(torch.float32).contiguous()
+        g, g_hn = gp(g_y), gp(g_hn)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        lib = nat.load()
+        with torch.cuda.device(dev):
+            off = nat.c_i64(0)
+            rows = []
+            for l in range(L):
+                nat.check(lib.dsp_bigru_tape_rows(mod._handle, l, T, B, nat.C.byref(off)))
+                rows.append(tape[off.value // 4:off.value // 4 + T * B * 2 * H].view(T, B, 2 * H))
+            for l in range(L - 1, -1, -1):
+                da = torch.empty(T, B, 2, 4 * H, dtype=torch.float32, device=dev)
+                nat.check(lib.dsp_bigru_backward(mod._handle, l, T, B, d_len.data_ptr(), tape.data_ptr(), ctx.tape_bytes, ptr(g),
+                                                 None if g_hn is None else g_hn[2 * l:].data_ptr(), da.data_ptr(),
+                                                 torch.cuda.current_stream(dev).cuda_stream))
+                dl = drop[l - 1] if (drop is not None and l > 0) else None
+                x_l = xc if l == 0 else (rows[l - 1] if dl is None else rows[l - 1] * dl)
+                need = [l > 0 or ctx.needs_input_grad[4]] + list(ctx.needs_input_grad[5 + 8 * l:13 + 8 * l])
+                res = gru_param_grads(params[8 * l:8 * l + 8], x_l, rows[l], da, dl, need)
+                grads[1 + 8 * l:9 + 8 * l] = res[1:]
+                g = res[0]
+            grads[0] = g
+        return (None,) * 4 + tuple(grads)
 
 
 class RNNHead(nn.Module):

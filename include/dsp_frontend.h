@@ -562,6 +562,59 @@ int dsp_bigru_workspace_bytes(const dsp_bigru* h, int32_t T, int32_t B, int64_t*
 int dsp_bigru_forward(const dsp_bigru* h, const float* d_x, int32_t T, int32_t B, const int32_t* d_len, float* d_y,
                       float* d_hn, void* d_work, int64_t work_bytes, void* stream);
 
+/*
+ * Training mode of the same encoder: a forward that also saves what the backward pass needs (the "tape"), and the backward
+ * recurrence of one layer (csrc/kernels_bigru_bwd.h, one launch per layer of the forward's shape, run in the opposite order of
+ * the forward's steps).  dsp_bigru_create packs a second, transposed copy of every weight_hh for it (rounded up to whole
+ * tiles: 4 H * 32 ceil(H / 128) * 4 bytes per layer and direction, 0.4 MB at H = 200).
+ *
+ * dsp_bigru_tape_bytes: the size of the caller's tape buffer at (T, B):
+ *   n_layers * (T B 2 H  +  2 ceil(B / 16) T 64 H) * 4 bytes        (1.6 GB at 2 layers, T 200, B 512, H 200).
+ * It holds, per layer, the [T, B, 2 H] output rows (forward | reverse; EVERY row is written, exact zeros at t >= len[b]) --
+ * there is no ping-pong here: the backward reads h of the step before from them and the parameter GEMMs read a layer's input
+ * from them -- and behind the rows of all layers, per layer, direction, slice of 16 columns, step and (hidden unit, column), r, z, n
+ * behind their non-linearities and n_h = W_hn h + b_hn, the factor r multiplied.  Only the steps a slice visits are stored.
+ * dsp_bigru_tape_rows: the byte offset of layer `layer`'s output rows in the tape.
+ *
+ * dsp_bigru_forward_train: dsp_bigru_forward with d_tape (16-byte aligned, at least dsp_bigru_tape_bytes; the caller owns it and
+ * keeps it unchanged until the last backward call) in place of the workspace.  d_drop: NULL, or [n_layers - 1, T, B, 2 H] fp32
+ * multipliers (0 or 1 / (1 - p), drawn by the caller): d_drop[l - 1] multiplies the input of layer l >= 1 (nn.GRU's inter-layer
+ * dropout).  With d_drop == NULL, d_y and d_hn are bit for bit what dsp_bigru_forward writes; either may be NULL.
+ *
+ * dsp_bigru_backward, for ONE layer: d_g is the gradient of a loss with respect to the layer's output -- for the top layer
+ * (layer == n_layers - 1) that of d_y, [T, B, H], read by both directions (y is their sum); below it [T, B, 2 H], forward |
+ * reverse, the dx of the layer above.  d_g_hn [2, B, H]: the gradient with respect to this layer's two rows of d_hn.  h_n of the
+ * forward direction is h at len - 1 and stays unchanged through the steps behind it, h_n of the reverse direction is h at
+ * t = 0, the last step its forward runs: BOTH are the state the backward recurrence starts from, so d_g_hn seeds dh before the
+ * first step it visits (t = max len - 1 of the slice for the forward direction, t = 0 for the reverse one).  Either of d_g and
+ * d_g_hn may be NULL, not both.  Per step t < len[b], with dh the gradient of h' and h the state in front of the step (the
+ * saved row t - 1, 0 at t = 0, for the forward direction; row t + 1 if t + 1 < len[b], else 0, for the reverse one):
+ *   dh += g[t];   dn = dh (1 - z);   dz = dh (h - n);   dn_pre = dn (1 - n^2);
+ *   da_r = dn_pre n_h r (1 - r);   da_z = dz z (1 - z);   da_nx = dn_pre;   da_nh = dn_pre r;
+ *   dh  = dh z + W_hr^T da_r + W_hz^T da_z + W_hn^T da_nh.
+ * A column with t >= len[b] does nothing: dh passes through and its row is exact zeros.  It writes
+ *   d_da [T, B, 2, 4 H]   per step, column and direction  da_nx | da_r | da_z | da_nh  (H floats each): floats [0, 3 H) are
+ *                         (n | r | z) of the input side, floats [H, 4 H) are (r | z | n) of the hidden side, both contiguous.
+ * Every element is written on every call, and the same arguments give the same bits.  T, B and d_len must be those of the
+ * forward call.  The gradients of the parameters and of the layer's input are GEMMs over d_da, left to the caller (K = T B;
+ * features/classifier.py::gru_param_grads does them with torch.matmul).  With A_i = d_da[.., dir, 0 : 3 H] and
+ * A_h = d_da[.., dir, H : 4 H] as [T B, 3 H], x_l the layer's input as the kernel read it (multipliers applied) and h' the
+ * state in front of each step as above, per direction:
+ *   d weight_ih = (A_i^T x_l, rows n | r | z reordered to r | z | n)      d bias_ih = the column sums of A_i, reordered alike
+ *   d weight_hh =  A_h^T h'                                              d bias_hh = the column sums of A_h
+ *   d x_l       = the sum over the two directions of A_i (weight_ih, rows reordered to n | r | z), times d_drop[l - 1] where
+ *                 there are multipliers: the d_g of the layer below, or the gradient of d_x.
+ * The caller interleaves the layers, top down, with these GEMMs.  Each call is launches on `stream` without allocation
+ * (capturable); bad sizes, a layer out of range, NULL or misaligned pointers, no gradient at all and a short tape are
+ * DSP_EINVAL, checked before any device call.
+ */
+int dsp_bigru_tape_bytes(const dsp_bigru* h, int32_t T, int32_t B, int64_t* bytes);
+int dsp_bigru_tape_rows(const dsp_bigru* h, int32_t layer, int32_t T, int32_t B, int64_t* offset_bytes);
+int dsp_bigru_forward_train(const dsp_bigru* h, const float* d_x, int32_t T, int32_t B, const int32_t* d_len, const float* d_drop,
+                            float* d_y, float* d_hn, void* d_tape, int64_t tape_bytes, void* stream);
+int dsp_bigru_backward(const dsp_bigru* h, int32_t layer, int32_t T, int32_t B, const int32_t* d_len, const void* d_tape,
+                       int64_t tape_bytes, const float* d_g, const float* d_g_hn, float* d_da, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

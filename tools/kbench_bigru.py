@@ -7,6 +7,10 @@ and RNNHead and HMRNNHead at B = 512 with the native encoder and without it.
 
     python tools/kbench_bigru.py [--out profiles/bigru_kbench.json] [--rounds 5]
     python tools/kbench_bigru.py --kernel-only B [--layers L]   # one warm-up and ten native calls, for a rocprofv3 --kernel-trace run
+    python tools/kbench_bigru.py --train [--out profiles/bigru_train_kbench.json] [--parent-lib PATH]
+        # the training step: forward_train, the backward recurrence per layer, the GEMMs and the whole autograd step, native
+        # against the nn.GRU path (39 -> 200, 2 and 3 layers, B 8 / 64 / 512, full and ragged); HMRNNHead and RNNHead training
+        # steps at B 512, everything native against everything default; and dsp_bigru_forward against a build of the parent commit
 
 Times are device-event times around calls on one stream, median over the rounds (min and max are kept beside it); every
 shape is warmed up first.  A direction of a layer multiplies 3 H (in + H) weights per column and step (in = 39, then 2 H).
@@ -43,13 +47,170 @@ def ragged_lengths(rng, B, T):
     return np.clip(n, 1, T)
 
 
+def forward_rounds(rounds):
+    """Child process of --train's guard: dsp_bigru_forward (2 layers, B 512, full lengths) of the library DSP_FRONTEND_LIB names."""
+    import ctypes
+    from features import _native as nat
+    from features.classifier import _DynEnc, fill_parameters
+    probe = ctypes.CDLL(nat.LIB_PATH)
+    for name in [n for n in nat.SIGNATURES if not hasattr(probe, name)]:     # a build of an older commit: the forward needs none of them
+        del nat.SIGNATURES[name]
+    dev = torch.device('cuda', 0)
+    torch.manual_seed(0)
+    enc = _DynEnc(39, 200, 2).eval()
+    fill_parameters(enc, 1)
+    enc = enc.to(dev)
+    x = torch.from_numpy(np.random.default_rng(2).standard_normal((200, 512, 39)).astype(np.float32)).to(dev)
+    lens = np.full(512, 200)
+    with torch.no_grad():
+        enc.run(x, lens, native=True)
+        torch.cuda.synchronize()
+        print(json.dumps([_time(lambda: enc.run(x, lens, native=True), 5) for _ in range(rounds)]))
+
+
+def _forward_ms_in_child(lib_path, rounds):
+    import subprocess
+    env = dict(os.environ, DSP_FRONTEND_LIB=lib_path)
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), '--forward-rounds', str(rounds)], env=env, check=True,
+                         capture_output=True, text=True, timeout=300).stdout
+    return json.loads(out.strip().splitlines()[-1])
+
+
+def train(args):
+    from features import _native as nat
+    from features.classifier import _DynEnc, HMRNNHead, RNNHead, fill_parameters, gru_param_grads
+    dev = torch.device('cuda', 0)
+    I, H, T = 39, 200, 200
+    rng = np.random.default_rng(2)
+    res = {'shape': {'input_size': I, 'hidden': H, 'T': T}, 'encoder_train': {}, 'heads_train': {}, 'forward_guard': {}}
+    lib = nat.load()
+    new = lambda *s: torch.from_numpy(rng.standard_normal(s).astype(np.float32)).to(dev)
+
+    def write():
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'w') as fh:
+                json.dump(res, fh, indent=1)
+
+    for L in (2, 3):
+        torch.manual_seed(0)
+        enc = _DynEnc(I, H, L)
+        fill_parameters(enc, 1)
+        enc = enc.to(dev)
+        params = [p.detach() for p in enc._params()]
+        for B in (8, 64, 512):
+            x, g_y, g_hn = new(T, B, I), new(T, B, H), new(2 * L, B, H)
+            xg = x.clone().requires_grad_(True)
+            for kind, lens in (('full', np.full(B, T)), ('ragged', ragged_lengths(rng, B, T))):
+                lens[0] = T                                                     # the same T rows on both paths
+                d_len = torch.from_numpy(lens.astype(np.int32)).to(dev)
+
+                def step(native):
+                    y, hn = enc.run(xg, lens, native=native)
+                    torch.autograd.backward([y, hn], [g_y, g_hn])
+                    enc.zero_grad(set_to_none=True); xg.grad = None
+                # the parts of the native step on raw buffers
+                handle = enc._native_handle(dev)
+                n, off = nat.c_i64(0), nat.c_i64(0)
+                nat.check(lib.dsp_bigru_tape_bytes(handle, T, B, nat.C.byref(n)))
+                tape = torch.empty(n.value // 4, device=dev)
+                y, hn = torch.empty(T, B, H, device=dev), torch.empty(2 * L, B, H, device=dev)
+                das = [torch.empty(T, B, 2, 4 * H, device=dev) for _ in range(L)]
+                gs = [new(T, B, 2 * H) for _ in range(L - 1)] + [g_y]            # stand-ins of dx for the layers below the top
+                rows = []
+                for l in range(L):
+                    nat.check(lib.dsp_bigru_tape_rows(handle, l, T, B, nat.C.byref(off)))
+                    rows.append(tape[off.value // 4:off.value // 4 + T * B * 2 * H].view(T, B, 2 * H))
+                st = lambda: torch.cuda.current_stream(dev).cuda_stream
+                fwd = lambda: nat.check(lib.dsp_bigru_forward_train(handle, x.data_ptr(), T, B, d_len.data_ptr(), None, y.data_ptr(),
+                                                                    hn.data_ptr(), tape.data_ptr(), n.value, st()))
+                bwd = lambda l: (lambda: nat.check(lib.dsp_bigru_backward(handle, l, T, B, d_len.data_ptr(), tape.data_ptr(), n.value,
+                                                                          gs[l].data_ptr(), g_hn[2 * l:].data_ptr(), das[l].data_ptr(), st())))
+
+                def gemms():
+                    for l in range(L):
+                        gru_param_grads(params[8 * l:8 * l + 8], x if l == 0 else rows[l - 1], rows[l], das[l])
+                runs = {'forward_train': (fwd, 3), **{f'backward_layer{l}': (bwd(l), 3) for l in range(L)}, 'gemms': (gemms, 3),
+                        'native_step': (lambda: step(True), 2), 'nn_gru_step': (lambda: step(False), 2)}
+                for f, _ in runs.values():
+                    f()
+                torch.cuda.synchronize()
+                ts = {k: [] for k in runs}
+                for _ in range(args.rounds):                                    # alternating
+                    for k, (f, reps) in runs.items():
+                        ts[k].append(_time(f, reps))
+                r = {k: _stats(v) for k, v in ts.items()}
+                r['tape_bytes'], r['mean_len'] = n.value, float(lens.mean())
+                r['sum_of_parts_ms'] = sum(v['median_ms'] for k, v in r.items() if isinstance(v, dict) and not k.endswith('_step'))
+                r['speedup'] = r['nn_gru_step']['median_ms'] / r['native_step']['median_ms']
+                res['encoder_train'][f'layers{L}_B{B}_{kind}'] = r
+                print(f"layers {L} B {B:4d} {kind:6s}: forward_train {r['forward_train']['median_ms']:.2f} + backward "
+                      + ' + '.join(f"{r[f'backward_layer{l}']['median_ms']:.2f}" for l in range(L))
+                      + f" + GEMMs {r['gemms']['median_ms']:.2f} = {r['sum_of_parts_ms']:.2f} ms; autograd step native "
+                      f"{r['native_step']['median_ms']:.2f} ms, nn.GRU {r['nn_gru_step']['median_ms']:.2f} ms -> x{r['speedup']:.2f}; "
+                      f"tape {n.value / 2**20:.0f} MiB", flush=True)
+                del tape, das, rows
+                write()
+    # whole training steps at B = 512 on [200, 512, 39]: everything native against everything default
+    B = 512
+    inp = new(T, B, I)
+    len0 = ragged_lengths(rng, B, T)
+    len0[0] = T
+    wl = new(B, 20)
+    torch.manual_seed(0)
+    hm, rn = HMRNNHead().to(dev), RNNHead().to(dev)
+
+    def head_step(head, **kw):
+        lo = head(inp, len0, **kw)
+        ((lo[0] if isinstance(lo, tuple) else lo) * wl).sum().backward()
+        head.zero_grad(set_to_none=True)
+    runs = {'HMRNNHead_all_native': lambda: head_step(hm, dropout=True, native=True, native_enc=True),
+            'HMRNNHead_native_hmlstm_nn_gru': lambda: head_step(hm, dropout=True, native=True, native_enc=False),
+            'HMRNNHead_default': lambda: head_step(hm, dropout=True),
+            'RNNHead_native_enc': lambda: head_step(rn, native_enc=True),
+            'RNNHead_default': lambda: head_step(rn)}
+    for f in runs.values():
+        f()
+    torch.cuda.synchronize()
+    ts = {k: [] for k in runs}
+    for _ in range(args.rounds):
+        for k, f in runs.items():
+            ts[k].append(_time(f, 1))
+    for k in runs:
+        res['heads_train'][k] = _stats(ts[k])
+        print(f"{k} forward + backward (B = 512, ragged): {res['heads_train'][k]['median_ms']:.1f} ms", flush=True)
+    write()
+    if args.parent_lib:
+        del hm, rn, inp
+        torch.cuda.empty_cache()
+        t_par, t_new = [], []
+        for _ in range(2):                                                    # alternating processes
+            t_par += _forward_ms_in_child(os.path.abspath(args.parent_lib), args.rounds)
+            t_new += _forward_ms_in_child(nat.LIB_PATH, args.rounds)
+        g = {'layers': 2, 'B': 512, 'parent': _stats(t_par), 'this_tree': _stats(t_new)}
+        g['parent_spread_ms'] = g['parent']['max_ms'] - g['parent']['min_ms']
+        g['difference_ms'] = g['this_tree']['median_ms'] - g['parent']['median_ms']
+        res['forward_guard'] = g
+        print(f"dsp_bigru_forward (2 layers, B = 512): parent {g['parent']['median_ms']:.3f} ms (min {g['parent']['min_ms']:.3f}, max "
+              f"{g['parent']['max_ms']:.3f}), this tree {g['this_tree']['median_ms']:.3f} ms (min {g['this_tree']['min_ms']:.3f}, max "
+              f"{g['this_tree']['max_ms']:.3f})", flush=True)
+    write()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--kernel-only', type=int, default=0, metavar='B')
     ap.add_argument('--layers', type=int, default=2)
+    ap.add_argument('--train', action='store_true')
+    ap.add_argument('--parent-lib', default=None, help='with --train: a build of the parent commit, for the forward guard')
+    ap.add_argument('--forward-rounds', type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.forward_rounds:
+        return forward_rounds(args.forward_rounds)
+    if args.train:
+        return train(args)
     from features.classifier import _DynEnc, HMRNNHead, RNNHead, fill_parameters
     dev = torch.device('cuda', 0)
     I, H, T = 39, 200, 200
