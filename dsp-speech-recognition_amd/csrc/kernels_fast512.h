@@ -336,12 +336,16 @@ __device__ __forceinline__ F512Group f512_locate_frame(const F512Params& P, cons
 //     middle of that window (delta of the edge-replicated x, then delta of the edge-replicated delta, exactly as the
 //     reference composes them), i.e. rows trail the computation by 2 N <= 4 frames.
 //   * The last 4 rows of a wave's run need the first group of the NEXT wave: every wave publishes its first group's
-//     cepstra in a small LDS area, ONE barrier follows the first iteration, and a final iteration without
-//     computation emits the tail.  The first wave of the workgroup also emits its own first rows.
+//     cepstra in a small LDS area after its first iteration, and a final iteration without computation -- every wave
+//     runs exactly one, and it starts with the workgroup's ONE barrier -- emits the tail.  The first wave of the
+//     workgroup also emits its own first rows.
+//   * With 8 S = 256 (NSTAGE - 1) samples (S = 160, six staging rounds) the last staged vector of a group is round 0 of
+//     the run's next group: the wave carries it over instead of fetching it again.
 template <int NROWS, int NI, int CAPS, int NSTAGE, int DTYPE, int WAVES, bool RAGGED, int FD = 0>
 __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_kernel(F512Params P, BatchGeom bg,
                                                              const void* __restrict__ wave,
                                                              float* __restrict__ out, int64_t ld_out) {
+    static_assert(!(FD != 0 && RAGGED), "the fused-delta run structure (carried staging vector, halo barrier) serves dense batches only");
     extern __shared__ __attribute__((aligned(256))) float smem_f[];
     float* const smem = smem_f;
     const int tid = threadIdx.x;
@@ -432,6 +436,11 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
     // the wave buffers where every wave leaves its first group (8 frames x 14 coefficients) for its predecessor.
     F512Run run = {0, 0, 0, 0};
     float fd_p0 = 0.f, fd_p1 = 0.f;
+    // ... and the last staged vector of that group: with 8 S = 256 (NSTAGE - 1) it is, lane for lane, round 0 of the
+    // run's next group (same four pre-emphasised samples), which is then not fetched again.  fd_cy_utt: the utterance
+    // whose next group may take it, -1 when the previous group was not fast-staged (or the plan has another hop).
+    float4 fd_cy = make_float4(0.f, 0.f, 0.f, 0.f);
+    int fd_cy_utt = -1;
     float* const fd_halo = smem + P.tab_floats + WAVES * F512_WAVE_FLOATS;
     if constexpr (FD) run = f512_run(bg, (int)blockIdx.x, (int)gridDim.x, wid, WAVES);
     const int n_iter = FD ? run.n_groups + 1 : nfull + 1;   // FD: one more, computation-free iteration emits the tail rows
@@ -502,9 +511,16 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
                 F512Raw<DTYPE> raw[NSTAGE];
                 float prev[NSTAGE];
                 const int64_t e0 = g0 + 4 * lane;
+                // Fused delta: the wave staged this group's round 0 as the last round of its previous group (see fd_cy)
+                bool carried = false;
+#ifndef F512_STAGE_DPP
+                if constexpr (FD != 0) carried = fd_cy_utt == utt;
+#endif
 #pragma unroll
-                for (int r = 0; r < NSTAGE; ++r)
+                for (int r = 0; r < NSTAGE; ++r) {
+                    if (FD != 0 && r == 0 && carried) continue;
                     raw[r] = RAGGED ? f512_load_raw_unaligned<DTYPE>(wave, e0 + 256 * r) : f512_load_raw<DTYPE>(wave, e0 + 256 * r);
+                }
                 // the sample before each vector: one more (cache-resident) dword per lane instead of a DPP shift,
                 // a v_readlane and a move per vector
 #ifndef F512_STAGE_DPP
@@ -512,7 +528,8 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
                 for (int r = 1; r < NSTAGE; ++r) prev[r] = dsp_load_sample<DTYPE>(wave, e0 + 256 * r - 1);
 #endif
                 // an utterance's first sample is not filtered (sigproc.py:185): y[0] = x[0] - c * 0
-                if (base > 0) prev[0] = dsp_load_sample<DTYPE>(wave, e0 - 1);
+                if (FD != 0 && carried) prev[0] = 0.f;
+                else if (base > 0) prev[0] = dsp_load_sample<DTYPE>(wave, e0 - 1);
                 else prev[0] = lane > 0 ? dsp_load_sample<DTYPE>(wave, e0 - 1) : 0.f;
 #ifdef F512_STAGE_DPP   // A/B: the round-2 form (previous sample through DPP wave_shr + v_readlane)
                 float left = prev[0];
@@ -527,12 +544,16 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
 #pragma unroll
                 for (int r = 0; r < NSTAGE; ++r) {
                     float x[4];
-                    f512_unpack<DTYPE>(raw[r], x);
                     float4 y;
-                    y.x = fmaf(-P.preemph, prev[r], x[0]);
-                    y.y = fmaf(-P.preemph, x[0], x[1]);
-                    y.z = fmaf(-P.preemph, x[1], x[2]);
-                    y.w = fmaf(-P.preemph, x[2], x[3]);
+                    if (FD != 0 && r == 0 && carried) {   // x[] stays unset: the ragged statistics below never meet a carried round
+                        y = fd_cy;
+                    } else {
+                        f512_unpack<DTYPE>(raw[r], x);
+                        y.x = fmaf(-P.preemph, prev[r], x[0]);
+                        y.y = fmaf(-P.preemph, x[0], x[1]);
+                        y.z = fmaf(-P.preemph, x[1], x[2]);
+                        y.w = fmaf(-P.preemph, x[2], x[3]);
+                    }
                     *reinterpret_cast<float4*>(wbuf + 4 * lane + 256 * r) = y;
                     if constexpr (RAGGED) {
                         if (do_stats) {
@@ -656,6 +677,7 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
                 }
             }
         }
+        if constexpr (FD != 0) fd_cy_utt = (fast_stage && 8 * P.S == 256 * (NSTAGE - 1)) ? utt : -1;
         if constexpr (RAGGED) {
             if (do_stats) {
                 // sums over each row of 16 lanes with DPP (vector pipe, no LDS traffic)
@@ -701,6 +723,11 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
         }
         FFTReg<32>::template run<NROWS>(z);
         F512_FENCE();
+        // The last staged vector, for the run's next group (fd_cy): picked up from the wave buffer here, after the
+        // register peak of pass 1 and before the exchange overwrites the samples.  Read after every group, one ds_read_b128 of the lane's own slot:
+        // after a slow-staged group, and in plans with another hop (8 S != 256 (NSTAGE - 1)), fd_cy_utt is -1 and the
+        // value is discarded.
+        if constexpr (FD != 0 && NSTAGE * 256 <= F512_WAVE_FLOATS) fd_cy = *reinterpret_cast<const float4*>(wbuf + 4 * lane + 256 * (NSTAGE - 1));
         F512_PIN(z);
         F512_STAMP(2);
         F512_PIN(z);
@@ -1047,11 +1074,15 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
             //      the next wave's first group from the halo area); rows 4..11 are emitted ----
             const int pr = (((c & 1) << 1) ^ ((c & 2) << 1) ^ ((c & 4) ? 14 : 0)) >> 1;   // coefficient pair of this lane; 7 = none
             const bool tail = r >= run.n_groups;
-            if (r == 0) {   // leave the first group for the wave before this one; the workgroup's only barrier
+            if (r == 0) {   // leave the first group for the wave before this one
                 if (pr < 7) *reinterpret_cast<float2*>(fd_halo + (wid * 8 + f) * 14 + 2 * pr) = make_float2(v0, v1);
-                __syncthreads();
             }
             if (tail) {
+                // The workgroup's only barrier after the tables.  Every wave runs exactly one tail iteration; the halo is
+                // written once, at r == 0, and read only here.  A wave with several groups published its first group long
+                // before it arrives (wave 0, with the most groups, arrives last); a wave whose run is a single group comes
+                // here straight from publishing it.  No wave waits for another wave's first HBM fetch alone any more.
+                __syncthreads();
                 const int nw = wid + 1 < WAVES ? wid + 1 : wid;   // no next wave: rows 8.. lie outside the workgroup, never used
                 const float2 hv = *reinterpret_cast<const float2*>(fd_halo + (nw * 8 + f) * 14 + 2 * (pr < 7 ? pr : 0));
                 v0 = hv.x;
