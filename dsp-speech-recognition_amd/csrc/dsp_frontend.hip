@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "dsp_common.h"
+#include "dsp_host.h"
 #include "kernels_generic.h"
 #include "kernels_fast512.h"
 #include "kernels_fast1536.h"
@@ -18,10 +19,6 @@
 #include "kernels_vad.h"
 #include "kernels_pitch.h"
 #include "kernels_cepstrum.h"
-#include "kernels_hmlstm.h"
-#include "kernels_hmlstm_bwd.h"
-#include "kernels_bigru.h"
-#include "kernels_bigru_bwd.h"
 
 thread_local int g_host_dry_run = 0;   // dsp_debug_host_dry_run: plan tables in host memory (sanitizer build, no GPU)
 
@@ -36,31 +33,9 @@ struct dsp_layout {
     int device;
 };
 
-// Packed parameters of one HM-LSTM (include/dsp_frontend.h: dsp_hmlstm); immutable after dsp_hmlstm_create.
-struct dsp_hmlstm {
-    int32_t I, H1, H2;
-    float* d_packed;       // one allocation: cell 1 W_01 | U_21 | U_11 | bias, cell 2 W_01 | U_11 | bias (kernels_hmlstm.h layout)
-    HmCell c1, c2;
-    const float4* wt[4];   // in the same allocation: U_11(2)^T, W_01(2)^T, U_21^T, U_11(1)^T (kernels_hmlstm_bwd.h layout)
-    int device;
-};
+static thread_local std::string g_err;  // dsp_last_error
 
-// Packed parameters of one bidirectional GRU encoder (include/dsp_frontend.h: dsp_bigru); immutable after dsp_bigru_create.
-struct dsp_bigru {
-    int32_t I, H, L;
-    float* d_packed;       // one allocation: per layer and direction the concatenated [W_ih | W_hh] tiles, then the bias (kernels_bigru.h layout)
-    GruDir dir[GRU_MAX_LAYERS][2];
-    const float4* wt[GRU_MAX_LAYERS][2];   // in the same allocation: weight_hh^T per layer and direction (kernels_bigru_bwd.h layout)
-    int32_t ngx[GRU_MAX_LAYERS], ng[GRU_MAX_LAYERS];
-    int device;
-};
-
-namespace {
-
-thread_local std::string g_err;
-thread_local int g_force_generic = 0;   // test switch, per calling thread: other threads' calls are unaffected
-
-int fail(int code, const char* fmt, ...) {
+int dsp_fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -70,11 +45,9 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(DSP_EHIP, "%s: %s", #expr, hipGetErrorString(e_));  \
-    } while (0)
+namespace {
+
+thread_local int g_force_generic = 0;   // test switch, per calling thread: other threads' calls are unaffected
 
 template <typename T>
 int upload(T** d, const T* h, size_t n) {
@@ -82,13 +55,6 @@ int upload(T** d, const T* h, size_t n) {
     if (n == 0) return DSP_OK;
     HIP_TRY(dsp_table_alloc_copy(reinterpret_cast<void**>(d), h, n * sizeof(T)));
     return DSP_OK;
-}
-
-int grid_for(int64_t work_items, int per_block) {
-    int64_t blocks = (work_items + per_block - 1) / per_block;
-    if (blocks < 1) blocks = 1;
-    const int64_t cap = (int64_t)dsp_cu_count() * 8;  // CUs x 8 resident blocks; the kernels grid-stride beyond
-    return (int)(blocks < cap ? blocks : cap);
 }
 
 bool factor_half_fft(int n2, std::vector<int>& radix) {
@@ -102,12 +68,12 @@ bool factor_half_fft(int n2, std::vector<int>& radix) {
 int check_geom(const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets,
                const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_frames_total,
                int64_t uniform_samples) {
-    if (!d_wave) return fail(DSP_EINVAL, "d_wave is NULL");
+    if (!d_wave) return dsp_fail(DSP_EINVAL, "d_wave is NULL");
     if (wave_dtype != DSP_WAVE_F32 && wave_dtype != DSP_WAVE_I16)
-        return fail(DSP_EINVAL, "unsupported wave_dtype %d", wave_dtype);
-    if (n_utt <= 0 || n_frames_total <= 0) return fail(DSP_EINVAL, "empty batch (n_utt=%d, frames=%lld)", n_utt, (long long)n_frames_total);
+        return dsp_fail(DSP_EINVAL, "unsupported wave_dtype %d", wave_dtype);
+    if (n_utt <= 0 || n_frames_total <= 0) return dsp_fail(DSP_EINVAL, "empty batch (n_utt=%d, frames=%lld)", n_utt, (long long)n_frames_total);
     if (uniform_samples <= 0 && (!d_sample_offsets || !d_frame_offsets))
-        return fail(DSP_EINVAL, "ragged batch needs d_sample_offsets and d_frame_offsets");
+        return dsp_fail(DSP_EINVAL, "ragged batch needs d_sample_offsets and d_frame_offsets");
     return DSP_OK;
 }
 
@@ -209,14 +175,14 @@ int check_owner_device(int owner, bool is_plan) {
     int dev = -1;
     HIP_TRY(hipGetDevice(&dev));
     if (dev == owner) return DSP_OK;
-    return is_plan ? fail(DSP_EINVAL, "plan belongs to device %d, current device is %d", owner, dev)
-                   : fail(DSP_EINVAL, "layout belongs to device %d, current device is %d", owner, dev);
+    return is_plan ? dsp_fail(DSP_EINVAL, "plan belongs to device %d, current device is %d", owner, dev)
+                   : dsp_fail(DSP_EINVAL, "layout belongs to device %d, current device is %d", owner, dev);
 }
 
 // dense batches: the caller's frame count must be n_utt utterances of T frames
 int check_dense_frames(int64_t n_frames_total, int32_t n_utt, int64_t T) {
     if (T * n_utt != n_frames_total)
-        return fail(DSP_EINVAL, "n_frames_total %lld != n_utt*T (%d*%lld)", (long long)n_frames_total, n_utt, (long long)T);
+        return dsp_fail(DSP_EINVAL, "n_frames_total %lld != n_utt*T (%d*%lld)", (long long)n_frames_total, n_utt, (long long)T);
     return DSP_OK;
 }
 
@@ -302,7 +268,7 @@ int features_batch_impl(const dsp_plan* plan, const void* d_wave, int wave_dtype
                         const int64_t* d_sample_offsets, const int64_t* d_frame_offsets, int32_t n_utt,
                         int64_t n_frames_total, int64_t uniform_samples, int out_kind, float* d_out,
                         int64_t ld_out, float* d_out2, void* stream, const DspRaggedTables* pre) {
-    if (!plan || !d_out) return fail(DSP_EINVAL, "plan/d_out is NULL");
+    if (!plan || !d_out) return dsp_fail(DSP_EINVAL, "plan/d_out is NULL");
     int rc = check_owner_device(plan->device, true);
     if (rc != DSP_OK) return rc;
     rc = check_geom(d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples);
@@ -314,24 +280,24 @@ int features_batch_impl(const dsp_plan* plan, const void* d_wave, int wave_dtype
         case DSP_OUT_POWSPEC: width = plan->K; break;
         case DSP_OUT_FBANK:
             width = plan->M;
-            if (plan->M <= 0) return fail(DSP_EINVAL, "plan has no mel filterbank");
-            if (!d_out2) return fail(DSP_EINVAL, "DSP_OUT_FBANK needs d_out2 (energy)");
+            if (plan->M <= 0) return dsp_fail(DSP_EINVAL, "plan has no mel filterbank");
+            if (!d_out2) return dsp_fail(DSP_EINVAL, "DSP_OUT_FBANK needs d_out2 (energy)");
             break;
         case DSP_OUT_MFCC:
             width = plan->C;
-            if (plan->M <= 0 || plan->C <= 0) return fail(DSP_EINVAL, "plan has no mel/DCT tables");
+            if (plan->M <= 0 || plan->C <= 0) return dsp_fail(DSP_EINVAL, "plan has no mel/DCT tables");
             break;
-        default: return fail(DSP_EINVAL, "unknown out_kind %d", out_kind);
+        default: return dsp_fail(DSP_EINVAL, "unknown out_kind %d", out_kind);
     }
     if (ld_out == 0) ld_out = width;
-    if (ld_out < width) return fail(DSP_EINVAL, "ld_out %lld < row width %d", (long long)ld_out, width);
+    if (ld_out < width) return dsp_fail(DSP_EINVAL, "ld_out %lld < row width %d", (long long)ld_out, width);
     BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, plan->L, plan->S);
     if (uniform_samples > 0 && (rc = check_dense_frames(n_frames_total, n_utt, bg.uniform_frames)) != DSP_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (out_kind == DSP_OUT_MFCC && !g_force_generic && !pre) {
         const int mrc = try_matrix_pipe(plan, d_wave, wave_dtype, bg, 0, d_out, ld_out, st);
         if (mrc == DSP_OK) return DSP_OK;
-        if (mrc < 0) return fail(mrc, "matrix-pipe MFCC kernel launch failed");
+        if (mrc < 0) return dsp_fail(mrc, "matrix-pipe MFCC kernel launch failed");
     }
     if (out_kind == DSP_OUT_MFCC && !g_force_generic && (plan->d_fast || plan->d_fast1536)) {
         BatchGeom fg = bg;
@@ -344,7 +310,7 @@ int features_batch_impl(const dsp_plan* plan, const void* d_wave, int wave_dtype
             frc = fast1536_launch(plan, fw, wave_dtype, fg, d_out, ld_out, st, pre);
         if (view && dsp_workspace_pool().release(view, st) != 0 && frc == DSP_OK) frc = DSP_EHIP;
         if (frc == DSP_OK) return DSP_OK;
-        if (frc < 0) return fail(frc, "fused kernel launch failed");
+        if (frc < 0) return dsp_fail(frc, "fused kernel launch failed");
     }
     return launch_generic(plan, d_wave, wave_dtype, bg, out_kind, d_out, ld_out, d_out2, st);
 }
@@ -361,10 +327,10 @@ int mfcc_delta_one_launch(const dsp_plan* plan, const void* d_wave, int wave_dty
     const BatchGeom fbg = make_geom(nullptr, nullptr, n_utt, n_frames_total, uniform_samples, plan->L, plan->S);
     const int mrc = try_matrix_pipe(plan, d_wave, wave_dtype, fbg, delta_n, d_out, 3 * (int64_t)plan->C, st);
     if (mrc == DSP_OK) return DSP_OK;
-    if (mrc < 0) return fail(mrc, "matrix-pipe MFCC + delta kernel launch failed");
+    if (mrc < 0) return dsp_fail(mrc, "matrix-pipe MFCC + delta kernel launch failed");
     if (!fast512_applicable(plan, fbg, d_wave, wave_dtype)) return 1;
     const int frc = fast512_launch_fused(plan, d_wave, wave_dtype, fbg, delta_n, d_out, st);
-    if (frc < 0) return fail(frc, "fused MFCC + delta kernel launch failed");
+    if (frc < 0) return dsp_fail(frc, "fused MFCC + delta kernel launch failed");
     return frc;
 }
 
@@ -409,9 +375,9 @@ int mfcc_delta_via_scratch(const dsp_plan* plan, const void* d_wave, int wave_dt
         if (ragged && !have_pre) prefix_ceil_kernel<<<1, 1024, 0, st>>>(d_frame_offsets, n_utt, DT_SHIFT, tile_off);
         launch_delta_rows(blocks, st, cep, frames_geom(d_frame_offsets, n_utt, n_frames_total, uniform_frames), C, delta_n,
                           d_out, tiles, tile_off);
-        if (hipGetLastError() != hipSuccess) rc = fail(DSP_EHIP, "delta_rows_kernel launch failed");
+        if (hipGetLastError() != hipSuccess) rc = dsp_fail(DSP_EHIP, "delta_rows_kernel launch failed");
     }
-    if (dsp_workspace_pool().release(w, st) != 0 && rc == DSP_OK) rc = fail(DSP_EHIP, "workspace release failed");
+    if (dsp_workspace_pool().release(w, st) != 0 && rc == DSP_OK) rc = dsp_fail(DSP_EHIP, "workspace release failed");
     return rc;
 }
 
@@ -432,8 +398,8 @@ int vad_features_impl(const dsp_layout* layout, const void* d_wave, int wave_dty
                       const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_frames_total,
                       int64_t uniform_samples, int32_t frame_len, int32_t frame_step, int32_t use_sq,
                       double* d_amp_sum, int32_t* d_zcr, void* stream) {
-    if (!d_amp_sum || !d_zcr) return fail(DSP_EINVAL, "dsp_vad_features_batch: NULL output");
-    if (frame_len <= 0 || frame_step <= 0) return fail(DSP_EINVAL, "frame_len/frame_step must be > 0");
+    if (!d_amp_sum || !d_zcr) return dsp_fail(DSP_EINVAL, "dsp_vad_features_batch: NULL output");
+    if (frame_len <= 0 || frame_step <= 0) return dsp_fail(DSP_EINVAL, "frame_len/frame_step must be > 0");
     int rc = check_geom(d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples);
     if (rc != DSP_OK) return rc;
     BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, frame_len, frame_step);
@@ -454,7 +420,7 @@ int vad_features_impl(const dsp_layout* layout, const void* d_wave, int wave_dty
                                      have_pre ? &pre : nullptr);
         if (view && dsp_workspace_pool().release(view, st) != 0 && ok && rc == DSP_OK) rc = DSP_EHIP;
         if (ok) {
-            if (rc != DSP_OK) return fail(rc, "vad tile kernel launch failed");
+            if (rc != DSP_OK) return dsp_fail(rc, "vad tile kernel launch failed");
             return DSP_OK;
         }
     }
@@ -486,12 +452,12 @@ SegWork seg_work_layout(int32_t n_utt, int64_t n_frames_bound, int32_t C) {
 int model_finalize_impl(const float* d_mfcc, int64_t ld_in, const int64_t* d_frame_offsets, int32_t n_utt, int32_t C,
                         int32_t N, int32_t max_len, float* d_out, int32_t* d_len0, const int64_t* d_segments,
                         const double* d_stats, void* stream) {
-    if (N < 1) return fail(DSP_EINVAL, "N must be an integer >= 1");  // base.py:71-72
-    if (C <= 0 || C > 32 || max_len <= 0) return fail(DSP_EINVAL, "need 0 < C <= 32 and max_len > 0");
+    if (N < 1) return dsp_fail(DSP_EINVAL, "N must be an integer >= 1");  // base.py:71-72
+    if (C <= 0 || C > 32 || max_len <= 0) return dsp_fail(DSP_EINVAL, "need 0 < C <= 32 and max_len > 0");
     if (ld_in == 0) ld_in = C;
-    if (ld_in < C) return fail(DSP_EINVAL, "ld_in %lld < C %d", (long long)ld_in, C);
+    if (ld_in < C) return dsp_fail(DSP_EINVAL, "ld_in %lld < C %d", (long long)ld_in, C);
     const size_t lds = ((size_t)(max_len + 2 * N) + (size_t)(max_len + N)) * C * sizeof(float);
-    if (lds > 64 * 1024) return fail(DSP_EINVAL, "max_len * C too large for the LDS tile (%zu bytes)", lds);
+    if (lds > 64 * 1024) return dsp_fail(DSP_EINVAL, "max_len * C too large for the LDS tile (%zu bytes)", lds);
     model_finalize_kernel<<<n_utt, 256, lds, (hipStream_t)stream>>>(d_mfcc, ld_in, d_frame_offsets, n_utt, C, N, max_len,
                                                                    d_out, d_len0, d_segments, d_stats);
     HIP_TRY(hipGetLastError());
@@ -502,9 +468,9 @@ int model_finalize_impl(const float* d_mfcc, int64_t ld_in, const int64_t* d_fra
 int endpoint_rule_impl(const double* d_amp_sum, const int32_t* d_zcr, const uint8_t* d_voiced, const int64_t* d_frame_offsets,
                        int32_t n_utt, int32_t frame_len, double cfg_frame, double cfg_step, int32_t* d_endpoints,
                        void* stream) {
-    if (!(cfg_frame > 0.0) || !(cfg_step > 0.0)) return fail(DSP_EINVAL, "cfg.frame / cfg.step must be > 0");
+    if (!(cfg_frame > 0.0) || !(cfg_step > 0.0)) return dsp_fail(DSP_EINVAL, "cfg.frame / cfg.step must be > 0");
     if (2 * (int)(0.100 / cfg_step) > DSP_MAX_SIL)
-        return fail(DSP_EINVAL, "cfg.step %g gives a silence window > %d frames", cfg_step, DSP_MAX_SIL);
+        return dsp_fail(DSP_EINVAL, "cfg.step %g gives a silence window > %d frames", cfg_step, DSP_MAX_SIL);
     endpoint_rule_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(
         d_amp_sum, d_zcr, d_frame_offsets, n_utt, frame_len, cfg_frame, cfg_step, d_endpoints, d_voiced);
     HIP_TRY(hipGetLastError());
@@ -598,10 +564,10 @@ int dsp_plan_has_fast_path(const dsp_plan* plan) { return plan && (plan->d_fast 
 const char* dsp_last_error(void) { return g_err.c_str(); }
 
 int dsp_device_count(int* n) {
-    if (!n) return fail(DSP_EINVAL, "n is NULL");
+    if (!n) return dsp_fail(DSP_EINVAL, "n is NULL");
     int c = 0;
     hipError_t e = hipGetDeviceCount(&c);
-    if (e != hipSuccess) { *n = 0; return fail(DSP_ENODEV, "hipGetDeviceCount: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { *n = 0; return dsp_fail(DSP_ENODEV, "hipGetDeviceCount: %s", hipGetErrorString(e)); }
     *n = c;
     return DSP_OK;
 }
@@ -612,13 +578,13 @@ int dsp_set_device(int device) {
 }
 
 int dsp_get_device(int* device) {
-    if (!device) return fail(DSP_EINVAL, "dsp_get_device: NULL argument");
+    if (!device) return dsp_fail(DSP_EINVAL, "dsp_get_device: NULL argument");
     HIP_TRY(hipGetDevice(device));
     return DSP_OK;
 }
 
 int dsp_malloc(void** d_ptr, size_t bytes) {
-    if (!d_ptr) return fail(DSP_EINVAL, "d_ptr is NULL");
+    if (!d_ptr) return dsp_fail(DSP_EINVAL, "d_ptr is NULL");
     HIP_TRY(hipMalloc(d_ptr, bytes ? bytes : 1));
     return DSP_OK;
 }
@@ -651,7 +617,7 @@ int dsp_stream_synchronize(void* stream) {
 
 int dsp_frame_count(int64_t n_samples, int32_t frame_len, int32_t frame_step, int64_t* n_frames) {
     if (!n_frames || frame_len <= 0 || frame_step <= 0 || n_samples < 0)
-        return fail(DSP_EINVAL, "dsp_frame_count: bad arguments");
+        return dsp_fail(DSP_EINVAL, "dsp_frame_count: bad arguments");
     if (n_samples <= frame_len) *n_frames = 1;
     else *n_frames = 1 + (n_samples - frame_len + frame_step - 1) / frame_step;
     return DSP_OK;
@@ -660,12 +626,12 @@ int dsp_frame_count(int64_t n_samples, int32_t frame_len, int32_t frame_step, in
 int dsp_frame_offsets(const int64_t* h_sample_offsets, int32_t n_utt, int32_t frame_len,
                       int32_t frame_step, int64_t* h_frame_offsets) {
     if (!h_sample_offsets || !h_frame_offsets || n_utt < 0)
-        return fail(DSP_EINVAL, "dsp_frame_offsets: bad arguments");
+        return dsp_fail(DSP_EINVAL, "dsp_frame_offsets: bad arguments");
     h_frame_offsets[0] = 0;
     for (int32_t b = 0; b < n_utt; ++b) {
         int64_t T;
         const int64_t n = h_sample_offsets[b + 1] - h_sample_offsets[b];
-        if (n < 0) return fail(DSP_EINVAL, "sample_offsets not monotone at %d", b);
+        if (n < 0) return dsp_fail(DSP_EINVAL, "sample_offsets not monotone at %d", b);
         int rc = dsp_frame_count(n, frame_len, frame_step, &T);
         if (rc != DSP_OK) return rc;
         h_frame_offsets[b + 1] = h_frame_offsets[b] + T;
@@ -674,26 +640,26 @@ int dsp_frame_offsets(const int64_t* h_sample_offsets, int32_t n_utt, int32_t fr
 }
 
 int dsp_plan_create(const dsp_plan_desc* d, dsp_plan** out) {
-    if (!d || !out) return fail(DSP_EINVAL, "NULL desc/out");
+    if (!d || !out) return dsp_fail(DSP_EINVAL, "NULL desc/out");
     *out = nullptr;
-    if (d->frame_len <= 0 || d->frame_step <= 0) return fail(DSP_EINVAL, "frame_len/frame_step must be > 0");
+    if (d->frame_len <= 0 || d->frame_step <= 0) return dsp_fail(DSP_EINVAL, "frame_len/frame_step must be > 0");
     std::vector<int> radix;
     if (d->nfft < 16 || d->nfft > 4096 || (d->nfft & 1) || !factor_half_fft(d->nfft / 2, radix))
-        return fail(DSP_EINVAL, "unsupported nfft %d (need 2^k or 3*2^k in [16, 4096])", d->nfft);
-    if (!d->h_window) return fail(DSP_EINVAL, "h_window is NULL");
+        return dsp_fail(DSP_EINVAL, "unsupported nfft %d (need 2^k or 3*2^k in [16, 4096])", d->nfft);
+    if (!d->h_window) return dsp_fail(DSP_EINVAL, "h_window is NULL");
     if (d->nfilt < 0 || d->numcep < 0 || d->numcep > d->nfilt)
-        return fail(DSP_EINVAL, "need 0 <= numcep <= nfilt (got %d, %d)", d->numcep, d->nfilt);
-    if (d->nfilt > d->nfft) return fail(DSP_EINVAL, "nfilt %d > nfft %d", d->nfilt, d->nfft);
+        return dsp_fail(DSP_EINVAL, "need 0 <= numcep <= nfilt (got %d, %d)", d->numcep, d->nfilt);
+    if (d->nfilt > d->nfft) return dsp_fail(DSP_EINVAL, "nfilt %d > nfft %d", d->nfilt, d->nfft);
     const int K = d->nfft / 2 + 1;
     std::vector<int32_t> off(d->nfilt > 0 ? d->nfilt : 1, 0);
     int64_t nnz = 0;
     if (d->nfilt > 0) {
         if (!d->h_mel_start || !d->h_mel_count || !d->h_mel_weights)
-            return fail(DSP_EINVAL, "mel tables missing");
-        if (d->numcep > 0 && !d->h_dct) return fail(DSP_EINVAL, "h_dct is NULL");
+            return dsp_fail(DSP_EINVAL, "mel tables missing");
+        if (d->numcep > 0 && !d->h_dct) return dsp_fail(DSP_EINVAL, "h_dct is NULL");
         for (int j = 0; j < d->nfilt; ++j) {
             if (d->h_mel_count[j] < 0 || d->h_mel_start[j] < 0 || d->h_mel_start[j] + d->h_mel_count[j] > K)
-                return fail(DSP_EINVAL, "mel filter %d spans bins outside [0,%d)", j, K);
+                return dsp_fail(DSP_EINVAL, "mel filter %d spans bins outside [0,%d)", j, K);
             off[j] = (int32_t)nnz;
             nnz += d->h_mel_count[j];
         }
@@ -747,8 +713,8 @@ int dsp_plan_destroy(dsp_plan* p) {
 int dsp_preemphasis_batch(const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets,
                           int32_t n_utt, int64_t n_samples_total, float coeff, float* d_out, void* stream) {
     if (!d_wave || !d_out || !d_sample_offsets || n_utt <= 0 || n_samples_total <= 0)
-        return fail(DSP_EINVAL, "dsp_preemphasis_batch: bad arguments");
-    if (wave_dtype != DSP_WAVE_I16 && wave_dtype != DSP_WAVE_F32) return fail(DSP_EINVAL, "unsupported wave_dtype %d", wave_dtype);
+        return dsp_fail(DSP_EINVAL, "dsp_preemphasis_batch: bad arguments");
+    if (wave_dtype != DSP_WAVE_I16 && wave_dtype != DSP_WAVE_F32) return dsp_fail(DSP_EINVAL, "unsupported wave_dtype %d", wave_dtype);
     const int grid = grid_for(n_samples_total, 256);
     dsp_dispatch_wave(wave_dtype, [&](auto dt) {
         preemphasis_kernel<decltype(dt)::value><<<grid, 256, 0, (hipStream_t)stream>>>(d_wave, d_sample_offsets, n_utt, n_samples_total, coeff, d_out);
@@ -768,10 +734,10 @@ int dsp_features_batch(const dsp_plan* plan, const void* d_wave, int wave_dtype,
 int dsp_delta_batch(const float* d_in, int64_t ld_in, const int64_t* d_frame_offsets, int32_t n_utt,
                     int64_t n_frames_total, int64_t uniform_frames, int32_t D, int32_t N, float* d_out,
                     int64_t ld_out, float* d_out_dd, int64_t ld_out_dd, void* stream) {
-    if (!d_in || !d_out) return fail(DSP_EINVAL, "dsp_delta_batch: NULL buffer");
-    if (N < 1) return fail(DSP_EINVAL, "N must be an integer >= 1");  // base.py:71-72
-    if (D <= 0 || n_utt <= 0 || n_frames_total <= 0) return fail(DSP_EINVAL, "dsp_delta_batch: empty input");
-    if (uniform_frames <= 0 && !d_frame_offsets) return fail(DSP_EINVAL, "ragged batch needs d_frame_offsets");
+    if (!d_in || !d_out) return dsp_fail(DSP_EINVAL, "dsp_delta_batch: NULL buffer");
+    if (N < 1) return dsp_fail(DSP_EINVAL, "N must be an integer >= 1");  // base.py:71-72
+    if (D <= 0 || n_utt <= 0 || n_frames_total <= 0) return dsp_fail(DSP_EINVAL, "dsp_delta_batch: empty input");
+    if (uniform_frames <= 0 && !d_frame_offsets) return dsp_fail(DSP_EINVAL, "ragged batch needs d_frame_offsets");
     if (ld_in == 0) ld_in = D;
     if (ld_out == 0) ld_out = D;
     if (ld_out_dd == 0) ld_out_dd = D;
@@ -782,18 +748,18 @@ int dsp_delta_batch(const float* d_in, int64_t ld_in, const int64_t* d_frame_off
     const int64_t blocks = delta_tile_blocks(uniform_frames, n_frames_total, n_utt, &tiles);
     // tiled LDS kernel where a tile fits (the tile table of a uniform batch is arithmetic); per-element kernel otherwise
     if (uniform_frames > 0 && delta_tile_lds(N, D) <= 64 * 1024) {
-        if (blocks > 0x7fffffff) return fail(DSP_EINVAL, "too many delta tiles");
-        if (!strides_ok) return fail(DSP_EINVAL, "row stride too large");
+        if (blocks > 0x7fffffff) return dsp_fail(DSP_EINVAL, "too many delta tiles");
+        if (!strides_ok) return dsp_fail(DSP_EINVAL, "row stride too large");
         launch_delta_tiled(blocks, st, d_in, ld_in, bg, D, N, d_out, ld_out, d_out_dd, ld_out_dd, tiles, nullptr);
     } else if (uniform_frames <= 0 && delta_tile_lds(N, D) <= 64 * 1024 && strides_ok) {
         // ragged: per-utterance tile prefix in a pooled, event-guarded workspace, grid sized by a bound
-        if (blocks > 0x7fffffff) return fail(DSP_EINVAL, "too many delta tiles");
+        if (blocks > 0x7fffffff) return dsp_fail(DSP_EINVAL, "too many delta tiles");
         DspWorkspace* w = dsp_workspace_pool().acquire(((size_t)n_utt + 1) * sizeof(int64_t), st);
-        if (!w) return fail(DSP_EHIP, "workspace allocation failed");
+        if (!w) return dsp_fail(DSP_EHIP, "workspace allocation failed");
         int64_t* tile_off = static_cast<int64_t*>(w->ptr);
         prefix_ceil_kernel<<<1, 1024, 0, st>>>(d_frame_offsets, n_utt, DT_SHIFT, tile_off);
         launch_delta_tiled(blocks, st, d_in, ld_in, bg, D, N, d_out, ld_out, d_out_dd, ld_out_dd, 0, tile_off);
-        if (dsp_workspace_pool().release(w, st) != 0) return fail(DSP_EHIP, "workspace release failed");
+        if (dsp_workspace_pool().release(w, st) != 0) return dsp_fail(DSP_EHIP, "workspace release failed");
     } else {
         delta_kernel<<<grid_for(n_frames_total * D, 256), 256, 0, st>>>(
             d_in, ld_in, bg, D, N, dsp_delta_inv_den(N), d_out, ld_out, d_out_dd, ld_out_dd);
@@ -806,14 +772,14 @@ int dsp_mfcc_delta_batch(const dsp_plan* plan, const void* d_wave, int wave_dtyp
                          const int64_t* d_sample_offsets, const int64_t* d_frame_offsets, int32_t n_utt,
                          int64_t n_frames_total, int64_t uniform_samples, int32_t delta_n, float* d_out,
                          void* stream) {
-    if (!plan) return fail(DSP_EINVAL, "plan is NULL");
-    if (delta_n < 1) return fail(DSP_EINVAL, "N must be an integer >= 1");  // base.py:71-72
+    if (!plan) return dsp_fail(DSP_EINVAL, "plan is NULL");
+    if (delta_n < 1) return dsp_fail(DSP_EINVAL, "N must be an integer >= 1");  // base.py:71-72
 #ifdef DSP_WS_MALLOC_ASYNC
     dsp_ws_diag_stream() = (hipStream_t)stream;
 #endif
     const int C = plan->C;
-    if (C <= 0) return fail(DSP_EINVAL, "plan has no mel/DCT tables");
-    if (!d_out) return fail(DSP_EINVAL, "plan/d_out is NULL");
+    if (C <= 0) return dsp_fail(DSP_EINVAL, "plan has no mel/DCT tables");
+    if (!d_out) return dsp_fail(DSP_EINVAL, "plan/d_out is NULL");
     {   // validate before the first launch or workspace acquire (the table kernels read the offset arrays)
         const int grc = check_geom(d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples);
         if (grc != DSP_OK) return grc;
@@ -834,7 +800,7 @@ int dsp_mfcc_delta_batch(const dsp_plan* plan, const void* d_wave, int wave_dtyp
 }
 
 int dsp_scale_columns(float* d_x, int64_t rows, int32_t cols, const float* d_scale, void* stream) {
-    if (!d_x || !d_scale || rows <= 0 || cols <= 0) return fail(DSP_EINVAL, "dsp_scale_columns: bad arguments");
+    if (!d_x || !d_scale || rows <= 0 || cols <= 0) return dsp_fail(DSP_EINVAL, "dsp_scale_columns: bad arguments");
     scale_columns_kernel<<<grid_for(rows * cols, 256), 256, 0, (hipStream_t)stream>>>(d_x, rows, cols, d_scale);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
@@ -842,25 +808,25 @@ int dsp_scale_columns(float* d_x, int64_t rows, int32_t cols, const float* d_sca
 
 int dsp_layout_create(const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_frames_total, int32_t frame_len,
                       int32_t frame_step, void* stream, dsp_layout** out) {
-    if (!out) return fail(DSP_EINVAL, "dsp_layout_create: out is NULL");
+    if (!out) return dsp_fail(DSP_EINVAL, "dsp_layout_create: out is NULL");
     *out = nullptr;
     if (!d_frame_offsets || n_utt <= 0 || n_frames_total <= 0 || frame_len <= 0 || frame_step <= 0)
-        return fail(DSP_EINVAL, "dsp_layout_create: bad arguments");
+        return dsp_fail(DSP_EINVAL, "dsp_layout_create: bad arguments");
     const int tile = vad_tile_frames(frame_len, frame_step);
     dsp_layout* l = new dsp_layout();
     memset(l, 0, sizeof(*l));
     l->n_utt = n_utt; l->frame_len = frame_len; l->frame_step = frame_step; l->n_frames_total = n_frames_total;
-    if (hipGetDevice(&l->device) != hipSuccess) { delete l; return fail(DSP_EHIP, "dsp_layout_create: hipGetDevice failed"); }
+    if (hipGetDevice(&l->device) != hipSuccess) { delete l; return dsp_fail(DSP_EHIP, "dsp_layout_create: hipGetDevice failed"); }
     if (tile != 0) {
         l->shift = tile == 16 ? 4 : 2;
         const int64_t bound = n_frames_total / tile + n_utt;
-        if (bound > 0x3fffffff) { delete l; return fail(DSP_EINVAL, "dsp_layout_create: batch too large"); }
+        if (bound > 0x3fffffff) { delete l; return dsp_fail(DSP_EINVAL, "dsp_layout_create: batch too large"); }
         const bool second = vad_scan_frames8(frame_len, frame_step, DSP_WAVE_I16, 0);      // int16 callers take 8-frame groups
         const int64_t bound2 = second ? n_frames_total / 8 + n_utt : 0;
         const size_t n1 = (size_t)n_utt + 1 + (size_t)bound, n2 = second ? (size_t)n_utt + 1 + (size_t)bound2 : 0;
         if (hipMalloc(reinterpret_cast<void**>(&l->group_off), (n1 + n2) * sizeof(int32_t)) != hipSuccess) {
             delete l;
-            return fail(DSP_EHIP, "dsp_layout_create: allocation failed");
+            return dsp_fail(DSP_EHIP, "dsp_layout_create: allocation failed");
         }
         l->group_utt = l->group_off + n_utt + 1;
         f512_build_group_tables(d_frame_offsets, n_utt, l->shift, l->group_off, l->group_utt, (hipStream_t)stream);
@@ -869,7 +835,7 @@ int dsp_layout_create(const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_f
             l->group_utt2 = l->group_off2 + n_utt + 1;
             f512_build_group_tables(d_frame_offsets, n_utt, 3, l->group_off2, l->group_utt2, (hipStream_t)stream);
         }
-        if (hipGetLastError() != hipSuccess) { (void)hipFree(l->group_off); delete l; return fail(DSP_EHIP, "dsp_layout_create: launch failed"); }
+        if (hipGetLastError() != hipSuccess) { (void)hipFree(l->group_off); delete l; return dsp_fail(DSP_EHIP, "dsp_layout_create: launch failed"); }
     }
     *out = l;
     return DSP_OK;
@@ -885,7 +851,7 @@ int dsp_layout_destroy(dsp_layout* layout) {
 int dsp_vad_features_layout_batch(const dsp_layout* layout, const void* d_wave, int wave_dtype,
                                   const int64_t* d_sample_offsets, const int64_t* d_frame_offsets, int32_t use_sq,
                                   double* d_amp_sum, int32_t* d_zcr, void* stream) {
-    if (!layout) return fail(DSP_EINVAL, "dsp_vad_features_layout_batch: layout is NULL");
+    if (!layout) return dsp_fail(DSP_EINVAL, "dsp_vad_features_layout_batch: layout is NULL");
     const int rc = check_owner_device(layout->device, false);
     if (rc != DSP_OK) return rc;
     return vad_features_impl(layout, d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, layout->n_utt,
@@ -905,8 +871,8 @@ int dsp_trim_scale_batch(const void* d_wave, int wave_dtype, const int64_t* d_sa
                          const int64_t* d_segments, const int64_t* d_dst_offsets, int32_t n_utt,
                          int32_t unit_variance, float* d_out, void* stream) {
     if (!d_wave || !d_sample_offsets || !d_segments || !d_dst_offsets || !d_out || n_utt <= 0)
-        return fail(DSP_EINVAL, "dsp_trim_scale_batch: bad arguments");
-    if (wave_dtype != DSP_WAVE_I16 && wave_dtype != DSP_WAVE_F32) return fail(DSP_EINVAL, "unsupported wave_dtype %d", wave_dtype);
+        return dsp_fail(DSP_EINVAL, "dsp_trim_scale_batch: bad arguments");
+    if (wave_dtype != DSP_WAVE_I16 && wave_dtype != DSP_WAVE_F32) return dsp_fail(DSP_EINVAL, "unsupported wave_dtype %d", wave_dtype);
     dsp_dispatch_wave(wave_dtype, [&](auto dt) {
         trim_scale_kernel<decltype(dt)::value><<<n_utt, 256, 0, (hipStream_t)stream>>>(d_wave, d_sample_offsets, d_segments, d_dst_offsets, unit_variance, d_out);
     });
@@ -915,7 +881,7 @@ int dsp_trim_scale_batch(const void* d_wave, int wave_dtype, const int64_t* d_sa
 }
 
 int dsp_segments_workspace_bytes(const dsp_plan* plan, int32_t n_utt, int64_t n_frames_bound, size_t* bytes) {
-    if (!plan || !bytes || n_utt <= 0 || n_frames_bound <= 0) return fail(DSP_EINVAL, "dsp_segments_workspace_bytes: bad arguments");
+    if (!plan || !bytes || n_utt <= 0 || n_frames_bound <= 0) return dsp_fail(DSP_EINVAL, "dsp_segments_workspace_bytes: bad arguments");
     *bytes = seg_work_layout(n_utt, n_frames_bound, plan->C).total;
     return DSP_OK;
 }
@@ -926,8 +892,8 @@ int dsp_mfcc_delta_segments_batch(const dsp_plan* plan, const void* d_wave, int 
                                   int32_t delta_n, int32_t flags, void* d_work, size_t work_bytes,
                                   float* d_out, void* stream) {
     const int unit_variance = flags & DSP_SEG_UNIT_VARIANCE;
-    if (!plan || !d_out || !d_work || !d_segments) return fail(DSP_EINVAL, "dsp_mfcc_delta_segments_batch: NULL argument");
-    if (delta_n < 0) return fail(DSP_EINVAL, "N must be an integer >= 1 (or 0: cepstra only)");  // base.py:71-72
+    if (!plan || !d_out || !d_work || !d_segments) return dsp_fail(DSP_EINVAL, "dsp_mfcc_delta_segments_batch: NULL argument");
+    if (delta_n < 0) return dsp_fail(DSP_EINVAL, "N must be an integer >= 1 (or 0: cepstra only)");  // base.py:71-72
     int rc = check_geom(d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt, n_frames_bound, 0);
     if (rc != DSP_OK) return rc;
     rc = check_owner_device(plan->device, true);
@@ -943,7 +909,7 @@ int dsp_mfcc_delta_segments_batch(const dsp_plan* plan, const void* d_wave, int 
         (unit_variance && !plan->append_energy) || (n_frames_bound >> 2) + n_utt > 0x3fffffff)
         return 1;
     const SegWork w = seg_work_layout(n_utt, n_frames_bound, C);
-    if (work_bytes < w.total) return fail(DSP_EINVAL, "work buffer too small (%zu < %zu bytes)", work_bytes, w.total);
+    if (work_bytes < w.total) return dsp_fail(DSP_EINVAL, "work buffer too small (%zu < %zu bytes)", work_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
     char* wp = static_cast<char*>(d_work);
     double* stats = unit_variance ? reinterpret_cast<double*>(wp + w.stats) : nullptr;
@@ -961,11 +927,11 @@ int dsp_mfcc_delta_segments_batch(const dsp_plan* plan, const void* d_wave, int 
     bg.stats = stats;
     rc = k512 ? fast512_launch(plan, d_wave, wave_dtype, bg, cep, (int64_t)C, st, &pre)
               : fast1536_launch(plan, d_wave, wave_dtype, bg, cep, (int64_t)C, st, &pre);
-    if (rc != DSP_OK) return fail(rc < 0 ? rc : DSP_EHIP, "fused kernel launch failed");
+    if (rc != DSP_OK) return dsp_fail(rc < 0 ? rc : DSP_EHIP, "fused kernel launch failed");
     if (delta_n == 0) return DSP_OK;    // (unit variance: c0 still lacks -ln(var); dsp_model_finalize_segments_batch applies it)
     int64_t tiles;
     const int64_t blocks = delta_tile_blocks(0, n_frames_bound, n_utt, &tiles);
-    if (blocks > 0x7fffffff) return fail(DSP_EINVAL, "too many delta tiles");
+    if (blocks > 0x7fffffff) return dsp_fail(DSP_EINVAL, "too many delta tiles");
     // (the tile -> utterance table exists only when the layout kernel built the tables)
     const int32_t* tile_utt = (flags & DSP_SEG_TABLES_READY) ? reinterpret_cast<const int32_t*>(wp + w.tutt) : nullptr;
     launch_delta_rows(blocks, st, cep, frames_geom(d_frame_offsets, n_utt, n_frames_bound, 0), C, delta_n, d_out, tiles, tile_off,
@@ -979,9 +945,9 @@ int dsp_endpoint_layout_batch(const int32_t* d_endpoints, const int64_t* d_sampl
                               const int64_t* d_jitter, int64_t* d_segments, int64_t* d_dst_offsets,
                               int64_t* d_frame_offsets, void* stream) {
     if (!endpoint_layout_args_ok(d_endpoints, d_sample_offsets, d_segments, d_dst_offsets, d_frame_offsets, n_utt))
-        return fail(DSP_EINVAL, "dsp_endpoint_layout_batch: bad arguments");
+        return dsp_fail(DSP_EINVAL, "dsp_endpoint_layout_batch: bad arguments");
     if (!(cfg_step > 0.0) || !(rate > 0.0) || frame_len <= 0 || frame_step <= 0)
-        return fail(DSP_EINVAL, "dsp_endpoint_layout_batch: step, rate, frame_len, frame_step must be > 0");
+        return dsp_fail(DSP_EINVAL, "dsp_endpoint_layout_batch: step, rate, frame_len, frame_step must be > 0");
     endpoint_layout_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(d_endpoints, d_sample_offsets, n_utt, cfg_step, rate,
                                                                frame_len, frame_step, d_jitter, d_segments,
                                                                d_dst_offsets, d_frame_offsets);
@@ -994,13 +960,13 @@ int dsp_endpoint_layout_segments_batch(const int32_t* d_endpoints, const int64_t
                                        int64_t* d_dst_offsets, int64_t* d_frame_offsets, const dsp_plan* plan,
                                        int64_t n_frames_bound, void* d_work, size_t work_bytes, void* stream) {
     if (!endpoint_layout_args_ok(d_endpoints, d_sample_offsets, d_segments, d_dst_offsets, d_frame_offsets, n_utt) || !plan || !d_work)
-        return fail(DSP_EINVAL, "dsp_endpoint_layout_segments_batch: bad arguments");
+        return dsp_fail(DSP_EINVAL, "dsp_endpoint_layout_segments_batch: bad arguments");
     if (!(cfg_step > 0.0) || !(rate > 0.0) || n_frames_bound <= 0)
-        return fail(DSP_EINVAL, "dsp_endpoint_layout_segments_batch: step, rate, n_frames_bound must be > 0");
+        return dsp_fail(DSP_EINVAL, "dsp_endpoint_layout_segments_batch: step, rate, n_frames_bound must be > 0");
     if ((n_frames_bound >> 2) + n_utt > 0x3fffffff)   // the kernel's group and tile counters are int32 (as dsp_mfcc_delta_segments_batch checks)
-        return fail(DSP_EINVAL, "dsp_endpoint_layout_segments_batch: batch too large");
+        return dsp_fail(DSP_EINVAL, "dsp_endpoint_layout_segments_batch: batch too large");
     const SegWork w = seg_work_layout(n_utt, n_frames_bound, plan->C);
-    if (work_bytes < w.total) return fail(DSP_EINVAL, "work buffer too small (%zu < %zu bytes)", work_bytes, w.total);
+    if (work_bytes < w.total) return dsp_fail(DSP_EINVAL, "work buffer too small (%zu < %zu bytes)", work_bytes, w.total);
     char* wp = static_cast<char*>(d_work);
     endpoint_layout_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(
         d_endpoints, d_sample_offsets, n_utt, cfg_step, rate, plan->L, plan->S, d_jitter, d_segments, d_dst_offsets,
@@ -1015,7 +981,7 @@ int dsp_endpoint_layout_segments_batch(const int32_t* d_endpoints, const int64_t
 int dsp_model_finalize_batch(const float* d_mfcc, int64_t ld_in, const int64_t* d_frame_offsets, int32_t n_utt,
                              int32_t C, int32_t N, int32_t max_len, float* d_out, int32_t* d_len0, void* stream) {
     if (!d_mfcc || !d_frame_offsets || !d_out || !d_len0 || n_utt <= 0)
-        return fail(DSP_EINVAL, "dsp_model_finalize_batch: bad arguments");
+        return dsp_fail(DSP_EINVAL, "dsp_model_finalize_batch: bad arguments");
     return model_finalize_impl(d_mfcc, ld_in, d_frame_offsets, n_utt, C, N, max_len, d_out, d_len0, nullptr, nullptr, stream);
 }
 
@@ -1023,7 +989,7 @@ int dsp_model_finalize_segments_batch(const float* d_mfcc, int64_t ld_in, const 
                                       const int64_t* d_segments, const void* d_work, int32_t n_utt, int32_t C, int32_t N,
                                       int32_t max_len, float* d_out, int32_t* d_len0, void* stream) {
     if (!d_mfcc || !d_frame_offsets || !d_segments || !d_work || !d_out || !d_len0 || n_utt <= 0)
-        return fail(DSP_EINVAL, "dsp_model_finalize_segments_batch: bad arguments");
+        return dsp_fail(DSP_EINVAL, "dsp_model_finalize_segments_batch: bad arguments");
     // the statistics sit at the start of the work buffer of dsp_mfcc_delta_segments_batch (seg_work_layout)
     return model_finalize_impl(d_mfcc, ld_in, d_frame_offsets, n_utt, C, N, max_len, d_out, d_len0, d_segments,
                                static_cast<const double*>(d_work), stream);
@@ -1032,7 +998,7 @@ int dsp_model_finalize_segments_batch(const float* d_mfcc, int64_t ld_in, const 
 int dsp_model_timefeat_batch(const double* d_amp_sum, const int64_t* d_frame_offsets, int32_t n_utt,
                              int32_t frame_len, int32_t max_len, float* d_out, void* stream) {
     if (!d_amp_sum || !d_frame_offsets || !d_out || n_utt <= 0 || frame_len <= 0 || max_len <= 0)
-        return fail(DSP_EINVAL, "dsp_model_timefeat_batch: bad arguments");
+        return dsp_fail(DSP_EINVAL, "dsp_model_timefeat_batch: bad arguments");
     timefeat_finalize_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_amp_sum, d_frame_offsets, n_utt, frame_len, max_len, d_out);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
@@ -1042,13 +1008,13 @@ int dsp_pitch_scores_batch(const float* d_sig, const int64_t* d_sample_offsets, 
                            int32_t n_utt, int64_t n_frames_total, int64_t uniform_samples, int32_t frame_len,
                            int32_t frame_step, const float* d_taps, int32_t center_clip, int32_t lag_min,
                            int32_t lag_max, float* d_scores, void* stream) {
-    if (!d_taps || !d_scores) return fail(DSP_EINVAL, "dsp_pitch_scores_batch: NULL taps/output");
+    if (!d_taps || !d_scores) return dsp_fail(DSP_EINVAL, "dsp_pitch_scores_batch: NULL taps/output");
     if (frame_len <= 0 || frame_len > PITCH_MAX_L || frame_step <= 0)
-        return fail(DSP_EINVAL, "need 0 < frame_len <= %d and frame_step > 0", PITCH_MAX_L);
-    if (lag_min < 0 || lag_max <= lag_min) return fail(DSP_EINVAL, "need 0 <= lag_min < lag_max");
+        return dsp_fail(DSP_EINVAL, "need 0 < frame_len <= %d and frame_step > 0", PITCH_MAX_L);
+    if (lag_min < 0 || lag_max <= lag_min) return dsp_fail(DSP_EINVAL, "need 0 <= lag_min < lag_max");
     int rc = check_geom(d_sig, DSP_WAVE_F32, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples);
     if (rc != DSP_OK) return rc;
-    if (n_frames_total > 0x7fffffff) return fail(DSP_EINVAL, "too many frames for one launch");
+    if (n_frames_total > 0x7fffffff) return dsp_fail(DSP_EINVAL, "too many frames for one launch");
     BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, frame_len, frame_step);
     int P = 1;
     while (P < frame_len) P <<= 1;
@@ -1073,9 +1039,9 @@ int dsp_pitch_scores_batch(const float* d_sig, const int64_t* d_sample_offsets, 
 
 int dsp_pitch_track_batch(const float* d_scores, const int64_t* d_frame_offsets, int32_t n_utt, int32_t n_lags,
                           int32_t bias, int32_t degree, double* d_pitch, void* stream) {
-    if (!d_scores || !d_frame_offsets || !d_pitch || n_utt <= 0) return fail(DSP_EINVAL, "dsp_pitch_track_batch: bad arguments");
-    if (n_lags <= 0 || n_lags > 256) return fail(DSP_EINVAL, "need 0 < n_lags <= 256");
-    if (degree != 2) return fail(DSP_EINVAL, "smoothing degree %d is not served on the device (the reference only uses 2)", degree);
+    if (!d_scores || !d_frame_offsets || !d_pitch || n_utt <= 0) return dsp_fail(DSP_EINVAL, "dsp_pitch_track_batch: bad arguments");
+    if (n_lags <= 0 || n_lags > 256) return dsp_fail(DSP_EINVAL, "need 0 < n_lags <= 256");
+    if (degree != 2) return dsp_fail(DSP_EINVAL, "smoothing degree %d is not served on the device (the reference only uses 2)", degree);
     pitch_track_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_scores, d_frame_offsets, n_lags, bias, d_pitch);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
@@ -1085,7 +1051,7 @@ int dsp_endpoint_rule_batch(const double* d_amp_sum, const int32_t* d_zcr, const
                             int32_t n_utt, int32_t frame_len, double cfg_frame, double cfg_step,
                             int32_t* d_endpoints, void* stream) {
     if (!d_amp_sum || !d_zcr || !d_frame_offsets || !d_endpoints || n_utt <= 0 || frame_len <= 0)
-        return fail(DSP_EINVAL, "dsp_endpoint_rule_batch: bad arguments");
+        return dsp_fail(DSP_EINVAL, "dsp_endpoint_rule_batch: bad arguments");
     return endpoint_rule_impl(d_amp_sum, d_zcr, nullptr, d_frame_offsets, n_utt, frame_len, cfg_frame, cfg_step, d_endpoints, stream);
 }
 
@@ -1093,19 +1059,19 @@ int dsp_acr_gate_batch(const void* d_wave, int wave_dtype, const int64_t* d_samp
                        const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_frames_total, int64_t uniform_samples,
                        int32_t frame_len, int32_t frame_step, int32_t lag_lo, int32_t lag_hi, double thresh,
                        uint8_t* d_voiced, void* stream) {
-    if (!d_voiced) return fail(DSP_EINVAL, "dsp_acr_gate_batch: d_voiced is NULL");
-    if (frame_len <= 0 || frame_step <= 0) return fail(DSP_EINVAL, "frame_len / frame_step must be > 0");
+    if (!d_voiced) return dsp_fail(DSP_EINVAL, "dsp_acr_gate_batch: d_voiced is NULL");
+    if (frame_len <= 0 || frame_step <= 0) return dsp_fail(DSP_EINVAL, "frame_len / frame_step must be > 0");
     if (lag_lo < 1 || lag_hi <= lag_lo || lag_hi > frame_len)
-        return fail(DSP_EINVAL, "lags [%d, %d) must lie in [1, frame_len = %d]", lag_lo, lag_hi, frame_len);
+        return dsp_fail(DSP_EINVAL, "lags [%d, %d) must lie in [1, frame_len = %d]", lag_lo, lag_hi, frame_len);
     const size_t lds = (size_t)4 * frame_len * sizeof(double);
-    if (lds > 64 * 1024) return fail(DSP_EINVAL, "frame_len %d too long for the autocorrelation gate (<= 2048)", frame_len);
+    if (lds > 64 * 1024) return dsp_fail(DSP_EINVAL, "frame_len %d too long for the autocorrelation gate (<= 2048)", frame_len);
     int rc = check_geom(d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples);
     if (rc != DSP_OK) return rc;
     BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, frame_len, frame_step);
     if (uniform_samples > 0 && (rc = check_dense_frames(n_frames_total, n_utt, bg.uniform_frames)) != DSP_OK) return rc;
     if (n_frames_total <= 0) return DSP_OK;
     const int64_t blocks = (n_frames_total + 3) / 4;
-    if (blocks > 0x7fffffff) return fail(DSP_EINVAL, "too many frames");
+    if (blocks > 0x7fffffff) return dsp_fail(DSP_EINVAL, "too many frames");
     hipStream_t st = (hipStream_t)stream;
     dsp_dispatch_wave(wave_dtype, [&](auto dt) {
         acr_gate_kernel<decltype(dt)::value><<<(int)blocks, 256, lds, st>>>(d_wave, bg, frame_len, frame_step, lag_lo, lag_hi, thresh, d_voiced);
@@ -1118,7 +1084,7 @@ int dsp_endpoint_rule_acr_batch(const double* d_amp_sum, const int32_t* d_zcr, c
                                 const int64_t* d_frame_offsets, int32_t n_utt, int32_t frame_len, double cfg_frame,
                                 double cfg_step, int32_t* d_endpoints, void* stream) {
     if (!d_amp_sum || !d_zcr || !d_voiced || !d_frame_offsets || !d_endpoints || n_utt <= 0 || frame_len <= 0)
-        return fail(DSP_EINVAL, "dsp_endpoint_rule_acr_batch: bad arguments");
+        return dsp_fail(DSP_EINVAL, "dsp_endpoint_rule_acr_batch: bad arguments");
     return endpoint_rule_impl(d_amp_sum, d_zcr, d_voiced, d_frame_offsets, n_utt, frame_len, cfg_frame, cfg_step, d_endpoints, stream);
 }
 
@@ -1126,9 +1092,9 @@ int dsp_resample_layout_batch(const int64_t* d_src_offsets, int32_t n_utt, int64
                               int32_t frame_len, int32_t frame_step, int64_t* d_dst_offsets, int64_t* d_frame_offsets,
                               void* stream) {
     if (!d_src_offsets || !d_frame_offsets || n_utt <= 0 || frame_len <= 0 || frame_step <= 0)
-        return fail(DSP_EINVAL, "dsp_resample_layout_batch: bad arguments");
+        return dsp_fail(DSP_EINVAL, "dsp_resample_layout_batch: bad arguments");
     if (dst_rate < 0 || (dst_rate > 0 && (src_rate <= 0 || dst_rate >= src_rate || !d_dst_offsets)))
-        return fail(DSP_EINVAL, "dsp_resample_layout_batch: need 0 < dst_rate < src_rate and d_dst_offsets (a decimation), or dst_rate = 0");
+        return dsp_fail(DSP_EINVAL, "dsp_resample_layout_batch: need 0 < dst_rate < src_rate and d_dst_offsets (a decimation), or dst_rate = 0");
     resample_layout_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(d_src_offsets, n_utt, src_rate, dst_rate, frame_len, frame_step,
                                                                d_dst_offsets, d_frame_offsets);
     HIP_TRY(hipGetLastError());
@@ -1138,8 +1104,8 @@ int dsp_resample_layout_batch(const int64_t* d_src_offsets, int32_t n_utt, int64
 int dsp_decimate_batch(const float* d_in, const int64_t* d_src_offsets, const int64_t* d_dst_offsets, int32_t n_utt,
                        int64_t n_out_bound, int64_t src_rate, int64_t dst_rate, float* d_out, void* stream) {
     if (!d_in || !d_src_offsets || !d_dst_offsets || !d_out || n_utt <= 0)
-        return fail(DSP_EINVAL, "dsp_decimate_batch: bad arguments");
-    if (src_rate <= 0 || dst_rate <= 0 || dst_rate >= src_rate) return fail(DSP_EINVAL, "dsp_decimate_batch: need 0 < dst_rate < src_rate");
+        return dsp_fail(DSP_EINVAL, "dsp_decimate_batch: bad arguments");
+    if (src_rate <= 0 || dst_rate <= 0 || dst_rate >= src_rate) return dsp_fail(DSP_EINVAL, "dsp_decimate_batch: need 0 < dst_rate < src_rate");
     if (n_out_bound <= 0) return DSP_OK;
     decimate_gather_kernel<<<grid_for(n_out_bound, 256), 256, 0, (hipStream_t)stream>>>(d_in, d_src_offsets, d_dst_offsets, n_utt,
                                                                                          src_rate, dst_rate, d_out);
@@ -1150,7 +1116,7 @@ int dsp_decimate_batch(const float* d_in, const int64_t* d_src_offsets, const in
 int dsp_model_pitchfeat_batch(const double* d_pitch, const int64_t* d_frame_offsets, int32_t n_utt, int32_t max_len,
                               float* d_out, void* stream) {
     if (!d_pitch || !d_frame_offsets || !d_out || n_utt <= 0 || max_len <= 0)
-        return fail(DSP_EINVAL, "dsp_model_pitchfeat_batch: bad arguments");
+        return dsp_fail(DSP_EINVAL, "dsp_model_pitchfeat_batch: bad arguments");
     pitchfeat_finalize_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_pitch, d_frame_offsets, n_utt, max_len, d_out);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
@@ -1159,9 +1125,9 @@ int dsp_model_pitchfeat_batch(const double* d_pitch, const int64_t* d_frame_offs
 int dsp_pitch_rows_batch(double* d_rows, const int64_t* d_frame_offsets, int32_t n_utt, int32_t n_lags, int32_t bias,
                          int32_t degree, int32_t flags, double* d_pitch, void* stream) {
     if (!d_rows || !d_frame_offsets || n_utt <= 0 || n_lags <= 0 || degree < 0)
-        return fail(DSP_EINVAL, "dsp_pitch_rows_batch: bad arguments");
-    if ((flags & 4) && !(flags & 2)) return fail(DSP_EINVAL, "dsp_pitch_rows_batch: the repair sweeps (4) need the arg-max (2)");
-    if ((flags & 2) && !d_pitch) return fail(DSP_EINVAL, "dsp_pitch_rows_batch: d_pitch is NULL");
+        return dsp_fail(DSP_EINVAL, "dsp_pitch_rows_batch: bad arguments");
+    if ((flags & 4) && !(flags & 2)) return dsp_fail(DSP_EINVAL, "dsp_pitch_rows_batch: the repair sweeps (4) need the arg-max (2)");
+    if ((flags & 2) && !d_pitch) return dsp_fail(DSP_EINVAL, "dsp_pitch_rows_batch: d_pitch is NULL");
     pitch_rows_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_rows, d_frame_offsets, n_lags, bias, degree, flags, d_pitch);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
@@ -1171,13 +1137,13 @@ int dsp_pitch_cepstrum_batch(const float* d_sig, const int64_t* d_sample_offsets
                              int32_t n_utt, int64_t n_frames_total, int64_t uniform_samples, int32_t frame_len,
                              int32_t frame_step, const float* d_taps, int32_t center_clip, float* d_rows, double* d_amp,
                              void* stream) {
-    if (!d_taps || !d_rows) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_batch: NULL taps/output");
+    if (!d_taps || !d_rows) return dsp_fail(DSP_EINVAL, "dsp_pitch_cepstrum_batch: NULL taps/output");
     if (!cepstrum_frame_len_ok(frame_len))
-        return fail(DSP_EINVAL, "dsp_pitch_cepstrum_batch: frame_len %d is not a power of two in [128, 1024]", frame_len);
-    if (frame_step <= 0) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_batch: frame_step must be > 0");
+        return dsp_fail(DSP_EINVAL, "dsp_pitch_cepstrum_batch: frame_len %d is not a power of two in [128, 1024]", frame_len);
+    if (frame_step <= 0) return dsp_fail(DSP_EINVAL, "dsp_pitch_cepstrum_batch: frame_step must be > 0");
     int rc = check_geom(d_sig, DSP_WAVE_F32, d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples);
     if (rc != DSP_OK) return rc;
-    if (n_frames_total > 0x7fffffff) return fail(DSP_EINVAL, "too many frames for one launch");
+    if (n_frames_total > 0x7fffffff) return dsp_fail(DSP_EINVAL, "too many frames for one launch");
     BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, frame_len, frame_step);
     if (uniform_samples > 0 && (rc = check_dense_frames(n_frames_total, n_utt, bg.uniform_frames)) != DSP_OK) return rc;
     const float2* tp = reinterpret_cast<const float2*>(d_taps);
@@ -1192,12 +1158,12 @@ int dsp_pitch_cepstrum_batch(const float* d_sig, const int64_t* d_sample_offsets
 
 int dsp_pitch_cepstrum_track_batch(const void* d_rows, int32_t rows_f64, const int64_t* d_frame_offsets, int32_t n_utt,
                                    int32_t frame_len, int32_t flags, double* d_pitch, int32_t* d_scores, void* stream) {
-    if (!d_rows || !d_frame_offsets || n_utt <= 0) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: bad arguments");
+    if (!d_rows || !d_frame_offsets || n_utt <= 0) return dsp_fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: bad arguments");
     if (!cepstrum_frame_len_ok(frame_len))
-        return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: frame_len %d is not a power of two in [128, 1024]", frame_len);
-    if ((flags & ~3) != 0) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: unknown flags %d", flags);
-    if ((flags & 2) && !d_pitch) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: d_pitch is NULL");
-    if (!(flags & 2) && !d_scores) return fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: nothing to write (no arg-max, d_scores is NULL)");
+        return dsp_fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: frame_len %d is not a power of two in [128, 1024]", frame_len);
+    if ((flags & ~3) != 0) return dsp_fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: unknown flags %d", flags);
+    if ((flags & 2) && !d_pitch) return dsp_fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: d_pitch is NULL");
+    if (!(flags & 2) && !d_scores) return dsp_fail(DSP_EINVAL, "dsp_pitch_cepstrum_track_batch: nothing to write (no arg-max, d_scores is NULL)");
     dispatch_cepstrum_frame_len(frame_len, [&](auto len) {
         auto launch = [&](auto row) {   // row: a value of the rows' element type
             pitch_cepstrum_track_kernel<decltype(row), decltype(len)::value><<<n_utt, 64, 0, (hipStream_t)stream>>>(
@@ -1211,8 +1177,8 @@ int dsp_pitch_cepstrum_track_batch(const void* d_rows, int32_t rows_f64, const i
 
 int dsp_pitch_feature_batch(const double* d_pitch, const double* d_amp, const int64_t* d_frame_offsets, int32_t n_utt,
                             double* d_seg, double* d_feat, int32_t* d_aux, void* stream) {
-    if (!d_amp || !d_frame_offsets || !d_aux || n_utt <= 0) return fail(DSP_EINVAL, "dsp_pitch_feature_batch: bad arguments");
-    if (d_pitch && (!d_seg || !d_feat)) return fail(DSP_EINVAL, "dsp_pitch_feature_batch: d_pitch needs d_seg and d_feat");
+    if (!d_amp || !d_frame_offsets || !d_aux || n_utt <= 0) return dsp_fail(DSP_EINVAL, "dsp_pitch_feature_batch: bad arguments");
+    if (d_pitch && (!d_seg || !d_feat)) return dsp_fail(DSP_EINVAL, "dsp_pitch_feature_batch: d_pitch needs d_seg and d_feat");
     pitch_feature_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_pitch, d_amp, d_frame_offsets, d_seg, d_feat, d_aux);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
@@ -1221,403 +1187,9 @@ int dsp_pitch_feature_batch(const double* d_pitch, const double* d_amp, const in
 int dsp_pitch_smooth_subseq_batch(const double* d_values, const int64_t* d_offsets, int32_t n_utt, int32_t tor,
                                   double thres, double* d_seg, int32_t* d_info, void* stream) {
     if (!d_values || !d_offsets || !d_seg || !d_info || n_utt <= 0)
-        return fail(DSP_EINVAL, "dsp_pitch_smooth_subseq_batch: bad arguments");
-    if (tor < 1) return fail(DSP_EINVAL, "dsp_pitch_smooth_subseq_batch: tor must be >= 1 (got %d)", tor);
+        return dsp_fail(DSP_EINVAL, "dsp_pitch_smooth_subseq_batch: bad arguments");
+    if (tor < 1) return dsp_fail(DSP_EINVAL, "dsp_pitch_smooth_subseq_batch: tor must be >= 1 (got %d)", tor);
     pitch_subseq_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_values, d_offsets, tor, thres, d_seg, d_info);
-    HIP_TRY(hipGetLastError());
-    return DSP_OK;
-}
-
-int dsp_hmlstm_create(const dsp_hmlstm_desc* d, dsp_hmlstm** out) {
-    if (!d || !out) return fail(DSP_EINVAL, "dsp_hmlstm_create: NULL argument");
-    *out = nullptr;
-    if (!hm_size_ok(d->input_size) || !hm_size_ok(d->hidden1) || !hm_size_ok(d->hidden2))
-        return fail(DSP_EINVAL, "dsp_hmlstm_create: input_size %d, hidden1 %d, hidden2 %d must be multiples of 4 in [4, %d]",
-                    d->input_size, d->hidden1, d->hidden2, HM_MAX_SIZE);
-    if (!d->d_c1_U11 || !d->d_c1_U21 || !d->d_c1_W01 || !d->d_c1_bias || !d->d_c2_U11 || !d->d_c2_W01 || !d->d_c2_bias)
-        return fail(DSP_EINVAL, "dsp_hmlstm_create: NULL parameter tensor");
-    const int32_t I = d->input_size, H1 = d->hidden1, H2 = d->hidden2;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    // segments in packing order: (source, H of the cell, K)
-    struct Seg { const float* src; int32_t H, K; };
-    const Seg segs[5] = {{d->d_c1_W01, H1, I}, {d->d_c1_U21, H1, H2}, {d->d_c1_U11, H1, H1}, {d->d_c2_W01, H2, H1}, {d->d_c2_U11, H2, H2}};
-    size_t off[8], total = 0;
-    for (int i = 0; i < 5; ++i) { off[i] = total; total += (size_t)hm_kgroups(segs[i].K) * hm_tiles(segs[i].H) * 256; }
-    off[5] = total; total += (size_t)hm_tiles(H1) * 16;
-    off[6] = total; total += (size_t)hm_tiles(H2) * 16;
-    // the transposed copies of the backward recurrence: (source, H of the cell, columns = hidden index of the product)
-    const Seg tsegs[4] = {{d->d_c2_U11, H2, H2}, {d->d_c2_W01, H2, H1}, {d->d_c1_U21, H1, H2}, {d->d_c1_U11, H1, H1}};
-    size_t toff[4];
-    for (int i = 0; i < 4; ++i) { toff[i] = total; total += (size_t)hm_bwd_packed_floats(tsegs[i].H, tsegs[i].K); }
-    float* buf = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), total * sizeof(float)));
-    // the parameters may have been written on any stream of the caller: create is rare, so it simply waits for the device
-    hipError_t e = hipDeviceSynchronize();
-    for (int i = 0; i < 5 && e == hipSuccess; ++i) {
-        const int64_t n = (int64_t)hm_kgroups(segs[i].K) * hm_tiles(segs[i].H) * 256;
-        hm_pack_kernel<<<(int)((n + 255) / 256), 256, 0, 0>>>(segs[i].src, segs[i].H, segs[i].K, hm_kgroups(segs[i].K), buf + off[i]);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) { hm_pack_bias_kernel<<<(hm_tiles(H1) * 16 + 255) / 256, 256, 0, 0>>>(d->d_c1_bias, H1, buf + off[5]); e = hipGetLastError(); }
-    if (e == hipSuccess) { hm_pack_bias_kernel<<<(hm_tiles(H2) * 16 + 255) / 256, 256, 0, 0>>>(d->d_c2_bias, H2, buf + off[6]); e = hipGetLastError(); }
-    for (int i = 0; i < 4 && e == hipSuccess; ++i) {
-        const int64_t n = hm_bwd_packed_floats(tsegs[i].H, tsegs[i].K);
-        hm_pack_t_kernel<<<(int)((n + 255) / 256), 256, 0, 0>>>(tsegs[i].src, tsegs[i].H, tsegs[i].K, HM_WAVES * hm_bwd_chunks(tsegs[i].K), buf + toff[i]);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        (void)hipFree(buf);
-        return fail(DSP_EHIP, "dsp_hmlstm_create: %s", hipGetErrorString(e));
-    }
-    dsp_hmlstm* h = new dsp_hmlstm();
-    h->I = I; h->H1 = H1; h->H2 = H2; h->d_packed = buf; h->device = dev;
-    auto f4 = [&](int i) { return reinterpret_cast<const float4*>(buf + off[i]); };
-    h->c1 = HmCell{{f4(0), f4(1), f4(2)}, buf + off[5], {hm_kgroups(I), hm_kgroups(H2), hm_kgroups(H1)}, H1, hm_tiles(H1)};
-    h->c2 = HmCell{{f4(3), nullptr, f4(4)}, buf + off[6], {hm_kgroups(H1), 0, hm_kgroups(H2)}, H2, hm_tiles(H2)};
-    for (int i = 0; i < 4; ++i) h->wt[i] = reinterpret_cast<const float4*>(buf + toff[i]);
-    *out = h;
-    return DSP_OK;
-}
-
-int dsp_hmlstm_destroy(dsp_hmlstm* h) {
-    if (!h) return DSP_OK;
-    hipError_t e = hipFree(h->d_packed);
-    delete h;
-    if (e != hipSuccess) return fail(DSP_EHIP, "dsp_hmlstm_destroy: %s", hipGetErrorString(e));
-    return DSP_OK;
-}
-
-// The checks and the launch behind dsp_hmlstm_forward (d_tape == NULL) and dsp_hmlstm_forward_train.
-static int hmlstm_forward_launch(const char* who, const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a,
-                                 const int32_t* d_len, const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2,
-                                 uint8_t* d_z1, uint8_t* d_z2, float* d_zhat, float* d_last_h2, float* d_tape, void* stream) {
-    if (!h || !d_x) return fail(DSP_EINVAL, "%s: NULL handle / input", who);
-    if (T < 1 || B < 1) return fail(DSP_EINVAL, "%s: T %d and B %d must be >= 1", who, T, B);
-    if (!std::isfinite(a)) return fail(DSP_EINVAL, "%s: the slope a is not finite", who);
-    if ((reinterpret_cast<uintptr_t>(d_x) & 15) != 0) return fail(DSP_EINVAL, "%s: d_x must be 16-byte aligned", who);
-    if (!d_state_out && !d_h1 && !d_h2 && !d_z1 && !d_z2 && !d_zhat && !d_last_h2)
-        return fail(DSP_EINVAL, "%s: nothing to write (every output is NULL)", who);
-    HmParams P;
-    P.c1 = h->c1; P.c2 = h->c2;
-    P.I = h->I; P.T = T; P.B = B; P.a = a;
-    P.x = d_x; P.len = d_len; P.state_in = d_state_in; P.state_out = d_state_out;
-    P.h1 = d_h1; P.h2 = d_h2; P.z1 = d_z1; P.z2 = d_z2; P.zhat = d_zhat; P.last_h2 = d_last_h2; P.tape = d_tape;
-    const int grid = (B + HM_COLS - 1) / HM_COLS;
-    const int nt = h->c1.n_tiles > h->c2.n_tiles ? h->c1.n_tiles : h->c2.n_tiles;   // tiles per wave: ceil(nt / 8)
-    hipStream_t st = (hipStream_t)stream;
-    if (d_tape) {
-        if (nt <= 2 * HM_WAVES) hmlstm_forward_kernel<2, true><<<grid, HM_THREADS, 0, st>>>(P);
-        else if (nt <= 4 * HM_WAVES) hmlstm_forward_kernel<4, true><<<grid, HM_THREADS, 0, st>>>(P);
-        else if (nt <= 7 * HM_WAVES) hmlstm_forward_kernel<7, true><<<grid, HM_THREADS, 0, st>>>(P);
-        else hmlstm_forward_kernel<9, true><<<grid, HM_THREADS, 0, st>>>(P);
-    } else {
-        if (nt <= 2 * HM_WAVES) hmlstm_forward_kernel<2><<<grid, HM_THREADS, 0, st>>>(P);
-        else if (nt <= 4 * HM_WAVES) hmlstm_forward_kernel<4><<<grid, HM_THREADS, 0, st>>>(P);
-        else if (nt <= 7 * HM_WAVES) hmlstm_forward_kernel<7><<<grid, HM_THREADS, 0, st>>>(P);
-        else hmlstm_forward_kernel<9><<<grid, HM_THREADS, 0, st>>>(P);
-    }
-    HIP_TRY(hipGetLastError());
-    return DSP_OK;
-}
-
-int dsp_hmlstm_forward(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
-                       const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1, uint8_t* d_z2,
-                       float* d_zhat, float* d_last_h2, void* stream) {
-    return hmlstm_forward_launch("dsp_hmlstm_forward", h, d_x, T, B, a, d_len, d_state_in, d_state_out, d_h1, d_h2, d_z1, d_z2,
-                                 d_zhat, d_last_h2, nullptr, stream);
-}
-
-int dsp_hmlstm_tape_bytes(const dsp_hmlstm* h, int32_t T, int32_t B, int64_t* bytes) {
-    if (!h || !bytes) return fail(DSP_EINVAL, "dsp_hmlstm_tape_bytes: NULL argument");
-    if (T < 1 || B < 1) return fail(DSP_EINVAL, "dsp_hmlstm_tape_bytes: T %d and B %d must be >= 1", T, B);
-    *bytes = hm_tape_floats(h->H1, h->H2, T, B) * (int64_t)sizeof(float);
-    return DSP_OK;
-}
-
-// The tape argument of the two training entry points.  Without a handle (h == NULL: the caller reports that next) the size is
-// held against the smallest tape any handle asks for at (T, B).
-static int hmlstm_check_tape(const char* who, const dsp_hmlstm* h, int32_t T, int32_t B, const void* d_tape, int64_t tape_bytes) {
-    if (!d_tape) return fail(DSP_EINVAL, "%s: NULL tape", who);
-    if ((reinterpret_cast<uintptr_t>(d_tape) & 15) != 0) return fail(DSP_EINVAL, "%s: d_tape must be 16-byte aligned", who);
-    const int64_t need = hm_tape_floats(h ? h->H1 : 4, h ? h->H2 : 4, T, B) * (int64_t)sizeof(float);
-    if (tape_bytes < need)
-        return fail(DSP_EINVAL, "%s: the tape is short (%lld bytes, dsp_hmlstm_tape_bytes asks for %lld)", who, (long long)tape_bytes, (long long)need);
-    return DSP_OK;
-}
-
-int dsp_hmlstm_forward_train(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
-                             const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1, uint8_t* d_z2,
-                             float* d_zhat, float* d_last_h2, void* d_tape, int64_t tape_bytes, void* stream) {
-    const char* who = "dsp_hmlstm_forward_train";
-    if (T < 1 || B < 1) return fail(DSP_EINVAL, "%s: T %d and B %d must be >= 1", who, T, B);
-    if (int rc = hmlstm_check_tape(who, h, T, B, d_tape, tape_bytes)) return rc;
-    if (!d_h1 || !d_h2 || !d_z1 || !d_z2) return fail(DSP_EINVAL, "%s: h1, h2, z1 and z2 are mandatory (the backward pass reads them)", who);
-    if (!d_x) return fail(DSP_EINVAL, "%s: NULL input", who);
-    if (!h) return fail(DSP_EINVAL, "%s: NULL handle", who);
-    return hmlstm_forward_launch(who, h, d_x, T, B, a, d_len, d_state_in, d_state_out, d_h1, d_h2, d_z1, d_z2, d_zhat,
-                                 d_last_h2, static_cast<float*>(d_tape), stream);
-}
-
-int dsp_hmlstm_backward(const dsp_hmlstm* h, int32_t T, int32_t B, float a, const int32_t* d_len, const float* d_state_in,
-                        const void* d_tape, int64_t tape_bytes, const float* d_h1, const float* d_h2, const uint8_t* d_z1,
-                        const uint8_t* d_z2, const float* d_g_h1, const float* d_g_h2, const float* d_g_last, float* d_dfs1,
-                        float* d_dfs2, void* stream) {
-    const char* who = "dsp_hmlstm_backward";
-    if (T < 1 || B < 1) return fail(DSP_EINVAL, "%s: T %d and B %d must be >= 1", who, T, B);
-    if (!std::isfinite(a)) return fail(DSP_EINVAL, "%s: the slope a is not finite", who);
-    if (int rc = hmlstm_check_tape(who, h, T, B, d_tape, tape_bytes)) return rc;
-    if (!d_h1 || !d_h2 || !d_z1 || !d_z2) return fail(DSP_EINVAL, "%s: NULL forward output (h1, h2, z1, z2)", who);
-    if (!d_g_h1 && !d_g_h2 && !d_g_last) return fail(DSP_EINVAL, "%s: no gradient to propagate (g_h1, g_h2 and g_last are all NULL)", who);
-    if (!d_dfs1 || !d_dfs2) return fail(DSP_EINVAL, "%s: NULL output (dfs1, dfs2)", who);
-    if (!h) return fail(DSP_EINVAL, "%s: NULL handle", who);
-    HmBwdParams P;
-    for (int i = 0; i < 4; ++i) P.wt[i] = h->wt[i];
-    P.H1 = h->H1; P.H2 = h->H2; P.T = T; P.B = B; P.a = a;
-    P.len = d_len; P.state_in = d_state_in; P.tape = static_cast<const float*>(d_tape);
-    P.h1 = d_h1; P.h2 = d_h2; P.z1 = d_z1; P.z2 = d_z2;
-    P.g_h1 = d_g_h1; P.g_h2 = d_g_h2; P.g_last = d_g_last; P.dfs1 = d_dfs1; P.dfs2 = d_dfs2;
-    const int grid = (B + HM_COLS - 1) / HM_COLS;
-    const size_t lds = hm_bwd_lds_bytes(h->H1, h->H2);       // up to 67.5 KB: above the static limit
-    hipStream_t st = (hipStream_t)stream;
-    const int nc = hm_bwd_chunks(h->H1 > h->H2 ? h->H1 : h->H2);
-    if (nc <= 1) {
-        static size_t granted[DSP_MAX_DEVICES] = {};
-        if (dsp_ensure_dynamic_lds((const void*)hmlstm_backward_kernel<1>, lds, granted) != 0)
-            return fail(DSP_EHIP, "%s: %zu bytes of LDS were not granted", who, lds);
-        hmlstm_backward_kernel<1><<<grid, HM_THREADS, lds, st>>>(P);
-    } else {
-        static size_t granted[DSP_MAX_DEVICES] = {};
-        if (dsp_ensure_dynamic_lds((const void*)hmlstm_backward_kernel<2>, lds, granted) != 0)
-            return fail(DSP_EHIP, "%s: %zu bytes of LDS were not granted", who, lds);
-        hmlstm_backward_kernel<2><<<grid, HM_THREADS, lds, st>>>(P);
-    }
-    HIP_TRY(hipGetLastError());
-    return DSP_OK;
-}
-
-static int64_t bigru_buffer_floats(const dsp_bigru* h, int32_t T, int32_t B) { return (int64_t)T * B * 2 * h->H; }
-
-int dsp_bigru_create(const dsp_bigru_desc* d, dsp_bigru** out) {
-    if (!d || !out) return fail(DSP_EINVAL, "dsp_bigru_create: NULL argument");
-    *out = nullptr;
-    const int32_t I = d->input_size, H = d->hidden, L = d->n_layers;
-    if (I < 1 || I > GRU_MAX_IN) return fail(DSP_EINVAL, "dsp_bigru_create: input_size %d must be in [1, %d]", I, GRU_MAX_IN);
-    if (H < 4 || H > GRU_MAX_H || (H & 3) != 0)
-        return fail(DSP_EINVAL, "dsp_bigru_create: hidden %d must be a multiple of 4 in [4, %d]", H, GRU_MAX_H);
-    if (L < 1 || L > GRU_MAX_LAYERS) return fail(DSP_EINVAL, "dsp_bigru_create: n_layers %d must be in [1, %d]", L, GRU_MAX_LAYERS);
-    for (int i = 0; i < 8 * L; ++i)
-        if (!d->d_params[i]) return fail(DSP_EINVAL, "dsp_bigru_create: NULL parameter tensor (index %d)", i);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    const int32_t nt = H / 4;
-    size_t woff[GRU_MAX_LAYERS][2], boff[GRU_MAX_LAYERS][2], total = 0;
-    int32_t ngx[GRU_MAX_LAYERS], ng[GRU_MAX_LAYERS];
-    for (int l = 0; l < L; ++l) {
-        ngx[l] = hm_kgroups(l == 0 ? I : 2 * H);
-        ng[l] = ngx[l] + hm_kgroups(H);
-        for (int dr = 0; dr < 2; ++dr) { woff[l][dr] = total; total += (size_t)ng[l] * nt * 256; }
-    }
-    for (int l = 0; l < L; ++l)
-        for (int dr = 0; dr < 2; ++dr) { boff[l][dr] = total; total += (size_t)4 * H; }
-    // the transposed copies of the backward recurrence
-    size_t toff[GRU_MAX_LAYERS][2];
-    for (int l = 0; l < L; ++l)
-        for (int dr = 0; dr < 2; ++dr) { toff[l][dr] = total; total += (size_t)gru_bwd_packed_floats(H); }
-    float* buf = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), total * sizeof(float)));
-    // the parameters may have been written on any stream of the caller: create is rare, so it simply waits for the device
-    hipError_t e = hipDeviceSynchronize();
-    for (int l = 0; l < L && e == hipSuccess; ++l) {
-        for (int dr = 0; dr < 2 && e == hipSuccess; ++dr) {
-            const float* const* p = d->d_params + 8 * l + 4 * dr;      // weight_ih, weight_hh, bias_ih, bias_hh
-            const int64_t n = (int64_t)ng[l] * nt * 256;
-            gru_pack_kernel<<<(int)((n + 255) / 256), 256, 0, 0>>>(p[0], p[1], H, l == 0 ? I : 2 * H, ngx[l], ng[l], buf + woff[l][dr]);
-            gru_pack_bias_kernel<<<(4 * H + 255) / 256, 256, 0, 0>>>(p[2], p[3], H, buf + boff[l][dr]);
-            const int64_t nb = gru_bwd_packed_floats(H);
-            gru_pack_t_kernel<<<(int)((nb + 255) / 256), 256, 0, 0>>>(p[1], H, HM_WAVES * hm_bwd_chunks(H), buf + toff[l][dr]);
-            e = hipGetLastError();
-        }
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        (void)hipFree(buf);
-        return fail(DSP_EHIP, "dsp_bigru_create: %s", hipGetErrorString(e));
-    }
-    dsp_bigru* h = new dsp_bigru();
-    h->I = I; h->H = H; h->L = L; h->d_packed = buf; h->device = dev;
-    for (int l = 0; l < L; ++l) {
-        h->ngx[l] = ngx[l]; h->ng[l] = ng[l];
-        for (int dr = 0; dr < 2; ++dr) {
-            h->dir[l][dr] = GruDir{reinterpret_cast<const float4*>(buf + woff[l][dr]), buf + boff[l][dr]};
-            h->wt[l][dr] = reinterpret_cast<const float4*>(buf + toff[l][dr]);
-        }
-    }
-    *out = h;
-    return DSP_OK;
-}
-
-int dsp_bigru_destroy(dsp_bigru* h) {
-    if (!h) return DSP_OK;
-    hipError_t e = hipFree(h->d_packed);
-    delete h;
-    if (e != hipSuccess) return fail(DSP_EHIP, "dsp_bigru_destroy: %s", hipGetErrorString(e));
-    return DSP_OK;
-}
-
-int dsp_bigru_workspace_bytes(const dsp_bigru* h, int32_t T, int32_t B, int64_t* bytes) {
-    if (!h || !bytes) return fail(DSP_EINVAL, "dsp_bigru_workspace_bytes: NULL argument");
-    if (T < 1 || B < 1) return fail(DSP_EINVAL, "dsp_bigru_workspace_bytes: T %d and B %d must be >= 1", T, B);
-    *bytes = (h->L > 1 ? 2 : 1) * bigru_buffer_floats(h, T, B) * (int64_t)sizeof(float);
-    return DSP_OK;
-}
-
-// One layer of the forward pass: the plain instantiations, or (tape != NULL) those that also save the gates.
-static void bigru_launch_layer(const dsp_bigru* h, int l, GruParams& P, float* tape, const float* drop, dim3 grid, hipStream_t st) {
-    P.d[0] = h->dir[l][0]; P.d[1] = h->dir[l][1];
-    P.I = l == 0 ? h->I : 2 * h->H; P.H = h->H; P.ngx = h->ngx[l]; P.ng = h->ng[l];
-    P.tape = tape; P.drop = drop;
-    const int nt = h->H / 4;                                                    // tiles per wave: ceil(nt / 8)
-    if (tape) {
-        if (nt <= 2 * HM_WAVES) bigru_layer_kernel<2, true><<<grid, HM_THREADS, 0, st>>>(P);
-        else if (nt <= 4 * HM_WAVES) bigru_layer_kernel<4, true><<<grid, HM_THREADS, 0, st>>>(P);
-        else if (nt <= 7 * HM_WAVES) bigru_layer_kernel<7, true><<<grid, HM_THREADS, 0, st>>>(P);
-        else bigru_layer_kernel<8, true><<<grid, HM_THREADS, 0, st>>>(P);
-    } else {
-        if (nt <= 2 * HM_WAVES) bigru_layer_kernel<2><<<grid, HM_THREADS, 0, st>>>(P);
-        else if (nt <= 4 * HM_WAVES) bigru_layer_kernel<4><<<grid, HM_THREADS, 0, st>>>(P);
-        else if (nt <= 7 * HM_WAVES) bigru_layer_kernel<7><<<grid, HM_THREADS, 0, st>>>(P);
-        else bigru_layer_kernel<8><<<grid, HM_THREADS, 0, st>>>(P);
-    }
-}
-
-int dsp_bigru_forward(const dsp_bigru* h, const float* d_x, int32_t T, int32_t B, const int32_t* d_len, float* d_y,
-                      float* d_hn, void* d_work, int64_t work_bytes, void* stream) {
-    if (!h || !d_x) return fail(DSP_EINVAL, "dsp_bigru_forward: NULL handle / input");
-    if (T < 1 || B < 1) return fail(DSP_EINVAL, "dsp_bigru_forward: T %d and B %d must be >= 1", T, B);
-    if (!d_y && !d_hn) return fail(DSP_EINVAL, "dsp_bigru_forward: nothing to write (d_y and d_hn are NULL)");
-    const int64_t per = bigru_buffer_floats(h, T, B), need = (h->L > 1 ? 2 : 1) * per * (int64_t)sizeof(float);
-    if (!d_work || work_bytes < need)
-        return fail(DSP_EINVAL, "dsp_bigru_forward: the workspace holds %lld bytes, %lld are needed", (long long)(d_work ? work_bytes : 0),
-                    (long long)need);
-    if ((reinterpret_cast<uintptr_t>(d_work) & 3) != 0) return fail(DSP_EINVAL, "dsp_bigru_forward: d_work must be 4-byte aligned");
-    float* bufs[2] = {static_cast<float*>(d_work), static_cast<float*>(d_work) + (h->L > 1 ? per : 0)};
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((B + HM_COLS - 1) / HM_COLS, 2);
-    for (int l = 0; l < h->L; ++l) {
-        const bool last = l == h->L - 1;
-        GruParams P;
-        P.T = T; P.B = B;
-        P.x = l == 0 ? d_x : bufs[(l - 1) & 1];
-        P.len = d_len;
-        P.out = (last && !d_y) ? nullptr : bufs[l & 1];
-        P.hn = d_hn ? d_hn + (int64_t)2 * l * B * h->H : nullptr;
-        bigru_launch_layer(h, l, P, nullptr, nullptr, grid, st);
-        HIP_TRY(hipGetLastError());
-    }
-    if (d_y) {
-        bigru_sum_kernel<<<grid_for((int64_t)T * B * h->H, 256), 256, 0, st>>>(bufs[(h->L - 1) & 1], d_len, T, B, h->H, d_y);
-        HIP_TRY(hipGetLastError());
-    }
-    return DSP_OK;
-}
-
-int dsp_bigru_tape_bytes(const dsp_bigru* h, int32_t T, int32_t B, int64_t* bytes) {
-    if (!h || !bytes) return fail(DSP_EINVAL, "dsp_bigru_tape_bytes: NULL argument");
-    if (T < 1 || B < 1) return fail(DSP_EINVAL, "dsp_bigru_tape_bytes: T %d and B %d must be >= 1", T, B);
-    *bytes = gru_tape_floats(h->H, h->L, T, B) * (int64_t)sizeof(float);
-    return DSP_OK;
-}
-
-int dsp_bigru_tape_rows(const dsp_bigru* h, int32_t layer, int32_t T, int32_t B, int64_t* offset_bytes) {
-    if (!h || !offset_bytes) return fail(DSP_EINVAL, "dsp_bigru_tape_rows: NULL argument");
-    if (T < 1 || B < 1) return fail(DSP_EINVAL, "dsp_bigru_tape_rows: T %d and B %d must be >= 1", T, B);
-    if (layer < 0 || layer >= h->L) return fail(DSP_EINVAL, "dsp_bigru_tape_rows: layer %d out of range [0, %d)", layer, h->L);
-    *offset_bytes = layer * gru_tape_rows_floats(h->H, T, B) * (int64_t)sizeof(float);
-    return DSP_OK;
-}
-
-// The tape argument of the two training entry points.  Without a handle (h == NULL: the caller reports that next) the size is
-// held against the smallest tape any handle asks for at (T, B).
-static int bigru_check_tape(const char* who, const dsp_bigru* h, int32_t T, int32_t B, const void* d_tape, int64_t tape_bytes) {
-    if (!d_tape) return fail(DSP_EINVAL, "%s: NULL tape", who);
-    if ((reinterpret_cast<uintptr_t>(d_tape) & 15) != 0) return fail(DSP_EINVAL, "%s: d_tape must be 16-byte aligned", who);
-    const int64_t need = gru_tape_floats(h ? h->H : 4, h ? h->L : 1, T, B) * (int64_t)sizeof(float);
-    if (tape_bytes < need)
-        return fail(DSP_EINVAL, "%s: the tape is short (%lld bytes, dsp_bigru_tape_bytes asks for %lld)", who, (long long)tape_bytes, (long long)need);
-    return DSP_OK;
-}
-
-// where layer l's output rows and gates start in the tape
-static float* bigru_tape_rows(const dsp_bigru* h, void* tape, int l, int32_t T, int32_t B) {
-    return static_cast<float*>(tape) + l * gru_tape_rows_floats(h->H, T, B);
-}
-static float* bigru_tape_gates(const dsp_bigru* h, void* tape, int l, int32_t T, int32_t B) {
-    return static_cast<float*>(tape) + h->L * gru_tape_rows_floats(h->H, T, B) + l * gru_tape_layer_gates_floats(h->H, T, B);
-}
-
-int dsp_bigru_forward_train(const dsp_bigru* h, const float* d_x, int32_t T, int32_t B, const int32_t* d_len, const float* d_drop,
-                            float* d_y, float* d_hn, void* d_tape, int64_t tape_bytes, void* stream) {
-    const char* who = "dsp_bigru_forward_train";
-    if (T < 1 || B < 1) return fail(DSP_EINVAL, "%s: T %d and B %d must be >= 1", who, T, B);
-    if (int rc = bigru_check_tape(who, h, T, B, d_tape, tape_bytes)) return rc;
-    if (!d_x) return fail(DSP_EINVAL, "%s: NULL input", who);
-    if (!h) return fail(DSP_EINVAL, "%s: NULL handle", who);
-    if ((reinterpret_cast<uintptr_t>(d_drop) & 3) != 0) return fail(DSP_EINVAL, "%s: d_drop must be 4-byte aligned", who);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((B + HM_COLS - 1) / HM_COLS, 2);
-    for (int l = 0; l < h->L; ++l) {
-        GruParams P;
-        P.T = T; P.B = B;
-        P.x = l == 0 ? d_x : bigru_tape_rows(h, d_tape, l - 1, T, B);
-        P.len = d_len;
-        P.out = bigru_tape_rows(h, d_tape, l, T, B);
-        P.hn = d_hn ? d_hn + (int64_t)2 * l * B * h->H : nullptr;
-        bigru_launch_layer(h, l, P, bigru_tape_gates(h, d_tape, l, T, B),
-                           (l > 0 && d_drop) ? d_drop + (int64_t)(l - 1) * gru_tape_rows_floats(h->H, T, B) : nullptr, grid, st);
-        HIP_TRY(hipGetLastError());
-    }
-    if (d_y) {
-        bigru_sum_kernel<<<grid_for((int64_t)T * B * h->H, 256), 256, 0, st>>>(bigru_tape_rows(h, d_tape, h->L - 1, T, B), d_len, T, B, h->H, d_y);
-        HIP_TRY(hipGetLastError());
-    }
-    return DSP_OK;
-}
-
-int dsp_bigru_backward(const dsp_bigru* h, int32_t layer, int32_t T, int32_t B, const int32_t* d_len, const void* d_tape,
-                       int64_t tape_bytes, const float* d_g, const float* d_g_hn, float* d_da, void* stream) {
-    const char* who = "dsp_bigru_backward";
-    if (T < 1 || B < 1) return fail(DSP_EINVAL, "%s: T %d and B %d must be >= 1", who, T, B);
-    if (int rc = bigru_check_tape(who, h, T, B, d_tape, tape_bytes)) return rc;
-    if (!d_g && !d_g_hn) return fail(DSP_EINVAL, "%s: no gradient to propagate (g and g_hn are both NULL)", who);
-    if (!d_da) return fail(DSP_EINVAL, "%s: NULL output (da)", who);
-    if (((reinterpret_cast<uintptr_t>(d_g) | reinterpret_cast<uintptr_t>(d_g_hn) | reinterpret_cast<uintptr_t>(d_da)) & 3) != 0)
-        return fail(DSP_EINVAL, "%s: g, g_hn and da must be 4-byte aligned", who);
-    if (!h) return fail(DSP_EINVAL, "%s: NULL handle", who);
-    if (layer < 0 || layer >= h->L) return fail(DSP_EINVAL, "%s: layer %d out of range [0, %d)", who, layer, h->L);
-    GruBwdParams P;
-    P.wt[0] = h->wt[layer][0]; P.wt[1] = h->wt[layer][1];
-    P.H = h->H; P.T = T; P.B = B;
-    P.g_stride = layer == h->L - 1 ? h->H : 2 * h->H;
-    P.len = d_len;
-    P.gates = bigru_tape_gates(h, const_cast<void*>(d_tape), layer, T, B);
-    P.out = bigru_tape_rows(h, const_cast<void*>(d_tape), layer, T, B);
-    P.g = d_g; P.g_hn = d_g_hn; P.da = d_da;
-    const dim3 grid((B + HM_COLS - 1) / HM_COLS, 2);
-    const size_t lds = gru_bwd_lds_bytes(h->H);                // up to 64 KiB: above the static limit
-    hipStream_t st = (hipStream_t)stream;
-    if (hm_bwd_chunks(h->H) <= 1) {
-        static size_t granted[DSP_MAX_DEVICES] = {};
-        if (dsp_ensure_dynamic_lds((const void*)bigru_backward_kernel<1>, lds, granted) != 0)
-            return fail(DSP_EHIP, "%s: %zu bytes of LDS were not granted", who, lds);
-        bigru_backward_kernel<1><<<grid, HM_THREADS, lds, st>>>(P);
-    } else {
-        static size_t granted[DSP_MAX_DEVICES] = {};
-        if (dsp_ensure_dynamic_lds((const void*)bigru_backward_kernel<2>, lds, granted) != 0)
-            return fail(DSP_EHIP, "%s: %zu bytes of LDS were not granted", who, lds);
-        bigru_backward_kernel<2><<<grid, HM_THREADS, lds, st>>>(P);
-    }
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }

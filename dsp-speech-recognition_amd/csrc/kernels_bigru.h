@@ -1,7 +1,7 @@
 // Forward pass of the reference's layers.DynamicEncoder (layers.py:42-76): n_layers bidirectional GRU layers over ragged
 // lengths, fp32, one launch per layer plus one that sums the two directions of the last layer.
 //
-// Shape.  As in kernels_hmlstm.h a workgroup owns a slice of HM_COLS = 16 batch columns for all steps of ONE direction
+// Shape.  As in kernels_hmlstm.h (rnn_common.h) a workgroup owns a slice of HM_COLS = 16 batch columns for all steps of ONE direction
 // (grid = slices x 2) and never waits on another workgroup: no grid barrier, no flag, every loop bounded by an argument.
 // A slice runs max(len) of its columns steps; the reverse direction starts there, so neither sorting nor packing is needed.
 //
@@ -10,10 +10,10 @@
 // registers.  The input part and the hidden part are ONE product over the concatenated K axis [x (padded to 16) | h]:
 // rows r and z carry weights in both parts, n_x only in the x part (W_in), n_h only in the h part (W_hn), zeros elsewhere,
 // which keeps W_in x and W_hn h in separate registers as  n = tanh(n_x + r * n_h)  needs.  The operand [x_t | h] is one LDS
-// buffer in the hm_idx layout and the product loop is hm_product of kernels_hmlstm.h, unchanged.
+// buffer in the hm_idx layout and the product loop is hm_product of rnn_common.h, unchanged.
 #pragma once
 
-#include "kernels_hmlstm.h"
+#include "rnn_common.h"
 
 #define GRU_MAX_IN 512      // input_size: 1 .. 512 (inner layers read 2 H <= 512)
 #define GRU_MAX_H 256       // hidden: multiple of 4 in [4, 256]
@@ -51,7 +51,7 @@ struct GruParams {
 __host__ __device__ static inline int64_t gru_tape_step(int32_t H) { return 64 * (int64_t)H; }
 static inline int64_t gru_tape_rows_floats(int32_t H, int32_t T, int32_t B) { return (int64_t)T * B * 2 * H; }
 static inline int64_t gru_tape_layer_gates_floats(int32_t H, int32_t T, int32_t B) {
-    return 2 * (int64_t)((B + HM_COLS - 1) / HM_COLS) * T * gru_tape_step(H);
+    return 2 * (int64_t)hm_slices(B) * T * gru_tape_step(H);
 }
 static inline int64_t gru_tape_floats(int32_t H, int32_t L, int32_t T, int32_t B) {
     return L * (gru_tape_rows_floats(H, T, B) + gru_tape_layer_gates_floats(H, T, B));
@@ -63,12 +63,10 @@ __global__ __launch_bounds__(256) void gru_pack_kernel(const float* __restrict__
     const int32_t nt = H / 4;
     const int64_t total = (int64_t)ng * nt * 256;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t e = (int32_t)(i & 3), l = (int32_t)((i >> 2) & 63);
-        const int64_t gt = i >> 8;
-        const int32_t t = (int32_t)(gt % nt), g = (int32_t)(gt / nt);
-        const int32_t r = l & 15, slot = r & 3, unit = 4 * t + (r >> 2), k = 16 * g + 4 * (l >> 4) + e;
+        const HmPackIdx p = hm_pack_idx(i, nt);
+        const int32_t r = p.l & 15, slot = r & 3, unit = 4 * p.t + (r >> 2), k = p.k;
         float v = 0.0f;
-        if (g < ngx) {
+        if (p.g < ngx) {
             if (slot < 3 && k < I) v = w_ih[(int64_t)(slot * H + unit) * I + k];
         } else {
             const int32_t kh = k - 16 * ngx, gate = slot == 3 ? 2 : slot;
@@ -93,33 +91,17 @@ template <int MAXS, bool TAPE = false>
 __device__ __forceinline__ void gru_cell(const GruDir& dp, int ng, int nt, const float* lds, float (&h)[MAXS], bool active,
                                          int w, int lane, float* tape = nullptr) {
     const int q = lane >> 4;
-#pragma unroll
-    for (int s0 = 0; s0 < MAXS; s0 += HM_CHUNK) {
-        const int t0 = w + HM_WAVES * s0;
-        if (t0 >= nt) break;
-        const int CAP = MAXS - s0 < HM_CHUNK ? MAXS - s0 : HM_CHUNK;          // tiles this chunk can hold (folds when unrolled)
-        const int left = (nt - t0 + HM_WAVES - 1) / HM_WAVES;                   // tiles of this wave from t0 on
-        hm_f32x4 acc[HM_CHUNK];
-        if (CAP >= 4 && left >= 4) hm_product<4>(acc, dp.w, ng, nt, lds, t0, lane);
-        else if (CAP >= 3 && left >= 3) hm_product<3>(acc, dp.w, ng, nt, lds, t0, lane);
-        else if (CAP >= 2 && left >= 2) hm_product<2>(acc, dp.w, ng, nt, lds, t0, lane);
-        else hm_product<1>(acc, dp.w, ng, nt, lds, t0, lane);
-#pragma unroll
-        for (int i = 0; i < HM_CHUNK; ++i) {
-            const int s = s0 + i, t = t0 + HM_WAVES * i;
-            if (i < CAP && t < nt) {
-                const float4 bv = *reinterpret_cast<const float4*>(dp.bias + t * 16 + 4 * q);
-                const hm_f32x4 f4 = acc[i] + hm_f32x4{bv.x, bv.y, bv.z, bv.w};
-                const float r = hm_sigmoid(f4.x), z = hm_sigmoid(f4.y), n = tanhf(f4.z + r * f4.w);
-                if (TAPE) {
-                    typedef __attribute__((address_space(1))) hm_f32x4 gw4;
-                    ((gw4*)hm_uniform(tape + t * 256))[lane] = hm_f32x4{r, z, n, f4.w};
-                }
-                const float hn = (1.0f - z) * n + z * h[s];
-                h[s] = active ? hn : h[s];                                      // a column behind its end keeps its h
-            }
-        }
-    }
+    struct Acc { hm_f32x4 acc[HM_CHUNK]; };
+    hm_for_chunks<MAXS, Acc>(
+        nt, w, [&](auto n, Acc& p, int t0) { hm_product<decltype(n)::value>(p.acc, dp.w, ng, nt, lds, t0, lane); },
+        [&](const Acc& p, int i, int s, int t) {
+            const float4 bv = *reinterpret_cast<const float4*>(dp.bias + t * 16 + 4 * q);
+            const hm_f32x4 f4 = p.acc[i] + hm_f32x4{bv.x, bv.y, bv.z, bv.w};
+            const float r = hm_sigmoid(f4.x), z = hm_sigmoid(f4.y), n = tanhf(f4.z + r * f4.w);
+            if (TAPE) ((hm_gf4*)hm_uniform(tape + t * 256))[lane] = hm_f32x4{r, z, n, f4.w};
+            const float hn = (1.0f - z) * n + z * h[s];
+            h[s] = active ? hn : h[s];                                          // a column behind its end keeps its h
+        });
 }
 
 template <int MAXS, bool TAPE = false>
@@ -135,17 +117,7 @@ __global__ __launch_bounds__(HM_THREADS) void bigru_layer_kernel(const GruParams
     float* hbuf = buf + P.ngx * (16 * HM_COLS);
 
     for (int i = tid; i < ng * (16 * HM_COLS); i += HM_THREADS) buf[i] = 0.f;
-    if (tid < HM_COLS) {
-        const int bb = b0 + tid;
-        int n = 0;                                                              // a column that does not exist is never active
-        if (bb < B) n = P.len ? min(max(P.len[bb], 1), T) : T;
-        lens[tid] = n;
-    }
-    __syncthreads();
-    int steps = 0;
-#pragma unroll
-    for (int c = 0; c < HM_COLS; ++c) steps = max(steps, lens[c]);
-    steps = __builtin_amdgcn_readfirstlane(steps);
+    const int steps = hm_slice_steps(P.len, b0, B, T, lens);
     const int mylen = lens[col];
 
     // x_t of the slice is one contiguous run of (columns of the slice) * I floats; rows need not be 16-byte aligned
@@ -214,14 +186,8 @@ __global__ __launch_bounds__(HM_THREADS) void bigru_layer_kernel(const GruParams
         }
     }
 
-    if (TAPE && P.out) {                    // the rows no step visited: the backward's GEMMs read every row of a layer
-        const int n = min(HM_COLS, B - b0) * H;
-        for (int t = steps; t < T; ++t)
-            for (int idx = tid; idx < n; idx += HM_THREADS) {
-                const int c = idx / H, j = idx - c * H;
-                P.out[((int64_t)t * B + b0 + c) * (2 * H) + dir * H + j] = 0.f;
-            }
-    }
+    // the rows no step visited: the backward's GEMMs read every row of a layer
+    if (TAPE && P.out) hm_zero_rows(P.out, H, 2 * H, dir * H, steps, T, b0, B);
 
     if (P.hn && b < B) {
 #pragma unroll

@@ -14,13 +14,13 @@
 // the owners compute the four gate gradients of their units and write them, as one float4, into the LDS operand of the matrix
 // pipe: its K order is (unit, slot), so float4 unit * 16 + col IS the owner's place (tile * 64 + lane, conflict free).  The n_x
 // slot stays in K (K = 4 H, its weights are zeros): the operand is 64 H floats, 64 KiB at H = 256.  dh += W_hh^T (da_r, da_z,
-// da_nh) is hm_bwd_product: the weights are packed transposed at create (gru_pack_t_kernel, hm_pack_t_kernel's scheme) with the
+// da_nh) is hm_bwd_product of rnn_common.h: the weights are packed transposed at create (gru_pack_t_kernel, hm_pack_t_kernel's scheme) with the
 // rows of an M tile permuted so that accumulator register r of chunk c is slot 4 c + r of the lane that owns the unit -- the
 // product lands in the owners' registers and nothing but da crosses LDS.  Two barriers per step.
 #pragma once
 
 #include "kernels_bigru.h"
-#include "kernels_hmlstm_bwd.h"
+#include "rnn_common.h"
 
 struct GruBwdParams {
     const float4* wt[2];        // packed transposed W_hh of the forward and the reverse direction (gru_pack_t_kernel)
@@ -43,12 +43,9 @@ static inline size_t gru_bwd_lds_bytes(int32_t H) { return (size_t)64 * H * size
 __global__ __launch_bounds__(256) void gru_pack_t_kernel(const float* __restrict__ w_hh, int32_t H, int32_t nt, float* __restrict__ dst) {
     const int64_t total = (int64_t)(H / 4) * nt * 256;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t e = (int32_t)(i & 3), l = (int32_t)((i >> 2) & 63);
-        const int64_t gt = i >> 8;
-        const int32_t tt = (int32_t)(gt % nt), g = (int32_t)(gt / nt);
-        const int32_t k = 16 * g + 4 * (l >> 4) + e, slot = k & 3, unit = k >> 2;
+        const HmPackIdx p = hm_pack_idx(i, nt);
+        const int32_t slot = p.k & 3, unit = p.k >> 2, m = hm_pack_t_m(p.t, p.l);
         const int32_t row = slot == 2 ? -1 : (slot == 3 ? 2 * H + unit : slot * H + unit);
-        const int32_t ii = l & 15, m = 4 * ((tt & 7) + 8 * (4 * (tt >> 3) + (ii & 3))) + (ii >> 2);
         dst[i] = (row >= 0 && m < H) ? w_hh[(int64_t)row * H + m] : 0.0f;
     }
 }
@@ -68,17 +65,7 @@ __global__ __launch_bounds__(HM_THREADS) void bigru_backward_kernel(const GruBwd
     const int H = P.H, T = P.T, B = P.B, nt = H >> 2, nc = hm_bwd_chunks(H);
     const bool col_ok = b < B;
 
-    if (tid < HM_COLS) {
-        const int bb = b0 + tid;
-        int n = 0;                                                              // a column that does not exist is never active
-        if (bb < B) n = P.len ? min(max(P.len[bb], 1), T) : T;
-        lens[tid] = n;
-    }
-    __syncthreads();
-    int steps = 0;
-#pragma unroll
-    for (int c = 0; c < HM_COLS; ++c) steps = max(steps, lens[c]);
-    steps = __builtin_amdgcn_readfirstlane(steps);
+    const int steps = hm_slice_steps(P.len, b0, B, T, lens);
     const int mylen = lens[col];
 
     const int64_t step = gru_tape_step(H);
@@ -117,7 +104,6 @@ __global__ __launch_bounds__(HM_THREADS) void bigru_backward_kernel(const GruBwd
         }
     };
 
-    typedef __attribute__((address_space(1))) float gfw;
     hm_lf4* d4 = (hm_lf4*)grb_smem;
     if (steps > 0) load(step_t(0));
 
@@ -137,12 +123,7 @@ __global__ __launch_bounds__(HM_THREADS) void bigru_backward_kernel(const GruBwd
                 if (!active) v = hm_f32x4{0.f, 0.f, 0.f, 0.f};              // a column behind its end: an exact zero row,
                 dh[s] = active ? d * z : dh[s];                                 // and dh passes through
                 d4[tl * 64 + lane] = v;
-                if (col_ok) {
-                    ((gfw*)hm_uniform(out + 4 * tl))[lo] = v.z;
-                    ((gfw*)hm_uniform(out + H + 4 * tl))[lo] = v.x;
-                    ((gfw*)hm_uniform(out + 2 * H + 4 * tl))[lo] = v.y;
-                    ((gfw*)hm_uniform(out + 3 * H + 4 * tl))[lo] = v.w;
-                }
+                if (col_ok) hm_store_gate_grads(out, H, tl, lo, v.z, v.x, v.y, v.w);        // rows n_x | r | z | n_h
             }
         }
         if (s0 + 1 < steps) load(step_t(s0 + 1));       // in flight behind the product
@@ -157,12 +138,5 @@ __global__ __launch_bounds__(HM_THREADS) void bigru_backward_kernel(const GruBwd
     }
 
     // the steps no column of the slice reaches: exact zero rows
-    const int nz = min(HM_COLS, B - b0) * 4 * H;
-    for (int t = steps; t < T; ++t) {
-        float* row = P.da + (((int64_t)t * B + b0) * 2 + dir) * (4 * H);
-        for (int idx = tid; idx < nz; idx += HM_THREADS) {
-            const int c = idx / (4 * H), j = idx - c * (4 * H);
-            row[c * 8 * H + j] = 0.f;
-        }
-    }
+    hm_zero_rows(P.da, 4 * H, 8 * H, dir * 4 * H, steps, T, b0, B);
 }

@@ -13,20 +13,12 @@
 // reference's order (hmrnn.py:84), z multiplied in as a factor, never branched on.
 #pragma once
 
-#include "dsp_common.h"
+#include "rnn_common.h"
 
-#define HM_COLS 16          // batch columns per workgroup = N of the 16x16x4 product
-#define HM_WAVES 8          // 512 threads: two waves per SIMD, so dependent accumulators never stall the matrix pipe
-#define HM_THREADS (HM_WAVES * 64)
 #define HM_MAX_SIZE 256     // input_size, H1, H2: multiples of 4 in [4, 256]
 #define HM_BUF_FLOATS (HM_MAX_SIZE * HM_COLS)
 
-typedef float hm_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) hm_f32x4 hm_gf4;   // four floats in global memory
-typedef __attribute__((address_space(3))) hm_f32x4 hm_lf4;   // four floats in LDS
-
 static inline bool hm_size_ok(int32_t n) { return n >= 4 && n <= HM_MAX_SIZE && (n & 3) == 0; }
-static inline int32_t hm_kgroups(int32_t k) { return (k + 15) >> 4; }      // K padded to 16: four products per packed float4
 static inline int32_t hm_tiles(int32_t h) { return h / 4 + 1; }            // H / 4 gate tiles + the boundary row's tile
 
 // One cell's packed parameters: for segment s (0: W_01, 1: U_21, 2: U_11), k-group g, tile t, lane l the float4
@@ -65,7 +57,7 @@ struct HmParams {
 // Slice s, step t starts at ((s * T) + t) * hm_tape_step: every column of the last slice is written, b >= B included.
 __host__ __device__ static inline int64_t hm_tape_step(int32_t H1, int32_t H2) { return 80 * (int64_t)(H1 + H2) + 32; }
 static inline int64_t hm_tape_floats(int32_t H1, int32_t H2, int32_t T, int32_t B) {
-    return (int64_t)((B + HM_COLS - 1) / HM_COLS) * T * hm_tape_step(H1, H2);
+    return (int64_t)hm_slices(B) * T * hm_tape_step(H1, H2);
 }
 
 // row of the reference's [4H + 1, K] matrix behind row r of tile t; -1: padding
@@ -80,11 +72,9 @@ __global__ __launch_bounds__(256) void hm_pack_kernel(const float* __restrict__ 
     const int32_t nt = H / 4 + 1;
     const int64_t total = (int64_t)ng * nt * 256;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t e = (int32_t)(i & 3), l = (int32_t)((i >> 2) & 63);
-        const int64_t gt = i >> 8;
-        const int32_t t = (int32_t)(gt % nt), g = (int32_t)(gt / nt);
-        const int32_t row = hm_row(t, l & 15, H), k = 16 * g + 4 * (l >> 4) + e;
-        dst[i] = (row >= 0 && k < K) ? src[(int64_t)row * K + k] : 0.0f;
+        const HmPackIdx p = hm_pack_idx(i, nt);
+        const int32_t row = hm_row(p.t, p.l & 15, H);
+        dst[i] = (row >= 0 && p.k < K) ? src[(int64_t)row * K + p.k] : 0.0f;
     }
 }
 
@@ -94,71 +84,6 @@ __global__ __launch_bounds__(256) void hm_pack_bias_kernel(const float* __restri
         const int32_t row = hm_row(i >> 4, i & 15, H);
         dst[i] = row >= 0 ? src[row] : 0.0f;
     }
-}
-
-// float index of element (k, col) of an LDS operand buffer: lane l of k-group g reads the float4 at 64 g + l
-__device__ __forceinline__ int hm_idx(int k, int col) { return (((k >> 2) * HM_COLS + col) << 2) + (k & 3); }
-
-__device__ __forceinline__ float hm_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
-
-// A wave-uniform address, taken through readfirstlane and so held in scalar registers: the loads below are then "scalar base
-// + the lane's own offset", and the per-slot addresses are not carried in vector registers across the step loop (which
-// spills; see hm_product).  Used by the training mode and by kernels_hmlstm_bwd.h.
-template <class Tp>
-__device__ __forceinline__ Tp* hm_uniform(Tp* p) {
-    const uint64_t a = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    return reinterpret_cast<Tp*>(((uint64_t)hi << 32) | lo);
-}
-
-#define HM_CHUNK 4          // tiles a wave accumulates side by side: independent accumulators, one read of the LDS operand
-
-// acc[i] = (packed segment) x (LDS operand) for the N tiles t0, t0 + 8, ..  Two k-groups per trip through two register
-// sets: the weights of the next k-group are in flight while the products of this one issue (L2 latency behind the matrix pipe).
-template <int N>
-__device__ __forceinline__ void hm_mfma4(hm_f32x4 (&acc)[HM_CHUNK], const hm_f32x4 (&a)[N], const hm_f32x4 b) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, b.x, acc[i], 0, 0, 0);
-        acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, b.y, acc[i], 0, 0, 0);
-        acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, b.z, acc[i], 0, 0, 0);
-        acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, b.w, acc[i], 0, 0, 0);
-    }
-}
-
-template <int N>
-__device__ __forceinline__ void hm_product(hm_f32x4 (&acc)[HM_CHUNK], const float4* __restrict__ wp, int ng, int nt,
-                                           const float* lds_b, int t0, int lane) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) acc[i] = hm_f32x4{0.f, 0.f, 0.f, 0.f};
-    const hm_lf4* lb = (const hm_lf4*)lds_b + lane;     // explicitly LDS: a generic pointer costs flat loads, which wait for every counter
-    // The start address is wave-uniform and made opaque to the optimiser: otherwise the start addresses of every product of
-    // both cells are hoisted out of the step loop and held in vector registers across it, which spills at 7 tiles per wave.
-    // It goes back to a pointer into GLOBAL memory (a generic one costs flat loads, which wait for every counter).
-    uint64_t wa = reinterpret_cast<uint64_t>(wp + (size_t)t0 * 64);
-    asm volatile("" : "+s"(wa));
-    const hm_gf4* wg = (const hm_gf4*)wa;
-    const size_t stride = (size_t)nt * 64;
-    const unsigned l = (unsigned)lane;
-    hm_f32x4 a0[N], a1[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) a0[i] = wg[l + HM_WAVES * i * 64];
-    int g = 0;
-    for (; g + 1 < ng; g += 2) {
-        const hm_gf4* w1 = wg + stride;
-#pragma unroll
-        for (int i = 0; i < N; ++i) a1[i] = w1[l + HM_WAVES * i * 64];
-        __builtin_amdgcn_sched_barrier(0);          // the requests stay in front of the products they overlap with
-        hm_mfma4<N>(acc, a0, lb[g * 64]);
-        __builtin_amdgcn_sched_barrier(0);
-        wg += (g + 2 < ng) ? 2 * stride : 0;        // behind the last k-group: re-request one already held (no branch, no read past the segment)
-#pragma unroll
-        for (int i = 0; i < N; ++i) a0[i] = wg[l + HM_WAVES * i * 64];
-        __builtin_amdgcn_sched_barrier(0);
-        hm_mfma4<N>(acc, a1, lb[(g + 1) * 64]);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if (g < ng) hm_mfma4<N>(acc, a0, lb[g * 64]);
 }
 
 // The three products of a cell for N tiles: fs = W_01 h_bottom + z U_21 h_top, acc = U_11 h (hmrnn.py:75-84)
@@ -187,6 +112,8 @@ __device__ __forceinline__ float hm_cell(const HmCell& cp, const float* lds_bott
     const int q = lane >> 4, nt = cp.n_tiles;
     const float nz = 1.0f - z, keep = nz * (1.0f - zb), upd = nz * zb;
     float zh = 0.f;
+    // The chunk walk of rnn_common.h's hm_for_chunks, written out: through the helper's callables the eight instantiations of
+    // the forward kernel compile to other code, which measured 1.3 - 2.4 % slower (profiles/rnn_common_refactor_ab.txt).
 #pragma unroll
     for (int s0 = 0; s0 < MAXS; s0 += HM_CHUNK) {
         const int t0 = w + HM_WAVES * s0;
@@ -209,10 +136,8 @@ __device__ __forceinline__ float hm_cell(const HmCell& cp, const float* lds_bott
                     const float f = hm_sigmoid(f4.x), gi = hm_sigmoid(f4.y), gg = tanhf(f4.w), ig = gi * gg, o = hm_sigmoid(f4.z);
                     const float cn = z * ig + keep * c[s] + upd * (f * c[s] + ig);
                     if (TAPE) {
-                        typedef __attribute__((address_space(1))) hm_f32x4 gw4;
-                        typedef __attribute__((address_space(1))) float gw;
-                        ((gw4*)hm_uniform(tape + t * 256))[lane] = hm_f32x4{f, gi, o, gg};
-                        ((gw*)hm_uniform(tape + (nt - 1) * 256 + t * 64))[lane] = cn;
+                        ((hm_gf4*)hm_uniform(tape + t * 256))[lane] = hm_f32x4{f, gi, o, gg};
+                        ((hm_gfw*)hm_uniform(tape + (nt - 1) * 256 + t * 64))[lane] = cn;
                     }
                     const float ot = o * tanhf(cn);
                     h[s] = z * ot + keep * h[s] + upd * ot;
@@ -221,7 +146,7 @@ __device__ __forceinline__ float hm_cell(const HmCell& cp, const float* lds_bott
                     // hard_sigm (hmrnn.py:25-28) in the reference's own rounding steps
                     const float pre = __fmul_rn(__fadd_rn(__fmul_rn(f4.x, a), 1.0f), 0.5f);
                     zh = fminf(fmaxf(pre, 0.0f), 1.0f);
-                    if (TAPE && q == 0) ((__attribute__((address_space(1))) float*)hm_uniform(mask))[lane & 15] = (pre >= 0.0f && pre <= 1.0f) ? 1.0f : 0.0f;
+                    if (TAPE && q == 0) ((hm_gfw*)hm_uniform(mask))[lane & 15] = (pre >= 0.0f && pre <= 1.0f) ? 1.0f : 0.0f;
                 }
             }
         }

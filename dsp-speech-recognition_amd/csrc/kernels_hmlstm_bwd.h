@@ -19,8 +19,7 @@
 #pragma once
 
 #include "kernels_hmlstm.h"
-
-typedef __attribute__((address_space(1))) const float hm_gf;     // a float in global memory, read only
+#include "rnn_common.h"
 
 struct HmBwdParams {
     const float4* wt[4];        // packed transposed: U_11(2)^T, W_01(2)^T, U_21^T, U_11(1)^T
@@ -40,8 +39,6 @@ struct HmBwdParams {
     float* dfs2;
 };
 
-// chunks of four owner slots a wave needs for H units: H / 4 gate tiles over 8 waves, four slots per M tile
-__host__ __device__ static inline int32_t hm_bwd_chunks(int32_t H) { return (((H >> 2) + HM_WAVES - 1) / HM_WAVES + 3) >> 2; }
 static inline int64_t hm_bwd_packed_floats(int32_t Hcell, int32_t Hout) { return (int64_t)(Hcell / 4 + 1) * HM_WAVES * hm_bwd_chunks(Hout) * 256; }
 static inline size_t hm_bwd_lds_bytes(int32_t H1, int32_t H2) { return ((size_t)((H1 > H2 ? H1 : H2) / 4 + 1) * 256 + 2 * HM_WAVES * HM_COLS) * sizeof(float); }
 
@@ -52,12 +49,9 @@ __global__ __launch_bounds__(256) void hm_pack_t_kernel(const float* __restrict_
                                                         float* __restrict__ dst) {
     const int64_t total = (int64_t)(H / 4 + 1) * nt * 256;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t e = (int32_t)(i & 3), l = (int32_t)((i >> 2) & 63);
-        const int64_t gt = i >> 8;
-        const int32_t tt = (int32_t)(gt % nt), g = (int32_t)(gt / nt);
-        const int32_t k = 16 * g + 4 * (l >> 4) + e;
+        const HmPackIdx p = hm_pack_idx(i, nt);
+        const int32_t k = p.k, m = hm_pack_t_m(p.t, p.l);
         const int32_t row = k < 4 * H ? (k & 3) * H + (k >> 2) : (k == 4 * H ? 4 * H : -1);
-        const int32_t ii = l & 15, m = 4 * ((tt & 7) + 8 * (4 * (tt >> 3) + (ii & 3))) + (ii >> 2);
         dst[i] = (row >= 0 && m < K) ? src[(int64_t)row * K + m] : 0.0f;
     }
 }
@@ -120,7 +114,6 @@ __device__ __forceinline__ void hm_bwd_cell(const HmBwdIn<NS>& in, int H, float 
                                             int w, int lane) {
     const int q = lane >> 4, ntg = H >> 2;
     const int lo = (lane & 15) * (4 * H + 1) + q;               // out: row 0 of column b0 at step t; the lane's part
-    typedef __attribute__((address_space(1))) float gfw;
     hm_lf4* d4 = (hm_lf4*)dfs;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -129,31 +122,13 @@ __device__ __forceinline__ void hm_bwd_cell(const HmBwdIn<NS>& in, int H, float 
             dh[s] += in.g[s];
             const hm_f32x4 d = hm_bwd_point(in.gt[s], in.cn[s], in.cp[s], in.hp[s], z, zb, dh[s], dc[s], pz, pzb);
             d4[tl * 64 + lane] = d;
-            if (col_ok) {
-                ((gfw*)hm_uniform(out + 4 * tl))[lo] = d.x;
-                ((gfw*)hm_uniform(out + H + 4 * tl))[lo] = d.y;
-                ((gfw*)hm_uniform(out + 2 * H + 4 * tl))[lo] = d.z;
-                ((gfw*)hm_uniform(out + 3 * H + 4 * tl))[lo] = d.w;
-            }
+            if (col_ok) hm_store_gate_grads(out, H, tl, lo, d.x, d.y, d.z, d.w);      // rows f | i | o | g
         }
     }
     if (w == 0) {
         d4[ntg * 64 + lane] = hm_f32x4{q == 0 ? zrow : 0.f, 0.f, 0.f, 0.f};
-        if (q == 0 && col_ok) ((gfw*)hm_uniform(out + 4 * H))[lo] = zrow;
+        if (q == 0 && col_ok) ((hm_gfw*)hm_uniform(out + 4 * H))[lo] = zrow;
     }
-}
-
-// acc (as slots) = (packed transposed matrix) x dfs for this wave's M tiles w, w + 8
-template <int NC>
-__device__ __forceinline__ void hm_bwd_product(float (&r)[4 * NC], const float4* wp, int ng, int nc, const float* dfs, int w, int lane) {
-    hm_f32x4 acc[HM_CHUNK];
-    if (NC >= 2 && nc >= 2) hm_product<2>(acc, wp, ng, HM_WAVES * 2, dfs, w, lane);
-    else {
-        hm_product<1>(acc, wp, ng, HM_WAVES, dfs, w, lane);
-        if (NC >= 2) acc[1] = hm_f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) { r[4 * c] = acc[c].x; r[4 * c + 1] = acc[c].y; r[4 * c + 2] = acc[c].z; r[4 * c + 3] = acc[c].w; }
 }
 
 // sum over the hidden units of each column: lanes q = 0..3 of a wave, then the eight waves in order through red [8][16]

@@ -22,7 +22,72 @@ import torch
 from torch import nn
 
 
-class _DynEnc(nn.Module):
+def _lengths(len0):
+    """Lengths as a list, a NumPy array or a tensor (any device, any integer dtype) -> an int64 NumPy array."""
+    return np.asarray(len0.cpu() if torch.is_tensor(len0) else len0, dtype=np.int64)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()      # an optional tensor: None is a NULL argument
+
+
+def _pack_state(hidden, H1, H2, B, **f32):
+    """hidden = (h1, c1, z1, h2, c2, z2) as [H, B] / [1, B] -> the flat h1 | c1 | z1 | h2 | c2 | z2 buffer of the kernels."""
+    state = torch.cat([v.detach().to(**f32).reshape(-1) for v in hidden])
+    assert state.numel() == (2 * H1 + 2 * H2 + 2) * B, 'hidden does not fit (h1, c1, z1, h2, c2, z2) of this batch'
+    return state
+
+
+def _split_state(state, H1, H2, B):
+    """The flat h1 | c1 | z1 | h2 | c2 | z2 buffer -> the six ``hidden`` views [H1, B], [H1, B], [1, B], [H2, B], [H2, B], [1, B]."""
+    rows = (H1, H1, 1, H2, H2, 1)
+    return tuple(v.view(n, B) for v, n in zip(torch.split(state, [n * B for n in rows]), rows))
+
+
+class _NativeHandle:
+    """The life cycle of a module's native handle (the packed copy of its parameters): built on first use, rebuilt when a
+    parameter moved or was written (data_ptr / _version), destroyed with the module, never shared with a copy.  The module
+    supplies ``_params()``, ``_descriptor(nat)`` -> the create function's descriptor of them, and ``_lib``, the prefix of the
+    library's create / destroy functions."""
+    _lib = _handle = _handle_key = None
+
+    def _drop_handle(self):
+        if self._handle is not None:
+            try:                                    # (at interpreter shutdown even the import may fail)
+                from . import _native as nat
+                getattr(nat.load(), self._lib + '_destroy')(self._handle)
+            except Exception:
+                pass
+            self._handle, self._handle_key = None, None
+
+    __del__ = _drop_handle
+
+    def __getstate__(self):
+        """Copies (copy.deepcopy, pickling) do not share the native handle: each builds its own on first use."""
+        d = self.__dict__.copy()
+        d['_handle'], d['_handle_key'] = None, None
+        return d
+
+    def _param_key(self, dev_index):
+        return (dev_index,) + tuple((p.data_ptr(), p._version) for p in self._params())
+
+    def _native_handle(self, dev):
+        key = self._param_key(dev.index)
+        if self._handle is None or key != self._handle_key:
+            from . import _native as nat
+            self._drop_handle()
+            d, h = self._descriptor(nat), nat.c_vp(0)
+            nat.check(getattr(nat.load(), self._lib + '_create')(nat.C.byref(d), nat.C.byref(h)))
+            self._handle, self._handle_key = h.value, key
+        return self._handle
+
+    def _check_unmodified(self, key):
+        """``key``: the ``_handle_key`` a forward ran with."""
+        if self._handle is None or self._handle_key != key or self._param_key(key[0]) != key:
+            raise RuntimeError(f'{type(self).__name__}: a parameter was modified between the native forward and its backward')
+
+
+class _DynEnc(_NativeHandle, nn.Module):
     """layers.DynamicEncoder (layers.py:42-76): bidirectional GRU over ragged lengths, output padded to max(lens) rows (zeros
     behind each end), forward + backward halves SUMMED.  Parameter names ``gru.*``.
 
@@ -43,12 +108,12 @@ class _DynEnc(nn.Module):
         ``native=None`` keeps ``nn.GRU`` whenever a gradient is required, unless ``native_train_default`` is set."""
     native_default = False         # what ``native=None`` picks where the native path can run: opt-in until DESIGN 7.3's timing shows it ahead
     native_train_default = False   # what ``native=None`` picks when a gradient is required: nn.GRU, until DESIGN 7.5's timing decides
+    _lib = 'dsp_bigru'
 
     def __init__(self, input_size, hidden_size, n_layers, dropout=0.0):
         super().__init__()
         self.hidden_size = hidden_size
         self.gru = nn.GRU(input_size, hidden_size, n_layers, dropout=dropout, bidirectional=True)
-        self._handle, self._handle_key = None, None
 
     # ---- native path ------------------------------------------------------------------------------------------------
     def _params(self):
@@ -77,38 +142,10 @@ class _DynEnc(nn.Module):
             return f'{nat.LIB_PATH} is not built'
         return None
 
-    def _drop_handle(self):
-        if getattr(self, '_handle', None) is not None:
-            try:                                    # (at interpreter shutdown even the import may fail)
-                from . import _native as nat
-                nat.load().dsp_bigru_destroy(self._handle)
-            except Exception:
-                pass
-            self._handle, self._handle_key = None, None
-
-    def __del__(self):
-        self._drop_handle()
-
-    def __getstate__(self):
-        """Copies (copy.deepcopy, pickling) do not share the native handle: each builds its own on first use."""
-        d = self.__dict__.copy()
-        d['_handle'], d['_handle_key'] = None, None
+    def _descriptor(self, nat):
+        d = nat.BigruDesc(self.gru.input_size, self.gru.hidden_size, self.gru.num_layers, 0)
+        d.d_params[:8 * self.gru.num_layers] = [p.data_ptr() for p in self._params()]
         return d
-
-    def _native_handle(self, dev):
-        """The packed copy of the parameters; rebuilt when one of them moved or was written (data_ptr / _version)."""
-        from . import _native as nat
-        ps = self._params()
-        key = (dev.index,) + tuple((p.data_ptr(), p._version) for p in ps)
-        if self._handle is None or key != self._handle_key:
-            self._drop_handle()
-            d = nat.BigruDesc(self.gru.input_size, self.gru.hidden_size, self.gru.num_layers, 0)
-            for i, p in enumerate(ps):
-                d.d_params[i] = p.data_ptr()
-            h = nat.c_vp(0)
-            nat.check(nat.load().dsp_bigru_create(nat.C.byref(d), nat.C.byref(h)))
-            self._handle, self._handle_key = h.value, key
-        return self._handle
 
     def _run_native(self, x, lens):
         from . import _native as nat
@@ -159,7 +196,7 @@ class _DynEnc(nn.Module):
 
     def run(self, x, lens, native=None):
         """-> (y [max(lens), B, H], h_n [2 n_layers, B, H]), the reference's return value (layers.py:76)."""
-        lens = torch.as_tensor(np.asarray(lens.cpu() if torch.is_tensor(lens) else lens), dtype=torch.int64)
+        lens = torch.as_tensor(_lengths(lens))
         if native is False:
             return self._run_torch(x, lens)
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
@@ -233,7 +270,7 @@ class _DynEncTrain(torch.autograd.Function):
         nat.check(lib.dsp_bigru_tape_bytes(handle, T, B, nat.C.byref(nbytes)))
         tape = torch.empty(nbytes.value // 4, **f32)
         y, hn = torch.empty(T, B, H, **f32), torch.empty(2 * L, B, H, **f32)
-        nat.check(lib.dsp_bigru_forward_train(handle, xc.data_ptr(), T, B, d_len.data_ptr(), None if drop is None else drop.data_ptr(),
+        nat.check(lib.dsp_bigru_forward_train(handle, xc.data_ptr(), T, B, d_len.data_ptr(), _ptr(drop),
                                               y.data_ptr(), hn.data_ptr(), tape.data_ptr(), nbytes.value,
                                               torch.cuda.current_stream(dev).cuda_stream))
         ctx.mod, ctx.tape_bytes, ctx.handle_key, ctx.has_drop = mod, nbytes.value, mod._handle_key, drop is not None
@@ -244,9 +281,7 @@ class _DynEncTrain(torch.autograd.Function):
     def backward(ctx, g_y, g_hn):
         from . import _native as nat
         mod = ctx.mod
-        now = ctx.handle_key[:1] + tuple((p.data_ptr(), p._version) for p in mod._params())
-        if mod._handle is None or mod._handle_key != ctx.handle_key or now != ctx.handle_key:
-            raise RuntimeError('_DynEnc: a parameter was modified between the native forward and its backward')
+        mod._check_unmodified(ctx.handle_key)
         saved = ctx.saved_tensors
         xc, d_len, tape = saved[:3]
         drop = saved[3] if ctx.has_drop else None
@@ -258,7 +293,6 @@ class _DynEncTrain(torch.autograd.Function):
             return (None,) * 4 + tuple(grads)
         gp = lambda g: None if g is None else g.to(torch.float32).contiguous()
         g, g_hn = gp(g_y), gp(g_hn)
-        ptr = lambda t: None if t is None else t.data_ptr()
         lib = nat.load()
         with torch.cuda.device(dev):
             off = nat.c_i64(0)
@@ -268,7 +302,7 @@ class _DynEncTrain(torch.autograd.Function):
                 rows.append(tape[off.value // 4:off.value // 4 + T * B * 2 * H].view(T, B, 2 * H))
             for l in range(L - 1, -1, -1):
                 da = torch.empty(T, B, 2, 4 * H, dtype=torch.float32, device=dev)
-                nat.check(lib.dsp_bigru_backward(mod._handle, l, T, B, d_len.data_ptr(), tape.data_ptr(), ctx.tape_bytes, ptr(g),
+                nat.check(lib.dsp_bigru_backward(mod._handle, l, T, B, d_len.data_ptr(), tape.data_ptr(), ctx.tape_bytes, _ptr(g),
                                                  None if g_hn is None else g_hn[2 * l:].data_ptr(), da.data_ptr(),
                                                  torch.cuda.current_stream(dev).cuda_stream))
                 dl = drop[l - 1] if (drop is not None and l > 0) else None
@@ -291,7 +325,7 @@ class RNNHead(nn.Module):
 
     def forward(self, inp, len0, native_enc=None):
         """inp: [T, B, 39] (zero beyond each utterance's length), len0: lengths (numpy / list / tensor) -> [B, 20]."""
-        lens = torch.as_tensor(np.asarray(len0.cpu() if torch.is_tensor(len0) else len0), dtype=torch.int64)
+        lens = torch.as_tensor(_lengths(len0))
         y = self.enc(inp, lens, native=native_enc)                          # [max(len0), B, H], zeros behind each end
         avg = y.sum(0) / lens.to(inp.device, inp.dtype).unsqueeze(1)        # rnn_clf.py:29-30
         mx = y.max(0).values                                                # rnn_clf.py:31 (over the padded rows too)
@@ -322,7 +356,7 @@ class HRNNHead(nn.Module):
         self.out = nn.Linear(400, 20)
 
     def _levels(self, inp, len0, native_enc=None):
-        len0 = np.asarray(len0.cpu() if torch.is_tensor(len0) else len0)
+        len0 = _lengths(len0)
         len1 = (len0 + self.hir - 1) // self.hir                      # rnn_clf.py:52
         y = self.enc1(inp, len0, native=native_enc)[:, :, -self.hidden_size:]            # rnn_clf.py:58
         return self.enc2(y[0::self.hir], len1, native=native_enc), len1                  # rnn_clf.py:61-65
@@ -448,7 +482,7 @@ class TransformerHead(nn.Module):
         self.hidden_size = 200
 
     def forward(self, inp, len0, dropout=True, native_enc=None):
-        len0 = np.asarray(len0.cpu() if torch.is_tensor(len0) else len0)
+        len0 = _lengths(len0)
         len1 = (len0 + self.hir - 1) // self.hir
         attn_out = self.attn_enc(inp)
         a = torch.nn.functional.dropout(attn_out, 0.5) if dropout else attn_out
@@ -554,13 +588,11 @@ class _HMLSTMTrain(torch.autograd.Function):
         z_1, z_2 = torch.empty(B, T, dtype=torch.uint8, device=dev), torch.empty(B, T, dtype=torch.uint8, device=dev)
         z_hat, last = torch.empty(T, 2, B, **f32), torch.empty(B, H2, **f32)
         nat.check(lib.dsp_hmlstm_forward_train(handle, xc.data_ptr(), T, B, a, d_len.data_ptr(),
-                                               None if state_in is None else state_in.data_ptr(), state_out.data_ptr(),
+                                               _ptr(state_in), state_out.data_ptr(),
                                                h_1.data_ptr(), h_2.data_ptr(), z_1.data_ptr(), z_2.data_ptr(), z_hat.data_ptr(),
                                                last.data_ptr(), tape.data_ptr(), nbytes.value,
                                                torch.cuda.current_stream(dev).cuda_stream))
-        ctx.mod, ctx.a, ctx.tape_bytes = mod, a, nbytes.value
-        ctx.handle_key = mod._handle_key
-        ctx.has_state = state_in is not None
+        ctx.mod, ctx.a, ctx.tape_bytes, ctx.handle_key, ctx.has_state = mod, a, nbytes.value, mod._handle_key, state_in is not None
         ctx.save_for_backward(xc, d_len, tape, h_1, h_2, z_1, z_2, *([state_in] if state_in is not None else []), *params)
         ctx.mark_non_differentiable(z_1, z_2, z_hat, state_out)
         return h_1, h_2, last, z_1, z_2, z_hat, state_out
@@ -576,20 +608,18 @@ class _HMLSTMTrain(torch.autograd.Function):
         T, B, _ = xc.shape
         H1, H2 = mod.size_list
         dev = xc.device
-        if mod._handle is None or mod._handle_key != ctx.handle_key:
-            raise RuntimeError('HMLSTM: a parameter was modified between the native forward and its backward')
+        mod._check_unmodified(ctx.handle_key)
         need = [ctx.needs_input_grad[4]] + list(ctx.needs_input_grad[5:12])
         if g_h1 is None and g_h2 is None and g_last is None:
             return (None,) * 12
         gp = lambda g: None if g is None else g.to(torch.float32).contiguous()
         g_h1, g_h2, g_last = gp(g_h1), gp(g_h2), gp(g_last)
-        ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(dev):
             dfs1 = torch.empty(T, B, 4 * H1 + 1, dtype=torch.float32, device=dev)
             dfs2 = torch.empty(T, B, 4 * H2 + 1, dtype=torch.float32, device=dev)
-            nat.check(nat.load().dsp_hmlstm_backward(mod._handle, T, B, ctx.a, d_len.data_ptr(), ptr(state_in), tape.data_ptr(),
+            nat.check(nat.load().dsp_hmlstm_backward(mod._handle, T, B, ctx.a, d_len.data_ptr(), _ptr(state_in), tape.data_ptr(),
                                                      ctx.tape_bytes, h_1.data_ptr(), h_2.data_ptr(), z_1.data_ptr(), z_2.data_ptr(),
-                                                     ptr(g_h1), ptr(g_h2), ptr(g_last), dfs1.data_ptr(), dfs2.data_ptr(),
+                                                     _ptr(g_h1), _ptr(g_h2), _ptr(g_last), dfs1.data_ptr(), dfs2.data_ptr(),
                                                      torch.cuda.current_stream(dev).cuda_stream))
             grads = hm_param_grads([p.detach() for p in params], xc, state_in, h_1, h_2, z_1, dfs1, dfs2, need)
         return (None, None, None, None) + grads
@@ -606,7 +636,7 @@ class HMLSTMResult:
             setattr(self, k, kw.get(k))
 
 
-class HMLSTM(nn.Module):
+class HMLSTM(_NativeHandle, nn.Module):
     """hmrnn.HM_LSTM (hmrnn.py:114-154): two hierarchical-multiscale LSTM cells over a [T, B, input_size] sequence.
     Parameter names, shapes and order equal the reference's (``cell_1.U_11, cell_1.U_21, cell_1.W_01, cell_1.bias,
     cell_2.U_11, cell_2.W_01, cell_2.bias``): its state_dict loads.
@@ -629,13 +659,13 @@ class HMLSTM(nn.Module):
     hmrnn.py:53,121-122, so its ``HMRNN.adjust_param`` -- which adds to ``HM_LSTM.a`` only -- never reaches them; here the
     one attribute is what both cells use.)"""
     native_train_default = False   # what ``native=None`` picks when a gradient is required: the loop, until DESIGN 7.4's timing shows the native path ahead
+    _lib = 'dsp_hmlstm'
 
     def __init__(self, a, input_size, size_list):
         super().__init__()
         self.a, self.input_size, self.size_list = float(a), int(input_size), [int(v) for v in size_list]
         self.cell_1 = _HMCell(self.input_size, self.size_list[0], self.size_list[1], False)
         self.cell_2 = _HMCell(self.size_list[0], self.size_list[1], None, True)
-        self._handle, self._handle_key = None, None
 
     # ---- native path ------------------------------------------------------------------------------------------------
     def _params(self):
@@ -656,38 +686,14 @@ class HMLSTM(nn.Module):
             return f'{nat.LIB_PATH} is not built'
         return None
 
-    def _drop_handle(self):
-        if self._handle is not None:
-            from . import _native as nat
-            try:
-                nat.load().dsp_hmlstm_destroy(self._handle)
-            except Exception:
-                pass
-            self._handle, self._handle_key = None, None
-
-    def __del__(self):
-        self._drop_handle()
-
-    def __getstate__(self):
-        """Copies (copy.deepcopy, pickling) do not share the native handle: each builds its own on first use."""
-        d = self.__dict__.copy()
-        d['_handle'], d['_handle_key'] = None, None
-        return d
+    def _descriptor(self, nat):
+        return nat.HmlstmDesc(self.input_size, self.size_list[0], self.size_list[1], 0, *[p.data_ptr() for p in self._params()])
 
     def _native_handle(self, dev):
-        """The packed copy of the parameters; rebuilt when one of them moved or was written (data_ptr / _version)."""
-        from . import _native as nat
-        ps = [p.detach() for p in self._params()]
-        if any(not p.is_contiguous() for p in ps):
+        if any(not p.is_contiguous() for p in self._params()):
+            from . import _native as nat
             raise nat.DspError('HMLSTM: parameters must be contiguous')
-        key = (dev.index,) + tuple((p.data_ptr(), p._version) for p in self._params())
-        if self._handle is None or key != self._handle_key:
-            self._drop_handle()
-            d = nat.HmlstmDesc(self.input_size, self.size_list[0], self.size_list[1], 0, *[p.data_ptr() for p in ps])
-            h = nat.c_vp(0)
-            nat.check(nat.load().dsp_hmlstm_create(nat.C.byref(d), nat.C.byref(h)))
-            self._handle, self._handle_key = h.value, key
-        return self._handle
+        return super()._native_handle(dev)
 
     def _run_native(self, x, hidden, lens, want_seq=True):
         from . import _native as nat
@@ -698,10 +704,7 @@ class HMLSTM(nn.Module):
         with torch.cuda.device(dev):
             handle = self._native_handle(dev)
             f32 = dict(dtype=torch.float32, device=dev)
-            state_in = None
-            if hidden is not None:
-                state_in = torch.cat([v.detach().to(**f32).reshape(-1) for v in hidden])
-                assert state_in.numel() == (2 * H1 + 2 * H2 + 2) * B, 'hidden does not fit (h1, c1, z1, h2, c2, z2) of this batch'
+            state_in = None if hidden is None else _pack_state(hidden, H1, H2, B, **f32)
             state_out = torch.empty((2 * H1 + 2 * H2 + 2) * B, **f32)
             h_1 = torch.empty(B, T, H1, **f32) if want_seq else None
             h_2 = torch.empty(B, T, H2, **f32) if want_seq else None
@@ -710,15 +713,12 @@ class HMLSTM(nn.Module):
             z_hat = torch.empty(T, 2, B, **f32)
             d_len = last = None
             if lens is not None:
-                d_len = torch.as_tensor(np.asarray(lens.cpu() if torch.is_tensor(lens) else lens), dtype=torch.int32).to(dev)
+                d_len = torch.as_tensor(_lengths(lens), dtype=torch.int32).to(dev)
                 last = torch.empty(B, H2, **f32)
-            ptr = lambda t: None if t is None else t.data_ptr()
-            nat.check(nat.load().dsp_hmlstm_forward(handle, x.data_ptr(), T, B, float(self.a), ptr(d_len), ptr(state_in),
-                                                    state_out.data_ptr(), ptr(h_1), ptr(h_2), ptr(z_1), ptr(z_2), z_hat.data_ptr(),
-                                                    ptr(last), torch.cuda.current_stream(dev).cuda_stream))
-        sizes = [H1 * B, H1 * B, B, H2 * B, H2 * B, B]
-        parts = torch.split(state_out, sizes)
-        hid = (parts[0].view(H1, B), parts[1].view(H1, B), parts[2].view(1, B), parts[3].view(H2, B), parts[4].view(H2, B), parts[5].view(1, B))
+            nat.check(nat.load().dsp_hmlstm_forward(handle, x.data_ptr(), T, B, float(self.a), _ptr(d_len), _ptr(state_in),
+                                                    state_out.data_ptr(), _ptr(h_1), _ptr(h_2), _ptr(z_1), _ptr(z_2), z_hat.data_ptr(),
+                                                    _ptr(last), torch.cuda.current_stream(dev).cuda_stream))
+        hid = _split_state(state_out, H1, H2, B)
         zf = lambda z: None if z is None else z.to(torch.float32).unsqueeze(2)
         return HMLSTMResult(h_1=h_1, h_2=h_2, z_1=zf(z_1), z_2=zf(z_2), hidden=hid, z_hat=z_hat, last_h2=last)
 
@@ -730,18 +730,13 @@ class HMLSTM(nn.Module):
         with torch.cuda.device(dev):
             self._native_handle(dev)
             f32 = dict(dtype=torch.float32, device=dev)
-            state_in = None
-            if hidden is not None:
-                state_in = torch.cat([v.detach().to(**f32).reshape(-1) for v in hidden])
-                assert state_in.numel() == (2 * H1 + 2 * H2 + 2) * B, 'hidden does not fit (h1, c1, z1, h2, c2, z2) of this batch'
+            state_in = None if hidden is None else _pack_state(hidden, H1, H2, B, **f32)
             if lens is not None:
-                d_len = torch.as_tensor(np.asarray(lens.cpu() if torch.is_tensor(lens) else lens), dtype=torch.int32).to(dev)
+                d_len = torch.as_tensor(_lengths(lens), dtype=torch.int32).to(dev)
             else:
                 d_len = torch.full((B,), T, dtype=torch.int32, device=dev)
             h_1, h_2, last, z_1, z_2, z_hat, state_out = _HMLSTMTrain.apply(self, float(self.a), d_len, state_in, x, *self._params())
-        sizes = [H1 * B, H1 * B, B, H2 * B, H2 * B, B]
-        parts = torch.split(state_out, sizes)
-        hid = (parts[0].view(H1, B), parts[1].view(H1, B), parts[2].view(1, B), parts[3].view(H2, B), parts[4].view(H2, B), parts[5].view(1, B))
+        hid = _split_state(state_out, H1, H2, B)
         zf = lambda z: z.to(torch.float32).unsqueeze(2)
         return HMLSTMResult(h_1=h_1, h_2=h_2, z_1=zf(z_1), z_2=zf(z_2), hidden=hid, z_hat=z_hat, last_h2=last if lens is not None else None)
 
@@ -764,7 +759,7 @@ class HMLSTM(nn.Module):
         h_2 = torch.stack(hs2, dim=1)
         last = None
         if lens is not None:
-            idx = torch.as_tensor(np.asarray(lens.cpu() if torch.is_tensor(lens) else lens), dtype=torch.int64).clamp(1, T) - 1
+            idx = torch.as_tensor(_lengths(lens)).clamp(1, T) - 1
             last = h_2[torch.arange(B, device=x.device), idx.to(x.device)]
         return HMLSTMResult(h_1=torch.stack(hs1, dim=1), h_2=h_2, z_1=torch.stack(zs1, dim=1), z_2=torch.stack(zs2, dim=1),
                             hidden=(h1, c1, z1, h2, c2, z2), z_hat=torch.stack(zh).detach(), last_h2=last)
@@ -806,7 +801,7 @@ class HMRNNHead(nn.Module):
         self.out = nn.Linear(600, 20)
 
     def forward(self, inp, len0, dropout=True, native=None, native_enc=None):
-        len0 = np.asarray(len0.cpu() if torch.is_tensor(len0) else len0)
+        len0 = _lengths(len0)
         enc = self.enc1(inp, len0, native=native_enc)                                                    # [max(len0), B, 200]
         if dropout:
             enc = torch.nn.functional.dropout(enc, 0.2)

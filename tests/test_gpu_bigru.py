@@ -288,6 +288,34 @@ def test_handle_follows_the_parameters():
         assert torch.equal(enc(x, lens, native=True), y2)
 
 
+def test_a_copy_owns_its_handle():
+    """copy.deepcopy leaves the native handle behind: the copy builds its own on first use, and deleting the copy destroys
+    that one alone -- the original keeps its handle and its results."""
+    import gc
+    import torch
+    from features.classifier import _DynEnc, fill_parameters
+    dev = _dev()
+    torch.manual_seed(0)
+    enc = _DynEnc(5, 4, 2).eval()
+    fill_parameters(enc, 11)
+    enc = enc.to(dev)
+    x, lens = _x(3, 3, 5, 12, dev), np.array([3, 1, 2])
+    with torch.no_grad():
+        y1, hn1 = enc.run(x, lens, native=True)
+        h1 = enc._handle
+        assert h1 is not None
+        twin = copy.deepcopy(enc)
+        assert twin._handle is None
+        y2, hn2 = twin.run(x, lens, native=True)
+        assert twin._handle not in (None, h1)
+        assert _np(y2).tobytes() == _np(y1).tobytes() and _np(hn2).tobytes() == _np(hn1).tobytes()
+        del twin
+        gc.collect()
+        y3, hn3 = enc.run(x, lens, native=True)
+    assert enc._handle == h1
+    assert _np(y3).tobytes() == _np(y1).tobytes() and _np(hn3).tobytes() == _np(hn1).tobytes()
+
+
 def test_graph_capture_and_replay_equals_the_eager_call(g):
     import torch
     from features import _native as nat

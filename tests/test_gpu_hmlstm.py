@@ -281,6 +281,34 @@ def test_handle_follows_the_parameters(g):
     assert m.run(xt).h_2.requires_grad
 
 
+def test_a_copy_owns_its_handle():
+    """copy.deepcopy leaves the native handle behind: the copy builds its own on first use, and deleting the copy destroys
+    that one alone -- the original keeps its handle and its results."""
+    import copy
+    import gc
+    import torch
+    dev = _dev()
+    m = _module(4, (4, 8), 13, dev)
+    x = torch.from_numpy(np.random.default_rng(14).standard_normal((3, 3, 4)).astype(np.float32)).to(dev)
+    lens = np.array([3, 1, 2])
+    fields = ('h_1', 'h_2', 'z_1', 'z_2', 'z_hat', 'last_h2')
+    bits = lambda r: [_np(getattr(r, k)).tobytes() for k in fields] + [_np(v).tobytes() for v in r.hidden]
+    with torch.no_grad():
+        r1 = bits(m.run(x, lens=lens, native=True))
+        h1 = m._handle
+        assert h1 is not None
+        twin = copy.deepcopy(m)
+        assert twin._handle is None
+        r2 = bits(twin.run(x, lens=lens, native=True))
+        assert twin._handle not in (None, h1)
+        assert r2 == r1
+        del twin
+        gc.collect()
+        r3 = bits(m.run(x, lens=lens, native=True))
+    assert m._handle == h1
+    assert r3 == r1
+
+
 def test_head_on_the_device_against_the_reference(g):
     """rnn_clf.HMRNN's fixture at the ROCm bar of the other heads.  The GRU in front runs through MIOpen: its deviation from
     the CPU reaches the boundary inputs, so the z_hat deviation of the whole head is measured and recorded on its own."""

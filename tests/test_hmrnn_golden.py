@@ -194,3 +194,30 @@ def test_create_refuses_unsupported_sizes_without_a_device(sizes):
     assert lib.dsp_hmlstm_create(C.byref(d), C.byref(h)) == nat.EINVAL
     assert lib.dsp_hmlstm_forward(None, None, 1, 1, 1.0, *([None] * 10)) == nat.EINVAL
     assert lib.dsp_hmlstm_destroy(None) == nat.OK
+
+
+def test_flat_state_helpers_round_trip_in_the_documented_order():
+    """_pack_state lays ``hidden`` out as h1 | c1 | z1 | h2 | c2 | z2 and _split_state hands the same six tensors back."""
+    import torch
+    from features.classifier import _pack_state, _split_state
+    H1, H2, B = 4, 8, 3
+    rng = np.random.default_rng(3)
+    hidden = tuple(torch.from_numpy(rng.standard_normal((n, B)).astype(np.float32)) for n in (H1, H1, 1, H2, H2, 1))
+    flat = _pack_state(hidden, H1, H2, B, dtype=torch.float32)
+    assert flat.shape == ((2 * H1 + 2 * H2 + 2) * B,)
+    assert torch.equal(flat, torch.cat([v.reshape(-1) for v in hidden]))        # the documented order, each part row-major [rows, B]
+    back = _split_state(flat, H1, H2, B)
+    assert len(back) == 6
+    for got, want in zip(back, hidden):
+        assert got.shape == want.shape and torch.equal(got, want)
+    with pytest.raises(AssertionError, match='hidden does not fit'):
+        _pack_state(hidden[:5], H1, H2, B, dtype=torch.float32)
+
+
+def test_lengths_helper_takes_lists_arrays_and_tensors():
+    import torch
+    from features.classifier import _lengths
+    want = np.array([5, 1, 3], dtype=np.int64)
+    for given in ([5, 1, 3], np.array([5, 1, 3], dtype=np.int32), torch.tensor([5, 1, 3]), torch.tensor([5, 1, 3], dtype=torch.int32)):
+        got = _lengths(given)
+        assert isinstance(got, np.ndarray) and got.dtype == np.int64 and np.array_equal(got, want)

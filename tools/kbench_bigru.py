@@ -11,6 +11,10 @@ and RNNHead and HMRNNHead at B = 512 with the native encoder and without it.
         # the training step: forward_train, the backward recurrence per layer, the GEMMs and the whole autograd step, native
         # against the nn.GRU path (39 -> 200, 2 and 3 layers, B 8 / 64 / 512, full and ragged); HMRNNHead and RNNHead training
         # steps at B 512, everything native against everything default; and dsp_bigru_forward against a build of the parent commit
+    python tools/kbench_bigru.py --ab PARENT_LIB [--out FILE.json]
+        # same-speed check against a build of the parent commit: dsp_bigru_forward, dsp_bigru_forward_train and dsp_bigru_backward
+        # per layer (2 and 3 layers, B 512), each library in fresh processes, order parent, this tree, parent, this tree, ...;
+        # the parent's processes form two series, whose difference is the bar
 
 Times are device-event times around calls on one stream, median over the rounds (min and max are kept beside it); every
 shape is warmed up first.  A direction of a layer multiplies 3 H (in + H) weights per column and step (in = 39, then 2 H).
@@ -48,24 +52,44 @@ def ragged_lengths(rng, B, T):
 
 
 def forward_rounds(rounds):
-    """Child process of --train's guard: dsp_bigru_forward (2 layers, B 512, full lengths) of the library DSP_FRONTEND_LIB names."""
+    """Child process of --train's guard and of --ab: the timed calls of the library DSP_FRONTEND_LIB names at 39 -> 200, B 512,
+    T 200, full lengths -> {call: the rounds' times}; 'forward' is dsp_bigru_forward with 2 layers."""
     import ctypes
     from features import _native as nat
     from features.classifier import _DynEnc, fill_parameters
     probe = ctypes.CDLL(nat.LIB_PATH)
-    for name in [n for n in nat.SIGNATURES if not hasattr(probe, name)]:     # a build of an older commit: the forward needs none of them
+    for name in [n for n in nat.SIGNATURES if not hasattr(probe, n)]:     # a build of an older commit: these calls need none of them
         del nat.SIGNATURES[name]
-    dev = torch.device('cuda', 0)
-    torch.manual_seed(0)
-    enc = _DynEnc(39, 200, 2).eval()
-    fill_parameters(enc, 1)
-    enc = enc.to(dev)
-    x = torch.from_numpy(np.random.default_rng(2).standard_normal((200, 512, 39)).astype(np.float32)).to(dev)
-    lens = np.full(512, 200)
-    with torch.no_grad():
-        enc.run(x, lens, native=True)
-        torch.cuda.synchronize()
-        print(json.dumps([_time(lambda: enc.run(x, lens, native=True), 5) for _ in range(rounds)]))
+    lib, dev = nat.load(), torch.device('cuda', 0)
+    I, H, T, B = 39, 200, 200, 512
+    rng = np.random.default_rng(2)
+    new = lambda *s: torch.from_numpy(rng.standard_normal(s).astype(np.float32)).to(dev)
+    x, lens = new(T, B, I), np.full(B, T)
+    d_len = torch.from_numpy(lens.astype(np.int32)).to(dev)
+    st = lambda: torch.cuda.current_stream(dev).cuda_stream
+    out = {}
+    for L in (2, 3):
+        torch.manual_seed(0)
+        enc = _DynEnc(I, H, L).eval()
+        fill_parameters(enc, 1)
+        enc = enc.to(dev)
+        handle, n = enc._native_handle(dev), nat.c_i64(0)
+        nat.check(lib.dsp_bigru_tape_bytes(handle, T, B, nat.C.byref(n)))
+        tape, y, hn, da = torch.empty(n.value // 4, device=dev), torch.empty(T, B, H, device=dev), torch.empty(2 * L, B, H, device=dev), torch.empty(T, B, 2, 4 * H, device=dev)
+        gs, g_hn = [new(T, B, 2 * H) for _ in range(L - 1)] + [new(T, B, H)], new(2 * L, B, H)
+        runs = {'forward' if L == 2 else f'forward_layers{L}': lambda: enc.run(x, lens, native=True),
+                f'forward_train_layers{L}': lambda: nat.check(lib.dsp_bigru_forward_train(handle, x.data_ptr(), T, B, d_len.data_ptr(), None, y.data_ptr(),
+                                                                                          hn.data_ptr(), tape.data_ptr(), n.value, st()))}
+        for l in range(L):
+            runs[f'backward_layers{L}_layer{l}'] = lambda l=l: nat.check(lib.dsp_bigru_backward(
+                handle, l, T, B, d_len.data_ptr(), tape.data_ptr(), n.value, gs[l].data_ptr(), g_hn[2 * l:].data_ptr(), da.data_ptr(), st()))
+        with torch.no_grad():
+            for f in runs.values():
+                f()
+            torch.cuda.synchronize()
+            for k, f in runs.items():
+                out[k] = [_time(f, 5) for _ in range(rounds)]
+    print(json.dumps(out))
 
 
 def _forward_ms_in_child(lib_path, rounds):
@@ -74,6 +98,30 @@ def _forward_ms_in_child(lib_path, rounds):
     out = subprocess.run([sys.executable, os.path.abspath(__file__), '--forward-rounds', str(rounds)], env=env, check=True,
                          capture_output=True, text=True, timeout=300).stdout
     return json.loads(out.strip().splitlines()[-1])
+
+
+def ab(args, child=_forward_ms_in_child):
+    """--ab: this process opens no GPU; four fresh processes per library, alternating, the parent's as two series (its 1st and
+    3rd, its 2nd and 4th process).  Per call: the three medians, the bar |parent A - parent B| and whether this tree's median
+    is within the bar of the parent's (the median of both series)."""
+    from features import _native as nat
+    runs = {'parent_a': {}, 'this_tree': {}, 'parent_b': {}}
+    for i in range(4):
+        for side, lib in (('parent_a' if i % 2 == 0 else 'parent_b', os.path.abspath(args.ab)), ('this_tree', nat.LIB_PATH)):
+            for k, v in child(lib, args.rounds).items():
+                runs[side].setdefault(k, []).extend(v)
+    med = lambda v: sorted(v)[len(v) // 2]
+    res = {}
+    print(f"{'call':34s} {'parent A':>9s} {'parent B':>9s} {'parent':>9s} {'this tree':>9s} {'b - p':>8s} {'bar':>7s}  verdict (ms, medians)")
+    for k in runs['this_tree']:
+        a, b2, t = med(runs['parent_a'][k]), med(runs['parent_b'][k]), med(runs['this_tree'][k])
+        p = med(runs['parent_a'][k] + runs['parent_b'][k])
+        r = res[k] = {'parent_a_ms': a, 'parent_b_ms': b2, 'parent_ms': p, 'this_tree_ms': t, 'bar_ms': abs(a - b2), 'inside': t - p <= abs(a - b2)}
+        print(f"{k:34s} {a:9.4f} {b2:9.4f} {p:9.4f} {t:9.4f} {t - p:+8.4f} {r['bar_ms']:7.4f}  {'inside' if r['inside'] else 'BEYOND'}", flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as fh:
+            json.dump(res, fh, indent=1)
 
 
 def train(args):
@@ -185,8 +233,8 @@ def train(args):
         torch.cuda.empty_cache()
         t_par, t_new = [], []
         for _ in range(2):                                                    # alternating processes
-            t_par += _forward_ms_in_child(os.path.abspath(args.parent_lib), args.rounds)
-            t_new += _forward_ms_in_child(nat.LIB_PATH, args.rounds)
+            t_par += _forward_ms_in_child(os.path.abspath(args.parent_lib), args.rounds)['forward']
+            t_new += _forward_ms_in_child(nat.LIB_PATH, args.rounds)['forward']
         g = {'layers': 2, 'B': 512, 'parent': _stats(t_par), 'this_tree': _stats(t_new)}
         g['parent_spread_ms'] = g['parent']['max_ms'] - g['parent']['min_ms']
         g['difference_ms'] = g['this_tree']['median_ms'] - g['parent']['median_ms']
@@ -205,10 +253,13 @@ def main():
     ap.add_argument('--layers', type=int, default=2)
     ap.add_argument('--train', action='store_true')
     ap.add_argument('--parent-lib', default=None, help='with --train: a build of the parent commit, for the forward guard')
+    ap.add_argument('--ab', default=None, metavar='PARENT_LIB', help='same-speed check against a build of the parent commit')
     ap.add_argument('--forward-rounds', type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.forward_rounds:
         return forward_rounds(args.forward_rounds)
+    if args.ab:
+        return ab(args)
     if args.train:
         return train(args)
     from features.classifier import _DynEnc, HMRNNHead, RNNHead, fill_parameters

@@ -10,6 +10,9 @@ launch) against the torch step loop on the same device in the same process, alte
                                                         # the training step: native forward_train / backward / GEMMs
                                                         # against the torch loop, the head, and the guard on the plain forward
     python tools/kbench_hmlstm.py --scan-train-seeds    # CPU only: the seeds of tests/test_gpu_hmlstm_train.py
+    python tools/kbench_hmlstm.py --ab PARENT_LIB [--out FILE.json]
+                                                        # same-speed check against a build of the parent commit (kbench_bigru.py's
+                                                        # --ab): forward, forward_train, backward and the HMRNN head at B 512
 
 Times are device-event times around calls on one stream, median over the rounds (min and max are kept beside it); every
 shape is warmed up first.  The operation count is 2 (4H+1) (I + H2 + H1 + H1 + H2) per column and step.
@@ -20,7 +23,7 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, 'dsp-speech-recognition_amd'), os.path.join(ROOT, 'tests')):
+for p in (ROOT, os.path.join(ROOT, 'dsp-speech-recognition_amd'), os.path.join(ROOT, 'tests'), os.path.join(ROOT, 'tools')):
     sys.path.insert(0, p)
 import numpy as np
 import torch
@@ -87,7 +90,7 @@ def scan_train_seeds():
 
 
 def _forward_ms_in_child(lib, rounds):
-    """dsp_hmlstm_forward at B 512 in a fresh process on the given library -> the rounds' times (this process keeps its own)."""
+    """The timed calls at B 512 in a fresh process on the given library -> {call: the rounds' times} (this process keeps its own)."""
     import subprocess
     env = dict(os.environ, DSP_FRONTEND_LIB=lib)
     out = subprocess.run([sys.executable, os.path.abspath(__file__), '--forward-rounds', str(rounds)], env=env, check=True,
@@ -96,22 +99,61 @@ def _forward_ms_in_child(lib, rounds):
 
 
 def forward_rounds(rounds):
+    """Child process of --train's guard and of --ab: 'forward' is dsp_hmlstm_forward through HMLSTM.run; forward_train and
+    backward are the raw calls; the HMRNN head (native GRU encoder and HM-LSTM) forward and training step."""
     import ctypes
     from features import _native as nat
-    from features.classifier import HMLSTM, fill_parameters
+    from features.classifier import HMLSTM, HMRNNHead, fill_parameters
     probe = ctypes.CDLL(nat.LIB_PATH)
-    for name in [n for n in nat.SIGNATURES if not hasattr(probe, name)]:     # a build of an older commit: the forward needs none of them
+    for name in [n for n in nat.SIGNATURES if not hasattr(probe, n)]:     # a build of an older commit: these calls need none of them
         del nat.SIGNATURES[name]
-    dev = torch.device('cuda', 0)
+    lib, dev = nat.load(), torch.device('cuda', 0)
+    I, H1, H2, T, B = 200, 200, 200, 200, 512
     torch.manual_seed(0)
-    m = HMLSTM(1.0, 200, [200, 200]).eval()
+    m = HMLSTM(1.0, I, [H1, H2]).eval()
     fill_parameters(m, 1)
     m = m.to(dev)
-    x = torch.from_numpy(np.random.default_rng(2).standard_normal((200, 512, 200)).astype(np.float32)).to(dev)
-    with torch.no_grad():
-        m.run(x, native=True)
-        torch.cuda.synchronize()
-        print(json.dumps([_time(lambda: m.run(x, native=True), 5) for _ in range(rounds)]))
+    rng = np.random.default_rng(2)
+    new = lambda *s: torch.from_numpy(rng.standard_normal(s).astype(np.float32)).to(dev)
+    x, g1, g2, gl = new(T, B, I), new(B, T, H1), new(B, T, H2), new(B, H2)
+    lens = torch.full((B,), T, dtype=torch.int32, device=dev)
+    handle, n = m._native_handle(dev), nat.c_i64(0)
+    nat.check(lib.dsp_hmlstm_tape_bytes(handle, T, B, nat.C.byref(n)))
+    f32 = dict(dtype=torch.float32, device=dev)
+    tape, h1, h2 = torch.empty(n.value // 4, **f32), torch.empty(B, T, H1, **f32), torch.empty(B, T, H2, **f32)
+    z1, z2 = torch.empty(B, T, dtype=torch.uint8, device=dev), torch.empty(B, T, dtype=torch.uint8, device=dev)
+    zhat, last, state = torch.empty(T, 2, B, **f32), torch.empty(B, H2, **f32), torch.empty((2 * H1 + 2 * H2 + 2) * B, **f32)
+    d1, d2 = torch.empty(T, B, 4 * H1 + 1, **f32), torch.empty(T, B, 4 * H2 + 1, **f32)
+    st = lambda: torch.cuda.current_stream(dev).cuda_stream
+    inp, wl = new(T, B, 39), new(B, 20)
+    len0 = rng.integers(20, T + 1, B)
+    len0[0] = T
+    torch.manual_seed(0)
+    hm = HMRNNHead().to(dev)
+
+    def head_forward():
+        with torch.no_grad():
+            hm(inp, len0, dropout=True, native=True, native_enc=True)
+
+    def head_step():
+        (hm(inp, len0, dropout=True, native=True, native_enc=True)[0] * wl).sum().backward()
+        hm.zero_grad(set_to_none=True)
+
+    def forward():
+        with torch.no_grad():
+            m.run(x, native=True)
+    runs = {'forward': forward,
+            'forward_train': lambda: nat.check(lib.dsp_hmlstm_forward_train(handle, x.data_ptr(), T, B, 1.0, lens.data_ptr(), None, state.data_ptr(),
+                                                                            h1.data_ptr(), h2.data_ptr(), z1.data_ptr(), z2.data_ptr(), zhat.data_ptr(),
+                                                                            last.data_ptr(), tape.data_ptr(), n.value, st())),
+            'backward': lambda: nat.check(lib.dsp_hmlstm_backward(handle, T, B, 1.0, lens.data_ptr(), None, tape.data_ptr(), n.value, h1.data_ptr(),
+                                                                  h2.data_ptr(), z1.data_ptr(), z2.data_ptr(), g1.data_ptr(), g2.data_ptr(),
+                                                                  gl.data_ptr(), d1.data_ptr(), d2.data_ptr(), st())),
+            'HMRNNHead_forward_all_native': head_forward, 'HMRNNHead_train_step_all_native': head_step}
+    for f in runs.values():
+        f()
+    torch.cuda.synchronize()
+    print(json.dumps({k: [_time(f, 5) for _ in range(rounds)] for k, f in runs.items()}))
 
 
 def train(args):
@@ -210,8 +252,8 @@ def train(args):
         torch.cuda.empty_cache()
         t_par, t_new = [], []
         for _ in range(2):                                                    # alternating processes
-            t_par += _forward_ms_in_child(os.path.abspath(args.parent_lib), args.rounds)
-            t_new += _forward_ms_in_child(nat.LIB_PATH, args.rounds)
+            t_par += _forward_ms_in_child(os.path.abspath(args.parent_lib), args.rounds)['forward']
+            t_new += _forward_ms_in_child(nat.LIB_PATH, args.rounds)['forward']
         g = {'B': 512, 'parent': _stats(t_par), 'this_tree': _stats(t_new)}
         # the margin: the parent's own min-max spread of rounds as profiles/hmlstm_kbench.json records it (this job's is kept beside it)
         with open(os.path.join(ROOT, 'profiles', 'hmlstm_kbench.json')) as fh:
@@ -234,10 +276,14 @@ def main():
     ap.add_argument('--scan-train-seeds', action='store_true')
     ap.add_argument('--train', action='store_true')
     ap.add_argument('--parent-lib', default=None, help='with --train: a build of the parent commit, for the forward guard')
+    ap.add_argument('--ab', default=None, metavar='PARENT_LIB', help='same-speed check against a build of the parent commit')
     ap.add_argument('--forward-rounds', type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.forward_rounds:
         return forward_rounds(args.forward_rounds)
+    if args.ab:
+        import kbench_bigru
+        return kbench_bigru.ab(args, _forward_ms_in_child)
     if args.scan_seeds:
         return scan_seeds()
     if args.scan_train_seeds:
