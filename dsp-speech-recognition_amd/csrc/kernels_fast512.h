@@ -62,6 +62,7 @@ struct Fast512Plan {
     F512Params P;
     int variant;           // which <NROWS, NI> instantiation serves this plan
     int caps;              // ... and which compile-time mel block table (0: counts from P.nb4)
+    int layout;            // ... and which compile-time plan layout (0: every field from P), see F512Tag
 };
 
 template <int CTRL>
@@ -89,6 +90,51 @@ __host__ __device__ constexpr int f512_cap_prefix(int caps, int i) {
     for (int k = 0; k < i; ++k) s += f512_cap(caps, k);
     return s;
 }
+
+// Where the tables sit in the blob (float offsets) and how many 16-byte vectors a wave stages: THE definition, used by
+// fast512_plan_init for every plan and, at compile time, by the kernel instantiations of the two standard plans below.
+// row_blocks: 16-byte blocks per lane row of mel weights (sum of the iterations' block counts).
+struct F512Layout {
+    int32_t tab_floats, off_tw1, off_dct, off_melw, off_mels, off_bias, off_coop, melw_row, span_vec;
+};
+__host__ __device__ constexpr int f512_pad64(int n) { return (n + 63) / 64 * 64; }
+__host__ __device__ constexpr F512Layout f512_layout(int nrows, int ni, int row_blocks, int S) {
+    F512Layout k = {};
+    k.melw_row = row_blocks > 0 ? 4 * row_blocks : 4;
+    if (((k.melw_row / 4) & 1) == 0) k.melw_row += 4;   // odd number of 16-byte slots per row
+    k.off_tw1 = 512;                                     // after the window
+    k.off_dct = k.off_tw1 + 15 * 8 * 4;
+    k.off_melw = f512_pad64(k.off_dct + (ni + 1) / 2 * 8 * 20);
+    k.off_mels = k.off_melw + 8 * k.melw_row;
+    k.off_bias = k.off_mels + ni * 8;
+    k.off_coop = (k.off_bias + 16 + 3) / 4 * 4;
+    k.tab_floats = f512_pad64(k.off_coop + 8 * 16);
+    // the wave stages every sample its pass-1 rows will touch: 16 x NROWS per frame (the window is zero beyond L)
+    k.span_vec = (7 * S + 16 * nrows + 3) / 4;
+    return k;
+}
+// Flat grouping: frames of a group's second utterance sit this many floats further into the LDS image.
+__host__ __device__ constexpr int f512_seam(int nrows, int S) { return (16 * nrows - S + 3) / 4 * 4; }
+
+// Compile-time plan layouts (template parameter LAYOUT of the kernel).  The layout fields of F512Params never change for
+// a plan and are the same for every caller of the two standard plans; as kernel arguments they occupy scalar registers
+// (the fused instantiation spilled 18 of them, read back with v_readlane inside the loop) and keep the store predicates
+// and address strides from folding.  Under a tag the kernel takes them as constants instead:
+//   0: every field from P (any plan)
+//   1: the metric plan            -- 16 kHz, 25 ms / 10 ms, 40 filters, 13 coefficients, appendEnergy
+//   2: the reference's defaults   -- the same with 26 filters
+// What a tag fixes: S, L, M, C, append_energy, seam_off, every F512Layout field, and `flat` where the host always sets it
+// (the fused-delta instantiations).  preemph, fd_inv_den, the magic divisors, the batch geometry and all pointers stay
+// run-time.  A plan takes a tag only if f512_view leaves every one of those fields as it found it (f512_view_is_identity).
+struct F512Tag { int nrows, ni, caps, S, L, M, C, append_energy; };
+__host__ __device__ constexpr F512Tag f512_tag(int layout) {
+    return layout == 1 ? F512Tag{25, 5, 1, 160, 400, 40, 13, 1} : F512Tag{25, 4, 2, 160, 400, 26, 13, 1};
+}
+__host__ __device__ constexpr F512Layout f512_tag_layout(int layout) {
+    const F512Tag t = f512_tag(layout);
+    return f512_layout(t.nrows, t.ni, f512_cap_prefix(t.caps, t.ni), t.S);
+}
+
 template <int I, int N, typename F>
 __device__ __forceinline__ void f512_static_for(F&& f) {
     if constexpr (I < N) {
@@ -246,6 +292,35 @@ __device__ __forceinline__ int f512_div(int x, uint32_t magic, uint32_t shift) {
     return (int)(((uint64_t)(uint32_t)x * magic) >> shift);
 }
 
+// The parameters as an instantiation reads them: under a tag, the layout fields are that tag's constants (nothing of P
+// survives for them, so the kernel cannot mix the two).  FLAT: the host sets P.flat on every launch of this instantiation.
+template <int LAYOUT, int NROWS, int NI, int CAPS, bool FLAT>
+__host__ __device__ __forceinline__ F512Params f512_view(F512Params P) {
+    if constexpr (LAYOUT != 0) {
+        constexpr F512Tag t = f512_tag(LAYOUT);
+        static_assert(t.nrows == NROWS && t.ni == NI && t.caps == CAPS, "a layout tag belongs to one <NROWS, NI, CAPS>");
+        constexpr F512Layout k = f512_tag_layout(LAYOUT);
+        P.S = t.S; P.L = t.L; P.M = t.M; P.C = t.C; P.append_energy = t.append_energy;
+        P.tab_floats = k.tab_floats; P.off_tw1 = k.off_tw1; P.off_dct = k.off_dct; P.off_melw = k.off_melw;
+        P.off_mels = k.off_mels; P.off_bias = k.off_bias; P.off_coop = k.off_coop;
+        P.melw_row = k.melw_row; P.span_vec = k.span_vec;
+        P.seam_off = f512_seam(NROWS, t.S);
+        if constexpr (FLAT) P.flat = 1;
+    }
+    return P;
+}
+// Does the tag describe these parameters?  EVERY field f512_view overwrites is compared.  (seam_off is read by the kernel
+// for flat grouping only and left 0 by the host otherwise; the fused form always groups flat.)
+template <int LAYOUT, int NROWS, int NI, int CAPS, bool FLAT>
+static inline bool f512_view_is_identity(const F512Params& P) {
+    const F512Params Q = f512_view<LAYOUT, NROWS, NI, CAPS, FLAT>(P);
+    return Q.S == P.S && Q.L == P.L && Q.M == P.M && Q.C == P.C && Q.append_energy == P.append_energy &&
+           Q.tab_floats == P.tab_floats && Q.off_tw1 == P.off_tw1 && Q.off_dct == P.off_dct && Q.off_melw == P.off_melw &&
+           Q.off_mels == P.off_mels && Q.off_bias == P.off_bias && Q.off_coop == P.off_coop &&
+           Q.melw_row == P.melw_row && Q.span_vec == P.span_vec &&
+           ((!FLAT && !P.flat) || Q.seam_off == P.seam_off) && Q.flat == P.flat;
+}
+
 // Where a frame group lives (all wave-uniform).
 struct F512Group {
     int utt, t0, T, nsamp;
@@ -341,11 +416,14 @@ __device__ __forceinline__ F512Group f512_locate_frame(const F512Params& P, cons
 //     workgroup also emits its own first rows.
 //   * With 8 S = 256 (NSTAGE - 1) samples (S = 160, six staging rounds) the last staged vector of a group is round 0 of
 //     the run's next group: the wave carries it over instead of fetching it again.
-template <int NROWS, int NI, int CAPS, int NSTAGE, int DTYPE, int WAVES, bool RAGGED, int FD = 0>
-__global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_kernel(F512Params P, BatchGeom bg,
+//
+// LAYOUT: compile-time plan layout (F512Tag); 0 reads every field from the arguments.
+template <int NROWS, int NI, int CAPS, int NSTAGE, int DTYPE, int WAVES, bool RAGGED, int FD = 0, int LAYOUT = 0>
+__global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_kernel(F512Params Parg, BatchGeom bg,
                                                              const void* __restrict__ wave,
                                                              float* __restrict__ out, int64_t ld_out) {
     static_assert(!(FD != 0 && RAGGED), "the fused-delta run structure (carried staging vector, halo barrier) serves dense batches only");
+    const F512Params P = f512_view<LAYOUT, NROWS, NI, CAPS, FD != 0>(Parg);   // the ONE view of the parameters below
     extern __shared__ __attribute__((aligned(256))) float smem_f[];
     float* const smem = smem_f;
     const int tid = threadIdx.x;
@@ -359,7 +437,11 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
     // launch every wave of the chip asks for its first 6 KB at once, a 25 MB burst.
     // (Inline asm for the table loads: the compiler would otherwise sink them below the touches and wait for everything.
     // Older than every load the compiler issues afterwards, they never make its own vmcnt waits too short.)
-    constexpr int TABV = 3;
+    // (Under a layout tag the table size is a constant: only the loads that carry table data are issued.  A load whose
+    // data no thread copies would leave its destination register dead in the compiler's eyes -- and reused -- while the
+    // load is still in flight.)
+    constexpr int TABV_TAG = LAYOUT != 0 ? (f512_tag_layout(LAYOUT).tab_floats + 64 * WAVES * 4 - 1) / (64 * WAVES * 4) : 3;
+    constexpr int TABV = TABV_TAG < 3 ? TABV_TAG : 3;
     typedef float f512_v4 __attribute__((ext_vector_type(4)));
     f512_v4 tabv_[TABV];
 #pragma unroll
@@ -1240,7 +1322,7 @@ static inline int fast512_plan_init(dsp_plan* p, const dsp_plan_desc* d, const i
     int variant, NI;  // template instantiation: <NROWS, NI, CAPS>
     // The wave stages every sample its pass-1 rows will touch (16 x NROWS per frame, window zero beyond
     // L), so no multiply ever sees stale LDS.  +1 vector: ragged batches stage from an aligned start.
-    const int span25 = 7 * d->frame_step + 400, span32 = 7 * d->frame_step + 512;
+    const int span25 = 7 * d->frame_step + 400;
     const int nstage = ((span25 + 3) / 4 + 1 + 63) / 64;
     if (nrows <= 25 && ni_real <= 4 && nstage <= 6) { variant = 0; NI = 4; }
     else if (nrows <= 25 && ni_real <= 5 && nstage <= 6) { variant = 1; NI = 5; }
@@ -1340,8 +1422,8 @@ static inline int fast512_plan_init(dsp_plan* p, const dsp_plan_desc* d, const i
         if (caps != 0) fp->P.nb4[i] = f512_cap(caps, i);
         row_blocks += fp->P.nb4[i];
     }
-    int melw_row = row_blocks > 0 ? 4 * row_blocks : 4;
-    if (((melw_row / 4) & 1) == 0) melw_row += 4;  // odd number of 16-byte slots per row
+    const F512Layout lay = f512_layout(variant == 2 ? 32 : 25, NI, row_blocks, d->frame_step);
+    const int melw_row = lay.melw_row;
     std::vector<float> melw((size_t)8 * melw_row, 0.f), mels((size_t)NI * 8, 0.f);
     for (int c = 0; c < 8; ++c) {
         int pos = 0;
@@ -1363,11 +1445,14 @@ static inline int fast512_plan_init(dsp_plan* p, const dsp_plan_desc* d, const i
             pos += len;
         }
     }
-    auto pad64 = [](size_t n) { return (n + 63) / 64 * 64; };
-    const size_t o_tw1 = 512, o_dct = o_tw1 + tw1.size(), o_melw = pad64(o_dct + dct.size());
-    const size_t o_mels = o_melw + melw.size(), o_bias = o_mels + mels.size();
-    const size_t o_coop = (o_bias + bias.size() + 3) / 4 * 4;
-    const size_t total = pad64(o_coop + coop.size());
+    const size_t o_tw1 = lay.off_tw1, o_dct = lay.off_dct, o_melw = lay.off_melw, o_mels = lay.off_mels;
+    const size_t o_bias = lay.off_bias, o_coop = lay.off_coop, total = lay.tab_floats;
+    // f512_layout packs the tables back to back: every table ends where the next one starts
+    if (o_tw1 + tw1.size() != o_dct || o_dct + dct.size() > o_melw || o_melw + melw.size() != o_mels ||
+        o_mels + mels.size() != o_bias || o_bias + bias.size() > o_coop || o_coop + coop.size() > total) {
+        delete fp;
+        return DSP_EINVAL;
+    }
     std::vector<float> blob(total, 0.f);
     memcpy(blob.data(), win.data(), 512 * 4);
     memcpy(blob.data() + o_tw1, tw1.data(), tw1.size() * 4);
@@ -1389,9 +1474,13 @@ static inline int fast512_plan_init(dsp_plan* p, const dsp_plan_desc* d, const i
     fp->P.L = L; fp->P.S = d->frame_step; fp->P.M = M; fp->P.C = C;
     fp->P.append_energy = d->append_energy ? 1 : 0;
     fp->P.preemph = d->preemph;
-    fp->P.span_vec = ((variant == 2 ? span32 : span25) + 3) / 4;
+    fp->P.span_vec = lay.span_vec;
     fp->variant = variant;
     fp->caps = caps;
+    // a standard plan runs the instantiations that hold its layout as constants: only if every such field agrees
+    fp->layout = 0;
+    if (variant == 1 && caps == 1 && f512_view_is_identity<1, 25, 5, 1, false>(fp->P)) fp->layout = 1;
+    if (variant == 0 && caps == 2 && f512_view_is_identity<2, 25, 4, 2, false>(fp->P)) fp->layout = 2;
     p->d_fast = fp;
     return DSP_OK;
 }
@@ -1405,7 +1494,7 @@ static inline void fast512_plan_free(dsp_plan* p) {
 }
 
 // (which batches the kernel can read: fast512_applicable, dsp_frontend.hip)
-template <int NROWS, int NI, int CAPS, int NSTAGE, int DTYPE, bool RAGGED>
+template <int NROWS, int NI, int CAPS, int NSTAGE, int DTYPE, bool RAGGED, int LAYOUT = 0>
 static int fast512_launch_k(const F512Params& P, const void* d_wave, const BatchGeom& bg, float* d_out,
                             int64_t ld_out, int64_t groups_bound, hipStream_t st) {
     const size_t lds = ((size_t)P.tab_floats + (size_t)F512_WAVES * F512_WAVE_FLOATS) * sizeof(float);
@@ -1413,14 +1502,15 @@ static int fast512_launch_k(const F512Params& P, const void* d_wave, const Batch
     const int64_t cap = (int64_t)dsp_cu_count() * (16 / F512_WAVES);  // CUs x resident workgroups (<= 16 waves per CU)
     int64_t blocks = (groups_bound + F512_WAVES - 1) / F512_WAVES;
     if (blocks > cap) blocks = cap;       // every CU fully occupied; the partial last round is dealt wave-major
-    auto k = mfcc512_kernel<NROWS, NI, CAPS, NSTAGE, DTYPE, F512_WAVES, RAGGED>;
+    auto k = mfcc512_kernel<NROWS, NI, CAPS, NSTAGE, DTYPE, F512_WAVES, RAGGED, 0, LAYOUT>;
     static size_t granted[DSP_MAX_DEVICES] = {};  // dynamic-LDS limit already raised, per device
     if (dsp_ensure_dynamic_lds((const void*)k, lds, granted) != 0) return DSP_EHIP;
     k<<<(int)blocks, 64 * F512_WAVES, lds, st>>>(P, bg, d_wave, d_out, ld_out);
     return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
 }
 
-template <int NROWS, int NI, int CAPS, int NSTAGE>
+// LAYOUT: the plan's tag (Fast512Plan::layout).  Dense batches run the tagged instantiation; ragged ones stay on tag 0.
+template <int NROWS, int NI, int CAPS, int NSTAGE, int LAYOUT = 0>
 static int fast512_launch_t(F512Params P, const void* d_wave, int dtype, const BatchGeom& bg, float* d_out,
                             int64_t ld_out, hipStream_t st, const DspRaggedTables* pre = nullptr) {
     if (bg.uniform_samples > 0) {
@@ -1433,13 +1523,19 @@ static int fast512_launch_t(F512Params P, const void* d_wave, int dtype, const B
         // (5 % idle slots).  Needs vector-aligned hops and room for the seam's second segment in the wave buffer.
         // (the seam is as long as the samples pass 1 READS per frame, 16 x NROWS >= L: a frame's rows beyond L meet a
         // zero window, but 0 x NaN of the next utterance's samples would still poison the frame)
-        const int seam = (16 * NROWS - P.S + 3) / 4 * 4;
+        const int seam = f512_seam(NROWS, P.S);
         if ((P.S % 4) == 0 && P.L > P.S && 16 * NROWS > P.S && bg.uniform_frames >= 8 && (bg.uniform_frames % 8) != 0 &&
             7 * P.S + 16 * NROWS + seam + 4 <= F512_WAVE_FLOATS && 7 * P.S + 16 * NROWS + seam <= 256 * (NSTAGE + 1) &&
             bg.total_frames + 8 <= 0x3fffffff) {
             P.flat = 1;
             P.seam_off = seam;
             P.total_groups = (bg.total_frames + 7) / 8;
+        }
+        if constexpr (LAYOUT != 0) {
+            if (f512_view_is_identity<LAYOUT, NROWS, NI, CAPS, false>(P))   // with seam_off as set above
+                return dsp_dispatch_wave(dtype, [&](auto dt) {
+                    return fast512_launch_k<NROWS, NI, CAPS, NSTAGE, decltype(dt)::value, false, LAYOUT>(P, d_wave, bg, d_out, ld_out, P.total_groups, st);
+                });
         }
         return dsp_dispatch_wave(dtype, [&](auto dt) {
             return fast512_launch_k<NROWS, NI, CAPS, NSTAGE, decltype(dt)::value, false>(P, d_wave, bg, d_out, ld_out, P.total_groups, st);
@@ -1458,6 +1554,8 @@ static inline int fast512_launch(const dsp_plan* p, const void* d_wave, int dtyp
                                  float* d_out, int64_t ld_out, hipStream_t st, const DspRaggedTables* pre = nullptr) {
     const Fast512Plan* fp = static_cast<const Fast512Plan*>(p->d_fast);
     // exact instantiations for the common shapes, a padded catch-all otherwise (chosen at plan init)
+    if (fp->layout == 1) return fast512_launch_t<25, 5, 1, 6, 1>(fp->P, d_wave, dtype, bg, d_out, ld_out, st, pre);
+    if (fp->layout == 2) return fast512_launch_t<25, 4, 2, 6, 2>(fp->P, d_wave, dtype, bg, d_out, ld_out, st, pre);
     if (fp->variant == 0 && fp->caps == 2) return fast512_launch_t<25, 4, 2, 6>(fp->P, d_wave, dtype, bg, d_out, ld_out, st, pre);
     if (fp->variant == 0) return fast512_launch_t<25, 4, 0, 6>(fp->P, d_wave, dtype, bg, d_out, ld_out, st, pre);
     if (fp->variant == 1 && fp->caps == 1) return fast512_launch_t<25, 5, 1, 6>(fp->P, d_wave, dtype, bg, d_out, ld_out, st, pre);
@@ -1470,7 +1568,7 @@ static inline int fast512_launch(const dsp_plan* p, const void* d_wave, int dtyp
 // ------------------------------------------------------------------------------------------------
 #define F512_FD_HALO_FLOATS (F512_WAVES * 8 * 14)
 
-template <int NROWS, int NI, int CAPS, int NSTAGE>
+template <int NROWS, int NI, int CAPS, int NSTAGE, int LAYOUT = 0>
 static int fast512_launch_fused_t(F512Params P, const void* d_wave, int dtype, const BatchGeom& bg, int delta_n,
                                   float* d_out, hipStream_t st) {
     const int64_t T = bg.uniform_frames;
@@ -1479,7 +1577,7 @@ static int fast512_launch_fused_t(F512Params P, const void* d_wave, int dtype, c
     // most one utterance boundary; the delta window reaches 2 N <= 4 frames back
     if (delta_n < 1 || delta_n > 2 || P.C > 14 || T < 8 * F512_WAVES - 7 || bg.n_utt < blocks) return 1;
     if ((P.S % 4) != 0 || P.L <= P.S || 16 * NROWS <= P.S) return 1;
-    const int seam = (16 * NROWS - P.S + 3) / 4 * 4;
+    const int seam = f512_seam(NROWS, P.S);
     if (7 * P.S + 16 * NROWS + seam + 4 > F512_WAVE_FLOATS || 7 * P.S + 16 * NROWS + seam > 256 * (NSTAGE + 1)) return 1;
     if (bg.total_frames + T + 16 > 0x3fffffff) return 1;
     P.flat = 1;
@@ -1494,12 +1592,18 @@ static int fast512_launch_fused_t(F512Params P, const void* d_wave, int dtype, c
     if (lds > 80 * 1024) return 1;   // two workgroups per CU
     const int64_t ld = 3 * (int64_t)P.C;
     const int nblk = (int)blocks;
-#define F512_FD_LAUNCH(DT, FDN)                                                                          \
+#define F512_FD_LAUNCH_L(DT, FDN, LAY)                                                                   \
     do {                                                                                                 \
-        auto k = mfcc512_kernel<NROWS, NI, CAPS, NSTAGE, DT, F512_WAVES, false, FDN>;                    \
+        auto k = mfcc512_kernel<NROWS, NI, CAPS, NSTAGE, DT, F512_WAVES, false, FDN, LAY>;               \
         static size_t granted[DSP_MAX_DEVICES] = {};                                                     \
         if (dsp_ensure_dynamic_lds((const void*)k, lds, granted) != 0) return DSP_EHIP;                  \
         k<<<nblk, 64 * F512_WAVES, lds, st>>>(P, bg, d_wave, d_out, ld);                                 \
+    } while (0)
+    // the tagged instantiation only if the tag still describes P with the launch-time fields (flat, seam_off) set
+    const bool tagged = LAYOUT != 0 && f512_view_is_identity<LAYOUT, NROWS, NI, CAPS, true>(P);
+#define F512_FD_LAUNCH(DT, FDN)                                                                          \
+    do {                                                                                                 \
+        if (tagged) F512_FD_LAUNCH_L(DT, FDN, LAYOUT); else F512_FD_LAUNCH_L(DT, FDN, 0);                \
     } while (0)
     if (dtype == DSP_WAVE_I16) {
         if (delta_n == 1) F512_FD_LAUNCH(DSP_WAVE_I16, 1); else F512_FD_LAUNCH(DSP_WAVE_I16, 2);
@@ -1507,6 +1611,7 @@ static int fast512_launch_fused_t(F512Params P, const void* d_wave, int dtype, c
         if (delta_n == 1) F512_FD_LAUNCH(DSP_WAVE_F32, 1); else F512_FD_LAUNCH(DSP_WAVE_F32, 2);
     }
 #undef F512_FD_LAUNCH
+#undef F512_FD_LAUNCH_L
     return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
 }
 
@@ -1516,6 +1621,8 @@ static inline int fast512_launch_fused(const dsp_plan* p, const void* d_wave, in
                                        float* d_out, hipStream_t st) {
     if (bg.uniform_samples <= 0) return 1;
     const Fast512Plan* fp = static_cast<const Fast512Plan*>(p->d_fast);
+    if (fp->layout == 1) return fast512_launch_fused_t<25, 5, 1, 6, 1>(fp->P, d_wave, dtype, bg, delta_n, d_out, st);
+    if (fp->layout == 2) return fast512_launch_fused_t<25, 4, 2, 6, 2>(fp->P, d_wave, dtype, bg, delta_n, d_out, st);
     if (fp->variant == 0 && fp->caps == 2) return fast512_launch_fused_t<25, 4, 2, 6>(fp->P, d_wave, dtype, bg, delta_n, d_out, st);
     if (fp->variant == 0) return fast512_launch_fused_t<25, 4, 0, 6>(fp->P, d_wave, dtype, bg, delta_n, d_out, st);
     if (fp->variant == 1 && fp->caps == 1) return fast512_launch_fused_t<25, 5, 1, 6>(fp->P, d_wave, dtype, bg, delta_n, d_out, st);
