@@ -1,4 +1,4 @@
-// Host-side plumbing shared by the translation units of libdsp_frontend.so (dsp_frontend.hip, dsp_rnn.hip).
+// Host-side plumbing shared by the translation units of libdsp_frontend.so (dsp_frontend.hip, dsp_rnn.hip, dsp_ensemble.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

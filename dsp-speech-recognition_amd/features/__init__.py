@@ -8,7 +8,8 @@ hand-written HIP kernels (gfx950) behind a ctypes C ABI (include/dsp_frontend.h)
 
 Unlike the reference's ``features/__init__.py`` this import has no side effects (no ./log/
 directory, no matplotlib / sklearn import).  Both pitch trackers (``pitch_detect_sr``, ``pitch_detect``) and
-``pitch_feature`` are here; the SVM half of the reference's pitch module is not.
+``pitch_feature`` are here, and ``features.ensemble`` evaluates the fitted pitch SVM and the ensemble's confidence gate
+(pitch_model.py:54-61, ensemble.py:44-67) on the device; fitting the SVM stays with sklearn.
 There is no CPU fallback: without the built library or without a GPU every compute call raises.
 """
 from .base import *  # noqa: F401,F403
@@ -19,6 +20,7 @@ from .pitch import (center_clip, max_pitch, pitch_detect_frame_sr, pitch_detect_
                     robust_max_pitch, smooth, window, pitch_detect, pitch_detect_frame, peak_score,
                     sub_endpoint_detect, find_smooth_subsequence, slope, quad_params, peakshift, pitch_feature,
                     pitch_feature_batch, pitch_features_device)
-from . import base, sigproc, endpoint, preprocess, pitch, batch, pipeline  # noqa: F401
+from . import base, sigproc, endpoint, preprocess, pitch, batch, pipeline, ensemble  # noqa: F401
 from .batch import FeaturePlan, EndpointPlan  # noqa: F401
 from .pipeline import VadMfccPipeline  # noqa: F401
+from .ensemble import PitchSVM, EnsembleBatch, ensemble_decide  # noqa: F401

@@ -46,6 +46,18 @@ class BigruDesc(C.Structure):
     ]
 
 
+class SvmDesc(C.Structure):
+    _fields_ = [
+        ('n_features', c_i32), ('n_sv', c_i32), ('class0', c_i32), ('class1', c_i32),
+        ('gamma', c_f64), ('intercept', c_f64),
+        ('h_center', c_vp), ('h_scale', c_vp), ('h_sv', c_vp), ('h_dual', c_vp),
+    ]
+
+
+class EnsembleRule(C.Structure):
+    _fields_ = [('label_a', c_i32), ('label_b', c_i32), ('threshold', c_f64), ('svm', c_vp)]
+
+
 # name -> (restype, argtypes); mirrors include/dsp_frontend.h one to one.
 SIGNATURES = {
     'dsp_abi_version': (C.c_int, []),
@@ -122,6 +134,12 @@ SIGNATURES = {
     'dsp_bigru_tape_rows': (C.c_int, [c_vp, c_i32, c_i32, c_i32, C.POINTER(c_i64)]),
     'dsp_bigru_forward_train': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'dsp_bigru_backward': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    'dsp_svm_create': (C.c_int, [C.POINTER(SvmDesc), C.POINTER(c_vp)]),
+    'dsp_svm_destroy': (C.c_int, [c_vp]),
+    'dsp_svm_decision_batch': (C.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    'dsp_ensemble_decide_batch': (C.c_int, [c_vp, c_i64, c_i32, c_i32, C.POINTER(EnsembleRule), c_i32, c_vp, c_i64, c_vp, c_i64,
+                                            c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'dsp_trim_preemph_batch': (C.c_int, [c_vp, C.c_int, c_vp, c_vp, c_vp, c_i32, c_f64, c_vp, c_vp]),
 }
 
 _lib = None

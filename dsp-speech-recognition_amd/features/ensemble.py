@@ -1,0 +1,305 @@
+"""The reference's ensemble (ensemble.py:44-67) on the device: the classifier answers first, and where it predicts one of a
+tone-confusable pair of words with too little confidence, an RBF support-vector machine on the clip's five pitch features
+decides instead (pitch_model.py:54-61).
+
+* ``PitchSVM`` holds one fitted ``RobustScaler`` + ``SVC(kernel='rbf')`` pair as plain arrays (``from_sklearn`` reads the
+  fitted objects' public attributes; nothing here imports the library that fitted them) and evaluates it with
+  ``dsp_svm_decision_batch``.
+* ``ensemble_decide`` is the gate: softmax, arg-max, the rules and the SVMs in one launch (``dsp_ensemble_decide_batch``).
+* ``EnsembleBatch`` runs the whole path for a batch of raw clips -- endpointing and the classifier's features
+  (``ModelFeatureBatch``), the classifier head, the pre-emphasised trimmed copy (``dsp_trim_preemph_batch``), the pitch
+  features (``pitch_features_device``) and the gate -- on torch's current stream; no clip, logit or feature visits the host.
+
+Training stays where it was: fit the scaler and the SVM with scikit-learn, then ``PitchSVM.from_sklearn(scaler, clf)``.
+"""
+from __future__ import annotations
+
+import types
+
+import numpy as np
+
+from . import _native as nat
+from .batch import _is_device_tensor, _stream_ptr, _wave_dtype_of
+
+MAX_FEATURES, MAX_SV, MAX_RULES = 16, 65536, 4
+REFERENCE_RULES = (((0, 1), 0.8), ((6, 7), 0.7))          # ensemble.py:50-53: (label pair, confidence threshold)
+
+
+def _torch_stream(dev):
+    import torch
+    return _stream_ptr(torch.cuda.current_stream(dev))
+
+
+class PitchSVM:
+    """A fitted scaler + two-class RBF SVM:  dec(x) = sum_i dual[i] exp(-gamma |(x - center) / scale - sv[i]|^2) + intercept,
+    predict = classes[dec > 0].  The native handle is built on first use on the current device and freed with the object."""
+
+    def __init__(self, support_vectors, dual_coef, intercept, gamma, classes, scale=None, center=None):
+        sv = np.ascontiguousarray(support_vectors, dtype=np.float64)
+        if sv.ndim != 2:
+            raise ValueError('support_vectors must be [n_sv, n_features]')
+        self.support_vectors = sv
+        self.dual_coef = np.ascontiguousarray(dual_coef, dtype=np.float64).reshape(-1)
+        if len(self.dual_coef) != len(sv):
+            raise ValueError(f'{len(self.dual_coef)} dual coefficients for {len(sv)} support vectors')
+        self.intercept = float(np.asarray(intercept, dtype=np.float64).reshape(-1)[0])
+        self.gamma = float(gamma)
+        cls = np.asarray(classes).reshape(-1)
+        if len(cls) != 2:
+            raise ValueError(f'a two-class model is needed, got classes {cls.tolist()}')
+        self.classes = (int(cls[0]), int(cls[1]))
+        F = sv.shape[1]
+        self.scale = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(-1)
+        self.center = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(-1)
+        for name, v in (('scale', self.scale), ('center', self.center)):
+            if v is not None and len(v) != F:
+                raise ValueError(f'{name} has {len(v)} entries for {F} features')
+        self._handle, self._handle_dev = None, None
+
+    # ---- construction --------------------------------------------------------------------------------------------
+    @classmethod
+    def from_arrays(cls, support_vectors, dual_coef, intercept, gamma, classes, scale=None, center=None):
+        return cls(support_vectors, dual_coef, intercept, gamma, classes, scale=scale, center=center)
+
+    @classmethod
+    def from_sklearn(cls, scaler, clf):
+        """From a fitted ``RobustScaler`` (or None) and a fitted two-class ``SVC(kernel='rbf')``: attributes only
+        (``scale_``, ``center_``, ``support_vectors_``, ``dual_coef_``, ``intercept_``, ``_gamma``, ``classes_``)."""
+        kernel = getattr(clf, 'kernel', None)
+        if kernel != 'rbf':
+            raise ValueError(f'only RBF kernels are served on the device, got kernel={kernel!r}')
+        classes = np.asarray(clf.classes_).reshape(-1)
+        dual = np.asarray(clf.dual_coef_, dtype=np.float64)
+        if len(classes) != 2 or dual.ndim != 2 or dual.shape[0] != 1:
+            raise ValueError(f'a two-class model is needed, got classes {classes.tolist()}')
+        gamma = getattr(clf, '_gamma', None)          # the resolved number; clf.gamma may be the string 'scale'
+        if gamma is None:
+            raise ValueError('the classifier has no resolved _gamma: is it fitted?')
+        scale = getattr(scaler, 'scale_', None) if scaler is not None else None
+        center = getattr(scaler, 'center_', None) if scaler is not None else None
+        return cls(clf.support_vectors_, dual[0], np.asarray(clf.intercept_).reshape(-1)[0], float(gamma), classes,
+                   scale=scale, center=center)
+
+    def save(self, path):
+        """The arrays as an .npz file (``load`` reads it back)."""
+        extra = {k: v for k, v in (('scale', self.scale), ('center', self.center)) if v is not None}
+        with open(path, 'wb') as f:
+            np.savez(f, support_vectors=self.support_vectors, dual_coef=self.dual_coef, intercept=np.float64(self.intercept),
+                     gamma=np.float64(self.gamma), classes=np.array(self.classes, dtype=np.int64), **extra)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(z['support_vectors'], z['dual_coef'], z['intercept'], float(z['gamma']), z['classes'],
+                       scale=z['scale'] if 'scale' in z.files else None, center=z['center'] if 'center' in z.files else None)
+
+    # ---- the native handle ---------------------------------------------------------------------------------------
+    @property
+    def n_features(self):
+        return self.support_vectors.shape[1]
+
+    @property
+    def n_sv(self):
+        return self.support_vectors.shape[0]
+
+    def descriptor(self):
+        """The dsp_svm_desc of these arrays (it points into them: keep the object alive while it is used)."""
+        d = nat.SvmDesc()
+        d.n_features, d.n_sv = self.n_features, self.n_sv
+        d.class0, d.class1 = self.classes
+        d.gamma, d.intercept = self.gamma, self.intercept
+        d.h_center = None if self.center is None else self.center.ctypes.data
+        d.h_scale = None if self.scale is None else self.scale.ctypes.data
+        d.h_sv, d.h_dual = self.support_vectors.ctypes.data, self.dual_coef.ctypes.data
+        return d
+
+    def handle(self):
+        dev = nat.current_device()
+        if self._handle is None or self._handle_dev != dev:
+            self._drop_handle()
+            d, h = self.descriptor(), nat.c_vp(0)
+            rc = nat.load().dsp_svm_create(nat.C.byref(d), nat.C.byref(h))
+            if rc == nat.EINVAL:
+                msg = nat.load().dsp_last_error()
+                raise ValueError(msg.decode() if msg else 'invalid model')
+            nat.check(rc)
+            self._handle, self._handle_dev = h.value, dev
+        return self._handle
+
+    def _drop_handle(self):
+        if getattr(self, '_handle', None) is not None:
+            try:                                    # (at interpreter shutdown even the import may fail)
+                nat.load().dsp_svm_destroy(self._handle)
+            except Exception:
+                pass
+            self._handle, self._handle_dev = None, None
+
+    __del__ = _drop_handle
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d['_handle'], d['_handle_dev'] = None, None      # a copy builds its own handle
+        return d
+
+    # ---- evaluation ----------------------------------------------------------------------------------------------
+    def _run(self, X, want_label):
+        """-> (decision, label) as device tensors (input: device tensor) or host arrays (anything else)."""
+        import torch
+        nat.require_device()
+        on_device = _is_device_tensor(X)
+        dev = X.device if on_device else torch.device('cuda', nat.current_device())
+        if on_device:
+            if X.dtype != torch.float64:
+                raise TypeError(f'features on the device must be float64, got {X.dtype}')
+            x = X
+        else:
+            x = torch.from_numpy(np.ascontiguousarray(np.asarray(X, dtype=np.float64))).to(dev)
+        if x.dim() == 1:
+            x = x.reshape(1, -1)
+        if x.dim() != 2 or x.shape[1] < self.n_features:
+            raise ValueError(f'features must be [n, >= {self.n_features}], got {tuple(x.shape)}')
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        n = x.shape[0]
+        dec = torch.empty(n, dtype=torch.float64, device=dev)
+        lab = torch.empty(n, dtype=torch.int32, device=dev) if want_label else None
+        if n:
+            nat.check(nat.load().dsp_svm_decision_batch(self.handle(), x.data_ptr(), x.stride(0), n, dec.data_ptr(),
+                                                        lab.data_ptr() if want_label else None, _torch_stream(dev)))
+        if on_device:
+            return dec, lab
+        return dec.cpu().numpy(), (lab.cpu().numpy() if want_label else None)
+
+    def decision_function(self, X):
+        """SVC.decision_function(scaler.transform(X)): fp64 [n]; a device tensor in gives a device tensor out."""
+        return self._run(X, False)[0]
+
+    def predict(self, X):
+        """SVC.predict(scaler.transform(X)): int32 [n] labels."""
+        return self._run(X, True)[1]
+
+
+def _as_rules(rules):
+    """((label_a, label_b), threshold, PitchSVM) triples -> (ctypes array or None, n); keeps nothing alive itself."""
+    rules = list(rules)
+    if len(rules) > MAX_RULES:
+        raise ValueError(f'at most {MAX_RULES} rules, got {len(rules)}')
+    if not rules:
+        return None, 0
+    arr = (nat.EnsembleRule * len(rules))()
+    for k, (labels, threshold, svm) in enumerate(rules):
+        arr[k].label_a, arr[k].label_b = (int(v) for v in labels)
+        arr[k].threshold = float(threshold)
+        arr[k].svm = svm.handle()
+    return arr, len(rules)
+
+
+def ensemble_decide(logits, rules, feat=None, valid=None, stream=None):
+    """model.py:156-157 + ensemble.py:49-53 for a batch, one launch.
+
+    ``logits``: [B, C] fp32 device tensor (2 <= C <= 64, finite).  ``rules``: up to four ``((label_a, label_b), threshold,
+    PitchSVM)``; a rule fires for a clip whose arg-max is one of its labels with softmax probability below the threshold.
+    ``feat``: [B, >= F] fp64 device tensor (row stride free) or None without rules; ``valid``: int32 device tensor, one flag
+    per clip (any stride, e.g. ``aux[:, 8]``), or None.  Returns device tensors (pred int32 [B], prob fp32 [B, C], used
+    int32 [B]: 0 = no rule, r + 1 = rule r's SVM decided, -(r + 1) = rule r fired on invalid features and the classifier's
+    label stands, decision fp64 [B]: the SVM's value where one was evaluated, else 0)."""
+    import torch
+    if not _is_device_tensor(logits) or logits.dtype != torch.float32 or logits.dim() != 2:
+        raise TypeError('logits must be a [B, C] float32 device tensor')
+    dev = logits.device
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    B, C = logits.shape
+    arr, n_rules = _as_rules(rules)
+    p_feat, ld_feat, p_valid, ld_valid = None, 0, None, 0
+    if n_rules:
+        if feat is None or not _is_device_tensor(feat) or feat.dtype != torch.float64 or feat.dim() != 2 or feat.shape[0] != B:
+            raise TypeError('feat must be a [B, F] float64 device tensor')
+        if feat.stride(1) != 1:
+            feat = feat.contiguous()
+        p_feat, ld_feat = feat.data_ptr(), feat.stride(0)
+        if valid is not None:
+            if not _is_device_tensor(valid) or valid.dtype != torch.int32 or valid.dim() != 1 or valid.shape[0] != B:
+                raise TypeError('valid must be a [B] int32 device tensor')
+            if B > 1 and valid.stride(0) < 1:
+                valid = valid.contiguous()
+            p_valid, ld_valid = valid.data_ptr(), max(int(valid.stride(0)), 1)
+    pred = torch.empty(B, dtype=torch.int32, device=dev)
+    prob = torch.empty((B, C), dtype=torch.float32, device=dev)
+    used = torch.empty(B, dtype=torch.int32, device=dev)
+    dec = torch.empty(B, dtype=torch.float64, device=dev)
+    st = _torch_stream(dev) if stream is None else _stream_ptr(stream)
+    rc = nat.load().dsp_ensemble_decide_batch(logits.data_ptr(), logits.stride(0), B, C, arr, n_rules, p_feat, ld_feat, p_valid,
+                                              ld_valid, pred.data_ptr(), prob.data_ptr(), used.data_ptr(), dec.data_ptr(), st)
+    if rc == nat.EINVAL:
+        msg = nat.load().dsp_last_error()
+        raise ValueError(msg.decode() if msg else 'invalid argument')
+    nat.check(rc)
+    return pred, prob, used, dec
+
+
+class EnsembleBatch:
+    """ensemble.EnsembleModel.test's loop body (ensemble.py:48-53) for a batch of raw clips, device-resident.
+
+    ``head``: any callable ``head(inp, len0, **kwargs)`` returning the logits [B, C] first (``HMRNNHead``; the caller passes
+    ``dropout=False`` and the like through ``run``).  ``rules``: ``((label_a, label_b), threshold, PitchSVM)`` triples, e.g.
+    built from ``REFERENCE_RULES``."""
+
+    def __init__(self, rate, head, rules, frame=0.03, step=0.01, coeff=0.97):
+        from .model_glue import ModelFeatureBatch
+        self.rate, self.head, self.rules, self.coeff = rate, head, list(rules), float(coeff)
+        self.features = ModelFeatureBatch(rate, frame=frame, step=step)
+        self._layouts = {}
+
+    def _layout(self, so):
+        """The pipeline layout of this batch shape, owned by this object: its d_seg / d_dst_off stay valid after
+        ModelFeatureBatch.run returns (a few shapes are kept, the most recently used last)."""
+        key = (nat.current_device(), so.tobytes())
+        lay = self._layouts.pop(key, None)
+        if lay is None:
+            lay = self.features.pipe.prepare(so, 0)
+            while len(self._layouts) >= 4:
+                self._layouts.pop(next(iter(self._layouts)))
+        self._layouts[key] = lay
+        return lay
+
+    def run(self, waves, sample_offsets, **head_kwargs):
+        """``waves``: concatenated clips, a 1-D host array (int16 or float) or device tensor (int16 / float32);
+        ``sample_offsets`` [B + 1].  Returns a namespace of device tensors: pred int32 [B] (the ensemble's labels), prob fp32
+        [B, C], used int32 [B], decision fp64 [B] (see ``ensemble_decide``), logits, feat fp64 [B, 5] and valid int32 [B]
+        (the pitch features), endpoints int64 [B, 2] (host array, samples)."""
+        import torch
+        from .pitch import N_AUX, pitch_features_device
+        nat.require_device()
+        lib = nat.load()
+        so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
+        B = len(so) - 1
+        # ONE contiguous device copy of the clips, held until the call returns: endpointing, the feature kernels and the
+        # pre-emphasised trim all read this buffer
+        if _is_device_tensor(waves):
+            clips = waves.reshape(-1).contiguous()
+        else:
+            host, _ = nat.as_wave(np.asarray(waves).reshape(-1))
+            clips = torch.from_numpy(host).to(torch.device('cuda', nat.current_device()))
+        dev = clips.device
+        dtype = _wave_dtype_of(clips)
+        lay = self._layout(so)
+        inp, len0, endpoints = self.features.run(clips, layout=lay)
+        out = self.head(inp, len0, **head_kwargs)
+        logits = out[0] if isinstance(out, (tuple, list)) else out
+        logits = logits.detach().to(torch.float32)
+        st = _torch_stream(dev)
+        trimmed = torch.empty(max(lay.total_samples, 1), dtype=torch.float32, device=dev)
+        nat.check(lib.dsp_trim_preemph_batch(clips.data_ptr(), dtype, lay.vad.p_sample, lay.d_seg.ptr, lay.d_dst_off.ptr, B,
+                                             self.coeff, trimmed.data_ptr(), st))
+        # the pitch chain's other buffers are library scratch that the next call reuses: the two results this call
+        # returns are torch's
+        feat = torch.empty((B, 5), dtype=torch.float64, device=dev)
+        aux = torch.empty((B, N_AUX), dtype=torch.int32, device=dev)
+        pitch_features_device(trimmed.data_ptr(), lay.d_dst_off.ptr, B, lay.total_samples, self.rate, stream=st,
+                              d_feat=feat.data_ptr(), d_aux=aux.data_ptr())
+        valid = aux[:, N_AUX - 1]
+        pred, prob, used, dec = ensemble_decide(logits, self.rules, feat, valid, stream=st)
+        return types.SimpleNamespace(pred=pred, prob=prob, used=used, decision=dec, logits=logits, feat=feat, valid=valid,
+                                     endpoints=endpoints, inp=inp, len0=len0, _clips=clips, _trimmed=trimmed)
+

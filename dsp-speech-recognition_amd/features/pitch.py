@@ -15,9 +15,12 @@
 ``from features.pitch import *`` also yields what the reference's module re-exports through its own imports and
 ``pitch_model.py`` relies on (``basic_endpoint_detection``, ``preemphasis``, ``to_frames``, ``pickle``, ...).
 
-Out of scope: ``greedy_max_pitch`` and ``dp_max_pitch`` (no caller anywhere), the SVM / ``__main__`` half of the
-reference's module (no sklearn, no matplotlib here), and frame lengths that are not a power of two in [128, 1024] on the
-cepstral path (``winlen = 0.0512`` gives 512, the only size a reference caller uses): those raise ``ValueError``.
+The SVM these features feed (pitch_model.py:54-61) and the ensemble's gate are in ``features/ensemble.py``.
+
+Out of scope: ``greedy_max_pitch`` and ``dp_max_pitch`` (no caller anywhere), the ``__main__`` experiment of the
+reference's module (fitting stays with sklearn; nothing here imports it or matplotlib), and frame lengths that are not a
+power of two in [128, 1024] on the cepstral path (``winlen = 0.0512`` gives 512, the only size a reference caller uses):
+those raise ``ValueError``.
 """
 from __future__ import annotations
 
@@ -208,9 +211,10 @@ def _check(rc):
 
 
 def _cepstrum_chain(p_x, p_so, p_fo, n_utt, frames_bound, L, S, stream=None, clip=True, want_scores=False, flags=3,
-                    tail=True):
+                    tail=True, d_feat=None, d_aux=None):
     """The three launches behind the 10 kHz signal, on library scratch buffers (nothing is allocated once they exist,
-    so the chain can be captured in a graph after one eager call)."""
+    so the chain can be captured in a graph after one eager call).  ``d_feat`` / ``d_aux``: the caller's own device
+    memory ([n_utt, 5] fp64, [n_utt, 9] int32, raw pointers) for the two results instead of scratch."""
     lib = nat.load()
     frames_bound = max(int(frames_bound), 1)
     out = types.SimpleNamespace(scores=None, feat=None, aux=None, seg=None)
@@ -225,8 +229,8 @@ def _cepstrum_chain(p_x, p_so, p_fo, n_utt, frames_bound, L, S, stream=None, cli
                                               out.scores.ptr if want_scores else None, stream))
     if tail:
         out.seg = nat.SCRATCH.get('cep_seg', frames_bound * 8)
-        out.feat = nat.SCRATCH.get('cep_feat', n_utt * 5 * 8)
-        out.aux = nat.SCRATCH.get('cep_aux', n_utt * N_AUX * 4)
+        out.feat = nat.SCRATCH.get('cep_feat', n_utt * 5 * 8) if d_feat is None else types.SimpleNamespace(ptr=int(d_feat))
+        out.aux = nat.SCRATCH.get('cep_aux', n_utt * N_AUX * 4) if d_aux is None else types.SimpleNamespace(ptr=int(d_aux))
         _check(lib.dsp_pitch_feature_batch(out.pitch.ptr, out.amp.ptr, p_fo, n_utt, out.seg.ptr, out.feat.ptr, out.aux.ptr, stream))
     return out
 
@@ -355,17 +359,18 @@ def peakshift(seq1, seq2):
     return np.median(seq2) - np.median(seq1)
 
 
-def pitch_features_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, stream=None, L=512, S=100):
+def pitch_features_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, stream=None, L=512, S=100, d_feat=None, d_aux=None):
     """pitch.pitch_feature for clips that are already on the device (fp32, concatenated, `rate` Hz): decimation to 10 kHz,
     then the three launches of the cepstral path; nothing leaves the device.  `stream` is None, a raw handle or a torch
     stream.  Returns library scratch buffers as attributes: feat [B, 5] fp64, aux [B, 9] int32 (p, p_bias, start1,
-    end1, start2, end2, len1, len2, valid), pitch and seg [one per frame] fp64, frame_off [B + 1] int64."""
+    end1, start2, end2, len1, len2, valid), pitch and seg [one per frame] fp64, frame_off [B + 1] int64.  With ``d_feat`` /
+    ``d_aux`` (raw device pointers) those two results go to the caller's memory, which the next call does not overwrite."""
     stream = _stream_ptr(stream)
     p_x, p_so, d_fo = _to_10k_on_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, L, S, stream)
     # a clip of n samples keeps at most n * 10000 / rate + 2 of them and has at most 2 + kept / S frames
     kept_bound = int(n_samples_bound) if rate <= 10000 else int(n_samples_bound) * 10000 // int(rate) + 2 * n_utt
     frames_bound = kept_bound // int(S) + 2 * n_utt + 1
-    out = _cepstrum_chain(p_x, p_so, d_fo.ptr, n_utt, frames_bound, L, S, stream=stream)
+    out = _cepstrum_chain(p_x, p_so, d_fo.ptr, n_utt, frames_bound, L, S, stream=stream, d_feat=d_feat, d_aux=d_aux)
     out.frame_off = d_fo
     return out
 

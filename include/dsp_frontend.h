@@ -615,6 +615,80 @@ int dsp_bigru_forward_train(const dsp_bigru* h, const float* d_x, int32_t T, int
 int dsp_bigru_backward(const dsp_bigru* h, int32_t layer, int32_t T, int32_t B, const int32_t* d_len, const void* d_tape,
                        int64_t tape_bytes, const float* d_g, const float* d_g_hn, float* d_da, void* stream);
 
+/* ---- the ensemble: pitch SVM and confidence gate (ensemble.EnsembleModel.test ensemble.py:44-67, PitchModel.test_iter pitch_model.py:54-61) ---- */
+/*
+ * A fitted RobustScaler + SVC(kernel='rbf') pair as its public attributes (pitch_model.py:23-24,59-61: scaler.transform, then
+ * clf.predict), two classes.  The desc carries HOST pointers, copied at create (like dsp_plan_desc):
+ *   dec(x) = sum_i h_dual[i] exp(-gamma |(x - h_center) / h_scale - h_sv[i]|^2) + intercept
+ *   label  = class0 where dec <= 0, class1 where dec > 0                       (SVC.classes_[dec > 0])
+ * gamma is the resolved number (SVC._gamma, not the string 'scale').  Sizes out of range, a gamma that is not finite and
+ * positive, a scale that is zero or not finite and any other non-finite number are DSP_EINVAL, checked before any device
+ * call.  Create stores the support vectors transposed and padded to whole wavefronts on the current device (a blocking
+ * copy: it must not run inside a stream capture); the handle is immutable afterwards and may be used from several streams.
+ * Under dsp_debug_host_dry_run(1) the tables stay in host memory: such a handle can only be destroyed, launches are refused.
+ */
+typedef struct dsp_svm dsp_svm;
+typedef struct dsp_svm_desc {
+    int32_t n_features, n_sv;            /* 1..16, 1..65536 */
+    int32_t class0, class1;              /* dec <= 0 -> class0, dec > 0 -> class1 */
+    double gamma, intercept;
+    const double* h_center;              /* [n_features]; NULL = 0 (RobustScaler(with_centering=False)) */
+    const double* h_scale;               /* [n_features]; NULL = 1 */
+    const double* h_sv;                  /* [n_sv, n_features] row-major (SVC.support_vectors_) */
+    const double* h_dual;                /* [n_sv] (SVC.dual_coef_[0]) */
+} dsp_svm_desc;
+int dsp_svm_create(const dsp_svm_desc* desc, dsp_svm** out);
+int dsp_svm_destroy(dsp_svm* svm);
+/*
+ * pitch_model.py:59-61 for a batch: row r of d_feat (fp64, row stride ld_feat >= n_features doubles) -> d_decision[r] (fp64)
+ * and d_label[r] (int32); either may be NULL, not both.  One wavefront per row, everything in fp64 with a true division by the
+ * scale and a fixed summation order: the same arguments give the same bits on every call.  One launch on `stream`, nothing
+ * allocated (capturable).
+ */
+int dsp_svm_decision_batch(const dsp_svm* svm, const double* d_feat, int64_t ld_feat, int32_t n_rows, double* d_decision,
+                           int32_t* d_label, void* stream);
+
+/*
+ * model.py:156-157 and ensemble.py:49-53 for a batch, one launch, one wavefront per clip:
+ *   d_prob[b, :] = softmax(d_logits[b, :])   fp64 arithmetic, max subtracted, rounded to fp32    F.softmax      model.py:156
+ *   pred         = the lowest index among the largest logits                                     torch.max      model.py:157
+ *   the first rule with pred in {label_a, label_b} and (double)d_prob[b, pred] < threshold fires: its SVM (the arithmetic of
+ *   dsp_svm_decision_batch, bit for bit) decides from row b of d_feat                           ensemble.py:50-53
+ * d_logits: [n_utt, n_classes] fp32, row stride ld_logits; the logits are assumed finite (with a NaN the row's outputs are
+ * unspecified).  d_valid: int32, element b * ld_valid says whether row b of d_feat holds features (dsp_pitch_feature_batch's
+ * d_aux[:, 8] with ld_valid = 9); NULL = all valid.  d_feat may be NULL when n_rules = 0.
+ *   d_pred [n_utt]             the final label
+ *   d_prob [n_utt, n_classes]  dense, or NULL
+ *   d_used [n_utt]             0: no rule fired;  r + 1: rule r's SVM decided;  -(r + 1): rule r fired but the features were
+ *                              invalid and the classifier's label stands -- the reference raises there (pitch.pitch_feature
+ *                              on a segment too short to fit)
+ *   d_decision [n_utt]         the SVM's value where one was evaluated, else 0; or NULL
+ * The rules (at most 4) are passed by value into the launch: nothing is uploaded or allocated per call (capturable).
+ * DSP_EINVAL before any device call: sizes out of range, a label >= n_classes, rules whose label sets overlap, SVMs with
+ * different feature counts, ld_feat below that count, a handle of another device or a dry-run one.
+ */
+typedef struct dsp_ensemble_rule {
+    int32_t label_a, label_b;
+    double threshold;
+    const dsp_svm* svm;
+} dsp_ensemble_rule;
+int dsp_ensemble_decide_batch(const float* d_logits, int64_t ld_logits, int32_t n_utt, int32_t n_classes,
+                              const dsp_ensemble_rule* rules, int32_t n_rules, const double* d_feat, int64_t ld_feat,
+                              const int32_t* d_valid, int64_t ld_valid, int32_t* d_pred, float* d_prob, int32_t* d_used,
+                              double* d_decision, void* stream);
+
+/*
+ * pitch_model.py:55-57 without the host: sig = preemphasis(sig, coeff) over the WHOLE clip (preprocess.py:19), then sig[l:r],
+ * as fp32 at d_dst_offsets[b]:
+ *   out[i] = (float)(x[l + i] - coeff * x[l + i - 1]),  and x[0] itself where l + i = 0
+ * so the first kept sample sees the one in front of the segment.  fp64 with the product and the difference rounded
+ * separately, as NumPy does, then one rounding to fp32.  int16 and fp32 input; fp32 samples are promoted to double first,
+ * which is what the reference computes on a float64 array holding the same values.  Tables as dsp_trim_scale_batch
+ * (d_sample_offsets [n_utt + 1], d_segments [n_utt, 2] relative to each clip and clipped to it, d_dst_offsets [n_utt]).
+ */
+int dsp_trim_preemph_batch(const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets, const int64_t* d_segments,
+                           const int64_t* d_dst_offsets, int32_t n_utt, double coeff, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
