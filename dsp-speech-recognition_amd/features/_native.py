@@ -252,6 +252,7 @@ class DeviceBuffer:
     def __init__(self, nbytes):
         require_device()
         self.nbytes = int(nbytes)
+        self.wave = None            # set by VadMfccPipeline.run on a result buffer: the wave buffer it was computed from
         p = c_vp(0)
         check(load().dsp_malloc(C.byref(p), max(self.nbytes, 1)))
         self.ptr = p.value

@@ -37,6 +37,20 @@ def _stream_ptr(stream):
     return int(getattr(stream, 'cuda_stream', stream))
 
 
+def _on_stream(stream, device):
+    """Context in which torch's own work (a ``.contiguous()`` copy, ``torch.empty``) belongs to ``stream`` -- a
+    torch stream or a raw handle -- instead of the current one: a copy made on the current stream is not ordered
+    against a kernel launched on ``stream``, and its block would be the wrong stream's to reuse.  None, or the
+    current stream itself, changes nothing."""
+    import contextlib
+    import torch
+    if stream is None or _stream_ptr(stream) == torch.cuda.current_stream(device).cuda_stream:
+        return contextlib.nullcontext()
+    if not isinstance(stream, torch.cuda.Stream):
+        stream = torch.cuda.ExternalStream(int(stream), device=device)
+    return torch.cuda.stream(stream)
+
+
 class _BatchLayout:
     """Sample/frame offsets of one batch on host and (for ragged batches) on the device."""
 
@@ -161,7 +175,8 @@ class FeaturePlan:
 
     def mfcc_batch(self, waves, sample_offsets=None, delta_n=0, out=None, stream=None, layout=None):
         """waves: [B, N] (uniform) or 1-D concatenation with ``sample_offsets[B+1]``.
-        Returns (features, frame_offsets)."""
+        Returns (features, frame_offsets).  A device tensor may be any view: a non-contiguous one is copied once,
+        on ``stream`` when one is given (where ``out`` is then allocated as well), else on torch's current stream."""
         nat.require_device()
         if layout is None:
             layout = self.layout(waves, sample_offsets)
@@ -169,10 +184,11 @@ class FeaturePlan:
         if _is_device_tensor(waves):
             import torch
             _check_device(waves)
-            if not waves.is_contiguous():
-                waves = waves.contiguous()
-            if out is None:
-                out = torch.empty((layout.total_frames, D), dtype=torch.float32, device=waves.device)
+            with _on_stream(stream, waves.device):     # the copy, `out` and the kernel that touches them: one stream
+                if not waves.is_contiguous():
+                    waves = waves.contiguous()
+                if out is None:
+                    out = torch.empty((layout.total_frames, D), dtype=torch.float32, device=waves.device)
             if stream is None:
                 stream = torch.cuda.current_stream(waves.device)
             self.run_raw(waves.data_ptr(), _wave_dtype_of(waves), layout, out.data_ptr(), delta_n, stream)

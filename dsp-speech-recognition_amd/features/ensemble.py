@@ -19,7 +19,7 @@ import types
 import numpy as np
 
 from . import _native as nat
-from .batch import _is_device_tensor, _stream_ptr, _wave_dtype_of
+from .batch import _is_device_tensor, _on_stream, _stream_ptr, _wave_dtype_of
 
 MAX_FEATURES, MAX_SV, MAX_RULES = 16, 65536, 4
 REFERENCE_RULES = (((0, 1), 0.8), ((6, 7), 0.7))          # ensemble.py:50-53: (label pair, confidence threshold)
@@ -202,32 +202,35 @@ def ensemble_decide(logits, rules, feat=None, valid=None, stream=None):
     ``feat``: [B, >= F] fp64 device tensor (row stride free) or None without rules; ``valid``: int32 device tensor, one flag
     per clip (any stride, e.g. ``aux[:, 8]``), or None.  Returns device tensors (pred int32 [B], prob fp32 [B, C], used
     int32 [B]: 0 = no rule, r + 1 = rule r's SVM decided, -(r + 1) = rule r fired on invalid features and the classifier's
-    label stands, decision fp64 [B]: the SVM's value where one was evaluated, else 0)."""
+    label stands, decision fp64 [B]: the SVM's value where one was evaluated, else 0).  ``stream`` (a torch stream or a raw
+    handle; default torch's current stream) takes the launch, the copy of any input whose inner stride is not 1, and the
+    allocation of the outputs."""
     import torch
     if not _is_device_tensor(logits) or logits.dtype != torch.float32 or logits.dim() != 2:
         raise TypeError('logits must be a [B, C] float32 device tensor')
     dev = logits.device
-    if logits.stride(1) != 1:
-        logits = logits.contiguous()
-    B, C = logits.shape
-    arr, n_rules = _as_rules(rules)
-    p_feat, ld_feat, p_valid, ld_valid = None, 0, None, 0
-    if n_rules:
-        if feat is None or not _is_device_tensor(feat) or feat.dtype != torch.float64 or feat.dim() != 2 or feat.shape[0] != B:
-            raise TypeError('feat must be a [B, F] float64 device tensor')
-        if feat.stride(1) != 1:
-            feat = feat.contiguous()
-        p_feat, ld_feat = feat.data_ptr(), feat.stride(0)
-        if valid is not None:
-            if not _is_device_tensor(valid) or valid.dtype != torch.int32 or valid.dim() != 1 or valid.shape[0] != B:
-                raise TypeError('valid must be a [B] int32 device tensor')
-            if B > 1 and valid.stride(0) < 1:
-                valid = valid.contiguous()
-            p_valid, ld_valid = valid.data_ptr(), max(int(valid.stride(0)), 1)
-    pred = torch.empty(B, dtype=torch.int32, device=dev)
-    prob = torch.empty((B, C), dtype=torch.float32, device=dev)
-    used = torch.empty(B, dtype=torch.int32, device=dev)
-    dec = torch.empty(B, dtype=torch.float64, device=dev)
+    with _on_stream(stream, dev):         # copies of strided inputs and the outputs: made on the stream of the launch
+        if logits.stride(1) != 1:
+            logits = logits.contiguous()
+        B, C = logits.shape
+        arr, n_rules = _as_rules(rules)
+        p_feat, ld_feat, p_valid, ld_valid = None, 0, None, 0
+        if n_rules:
+            if feat is None or not _is_device_tensor(feat) or feat.dtype != torch.float64 or feat.dim() != 2 or feat.shape[0] != B:
+                raise TypeError('feat must be a [B, F] float64 device tensor')
+            if feat.stride(1) != 1:
+                feat = feat.contiguous()
+            p_feat, ld_feat = feat.data_ptr(), feat.stride(0)
+            if valid is not None:
+                if not _is_device_tensor(valid) or valid.dtype != torch.int32 or valid.dim() != 1 or valid.shape[0] != B:
+                    raise TypeError('valid must be a [B] int32 device tensor')
+                if B > 1 and valid.stride(0) < 1:
+                    valid = valid.contiguous()
+                p_valid, ld_valid = valid.data_ptr(), max(int(valid.stride(0)), 1)
+        pred = torch.empty(B, dtype=torch.int32, device=dev)
+        prob = torch.empty((B, C), dtype=torch.float32, device=dev)
+        used = torch.empty(B, dtype=torch.int32, device=dev)
+        dec = torch.empty(B, dtype=torch.float64, device=dev)
     st = _torch_stream(dev) if stream is None else _stream_ptr(stream)
     rc = nat.load().dsp_ensemble_decide_batch(logits.data_ptr(), logits.stride(0), B, C, arr, n_rules, p_feat, ld_feat, p_valid,
                                               ld_valid, pred.data_ptr(), prob.data_ptr(), used.data_ptr(), dec.data_ptr(), st)

@@ -168,10 +168,12 @@ class ModelFeatureBatch:
         """-> (inp [max_len, B, 39 (+2) (+2)] torch tensor on the library's device, len0 [B], endpoints [B, 2]).
         ``jitter``: int [B, 2] endpoint offsets (see draw_jitter) for the training path (augment=True);
         None = test path.  ``use_timefeat`` / ``use_pitch`` append the optional streams of model.py:125-128
-        in the reference's order (pitch, then amplitude): the amplitude stream is computed on the device
-        (dsp_vad_features_batch on the trimmed clips + dsp_model_timefeat_batch); the pitch stream runs the
-        per-utterance pitch tracker on the trimmed clips (its smoothing / octave repair is sequential host
-        logic), which costs a download and a host loop.  torch only owns the result tensors."""
+        in the reference's order (pitch, then amplitude), both computed on the device from one trimmed, scaled
+        fp32 copy of the clips (dsp_trim_scale_batch): the amplitude stream by dsp_vad_features_batch +
+        dsp_model_timefeat_batch, the pitch stream by the batched tracker (_pitch_streams) -- no clip and no track
+        crosses PCIe.  ``waves`` may be any view of a device tensor: a non-contiguous one is copied once on torch's
+        current stream (the stream of every launch here), and that copy is held until the call's last kernel has
+        finished.  torch only owns the result tensors."""
         import torch
         from . import _native as nat
         from .batch import _is_device_tensor, _stream_ptr
@@ -197,15 +199,15 @@ class ModelFeatureBatch:
         extra = []
         if (use_pitch or use_timefeat) and lay.c0_shift_pending:
             # the optional streams work on the trimmed, scaled clips themselves: make that copy now (model.py:62-63)
-            wave_ptr, wave_dtype = self.pipe._last_wave
-            nat.check(lib.dsp_trim_scale_batch(wave_ptr, wave_dtype, lay.vad.p_sample, lay.d_seg.ptr, lay.d_dst_off.ptr,
+            wave = d_m0.wave                  # the buffer pipe.run launched on, alive until d_m0 goes (after the synchronisation below)
+            nat.check(lib.dsp_trim_scale_batch(wave.ptr, wave.dtype, lay.vad.p_sample, lay.d_seg.ptr, lay.d_dst_off.ptr,
                                                B, 1, lay.d_trim.ptr, st))
         if use_pitch:
             extra.append(self._pitch_streams(lay, st, dev))
         if use_timefeat:
             extra.append(self._timefeat_streams(lay, st, dev))
         seg = lay.d_seg.download((B, 2), np.int64, st)       # first host synchronisation of the default call
-        nat.check(lib.dsp_stream_synchronize(st))            # d_m0 is freed on return: its consumer has finished
+        nat.check(lib.dsp_stream_synchronize(st))            # d_m0 and the wave buffer it holds go on return: their consumers have finished
         if extra:
             inp = torch.cat([inp] + extra, dim=2)
         return inp, len0.cpu().numpy(), seg
@@ -231,9 +233,15 @@ class ModelFeatureBatch:
         """A HIP graph of ``enqueue`` over device-resident ``waves`` (torch tensor, int16 / float32) and a prepared layout:
         ``g = mfb.capture(waves, lay)``; put new clips of the same lengths into ``waves`` and call ``g.replay()`` ->
         (inp [max_len, B, 39], len0 [B] int32), both on the device, valid after the current stream's work (no host
-        synchronisation).  One eager call runs first (it builds the layout's long-lived index tables)."""
+        synchronisation).  One eager call runs first (it builds the layout's long-lived index tables).
+        The graph reads ``waves`` at its address, sample after sample: a non-contiguous view cannot be served (a copy
+        would not see what the caller writes later) and raises ValueError; a contiguous view at any offset is fine."""
         import torch
-        from .batch import _wave_dtype_of
+        from .batch import _is_device_tensor, _wave_dtype_of
+        if not _is_device_tensor(waves):
+            raise TypeError('capture needs a device tensor')
+        if not waves.is_contiguous():
+            raise ValueError('capture needs a contiguous waves tensor: the graph reads it in place on every replay')
         dev = waves.device
         C, B = self.pipe.features.C, layout.n_utt
         m0 = torch.empty((max(layout.frames_bound, 1), C), dtype=torch.float32, device=dev)

@@ -31,11 +31,13 @@ from . import _native as nat
 from .batch import EndpointPlan, FeaturePlan, _BatchLayout, _is_device_tensor, _stream_ptr, _wave_dtype_of
 
 
-class _Borrowed:
-    """Device memory owned by the caller (a tensor); only the address is kept."""
+class _WaveRef:
+    """The wave buffer one ``run`` launched on: its address and sample type, together with the object that keeps the
+    memory alive -- the caller's tensor, the contiguous copy made of a strided one, or this thread's upload slot.
+    It travels with the result (``d_out.wave``): whoever reads the clips again later holds it until that work is done."""
 
-    def __init__(self, ptr):
-        self.ptr = int(ptr)
+    def __init__(self, owner, ptr, dtype):
+        self.owner, self.ptr, self.dtype = owner, int(ptr), dtype
 
 
 class _TensorBuffer:
@@ -44,6 +46,7 @@ class _TensorBuffer:
 
     def __init__(self, tensor):
         self.tensor = tensor
+        self.wave = None            # VadMfccPipeline.run: the _WaveRef of the wave buffer these rows were computed from
         self.ptr = tensor.data_ptr()
         self.nbytes = tensor.numel() * tensor.element_size()
 
@@ -192,7 +195,10 @@ class VadMfccPipeline:
         Returns (features [sum T_b, D] fp32, frame_offsets [B+1], endpoints [B, 2] in samples);
         with ``download=False`` nothing is copied or synchronised and the result is
         ((DeviceBuffer of [frames_bound, D] rows, PipelineLayout), None, None): the true frame offsets
-        and endpoints are in layout.d_frame_off / layout.d_seg on the device."""
+        and endpoints are in layout.d_frame_off / layout.d_seg on the device.  The buffer's ``wave`` attribute
+        (a _WaveRef) is the wave buffer the kernels were launched on, kept alive with the result.
+        A device tensor may be any view; a non-contiguous one is copied once, on torch's current stream, which is
+        also the stream of every launch."""
         nat.require_device()
         if layout is not None:
             lay = layout
@@ -209,11 +215,12 @@ class VadMfccPipeline:
                 raise nat.DspError(f'waveforms live on cuda:{waves.device.index}, the library is on device '
                                    f'{nat.current_device()} (dsp_set_device)')
             dtype = _wave_dtype_of(waves)
-            d_wave = _Borrowed(waves.data_ptr())
+            ref = _WaveRef(waves, waves.data_ptr(), dtype)
             stream = torch.cuda.current_stream(waves.device)
         else:
             wave, dtype = nat.as_wave(np.asarray(waves).reshape(-1))
             d_wave = nat.device_array('batch_wave', wave)
+            ref = _WaveRef(d_wave, d_wave.ptr, dtype)
         d_jit = None
         if jitter is not None:
             j = np.ascontiguousarray(jitter, dtype=np.int64).reshape(lay.n_utt, 2)
@@ -223,8 +230,8 @@ class VadMfccPipeline:
                                               device=waves.device))
         else:
             d_out = nat.DeviceBuffer(max(lay.frames_bound, 1) * lay.D * 4)  # owned by the result
-        self._last_wave = (d_wave.ptr, dtype)      # (ModelFeatureBatch's optional streams trim the same buffer again)
-        self.launch(d_wave.ptr, dtype, lay, d_out.ptr, stream, d_jit, defer_c0_shift=defer_c0_shift and not download)
+        d_out.wave = ref                           # (ModelFeatureBatch's optional streams trim the same buffer again)
+        self.launch(ref.ptr, dtype, lay, d_out.ptr, stream, d_jit, defer_c0_shift=defer_c0_shift and not download)
         if not download:
             return (d_out, lay), None, None
         st = _stream_ptr(stream)
