@@ -69,6 +69,18 @@ struct BatchGeom {
     double* stats;
 };
 
+// Where the kernels that write the classifier's input (model_finalize_kernel, timefeat_finalize_kernel,
+// pitchfeat_finalize_kernel) put utterance b: elements (t, col(b), col_offset + k) of a [max_len, n_cols, row_width] fp32
+// tensor.  dst_col == nullptr is the identity; the unplaced entry points pass (nullptr, n_utt, the stream's own width, 0).
+struct OutPlacement {
+    const int32_t* dst_col;     // [n_utt] distinct columns in [0, n_cols), or nullptr
+    int32_t n_cols, row_width, col_offset;
+    __device__ __forceinline__ int32_t col(int32_t b) const { return dst_col ? dst_col[b] : b; }
+    // first element of utterance column `c` in row t = 0; rows are stride() apart
+    __device__ __forceinline__ float* base(float* out, int32_t c) const { return out + (int64_t)c * row_width + col_offset; }
+    __device__ __forceinline__ int64_t stride() const { return (int64_t)n_cols * row_width; }
+};
+
 // Largest b with off[b] <= g  (off is non-decreasing, off[0] == 0, off[n] == total > g).
 __device__ __forceinline__ int32_t dsp_find_utt(const int64_t* __restrict__ off, int32_t n, int64_t g) {
     int32_t lo = 0, hi = n;  // invariant: off[lo] <= g < off[hi]

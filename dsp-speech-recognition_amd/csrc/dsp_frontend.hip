@@ -448,18 +448,36 @@ SegWork seg_work_layout(int32_t n_utt, int64_t n_frames_bound, int32_t C) {
     return w;
 }
 
-// The argument checks the two model-finalize entry points share (behind their own), and the launch.
+// The identity placement of the unplaced entry points: utterance b is column b of a [max_len, n_utt, width] tensor.
+inline OutPlacement identity_placement(int32_t n_utt, int32_t width) { return OutPlacement{nullptr, n_utt, width, 0}; }
+
+// The checks of a caller's placement (dsp_model_*_placed_batch) for a stream `width` floats wide; before any launch.  A
+// thread under dsp_debug_host_dry_run has no device: what passed every check is refused here instead of launched.
+int placement_check(const OutPlacement& pl, int32_t n_utt, int32_t width) {
+    if (pl.n_cols < n_utt) return dsp_fail(DSP_EINVAL, "n_cols %d < n_utt %d", pl.n_cols, n_utt);
+    if (pl.col_offset < 0) return dsp_fail(DSP_EINVAL, "col_offset %d is negative", pl.col_offset);
+    if ((int64_t)pl.col_offset + width > pl.row_width)
+        return dsp_fail(DSP_EINVAL, "col_offset %d + %d columns do not fit row_width %d", pl.col_offset, width, pl.row_width);
+    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dry_run: launches are refused under dsp_debug_host_dry_run");
+    return DSP_OK;
+}
+
+// The argument checks the model-finalize entry points share (behind their own), and the launch.  pl.row_width == 0: the
+// identity placement at this stream's own width.
 int model_finalize_impl(const float* d_mfcc, int64_t ld_in, const int64_t* d_frame_offsets, int32_t n_utt, int32_t C,
                         int32_t N, int32_t max_len, float* d_out, int32_t* d_len0, const int64_t* d_segments,
-                        const double* d_stats, void* stream) {
+                        const double* d_stats, OutPlacement pl, void* stream) {
     if (N < 1) return dsp_fail(DSP_EINVAL, "N must be an integer >= 1");  // base.py:71-72
     if (C <= 0 || C > 32 || max_len <= 0) return dsp_fail(DSP_EINVAL, "need 0 < C <= 32 and max_len > 0");
     if (ld_in == 0) ld_in = C;
     if (ld_in < C) return dsp_fail(DSP_EINVAL, "ld_in %lld < C %d", (long long)ld_in, C);
     const size_t lds = ((size_t)(max_len + 2 * N) + (size_t)(max_len + N)) * C * sizeof(float);
     if (lds > 64 * 1024) return dsp_fail(DSP_EINVAL, "max_len * C too large for the LDS tile (%zu bytes)", lds);
+    int rc;
+    if (pl.row_width == 0) pl.row_width = 3 * C;                      // the unplaced entry points: rows of this stream alone
+    else if ((rc = placement_check(pl, n_utt, 3 * C)) != DSP_OK) return rc;
     model_finalize_kernel<<<n_utt, 256, lds, (hipStream_t)stream>>>(d_mfcc, ld_in, d_frame_offsets, n_utt, C, N, max_len,
-                                                                   d_out, d_len0, d_segments, d_stats);
+                                                                   d_out, d_len0, pl, d_segments, d_stats);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }
@@ -982,7 +1000,8 @@ int dsp_model_finalize_batch(const float* d_mfcc, int64_t ld_in, const int64_t* 
                              int32_t C, int32_t N, int32_t max_len, float* d_out, int32_t* d_len0, void* stream) {
     if (!d_mfcc || !d_frame_offsets || !d_out || !d_len0 || n_utt <= 0)
         return dsp_fail(DSP_EINVAL, "dsp_model_finalize_batch: bad arguments");
-    return model_finalize_impl(d_mfcc, ld_in, d_frame_offsets, n_utt, C, N, max_len, d_out, d_len0, nullptr, nullptr, stream);
+    return model_finalize_impl(d_mfcc, ld_in, d_frame_offsets, n_utt, C, N, max_len, d_out, d_len0, nullptr, nullptr,
+                               identity_placement(n_utt, 0), stream);
 }
 
 int dsp_model_finalize_segments_batch(const float* d_mfcc, int64_t ld_in, const int64_t* d_frame_offsets,
@@ -992,14 +1011,41 @@ int dsp_model_finalize_segments_batch(const float* d_mfcc, int64_t ld_in, const 
         return dsp_fail(DSP_EINVAL, "dsp_model_finalize_segments_batch: bad arguments");
     // the statistics sit at the start of the work buffer of dsp_mfcc_delta_segments_batch (seg_work_layout)
     return model_finalize_impl(d_mfcc, ld_in, d_frame_offsets, n_utt, C, N, max_len, d_out, d_len0, d_segments,
-                               static_cast<const double*>(d_work), stream);
+                               static_cast<const double*>(d_work), identity_placement(n_utt, 0), stream);
+}
+
+int dsp_model_finalize_placed_batch(const float* d_mfcc, int64_t ld_in, const int64_t* d_frame_offsets,
+                                    const int64_t* d_segments, const void* d_work, int32_t n_utt, int32_t C, int32_t N,
+                                    int32_t max_len, float* d_out, int32_t* d_len0, const int32_t* d_dst_col, int32_t n_cols,
+                                    int32_t row_width, int32_t col_offset, void* stream) {
+    if (!d_mfcc || !d_frame_offsets || !d_out || !d_len0 || n_utt <= 0)
+        return dsp_fail(DSP_EINVAL, "dsp_model_finalize_placed_batch: NULL argument or n_utt <= 0");
+    if ((d_segments == nullptr) != (d_work == nullptr))
+        return dsp_fail(DSP_EINVAL, "dsp_model_finalize_placed_batch: d_segments and d_work go together (both, or both NULL)");
+    if (row_width <= 0) return dsp_fail(DSP_EINVAL, "dsp_model_finalize_placed_batch: row_width %d must be > 0", row_width);
+    return model_finalize_impl(d_mfcc, ld_in, d_frame_offsets, n_utt, C, N, max_len, d_out, d_len0, d_segments,
+                               static_cast<const double*>(d_work), OutPlacement{d_dst_col, n_cols, row_width, col_offset}, stream);
 }
 
 int dsp_model_timefeat_batch(const double* d_amp_sum, const int64_t* d_frame_offsets, int32_t n_utt,
                              int32_t frame_len, int32_t max_len, float* d_out, void* stream) {
     if (!d_amp_sum || !d_frame_offsets || !d_out || n_utt <= 0 || frame_len <= 0 || max_len <= 0)
         return dsp_fail(DSP_EINVAL, "dsp_model_timefeat_batch: bad arguments");
-    timefeat_finalize_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_amp_sum, d_frame_offsets, n_utt, frame_len, max_len, d_out);
+    timefeat_finalize_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_amp_sum, d_frame_offsets, n_utt, frame_len, max_len, d_out,
+                                                                    identity_placement(n_utt, 2));
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+int dsp_model_timefeat_placed_batch(const double* d_amp_sum, const int64_t* d_frame_offsets, int32_t n_utt, int32_t frame_len,
+                                    int32_t max_len, float* d_out, const int32_t* d_dst_col, int32_t n_cols, int32_t row_width,
+                                    int32_t col_offset, void* stream) {
+    if (!d_amp_sum || !d_frame_offsets || !d_out || n_utt <= 0 || frame_len <= 0 || max_len <= 0)
+        return dsp_fail(DSP_EINVAL, "dsp_model_timefeat_placed_batch: NULL argument, or n_utt, frame_len or max_len <= 0");
+    const OutPlacement pl{d_dst_col, n_cols, row_width, col_offset};
+    int rc = placement_check(pl, n_utt, 2);
+    if (rc != DSP_OK) return rc;
+    timefeat_finalize_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_amp_sum, d_frame_offsets, n_utt, frame_len, max_len, d_out, pl);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }
@@ -1117,7 +1163,41 @@ int dsp_model_pitchfeat_batch(const double* d_pitch, const int64_t* d_frame_offs
                               float* d_out, void* stream) {
     if (!d_pitch || !d_frame_offsets || !d_out || n_utt <= 0 || max_len <= 0)
         return dsp_fail(DSP_EINVAL, "dsp_model_pitchfeat_batch: bad arguments");
-    pitchfeat_finalize_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_pitch, d_frame_offsets, n_utt, max_len, d_out);
+    pitchfeat_finalize_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_pitch, d_frame_offsets, n_utt, max_len, d_out,
+                                                                     identity_placement(n_utt, 2));
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+int dsp_model_pitchfeat_placed_batch(const double* d_pitch, const int64_t* d_frame_offsets, int32_t n_utt, int32_t max_len,
+                                     float* d_out, const int32_t* d_dst_col, int32_t n_cols, int32_t row_width,
+                                     int32_t col_offset, void* stream) {
+    if (!d_pitch || !d_frame_offsets || !d_out || n_utt <= 0 || max_len <= 0)
+        return dsp_fail(DSP_EINVAL, "dsp_model_pitchfeat_placed_batch: NULL argument, or n_utt or max_len <= 0");
+    const OutPlacement pl{d_dst_col, n_cols, row_width, col_offset};
+    int rc = placement_check(pl, n_utt, 2);
+    if (rc != DSP_OK) return rc;
+    pitchfeat_finalize_kernel<<<n_utt, 64, 0, (hipStream_t)stream>>>(d_pitch, d_frame_offsets, n_utt, max_len, d_out, pl);
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+int dsp_gather_clips_batch(const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets, const int32_t* d_pick,
+                           int32_t n_pick, const int64_t* d_dst_offsets, void* d_out, void* stream) {
+    if (!d_wave || !d_sample_offsets || !d_pick || !d_dst_offsets || !d_out)
+        return dsp_fail(DSP_EINVAL, "dsp_gather_clips_batch: NULL argument");
+    if (n_pick < 0) return dsp_fail(DSP_EINVAL, "dsp_gather_clips_batch: n_pick %d is negative", n_pick);
+    if (wave_dtype != DSP_WAVE_F32 && wave_dtype != DSP_WAVE_I16)
+        return dsp_fail(DSP_EINVAL, "dsp_gather_clips_batch: bad wave_dtype %d", wave_dtype);
+    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dry_run: launches are refused under dsp_debug_host_dry_run");
+    if (n_pick == 0) return DSP_OK;
+    const dim3 grid(GATHER_CHUNKS, (unsigned)n_pick);
+    if (wave_dtype == DSP_WAVE_I16)
+        gather_clips_kernel<int16_t><<<grid, 256, 0, (hipStream_t)stream>>>(static_cast<const int16_t*>(d_wave), d_sample_offsets,
+                                                                            d_pick, d_dst_offsets, static_cast<int16_t*>(d_out));
+    else
+        gather_clips_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(static_cast<const float*>(d_wave), d_sample_offsets,
+                                                                          d_pick, d_dst_offsets, static_cast<float*>(d_out));
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }

@@ -987,14 +987,17 @@ __global__ __launch_bounds__(256) void trim_scale_kernel(const void* __restrict_
 //   a[t]  = amp_sum[t] / L                 get_amplitude of the trimmed, scaled clip (endpoint.py:109-131)
 //   z     = (a - mean) / std               sklearn scale: population std, 0 -> 1
 //   out[t, b, 0] = z[t], out[t, b, 1] = z[t + 1] - z[t]  (deviation, model.py:29-33: T - 1 rows),
-// each zero padded / truncated to max_len rows (model.py:35-50).  One wave per utterance, fp64.
+// each zero padded / truncated to max_len rows (model.py:35-50), at the place `pl` names.  One wave per utterance, fp64.
 __global__ __launch_bounds__(64) void timefeat_finalize_kernel(const double* __restrict__ amp_sum,
                                                                const int64_t* __restrict__ frame_off, int32_t n_utt,
-                                                               int32_t L, int32_t max_len, float* __restrict__ out) {
+                                                               int32_t L, int32_t max_len, float* __restrict__ out,
+                                                               OutPlacement pl) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int64_t base = frame_off[b];
     const int T = (int)(frame_off[b + 1] - base);
     const double* a = amp_sum + base;
+    float* ob = pl.base(out, pl.col(b));
+    const int64_t row = pl.stride();
     const double inv_L = 1.0 / (double)L;
     double s = 0.0;
     for (int t = lane; t < T; t += 64) s += a[t] * inv_L;
@@ -1017,7 +1020,7 @@ __global__ __launch_bounds__(64) void timefeat_finalize_kernel(const double* __r
             z0 = (float)zt;
             if (t + 1 < T) z1 = (float)((a[t + 1] * inv_L - mu) * inv - zt);
         }
-        float* o = out + ((int64_t)t * n_utt + b) * 2;
+        float* o = ob + (int64_t)t * row;
         o[0] = z0;
         o[1] = z1;
     }
@@ -1029,11 +1032,13 @@ __global__ __launch_bounds__(64) void timefeat_finalize_kernel(const double* __r
 //   d1 = delta(x, N), d2 = delta(d1, N)    edge replicated, base.py:70-79            (model.py:76-77)
 //   z  = (x - mean_c) / std_c              per coefficient, population std, 0 -> 1   (model.py:78)
 //   out[t, b, :] = z | d1 | d2 for t < min(T, max_len), zeros up to max_len          (model.py:35-50)
+// `pl` says where (t, b, :) lies in `out` and which len0 entry is b's (OutPlacement, dsp_common.h).
 // Statistics in fp64 over all T frames; only the first max_len (+ halo) rows are staged in LDS.
 __global__ __launch_bounds__(256) void model_finalize_kernel(const float* __restrict__ mfcc, int64_t ld_in,
                                                              const int64_t* __restrict__ frame_off, int32_t n_utt,
                                                              int32_t C, int32_t N, int32_t max_len,
                                                              float* __restrict__ out, int32_t* __restrict__ len0,
+                                                             OutPlacement pl,
                                                              // cepstra of segments read IN PLACE (dsp_mfcc_delta_segments_batch,
                                                              // delta_n = 0, unit variance): c0 still lacks the -ln(var) of
                                                              // model.py:62-63 -- applied here, at every read, from the sums
@@ -1132,8 +1137,9 @@ __global__ __launch_bounds__(256) void model_finalize_kernel(const float* __rest
     }
     __syncthreads();
     auto dat = [&](int t, int c) { t = t < 0 ? 0 : (t >= T ? T - 1 : t); return sd1[t * C + c]; };
-    const int64_t row = (int64_t)n_utt * 3 * C;
-    float* ob = out + (int64_t)b * 3 * C;
+    const int32_t col = pl.col(b);
+    const int64_t row = pl.stride();
+    float* ob = pl.base(out, col);
     for (int i = tid; i < max_len * C; i += 256) {
         const int t = i / C, c = i % C;
         float z = 0.f, d1 = 0.f, d2 = 0.f;
@@ -1149,6 +1155,38 @@ __global__ __launch_bounds__(256) void model_finalize_kernel(const float* __rest
         o[C + c] = d1;
         o[2 * C + c] = d2;
     }
-    if (tid == 0) len0[b] = keep;
+    if (tid == 0) len0[col] = keep;
 }
 
+
+// Clip pick[i] of a batch copied, sample type kept, to out + dst_off[i] (dsp_gather_clips_batch): the clips of one sample
+// rate of a mixed-rate batch (reader.mini_batch_iterator shuffles the file list, reader.py:80) made one contiguous run.
+// GATHER_CHUNKS workgroups share a clip, each striding over it, so one long clip is not one workgroup's work alone.
+// Where source and destination are equally misaligned against 16 bytes the body moves as 16-byte vectors with an
+// element-wise head and tail; otherwise element by element.
+constexpr int GATHER_CHUNKS = 8;
+template <typename T>
+__global__ __launch_bounds__(256) void gather_clips_kernel(const T* __restrict__ wave, const int64_t* __restrict__ src_off,
+                                                           const int32_t* __restrict__ pick, const int64_t* __restrict__ dst_off,
+                                                           T* __restrict__ out) {
+    constexpr int V = 16 / (int)sizeof(T);
+    const int i = blockIdx.y;
+    const int32_t u = pick[i];
+    const int64_t s0 = src_off[u], n = src_off[u + 1] - s0;
+    const T* src = wave + s0;
+    T* dst = out + dst_off[i];
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthr = (int64_t)gridDim.x * 256;
+    const uintptr_t mis_s = reinterpret_cast<uintptr_t>(src) & 15, mis_d = reinterpret_cast<uintptr_t>(dst) & 15;
+    if (mis_s != mis_d) {
+        for (int64_t k = tid; k < n; k += nthr) dst[k] = src[k];
+        return;
+    }
+    int64_t head = (int64_t)(((16 - mis_d) & 15) / sizeof(T));
+    if (head > n) head = n;
+    const int64_t nvec = (n - head) / V;
+    for (int64_t k = tid; k < head; k += nthr) dst[k] = src[k];
+    const uint4* vs = reinterpret_cast<const uint4*>(src + head);
+    uint4* vd = reinterpret_cast<uint4*>(dst + head);
+    for (int64_t k = tid; k < nvec; k += nthr) vd[k] = vs[k];
+    for (int64_t k = head + nvec * V + tid; k < n; k += nthr) dst[k] = src[k];
+}

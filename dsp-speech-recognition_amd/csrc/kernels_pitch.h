@@ -338,11 +338,13 @@ __global__ __launch_bounds__(256) void decimate_gather_kernel(const float* __res
 // truncated to max_len rows (model.py:35-50).  One wave per utterance.
 __global__ __launch_bounds__(64) void pitchfeat_finalize_kernel(const double* __restrict__ pitch,
                                                                 const int64_t* __restrict__ frame_off, int32_t n_utt,
-                                                                int32_t max_len, float* __restrict__ out) {
+                                                                int32_t max_len, float* __restrict__ out, OutPlacement pl) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int64_t base = frame_off[b];
     const int T = (int)(frame_off[b + 1] - base);
     const double* p = pitch + base;
+    float* ob = pl.base(out, pl.col(b));
+    const int64_t row = pl.stride();
     for (int t = lane; t < max_len; t += 64) {
         float z0 = 0.f, z1 = 0.f;
         if (t < T) {
@@ -350,7 +352,7 @@ __global__ __launch_bounds__(64) void pitchfeat_finalize_kernel(const double* __
             z0 = (float)a;
             if (t + 1 < T) z1 = (float)(p[t + 1] / 150.0 - a);
         }
-        float* o = out + ((int64_t)t * n_utt + b) * 2;
+        float* o = ob + (int64_t)t * row;
         o[0] = z0;
         o[1] = z1;
     }

@@ -10,6 +10,8 @@ Unlike the reference's ``features/__init__.py`` this import has no side effects 
 directory, no matplotlib / sklearn import).  Both pitch trackers (``pitch_detect_sr``, ``pitch_detect``) and
 ``pitch_feature`` are here, and ``features.ensemble`` evaluates the fitted pitch SVM and the ensemble's confidence gate
 (pitch_model.py:54-61, ensemble.py:44-67) on the device; fitting the SVM stays with sklearn.
+``get_batch_full(feat)`` is RNNModel.get_batch_full (model.py:114-135) for the reference's list of (sig, rate) pairs, the
+rates mixed as reader.mini_batch_iterator yields them.
 There is no CPU fallback: without the built library or without a GPU every compute call raises.
 """
 from .base import *  # noqa: F401,F403
@@ -23,4 +25,5 @@ from .pitch import (center_clip, max_pitch, pitch_detect_frame_sr, pitch_detect_
 from . import base, sigproc, endpoint, preprocess, pitch, batch, pipeline, ensemble  # noqa: F401
 from .batch import FeaturePlan, EndpointPlan  # noqa: F401
 from .pipeline import VadMfccPipeline  # noqa: F401
-from .ensemble import PitchSVM, EnsembleBatch, ensemble_decide  # noqa: F401
+from .ensemble import PitchSVM, EnsembleBatch, MixedRateEnsembleBatch, ensemble_decide  # noqa: F401
+from .model_glue import MixedRateFeatureBatch, get_batch_full  # noqa: F401

@@ -140,6 +140,11 @@ SIGNATURES = {
     'dsp_ensemble_decide_batch': (C.c_int, [c_vp, c_i64, c_i32, c_i32, C.POINTER(EnsembleRule), c_i32, c_vp, c_i64, c_vp, c_i64,
                                             c_vp, c_vp, c_vp, c_vp, c_vp]),
     'dsp_trim_preemph_batch': (C.c_int, [c_vp, C.c_int, c_vp, c_vp, c_vp, c_i32, c_f64, c_vp, c_vp]),
+    'dsp_model_finalize_placed_batch': (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp,
+                                                  c_vp, c_i32, c_i32, c_i32, c_vp]),
+    'dsp_model_timefeat_placed_batch': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    'dsp_model_pitchfeat_placed_batch': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    'dsp_gather_clips_batch': (C.c_int, [c_vp, C.c_int, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

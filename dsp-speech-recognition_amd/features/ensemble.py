@@ -306,3 +306,51 @@ class EnsembleBatch:
         return types.SimpleNamespace(pred=pred, prob=prob, used=used, decision=dec, logits=logits, feat=feat, valid=valid,
                                      endpoints=endpoints, inp=inp, len0=len0, _clips=clips, _trimmed=trimmed)
 
+
+
+class MixedRateEnsembleBatch:
+    """EnsembleBatch for a batch whose clips have different sample rates (reader.mini_batch_iterator shuffles the file list,
+    reader.py:80; ensemble.py:48-53 and pitch_model.py:54-61 treat every clip at its own rate): the classifier's features
+    from MixedRateFeatureBatch, ONE ``head`` call on the whole batch, the pre-emphasised trim and the five pitch features per
+    rate group with their rows placed in batch order, and one gate launch over the batch."""
+
+    def __init__(self, head, rules, frame=0.03, step=0.01, coeff=0.97):
+        from .model_glue import MixedRateFeatureBatch
+        self.head, self.rules, self.coeff = head, list(rules), float(coeff)
+        self.features = MixedRateFeatureBatch(frame=frame, step=step)
+
+    def run(self, waves, sample_offsets=None, rates=None, **head_kwargs):
+        """``waves`` / ``sample_offsets`` / ``rates`` as MixedRateFeatureBatch.run.  Returns the namespace of EnsembleBatch.run,
+        every row in batch order."""
+        import torch
+        from .pitch import N_AUX, pitch_features_device
+        lib = nat.load()
+        ctx = self.features._launch(waves, sample_offsets, rates)
+        clips = ctx.group_waves                   # one contiguous device buffer per rate, held until the call returns
+        len0, endpoints = self.features._finish(ctx)
+        inp, dev, st, B = ctx.inp, ctx.dev, ctx.st, ctx.plan.B
+        out = self.head(inp, len0, **head_kwargs)
+        logits = out[0] if isinstance(out, (tuple, list)) else out
+        logits = logits.detach().to(torch.float32)
+        feat = torch.empty((B, 5), dtype=torch.float64, device=dev)
+        aux = torch.empty((B, N_AUX), dtype=torch.int32, device=dev)
+        trimmed = []
+        for g, wave in zip(ctx.plan.groups, clips):
+            lay, n = g.lay, len(g.index)
+            trim = torch.empty(max(lay.total_samples, 1), dtype=torch.float32, device=dev)
+            nat.check(lib.dsp_trim_preemph_batch(wave.data_ptr(), _wave_dtype_of(wave), lay.vad.p_sample, lay.d_seg.ptr,
+                                                 lay.d_dst_off.ptr, n, self.coeff, trim.data_ptr(), st))
+            one = g.d_index is None               # a single rate: the group's rows are the batch's
+            feat_g = feat if one else torch.empty((n, 5), dtype=torch.float64, device=dev)
+            aux_g = aux if one else torch.empty((n, N_AUX), dtype=torch.int32, device=dev)
+            pitch_features_device(trim.data_ptr(), lay.d_dst_off.ptr, n, lay.total_samples, g.rate, stream=st,
+                                  d_feat=feat_g.data_ptr(), d_aux=aux_g.data_ptr())
+            if not one:                           # five doubles and nine ints per clip
+                pos = g.d_index.long()
+                feat.index_copy_(0, pos, feat_g)
+                aux.index_copy_(0, pos, aux_g)
+            trimmed.append(trim)
+        valid = aux[:, N_AUX - 1]
+        pred, prob, used, dec = ensemble_decide(logits, self.rules, feat, valid, stream=st)
+        return types.SimpleNamespace(pred=pred, prob=prob, used=used, decision=dec, logits=logits, feat=feat, valid=valid,
+                                     endpoints=endpoints, inp=inp, len0=len0, _clips=clips, _trimmed=trimmed)

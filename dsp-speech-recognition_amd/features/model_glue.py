@@ -229,6 +229,33 @@ class ModelFeatureBatch:
             nat.check(lib.dsp_model_finalize_batch(d_m0, C, lay.d_frame_off.ptr, lay.n_utt, C, self.delta_n, self.max_len,
                                                    d_inp, d_len0, st))
 
+    def enqueue_placed(self, d_wave, wave_dtype, lay, d_m0, d_inp, d_len0, d_dst_col, n_cols, row_width, stream, dev,
+                       d_jitter=None, use_pitch=False, use_timefeat=False):
+        """``enqueue`` for a sub-batch of a larger one (MixedRateFeatureBatch): utterance b's rows go to
+        ``d_inp[:, dst_col[b], 0:3 C]`` of a [max_len, n_cols, row_width] tensor and its length to ``d_len0[dst_col[b]]``
+        (dsp_model_finalize_placed_batch; ``d_dst_col`` None = identity), the optional streams of ``run`` to the columns
+        behind, in the reference's order (model.py:125-128).  Launches only; returns the temporaries the optional streams
+        read, which the caller keeps until ``stream`` has finished.  Without optional streams nothing is allocated."""
+        from . import _native as nat
+        from .batch import _stream_ptr
+        lib = nat.load()
+        st = _stream_ptr(stream)
+        B, C = lay.n_utt, self.pipe.features.C
+        self.pipe.launch(d_wave, wave_dtype, lay, d_m0, stream, d_jitter, defer_c0_shift=True)
+        seg, work = (lay.d_seg.ptr, lay.d_work.ptr) if lay.c0_shift_pending else (None, None)
+        nat.check(lib.dsp_model_finalize_placed_batch(d_m0, C, lay.d_frame_off.ptr, seg, work, B, C, self.delta_n, self.max_len,
+                                                      d_inp, d_len0, d_dst_col, n_cols, row_width, 0, st))
+        hold, col = [], 3 * C
+        if (use_pitch or use_timefeat) and lay.c0_shift_pending:      # the trimmed, scaled clips themselves (model.py:62-63)
+            nat.check(lib.dsp_trim_scale_batch(d_wave, wave_dtype, lay.vad.p_sample, lay.d_seg.ptr, lay.d_dst_off.ptr,
+                                               B, 1, lay.d_trim.ptr, st))
+        if use_pitch:
+            hold += self._pitch_streams(lay, st, dev, place=(d_inp, d_dst_col, n_cols, row_width, col))
+            col += 2
+        if use_timefeat:
+            hold += self._timefeat_streams(lay, st, dev, place=(d_inp, d_dst_col, n_cols, row_width, col))
+        return hold
+
     def capture(self, waves, layout):
         """A HIP graph of ``enqueue`` over device-resident ``waves`` (torch tensor, int16 / float32) and a prepared layout:
         ``g = mfb.capture(waves, lay)``; put new clips of the same lengths into ``waves`` and call ``g.replay()`` ->
@@ -258,17 +285,20 @@ class ModelFeatureBatch:
             self.enqueue(waves.data_ptr(), dtype, layout, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(), torch.cuda.current_stream(dev))
         return _ModelFeatureGraph(graph, waves, m0, inp, len0, layout)
 
-    def _timefeat_streams(self, lay, st, dev):
+    def _timefeat_streams(self, lay, st, dev, place=None):
         """[max_len, B, 2]: z-scored frame amplitude of the trimmed, scaled clips and its first difference
         (model.py:97-101), on the device -- at the amplitude stream's OWN framing (int(rate * cfg.frame),
         int(cfg.step * rate): to_frames truncates, sigproc.py:19; the MFCC framing rounds half up, so the two differ at
-        e.g. 22.05 kHz): its frame offsets come from one small launch over the trimmed offsets."""
+        e.g. 22.05 kHz): its frame offsets come from one small launch over the trimmed offsets.
+        ``place`` = (d_out, d_dst_col, n_cols, row_width, col_offset): the two columns go there instead
+        (dsp_model_timefeat_placed_batch), nothing is synchronised and the temporaries are returned for the caller to hold."""
         import torch
         from . import _native as nat
         lib = nat.load()
         ep, fp = self.pipe.endpoint, self.pipe.features
         L2, S2 = int(self.rate * ep.frame), int(ep.step * self.rate)       # to_frames truncation, sigproc.py:19
         B = lay.n_utt
+        d_fo2 = None
         if (L2, S2) == (fp.L, fp.S):
             p_fo, frames_bound = lay.d_frame_off.ptr, lay.frames_bound
         else:
@@ -279,17 +309,21 @@ class ModelFeatureBatch:
         d_zcr = torch.empty(max(frames_bound, 1), dtype=torch.int32, device=dev)
         nat.check(lib.dsp_vad_features_batch(lay.d_trim.ptr, nat.WAVE_F32, lay.d_dst_off.ptr, p_fo, B,
                                              frames_bound, 0, L2, S2, 0, d_amp.data_ptr(), d_zcr.data_ptr(), st))
+        if place is not None:
+            nat.check(lib.dsp_model_timefeat_placed_batch(d_amp.data_ptr(), p_fo, B, L2, self.max_len, *place, st))
+            return [d_amp, d_zcr, d_fo2]
         out = torch.empty((self.max_len, B, 2), dtype=torch.float32, device=dev)
         nat.check(lib.dsp_model_timefeat_batch(d_amp.data_ptr(), p_fo, B, L2, self.max_len,
                                                out.data_ptr(), st))
         nat.check(lib.dsp_stream_synchronize(st))            # d_amp / d_zcr / the offsets are released on return
         return out
 
-    def _pitch_streams(self, lay, st, dev):
+    def _pitch_streams(self, lay, st, dev, place=None):
         """[max_len, B, 2]: pitch track / 150 and its first difference (model.py:90-95) of the trimmed, scaled
         clips, on the device: decimation to 10 kHz (an index selection, preprocess.py:21-28), frame scores, smoothing,
         arg-max, octave repair (pitch.py:96-206) and the [max_len, B, 2] layout -- six launches, no clip and no track
-        crosses PCIe."""
+        crosses PCIe.  ``place`` as in _timefeat_streams (dsp_model_pitchfeat_placed_batch); the track is library scratch
+        that later launches on the same stream may reuse, so there is nothing to hold."""
         import torch
         from . import _native as nat
         from .pitch import pitch_tracks_device
@@ -298,6 +332,291 @@ class ModelFeatureBatch:
         cfg = _endpoint.cfg
         L, S = int(10000 * cfg.frame), int(cfg.step * 10000)
         d_pitch, d_fo = pitch_tracks_device(lay.d_trim.ptr, lay.d_dst_off.ptr, B, int(lay.total_samples), self.rate, L, S, st)
+        if place is not None:
+            nat.check(lib.dsp_model_pitchfeat_placed_batch(d_pitch.ptr, d_fo.ptr, B, self.max_len, *place, st))
+            return []
         out = torch.empty((self.max_len, B, 2), dtype=torch.float32, device=dev)
         nat.check(lib.dsp_model_pitchfeat_batch(d_pitch.ptr, d_fo.ptr, B, self.max_len, out.data_ptr(), st))
         return out
+
+
+# ---- mixed sample rates in one batch ---------------------------------------------------------------------------------
+# reader.mini_batch_iterator shuffles the file list and yields feat = [(sig, rate), ...] (reader.py:80); the recordings are
+# at 44.1 kHz and 48 kHz, and model.py:114-135 treats every clip at its own rate.  Framing, window, mel table and the VAD
+# frames differ per rate, so a mixed batch runs as one sub-batch per distinct rate, one after the other on one stream, each
+# writing its rows straight into the shared [200, B, width] tensor (the placed entry points of include/dsp_frontend.h).
+
+
+class RateGroup:
+    """The clips of one sample rate in a batch: ``index`` (int32, ascending batch positions -- the sub-batch's order, its
+    pick list and its destination columns at once) and whether they are one contiguous run of the batch."""
+
+    def __init__(self, rate, index):
+        self.rate = int(rate)
+        self.index = np.ascontiguousarray(index, dtype=np.int32)
+        self.contiguous = bool(self.index[-1] - self.index[0] + 1 == len(self.index))
+
+
+def group_by_rate(rates):
+    """[B] rates -> RateGroups in order of first appearance, batch order kept inside a group; their ``index`` arrays
+    partition range(B)."""
+    rates = np.asarray(rates).reshape(-1)
+    seen = {}
+    for b, r in enumerate(rates.tolist()):
+        seen.setdefault(int(r), []).append(b)
+    return [RateGroup(r, idx) for r, idx in seen.items()]
+
+
+def _as_rates(rates):
+    r = np.asarray(rates).reshape(-1)
+    if r.size and not np.issubdtype(r.dtype, np.integer):
+        if not np.all(r == np.floor(r)):
+            raise ValueError('sample rates must be whole numbers')
+        r = r.astype(np.int64)
+    if np.any(r <= 0):
+        raise ValueError(f'sample rates must be positive, got {r[r <= 0].tolist()}')
+    return r.astype(np.int64)
+
+
+class _MixedPlan:
+    """Everything about a mixed-rate batch that depends only on its sample offsets and rates: the groups, each group's
+    rebased offsets and pipeline layout, and the small device tables of the placement and the gather."""
+
+    def __init__(self, owner, so, rates, dev, device_input):
+        import torch
+        self.so, self.B = so, len(so) - 1
+        self.groups = group_by_rate(rates)
+        identity = len(self.groups) == 1
+        self.d_so = None
+        lens = np.diff(so)
+        for g in self.groups:
+            g.so = np.concatenate(([0], np.cumsum(lens[g.index]))).astype(np.int64)
+            g.lay = owner._mfb(g.rate).pipe.prepare(g.so, 0)
+            g.d_index = None if identity else torch.from_numpy(g.index).to(dev)
+            g.d_dst_off = None
+            if device_input and not g.contiguous:           # interleaved clips on the device: dsp_gather_clips_batch
+                if self.d_so is None:
+                    self.d_so = torch.from_numpy(so).to(dev)
+                g.d_dst_off = torch.from_numpy(g.so).to(dev)
+        self.order = np.concatenate([g.index for g in self.groups])
+
+
+class _MixedRateGraph:
+    """What MixedRateFeatureBatch.capture returns: replay() re-runs the captured launches on whatever ``waves`` holds now."""
+
+    def __init__(self, graph, waves, plan, inp, len0, hold):
+        self.graph, self.waves, self.plan, self.inp, self.len0, self._hold = graph, waves, plan, inp, len0, hold
+
+    def replay(self):
+        self.graph.replay()
+        return self.inp, self.len0
+
+
+class MixedRateFeatureBatch:
+    """RNNModel.get_batch_full (model.py:113-135) for a batch whose clips have different sample rates: one
+    ModelFeatureBatch per rate seen (created on first use), the rate groups processed in order of first appearance on one
+    stream, every group's rows -- and the optional streams of model.py:125-128 -- written in place into one
+    [max_len, B, width] tensor in batch order.  No torch.cat, no permutation pass, one host synchronisation at the end."""
+
+    def __init__(self, frame=0.03, step=0.01, nfft=1536, delta_n=3, max_len=200):
+        import threading
+        self.frame, self.step, self.nfft, self.delta_n, self.max_len = frame, step, nfft, delta_n, max_len
+        self._by_rate = {}
+        self._tls = threading.local()   # per thread: the plans of the last few batch shapes (VadMfccPipeline._cached_layout)
+
+    def _mfb(self, rate):
+        mfb = self._by_rate.get(int(rate))
+        if mfb is None:
+            mfb = self._by_rate[int(rate)] = ModelFeatureBatch(int(rate), frame=self.frame, step=self.step, nfft=self.nfft,
+                                                               delta_n=self.delta_n, max_len=self.max_len)
+        return mfb
+
+    @staticmethod
+    def draw_jitter(rates, rng):
+        """The augmentation of model.py:54-60 in the reference's consumption order (model.py:55-58): for b in batch order
+        -rng.randint(0, int(0.1 * rates[b])), then +rng.randint(0, int(0.1 * rates[b])) -> int64 [B, 2]."""
+        rates = np.asarray(rates).reshape(-1)
+        j = np.empty((len(rates), 2), dtype=np.int64)
+        for b, r in enumerate(rates.tolist()):
+            hi = int(0.1 * r)
+            j[b, 0] = -rng.randint(0, hi)
+            j[b, 1] = rng.randint(0, hi)
+        return j
+
+    # ---- inputs ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _inputs(waves, sample_offsets, rates):
+        """-> (clips, so, rates): ``clips`` a 1-D device tensor, or a list of B host arrays; ValueError before any device
+        work for a rate list of the wrong length or a non-positive rate."""
+        from .batch import _is_device_tensor
+        rates = _as_rates(rates)
+        if isinstance(waves, (list, tuple)):
+            clips = [np.asarray(c).reshape(-1) for c in waves]
+            so = np.concatenate(([0], np.cumsum([len(c) for c in clips]))).astype(np.int64)
+        else:
+            if sample_offsets is None:
+                raise ValueError('concatenated waves need sample_offsets')
+            so = np.ascontiguousarray(sample_offsets, dtype=np.int64).reshape(-1)
+            if _is_device_tensor(waves):
+                if waves.dim() != 1:
+                    raise ValueError('device waves must be 1-D (a view such as buf[:, 0] is fine)')
+                clips = waves
+            else:
+                flat = np.asarray(waves).reshape(-1)
+                clips = [flat[so[b]:so[b + 1]] for b in range(len(so) - 1)]
+        if len(so) < 2:
+            raise ValueError('an empty batch')
+        if len(rates) != len(so) - 1:
+            raise ValueError(f'{len(rates)} rates for {len(so) - 1} clips')
+        return clips, so, rates
+
+    def _plan(self, so, rates, dev, device_input):
+        cache = getattr(self._tls, 'plans', None)
+        if cache is None:
+            cache = self._tls.plans = {}
+        key = (dev.index, bool(device_input), so.tobytes(), rates.tobytes())
+        plan = cache.pop(key, None)
+        if plan is None:
+            plan = _MixedPlan(self, so, rates, dev, device_input)
+            while len(cache) >= 4:
+                cache.pop(next(iter(cache)))
+        cache[key] = plan              # most recently used last
+        return plan
+
+    @staticmethod
+    def _group_wave(clips, plan, g, dev, st):
+        """The clips of group ``g`` as one contiguous 1-D device tensor: a view of a device batch where they form one run,
+        one gather launch where they do not, one upload of the host clips concatenated per rate."""
+        import torch
+        from . import _native as nat
+        from .batch import _is_device_tensor, _wave_dtype_of
+        if not _is_device_tensor(clips):
+            parts = [nat.as_wave(clips[b]) for b in g.index]
+            if any(dt != nat.WAVE_I16 for _, dt in parts):
+                parts = [(np.asarray(a, dtype=np.float32), nat.WAVE_F32) for a, _ in parts]
+            return torch.from_numpy(np.concatenate([a for a, _ in parts])).to(dev)
+        if g.contiguous:
+            lo = int(plan.so[g.index[0]])
+            return clips[lo:lo + int(g.so[-1])]
+        out = torch.empty(max(int(g.so[-1]), 1), dtype=clips.dtype, device=dev)
+        nat.check(nat.load().dsp_gather_clips_batch(clips.data_ptr(), _wave_dtype_of(clips), plan.d_so.data_ptr(), g.d_index.data_ptr(),
+                                                    len(g.index), g.d_dst_off.data_ptr(), out.data_ptr(), st))
+        return out
+
+    # ---- the call ----------------------------------------------------------------------------------------------------
+    def _launch(self, waves, sample_offsets, rates, jitter=None, use_pitch=False, use_timefeat=False, plan=None):
+        """Queue the whole batch on torch's current stream -> a namespace (inp, len0 on the device, plan, waves per group,
+        hold: every temporary a launch reads).  Nothing is synchronised once the plan of the batch shape exists."""
+        import types
+        import torch
+        from . import _native as nat
+        from .batch import _is_device_tensor, _stream_ptr, _wave_dtype_of
+        clips, so, rates = self._inputs(waves, sample_offsets, rates)
+        nat.require_device()
+        B = len(so) - 1
+        on_device = _is_device_tensor(clips)
+        if on_device and clips.device.index != nat.current_device():
+            raise nat.DspError(f'waveforms live on cuda:{clips.device.index}, the library is on device '
+                               f'{nat.current_device()} (dsp_set_device)')
+        dev = clips.device if on_device else torch.device('cuda', nat.current_device())
+        stream = torch.cuda.current_stream(dev)
+        st = _stream_ptr(stream)
+        hold = []
+        if on_device:
+            _wave_dtype_of(clips)                    # TypeError for anything but int16 / float32
+            if not clips.is_contiguous():            # a strided view: one copy on the stream of the launches, held to the end
+                clips = clips.contiguous()
+            hold.append(clips)
+        if plan is None:
+            plan = self._plan(so, rates, dev, on_device)
+        C = plan.groups[0].lay.D
+        width = 3 * C + (2 if use_pitch else 0) + (2 if use_timefeat else 0)
+        inp = torch.empty((self.max_len, B, width), dtype=torch.float32, device=dev)
+        len0 = torch.empty(B, dtype=torch.int32, device=dev)
+        d_jit = None
+        if jitter is not None:                       # one upload, rows in group order: each group reads its own slice
+            j = np.ascontiguousarray(jitter, dtype=np.int64).reshape(B, 2)
+            d_jit = torch.from_numpy(np.ascontiguousarray(j[plan.order])).to(dev)
+            hold.append(d_jit)
+        group_waves, row = [], 0
+        for g in plan.groups:
+            wave = self._group_wave(clips, plan, g, dev, st)
+            m0 = torch.empty(max(g.lay.frames_bound, 1) * C, dtype=torch.float32, device=dev)
+            group_waves.append(wave)
+            hold += [wave, m0]
+            hold += self._mfb(g.rate).enqueue_placed(
+                wave.data_ptr(), _wave_dtype_of(wave), g.lay, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(),
+                None if g.d_index is None else g.d_index.data_ptr(), B, width, stream, dev,
+                d_jitter=None if d_jit is None else d_jit.data_ptr() + 16 * row, use_pitch=use_pitch, use_timefeat=use_timefeat)
+            row += len(g.index)
+        return types.SimpleNamespace(inp=inp, len0=len0, plan=plan, group_waves=group_waves, hold=hold, st=st, dev=dev)
+
+    @staticmethod
+    def _finish(ctx):
+        """Endpoints [B, 2] (samples of each clip's own rate, endpoint.py:64) and len0 to the host: the call's one
+        synchronisation; afterwards the temporaries of the launches may go."""
+        from . import _native as nat
+        plan = ctx.plan
+        endpoints = np.zeros((plan.B, 2), dtype=np.int64)
+        for g in plan.groups:
+            endpoints[g.index] = g.lay.d_seg.download((len(g.index), 2), np.int64, ctx.st)
+        nat.check(nat.load().dsp_stream_synchronize(ctx.st))
+        len0 = ctx.len0.cpu().numpy()
+        ctx.hold = []
+        return len0, endpoints
+
+    def run(self, waves, sample_offsets=None, rates=None, jitter=None, use_pitch=False, use_timefeat=False):
+        """``waves``: concatenated clips as a host 1-D array or a 1-D device tensor (int16 / float32, any view) with
+        ``sample_offsets`` [B + 1], or a list of B host arrays; ``rates``: [B] sample rates.  -> (inp [max_len, B, 39 (+2)
+        (+2)] on the library's device, len0 [B], endpoints [B, 2]), all in batch order; ``jitter`` / ``use_pitch`` /
+        ``use_timefeat`` as ModelFeatureBatch.run, each clip at its own rate's framings and decimation (model.py:90-101).
+        A batch with a single rate is ModelFeatureBatch(rate).run."""
+        ctx = self._launch(waves, sample_offsets, rates, jitter, use_pitch, use_timefeat)
+        len0, endpoints = self._finish(ctx)
+        return ctx.inp, len0, endpoints
+
+    def capture(self, waves, sample_offsets, rates):
+        """A HIP graph of the default call over device-resident ``waves`` (contiguous 1-D tensor, int16 / float32):
+        ``g = mr.capture(waves, so, rates)``; write new clips of the same lengths and rates into ``waves`` and call
+        ``g.replay()`` -> (inp [max_len, B, 39], len0 [B] int32), on the device, valid after the current stream's work (no
+        host synchronisation).  The sub-pipelines are queued one after the other on the capture stream: the graph is one
+        chain, no forked branches.  One eager call runs first (it builds the layouts' long-lived index tables)."""
+        import torch
+        from .batch import _is_device_tensor
+        if not _is_device_tensor(waves):
+            raise TypeError('capture needs a device tensor')
+        if not waves.is_contiguous():
+            raise ValueError('capture needs a contiguous waves tensor: the graph reads it in place on every replay')
+        clips, so, rates = self._inputs(waves, sample_offsets, rates)
+        dev = waves.device
+        plan = _MixedPlan(self, so, rates, dev, True)          # the graph's own: nothing else writes its tables
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            warm = self._launch(waves, so, rates, plan=plan)
+        side.synchronize()
+        del warm
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            ctx = self._launch(waves, so, rates, plan=plan)
+        return _MixedRateGraph(graph, waves, plan, ctx.inp, ctx.len0, ctx.hold)
+
+
+_DEFAULT_MIXED = None
+
+
+def get_batch_full(feat, augment=False, rng=None, use_pitch=False, use_timefeat=False):
+    """RNNModel.get_batch_full (model.py:114-135) with the reference's signature: ``feat`` is the list of (sig, rate) pairs
+    reader.mini_batch_iterator yields (``sig`` any 1-D numeric array, the strided ``sig[:, 0]`` of reader.py:80 included;
+    the rates may differ from clip to clip).  -> (inp [200, B, 39 (+2) (+2)] torch tensor on the library's device, len0
+    NumPy [B]) in batch order, as model.py:135.  ``augment=True`` (model.py:144) draws the endpoint jitter from ``rng``, a
+    ``random.Random`` -- by default the module-level generator the reference uses -- in the reference's order."""
+    global _DEFAULT_MIXED
+    import random
+    if _DEFAULT_MIXED is None:
+        _DEFAULT_MIXED = MixedRateFeatureBatch()
+    sigs = [np.asarray(sig) for sig, _ in feat]
+    rates = [rate for _, rate in feat]
+    jitter = MixedRateFeatureBatch.draw_jitter(rates, rng if rng is not None else random) if augment else None
+    inp, len0, _ = _DEFAULT_MIXED.run(sigs, None, rates, jitter=jitter, use_pitch=use_pitch, use_timefeat=use_timefeat)
+    return inp, len0

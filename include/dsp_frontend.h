@@ -689,6 +689,47 @@ int dsp_ensemble_decide_batch(const float* d_logits, int64_t ld_logits, int32_t 
 int dsp_trim_preemph_batch(const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets, const int64_t* d_segments,
                            const int64_t* d_dst_offsets, int32_t n_utt, double coeff, float* d_out, void* stream);
 
+/* ---- mixed sample rates in one batch (RNNModel.get_batch_full on a shuffled batch, model.py:114-135) ---------------- */
+/*
+ * reader.mini_batch_iterator shuffles the file list and yields feat = [(sig, rate), ...] (reader.py:80), and the data set
+ * holds 44.1 kHz and 48 kHz recordings: model.py:114-135 runs endpoint_detect(sig, rate) and feature_extract_mfcc(s, r) with
+ * each clip's own rate.  Framing, window and mel table differ per rate, so a batch runs as one sub-batch per distinct rate;
+ * the entry points below let every sub-batch write its rows straight into the shared [max_len, B, width] tensor of
+ * model.py:131-135, and make the clips of one rate contiguous when they are not.
+ *
+ * The placed forms of the three kernels that write the classifier's input.  Utterance b of the call writes element
+ *   (t, dst_col[b], col_offset + k),  k < 3C (finalize) or 2 (the optional streams of model.py:90-101, 125-128),
+ * of a [max_len, n_cols, row_width] fp32 tensor, for every t < max_len (zero rows beyond the stream's own length,
+ * model.py:35-50); nothing outside those blocks is touched.  d_dst_col: [n_utt] DISTINCT columns in [0, n_cols) -- the
+ * caller guarantees it -- or NULL for the identity.  Checked before any launch: n_cols >= n_utt, col_offset >= 0,
+ * col_offset + the stream's width <= row_width, and what the unplaced entry point checks.  The values are the unplaced entry
+ * points' bit for bit: the kernels are the same, the unplaced calls pass the identity.
+ *
+ * dsp_model_finalize_placed_batch covers both sources: d_segments / d_work NULL = dsp_model_finalize_batch, both set =
+ * dsp_model_finalize_segments_batch.  d_len0 is [n_cols]: utterance b's min(T_b, max_len) goes to d_len0[dst_col[b]].
+ */
+int dsp_model_finalize_placed_batch(const float* d_mfcc, int64_t ld_in, const int64_t* d_frame_offsets,
+                                    const int64_t* d_segments, const void* d_work, int32_t n_utt, int32_t C, int32_t N,
+                                    int32_t max_len, float* d_out, int32_t* d_len0, const int32_t* d_dst_col, int32_t n_cols,
+                                    int32_t row_width, int32_t col_offset, void* stream);
+/* dsp_model_timefeat_batch (model.py:97-101) and dsp_model_pitchfeat_batch (model.py:90-95), placed. */
+int dsp_model_timefeat_placed_batch(const double* d_amp_sum, const int64_t* d_frame_offsets, int32_t n_utt, int32_t frame_len,
+                                    int32_t max_len, float* d_out, const int32_t* d_dst_col, int32_t n_cols, int32_t row_width,
+                                    int32_t col_offset, void* stream);
+int dsp_model_pitchfeat_placed_batch(const double* d_pitch, const int64_t* d_frame_offsets, int32_t n_utt, int32_t max_len,
+                                     float* d_out, const int32_t* d_dst_col, int32_t n_cols, int32_t row_width,
+                                     int32_t col_offset, void* stream);
+
+/*
+ * Clip d_pick[i] of the source batch (samples [d_sample_offsets[p], d_sample_offsets[p + 1]) of d_wave, p = d_pick[i]) is
+ * copied, sample type kept (int16 stays int16, reader.py:80), to d_out + d_dst_offsets[i] (in samples), i < n_pick.  A plain
+ * copy: 16-byte vectors where source and destination are equally aligned, element by element elsewhere; several workgroups
+ * per clip.  Needed only when the clips of one rate do not already form one contiguous run of the device buffer.
+ * n_pick = 0 is a no-op, n_pick <= 65535 (one grid row per clip); the regions must not overlap d_wave.
+ */
+int dsp_gather_clips_batch(const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets, const int32_t* d_pick,
+                           int32_t n_pick, const int64_t* d_dst_offsets, void* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

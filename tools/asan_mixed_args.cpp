@@ -1,0 +1,97 @@
+// Stand-alone host check of the mixed-rate entry points (include/dsp_frontend.h: dsp_model_finalize_placed_batch,
+// dsp_model_timefeat_placed_batch, dsp_model_pitchfeat_placed_batch, dsp_gather_clips_batch; csrc/dsp_frontend.hip).  Every
+// argument error is DSP_EINVAL with a message before any device call, and under dsp_debug_host_dry_run(1) a call whose
+// arguments pass every check is refused instead of launched: the program needs no GPU.
+// `make -C dsp-speech-recognition_amd/csrc asan-mixed` builds it with AddressSanitizer + UBSan against the sanitized build
+// of the library and runs it; it needs no preloaded runtime.
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "dsp_frontend.h"
+
+static int g_bad = 0;
+
+static void expect(int rc, const char* what, int line) {
+    const char* e = dsp_last_error();
+    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
+        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
+        ++g_bad;
+    }
+}
+#define EXPECT(call, what) expect((call), (what), __LINE__)
+
+int main() {
+    dsp_debug_host_dry_run(1);
+    alignas(16) static float rows[64];               // pointers that are only checked, never followed
+    alignas(16) static double dbl[64];
+    alignas(16) static int32_t ints[64];
+    alignas(16) static int16_t pcm[64];
+    static int64_t offs[8];
+    const int C = 13;
+
+    // valid arguments, every form: checked to the end, then refused because nothing may be launched here
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 3, C, 3, 200, rows, ints, ints, 9, 44, 2, nullptr), "dry_run");
+    EXPECT(dsp_model_finalize_placed_batch(rows, 0, offs, offs, dbl, 3, C, 3, 200, rows, ints, nullptr, 3, 39, 0, nullptr), "dry_run");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 3, C, 3, 200, rows, ints, ints, 3, 44, 5, nullptr), "dry_run");
+    EXPECT(dsp_model_timefeat_placed_batch(dbl, offs, 3, 1323, 200, rows, ints, 9, 43, 41, nullptr), "dry_run");
+    EXPECT(dsp_model_timefeat_placed_batch(dbl, offs, 3, 480, 200, rows, nullptr, 3, 2, 0, nullptr), "dry_run");
+    EXPECT(dsp_model_pitchfeat_placed_batch(dbl, offs, 3, 200, rows, ints, 9, 43, 39, nullptr), "dry_run");
+    EXPECT(dsp_model_pitchfeat_placed_batch(dbl, offs, 1, 200, rows, nullptr, 1, 2, 0, nullptr), "dry_run");
+    EXPECT(dsp_gather_clips_batch(pcm, DSP_WAVE_I16, offs, ints, 3, offs, pcm, nullptr), "dry_run");
+    EXPECT(dsp_gather_clips_batch(rows, DSP_WAVE_F32, offs, ints, 0, offs, rows, nullptr), "dry_run");
+
+    // the placement
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 3, C, 3, 200, rows, ints, ints, 2, 44, 2, nullptr), "n_cols");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 3, C, 3, 200, rows, ints, ints, -1, 44, 2, nullptr), "n_cols");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 3, C, 3, 200, rows, ints, ints, 9, 44, -1, nullptr), "col_offset");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 3, C, 3, 200, rows, ints, ints, 9, 44, 6, nullptr), "row_width");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 3, C, 3, 200, rows, ints, ints, 9, 44, INT32_MAX, nullptr), "row_width");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 3, C, 3, 200, rows, ints, ints, 9, 0, 0, nullptr), "row_width");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 3, C, 3, 200, rows, ints, ints, 9, -44, 0, nullptr), "row_width");
+    // ... and what the unplaced entry points check
+    EXPECT(dsp_model_finalize_placed_batch(nullptr, C, offs, nullptr, nullptr, 3, C, 3, 200, rows, ints, ints, 9, 44, 2, nullptr), "NULL");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, nullptr, nullptr, nullptr, 3, C, 3, 200, rows, ints, ints, 9, 44, 2, nullptr), "NULL");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 3, C, 3, 200, nullptr, ints, ints, 9, 44, 2, nullptr), "NULL");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 3, C, 3, 200, rows, nullptr, ints, 9, 44, 2, nullptr), "NULL");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 0, C, 3, 200, rows, ints, ints, 9, 44, 2, nullptr), "n_utt");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, offs, nullptr, 3, C, 3, 200, rows, ints, ints, 9, 44, 2, nullptr), "go together");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, dbl, 3, C, 3, 200, rows, ints, ints, 9, 44, 2, nullptr), "go together");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 3, C, 0, 200, rows, ints, ints, 9, 44, 2, nullptr), "N must be");
+    EXPECT(dsp_model_finalize_placed_batch(rows, 33, offs, nullptr, nullptr, 3, 33, 3, 200, rows, ints, ints, 9, 200, 2, nullptr), "C <= 32");
+    EXPECT(dsp_model_finalize_placed_batch(rows, C, offs, nullptr, nullptr, 3, C, 3, 0, rows, ints, ints, 9, 44, 2, nullptr), "max_len");
+    EXPECT(dsp_model_finalize_placed_batch(rows, 12, offs, nullptr, nullptr, 3, C, 3, 200, rows, ints, ints, 9, 44, 2, nullptr), "ld_in");
+    EXPECT(dsp_model_finalize_placed_batch(rows, 32, offs, nullptr, nullptr, 3, 32, 3, 400, rows, ints, ints, 9, 100, 2, nullptr), "LDS");
+
+    EXPECT(dsp_model_timefeat_placed_batch(nullptr, offs, 3, 1323, 200, rows, ints, 9, 43, 41, nullptr), "NULL");
+    EXPECT(dsp_model_timefeat_placed_batch(dbl, nullptr, 3, 1323, 200, rows, ints, 9, 43, 41, nullptr), "NULL");
+    EXPECT(dsp_model_timefeat_placed_batch(dbl, offs, 3, 1323, 200, nullptr, ints, 9, 43, 41, nullptr), "NULL");
+    EXPECT(dsp_model_timefeat_placed_batch(dbl, offs, 0, 1323, 200, rows, ints, 9, 43, 41, nullptr), "n_utt");
+    EXPECT(dsp_model_timefeat_placed_batch(dbl, offs, 3, 0, 200, rows, ints, 9, 43, 41, nullptr), "frame_len");
+    EXPECT(dsp_model_timefeat_placed_batch(dbl, offs, 3, 1323, 0, rows, ints, 9, 43, 41, nullptr), "max_len");
+    EXPECT(dsp_model_timefeat_placed_batch(dbl, offs, 3, 1323, 200, rows, ints, 2, 43, 41, nullptr), "n_cols");
+    EXPECT(dsp_model_timefeat_placed_batch(dbl, offs, 3, 1323, 200, rows, ints, 9, 43, -1, nullptr), "col_offset");
+    EXPECT(dsp_model_timefeat_placed_batch(dbl, offs, 3, 1323, 200, rows, ints, 9, 43, 42, nullptr), "row_width");
+
+    EXPECT(dsp_model_pitchfeat_placed_batch(nullptr, offs, 3, 200, rows, ints, 9, 43, 39, nullptr), "NULL");
+    EXPECT(dsp_model_pitchfeat_placed_batch(dbl, nullptr, 3, 200, rows, ints, 9, 43, 39, nullptr), "NULL");
+    EXPECT(dsp_model_pitchfeat_placed_batch(dbl, offs, 3, 200, nullptr, ints, 9, 43, 39, nullptr), "NULL");
+    EXPECT(dsp_model_pitchfeat_placed_batch(dbl, offs, 0, 200, rows, ints, 9, 43, 39, nullptr), "n_utt");
+    EXPECT(dsp_model_pitchfeat_placed_batch(dbl, offs, 3, 0, rows, ints, 9, 43, 39, nullptr), "max_len");
+    EXPECT(dsp_model_pitchfeat_placed_batch(dbl, offs, 3, 200, rows, ints, 2, 43, 39, nullptr), "n_cols");
+    EXPECT(dsp_model_pitchfeat_placed_batch(dbl, offs, 3, 200, rows, ints, 9, 43, -2, nullptr), "col_offset");
+    EXPECT(dsp_model_pitchfeat_placed_batch(dbl, offs, 3, 200, rows, ints, 9, 43, INT32_MAX - 1, nullptr), "row_width");
+
+    EXPECT(dsp_gather_clips_batch(nullptr, DSP_WAVE_I16, offs, ints, 3, offs, pcm, nullptr), "NULL");
+    EXPECT(dsp_gather_clips_batch(pcm, DSP_WAVE_I16, nullptr, ints, 3, offs, pcm, nullptr), "NULL");
+    EXPECT(dsp_gather_clips_batch(pcm, DSP_WAVE_I16, offs, nullptr, 3, offs, pcm, nullptr), "NULL");
+    EXPECT(dsp_gather_clips_batch(pcm, DSP_WAVE_I16, offs, ints, 3, nullptr, pcm, nullptr), "NULL");
+    EXPECT(dsp_gather_clips_batch(pcm, DSP_WAVE_I16, offs, ints, 3, offs, nullptr, nullptr), "NULL");
+    EXPECT(dsp_gather_clips_batch(pcm, DSP_WAVE_I16, offs, ints, -1, offs, pcm, nullptr), "n_pick");
+    EXPECT(dsp_gather_clips_batch(pcm, 2, offs, ints, 3, offs, pcm, nullptr), "wave_dtype");
+    EXPECT(dsp_gather_clips_batch(pcm, -1, offs, ints, 3, offs, pcm, nullptr), "wave_dtype");
+
+    dsp_debug_host_dry_run(0);
+    std::printf("asan_mixed_args: %s\n", g_bad ? "FAILED" : "ok");
+    return g_bad ? 1 : 0;
+}
