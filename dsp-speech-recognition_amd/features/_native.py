@@ -54,6 +54,13 @@ class SvmDesc(C.Structure):
     ]
 
 
+class AttnDesc(C.Structure):
+    _fields_ = [
+        ('d_model', c_i32), ('d_inner', c_i32), ('n_head', c_i32), ('d_k', c_i32), ('d_v', c_i32), ('eps', c_f32),
+        ('d_params', c_vp * 16),
+    ]
+
+
 class EnsembleRule(C.Structure):
     _fields_ = [('label_a', c_i32), ('label_b', c_i32), ('threshold', c_f64), ('svm', c_vp)]
 
@@ -145,6 +152,11 @@ SIGNATURES = {
     'dsp_model_timefeat_placed_batch': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     'dsp_model_pitchfeat_placed_batch': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     'dsp_gather_clips_batch': (C.c_int, [c_vp, C.c_int, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    'dsp_attn_create': (C.c_int, [C.POINTER(AttnDesc), C.POINTER(c_vp)]),
+    'dsp_attn_destroy': (C.c_int, [c_vp]),
+    'dsp_attn_workspace_bytes': (C.c_int, [c_vp, c_i32, c_i32, C.POINTER(c_i64)]),
+    'dsp_attn_forward': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
+    'dsp_selfattn_pool_batch': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

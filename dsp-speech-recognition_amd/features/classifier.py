@@ -16,6 +16,9 @@ the time axis of the GRU output is max(len0), not the padded 200, and the max po
 The encoder in front of every head (``_DynEnc``) has a native forward pass (csrc/kernels_bigru.h) beside the ``nn.GRU`` route;
 both yield max(len0) rows with zero rows behind each end, so the pooling above is the same on either.  With a gradient
 required, ``native_enc=True`` takes the native training path (``_DynEncTrain``, csrc/kernels_bigru_bwd.h).
+
+The two attention blocks -- ``_TransformerEncoder`` in front of ``TransformerHead`` and ``_SelfAttn``, the pooling of
+``HRNNAttHead`` -- have opt-in native forward passes as well (csrc/kernels_attn.h), reached through ``native_attn=True``.
 """
 import numpy as np
 import torch
@@ -332,11 +335,11 @@ class RNNHead(nn.Module):
         return self.out(torch.cat([avg, mx], dim=1))
 
 
-def _pool_head(y, lens, out, attn=None):
+def _pool_head(y, lens, out, attn=None, native_attn=None):
     """The pooled features of rnn_clf.py:68-72 / 107-115: sum over time / length (or the self-attention vector) || max over
     time -- both over the zero rows pad_packed_sequence leaves behind shorter utterances -- and the pre-dropout logits."""
     n = torch.as_tensor(np.asarray(lens), dtype=y.dtype, device=y.device)
-    first = attn(y) if attn is not None else y.sum(0) / n.unsqueeze(1)
+    first = attn(y, native=native_attn) if attn is not None else y.sum(0) / n.unsqueeze(1)
     feat = torch.cat([first, y.max(0).values], dim=1)
     return out(feat), feat
 
@@ -367,18 +370,77 @@ class HRNNHead(nn.Module):
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
 
 
+def _attn_needs_grad(x, module):
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
+
+
+def _attn_input_reason(x, params):
+    """The reasons common to both attention blocks' native paths: device, dtype, parameter layout, library."""
+    from . import _native as nat
+    import os
+    if x.dtype != torch.float32 or any(p.dtype != torch.float32 or p.device != x.device for p in params):
+        return 'input and parameters must be float32 on one device'
+    if not x.is_cuda:
+        return 'the input is not on a GPU'
+    if any(not p.is_contiguous() for p in params):
+        return 'parameters must be contiguous'
+    if not os.path.exists(nat.LIB_PATH):
+        return f'{nat.LIB_PATH} is not built'
+    return None
+
+
 class _SelfAttn(nn.Module):
-    """layers.SelfAttn (layers.py:78-95): softmax over ALL rows of the padded output, zero rows included."""
+    """layers.SelfAttn (layers.py:78-95): softmax over ALL rows of the padded output, zero rows included.
+
+    Two paths compute the same thing: the torch chain below, and ``dsp_selfattn_pool_batch`` (csrc/kernels_attn.h: one launch,
+    forward only, fp32, on the parameter tensors in place on the current stream).  ``native=True`` insists on the native one
+    (and raises where it cannot run), ``native=False`` keeps torch, ``native=None`` picks native only where ``native_default``
+    says so."""
+    native_default = False         # opt-in until DESIGN 7.9's timing shows it ahead at every size
 
     def __init__(self, hidden_size):
         super().__init__()
         self.attn = nn.Linear(hidden_size, hidden_size)
         self.v = nn.Linear(hidden_size, 1)
 
-    def forward(self, y):
+    def native_supported(self, y):
+        """Why the native path cannot serve ``y`` [T, B, H] (a string), or None when it can."""
+        if _attn_needs_grad(y, self):
+            return 'a gradient is required (the native path is forward only)'
+        why = _attn_input_reason(y, list(self.parameters()))
+        if why is not None:
+            return why
+        T, H = y.shape[0], y.shape[2]
+        if not (1 <= T <= 1024 and 4 <= H <= 256 and H % 4 == 0 and H == self.attn.in_features):
+            return 'sizes out of range: T in [1, 1024], H a multiple of 4 in [4, 256]'
+        return None
+
+    def _run_native(self, y):
+        from . import _native as nat
+        T, B, H = y.shape
+        dev = y.device
+        yc = y.detach().contiguous()                                            # (a copy of a view is held until the call returns)
+        with torch.cuda.device(dev):
+            out = torch.empty(B, H, dtype=torch.float32, device=dev)
+            nat.check(nat.load().dsp_selfattn_pool_batch(yc.data_ptr(), T, B, H, self.attn.weight.data_ptr(), self.attn.bias.data_ptr(),
+                                                         self.v.weight.data_ptr(), self.v.bias.data_ptr(), out.data_ptr(),
+                                                         torch.cuda.current_stream(dev).cuda_stream))
+        return out
+
+    def _run_torch(self, y):
         y = y.transpose(0, 1)                                                   # [B, T, H]
         w = torch.softmax(self.v(torch.tanh(self.attn(y))).squeeze(2), 1)       # [B, T]
         return torch.bmm(w.unsqueeze(1), y).squeeze(1)
+
+    def forward(self, y, native=None):
+        if native is False or (native is None and not self.native_default):
+            return self._run_torch(y)
+        why = self.native_supported(y)
+        if why is None:
+            return self._run_native(y)
+        if native:
+            raise RuntimeError(f'_SelfAttn: the native path cannot run: {why}')
+        return self._run_torch(y)
 
 
 class HRNNAttHead(HRNNHead):
@@ -390,9 +452,9 @@ class HRNNAttHead(HRNNHead):
         super().__init__(feat_size)
         self.attn = _SelfAttn(200)
 
-    def forward(self, inp, len0, dropout=True, native_enc=None):
+    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None):
         y2, len1 = self._levels(inp, len0, native_enc)
-        out, feat = _pool_head(y2, len1, self.out, self.attn)
+        out, feat = _pool_head(y2, len1, self.out, self.attn, native_attn)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
 
 
@@ -457,14 +519,82 @@ class _PosFFN(nn.Module):
         return self.layer_norm(o + x)
 
 
-class _TransformerEncoder(nn.Module):
+class _TransformerEncoder(_NativeHandle, nn.Module):
+    """transformer.EncoderLayer (transformer.py:16-30): ``_MHA`` then ``_PosFFN`` over x [T, B, d_model], all T rows as given.
+
+    Two paths compute the same thing: the torch chain (any device, with gradients), and ``dsp_attn_forward``
+    (csrc/kernels_attn.h: three launches that never hold a [B, T, T] tensor; forward only, fp32, n_head = 1, on the current
+    stream).  ``native=True`` insists on the native one (and raises where it cannot run), ``native=False`` keeps torch,
+    ``native=None`` picks native only where ``native_default`` says so."""
+    native_default = False         # opt-in until DESIGN 7.9's timing shows it ahead at every size
+    _lib = 'dsp_attn'
+
     def __init__(self, d_model, d_inner, n_head, d_k, d_v):
         super().__init__()
+        self.d_model, self.d_inner = d_model, d_inner
         self.slf_attn = _MHA(n_head, d_model, d_k, d_v)
         self.pos_ffn = _PosFFN(d_model, d_inner)
 
-    def forward(self, x):
+    def _params(self):
+        """Module order: w_qs, w_ks, w_vs, LN1 a_2, b_2, proj weight, bias, w_1 weight, bias, w_2 weight, bias, LN2 a_2, b_2."""
+        return list(self.parameters())
+
+    def native_supported(self, x):
+        """Why the native path cannot serve ``x`` [T, B, d_model] (a string), or None when it can."""
+        a = self.slf_attn
+        if a.n_head != 1:
+            return f'n_head is {a.n_head}: the native path serves n_head = 1'
+        if _attn_needs_grad(x, self):
+            return 'a gradient is required (the native path is forward only)'
+        why = _attn_input_reason(x, self._params())
+        if why is not None:
+            return why
+        ok4 = lambda v, hi: 4 <= v <= hi and v % 4 == 0
+        if not (1 <= self.d_model <= 64 and ok4(a.d_k, 128) and ok4(a.d_v, 128) and ok4(self.d_inner, 256)
+                and 1 <= x.shape[0] <= 1024 and x.shape[2] == self.d_model):
+            return 'sizes out of range: d_model in [1, 64], d_k and d_v multiples of 4 in [4, 128], d_inner a multiple of 4 in [4, 256], T in [1, 1024]'
+        if a.layer_norm.eps != self.pos_ffn.layer_norm.eps:
+            return 'the two layer norms differ in eps'
+        return None
+
+    def _descriptor(self, nat):
+        a = self.slf_attn
+        d = nat.AttnDesc(self.d_model, self.d_inner, a.n_head, a.d_k, a.d_v, a.layer_norm.eps)
+        ps = self._params()
+        d.d_params[:len(ps)] = [p.data_ptr() for p in ps]
+        return d
+
+    def _run_native(self, x):
+        from . import _native as nat
+        T, B, d = x.shape
+        dev = x.device
+        xc = x.detach().contiguous()                                            # (a copy of a view is held until the call returns)
+        with torch.cuda.device(dev):
+            handle = self._native_handle(dev)
+            lib = nat.load()
+            nbytes = nat.c_i64(0)
+            nat.check(lib.dsp_attn_workspace_bytes(handle, T, B, nat.C.byref(nbytes)))
+            work = torch.empty(nbytes.value // 4, dtype=torch.float32, device=dev)
+            y = torch.empty(T, B, d, dtype=torch.float32, device=dev)
+            nat.check(lib.dsp_attn_forward(handle, xc.data_ptr(), T, B, y.data_ptr(), work.data_ptr(), nbytes.value,
+                                           torch.cuda.current_stream(dev).cuda_stream))
+        return y
+
+    def _run_torch(self, x):
         return self.pos_ffn(self.slf_attn(x))
+
+    def run(self, x, native=None):
+        if native is False or (native is None and not self.native_default):
+            return self._run_torch(x)
+        why = self.native_supported(x)
+        if why is None:
+            return self._run_native(x)
+        if native:
+            raise RuntimeError(f'_TransformerEncoder: the native path cannot run: {why}')
+        return self._run_torch(x)
+
+    def forward(self, x, native=None):
+        return self.run(x, native)
 
 
 class TransformerHead(nn.Module):
@@ -481,10 +611,10 @@ class TransformerHead(nn.Module):
         self.out = nn.Linear(400, 20)
         self.hidden_size = 200
 
-    def forward(self, inp, len0, dropout=True, native_enc=None):
+    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None):
         len0 = _lengths(len0)
         len1 = (len0 + self.hir - 1) // self.hir
-        attn_out = self.attn_enc(inp)
+        attn_out = self.attn_enc(inp, native=native_attn)
         a = torch.nn.functional.dropout(attn_out, 0.5) if dropout else attn_out
         # (the reference concatenates all 200 padded rows; the packed GRU then reads max(len0) of them)
         y = self.rnn_enc_1(torch.cat([inp, a], 2), len0, native=native_enc)[:, :, -self.hidden_size:]

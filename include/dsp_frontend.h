@@ -730,6 +730,74 @@ int dsp_model_pitchfeat_placed_batch(const double* d_pitch, const int64_t* d_fra
 int dsp_gather_clips_batch(const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets, const int32_t* d_pick,
                            int32_t n_pick, const int64_t* d_dst_offsets, void* d_out, void* stream);
 
+/* ---- the attention blocks: rnn_clf.Transformer's encoder layer and rnn_clf.HRNN_Att's pooling (forward, fp32) ------- */
+/*
+ * transformer.EncoderLayer with n_head = 1 (transformer.py:16-140: MultiHeadAttention, ScaledDotProductAttention,
+ * PositionwiseFeedForward; layers.py:125-143: LayerNormalization) over x [T, B, d_model].  ALL T rows as given take part (no
+ * length mask: the zero rows behind short utterances count too).  Per utterance b, with x_b [T, d]:
+ *   q = x_b w_qs, k = x_b w_ks, v = x_b w_vs                                        transformer.py:98-100
+ *   s[b,t,u] = tanh(q[b,t]) . k[b,u] / sqrt(d_model)                                transformer.py:38,50-52 (tanh on q only)
+ *   a[b,t,u] = exp(s[b,t,u]) / sum_b' exp(s[b',t,u])                                transformer.py:41,56: nn.Softmax() without a dim
+ *                                                                                   on a 3-D tensor is a softmax over the BATCH axis
+ *   o[b,t] = sum_u a[b,t,u] v[b,u];   z1 = LN1(proj(o) + x[b,t])                    transformer.py:58,112-121
+ *   y[b,t] = LN2(w_2 relu(w_1 z1 + b_1) + b_2 + z1)                                 transformer.py:134-139
+ *   LN(z) = (z - mean) / (std_unbiased + eps) * a_2 + b_2                           layers.py:138-142
+ * layers.py:136 returns z unchanged when z.size(1) == 1: LN1 sees [B, T, d] and is skipped when T == 1, LN2 sees [T, B, d]
+ * and is skipped when B == 1.  Utterances are coupled through the softmax; at B == 1 every weight is exactly 1.
+ *
+ * Three launches on `stream` (csrc/kernels_attn.h): a projection, the statistics max_b s and sum_b exp(s - max) for every
+ * (t, u), and the output, which recomputes the scores; no [B, T, T] tensor exists.  The maximum is subtracted (scores beyond
+ * +-88 do not overflow), the sum over b runs in a fixed order without atomics (the same arguments give the same bits).
+ *
+ * d_params: DSP_ATTN_PARAMS DEVICE pointers in the module's parameter order, row-major as torch holds them:
+ *   slf_attn.w_qs [1, d_model, d_k], w_ks [1, d_model, d_k], w_vs [1, d_model, d_v], slf_attn.layer_norm.a_2, b_2 [d_model],
+ *   slf_attn.proj.weight [d_model, d_v], bias [d_model], pos_ffn.w_1.weight [d_inner, d_model, 1], bias [d_inner],
+ *   pos_ffn.w_2.weight [d_model, d_inner, 1], bias [d_model], pos_ffn.layer_norm.a_2, b_2 [d_model].
+ * Sizes out of range, n_head != 1 or a NULL parameter are DSP_EINVAL, checked before any device call.  Create copies and
+ * repacks the parameters on the current device (blocking: it must not run inside a stream capture); the handle is immutable
+ * afterwards, belongs to that device and may be used from several streams.  Under dsp_debug_host_dry_run(1) d_params are read as
+ * HOST memory and the packed copy stays there: such a handle can only be destroyed, launches are refused.
+ */
+#define DSP_ATTN_PARAMS 13
+typedef struct dsp_attn dsp_attn;
+typedef struct dsp_attn_desc {
+    int32_t d_model;      /* 1 .. 64; rows of x need no alignment beyond a float's (39 in the shipped head) */
+    int32_t d_inner;      /* multiple of 4 in [4, 256] */
+    int32_t n_head;       /* 1 */
+    int32_t d_k, d_v;     /* multiples of 4 in [4, 128] */
+    float eps;            /* layers.py:128: 1e-3 */
+    const float* d_params[16];
+} dsp_attn_desc;
+int dsp_attn_create(const dsp_attn_desc* desc, dsp_attn** out);
+int dsp_attn_destroy(dsp_attn* h);
+/*
+ * bytes of the workspace dsp_attn_forward needs at (T, B), T in [1, 1024], B >= 1: zero-padded copies of x and of the folded
+ * queries, 2 B T' D' floats (T', D': T and d_model rounded up to 16), and the two [T', T'] statistics.  No term grows with B T T:
+ * 41 MB at (200, 512) and d_model 39, half of one [B, T, T] fp32 tensor.
+ */
+int dsp_attn_workspace_bytes(const dsp_attn* h, int32_t T, int32_t B, int64_t* bytes);
+/*
+ * d_x, d_y: [T, B, d_model] fp32, dense; every element of d_y is written on every call, d_x is only read (d_y == d_x is not
+ * supported).  d_work: the caller's buffer of at least dsp_attn_workspace_bytes bytes, 16-byte aligned, so that the call
+ * allocates nothing and can be captured into a HIP graph.
+ */
+int dsp_attn_forward(const dsp_attn* h, const float* d_x, int32_t T, int32_t B, float* d_y, void* d_work, int64_t work_bytes,
+                     void* stream);
+
+/*
+ * layers.SelfAttn (layers.py:78-95) over d_y [T, B, H] fp32, dense and 16-byte aligned:
+ *   e[t,b] = d_v . tanh(d_W y[t,b] + d_bW) + d_c[0]                  layers.py:88-90 (attn: Linear(H, H), v: Linear(H, 1))
+ *   w[.,b] = softmax of e[.,b] over ALL T rows                       layers.py:91 -- the zero rows behind a short utterance get
+ *                                                                    e = d_v . tanh(d_bW) + d_c[0] and a non-zero weight
+ *   d_out[b] = sum_t w[t,b] y[t,b]                                   layers.py:93-94, [B, H]
+ * d_W [H, H] (16-byte aligned), d_bW [H], d_v [H] and d_c [1] are torch's own parameter tensors (attn.weight, attn.bias,
+ * v.weight, v.bias), read in place: there is no handle.  One launch on `stream`, one wavefront per column, sums in a fixed
+ * order; nothing is allocated (capturable).  T in [1, 1024], B >= 1, H a multiple of 4 in [4, 256]; anything else, a NULL or
+ * misaligned pointer is DSP_EINVAL, checked before any device call.
+ */
+int dsp_selfattn_pool_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
+                            const float* d_c, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,131 @@
+// Stand-alone host check of the attention entry points (include/dsp_frontend.h: dsp_attn_create, dsp_attn_destroy,
+// dsp_attn_workspace_bytes, dsp_attn_forward, dsp_selfattn_pool_batch; csrc/dsp_attn.hip).  Under dsp_debug_host_dry_run(1)
+// create reads its parameters as host memory and packs them there, so the packing runs here -- on exact-size arrays, where a
+// read past either end of a parameter is a report -- and every argument error is DSP_EINVAL with a message before any device
+// call: the program needs no GPU.  `make -C dsp-speech-recognition_amd/csrc asan-attn` builds it with AddressSanitizer + UBSan
+// against the sanitized build of the library and runs it; it needs no preloaded runtime.
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "dsp_frontend.h"
+
+static int g_bad = 0;
+
+static void expect(int rc, const char* what, int line) {
+    const char* e = dsp_last_error();
+    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
+        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
+        ++g_bad;
+    }
+}
+static void expect_ok(int rc, int line) {
+    if (rc != DSP_OK) {
+        const char* e = dsp_last_error();
+        std::printf("line %d: rc %d, message '%s', expected DSP_OK\n", line, rc, e ? e : "(none)");
+        ++g_bad;
+    }
+}
+#define EXPECT(call, what) expect((call), (what), __LINE__)
+#define EXPECT_OK(call) expect_ok((call), __LINE__)
+
+// The 13 parameters of a block as exact-size host arrays.
+struct Block {
+    std::vector<std::vector<float>> p;
+    dsp_attn_desc d;
+    Block(int dm, int di, int dk, int dv) {
+        const size_t n[DSP_ATTN_PARAMS] = {(size_t)dm * dk, (size_t)dm * dk, (size_t)dm * dv, (size_t)dm, (size_t)dm, (size_t)dm * dv, (size_t)dm,
+                                           (size_t)di * dm, (size_t)di, (size_t)dm * di, (size_t)dm, (size_t)dm, (size_t)dm};
+        d = dsp_attn_desc{dm, di, 1, dk, dv, 1e-3f, {}};
+        for (int i = 0; i < DSP_ATTN_PARAMS; ++i) {
+            p.emplace_back(n[i]);
+            for (size_t j = 0; j < n[i]; ++j) p[i][j] = 0.001f * (float)((j * 7 + i) % 311) - 0.1f;
+            d.d_params[i] = p[i].data();
+        }
+    }
+};
+
+int main() {
+    dsp_debug_host_dry_run(1);
+    const int sizes[][4] = {{39, 200, 100, 100}, {6, 8, 4, 12}, {1, 4, 4, 4}, {64, 256, 128, 128}, {17, 36, 20, 52}};
+    dsp_attn* keep = nullptr;
+    for (const auto& s : sizes) {
+        Block blk(s[0], s[1], s[2], s[3]);
+        dsp_attn* h = nullptr;
+        EXPECT_OK(dsp_attn_create(&blk.d, &h));
+        if (h && !keep) { keep = h; continue; }
+        EXPECT_OK(dsp_attn_destroy(h));
+    }
+    EXPECT_OK(dsp_attn_destroy(nullptr));
+
+    Block good(39, 200, 100, 100);
+    dsp_attn* h = nullptr;
+    EXPECT(dsp_attn_create(nullptr, &h), "NULL argument");
+    EXPECT(dsp_attn_create(&good.d, nullptr), "NULL argument");
+    { dsp_attn_desc d = good.d; d.n_head = 2; EXPECT(dsp_attn_create(&d, &h), "n_head 2 must be 1"); }
+    { dsp_attn_desc d = good.d; d.d_model = 0; EXPECT(dsp_attn_create(&d, &h), "d_model 0 must be in [1, 64]"); }
+    { dsp_attn_desc d = good.d; d.d_model = 65; EXPECT(dsp_attn_create(&d, &h), "d_model 65 must be in [1, 64]"); }
+    { dsp_attn_desc d = good.d; d.d_k = 102; EXPECT(dsp_attn_create(&d, &h), "must be multiples of 4 in [4, 128]"); }
+    { dsp_attn_desc d = good.d; d.d_k = 0; EXPECT(dsp_attn_create(&d, &h), "must be multiples of 4 in [4, 128]"); }
+    { dsp_attn_desc d = good.d; d.d_v = 132; EXPECT(dsp_attn_create(&d, &h), "must be multiples of 4 in [4, 128]"); }
+    { dsp_attn_desc d = good.d; d.d_inner = 260; EXPECT(dsp_attn_create(&d, &h), "d_inner 260 must be a multiple of 4 in [4, 256]"); }
+    { dsp_attn_desc d = good.d; d.d_inner = 201; EXPECT(dsp_attn_create(&d, &h), "d_inner 201 must be a multiple of 4 in [4, 256]"); }
+    { dsp_attn_desc d = good.d; d.eps = std::numeric_limits<float>::quiet_NaN(); EXPECT(dsp_attn_create(&d, &h), "eps must be finite"); }
+    { dsp_attn_desc d = good.d; d.eps = -1.f; EXPECT(dsp_attn_create(&d, &h), "eps must be finite"); }
+    for (int i = 0; i < DSP_ATTN_PARAMS; ++i) {
+        dsp_attn_desc d = good.d;
+        d.d_params[i] = nullptr;
+        EXPECT(dsp_attn_create(&d, &h), "NULL parameter tensor");
+    }
+
+    if (keep) {
+        int64_t bytes = 0;
+        EXPECT(dsp_attn_workspace_bytes(nullptr, 200, 8, &bytes), "NULL argument");
+        EXPECT(dsp_attn_workspace_bytes(keep, 200, 8, nullptr), "NULL argument");
+        EXPECT(dsp_attn_workspace_bytes(keep, 0, 8, &bytes), "T 0 must be in [1, 1024]");
+        EXPECT(dsp_attn_workspace_bytes(keep, 1025, 8, &bytes), "T 1025 must be in [1, 1024]");
+        EXPECT(dsp_attn_workspace_bytes(keep, 200, 0, &bytes), "B 0 must be >= 1");
+        EXPECT(dsp_attn_workspace_bytes(keep, 1024, 0x7fffffff, &bytes), "more than one launch holds");
+        EXPECT_OK(dsp_attn_workspace_bytes(keep, 200, 512, &bytes));
+        if (bytes <= 0 || bytes >= (int64_t)4 * 512 * 200 * 200) { std::printf("workspace at (200, 512): %lld bytes\n", (long long)bytes); ++g_bad; }
+        EXPECT_OK(dsp_attn_workspace_bytes(keep, 5, 3, &bytes));
+        alignas(16) static float x[5 * 3 * 39], y[5 * 3 * 39], work[16];   // never reached: every call below returns before a launch
+        EXPECT(dsp_attn_forward(nullptr, x, 5, 3, y, work, bytes, nullptr), "NULL handle / input / output");
+        EXPECT(dsp_attn_forward(keep, nullptr, 5, 3, y, work, bytes, nullptr), "NULL handle / input / output");
+        EXPECT(dsp_attn_forward(keep, x, 5, 3, nullptr, work, bytes, nullptr), "NULL handle / input / output");
+        EXPECT(dsp_attn_forward(keep, x, 0, 3, y, work, bytes, nullptr), "T 0 must be in [1, 1024]");
+        EXPECT(dsp_attn_forward(keep, x, 5, -1, y, work, bytes, nullptr), "B -1 must be >= 1");
+        EXPECT(dsp_attn_forward(keep, x, 5, 3, y, nullptr, bytes, nullptr), "the workspace holds 0 bytes");
+        EXPECT(dsp_attn_forward(keep, x, 5, 3, y, work, bytes - 1, nullptr), "are needed");
+        EXPECT(dsp_attn_forward(keep, x, 5, 3, y, reinterpret_cast<char*>(work) + 4, bytes, nullptr), "d_work must be 16-byte aligned");
+        EXPECT(dsp_attn_forward(keep, x, 5, 3, y, work, bytes, nullptr), "dry_run: launches are refused");
+        EXPECT_OK(dsp_attn_destroy(keep));
+    } else {
+        std::printf("no handle was created\n");
+        ++g_bad;
+    }
+
+    alignas(16) static float yy[16], W[16], bW[4], v[4], c[1], out[4];
+    EXPECT(dsp_selfattn_pool_batch(nullptr, 1, 1, 4, W, bW, v, c, out, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_batch(yy, 1, 1, 4, nullptr, bW, v, c, out, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_batch(yy, 1, 1, 4, W, nullptr, v, c, out, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_batch(yy, 1, 1, 4, W, bW, nullptr, c, out, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_batch(yy, 1, 1, 4, W, bW, v, nullptr, out, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_batch(yy, 1, 1, 4, W, bW, v, c, nullptr, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_batch(yy, 0, 1, 4, W, bW, v, c, out, nullptr), "T 0 must be in [1, 1024]");
+    EXPECT(dsp_selfattn_pool_batch(yy, 1025, 1, 4, W, bW, v, c, out, nullptr), "T 1025 must be in [1, 1024]");
+    EXPECT(dsp_selfattn_pool_batch(yy, 1, 0, 4, W, bW, v, c, out, nullptr), "B 0 must be >= 1");
+    EXPECT(dsp_selfattn_pool_batch(yy, 1, 1, 0, W, bW, v, c, out, nullptr), "H 0 must be a multiple of 4 in [4, 256]");
+    EXPECT(dsp_selfattn_pool_batch(yy, 1, 1, 6, W, bW, v, c, out, nullptr), "H 6 must be a multiple of 4 in [4, 256]");
+    EXPECT(dsp_selfattn_pool_batch(yy, 1, 1, 260, W, bW, v, c, out, nullptr), "H 260 must be a multiple of 4 in [4, 256]");
+    EXPECT(dsp_selfattn_pool_batch(yy + 1, 1, 1, 4, W, bW, v, c, out, nullptr), "must be 16-byte aligned");
+    EXPECT(dsp_selfattn_pool_batch(yy, 1, 1, 4, W + 1, bW, v, c, out, nullptr), "must be 16-byte aligned");
+    EXPECT(dsp_selfattn_pool_batch(yy, 1, 1, 4, W, bW, v, c, out, nullptr), "dry_run: launches are refused");
+
+    dsp_debug_host_dry_run(0);
+    if (g_bad) { std::printf("asan_attn_args: %d FAILED\n", g_bad); return 1; }
+    std::printf("asan_attn_args: ok\n");
+    return 0;
+}
