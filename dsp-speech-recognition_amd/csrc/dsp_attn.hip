@@ -1,5 +1,5 @@
-// The attention entry points of libdsp_frontend.so (include/dsp_frontend.h: dsp_attn_*, dsp_selfattn_pool_batch): argument
-// checks, the packed-parameter handle of a Transformer encoder block and the launches of kernels_attn.h.  gfx950 / ROCm only.
+// The attention entry points of libdsp_frontend.so (include/dsp_frontend.h: dsp_attn_*, dsp_selfattn_pool_*): argument
+// checks, the packed-parameter handle of a Transformer encoder block and the launches of kernels_attn.h and kernels_attn_bwd.h.  gfx950 / ROCm only.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -8,12 +8,15 @@
 #include "dsp_common.h"
 #include "dsp_host.h"
 #include "kernels_attn.h"
+#include "kernels_attn_bwd.h"
 
 // Packed parameters of one encoder block (include/dsp_frontend.h: dsp_attn); immutable after dsp_attn_create.
 struct dsp_attn {
     int32_t d, d_inner, d_k, d_v;
-    float* d_packed;       // one allocation: the six packed matrices, then the seven padded vectors (kernels_attn.h: AttnWeights)
+    float* d_packed;       // one allocation: the six packed matrices of the forward, the six of the backward (kernels_attn_bwd.h:
+                           // AttnBwdWeights), then the seven padded vectors (kernels_attn.h: AttnWeights)
     AttnWeights w;
+    AttnBwdWeights v;
     int device;            // -1 for a dry-run handle
     int dry_run;           // the packed copy is in HOST memory (dsp_debug_host_dry_run): the handle can be destroyed, nothing else
 };
@@ -26,10 +29,36 @@ int64_t attn_work_bytes(const dsp_attn* h, int32_t T, int32_t B) {
     return 2 * (attn_act_floats(h, T, B) + attn_stat_floats(T)) * (int64_t)sizeof(float);
 }
 
+// Training: the tape is the forward's workspace and the rows M behind it; the backward's workspace holds the padded g_M, the
+// row part of dx and the statistic D; da holds the seven dense row gradients.
+int64_t attn_tape_bytes(const dsp_attn* h, int32_t T, int32_t B) {
+    return (3 * attn_act_floats(h, T, B) + 2 * attn_stat_floats(T)) * (int64_t)sizeof(float);
+}
+int64_t attn_bwd_work_bytes(const dsp_attn* h, int32_t T, int32_t B) {
+    return (2 * attn_act_floats(h, T, B) + attn_stat_floats(T)) * (int64_t)sizeof(float);
+}
+int64_t attn_da_bytes(const dsp_attn* h, int32_t T, int32_t B) {
+    return (int64_t)T * B * (4 * h->d + h->d_inner + h->d_v + h->d_k) * (int64_t)sizeof(float);
+}
+
 int attn_check_tb(const char* who, int32_t T, int32_t B) {
     if (T < 1 || T > AT_MAX_T) return dsp_fail(DSP_EINVAL, "%s: T %d must be in [1, %d]", who, T, AT_MAX_T);
     if (B < 1) return dsp_fail(DSP_EINVAL, "%s: B %d must be >= 1", who, B);
     if ((int64_t)B * (at_pad16(T) >> 4) > 0x7fffffff) return dsp_fail(DSP_EINVAL, "%s: B %d x T %d is more than one launch holds", who, B, T);
+    return DSP_OK;
+}
+
+// The training entry points: the sizes of the forward, and a d_model of at least 2 (the unbiased sigma of one element is 0 / 0).
+int attn_check_train(const char* who, const dsp_attn* h, int32_t T, int32_t B) {
+    if (int rc = attn_check_tb(who, T, B)) return rc;
+    if (h->d < 2) return dsp_fail(DSP_EINVAL, "%s: d_model %d must be in [2, %d] for training", who, h->d, AT_MAX_D);
+    return DSP_OK;
+}
+
+int attn_check_buffer(const char* who, const char* name, const void* p, int64_t have, int64_t need) {
+    if (!p || have < need)
+        return dsp_fail(DSP_EINVAL, "%s: %s holds %lld bytes, %lld are needed", who, name, (long long)(p ? have : 0), (long long)need);
+    if ((reinterpret_cast<uintptr_t>(p) & 15) != 0) return dsp_fail(DSP_EINVAL, "%s: %s must be 16-byte aligned", who, name);
     return DSP_OK;
 }
 
@@ -83,15 +112,19 @@ int dsp_attn_create(const dsp_attn_desc* desc, dsp_attn** out) {
     const int32_t DP = at_pad16(d), KP = at_pad16(dk), VP = at_pad16(dv), IP = at_pad16(di);
     // matrices as (source, K, N, stride of k, stride of n), then vectors as (source, n, padded n)
     struct Mat { const float* src; int32_t K, N; int64_t sk, sn; };
-    const Mat mats[6] = {{p[0], d, dk, dk, 1}, {p[1], dk, d, 1, dk}, {p[2], d, dv, dv, 1},
-                         {p[5], dv, d, 1, dv}, {p[7], d, di, 1, d}, {p[9], di, d, 1, di}};
+    // (the last six are the backward's: each matrix of the forward the other way round)
+    constexpr int NM = 12;
+    const Mat mats[NM] = {{p[0], d, dk, dk, 1}, {p[1], dk, d, 1, dk}, {p[2], d, dv, dv, 1},
+                          {p[5], dv, d, 1, dv}, {p[7], d, di, 1, d}, {p[9], di, d, 1, di},
+                          {p[9], d, di, di, 1}, {p[7], di, d, d, 1}, {p[5], d, dv, dv, 1},
+                          {p[2], dv, d, 1, dv}, {p[1], d, dk, dk, 1}, {p[0], dk, d, 1, dk}};
     struct Vec { const float* src; int32_t n, np; };
     const Vec vecs[7] = {{p[3], d, DP}, {p[4], d, DP}, {p[6], d, DP}, {p[8], di, IP}, {p[10], d, DP}, {p[11], d, DP}, {p[12], d, DP}};
-    size_t moff[6], voff[7], total = 0;
-    for (int i = 0; i < 6; ++i) { moff[i] = total; total += (size_t)at_pad16(mats[i].K) * at_pad16(mats[i].N); }
+    size_t moff[NM], voff[7], total = 0;
+    for (int i = 0; i < NM; ++i) { moff[i] = total; total += (size_t)at_pad16(mats[i].K) * at_pad16(mats[i].N); }
     for (int i = 0; i < 7; ++i) { voff[i] = total; total += (size_t)vecs[i].np; }
     std::vector<float> blob(total, 0.f);
-    for (int i = 0; i < 6; ++i) at_pack_host(blob.data() + moff[i], mats[i].src, mats[i].K, mats[i].N, mats[i].sk, mats[i].sn);
+    for (int i = 0; i < NM; ++i) at_pack_host(blob.data() + moff[i], mats[i].src, mats[i].K, mats[i].N, mats[i].sk, mats[i].sn);
     for (int i = 0; i < 7; ++i)
         for (int j = 0; j < vecs[i].n; ++j) blob[voff[i] + j] = vecs[i].src[j];
     void* tables = nullptr;
@@ -105,6 +138,7 @@ int dsp_attn_create(const dsp_attn_desc* desc, dsp_attn** out) {
     auto f4 = [&](int i) { return reinterpret_cast<const float4*>(buf + moff[i]); };
     AttnWeights& w = h->w;
     w.wq = f4(0); w.wkt = f4(1); w.wv = f4(2); w.wpt = f4(3); w.w1t = f4(4); w.w2t = f4(5);
+    h->v = AttnBwdWeights{f4(6), f4(7), f4(8), f4(9), f4(10), f4(11)};
     w.ln1a = buf + voff[0]; w.ln1b = buf + voff[1]; w.pb = buf + voff[2]; w.b1 = buf + voff[3]; w.b2 = buf + voff[4];
     w.ln2a = buf + voff[5]; w.ln2b = buf + voff[6];
     w.d = d; w.ngd = DP >> 4; w.ngk = KP >> 4; w.ngv = VP >> 4; w.ngi = IP >> 4;
@@ -129,16 +163,12 @@ int dsp_attn_workspace_bytes(const dsp_attn* h, int32_t T, int32_t B, int64_t* b
     return DSP_OK;
 }
 
-int dsp_attn_forward(const dsp_attn* h, const float* d_x, int32_t T, int32_t B, float* d_y, void* d_work, int64_t work_bytes,
-                     void* stream) {
-    const char* who = "dsp_attn_forward";
-    if (!h || !d_x || !d_y) return dsp_fail(DSP_EINVAL, "%s: NULL handle / input / output", who);
-    if (int rc = attn_check_tb(who, T, B)) return rc;
-    const int64_t need = attn_work_bytes(h, T, B);
-    if (!d_work || work_bytes < need)
-        return dsp_fail(DSP_EINVAL, "%s: the workspace holds %lld bytes, %lld are needed", who, (long long)(d_work ? work_bytes : 0), (long long)need);
-    if ((reinterpret_cast<uintptr_t>(d_work) & 15) != 0) return dsp_fail(DSP_EINVAL, "%s: d_work must be 16-byte aligned", who);
-    if (int rc = attn_check_launch(who, h)) return rc;
+}  // extern "C"
+
+namespace {
+
+// The three launches of the forward; train: d_work is the tape, whose M rows lie behind the forward's workspace.
+int attn_launch_forward(const dsp_attn* h, const float* d_x, int32_t T, int32_t B, float* d_y, void* d_work, bool train, void* stream) {
     AttnParams P;
     P.w = h->w;
     P.T = T; P.TP = at_pad16(T); P.B = B;
@@ -147,6 +177,7 @@ int dsp_attn_forward(const dsp_attn* h, const float* d_x, int32_t T, int32_t B, 
     P.qp = P.xp + attn_act_floats(h, T, B);
     P.smax = P.qp + attn_act_floats(h, T, B);
     P.ssum = P.smax + attn_stat_floats(T);
+    P.msave = train ? P.ssum + attn_stat_floats(T) : nullptr;
     hipStream_t st = (hipStream_t)stream;
     const int tiles = P.TP >> 4;
     attn_proj_kernel<<<B * tiles, 64, 0, st>>>(P);
@@ -158,9 +189,94 @@ int dsp_attn_forward(const dsp_attn* h, const float* d_x, int32_t T, int32_t B, 
     return DSP_OK;
 }
 
-int dsp_selfattn_pool_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
-                            const float* d_c, float* d_out, void* stream) {
-    const char* who = "dsp_selfattn_pool_batch";
+}  // namespace
+
+extern "C" {
+
+int dsp_attn_forward(const dsp_attn* h, const float* d_x, int32_t T, int32_t B, float* d_y, void* d_work, int64_t work_bytes,
+                     void* stream) {
+    const char* who = "dsp_attn_forward";
+    if (!h || !d_x || !d_y) return dsp_fail(DSP_EINVAL, "%s: NULL handle / input / output", who);
+    if (int rc = attn_check_tb(who, T, B)) return rc;
+    const int64_t need = attn_work_bytes(h, T, B);
+    if (!d_work || work_bytes < need)
+        return dsp_fail(DSP_EINVAL, "%s: the workspace holds %lld bytes, %lld are needed", who, (long long)(d_work ? work_bytes : 0), (long long)need);
+    if ((reinterpret_cast<uintptr_t>(d_work) & 15) != 0) return dsp_fail(DSP_EINVAL, "%s: d_work must be 16-byte aligned", who);
+    if (int rc = attn_check_launch(who, h)) return rc;
+    return attn_launch_forward(h, d_x, T, B, d_y, d_work, false, stream);
+}
+
+int dsp_attn_tape_bytes(const dsp_attn* h, int32_t T, int32_t B, int64_t* bytes) {
+    const char* who = "dsp_attn_tape_bytes";
+    if (!h || !bytes) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
+    if (int rc = attn_check_train(who, h, T, B)) return rc;
+    *bytes = attn_tape_bytes(h, T, B);
+    return DSP_OK;
+}
+
+int dsp_attn_forward_train(const dsp_attn* h, const float* d_x, int32_t T, int32_t B, float* d_y, void* d_tape, int64_t tape_bytes,
+                           void* stream) {
+    const char* who = "dsp_attn_forward_train";
+    if (!h || !d_x || !d_y) return dsp_fail(DSP_EINVAL, "%s: NULL handle / input / output", who);
+    if (int rc = attn_check_train(who, h, T, B)) return rc;
+    if (int rc = attn_check_buffer(who, "d_tape", d_tape, tape_bytes, attn_tape_bytes(h, T, B))) return rc;
+    if (int rc = attn_check_launch(who, h)) return rc;
+    return attn_launch_forward(h, d_x, T, B, d_y, d_tape, true, stream);
+}
+
+int dsp_attn_backward_bytes(const dsp_attn* h, int32_t T, int32_t B, int64_t* work_bytes, int64_t* da_bytes) {
+    const char* who = "dsp_attn_backward_bytes";
+    if (!h || !work_bytes || !da_bytes) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
+    if (int rc = attn_check_train(who, h, T, B)) return rc;
+    *work_bytes = attn_bwd_work_bytes(h, T, B);
+    *da_bytes = attn_da_bytes(h, T, B);
+    return DSP_OK;
+}
+
+int dsp_attn_backward(const dsp_attn* h, int32_t T, int32_t B, const void* d_tape, int64_t tape_bytes, const float* d_gy, float* d_gx,
+                      float* d_da, int64_t da_bytes, void* d_work, int64_t work_bytes, void* stream) {
+    const char* who = "dsp_attn_backward";
+    if (!h || !d_gy) return dsp_fail(DSP_EINVAL, "%s: NULL handle / gradient", who);
+    if (int rc = attn_check_train(who, h, T, B)) return rc;
+    if (int rc = attn_check_buffer(who, "d_tape", d_tape, tape_bytes, attn_tape_bytes(h, T, B))) return rc;
+    if (int rc = attn_check_buffer(who, "d_work", d_work, work_bytes, attn_bwd_work_bytes(h, T, B))) return rc;
+    const int64_t da_need = attn_da_bytes(h, T, B);
+    if (!d_da || da_bytes < da_need)
+        return dsp_fail(DSP_EINVAL, "%s: d_da holds %lld bytes, %lld are needed", who, (long long)(d_da ? da_bytes : 0), (long long)da_need);
+    if (int rc = attn_check_launch(who, h)) return rc;
+    AttnBwdParams P;
+    P.w = h->w; P.v = h->v;
+    P.T = T; P.TP = at_pad16(T); P.B = B;
+    P.di = h->d_inner; P.dk = h->d_k; P.dv = h->d_v;
+    const int64_t act = attn_act_floats(h, T, B), stat = attn_stat_floats(T), rows = (int64_t)T * B;
+    const float* tape = static_cast<const float*>(d_tape);
+    P.xp = tape; P.qp = P.xp + act; P.smax = P.qp + act; P.ssum = P.smax + stat; P.mp = P.ssum + stat;
+    P.gy = d_gy; P.gx = d_gx;
+    P.g_r2 = d_da;                       P.g_pre1 = P.g_r2 + rows * h->d;  P.g_z1 = P.g_pre1 + rows * h->d_inner;
+    P.g_r1 = P.g_z1 + rows * h->d;       P.g_o = P.g_r1 + rows * h->d;     P.g_q = P.g_o + rows * h->d_v;
+    P.g_preq = P.g_q + rows * h->d;
+    P.gm = static_cast<float*>(d_work); P.dxr = P.gm + act; P.dstat = P.dxr + act;
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = P.TP >> 4;
+    attn_bwd_row_kernel<<<B * tiles, 64, 0, st>>>(P);
+    HIP_TRY(hipGetLastError());
+    attn_bwd_stats_kernel<<<dim3(tiles, tiles), AT_STAT_WAVES * 64, 0, st>>>(P);
+    HIP_TRY(hipGetLastError());
+    attn_bwd_q_kernel<<<B * tiles, 64, 0, st>>>(P);
+    HIP_TRY(hipGetLastError());
+    if (d_gx) {
+        attn_bwd_col_kernel<<<B * tiles, 64, 0, st>>>(P);
+        HIP_TRY(hipGetLastError());
+    }
+    return DSP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int selfattn_pool(const char* who, const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
+                  const float* d_c, float* d_out, float* d_w, void* stream) {
     if (!d_y || !d_W || !d_bW || !d_v || !d_c || !d_out) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
     if (T < 1 || T > AT_MAX_T) return dsp_fail(DSP_EINVAL, "%s: T %d must be in [1, %d]", who, T, AT_MAX_T);
     if (B < 1) return dsp_fail(DSP_EINVAL, "%s: B %d must be >= 1", who, B);
@@ -168,7 +284,39 @@ int dsp_selfattn_pool_batch(const float* d_y, int32_t T, int32_t B, int32_t H, c
     if (((reinterpret_cast<uintptr_t>(d_y) | reinterpret_cast<uintptr_t>(d_W)) & 15) != 0)
         return dsp_fail(DSP_EINVAL, "%s: d_y and d_W must be 16-byte aligned", who);
     if (int rc = attn_check_launch(who, nullptr)) return rc;
-    selfattn_pool_kernel<<<B, 64, 0, (hipStream_t)stream>>>(d_y, T, B, H, d_W, d_bW, d_v, d_c, d_out);
+    selfattn_pool_kernel<<<B, 64, 0, (hipStream_t)stream>>>(d_y, T, B, H, d_W, d_bW, d_v, d_c, d_out, d_w);
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dsp_selfattn_pool_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
+                            const float* d_c, float* d_out, void* stream) {
+    return selfattn_pool("dsp_selfattn_pool_batch", d_y, T, B, H, d_W, d_bW, d_v, d_c, d_out, nullptr, stream);
+}
+
+int dsp_selfattn_pool_train_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
+                                  const float* d_c, float* d_out, float* d_w, void* stream) {
+    const char* who = "dsp_selfattn_pool_train_batch";
+    if (!d_w) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
+    return selfattn_pool(who, d_y, T, B, H, d_W, d_bW, d_v, d_c, d_out, d_w, stream);
+}
+
+int dsp_selfattn_pool_backward_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
+                                     const float* d_w, const float* d_gout, float* d_gy, float* d_gpre, float* d_ge, float* d_gvpart,
+                                     void* stream) {
+    const char* who = "dsp_selfattn_pool_backward_batch";
+    if (!d_y || !d_W || !d_bW || !d_v || !d_w || !d_gout || !d_gpre || !d_ge || !d_gvpart) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
+    if (T < 1 || T > AT_MAX_T) return dsp_fail(DSP_EINVAL, "%s: T %d must be in [1, %d]", who, T, AT_MAX_T);
+    if (B < 1) return dsp_fail(DSP_EINVAL, "%s: B %d must be >= 1", who, B);
+    if (!mult4_in(H, AT_MAX_H)) return dsp_fail(DSP_EINVAL, "%s: H %d must be a multiple of 4 in [4, %d]", who, H, AT_MAX_H);
+    if (((reinterpret_cast<uintptr_t>(d_y) | reinterpret_cast<uintptr_t>(d_W) | reinterpret_cast<uintptr_t>(d_gout)) & 15) != 0)
+        return dsp_fail(DSP_EINVAL, "%s: d_y, d_W and d_gout must be 16-byte aligned", who);
+    if (int rc = attn_check_launch(who, nullptr)) return rc;
+    selfattn_pool_bwd_kernel<<<B, 64, 0, (hipStream_t)stream>>>(d_y, T, B, H, d_W, d_bW, d_v, d_w, d_gout, d_gy, d_gpre, d_ge, d_gvpart);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }

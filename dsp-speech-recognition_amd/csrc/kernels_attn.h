@@ -1,4 +1,4 @@
-// The attention blocks of the classifiers, forward only, fp32, on v_mfma_f32_16x16x4_f32:
+// The attention blocks of the classifiers, forward (the gradients: kernels_attn_bwd.h), fp32, on v_mfma_f32_16x16x4_f32:
 //   * the Transformer encoder block in front of rnn_clf.Transformer (transformer.py:16-140, layers.py:125-143) as three launches
 //     -- projection, batch-softmax statistics, output -- none of which holds a [B, T, T] tensor;
 //   * layers.SelfAttn (layers.py:78-95), the pooling of rnn_clf.HRNN_Att, as one launch.
@@ -60,6 +60,7 @@ struct AttnParams {
     float* qp;             //            [B, TP, DP]
     float* smax;           //            [TP, TP]
     float* ssum;           //            [TP, TP]
+    float* msave;          // training: [B, TP, DP], the weighted sums M in front of W_v (kernels_attn_bwd.h); NULL otherwise
 };
 
 __device__ __forceinline__ hm_f32x4 at_mfma4(hm_f32x4 acc, const hm_f32x4 a, const hm_f32x4 b) {
@@ -229,6 +230,12 @@ __global__ __launch_bounds__(64) void attn_out_kernel(const AttnParams P) {
 #pragma unroll
     for (int n = 0; n < AT_MAX_D / 16; ++n)
         if (n < ngd) *(hm_lf4*)(bufA + c0 * AT_SA + 16 * n + r0) = cacc[n];
+    if (P.msave != nullptr) {
+        float* mrow = P.msave + ((int64_t)b * P.TP + t0 + c0) * DP + r0;
+#pragma unroll
+        for (int n = 0; n < AT_MAX_D / 16; ++n)
+            if (n < ngd) *(hm_gf4*)(mrow + 16 * n) = cacc[n];
+    }
     __syncthreads();
     at_dense(bufA, AT_SA, W.wv, ngd, W.ngv, lane, [&](int t, const hm_f32x4& acc) {
 #pragma unroll
@@ -285,7 +292,8 @@ static inline void at_pack_host(float* dst, const float* src, int K, int N, int6
 // float4 per lane and k-group; H is a multiple of 4, so a float4 lies inside the row or behind it.
 __global__ __launch_bounds__(64) void selfattn_pool_kernel(const float* __restrict__ y, int T, int B, int H, const float* __restrict__ Wm,
                                                            const float* __restrict__ bW, const float* __restrict__ v,
-                                                           const float* __restrict__ cb, float* __restrict__ out) {
+                                                           const float* __restrict__ cb, float* __restrict__ out,
+                                                           float* __restrict__ wsave /* training: the weights [T, B]; or NULL */) {
     __shared__ float e[AT_MAX_T];
     const int lane = threadIdx.x, b = blockIdx.x;
     const int ng = (H + 15) >> 4, nt = ng;
@@ -346,6 +354,8 @@ __global__ __launch_bounds__(64) void selfattn_pool_kernel(const float* __restri
     __syncthreads();
     for (int t = lane; t < T; t += 64) e[t] = expf(e[t] - mx) / sum;
     __syncthreads();
+    if (wsave != nullptr)
+        for (int t = lane; t < T; t += 64) wsave[(int64_t)t * B + b] = e[t];
     for (int h = lane; h < H; h += 64) {
         float s = 0.f;
         for (int t = 0; t < T; ++t) s += e[t] * y[((int64_t)t * B + b) * H + h];

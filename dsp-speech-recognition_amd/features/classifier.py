@@ -18,7 +18,11 @@ both yield max(len0) rows with zero rows behind each end, so the pooling above i
 required, ``native_enc=True`` takes the native training path (``_DynEncTrain``, csrc/kernels_bigru_bwd.h).
 
 The two attention blocks -- ``_TransformerEncoder`` in front of ``TransformerHead`` and ``_SelfAttn``, the pooling of
-``HRNNAttHead`` -- have opt-in native forward passes as well (csrc/kernels_attn.h), reached through ``native_attn=True``.
+``HRNNAttHead`` -- have opt-in native forward passes as well (csrc/kernels_attn.h), reached through ``native_attn=True``.  With a
+gradient required, ``native_attn=True`` takes their native training paths (``_AttnTrain`` / ``_SelfAttnTrain``,
+csrc/kernels_attn_bwd.h): the forward saves a tape without any [B, T, T] tensor, the backward is four launches (one for the
+pooling) and the parameter gradients are GEMMs over the rows it leaves (``attn_param_grads``).  ``native_attn=None`` keeps the
+torch chains whenever a gradient is required, unless ``native_train_default`` is set.
 """
 import numpy as np
 import torch
@@ -389,23 +393,80 @@ def _attn_input_reason(x, params):
     return None
 
 
+def _aligned16(t):
+    """A dense fp32 tensor whose first element is 16-byte aligned (a copy where ``t`` is a view that is not)."""
+    t = t.detach().to(torch.float32).contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _SelfAttnTrain(torch.autograd.Function):
+    """_SelfAttn's native training path.  forward: dsp_selfattn_pool_train_batch (the forward kernel, which also saves the weights
+    w [T, B]); backward: dsp_selfattn_pool_backward_batch (one launch) and the sums over what it wrote.  Inputs: (y, attn.weight,
+    attn.bias, v.weight, v.bias), read in place: autograd's version check on the saved tensors is what guards against a
+    parameter written between forward and backward."""
+
+    @staticmethod
+    def forward(ctx, y, W, bW, v, c):
+        from . import _native as nat
+        ctx.set_materialize_grads(False)
+        T, B, H = y.shape
+        dev = y.device
+        yc = _aligned16(y)
+        with torch.cuda.device(dev):
+            out = torch.empty(B, H, dtype=torch.float32, device=dev)
+            w = torch.empty(T, B, dtype=torch.float32, device=dev)
+            nat.check(nat.load().dsp_selfattn_pool_train_batch(yc.data_ptr(), T, B, H, W.data_ptr(), bW.data_ptr(), v.data_ptr(),
+                                                               c.data_ptr(), out.data_ptr(), w.data_ptr(),
+                                                               torch.cuda.current_stream(dev).cuda_stream))
+        ctx.save_for_backward(yc, w, W, bW, v)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        from . import _native as nat
+        need = ctx.needs_input_grad
+        if g_out is None or not any(need):
+            return (None,) * 5
+        yc, w, W, bW, v = ctx.saved_tensors
+        T, B, H = yc.shape
+        dev = yc.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        g = _aligned16(g_out)
+        with torch.cuda.device(dev):
+            g_y = torch.empty(T, B, H, **f32) if need[0] else None
+            g_pre, g_e, gv = torch.empty(T, B, H, **f32), torch.empty(T, B, **f32), torch.empty(B, H, **f32)
+            nat.check(nat.load().dsp_selfattn_pool_backward_batch(yc.data_ptr(), T, B, H, W.data_ptr(), bW.data_ptr(), v.data_ptr(),
+                                                                  w.data_ptr(), g.data_ptr(), _ptr(g_y), g_pre.data_ptr(),
+                                                                  g_e.data_ptr(), gv.data_ptr(),
+                                                                  torch.cuda.current_stream(dev).cuda_stream))
+            return (g_y,
+                    _rows_gemm(g_pre, yc) if need[1] else None,
+                    _rows_sum(g_pre) if need[2] else None,
+                    gv.sum(0, keepdim=True) if need[3] else None,
+                    g_e.sum().reshape(1) if need[4] else None)
+
+
 class _SelfAttn(nn.Module):
     """layers.SelfAttn (layers.py:78-95): softmax over ALL rows of the padded output, zero rows included.
 
     Two paths compute the same thing: the torch chain below, and ``dsp_selfattn_pool_batch`` (csrc/kernels_attn.h: one launch,
-    forward only, fp32, on the parameter tensors in place on the current stream).  ``native=True`` insists on the native one
-    (and raises where it cannot run), ``native=False`` keeps torch, ``native=None`` picks native only where ``native_default``
-    says so."""
+    fp32, on the parameter tensors in place on the current stream).  ``native=True`` insists on the native one (and raises
+    where it cannot run), ``native=False`` keeps torch, ``native=None`` picks native only where ``native_default`` says so.
+    With a gradient required, ``native=True`` takes the native TRAINING path (``_SelfAttnTrain``: the forward kernel saves
+    the weights, the backward is one launch, csrc/kernels_attn_bwd.h) in either mode -- the module has no mode-dependent
+    behaviour --, and ``native=None`` keeps torch unless ``native_train_default`` is set."""
     native_default = False         # opt-in until DESIGN 7.9's timing shows it ahead at every size
+    native_train_default = False   # what ``native=None`` picks when a gradient is required: torch, until DESIGN 7.10's timing decides
 
     def __init__(self, hidden_size):
         super().__init__()
         self.attn = nn.Linear(hidden_size, hidden_size)
         self.v = nn.Linear(hidden_size, 1)
 
-    def native_supported(self, y):
-        """Why the native path cannot serve ``y`` [T, B, H] (a string), or None when it can."""
-        if _attn_needs_grad(y, self):
+    def native_supported(self, y, train=False):
+        """Why the native path cannot serve ``y`` [T, B, H] (a string), or None when it can.  ``train``: the training path,
+        for which a required gradient is no reason."""
+        if not train and _attn_needs_grad(y, self):
             return 'a gradient is required (the native path is forward only)'
         why = _attn_input_reason(y, list(self.parameters()))
         if why is not None:
@@ -427,19 +488,25 @@ class _SelfAttn(nn.Module):
                                                          torch.cuda.current_stream(dev).cuda_stream))
         return out
 
+    def _run_native_train(self, y):
+        return _SelfAttnTrain.apply(y, self.attn.weight, self.attn.bias, self.v.weight, self.v.bias)
+
     def _run_torch(self, y):
         y = y.transpose(0, 1)                                                   # [B, T, H]
         w = torch.softmax(self.v(torch.tanh(self.attn(y))).squeeze(2), 1)       # [B, T]
         return torch.bmm(w.unsqueeze(1), y).squeeze(1)
 
     def forward(self, y, native=None):
-        if native is False or (native is None and not self.native_default):
+        if native is False:
             return self._run_torch(y)
-        why = self.native_supported(y)
+        needs_grad = _attn_needs_grad(y, self)
+        if native is None and not (self.native_train_default if needs_grad else self.native_default):
+            return self._run_torch(y)                                           # (nothing to find out about the native path)
+        why = self.native_supported(y, train=needs_grad)
         if why is None:
-            return self._run_native(y)
+            return self._run_native_train(y) if needs_grad else self._run_native(y)
         if native:
-            raise RuntimeError(f'_SelfAttn: the native path cannot run: {why}')
+            raise RuntimeError(f"_SelfAttn: the native {'training path (a gradient is required)' if needs_grad else 'path'} cannot run: {why}")
         return self._run_torch(y)
 
 
@@ -519,14 +586,145 @@ class _PosFFN(nn.Module):
         return self.layer_norm(o + x)
 
 
+def _ln_unit(r, eps):
+    """The rows of layers.LayerNormalization in front of the gain: (r - mean) / (std_unbiased + eps)."""
+    return (r - r.mean(-1, keepdim=True)) / (r.std(-1, keepdim=True) + eps)
+
+
+def _rows_gemm(a, b):
+    """a [T, B, m], b [T, B, n] -> a^T b [m, n] over all T B rows.  With a wide batch the product is one GEMM per time step,
+    summed over t afterwards: a single [m, T B] x [T B, n] product has m n / tile outputs and runs on a handful of workgroups
+    however long T B is.  The rule depends on the shapes alone: the same arguments give the same bits."""
+    T, B, m = a.shape
+    if B >= 64 and T > 1:
+        return torch.bmm(a.transpose(1, 2), b).sum(0)
+    return a.reshape(T * B, m).t() @ b.reshape(T * B, -1)
+
+
+def _rows_sum(a):
+    """a [T, B, n] -> the column sums [n], over t first: B n outputs keep the reduction parallel, n alone do not."""
+    return a.sum(0).sum(0)
+
+
+def attn_param_grads(params, x, M, g_y, da, need=None, eps=1e-3):
+    """The GEMMs and column sums behind the encoder layer's backward (include/dsp_frontend.h: dsp_attn_backward).  params: the
+    13 tensors of ``_TransformerEncoder._params()``; x [T, B, d]: the layer's input; M [T, B, d]: the weighted sums
+    sum_u A x_b[u] of the tape; g_y [T, B, d]: the gradient of the output; da: the seven row tensors g_r2, g_pre1, g_z1,
+    g_r1, g_o, g_q', g_preQ, each [T, B, .].  The row-wise forward values (o, z1, h and the normalised rows) are recomputed
+    from M and x; the B T T part is never run.  -> the 13 gradients in the order of ``params``; ``need`` (13 booleans) leaves
+    out what is not wanted.  The gain and shift of a skipped LayerNorm (T == 1: the first, B == 1: the second) get None, as
+    they get no gradient from autograd."""
+    T, B, d = x.shape
+    need = [True] * 13 if need is None else list(need)
+    res = [None] * 13
+    if not any(need):
+        return tuple(res)
+    wq, wk, wv, a1, b1, wp, bp, w1, c1, w2, c2, a2, b2 = params
+    g_r2, g_pre1, g_z1, g_r1, g_o, g_q, g_preq = da
+    ln1, ln2 = T > 1, B > 1
+    if need[0]: res[0] = _rows_gemm(x, g_preq).unsqueeze(0)
+    if need[1]: res[1] = (_rows_gemm(g_q, torch.tanh(x @ wq[0])) / float(np.power(d, 0.5))).unsqueeze(0)
+    if need[2]: res[2] = _rows_gemm(M, g_o).unsqueeze(0)
+    if need[4] and ln1: res[4] = _rows_sum(g_z1)
+    if need[6]: res[6] = _rows_sum(g_r1)
+    if need[8]: res[8] = _rows_sum(g_pre1)
+    if need[10]: res[10] = _rows_sum(g_r2)
+    if need[12] and ln2: res[12] = _rows_sum(g_y)
+    if not (need[5] or need[7] or need[9] or (need[3] and ln1) or (need[11] and ln2)):
+        return tuple(res)
+    o = M @ wv[0]
+    if need[5]: res[5] = _rows_gemm(g_r1, o)
+    if not (need[7] or need[9] or (need[3] and ln1) or (need[11] and ln2)):
+        return tuple(res)
+    z1 = o @ wp.t() + bp + x
+    if ln1:
+        n1 = _ln_unit(z1, eps)
+        if need[3]: res[3] = _rows_sum(g_z1 * n1)
+        z1 = n1 * a1 + b1
+    if need[7]: res[7] = _rows_gemm(g_pre1, z1).unsqueeze(2)
+    if need[9] or (need[11] and ln2):
+        h = torch.relu(z1 @ w1[:, :, 0].t() + c1)
+        if need[9]: res[9] = _rows_gemm(g_r2, h).unsqueeze(2)
+        if need[11] and ln2:
+            res[11] = _rows_sum(g_y * _ln_unit(h @ w2[:, :, 0].t() + c2 + z1, eps))
+    return tuple(res)
+
+
+def attn_tape_views(tape, T, B, d):
+    """The tape of dsp_attn_forward_train (include/dsp_frontend.h) -> M [T, B, d], a view."""
+    TP, DP = (T + 15) // 16 * 16, (d + 15) // 16 * 16
+    off = 2 * B * TP * DP + 2 * TP * TP
+    return tape[off:off + B * TP * DP].view(B, TP, DP)[:, :T, :d].transpose(0, 1)
+
+
+class _AttnTrain(torch.autograd.Function):
+    """_TransformerEncoder's native training path.  forward: dsp_attn_forward_train (the forward's three launches, which also
+    save the tape); backward: dsp_attn_backward (four launches, three when x needs no gradient) and ``attn_param_grads``.
+    Inputs: (module, x, the 13 parameters in module order); output: y [T, B, d_model]."""
+
+    @staticmethod
+    def forward(ctx, mod, x, *params):
+        from . import _native as nat
+        ctx.set_materialize_grads(False)                     # an unused output hands None to backward, not a tensor of zeros
+        T, B, d = x.shape
+        dev = x.device
+        xc = x.detach().contiguous()
+        with torch.cuda.device(dev):
+            handle, lib = mod._native_handle(dev), nat.load()
+            nbytes = nat.c_i64(0)
+            nat.check(lib.dsp_attn_tape_bytes(handle, T, B, nat.C.byref(nbytes)))
+            tape = torch.empty(nbytes.value // 4, dtype=torch.float32, device=dev)
+            y = torch.empty(T, B, d, dtype=torch.float32, device=dev)
+            nat.check(lib.dsp_attn_forward_train(handle, xc.data_ptr(), T, B, y.data_ptr(), tape.data_ptr(), nbytes.value,
+                                                 torch.cuda.current_stream(dev).cuda_stream))
+        ctx.mod, ctx.tape_bytes, ctx.handle_key = mod, nbytes.value, mod._handle_key
+        ctx.save_for_backward(xc, tape, *params)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        from . import _native as nat
+        mod = ctx.mod
+        need_x, need = ctx.needs_input_grad[1], list(ctx.needs_input_grad[2:])
+        if g_y is None or not (need_x or any(need)):
+            return (None,) * 15
+        mod._check_unmodified(ctx.handle_key)
+        saved = ctx.saved_tensors
+        xc, tape = saved[:2]
+        params = [p.detach() for p in saved[2:]]
+        T, B, d = xc.shape
+        dev = xc.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        g = g_y.detach().to(torch.float32).contiguous()
+        lib = nat.load()
+        with torch.cuda.device(dev):
+            wb, db = nat.c_i64(0), nat.c_i64(0)
+            nat.check(lib.dsp_attn_backward_bytes(mod._handle, T, B, nat.C.byref(wb), nat.C.byref(db)))
+            work, da = torch.empty(wb.value // 4, **f32), torch.empty(db.value // 4, **f32)
+            g_x = torch.empty(T, B, d, **f32) if need_x else None
+            nat.check(lib.dsp_attn_backward(mod._handle, T, B, tape.data_ptr(), ctx.tape_bytes, g.data_ptr(), _ptr(g_x),
+                                            da.data_ptr(), db.value, work.data_ptr(), wb.value,
+                                            torch.cuda.current_stream(dev).cuda_stream))
+            a = mod.slf_attn
+            rows = [v.view(T, B, n) for v, n in zip(torch.split(da, [T * B * n for n in mod._da_widths()]), mod._da_widths())]
+            grads = attn_param_grads(params, xc, attn_tape_views(tape, T, B, d), g, rows, need, a.layer_norm.eps)
+        return (None, g_x) + tuple(grads)
+
+
 class _TransformerEncoder(_NativeHandle, nn.Module):
     """transformer.EncoderLayer (transformer.py:16-30): ``_MHA`` then ``_PosFFN`` over x [T, B, d_model], all T rows as given.
 
     Two paths compute the same thing: the torch chain (any device, with gradients), and ``dsp_attn_forward``
-    (csrc/kernels_attn.h: three launches that never hold a [B, T, T] tensor; forward only, fp32, n_head = 1, on the current
-    stream).  ``native=True`` insists on the native one (and raises where it cannot run), ``native=False`` keeps torch,
-    ``native=None`` picks native only where ``native_default`` says so."""
+    (csrc/kernels_attn.h: three launches that never hold a [B, T, T] tensor; fp32, n_head = 1, on the current stream).
+    ``native=True`` insists on the native one (and raises where it cannot run), ``native=False`` keeps torch,
+    ``native=None`` picks native only where ``native_default`` says so.
+    With a gradient required, ``native=True`` takes the native TRAINING path (``_AttnTrain``): the forward saves a tape
+    (``dsp_attn_forward_train``), the backward is four launches without a [B, T, T] tensor (``dsp_attn_backward``,
+    csrc/kernels_attn_bwd.h) and the parameter gradients are GEMMs over the rows it leaves (``attn_param_grads``).  The module
+    has no mode-dependent behaviour, so ``.train()`` and ``.eval()`` are both served.  ``native=None`` keeps torch whenever
+    a gradient is required, unless ``native_train_default`` is set."""
     native_default = False         # opt-in until DESIGN 7.9's timing shows it ahead at every size
+    native_train_default = False   # what ``native=None`` picks when a gradient is required: torch, until DESIGN 7.10's timing decides
     _lib = 'dsp_attn'
 
     def __init__(self, d_model, d_inner, n_head, d_k, d_v):
@@ -539,12 +737,18 @@ class _TransformerEncoder(_NativeHandle, nn.Module):
         """Module order: w_qs, w_ks, w_vs, LN1 a_2, b_2, proj weight, bias, w_1 weight, bias, w_2 weight, bias, LN2 a_2, b_2."""
         return list(self.parameters())
 
-    def native_supported(self, x):
-        """Why the native path cannot serve ``x`` [T, B, d_model] (a string), or None when it can."""
+    def _da_widths(self):
+        """The widths of dsp_attn_backward's seven row tensors: g_r2, g_pre1, g_z1, g_r1, g_o, g_q', g_preQ."""
+        d, a = self.d_model, self.slf_attn
+        return [d, self.d_inner, d, d, a.d_v, d, a.d_k]
+
+    def native_supported(self, x, train=False):
+        """Why the native path cannot serve ``x`` [T, B, d_model] (a string), or None when it can.  ``train``: the training
+        path, for which a required gradient is no reason."""
         a = self.slf_attn
         if a.n_head != 1:
             return f'n_head is {a.n_head}: the native path serves n_head = 1'
-        if _attn_needs_grad(x, self):
+        if not train and _attn_needs_grad(x, self):
             return 'a gradient is required (the native path is forward only)'
         why = _attn_input_reason(x, self._params())
         if why is not None:
@@ -553,6 +757,8 @@ class _TransformerEncoder(_NativeHandle, nn.Module):
         if not (1 <= self.d_model <= 64 and ok4(a.d_k, 128) and ok4(a.d_v, 128) and ok4(self.d_inner, 256)
                 and 1 <= x.shape[0] <= 1024 and x.shape[2] == self.d_model):
             return 'sizes out of range: d_model in [1, 64], d_k and d_v multiples of 4 in [4, 128], d_inner a multiple of 4 in [4, 256], T in [1, 1024]'
+        if train and self.d_model < 2:
+            return 'd_model is 1: training needs d_model in [2, 64] (the unbiased std of one element is not a number)'
         if a.layer_norm.eps != self.pos_ffn.layer_norm.eps:
             return 'the two layer norms differ in eps'
         return None
@@ -580,17 +786,24 @@ class _TransformerEncoder(_NativeHandle, nn.Module):
                                            torch.cuda.current_stream(dev).cuda_stream))
         return y
 
+    def _run_native_train(self, x):
+        """The native training path: y attached to the autograd graph.  (The handle is created here, outside any capture.)"""
+        return _AttnTrain.apply(self, x, *self._params())
+
     def _run_torch(self, x):
         return self.pos_ffn(self.slf_attn(x))
 
     def run(self, x, native=None):
-        if native is False or (native is None and not self.native_default):
+        if native is False:
             return self._run_torch(x)
-        why = self.native_supported(x)
+        needs_grad = _attn_needs_grad(x, self)
+        if native is None and not (self.native_train_default if needs_grad else self.native_default):
+            return self._run_torch(x)                                           # (nothing to find out about the native path)
+        why = self.native_supported(x, train=needs_grad)
         if why is None:
-            return self._run_native(x)
+            return self._run_native_train(x) if needs_grad else self._run_native(x)
         if native:
-            raise RuntimeError(f'_TransformerEncoder: the native path cannot run: {why}')
+            raise RuntimeError(f"_TransformerEncoder: the native {'training path (a gradient is required)' if needs_grad else 'path'} cannot run: {why}")
         return self._run_torch(x)
 
     def forward(self, x, native=None):

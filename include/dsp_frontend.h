@@ -785,6 +785,54 @@ int dsp_attn_forward(const dsp_attn* h, const float* d_x, int32_t T, int32_t B, 
                      void* stream);
 
 /*
+ * Training the encoder layer: dsp_attn_forward_train saves a tape, dsp_attn_backward turns the gradient of y into the gradient
+ * of x and into the row gradients from which the 13 parameter gradients are plain GEMMs and column sums
+ * (features/classifier.py: attn_param_grads).  Sizes as the forward's, except d_model in [2, 64]: the unbiased std of one
+ * element (layers.py:139) is 0 / 0 in the reference as well.  Every entry point below checks its sizes and the byte counts
+ * of the caller's buffers before any device call (DSP_EINVAL), allocates nothing and is capturable into a HIP graph.
+ *
+ * With Qt = tanh(x w_qs), q' = Qt w_ks^T / sqrt(d_model) (so that s[b,t,u] = q'[b,t] . x_b[u]), A the batch-axis softmax of
+ * transformer.py:41,56, M[b,t] = sum_u A[b,t,u] x_b[u], o = M w_vs, r1 = proj(o) + x, z1 = LN1(r1), h = relu(w_1 z1 + b_1),
+ * r2 = w_2 h + b_2 + z1, y = LN2(r2) (transformer.py:112-121,134-139; layers.py:136-142 with both skips):
+ *   row-wise:   g_r2 = LN2'(g_y);  g_pre1 = (g_r2 w_2) [h > 0];  g_z1 = g_r2 + g_pre1 w_1;  g_r1 = LN1'(g_z1);
+ *               g_o = g_r1 proj.weight;  g_M = g_o w_vs^T
+ *   LN'(g):     c = r - mean, s = std_unbiased + eps, g_n = g a_2:  (g_n - mean(g_n)) / s - c sum(g_n c) / (s^2 std (d - 1));
+ *               a skipped LN (layers.py:136) passes g through
+ *   coupled:    g_A[b,t,u] = g_M[b,t] . x_b[u];  D[t,u] = sum_b A g_A;  g_S = A (g_A - D);  g_q'[b,t] = sum_u g_S x_b[u];
+ *               g_preQ = (g_q' w_ks / sqrt(d_model)) (1 - Qt^2)
+ *   dx[b,t]   = g_r1[b,t] + g_preQ[b,t] w_qs^T + sum_t' (A[b,t',t] g_M[b,t'] + g_S[b,t',t] q'[b,t'])
+ * Four launches (csrc/kernels_attn_bwd.h): rows, the [T', T'] statistic D, the sums over u, the sums over t (left out when
+ * d_gx is NULL).  The score tiles are recomputed from the tape; no [B, T, T] tensor exists.  Sums run in a fixed order without
+ * atomics: the same arguments give the same bits.
+ *
+ * The tape, in floats (T', D': T and d_model rounded up to 16):
+ *   x padded [B, T', D'] | q' [B, T', D'] | max_b s [T', T'] | sum_b exp(s - max) [T', T'] | M [B, T', D']
+ * i.e. the forward's workspace and the rows M behind it; rows t >= T of M are not meaningful.  61 MB at (200, 512), d_model 39.
+ */
+int dsp_attn_tape_bytes(const dsp_attn* h, int32_t T, int32_t B, int64_t* bytes);
+/*
+ * dsp_attn_forward that also fills d_tape (at least dsp_attn_tape_bytes bytes, 16-byte aligned).  d_y is bit for bit the
+ * output of dsp_attn_forward: the same three launches, the last of which also stores M.
+ */
+int dsp_attn_forward_train(const dsp_attn* h, const float* d_x, int32_t T, int32_t B, float* d_y, void* d_tape, int64_t tape_bytes,
+                           void* stream);
+/*
+ * work_bytes: the backward's workspace (padded g_M and row part of dx, 2 B T' D' floats, and D [T', T']).  da_bytes: the
+ * row gradients, T B (4 d_model + d_inner + d_v + d_k) floats.
+ */
+int dsp_attn_backward_bytes(const dsp_attn* h, int32_t T, int32_t B, int64_t* work_bytes, int64_t* da_bytes);
+/*
+ * d_tape: as dsp_attn_forward_train left it, with the same handle, T and B.  d_gy [T, B, d_model]: the gradient of y, dense.
+ * d_gx [T, B, d_model]: the gradient of x, every element written; NULL: not wanted (one launch fewer).  d_da: seven dense
+ * tensors one behind the other, every element written:
+ *   g_r2 [T, B, d_model] | g_pre1 [T, B, d_inner] | g_z1 [T, B, d_model] | g_r1 [T, B, d_model] | g_o [T, B, d_v] |
+ *   g_q' [T, B, d_model] | g_preQ [T, B, d_k]
+ * d_tape and d_work are 16-byte aligned.  Nothing behind T rows is written to d_gx or d_da.
+ */
+int dsp_attn_backward(const dsp_attn* h, int32_t T, int32_t B, const void* d_tape, int64_t tape_bytes, const float* d_gy, float* d_gx,
+                      float* d_da, int64_t da_bytes, void* d_work, int64_t work_bytes, void* stream);
+
+/*
  * layers.SelfAttn (layers.py:78-95) over d_y [T, B, H] fp32, dense and 16-byte aligned:
  *   e[t,b] = d_v . tanh(d_W y[t,b] + d_bW) + d_c[0]                  layers.py:88-90 (attn: Linear(H, H), v: Linear(H, 1))
  *   w[.,b] = softmax of e[.,b] over ALL T rows                       layers.py:91 -- the zero rows behind a short utterance get
@@ -797,6 +845,23 @@ int dsp_attn_forward(const dsp_attn* h, const float* d_x, int32_t T, int32_t B, 
  */
 int dsp_selfattn_pool_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
                             const float* d_c, float* d_out, void* stream);
+/*
+ * dsp_selfattn_pool_batch that also writes the weights w [T, B] to d_w; d_out is bit for bit dsp_selfattn_pool_batch's.
+ */
+int dsp_selfattn_pool_train_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
+                                  const float* d_c, float* d_out, float* d_w, void* stream);
+/*
+ * The backward of layers.py:88-94 given d_w (the saved weights) and d_gout [B, H] (16-byte aligned), the gradient of d_out:
+ *   g_w[t] = g_out[b] . y[t,b];   g_e = w (g_w - sum_t w g_w);   g_pre = g_e v (1 - tanh^2(W y + b_W));   g_y = w g_out + g_pre W
+ * One launch, one wavefront per column; the pre-activations are recomputed on the matrix pipe; sums over t and over the lanes
+ * of a row run in a fixed order.  Written, every element: d_gpre [T, B, H], d_ge [T, B], d_gvpart [B, H] = sum_t g_e tanh(.)
+ * per column, and d_gy [T, B, H] unless it is NULL (not wanted).  The parameter gradients are sums over these:
+ * attn.weight: g_pre^T y, attn.bias: sum g_pre, v.weight: sum_b d_gvpart, v.bias: sum g_e.  Sizes, alignment and checks as the
+ * forward's; nothing is allocated (capturable).
+ */
+int dsp_selfattn_pool_backward_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
+                                     const float* d_w, const float* d_gout, float* d_gy, float* d_gpre, float* d_ge, float* d_gvpart,
+                                     void* stream);
 
 #ifdef __cplusplus
 }

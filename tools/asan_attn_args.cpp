@@ -1,5 +1,7 @@
 // Stand-alone host check of the attention entry points (include/dsp_frontend.h: dsp_attn_create, dsp_attn_destroy,
-// dsp_attn_workspace_bytes, dsp_attn_forward, dsp_selfattn_pool_batch; csrc/dsp_attn.hip).  Under dsp_debug_host_dry_run(1)
+// dsp_attn_workspace_bytes, dsp_attn_forward, dsp_selfattn_pool_batch, and the training ones: dsp_attn_tape_bytes,
+// dsp_attn_forward_train, dsp_attn_backward_bytes, dsp_attn_backward, dsp_selfattn_pool_train_batch,
+// dsp_selfattn_pool_backward_batch; csrc/dsp_attn.hip).  Create packs the backward's six matrices with the forward's.  Under dsp_debug_host_dry_run(1)
 // create reads its parameters as host memory and packs them there, so the packing runs here -- on exact-size arrays, where a
 // read past either end of a parameter is a report -- and every argument error is DSP_EINVAL with a message before any device
 // call: the program needs no GPU.  `make -C dsp-speech-recognition_amd/csrc asan-attn` builds it with AddressSanitizer + UBSan
@@ -101,7 +103,66 @@ int main() {
         EXPECT(dsp_attn_forward(keep, x, 5, 3, y, work, bytes - 1, nullptr), "are needed");
         EXPECT(dsp_attn_forward(keep, x, 5, 3, y, reinterpret_cast<char*>(work) + 4, bytes, nullptr), "d_work must be 16-byte aligned");
         EXPECT(dsp_attn_forward(keep, x, 5, 3, y, work, bytes, nullptr), "dry_run: launches are refused");
+
+        // ---- training: tape / work / da byte counts and the checks of forward_train and backward
+        int64_t tape = 0, wk = 0, da = 0;
+        EXPECT(dsp_attn_tape_bytes(nullptr, 200, 8, &tape), "NULL argument");
+        EXPECT(dsp_attn_tape_bytes(keep, 200, 8, nullptr), "NULL argument");
+        EXPECT(dsp_attn_tape_bytes(keep, 0, 8, &tape), "T 0 must be in [1, 1024]");
+        EXPECT(dsp_attn_tape_bytes(keep, 200, 0, &tape), "B 0 must be >= 1");
+        EXPECT(dsp_attn_backward_bytes(nullptr, 200, 8, &wk, &da), "NULL argument");
+        EXPECT(dsp_attn_backward_bytes(keep, 200, 8, nullptr, &da), "NULL argument");
+        EXPECT(dsp_attn_backward_bytes(keep, 200, 8, &wk, nullptr), "NULL argument");
+        EXPECT(dsp_attn_backward_bytes(keep, 1025, 8, &wk, &da), "T 1025 must be in [1, 1024]");
+        EXPECT(dsp_attn_backward_bytes(keep, 1024, 0x7fffffff, &wk, &da), "more than one launch holds");
+        EXPECT_OK(dsp_attn_tape_bytes(keep, 200, 512, &tape));
+        EXPECT_OK(dsp_attn_backward_bytes(keep, 200, 512, &wk, &da));
+        const int64_t one_btt = (int64_t)4 * 512 * 200 * 200, TP = 208, DP = 48;
+        if (tape != 4 * (3 * 512 * TP * DP + 2 * TP * TP) || tape >= one_btt) { std::printf("tape at (200, 512): %lld bytes\n", (long long)tape); ++g_bad; }
+        if (wk != 4 * (2 * 512 * TP * DP + TP * TP) || wk >= one_btt) { std::printf("work at (200, 512): %lld bytes\n", (long long)wk); ++g_bad; }
+        if (da != (int64_t)4 * 200 * 512 * (4 * 39 + 200 + 100 + 100)) { std::printf("da at (200, 512): %lld bytes\n", (long long)da); ++g_bad; }
+        EXPECT_OK(dsp_attn_tape_bytes(keep, 5, 3, &tape));
+        EXPECT_OK(dsp_attn_backward_bytes(keep, 5, 3, &wk, &da));
+        alignas(16) static float buf[16];                                    // never reached, as above
+        char* mis = reinterpret_cast<char*>(buf) + 4;
+        EXPECT(dsp_attn_forward_train(nullptr, x, 5, 3, y, buf, tape, nullptr), "NULL handle / input / output");
+        EXPECT(dsp_attn_forward_train(keep, nullptr, 5, 3, y, buf, tape, nullptr), "NULL handle / input / output");
+        EXPECT(dsp_attn_forward_train(keep, x, 5, 3, nullptr, buf, tape, nullptr), "NULL handle / input / output");
+        EXPECT(dsp_attn_forward_train(keep, x, 0, 3, y, buf, tape, nullptr), "T 0 must be in [1, 1024]");
+        EXPECT(dsp_attn_forward_train(keep, x, 5, 0, y, buf, tape, nullptr), "B 0 must be >= 1");
+        EXPECT(dsp_attn_forward_train(keep, x, 5, 3, y, nullptr, tape, nullptr), "d_tape holds 0 bytes");
+        EXPECT(dsp_attn_forward_train(keep, x, 5, 3, y, buf, tape - 1, nullptr), "are needed");
+        EXPECT(dsp_attn_forward_train(keep, x, 5, 3, y, mis, tape, nullptr), "d_tape must be 16-byte aligned");
+        EXPECT(dsp_attn_forward_train(keep, x, 5, 3, y, buf, tape, nullptr), "dry_run: launches are refused");
+        EXPECT(dsp_attn_backward(nullptr, 5, 3, buf, tape, x, y, buf, da, buf, wk, nullptr), "NULL handle / gradient");
+        EXPECT(dsp_attn_backward(keep, 5, 3, buf, tape, nullptr, y, buf, da, buf, wk, nullptr), "NULL handle / gradient");
+        EXPECT(dsp_attn_backward(keep, 1025, 3, buf, tape, x, y, buf, da, buf, wk, nullptr), "T 1025 must be in [1, 1024]");
+        EXPECT(dsp_attn_backward(keep, 5, -1, buf, tape, x, y, buf, da, buf, wk, nullptr), "B -1 must be >= 1");
+        EXPECT(dsp_attn_backward(keep, 5, 3, nullptr, tape, x, y, buf, da, buf, wk, nullptr), "d_tape holds 0 bytes");
+        EXPECT(dsp_attn_backward(keep, 5, 3, buf, tape - 1, x, y, buf, da, buf, wk, nullptr), "are needed");
+        EXPECT(dsp_attn_backward(keep, 5, 3, mis, tape, x, y, buf, da, buf, wk, nullptr), "d_tape must be 16-byte aligned");
+        EXPECT(dsp_attn_backward(keep, 5, 3, buf, tape, x, y, buf, da, nullptr, wk, nullptr), "d_work holds 0 bytes");
+        EXPECT(dsp_attn_backward(keep, 5, 3, buf, tape, x, y, buf, da, buf, wk - 1, nullptr), "are needed");
+        EXPECT(dsp_attn_backward(keep, 5, 3, buf, tape, x, y, buf, da, mis, wk, nullptr), "d_work must be 16-byte aligned");
+        EXPECT(dsp_attn_backward(keep, 5, 3, buf, tape, x, y, nullptr, da, buf, wk, nullptr), "d_da holds 0 bytes");
+        EXPECT(dsp_attn_backward(keep, 5, 3, buf, tape, x, y, buf, da - 1, buf, wk, nullptr), "are needed");
+        EXPECT(dsp_attn_backward(keep, 5, 3, buf, tape, x, y, buf, da, buf, wk, nullptr), "dry_run: launches are refused");
+        EXPECT(dsp_attn_backward(keep, 5, 3, buf, tape, x, nullptr, buf, da, buf, wk, nullptr), "dry_run: launches are refused");   // d_gx is optional
         EXPECT_OK(dsp_attn_destroy(keep));
+
+        // d_model = 1: the forward serves it, training does not
+        Block one(1, 4, 4, 4);
+        dsp_attn* h1 = nullptr;
+        EXPECT_OK(dsp_attn_create(&one.d, &h1));
+        if (h1) {
+            const char* what = "d_model 1 must be in [2, 64] for training";
+            EXPECT_OK(dsp_attn_workspace_bytes(h1, 5, 3, &bytes));
+            EXPECT(dsp_attn_tape_bytes(h1, 5, 3, &tape), what);
+            EXPECT(dsp_attn_backward_bytes(h1, 5, 3, &wk, &da), what);
+            EXPECT(dsp_attn_forward_train(h1, x, 5, 3, y, buf, 1 << 20, nullptr), what);
+            EXPECT(dsp_attn_backward(h1, 5, 3, buf, 1 << 20, x, y, buf, 1 << 20, buf, 1 << 20, nullptr), what);
+            EXPECT_OK(dsp_attn_destroy(h1));
+        }
     } else {
         std::printf("no handle was created\n");
         ++g_bad;
@@ -123,6 +184,33 @@ int main() {
     EXPECT(dsp_selfattn_pool_batch(yy + 1, 1, 1, 4, W, bW, v, c, out, nullptr), "must be 16-byte aligned");
     EXPECT(dsp_selfattn_pool_batch(yy, 1, 1, 4, W + 1, bW, v, c, out, nullptr), "must be 16-byte aligned");
     EXPECT(dsp_selfattn_pool_batch(yy, 1, 1, 4, W, bW, v, c, out, nullptr), "dry_run: launches are refused");
+
+    alignas(16) static float w1[4], go[4], gy[4], gp[4], ge[4], gv[4];
+    EXPECT(dsp_selfattn_pool_train_batch(nullptr, 1, 1, 4, W, bW, v, c, out, w1, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_train_batch(yy, 1, 1, 4, W, bW, v, c, nullptr, w1, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_train_batch(yy, 1, 1, 4, W, bW, v, c, out, nullptr, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_train_batch(yy, 0, 1, 4, W, bW, v, c, out, w1, nullptr), "T 0 must be in [1, 1024]");
+    EXPECT(dsp_selfattn_pool_train_batch(yy, 1, 0, 4, W, bW, v, c, out, w1, nullptr), "B 0 must be >= 1");
+    EXPECT(dsp_selfattn_pool_train_batch(yy, 1, 1, 6, W, bW, v, c, out, w1, nullptr), "H 6 must be a multiple of 4 in [4, 256]");
+    EXPECT(dsp_selfattn_pool_train_batch(yy + 1, 1, 1, 4, W, bW, v, c, out, w1, nullptr), "must be 16-byte aligned");
+    EXPECT(dsp_selfattn_pool_train_batch(yy, 1, 1, 4, W, bW, v, c, out, w1, nullptr), "dry_run: launches are refused");
+    EXPECT(dsp_selfattn_pool_backward_batch(nullptr, 1, 1, 4, W, bW, v, w1, go, gy, gp, ge, gv, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 4, nullptr, bW, v, w1, go, gy, gp, ge, gv, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 4, W, nullptr, v, w1, go, gy, gp, ge, gv, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 4, W, bW, nullptr, w1, go, gy, gp, ge, gv, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 4, W, bW, v, nullptr, go, gy, gp, ge, gv, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 4, W, bW, v, w1, nullptr, gy, gp, ge, gv, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 4, W, bW, v, w1, go, gy, nullptr, ge, gv, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 4, W, bW, v, w1, go, gy, gp, nullptr, gv, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 4, W, bW, v, w1, go, gy, gp, ge, nullptr, nullptr), "NULL argument");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1025, 1, 4, W, bW, v, w1, go, gy, gp, ge, gv, nullptr), "T 1025 must be in [1, 1024]");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 0, 4, W, bW, v, w1, go, gy, gp, ge, gv, nullptr), "B 0 must be >= 1");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 260, W, bW, v, w1, go, gy, gp, ge, gv, nullptr), "H 260 must be a multiple of 4 in [4, 256]");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy + 1, 1, 1, 4, W, bW, v, w1, go, gy, gp, ge, gv, nullptr), "must be 16-byte aligned");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 4, W + 1, bW, v, w1, go, gy, gp, ge, gv, nullptr), "must be 16-byte aligned");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 4, W, bW, v, w1, go + 1, gy, gp, ge, gv, nullptr), "must be 16-byte aligned");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 4, W, bW, v, w1, go, gy, gp, ge, gv, nullptr), "dry_run: launches are refused");
+    EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 4, W, bW, v, w1, go, nullptr, gp, ge, gv, nullptr), "dry_run: launches are refused");   // d_gy is optional
 
     dsp_debug_host_dry_run(0);
     if (g_bad) { std::printf("asan_attn_args: %d FAILED\n", g_bad); return 1; }
