@@ -23,6 +23,10 @@ struct dsp_plan {
     int32_t* d_mel_off;     // [M] prefix offsets into d_mel_w
     float* d_mel_w;         // [mel_nnz]
     float* d_dct;           // [C, M]
+    // fp64 tables of the repair of cancelled mel filters (kernels_repair.h); d_repair is a DspRepairTab naming them
+    double* d_window64;     // [lfft]
+    double* d_twiddle64;    // [nfft][2]  cos, sin of 2 pi k / nfft
+    void* d_repair;         // NULL for a plan without mel tables
     void* d_fast;           // tables of the specialised NFFT=512 kernel (NULL if not applicable)
     void* d_fast1536;       // tables of the specialised NFFT=1536 kernel (NULL if not applicable)
     void* d_mfma;           // tables of the matrix-pipe NFFT=512 kernel, kernels_mfma512.h (NULL if not applicable)

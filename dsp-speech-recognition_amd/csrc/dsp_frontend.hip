@@ -104,6 +104,7 @@ GenericParams generic_params(const dsp_plan* p) {
     P.window = p->d_window; P.tw = p->d_twiddle;
     P.mel_start = p->d_mel_start; P.mel_count = p->d_mel_count; P.mel_off = p->d_mel_off;
     P.mel_w = p->d_mel_w; P.dct = p->d_dct;
+    P.repair = static_cast<const DspRepairTab*>(p->d_repair);
     std::vector<int> radix;
     factor_half_fft(p->nfft / 2, radix);
     P.n_pass = (int)radix.size();
@@ -665,6 +666,8 @@ int dsp_plan_create(const dsp_plan_desc* d, dsp_plan** out) {
     if (d->nfft < 16 || d->nfft > 4096 || (d->nfft & 1) || !factor_half_fft(d->nfft / 2, radix))
         return dsp_fail(DSP_EINVAL, "unsupported nfft %d (need 2^k or 3*2^k in [16, 4096])", d->nfft);
     if (!d->h_window) return dsp_fail(DSP_EINVAL, "h_window is NULL");
+    if (d->nfilt > 0 && !d->h_window64) return dsp_fail(DSP_EINVAL, "h_window64 is NULL");
+    if (d->nfilt > 0 && (float)d->preemph64 != d->preemph) return dsp_fail(DSP_EINVAL, "preemph64 does not round to preemph");
     if (d->nfilt < 0 || d->numcep < 0 || d->numcep > d->nfilt)
         return dsp_fail(DSP_EINVAL, "need 0 <= numcep <= nfilt (got %d, %d)", d->numcep, d->nfilt);
     if (d->nfilt > d->nfft) return dsp_fail(DSP_EINVAL, "nfilt %d > nfft %d", d->nfilt, d->nfft);
@@ -707,6 +710,28 @@ int dsp_plan_create(const dsp_plan_desc* d, dsp_plan** out) {
         if (rc == DSP_OK) rc = upload(&p->d_mel_w, d->h_mel_weights, (size_t)nnz);
         if (rc == DSP_OK && d->numcep > 0) rc = upload(&p->d_dct, d->h_dct, (size_t)d->numcep * d->nfilt);
     }
+    if (rc == DSP_OK && d->nfilt > 0) {
+        // the fp64 side of the plan (kernels_repair.h): window and coefficient as the caller has them in fp64, and an
+        // exact twiddle table
+        std::vector<double> tw64((size_t)2 * d->nfft);
+        for (int k = 0; k < d->nfft; ++k) {
+            const double a = 2.0 * M_PI * (double)k / (double)d->nfft;
+            tw64[2 * k] = cos(a);
+            tw64[2 * k + 1] = sin(a);
+        }
+        rc = upload(&p->d_window64, d->h_window64, (size_t)p->lfft);
+        if (rc == DSP_OK) rc = upload(&p->d_twiddle64, tw64.data(), tw64.size());
+        if (rc == DSP_OK) {
+            DspRepairTab t;
+            memset(&t, 0, sizeof(t));
+            t.preemph = d->preemph64; t.lfft = p->lfft; t.nfft = p->nfft;
+            t.window = p->d_window64; t.tw = p->d_twiddle64;
+            t.mel_start = p->d_mel_start; t.mel_count = p->d_mel_count; t.mel_off = p->d_mel_off; t.mel_w = p->d_mel_w;
+            DspRepairTab* dt = nullptr;
+            rc = upload(&dt, &t, 1);
+            p->d_repair = dt;
+        }
+    }
     if (rc == DSP_OK) rc = fast512_plan_init(p, d, off.data());
     if (rc == DSP_OK && d->nfilt > 0 && d->numcep > 0) rc = fast1536_plan_init(p, d, off.data());
     if (rc == DSP_OK && d->nfilt > 0 && d->numcep > 0 && p->d_fast) rc = mfma512_plan_init(p, d);
@@ -718,7 +743,8 @@ int dsp_plan_create(const dsp_plan_desc* d, dsp_plan** out) {
 
 int dsp_plan_destroy(dsp_plan* p) {
     if (!p) return DSP_OK;
-    void* bufs[] = {p->d_window, p->d_twiddle, p->d_mel_start, p->d_mel_count, p->d_mel_off, p->d_mel_w, p->d_dct};
+    void* bufs[] = {p->d_window, p->d_twiddle, p->d_mel_start, p->d_mel_count, p->d_mel_off, p->d_mel_w, p->d_dct,
+                    p->d_window64, p->d_twiddle64, p->d_repair};
     for (void* b : bufs) dsp_table_free(b, p->dry_run);
     fast512_plan_free(p);
     fast1536_plan_free(p);

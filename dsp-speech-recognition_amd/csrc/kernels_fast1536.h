@@ -608,6 +608,10 @@ static inline bool fast1536_shape_ok(const dsp_plan_desc* d) {
 static inline int fast1536_plan_init(dsp_plan* p, const dsp_plan_desc* d, const int32_t* mel_off) {
     p->d_fast1536 = nullptr;
     if (!fast1536_shape_ok(d)) return DSP_OK;
+    // This kernel has no fp64 repair of cancelled mel filters (kernels_repair.h).  Data does not cancel three neighbouring
+    // bins at once, and neither model plan has a narrower filter; a plan that has one runs on the generic kernel.
+    for (int j = 0; j < d->nfilt; ++j)
+        if (d->h_mel_count[j] <= 2) return DSP_OK;
     const int M = d->nfilt, C = d->numcep, L = d->frame_len;
     const int ni_real = (M + 15) / 16;
     const int span_vec = (3 * d->frame_step + 1536 + 3) / 4;

@@ -26,6 +26,7 @@
 #include "dsp_common.h"
 #include "launch_common.h"
 #include "fft_inreg.h"
+#include "kernels_repair.h"
 
 #define F512_WAVE_FLOATS 2112  // per-wave LDS: 8 frames x 264 floats (staging / exchange alias it)
 #define F512_PS_STRIDE 264     // == 8 (mod 32): the 8 frames' rows start on distinct bank octets
@@ -319,6 +320,22 @@ static inline bool f512_view_is_identity(const F512Params& P) {
            Q.off_mels == P.off_mels && Q.off_bias == P.off_bias && Q.off_coop == P.off_coop &&
            Q.melw_row == P.melw_row && Q.span_vec == P.span_vec &&
            ((!FLAT && !P.flat) || Q.seam_off == P.seam_off) && Q.flat == P.flat;
+}
+
+// The mel filter of slot (iteration i, lane c) of a plan with M filters, -1 for an empty slot: the dealing rule of
+// fast512_plan_init (which checks its table against this function) for the fp64 repair, which must name the filter.
+__host__ __device__ constexpr int f512_slot_filter(int i, int c, int M, int NI) {
+    const int n_pairs = (M + 1) / 2, full = NI / 2;
+    if (i < full) {
+        const int pr = i * 8 + c;
+        return pr < n_pairs ? pr : -1;
+    }
+    if ((NI & 1) && i == full) {
+        const int pr = 8 * full + (c < 4 ? c : 7 - c);
+        return pr < n_pairs ? (c < 4 ? pr : M - 1 - pr) : -1;
+    }
+    const int pr = (NI - 1 - i) * 8 + (7 - c);
+    return pr < n_pairs ? M - 1 - pr : -1;
 }
 
 // Where a frame group lives (all wave-uniform).
@@ -1052,6 +1069,14 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
         //      b128 blocks of 4 taps.  Weights carry 2^21 = 2^32 / 2048; an all-zero filter gives log2(eps 2^32) = -20
         //      (base.py:30, eps = 2^-52). ----
         float lm[NI];
+        // Filters too small for the fp32 spectrum (kernels_repair.h): 0 < acc < DSP_REPAIR_RATIO x energy, as ONE unsigned
+        // compare of the bit patterns minus one (acc = 0 -- an empty slot, silence -- wraps to the top and never passes).
+        // The compare's lane mask is a scalar: two vector instructions per filter iteration on the hot path.  A threshold
+        // of zero (-DDSP_REPAIR_RATIO=0.f: the repair switched off, for measurements; or a product flushed to zero on a
+        // nearly silent frame) must flag nothing, so its own "minus one" does not wrap.
+        unsigned long long rep_m[NI];
+        const uint32_t rep_tb = __float_as_uint(DSP_REPAIR_RATIO * energy);
+        const uint32_t rep_te = (rep_tb > 1u ? rep_tb : 1u) - 1u;
         {
             const float4* wrow = reinterpret_cast<const float4*>(s_melw + c * P.melw_row);
             f512_static_for<0, NI>([&](auto ic) {
@@ -1083,6 +1108,44 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
                 const float acc = acc0 + acc1;
                 const float l2 = __builtin_amdgcn_logf(acc);
                 lm[i] = acc == 0.f ? -20.f : l2;
+                rep_m[i] = __ballot(__float_as_uint(acc) - 1u < rep_te);
+            });
+        }
+        unsigned long long rep_any = 0;
+#pragma unroll
+        for (int i = 0; i < NI; ++i) rep_any |= rep_m[i];
+        if (rep_any != 0) {
+            // Rare (one frame in 4 000 of a noise batch) and wave-uniform: the flagged filters' bins again as fp64 DFT sums
+            // over the samples in memory, by the whole wave, one filter at a time.  The pointer to the plan's fp64 tables
+            // sits behind the LDS image of the table blob.  The group is located AGAIN here, from an opaque copy of its
+            // index: keeping the first result alive down to this point would cost the whole loop scalar registers.
+            int Gc = FD ? run.first_frame + 8 * r : G;
+            asm volatile("" : "+s"(Gc));
+            const F512Group g2 = FD ? f512_locate_frame(P, bg, Gc) : f512_locate<RAGGED>(P, bg, Gc);
+            const DspRepairTab* rep = *reinterpret_cast<const DspRepairTab* const*>(P.tables + P.tab_floats);
+            f512_static_for<0, NI>([&](auto ic) {      // unrolled: lm[] stays in registers only under constant indices
+                constexpr int i = decltype(ic)::value;
+                unsigned long long m = rep_m[i];
+                while (m != 0) {
+                    const int sl = __builtin_ctzll(m);
+                    m &= m - 1;
+                    const int fs = sl >> 3;
+                    const int j = f512_slot_filter(i, sl & 7, P.M, NI);
+                    int64_t us0 = g2.s0;
+                    int ut = g2.t0 + fs;
+                    bool ok = j >= 0 && ut < g2.T;     // frame slots behind the utterance's end are never stored
+                    if (!RAGGED && P.flat && fs >= g2.nf1) {    // flat grouping: the slot belongs to the next utterance
+                        us0 += g2.nsamp;
+                        ut = fs - g2.nf1;
+                        ok = j >= 0 && ut < g2.T && g2.utt + 1 < bg.n_utt;
+                    }
+                    if (!ok) continue;
+                    const double a = dsp_repair_mel_f64<DTYPE>(rep, wave, us0, (int64_t)g2.nsamp, (int64_t)ut * P.S, j, lane);
+                    // back to the kernel's scale (2^32) and its own logarithm
+                    const float af = (float)(a * 4294967296.0);
+                    const float nl = af == 0.f ? -20.f : __builtin_amdgcn_logf(af);
+                    if (lane == sl) lm[i] = nl;
+                }
             });
         }
         F512_FENCE();
@@ -1376,6 +1439,9 @@ static inline int fast512_plan_init(dsp_plan* p, const dsp_plan_desc* d, const i
         slot[(size_t)u * 8 + c] = ja;
         slot[(size_t)(NI - 1 - u) * 8 + (7 - c)] = jb;
     }
+    for (int i = 0; i < NI; ++i)
+        for (int c = 0; c < 8; ++c)
+            if (slot[(size_t)i * 8 + c] != f512_slot_filter(i, c, M, NI)) return DSP_EINVAL;   // the kernel's repair names filters by that rule
     const int NU = (NI + 1) / 2;
     const double LN2 = 0.69314718055994530942;
     std::vector<float> dct((size_t)NU * 8 * 20, 0.f);  // [unit][lane] rows of 16 (+4 pad: 5 x 16 B, conflict-free b128)
@@ -1453,7 +1519,9 @@ static inline int fast512_plan_init(dsp_plan* p, const dsp_plan_desc* d, const i
         delete fp;
         return DSP_EINVAL;
     }
-    std::vector<float> blob(total, 0.f);
+    std::vector<float> blob(total + 2, 0.f);   // + the pointer to the plan's fp64 repair tables, read from global memory
+    memcpy(blob.data() + total, &p->d_repair, sizeof(p->d_repair));
+    static_assert(sizeof(p->d_repair) == 2 * sizeof(float), "the pointer takes the two floats behind the tables");
     memcpy(blob.data(), win.data(), 512 * 4);
     memcpy(blob.data() + o_tw1, tw1.data(), tw1.size() * 4);
     memcpy(blob.data() + o_dct, dct.data(), dct.size() * 4);
@@ -1461,7 +1529,7 @@ static inline int fast512_plan_init(dsp_plan* p, const dsp_plan_desc* d, const i
     memcpy(blob.data() + o_mels, mels.data(), mels.size() * 4);
     memcpy(blob.data() + o_bias, bias.data(), bias.size() * 4);
     memcpy(blob.data() + o_coop, coop.data(), coop.size() * 4);
-    if (dsp_table_alloc_copy(reinterpret_cast<void**>(&fp->d_tables), blob.data(), total * 4) != hipSuccess) {
+    if (dsp_table_alloc_copy(reinterpret_cast<void**>(&fp->d_tables), blob.data(), blob.size() * 4) != hipSuccess) {
         delete fp;
         return DSP_EHIP;
     }

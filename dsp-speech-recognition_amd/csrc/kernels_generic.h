@@ -7,6 +7,7 @@
 #pragma once
 
 #include "dsp_common.h"
+#include "kernels_repair.h"
 
 #define DSP_GEN_WAVES 4
 #define DSP_MAX_RADIX_PASSES 12
@@ -21,6 +22,7 @@ struct GenericParams {
     const int32_t* mel_off;
     const float* mel_w;
     const float* dct;
+    const DspRepairTab* repair;  // fp64 tables for cancelled mel filters (kernels_repair.h)
     int32_t n_pass;
     int32_t radix[DSP_MAX_RADIX_PASSES];
 };
@@ -156,16 +158,32 @@ __global__ __launch_bounds__(64 * DSP_GEN_WAVES) void features_generic_kernel(
 
         // ---- mel filterbank (base.py:28-30), log (base.py:12) ----
         float* logmel = reinterpret_cast<float*>(src);  // spectrum Z is dead now
-        for (int j = lane; j < P.M; j += 64) {
-            const int b0 = P.mel_start[j], cnt = P.mel_count[j];
-            const float* w = P.mel_w + P.mel_off[j];
+        for (int j0 = 0; j0 < P.M; j0 += 64) {
+            const int j = j0 + lane;
             float acc = 0.f;
-            for (int i = 0; i < cnt; ++i) acc = fmaf(w[i], pspec[b0 + i], acc);
-            if (acc == 0.f) acc = DSP_EPS_F32;  // base.py:30
-            if (out_kind == DSP_OUT_FBANK) {
-                if (active) out[g * ld_out + j] = acc;
-            } else {
-                logmel[j] = logf(acc);
+            if (j < P.M) {
+                const int b0 = P.mel_start[j], cnt = P.mel_count[j];
+                const float* w = P.mel_w + P.mel_off[j];
+                for (int i = 0; i < cnt; ++i) acc = fmaf(w[i], pspec[b0 + i], acc);
+            }
+            float lg = logf(acc == 0.f ? DSP_EPS_F32 : acc);  // base.py:30
+            if (out_kind == DSP_OUT_MFCC) {
+                // a filter the fp32 spectrum cannot carry: its bins again in fp64 (kernels_repair.h); rare and wave-uniform
+                unsigned long long m = __ballot(j < P.M && acc > 0.f && acc < DSP_REPAIR_RATIO * esum);
+                while (m != 0) {
+                    const int src_lane = __builtin_ctzll(m);
+                    m &= m - 1;
+                    const double a = dsp_repair_mel_f64<DTYPE>(P.repair, wave, s0, nsamp, first, j0 + src_lane, lane);
+                    if (lane == src_lane) lg = (float)log(a == 0.0 ? (double)DSP_EPS_F32 : a);
+                }
+            }
+            if (j < P.M) {
+                if (out_kind == DSP_OUT_FBANK) {
+                    if (acc == 0.f) acc = DSP_EPS_F32;
+                    if (active) out[g * ld_out + j] = acc;
+                } else {
+                    logmel[j] = lg;
+                }
             }
         }
         if (out_kind == DSP_OUT_FBANK) {

@@ -27,7 +27,7 @@ class PlanDesc(C.Structure):
         ('frame_len', c_i32), ('frame_step', c_i32), ('nfft', c_i32), ('nfilt', c_i32),
         ('numcep', c_i32), ('append_energy', c_i32), ('preemph', c_f32),
         ('h_window', c_vp), ('h_mel_start', c_vp), ('h_mel_count', c_vp), ('h_mel_weights', c_vp),
-        ('h_dct', c_vp),
+        ('h_dct', c_vp), ('h_window64', c_vp), ('preemph64', c_f64),
     ]
 
 
@@ -219,7 +219,7 @@ def load():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        if lib.dsp_abi_version() != 1:
+        if lib.dsp_abi_version() != 2:
             raise DspError(f'ABI version mismatch: {lib.dsp_abi_version()}')
         _lib = lib
     return _lib

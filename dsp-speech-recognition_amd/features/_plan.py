@@ -109,7 +109,9 @@ class Plan:
             nat.require_device()
         self.L, self.S, self.nfft = int(L), int(S), int(nfft)
         self.K = self.nfft // 2 + 1
-        self.window = np.ascontiguousarray(window, dtype=np.float32)
+        # the window in fp64 as winfunc returned it (the fp64 repair of cancelled mel filters needs it), and rounded
+        self.window64 = np.ascontiguousarray(window, dtype=np.float64)
+        self.window = np.ascontiguousarray(self.window64, dtype=np.float32)
         if self.window.shape != (self.L,):
             raise ValueError(f'winfunc returned shape {self.window.shape}, expected ({self.L},)')
         self.M = 0 if fb is None else int(fb.shape[0])
@@ -119,8 +121,10 @@ class Plan:
         desc.nfilt, desc.numcep = self.M, self.C
         desc.append_energy = 1 if append_energy else 0
         desc.preemph = float(preemph)
+        desc.preemph64 = float(preemph)
         desc.h_window = self.window.ctypes.data
-        self._keep = [self.window]
+        desc.h_window64 = self.window64.ctypes.data
+        self._keep = [self.window, self.window64]
         if fb is not None:
             start, count, weights = mel_csr(fb)
             if weights.size == 0:
@@ -186,7 +190,7 @@ def mfcc_plan(samplerate, winlen, winstep, numcep, nfilt, nfft, lowfreq, highfre
               ceplifter, appendEnergy, winfunc, with_dct=True):
     """Plan for base.fbank / base.mfcc argument tuples."""
     L, S = frame_sizes(winlen * samplerate, winstep * samplerate)
-    w = np.ascontiguousarray(np.asarray(winfunc(L), dtype=np.float64), dtype=np.float32)
+    w = np.ascontiguousarray(np.asarray(winfunc(L), dtype=np.float64))
     highfreq = highfreq or samplerate / 2
     key = ('mfcc', L, S, int(nfft), int(nfilt), int(numcep) if with_dct else -1, float(samplerate),
            float(lowfreq), float(highfreq), float(preemph), float(ceplifter), bool(appendEnergy),

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define DSP_ABI_VERSION 1
+#define DSP_ABI_VERSION 2
 
 /* status codes */
 #define DSP_OK          0
@@ -73,6 +73,11 @@ typedef struct dsp_plan_desc {
     const int32_t* h_mel_count;   /* [M] number of stored weights                                  */
     const float*   h_mel_weights; /* [sum count] row after row                                     */
     const float*   h_dct;         /* [C, M] row-major, lifter already multiplied in                */
+    /* The fp64 side (ABI 2).  A mel filter that comes out below 7e-10 of its frame's energy -- pre-emphasis and window
+       nearly cancel its one or two bins -- is beyond an fp32 spectrum; the MFCC kernels recompute such a filter's bins
+       as fp64 DFT sums over the samples, and need window and coefficient as the reference has them. */
+    const double*  h_window64;    /* [L] the window before it was rounded to h_window; read only if nfilt > 0 */
+    double         preemph64;     /* the coefficient before it was rounded to preemph; checked and read only if nfilt > 0 */
 } dsp_plan_desc;
 
 /* ---- library / device plumbing ------------------------------------------------------------- */

@@ -96,4 +96,4 @@ def test_training_entry_points_reject_bad_arguments_without_a_device():
     for call, what in cases:
         rc = call()
         assert rc == nat.EINVAL and what in lib.dsp_last_error(), (rc, what, lib.dsp_last_error())
-    assert lib.dsp_abi_version() == 1
+    assert lib.dsp_abi_version() == 2

@@ -36,7 +36,7 @@ def test_config2_batch_1024_vs_oracle(plan, dtype):
     assert out.shape == (B * 99, 39) and fo[-1] == B * 99
     assert np.isfinite(out).all()
     worst = 0.0
-    for b in list(range(0, B, 37)) + [B - 1]:
+    for b in range(B):              # every utterance: a sample does not meet the one frame in 1e5 that cancels a narrow filter
         ref = dsp_oracle.mfcc_delta(waves[b].astype(np.float64), delta_n=2, winfunc=np.hamming, **CFG)
         worst = max(worst, normwise(out[fo[b]:fo[b + 1]], ref))
     assert worst <= TOL, worst

@@ -29,7 +29,7 @@ def test_header_symbols_exported(nat):
     for name in sorted(declared):
         assert hasattr(lib, name), f'{name} declared in the header but not exported'
     assert declared == set(nat.SIGNATURES), declared ^ set(nat.SIGNATURES)
-    assert lib.dsp_abi_version() == 1
+    assert lib.dsp_abi_version() == 2
 
 
 def test_library_exports_nothing_the_header_does_not_declare(nat):
@@ -48,9 +48,10 @@ def test_library_exports_nothing_the_header_does_not_declare(nat):
 
 def test_plan_desc_layout_matches_header(nat):
     import ctypes as C
-    # 6 int32 + 1 float (28 bytes, padded to 32) + 5 pointers
-    assert C.sizeof(nat.PlanDesc) == 32 + 5 * 8
+    # 6 int32 + 1 float (28 bytes, padded to 32) + 5 pointers + the fp64 side (ABI 2): 1 pointer + 1 double
+    assert C.sizeof(nat.PlanDesc) == 32 + 5 * 8 + 8 + 8
     assert nat.PlanDesc.h_window.offset == 32
+    assert nat.PlanDesc.h_window64.offset == 72 and nat.PlanDesc.preemph64.offset == 80
 
 
 def test_frame_count_host(nat):
