@@ -51,6 +51,7 @@ struct F1536Params {
     int64_t groups_per_utt, total_groups;
     const int32_t* group_off;   // ragged: [B+1] prefix of ceil(T_b / 4)
     const int32_t* group_utt;
+    const DspRepairTab* repair;   // fp64 tables of the repair of cancelled mel filters (kernels_repair.h)
 };
 
 struct Fast1536Plan {
@@ -547,6 +548,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES > 8 ? 3 : 2)) void mfcc1536_kern
         F512_FENCE();
         // gather the pieces of this lane's filters (c + 16 i) of its own frame, log
         float lm[NI];
+        unsigned long long rep_m[NI];
         {
             const float* pf = part + f * F1536_PART_STRIDE;
 #pragma unroll
@@ -555,8 +557,38 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES > 8 ? 3 : 2)) void mfcc1536_kern
                 const int4 x0 = px[0], x1 = px[1];
                 float acc = (pf[x0.x] + pf[x0.y]) + (pf[x0.z] + pf[x0.w]);
                 acc += (pf[x1.x] + pf[x1.y]) + (pf[x1.z] + pf[x1.w]);
+                // a filter the fp32 spectrum cannot carry (kernels_repair.h; 769 bins: the constant itself)
+                rep_m[i] = __ballot(acc > 0.f && acc < DSP_REPAIR_RATIO * energy);
                 if (acc == 0.f) acc = DSP_EPS_F32;
                 lm[i] = __logf(acc);
+            }
+        }
+        {
+            unsigned long long rep_any = 0;
+#pragma unroll
+            for (int i = 0; i < NI; ++i) rep_any |= rep_m[i];
+            if (rep_any != 0) {
+                // Rare and wave-uniform: the flagged filters' bins again as fp64 DFT sums over the samples in memory, by the
+                // whole wave, one filter at a time, as in kernels_fast512.h.  Lane s holds filter (s & 15) + 16 i of frame s >> 4.
+                // The group is located AGAIN here, from an opaque copy of its index: keeping the utterance's start alive
+                // down to this point would cost the whole loop scalar registers.
+                int Gc = G;
+                asm volatile("" : "+s"(Gc));
+                const F512Group g2 = f1536_locate<RAGGED>(P, bg, Gc);
+                const DspRepairTab* rep = P.repair;
+#pragma unroll
+                for (int i = 0; i < NI; ++i) {           // unrolled: lm[] stays in registers only under constant indices
+                    unsigned long long m = rep_m[i];
+                    while (m != 0) {
+                        const int sl = __builtin_ctzll(m);
+                        m &= m - 1;
+                        const int j = (sl & 15) + 16 * i, ut = g2.t0 + (sl >> 4);
+                        if (j >= P.M || ut >= g2.T) continue;   // frame slots behind the utterance's end are never stored
+                        const double a = dsp_repair_mel_f64<DTYPE>(rep, wave, g2.s0, (int64_t)g2.nsamp, (int64_t)ut * P.S, j, lane);
+                        const float nl = __logf(a == 0.0 ? DSP_EPS_F32 : (float)a);
+                        if (lane == sl) lm[i] = nl;
+                    }
+                }
             }
         }
         F512_FENCE();
@@ -608,8 +640,8 @@ static inline bool fast1536_shape_ok(const dsp_plan_desc* d) {
 static inline int fast1536_plan_init(dsp_plan* p, const dsp_plan_desc* d, const int32_t* mel_off) {
     p->d_fast1536 = nullptr;
     if (!fast1536_shape_ok(d)) return DSP_OK;
-    // This kernel has no fp64 repair of cancelled mel filters (kernels_repair.h).  Data does not cancel three neighbouring
-    // bins at once, and neither model plan has a narrower filter; a plan that has one runs on the generic kernel.
+    // Neither model plan has a filter of one or two bins; a plan that has one runs on the generic kernel.  (Wider filters
+    // are held against the frame's energy here as there and recomputed in fp64 when the spectrum cannot carry them.)
     for (int j = 0; j < d->nfilt; ++j)
         if (d->h_mel_count[j] <= 2) return DSP_OK;
     const int M = d->nfilt, C = d->numcep, L = d->frame_len;
@@ -752,6 +784,7 @@ static inline int fast1536_plan_init(dsp_plan* p, const dsp_plan_desc* d, const 
     fp->P.preemph = d->preemph;
     fp->P.span_vec = span_vec;
     fp->P.wave_floats = (int32_t)wave_floats;
+    fp->P.repair = static_cast<const DspRepairTab*>(p->d_repair);
     fp->variant = variant;
     p->d_fast1536 = fp;
     return DSP_OK;

@@ -77,6 +77,7 @@ __global__ __launch_bounds__(64 * DSP_GEN_WAVES) void features_generic_kernel(
     const int N2 = P.nfft >> 1;
     float2* bufA = reinterpret_cast<float2*>(smem) + (size_t)wid * 2 * N2;
     float2* bufB = bufA + N2;
+    const float repair_thr = dsp_repair_threshold(N2 + 1);   // by the plan's bin count (kernels_repair.h)
 
     // ragged batches: bg.total_frames may be an upper bound (device-built layouts), the table holds the truth
     const int64_t total_frames = bg.uniform_frames > 0 ? bg.total_frames : bg.frame_off[bg.n_utt];   // the table is read for ragged geometry only
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(64 * DSP_GEN_WAVES) void features_generic_kernel(
             float lg = logf(acc == 0.f ? DSP_EPS_F32 : acc);  // base.py:30
             if (out_kind == DSP_OUT_MFCC) {
                 // a filter the fp32 spectrum cannot carry: its bins again in fp64 (kernels_repair.h); rare and wave-uniform
-                unsigned long long m = __ballot(j < P.M && acc > 0.f && acc < DSP_REPAIR_RATIO * esum);
+                unsigned long long m = __ballot(j < P.M && acc > 0.f && acc < repair_thr * esum);
                 while (m != 0) {
                     const int src_lane = __builtin_ctzll(m);
                     m &= m - 1;

@@ -18,11 +18,30 @@
 // median bin magnitude is 7e-10 of the frame's energy (257 bins); the first ratio at which the unrepaired kernels miss
 // 5e-5 is 1e-4.  Every flagged filter costs its wave a few microseconds, so the margin is not made larger than that:
 // at 7e-10 a white-noise batch flags one frame in 4 000.
+// The value was derived at NFFT 512 (K = 257 bins) and holds as it is for every plan with at least that many bins (the
+// NFFT = 512 and 1536 kernels use the constant itself; measured on the generic kernel without the repair, white noise at
+// NFFT 256 .. 4096 never misses 5e-5 above it).  With fewer bins one bin is a larger share of the energy, the filterbank
+// is smaller and so are the cepstra the error is held against.  profiles/generic_repair_sweep.txt has the generic kernel's
+// error against the smallest filter / energy ratio of a frame per NFFT: no frame misses 5e-5 above 7e-7 at 9 bins, 2e-7 at
+// 13, 7e-9 at 33, 65 and 97 bins, 7e-10 from 129 bins on -- steeper than 257 / K and, at 97 bins, than its square.
+// dsp_repair_threshold is the constant times (257 / K)^3 below 257 bins: the same value at 257, never a smaller one, at
+// least 1.9 times every figure above.  It flags a few per cent of all frames at the smallest sizes, where the fp64 sum
+// over a frame of 16 .. 200 samples costs next to nothing.
 // -DDSP_REPAIR_RATIO=0.f switches the repair off in every kernel (nothing is below zero): the build the "without the
-// repair" figures were measured on.
+// repair" figures were measured on.  -DDSP_REPAIR_BINS=0 keeps the constant at every size (the rule before the sweep).
 #ifndef DSP_REPAIR_RATIO
 #define DSP_REPAIR_RATIO 7e-10f
 #endif
+#ifndef DSP_REPAIR_BINS
+#define DSP_REPAIR_BINS 257
+#endif
+
+// The threshold of a plan with K = NFFT / 2 + 1 bins (tests/generic_cases.py mirrors it operation by operation).
+__host__ __device__ __forceinline__ float dsp_repair_threshold(int K) {
+    if (K >= DSP_REPAIR_BINS) return DSP_REPAIR_RATIO;
+    const float s = (float)DSP_REPAIR_BINS / (float)K;
+    return DSP_REPAIR_RATIO * (s * s * s);
+}
 
 // One per plan with mel tables, in device memory (host memory under dsp_debug_host_dry_run).
 struct DspRepairTab {

@@ -63,7 +63,8 @@ typedef struct dsp_plan_desc {
     int32_t frame_len;        /* L  samples per frame (after round_half_up)                        */
     int32_t frame_step;       /* S  hop in samples                                                 */
     int32_t nfft;             /* NFFT: 2^k or 3*2^k, 16 <= NFFT <= 4096; frames longer are truncated
-                                 (sigproc.py:143-147)                                              */
+                                 (sigproc.py:143-147).  Each of the 17 sizes runs in a device test
+                                 against the oracle (tests/test_gpu_generic_configs.py)            */
     int32_t nfilt;            /* M  mel filters (0 if the plan is only used up to POWSPEC)         */
     int32_t numcep;           /* C  cepstra kept, C <= M                                           */
     int32_t append_energy;    /* base.py:15 -- column 0 := log(frame energy)                       */
