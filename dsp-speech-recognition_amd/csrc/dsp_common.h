@@ -10,6 +10,12 @@
 
 #define DSP_EPS_F32 2.220446049250313e-16f  // numpy.finfo(float).eps, base.py:26,30 (normal in fp32)
 
+// dsp_plan_transform's routes
+#define DSP_ROUTE_PASSES 0   // 2^k and 3 * 2^k: the pass list dsp_plan_create has always built
+#define DSP_ROUTE_MIXED 1    // even, half = 2^a 3^b 5^c: radix-5 passes, any number of 3s
+#define DSP_ROUTE_CHIRP 2    // everything else: chirp-z over a convolution of conv_len points
+#define DSP_CHIRP_LDS_MAX (160 * 1024)   // LDS of a workgroup on the chirp-z route
+
 struct dsp_plan {
     int32_t L, S, nfft, K, M, C, append_energy;
     int32_t lfft;       // min(L, nfft): samples of a frame that reach the FFT (sigproc.py:143-147)
@@ -31,6 +37,15 @@ struct dsp_plan {
     void* d_fast1536;       // tables of the specialised NFFT=1536 kernel (NULL if not applicable)
     void* d_mfma;           // tables of the matrix-pipe NFFT=512 kernel, kernels_mfma512.h (NULL if not applicable)
     void* d_mfmat;          // tables of its frame-per-product form, kernels_mfma512t.h (NULL if not applicable)
+    // the transform of the generic kernel (kernels_generic.h; dsp_plan_transform): DSP_ROUTE_*, its pass list (the passes of
+    // the convolution transform on the chirp-z route) and the chirp-z tables with the host copies the debug read-back returns
+    int32_t route, conv_len, n_pass;
+    int32_t radix[12];
+    float2* d_cz_w;         // [nfft]      exp(-i pi n^2 / nfft)
+    float2* d_cz_spec;      // [conv_len]  transform of the conjugate chirp in the forward passes' output order, / conv_len
+    float2* d_cz_tw;        // [conv_len]  exp(-2 pi i k / conv_len)
+    float2* h_cz_w;
+    float2* h_cz_spec;
     int device;
     int dry_run;            // tables live in HOST memory (dsp_debug_host_dry_run): the plan can be destroyed, nothing else
 };

@@ -3,6 +3,7 @@
 
 #include <atomic>
 #include <cmath>
+#include <complex>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -57,12 +58,82 @@ int upload(T** d, const T* h, size_t n) {
     return DSP_OK;
 }
 
+// the pass list of a transform of n2 = 2^a 3^b 5^c points: the 3s, the 5s, the 4s, a last 2.  For 2^k and 3 * 2^k (the
+// sizes dsp_plan_create accepts, and every convolution length of the chirp-z route) that is one optional 3, 4s and a 2
 bool factor_half_fft(int n2, std::vector<int>& radix) {
     radix.clear();
-    if (n2 % 3 == 0) { radix.push_back(3); n2 /= 3; }
+    while (n2 % 3 == 0) { radix.push_back(3); n2 /= 3; }
+    while (n2 % 5 == 0) { radix.push_back(5); n2 /= 5; }
     while (n2 % 4 == 0) { radix.push_back(4); n2 /= 4; }
     if (n2 % 2 == 0) { radix.push_back(2); n2 /= 2; }
     return n2 == 1 && radix.size() <= DSP_MAX_RADIX_PASSES;
+}
+
+bool is_pow2_or_3pow2(int n) {
+    if (n > 0 && n % 3 == 0) n /= 3;
+    return n > 0 && (n & (n - 1)) == 0;
+}
+
+// smallest 2^k or 3 * 2^k that is >= n
+int chirp_conv_len(int n) {
+    int best = 1;
+    while (best < n) best <<= 1;
+    for (int m = 3; m < best; m <<= 1)
+        if (m >= n) { best = m; break; }
+    return best;
+}
+
+// dif_pass of kernels_generic.h in fp64 on the host, all passes: natural order in, the kernels' digit-reversed order out.
+// O(n log n): the butterflies are direct R-point sums over an exact root table.
+void host_dif_f64(std::vector<std::complex<double>>& a, const std::vector<int>& radix) {
+    const int n = (int)a.size();
+    std::vector<std::complex<double>> tw(n);
+    for (int k = 0; k < n; ++k) {
+        const double ang = -2.0 * M_PI * (double)k / (double)n;
+        tw[k] = std::complex<double>(cos(ang), sin(ang));
+    }
+    int blk = n;
+    for (int R : radix) {
+        const int sub = blk / R, twstep = n / blk;
+        for (int b = 0; b < n / R; ++b) {
+            const int j = b % sub, base = (b - j) * R + j;
+            std::complex<double> u[5], y[5];
+            for (int q = 0; q < R; ++q) u[q] = a[base + q * sub];
+            for (int q2 = 0; q2 < R; ++q2) {
+                y[q2] = u[0];
+                for (int q = 1; q < R; ++q) y[q2] += u[q] * tw[(size_t)((q * q2) % R) * (n / R)];
+                y[q2] *= tw[(size_t)j * q2 * twstep];
+            }
+            for (int q = 0; q < R; ++q) a[base + q * sub] = y[q];
+        }
+        blk /= R;
+    }
+}
+
+// The tables of the chirp-z route (GenericParams::cz_*), built in fp64 and rounded to fp32 once.
+void chirp_tables(int nfft, int lfft, int K, int conv_len, const std::vector<int>& radix, std::vector<float2>& w,
+                  std::vector<float2>& spec, std::vector<float2>& tw) {
+    std::vector<std::complex<double>> w64(nfft);
+    w.resize(nfft);
+    for (int n = 0; n < nfft; ++n) {
+        const int64_t r = ((int64_t)n * n) % (2 * (int64_t)nfft);       // the argument reduced in integers
+        const double ang = -M_PI * (double)r / (double)nfft;
+        w64[n] = std::complex<double>(cos(ang), sin(ang));
+        w[n] = make_float2((float)w64[n].real(), (float)w64[n].imag());
+    }
+    // conj(w)[m], m = -(lfft - 1) .. K - 1, laid out circularly
+    std::vector<std::complex<double>> h(conv_len, std::complex<double>(0.0, 0.0));
+    for (int m = 0; m < K; ++m) h[m] = std::conj(w64[m]);
+    for (int m = 1; m < lfft; ++m) h[conv_len - m] = std::conj(w64[m]);
+    host_dif_f64(h, radix);
+    spec.resize(conv_len);
+    tw.resize(conv_len);
+    const double inv = 1.0 / (double)conv_len;
+    for (int i = 0; i < conv_len; ++i) {
+        spec[i] = make_float2((float)(h[i].real() * inv), (float)(h[i].imag() * inv));
+        const double ang = -2.0 * M_PI * (double)i / (double)conv_len;
+        tw[i] = make_float2((float)cos(ang), (float)sin(ang));
+    }
 }
 
 int check_geom(const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets,
@@ -105,10 +176,9 @@ GenericParams generic_params(const dsp_plan* p) {
     P.mel_start = p->d_mel_start; P.mel_count = p->d_mel_count; P.mel_off = p->d_mel_off;
     P.mel_w = p->d_mel_w; P.dct = p->d_dct;
     P.repair = static_cast<const DspRepairTab*>(p->d_repair);
-    std::vector<int> radix;
-    factor_half_fft(p->nfft / 2, radix);
-    P.n_pass = (int)radix.size();
-    for (int i = 0; i < P.n_pass; ++i) P.radix[i] = radix[i];
+    P.n_pass = p->n_pass;
+    for (int i = 0; i < P.n_pass; ++i) P.radix[i] = p->radix[i];
+    P.conv_len = p->conv_len; P.cz_w = p->d_cz_w; P.cz_spec = p->d_cz_spec; P.cz_tw = p->d_cz_tw;
     return P;
 }
 
@@ -253,15 +323,27 @@ void launch_delta_rows(int64_t blocks, hipStream_t st, const float* cep, const B
 int launch_generic(const dsp_plan* plan, const void* d_wave, int wave_dtype, const BatchGeom& bg,
                    int out_kind, float* d_out, int64_t ld_out, float* d_out2, hipStream_t st) {
     GenericParams P = generic_params(plan);
-    const size_t lds = (size_t)DSP_GEN_WAVES * 2 * (plan->nfft / 2) * sizeof(float2);
-    const int grid = grid_for(bg.total_frames, DSP_GEN_WAVES);
-    return dsp_dispatch_wave(wave_dtype, [&](auto dt) {
-        auto k = features_generic_kernel<decltype(dt)::value>;
+    // frames (waves) of a workgroup: DSP_GEN_WAVES; on the chirp-z route as many of them as fit 160 KiB of LDS
+    int waves = DSP_GEN_WAVES;
+    size_t lds = (size_t)DSP_GEN_WAVES * 2 * (plan->nfft / 2) * sizeof(float2);
+    if (plan->route == DSP_ROUTE_CHIRP) {
+        const size_t per_frame = (size_t)dsp_chirp_frame_lds(plan->conv_len, plan->K) * sizeof(float2);
+        while (waves > 1 && waves * per_frame > DSP_CHIRP_LDS_MAX) --waves;
+        lds = waves * per_frame;
+    }
+    const int grid = grid_for(bg.total_frames, waves);
+    auto launch = [&](auto k) {
         if (lds > 48 * 1024)
             HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k<<<grid, 64 * DSP_GEN_WAVES, lds, st>>>(P, bg, d_wave, out_kind, d_out, ld_out, d_out2);
+        k<<<grid, 64 * waves, lds, st>>>(P, bg, d_wave, out_kind, d_out, ld_out, d_out2);
         HIP_TRY(hipGetLastError());
         return (int)DSP_OK;
+    };
+    return dsp_dispatch_wave(wave_dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (plan->route == DSP_ROUTE_CHIRP) return launch(features_generic_kernel<DT, DSP_ROUTE_CHIRP>);
+        if (plan->route == DSP_ROUTE_MIXED) return launch(features_generic_kernel<DT, DSP_ROUTE_MIXED>);
+        return launch(features_generic_kernel<DT>);
     });
 }
 
@@ -658,13 +740,30 @@ int dsp_frame_offsets(const int64_t* h_sample_offsets, int32_t n_utt, int32_t fr
     return DSP_OK;
 }
 
-int dsp_plan_create(const dsp_plan_desc* d, dsp_plan** out) {
+int dsp_plan_create(const dsp_plan_desc* d, dsp_plan** out) { return dsp_plan_create_ex(d, 0, out); }
+
+int dsp_plan_create_ex(const dsp_plan_desc* d, uint32_t flags, dsp_plan** out) {
     if (!d || !out) return dsp_fail(DSP_EINVAL, "NULL desc/out");
     *out = nullptr;
+    if (flags & ~(uint32_t)DSP_PLAN_ANY_NFFT) return dsp_fail(DSP_EINVAL, "unknown plan flags 0x%x", flags);
     if (d->frame_len <= 0 || d->frame_step <= 0) return dsp_fail(DSP_EINVAL, "frame_len/frame_step must be > 0");
-    std::vector<int> radix;
-    if (d->nfft < 16 || d->nfft > 4096 || (d->nfft & 1) || !factor_half_fft(d->nfft / 2, radix))
+    if ((flags & DSP_PLAN_ANY_NFFT) && (d->nfft < 16 || d->nfft > 4096))
+        return dsp_fail(DSP_EINVAL, "unsupported nfft %d (need 16 <= nfft <= 4096)", d->nfft);
+    if (!(flags & DSP_PLAN_ANY_NFFT) && (d->nfft < 16 || d->nfft > 4096 || !is_pow2_or_3pow2(d->nfft)))
         return dsp_fail(DSP_EINVAL, "unsupported nfft %d (need 2^k or 3*2^k in [16, 4096])", d->nfft);
+    // the transform: the pass list of the 17 sizes, mixed radix for the other even sizes with a 5-smooth half, chirp-z for the rest
+    std::vector<int> radix;
+    int route = DSP_ROUTE_PASSES, conv_len = 0;
+    const int lfft_ = d->frame_len < d->nfft ? d->frame_len : d->nfft;
+    if (is_pow2_or_3pow2(d->nfft)) {
+        factor_half_fft(d->nfft / 2, radix);
+    } else if (!(d->nfft & 1) && factor_half_fft(d->nfft / 2, radix)) {
+        route = DSP_ROUTE_MIXED;
+    } else {
+        route = DSP_ROUTE_CHIRP;
+        conv_len = chirp_conv_len(lfft_ + d->nfft / 2);      // lfft + K - 1
+        factor_half_fft(conv_len, radix);
+    }
     if (!d->h_window) return dsp_fail(DSP_EINVAL, "h_window is NULL");
     if (d->nfilt > 0 && !d->h_window64) return dsp_fail(DSP_EINVAL, "h_window64 is NULL");
     if (d->nfilt > 0 && (float)d->preemph64 != d->preemph) return dsp_fail(DSP_EINVAL, "preemph64 does not round to preemph");
@@ -695,6 +794,8 @@ int dsp_plan_create(const dsp_plan_desc* d, dsp_plan** out) {
     p->M = d->nfilt; p->C = d->numcep; p->append_energy = d->append_energy ? 1 : 0;
     p->lfft = d->frame_len < d->nfft ? d->frame_len : d->nfft;
     p->preemph = d->preemph; p->mel_nnz = (int32_t)nnz; p->device = dev;
+    p->route = route; p->conv_len = conv_len; p->n_pass = (int32_t)radix.size();
+    for (size_t i = 0; i < radix.size(); ++i) p->radix[i] = radix[i];
     std::vector<float2> tw(d->nfft);
     for (int k = 0; k < d->nfft; ++k) {
         const double a = -2.0 * M_PI * (double)k / (double)d->nfft;
@@ -703,6 +804,21 @@ int dsp_plan_create(const dsp_plan_desc* d, dsp_plan** out) {
     int rc = DSP_OK;
     if (rc == DSP_OK) rc = upload(&p->d_window, d->h_window, (size_t)d->frame_len);
     if (rc == DSP_OK) rc = upload(&p->d_twiddle, tw.data(), tw.size());
+    if (rc == DSP_OK && route == DSP_ROUTE_CHIRP) {
+        std::vector<float2> cw, cspec, ctw;
+        chirp_tables(p->nfft, p->lfft, K, conv_len, radix, cw, cspec, ctw);
+        // host copies for dsp_debug_plan_transform_tables
+        p->h_cz_w = static_cast<float2*>(malloc(cw.size() * sizeof(float2)));
+        p->h_cz_spec = static_cast<float2*>(malloc(cspec.size() * sizeof(float2)));
+        if (!p->h_cz_w || !p->h_cz_spec) rc = dsp_fail(DSP_EHIP, "out of host memory");
+        if (rc == DSP_OK) {
+            memcpy(p->h_cz_w, cw.data(), cw.size() * sizeof(float2));
+            memcpy(p->h_cz_spec, cspec.data(), cspec.size() * sizeof(float2));
+            rc = upload(&p->d_cz_w, cw.data(), cw.size());
+        }
+        if (rc == DSP_OK) rc = upload(&p->d_cz_spec, cspec.data(), cspec.size());
+        if (rc == DSP_OK) rc = upload(&p->d_cz_tw, ctw.data(), ctw.size());
+    }
     if (rc == DSP_OK && d->nfilt > 0) {
         rc = upload(&p->d_mel_start, d->h_mel_start, (size_t)d->nfilt);
         if (rc == DSP_OK) rc = upload(&p->d_mel_count, d->h_mel_count, (size_t)d->nfilt);
@@ -741,11 +857,33 @@ int dsp_plan_create(const dsp_plan_desc* d, dsp_plan** out) {
     return DSP_OK;
 }
 
+int dsp_plan_transform(const dsp_plan* plan, int32_t* route, int32_t* conv_len) {
+    if (!plan || !route || !conv_len) return dsp_fail(DSP_EINVAL, "dsp_plan_transform: NULL argument");
+    *route = plan->route;
+    *conv_len = plan->conv_len;
+    return DSP_OK;
+}
+
+int dsp_debug_plan_transform_tables(const dsp_plan* plan, int32_t* radix, int32_t radix_cap, int32_t* n_pass, float* h_chirp,
+                                    float* h_chirp_spec) {
+    if (!plan || !radix || !n_pass) return dsp_fail(DSP_EINVAL, "dsp_debug_plan_transform_tables: NULL argument");
+    if (radix_cap < plan->n_pass) return dsp_fail(DSP_EINVAL, "radix_cap %d < %d passes", radix_cap, plan->n_pass);
+    *n_pass = plan->n_pass;
+    for (int i = 0; i < plan->n_pass; ++i) radix[i] = plan->radix[i];
+    if (plan->route == DSP_ROUTE_CHIRP) {
+        if (h_chirp) memcpy(h_chirp, plan->h_cz_w, (size_t)plan->nfft * sizeof(float2));
+        if (h_chirp_spec) memcpy(h_chirp_spec, plan->h_cz_spec, (size_t)plan->conv_len * sizeof(float2));
+    }
+    return DSP_OK;
+}
+
 int dsp_plan_destroy(dsp_plan* p) {
     if (!p) return DSP_OK;
     void* bufs[] = {p->d_window, p->d_twiddle, p->d_mel_start, p->d_mel_count, p->d_mel_off, p->d_mel_w, p->d_dct,
-                    p->d_window64, p->d_twiddle64, p->d_repair};
+                    p->d_window64, p->d_twiddle64, p->d_repair, p->d_cz_w, p->d_cz_spec, p->d_cz_tw};
     for (void* b : bufs) dsp_table_free(b, p->dry_run);
+    free(p->h_cz_w);
+    free(p->h_cz_spec);
     fast512_plan_free(p);
     fast1536_plan_free(p);
     mfma512_plan_free(p);

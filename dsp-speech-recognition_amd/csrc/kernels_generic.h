@@ -4,6 +4,11 @@
 // real-spectrum untangle, |X|^2/NFFT, CSR mel triangles, log, DCT*lifter, energy swap.
 // This is the correctness workhorse and the fallback for every configuration the specialised
 // NFFT=512 kernel (kernels_fast512.h) does not cover.
+//
+// The transform is a template parameter (ROUTE, dsp_plan_transform reports it); everything behind the spectrum is shared:
+//   0  the pass list of the 17 sizes 2^k and 3*2^k, radices 4 / 2 / 3: this instantiation is the one the parent had
+//   1  any even NFFT whose half is 2^a 3^b 5^c: the same packed transform with radix-5 passes and any number of 3s
+//   2  every other NFFT (odd, or a prime factor above 5 in its half): chirp-z (Bluestein), see chirp_spectrum below
 #pragma once
 
 #include "dsp_common.h"
@@ -24,7 +29,12 @@ struct GenericParams {
     const float* dct;
     const DspRepairTab* repair;  // fp64 tables for cancelled mel filters (kernels_repair.h)
     int32_t n_pass;
-    int32_t radix[DSP_MAX_RADIX_PASSES];
+    int32_t radix[DSP_MAX_RADIX_PASSES];   // route 2: the passes of the convolution transform of conv_len points
+    // the chirp-z route only (NULL / 0 otherwise)
+    int32_t conv_len;        // 2^k or 3*2^k >= lfft + K - 1
+    const float2* cz_w;      // [nfft]      w[n] = exp(-i pi n^2 / nfft)
+    const float2* cz_spec;   // [conv_len]  transform of conj(w) laid out circularly, in the order dif_pass leaves it, / conv_len
+    const float2* cz_tw;     // [conv_len]  exp(-2 pi i k / conv_len)
 };
 
 // One Stockham pass of radix R over n complex points held in LDS (in -> out), executed by one wave.
@@ -55,7 +65,7 @@ __device__ __forceinline__ void stockham_pass(const float2* __restrict__ in, flo
             out[j0] = make_float2(u[0].x + t1.x, u[0].y + t1.y);
             out[j0 + p] = make_float2(t2.x + t3.y, t2.y - t3.x);
             out[j0 + 2 * p] = make_float2(t2.x - t3.y, t2.y + t3.x);
-        } else {  // R == 4, forward: W4 = -i
+        } else if constexpr (R == 4) {  // forward: W4 = -i
             float2 a = make_float2(u[0].x + u[2].x, u[0].y + u[2].y);
             float2 b = make_float2(u[0].x - u[2].x, u[0].y - u[2].y);
             float2 c = make_float2(u[1].x + u[3].x, u[1].y + u[3].y);
@@ -64,26 +74,146 @@ __device__ __forceinline__ void stockham_pass(const float2* __restrict__ in, flo
             out[j0 + p] = make_float2(b.x + d.y, b.y - d.x);      // b - i d
             out[j0 + 2 * p] = make_float2(a.x - c.x, a.y - c.y);
             out[j0 + 3 * p] = make_float2(b.x - d.y, b.y + d.x);  // b + i d
+        } else {  // R == 5 (route 1 only)
+            static_assert(R == 5, "radices 2, 3, 4, 5");
+            const float c1 = 0.30901699437494742f, c2 = -0.80901699437494742f;   // cos(2 pi / 5), cos(4 pi / 5)
+            const float s1 = 0.95105651629515357f, s2 = 0.58778525229247313f;    // sin(2 pi / 5), sin(4 pi / 5)
+            float2 a1 = make_float2(u[1].x + u[4].x, u[1].y + u[4].y), b1 = make_float2(u[1].x - u[4].x, u[1].y - u[4].y);
+            float2 a2 = make_float2(u[2].x + u[3].x, u[2].y + u[3].y), b2 = make_float2(u[2].x - u[3].x, u[2].y - u[3].y);
+            float2 m1 = make_float2(fmaf(c1, a1.x, fmaf(c2, a2.x, u[0].x)), fmaf(c1, a1.y, fmaf(c2, a2.y, u[0].y)));
+            float2 m2 = make_float2(fmaf(c2, a1.x, fmaf(c1, a2.x, u[0].x)), fmaf(c2, a1.y, fmaf(c1, a2.y, u[0].y)));
+            float2 n1 = make_float2(fmaf(s1, b1.x, s2 * b2.x), fmaf(s1, b1.y, s2 * b2.y));
+            float2 n2 = make_float2(fmaf(s2, b1.x, -s1 * b2.x), fmaf(s2, b1.y, -s1 * b2.y));
+            out[j0] = make_float2(u[0].x + a1.x + a2.x, u[0].y + a1.y + a2.y);
+            out[j0 + p] = make_float2(m1.x + n1.y, m1.y - n1.x);      // m1 - i n1
+            out[j0 + 2 * p] = make_float2(m2.x + n2.y, m2.y - n2.x);  // m2 - i n2
+            out[j0 + 3 * p] = make_float2(m2.x - n2.y, m2.y + n2.x);  // m2 + i n2
+            out[j0 + 4 * p] = make_float2(m1.x - n1.y, m1.y + n1.x);  // m1 + i n1
         }
     }
 }
 
-template <int DTYPE>
+// ---- the chirp-z route: in-place passes over n complex points of one wave's LDS buffer ----
+// X[k] = w[k] sum_n (x[n] w[n]) conj(w)[k - n]: a circular convolution of conv_len >= lfft + K - 1 points, done as a forward
+// transform, a pointwise product with the stored transform of conj(w), and an inverse transform.  The forward passes are
+// decimation in frequency (natural order in, digit-reversed out), the inverse passes their conjugate transposes in the
+// opposite order (digit-reversed in, natural out), so nothing is permuted and one buffer serves; the stored spectrum lies in
+// the order the forward passes leave theirs (the host runs the same passes in fp64 to build it).
+
+// R-point DFT of u[] in place; INV: conjugate roots
+template <int R, bool INV>
+__device__ __forceinline__ void cz_butterfly(float2 (&u)[R]) {
+    if constexpr (R == 2) {
+        const float2 a = u[0], b = u[1];
+        u[0] = make_float2(a.x + b.x, a.y + b.y);
+        u[1] = make_float2(a.x - b.x, a.y - b.y);
+    } else if constexpr (R == 3) {
+        const float h = INV ? -0.86602540378443864676f : 0.86602540378443864676f;
+        const float2 t1 = make_float2(u[1].x + u[2].x, u[1].y + u[2].y);
+        const float2 t2 = make_float2(fmaf(-0.5f, t1.x, u[0].x), fmaf(-0.5f, t1.y, u[0].y));
+        const float2 t3 = make_float2(h * (u[1].x - u[2].x), h * (u[1].y - u[2].y));
+        u[0] = make_float2(u[0].x + t1.x, u[0].y + t1.y);
+        u[1] = make_float2(t2.x + t3.y, t2.y - t3.x);
+        u[2] = make_float2(t2.x - t3.y, t2.y + t3.x);
+    } else {
+        static_assert(R == 4, "radices 2, 3, 4");
+        const float2 a = make_float2(u[0].x + u[2].x, u[0].y + u[2].y), b = make_float2(u[0].x - u[2].x, u[0].y - u[2].y);
+        const float2 c = make_float2(u[1].x + u[3].x, u[1].y + u[3].y);
+        float2 d = make_float2(u[1].x - u[3].x, u[1].y - u[3].y);
+        if (INV) d = make_float2(-d.x, -d.y);
+        u[0] = make_float2(a.x + c.x, a.y + c.y);
+        u[1] = make_float2(b.x + d.y, b.y - d.x);
+        u[2] = make_float2(a.x - c.x, a.y - c.y);
+        u[3] = make_float2(b.x - d.y, b.y + d.x);
+    }
+}
+
+// forward pass of radix R over blocks of `blk` points (blk = n, n / R0, ... down the pass list): butterfly over the R points
+// j + q blk / R of a block, then output q times exp(-2 pi i j q / blk).  A butterfly reads and writes its own R points only.
+template <int R>
+__device__ __forceinline__ void dif_pass(float2* __restrict__ buf, int n, int blk, int lane, const float2* __restrict__ tw) {
+    const int sub = blk / R, twstep = n / blk;
+    for (int b = lane; b < n / R; b += 64) {
+        const int j = b % sub, base = (b - j) * R + j;
+        float2 u[R];
+#pragma unroll
+        for (int q = 0; q < R; ++q) u[q] = buf[base + q * sub];
+        cz_butterfly<R, false>(u);
+        buf[base] = u[0];
+#pragma unroll
+        for (int q = 1; q < R; ++q) buf[base + q * sub] = j ? cmul(u[q], tw[j * q * twstep]) : u[q];
+    }
+}
+
+// its conjugate transpose (an inverse pass, not scaled): conjugate twiddles first, then the conjugate butterfly
+template <int R>
+__device__ __forceinline__ void dit_pass(float2* __restrict__ buf, int n, int blk, int lane, const float2* __restrict__ tw) {
+    const int sub = blk / R, twstep = n / blk;
+    for (int b = lane; b < n / R; b += 64) {
+        const int j = b % sub, base = (b - j) * R + j;
+        float2 u[R];
+        u[0] = buf[base];
+#pragma unroll
+        for (int q = 1; q < R; ++q) {
+            float2 v = buf[base + q * sub];
+            if (j) {
+                const float2 w = tw[j * q * twstep];
+                v = cmul(v, make_float2(w.x, -w.y));
+            }
+            u[q] = v;
+        }
+        cz_butterfly<R, true>(u);
+#pragma unroll
+        for (int q = 0; q < R; ++q) buf[base + q * sub] = u[q];
+    }
+}
+
+// buf[0 .. conv_len) holds x[n] w[n] (zeros from lfft on) -> buf[k] = sum_n x[n] w[n] conj(w)[k - n], k < K
+__device__ __forceinline__ void chirp_spectrum(float2* __restrict__ buf, const GenericParams& P, int lane) {
+    const int n = P.conv_len;
+    int blk = n;
+    for (int s = 0; s < P.n_pass; ++s) {
+        const int R = P.radix[s];
+        if (R == 4) dif_pass<4>(buf, n, blk, lane, P.cz_tw);
+        else if (R == 2) dif_pass<2>(buf, n, blk, lane, P.cz_tw);
+        else dif_pass<3>(buf, n, blk, lane, P.cz_tw);
+        blk /= R;
+        __syncthreads();
+    }
+    for (int i = lane; i < n; i += 64) buf[i] = cmul(buf[i], P.cz_spec[i]);
+    __syncthreads();
+    for (int s = P.n_pass - 1; s >= 0; --s) {
+        const int R = P.radix[s];
+        blk *= R;
+        if (R == 4) dit_pass<4>(buf, n, blk, lane, P.cz_tw);
+        else if (R == 2) dit_pass<2>(buf, n, blk, lane, P.cz_tw);
+        else dit_pass<3>(buf, n, blk, lane, P.cz_tw);
+        __syncthreads();
+    }
+}
+
+// LDS of one wave's frame on the chirp-z route, in float2 units: the convolution buffer and K floats of power spectrum
+__host__ __device__ __forceinline__ int dsp_chirp_frame_lds(int conv_len, int K) { return conv_len + (K + 1) / 2; }
+
+template <int DTYPE, int ROUTE = 0>
 __global__ __launch_bounds__(64 * DSP_GEN_WAVES) void features_generic_kernel(
     GenericParams P, BatchGeom bg, const void* __restrict__ wave, int out_kind, float* __restrict__ out,
     int64_t ld_out, float* __restrict__ out2) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int N2 = P.nfft >> 1;
-    float2* bufA = reinterpret_cast<float2*>(smem) + (size_t)wid * 2 * N2;
-    float2* bufB = bufA + N2;
+    // routes 0 and 1: two buffers of NFFT / 2 points per wave; route 2: one of conv_len points and the power spectrum behind it
+    float2* bufA = reinterpret_cast<float2*>(smem) + (ROUTE == 2 ? (size_t)wid * dsp_chirp_frame_lds(P.conv_len, N2 + 1) : (size_t)wid * 2 * N2);
+    float2* bufB = bufA + (ROUTE == 2 ? P.conv_len : N2);
     const float repair_thr = dsp_repair_threshold(N2 + 1);   // by the plan's bin count (kernels_repair.h)
+    // frames of a workgroup: route 2 launches as many waves as its LDS allows (1 .. DSP_GEN_WAVES)
+    const int waves = ROUTE == 2 ? (int)(blockDim.x >> 6) : DSP_GEN_WAVES;
 
     // ragged batches: bg.total_frames may be an upper bound (device-built layouts), the table holds the truth
     const int64_t total_frames = bg.uniform_frames > 0 ? bg.total_frames : bg.frame_off[bg.n_utt];   // the table is read for ragged geometry only
-    const int64_t n_tiles = (total_frames + DSP_GEN_WAVES - 1) / DSP_GEN_WAVES;
+    const int64_t n_tiles = (total_frames + waves - 1) / waves;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        int64_t g = tile * DSP_GEN_WAVES + wid;
+        int64_t g = tile * waves + wid;
         const bool active = g < total_frames;
         if (!active) g = total_frames - 1;  // keep the wave in step with the barriers
         int32_t utt;
@@ -105,37 +235,57 @@ __global__ __launch_bounds__(64 * DSP_GEN_WAVES) void features_generic_kernel(
             if (out_kind == DSP_OUT_FRAMES) {
                 if (active) out[g * ld_out + n] = v;
             } else if (n < P.lfft) {
-                fr[n] = v;
+                if constexpr (ROUTE == 2) {
+                    const float2 w = P.cz_w[n];
+                    bufA[n] = make_float2(v * w.x, v * w.y);
+                } else {
+                    fr[n] = v;
+                }
             }
         }
         if (out_kind == DSP_OUT_FRAMES) continue;  // uniform over the block
-        for (int n = P.lfft + lane; n < P.nfft; n += 64) fr[n] = 0.f;
+        if constexpr (ROUTE == 2) {
+            for (int n = P.lfft + lane; n < P.conv_len; n += 64) bufA[n] = make_float2(0.f, 0.f);
+        } else {
+            for (int n = P.lfft + lane; n < P.nfft; n += 64) fr[n] = 0.f;
+        }
         __syncthreads();
 
-        // ---- complex FFT of z[m] = x[2m] + i x[2m+1], m < NFFT/2 ----
         float2* src = bufA;
         float2* dst = bufB;
-        int p = 1;
-        for (int s = 0; s < P.n_pass; ++s) {
-            const int R = P.radix[s];
-            if (R == 4) stockham_pass<4>(src, dst, N2, p, lane, P.tw, P.nfft);
-            else if (R == 2) stockham_pass<2>(src, dst, N2, p, lane, P.tw, P.nfft);
-            else stockham_pass<3>(src, dst, N2, p, lane, P.tw, P.nfft);
-            p *= R;
-            float2* tmp = src; src = dst; dst = tmp;
-            __syncthreads();
+        if constexpr (ROUTE == 2) {
+            // ---- chirp-z: src[k] w[k] = X[k], k <= NFFT/2 ----
+            chirp_spectrum(bufA, P, lane);
+        } else {
+            // ---- complex FFT of z[m] = x[2m] + i x[2m+1], m < NFFT/2 ----
+            int p = 1;
+            for (int s = 0; s < P.n_pass; ++s) {
+                const int R = P.radix[s];
+                if (R == 4) stockham_pass<4>(src, dst, N2, p, lane, P.tw, P.nfft);
+                else if (R == 2) stockham_pass<2>(src, dst, N2, p, lane, P.tw, P.nfft);
+                else if (ROUTE == 0 || R == 3) stockham_pass<3>(src, dst, N2, p, lane, P.tw, P.nfft);
+                else stockham_pass<5>(src, dst, N2, p, lane, P.tw, P.nfft);
+                p *= R;
+                float2* tmp = src; src = dst; dst = tmp;
+                __syncthreads();
+            }
         }
         // ---- untangle to the real-input spectrum, |X|^2 / NFFT (sigproc.py:136-158) ----
         float* pspec = reinterpret_cast<float*>(dst);  // K = N2 + 1 <= 2*N2 floats
         const float inv_nfft = 1.0f / (float)P.nfft;
         float esum = 0.f;
         for (int k = lane; k <= N2; k += 64) {
-            const float2 zk = src[k == N2 ? 0 : k];
-            const float2 zc = src[k == 0 ? 0 : N2 - k];
-            const float2 e = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y - zc.y));
-            const float2 o = make_float2(0.5f * (zk.y + zc.y), -0.5f * (zk.x - zc.x));
-            const float2 w = P.tw[k];
-            const float2 x = make_float2(e.x + fmaf(w.x, o.x, -w.y * o.y), e.y + fmaf(w.x, o.y, w.y * o.x));
+            float2 x;
+            if constexpr (ROUTE == 2) {
+                x = cmul(src[k], P.cz_w[k]);
+            } else {
+                const float2 zk = src[k == N2 ? 0 : k];
+                const float2 zc = src[k == 0 ? 0 : N2 - k];
+                const float2 e = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y - zc.y));
+                const float2 o = make_float2(0.5f * (zk.y + zc.y), -0.5f * (zk.x - zc.x));
+                const float2 w = P.tw[k];
+                x = make_float2(e.x + fmaf(w.x, o.x, -w.y * o.y), e.y + fmaf(w.x, o.y, w.y * o.x));
+            }
             const float m2 = fmaf(x.x, x.x, x.y * x.y);
             if (out_kind == DSP_OUT_MAGSPEC) {
                 if (active) out[g * ld_out + k] = sqrtf(m2);

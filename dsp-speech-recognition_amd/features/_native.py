@@ -18,6 +18,8 @@ LIB_PATH = os.environ.get('DSP_FRONTEND_LIB', os.path.join(_PKG, 'lib', 'libdsp_
 OK, EINVAL, EHIP, ENODEV = 0, -1, -2, -3
 WAVE_F32, WAVE_I16 = 0, 1
 OUT_FRAMES, OUT_MAGSPEC, OUT_POWSPEC, OUT_FBANK, OUT_MFCC = 0, 1, 2, 3, 4
+PLAN_ANY_NFFT = 1
+ROUTE_PASSES, ROUTE_MIXED, ROUTE_CHIRP = 0, 1, 2
 
 c_i32, c_i64, c_f32, c_f64, c_vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 
@@ -81,6 +83,9 @@ SIGNATURES = {
     'dsp_frame_count': (C.c_int, [c_i64, c_i32, c_i32, C.POINTER(c_i64)]),
     'dsp_frame_offsets': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp]),
     'dsp_plan_create': (C.c_int, [C.POINTER(PlanDesc), C.POINTER(c_vp)]),
+    'dsp_plan_create_ex': (C.c_int, [C.POINTER(PlanDesc), C.c_uint32, C.POINTER(c_vp)]),
+    'dsp_plan_transform': (C.c_int, [c_vp, C.POINTER(c_i32), C.POINTER(c_i32)]),
+    'dsp_debug_plan_transform_tables': (C.c_int, [c_vp, c_vp, c_i32, C.POINTER(c_i32), c_vp, c_vp]),
     'dsp_plan_destroy': (C.c_int, [c_vp]),
     'dsp_plan_has_fast_path': (C.c_int, [c_vp]),
     'dsp_debug_force_generic': (C.c_int, [C.c_int]),

@@ -102,7 +102,9 @@ def lifter_vector(ncoeff, L=22):
 class Plan:
     """Owns one dsp_plan handle plus the host copies of its tables."""
 
-    def __init__(self, L, S, nfft, window, preemph=0.0, fb=None, dct=None, append_energy=False, host_dry_run=False):
+    def __init__(self, L, S, nfft, window, preemph=0.0, fb=None, dct=None, append_energy=False, host_dry_run=False,
+                 any_nfft=False):
+        # any_nfft: every integer 16 <= nfft <= 4096 (dsp_plan_create_ex with DSP_PLAN_ANY_NFFT), as the reference's rfft takes
         # host_dry_run (tests of the sanitizer build only): every host-side table builder runs, the tables stay in host
         # memory, no device is touched; the plan can be destroyed and nothing else (include/dsp_frontend.h)
         if not host_dry_run:
@@ -140,11 +142,33 @@ class Plan:
         if host_dry_run:
             nat.check(nat.load().dsp_debug_host_dry_run(1))
         try:
-            nat.check(nat.load().dsp_plan_create(C.byref(desc), C.byref(h)))
+            if any_nfft:
+                nat.check(nat.load().dsp_plan_create_ex(C.byref(desc), nat.PLAN_ANY_NFFT, C.byref(h)))
+            else:
+                nat.check(nat.load().dsp_plan_create(C.byref(desc), C.byref(h)))
         finally:
             if host_dry_run:
                 nat.check(nat.load().dsp_debug_host_dry_run(0))
         self.handle = h.value
+
+    def transform(self):
+        """(route, conv_len) of dsp_plan_transform: 0 the pass list of 2^k / 3 2^k, 1 mixed radix, 2 chirp-z."""
+        route, conv = C.c_int32(-1), C.c_int32(-1)
+        nat.check(nat.load().dsp_plan_transform(self.handle, C.byref(route), C.byref(conv)))
+        return route.value, conv.value
+
+    def transform_tables(self):
+        """(pass list, chirp [nfft] complex64 or None, stored chirp spectrum [conv_len] complex64 or None): the debug
+        read-back of the transform's host tables (works on a host_dry_run plan)."""
+        route, conv = self.transform()
+        radix = (C.c_int32 * 12)()
+        n = C.c_int32(0)
+        w = np.zeros(self.nfft if route == nat.ROUTE_CHIRP else 0, dtype=np.complex64)
+        sp = np.zeros(conv, dtype=np.complex64)
+        nat.check(nat.load().dsp_debug_plan_transform_tables(self.handle, radix, 12, C.byref(n), w.ctypes.data if w.size else None,
+                                                             sp.ctypes.data if sp.size else None))
+        passes = [int(radix[i]) for i in range(n.value)]
+        return (passes, w, sp) if route == nat.ROUTE_CHIRP else (passes, None, None)
 
     def __del__(self):
         h = getattr(self, 'handle', None)
@@ -173,8 +197,8 @@ def _cached(key, build):
         return p
 
 
-def frame_plan(L, S, window, nfft=None, preemph=0.0):
-    """Plan that stops at frames / spectra (no mel tables)."""
+def frame_plan(L, S, window, nfft=None, preemph=0.0, any_nfft=False):
+    """Plan that stops at frames / spectra (no mel tables).  nfft=None: the power of two that holds a frame."""
     L, S = int(L), int(S)
     if nfft is None:
         nfft = 16
@@ -182,23 +206,23 @@ def frame_plan(L, S, window, nfft=None, preemph=0.0):
             nfft *= 2
         nfft = min(nfft, 4096)
     w = np.ascontiguousarray(window, dtype=np.float32)
-    key = ('frame', L, S, int(nfft), float(preemph), w.tobytes())
-    return _cached(key, lambda: Plan(L, S, nfft, w, preemph=preemph))
+    key = ('frame', L, S, int(nfft), float(preemph), w.tobytes(), bool(any_nfft))
+    return _cached(key, lambda: Plan(L, S, nfft, w, preemph=preemph, any_nfft=any_nfft))
 
 
 def mfcc_plan(samplerate, winlen, winstep, numcep, nfilt, nfft, lowfreq, highfreq, preemph,
-              ceplifter, appendEnergy, winfunc, with_dct=True):
+              ceplifter, appendEnergy, winfunc, with_dct=True, any_nfft=False):
     """Plan for base.fbank / base.mfcc argument tuples."""
     L, S = frame_sizes(winlen * samplerate, winstep * samplerate)
     w = np.ascontiguousarray(np.asarray(winfunc(L), dtype=np.float64))
     highfreq = highfreq or samplerate / 2
     key = ('mfcc', L, S, int(nfft), int(nfilt), int(numcep) if with_dct else -1, float(samplerate),
            float(lowfreq), float(highfreq), float(preemph), float(ceplifter), bool(appendEnergy),
-           w.tobytes())
+           w.tobytes(), bool(any_nfft))
 
     def build():
         fb = filterbank_matrix(nfilt, nfft, samplerate, lowfreq, highfreq)
         dct = dct_lifter_matrix(nfilt, numcep, ceplifter) if with_dct else None
-        return Plan(L, S, nfft, w, preemph=preemph, fb=fb, dct=dct, append_energy=appendEnergy)
+        return Plan(L, S, nfft, w, preemph=preemph, fb=fb, dct=dct, append_energy=appendEnergy, any_nfft=any_nfft)
 
     return _cached(key, build)

@@ -37,7 +37,7 @@ def mfcc(signal, samplerate=16000, winlen=0.025, winstep=0.01, numcep=13,
     log-energy swap of column 0."""
     sig, pre = _prepare_signal(signal, preemph)
     plan = _plan.mfcc_plan(samplerate, winlen, winstep, numcep, nfilt, nfft, lowfreq, highfreq, pre,
-                           ceplifter, appendEnergy, winfunc)
+                           ceplifter, appendEnergy, winfunc, any_nfft=True)
     return _run.features(plan, sig, nat.OUT_MFCC).astype(numpy.float64)
 
 
@@ -48,7 +48,7 @@ def fbank(signal, samplerate=16000, winlen=0.025, winstep=0.01,
     energy[T]); exact zeros are replaced by float64 eps as the reference does before any log."""
     sig, pre = _prepare_signal(signal, preemph)
     plan = _plan.mfcc_plan(samplerate, winlen, winstep, 0, nfilt, nfft, lowfreq, highfreq, pre,
-                           0, False, winfunc, with_dct=False)
+                           0, False, winfunc, with_dct=False, any_nfft=True)
     feat, energy = _run.features(plan, sig, nat.OUT_FBANK)
     return feat.astype(numpy.float64), energy.astype(numpy.float64)
 

@@ -151,7 +151,7 @@ class FeaturePlan:
                  lowfreq=0, highfreq=None, preemph=0.97, ceplifter=22, appendEnergy=True,
                  winfunc=_ones):
         self.plan = _plan.mfcc_plan(samplerate, winlen, winstep, numcep, nfilt, nfft, lowfreq,
-                                    highfreq, preemph, ceplifter, appendEnergy, winfunc)
+                                    highfreq, preemph, ceplifter, appendEnergy, winfunc, any_nfft=True)
         self.L, self.S, self.C = self.plan.L, self.plan.S, self.plan.C
 
     def layout(self, waves, sample_offsets=None):

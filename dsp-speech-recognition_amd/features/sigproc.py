@@ -47,7 +47,7 @@ def _spectrum(frames, NFFT, kind):
     if L > NFFT:  # sigproc.py:143-146
         logging.warning('frame length (%d) is greater than FFT size (%d), frame will be truncated. '
                         'Increase NFFT to avoid.', L, NFFT)
-    plan = _plan.frame_plan(L, L, numpy.ones(L), nfft=NFFT)
+    plan = _plan.frame_plan(L, L, numpy.ones(L), nfft=NFFT, any_nfft=True)      # any 16 <= NFFT <= 4096, as numpy's rfft
     return _run.rows_features(plan, frames, kind).astype(numpy.float64)
 
 

@@ -62,9 +62,11 @@ typedef struct dsp_plan dsp_plan;
 typedef struct dsp_plan_desc {
     int32_t frame_len;        /* L  samples per frame (after round_half_up)                        */
     int32_t frame_step;       /* S  hop in samples                                                 */
-    int32_t nfft;             /* NFFT: 2^k or 3*2^k, 16 <= NFFT <= 4096; frames longer are truncated
+    int32_t nfft;             /* NFFT: 2^k or 3*2^k, 16 <= NFFT <= 4096 -- with DSP_PLAN_ANY_NFFT every
+                                 integer in that range; frames longer are truncated
                                  (sigproc.py:143-147).  Each of the 17 sizes runs in a device test
-                                 against the oracle (tests/test_gpu_generic_configs.py)            */
+                                 against the oracle (tests/test_gpu_generic_configs.py), 24 of the
+                                 others in tests/test_gpu_anyfft.py                                */
     int32_t nfilt;            /* M  mel filters (0 if the plan is only used up to POWSPEC)         */
     int32_t numcep;           /* C  cepstra kept, C <= M                                           */
     int32_t append_energy;    /* base.py:15 -- column 0 := log(frame energy)                       */
@@ -103,6 +105,22 @@ int dsp_frame_offsets(const int64_t* h_sample_offsets, int32_t n_utt, int32_t fr
 
 /* ---- plans --------------------------------------------------------------------------------- */
 int dsp_plan_create(const dsp_plan_desc* desc, dsp_plan** plan);
+/* flags = 0: dsp_plan_create.  DSP_PLAN_ANY_NFFT: every integer 16 <= nfft <= 4096 is accepted, as numpy.fft.rfft takes any
+   size (sigproc.py:136-148, base.py:40-58); the sizes dsp_plan_create accepts get the plan it builds. */
+#define DSP_PLAN_ANY_NFFT 1
+int dsp_plan_create_ex(const dsp_plan_desc* desc, uint32_t flags, dsp_plan** plan);
+/* How the generic kernel transforms a frame of this plan.  route 0: the pass list of the 17 sizes 2^k and 3*2^k; 1: mixed
+   radix (even nfft whose half is 2^a 3^b 5^c: radix 2 / 3 / 4 / 5 passes over the packed real transform); 2: chirp-z
+   (every other size), a circular convolution of *conv_len points (the smallest 2^k or 3*2^k >= min(frame_len, nfft) +
+   nfft/2).  *conv_len is 0 on routes 0 and 1. */
+int dsp_plan_transform(const dsp_plan* plan, int32_t* route, int32_t* conv_len);
+/* testing aid: the transform's host tables, also of a plan made under dsp_debug_host_dry_run.  radix[0 .. *n_pass) is the
+   pass list (on route 2 that of the convolution transform; radix_cap: the room in radix, 12 always suffices).  Route 2
+   only, either may be NULL: h_chirp [nfft][2] = exp(-i pi n^2 / nfft), h_chirp_spec [conv_len][2] = the transform of the
+   conjugate chirp as stored -- divided by conv_len, in the order the forward passes leave their output (tools/anyfft_emul.py
+   restates it), both rounded to fp32. */
+int dsp_debug_plan_transform_tables(const dsp_plan* plan, int32_t* radix, int32_t radix_cap, int32_t* n_pass, float* h_chirp,
+                                    float* h_chirp_spec);
 int dsp_plan_destroy(dsp_plan* plan);
 /* 1 if the plan is served by a specialised fused kernel (NFFT = 512 or 1536), 0 if only by the generic one */
 int dsp_plan_has_fast_path(const dsp_plan* plan);

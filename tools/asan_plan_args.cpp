@@ -1,4 +1,4 @@
-// Stand-alone host check of dsp_plan_create (include/dsp_frontend.h, ABI 2: the plan descriptor carries the fp64 window and
+// Stand-alone host check of dsp_plan_create and dsp_plan_create_ex (include/dsp_frontend.h, ABI 2: the plan descriptor carries the fp64 window and
 // the fp64 pre-emphasis coefficient for the repair of cancelled mel filters, csrc/kernels_repair.h).  Under
 // dsp_debug_host_dry_run(1) every host-side table builder runs -- the fp64 window / twiddle tables, the repair descriptor and
 // the NFFT = 512 blob with the pointer behind it included -- with the tables in host memory: the program needs no GPU.
@@ -94,6 +94,55 @@ int main() {
         dsp_plan* p = nullptr;
         if (dsp_plan_create(&d, &p) != DSP_OK) { std::printf("frame plan: %s\n", dsp_last_error()); ++g_bad; }
         dsp_plan_destroy(p);
+    }
+    // dsp_plan_create_ex with DSP_PLAN_ANY_NFFT: the factoriser, the chirp tables and their fp64 transform, the debug read-back
+    // into exactly-sized buffers -- every size the device tests use, every size below 128, three frame lengths each
+    {
+        std::vector<int> sizes = {20, 50, 160, 400, 576, 1000, 1200, 2000, 3456, 3750, 4000, 4050,
+                                  17, 22, 25, 331, 401, 551, 1103, 1323, 2049, 4093, 4094, 4095, 1440, 512, 1536, 4096};
+        for (int n = 16; n < 128; ++n) sizes.push_back(n);
+        for (int nfft : sizes) {
+            const int lens[3] = {25 * nfft / 32, nfft, nfft + nfft / 4 + 1};
+            for (int L : lens) {
+                const int M = nfft / 4 < 26 ? nfft / 4 : 26, Cc = M < 13 ? M : 13;
+                const Tables t = make_tables(L, nfft, M, Cc, 1);
+                dsp_plan_desc d = make_desc(t, L, L / 3 > 0 ? L / 3 : 1, nfft, M, Cc, 0.97);
+                dsp_plan* p = nullptr;
+                if (dsp_plan_create_ex(&d, DSP_PLAN_ANY_NFFT, &p) != DSP_OK || !p) {
+                    std::printf("any-nfft plan %d L %d: %s\n", nfft, L, dsp_last_error());
+                    ++g_bad;
+                    continue;
+                }
+                int32_t route = -1, conv = -1, n_pass = 0;
+                std::vector<int32_t> radix(12);
+                if (dsp_plan_transform(p, &route, &conv) != DSP_OK || route < 0 || route > 2) { std::printf("nfft %d: route %d\n", nfft, route); ++g_bad; }
+                const int lfft = L < nfft ? L : nfft;
+                if (route == 2 && conv < lfft + nfft / 2) { std::printf("nfft %d L %d: conv_len %d too short\n", nfft, L, conv); ++g_bad; }
+                if (route != 2 && conv != 0) { std::printf("nfft %d: conv_len %d on route %d\n", nfft, conv, route); ++g_bad; }
+                std::vector<float> chirp(route == 2 ? 2 * (size_t)nfft : 0), spec(route == 2 ? 2 * (size_t)conv : 0);
+                if (dsp_debug_plan_transform_tables(p, radix.data(), 12, &n_pass, route == 2 ? chirp.data() : nullptr,
+                                                    route == 2 ? spec.data() : nullptr) != DSP_OK) {
+                    std::printf("nfft %d: read-back: %s\n", nfft, dsp_last_error());
+                    ++g_bad;
+                }
+                long long prod = 1;
+                for (int i = 0; i < n_pass; ++i) prod *= radix[i];
+                if (prod != (route == 2 ? conv : nfft / 2)) { std::printf("nfft %d: passes multiply to %lld\n", nfft, prod); ++g_bad; }
+                if (route == 2 && (chirp[0] != 1.f || chirp[1] != 0.f)) { std::printf("nfft %d: chirp[0]\n", nfft); ++g_bad; }
+                EXPECT(dsp_debug_plan_transform_tables(p, radix.data(), n_pass - 1, &n_pass, nullptr, nullptr), "radix_cap");
+                dsp_plan_destroy(p);
+            }
+        }
+        const Tables t = make_tables(20, 512, 4, 4, 1);
+        dsp_plan* p = nullptr;
+        for (int bad : {15, 4097, 0}) {
+            dsp_plan_desc d = make_desc(t, 20, 7, bad, 4, 4, 0.97);
+            EXPECT(dsp_plan_create_ex(&d, DSP_PLAN_ANY_NFFT, &p), "16 <= nfft <= 4096");
+        }
+        dsp_plan_desc d = make_desc(t, 20, 7, 500, 4, 4, 0.97);
+        EXPECT(dsp_plan_create_ex(&d, 0, &p), "2^k or 3*2^k");
+        EXPECT(dsp_plan_create(&d, &p), "2^k or 3*2^k");
+        EXPECT(dsp_plan_create_ex(&d, 2, &p), "flags");
     }
     // the argument checks of the new fields
     {
