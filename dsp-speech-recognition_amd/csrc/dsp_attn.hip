@@ -276,7 +276,7 @@ int dsp_attn_backward(const dsp_attn* h, int32_t T, int32_t B, const void* d_tap
 namespace {
 
 int selfattn_pool(const char* who, const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
-                  const float* d_c, float* d_out, float* d_w, void* stream) {
+                  const float* d_c, float* d_out, float* d_w, const int32_t* d_rows, void* stream) {
     if (!d_y || !d_W || !d_bW || !d_v || !d_c || !d_out) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
     if (T < 1 || T > AT_MAX_T) return dsp_fail(DSP_EINVAL, "%s: T %d must be in [1, %d]", who, T, AT_MAX_T);
     if (B < 1) return dsp_fail(DSP_EINVAL, "%s: B %d must be >= 1", who, B);
@@ -284,7 +284,7 @@ int selfattn_pool(const char* who, const float* d_y, int32_t T, int32_t B, int32
     if (((reinterpret_cast<uintptr_t>(d_y) | reinterpret_cast<uintptr_t>(d_W)) & 15) != 0)
         return dsp_fail(DSP_EINVAL, "%s: d_y and d_W must be 16-byte aligned", who);
     if (int rc = attn_check_launch(who, nullptr)) return rc;
-    selfattn_pool_kernel<<<B, 64, 0, (hipStream_t)stream>>>(d_y, T, B, H, d_W, d_bW, d_v, d_c, d_out, d_w);
+    selfattn_pool_kernel<<<B, 64, 0, (hipStream_t)stream>>>(d_y, T, B, H, d_W, d_bW, d_v, d_c, d_out, d_w, d_rows);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }
@@ -295,14 +295,21 @@ extern "C" {
 
 int dsp_selfattn_pool_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
                             const float* d_c, float* d_out, void* stream) {
-    return selfattn_pool("dsp_selfattn_pool_batch", d_y, T, B, H, d_W, d_bW, d_v, d_c, d_out, nullptr, stream);
+    return selfattn_pool("dsp_selfattn_pool_batch", d_y, T, B, H, d_W, d_bW, d_v, d_c, d_out, nullptr, nullptr, stream);
+}
+
+int dsp_selfattn_pool_rows_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
+                                 const float* d_c, float* d_out, const int32_t* d_rows, void* stream) {
+    const char* who = "dsp_selfattn_pool_rows_batch";
+    if (!d_rows) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
+    return selfattn_pool(who, d_y, T, B, H, d_W, d_bW, d_v, d_c, d_out, nullptr, d_rows, stream);
 }
 
 int dsp_selfattn_pool_train_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
                                   const float* d_c, float* d_out, float* d_w, void* stream) {
     const char* who = "dsp_selfattn_pool_train_batch";
     if (!d_w) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
-    return selfattn_pool(who, d_y, T, B, H, d_W, d_bW, d_v, d_c, d_out, d_w, stream);
+    return selfattn_pool(who, d_y, T, B, H, d_W, d_bW, d_v, d_c, d_out, d_w, nullptr, stream);
 }
 
 int dsp_selfattn_pool_backward_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,

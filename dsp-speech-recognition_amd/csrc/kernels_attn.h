@@ -288,14 +288,18 @@ static inline void at_pack_host(float* dst, const float* src, int K, int N, int6
 }
 
 // layers.SelfAttn for column b: e[t] = v . tanh(W y[t, b] + b_W) + c over all T rows, softmax over t, out[b] = sum_t w[t] y[t, b].
-// One wave per column.  W [H, H] and y are read in place: row n of W is the B operand's column n (K = the input index), a
+// One wave per column (d_rows: over the first min(*d_rows, T) rows only).  W [H, H] and y are read in place: row n of W is the B operand's column n (K = the input index), a
 // float4 per lane and k-group; H is a multiple of 4, so a float4 lies inside the row or behind it.
 __global__ __launch_bounds__(64) void selfattn_pool_kernel(const float* __restrict__ y, int T, int B, int H, const float* __restrict__ Wm,
                                                            const float* __restrict__ bW, const float* __restrict__ v,
                                                            const float* __restrict__ cb, float* __restrict__ out,
-                                                           float* __restrict__ wsave /* training: the weights [T, B]; or NULL */) {
+                                                           float* __restrict__ wsave /* training: the weights [T, B]; or NULL */,
+                                                           const int32_t* __restrict__ d_rows /* the row count on the device; or NULL */) {
     __shared__ float e[AT_MAX_T];
     const int lane = threadIdx.x, b = blockIdx.x;
+    // dsp_selfattn_pool_rows_batch: only the first *d_rows rows of the buffer exist for the softmax (one wave-uniform read; T,
+    // the buffer's row count, stays the bound of every loop below)
+    if (d_rows != nullptr) T = max(1, min(d_rows[0], T));
     const int ng = (H + 15) >> 4, nt = ng;
     const int r0 = 4 * (lane >> 4), c0 = lane & 15;
     const float c = cb[0];

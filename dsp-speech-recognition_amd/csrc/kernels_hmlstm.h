@@ -2,7 +2,8 @@
 // whole batch, fp32, as ONE persistent launch.
 //
 // Shape.  The recurrence is independent per utterance (batch column), so a workgroup owns a slice of HM_COLS = 16 columns,
-// runs all T steps for it and never waits on another workgroup: no grid barrier, no flag, every loop bounded by an argument.
+// runs all T steps for it (fewer when only h_2 at len - 1 is asked for, see the step loop) and never waits on another
+// workgroup: no grid barrier, no flag, every loop bounded by an argument.
 // h1 / h2 / x_t of the slice live in LDS (as the B operand of the matrix pipe), c and the owner's copy of h in registers,
 // z1 / z2 in LDS.  The gate products are v_mfma_f32_16x16x4_f32 (an exact fp32 FMA chain): gate rows as M, the 16 columns
 // as N, the hidden / input index as K.  Weights are streamed from L2 every step in a layout packed once at create
@@ -269,15 +270,25 @@ __global__ __launch_bounds__(HM_THREADS) void hmlstm_forward_kernel(const HmPara
     put_x();
     __syncthreads();
 
+    // When h_2 at len - 1 is the ONLY output asked for, nothing behind the longest column of the slice can reach it: the slice
+    // stops there (wave-uniform, at most T).  Any other output is defined over all T steps.
+    int steps = T;
+    if (!TAPE && P.len && P.last_h2 && !P.state_out && !P.h1 && !P.h2 && !P.z1 && !P.z2 && !P.zhat) {
+        steps = 1;
+        for (int c = 0; c < HM_COLS; ++c)
+            if (b0 + c < B) steps = max(steps, lens[c]);
+        steps = __builtin_amdgcn_readfirstlane(steps);
+    }
+
     float* tp = nullptr;                    // this slice's tape rows of step t
     if (TAPE) tp = P.tape + (int64_t)blockIdx.x * T * hm_tape_step(H1, H2);
-    for (int t = 0; t < T; ++t) {
-        if (t + 1 < T) load_x(t + 1);
+    for (int t = 0; t < steps; ++t) {
+        if (t + 1 < steps) load_x(t + 1);
         // ---- cell 1: bottom = x_t with z_bottom = 1, top = h2 of the previous step (hmrnn.py:146)
         const float zh1 = hm_cell<MAXS, TAPE>(P.c1, xbuf, h2buf, h1buf, c1, h1, z1s[col], 1.0f, P.a, w, lane, tp,
                                               TAPE ? tp + 80 * (H1 + H2) : nullptr);
         __syncthreads();                    // every wave has read xbuf, h1buf and z1s
-        if (t + 1 < T) put_x();
+        if (t + 1 < steps) put_x();
         hm_publish<MAXS>(h1, nt1, zh1, h1buf, z1s, w, lane, P.zhat ? P.zhat + ((int64_t)t * 2) * B + b : nullptr,
                          P.z1 ? P.z1 + (int64_t)b * T + t : nullptr, col_ok);
         __syncthreads();                    // h1buf / z1s hold step t

@@ -162,6 +162,9 @@ SIGNATURES = {
     'dsp_attn_workspace_bytes': (C.c_int, [c_vp, c_i32, c_i32, C.POINTER(c_i64)]),
     'dsp_attn_forward': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
     'dsp_selfattn_pool_batch': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'dsp_selfattn_pool_rows_batch': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'dsp_head_lengths_batch': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'dsp_head_pool_batch': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
     'dsp_attn_tape_bytes': (C.c_int, [c_vp, c_i32, c_i32, C.POINTER(c_i64)]),
     'dsp_attn_forward_train': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
     'dsp_attn_backward_bytes': (C.c_int, [c_vp, c_i32, c_i32, C.POINTER(c_i64), C.POINTER(c_i64)]),

@@ -23,6 +23,12 @@ gradient required, ``native_attn=True`` takes their native training paths (``_At
 csrc/kernels_attn_bwd.h): the forward saves a tape without any [B, T, T] tensor, the backward is four launches (one for the
 pooling) and the parameter gradients are GEMMs over the rows it leaves (``attn_param_grads``).  ``native_attn=None`` keeps the
 torch chains whenever a gradient is required, unless ``native_train_default`` is set.
+
+``device_len=True`` on a head's forward keeps the lengths on the device (a [B] int32 tensor, e.g. the ``len0`` a captured front
+end leaves there): the row counts come from ``dsp_head_lengths_batch``, the encoders run over all ``inp.shape[0]`` rows with the
+lengths read in place, and the two places that need max(len0) -- the pooling and ``_SelfAttn``'s softmax -- read it from device
+memory (``dsp_head_pool_batch``, ``dsp_selfattn_pool_rows_batch``; csrc/kernels_head.h).  Nothing reads device memory from the
+host, so the call can be captured in a HIP graph.  Forward only, every stage native.
 """
 import numpy as np
 import torch
@@ -36,6 +42,50 @@ def _lengths(len0):
 
 def _ptr(t):
     return None if t is None else t.data_ptr()      # an optional tensor: None is a NULL argument
+
+
+def _check_device_len(who, inp, len0, module):
+    """The conditions of ``device_len=True``: lengths as a [B] int32 tensor on ``inp``'s device, no gradient required."""
+    if not torch.is_tensor(inp) or not inp.is_cuda:
+        raise RuntimeError(f'{who}: device_len=True cannot run: the input is not on a GPU')
+    if not (torch.is_tensor(len0) and len0.dtype == torch.int32 and len0.dim() == 1 and len0.shape[0] == inp.shape[1]
+            and len0.device == inp.device):
+        raise TypeError(f"{who}: device_len=True needs len0 as a [B] int32 tensor on the input's device")
+    if torch.is_grad_enabled() and (inp.requires_grad or any(p.requires_grad for p in module.parameters())):
+        raise RuntimeError(f'{who}: device_len=True cannot run: a gradient is required (the device-length path is forward only)')
+
+
+def head_length_info(len0, T, hir):
+    """The row counts of a batch whose lengths are on the device (``dsp_head_lengths_batch``, one launch on the current
+    stream): len0 [B] int32 device tensor -> (len0c [B] = clamp(len0, 1, T), len1 [B] = ceil(len0c / hir), info [4] =
+    (max len0c, ceil(max len0c / hir), number of entries that had to be clamped, 0)), three int32 device tensors."""
+    from . import _native as nat
+    if not (torch.is_tensor(len0) and len0.is_cuda and len0.dtype == torch.int32 and len0.dim() == 1):
+        raise TypeError('head_length_info needs a [B] int32 device tensor')
+    dev, B = len0.device, len0.shape[0]
+    len0 = len0.contiguous()
+    with torch.cuda.device(dev):
+        len0c = torch.empty(B, dtype=torch.int32, device=dev)
+        len1 = torch.empty(B, dtype=torch.int32, device=dev)
+        info = torch.empty(4, dtype=torch.int32, device=dev)
+        nat.check(nat.load().dsp_head_lengths_batch(len0.data_ptr(), B, int(T), int(hir), len0c.data_ptr(), len1.data_ptr(),
+                                                    info.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return len0c, len1, info
+
+
+def _pool_native(y, d_len, d_rows, avg=True):
+    """``dsp_head_pool_batch`` over y [T, B, H] (fp32, on a GPU): -> [B, 2 H] = sum over t < len / len || max over the first
+    *d_rows rows (zero rows included, unread), or the max half [B, H] alone with ``avg=False``."""
+    from . import _native as nat
+    T, B, H = y.shape
+    dev = y.device
+    yc = y.detach().to(torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        feat = torch.empty(B, 2 * H if avg else H, dtype=torch.float32, device=dev)
+        nat.check(nat.load().dsp_head_pool_batch(yc.data_ptr(), T, B, H, d_len.data_ptr(), d_rows.data_ptr(), feat.data_ptr(),
+                                                 feat.stride(0), 0 if avg else -1, H if avg else 0,
+                                                 torch.cuda.current_stream(dev).cuda_stream))
+    return feat
 
 
 def _pack_state(hidden, H1, H2, B, **f32):
@@ -155,15 +205,20 @@ class _DynEnc(_NativeHandle, nn.Module):
         return d
 
     def _run_native(self, x, lens):
-        from . import _native as nat
-        B, H, dev = x.shape[1], self.hidden_size, x.device
+        B, dev = x.shape[1], x.device
         T = int(lens.max())
         assert lens.numel() == B and int(lens.min()) >= 1 and T <= x.shape[0], 'lengths do not fit the input'
+        with torch.cuda.device(dev):
+            return self._launch_native(x, T, lens.to(torch.int32).to(dev))
+
+    def _launch_native(self, x, T, d_len):
+        """The forward over the first ``T`` rows of x with the lengths ``d_len`` ([B] int32, in [1, T]) read on the device."""
+        from . import _native as nat
+        B, H, dev = x.shape[1], self.hidden_size, x.device
         x = x.detach().contiguous()
         with torch.cuda.device(dev):
             handle = self._native_handle(dev)
             lib = nat.load()
-            d_len = lens.to(torch.int32).to(dev)
             nbytes = nat.c_i64(0)
             nat.check(lib.dsp_bigru_workspace_bytes(handle, T, B, nat.C.byref(nbytes)))
             work = torch.empty(nbytes.value // 4, dtype=torch.float32, device=dev)
@@ -201,8 +256,17 @@ class _DynEnc(_NativeHandle, nn.Module):
         h = self.hidden_size
         return (y[:, :, :h] + y[:, :, h:])[:, unsort].contiguous(), hn[:, unsort].contiguous()
 
-    def run(self, x, lens, native=None):
-        """-> (y [max(lens), B, H], h_n [2 n_layers, B, H]), the reference's return value (layers.py:76)."""
+    def run(self, x, lens, native=None, device_len=False):
+        """-> (y [max(lens), B, H], h_n [2 n_layers, B, H]), the reference's return value (layers.py:76).
+        ``device_len=True``: ``lens`` is a [B] int32 tensor on x's device with entries in [1, x.shape[0]] and stays there; the
+        native forward runs over all x.shape[0] rows (y has that many, exact zero rows behind each end) and nothing is read
+        back.  Forward only: a required gradient, or anything else the native path cannot serve, raises."""
+        if device_len:
+            _check_device_len('_DynEnc', x, lens, self)
+            why = self.native_supported(x)
+            if why is not None:
+                raise RuntimeError(f'_DynEnc: the native path cannot run: {why}')
+            return self._launch_native(x, x.shape[0], lens.contiguous())
         lens = torch.as_tensor(_lengths(lens))
         if native is False:
             return self._run_torch(x, lens)
@@ -221,8 +285,8 @@ class _DynEnc(_NativeHandle, nn.Module):
             return self._run_native_train(x, lens) if needs_grad else self._run_native(x, lens)
         return self._run_torch(x, lens)
 
-    def forward(self, x, lens, native=None):
-        return self.run(x, lens, native)[0]
+    def forward(self, x, lens, native=None, device_len=False):
+        return self.run(x, lens, native, device_len)[0]
 
 
 def gru_param_grads(params, x, out, da, drop=None, need=None):
@@ -330,8 +394,14 @@ class RNNHead(nn.Module):
         self.enc = _DynEnc(feat_size, hidden, layers)
         self.out = nn.Linear(2 * hidden, classes)
 
-    def forward(self, inp, len0, native_enc=None):
-        """inp: [T, B, 39] (zero beyond each utterance's length), len0: lengths (numpy / list / tensor) -> [B, 20]."""
+    def forward(self, inp, len0, native_enc=None, device_len=False):
+        """inp: [T, B, 39] (zero beyond each utterance's length), len0: lengths (numpy / list / tensor) -> [B, 20].
+        ``device_len=True``: len0 is a [B] int32 tensor on inp's device and is never read from the host (module docstring)."""
+        if device_len:
+            _check_device_len('RNNHead', inp, len0, self)
+            d_len, _, info = head_length_info(len0, inp.shape[0], 1)
+            y = self.enc(inp, d_len, device_len=True)                           # [T, B, H], zeros behind each end
+            return self.out(_pool_native(y, d_len, info[0:1]))
         lens = torch.as_tensor(_lengths(len0))
         y = self.enc(inp, lens, native=native_enc)                          # [max(len0), B, H], zeros behind each end
         avg = y.sum(0) / lens.to(inp.device, inp.dtype).unsqueeze(1)        # rnn_clf.py:29-30
@@ -368,7 +438,26 @@ class HRNNHead(nn.Module):
         y = self.enc1(inp, len0, native=native_enc)[:, :, -self.hidden_size:]            # rnn_clf.py:58
         return self.enc2(y[0::self.hir], len1, native=native_enc), len1                  # rnn_clf.py:61-65
 
-    def forward(self, inp, len0, dropout=True, native_enc=None):
+    def _levels_device(self, inp, len0):
+        """``_levels`` with the lengths on the device: all ceil(T / hir) picked rows go into enc2 -> (y2, len1, info)."""
+        d_len, d_len1, info = head_length_info(len0, inp.shape[0], self.hir)
+        y = self.enc1(inp, d_len, device_len=True)[:, :, -self.hidden_size:]
+        return self.enc2(y[0::self.hir], d_len1, device_len=True), d_len1, info
+
+    def _forward_device(self, inp, len0, dropout, attn=None):
+        _check_device_len(type(self).__name__, inp, len0, self)
+        y2, d_len1, info = self._levels_device(inp, len0)
+        rows = info[1:2]                                                        # ceil(max(len0) / hir), on the device
+        if attn is None:
+            feat = _pool_native(y2, d_len1, rows)
+        else:
+            feat = torch.cat([attn(y2, native=True, d_rows=rows), _pool_native(y2, d_len1, rows, avg=False)], dim=1)
+        out = self.out(feat)
+        return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
+
+    def forward(self, inp, len0, dropout=True, native_enc=None, device_len=False):
+        if device_len:
+            return self._forward_device(inp, len0, dropout)
         y2, len1 = self._levels(inp, len0, native_enc)
         out, feat = _pool_head(y2, len1, self.out)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
@@ -476,16 +565,19 @@ class _SelfAttn(nn.Module):
             return 'sizes out of range: T in [1, 1024], H a multiple of 4 in [4, 256]'
         return None
 
-    def _run_native(self, y):
+    def _run_native(self, y, d_rows=None):
         from . import _native as nat
         T, B, H = y.shape
         dev = y.device
         yc = y.detach().contiguous()                                            # (a copy of a view is held until the call returns)
         with torch.cuda.device(dev):
             out = torch.empty(B, H, dtype=torch.float32, device=dev)
-            nat.check(nat.load().dsp_selfattn_pool_batch(yc.data_ptr(), T, B, H, self.attn.weight.data_ptr(), self.attn.bias.data_ptr(),
-                                                         self.v.weight.data_ptr(), self.v.bias.data_ptr(), out.data_ptr(),
-                                                         torch.cuda.current_stream(dev).cuda_stream))
+            params = (self.attn.weight.data_ptr(), self.attn.bias.data_ptr(), self.v.weight.data_ptr(), self.v.bias.data_ptr())
+            st = torch.cuda.current_stream(dev).cuda_stream
+            if d_rows is None:
+                nat.check(nat.load().dsp_selfattn_pool_batch(yc.data_ptr(), T, B, H, *params, out.data_ptr(), st))
+            else:
+                nat.check(nat.load().dsp_selfattn_pool_rows_batch(yc.data_ptr(), T, B, H, *params, out.data_ptr(), d_rows.data_ptr(), st))
         return out
 
     def _run_native_train(self, y):
@@ -496,7 +588,14 @@ class _SelfAttn(nn.Module):
         w = torch.softmax(self.v(torch.tanh(self.attn(y))).squeeze(2), 1)       # [B, T]
         return torch.bmm(w.unsqueeze(1), y).squeeze(1)
 
-    def forward(self, y, native=None):
+    def forward(self, y, native=None, d_rows=None):
+        """``d_rows``: a one-element int32 device tensor -- the softmax runs over the first min(*d_rows, T) rows of y only,
+        the count read on the device (``dsp_selfattn_pool_rows_batch``); native and forward only."""
+        if d_rows is not None:
+            why = self.native_supported(y)
+            if why is not None:
+                raise RuntimeError(f'_SelfAttn: the native path cannot run: {why}')
+            return self._run_native(y, d_rows)
         if native is False:
             return self._run_torch(y)
         needs_grad = _attn_needs_grad(y, self)
@@ -519,7 +618,9 @@ class HRNNAttHead(HRNNHead):
         super().__init__(feat_size)
         self.attn = _SelfAttn(200)
 
-    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None):
+    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False):
+        if device_len:
+            return self._forward_device(inp, len0, dropout, self.attn)
         y2, len1 = self._levels(inp, len0, native_enc)
         out, feat = _pool_head(y2, len1, self.out, self.attn, native_attn)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
@@ -824,7 +925,17 @@ class TransformerHead(nn.Module):
         self.out = nn.Linear(400, 20)
         self.hidden_size = 200
 
-    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None):
+    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False):
+        if device_len:
+            _check_device_len('TransformerHead', inp, len0, self)
+            d_len, d_len1, info = head_length_info(len0, inp.shape[0], self.hir)
+            attn_out = self.attn_enc(inp, native=True)
+            a = torch.nn.functional.dropout(attn_out, 0.5) if dropout else attn_out
+            y = self.rnn_enc_1(torch.cat([inp, a], 2), d_len, device_len=True)[:, :, -self.hidden_size:]
+            y2 = self.rnn_enc_2(y[0::self.hir], d_len1, device_len=True)
+            feat = _pool_native(y2, d_len1, info[1:2])
+            out = self.out(feat)
+            return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat, attn_out
         len0 = _lengths(len0)
         len1 = (len0 + self.hir - 1) // self.hir
         attn_out = self.attn_enc(inp, native=native_attn)
@@ -1038,7 +1149,10 @@ class HMLSTM(_NativeHandle, nn.Module):
             raise nat.DspError('HMLSTM: parameters must be contiguous')
         return super()._native_handle(dev)
 
-    def _run_native(self, x, hidden, lens, want_seq=True):
+    def _run_native(self, x, hidden, lens, want_seq=True, d_len=None, last_only=False):
+        """``d_len``: the lengths as a [B] int32 tensor on x's device, read in place (``lens`` is then ignored).
+        ``last_only``: ``last_h2`` is the one output asked for -- the kernel then stops every 16-column slice at its longest
+        length instead of running all T rows."""
         from . import _native as nat
         T, B, _ = x.shape
         H1, H2 = self.size_list
@@ -1048,20 +1162,22 @@ class HMLSTM(_NativeHandle, nn.Module):
             handle = self._native_handle(dev)
             f32 = dict(dtype=torch.float32, device=dev)
             state_in = None if hidden is None else _pack_state(hidden, H1, H2, B, **f32)
-            state_out = torch.empty((2 * H1 + 2 * H2 + 2) * B, **f32)
+            want_seq = want_seq and not last_only
+            state_out = None if last_only else torch.empty((2 * H1 + 2 * H2 + 2) * B, **f32)
             h_1 = torch.empty(B, T, H1, **f32) if want_seq else None
             h_2 = torch.empty(B, T, H2, **f32) if want_seq else None
             z_1 = torch.empty(B, T, dtype=torch.uint8, device=dev) if want_seq else None
             z_2 = torch.empty(B, T, dtype=torch.uint8, device=dev) if want_seq else None
-            z_hat = torch.empty(T, 2, B, **f32)
-            d_len = last = None
-            if lens is not None:
+            z_hat = None if last_only else torch.empty(T, 2, B, **f32)
+            last = None
+            if d_len is None and lens is not None:
                 d_len = torch.as_tensor(_lengths(lens), dtype=torch.int32).to(dev)
+            if d_len is not None:
                 last = torch.empty(B, H2, **f32)
             nat.check(nat.load().dsp_hmlstm_forward(handle, x.data_ptr(), T, B, float(self.a), _ptr(d_len), _ptr(state_in),
-                                                    state_out.data_ptr(), _ptr(h_1), _ptr(h_2), _ptr(z_1), _ptr(z_2), z_hat.data_ptr(),
+                                                    _ptr(state_out), _ptr(h_1), _ptr(h_2), _ptr(z_1), _ptr(z_2), _ptr(z_hat),
                                                     _ptr(last), torch.cuda.current_stream(dev).cuda_stream))
-        hid = _split_state(state_out, H1, H2, B)
+        hid = None if last_only else _split_state(state_out, H1, H2, B)
         zf = lambda z: None if z is None else z.to(torch.float32).unsqueeze(2)
         return HMLSTMResult(h_1=h_1, h_2=h_2, z_1=zf(z_1), z_2=zf(z_2), hidden=hid, z_hat=z_hat, last_h2=last)
 
@@ -1107,8 +1223,20 @@ class HMLSTM(_NativeHandle, nn.Module):
         return HMLSTMResult(h_1=torch.stack(hs1, dim=1), h_2=h_2, z_1=torch.stack(zs1, dim=1), z_2=torch.stack(zs2, dim=1),
                             hidden=(h1, c1, z1, h2, c2, z2), z_hat=torch.stack(zh).detach(), last_h2=last)
 
-    def run(self, x, hidden=None, lens=None, native=None):
-        """Everything the forward pass yields, as an HMLSTMResult.  x: [T, B, input_size]."""
+    def run(self, x, hidden=None, lens=None, native=None, device_len=False):
+        """Everything the forward pass yields, as an HMLSTMResult.  x: [T, B, input_size].
+        ``device_len=True``: ``lens`` is a [B] int32 tensor on x's device with entries in [1, T] and stays there; the native
+        forward yields ``last_h2`` alone (every other field is None), which lets each 16-column slice stop at its longest
+        length instead of running all T rows.
+        Forward only: a required gradient, or anything else the native path cannot serve, raises."""
+        if device_len:
+            _check_device_len('HMLSTM', x, lens, self)
+            if torch.is_grad_enabled() and hidden is not None and any(v.requires_grad for v in hidden):
+                raise RuntimeError('HMLSTM: device_len=True cannot run: the initial hidden requires a gradient')
+            why = self.native_supported(x)
+            if why is not None:
+                raise RuntimeError(f'HMLSTM: the native path cannot run: {why}')
+            return self._run_native(x, hidden, None, d_len=lens.contiguous(), last_only=True)
         hidden_grad = torch.is_grad_enabled() and hidden is not None and any(v.requires_grad for v in hidden)
         needs_grad = hidden_grad or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))
         if needs_grad and native is None and not self.native_train_default:
@@ -1143,7 +1271,17 @@ class HMRNNHead(nn.Module):
         self.enc2 = HMLSTM(1.0, 200, [200, 200])
         self.out = nn.Linear(600, 20)
 
-    def forward(self, inp, len0, dropout=True, native=None, native_enc=None):
+    def forward(self, inp, len0, dropout=True, native=None, native_enc=None, device_len=False):
+        if device_len:
+            _check_device_len('HMRNNHead', inp, len0, self)
+            d_len, _, info = head_length_info(len0, inp.shape[0], 1)
+            enc = self.enc1(inp, d_len, device_len=True)                                                 # [T, B, 200], zeros behind each end
+            if dropout:
+                enc = torch.nn.functional.dropout(enc, 0.2)
+            last = self.enc2.run(enc, None, lens=d_len, device_len=True).last_h2
+            feat = torch.cat([_pool_native(enc, d_len, info[0:1]), last], dim=1)
+            out = self.out(feat)
+            return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
         len0 = _lengths(len0)
         enc = self.enc1(inp, len0, native=native_enc)                                                    # [max(len0), B, 200]
         if dropout:

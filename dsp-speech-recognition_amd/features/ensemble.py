@@ -9,6 +9,9 @@ decides instead (pitch_model.py:54-61).
 * ``EnsembleBatch`` runs the whole path for a batch of raw clips -- endpointing and the classifier's features
   (``ModelFeatureBatch``), the classifier head, the pre-emphasised trimmed copy (``dsp_trim_preemph_batch``), the pitch
   features (``pitch_features_device``) and the gate -- on torch's current stream; no clip, logit or feature visits the host.
+  ``run()`` downloads the lengths and the endpoints between the front end and the head (one synchronisation);
+  ``run(sync_free=True)`` leaves them on the device (``device_len=True`` on the head), and ``capture()`` records that whole
+  chain into ONE HIP graph whose ``replay()`` serves new clips written into the captured buffer.
 
 Training stays where it was: fit the scaler and the SVM with scikit-learn, then ``PitchSVM.from_sklearn(scaler, clf)``.
 """
@@ -241,6 +244,52 @@ def ensemble_decide(logits, rules, feat=None, valid=None, stream=None):
     return pred, prob, used, dec
 
 
+class _TensorBuffer:
+    """A torch tensor behind the interface of a ``nat.DeviceBuffer`` (``ptr``, ``nbytes``, ``download``): in place of a layout's
+    segment table, so that torch -- inside a captured graph too -- can copy what the endpoint kernels write there."""
+
+    def __init__(self, tensor):
+        self.tensor, self.ptr, self.nbytes, self.wave = tensor, tensor.data_ptr(), tensor.numel() * tensor.element_size(), None
+
+    def download(self, shape, dtype, stream=None):
+        out = np.empty(shape, dtype=dtype)
+        assert out.nbytes <= self.nbytes, (out.nbytes, self.nbytes)
+        nat.check(nat.load().dsp_memcpy_d2h(out.ctypes.data, self.ptr, out.nbytes, stream))
+        return out
+
+    def free(self):
+        self.tensor = self.ptr = None
+
+
+def _segments_tensor(lay, dev):
+    """The segment table [B, 2] int64 of a pipeline layout THIS module owns, as a torch tensor (swapped in on first use; no
+    launch of the layout is in flight then: a fresh layout has none, a cached one is swapped before its first launch)."""
+    import torch
+    if not isinstance(lay.d_seg, _TensorBuffer):
+        lay.d_seg = _TensorBuffer(torch.zeros(2 * lay.n_utt, dtype=torch.int64, device=dev))
+    return lay.d_seg.tensor.view(lay.n_utt, 2)
+
+
+def _logits_of(out):
+    import torch
+    logits = out[0] if isinstance(out, (tuple, list)) else out
+    return logits.detach().to(torch.float32)
+
+
+class _EnsembleGraph:
+    """What ``EnsembleBatch.capture`` / ``MixedRateEnsembleBatch.capture`` return.  ``replay()`` re-runs the captured chain on
+    whatever ``waves`` holds now and returns the namespace of ``run()`` with every field a device tensor (``len0`` int32,
+    ``endpoints`` int64 [B, 2], and ``n_clamped``: how many lengths the head had to clamp into [1, 200]), valid after the
+    current stream's work; nothing is synchronised.  The object owns every buffer the graph's kernels touch."""
+
+    def __init__(self, graph, waves, out, hold):
+        self.graph, self.waves, self.out, self._hold = graph, waves, out, hold
+
+    def replay(self):
+        self.graph.replay()
+        return self.out
+
+
 class EnsembleBatch:
     """ensemble.EnsembleModel.test's loop body (ensemble.py:48-53) for a batch of raw clips, device-resident.
 
@@ -266,11 +315,15 @@ class EnsembleBatch:
         self._layouts[key] = lay
         return lay
 
-    def run(self, waves, sample_offsets, **head_kwargs):
+    def run(self, waves, sample_offsets, sync_free=False, **head_kwargs):
         """``waves``: concatenated clips, a 1-D host array (int16 or float) or device tensor (int16 / float32);
         ``sample_offsets`` [B + 1].  Returns a namespace of device tensors: pred int32 [B] (the ensemble's labels), prob fp32
         [B, C], used int32 [B], decision fp64 [B] (see ``ensemble_decide``), logits, feat fp64 [B, 5] and valid int32 [B]
-        (the pitch features), endpoints int64 [B, 2] (host array, samples)."""
+        (the pitch features), endpoints int64 [B, 2] (host array, samples), len0 [B] (host array).  This call downloads len0
+        and the endpoints between the front end and the head: one host synchronisation per batch.
+        ``sync_free=True``: nothing is synchronised -- the head is called with ``device_len=True`` (so it must be one of
+        features/classifier.py's), ``len0`` (int32) and ``endpoints`` are device tensors, and ``n_clamped`` (int32 [1]) counts
+        the lengths the head had to clamp."""
         import torch
         from .pitch import N_AUX, pitch_features_device
         nat.require_device()
@@ -287,10 +340,12 @@ class EnsembleBatch:
         dev = clips.device
         dtype = _wave_dtype_of(clips)
         lay = self._layout(so)
+        if sync_free:
+            _segments_tensor(lay, dev)
+            m0 = torch.empty((max(lay.frames_bound, 1), self.features.pipe.features.C), dtype=torch.float32, device=dev)
+            return self._chain(clips, lay, m0, None, head_kwargs)
         inp, len0, endpoints = self.features.run(clips, layout=lay)
-        out = self.head(inp, len0, **head_kwargs)
-        logits = out[0] if isinstance(out, (tuple, list)) else out
-        logits = logits.detach().to(torch.float32)
+        logits = _logits_of(self.head(inp, len0, **head_kwargs))
         st = _torch_stream(dev)
         trimmed = torch.empty(max(lay.total_samples, 1), dtype=torch.float32, device=dev)
         nat.check(lib.dsp_trim_preemph_batch(clips.data_ptr(), dtype, lay.vad.p_sample, lay.d_seg.ptr, lay.d_dst_off.ptr, B,
@@ -306,6 +361,71 @@ class EnsembleBatch:
         return types.SimpleNamespace(pred=pred, prob=prob, used=used, decision=dec, logits=logits, feat=feat, valid=valid,
                                      endpoints=endpoints, inp=inp, len0=len0, _clips=clips, _trimmed=trimmed)
 
+    def _chain(self, clips, lay, m0, arena, head_kwargs):
+        """The whole path as launches on torch's current stream, nothing synchronised, no device memory read from the host:
+        front end (``ModelFeatureBatch.enqueue``), head with ``device_len=True``, pre-emphasised trim, pitch features, gate.
+        ``lay``: a layout of this object whose segment table is a torch tensor; ``m0``: the front end's [frames_bound, C]
+        scratch; ``arena``: the pitch chain's buffers (None: library scratch, for an eager call)."""
+        import torch
+        from .classifier import head_length_info
+        from .pitch import N_AUX, pitch_features_device
+        lib = nat.load()
+        dev, B = clips.device, lay.n_utt
+        stream = torch.cuda.current_stream(dev)
+        st = _stream_ptr(stream)
+        mfb = self.features
+        inp = torch.empty((mfb.max_len, B, 3 * mfb.pipe.features.C), dtype=torch.float32, device=dev)
+        len0 = torch.empty(B, dtype=torch.int32, device=dev)
+        mfb.enqueue(clips.data_ptr(), _wave_dtype_of(clips), lay, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(), stream)
+        logits = _logits_of(self.head(inp, len0, device_len=True, **head_kwargs))
+        n_clamped = head_length_info(len0, mfb.max_len, 1)[2][2:3]
+        trimmed = torch.empty(max(lay.total_samples, 1), dtype=torch.float32, device=dev)
+        nat.check(lib.dsp_trim_preemph_batch(clips.data_ptr(), _wave_dtype_of(clips), lay.vad.p_sample, lay.d_seg.ptr, lay.d_dst_off.ptr,
+                                             B, self.coeff, trimmed.data_ptr(), st))
+        feat = torch.empty((B, 5), dtype=torch.float64, device=dev)
+        aux = torch.empty((B, N_AUX), dtype=torch.int32, device=dev)
+        pitch_features_device(trimmed.data_ptr(), lay.d_dst_off.ptr, B, lay.total_samples, self.rate, stream=st,
+                              d_feat=feat.data_ptr(), d_aux=aux.data_ptr(), arena=arena)
+        valid = aux[:, N_AUX - 1]
+        pred, prob, used, dec = ensemble_decide(logits, self.rules, feat, valid, stream=st)
+        endpoints = _segments_tensor(lay, dev).clone()
+        return types.SimpleNamespace(pred=pred, prob=prob, used=used, decision=dec, logits=logits, feat=feat, valid=valid,
+                                     endpoints=endpoints, inp=inp, len0=len0, n_clamped=n_clamped, _clips=clips, _trimmed=trimmed)
+
+    def capture(self, waves, sample_offsets, **head_kwargs):
+        """ONE HIP graph of the whole path over device-resident ``waves`` (a contiguous tensor, int16 / float32):
+        ``g = eb.capture(waves, so, dropout=False)``; write new clips of the same lengths into ``waves`` and call
+        ``g.replay()`` -> the namespace of ``run(sync_free=True)``.  One eager call runs first (it builds the native handles and
+        the layout's index tables and fills the graph's own arena).  The graph object owns every buffer its kernels touch --
+        the layout, the front end's scratch, the pitch chain's buffers and FIR taps -- so no later call of the library can
+        free or overwrite what a replay reads.  The graph reads ``waves`` at its address: a non-contiguous view raises
+        ValueError; the head must accept ``device_len=True``."""
+        import torch
+        if not _is_device_tensor(waves):
+            raise TypeError('capture needs a device tensor')
+        if not waves.is_contiguous():
+            raise ValueError('capture needs a contiguous waves tensor: the graph reads it in place on every replay')
+        nat.require_device()
+        so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
+        dev = waves.device
+        clips = waves.reshape(-1)                          # a view: the same memory
+        _wave_dtype_of(clips)                              # TypeError for anything but int16 / float32
+        lay = self.features.pipe.prepare(so, 0)            # the graph's own: nothing else launches on its tables
+        _segments_tensor(lay, dev)
+        m0 = torch.empty((max(lay.frames_bound, 1), self.features.pipe.features.C), dtype=torch.float32, device=dev)
+        arena = {}
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.no_grad():
+            with torch.cuda.stream(side):
+                warm = self._chain(clips, lay, m0, arena, head_kwargs)
+            side.synchronize()
+            del warm
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                out = self._chain(clips, lay, m0, arena, head_kwargs)
+        return _EnsembleGraph(graph, waves, out, [lay, m0, arena, clips, list(self.rules)])
+
 
 
 class MixedRateEnsembleBatch:
@@ -319,19 +439,48 @@ class MixedRateEnsembleBatch:
         self.head, self.rules, self.coeff = head, list(rules), float(coeff)
         self.features = MixedRateFeatureBatch(frame=frame, step=step)
 
-    def run(self, waves, sample_offsets=None, rates=None, **head_kwargs):
+    def run(self, waves, sample_offsets=None, rates=None, sync_free=False, **head_kwargs):
         """``waves`` / ``sample_offsets`` / ``rates`` as MixedRateFeatureBatch.run.  Returns the namespace of EnsembleBatch.run,
-        every row in batch order."""
+        every row in batch order; ``sync_free=True`` as there (device input: no synchronisation once the plan of the batch
+        shape exists)."""
+        if sync_free:
+            import torch
+            mr = self.features
+            clips, so, r = mr._inputs(waves, sample_offsets, rates)
+            on_device = _is_device_tensor(clips)
+            dev = clips.device if on_device else torch.device('cuda', nat.current_device())
+            plan = mr._plan(so, r, dev, on_device)       # this object's: its segment tables become torch's before the launches
+            for g in plan.groups:
+                _segments_tensor(g.lay, dev)
+            return self._tail(mr._launch(waves, sample_offsets, rates, plan=plan), None, None, head_kwargs, None)
+        ctx = self.features._launch(waves, sample_offsets, rates)
+        len0, endpoints = self.features._finish(ctx)
+        return self._tail(ctx, len0, endpoints, head_kwargs, None)
+
+    def _tail(self, ctx, len0, endpoints, head_kwargs, arenas):
+        """Everything behind the front end's launches.  ``len0`` / ``endpoints`` None: they stay on the device (the head is
+        called with ``device_len=True``, the endpoints are copied from the groups' segment tables by torch); ``arenas``: one
+        dict per rate group for the pitch chain's buffers, or None for library scratch."""
         import torch
         from .pitch import N_AUX, pitch_features_device
         lib = nat.load()
-        ctx = self.features._launch(waves, sample_offsets, rates)
         clips = ctx.group_waves                   # one contiguous device buffer per rate, held until the call returns
-        len0, endpoints = self.features._finish(ctx)
         inp, dev, st, B = ctx.inp, ctx.dev, ctx.st, ctx.plan.B
-        out = self.head(inp, len0, **head_kwargs)
-        logits = out[0] if isinstance(out, (tuple, list)) else out
-        logits = logits.detach().to(torch.float32)
+        n_clamped = None
+        if len0 is None:
+            from .classifier import head_length_info
+            len0 = ctx.len0
+            logits = _logits_of(self.head(inp, len0, device_len=True, **head_kwargs))
+            n_clamped = head_length_info(len0, inp.shape[0], 1)[2][2:3]
+            endpoints = torch.empty((B, 2), dtype=torch.int64, device=dev)
+            for g in ctx.plan.groups:
+                seg = _segments_tensor(g.lay, dev)
+                if g.d_index is None:
+                    endpoints.copy_(seg)
+                else:
+                    endpoints.index_copy_(0, g.d_index.long(), seg)
+        else:
+            logits = _logits_of(self.head(inp, len0, **head_kwargs))
         feat = torch.empty((B, 5), dtype=torch.float64, device=dev)
         aux = torch.empty((B, N_AUX), dtype=torch.int32, device=dev)
         trimmed = []
@@ -344,7 +493,8 @@ class MixedRateEnsembleBatch:
             feat_g = feat if one else torch.empty((n, 5), dtype=torch.float64, device=dev)
             aux_g = aux if one else torch.empty((n, N_AUX), dtype=torch.int32, device=dev)
             pitch_features_device(trim.data_ptr(), lay.d_dst_off.ptr, n, lay.total_samples, g.rate, stream=st,
-                                  d_feat=feat_g.data_ptr(), d_aux=aux_g.data_ptr())
+                                  d_feat=feat_g.data_ptr(), d_aux=aux_g.data_ptr(),
+                                  arena=None if arenas is None else arenas[len(trimmed)])
             if not one:                           # five doubles and nine ints per clip
                 pos = g.d_index.long()
                 feat.index_copy_(0, pos, feat_g)
@@ -352,5 +502,40 @@ class MixedRateEnsembleBatch:
             trimmed.append(trim)
         valid = aux[:, N_AUX - 1]
         pred, prob, used, dec = ensemble_decide(logits, self.rules, feat, valid, stream=st)
-        return types.SimpleNamespace(pred=pred, prob=prob, used=used, decision=dec, logits=logits, feat=feat, valid=valid,
-                                     endpoints=endpoints, inp=inp, len0=len0, _clips=clips, _trimmed=trimmed)
+        ns = types.SimpleNamespace(pred=pred, prob=prob, used=used, decision=dec, logits=logits, feat=feat, valid=valid,
+                                   endpoints=endpoints, inp=inp, len0=len0, _clips=clips, _trimmed=trimmed)
+        if n_clamped is not None:
+            ns.n_clamped, ns._hold = n_clamped, ctx.hold          # (torch tensors: released in stream order)
+        return ns
+
+    def capture(self, waves, sample_offsets, rates, **head_kwargs):
+        """``EnsembleBatch.capture`` for a mixed-rate batch: ONE HIP graph of the front end's sub-pipelines (queued one after
+        the other: a chain, no forked branches), the head with ``device_len=True``, and per rate group the trim and the pitch
+        features, then the gate.  ``waves``: a contiguous 1-D device tensor (a non-contiguous one raises ValueError);
+        ``replay()`` -> the namespace of ``run(sync_free=True)``, rows in batch order.  The graph object owns the plan, every
+        group's layout and pitch arena, and the temporaries of the launches.  (The optional ``use_pitch`` / ``use_timefeat``
+        streams are not part of the capture.)"""
+        import torch
+        from .model_glue import _MixedPlan
+        if not _is_device_tensor(waves):
+            raise TypeError('capture needs a device tensor')
+        if not waves.is_contiguous():
+            raise ValueError('capture needs a contiguous waves tensor: the graph reads it in place on every replay')
+        mr = self.features
+        _, so, rates = mr._inputs(waves, sample_offsets, rates)
+        dev = waves.device
+        plan = _MixedPlan(mr, so, rates, dev, True)            # the graph's own: nothing else writes its tables
+        for g in plan.groups:
+            _segments_tensor(g.lay, dev)
+        arenas = [{} for _ in plan.groups]
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.no_grad():
+            with torch.cuda.stream(side):
+                warm = self._tail(mr._launch(waves, so, rates, plan=plan), None, None, head_kwargs, arenas)
+            side.synchronize()
+            del warm
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                out = self._tail(mr._launch(waves, so, rates, plan=plan), None, None, head_kwargs, arenas)
+        return _EnsembleGraph(graph, waves, out, [plan, arenas, list(self.rules)])

@@ -65,14 +65,32 @@ def center_clip(frame, binary=True):
     return np.where(up, frame - med, np.where(dn, frame + med, 0.0))
 
 
-def _device_taps(L, rate, high_freq=900):
+def _device_taps(L, rate, high_freq=900, arena=None):
+    """The FIR taps on the device: from the module's cache, or -- with an ``arena`` -- a copy the arena owns."""
     key = (nat.current_device(), int(L), int(rate), int(high_freq))
-    buf = _taps_cache.get(key)
+    cache = _taps_cache if arena is None else arena
+    key = key if arena is None else ('taps',) + key
+    buf = cache.get(key)
     if buf is None:
         h = bandpass_taps(L, rate, 50, high_freq, 'hamming')
         arr = np.stack([h.real, h.imag], axis=1).astype(np.float32)
         buf = nat.DeviceBuffer(arr.nbytes).upload(arr)
-        _taps_cache[key] = buf
+        cache[key] = buf
+    return buf
+
+
+def _slot(arena, name, nbytes):
+    """A named device buffer of ``nbytes``: this thread's library scratch slot -- which a later, larger call frees and
+    replaces, so a pointer into it must not outlive the call -- or, with an ``arena`` (a dict its caller owns, e.g. a captured
+    graph), a buffer of the arena: allocated on first use (an eager call) and never replaced; a later request that does not
+    fit is an error, not a reallocation."""
+    if arena is None:
+        return nat.SCRATCH.get(name, nbytes)
+    buf = arena.get(name)
+    if buf is None:
+        buf = arena[name] = nat.DeviceBuffer(max(int(nbytes), 4))
+    elif buf.nbytes < nbytes:
+        raise ValueError(f'arena buffer {name!r} holds {buf.nbytes} bytes, {nbytes} are needed: an arena serves one batch shape')
     return buf
 
 
@@ -154,17 +172,17 @@ def pitch_tracks_batch(sig10k, sample_offsets, L, S, rate=10000):
     return d_pitch.download((int(fo[-1]),), np.float64), fo
 
 
-def _to_10k_on_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, L, S, stream):
+def _to_10k_on_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, L, S, stream, arena=None):
     """preprocess.downsampling to 10 kHz for clips on the device (dsp_resample_layout_batch + dsp_decimate_batch) and the
     frame offsets of the result at (L, S) -> (p_x, p_so, d_fo): signal and sample offsets as pointers, frame offsets as
-    a scratch buffer."""
+    a scratch buffer (``arena``: a buffer of the caller's arena instead, see ``_slot``)."""
     lib = nat.load()
-    d_fo = nat.SCRATCH.get('pitch_fo10', (n_utt + 1) * 8)
+    d_fo = _slot(arena, 'pitch_fo10', (n_utt + 1) * 8)
     if rate <= 10000:           # downsampling keeps every sample when the clip is at 10 kHz or below (preprocess.py:21-28)
         nat.check(lib.dsp_resample_layout_batch(d_src_off, n_utt, int(rate), 0, int(L), int(S), None, d_fo.ptr, stream))
         return d_clips, d_src_off, d_fo
-    d_so10 = nat.SCRATCH.get('pitch_so10', (n_utt + 1) * 8)
-    d_x10 = nat.SCRATCH.get('pitch_x10', max(4, int(n_samples_bound) * 4))
+    d_so10 = _slot(arena, 'pitch_so10', (n_utt + 1) * 8)
+    d_x10 = _slot(arena, 'pitch_x10', max(4, int(n_samples_bound) * 4))
     nat.check(lib.dsp_resample_layout_batch(d_src_off, n_utt, int(rate), 10000, int(L), int(S), d_so10.ptr, d_fo.ptr, stream))
     nat.check(lib.dsp_decimate_batch(d_clips, d_src_off, d_so10.ptr, n_utt, int(n_samples_bound), int(rate), 10000, d_x10.ptr, stream))
     return d_x10.ptr, d_so10.ptr, d_fo
@@ -211,26 +229,27 @@ def _check(rc):
 
 
 def _cepstrum_chain(p_x, p_so, p_fo, n_utt, frames_bound, L, S, stream=None, clip=True, want_scores=False, flags=3,
-                    tail=True, d_feat=None, d_aux=None):
-    """The three launches behind the 10 kHz signal, on library scratch buffers (nothing is allocated once they exist,
-    so the chain can be captured in a graph after one eager call).  ``d_feat`` / ``d_aux``: the caller's own device
-    memory ([n_utt, 5] fp64, [n_utt, 9] int32, raw pointers) for the two results instead of scratch."""
+                    tail=True, d_feat=None, d_aux=None, arena=None):
+    """The three launches behind the 10 kHz signal, on library scratch buffers (nothing is allocated once they exist).
+    ``d_feat`` / ``d_aux``: the caller's own device memory ([n_utt, 5] fp64, [n_utt, 9] int32, raw pointers) for the two
+    results instead of scratch.  ``arena``: a dict the caller owns -- every buffer of the chain, the FIR taps included, is
+    then the arena's (``_slot``): what a captured graph needs, since a scratch slot may be freed by any later, larger call."""
     lib = nat.load()
     frames_bound = max(int(frames_bound), 1)
     out = types.SimpleNamespace(scores=None, feat=None, aux=None, seg=None)
-    out.rows = nat.SCRATCH.get('cep_rows', frames_bound * int(L) * 4)
-    out.amp = nat.SCRATCH.get('cep_amp', frames_bound * 8)
-    out.pitch = nat.SCRATCH.get('cep_pitch', frames_bound * 8)
+    out.rows = _slot(arena, 'cep_rows', frames_bound * int(L) * 4)
+    out.amp = _slot(arena, 'cep_amp', frames_bound * 8)
+    out.pitch = _slot(arena, 'cep_pitch', frames_bound * 8)
     if want_scores:
-        out.scores = nat.SCRATCH.get('cep_scores', frames_bound * (CEP_MAX - CEP_MIN) * 4)
+        out.scores = _slot(arena, 'cep_scores', frames_bound * (CEP_MAX - CEP_MIN) * 4)
     _check(lib.dsp_pitch_cepstrum_batch(p_x, p_so, p_fo, n_utt, frames_bound, 0, int(L), int(S),
-                                        _device_taps(L, 10000, 1000).ptr, 1 if clip else 0, out.rows.ptr, out.amp.ptr, stream))
+                                        _device_taps(L, 10000, 1000, arena).ptr, 1 if clip else 0, out.rows.ptr, out.amp.ptr, stream))
     _check(lib.dsp_pitch_cepstrum_track_batch(out.rows.ptr, 0, p_fo, n_utt, int(L), int(flags), out.pitch.ptr,
                                               out.scores.ptr if want_scores else None, stream))
     if tail:
-        out.seg = nat.SCRATCH.get('cep_seg', frames_bound * 8)
-        out.feat = nat.SCRATCH.get('cep_feat', n_utt * 5 * 8) if d_feat is None else types.SimpleNamespace(ptr=int(d_feat))
-        out.aux = nat.SCRATCH.get('cep_aux', n_utt * N_AUX * 4) if d_aux is None else types.SimpleNamespace(ptr=int(d_aux))
+        out.seg = _slot(arena, 'cep_seg', frames_bound * 8)
+        out.feat = _slot(arena, 'cep_feat', n_utt * 5 * 8) if d_feat is None else types.SimpleNamespace(ptr=int(d_feat))
+        out.aux = _slot(arena, 'cep_aux', n_utt * N_AUX * 4) if d_aux is None else types.SimpleNamespace(ptr=int(d_aux))
         _check(lib.dsp_pitch_feature_batch(out.pitch.ptr, out.amp.ptr, p_fo, n_utt, out.seg.ptr, out.feat.ptr, out.aux.ptr, stream))
     return out
 
@@ -359,18 +378,21 @@ def peakshift(seq1, seq2):
     return np.median(seq2) - np.median(seq1)
 
 
-def pitch_features_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, stream=None, L=512, S=100, d_feat=None, d_aux=None):
+def pitch_features_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, stream=None, L=512, S=100, d_feat=None, d_aux=None,
+                          arena=None):
     """pitch.pitch_feature for clips that are already on the device (fp32, concatenated, `rate` Hz): decimation to 10 kHz,
     then the three launches of the cepstral path; nothing leaves the device.  `stream` is None, a raw handle or a torch
     stream.  Returns library scratch buffers as attributes: feat [B, 5] fp64, aux [B, 9] int32 (p, p_bias, start1,
     end1, start2, end2, len1, len2, valid), pitch and seg [one per frame] fp64, frame_off [B + 1] int64.  With ``d_feat`` /
-    ``d_aux`` (raw device pointers) those two results go to the caller's memory, which the next call does not overwrite."""
+    ``d_aux`` (raw device pointers) those two results go to the caller's memory, which the next call does not overwrite.
+    With ``arena`` (a dict the caller owns and keeps alive, one per batch shape) every other buffer and the FIR taps are the
+    arena's instead of library scratch: after one eager call that fills it, the launches can be captured in a graph."""
     stream = _stream_ptr(stream)
-    p_x, p_so, d_fo = _to_10k_on_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, L, S, stream)
+    p_x, p_so, d_fo = _to_10k_on_device(d_clips, d_src_off, n_utt, n_samples_bound, rate, L, S, stream, arena)
     # a clip of n samples keeps at most n * 10000 / rate + 2 of them and has at most 2 + kept / S frames
     kept_bound = int(n_samples_bound) if rate <= 10000 else int(n_samples_bound) * 10000 // int(rate) + 2 * n_utt
     frames_bound = kept_bound // int(S) + 2 * n_utt + 1
-    out = _cepstrum_chain(p_x, p_so, d_fo.ptr, n_utt, frames_bound, L, S, stream=stream, d_feat=d_feat, d_aux=d_aux)
+    out = _cepstrum_chain(p_x, p_so, d_fo.ptr, n_utt, frames_bound, L, S, stream=stream, d_feat=d_feat, d_aux=d_aux, arena=arena)
     out.frame_off = d_fo
     return out
 

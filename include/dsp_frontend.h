@@ -497,8 +497,9 @@ int dsp_hmlstm_destroy(dsp_hmlstm* h);
  *   d_z1, d_z2 [B, T] uint8            the boundary bits, hmrnn.py:150-151
  *   d_zhat [T, 2, B] fp32              hard_sigm in front of the threshold (cell 1, cell 2), hmrnn.py:90
  *   d_last_h2 [B, H2]                  h_2[b, len[b] - 1], rnn_clf.py:140-143
- * All T steps are run for every column.  One launch on `stream`, no workspace, no allocation: the call can be captured
- * into a HIP graph.
+ * All T steps are run for every column -- except when d_last_h2 (with d_len) is the ONLY output: nothing behind a column's
+ * length reaches it, so each 16-column slice then stops at the longest length among its columns (same bits in d_last_h2).
+ * One launch on `stream`, no workspace, no allocation: the call can be captured into a HIP graph.
  */
 int dsp_hmlstm_forward(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
                        const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1,
@@ -870,6 +871,14 @@ int dsp_attn_backward(const dsp_attn* h, int32_t T, int32_t B, const void* d_tap
 int dsp_selfattn_pool_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
                             const float* d_c, float* d_out, void* stream);
 /*
+ * dsp_selfattn_pool_batch over the first rows = clamp(*d_rows, 1, T) rows of d_y only, the count read from device memory (one
+ * wave-uniform read per workgroup): the softmax of a batch whose padded row count ceil(max(len0) / hir) only the device
+ * knows (dsp_head_lengths_batch: d_info + 1).  T stays the row count of the buffer and the bound of every loop; d_out is bit for
+ * bit dsp_selfattn_pool_batch's on d_y[:rows].  d_rows NULL is DSP_EINVAL; every other check as dsp_selfattn_pool_batch.
+ */
+int dsp_selfattn_pool_rows_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
+                                 const float* d_c, float* d_out, const int32_t* d_rows, void* stream);
+/*
  * dsp_selfattn_pool_batch that also writes the weights w [T, B] to d_w; d_out is bit for bit dsp_selfattn_pool_batch's.
  */
 int dsp_selfattn_pool_train_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
@@ -886,6 +895,35 @@ int dsp_selfattn_pool_train_batch(const float* d_y, int32_t T, int32_t B, int32_
 int dsp_selfattn_pool_backward_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
                                      const float* d_w, const float* d_gout, float* d_gy, float* d_gpre, float* d_ge, float* d_gvpart,
                                      void* stream);
+
+/* ---- the classifier heads with the lengths on the device (csrc/kernels_head.h) ----
+ *
+ * The row counts of a batch, one launch of one workgroup: d_len0 [B] int32 (e.g. the len0 dsp_model_finalize_*_batch wrote) ->
+ *   d_len0c[b] = clamp(d_len0[b], 1, T)          (d_len0c may be d_len0 itself)
+ *   d_len1[b]  = ceil(d_len0c[b] / hir)          rnn_clf.py:52
+ *   d_info[0]  = max_b d_len0c[b]                the rows pad_packed_sequence leaves (rnn_clf.py:31, 146)
+ *   d_info[1]  = ceil(d_info[0] / hir)           the rows of the second level (rnn_clf.py:68, 113)
+ *   d_info[2]  = number of entries outside [1, T] (the host-length path asserts; the device path counts)
+ *   d_info[3]  = 0
+ * B in [1, 65535], T >= 1, hir >= 1; anything else or a NULL pointer is DSP_EINVAL before any device call.  Nothing is
+ * allocated or synchronised (capturable).
+ */
+int dsp_head_lengths_batch(const int32_t* d_len0, int32_t B, int32_t T, int32_t hir, int32_t* d_len0c, int32_t* d_len1, int32_t* d_info,
+                           void* stream);
+/*
+ * The pooling of the heads (rnn_clf.py:29-31, 68-72, 113-115, 146) over d_y [T, B, H] fp32, dense, whose rows t >= len are
+ * exact zeros in the reference and are NEVER READ here: with len = clamp(d_len[b], 1, T) and rows = d_rows ? min(*d_rows, T) : T
+ *   d_feat[b * ld_feat + col_avg + h] = (sum_{t < len} d_y[t, b, h]) / (float)len        skipped when col_avg < 0
+ *   d_feat[b * ld_feat + col_max + h] = max_{t < len} d_y[t, b, h], and where len < rows the maximum of that and 0.0f
+ * i.e. y[:rows].sum(0) / n and y[:rows].max(0).values of a y with zero rows behind each end.  A NaN in an active row makes
+ * the column's results NaN (torch.max / sum).  Only d_feat[b, col .. col + H) is written.  One launch; a column's rows are
+ * split over four waves whose partial sums and maxima are combined in a fixed order: the same bits on every run.  16-byte
+ * loads when H is a multiple of 4 and d_y is 16-byte aligned.  T, B >= 1, H in [1, 65535 * 64], col_max >= 0, the two column
+ * ranges disjoint and inside ld_feat; anything else or a NULL d_y / d_len / d_feat is DSP_EINVAL before any device call.
+ * Nothing is allocated or synchronised (capturable).
+ */
+int dsp_head_pool_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const int32_t* d_len, const int32_t* d_rows, float* d_feat,
+                        int64_t ld_feat, int32_t col_avg, int32_t col_max, void* stream);
 
 #ifdef __cplusplus
 }
