@@ -246,6 +246,14 @@ def check(rc):
         raise DspError(f'dsp_frontend error {rc}: {msg.decode() if msg else "?"}')
 
 
+def check_value(rc, what):
+    """``check`` where EINVAL is the caller's value at fault: ValueError with the library's message (else ``what``)."""
+    if rc == EINVAL:
+        msg = load().dsp_last_error()
+        raise ValueError(msg.decode() if msg else what)
+    check(rc)
+
+
 _device_ready = False
 
 

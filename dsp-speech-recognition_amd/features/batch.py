@@ -51,6 +51,45 @@ def _on_stream(stream, device):
     return torch.cuda.stream(stream)
 
 
+class _CapturedGraph:
+    """What every ``capture`` returns: ``replay()`` re-runs the captured launches on whatever ``waves`` holds now and
+    returns ``result`` (device tensors, valid after the current stream's work; nothing is synchronised).  ``hold``: every
+    buffer the graph's kernels touch that the result does not already keep alive."""
+
+    def __init__(self, graph, waves, result, hold):
+        self.graph, self.waves, self.result, self.hold = graph, waves, result, hold
+
+    def replay(self):
+        self.graph.replay()
+        return self.result
+
+
+def _capture(waves, prepare):
+    """The capture recipe.  The graph reads ``waves`` at its address, sample after sample: a host array raises TypeError, a
+    non-contiguous view (a copy would not see what the caller writes later) ValueError.  Then ``prepare()`` builds what
+    the graph owns -- a layout, plan or arena of its own, so that nothing else launches on the graph's tables -- and
+    returns ``(queue, hold)``: ``queue()`` puts the launches on torch's current stream and returns their result.  It runs
+    twice on a side stream: one eager warm call (it builds handles, long-lived index tables and arenas), then under
+    ``torch.cuda.graph``."""
+    import torch
+    if not _is_device_tensor(waves):
+        raise TypeError('capture needs a device tensor')
+    if not waves.is_contiguous():
+        raise ValueError('capture needs a contiguous waves tensor: the graph reads it in place on every replay')
+    queue, hold = prepare()
+    side = torch.cuda.Stream(waves.device)
+    side.wait_stream(torch.cuda.current_stream(waves.device))
+    with torch.no_grad():
+        with torch.cuda.stream(side):
+            warm = queue()
+        side.synchronize()
+        del warm
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            result = queue()
+    return _CapturedGraph(graph, waves, result, hold)
+
+
 class _BatchLayout:
     """Sample/frame offsets of one batch on host and (for ragged batches) on the device."""
 

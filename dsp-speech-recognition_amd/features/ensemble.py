@@ -22,7 +22,8 @@ import types
 import numpy as np
 
 from . import _native as nat
-from .batch import _is_device_tensor, _on_stream, _stream_ptr, _wave_dtype_of
+from .batch import _capture, _is_device_tensor, _on_stream, _stream_ptr, _wave_dtype_of
+from .pipeline import _TensorBuffer
 
 MAX_FEATURES, MAX_SV, MAX_RULES = 16, 65536, 4
 REFERENCE_RULES = (((0, 1), 0.8), ((6, 7), 0.7))          # ensemble.py:50-53: (label pair, confidence threshold)
@@ -121,11 +122,7 @@ class PitchSVM:
         if self._handle is None or self._handle_dev != dev:
             self._drop_handle()
             d, h = self.descriptor(), nat.c_vp(0)
-            rc = nat.load().dsp_svm_create(nat.C.byref(d), nat.C.byref(h))
-            if rc == nat.EINVAL:
-                msg = nat.load().dsp_last_error()
-                raise ValueError(msg.decode() if msg else 'invalid model')
-            nat.check(rc)
+            nat.check_value(nat.load().dsp_svm_create(nat.C.byref(d), nat.C.byref(h)), 'invalid model')
             self._handle, self._handle_dev = h.value, dev
         return self._handle
 
@@ -237,28 +234,8 @@ def ensemble_decide(logits, rules, feat=None, valid=None, stream=None):
     st = _torch_stream(dev) if stream is None else _stream_ptr(stream)
     rc = nat.load().dsp_ensemble_decide_batch(logits.data_ptr(), logits.stride(0), B, C, arr, n_rules, p_feat, ld_feat, p_valid,
                                               ld_valid, pred.data_ptr(), prob.data_ptr(), used.data_ptr(), dec.data_ptr(), st)
-    if rc == nat.EINVAL:
-        msg = nat.load().dsp_last_error()
-        raise ValueError(msg.decode() if msg else 'invalid argument')
-    nat.check(rc)
+    nat.check_value(rc, 'invalid argument')
     return pred, prob, used, dec
-
-
-class _TensorBuffer:
-    """A torch tensor behind the interface of a ``nat.DeviceBuffer`` (``ptr``, ``nbytes``, ``download``): in place of a layout's
-    segment table, so that torch -- inside a captured graph too -- can copy what the endpoint kernels write there."""
-
-    def __init__(self, tensor):
-        self.tensor, self.ptr, self.nbytes, self.wave = tensor, tensor.data_ptr(), tensor.numel() * tensor.element_size(), None
-
-    def download(self, shape, dtype, stream=None):
-        out = np.empty(shape, dtype=dtype)
-        assert out.nbytes <= self.nbytes, (out.nbytes, self.nbytes)
-        nat.check(nat.load().dsp_memcpy_d2h(out.ctypes.data, self.ptr, out.nbytes, stream))
-        return out
-
-    def free(self):
-        self.tensor = self.ptr = None
 
 
 def _segments_tensor(lay, dev):
@@ -276,21 +253,68 @@ def _logits_of(out):
     return logits.detach().to(torch.float32)
 
 
-class _EnsembleGraph:
-    """What ``EnsembleBatch.capture`` / ``MixedRateEnsembleBatch.capture`` return.  ``replay()`` re-runs the captured chain on
-    whatever ``waves`` holds now and returns the namespace of ``run()`` with every field a device tensor (``len0`` int32,
-    ``endpoints`` int64 [B, 2], and ``n_clamped``: how many lengths the head had to clamp into [1, 200]), valid after the
-    current stream's work; nothing is synchronised.  The object owns every buffer the graph's kernels touch."""
+class _EnsembleTail:
+    """What ``EnsembleBatch`` and ``MixedRateEnsembleBatch`` (``head``, ``rules``, ``coeff``) share: everything behind the
+    front end's launches."""
 
-    def __init__(self, graph, waves, out, hold):
-        self.graph, self.waves, self.out, self._hold = graph, waves, out, hold
+    def _tail(self, inp, d_len0, host, groups, head_kwargs, arenas=None):
+        """The head, per rate group the pre-emphasised trim and the five pitch features, ONE gate launch over the batch, and
+        the namespace of ``run`` -- launches on torch's current stream.  ``host``: the (len0, endpoints) arrays the front
+        end downloaded, or None: they stay on the device -- the head is called with ``device_len=True`` on ``d_len0``,
+        ``n_clamped`` counts what it had to clamp, and torch copies the endpoints from the groups' segment tables
+        (``_segments_tensor``).  ``groups``: (layout, contiguous wave tensor, rate, d_index) per rate; ``d_index``: the
+        group's batch positions (int32 device tensor), or None where the group is the whole batch and its rows are written
+        in place.  ``arenas``: one dict per group for the pitch chain's buffers, or None for library scratch."""
+        import torch
+        from .pitch import N_AUX, pitch_features_device
+        lib = nat.load()
+        dev, B = inp.device, inp.shape[1]
+        st = _torch_stream(dev)
+        extra = {}
+        if host is None:
+            from .classifier import head_length_info
+            len0 = d_len0
+            logits = _logits_of(self.head(inp, len0, device_len=True, **head_kwargs))
+            extra['n_clamped'] = head_length_info(len0, inp.shape[0], 1)[2][2:3]
+        else:
+            len0, endpoints = host
+            logits = _logits_of(self.head(inp, len0, **head_kwargs))
+        # the pitch chain's other buffers are library scratch that the next call reuses (or the arena's): the two results
+        # this call returns are torch's
+        feat = torch.empty((B, 5), dtype=torch.float64, device=dev)
+        aux = torch.empty((B, N_AUX), dtype=torch.int32, device=dev)
+        trimmed = []
+        for k, (lay, wave, rate, d_index) in enumerate(groups):
+            n = lay.n_utt
+            trim = torch.empty(max(lay.total_samples, 1), dtype=torch.float32, device=dev)
+            nat.check(lib.dsp_trim_preemph_batch(wave.data_ptr(), _wave_dtype_of(wave), lay.vad.p_sample, lay.d_seg.ptr,
+                                                 lay.d_dst_off.ptr, n, self.coeff, trim.data_ptr(), st))
+            one = d_index is None
+            feat_g = feat if one else torch.empty((n, 5), dtype=torch.float64, device=dev)
+            aux_g = aux if one else torch.empty((n, N_AUX), dtype=torch.int32, device=dev)
+            pitch_features_device(trim.data_ptr(), lay.d_dst_off.ptr, n, lay.total_samples, rate, stream=st,
+                                  d_feat=feat_g.data_ptr(), d_aux=aux_g.data_ptr(), arena=None if arenas is None else arenas[k])
+            if not one:                           # five doubles and nine ints per clip
+                pos = d_index.long()
+                feat.index_copy_(0, pos, feat_g)
+                aux.index_copy_(0, pos, aux_g)
+            trimmed.append(trim)
+        valid = aux[:, N_AUX - 1]
+        pred, prob, used, dec = ensemble_decide(logits, self.rules, feat, valid, stream=st)
+        if host is None:
+            endpoints = torch.empty((B, 2), dtype=torch.int64, device=dev)
+            for lay, _, _, d_index in groups:
+                seg = _segments_tensor(lay, dev)
+                if d_index is None:
+                    endpoints.copy_(seg)
+                else:
+                    endpoints.index_copy_(0, d_index.long(), seg)
+        return types.SimpleNamespace(pred=pred, prob=prob, used=used, decision=dec, logits=logits, feat=feat, valid=valid,
+                                     endpoints=endpoints, inp=inp, len0=len0, _clips=[g[1] for g in groups], _trimmed=trimmed,
+                                     **extra)
 
-    def replay(self):
-        self.graph.replay()
-        return self.out
 
-
-class EnsembleBatch:
+class EnsembleBatch(_EnsembleTail):
     """ensemble.EnsembleModel.test's loop body (ensemble.py:48-53) for a batch of raw clips, device-resident.
 
     ``head``: any callable ``head(inp, len0, **kwargs)`` returning the logits [B, C] first (``HMRNNHead``; the caller passes
@@ -325,11 +349,8 @@ class EnsembleBatch:
         features/classifier.py's), ``len0`` (int32) and ``endpoints`` are device tensors, and ``n_clamped`` (int32 [1]) counts
         the lengths the head had to clamp."""
         import torch
-        from .pitch import N_AUX, pitch_features_device
         nat.require_device()
-        lib = nat.load()
         so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
-        B = len(so) - 1
         # ONE contiguous device copy of the clips, held until the call returns: endpointing, the feature kernels and the
         # pre-emphasised trim all read this buffer
         if _is_device_tensor(waves):
@@ -337,98 +358,53 @@ class EnsembleBatch:
         else:
             host, _ = nat.as_wave(np.asarray(waves).reshape(-1))
             clips = torch.from_numpy(host).to(torch.device('cuda', nat.current_device()))
-        dev = clips.device
-        dtype = _wave_dtype_of(clips)
+        _wave_dtype_of(clips)                              # TypeError for anything but int16 / float32
         lay = self._layout(so)
         if sync_free:
-            _segments_tensor(lay, dev)
-            m0 = torch.empty((max(lay.frames_bound, 1), self.features.pipe.features.C), dtype=torch.float32, device=dev)
-            return self._chain(clips, lay, m0, None, head_kwargs)
+            return self._chain(clips, lay, self._m0(lay, clips.device), None, head_kwargs)
         inp, len0, endpoints = self.features.run(clips, layout=lay)
-        logits = _logits_of(self.head(inp, len0, **head_kwargs))
-        st = _torch_stream(dev)
-        trimmed = torch.empty(max(lay.total_samples, 1), dtype=torch.float32, device=dev)
-        nat.check(lib.dsp_trim_preemph_batch(clips.data_ptr(), dtype, lay.vad.p_sample, lay.d_seg.ptr, lay.d_dst_off.ptr, B,
-                                             self.coeff, trimmed.data_ptr(), st))
-        # the pitch chain's other buffers are library scratch that the next call reuses: the two results this call
-        # returns are torch's
-        feat = torch.empty((B, 5), dtype=torch.float64, device=dev)
-        aux = torch.empty((B, N_AUX), dtype=torch.int32, device=dev)
-        pitch_features_device(trimmed.data_ptr(), lay.d_dst_off.ptr, B, lay.total_samples, self.rate, stream=st,
-                              d_feat=feat.data_ptr(), d_aux=aux.data_ptr())
-        valid = aux[:, N_AUX - 1]
-        pred, prob, used, dec = ensemble_decide(logits, self.rules, feat, valid, stream=st)
-        return types.SimpleNamespace(pred=pred, prob=prob, used=used, decision=dec, logits=logits, feat=feat, valid=valid,
-                                     endpoints=endpoints, inp=inp, len0=len0, _clips=clips, _trimmed=trimmed)
+        return self._tail(inp, None, (len0, endpoints), [(lay, clips, self.rate, None)], head_kwargs)
+
+    def _m0(self, lay, dev):
+        """The front end's [frames_bound, C] scratch for ``_chain``; the layout's segment table becomes a torch tensor."""
+        import torch
+        _segments_tensor(lay, dev)
+        return torch.empty((max(lay.frames_bound, 1), self.features.pipe.features.C), dtype=torch.float32, device=dev)
 
     def _chain(self, clips, lay, m0, arena, head_kwargs):
         """The whole path as launches on torch's current stream, nothing synchronised, no device memory read from the host:
-        front end (``ModelFeatureBatch.enqueue``), head with ``device_len=True``, pre-emphasised trim, pitch features, gate.
-        ``lay``: a layout of this object whose segment table is a torch tensor; ``m0``: the front end's [frames_bound, C]
-        scratch; ``arena``: the pitch chain's buffers (None: library scratch, for an eager call)."""
+        front end (``ModelFeatureBatch.enqueue``), then ``_tail`` with the lengths on the device.  ``lay`` / ``m0``: a layout
+        of this object and its scratch (``_m0``); ``arena``: the pitch chain's buffers (None: library scratch, for an eager
+        call)."""
         import torch
-        from .classifier import head_length_info
-        from .pitch import N_AUX, pitch_features_device
-        lib = nat.load()
-        dev, B = clips.device, lay.n_utt
-        stream = torch.cuda.current_stream(dev)
-        st = _stream_ptr(stream)
-        mfb = self.features
+        mfb, dev, B = self.features, clips.device, lay.n_utt
         inp = torch.empty((mfb.max_len, B, 3 * mfb.pipe.features.C), dtype=torch.float32, device=dev)
         len0 = torch.empty(B, dtype=torch.int32, device=dev)
-        mfb.enqueue(clips.data_ptr(), _wave_dtype_of(clips), lay, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(), stream)
-        logits = _logits_of(self.head(inp, len0, device_len=True, **head_kwargs))
-        n_clamped = head_length_info(len0, mfb.max_len, 1)[2][2:3]
-        trimmed = torch.empty(max(lay.total_samples, 1), dtype=torch.float32, device=dev)
-        nat.check(lib.dsp_trim_preemph_batch(clips.data_ptr(), _wave_dtype_of(clips), lay.vad.p_sample, lay.d_seg.ptr, lay.d_dst_off.ptr,
-                                             B, self.coeff, trimmed.data_ptr(), st))
-        feat = torch.empty((B, 5), dtype=torch.float64, device=dev)
-        aux = torch.empty((B, N_AUX), dtype=torch.int32, device=dev)
-        pitch_features_device(trimmed.data_ptr(), lay.d_dst_off.ptr, B, lay.total_samples, self.rate, stream=st,
-                              d_feat=feat.data_ptr(), d_aux=aux.data_ptr(), arena=arena)
-        valid = aux[:, N_AUX - 1]
-        pred, prob, used, dec = ensemble_decide(logits, self.rules, feat, valid, stream=st)
-        endpoints = _segments_tensor(lay, dev).clone()
-        return types.SimpleNamespace(pred=pred, prob=prob, used=used, decision=dec, logits=logits, feat=feat, valid=valid,
-                                     endpoints=endpoints, inp=inp, len0=len0, n_clamped=n_clamped, _clips=clips, _trimmed=trimmed)
+        mfb.enqueue(clips.data_ptr(), _wave_dtype_of(clips), lay, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(),
+                    torch.cuda.current_stream(dev))
+        return self._tail(inp, len0, None, [(lay, clips, self.rate, None)], head_kwargs, None if arena is None else [arena])
 
     def capture(self, waves, sample_offsets, **head_kwargs):
         """ONE HIP graph of the whole path over device-resident ``waves`` (a contiguous tensor, int16 / float32):
         ``g = eb.capture(waves, so, dropout=False)``; write new clips of the same lengths into ``waves`` and call
-        ``g.replay()`` -> the namespace of ``run(sync_free=True)``.  One eager call runs first (it builds the native handles and
-        the layout's index tables and fills the graph's own arena).  The graph object owns every buffer its kernels touch --
-        the layout, the front end's scratch, the pitch chain's buffers and FIR taps -- so no later call of the library can
-        free or overwrite what a replay reads.  The graph reads ``waves`` at its address: a non-contiguous view raises
-        ValueError; the head must accept ``device_len=True``."""
-        import torch
-        if not _is_device_tensor(waves):
-            raise TypeError('capture needs a device tensor')
-        if not waves.is_contiguous():
-            raise ValueError('capture needs a contiguous waves tensor: the graph reads it in place on every replay')
-        nat.require_device()
-        so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
-        dev = waves.device
-        clips = waves.reshape(-1)                          # a view: the same memory
-        _wave_dtype_of(clips)                              # TypeError for anything but int16 / float32
-        lay = self.features.pipe.prepare(so, 0)            # the graph's own: nothing else launches on its tables
-        _segments_tensor(lay, dev)
-        m0 = torch.empty((max(lay.frames_bound, 1), self.features.pipe.features.C), dtype=torch.float32, device=dev)
-        arena = {}
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.no_grad():
-            with torch.cuda.stream(side):
-                warm = self._chain(clips, lay, m0, arena, head_kwargs)
-            side.synchronize()
-            del warm
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side):
-                out = self._chain(clips, lay, m0, arena, head_kwargs)
-        return _EnsembleGraph(graph, waves, out, [lay, m0, arena, clips, list(self.rules)])
+        ``g.replay()`` -> the namespace of ``run(sync_free=True)``, every field a device tensor, valid after the current
+        stream's work.  One eager call runs first (it builds the native handles and the layout's index tables and fills the
+        graph's own arena).  The graph object owns every buffer its kernels touch -- the layout, the front end's scratch,
+        the pitch chain's buffers and FIR taps -- so no later call of the library can free or overwrite what a replay reads.
+        The graph reads ``waves`` at its address: a non-contiguous view raises ValueError; the head must accept
+        ``device_len=True``."""
+        def prepare():
+            nat.require_device()
+            clips = waves.reshape(-1)                          # a view: the same memory
+            _wave_dtype_of(clips)                              # TypeError for anything but int16 / float32
+            so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
+            lay = self.features.pipe.prepare(so, 0)            # the graph's own: nothing else launches on its tables
+            m0, arena = self._m0(lay, waves.device), {}
+            return (lambda: self._chain(clips, lay, m0, arena, head_kwargs)), [lay, m0, arena, clips, list(self.rules)]
+        return _capture(waves, prepare)
 
 
-
-class MixedRateEnsembleBatch:
+class MixedRateEnsembleBatch(_EnsembleTail):
     """EnsembleBatch for a batch whose clips have different sample rates (reader.mini_batch_iterator shuffles the file list,
     reader.py:80; ensemble.py:48-53 and pitch_model.py:54-61 treat every clip at its own rate): the classifier's features
     from MixedRateFeatureBatch, ONE ``head`` call on the whole batch, the pre-emphasised trim and the five pitch features per
@@ -443,70 +419,29 @@ class MixedRateEnsembleBatch:
         """``waves`` / ``sample_offsets`` / ``rates`` as MixedRateFeatureBatch.run.  Returns the namespace of EnsembleBatch.run,
         every row in batch order; ``sync_free=True`` as there (device input: no synchronisation once the plan of the batch
         shape exists)."""
+        mr = self.features
         if sync_free:
             import torch
-            mr = self.features
             clips, so, r = mr._inputs(waves, sample_offsets, rates)
             on_device = _is_device_tensor(clips)
             dev = clips.device if on_device else torch.device('cuda', nat.current_device())
             plan = mr._plan(so, r, dev, on_device)       # this object's: its segment tables become torch's before the launches
-            for g in plan.groups:
-                _segments_tensor(g.lay, dev)
-            return self._tail(mr._launch(waves, sample_offsets, rates, plan=plan), None, None, head_kwargs, None)
-        ctx = self.features._launch(waves, sample_offsets, rates)
-        len0, endpoints = self.features._finish(ctx)
-        return self._tail(ctx, len0, endpoints, head_kwargs, None)
+            return self._chain(waves, so, r, plan, dev, None, head_kwargs)
+        ctx = mr._launch(waves, sample_offsets, rates)
+        return self._after(ctx, mr._finish(ctx), head_kwargs, None)
 
-    def _tail(self, ctx, len0, endpoints, head_kwargs, arenas):
-        """Everything behind the front end's launches.  ``len0`` / ``endpoints`` None: they stay on the device (the head is
-        called with ``device_len=True``, the endpoints are copied from the groups' segment tables by torch); ``arenas``: one
-        dict per rate group for the pitch chain's buffers, or None for library scratch."""
-        import torch
-        from .pitch import N_AUX, pitch_features_device
-        lib = nat.load()
-        clips = ctx.group_waves                   # one contiguous device buffer per rate, held until the call returns
-        inp, dev, st, B = ctx.inp, ctx.dev, ctx.st, ctx.plan.B
-        n_clamped = None
-        if len0 is None:
-            from .classifier import head_length_info
-            len0 = ctx.len0
-            logits = _logits_of(self.head(inp, len0, device_len=True, **head_kwargs))
-            n_clamped = head_length_info(len0, inp.shape[0], 1)[2][2:3]
-            endpoints = torch.empty((B, 2), dtype=torch.int64, device=dev)
-            for g in ctx.plan.groups:
-                seg = _segments_tensor(g.lay, dev)
-                if g.d_index is None:
-                    endpoints.copy_(seg)
-                else:
-                    endpoints.index_copy_(0, g.d_index.long(), seg)
-        else:
-            logits = _logits_of(self.head(inp, len0, **head_kwargs))
-        feat = torch.empty((B, 5), dtype=torch.float64, device=dev)
-        aux = torch.empty((B, N_AUX), dtype=torch.int32, device=dev)
-        trimmed = []
-        for g, wave in zip(ctx.plan.groups, clips):
-            lay, n = g.lay, len(g.index)
-            trim = torch.empty(max(lay.total_samples, 1), dtype=torch.float32, device=dev)
-            nat.check(lib.dsp_trim_preemph_batch(wave.data_ptr(), _wave_dtype_of(wave), lay.vad.p_sample, lay.d_seg.ptr,
-                                                 lay.d_dst_off.ptr, n, self.coeff, trim.data_ptr(), st))
-            one = g.d_index is None               # a single rate: the group's rows are the batch's
-            feat_g = feat if one else torch.empty((n, 5), dtype=torch.float64, device=dev)
-            aux_g = aux if one else torch.empty((n, N_AUX), dtype=torch.int32, device=dev)
-            pitch_features_device(trim.data_ptr(), lay.d_dst_off.ptr, n, lay.total_samples, g.rate, stream=st,
-                                  d_feat=feat_g.data_ptr(), d_aux=aux_g.data_ptr(),
-                                  arena=None if arenas is None else arenas[len(trimmed)])
-            if not one:                           # five doubles and nine ints per clip
-                pos = g.d_index.long()
-                feat.index_copy_(0, pos, feat_g)
-                aux.index_copy_(0, pos, aux_g)
-            trimmed.append(trim)
-        valid = aux[:, N_AUX - 1]
-        pred, prob, used, dec = ensemble_decide(logits, self.rules, feat, valid, stream=st)
-        ns = types.SimpleNamespace(pred=pred, prob=prob, used=used, decision=dec, logits=logits, feat=feat, valid=valid,
-                                   endpoints=endpoints, inp=inp, len0=len0, _clips=clips, _trimmed=trimmed)
-        if n_clamped is not None:
-            ns.n_clamped, ns._hold = n_clamped, ctx.hold          # (torch tensors: released in stream order)
+    def _after(self, ctx, host, head_kwargs, arenas):
+        """``_tail`` behind the launches of ``MixedRateFeatureBatch._launch``: one contiguous device buffer per rate."""
+        groups = [(g.lay, wave, g.rate, g.d_index) for g, wave in zip(ctx.plan.groups, ctx.group_waves)]
+        ns = self._tail(ctx.inp, ctx.len0, host, groups, head_kwargs, arenas)
+        ns._hold = ctx.hold                       # the temporaries of the launches (torch tensors: released in stream order)
         return ns
+
+    def _chain(self, waves, so, rates, plan, dev, arenas, head_kwargs):
+        """The whole path on ``plan`` with nothing synchronised: the lengths and the endpoints stay on the device."""
+        for g in plan.groups:
+            _segments_tensor(g.lay, dev)
+        return self._after(self.features._launch(waves, so, rates, plan=plan), None, head_kwargs, arenas)
 
     def capture(self, waves, sample_offsets, rates, **head_kwargs):
         """``EnsembleBatch.capture`` for a mixed-rate batch: ONE HIP graph of the front end's sub-pipelines (queued one after
@@ -515,27 +450,11 @@ class MixedRateEnsembleBatch:
         ``replay()`` -> the namespace of ``run(sync_free=True)``, rows in batch order.  The graph object owns the plan, every
         group's layout and pitch arena, and the temporaries of the launches.  (The optional ``use_pitch`` / ``use_timefeat``
         streams are not part of the capture.)"""
-        import torch
         from .model_glue import _MixedPlan
-        if not _is_device_tensor(waves):
-            raise TypeError('capture needs a device tensor')
-        if not waves.is_contiguous():
-            raise ValueError('capture needs a contiguous waves tensor: the graph reads it in place on every replay')
-        mr = self.features
-        _, so, rates = mr._inputs(waves, sample_offsets, rates)
-        dev = waves.device
-        plan = _MixedPlan(mr, so, rates, dev, True)            # the graph's own: nothing else writes its tables
-        for g in plan.groups:
-            _segments_tensor(g.lay, dev)
-        arenas = [{} for _ in plan.groups]
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.no_grad():
-            with torch.cuda.stream(side):
-                warm = self._tail(mr._launch(waves, so, rates, plan=plan), None, None, head_kwargs, arenas)
-            side.synchronize()
-            del warm
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side):
-                out = self._tail(mr._launch(waves, so, rates, plan=plan), None, None, head_kwargs, arenas)
-        return _EnsembleGraph(graph, waves, out, [plan, arenas, list(self.rules)])
+
+        def prepare():
+            _, so, r = self.features._inputs(waves, sample_offsets, rates)
+            plan = _MixedPlan(self.features, so, r, waves.device, True)    # the graph's own: nothing else writes its tables
+            arenas = [{} for _ in plan.groups]
+            return (lambda: self._chain(waves, so, r, plan, waves.device, arenas, head_kwargs)), [plan, arenas, list(self.rules)]
+        return _capture(waves, prepare)

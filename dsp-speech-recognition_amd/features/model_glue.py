@@ -10,8 +10,12 @@ from __future__ import annotations
 
 import numpy as np
 
-from .base import delta, mfcc
+from . import _native as nat
 from . import endpoint as _endpoint
+from .base import delta, mfcc
+from .batch import _capture, _is_device_tensor, _stream_ptr, _wave_dtype_of
+from .pipeline import VadMfccPipeline
+from .pitch import pitch_detect_sr, pitch_tracks_device
 
 
 def endpoint_detect(sig, rate, augment=False, rng=None):
@@ -55,7 +59,6 @@ def deviation(arr, smooth=1):
 def feature_extract_pitch(sound, rate):
     """model.py:90-95, the optional pitch stream (cfg.use_pitch): pitch track / 150 and its
     first difference, both [T, 1]."""
-    from .pitch import pitch_detect_sr
     cfg = _endpoint.cfg
     pitch0, _ = pitch_detect_sr(np.asarray(sound).reshape(-1), rate, winlen=cfg.frame, step=cfg.step)
     pitch0 = np.array(pitch0).reshape(-1, 1) / 150
@@ -113,7 +116,6 @@ def batch_to_rnn_input(features, frame_offsets, max_len=200):
 def model_finalize(mfcc0, frame_offsets, delta_n=3, max_len=200):
     """Host-array form of dsp_model_finalize_batch: ``mfcc0`` [sum T_b, C] (the raw MFCCs of a
     batch) -> (inp [max_len, B, 3C] fp32, len0 [B]) as model.py:75-78 + 35-50 build them."""
-    from . import _native as nat
     nat.require_device()
     lib = nat.load()
     m = np.ascontiguousarray(mfcc0, dtype=np.float32)
@@ -128,26 +130,15 @@ def model_finalize(mfcc0, frame_offsets, delta_n=3, max_len=200):
     return d_out.download((max_len, B, 3 * C), np.float32), d_len.download((B,), np.int32)
 
 
-class _ModelFeatureGraph:
-    """What ModelFeatureBatch.capture returns: replay() re-runs the captured launches on whatever ``waves`` holds now."""
-
-    def __init__(self, graph, waves, m0, inp, len0, layout):
-        self.graph, self.waves, self.m0, self.inp, self.len0, self.layout = graph, waves, m0, inp, len0, layout
-
-    def replay(self):
-        self.graph.replay()
-        return self.inp, self.len0
-
-
 class ModelFeatureBatch:
     """Batched, device-resident form of RNNModel.get_batch_full (model.py:113-135): endpointing ->
     (optional endpoint jitter, model.py:54-60) -> trim -> unit variance -> MFCC on the (1, N) view (no
     pre-emphasis, sigproc.py:185) -> minus the utterance's scalar mean -> delta(3), delta(delta, 3) ->
     z-score of the static coefficients -> [200, B, 39] zero padded.  Every step is a kernel behind the C
-    ABI, queued on one stream with no host round trip in between (features/pipeline.py)."""
+    ABI, queued on one stream with no host round trip in between (features/pipeline.py).  ``run``, ``enqueue`` and
+    ``enqueue_placed`` are one launch sequence: ``pipe.launch``, then ``_after_launch``."""
 
     def __init__(self, rate, frame=0.03, step=0.01, nfft=1536, delta_n=3, max_len=200):
-        from .pipeline import VadMfccPipeline
         self.rate = rate
         self.pipe = VadMfccPipeline(rate=rate, frame=frame, step=step, unit_variance=True, winlen=frame,
                                     winstep=step, nfft=nfft, preemph=0.0, winfunc=np.hamming)
@@ -157,27 +148,18 @@ class ModelFeatureBatch:
         """The augmentation of model.py:54-60 for a whole batch: (-randint(0, 0.1 rate), +randint(0, 0.1
         rate)) per utterance from ``rng`` (a random.Random, consumed in the reference's order: s_l then
         s_r, utterance by utterance)."""
-        hi = int(0.1 * self.rate)
-        j = np.empty((n_utt, 2), dtype=np.int64)
-        for b in range(n_utt):
-            j[b, 0] = -rng.randint(0, hi)
-            j[b, 1] = rng.randint(0, hi)
-        return j
+        return MixedRateFeatureBatch.draw_jitter([self.rate] * n_utt, rng)
 
     def run(self, waves, sample_offsets=None, jitter=None, layout=None, use_pitch=False, use_timefeat=False):
         """-> (inp [max_len, B, 39 (+2) (+2)] torch tensor on the library's device, len0 [B], endpoints [B, 2]).
         ``jitter``: int [B, 2] endpoint offsets (see draw_jitter) for the training path (augment=True);
         None = test path.  ``use_timefeat`` / ``use_pitch`` append the optional streams of model.py:125-128
         in the reference's order (pitch, then amplitude), both computed on the device from one trimmed, scaled
-        fp32 copy of the clips (dsp_trim_scale_batch): the amplitude stream by dsp_vad_features_batch +
-        dsp_model_timefeat_batch, the pitch stream by the batched tracker (_pitch_streams) -- no clip and no track
-        crosses PCIe.  ``waves`` may be any view of a device tensor: a non-contiguous one is copied once on torch's
-        current stream (the stream of every launch here), and that copy is held until the call's last kernel has
-        finished.  torch only owns the result tensors."""
+        fp32 copy of the clips (dsp_trim_scale_batch) and written into their columns of ``inp`` in place -- no clip and
+        no track crosses PCIe.  ``waves`` may be any view of a device tensor: a non-contiguous one is copied once on
+        torch's current stream (the stream of every launch here), and that copy is held until the call's last kernel has
+        finished.  torch only owns the result tensor."""
         import torch
-        from . import _native as nat
-        from .batch import _is_device_tensor, _stream_ptr
-        lib = nat.load()
         dev = waves.device if _is_device_tensor(waves) else torch.device('cuda', nat.current_device())
         stream = torch.cuda.current_stream(dev)
         if layout is None:       # this call consumes the layout's tables before it returns: a cached one is safe
@@ -185,49 +167,25 @@ class ModelFeatureBatch:
         # the clips are read where they lie (no trimmed fp32 copy): the MFCC kernel accumulates the unit-variance
         # statistics, the finalize kernel applies them to c0 as it reads
         (d_m0, lay), _, _ = self.pipe.run(waves, delta_n=0, download=False, layout=layout, jitter=jitter, defer_c0_shift=True)
-        B, C = lay.n_utt, self.pipe.features.C
-        inp = torch.empty((self.max_len, B, 3 * C), dtype=torch.float32, device=dev)
+        B = lay.n_utt
+        width = 3 * self.pipe.features.C + (2 if use_pitch else 0) + (2 if use_timefeat else 0)
+        inp = torch.empty((self.max_len, B, width), dtype=torch.float32, device=dev)
         len0 = torch.empty(B, dtype=torch.int32, device=dev)
         # host input: the pipeline ran on the legacy default stream, which orders against `stream`
         st = _stream_ptr(stream) if _is_device_tensor(waves) else None
-        if lay.c0_shift_pending:
-            nat.check(lib.dsp_model_finalize_segments_batch(d_m0.ptr, C, lay.d_frame_off.ptr, lay.d_seg.ptr, lay.d_work.ptr, B, C,
-                                                            self.delta_n, self.max_len, inp.data_ptr(), len0.data_ptr(), st))
-        else:
-            nat.check(lib.dsp_model_finalize_batch(d_m0.ptr, C, lay.d_frame_off.ptr, B, C, self.delta_n, self.max_len,
-                                                   inp.data_ptr(), len0.data_ptr(), st))
-        extra = []
-        if (use_pitch or use_timefeat) and lay.c0_shift_pending:
-            # the optional streams work on the trimmed, scaled clips themselves: make that copy now (model.py:62-63)
-            wave = d_m0.wave                  # the buffer pipe.run launched on, alive until d_m0 goes (after the synchronisation below)
-            nat.check(lib.dsp_trim_scale_batch(wave.ptr, wave.dtype, lay.vad.p_sample, lay.d_seg.ptr, lay.d_dst_off.ptr,
-                                               B, 1, lay.d_trim.ptr, st))
-        if use_pitch:
-            extra.append(self._pitch_streams(lay, st, dev))
-        if use_timefeat:
-            extra.append(self._timefeat_streams(lay, st, dev))
+        wave = d_m0.wave                      # the buffer pipe.run launched on, alive until d_m0 goes
+        hold = self._after_launch(wave.ptr, wave.dtype, lay, d_m0.ptr, inp.data_ptr(), len0.data_ptr(), None, B, width, st, dev,
+                                  use_pitch, use_timefeat)
         seg = lay.d_seg.download((B, 2), np.int64, st)       # first host synchronisation of the default call
-        nat.check(lib.dsp_stream_synchronize(st))            # d_m0 and the wave buffer it holds go on return: their consumers have finished
-        if extra:
-            inp = torch.cat([inp] + extra, dim=2)
+        nat.check(nat.load().dsp_stream_synchronize(st))     # d_m0, its wave buffer and `hold` go on return: their consumers have finished
+        del hold
         return inp, len0.cpu().numpy(), seg
 
     def enqueue(self, d_wave, wave_dtype, lay, d_m0, d_inp, d_len0, stream):
         """The default call (no optional streams, no jitter) as launches only -- raw device pointers, nothing allocated,
         nothing synchronised: endpointing, the layout glue, the feature kernel on the clips in place and the finalize
         kernel.  ``d_m0``: [lay.frames_bound, C] fp32 scratch, ``d_inp``: [max_len, B, 3 C] fp32, ``d_len0``: [B] int32."""
-        from . import _native as nat
-        from .batch import _stream_ptr
-        lib = nat.load()
-        st = _stream_ptr(stream)
-        C = self.pipe.features.C
-        self.pipe.launch(d_wave, wave_dtype, lay, d_m0, stream, None, defer_c0_shift=True)
-        if lay.c0_shift_pending:
-            nat.check(lib.dsp_model_finalize_segments_batch(d_m0, C, lay.d_frame_off.ptr, lay.d_seg.ptr, lay.d_work.ptr, lay.n_utt, C,
-                                                            self.delta_n, self.max_len, d_inp, d_len0, st))
-        else:
-            nat.check(lib.dsp_model_finalize_batch(d_m0, C, lay.d_frame_off.ptr, lay.n_utt, C, self.delta_n, self.max_len,
-                                                   d_inp, d_len0, st))
+        self.enqueue_placed(d_wave, wave_dtype, lay, d_m0, d_inp, d_len0, None, lay.n_utt, 3 * self.pipe.features.C, stream, None)
 
     def enqueue_placed(self, d_wave, wave_dtype, lay, d_m0, d_inp, d_len0, d_dst_col, n_cols, row_width, stream, dev,
                        d_jitter=None, use_pitch=False, use_timefeat=False):
@@ -236,12 +194,17 @@ class ModelFeatureBatch:
         (dsp_model_finalize_placed_batch; ``d_dst_col`` None = identity), the optional streams of ``run`` to the columns
         behind, in the reference's order (model.py:125-128).  Launches only; returns the temporaries the optional streams
         read, which the caller keeps until ``stream`` has finished.  Without optional streams nothing is allocated."""
-        from . import _native as nat
-        from .batch import _stream_ptr
-        lib = nat.load()
-        st = _stream_ptr(stream)
-        B, C = lay.n_utt, self.pipe.features.C
         self.pipe.launch(d_wave, wave_dtype, lay, d_m0, stream, d_jitter, defer_c0_shift=True)
+        return self._after_launch(d_wave, wave_dtype, lay, d_m0, d_inp, d_len0, d_dst_col, n_cols, row_width, _stream_ptr(stream), dev,
+                                  use_pitch, use_timefeat)
+
+    def _after_launch(self, d_wave, wave_dtype, lay, d_m0, d_inp, d_len0, d_dst_col, n_cols, row_width, st, dev,
+                      use_pitch, use_timefeat):
+        """Everything behind ``pipe.launch(..., defer_c0_shift=True)``, queued on the raw stream ``st``, always in placed form
+        (``d_dst_col`` None, ``n_cols`` = B, ``row_width`` = the tensor's own width: the identity): the finalize kernel, then
+        the optional streams at their column offsets.  Returns the temporaries to hold until ``st`` has finished."""
+        lib = nat.load()
+        B, C = lay.n_utt, self.pipe.features.C
         seg, work = (lay.d_seg.ptr, lay.d_work.ptr) if lay.c0_shift_pending else (None, None)
         nat.check(lib.dsp_model_finalize_placed_batch(d_m0, C, lay.d_frame_off.ptr, seg, work, B, C, self.delta_n, self.max_len,
                                                       d_inp, d_len0, d_dst_col, n_cols, row_width, 0, st))
@@ -250,10 +213,10 @@ class ModelFeatureBatch:
             nat.check(lib.dsp_trim_scale_batch(d_wave, wave_dtype, lay.vad.p_sample, lay.d_seg.ptr, lay.d_dst_off.ptr,
                                                B, 1, lay.d_trim.ptr, st))
         if use_pitch:
-            hold += self._pitch_streams(lay, st, dev, place=(d_inp, d_dst_col, n_cols, row_width, col))
+            self._pitch_streams(lay, st, (d_inp, d_dst_col, n_cols, row_width, col))
             col += 2
         if use_timefeat:
-            hold += self._timefeat_streams(lay, st, dev, place=(d_inp, d_dst_col, n_cols, row_width, col))
+            hold += self._timefeat_streams(lay, st, dev, (d_inp, d_dst_col, n_cols, row_width, col))
         return hold
 
     def capture(self, waves, layout):
@@ -263,37 +226,29 @@ class ModelFeatureBatch:
         synchronisation).  One eager call runs first (it builds the layout's long-lived index tables).
         The graph reads ``waves`` at its address, sample after sample: a non-contiguous view cannot be served (a copy
         would not see what the caller writes later) and raises ValueError; a contiguous view at any offset is fine."""
-        import torch
-        from .batch import _is_device_tensor, _wave_dtype_of
-        if not _is_device_tensor(waves):
-            raise TypeError('capture needs a device tensor')
-        if not waves.is_contiguous():
-            raise ValueError('capture needs a contiguous waves tensor: the graph reads it in place on every replay')
-        dev = waves.device
-        C, B = self.pipe.features.C, layout.n_utt
-        m0 = torch.empty((max(layout.frames_bound, 1), C), dtype=torch.float32, device=dev)
-        inp = torch.empty((self.max_len, B, 3 * C), dtype=torch.float32, device=dev)
-        len0 = torch.empty(B, dtype=torch.int32, device=dev)
-        dtype = _wave_dtype_of(waves)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            self.enqueue(waves.data_ptr(), dtype, layout, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(), side)
-        side.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=side):
-            self.enqueue(waves.data_ptr(), dtype, layout, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(), torch.cuda.current_stream(dev))
-        return _ModelFeatureGraph(graph, waves, m0, inp, len0, layout)
 
-    def _timefeat_streams(self, lay, st, dev, place=None):
-        """[max_len, B, 2]: z-scored frame amplitude of the trimmed, scaled clips and its first difference
-        (model.py:97-101), on the device -- at the amplitude stream's OWN framing (int(rate * cfg.frame),
-        int(cfg.step * rate): to_frames truncates, sigproc.py:19; the MFCC framing rounds half up, so the two differ at
-        e.g. 22.05 kHz): its frame offsets come from one small launch over the trimmed offsets.
-        ``place`` = (d_out, d_dst_col, n_cols, row_width, col_offset): the two columns go there instead
-        (dsp_model_timefeat_placed_batch), nothing is synchronised and the temporaries are returned for the caller to hold."""
+        def prepare():
+            import torch
+            dev, dtype = waves.device, _wave_dtype_of(waves)
+            C, B = self.pipe.features.C, layout.n_utt
+            m0 = torch.empty((max(layout.frames_bound, 1), C), dtype=torch.float32, device=dev)
+            inp = torch.empty((self.max_len, B, 3 * C), dtype=torch.float32, device=dev)
+            len0 = torch.empty(B, dtype=torch.int32, device=dev)
+
+            def queue():
+                self.enqueue(waves.data_ptr(), dtype, layout, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(),
+                             torch.cuda.current_stream(dev))
+                return inp, len0
+            return queue, [m0, layout]
+        return _capture(waves, prepare)
+
+    def _timefeat_streams(self, lay, st, dev, place):
+        """Z-scored frame amplitude of the trimmed, scaled clips and its first difference (model.py:97-101), on the
+        device -- at the amplitude stream's OWN framing (int(rate * cfg.frame), int(cfg.step * rate): to_frames truncates,
+        sigproc.py:19; the MFCC framing rounds half up, so the two differ at e.g. 22.05 kHz): its frame offsets come from
+        one small launch over the trimmed offsets.  ``place`` = (d_out, d_dst_col, n_cols, row_width, col_offset): where the
+        two columns go (dsp_model_timefeat_placed_batch).  Returns the temporaries for the caller to hold."""
         import torch
-        from . import _native as nat
         lib = nat.load()
         ep, fp = self.pipe.endpoint, self.pipe.features
         L2, S2 = int(self.rate * ep.frame), int(ep.step * self.rate)       # to_frames truncation, sigproc.py:19
@@ -309,35 +264,19 @@ class ModelFeatureBatch:
         d_zcr = torch.empty(max(frames_bound, 1), dtype=torch.int32, device=dev)
         nat.check(lib.dsp_vad_features_batch(lay.d_trim.ptr, nat.WAVE_F32, lay.d_dst_off.ptr, p_fo, B,
                                              frames_bound, 0, L2, S2, 0, d_amp.data_ptr(), d_zcr.data_ptr(), st))
-        if place is not None:
-            nat.check(lib.dsp_model_timefeat_placed_batch(d_amp.data_ptr(), p_fo, B, L2, self.max_len, *place, st))
-            return [d_amp, d_zcr, d_fo2]
-        out = torch.empty((self.max_len, B, 2), dtype=torch.float32, device=dev)
-        nat.check(lib.dsp_model_timefeat_batch(d_amp.data_ptr(), p_fo, B, L2, self.max_len,
-                                               out.data_ptr(), st))
-        nat.check(lib.dsp_stream_synchronize(st))            # d_amp / d_zcr / the offsets are released on return
-        return out
+        nat.check(lib.dsp_model_timefeat_placed_batch(d_amp.data_ptr(), p_fo, B, L2, self.max_len, *place, st))
+        return [d_amp, d_zcr, d_fo2]
 
-    def _pitch_streams(self, lay, st, dev, place=None):
-        """[max_len, B, 2]: pitch track / 150 and its first difference (model.py:90-95) of the trimmed, scaled
-        clips, on the device: decimation to 10 kHz (an index selection, preprocess.py:21-28), frame scores, smoothing,
-        arg-max, octave repair (pitch.py:96-206) and the [max_len, B, 2] layout -- six launches, no clip and no track
-        crosses PCIe.  ``place`` as in _timefeat_streams (dsp_model_pitchfeat_placed_batch); the track is library scratch
-        that later launches on the same stream may reuse, so there is nothing to hold."""
-        import torch
-        from . import _native as nat
-        from .pitch import pitch_tracks_device
-        lib = nat.load()
-        B = lay.n_utt
+    def _pitch_streams(self, lay, st, place):
+        """Pitch track / 150 and its first difference (model.py:90-95) of the trimmed, scaled clips, on the device:
+        decimation to 10 kHz (an index selection, preprocess.py:21-28), frame scores, smoothing, arg-max, octave repair
+        (pitch.py:96-206) and the two columns at ``place`` (as in _timefeat_streams; dsp_model_pitchfeat_placed_batch) --
+        six launches, no clip and no track crosses PCIe.  The track is library scratch that later launches on the same
+        stream may reuse, so there is nothing to hold."""
         cfg = _endpoint.cfg
         L, S = int(10000 * cfg.frame), int(cfg.step * 10000)
-        d_pitch, d_fo = pitch_tracks_device(lay.d_trim.ptr, lay.d_dst_off.ptr, B, int(lay.total_samples), self.rate, L, S, st)
-        if place is not None:
-            nat.check(lib.dsp_model_pitchfeat_placed_batch(d_pitch.ptr, d_fo.ptr, B, self.max_len, *place, st))
-            return []
-        out = torch.empty((self.max_len, B, 2), dtype=torch.float32, device=dev)
-        nat.check(lib.dsp_model_pitchfeat_batch(d_pitch.ptr, d_fo.ptr, B, self.max_len, out.data_ptr(), st))
-        return out
+        d_pitch, d_fo = pitch_tracks_device(lay.d_trim.ptr, lay.d_dst_off.ptr, lay.n_utt, int(lay.total_samples), self.rate, L, S, st)
+        nat.check(nat.load().dsp_model_pitchfeat_placed_batch(d_pitch.ptr, d_fo.ptr, lay.n_utt, self.max_len, *place, st))
 
 
 # ---- mixed sample rates in one batch ---------------------------------------------------------------------------------
@@ -401,17 +340,6 @@ class _MixedPlan:
         self.order = np.concatenate([g.index for g in self.groups])
 
 
-class _MixedRateGraph:
-    """What MixedRateFeatureBatch.capture returns: replay() re-runs the captured launches on whatever ``waves`` holds now."""
-
-    def __init__(self, graph, waves, plan, inp, len0, hold):
-        self.graph, self.waves, self.plan, self.inp, self.len0, self._hold = graph, waves, plan, inp, len0, hold
-
-    def replay(self):
-        self.graph.replay()
-        return self.inp, self.len0
-
-
 class MixedRateFeatureBatch:
     """RNNModel.get_batch_full (model.py:113-135) for a batch whose clips have different sample rates: one
     ModelFeatureBatch per rate seen (created on first use), the rate groups processed in order of first appearance on one
@@ -448,7 +376,6 @@ class MixedRateFeatureBatch:
     def _inputs(waves, sample_offsets, rates):
         """-> (clips, so, rates): ``clips`` a 1-D device tensor, or a list of B host arrays; ValueError before any device
         work for a rate list of the wrong length or a non-positive rate."""
-        from .batch import _is_device_tensor
         rates = _as_rates(rates)
         if isinstance(waves, (list, tuple)):
             clips = [np.asarray(c).reshape(-1) for c in waves]
@@ -488,8 +415,6 @@ class MixedRateFeatureBatch:
         """The clips of group ``g`` as one contiguous 1-D device tensor: a view of a device batch where they form one run,
         one gather launch where they do not, one upload of the host clips concatenated per rate."""
         import torch
-        from . import _native as nat
-        from .batch import _is_device_tensor, _wave_dtype_of
         if not _is_device_tensor(clips):
             parts = [nat.as_wave(clips[b]) for b in g.index]
             if any(dt != nat.WAVE_I16 for _, dt in parts):
@@ -509,8 +434,6 @@ class MixedRateFeatureBatch:
         hold: every temporary a launch reads).  Nothing is synchronised once the plan of the batch shape exists."""
         import types
         import torch
-        from . import _native as nat
-        from .batch import _is_device_tensor, _stream_ptr, _wave_dtype_of
         clips, so, rates = self._inputs(waves, sample_offsets, rates)
         nat.require_device()
         B = len(so) - 1
@@ -555,7 +478,6 @@ class MixedRateFeatureBatch:
     def _finish(ctx):
         """Endpoints [B, 2] (samples of each clip's own rate, endpoint.py:64) and len0 to the host: the call's one
         synchronisation; afterwards the temporaries of the launches may go."""
-        from . import _native as nat
         plan = ctx.plan
         endpoints = np.zeros((plan.B, 2), dtype=np.int64)
         for g in plan.groups:
@@ -581,25 +503,18 @@ class MixedRateFeatureBatch:
         ``g.replay()`` -> (inp [max_len, B, 39], len0 [B] int32), on the device, valid after the current stream's work (no
         host synchronisation).  The sub-pipelines are queued one after the other on the capture stream: the graph is one
         chain, no forked branches.  One eager call runs first (it builds the layouts' long-lived index tables)."""
-        import torch
-        from .batch import _is_device_tensor
-        if not _is_device_tensor(waves):
-            raise TypeError('capture needs a device tensor')
-        if not waves.is_contiguous():
-            raise ValueError('capture needs a contiguous waves tensor: the graph reads it in place on every replay')
-        clips, so, rates = self._inputs(waves, sample_offsets, rates)
-        dev = waves.device
-        plan = _MixedPlan(self, so, rates, dev, True)          # the graph's own: nothing else writes its tables
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            warm = self._launch(waves, so, rates, plan=plan)
-        side.synchronize()
-        del warm
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=side):
-            ctx = self._launch(waves, so, rates, plan=plan)
-        return _MixedRateGraph(graph, waves, plan, ctx.inp, ctx.len0, ctx.hold)
+
+        def prepare():
+            _, so, r = self._inputs(waves, sample_offsets, rates)
+            plan = _MixedPlan(self, so, r, waves.device, True)     # the graph's own: nothing else writes its tables
+            hold = [plan]
+
+            def queue():
+                ctx = self._launch(waves, so, r, plan=plan)
+                hold[1:] = [ctx.hold]          # the captured call's temporaries (the warm call's go)
+                return ctx.inp, ctx.len0
+            return queue, hold
+        return _capture(waves, prepare)
 
 
 _DEFAULT_MIXED = None

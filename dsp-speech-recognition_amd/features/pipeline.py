@@ -41,8 +41,10 @@ class _WaveRef:
 
 
 class _TensorBuffer:
-    """Result rows held in a torch tensor (device-tensor inputs: torch's caching allocator instead of a
-    hipMalloc / hipFree pair per call); same surface as DeviceBuffer where the callers need it."""
+    """A torch tensor behind the surface of a ``nat.DeviceBuffer`` (``ptr``, ``nbytes``, ``wave``, ``download``, ``free``):
+    result rows of a device-tensor input (torch's caching allocator instead of a hipMalloc / hipFree pair per call), and
+    -- features/ensemble.py -- a layout's segment table, so that torch, inside a captured graph too, can copy what the
+    endpoint kernels write there."""
 
     def __init__(self, tensor):
         self.tensor = tensor
@@ -51,8 +53,13 @@ class _TensorBuffer:
         self.nbytes = tensor.numel() * tensor.element_size()
 
     def download(self, shape, dtype, stream=None):
-        n = int(np.prod(shape))
-        return self.tensor.reshape(-1)[:n].cpu().numpy().astype(dtype, copy=False).reshape(shape)
+        out = np.empty(shape, dtype=dtype)
+        assert out.nbytes <= self.nbytes, (out.nbytes, self.nbytes)
+        nat.check(nat.load().dsp_memcpy_d2h(out.ctypes.data, self.ptr, out.nbytes, stream))
+        return out
+
+    def free(self):
+        self.tensor = self.ptr = None
 
 
 class _DeviceLayout:
@@ -152,7 +159,7 @@ class VadMfccPipeline:
         """Queue the whole pipeline on `stream` (raw pointers, no host synchronisation, no allocation):
         features land in `d_out` ([lay.frames_bound, D] fp32, rows packed by lay.d_frame_off).
         ``defer_c0_shift`` (cepstra only, unit variance): the caller applies the -ln(var) of c0 itself
-        (dsp_model_finalize_segments_batch does, from the statistics in lay.d_work) -- then the clips are read in
+        (dsp_model_finalize_placed_batch does, given lay.d_seg and the statistics in lay.d_work) -- then the clips are read in
         place for delta_n = 0 as well and ``lay.c0_shift_pending`` says so; otherwise cepstra-only unit-variance
         output takes the trimmed, scaled copy."""
         lib = nat.load()

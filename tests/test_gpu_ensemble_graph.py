@@ -152,3 +152,5 @@ def test_mixed_rate_capture(env, monkeypatch):
         _compare('mixed_sync_free', free, mb.run(np.concatenate(clips_b), so, rates, dropout=False), 4)
     with pytest.raises(ValueError, match='contiguous'):
         mb.capture(torch.from_numpy(np.stack([np.concatenate(clips_a)] * 2, axis=1)).to(env.dev)[:, 0], so, rates, dropout=False)
+    with pytest.raises(TypeError, match='device tensor'):
+        mb.capture(np.concatenate(clips_a), so, rates, dropout=False)

@@ -367,6 +367,8 @@ def test_graph_replays_on_new_data(env):
             assert record('mixed_graph_vs_eager', normwise(inp[:, b].cpu().numpy(), eager[:, b].cpu().numpy())) <= 5e-5
     with pytest.raises(ValueError, match='contiguous'):
         mr.capture(_dev(env, np.stack([np.concatenate(clips_a)] * 2, axis=1))[:, 0], so, rates)
+    with pytest.raises(TypeError, match='device tensor'):
+        mr.capture(np.concatenate(clips_a), so, rates)
 
 
 # ---- 9: ensemble ----
