@@ -487,19 +487,19 @@ int vad_features_impl(const dsp_layout* layout, const void* d_wave, int wave_dty
     if (rc != DSP_OK) return rc;
     BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, frame_len, frame_step);
     hipStream_t st = (hipStream_t)stream;
-    const int tile = vad_tile_frames(frame_len, frame_step);
-    if (!g_force_generic && tile != 0) {
+    const VadRoute route = vad_route(frame_len, frame_step, wave_dtype, use_sq, g_force_generic != 0);   // what dsp_debug_vad_route returns
+    if (route.family != DSP_VAD_ROUTE_PER_FRAME) {
         BatchGeom fg = bg;
         const void* fw = d_wave;
         DspWorkspace* view = fused_kernel_view(fg, fw, wave_dtype, st);
-        const bool ok = vad_tile_applicable(fg, fw, wave_dtype, tile);
+        const bool ok = vad_tile_applicable(fg, fw, wave_dtype, route.fr);
         DspRaggedTables pre;
         const bool have_pre = layout != nullptr && layout->group_off != nullptr && view == nullptr;
         if (have_pre) {
             pre.shift = layout->shift; pre.group_off = layout->group_off; pre.group_utt = layout->group_utt;
             if (layout->group_off2 != nullptr) { pre.shift2 = 3; pre.group_off2 = layout->group_off2; pre.group_utt2 = layout->group_utt2; }
         }
-        if (ok) rc = vad_tile_launch(tile, frame_len, frame_step, use_sq, fg, fw, wave_dtype, d_amp_sum, d_zcr, st,
+        if (ok) rc = vad_tile_launch(route, frame_len, frame_step, use_sq, fg, fw, wave_dtype, d_amp_sum, d_zcr, st,
                                      have_pre ? &pre : nullptr);
         if (view && dsp_workspace_pool().release(view, st) != 0 && ok && rc == DSP_OK) rc = DSP_EHIP;
         if (ok) {
@@ -629,6 +629,14 @@ int dsp_abi_version(void) { return DSP_ABI_VERSION; }
 int dsp_debug_force_generic(int on) {
     g_force_generic = on ? 1 : 0;
     return DSP_OK;
+}
+
+int dsp_debug_vad_route(int32_t frame_len, int32_t frame_step, int wave_dtype, int32_t use_sq, int32_t* frames_per_wave) {
+    if (frame_len <= 0 || frame_step <= 0) return dsp_fail(DSP_EINVAL, "frame_len/frame_step must be > 0");
+    if (wave_dtype != DSP_WAVE_F32 && wave_dtype != DSP_WAVE_I16) return dsp_fail(DSP_EINVAL, "dsp_debug_vad_route: unknown wave_dtype %d", wave_dtype);
+    const VadRoute route = vad_route(frame_len, frame_step, wave_dtype, use_sq, g_force_generic != 0);   // what vad_features_impl switches on
+    if (frames_per_wave) *frames_per_wave = route.fr;
+    return route.family;
 }
 
 int dsp_debug_host_dry_run(int on) {
@@ -994,7 +1002,10 @@ int dsp_layout_create(const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_f
     *out = nullptr;
     if (!d_frame_offsets || n_utt <= 0 || n_frames_total <= 0 || frame_len <= 0 || frame_step <= 0)
         return dsp_fail(DSP_EINVAL, "dsp_layout_create: bad arguments");
-    const int tile = vad_tile_frames(frame_len, frame_step);
+    // the group sizes vad_route can answer for this framing: fp32 callers (and x^2) take `tile` frames per wave, int16 sums of |x|
+    // `tile` or eight (the handle serves every thread: dsp_debug_force_generic is not consulted, a forced call ignores the tables)
+    const VadRoute r32 = vad_route(frame_len, frame_step, DSP_WAVE_F32, 0, false);
+    const int tile = r32.family == DSP_VAD_ROUTE_PER_FRAME ? 0 : r32.fr;
     dsp_layout* l = new dsp_layout();
     memset(l, 0, sizeof(*l));
     l->n_utt = n_utt; l->frame_len = frame_len; l->frame_step = frame_step; l->n_frames_total = n_frames_total;
@@ -1003,7 +1014,7 @@ int dsp_layout_create(const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_f
         l->shift = tile == 16 ? 4 : 2;
         const int64_t bound = n_frames_total / tile + n_utt;
         if (bound > 0x3fffffff) { delete l; return dsp_fail(DSP_EINVAL, "dsp_layout_create: batch too large"); }
-        const bool second = vad_scan_frames8(frame_len, frame_step, DSP_WAVE_I16, 0);      // int16 callers take 8-frame groups
+        const bool second = vad_route(frame_len, frame_step, DSP_WAVE_I16, 0, false).fr == 8;      // int16 callers take 8-frame groups
         const int64_t bound2 = second ? n_frames_total / 8 + n_utt : 0;
         const size_t n1 = (size_t)n_utt + 1 + (size_t)bound, n2 = second ? (size_t)n_utt + 1 + (size_t)bound2 : 0;
         if (hipMalloc(reinterpret_cast<void**>(&l->group_off), (n1 + n2) * sizeof(int32_t)) != hipSuccess) {

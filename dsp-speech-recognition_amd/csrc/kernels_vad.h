@@ -519,9 +519,27 @@ static inline bool vad_scan_frames8(int32_t L, int32_t S, int dtype, int32_t use
     return (7 * (int64_t)S + L + 3) / 4 <= 64 * 20 && (3 * (int64_t)S + L + 3) / 4 + 1 <= 64 * VAD_NSTAGE;
 }
 
+// THE choice of kernel for a framing, sample type and use_sq: dsp_vad_features_batch switches on it (vad_features_impl,
+// vad_tile_launch, vad_tile_launch_k), dsp_layout_create sizes its tables by it and dsp_debug_vad_route returns it, so a test
+// that asserts the route asserts what runs.  `family` is a DSP_VAD_ROUTE_* code of include/dsp_frontend.h, `fr` the frames
+// one wave takes at a time (1: the one-wave-per-frame kernel).
+struct VadRoute {
+    int family, fr;
+};
+static inline VadRoute vad_route(int32_t L, int32_t S, int dtype, int32_t use_sq, bool force_generic) {
+    const int tile = force_generic ? 0 : vad_tile_frames(L, S);
+    if (tile == 0) return {DSP_VAD_ROUTE_PER_FRAME, 1};
+    // int16, sum |x|, any frame length and hop: integer partials and prefix sums
+    if (dtype == DSP_WAVE_I16 && !use_sq) return {DSP_VAD_ROUTE_SCAN, tile == 16 ? 16 : (vad_scan_frames8(L, S, dtype, use_sq) ? 8 : 4)};
+    // vector-aligned frames: the visit-once kernel, both input types
+    if ((L % 4) == 0 && (S % 4) == 0) return {DSP_VAD_ROUTE_SUM, tile};
+    // what is left walks every frame: float sum |x|, sum x^2 of either type
+    return {dtype == DSP_WAVE_F32 && !use_sq ? DSP_VAD_ROUTE_TILE_ABS : DSP_VAD_ROUTE_TILE_SQ, tile};
+}
+
 // (which batches the kernels can read: vad_tile_applicable, dsp_frontend.hip)
 template <int DTYPE, int FR, bool RAGGED>
-static int vad_tile_launch_k(const VadParams& P, const BatchGeom& bg, const void* d_wave, double* d_amp,
+static int vad_tile_launch_k(int family, const VadParams& P, const BatchGeom& bg, const void* d_wave, double* d_amp,
                              int32_t* d_zcr, int64_t groups_bound, hipStream_t st) {
     const size_t lds = (size_t)VAD_WAVES * P.wave_floats * sizeof(float);
     int64_t blocks = (groups_bound + VAD_WAVES - 1) / VAD_WAVES;
@@ -530,10 +548,11 @@ static int vad_tile_launch_k(const VadParams& P, const BatchGeom& bg, const void
         const int64_t rounds = (blocks + cap - 1) / cap;
         blocks = (blocks + rounds - 1) / rounds;
     }
-    if constexpr (DTYPE == DSP_WAVE_I16) {
-        // int16, sum |x|, any frame length and hop: integer partials and prefix sums (a vector's sum stays below 2^17, a
-        // group's below 2^27).  vad_tile_frames has seen to it that the span fits the staging rounds, and L >= 64.
-        if (!P.use_sq) {
+    switch (family) {
+    case DSP_VAD_ROUTE_SCAN:
+        // a vector's sum stays below 2^17, a group's below 2^27.  vad_tile_frames has seen to it that the span fits the
+        // staging rounds, and L >= 64.
+        if constexpr (DTYPE == DSP_WAVE_I16) {
             const size_t ldss = (size_t)VAD_WAVES * 2 * 64 * VAD_SCAN_CH * sizeof(int32_t);
             int64_t blockss = (groups_bound + VAD_WAVES - 1) / VAD_WAVES;
             const int64_t caps = (int64_t)dsp_cu_count() * 6;          // 24.6 KB per workgroup: six per CU
@@ -541,41 +560,45 @@ static int vad_tile_launch_k(const VadParams& P, const BatchGeom& bg, const void
             vad_scan_kernel<FR, RAGGED><<<(int)blockss, 64 * VAD_WAVES, ldss, st>>>(P, bg, static_cast<const int16_t*>(d_wave), d_amp, d_zcr);
             return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
         }
-    }
-    if ((P.L % 4) == 0 && (P.S % 4) == 0) {
-        // vector-aligned frames: visit-once kernel with 12 bytes of LDS per vector, both input types
+        return DSP_EINVAL;   // vad_route sends int16 here only
+    case DSP_VAD_ROUTE_SUM: {
+        // 12 bytes of LDS per vector
         VadParams Q = P;
         Q.span_vec = ((FR - 1) * P.S + P.L) / 4;
         Q.off_e = (int32_t)((((size_t)Q.span_vec * 8 + 15) / 16 * 16) / 4);       // floats
         Q.wave_floats = (int32_t)(((size_t)Q.off_e + Q.span_vec + 63) / 64 * 64);
-        if (Q.span_vec <= 64 * VAD_NSTAGE) {
-            const size_t lds3 = (size_t)VAD_WAVES * Q.wave_floats * sizeof(float);
-            int64_t blocks3 = (groups_bound + VAD_WAVES - 1) / VAD_WAVES;
-            int per_cu = (int)((size_t)(150 * 1024) / (lds3 ? lds3 : 1));
-            if (per_cu > 8) per_cu = 8;
-            if (per_cu < 1) per_cu = 1;
-            const int64_t cap3 = (int64_t)dsp_cu_count() * per_cu;
-            if (blocks3 > cap3) blocks3 = cap3;
-            auto k = vad_sum_kernel<DTYPE, FR, RAGGED, false>;
-            static size_t granted[DSP_MAX_DEVICES] = {};
-            if (lds3 > 48 * 1024 && dsp_ensure_dynamic_lds((const void*)k, lds3, granted) != 0) return DSP_EHIP;
-            k<<<(int)blocks3, 64 * VAD_WAVES, lds3, st>>>(Q, bg, d_wave, d_amp, d_zcr);
-            return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
-        }
+        // Cannot fail once vad_tile_frames has accepted the shape: it asked for ((FR - 1) S + L + 3) / 4 + 1 <= 64 VAD_NSTAGE,
+        // and with L and S multiples of 4 this span is that quotient itself, one below the limit at the most.
+        if (Q.span_vec > 64 * VAD_NSTAGE) return DSP_EINVAL;
+        const size_t lds3 = (size_t)VAD_WAVES * Q.wave_floats * sizeof(float);
+        int64_t blocks3 = (groups_bound + VAD_WAVES - 1) / VAD_WAVES;
+        int per_cu = (int)((size_t)(150 * 1024) / (lds3 ? lds3 : 1));
+        if (per_cu > 8) per_cu = 8;   // the largest resident-workgroup cap of this file (tests size their multi-round batches by it)
+        if (per_cu < 1) per_cu = 1;
+        const int64_t cap3 = (int64_t)dsp_cu_count() * per_cu;
+        if (blocks3 > cap3) blocks3 = cap3;
+        auto k = vad_sum_kernel<DTYPE, FR, RAGGED, false>;
+        static size_t granted[DSP_MAX_DEVICES] = {};
+        if (lds3 > 48 * 1024 && dsp_ensure_dynamic_lds((const void*)k, lds3, granted) != 0) return DSP_EHIP;
+        k<<<(int)blocks3, 64 * VAD_WAVES, lds3, st>>>(Q, bg, d_wave, d_amp, d_zcr);
+        return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
     }
-    // what is left walks every frame: sum x^2 of either type, float sum |x|
-    if constexpr (DTYPE == DSP_WAVE_F32) {
-        if (!P.use_sq) {
+    case DSP_VAD_ROUTE_TILE_ABS:
+        if constexpr (DTYPE == DSP_WAVE_F32) {
             vad_tile_kernel<DTYPE, FR, RAGGED, 1><<<(int)blocks, 64 * VAD_WAVES, lds, st>>>(P, bg, d_wave, d_amp, d_zcr);
             return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
         }
+        return DSP_EINVAL;   // vad_route sends fp32 here only
+    case DSP_VAD_ROUTE_TILE_SQ:
+        vad_tile_kernel<DTYPE, FR, RAGGED, 2><<<(int)blocks, 64 * VAD_WAVES, lds, st>>>(P, bg, d_wave, d_amp, d_zcr);
+        return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
+    default:
+        return DSP_EINVAL;
     }
-    vad_tile_kernel<DTYPE, FR, RAGGED, 2><<<(int)blocks, 64 * VAD_WAVES, lds, st>>>(P, bg, d_wave, d_amp, d_zcr);
-    return hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP;
 }
 
 template <int FR>
-static int vad_tile_launch_t(VadParams P, const BatchGeom& bg, const void* d_wave, int dtype, double* d_amp,
+static int vad_tile_launch_t(int family, VadParams P, const BatchGeom& bg, const void* d_wave, int dtype, double* d_amp,
                              int32_t* d_zcr, hipStream_t st, const DspRaggedTables* pre = nullptr) {
     P.span_vec = ((FR - 1) * P.S + P.L + 3) / 4;
     P.wave_floats = (4 * (P.span_vec + 1) + 63) / 64 * 64;
@@ -584,29 +607,31 @@ static int vad_tile_launch_t(VadParams P, const BatchGeom& bg, const void* d_wav
         P.groups_per_utt = (bg.uniform_frames + FR - 1) / FR;
         P.total_groups = P.groups_per_utt * bg.n_utt;
         return dsp_dispatch_wave(dtype, [&](auto dt) {
-            return vad_tile_launch_k<decltype(dt)::value, FR, false>(P, bg, d_wave, d_amp, d_zcr, P.total_groups, st);
+            return vad_tile_launch_k<decltype(dt)::value, FR, false>(family, P, bg, d_wave, d_amp, d_zcr, P.total_groups, st);
         });
     }
     const int64_t bound = bg.total_frames / FR + bg.n_utt;
     DspWorkspace* w;   // (prebuilt tables: those of a dsp_layout, built once per batch shape)
     if (!dsp_ragged_tables_acquire(P, pre, SHIFT, bg, bound, st, w)) return DSP_EHIP;
     const int rc = dsp_dispatch_wave(dtype, [&](auto dt) {
-        return vad_tile_launch_k<decltype(dt)::value, FR, true>(P, bg, d_wave, d_amp, d_zcr, bound, st);
+        return vad_tile_launch_k<decltype(dt)::value, FR, true>(family, P, bg, d_wave, d_amp, d_zcr, bound, st);
     });
     return dsp_ragged_tables_release(w, st, rc);
 }
 
-static inline int vad_tile_launch(int FR, int32_t L, int32_t S, int32_t use_sq, const BatchGeom& bg, const void* d_wave,
+// `route`: vad_route's answer for (L, S, dtype, use_sq), any family but the per-frame one
+static inline int vad_tile_launch(VadRoute route, int32_t L, int32_t S, int32_t use_sq, const BatchGeom& bg, const void* d_wave,
                                   int dtype, double* d_amp, int32_t* d_zcr, hipStream_t st,
                                   const DspRaggedTables* pre = nullptr) {
     VadParams P;
     memset(&P, 0, sizeof(P));
     P.L = L; P.S = S; P.use_sq = use_sq;
-    if (FR == 16) return vad_tile_launch_t<16>(P, bg, d_wave, dtype, d_amp, d_zcr, st, pre);
+    if (route.fr == 16) return vad_tile_launch_t<16>(route.family, P, bg, d_wave, dtype, d_amp, d_zcr, st, pre);
     // int16 clips whose 16-frame groups do not fit (44.1 kHz: 30 ms / 10 ms = 1323 / 441 samples): eight frames per wave
     // (1103 of 1280 staged vectors; 1200 at 48 kHz) instead of four -- 1.25 x instead of 1.5 x of the samples read, half the prefix-scan
     // work per frame: 23.4 vs 30.0 us per 69 MB (same-job A/B)
-    if (vad_scan_frames8(L, S, dtype, use_sq)) {
+    if (route.fr == 8) {
+        if (route.family != DSP_VAD_ROUTE_SCAN || dtype != DSP_WAVE_I16) return DSP_EINVAL;   // vad_route: the scan kernel alone
         P.span_vec = (int32_t)((7 * (int64_t)S + L + 3) / 4);
         const size_t ldss = (size_t)VAD_WAVES * 2 * 64 * 20 * sizeof(int32_t);     // CH = 20 dwords per lane and array
         const int64_t cap = (int64_t)dsp_cu_count() * 3;                             // 40 KB per workgroup: three per CU
@@ -626,5 +651,6 @@ static inline int vad_tile_launch(int FR, int32_t L, int32_t S, int32_t use_sq, 
         vad_scan_kernel<8, true><<<(int)blocks, 64 * VAD_WAVES, ldss, st>>>(P, bg, static_cast<const int16_t*>(d_wave), d_amp, d_zcr);
         return dsp_ragged_tables_release(w, st, hipGetLastError() == hipSuccess ? DSP_OK : DSP_EHIP);
     }
-    return vad_tile_launch_t<4>(P, bg, d_wave, dtype, d_amp, d_zcr, st, pre);
+    if (route.fr != 4) return DSP_EINVAL;
+    return vad_tile_launch_t<4>(route.family, P, bg, d_wave, dtype, d_amp, d_zcr, st, pre);
 }

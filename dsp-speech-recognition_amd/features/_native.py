@@ -20,6 +20,7 @@ WAVE_F32, WAVE_I16 = 0, 1
 OUT_FRAMES, OUT_MAGSPEC, OUT_POWSPEC, OUT_FBANK, OUT_MFCC = 0, 1, 2, 3, 4
 PLAN_ANY_NFFT = 1
 ROUTE_PASSES, ROUTE_MIXED, ROUTE_CHIRP = 0, 1, 2
+VAD_PER_FRAME, VAD_SCAN, VAD_SUM, VAD_TILE_ABS, VAD_TILE_SQ = 0, 1, 2, 3, 4     # dsp_debug_vad_route
 
 c_i32, c_i64, c_f32, c_f64, c_vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 
@@ -92,6 +93,7 @@ SIGNATURES = {
     'dsp_debug_pool_stats': (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     'dsp_debug_use_mfma512': (C.c_int, [C.c_int]),
     'dsp_debug_host_dry_run': (C.c_int, [C.c_int]),
+    'dsp_debug_vad_route': (C.c_int, [c_i32, c_i32, C.c_int, c_i32, C.POINTER(c_i32)]),
     'dsp_plan_has_mfma512': (C.c_int, [c_vp]),
     'dsp_preemphasis_batch': (C.c_int, [c_vp, C.c_int, c_vp, c_i32, c_i64, c_f32, c_vp, c_vp]),
     'dsp_features_batch': (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, c_i32, c_i64, c_i64, C.c_int,

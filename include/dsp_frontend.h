@@ -145,6 +145,19 @@ int dsp_debug_pool_stats(long long* n_buffers, long long* bytes);
    device -- for the sanitizer build (`make -C dsp-speech-recognition_amd/csrc asan`, tests/test_host_asan.py), which runs
    on a machine without a GPU.  Such a plan can only be destroyed; launches with it are refused. */
 int dsp_debug_host_dry_run(int on);
+/* testing aid: which kernel family dsp_vad_features_batch / dsp_vad_features_layout_batch launch for this framing, sample
+   type and use_sq on the calling thread -- the launcher switches on the very function this returns, so the answer cannot
+   drift from what runs.  Returns one of the codes below (or DSP_EINVAL for frame_len / frame_step < 1 or an unknown
+   wave_dtype) and writes the frames one wavefront takes at a time (1, 4, 8 or 16) to *frames_per_wave (may be NULL).
+   Touches no device.  Honours dsp_debug_force_generic.  A batch the vector kernels cannot read (more than 2^30 groups)
+   still takes the per-frame kernel; misaligned buffers and dense batches with N % 4 != 0 keep their route (they are
+   launched as ragged batches of an aligned buffer). */
+#define DSP_VAD_ROUTE_PER_FRAME 0 /* vad_features_kernel: one wavefront per frame, any framing */
+#define DSP_VAD_ROUTE_SCAN 1      /* vad_scan_kernel: int16, sum |x|, integer prefix sums */
+#define DSP_VAD_ROUTE_SUM 2       /* vad_sum_kernel: frame_len and frame_step multiples of 4 */
+#define DSP_VAD_ROUTE_TILE_ABS 3  /* vad_tile_kernel, fp64 sums of |x|: fp32 input */
+#define DSP_VAD_ROUTE_TILE_SQ 4   /* vad_tile_kernel, fp64 sums of x^2: either input */
+int dsp_debug_vad_route(int32_t frame_len, int32_t frame_step, int wave_dtype, int32_t use_sq, int32_t* frames_per_wave);
 
 /* ---- the hot path -------------------------------------------------------------------------- */
 /*
