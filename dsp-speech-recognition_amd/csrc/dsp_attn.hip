@@ -74,6 +74,30 @@ int attn_check_launch(const char* who, const dsp_attn* h) {
     return DSP_OK;
 }
 
+// The packed buffer of a handle: the 12 matrices as (source, K, N, stride of k, stride of n) -- the last six are the backward's,
+// each matrix of the forward the other way round -- and the 7 vectors as (source, n, padded n), with their offsets in floats.
+// What dsp_attn_create packs on the host and dsp_attn_refresh gathers on the device, into the same places.
+struct AttnMat { const float* src; int32_t K, N; int64_t sk, sn; };
+struct AttnVec { const float* src; int32_t n, np; };
+struct AttnLayout {
+    AttnMat mats[AT_PACK_MATS];
+    AttnVec vecs[AT_PACK_VECS];
+    size_t moff[AT_PACK_MATS], voff[AT_PACK_VECS], total;
+};
+
+void attn_layout(const float* const* p, int32_t d, int32_t di, int32_t dk, int32_t dv, AttnLayout& lay) {
+    const int32_t DP = at_pad16(d), IP = at_pad16(di);
+    const AttnMat mats[AT_PACK_MATS] = {{p[0], d, dk, dk, 1}, {p[1], dk, d, 1, dk}, {p[2], d, dv, dv, 1},
+                                        {p[5], dv, d, 1, dv}, {p[7], d, di, 1, d}, {p[9], di, d, 1, di},
+                                        {p[9], d, di, di, 1}, {p[7], di, d, d, 1}, {p[5], d, dv, dv, 1},
+                                        {p[2], dv, d, 1, dv}, {p[1], d, dk, dk, 1}, {p[0], dk, d, 1, dk}};
+    const AttnVec vecs[AT_PACK_VECS] = {{p[3], d, DP}, {p[4], d, DP}, {p[6], d, DP}, {p[8], di, IP}, {p[10], d, DP}, {p[11], d, DP}, {p[12], d, DP}};
+    size_t total = 0;
+    for (int i = 0; i < AT_PACK_MATS; ++i) { lay.mats[i] = mats[i]; lay.moff[i] = total; total += (size_t)at_pad16(mats[i].K) * at_pad16(mats[i].N); }
+    for (int i = 0; i < AT_PACK_VECS; ++i) { lay.vecs[i] = vecs[i]; lay.voff[i] = total; total += (size_t)vecs[i].np; }
+    lay.total = total;
+}
+
 }  // namespace
 
 extern "C" {
@@ -110,22 +134,15 @@ int dsp_attn_create(const dsp_attn_desc* desc, dsp_attn** out) {
         }
     }
     const int32_t DP = at_pad16(d), KP = at_pad16(dk), VP = at_pad16(dv), IP = at_pad16(di);
-    // matrices as (source, K, N, stride of k, stride of n), then vectors as (source, n, padded n)
-    struct Mat { const float* src; int32_t K, N; int64_t sk, sn; };
-    // (the last six are the backward's: each matrix of the forward the other way round)
-    constexpr int NM = 12;
-    const Mat mats[NM] = {{p[0], d, dk, dk, 1}, {p[1], dk, d, 1, dk}, {p[2], d, dv, dv, 1},
-                          {p[5], dv, d, 1, dv}, {p[7], d, di, 1, d}, {p[9], di, d, 1, di},
-                          {p[9], d, di, di, 1}, {p[7], di, d, d, 1}, {p[5], d, dv, dv, 1},
-                          {p[2], dv, d, 1, dv}, {p[1], d, dk, dk, 1}, {p[0], dk, d, 1, dk}};
-    struct Vec { const float* src; int32_t n, np; };
-    const Vec vecs[7] = {{p[3], d, DP}, {p[4], d, DP}, {p[6], d, DP}, {p[8], di, IP}, {p[10], d, DP}, {p[11], d, DP}, {p[12], d, DP}};
-    size_t moff[NM], voff[7], total = 0;
-    for (int i = 0; i < NM; ++i) { moff[i] = total; total += (size_t)at_pad16(mats[i].K) * at_pad16(mats[i].N); }
-    for (int i = 0; i < 7; ++i) { voff[i] = total; total += (size_t)vecs[i].np; }
+    AttnLayout lay;
+    attn_layout(p, d, di, dk, dv, lay);
+    const AttnMat* mats = lay.mats;
+    const AttnVec* vecs = lay.vecs;
+    const size_t *moff = lay.moff, *voff = lay.voff, total = lay.total;
+    constexpr int NM = AT_PACK_MATS;
     std::vector<float> blob(total, 0.f);
     for (int i = 0; i < NM; ++i) at_pack_host(blob.data() + moff[i], mats[i].src, mats[i].K, mats[i].N, mats[i].sk, mats[i].sn);
-    for (int i = 0; i < 7; ++i)
+    for (int i = 0; i < AT_PACK_VECS; ++i)
         for (int j = 0; j < vecs[i].n; ++j) blob[voff[i] + j] = vecs[i].src[j];
     void* tables = nullptr;
     const hipError_t e = dsp_table_alloc_copy(&tables, blob.data(), total * sizeof(float));
@@ -152,6 +169,35 @@ int dsp_attn_destroy(dsp_attn* h) {
     if (!h) return DSP_OK;
     dsp_table_free(h->d_packed, h->dry_run);
     delete h;
+    return DSP_OK;
+}
+
+int dsp_attn_refresh(dsp_attn* h, const dsp_attn_desc* desc, void* stream) {
+    const char* who = "dsp_attn_refresh";
+    if (!h || !desc) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
+    if (desc->n_head != 1 || desc->d_model != h->d || desc->d_inner != h->d_inner || desc->d_k != h->d_k || desc->d_v != h->d_v)
+        return dsp_fail(DSP_EINVAL, "%s: n_head %d, d_model %d, d_inner %d, d_k %d, d_v %d differ from the handle's 1, %d, %d, %d, %d", who,
+                        desc->n_head, desc->d_model, desc->d_inner, desc->d_k, desc->d_v, h->d, h->d_inner, h->d_k, h->d_v);
+    if (desc->eps != h->w.eps) return dsp_fail(DSP_EINVAL, "%s: eps differs from the handle's", who);
+    for (int i = 0; i < DSP_ATTN_PARAMS; ++i)
+        if (!desc->d_params[i]) return dsp_fail(DSP_EINVAL, "%s: NULL parameter tensor (index %d)", who, i);
+    if (int rc = attn_check_launch(who, h)) return rc;
+    AttnLayout lay;
+    attn_layout(desc->d_params, h->d, h->d_inner, h->d_k, h->d_v, lay);
+    AtPackJobs J;
+    int64_t most = 0;
+    for (int i = 0; i < AT_PACK_MATS; ++i) {
+        const AttnMat& m = lay.mats[i];
+        J.job[i] = AtPackJob{m.src, h->d_packed + lay.moff[i], m.K, m.N, m.sk, m.sn};
+        const int64_t n = (int64_t)at_pad16(m.K) * at_pad16(m.N);
+        most = n > most ? n : most;
+    }
+    for (int i = 0; i < AT_PACK_VECS; ++i) {     // K = 0 marks a vector: its n elements are copied, the zero padding behind them stays
+        J.job[AT_PACK_MATS + i] = AtPackJob{lay.vecs[i].src, h->d_packed + lay.voff[i], 0, lay.vecs[i].n, 0, 1};
+        most = lay.vecs[i].n > most ? lay.vecs[i].n : most;
+    }
+    attn_pack_kernel<<<dim3((unsigned)((most + 255) / 256), AT_PACK_MATS + AT_PACK_VECS), 256, 0, (hipStream_t)stream>>>(J);
+    HIP_TRY(hipGetLastError());
     return DSP_OK;
 }
 
@@ -312,10 +358,20 @@ int dsp_selfattn_pool_train_batch(const float* d_y, int32_t T, int32_t B, int32_
     return selfattn_pool(who, d_y, T, B, H, d_W, d_bW, d_v, d_c, d_out, d_w, nullptr, stream);
 }
 
-int dsp_selfattn_pool_backward_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
-                                     const float* d_w, const float* d_gout, float* d_gy, float* d_gpre, float* d_ge, float* d_gvpart,
-                                     void* stream) {
-    const char* who = "dsp_selfattn_pool_backward_batch";
+int dsp_selfattn_pool_rows_train_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW,
+                                       const float* d_v, const float* d_c, float* d_out, float* d_w, const int32_t* d_rows, void* stream) {
+    const char* who = "dsp_selfattn_pool_rows_train_batch";
+    if (!d_w || !d_rows) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
+    return selfattn_pool(who, d_y, T, B, H, d_W, d_bW, d_v, d_c, d_out, d_w, d_rows, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+int selfattn_pool_backward(const char* who, const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW,
+                           const float* d_v, const float* d_w, const float* d_gout, float* d_gy, float* d_gpre, float* d_ge, float* d_gvpart,
+                           const int32_t* d_rows, void* stream) {
     if (!d_y || !d_W || !d_bW || !d_v || !d_w || !d_gout || !d_gpre || !d_ge || !d_gvpart) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
     if (T < 1 || T > AT_MAX_T) return dsp_fail(DSP_EINVAL, "%s: T %d must be in [1, %d]", who, T, AT_MAX_T);
     if (B < 1) return dsp_fail(DSP_EINVAL, "%s: B %d must be >= 1", who, B);
@@ -323,9 +379,28 @@ int dsp_selfattn_pool_backward_batch(const float* d_y, int32_t T, int32_t B, int
     if (((reinterpret_cast<uintptr_t>(d_y) | reinterpret_cast<uintptr_t>(d_W) | reinterpret_cast<uintptr_t>(d_gout)) & 15) != 0)
         return dsp_fail(DSP_EINVAL, "%s: d_y, d_W and d_gout must be 16-byte aligned", who);
     if (int rc = attn_check_launch(who, nullptr)) return rc;
-    selfattn_pool_bwd_kernel<<<B, 64, 0, (hipStream_t)stream>>>(d_y, T, B, H, d_W, d_bW, d_v, d_w, d_gout, d_gy, d_gpre, d_ge, d_gvpart);
+    selfattn_pool_bwd_kernel<<<B, 64, 0, (hipStream_t)stream>>>(d_y, T, B, H, d_W, d_bW, d_v, d_w, d_gout, d_gy, d_gpre, d_ge, d_gvpart, d_rows);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dsp_selfattn_pool_backward_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW, const float* d_v,
+                                     const float* d_w, const float* d_gout, float* d_gy, float* d_gpre, float* d_ge, float* d_gvpart,
+                                     void* stream) {
+    return selfattn_pool_backward("dsp_selfattn_pool_backward_batch", d_y, T, B, H, d_W, d_bW, d_v, d_w, d_gout, d_gy, d_gpre, d_ge, d_gvpart,
+                                  nullptr, stream);
+}
+
+int dsp_selfattn_pool_rows_backward_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW,
+                                          const float* d_v, const float* d_w, const float* d_gout, float* d_gy, float* d_gpre, float* d_ge,
+                                          float* d_gvpart, const int32_t* d_rows, void* stream) {
+    const char* who = "dsp_selfattn_pool_rows_backward_batch";
+    if (!d_rows) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
+    return selfattn_pool_backward(who, d_y, T, B, H, d_W, d_bW, d_v, d_w, d_gout, d_gy, d_gpre, d_ge, d_gvpart, d_rows, stream);
 }
 
 }  // extern "C"

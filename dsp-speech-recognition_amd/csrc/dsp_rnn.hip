@@ -98,6 +98,82 @@ struct RnnPacked {
 
 inline int pack_blocks(int64_t n) { return (int)((n + 255) / 256); }
 
+// Where the pieces of a handle's packed buffer lie, and the pack launches that fill them: what create runs on stream 0 and
+// refresh on the caller's stream, into the same places.
+struct HmSeg { const float* src; int32_t H, K; };
+struct HmLayout {
+    HmSeg segs[5], tsegs[4];       // (source, H of the cell, K) in packing order; the transposed copies of the backward recurrence
+    size_t off[5], boff[2], toff[4];
+};
+inline int64_t hm_seg_floats(const HmSeg& s) { return (int64_t)hm_kgroups(s.K) * hm_tiles(s.H) * 256; }
+
+void hmlstm_layout(const dsp_hmlstm_desc* d, RnnPacked& pk, HmLayout& lay) {
+    const int32_t I = d->input_size, H1 = d->hidden1, H2 = d->hidden2;
+    const HmSeg segs[5] = {{d->d_c1_W01, H1, I}, {d->d_c1_U21, H1, H2}, {d->d_c1_U11, H1, H1}, {d->d_c2_W01, H2, H1}, {d->d_c2_U11, H2, H2}};
+    // the transposed copies of the backward recurrence: (source, H of the cell, columns = hidden index of the product)
+    const HmSeg tsegs[4] = {{d->d_c2_U11, H2, H2}, {d->d_c2_W01, H2, H1}, {d->d_c1_U21, H1, H2}, {d->d_c1_U11, H1, H1}};
+    for (int i = 0; i < 5; ++i) { lay.segs[i] = segs[i]; lay.off[i] = pk.reserve((size_t)hm_seg_floats(segs[i])); }
+    lay.boff[0] = pk.reserve((size_t)hm_tiles(H1) * 16);
+    lay.boff[1] = pk.reserve((size_t)hm_tiles(H2) * 16);
+    for (int i = 0; i < 4; ++i) { lay.tsegs[i] = tsegs[i]; lay.toff[i] = pk.reserve((size_t)hm_bwd_packed_floats(tsegs[i].H, tsegs[i].K)); }
+}
+
+void hmlstm_pack(const dsp_hmlstm_desc* d, const HmLayout& lay, RnnPacked& pk, float* buf, hipStream_t st) {
+    const int32_t H1 = d->hidden1, H2 = d->hidden2;
+    for (int i = 0; i < 5; ++i)
+        pk.run([&] {
+            const HmSeg& g = lay.segs[i];
+            hm_pack_kernel<<<pack_blocks(hm_seg_floats(g)), 256, 0, st>>>(g.src, g.H, g.K, hm_kgroups(g.K), buf + lay.off[i]);
+        });
+    pk.run([&] { hm_pack_bias_kernel<<<pack_blocks(hm_tiles(H1) * 16), 256, 0, st>>>(d->d_c1_bias, H1, buf + lay.boff[0]); });
+    pk.run([&] { hm_pack_bias_kernel<<<pack_blocks(hm_tiles(H2) * 16), 256, 0, st>>>(d->d_c2_bias, H2, buf + lay.boff[1]); });
+    for (int i = 0; i < 4; ++i)
+        pk.run([&] {
+            const HmSeg& g = lay.tsegs[i];
+            hm_pack_t_kernel<<<pack_blocks(hm_bwd_packed_floats(g.H, g.K)), 256, 0, st>>>(g.src, g.H, g.K, HM_WAVES * hm_bwd_chunks(g.K),
+                                                                                         buf + lay.toff[i]);
+        });
+}
+
+struct GruLayout {
+    size_t woff[GRU_MAX_LAYERS][2], boff[GRU_MAX_LAYERS][2], toff[GRU_MAX_LAYERS][2];
+    int32_t ngx[GRU_MAX_LAYERS], ng[GRU_MAX_LAYERS];
+};
+
+void bigru_layout(int32_t I, int32_t H, int32_t L, RnnPacked& pk, GruLayout& lay) {
+    const int32_t nt = H / 4;
+    for (int l = 0; l < L; ++l) {
+        lay.ngx[l] = hm_kgroups(l == 0 ? I : 2 * H);
+        lay.ng[l] = lay.ngx[l] + hm_kgroups(H);
+        for (int dr = 0; dr < 2; ++dr) lay.woff[l][dr] = pk.reserve((size_t)lay.ng[l] * nt * 256);
+    }
+    for (int l = 0; l < L; ++l)
+        for (int dr = 0; dr < 2; ++dr) lay.boff[l][dr] = pk.reserve((size_t)4 * H);
+    for (int l = 0; l < L; ++l)       // the transposed copies of the backward recurrence
+        for (int dr = 0; dr < 2; ++dr) lay.toff[l][dr] = pk.reserve((size_t)gru_bwd_packed_floats(H));
+}
+
+void bigru_pack(const dsp_bigru_desc* d, int32_t I, int32_t H, int32_t L, const GruLayout& lay, RnnPacked& pk, float* buf, hipStream_t st) {
+    const int32_t nt = H / 4;
+    for (int l = 0; l < L; ++l)
+        for (int dr = 0; dr < 2; ++dr)
+            pk.run([&] {
+                const float* const* p = d->d_params + 8 * l + 4 * dr;      // weight_ih, weight_hh, bias_ih, bias_hh
+                gru_pack_kernel<<<pack_blocks((int64_t)lay.ng[l] * nt * 256), 256, 0, st>>>(p[0], p[1], H, l == 0 ? I : 2 * H, lay.ngx[l], lay.ng[l],
+                                                                                          buf + lay.woff[l][dr]);
+                gru_pack_bias_kernel<<<pack_blocks(4 * H), 256, 0, st>>>(p[2], p[3], H, buf + lay.boff[l][dr]);
+                gru_pack_t_kernel<<<pack_blocks(gru_bwd_packed_floats(H)), 256, 0, st>>>(p[1], H, HM_WAVES * hm_bwd_chunks(H), buf + lay.toff[l][dr]);
+            });
+}
+
+// dsp_*_refresh launches on the handle's device only.
+int rnn_check_refresh(const char* who, int device) {
+    int dev = -1;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev != device) return dsp_fail(DSP_EINVAL, "%s: the handle belongs to device %d, current device is %d", who, device, dev);
+    return DSP_OK;
+}
+
 template <class H>
 int rnn_destroy(const char* who, H* h) {
     if (!h) return DSP_OK;
@@ -173,40 +249,40 @@ int dsp_hmlstm_create(const dsp_hmlstm_desc* d, dsp_hmlstm** out) {
     const int32_t I = d->input_size, H1 = d->hidden1, H2 = d->hidden2;
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    // segments in packing order: (source, H of the cell, K)
-    struct Seg { const float* src; int32_t H, K; };
-    const Seg segs[5] = {{d->d_c1_W01, H1, I}, {d->d_c1_U21, H1, H2}, {d->d_c1_U11, H1, H1}, {d->d_c2_W01, H2, H1}, {d->d_c2_U11, H2, H2}};
-    // the transposed copies of the backward recurrence: (source, H of the cell, columns = hidden index of the product)
-    const Seg tsegs[4] = {{d->d_c2_U11, H2, H2}, {d->d_c2_W01, H2, H1}, {d->d_c1_U21, H1, H2}, {d->d_c1_U11, H1, H1}};
-    auto seg_floats = [](const Seg& s) { return (int64_t)hm_kgroups(s.K) * hm_tiles(s.H) * 256; };
     RnnPacked pk;
-    size_t off[5], boff[2], toff[4];
-    for (int i = 0; i < 5; ++i) off[i] = pk.reserve((size_t)seg_floats(segs[i]));
-    boff[0] = pk.reserve((size_t)hm_tiles(H1) * 16);
-    boff[1] = pk.reserve((size_t)hm_tiles(H2) * 16);
-    for (int i = 0; i < 4; ++i) toff[i] = pk.reserve((size_t)hm_bwd_packed_floats(tsegs[i].H, tsegs[i].K));
+    HmLayout lay;
+    hmlstm_layout(d, pk, lay);
     if (int rc = pk.alloc()) return rc;
     float* buf = pk.buf;
-    for (int i = 0; i < 5; ++i)
-        pk.run([&] { hm_pack_kernel<<<pack_blocks(seg_floats(segs[i])), 256, 0, 0>>>(segs[i].src, segs[i].H, segs[i].K, hm_kgroups(segs[i].K), buf + off[i]); });
-    pk.run([&] { hm_pack_bias_kernel<<<pack_blocks(hm_tiles(H1) * 16), 256, 0, 0>>>(d->d_c1_bias, H1, buf + boff[0]); });
-    pk.run([&] { hm_pack_bias_kernel<<<pack_blocks(hm_tiles(H2) * 16), 256, 0, 0>>>(d->d_c2_bias, H2, buf + boff[1]); });
-    for (int i = 0; i < 4; ++i)
-        pk.run([&] {
-            hm_pack_t_kernel<<<pack_blocks(hm_bwd_packed_floats(tsegs[i].H, tsegs[i].K)), 256, 0, 0>>>(
-                tsegs[i].src, tsegs[i].H, tsegs[i].K, HM_WAVES * hm_bwd_chunks(tsegs[i].K), buf + toff[i]);
-        });
+    hmlstm_pack(d, lay, pk, buf, 0);
     if (int rc = pk.finish("dsp_hmlstm_create")) return rc;
     dsp_hmlstm* h = new dsp_hmlstm();
     h->I = I; h->H1 = H1; h->H2 = H2; h->d_packed = buf; h->device = dev;
-    h->c1 = HmCell{{pk.f4(off[0]), pk.f4(off[1]), pk.f4(off[2])}, buf + boff[0], {hm_kgroups(I), hm_kgroups(H2), hm_kgroups(H1)}, H1, hm_tiles(H1)};
-    h->c2 = HmCell{{pk.f4(off[3]), nullptr, pk.f4(off[4])}, buf + boff[1], {hm_kgroups(H1), 0, hm_kgroups(H2)}, H2, hm_tiles(H2)};
-    for (int i = 0; i < 4; ++i) h->wt[i] = pk.f4(toff[i]);
+    h->c1 = HmCell{{pk.f4(lay.off[0]), pk.f4(lay.off[1]), pk.f4(lay.off[2])}, buf + lay.boff[0], {hm_kgroups(I), hm_kgroups(H2), hm_kgroups(H1)}, H1, hm_tiles(H1)};
+    h->c2 = HmCell{{pk.f4(lay.off[3]), nullptr, pk.f4(lay.off[4])}, buf + lay.boff[1], {hm_kgroups(H1), 0, hm_kgroups(H2)}, H2, hm_tiles(H2)};
+    for (int i = 0; i < 4; ++i) h->wt[i] = pk.f4(lay.toff[i]);
     *out = h;
     return DSP_OK;
 }
 
 int dsp_hmlstm_destroy(dsp_hmlstm* h) { return rnn_destroy("dsp_hmlstm_destroy", h); }
+
+int dsp_hmlstm_refresh(dsp_hmlstm* h, const dsp_hmlstm_desc* d, void* stream) {
+    const char* who = "dsp_hmlstm_refresh";
+    if (!h || !d) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
+    if (d->input_size != h->I || d->hidden1 != h->H1 || d->hidden2 != h->H2)
+        return dsp_fail(DSP_EINVAL, "%s: input_size %d, hidden1 %d, hidden2 %d differ from the handle's %d, %d, %d", who, d->input_size,
+                        d->hidden1, d->hidden2, h->I, h->H1, h->H2);
+    if (!d->d_c1_U11 || !d->d_c1_U21 || !d->d_c1_W01 || !d->d_c1_bias || !d->d_c2_U11 || !d->d_c2_W01 || !d->d_c2_bias)
+        return dsp_fail(DSP_EINVAL, "%s: NULL parameter tensor", who);
+    if (int rc = rnn_check_refresh(who, h->device)) return rc;
+    RnnPacked pk;
+    HmLayout lay;
+    hmlstm_layout(d, pk, lay);
+    hmlstm_pack(d, lay, pk, h->d_packed, (hipStream_t)stream);
+    if (pk.err != hipSuccess) return dsp_fail(DSP_EHIP, "%s: %s", who, hipGetErrorString(pk.err));
+    return DSP_OK;
+}
 
 int dsp_hmlstm_forward(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
                        const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1, uint8_t* d_z2,
@@ -272,37 +348,20 @@ int dsp_bigru_create(const dsp_bigru_desc* d, dsp_bigru** out) {
         if (!d->d_params[i]) return dsp_fail(DSP_EINVAL, "dsp_bigru_create: NULL parameter tensor (index %d)", i);
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    const int32_t nt = H / 4;
     RnnPacked pk;
-    size_t woff[GRU_MAX_LAYERS][2], boff[GRU_MAX_LAYERS][2], toff[GRU_MAX_LAYERS][2];
-    int32_t ngx[GRU_MAX_LAYERS], ng[GRU_MAX_LAYERS];
-    for (int l = 0; l < L; ++l) {
-        ngx[l] = hm_kgroups(l == 0 ? I : 2 * H);
-        ng[l] = ngx[l] + hm_kgroups(H);
-        for (int dr = 0; dr < 2; ++dr) woff[l][dr] = pk.reserve((size_t)ng[l] * nt * 256);
-    }
-    for (int l = 0; l < L; ++l)
-        for (int dr = 0; dr < 2; ++dr) boff[l][dr] = pk.reserve((size_t)4 * H);
-    for (int l = 0; l < L; ++l)       // the transposed copies of the backward recurrence
-        for (int dr = 0; dr < 2; ++dr) toff[l][dr] = pk.reserve((size_t)gru_bwd_packed_floats(H));
+    GruLayout lay;
+    bigru_layout(I, H, L, pk, lay);
     if (int rc = pk.alloc()) return rc;
     float* buf = pk.buf;
-    for (int l = 0; l < L; ++l)
-        for (int dr = 0; dr < 2; ++dr)
-            pk.run([&] {
-                const float* const* p = d->d_params + 8 * l + 4 * dr;      // weight_ih, weight_hh, bias_ih, bias_hh
-                gru_pack_kernel<<<pack_blocks((int64_t)ng[l] * nt * 256), 256, 0, 0>>>(p[0], p[1], H, l == 0 ? I : 2 * H, ngx[l], ng[l], buf + woff[l][dr]);
-                gru_pack_bias_kernel<<<pack_blocks(4 * H), 256, 0, 0>>>(p[2], p[3], H, buf + boff[l][dr]);
-                gru_pack_t_kernel<<<pack_blocks(gru_bwd_packed_floats(H)), 256, 0, 0>>>(p[1], H, HM_WAVES * hm_bwd_chunks(H), buf + toff[l][dr]);
-            });
+    bigru_pack(d, I, H, L, lay, pk, buf, 0);
     if (int rc = pk.finish("dsp_bigru_create")) return rc;
     dsp_bigru* h = new dsp_bigru();
     h->I = I; h->H = H; h->L = L; h->d_packed = buf; h->device = dev;
     for (int l = 0; l < L; ++l) {
-        h->ngx[l] = ngx[l]; h->ng[l] = ng[l];
+        h->ngx[l] = lay.ngx[l]; h->ng[l] = lay.ng[l];
         for (int dr = 0; dr < 2; ++dr) {
-            h->dir[l][dr] = GruDir{pk.f4(woff[l][dr]), buf + boff[l][dr]};
-            h->wt[l][dr] = pk.f4(toff[l][dr]);
+            h->dir[l][dr] = GruDir{pk.f4(lay.woff[l][dr]), buf + lay.boff[l][dr]};
+            h->wt[l][dr] = pk.f4(lay.toff[l][dr]);
         }
     }
     *out = h;
@@ -310,6 +369,23 @@ int dsp_bigru_create(const dsp_bigru_desc* d, dsp_bigru** out) {
 }
 
 int dsp_bigru_destroy(dsp_bigru* h) { return rnn_destroy("dsp_bigru_destroy", h); }
+
+int dsp_bigru_refresh(dsp_bigru* h, const dsp_bigru_desc* d, void* stream) {
+    const char* who = "dsp_bigru_refresh";
+    if (!h || !d) return dsp_fail(DSP_EINVAL, "%s: NULL argument", who);
+    if (d->input_size != h->I || d->hidden != h->H || d->n_layers != h->L)
+        return dsp_fail(DSP_EINVAL, "%s: input_size %d, hidden %d, n_layers %d differ from the handle's %d, %d, %d", who, d->input_size,
+                        d->hidden, d->n_layers, h->I, h->H, h->L);
+    for (int i = 0; i < 8 * h->L; ++i)
+        if (!d->d_params[i]) return dsp_fail(DSP_EINVAL, "%s: NULL parameter tensor (index %d)", who, i);
+    if (int rc = rnn_check_refresh(who, h->device)) return rc;
+    RnnPacked pk;
+    GruLayout lay;
+    bigru_layout(h->I, h->H, h->L, pk, lay);
+    bigru_pack(d, h->I, h->H, h->L, lay, pk, h->d_packed, (hipStream_t)stream);
+    if (pk.err != hipSuccess) return dsp_fail(DSP_EHIP, "%s: %s", who, hipGetErrorString(pk.err));
+    return DSP_OK;
+}
 
 int dsp_bigru_workspace_bytes(const dsp_bigru* h, int32_t T, int32_t B, int64_t* bytes) {
     if (!h || !bytes) return dsp_fail(DSP_EINVAL, "dsp_bigru_workspace_bytes: NULL argument");

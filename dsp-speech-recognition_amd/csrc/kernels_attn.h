@@ -287,6 +287,28 @@ static inline void at_pack_host(float* dst, const float* src, int K, int N, int6
                 }
 }
 
+// at_pack_host on the device (dsp_attn_refresh): one launch gathers the 12 matrices and 7 vectors of a handle into the packed
+// buffer it already has.  blockIdx.y picks the job; a thread owns one float of the padded tile layout (K > 0) or one element of
+// a vector (K == 0: dst[n] = src[n], the padding behind is left as create wrote it).  Pure data movement: the same bytes.
+constexpr int AT_PACK_MATS = 12, AT_PACK_VECS = 7;
+struct AtPackJob { const float* src; float* dst; int32_t K, N; int64_t sk, sn; };
+struct AtPackJobs { AtPackJob job[AT_PACK_MATS + AT_PACK_VECS]; };
+
+__global__ __launch_bounds__(256) void attn_pack_kernel(const AtPackJobs J) {
+    const AtPackJob& j = J.job[blockIdx.y];
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j.K == 0) {
+        if (idx < j.N) j.dst[idx] = j.src[idx];
+        return;
+    }
+    const int ng = (j.K + 15) >> 4, nt = (j.N + 15) >> 4;
+    if (idx >=(int64_t)ng * nt * 256) return;
+    const int e = (int)(idx & 3), l = (int)((idx >> 2) & 63);
+    const int tile = (int)(idx >> 8), g = tile / nt, t = tile - g * nt;
+    const int k = 16 * g + 4 * (l >> 4) + e, n = 16 * t + (l & 15);
+    j.dst[idx] = (k < j.K && n < j.N) ? j.src[k * j.sk + n * j.sn] : 0.f;
+}
+
 // layers.SelfAttn for column b: e[t] = v . tanh(W y[t, b] + b_W) + c over all T rows, softmax over t, out[b] = sum_t w[t] y[t, b].
 // One wave per column (d_rows: over the first min(*d_rows, T) rows only).  W [H, H] and y are read in place: row n of W is the B operand's column n (K = the input index), a
 // float4 per lane and k-group; H is a multiple of 4, so a float4 lies inside the row or behind it.
@@ -299,6 +321,7 @@ __global__ __launch_bounds__(64) void selfattn_pool_kernel(const float* __restri
     const int lane = threadIdx.x, b = blockIdx.x;
     // dsp_selfattn_pool_rows_batch: only the first *d_rows rows of the buffer exist for the softmax (one wave-uniform read; T,
     // the buffer's row count, stays the bound of every loop below)
+    const int Tbuf = T;
     if (d_rows != nullptr) T = max(1, min(d_rows[0], T));
     const int ng = (H + 15) >> 4, nt = ng;
     const int r0 = 4 * (lane >> 4), c0 = lane & 15;
@@ -358,8 +381,8 @@ __global__ __launch_bounds__(64) void selfattn_pool_kernel(const float* __restri
     __syncthreads();
     for (int t = lane; t < T; t += 64) e[t] = expf(e[t] - mx) / sum;
     __syncthreads();
-    if (wsave != nullptr)
-        for (int t = lane; t < T; t += 64) wsave[(int64_t)t * B + b] = e[t];
+    if (wsave != nullptr)                                   // (dsp_selfattn_pool_rows_train_batch: exact zeros behind the row count)
+        for (int t = lane; t < Tbuf; t += 64) wsave[(int64_t)t * B + b] = t < T ? e[t] : 0.f;
     for (int h = lane; h < H; h += 64) {
         float s = 0.f;
         for (int t = 0; t < T; ++t) s += e[t] * y[((int64_t)t * B + b) * H + h];

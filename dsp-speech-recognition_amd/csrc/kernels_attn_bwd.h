@@ -386,10 +386,15 @@ __global__ __launch_bounds__(64) void selfattn_pool_bwd_kernel(const float* __re
                                                                const float* __restrict__ bW, const float* __restrict__ v,
                                                                const float* __restrict__ wsv, const float* __restrict__ gout,
                                                                float* __restrict__ gy, float* __restrict__ gpre, float* __restrict__ ge_out,
-                                                               float* __restrict__ gvp_out) {
+                                                               float* __restrict__ gvp_out,
+                                                               const int32_t* __restrict__ d_rows /* the row count on the device; or NULL */) {
     __shared__ float ws[AT_MAX_T], ge[AT_MAX_T], gvp[AT_MAX_H];
     __shared__ __attribute__((aligned(16))) float gp[16 * AT_SB];
     const int lane = threadIdx.x, b = blockIdx.x;
+    // dsp_selfattn_pool_rows_backward_batch: the first *d_rows rows of the buffers are the block (one wave-uniform read); the
+    // rows behind them are written as zeros at the end
+    const int Tbuf = T;
+    if (d_rows != nullptr) T = max(1, min(d_rows[0], T));
     const int ng = (H + 15) >> 4, nt = ng, HP = ng << 4;
     const int r0 = 4 * (lane >> 4), c0 = lane & 15;
     const int TP = (T + 15) & ~15;
@@ -503,5 +508,12 @@ __global__ __launch_bounds__(64) void selfattn_pool_bwd_kernel(const float* __re
         __syncthreads();
     }
     for (int h = lane; h < H; h += 64) gvp_out[(int64_t)b * H + h] = gvp[h];
+    for (int t = T; t < Tbuf; ++t) {
+        for (int h = lane; h < H; h += 64) {
+            gpre[((int64_t)t * B + b) * H + h] = 0.f;
+            if (gy != nullptr) gy[((int64_t)t * B + b) * H + h] = 0.f;
+        }
+        if (lane == 0) ge_out[(int64_t)t * B + b] = 0.f;
+    }
     (void)HP;
 }

@@ -173,6 +173,14 @@ SIGNATURES = {
     'dsp_attn_backward': (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     'dsp_selfattn_pool_train_batch': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'dsp_selfattn_pool_backward_batch': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'dsp_head_pool_train_batch': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    'dsp_head_pool_backward_batch': (C.c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    'dsp_selfattn_pool_rows_train_batch': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'dsp_selfattn_pool_rows_backward_batch': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                        c_vp, c_vp]),
+    'dsp_bigru_refresh': (C.c_int, [c_vp, C.POINTER(BigruDesc), c_vp]),
+    'dsp_hmlstm_refresh': (C.c_int, [c_vp, C.POINTER(HmlstmDesc), c_vp]),
+    'dsp_attn_refresh': (C.c_int, [c_vp, C.POINTER(AttnDesc), c_vp]),
 }
 
 _lib = None

@@ -28,7 +28,12 @@ torch chains whenever a gradient is required, unless ``native_train_default`` is
 end leaves there): the row counts come from ``dsp_head_lengths_batch``, the encoders run over all ``inp.shape[0]`` rows with the
 lengths read in place, and the two places that need max(len0) -- the pooling and ``_SelfAttn``'s softmax -- read it from device
 memory (``dsp_head_pool_batch``, ``dsp_selfattn_pool_rows_batch``; csrc/kernels_head.h).  Nothing reads device memory from the
-host, so the call can be captured in a HIP graph.  Forward only, every stage native.
+host, so the call can be captured in a HIP graph.  Forward only, every stage native -- unless ``device_grad=True`` is given as
+well: a required gradient is then served on the same path, still without a host round trip.  The encoders take their native
+training paths over all ``inp.shape[0]`` rows with the lengths read in place, the pooling and ``_SelfAttn`` get their
+backward from ``dsp_head_pool_train_batch`` / ``dsp_head_pool_backward_batch`` and the ``dsp_selfattn_pool_rows_*`` pair, and the
+native handles are repacked in place after an optimiser step (``dsp_*_refresh``) instead of destroyed and rebuilt, so a whole
+training step -- refresh, forward, loss, backward -- can be captured too (features/train.py: ``TrainBatch``).
 """
 import numpy as np
 import torch
@@ -44,15 +49,25 @@ def _ptr(t):
     return None if t is None else t.data_ptr()      # an optional tensor: None is a NULL argument
 
 
-def _check_device_len(who, inp, len0, module):
-    """The conditions of ``device_len=True``: lengths as a [B] int32 tensor on ``inp``'s device, no gradient required."""
+def _check_device_grad(who, device_len, device_grad):
+    """``device_grad=True`` is the training form of ``device_len=True`` and means nothing without it."""
+    if device_grad and not device_len:
+        raise ValueError(f'{who}: device_grad=True needs device_len=True (it is the training form of the device-length path)')
+
+
+def _check_device_len(who, inp, len0, module, device_grad=False):
+    """The conditions of ``device_len=True``: lengths as a [B] int32 tensor on ``inp``'s device, and no gradient required
+    unless ``device_grad`` is given.  -> whether a gradient is required."""
     if not torch.is_tensor(inp) or not inp.is_cuda:
         raise RuntimeError(f'{who}: device_len=True cannot run: the input is not on a GPU')
     if not (torch.is_tensor(len0) and len0.dtype == torch.int32 and len0.dim() == 1 and len0.shape[0] == inp.shape[1]
             and len0.device == inp.device):
         raise TypeError(f"{who}: device_len=True needs len0 as a [B] int32 tensor on the input's device")
-    if torch.is_grad_enabled() and (inp.requires_grad or any(p.requires_grad for p in module.parameters())):
-        raise RuntimeError(f'{who}: device_len=True cannot run: a gradient is required (the device-length path is forward only)')
+    needs_grad = torch.is_grad_enabled() and (inp.requires_grad or any(p.requires_grad for p in module.parameters()))
+    if needs_grad and not device_grad:
+        raise RuntimeError(f'{who}: device_len=True cannot run: a gradient is required (the device-length path is forward only '
+                           'unless device_grad=True is given)')
+    return needs_grad
 
 
 def head_length_info(len0, T, hir):
@@ -73,10 +88,13 @@ def head_length_info(len0, T, hir):
     return len0c, len1, info
 
 
-def _pool_native(y, d_len, d_rows, avg=True):
+def _pool_native(y, d_len, d_rows, avg=True, grad=False):
     """``dsp_head_pool_batch`` over y [T, B, H] (fp32, on a GPU): -> [B, 2 H] = sum over t < len / len || max over the first
-    *d_rows rows (zero rows included, unread), or the max half [B, H] alone with ``avg=False``."""
+    *d_rows rows (zero rows included, unread), or the max half [B, H] alone with ``avg=False``.  ``grad=True``: where y requires a gradient the result carries it
+    (``_PoolTrain``); otherwise y is read detached, as always."""
     from . import _native as nat
+    if grad and torch.is_grad_enabled() and y.requires_grad:                  # ``grad``: the caller's device_grad=True
+        return _PoolTrain.apply(y, d_len, d_rows, avg)
     T, B, H = y.shape
     dev = y.device
     yc = y.detach().to(torch.float32).contiguous()
@@ -86,6 +104,48 @@ def _pool_native(y, d_len, d_rows, avg=True):
                                                  feat.stride(0), 0 if avg else -1, H if avg else 0,
                                                  torch.cuda.current_stream(dev).cuda_stream))
     return feat
+
+
+class _PoolTrain(torch.autograd.Function):
+    """``_pool_native`` with a gradient.  forward: dsp_head_pool_train_batch (the pooling kernel, which also saves the row each
+    maximum came from, arg [B, H] int32); backward: dsp_head_pool_backward_batch, one streaming launch that writes every
+    element of g_y [T, B, H] (zeros at t >= len; the gradient of a maximum the padding won is dropped).  The lengths and the
+    row count are read on the device in both."""
+
+    @staticmethod
+    def forward(ctx, y, d_len, d_rows, avg):
+        from . import _native as nat
+        ctx.set_materialize_grads(False)
+        T, B, H = y.shape
+        dev = y.device
+        yc = y.detach().to(torch.float32).contiguous()
+        with torch.cuda.device(dev):
+            feat = torch.empty(B, 2 * H if avg else H, dtype=torch.float32, device=dev)
+            arg = torch.empty(B, H, dtype=torch.int32, device=dev)
+            nat.check(nat.load().dsp_head_pool_train_batch(yc.data_ptr(), T, B, H, d_len.data_ptr(), d_rows.data_ptr(), feat.data_ptr(),
+                                                           feat.stride(0), 0 if avg else -1, H if avg else 0, arg.data_ptr(),
+                                                           torch.cuda.current_stream(dev).cuda_stream))
+        ctx.shape, ctx.avg = (T, B, H), avg
+        ctx.save_for_backward(d_len, arg)
+        return feat
+
+    @staticmethod
+    def backward(ctx, g_feat):
+        from . import _native as nat
+        if g_feat is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        d_len, arg = ctx.saved_tensors
+        T, B, H = ctx.shape
+        dev = arg.device
+        g = g_feat.detach().to(torch.float32)
+        if g.stride(1) != 1 or g.stride(0) < g.shape[1]:                        # (the call takes any row stride, not a column stride)
+            g = g.contiguous()
+        with torch.cuda.device(dev):
+            g_y = torch.empty(T, B, H, dtype=torch.float32, device=dev)
+            nat.check(nat.load().dsp_head_pool_backward_batch(g.data_ptr(), g.stride(0), 0 if ctx.avg else -1, H if ctx.avg else 0,
+                                                              d_len.data_ptr(), arg.data_ptr(), T, B, H, g_y.data_ptr(),
+                                                              torch.cuda.current_stream(dev).cuda_stream))
+        return g_y, None, None, None
 
 
 def _pack_state(hidden, H1, H2, B, **f32):
@@ -128,8 +188,23 @@ class _NativeHandle:
     def _param_key(self, dev_index):
         return (dev_index,) + tuple((p.data_ptr(), p._version) for p in self._params())
 
-    def _native_handle(self, dev):
+    def _native_handle(self, dev, refresh=False):
+        """``refresh=True``: where the key differs from the handle's in ``_version``s only -- same device, same tensors,
+        written in place, which is what an optimiser step leaves -- the handle is kept and its packed copy rewritten by
+        launches on torch's current stream (``dsp_*_refresh``: nothing allocated or synchronised; the stream orders the
+        repack behind the step that wrote the parameters and in front of the calls that follow).  ``refresh='always'`` repacks
+        on an equal key as well, so that a recorded sequence carries the repack.  Anything else rebuilds as before."""
         key = self._param_key(dev.index)
+        old = self._handle_key
+        if refresh and self._handle is not None and key[0] == old[0] and [p for p, _ in key[1:]] == [p for p, _ in old[1:]]:
+            if key != old or refresh == 'always':
+                from . import _native as nat
+                d = self._descriptor(nat)
+                with torch.cuda.device(dev):
+                    nat.check(getattr(nat.load(), self._lib + '_refresh')(self._handle, nat.C.byref(d),
+                                                                         torch.cuda.current_stream(dev).cuda_stream))
+                self._handle_key = key
+            return self._handle
         if self._handle is None or key != self._handle_key:
             from . import _native as nat
             self._drop_handle()
@@ -246,6 +321,22 @@ class _DynEnc(_NativeHandle, nn.Module):
                 assert tuple(drop.shape) == (g.num_layers - 1, T, B, 2 * H), 'drop does not fit [n_layers - 1, T, B, 2 H]'
             return _DynEncTrain.apply(self, T, d_len, drop, x, *self._params())
 
+    def _run_device_train(self, x, d_len, drop=None):
+        """The native training path with the lengths on the device (``device_grad=True``): all x.shape[0] rows of the buffer
+        are used -- max(len0) is not known here --, so the multipliers are drawn as [n_layers - 1, x.shape[0], B, 2 H].  The
+        handle survives an optimiser step (``refresh=True``)."""
+        B, H, dev, g = x.shape[1], self.hidden_size, x.device, self.gru
+        T = x.shape[0]
+        with torch.cuda.device(dev):
+            self._native_handle(dev, refresh=True)
+            if drop is None and self.training and g.dropout > 0 and g.num_layers > 1:
+                keep = 1.0 - g.dropout
+                drop = (torch.rand(g.num_layers - 1, T, B, 2 * H, device=dev) < keep).to(torch.float32) / keep
+            if drop is not None:
+                drop = drop.detach().to(torch.float32).contiguous()
+                assert tuple(drop.shape) == (g.num_layers - 1, T, B, 2 * H), 'drop does not fit [n_layers - 1, T, B, 2 H]'
+            return _DynEncDeviceTrain.apply(self, T, d_len, drop, x, *self._params())
+
     # ---- nn.GRU path (layers.py:63-76) -----------------------------------------------------------------------------------
     def _run_torch(self, x, lens):
         order = torch.argsort(lens, descending=True, stable=True)
@@ -256,16 +347,27 @@ class _DynEnc(_NativeHandle, nn.Module):
         h = self.hidden_size
         return (y[:, :, :h] + y[:, :, h:])[:, unsort].contiguous(), hn[:, unsort].contiguous()
 
-    def run(self, x, lens, native=None, device_len=False):
+    def run(self, x, lens, native=None, device_len=False, device_grad=False):
         """-> (y [max(lens), B, H], h_n [2 n_layers, B, H]), the reference's return value (layers.py:76).
         ``device_len=True``: ``lens`` is a [B] int32 tensor on x's device with entries in [1, x.shape[0]] and stays there; the
         native forward runs over all x.shape[0] rows (y has that many, exact zero rows behind each end) and nothing is read
-        back.  Forward only: a required gradient, or anything else the native path cannot serve, raises."""
+        back.  Forward only: a required gradient, or anything else the native path cannot serve, raises --
+        unless ``device_grad=True`` is given as well: a required gradient then takes the native training path over all
+        x.shape[0] rows (``_run_device_train``; training mode, as ``native=True``), and the handle is refreshed in place
+        after an optimiser step instead of rebuilt."""
+        _check_device_grad('_DynEnc', device_len, device_grad)
         if device_len:
-            _check_device_len('_DynEnc', x, lens, self)
-            why = self.native_supported(x)
+            needs_grad = _check_device_len('_DynEnc', x, lens, self, device_grad)
+            if needs_grad and not self.training:
+                why = 'a gradient is required and the module is in eval mode (the native training path serves training mode)'
+            else:
+                why = self.native_supported(x, train=needs_grad)
             if why is not None:
                 raise RuntimeError(f'_DynEnc: the native path cannot run: {why}')
+            if needs_grad:
+                return self._run_device_train(x, lens.contiguous())
+            if device_grad:
+                self._native_handle(x.device, refresh=True)
             return self._launch_native(x, x.shape[0], lens.contiguous())
         lens = torch.as_tensor(_lengths(lens))
         if native is False:
@@ -285,21 +387,32 @@ class _DynEnc(_NativeHandle, nn.Module):
             return self._run_native_train(x, lens) if needs_grad else self._run_native(x, lens)
         return self._run_torch(x, lens)
 
-    def forward(self, x, lens, native=None, device_len=False):
-        return self.run(x, lens, native, device_len)[0]
+    def forward(self, x, lens, native=None, device_len=False, device_grad=False):
+        return self.run(x, lens, native, device_len, device_grad)[0]
 
 
-def gru_param_grads(params, x, out, da, drop=None, need=None):
+def _ones_col_sum(a):
+    """a [n, m] -> the column sums [m] as a product with a row of ones.  The device-length training path forms the GRU bias
+    gradients with it in place of ``a.sum(0)``: recorded in a HIP graph inside a whole training step, that reduction
+    (T B = 1000 rows of a strided view into 600 columns) gave seven of the eight bias gradients wrong by up to 0.1 max |ref|
+    from the SECOND replay on, while every product replayed bit for bit.  torch's split reductions zero their counters with
+    a memset, and a recorded memset of more than 4 bytes is not replayed faithfully on this stack (DESIGN 7.12,
+    tools/probes/graph_memset_replay.py).  The host-length routes keep ``a.sum(0)`` and their bits."""
+    return (a.new_ones(1, a.shape[0]) @ a).reshape(-1)
+
+
+def gru_param_grads(params, x, out, da, drop=None, need=None, col_sum=None):
     """The GEMMs behind one layer of the backward recurrence (include/dsp_frontend.h: dsp_bigru_backward).  params: the
     layer's weight_ih, weight_hh, bias_ih, bias_hh of the forward direction, then of the reverse one; x [T, B, in]: the
     layer's input as the kernel read it (dropout multipliers applied); out [T, B, 2 H]: the layer's output rows, forward |
     reverse, zero rows behind each column's end; da [T, B, 2, 4 H]: the gradients of the pre-activations, n_x | r | z | n_h;
     drop [T, B, in]: the multipliers of x, or None.  -> (dx -- the gradient of the layer's input in front of the
     multipliers -- then the eight parameter gradients in the order of ``params``); ``need`` (9 booleans) leaves out what is
-    not wanted."""
+    not wanted.  ``col_sum``: what forms the bias gradients' column sums (default ``a.sum(0)``)."""
     T, B, I = x.shape
     H = out.shape[2] // 2
     need = [True] * 9 if need is None else need
+    col_sum = (lambda a: a.sum(0)) if col_sum is None else col_sum
     d2, x2 = da.reshape(T * B, 2, 4 * H), x.reshape(T * B, I)
     rzn = lambda v: torch.cat([v[H:], v[:H]], 0)            # rows n | r | z -> nn.GRU's r | z | n
     res = [None] * 9
@@ -315,8 +428,8 @@ def gru_param_grads(params, x, out, da, drop=None, need=None):
         if need[2 + 4 * d]:
             hp = torch.cat([zero, out[:-1, :, :H]], 0) if d == 0 else torch.cat([out[1:, :, H:], zero], 0)
             res[2 + 4 * d] = a_hh.t() @ hp.reshape(T * B, H)
-        if need[3 + 4 * d]: res[3 + 4 * d] = rzn(a_ih.sum(0))
-        if need[4 + 4 * d]: res[4 + 4 * d] = a_hh.sum(0)
+        if need[3 + 4 * d]: res[3 + 4 * d] = rzn(col_sum(a_ih))
+        if need[4 + 4 * d]: res[4 + 4 * d] = col_sum(a_hh)
     if need[0]:
         dx = dx.view(T, B, I)
         res[0] = dx * drop if drop is not None else dx
@@ -331,59 +444,80 @@ class _DynEncTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mod, T, d_len, drop, x, *params):
-        from . import _native as nat
-        ctx.set_materialize_grads(False)                     # an unused output hands None to backward, not a tensor of zeros
-        B, H, L, dev = x.shape[1], mod.hidden_size, mod.gru.num_layers, x.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        xc = x.detach().contiguous()
-        handle, lib = mod._native_handle(dev), nat.load()
-        nbytes = nat.c_i64(0)
-        nat.check(lib.dsp_bigru_tape_bytes(handle, T, B, nat.C.byref(nbytes)))
-        tape = torch.empty(nbytes.value // 4, **f32)
-        y, hn = torch.empty(T, B, H, **f32), torch.empty(2 * L, B, H, **f32)
-        nat.check(lib.dsp_bigru_forward_train(handle, xc.data_ptr(), T, B, d_len.data_ptr(), _ptr(drop),
-                                              y.data_ptr(), hn.data_ptr(), tape.data_ptr(), nbytes.value,
-                                              torch.cuda.current_stream(dev).cuda_stream))
-        ctx.mod, ctx.tape_bytes, ctx.handle_key, ctx.has_drop = mod, nbytes.value, mod._handle_key, drop is not None
-        ctx.save_for_backward(xc, d_len, tape, *([drop] if drop is not None else []), *params)
-        return y, hn
+        return _dynenc_train_forward(ctx, None, mod, T, d_len, drop, x, *params)
 
     @staticmethod
     def backward(ctx, g_y, g_hn):
-        from . import _native as nat
-        mod = ctx.mod
-        mod._check_unmodified(ctx.handle_key)
-        saved = ctx.saved_tensors
-        xc, d_len, tape = saved[:3]
-        drop = saved[3] if ctx.has_drop else None
-        params = [p.detach() for p in saved[4 if ctx.has_drop else 3:]]
-        T, B, _ = xc.shape
-        H, L, dev = mod.hidden_size, mod.gru.num_layers, xc.device
-        grads = [None] * (1 + 8 * L)
-        if g_y is None and g_hn is None:
-            return (None,) * 4 + tuple(grads)
-        gp = lambda g: None if g is None else g.to(torch.float32).contiguous()
-        g, g_hn = gp(g_y), gp(g_hn)
-        lib = nat.load()
-        with torch.cuda.device(dev):
-            off = nat.c_i64(0)
-            rows = []
-            for l in range(L):
-                nat.check(lib.dsp_bigru_tape_rows(mod._handle, l, T, B, nat.C.byref(off)))
-                rows.append(tape[off.value // 4:off.value // 4 + T * B * 2 * H].view(T, B, 2 * H))
-            for l in range(L - 1, -1, -1):
-                da = torch.empty(T, B, 2, 4 * H, dtype=torch.float32, device=dev)
-                nat.check(lib.dsp_bigru_backward(mod._handle, l, T, B, d_len.data_ptr(), tape.data_ptr(), ctx.tape_bytes, _ptr(g),
-                                                 None if g_hn is None else g_hn[2 * l:].data_ptr(), da.data_ptr(),
-                                                 torch.cuda.current_stream(dev).cuda_stream))
-                dl = drop[l - 1] if (drop is not None and l > 0) else None
-                x_l = xc if l == 0 else (rows[l - 1] if dl is None else rows[l - 1] * dl)
-                need = [l > 0 or ctx.needs_input_grad[4]] + list(ctx.needs_input_grad[5 + 8 * l:13 + 8 * l])
-                res = gru_param_grads(params[8 * l:8 * l + 8], x_l, rows[l], da, dl, need)
-                grads[1 + 8 * l:9 + 8 * l] = res[1:]
-                g = res[0]
-            grads[0] = g
+        return _dynenc_train_backward(ctx, g_y, g_hn)
+
+
+class _DynEncDeviceTrain(torch.autograd.Function):
+    """``_DynEncTrain`` as the device-length path calls it (``_DynEnc._run_device_train``): the same kernels and products, the
+    bias gradients' column sums formed by ``_ones_col_sum``."""
+
+    @staticmethod
+    def forward(ctx, mod, T, d_len, drop, x, *params):
+        return _dynenc_train_forward(ctx, _ones_col_sum, mod, T, d_len, drop, x, *params)
+
+    @staticmethod
+    def backward(ctx, g_y, g_hn):
+        return _dynenc_train_backward(ctx, g_y, g_hn)
+
+
+def _dynenc_train_forward(ctx, col_sum, mod, T, d_len, drop, x, *params):
+    from . import _native as nat
+    ctx.set_materialize_grads(False)                     # an unused output hands None to backward, not a tensor of zeros
+    B, H, L, dev = x.shape[1], mod.hidden_size, mod.gru.num_layers, x.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    xc = x.detach().contiguous()
+    handle, lib = mod._native_handle(dev), nat.load()
+    nbytes = nat.c_i64(0)
+    nat.check(lib.dsp_bigru_tape_bytes(handle, T, B, nat.C.byref(nbytes)))
+    tape = torch.empty(nbytes.value // 4, **f32)
+    y, hn = torch.empty(T, B, H, **f32), torch.empty(2 * L, B, H, **f32)
+    nat.check(lib.dsp_bigru_forward_train(handle, xc.data_ptr(), T, B, d_len.data_ptr(), _ptr(drop),
+                                          y.data_ptr(), hn.data_ptr(), tape.data_ptr(), nbytes.value,
+                                          torch.cuda.current_stream(dev).cuda_stream))
+    ctx.mod, ctx.tape_bytes, ctx.handle_key, ctx.has_drop = mod, nbytes.value, mod._handle_key, drop is not None
+    ctx.col_sum = col_sum
+    ctx.save_for_backward(xc, d_len, tape, *([drop] if drop is not None else []), *params)
+    return y, hn
+
+def _dynenc_train_backward(ctx, g_y, g_hn):
+    from . import _native as nat
+    mod = ctx.mod
+    mod._check_unmodified(ctx.handle_key)
+    saved = ctx.saved_tensors
+    xc, d_len, tape = saved[:3]
+    drop = saved[3] if ctx.has_drop else None
+    params = [p.detach() for p in saved[4 if ctx.has_drop else 3:]]
+    T, B, _ = xc.shape
+    H, L, dev = mod.hidden_size, mod.gru.num_layers, xc.device
+    grads = [None] * (1 + 8 * L)
+    if g_y is None and g_hn is None:
         return (None,) * 4 + tuple(grads)
+    gp = lambda g: None if g is None else g.to(torch.float32).contiguous()
+    g, g_hn = gp(g_y), gp(g_hn)
+    lib = nat.load()
+    with torch.cuda.device(dev):
+        off = nat.c_i64(0)
+        rows = []
+        for l in range(L):
+            nat.check(lib.dsp_bigru_tape_rows(mod._handle, l, T, B, nat.C.byref(off)))
+            rows.append(tape[off.value // 4:off.value // 4 + T * B * 2 * H].view(T, B, 2 * H))
+        for l in range(L - 1, -1, -1):
+            da = torch.empty(T, B, 2, 4 * H, dtype=torch.float32, device=dev)
+            nat.check(lib.dsp_bigru_backward(mod._handle, l, T, B, d_len.data_ptr(), tape.data_ptr(), ctx.tape_bytes, _ptr(g),
+                                             None if g_hn is None else g_hn[2 * l:].data_ptr(), da.data_ptr(),
+                                             torch.cuda.current_stream(dev).cuda_stream))
+            dl = drop[l - 1] if (drop is not None and l > 0) else None
+            x_l = xc if l == 0 else (rows[l - 1] if dl is None else rows[l - 1] * dl)
+            need = [l > 0 or ctx.needs_input_grad[4]] + list(ctx.needs_input_grad[5 + 8 * l:13 + 8 * l])
+            res = gru_param_grads(params[8 * l:8 * l + 8], x_l, rows[l], da, dl, need, ctx.col_sum)
+            grads[1 + 8 * l:9 + 8 * l] = res[1:]
+            g = res[0]
+        grads[0] = g
+    return (None,) * 4 + tuple(grads)
 
 
 class RNNHead(nn.Module):
@@ -394,14 +528,16 @@ class RNNHead(nn.Module):
         self.enc = _DynEnc(feat_size, hidden, layers)
         self.out = nn.Linear(2 * hidden, classes)
 
-    def forward(self, inp, len0, native_enc=None, device_len=False):
+    def forward(self, inp, len0, native_enc=None, device_len=False, device_grad=False):
         """inp: [T, B, 39] (zero beyond each utterance's length), len0: lengths (numpy / list / tensor) -> [B, 20].
-        ``device_len=True``: len0 is a [B] int32 tensor on inp's device and is never read from the host (module docstring)."""
+        ``device_len=True``: len0 is a [B] int32 tensor on inp's device and is never read from the host (module docstring);
+        ``device_grad=True`` with it serves a required gradient on that path."""
+        _check_device_grad('RNNHead', device_len, device_grad)
         if device_len:
-            _check_device_len('RNNHead', inp, len0, self)
+            _check_device_len('RNNHead', inp, len0, self, device_grad)
             d_len, _, info = head_length_info(len0, inp.shape[0], 1)
-            y = self.enc(inp, d_len, device_len=True)                           # [T, B, H], zeros behind each end
-            return self.out(_pool_native(y, d_len, info[0:1]))
+            y = self.enc(inp, d_len, device_len=True, device_grad=device_grad)  # [T, B, H], zeros behind each end
+            return self.out(_pool_native(y, d_len, info[0:1], grad=device_grad))
         lens = torch.as_tensor(_lengths(len0))
         y = self.enc(inp, lens, native=native_enc)                          # [max(len0), B, H], zeros behind each end
         avg = y.sum(0) / lens.to(inp.device, inp.dtype).unsqueeze(1)        # rnn_clf.py:29-30
@@ -438,26 +574,27 @@ class HRNNHead(nn.Module):
         y = self.enc1(inp, len0, native=native_enc)[:, :, -self.hidden_size:]            # rnn_clf.py:58
         return self.enc2(y[0::self.hir], len1, native=native_enc), len1                  # rnn_clf.py:61-65
 
-    def _levels_device(self, inp, len0):
+    def _levels_device(self, inp, len0, device_grad=False):
         """``_levels`` with the lengths on the device: all ceil(T / hir) picked rows go into enc2 -> (y2, len1, info)."""
         d_len, d_len1, info = head_length_info(len0, inp.shape[0], self.hir)
-        y = self.enc1(inp, d_len, device_len=True)[:, :, -self.hidden_size:]
-        return self.enc2(y[0::self.hir], d_len1, device_len=True), d_len1, info
+        y = self.enc1(inp, d_len, device_len=True, device_grad=device_grad)[:, :, -self.hidden_size:]
+        return self.enc2(y[0::self.hir], d_len1, device_len=True, device_grad=device_grad), d_len1, info
 
-    def _forward_device(self, inp, len0, dropout, attn=None):
-        _check_device_len(type(self).__name__, inp, len0, self)
-        y2, d_len1, info = self._levels_device(inp, len0)
+    def _forward_device(self, inp, len0, dropout, attn=None, device_grad=False):
+        _check_device_len(type(self).__name__, inp, len0, self, device_grad)
+        y2, d_len1, info = self._levels_device(inp, len0, device_grad)
         rows = info[1:2]                                                        # ceil(max(len0) / hir), on the device
         if attn is None:
-            feat = _pool_native(y2, d_len1, rows)
+            feat = _pool_native(y2, d_len1, rows, grad=device_grad)
         else:
-            feat = torch.cat([attn(y2, native=True, d_rows=rows), _pool_native(y2, d_len1, rows, avg=False)], dim=1)
+            feat = torch.cat([attn(y2, native=True, d_rows=rows, device_grad=device_grad), _pool_native(y2, d_len1, rows, avg=False, grad=device_grad)], dim=1)
         out = self.out(feat)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
 
-    def forward(self, inp, len0, dropout=True, native_enc=None, device_len=False):
+    def forward(self, inp, len0, dropout=True, native_enc=None, device_len=False, device_grad=False):
+        _check_device_grad(type(self).__name__, device_len, device_grad)
         if device_len:
-            return self._forward_device(inp, len0, dropout)
+            return self._forward_device(inp, len0, dropout, device_grad=device_grad)
         y2, len1 = self._levels(inp, len0, native_enc)
         out, feat = _pool_head(y2, len1, self.out)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
@@ -496,43 +633,77 @@ class _SelfAttnTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, W, bW, v, c):
-        from . import _native as nat
-        ctx.set_materialize_grads(False)
-        T, B, H = y.shape
-        dev = y.device
-        yc = _aligned16(y)
-        with torch.cuda.device(dev):
-            out = torch.empty(B, H, dtype=torch.float32, device=dev)
-            w = torch.empty(T, B, dtype=torch.float32, device=dev)
-            nat.check(nat.load().dsp_selfattn_pool_train_batch(yc.data_ptr(), T, B, H, W.data_ptr(), bW.data_ptr(), v.data_ptr(),
-                                                               c.data_ptr(), out.data_ptr(), w.data_ptr(),
-                                                               torch.cuda.current_stream(dev).cuda_stream))
-        ctx.save_for_backward(yc, w, W, bW, v)
-        return out
+        return _selfattn_train_forward(ctx, y, W, bW, v, c, None)
 
     @staticmethod
     def backward(ctx, g_out):
-        from . import _native as nat
+        return _selfattn_train_backward(ctx, g_out, ctx.needs_input_grad, None)
+
+
+def _selfattn_train_forward(ctx, y, W, bW, v, c, d_rows):
+    """The forward of ``_SelfAttnTrain`` (d_rows None) and ``_SelfAttnRowsTrain``."""
+    from . import _native as nat
+    ctx.set_materialize_grads(False)
+    T, B, H = y.shape
+    dev = y.device
+    yc = _aligned16(y)
+    with torch.cuda.device(dev):
+        out = torch.empty(B, H, dtype=torch.float32, device=dev)
+        w = torch.empty(T, B, dtype=torch.float32, device=dev)
+        lib, args = nat.load(), (yc.data_ptr(), T, B, H, W.data_ptr(), bW.data_ptr(), v.data_ptr(), c.data_ptr(), out.data_ptr(), w.data_ptr())
+        st = torch.cuda.current_stream(dev).cuda_stream
+        if d_rows is None:
+            nat.check(lib.dsp_selfattn_pool_train_batch(*args, st))
+        else:
+            nat.check(lib.dsp_selfattn_pool_rows_train_batch(*args, d_rows.data_ptr(), st))
+    ctx.save_for_backward(yc, w, W, bW, v)
+    return out
+
+
+def _selfattn_train_backward(ctx, g_out, need, d_rows):
+    """The backward of both: -> the gradients of (y, W, bW, v, c); ``need``: which of the five are wanted.  With ``d_rows`` the
+    kernel leaves exact zeros behind the row count, so the sums over all T rows below are the sums over the block."""
+    from . import _native as nat
+    if g_out is None or not any(need):
+        return (None,) * 5
+    yc, w, W, bW, v = ctx.saved_tensors
+    T, B, H = yc.shape
+    dev = yc.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    g = _aligned16(g_out)
+    with torch.cuda.device(dev):
+        g_y = torch.empty(T, B, H, **f32) if need[0] else None
+        g_pre, g_e, gv = torch.empty(T, B, H, **f32), torch.empty(T, B, **f32), torch.empty(B, H, **f32)
+        lib = nat.load()
+        args = (yc.data_ptr(), T, B, H, W.data_ptr(), bW.data_ptr(), v.data_ptr(), w.data_ptr(), g.data_ptr(), _ptr(g_y), g_pre.data_ptr(),
+                g_e.data_ptr(), gv.data_ptr())
+        st = torch.cuda.current_stream(dev).cuda_stream
+        if d_rows is None:
+            nat.check(lib.dsp_selfattn_pool_backward_batch(*args, st))
+        else:
+            nat.check(lib.dsp_selfattn_pool_rows_backward_batch(*args, d_rows.data_ptr(), st))
+        return (g_y,
+                _rows_gemm(g_pre, yc) if need[1] else None,
+                _rows_sum(g_pre) if need[2] else None,
+                gv.sum(0, keepdim=True) if need[3] else None,
+                g_e.sum().reshape(1) if need[4] else None)
+
+
+class _SelfAttnRowsTrain(torch.autograd.Function):
+    """``_SelfAttnTrain`` over the first clamp(*d_rows, 1, T) rows of y, the count read on the device
+    (dsp_selfattn_pool_rows_train_batch / dsp_selfattn_pool_rows_backward_batch).  Inputs: (y, d_rows, attn.weight, attn.bias,
+    v.weight, v.bias); the parameter gradients are computed as ``_SelfAttnTrain`` computes them."""
+
+    @staticmethod
+    def forward(ctx, y, d_rows, W, bW, v, c):
+        ctx.d_rows = d_rows
+        return _selfattn_train_forward(ctx, y, W, bW, v, c, d_rows)
+
+    @staticmethod
+    def backward(ctx, g_out):
         need = ctx.needs_input_grad
-        if g_out is None or not any(need):
-            return (None,) * 5
-        yc, w, W, bW, v = ctx.saved_tensors
-        T, B, H = yc.shape
-        dev = yc.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        g = _aligned16(g_out)
-        with torch.cuda.device(dev):
-            g_y = torch.empty(T, B, H, **f32) if need[0] else None
-            g_pre, g_e, gv = torch.empty(T, B, H, **f32), torch.empty(T, B, **f32), torch.empty(B, H, **f32)
-            nat.check(nat.load().dsp_selfattn_pool_backward_batch(yc.data_ptr(), T, B, H, W.data_ptr(), bW.data_ptr(), v.data_ptr(),
-                                                                  w.data_ptr(), g.data_ptr(), _ptr(g_y), g_pre.data_ptr(),
-                                                                  g_e.data_ptr(), gv.data_ptr(),
-                                                                  torch.cuda.current_stream(dev).cuda_stream))
-            return (g_y,
-                    _rows_gemm(g_pre, yc) if need[1] else None,
-                    _rows_sum(g_pre) if need[2] else None,
-                    gv.sum(0, keepdim=True) if need[3] else None,
-                    g_e.sum().reshape(1) if need[4] else None)
+        res = _selfattn_train_backward(ctx, g_out, (need[0],) + tuple(need[2:]), ctx.d_rows)
+        return (res[0], None) + tuple(res[1:])
 
 
 class _SelfAttn(nn.Module):
@@ -588,13 +759,19 @@ class _SelfAttn(nn.Module):
         w = torch.softmax(self.v(torch.tanh(self.attn(y))).squeeze(2), 1)       # [B, T]
         return torch.bmm(w.unsqueeze(1), y).squeeze(1)
 
-    def forward(self, y, native=None, d_rows=None):
+    def forward(self, y, native=None, d_rows=None, device_grad=False):
         """``d_rows``: a one-element int32 device tensor -- the softmax runs over the first min(*d_rows, T) rows of y only,
-        the count read on the device (``dsp_selfattn_pool_rows_batch``); native and forward only."""
+        the count read on the device (``dsp_selfattn_pool_rows_batch``); native, and forward only unless
+        ``device_grad=True`` is given: a required gradient then takes ``_SelfAttnRowsTrain``."""
+        if device_grad and d_rows is None:
+            raise ValueError('_SelfAttn: device_grad=True needs d_rows (it is the training form of the device-length path)')
         if d_rows is not None:
-            why = self.native_supported(y)
+            needs_grad = device_grad and _attn_needs_grad(y, self)
+            why = self.native_supported(y, train=needs_grad)
             if why is not None:
                 raise RuntimeError(f'_SelfAttn: the native path cannot run: {why}')
+            if needs_grad:
+                return _SelfAttnRowsTrain.apply(y, d_rows, self.attn.weight, self.attn.bias, self.v.weight, self.v.bias)
             return self._run_native(y, d_rows)
         if native is False:
             return self._run_torch(y)
@@ -618,9 +795,10 @@ class HRNNAttHead(HRNNHead):
         super().__init__(feat_size)
         self.attn = _SelfAttn(200)
 
-    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False):
+    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False, device_grad=False):
+        _check_device_grad('HRNNAttHead', device_len, device_grad)
         if device_len:
-            return self._forward_device(inp, len0, dropout, self.attn)
+            return self._forward_device(inp, len0, dropout, self.attn, device_grad)
         y2, len1 = self._levels(inp, len0, native_enc)
         out, feat = _pool_head(y2, len1, self.out, self.attn, native_attn)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
@@ -894,7 +1072,9 @@ class _TransformerEncoder(_NativeHandle, nn.Module):
     def _run_torch(self, x):
         return self.pos_ffn(self.slf_attn(x))
 
-    def run(self, x, native=None):
+    def run(self, x, native=None, refresh=False):
+        """``refresh``: what ``_native_handle`` is told on the native paths -- True keeps the handle across an optimiser step and
+        repacks it in place (the ``device_grad=True`` path of ``TransformerHead``), 'always' repacks in any case."""
         if native is False:
             return self._run_torch(x)
         needs_grad = _attn_needs_grad(x, self)
@@ -902,13 +1082,15 @@ class _TransformerEncoder(_NativeHandle, nn.Module):
             return self._run_torch(x)                                           # (nothing to find out about the native path)
         why = self.native_supported(x, train=needs_grad)
         if why is None:
+            if refresh:
+                self._native_handle(x.device, refresh=refresh)                  # (the paths' own call then finds an equal key)
             return self._run_native_train(x) if needs_grad else self._run_native(x)
         if native:
             raise RuntimeError(f"_TransformerEncoder: the native {'training path (a gradient is required)' if needs_grad else 'path'} cannot run: {why}")
         return self._run_torch(x)
 
-    def forward(self, x, native=None):
-        return self.run(x, native)
+    def forward(self, x, native=None, refresh=False):
+        return self.run(x, native, refresh)
 
 
 class TransformerHead(nn.Module):
@@ -925,15 +1107,16 @@ class TransformerHead(nn.Module):
         self.out = nn.Linear(400, 20)
         self.hidden_size = 200
 
-    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False):
+    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False, device_grad=False):
+        _check_device_grad('TransformerHead', device_len, device_grad)
         if device_len:
-            _check_device_len('TransformerHead', inp, len0, self)
+            _check_device_len('TransformerHead', inp, len0, self, device_grad)
             d_len, d_len1, info = head_length_info(len0, inp.shape[0], self.hir)
-            attn_out = self.attn_enc(inp, native=True)
+            attn_out = self.attn_enc(inp, native=True, refresh=device_grad)
             a = torch.nn.functional.dropout(attn_out, 0.5) if dropout else attn_out
-            y = self.rnn_enc_1(torch.cat([inp, a], 2), d_len, device_len=True)[:, :, -self.hidden_size:]
-            y2 = self.rnn_enc_2(y[0::self.hir], d_len1, device_len=True)
-            feat = _pool_native(y2, d_len1, info[1:2])
+            y = self.rnn_enc_1(torch.cat([inp, a], 2), d_len, device_len=True, device_grad=device_grad)[:, :, -self.hidden_size:]
+            y2 = self.rnn_enc_2(y[0::self.hir], d_len1, device_len=True, device_grad=device_grad)
+            feat = _pool_native(y2, d_len1, info[1:2], grad=device_grad)
             out = self.out(feat)
             return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat, attn_out
         len0 = _lengths(len0)
@@ -1143,11 +1326,11 @@ class HMLSTM(_NativeHandle, nn.Module):
     def _descriptor(self, nat):
         return nat.HmlstmDesc(self.input_size, self.size_list[0], self.size_list[1], 0, *[p.data_ptr() for p in self._params()])
 
-    def _native_handle(self, dev):
+    def _native_handle(self, dev, refresh=False):
         if any(not p.is_contiguous() for p in self._params()):
             from . import _native as nat
             raise nat.DspError('HMLSTM: parameters must be contiguous')
-        return super()._native_handle(dev)
+        return super()._native_handle(dev, refresh)
 
     def _run_native(self, x, hidden, lens, want_seq=True, d_len=None, last_only=False):
         """``d_len``: the lengths as a [B] int32 tensor on x's device, read in place (``lens`` is then ignored).
@@ -1181,15 +1364,21 @@ class HMLSTM(_NativeHandle, nn.Module):
         zf = lambda z: None if z is None else z.to(torch.float32).unsqueeze(2)
         return HMLSTMResult(h_1=h_1, h_2=h_2, z_1=zf(z_1), z_2=zf(z_2), hidden=hid, z_hat=z_hat, last_h2=last)
 
-    def _run_native_train(self, x, hidden, lens):
-        """The native training path: the same HMLSTMResult, h_1 / h_2 / last_h2 attached to the autograd graph."""
+    def _run_native_train(self, x, hidden, lens, d_len=None):
+        """The native training path: the same HMLSTMResult, h_1 / h_2 / last_h2 attached to the autograd graph.
+        ``d_len`` (``device_grad=True``): the lengths as a [B] int32 tensor on x's device, read in place; ``last_h2`` is then
+        the only field returned, and the handle survives an optimiser step (``refresh=True``).  All T rows run on this path
+        -- the forward-only ``last_only`` shortcut does not apply: the backward recurrence reads the tape of every row."""
         T, B, _ = x.shape
         H1, H2 = self.size_list
         dev = x.device
         with torch.cuda.device(dev):
-            self._native_handle(dev)
+            self._native_handle(dev, refresh=d_len is not None)
             f32 = dict(dtype=torch.float32, device=dev)
             state_in = None if hidden is None else _pack_state(hidden, H1, H2, B, **f32)
+            if d_len is not None:
+                last = _HMLSTMTrain.apply(self, float(self.a), d_len, state_in, x, *self._params())[2]
+                return HMLSTMResult(last_h2=last)
             if lens is not None:
                 d_len = torch.as_tensor(_lengths(lens), dtype=torch.int32).to(dev)
             else:
@@ -1223,19 +1412,27 @@ class HMLSTM(_NativeHandle, nn.Module):
         return HMLSTMResult(h_1=torch.stack(hs1, dim=1), h_2=h_2, z_1=torch.stack(zs1, dim=1), z_2=torch.stack(zs2, dim=1),
                             hidden=(h1, c1, z1, h2, c2, z2), z_hat=torch.stack(zh).detach(), last_h2=last)
 
-    def run(self, x, hidden=None, lens=None, native=None, device_len=False):
+    def run(self, x, hidden=None, lens=None, native=None, device_len=False, device_grad=False):
         """Everything the forward pass yields, as an HMLSTMResult.  x: [T, B, input_size].
         ``device_len=True``: ``lens`` is a [B] int32 tensor on x's device with entries in [1, T] and stays there; the native
         forward yields ``last_h2`` alone (every other field is None), which lets each 16-column slice stop at its longest
         length instead of running all T rows.
-        Forward only: a required gradient, or anything else the native path cannot serve, raises."""
+        Forward only: a required gradient, or anything else the native path cannot serve, raises -- unless
+        ``device_grad=True`` is given as well: a required gradient then takes the native training path with the lengths read
+        on the device.  ``last_h2`` is still the only field returned, but ALL T rows run, because the backward recurrence
+        needs the tape of every row; the handle is refreshed in place after an optimiser step instead of rebuilt."""
+        _check_device_grad('HMLSTM', device_len, device_grad)
         if device_len:
-            _check_device_len('HMLSTM', x, lens, self)
+            needs_grad = _check_device_len('HMLSTM', x, lens, self, device_grad)
             if torch.is_grad_enabled() and hidden is not None and any(v.requires_grad for v in hidden):
                 raise RuntimeError('HMLSTM: device_len=True cannot run: the initial hidden requires a gradient')
             why = self.native_supported(x)
             if why is not None:
                 raise RuntimeError(f'HMLSTM: the native path cannot run: {why}')
+            if needs_grad:
+                return self._run_native_train(x, hidden, None, d_len=lens.contiguous())
+            if device_grad:
+                self._native_handle(x.device, refresh=True)
             return self._run_native(x, hidden, None, d_len=lens.contiguous(), last_only=True)
         hidden_grad = torch.is_grad_enabled() and hidden is not None and any(v.requires_grad for v in hidden)
         needs_grad = hidden_grad or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))
@@ -1271,15 +1468,16 @@ class HMRNNHead(nn.Module):
         self.enc2 = HMLSTM(1.0, 200, [200, 200])
         self.out = nn.Linear(600, 20)
 
-    def forward(self, inp, len0, dropout=True, native=None, native_enc=None, device_len=False):
+    def forward(self, inp, len0, dropout=True, native=None, native_enc=None, device_len=False, device_grad=False):
+        _check_device_grad('HMRNNHead', device_len, device_grad)
         if device_len:
-            _check_device_len('HMRNNHead', inp, len0, self)
+            _check_device_len('HMRNNHead', inp, len0, self, device_grad)
             d_len, _, info = head_length_info(len0, inp.shape[0], 1)
-            enc = self.enc1(inp, d_len, device_len=True)                                                 # [T, B, 200], zeros behind each end
+            enc = self.enc1(inp, d_len, device_len=True, device_grad=device_grad)                        # [T, B, 200], zeros behind each end
             if dropout:
                 enc = torch.nn.functional.dropout(enc, 0.2)
-            last = self.enc2.run(enc, None, lens=d_len, device_len=True).last_h2
-            feat = torch.cat([_pool_native(enc, d_len, info[0:1]), last], dim=1)
+            last = self.enc2.run(enc, None, lens=d_len, device_len=True, device_grad=device_grad).last_h2
+            feat = torch.cat([_pool_native(enc, d_len, info[0:1], grad=device_grad), last], dim=1)
             out = self.out(feat)
             return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
         len0 = _lengths(len0)

@@ -181,11 +181,14 @@ class ModelFeatureBatch:
         del hold
         return inp, len0.cpu().numpy(), seg
 
-    def enqueue(self, d_wave, wave_dtype, lay, d_m0, d_inp, d_len0, stream):
-        """The default call (no optional streams, no jitter) as launches only -- raw device pointers, nothing allocated,
+    def enqueue(self, d_wave, wave_dtype, lay, d_m0, d_inp, d_len0, stream, d_jitter=None):
+        """The default call (no optional streams) as launches only -- raw device pointers, nothing allocated,
         nothing synchronised: endpointing, the layout glue, the feature kernel on the clips in place and the finalize
-        kernel.  ``d_m0``: [lay.frames_bound, C] fp32 scratch, ``d_inp``: [max_len, B, 3 C] fp32, ``d_len0``: [B] int32."""
-        self.enqueue_placed(d_wave, wave_dtype, lay, d_m0, d_inp, d_len0, None, lay.n_utt, 3 * self.pipe.features.C, stream, None)
+        kernel.  ``d_m0``: [lay.frames_bound, C] fp32 scratch, ``d_inp``: [max_len, B, 3 C] fp32, ``d_len0``: [B] int32.
+        ``d_jitter``: the endpoint offsets of the augmented front end (model.py:54-60; ``draw_jitter``) as a raw pointer to
+        [B, 2] int64 in device memory, read in place by the launches; None = the test path."""
+        self.enqueue_placed(d_wave, wave_dtype, lay, d_m0, d_inp, d_len0, None, lay.n_utt, 3 * self.pipe.features.C, stream, None,
+                            d_jitter=d_jitter)
 
     def enqueue_placed(self, d_wave, wave_dtype, lay, d_m0, d_inp, d_len0, d_dst_col, n_cols, row_width, stream, dev,
                        d_jitter=None, use_pitch=False, use_timefeat=False):

@@ -1,0 +1,230 @@
+"""One training step of a classifier head on raw clips without a host round trip: the training twin of
+``ensemble.EnsembleBatch`` for one sample rate (model.py:137-147: ``get_batch_full(feat, augment=True)``, the classifier,
+``F.cross_entropy``, ``backward``).
+
+* ``TrainBatch.run`` queues the augmented front end (``ModelFeatureBatch.enqueue`` with the endpoint jitter of model.py:54-60
+  read from device memory), the head with ``device_len=True, device_grad=True`` and the loss on torch's current stream.
+  ``len0`` never leaves the device and nothing is synchronised; the caller calls ``loss.backward()``.
+* ``TrainBatch.capture`` records a refresh of every native handle of the head, the front end, the forward, the loss and the
+  backward into ONE HIP graph.  ``replay()`` serves new clips, labels and jitter written into the captured buffers and leaves
+  the gradients in ``.grad`` tensors the graph owns.  The optimiser step stays the caller's, eager, after ``replay()``: it
+  writes the parameters in place, and the refresh at the head of the next replay repacks them.
+"""
+from __future__ import annotations
+
+import types
+
+import numpy as np
+
+from . import _native as nat
+from .batch import _is_device_tensor, _wave_dtype_of
+
+
+# Where ``TrainBatch.capture`` records: head class -> batch sizes at which tests/test_gpu_train_capture.py (B >= 32) and
+# tests/test_gpu_device_train.py (B = 5) compare a second replay with the eager step, bit for bit.
+CAPTURE_VERIFIED = {'RNNHead': (32, 512), 'HRNNHead': (32, 512), 'HRNNAttHead': (32, 512), 'TransformerHead': (32, 512),
+                    'HMRNNHead': (5, 32, 512)}
+
+
+def _logits_of(out):
+    return out[0] if isinstance(out, (tuple, list)) else out
+
+
+class _CapturedStep:
+    """What ``TrainBatch.capture`` returns.  ``replay()`` re-runs the recorded step on whatever the captured buffers hold now
+    and returns ``result`` (loss, logits, inp, len0, n_clamped: device tensors, valid after the current stream's work; nothing
+    is synchronised).  ``grads``: the gradient tensors the graph owns, in the order of ``params``; every replay OVERWRITES
+    them (it does not accumulate) and makes them the parameters' ``.grad`` again, so an ``optimizer.zero_grad()`` between
+    replays -- which drops ``.grad`` -- costs nothing and loses nothing.  ``hold``: every buffer the graph's kernels touch
+    that the result does not already keep alive."""
+
+    def __init__(self, graph, result, params, grads, hold):
+        self.graph, self.result, self.params, self.grads, self.hold = graph, result, params, grads, hold
+
+    def replay(self):
+        self.graph.replay()
+        for p, g in zip(self.params, self.grads):
+            p.grad = g
+        return self.result
+
+
+class TrainBatch:
+    """model.py:137-147 for a batch of raw clips of one sample rate, device-resident.
+
+    ``head``: one of features/classifier.py's heads in training mode (it is called with ``device_len=True,
+    device_grad=True``; further keywords -- ``dropout=False`` and the like -- go through ``run`` / ``capture``)."""
+
+    def __init__(self, rate, head, frame=0.03, step=0.01):
+        from .model_glue import ModelFeatureBatch
+        self.rate, self.head = rate, head
+        self.features = ModelFeatureBatch(rate, frame=frame, step=step)
+        self._layouts = {}
+
+    def draw_jitter(self, n_utt, rng):
+        """The endpoint offsets of model.py:54-60 for a batch (``ModelFeatureBatch.draw_jitter``): int64 [B, 2]."""
+        return self.features.draw_jitter(n_utt, rng)
+
+    def _layout(self, so):
+        """The pipeline layout of this batch shape, owned by this object (a few shapes are kept, the most recently used last)."""
+        key = (nat.current_device(), so.tobytes())
+        lay = self._layouts.pop(key, None)
+        if lay is None:
+            lay = self.features.pipe.prepare(so, 0)
+            while len(self._layouts) >= 4:
+                self._layouts.pop(next(iter(self._layouts)))
+        self._layouts[key] = lay
+        return lay
+
+    def _m0(self, lay, dev):
+        import torch
+        return torch.empty((max(lay.frames_bound, 1), self.features.pipe.features.C), dtype=torch.float32, device=dev)
+
+    @staticmethod
+    def _labels(labels, B, dev):
+        import torch
+        if not torch.is_tensor(labels):
+            labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int64))
+        labels = labels.to(device=dev, dtype=torch.int64)
+        if tuple(labels.shape) != (B,):
+            raise ValueError(f'labels must be [B] = [{B}], got {tuple(labels.shape)}')
+        return labels
+
+    @staticmethod
+    def _jitter(jitter, B, dev):
+        import torch
+        if jitter is None:
+            return None
+        if not torch.is_tensor(jitter):
+            jitter = torch.from_numpy(np.ascontiguousarray(jitter, dtype=np.int64))
+        jitter = jitter.to(device=dev, dtype=torch.int64).contiguous()
+        if tuple(jitter.shape) != (B, 2):
+            raise ValueError(f'jitter must be [B, 2] = [{B}, 2], got {tuple(jitter.shape)}')
+        return jitter
+
+    def _chain(self, clips, lay, m0, labels, d_jit, head_kwargs, alias=None):
+        """Front end, head, loss: launches on torch's current stream, nothing synchronised, no device memory read from the
+        host.  ``alias``: name -> tensor to stand in for the head's parameters during the call (``capture``)."""
+        import torch
+        from .classifier import head_length_info
+        mfb, dev, B = self.features, clips.device, lay.n_utt
+        inp = torch.empty((mfb.max_len, B, 3 * mfb.pipe.features.C), dtype=torch.float32, device=dev)
+        len0 = torch.empty(B, dtype=torch.int32, device=dev)
+        mfb.enqueue(clips.data_ptr(), _wave_dtype_of(clips), lay, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(),
+                    torch.cuda.current_stream(dev), d_jitter=None if d_jit is None else d_jit.data_ptr())
+        kw = dict(device_len=True, device_grad=True, **head_kwargs)
+        if alias is None:
+            out = self.head(inp, len0, **kw)
+        else:
+            out = torch.func.functional_call(self.head, alias, (inp, len0), kw)
+        logits = _logits_of(out)
+        loss = torch.nn.functional.cross_entropy(logits, labels)                        # model.py:141-147
+        n_clamped = head_length_info(len0, inp.shape[0], 1)[2][2:3]
+        return types.SimpleNamespace(loss=loss, logits=logits, inp=inp, len0=len0, n_clamped=n_clamped,
+                                     _hold=[clips, lay, m0, labels, d_jit])
+
+    def run(self, waves, sample_offsets, labels, jitter=None, **head_kwargs):
+        """``waves``: concatenated clips, a 1-D host array (int16 or float) or device tensor (int16 / float32);
+        ``sample_offsets`` [B + 1]; ``labels`` [B] class indices; ``jitter``: int [B, 2] endpoint offsets (``draw_jitter``;
+        model.py:144 trains with augment=True) or None.  Device tensors are read where they lie; host arrays are uploaded
+        first.  -> a namespace (loss: the scalar ``F.cross_entropy(logits, labels)``, attached to the autograd graph; logits
+        [B, C]; inp [200, B, 39]; len0 int32 [B]; n_clamped int32 [1]: the lengths the head had to clamp), all on the device.
+        Nothing is synchronised and no device memory is read from the host: the caller calls ``loss.backward()`` and then
+        its optimiser -- the head's native handles survive the step (they are repacked in place by the next call)."""
+        import torch
+        nat.require_device()
+        so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
+        if _is_device_tensor(waves):
+            clips = waves.reshape(-1).contiguous()
+        else:
+            host, _ = nat.as_wave(np.asarray(waves).reshape(-1))
+            clips = torch.from_numpy(host).to(torch.device('cuda', nat.current_device()))
+        _wave_dtype_of(clips)                              # TypeError for anything but int16 / float32
+        dev, B = clips.device, len(so) - 1
+        lay = self._layout(so)
+        return self._chain(clips, lay, self._m0(lay, dev), self._labels(labels, B, dev), self._jitter(jitter, B, dev), head_kwargs)
+
+    def capture(self, waves, sample_offsets, labels, jitter=None, **head_kwargs):
+        """ONE HIP graph of a whole step but the optimiser: ``g = tb.capture(waves, so, labels, jitter, dropout=False)``;
+        ``g.replay()`` does, in order, (1) a refresh of every native handle of the head -- the repack of whatever the
+        optimiser wrote since the last replay --, (2) the front end, (3) the forward, (4) the loss and (5) the backward into
+        ``.grad`` tensors the graph owns (``g.grads``), which every replay overwrites.  It returns the namespace of ``run``.
+        ``waves`` (contiguous device tensor, int16 / float32), ``labels`` (int64 [B] device tensor) and ``jitter`` (int64
+        [B, 2] device tensor, or None) are read at their addresses on every replay: write the next batch -- clips of the same
+        lengths -- into them.  The optimiser step stays the caller's, eager, after ``replay()``.
+
+        The recipe is torch's for a whole network: warm-up steps on a side stream (they build the native handles and the
+        layout's tables), then forward and backward recorded under ``torch.cuda.graph``.  Whatever ``.grad`` the parameters
+        held before is dropped.  Recording raises on anything that synchronises or reads device memory from the host.
+
+        The recorded step does not differentiate with respect to the module's own parameter objects but with respect to
+        private leaf aliases of them (same storage, same version counter, made here on the capture stream and kept by the
+        returned object).  A gradient accumulator is bound to the stream it was created on, and an autograd graph of an
+        earlier eager step that is still alive keeps the parameters' accumulators, bound to the default stream; a recorded
+        backward through those would pull that stream into the capture as a second branch.  The aliases' accumulators are
+        created by the warm-up on the capture stream whatever the caller still holds.  The returned ``loss`` and ``logits``
+        are detached.
+
+        Only the heads and batch sizes of ``CAPTURE_VERIFIED`` are served: a recorded multi-workgroup reduction of torch's
+        has been seen to go wrong on replay on this stack, so a head / size pair is recorded only where
+        tests/test_gpu_train_capture.py has compared a second replay with the eager step bit for bit.  Anything else raises
+        NotImplementedError; ``run`` serves every head and size."""
+        import torch
+        from .classifier import _NativeHandle
+        if not _is_device_tensor(waves):
+            raise TypeError('capture needs a device tensor')
+        if not waves.is_contiguous():
+            raise ValueError('capture needs a contiguous waves tensor: the graph reads it in place on every replay')
+        nat.require_device()
+        dev = waves.device
+        clips = waves.reshape(-1)                              # a view: the same memory
+        _wave_dtype_of(clips)
+        so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
+        B = len(so) - 1
+        kind = type(self.head).__name__
+        if B not in CAPTURE_VERIFIED.get(kind, ()):
+            raise NotImplementedError(f'capture: {kind} at B = {B} is not in CAPTURE_VERIFIED ({CAPTURE_VERIFIED}): a replay of this head '
+                                      'and size has not been compared with the eager step; use run()')
+        if not (_is_device_tensor(labels) and labels.dtype == torch.int64 and tuple(labels.shape) == (B,) and labels.is_contiguous()):
+            raise TypeError('capture needs labels as a contiguous [B] int64 device tensor: the graph reads it in place')
+        if jitter is not None and not (_is_device_tensor(jitter) and jitter.dtype == torch.int64 and tuple(jitter.shape) == (B, 2)
+                                       and jitter.is_contiguous()):
+            raise TypeError('capture needs jitter as a contiguous [B, 2] int64 device tensor (or None): the graph reads it in place')
+        lay = self.features.pipe.prepare(so, 0)                # the graph's own: nothing else launches on its tables
+        m0 = self._m0(lay, dev)
+        names = [n for n, p in self.head.named_parameters() if p.requires_grad]
+        params = [p for p in self.head.parameters() if p.requires_grad]
+        handles = [m for m in self.head.modules() if isinstance(m, _NativeHandle)]
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            leaves = [p.detach().requires_grad_(True) for p in params]      # aliases: the optimiser's writes to p are theirs
+        alias = dict(zip(names, leaves))
+
+        def step(record):
+            if record:                                         # the recorded sequence carries the repack
+                for m in handles:
+                    if m._handle is not None:
+                        m._native_handle(dev, refresh='always')
+            out = self._chain(clips, lay, m0, labels, jitter, head_kwargs, alias)
+            with torch.autograd.set_multithreading_enabled(False):      # every recorded launch comes from the capturing thread
+                out.loss.backward()
+            out.loss, out.logits = out.loss.detach(), out.logits.detach()
+            return out
+
+        with torch.enable_grad():
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    for v in leaves:
+                        v.grad = None
+                    warm = step(False)
+            side.synchronize()
+            del warm
+            for v in leaves:
+                v.grad = None
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                result = step(True)
+        grads = [v.grad for v in leaves]
+        for p in params:
+            p.grad = None
+        return _CapturedStep(graph, result, params, grads, [lay, m0, clips, labels, jitter, leaves])

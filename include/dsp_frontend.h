@@ -938,6 +938,55 @@ int dsp_head_lengths_batch(const int32_t* d_len0, int32_t B, int32_t T, int32_t 
 int dsp_head_pool_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const int32_t* d_len, const int32_t* d_rows, float* d_feat,
                         int64_t ld_feat, int32_t col_avg, int32_t col_max, void* stream);
 
+/* ---- training with the lengths on the device: the backward of the pieces above, and handles that survive an optimiser step ----
+ *
+ * dsp_head_pool_batch that also writes d_arg [B, H] int32, the row the max column came from: the smallest t < len whose value
+ * the maximum returned (torch.max's first occurrence; the first NaN row if there is one), and -1 where the padding's 0.0f won
+ * (len < rows and 0 > the maximum over the active rows; a tie between an active 0.0 and the padding goes to the active row).
+ * d_feat is bit for bit dsp_head_pool_batch's.  d_arg NULL is DSP_EINVAL; every other check as dsp_head_pool_batch.
+ */
+int dsp_head_pool_train_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const int32_t* d_len, const int32_t* d_rows, float* d_feat,
+                              int64_t ld_feat, int32_t col_avg, int32_t col_max, int32_t* d_arg, void* stream);
+/*
+ * The backward of the pooling given d_gfeat [B, ld_g], the gradient of d_feat (columns col_avg / col_max as in the forward), the
+ * lengths and d_arg of dsp_head_pool_train_batch.  EVERY element of d_gy [T, B, H] is written exactly once, with
+ * len = clamp(d_len[b], 1, T):
+ *   t <  len:  (col_avg >= 0 ? d_gfeat[b, col_avg + h] / (float)len : 0) + (d_arg[b, h] == t ? d_gfeat[b, col_max + h] : 0)
+ *   t >= len:  0.0f
+ * The quotient is formed once per (b, h).  The gradient of a padding win (d_arg = -1) is dropped: those rows are constants of
+ * the encoders.  One streaming launch, no atomics, no reduction: the same bits on every run; 16-byte stores when H is a
+ * multiple of 4 and d_gy is 16-byte aligned.  Sizes and column checks as dsp_head_pool_batch (against ld_g); anything else or a
+ * NULL pointer is DSP_EINVAL before any device call.  Nothing is allocated or synchronised (capturable).
+ */
+int dsp_head_pool_backward_batch(const float* d_gfeat, int64_t ld_g, int32_t col_avg, int32_t col_max, const int32_t* d_len,
+                                 const int32_t* d_arg, int32_t T, int32_t B, int32_t H, float* d_gy, void* stream);
+/*
+ * The training twins of dsp_selfattn_pool_rows_batch: dsp_selfattn_pool_train_batch / dsp_selfattn_pool_backward_batch over the
+ * first rows = clamp(*d_rows, 1, T) rows of the [T, ..] buffers, the count read from device memory (one wave-uniform read per
+ * workgroup).  Results are bit for bit those of the plain calls on d_y[:rows] (and d_w[:rows]); every element of d_w, d_gy,
+ * d_gpre and d_ge at t >= rows is written as 0.0f.  d_rows NULL is DSP_EINVAL; every other check as the plain calls.
+ */
+int dsp_selfattn_pool_rows_train_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW,
+                                       const float* d_v, const float* d_c, float* d_out, float* d_w, const int32_t* d_rows, void* stream);
+int dsp_selfattn_pool_rows_backward_batch(const float* d_y, int32_t T, int32_t B, int32_t H, const float* d_W, const float* d_bW,
+                                          const float* d_v, const float* d_w, const float* d_gout, float* d_gy, float* d_gpre, float* d_ge,
+                                          float* d_gvpart, const int32_t* d_rows, void* stream);
+/*
+ * Repack the parameters `desc` points to into the handle's EXISTING packed buffer, with launches on `stream`: what a training
+ * loop calls after the optimiser wrote the parameters, instead of destroy + create.  Nothing is allocated or synchronised
+ * (capturable).  The sizes of the descriptor must equal the handle's; anything else, a NULL pointer or (dsp_attn) a dry-run
+ * handle is DSP_EINVAL before any device call.  The two recurrent handles run create's pack kernels; dsp_attn_refresh gathers
+ * the 12 matrices and 7 vectors on the device into the layout create packed on the host (pure data movement: the same bytes;
+ * the zero padding written at create stays).  After a refresh every call through the handle gives the bits a freshly created
+ * handle on the same parameters gives.
+ * ORDERING: the refresh writes the buffer every call through the handle reads.  Work enqueued on `stream` is ordered by the
+ * stream; the caller orders the refresh after earlier uses of the handle on OTHER streams (and later uses there after the
+ * refresh), and after whatever wrote the parameters.
+ */
+int dsp_bigru_refresh(dsp_bigru* h, const dsp_bigru_desc* desc, void* stream);
+int dsp_hmlstm_refresh(dsp_hmlstm* h, const dsp_hmlstm_desc* desc, void* stream);
+int dsp_attn_refresh(dsp_attn* h, const dsp_attn_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

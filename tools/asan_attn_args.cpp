@@ -148,6 +148,22 @@ int main() {
         EXPECT(dsp_attn_backward(keep, 5, 3, buf, tape, x, y, buf, da - 1, buf, wk, nullptr), "are needed");
         EXPECT(dsp_attn_backward(keep, 5, 3, buf, tape, x, y, buf, da, buf, wk, nullptr), "dry_run: launches are refused");
         EXPECT(dsp_attn_backward(keep, 5, 3, buf, tape, x, nullptr, buf, da, buf, wk, nullptr), "dry_run: launches are refused");   // d_gx is optional
+
+        // ---- refresh: the descriptor's sizes must be the handle's, no NULL, and a dry-run handle is refused
+        EXPECT(dsp_attn_refresh(nullptr, &good.d, nullptr), "NULL argument");
+        EXPECT(dsp_attn_refresh(keep, nullptr, nullptr), "NULL argument");
+        { dsp_attn_desc d = good.d; d.n_head = 2; EXPECT(dsp_attn_refresh(keep, &d, nullptr), "differ from the handle's"); }
+        { dsp_attn_desc d = good.d; d.d_model = 38; EXPECT(dsp_attn_refresh(keep, &d, nullptr), "differ from the handle's"); }
+        { dsp_attn_desc d = good.d; d.d_inner = 204; EXPECT(dsp_attn_refresh(keep, &d, nullptr), "differ from the handle's"); }
+        { dsp_attn_desc d = good.d; d.d_k = 96; EXPECT(dsp_attn_refresh(keep, &d, nullptr), "differ from the handle's"); }
+        { dsp_attn_desc d = good.d; d.d_v = 104; EXPECT(dsp_attn_refresh(keep, &d, nullptr), "differ from the handle's"); }
+        { dsp_attn_desc d = good.d; d.eps = 1e-4f; EXPECT(dsp_attn_refresh(keep, &d, nullptr), "eps differs from the handle's"); }
+        for (int i = 0; i < DSP_ATTN_PARAMS; ++i) {
+            dsp_attn_desc d = good.d;
+            d.d_params[i] = nullptr;
+            EXPECT(dsp_attn_refresh(keep, &d, nullptr), "NULL parameter tensor");
+        }
+        EXPECT(dsp_attn_refresh(keep, &good.d, nullptr), "dry_run: launches are refused");
         EXPECT_OK(dsp_attn_destroy(keep));
 
         // d_model = 1: the forward serves it, training does not
