@@ -12,7 +12,8 @@ directory, no matplotlib / sklearn import).  Both pitch trackers (``pitch_detect
 (pitch_model.py:54-61, ensemble.py:44-67) on the device; fitting the SVM stays with sklearn.
 ``get_batch_full(feat)`` is RNNModel.get_batch_full (model.py:114-135) for the reference's list of (sig, rate) pairs, the
 rates mixed as reader.mini_batch_iterator yields them.  ``TrainBatch`` is the training step of model.py:137-147 on raw clips
-with the lengths kept on the device (features/train.py).
+with the lengths kept on the device (features/train.py), and ``DeviceAdam`` its optimiser step (model.py:140-149) with the
+state on the device, recordable behind the backward (features/optim.py).
 There is no CPU fallback: without the built library or without a GPU every compute call raises.
 """
 from .base import *  # noqa: F401,F403
@@ -23,9 +24,10 @@ from .pitch import (center_clip, max_pitch, pitch_detect_frame_sr, pitch_detect_
                     robust_max_pitch, smooth, window, pitch_detect, pitch_detect_frame, peak_score,
                     sub_endpoint_detect, find_smooth_subsequence, slope, quad_params, peakshift, pitch_feature,
                     pitch_feature_batch, pitch_features_device)
-from . import base, sigproc, endpoint, preprocess, pitch, batch, pipeline, ensemble, train  # noqa: F401
+from . import base, sigproc, endpoint, preprocess, pitch, batch, pipeline, ensemble, train, optim  # noqa: F401
 from .batch import FeaturePlan, EndpointPlan  # noqa: F401
 from .pipeline import VadMfccPipeline  # noqa: F401
 from .ensemble import PitchSVM, EnsembleBatch, MixedRateEnsembleBatch, ensemble_decide  # noqa: F401
 from .model_glue import MixedRateFeatureBatch, get_batch_full  # noqa: F401
 from .train import TrainBatch  # noqa: F401
+from .optim import DeviceAdam  # noqa: F401

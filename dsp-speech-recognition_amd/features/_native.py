@@ -181,6 +181,15 @@ SIGNATURES = {
     'dsp_bigru_refresh': (C.c_int, [c_vp, C.POINTER(BigruDesc), c_vp]),
     'dsp_hmlstm_refresh': (C.c_int, [c_vp, C.POINTER(HmlstmDesc), c_vp]),
     'dsp_attn_refresh': (C.c_int, [c_vp, C.POINTER(AttnDesc), c_vp]),
+    'dsp_adam_chunk_elems': (C.c_int, []),
+    'dsp_adam_chunk_table': (C.c_int, [c_i32, c_vp, c_i64, c_vp, c_vp, C.POINTER(c_i64)]),
+    'dsp_adam_create': (C.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_f64, C.POINTER(c_vp)]),
+    'dsp_adam_destroy': (C.c_int, [c_vp]),
+    'dsp_adam_bind_grads': (C.c_int, [c_vp, c_vp, c_vp]),
+    'dsp_adam_set_hyper': (C.c_int, [c_vp, c_f64, c_f64, c_f64, c_f64, c_vp]),
+    'dsp_adam_set_step': (C.c_int, [c_vp, c_i64, c_vp]),
+    'dsp_adam_get_state': (C.c_int, [c_vp, C.POINTER(c_i64), c_vp, c_vp]),
+    'dsp_adam_step': (C.c_int, [c_vp, c_i32, c_vp]),
 }
 
 _lib = None

@@ -7,8 +7,10 @@
   ``len0`` never leaves the device and nothing is synchronised; the caller calls ``loss.backward()``.
 * ``TrainBatch.capture`` records a refresh of every native handle of the head, the front end, the forward, the loss and the
   backward into ONE HIP graph.  ``replay()`` serves new clips, labels and jitter written into the captured buffers and leaves
-  the gradients in ``.grad`` tensors the graph owns.  The optimiser step stays the caller's, eager, after ``replay()``: it
-  writes the parameters in place, and the refresh at the head of the next replay repacks them.
+  the gradients in ``.grad`` tensors the graph owns.  Without ``optimizer=`` the optimiser step stays the caller's, eager,
+  after ``replay()``: it writes the parameters in place, and the refresh at the head of the next replay repacks them.  With
+  ``optimizer=`` a ``features.optim.DeviceAdam`` over the head's trainable parameters, its step is recorded behind the backward:
+  the whole of model.py:137-149 is one replay.
 """
 from __future__ import annotations
 
@@ -36,15 +38,20 @@ class _CapturedStep:
     is synchronised).  ``grads``: the gradient tensors the graph owns, in the order of ``params``; every replay OVERWRITES
     them (it does not accumulate) and makes them the parameters' ``.grad`` again, so an ``optimizer.zero_grad()`` between
     replays -- which drops ``.grad`` -- costs nothing and loses nothing.  ``hold``: every buffer the graph's kernels touch
-    that the result does not already keep alive."""
+    that the result does not already keep alive.  ``optimizer``: the ``DeviceAdam`` whose step the graph carries, or None; with
+    one, a replay also binds the optimiser to ``grads`` (a recorded launch in front of the step, so an eager ``step()`` on other
+    gradients in between does not mislead it), updates the parameters and the optimiser's state, and ``replay()`` bumps the
+    parameters' version counters afterwards."""
 
-    def __init__(self, graph, result, params, grads, hold):
-        self.graph, self.result, self.params, self.grads, self.hold = graph, result, params, grads, hold
+    def __init__(self, graph, result, params, grads, hold, optimizer=None):
+        self.graph, self.result, self.params, self.grads, self.hold, self.optimizer = graph, result, params, grads, hold, optimizer
 
     def replay(self):
         self.graph.replay()
         for p, g in zip(self.params, self.grads):
             p.grad = g
+        if self.optimizer is not None:
+            self.optimizer._after_replay(self.grads)
         return self.result
 
 
@@ -143,14 +150,20 @@ class TrainBatch:
         lay = self._layout(so)
         return self._chain(clips, lay, self._m0(lay, dev), self._labels(labels, B, dev), self._jitter(jitter, B, dev), head_kwargs)
 
-    def capture(self, waves, sample_offsets, labels, jitter=None, **head_kwargs):
-        """ONE HIP graph of a whole step but the optimiser: ``g = tb.capture(waves, so, labels, jitter, dropout=False)``;
+    def capture(self, waves, sample_offsets, labels, jitter=None, optimizer=None, **head_kwargs):
+        """ONE HIP graph of a whole step; without ``optimizer`` all of it but the optimiser: ``g = tb.capture(waves, so, labels, jitter, dropout=False)``;
         ``g.replay()`` does, in order, (1) a refresh of every native handle of the head -- the repack of whatever the
         optimiser wrote since the last replay --, (2) the front end, (3) the forward, (4) the loss and (5) the backward into
         ``.grad`` tensors the graph owns (``g.grads``), which every replay overwrites.  It returns the namespace of ``run``.
         ``waves`` (contiguous device tensor, int16 / float32), ``labels`` (int64 [B] device tensor) and ``jitter`` (int64
         [B, 2] device tensor, or None) are read at their addresses on every replay: write the next batch -- clips of the same
-        lengths -- into them.  The optimiser step stays the caller's, eager, after ``replay()``.
+        lengths -- into them.  With ``optimizer=None`` the optimiser step stays the caller's, eager, after ``replay()``.
+
+        ``optimizer``: a ``features.optim.DeviceAdam`` over exactly the head's trainable parameters, in their order.  The
+        recorded sequence then ends in (6) the binding of the optimiser to ``g.grads`` and its step -- three launches of the
+        library's, nothing of torch's -- and ``replay()`` bumps the parameters' version counters.  ``capture()`` itself changes
+        neither the parameters nor the optimiser's state (the warm-up steps do not step), and ``optimizer.set_lr`` between
+        replays takes effect without a new capture.  ``optimizer=None`` records exactly what it recorded before.
 
         The recipe is torch's for a whole network: warm-up steps on a side stream (they build the native handles and the
         layout's tables), then forward and backward recorded under ``torch.cuda.graph``.  Whatever ``.grad`` the parameters
@@ -193,7 +206,15 @@ class TrainBatch:
         m0 = self._m0(lay, dev)
         names = [n for n, p in self.head.named_parameters() if p.requires_grad]
         params = [p for p in self.head.parameters() if p.requires_grad]
+        if optimizer is not None:
+            from .optim import DeviceAdam
+            if not isinstance(optimizer, DeviceAdam):
+                raise TypeError(f'capture: optimizer must be a features.optim.DeviceAdam or None, not {type(optimizer).__name__}: only its '
+                                'step can be recorded')
+            if len(optimizer.params) != len(params) or any(a is not b for a, b in zip(optimizer.params, params)):
+                raise ValueError("capture: the optimizer's parameters must be the head's trainable parameters, in their order")
         handles = [m for m in self.head.modules() if isinstance(m, _NativeHandle)]
+        bound = None if optimizer is None else optimizer._bound
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -208,6 +229,8 @@ class TrainBatch:
             out = self._chain(clips, lay, m0, labels, jitter, head_kwargs, alias)
             with torch.autograd.set_multithreading_enabled(False):      # every recorded launch comes from the capturing thread
                 out.loss.backward()
+            if record and optimizer is not None:               # the graph's own gradients: their addresses are known from here on
+                optimizer._launch([v.grad for v in leaves], False, rebind='always')
             out.loss, out.logits = out.loss.detach(), out.logits.detach()
             return out
 
@@ -227,4 +250,6 @@ class TrainBatch:
         grads = [v.grad for v in leaves]
         for p in params:
             p.grad = None
-        return _CapturedStep(graph, result, params, grads, [lay, m0, clips, labels, jitter, leaves])
+        if optimizer is not None:
+            optimizer._bound = bound                           # the recorded binding has not run yet
+        return _CapturedStep(graph, result, params, grads, [lay, m0, clips, labels, jitter, leaves], optimizer)

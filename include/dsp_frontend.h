@@ -987,6 +987,46 @@ int dsp_bigru_refresh(dsp_bigru* h, const dsp_bigru_desc* desc, void* stream);
 int dsp_hmlstm_refresh(dsp_hmlstm* h, const dsp_hmlstm_desc* desc, void* stream);
 int dsp_attn_refresh(dsp_attn* h, const dsp_attn_desc* desc, void* stream);
 
+/* ---- device-resident Adam: the optimiser step of model.py:140-149 (torch.optim.Adam, weight_decay = 0, amsgrad off), capturable ----
+ *
+ * A handle owns, in ONE device allocation, the step count, the hyper-parameters (fp64), the pointer tables of n fp32 tensors
+ * (parameter p, first moment m, second moment v, gradient g) and a chunk table.  dsp_adam_step is two launches on `stream`:
+ *   1. one thread: t = ++step; step_size = lr / (1 - beta1^t) and bc2 = sqrt(1 - beta2^t), formed in fp64, rounded to fp32 once;
+ *   2. every tensor in one launch, per element (fp32, every product, sum, quotient and root rounded to nearest):
+ *        m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;  p = p - step_size * (m / (sqrt(v) / bc2 + eps))
+ *      zero_grads != 0 also writes 0.0f over each gradient after reading it (zero_grad(set_to_none=False)).
+ * A workgroup takes chunks of dsp_adam_chunk_elems() elements of ONE tensor (the table is built at create) and reads its
+ * descriptor wave-uniformly; a lane does 16-byte loads and stores where p, g, m and v of the tensor are all 16-byte aligned,
+ * 4-byte ones for any other tensor and for the tail numel % 4: alignment changes the route, never the bits.  No atomics, no
+ * LDS, no memset; every element belongs to exactly one lane: the same bits on every run.  Everything the two launches read
+ * -- tables, hyper-parameters, step count -- is read from device memory when they RUN: a recorded dsp_adam_step follows
+ * dsp_adam_set_hyper / dsp_adam_set_step / dsp_adam_bind_grads calls made between replays.
+ *
+ * dsp_adam_create allocates and uploads (blocking, like every create here); the step count starts at 0.  bind_grads, set_hyper,
+ * set_step and step only launch on `stream`: nothing is allocated, copied from host memory or synchronised (capturable).
+ * dsp_adam_get_state reads step and hyper[4] = {lr, beta1, beta2, eps} back and synchronises `stream`.
+ * DSP_EINVAL with a message before any device call: a NULL argument or pointer, n <= 0, numel <= 0, beta outside [0, 1),
+ * eps < 0, a non-finite lr or eps, a pointer that is not 4-byte aligned, a negative step, p / m / v (and, in bind_grads, g)
+ * ranges that overlap each other, a step before any bind_grads, a handle of another device.  Under dsp_debug_host_dry_run(1)
+ * the tables stay in host memory: such a handle can only be destroyed, launches are refused.
+ *
+ * dsp_adam_chunk_table is the table builder alone, host only (no device): chunk k covers elements
+ * [offset[k], min(offset[k] + dsp_adam_chunk_elems(), numel[tensor[k]])) of tensor[k]; tensors in order, offsets ascending, every
+ * element of every tensor in exactly one chunk.  *n_chunks is always written; tensor and offset both NULL asks for the count alone,
+ * otherwise capacity must hold it.
+ */
+typedef struct dsp_adam dsp_adam;
+int dsp_adam_chunk_elems(void);
+int dsp_adam_chunk_table(int32_t n, const int64_t* numel, int64_t capacity, int32_t* tensor, int64_t* offset, int64_t* n_chunks);
+int dsp_adam_create(int32_t n, const int64_t* numel, float* const* d_p, float* const* d_m, float* const* d_v, double lr, double beta1,
+                    double beta2, double eps, dsp_adam** out);
+int dsp_adam_destroy(dsp_adam* h);
+int dsp_adam_bind_grads(dsp_adam* h, float* const* d_g, void* stream);
+int dsp_adam_set_hyper(dsp_adam* h, double lr, double beta1, double beta2, double eps, void* stream);
+int dsp_adam_set_step(dsp_adam* h, int64_t step, void* stream);
+int dsp_adam_get_state(const dsp_adam* h, int64_t* step, double* hyper, void* stream);
+int dsp_adam_step(dsp_adam* h, int32_t zero_grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,199 @@
+// Stand-alone host check of the optimiser entry points (include/dsp_frontend.h: dsp_adam_*; csrc/dsp_optim.hip): the chunk-table
+// builder (every element of every tensor in exactly one chunk, nothing written behind the capacity), and every argument check --
+// DSP_EINVAL with a message before any device call; under dsp_debug_host_dry_run(1) dsp_adam_create builds its tables in host memory
+// and what passed every check is refused instead of launched: the program needs no GPU.
+// `make -C dsp-speech-recognition_amd/csrc asan-optim` builds it with AddressSanitizer + UBSan against the sanitized build of the
+// library and runs it; it needs no preloaded runtime.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "dsp_frontend.h"
+
+static int g_bad = 0;
+
+static void expect(int rc, const char* what, int line) {
+    const char* e = dsp_last_error();
+    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
+        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
+        ++g_bad;
+    }
+}
+#define EXPECT(call, what) expect((call), (what), __LINE__)
+#define REQUIRE(cond)                                                   \
+    do {                                                                \
+        if (!(cond)) {                                                  \
+            std::printf("line %d: %s does not hold\n", __LINE__, #cond); \
+            ++g_bad;                                                    \
+        }                                                               \
+    } while (0)
+
+// Every element of every tensor in exactly one chunk; exactly-sized output arrays, so a write behind them is the sanitizer's.
+static void check_cover(const std::vector<int64_t>& numel) {
+    const int32_t n = (int32_t)numel.size();
+    const int64_t C = dsp_adam_chunk_elems();
+    int64_t nc = -1;
+    REQUIRE(dsp_adam_chunk_table(n, numel.data(), 0, nullptr, nullptr, &nc) == DSP_OK);
+    int64_t want = 0;
+    for (int64_t v : numel) want += (v + C - 1) / C;
+    REQUIRE(nc == want);
+    std::vector<int32_t> tensor((size_t)nc);
+    std::vector<int64_t> offset((size_t)nc);
+    int64_t nc2 = -1;
+    REQUIRE(dsp_adam_chunk_table(n, numel.data(), nc, tensor.data(), offset.data(), &nc2) == DSP_OK && nc2 == nc);
+    std::vector<std::vector<uint8_t>> seen;
+    for (int64_t v : numel) seen.emplace_back((size_t)v, 0);
+    for (int64_t k = 0; k < nc; ++k) {
+        const int32_t t = tensor[(size_t)k];
+        const int64_t off = offset[(size_t)k];
+        REQUIRE(t >= 0 && t < n && off >= 0 && off % C == 0 && off < numel[(size_t)t]);
+        if (t < 0 || t >= n || off < 0) continue;
+        for (int64_t i = off; i < off + C && i < numel[(size_t)t]; ++i) ++seen[(size_t)t][(size_t)i];
+    }
+    for (const auto& s : seen)
+        for (uint8_t c : s) REQUIRE(c == 1);
+}
+
+int main() {
+    const int64_t C = dsp_adam_chunk_elems();
+    REQUIRE(C >= 4 && C % 4 == 0);
+    check_cover({1, 3, 4, 5, 63, 64, 1023, C - 1, C, C + 1, 3 * C + 7});
+    check_cover({3 * C + 7, 1});
+    check_cover({1});
+
+    // never reached by a kernel: every call below returns before a launch
+    alignas(16) static float buf[64];
+    const int64_t numel[2] = {5, 3};
+    float* P[2] = {buf + 0, buf + 8};
+    float* M[2] = {buf + 16, buf + 24};
+    float* V[2] = {buf + 32, buf + 40};
+    dsp_adam* h = nullptr;
+    const double nan = std::nan(""), inf = INFINITY;
+
+    EXPECT(dsp_adam_create(2, numel, P, M, V, 1e-3, 0.9, 0.999, 1e-8, nullptr), "NULL argument");
+    EXPECT(dsp_adam_create(2, nullptr, P, M, V, 1e-3, 0.9, 0.999, 1e-8, &h), "NULL argument");
+    EXPECT(dsp_adam_create(2, numel, nullptr, M, V, 1e-3, 0.9, 0.999, 1e-8, &h), "NULL argument");
+    EXPECT(dsp_adam_create(2, numel, P, nullptr, V, 1e-3, 0.9, 0.999, 1e-8, &h), "NULL argument");
+    EXPECT(dsp_adam_create(2, numel, P, M, nullptr, 1e-3, 0.9, 0.999, 1e-8, &h), "NULL argument");
+    EXPECT(dsp_adam_create(0, numel, P, M, V, 1e-3, 0.9, 0.999, 1e-8, &h), "n 0 must be >= 1");
+    EXPECT(dsp_adam_create(-1, numel, P, M, V, 1e-3, 0.9, 0.999, 1e-8, &h), "n -1 must be >= 1");
+    {
+        const int64_t zero[2] = {5, 0}, neg[2] = {-1, 3}, huge[2] = {5, ((int64_t)1 << 40) + 1};
+        EXPECT(dsp_adam_create(2, zero, P, M, V, 1e-3, 0.9, 0.999, 1e-8, &h), "numel[1] 0 must be in [1, 2^40]");
+        EXPECT(dsp_adam_create(2, neg, P, M, V, 1e-3, 0.9, 0.999, 1e-8, &h), "numel[0] -1 must be in [1, 2^40]");
+        EXPECT(dsp_adam_create(2, huge, P, M, V, 1e-3, 0.9, 0.999, 1e-8, &h), "numel[1] 1099511627777 must be in [1, 2^40]");
+    }
+    EXPECT(dsp_adam_create(2, numel, P, M, V, nan, 0.9, 0.999, 1e-8, &h), "lr is not finite");
+    EXPECT(dsp_adam_create(2, numel, P, M, V, -inf, 0.9, 0.999, 1e-8, &h), "lr is not finite");
+    EXPECT(dsp_adam_create(2, numel, P, M, V, 1e-3, 1.0, 0.999, 1e-8, &h), "beta1 1 must be in [0, 1)");
+    EXPECT(dsp_adam_create(2, numel, P, M, V, 1e-3, -0.1, 0.999, 1e-8, &h), "beta1 -0.1 must be in [0, 1)");
+    EXPECT(dsp_adam_create(2, numel, P, M, V, 1e-3, nan, 0.999, 1e-8, &h), "beta1");
+    EXPECT(dsp_adam_create(2, numel, P, M, V, 1e-3, 0.9, 1.0, 1e-8, &h), "beta2 1 must be in [0, 1)");
+    EXPECT(dsp_adam_create(2, numel, P, M, V, 1e-3, 0.9, -1.0, 1e-8, &h), "beta2 -1 must be in [0, 1)");
+    EXPECT(dsp_adam_create(2, numel, P, M, V, 1e-3, 0.9, nan, 1e-8, &h), "beta2");
+    EXPECT(dsp_adam_create(2, numel, P, M, V, 1e-3, 0.9, 0.999, -1e-8, &h), "eps -1e-08 must be finite and >= 0");
+    EXPECT(dsp_adam_create(2, numel, P, M, V, 1e-3, 0.9, 0.999, nan, &h), "eps");
+    EXPECT(dsp_adam_create(2, numel, P, M, V, 1e-3, 0.9, 0.999, inf, &h), "eps");
+    {
+        float* p_null[2] = {buf, nullptr};
+        float* m_null[2] = {nullptr, buf + 24};
+        float* v_null[2] = {buf + 32, nullptr};
+        EXPECT(dsp_adam_create(2, numel, p_null, M, V, 1e-3, 0.9, 0.999, 1e-8, &h), "NULL pointer p[1]");
+        EXPECT(dsp_adam_create(2, numel, P, m_null, V, 1e-3, 0.9, 0.999, 1e-8, &h), "NULL pointer m[0]");
+        EXPECT(dsp_adam_create(2, numel, P, M, v_null, 1e-3, 0.9, 0.999, 1e-8, &h), "NULL pointer v[1]");
+        float* p_odd[2] = {reinterpret_cast<float*>(reinterpret_cast<char*>(buf) + 2), buf + 8};
+        EXPECT(dsp_adam_create(2, numel, p_odd, M, V, 1e-3, 0.9, 0.999, 1e-8, &h), "p[0] is not 4-byte aligned");
+        float* p_ov[2] = {buf, buf + 4};            // 5 elements at 0 reach into 4
+        float* m_ov[2] = {buf + 16, buf + 2};       // m[1] inside p[0]
+        float* v_ov[2] = {buf + 20, buf + 40};      // v[0] starts inside m[0]
+        float* v_same[2] = {buf + 32, buf + 8};     // v[1] is p[1]
+        float* p_touch[2] = {buf + 0, buf + 5};     // adjacent ranges do not overlap: this one passes
+        EXPECT(dsp_adam_create(2, numel, p_ov, M, V, 1e-3, 0.9, 0.999, 1e-8, &h), "p[0] and p[1] overlap");
+        EXPECT(dsp_adam_create(2, numel, P, m_ov, V, 1e-3, 0.9, 0.999, 1e-8, &h), "p[0] and m[1] overlap");
+        EXPECT(dsp_adam_create(2, numel, P, M, v_ov, 1e-3, 0.9, 0.999, 1e-8, &h), "m[0] and v[0] overlap");
+        EXPECT(dsp_adam_create(2, numel, P, M, v_same, 1e-3, 0.9, 0.999, 1e-8, &h), "overlap");
+        REQUIRE(h == nullptr);
+        dsp_debug_host_dry_run(1);
+        REQUIRE(dsp_adam_create(2, numel, p_touch, M, V, 1e-3, 0.9, 0.999, 1e-8, &h) == DSP_OK && h);
+        REQUIRE(dsp_adam_destroy(h) == DSP_OK);
+        dsp_debug_host_dry_run(0);
+        h = nullptr;
+    }
+
+    EXPECT(dsp_adam_bind_grads(nullptr, P, nullptr), "NULL argument");
+    EXPECT(dsp_adam_set_hyper(nullptr, 1e-3, 0.9, 0.999, 1e-8, nullptr), "NULL argument");
+    EXPECT(dsp_adam_set_step(nullptr, 0, nullptr), "NULL argument");
+    int64_t step = 0;
+    double hyper[4];
+    EXPECT(dsp_adam_get_state(nullptr, &step, hyper, nullptr), "NULL argument");
+    EXPECT(dsp_adam_step(nullptr, 0, nullptr), "NULL argument");
+    REQUIRE(dsp_adam_destroy(nullptr) == DSP_OK);
+
+    int64_t nc = 0, one_off[1];
+    int32_t one_t[1];
+    EXPECT(dsp_adam_chunk_table(2, nullptr, 0, nullptr, nullptr, &nc), "NULL argument");
+    EXPECT(dsp_adam_chunk_table(2, numel, 0, nullptr, nullptr, nullptr), "NULL argument");
+    EXPECT(dsp_adam_chunk_table(0, numel, 0, nullptr, nullptr, &nc), "n 0 must be >= 1");
+    EXPECT(dsp_adam_chunk_table(2, numel, 2, one_t, nullptr, &nc), "NULL argument");
+    EXPECT(dsp_adam_chunk_table(2, numel, 2, nullptr, one_off, &nc), "NULL argument");
+    EXPECT(dsp_adam_chunk_table(2, numel, 1, one_t, one_off, &nc), "capacity 1 is below the 2 chunks");
+    EXPECT(dsp_adam_chunk_table(2, numel, -1, one_t, one_off, &nc), "capacity -1 is below the 2 chunks");
+
+    // a dry-run handle: the tables are built (and freed) in host memory, every launch is refused
+    dsp_debug_host_dry_run(1);
+    const char* refused = "dsp_debug_host_dry_run: launches are refused";
+    {
+        // many tensors, several chunks each: the blob's layout under the sanitizer
+        std::vector<int64_t> big = {1, 3, 4, 5, 63, 64, 1023, C - 1, C, C + 1, 3 * C + 7};
+        std::vector<float*> bp, bm, bv;
+        float* fake = reinterpret_cast<float*>(uintptr_t(1) << 32);     // addresses only: nothing is dereferenced
+        for (int64_t v : big) {
+            bp.push_back(fake); fake += v;
+            bm.push_back(fake); fake += v;
+            bv.push_back(fake); fake += v;
+        }
+        dsp_adam* hb = nullptr;
+        REQUIRE(dsp_adam_create((int32_t)big.size(), big.data(), bp.data(), bm.data(), bv.data(), 1e-3, 0.9, 0.999, 1e-8, &hb) == DSP_OK && hb);
+        std::vector<float*> bg;
+        for (int64_t v : big) { bg.push_back(fake); fake += v; }
+        EXPECT(dsp_adam_bind_grads(hb, bg.data(), nullptr), refused);
+        bg[3] = bp[2];
+        EXPECT(dsp_adam_bind_grads(hb, bg.data(), nullptr), "overlap");
+        REQUIRE(dsp_adam_destroy(hb) == DSP_OK);
+    }
+    REQUIRE(dsp_adam_create(2, numel, P, M, V, 1e-3, 0.9, 0.999, 1e-8, &h) == DSP_OK && h);
+    if (h) {
+        float* G[2] = {buf + 48, buf + 56};
+        float* g_null[2] = {buf + 48, nullptr};
+        float* g_ov[2] = {buf + 48, buf + 50};
+        float* g_v[2] = {buf + 48, buf + 42};       // g[1] reaches into v[1]
+        float* g_odd[2] = {buf + 48, reinterpret_cast<float*>(reinterpret_cast<char*>(buf + 56) + 1)};
+        EXPECT(dsp_adam_step(h, 0, nullptr), "no gradients are bound");
+        EXPECT(dsp_adam_bind_grads(h, nullptr, nullptr), "NULL argument");
+        EXPECT(dsp_adam_bind_grads(h, g_null, nullptr), "NULL pointer g[1]");
+        EXPECT(dsp_adam_bind_grads(h, g_odd, nullptr), "g[1] is not 4-byte aligned");
+        EXPECT(dsp_adam_bind_grads(h, g_ov, nullptr), "g[0] and g[1] overlap");
+        EXPECT(dsp_adam_bind_grads(h, g_v, nullptr), "v[1] and g[1] overlap");
+        EXPECT(dsp_adam_bind_grads(h, G, nullptr), refused);
+        EXPECT(dsp_adam_step(h, 1, nullptr), "no gradients are bound");      // a refused bind binds nothing
+        EXPECT(dsp_adam_set_hyper(h, nan, 0.9, 0.999, 1e-8, nullptr), "lr is not finite");
+        EXPECT(dsp_adam_set_hyper(h, 1e-3, 1.0, 0.999, 1e-8, nullptr), "beta1 1 must be in [0, 1)");
+        EXPECT(dsp_adam_set_hyper(h, 1e-3, 0.9, -0.5, 1e-8, nullptr), "beta2 -0.5 must be in [0, 1)");
+        EXPECT(dsp_adam_set_hyper(h, 1e-3, 0.9, 0.999, -1.0, nullptr), "eps -1 must be finite and >= 0");
+        EXPECT(dsp_adam_set_hyper(h, 0.8e-3, 0.9, 0.999, 1e-8, nullptr), refused);
+        EXPECT(dsp_adam_set_hyper(h, 0.0, 0.0, 0.0, 0.0, nullptr), refused);  // the edges of every range
+        EXPECT(dsp_adam_set_step(h, -1, nullptr), "step -1 must be >= 0");
+        EXPECT(dsp_adam_set_step(h, 10000, nullptr), refused);
+        EXPECT(dsp_adam_get_state(h, nullptr, hyper, nullptr), "NULL argument");
+        EXPECT(dsp_adam_get_state(h, &step, nullptr, nullptr), "NULL argument");
+        EXPECT(dsp_adam_get_state(h, &step, hyper, nullptr), refused);
+        REQUIRE(dsp_adam_destroy(h) == DSP_OK);
+    }
+    dsp_debug_host_dry_run(0);
+
+    if (g_bad) { std::printf("asan_optim_args: %d FAILED\n", g_bad); return 1; }
+    std::printf("asan_optim_args: ok\n");
+    return 0;
+}

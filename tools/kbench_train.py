@@ -8,7 +8,10 @@ step -- of ``HMRNNHead`` and ``TransformerHead`` (seeded weights, training mode,
       host_keep  the same step with the optimiser working on a shadow copy of the parameters, so that the handles stay:
                (1) minus this is what the handle re-creation costs;
   (2) run      ``TrainBatch.run`` + ``backward``: lengths on the device, handles repacked in place, nothing synchronised;
-  (3) replay   ``TrainBatch.capture(...).replay()``: refresh, front end, forward, loss and backward as ONE HIP graph
+  (3) replay   ``TrainBatch.capture(...).replay()``: refresh, front end, forward, loss and backward as ONE HIP graph, the eager
+               Adam step behind it;
+  (4) replay_adam  ``TrainBatch.capture(..., optimizer=DeviceAdam(...)).replay()``: the same graph with the native Adam step
+               (csrc/kernels_optim.h) recorded behind the backward -- the whole step is one replay
 
 at B = 32 (the reference's cfg.batch_size) and B = 512, on the stored 16 kHz chirps of tests/ensemble_cases.py, repeated.
 
@@ -16,7 +19,14 @@ The host route takes the jitter as a host array and uploads it on every step (16
 what that route does in a training loop; the device routes read a jitter already on the device.  ``capture`` serves the head / size
 pairs of ``features.train.CAPTURE_VERIFIED``, which hold the defaults here.
 
-Every figure is a host clock around --iters back-to-back steps that end in a device synchronise, divided by --iters, after
+Routes (3) and (4) are also timed with device events round the same --iters steps (``*_event_us``).  The ``adam`` section times
+the optimiser step ALONE on each head's parameter list with random gradients, device events round --adam-iters back-to-back
+steps: ``DeviceAdam.step()`` against ``torch.optim.Adam.step()`` in its default, ``foreach=False`` and ``fused=True`` forms, the
+median of --rounds rounds with the spread (max - min), and the bytes per second ``DeviceAdam`` moves (28 bytes per parameter:
+p, m, v read and written, g read); ``device_adam_graph`` is the native step per step of 20 recorded as one graph, i.e. its two
+launches without the host side of ``step()``.
+
+Every other figure is a host clock around --iters back-to-back steps that end in a device synchronise, divided by --iters, after
 --warmup steps; the routes are timed one after the other in each of --rounds rounds and the median round is reported (all
 rounds are kept in the JSON).  Writes --out (default profiles/train_kbench.json) and prints it as one JSON line.
 
@@ -47,11 +57,63 @@ def per_step_us(torch, dev, fn, iters, warmup):
     return (time.perf_counter() - t0) / iters * 1e6
 
 
+def per_step_event_us(torch, dev, fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize(dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / iters
+
+
+def adam_alone(torch, dev, head, iters, warmup, rounds):
+    """The optimiser step alone on the head's parameter list, each optimiser on its own copy, random gradients."""
+    from features.optim import DeviceAdam
+    gen = torch.Generator(device='cpu').manual_seed(7)
+    base = [p.detach().clone() for p in head.parameters() if p.requires_grad]
+    grads = [(1e-2 * torch.randn(p.shape, generator=gen)).to(dev) for p in base]
+    makers = {'device_adam': lambda ps: DeviceAdam(ps, lr=1e-4), 'torch_default': lambda ps: torch.optim.Adam(ps, lr=1e-4),
+              'torch_foreach_false': lambda ps: torch.optim.Adam(ps, lr=1e-4, foreach=False),
+              'torch_fused': lambda ps: torch.optim.Adam(ps, lr=1e-4, fused=True)}
+    opts = {}
+    for name, make in makers.items():
+        ps = [p.clone().requires_grad_(True) for p in base]
+        for p, g in zip(ps, grads):
+            p.grad = g.clone()
+        opts[name] = make(ps)
+    times = {name: [] for name in makers}
+    for _ in range(rounds):
+        for name, opt in opts.items():
+            times[name].append(per_step_event_us(torch, dev, opt.step, iters, warmup))
+    # ... and 20 native steps recorded as one graph: the two launches of a step without the host side of step()
+    dopt = opts['device_adam']
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        for _ in range(20):
+            dopt._launch([p.grad for p in dopt.params], False)
+    times['device_adam_graph'] = [per_step_event_us(torch, dev, graph.replay, max(iters // 20, 1), warmup) / 20 for _ in range(rounds)]
+    n = sum(p.numel() for p in base)
+    row = {'tensors': len(base), 'parameters': n, 'bytes_per_step': 28 * n, 'rounds': times}
+    for name, v in times.items():
+        row[name + '_us'] = float(np.median(v))
+        row[name + '_spread_us'] = float(max(v) - min(v))
+    row['device_adam_bytes_per_s'] = 28 * n / (row['device_adam_us'] * 1e-6)
+    row['device_adam_graph_bytes_per_s'] = 28 * n / (row['device_adam_graph_us'] * 1e-6)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--adam-iters', type=int, default=200)
     ap.add_argument('--batches', default='32,512')
     ap.add_argument('--heads', default='hmrnn,transformer')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'train_kbench.json'))
@@ -61,15 +123,22 @@ def main():
     from features import _native as nat
     from features.classifier import HMRNNHead, TransformerHead, fill_parameters
     from features.model_glue import ModelFeatureBatch
+    from features.optim import DeviceAdam
     from features.train import TrainBatch
     nat.require_device()
     dev = torch.device('cuda', nat.current_device())
     stored, rate = make_clips()
     kinds = {'hmrnn': (HMRNNHead, dict(native=True, native_enc=True)), 'transformer': (TransformerHead, dict(native_enc=True, native_attn=True))}
     res = {'iters': args.iters, 'warmup': args.warmup, 'rounds': args.rounds, 'optimizer': 'torch.optim.Adam(lr=1e-4), eager',
-           'clock': 'host clock around iters steps ending in a device synchronise', 'steps': {}}
+           'clock': 'host clock around iters steps ending in a device synchronise; *_event_us and the adam section: device events',
+           'adam': {}, 'steps': {}}
     for kind in args.heads.split(','):
         cls, host_kw = kinds[kind]
+        torch.manual_seed(0)
+        row = adam_alone(torch, dev, cls().to(dev), args.adam_iters, args.warmup, args.rounds)
+        res['adam'][kind] = row
+        print(f'{kind} Adam alone ({row["tensors"]} tensors, {row["parameters"]} parameters): '
+              + ', '.join(f'{k}={v:.1f}' for k, v in row.items() if k.endswith('_us')) + f', {row["device_adam_bytes_per_s"] / 1e12:.2f} TB/s eager, {row["device_adam_graph_bytes_per_s"] / 1e12:.2f} TB/s recorded', flush=True)
         for B in (int(v) for v in args.batches.split(',')):
             torch.manual_seed(0)
             head = cls().train()
@@ -105,7 +174,8 @@ def main():
                 out.loss.backward()
                 opt.step()
 
-            rounds = {'host_us': [], 'host_keep_us': [], 'run_us': [], 'replay_us': []}
+            rounds = {'host_us': [], 'host_keep_us': [], 'run_us': [], 'replay_us': [], 'replay_event_us': [], 'replay_adam_us': [],
+                      'replay_adam_event_us': []}
             for _ in range(args.rounds):
                 rounds['host_us'].append(per_step_us(torch, dev, host, args.iters, args.warmup))
                 rounds['host_keep_us'].append(per_step_us(torch, dev, lambda: host(True), args.iters, args.warmup))
@@ -117,17 +187,25 @@ def main():
                 g.replay()
                 opt.step()
 
+            # the same head goes on training under the native optimiser: one replay is the whole step
+            dopt = DeviceAdam(params, lr=1e-4)
+            g2 = tb.capture(buf, so, labels, d_jit, optimizer=dopt)
             for _ in range(args.rounds):
                 rounds['replay_us'].append(per_step_us(torch, dev, replay, args.iters, args.warmup))
+                rounds['replay_event_us'].append(per_step_event_us(torch, dev, replay, args.iters, args.warmup))
+                rounds['replay_adam_us'].append(per_step_us(torch, dev, g2.replay, args.iters, args.warmup))
+                rounds['replay_adam_event_us'].append(per_step_event_us(torch, dev, g2.replay, args.iters, args.warmup))
             row = {k: float(np.median(v)) for k, v in rounds.items()}
             row['handle_rebuild_us'] = row['host_us'] - row['host_keep_us']
             row['host_over_run'] = row['host_us'] / row['run_us']
             row['host_over_replay'] = row['host_us'] / row['replay_us']
+            row['replay_over_replay_adam'] = row['replay_us'] / row['replay_adam_us']
+            row['spreads'] = {k: float(max(v) - min(v)) for k, v in rounds.items()}
             row['seconds_of_audio'] = float(so[-1]) / rate
             row['rounds'] = rounds
             res['steps'][f'{kind}_B{B}'] = row
             print(f'{kind} B={B}: ' + ', '.join(f'{k}={v:.0f}' for k, v in row.items() if k.endswith('_us')), flush=True)
-            del g
+            del g, g2
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as fh:
         json.dump(res, fh, indent=1)
