@@ -150,6 +150,9 @@ __host__ __device__ constexpr int f512_cbase(int c) { return ((c & 1) ? 2 : 0) ^
 typedef float f512_f2u __attribute__((ext_vector_type(2), aligned(4)));
 
 #define F512_FENCE() asm volatile("" ::: "memory")
+// Listing markers (comments in the assembly, no instruction): tools/pipe_cycles.py prices the hot path of a group and
+// leaves out, or reports on its own, what lies between a begin and its end.
+#define F512_PATH(s) asm volatile("; F512_PATH " s)
 
 // Diagnostic build (-DF512_STAMPS, see tools/kbench.py): every wave accumulates the shader-clock span of
 // each phase of its groups in registers and adds them to a per-wave slot at exit; phases are pinned with
@@ -227,6 +230,13 @@ template <int ROW0>
 __device__ __forceinline__ void f512_load_rows1(uint32_t fr, uint32_t wn, f512_v2& xv, f512_v2& wv) {
     asm volatile("ds_read_b64 %0, %2 offset:%4\n\tds_read_b64 %1, %3 offset:%4\n\ts_waitcnt lgkmcnt(0)"
                  : "=&v"(xv), "=&v"(wv) : "v"(fr), "v"(wn), "n"(64 * ROW0) : "memory");
+}
+// Two dwords to LDS at two dword offsets (0 .. 255) from one byte address: ONE ds_write2_b32.  From inline asm, because
+// the compiler pairs only stores it finds next to each other after scheduling (4 of the 16 pairs of the spectrum row).
+template <int OFF0, int OFF1>
+__device__ __forceinline__ void f512_lds_store2(uint32_t addr, float a, float b) {
+    static_assert(OFF0 >= 0 && OFF0 < 256 && OFF1 >= 0 && OFF1 < 256, "ds_write2_b32 offsets are 8-bit dword counts");
+    asm volatile("ds_write2_b32 %0, %1, %2 offset0:%3 offset1:%4" :: "v"(addr), "v"(a), "v"(b), "n"(OFF0), "n"(OFF1) : "memory");
 }
 // z[ROW0 ..] = x * w for rows ROW0 .. NROWS-1, eight at a time
 template <int NROWS, int ROW0>
@@ -675,6 +685,7 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
                 }
             }
         } else if (!RAGGED) {
+            F512_PATH("slow_stage begin");
             // Dense batch, end of an utterance: zero padding past its last sample and, for flat grouping, the
             // first frames of the NEXT utterance as a second segment `seam_off` floats behind where they would
             // sit otherwise (frame slot f >= nf1 reads from f S + seam_off), so the two utterances' samples
@@ -716,7 +727,9 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
                 y.w = __uint_as_float(__float_as_uint(y.w) & m);
                 if (v < span_vec) *reinterpret_cast<float4*>(wbuf + p) = y;
             }
+            F512_PATH("slow_stage end");
         } else {
+            F512_PATH("slow_stage begin");
             {
                 const int64_t a0 = g0 - d;                         // aligned element index of LDS slot 0
                 const int span_vec = RAGGED ? P.span_vec + 1 : P.span_vec;
@@ -775,6 +788,7 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
                     if (NSTAGE * 256 <= F512_WAVE_FLOATS || v < span_vec) *reinterpret_cast<float4*>(wbuf + 4 * v) = y;
                 }
             }
+            F512_PATH("slow_stage end");
         }
         if constexpr (FD != 0) fd_cy_utt = (fast_stage && 8 * P.S == 256 * (NSTAGE - 1)) ? utt : -1;
         if constexpr (RAGGED) {
@@ -965,6 +979,7 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
         // power spectrum |X|^2 / 512: rows carry a factor 2 -> 1/2048.  That power of two is applied
         // (exactly) to the mel weights at plan time and to the energy sum once, not to every bin.
         float p0[16], p1[16];
+        float* const ps = wbuf + f * F512_PS_STRIDE;   // the frame's spectrum row in LDS
         constexpr float S1 = 1.0f / 2048.0f;
 #ifndef F512_COOP
         constexpr float S2 = 1.0f / 16.0f;   // the packed unit carries 8, not 2
@@ -986,15 +1001,13 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
 #else
         // Slot layout of p0 (unit 0): p0[k] -> bin c + 32 k (k < 8), bin 512 - 32 k - c (k >= 8).
         // Lane 0 (c = 0) owns bins 16 j instead: the even ones (32 k) fit the same slots, bin 256 is
-        // slot 8, slots 9..15 repeat bins 224..32, and the 8 odd ones (16, 48, .., 240) go to podd[].
-        float podd[8];
+        // slot 8, slots 9..15 repeat bins 224..32, and the 8 odd ones (16, 48, .., 240) are stored where they are made.
         // energy: every lane sums its 32 bins; lane 0's first unit is replaced by its 17 distinct bins below
         float e0 = p0[0], e1 = p1[0];
 #pragma unroll
         for (int k = 1; k < 16; ++k) { e0 += p0[k]; e1 += p1[k]; }
-#pragma unroll
-        for (int m = 0; m < 8; ++m) podd[m] = 0.f;
         if (c == 0) {
+            F512_PATH("c0 begin");
             // u0 = FFT16 of r[2m] + i r[2m+1]; finish the 32-point real FFT R[j] = X[16 j], j = 0..16
             // (factor 8 carried: 1/16 relative to the other units)
             float R[17];
@@ -1022,8 +1035,18 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
             for (int k = 0; k < 8; ++k) {
                 p0[k] = R[2 * k];
                 p0[8 + k] = R[16 - 2 * k];
-                podd[k] = R[2 * k + 1];
             }
+            // The odd bins 16 + 32 m go to the frame's spectrum row from here, in pairs: no lane holds registers for them
+            // outside this branch.  The row aliases the exchange buffers of this frame and the next, which every lane of
+            // the wave has read by now (the wave's LDS operations complete in order); no other store writes these bins.
+            {
+                const uint32_t pa = f512_lds_addr(ps);
+                f512_static_for<0, 4>([&](auto hc) {
+                    constexpr int m = 2 * decltype(hc)::value;
+                    f512_lds_store2<32 * m + 16, 32 * m + 48>(pa, R[2 * m + 1], R[2 * m + 3]);
+                });
+            }
+            F512_PATH("c0 end");
         }
 #endif
         // |X|^2 / 512 with the factor 2 of the rows = 1 / 2048; the mel weights and this sum both carry an extra
@@ -1034,17 +1057,16 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
         F512_STAMP(6);
         F512_PIN(p0); F512_PIN(p1);
         // ---- power spectrum -> LDS row of this frame: two base registers, immediate offsets ----
-        float* ps = wbuf + f * F512_PS_STRIDE;
         {
-            float* lo = ps + c;           // bins c + 32 k           (+8 for unit 1)
-            float* hi = ps + 32 - c;      // bins 512 - 32 k - c = (32 - c) + 32 (15 - k)   (-8 for unit 1)
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                lo[32 * k] = p0[k];
-                hi[32 * (7 - k)] = p0[8 + k];
-                lo[32 * k + 8] = p1[k];
-                hi[32 * (7 - k) - 8] = p1[8 + k];
-            }
+            // Every store carries one bin of each unit: two dwords at two offsets from one base cost the path to the LDS
+            // 6 cycles (address + 2 data registers) where two single stores cost 8.
+            const uint32_t lo = f512_lds_addr(ps + c);        // bins c + 32 k           (+8 for unit 1)
+            const uint32_t hi = f512_lds_addr(ps + 24 - c);   // bins 512 - 32 k - c = (32 - c) + 32 (15 - k)   (-8 for unit 1)
+            f512_static_for<0, 8>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                f512_lds_store2<32 * k, 32 * k + 8>(lo, p0[k], p1[k]);
+                f512_lds_store2<32 * (7 - k) + 8, 32 * (7 - k)>(hi, p0[8 + k], p1[8 + k]);
+            });
 #ifdef F512_COOP
             F512_FENCE();                                // after lane 0's garbage slot: the bins 32 k are rewritten here
             ps[32 * coop_k] = coop_e;                    // X[32 k]
@@ -1053,12 +1075,7 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
             // it must hold finite values; nothing else ever writes these slots in the last frame's row)
             ps[256 + c] = c == 0 ? coop_e8 : 0.f;
 #else
-            if (c == 0) {
-#pragma unroll
-                for (int m = 0; m < 8; ++m) ps[32 * m + 16] = podd[m];
-            } else {
-                ps[256 + c] = 0.f;
-            }
+            if (c != 0) ps[256 + c] = 0.f;   // (lane 0's own bins 16 + 32 m: stored in its branch above)
 #endif
         }
         F512_FENCE();
@@ -1115,6 +1132,7 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
 #pragma unroll
         for (int i = 0; i < NI; ++i) rep_any |= rep_m[i];
         if (rep_any != 0) {
+            F512_PATH("repair begin");
             // Rare (one frame in 4 000 of a noise batch) and wave-uniform: the flagged filters' bins again as fp64 DFT sums
             // over the samples in memory, by the whole wave, one filter at a time.  The pointer to the plan's fp64 tables
             // sits behind the LDS image of the table blob.  The group is located AGAIN here, from an opaque copy of its
@@ -1147,6 +1165,7 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
                     if (lane == sl) lm[i] = nl;
                 }
             });
+            F512_PATH("repair end");
         }
         F512_FENCE();
         F512_PIN(lm);
@@ -1285,6 +1304,7 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
                     odd = make_float2(a0 * inv_den, a1 * inv_den);
                     row_ok = true;
                 } else {
+                    F512_PATH("clamp begin");
 #pragma unroll
                     for (int pass = 0; pass < 2; ++pass) {   // delta of rows 2..9, then 10..13 (rows above 13 repeat row 13)
                         const int i = pass == 0 ? 2 + f : (10 + f < 13 ? 10 + f : 13);
@@ -1316,6 +1336,7 @@ __global__ __launch_bounds__(64 * WAVES, F512_MIN_WAVES_PER_SIMD) void mfcc512_k
                     od = *reinterpret_cast<const float2*>(td + i * 16 + 2 * pr);
                     odd = make_float2(a0 * inv_den, a1 * inv_den);
                     row_ok = Fi >= run.wg_first && Fi < run.wg_end;
+                    F512_PATH("clamp end");
                 }
                 if (row_ok) {
                     if (2 * pr + 1 < C) {
