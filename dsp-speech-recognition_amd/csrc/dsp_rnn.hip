@@ -190,10 +190,11 @@ int64_t bigru_tape_need(const dsp_bigru* h, int32_t T, int32_t B) {
     return gru_tape_floats(h ? h->H : 4, h ? h->L : 1, T, B) * (int64_t)sizeof(float);
 }
 
-// The checks and the launch behind dsp_hmlstm_forward (d_tape == NULL) and dsp_hmlstm_forward_train.
+// The checks and the launch behind dsp_hmlstm_forward (d_tape == NULL) and dsp_hmlstm_forward_train[_rows] (d_rows: the row
+// bound's word or NULL; the training mode alone reads it).
 int hmlstm_forward_launch(const char* who, const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a,
-                          const int32_t* d_len, const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2,
-                          uint8_t* d_z1, uint8_t* d_z2, float* d_zhat, float* d_last_h2, float* d_tape, void* stream) {
+                          const int32_t* d_len, const int32_t* d_rows, const float* d_state_in, float* d_state_out, float* d_h1,
+                          float* d_h2, uint8_t* d_z1, uint8_t* d_z2, float* d_zhat, float* d_last_h2, float* d_tape, void* stream) {
     if (!h || !d_x) return dsp_fail(DSP_EINVAL, "%s: NULL handle / input", who);
     if (int rc = rnn_check_tb(who, T, B)) return rc;
     if (!std::isfinite(a)) return dsp_fail(DSP_EINVAL, "%s: the slope a is not finite", who);
@@ -204,7 +205,7 @@ int hmlstm_forward_launch(const char* who, const dsp_hmlstm* h, const float* d_x
     P.c1 = h->c1; P.c2 = h->c2;
     P.I = h->I; P.T = T; P.B = B; P.a = a;
     P.x = d_x; P.len = d_len; P.state_in = d_state_in; P.state_out = d_state_out;
-    P.h1 = d_h1; P.h2 = d_h2; P.z1 = d_z1; P.z2 = d_z2; P.zhat = d_zhat; P.last_h2 = d_last_h2; P.tape = d_tape;
+    P.h1 = d_h1; P.h2 = d_h2; P.z1 = d_z1; P.z2 = d_z2; P.zhat = d_zhat; P.last_h2 = d_last_h2; P.tape = d_tape; P.rows = d_rows;
     const int grid = hm_slices(B);
     const int nt = h->c1.n_tiles > h->c2.n_tiles ? h->c1.n_tiles : h->c2.n_tiles;
     hipStream_t st = (hipStream_t)stream;
@@ -212,6 +213,44 @@ int hmlstm_forward_launch(const char* who, const dsp_hmlstm* h, const float* d_x
     else rnn_dispatch_tiles<9>(nt, [&](auto m) { hmlstm_forward_kernel<decltype(m)::value><<<grid, HM_THREADS, 0, st>>>(P); });
     HIP_TRY(hipGetLastError());
     return DSP_OK;
+}
+
+// dsp_hmlstm_forward_train and dsp_hmlstm_forward_train_rows (d_rows may be NULL: the plain call)
+int hmlstm_forward_train(const char* who, const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
+                         const int32_t* d_rows, const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1,
+                         uint8_t* d_z2, float* d_zhat, float* d_last_h2, void* d_tape, int64_t tape_bytes, void* stream) {
+    if (int rc = rnn_check_tb(who, T, B)) return rc;
+    if (int rc = rnn_check_tape(who, d_tape, tape_bytes, hmlstm_tape_need(h, T, B), "dsp_hmlstm_tape_bytes")) return rc;
+    if (!d_h1 || !d_h2 || !d_z1 || !d_z2) return dsp_fail(DSP_EINVAL, "%s: h1, h2, z1 and z2 are mandatory (the backward pass reads them)", who);
+    if (!d_x) return dsp_fail(DSP_EINVAL, "%s: NULL input", who);
+    if (!h) return dsp_fail(DSP_EINVAL, "%s: NULL handle", who);
+    return hmlstm_forward_launch(who, h, d_x, T, B, a, d_len, d_rows, d_state_in, d_state_out, d_h1, d_h2, d_z1, d_z2, d_zhat,
+                                 d_last_h2, static_cast<float*>(d_tape), stream);
+}
+
+// dsp_hmlstm_backward and dsp_hmlstm_backward_rows, the same way
+int hmlstm_backward(const char* who, const dsp_hmlstm* h, int32_t T, int32_t B, float a, const int32_t* d_len, const int32_t* d_rows,
+                    const float* d_state_in, const void* d_tape, int64_t tape_bytes, const float* d_h1, const float* d_h2,
+                    const uint8_t* d_z1, const uint8_t* d_z2, const float* d_g_h1, const float* d_g_h2, const float* d_g_last,
+                    float* d_dfs1, float* d_dfs2, void* stream) {
+    if (int rc = rnn_check_tb(who, T, B)) return rc;
+    if (!std::isfinite(a)) return dsp_fail(DSP_EINVAL, "%s: the slope a is not finite", who);
+    if (int rc = rnn_check_tape(who, d_tape, tape_bytes, hmlstm_tape_need(h, T, B), "dsp_hmlstm_tape_bytes")) return rc;
+    if (!d_h1 || !d_h2 || !d_z1 || !d_z2) return dsp_fail(DSP_EINVAL, "%s: NULL forward output (h1, h2, z1, z2)", who);
+    if (!d_g_h1 && !d_g_h2 && !d_g_last) return dsp_fail(DSP_EINVAL, "%s: no gradient to propagate (g_h1, g_h2 and g_last are all NULL)", who);
+    if (!d_dfs1 || !d_dfs2) return dsp_fail(DSP_EINVAL, "%s: NULL output (dfs1, dfs2)", who);
+    if (!h) return dsp_fail(DSP_EINVAL, "%s: NULL handle", who);
+    HmBwdParams P;
+    for (int i = 0; i < 4; ++i) P.wt[i] = h->wt[i];
+    P.H1 = h->H1; P.H2 = h->H2; P.T = T; P.B = B; P.a = a;
+    P.len = d_len; P.state_in = d_state_in; P.tape = static_cast<const float*>(d_tape);
+    P.h1 = d_h1; P.h2 = d_h2; P.z1 = d_z1; P.z2 = d_z2;
+    P.g_h1 = d_g_h1; P.g_h2 = d_g_h2; P.g_last = d_g_last; P.dfs1 = d_dfs1; P.dfs2 = d_dfs2; P.rows = d_rows;
+    const dim3 grid(hm_slices(B));
+    const size_t lds = hm_bwd_lds_bytes(h->H1, h->H2);       // up to 67.5 KB: above the static limit
+    hipStream_t st = (hipStream_t)stream;
+    if (hm_bwd_chunks(h->H1 > h->H2 ? h->H1 : h->H2) <= 1) return rnn_launch_dynamic_lds<hmlstm_backward_kernel<1>>(who, grid, lds, st, P);
+    return rnn_launch_dynamic_lds<hmlstm_backward_kernel<2>>(who, grid, lds, st, P);
 }
 
 int64_t bigru_buffer_floats(const dsp_bigru* h, int32_t T, int32_t B) { return (int64_t)T * B * 2 * h->H; }
@@ -287,8 +326,8 @@ int dsp_hmlstm_refresh(dsp_hmlstm* h, const dsp_hmlstm_desc* d, void* stream) {
 int dsp_hmlstm_forward(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
                        const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1, uint8_t* d_z2,
                        float* d_zhat, float* d_last_h2, void* stream) {
-    return hmlstm_forward_launch("dsp_hmlstm_forward", h, d_x, T, B, a, d_len, d_state_in, d_state_out, d_h1, d_h2, d_z1, d_z2,
-                                 d_zhat, d_last_h2, nullptr, stream);
+    return hmlstm_forward_launch("dsp_hmlstm_forward", h, d_x, T, B, a, d_len, nullptr, d_state_in, d_state_out, d_h1, d_h2, d_z1,
+                                 d_z2, d_zhat, d_last_h2, nullptr, stream);
 }
 
 int dsp_hmlstm_tape_bytes(const dsp_hmlstm* h, int32_t T, int32_t B, int64_t* bytes) {
@@ -301,39 +340,32 @@ int dsp_hmlstm_tape_bytes(const dsp_hmlstm* h, int32_t T, int32_t B, int64_t* by
 int dsp_hmlstm_forward_train(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
                              const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2, uint8_t* d_z1, uint8_t* d_z2,
                              float* d_zhat, float* d_last_h2, void* d_tape, int64_t tape_bytes, void* stream) {
-    const char* who = "dsp_hmlstm_forward_train";
-    if (int rc = rnn_check_tb(who, T, B)) return rc;
-    if (int rc = rnn_check_tape(who, d_tape, tape_bytes, hmlstm_tape_need(h, T, B), "dsp_hmlstm_tape_bytes")) return rc;
-    if (!d_h1 || !d_h2 || !d_z1 || !d_z2) return dsp_fail(DSP_EINVAL, "%s: h1, h2, z1 and z2 are mandatory (the backward pass reads them)", who);
-    if (!d_x) return dsp_fail(DSP_EINVAL, "%s: NULL input", who);
-    if (!h) return dsp_fail(DSP_EINVAL, "%s: NULL handle", who);
-    return hmlstm_forward_launch(who, h, d_x, T, B, a, d_len, d_state_in, d_state_out, d_h1, d_h2, d_z1, d_z2, d_zhat,
-                                 d_last_h2, static_cast<float*>(d_tape), stream);
+    return hmlstm_forward_train("dsp_hmlstm_forward_train", h, d_x, T, B, a, d_len, nullptr, d_state_in, d_state_out, d_h1, d_h2, d_z1,
+                                d_z2, d_zhat, d_last_h2, d_tape, tape_bytes, stream);
+}
+
+int dsp_hmlstm_forward_train_rows(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
+                                  const int32_t* d_rows, const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2,
+                                  uint8_t* d_z1, uint8_t* d_z2, float* d_zhat, float* d_last_h2, void* d_tape, int64_t tape_bytes,
+                                  void* stream) {
+    return hmlstm_forward_train("dsp_hmlstm_forward_train_rows", h, d_x, T, B, a, d_len, d_rows, d_state_in, d_state_out, d_h1, d_h2,
+                                d_z1, d_z2, d_zhat, d_last_h2, d_tape, tape_bytes, stream);
 }
 
 int dsp_hmlstm_backward(const dsp_hmlstm* h, int32_t T, int32_t B, float a, const int32_t* d_len, const float* d_state_in,
                         const void* d_tape, int64_t tape_bytes, const float* d_h1, const float* d_h2, const uint8_t* d_z1,
                         const uint8_t* d_z2, const float* d_g_h1, const float* d_g_h2, const float* d_g_last, float* d_dfs1,
                         float* d_dfs2, void* stream) {
-    const char* who = "dsp_hmlstm_backward";
-    if (int rc = rnn_check_tb(who, T, B)) return rc;
-    if (!std::isfinite(a)) return dsp_fail(DSP_EINVAL, "%s: the slope a is not finite", who);
-    if (int rc = rnn_check_tape(who, d_tape, tape_bytes, hmlstm_tape_need(h, T, B), "dsp_hmlstm_tape_bytes")) return rc;
-    if (!d_h1 || !d_h2 || !d_z1 || !d_z2) return dsp_fail(DSP_EINVAL, "%s: NULL forward output (h1, h2, z1, z2)", who);
-    if (!d_g_h1 && !d_g_h2 && !d_g_last) return dsp_fail(DSP_EINVAL, "%s: no gradient to propagate (g_h1, g_h2 and g_last are all NULL)", who);
-    if (!d_dfs1 || !d_dfs2) return dsp_fail(DSP_EINVAL, "%s: NULL output (dfs1, dfs2)", who);
-    if (!h) return dsp_fail(DSP_EINVAL, "%s: NULL handle", who);
-    HmBwdParams P;
-    for (int i = 0; i < 4; ++i) P.wt[i] = h->wt[i];
-    P.H1 = h->H1; P.H2 = h->H2; P.T = T; P.B = B; P.a = a;
-    P.len = d_len; P.state_in = d_state_in; P.tape = static_cast<const float*>(d_tape);
-    P.h1 = d_h1; P.h2 = d_h2; P.z1 = d_z1; P.z2 = d_z2;
-    P.g_h1 = d_g_h1; P.g_h2 = d_g_h2; P.g_last = d_g_last; P.dfs1 = d_dfs1; P.dfs2 = d_dfs2;
-    const dim3 grid(hm_slices(B));
-    const size_t lds = hm_bwd_lds_bytes(h->H1, h->H2);       // up to 67.5 KB: above the static limit
-    hipStream_t st = (hipStream_t)stream;
-    if (hm_bwd_chunks(h->H1 > h->H2 ? h->H1 : h->H2) <= 1) return rnn_launch_dynamic_lds<hmlstm_backward_kernel<1>>(who, grid, lds, st, P);
-    return rnn_launch_dynamic_lds<hmlstm_backward_kernel<2>>(who, grid, lds, st, P);
+    return hmlstm_backward("dsp_hmlstm_backward", h, T, B, a, d_len, nullptr, d_state_in, d_tape, tape_bytes, d_h1, d_h2, d_z1, d_z2,
+                           d_g_h1, d_g_h2, d_g_last, d_dfs1, d_dfs2, stream);
+}
+
+int dsp_hmlstm_backward_rows(const dsp_hmlstm* h, int32_t T, int32_t B, float a, const int32_t* d_len, const int32_t* d_rows,
+                             const float* d_state_in, const void* d_tape, int64_t tape_bytes, const float* d_h1, const float* d_h2,
+                             const uint8_t* d_z1, const uint8_t* d_z2, const float* d_g_h1, const float* d_g_h2,
+                             const float* d_g_last, float* d_dfs1, float* d_dfs2, void* stream) {
+    return hmlstm_backward("dsp_hmlstm_backward_rows", h, T, B, a, d_len, d_rows, d_state_in, d_tape, tape_bytes, d_h1, d_h2, d_z1, d_z2,
+                           d_g_h1, d_g_h2, d_g_last, d_dfs1, d_dfs2, stream);
 }
 
 int dsp_bigru_create(const dsp_bigru_desc* d, dsp_bigru** out) {

@@ -46,6 +46,7 @@ struct HmParams {
     float* zhat;                // [T, 2, B]
     float* last_h2;             // [B, H2]
     float* tape;                // training mode (the TAPE instantiations) only: hm_tape_* below
+    const int32_t* rows;        // training mode only, or nullptr: one word, the row bound R = clamp(*rows, 1, T) (hm_row_bound)
 };
 
 // The tape of the training mode: what the backward recurrence (kernels_hmlstm_bwd.h) reads beside the outputs h1 / h2 / z1 / z2.
@@ -56,6 +57,7 @@ struct HmParams {
 //   cell 2: the same;
 //   m1 [16], m2 [16]: 1.0f where 0 <= (f_s[4H] a + 1) / 2 <= 1 (the clamp of hard_sigm passes the gradient), else 0.
 // Slice s, step t starts at ((s * T) + t) * hm_tape_step: every column of the last slice is written, b >= B included.
+// Under a row bound R (HmParams::rows) the stride stays T and only the steps t < R are written.
 __host__ __device__ static inline int64_t hm_tape_step(int32_t H1, int32_t H2) { return 80 * (int64_t)(H1 + H2) + 32; }
 static inline int64_t hm_tape_floats(int32_t H1, int32_t H2, int32_t T, int32_t B) {
     return (int64_t)hm_slices(B) * T * hm_tape_step(H1, H2);
@@ -201,18 +203,21 @@ __global__ __launch_bounds__(HM_THREADS) void hmlstm_forward_kernel(const HmPara
     const int H1 = P.c1.H, H2 = P.c2.H, I = P.I, T = P.T, B = P.B;
     const bool col_ok = b < B;
     const int nt1 = P.c1.n_tiles, nt2 = P.c2.n_tiles;
+    // The rows this call runs.  Training mode under a row bound: the call is the one at T = R on the rows in front of R (the
+    // buffers keep their strides of T) and leaves exact zeros behind.  Everywhere else R is T.
+    const int R = TAPE ? hm_row_bound(P.rows, T) : T;
 
     for (int i = tid; i < HM_BUF_FLOATS; i += HM_THREADS) { xbuf[i] = 0.f; h1buf[i] = 0.f; h2buf[i] = 0.f; }
     if (tid < HM_COLS) {
         const int bb = b0 + tid;
         float v1 = 0.f, v2 = 0.f;
-        int n = T;
+        int n = R;
         if (bb < B) {
             if (P.state_in) {
                 v1 = P.state_in[(int64_t)2 * H1 * B + bb];
                 v2 = P.state_in[(int64_t)(2 * H1 + 1 + 2 * H2) * B + bb];
             }
-            if (P.len) n = min(max(P.len[bb], 1), T);
+            if (P.len) n = min(max(P.len[bb], 1), R);
         }
         z1s[tid] = v1;
         z2s[tid] = v2;
@@ -271,8 +276,8 @@ __global__ __launch_bounds__(HM_THREADS) void hmlstm_forward_kernel(const HmPara
     __syncthreads();
 
     // When h_2 at len - 1 is the ONLY output asked for, nothing behind the longest column of the slice can reach it: the slice
-    // stops there (wave-uniform, at most T).  Any other output is defined over all T steps.
-    int steps = T;
+    // stops there (wave-uniform, at most T).  Any other output is defined over all T steps (R under a row bound).
+    int steps = R;
     if (!TAPE && P.len && P.last_h2 && !P.state_out && !P.h1 && !P.h2 && !P.z1 && !P.z2 && !P.zhat) {
         steps = 1;
         for (int c = 0; c < HM_COLS; ++c)
@@ -302,6 +307,23 @@ __global__ __launch_bounds__(HM_THREADS) void hmlstm_forward_kernel(const HmPara
         __syncthreads();                    // h2buf / z2s hold step t
         if (P.h2 || P.last_h2) hm_store_rows(h2buf, H2, b0, B, T, t, P.h2, P.last_h2, lens);
         if (TAPE) tp += hm_tape_step(H1, H2);
+    }
+
+    if (TAPE && R < T) {                    // behind the bound: every element of every output is still written, as an exact zero
+        if (P.h1) hm_zero_tail_bth(P.h1, H1, R, T, b0, B);
+        if (P.h2) hm_zero_tail_bth(P.h2, H2, R, T, b0, B);
+        const int cols = min(HM_COLS, B - b0), nz = T - R;
+        for (int idx = tid; idx < cols * nz; idx += HM_THREADS) {
+            const int c = idx / nz, j = idx - c * nz;
+            const int64_t at = (int64_t)(b0 + c) * T + R + j;
+            if (P.z1) P.z1[at] = 0;
+            if (P.z2) P.z2[at] = 0;
+        }
+        if (P.zhat)
+            for (int idx = tid; idx < 2 * nz * cols; idx += HM_THREADS) {
+                const int row = idx / cols, c = idx - row * cols;
+                P.zhat[((int64_t)2 * R + row) * B + b0 + c] = 0.f;
+            }
     }
 
     if (P.state_out && col_ok) {

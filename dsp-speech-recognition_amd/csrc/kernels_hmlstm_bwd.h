@@ -1,7 +1,7 @@
 // Backward recurrence of the HM-LSTM (kernels_hmlstm.h is the forward; its training mode leaves the tape read here), fp32,
 // as ONE persistent launch of the same shape: a workgroup of 512 threads owns a slice of HM_COLS = 16 batch columns, runs the
-// steps t = T - 1 .. 0 for it and never waits on another workgroup -- no grid barrier, no flag, every loop bounded by an
-// argument.  What it leaves are dfs1 [T, B, 4 H1 + 1] and dfs2 [T, B, 4 H2 + 1], the gradients of the two cells'
+// steps t = T - 1 .. 0 for it (R - 1 .. 0 under a row bound, HmBwdParams::rows) and never waits on another workgroup -- no
+// grid barrier, no flag, every loop bounded by an argument.  What it leaves are dfs1 [T, B, 4 H1 + 1] and dfs2 [T, B, 4 H2 + 1], the gradients of the two cells'
 // pre-activations f_s (hmrnn.py:84); the gradients of x and of the parameters are plain GEMMs over them
 // (include/dsp_frontend.h states the formulas).
 //
@@ -37,6 +37,7 @@ struct HmBwdParams {
     const float* g_last;        // [B, H2]
     float* dfs1;                // [T, B, 4 H1 + 1]
     float* dfs2;
+    const int32_t* rows;        // nullptr, or the word the forward was given: the row bound R = clamp(*rows, 1, T) (hm_row_bound)
 };
 
 static inline int64_t hm_bwd_packed_floats(int32_t Hcell, int32_t Hout) { return (int64_t)(Hcell / 4 + 1) * HM_WAVES * hm_bwd_chunks(Hout) * 256; }
@@ -151,6 +152,9 @@ __global__ __launch_bounds__(HM_THREADS) void hmlstm_backward_kernel(const HmBwd
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), col = lane & 15;
     const int b0 = blockIdx.x * HM_COLS, b = b0 + col;
     const int H1 = P.H1, H2 = P.H2, T = P.T, B = P.B;
+    // Under a row bound the steps run from R - 1 down: nothing of the rows t >= R is read (neither the tape nor the
+    // forward's outputs nor g_h1 / g_h2), and dfs1 / dfs2 get exact zeros there.  Strides stay those of T.
+    const int R = hm_row_bound(P.rows, T);
     const bool col_ok = b < B;
     const int ng1 = (H1 >> 2) + 1, ng2 = (H2 >> 2) + 1, nc1 = hm_bwd_chunks(H1), nc2 = hm_bwd_chunks(H2);
     const int ngmax = ng1 > ng2 ? ng1 : ng2;
@@ -164,9 +168,16 @@ __global__ __launch_bounds__(HM_THREADS) void hmlstm_backward_kernel(const HmBwd
     const float* st = P.state_in;
     const float* st_h1 = st, *st_c1 = st ? st + (int64_t)H1 * B : nullptr;
     const float* st_h2 = st ? st + (int64_t)(2 * H1 + 1) * B : nullptr, *st_c2 = st ? st + (int64_t)(2 * H1 + 1 + H2) * B : nullptr;
-    int last_t = T - 1;
-    if (P.len && col_ok) last_t = min(max(P.len[b], 1), T) - 1;
+    int last_t = R - 1;
+    if (P.len && col_ok) last_t = min(max(P.len[b], 1), R) - 1;
     const float half_a = 0.5f * P.a;
+
+    // Every element of dfs is written on every call: the rows the loop below does not reach, first (in front of the loop
+    // nothing of this stays live across it).
+    if (R < T) {
+        hm_zero_rows(P.dfs1, 4 * H1 + 1, 4 * H1 + 1, 0, R, T, b0, B);
+        hm_zero_rows(P.dfs2, 4 * H2 + 1, 4 * H2 + 1, 0, R, T, b0, B);
+    }
 
     float dh1[NS], dc1[NS], dh2[NS], dc2[NS];
 #pragma unroll
@@ -201,12 +212,12 @@ __global__ __launch_bounds__(HM_THREADS) void hmlstm_backward_kernel(const HmBwd
         nm1 = tm[col];
         nm2 = tm[16 + col];
     };
-    if (col_ok) z1t = (float)((hm_gu8*)hm_uniform(P.z1 + (int64_t)b0 * T + T - 1))[col * T];
-    load2(T - 1);
-    loadz(T - 1);
+    if (col_ok) z1t = (float)((hm_gu8*)hm_uniform(P.z1 + (int64_t)b0 * T + R - 1))[col * T];
+    load2(R - 1);
+    loadz(R - 1);
     __syncthreads();
 
-    for (int t = T - 1; t >= 0; --t) {
+    for (int t = R - 1; t >= 0; --t) {
         const float z1p = nz1p, z2p = nz2p, m1 = nm1, m2 = nm2;
         float* out2 = P.dfs2 + ((int64_t)t * B + b0) * (4 * H2 + 1);
         float* out1 = P.dfs1 + ((int64_t)t * B + b0) * (4 * H1 + 1);
@@ -259,4 +270,5 @@ __global__ __launch_bounds__(HM_THREADS) void hmlstm_backward_kernel(const HmBwd
         dz1 = hm_bwd_col_sum(red0, col);
         z1t = z1p;
     }
+
 }

@@ -157,6 +157,32 @@ __device__ __forceinline__ int hm_slice_steps(const int32_t* len, int b0, int B,
     return __builtin_amdgcn_readfirstlane(steps);
 }
 
+// The row bound of the HM-LSTM's training pair: T without one, else the word at `rows` clamped to [1, T] -- one wave-uniform
+// read, held in a scalar register.  Whatever the word holds, the result is in [1, T]: no index and no loop bound derived
+// from it leaves what the argument T allows.
+__device__ __forceinline__ int hm_row_bound(const int32_t* rows, int T) {
+    if (!rows) return T;
+    return min(max(__builtin_amdgcn_readfirstlane(*rows), 1), T);
+}
+
+// Exact zeros behind row R of a [B, T, H] output (H a multiple of 4) for the slice's columns b0 .. : per column the
+// (T - R) H floats from (b T + R) H on are contiguous, so they go out as 16-byte stores where the buffer's base allows.
+__device__ __forceinline__ void hm_zero_tail_bth(float* out, int H, int R, int T, int b0, int B) {
+    const int cols = min(HM_COLS, B - b0), n = (T - R) * H;
+    if ((reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+        const int n4 = n >> 2;
+        for (int idx = threadIdx.x; idx < cols * n4; idx += HM_THREADS) {
+            const int c = idx / n4, j = idx - c * n4;
+            ((hm_gf4*)(out + ((int64_t)(b0 + c) * T + R) * H))[j] = hm_f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    } else {
+        for (int idx = threadIdx.x; idx < cols * n; idx += HM_THREADS) {
+            const int c = idx / n, j = idx - c * n;
+            out[((int64_t)(b0 + c) * T + R) * H + j] = 0.f;
+        }
+    }
+}
+
 // Exact zeros in the rows of the steps no column of the slice reaches (t in [steps, T)): per step and column of the slice
 // `width` floats at out[(t * B + b) * stride + off ..].
 __device__ __forceinline__ void hm_zero_rows(float* out, int width, int stride, int off, int steps, int T, int b0, int B) {

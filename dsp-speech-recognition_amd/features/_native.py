@@ -140,6 +140,10 @@ SIGNATURES = {
                                            c_i64, c_vp]),
     'dsp_hmlstm_backward': (C.c_int, [c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_vp, c_vp]),
+    'dsp_hmlstm_forward_train_rows': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                c_vp, c_vp, c_i64, c_vp]),
+    'dsp_hmlstm_backward_rows': (C.c_int, [c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp, c_vp, c_vp, c_vp]),
     'dsp_bigru_create': (C.c_int, [C.POINTER(BigruDesc), C.POINTER(c_vp)]),
     'dsp_bigru_destroy': (C.c_int, [c_vp]),
     'dsp_bigru_workspace_bytes': (C.c_int, [c_vp, c_i32, c_i32, C.POINTER(c_i64)]),

@@ -1204,11 +1204,14 @@ def hm_param_grads(params, x, state_in, h_1, h_2, z_1, dfs1, dfs2, need=None):
 class _HMLSTMTrain(torch.autograd.Function):
     """HMLSTM's native training path.  forward: dsp_hmlstm_forward_train (the forward kernel, which also saves the tape);
     backward: dsp_hmlstm_backward (the recurrence, one launch) and ``hm_param_grads``.  Inputs: (module, a, d_len int32 [B],
-    state_in or None, x, the seven parameters); outputs: h_1, h_2, last_h2 (differentiable) and z_1, z_2 (uint8 [B, T]),
-    z_hat, state_out (marked non-differentiable)."""
+    d_rows or None, state_in or None, x, the seven parameters); outputs: h_1, h_2, last_h2 (differentiable) and z_1, z_2
+    (uint8 [B, T]), z_hat, state_out (marked non-differentiable).
+    ``d_rows``: a one-element int32 tensor on x's device, the row bound of both passes (dsp_hmlstm_forward_train_rows /
+    dsp_hmlstm_backward_rows): the kernels stop at clamp(d_rows[0], 1, T) rows and leave exact zeros behind.  It is read on
+    the device when the kernels run and must hold the same value at the backward call."""
 
     @staticmethod
-    def forward(ctx, mod, a, d_len, state_in, x, *params):
+    def forward(ctx, mod, a, d_len, d_rows, state_in, x, *params):
         from . import _native as nat
         ctx.set_materialize_grads(False)                     # an unused output hands None to backward, not a tensor of zeros
         T, B, _ = x.shape
@@ -1224,13 +1227,15 @@ class _HMLSTMTrain(torch.autograd.Function):
         h_1, h_2 = torch.empty(B, T, H1, **f32), torch.empty(B, T, H2, **f32)
         z_1, z_2 = torch.empty(B, T, dtype=torch.uint8, device=dev), torch.empty(B, T, dtype=torch.uint8, device=dev)
         z_hat, last = torch.empty(T, 2, B, **f32), torch.empty(B, H2, **f32)
-        nat.check(lib.dsp_hmlstm_forward_train(handle, xc.data_ptr(), T, B, a, d_len.data_ptr(),
-                                               _ptr(state_in), state_out.data_ptr(),
-                                               h_1.data_ptr(), h_2.data_ptr(), z_1.data_ptr(), z_2.data_ptr(), z_hat.data_ptr(),
-                                               last.data_ptr(), tape.data_ptr(), nbytes.value,
-                                               torch.cuda.current_stream(dev).cuda_stream))
-        ctx.mod, ctx.a, ctx.tape_bytes, ctx.handle_key, ctx.has_state = mod, a, nbytes.value, mod._handle_key, state_in is not None
-        ctx.save_for_backward(xc, d_len, tape, h_1, h_2, z_1, z_2, *([state_in] if state_in is not None else []), *params)
+        call = lib.dsp_hmlstm_forward_train if d_rows is None else lib.dsp_hmlstm_forward_train_rows
+        rows = () if d_rows is None else (d_rows.data_ptr(),)
+        nat.check(call(handle, xc.data_ptr(), T, B, a, d_len.data_ptr(), *rows, _ptr(state_in), state_out.data_ptr(),
+                       h_1.data_ptr(), h_2.data_ptr(), z_1.data_ptr(), z_2.data_ptr(), z_hat.data_ptr(),
+                       last.data_ptr(), tape.data_ptr(), nbytes.value, torch.cuda.current_stream(dev).cuda_stream))
+        ctx.mod, ctx.a, ctx.tape_bytes, ctx.handle_key = mod, a, nbytes.value, mod._handle_key
+        ctx.has_rows, ctx.has_state = d_rows is not None, state_in is not None
+        ctx.save_for_backward(xc, d_len, tape, h_1, h_2, z_1, z_2, *([d_rows] if ctx.has_rows else []),
+                              *([state_in] if ctx.has_state else []), *params)
         ctx.mark_non_differentiable(z_1, z_2, z_hat, state_out)
         return h_1, h_2, last, z_1, z_2, z_hat, state_out
 
@@ -1239,27 +1244,35 @@ class _HMLSTMTrain(torch.autograd.Function):
         from . import _native as nat
         saved = ctx.saved_tensors
         xc, d_len, tape, h_1, h_2, z_1, z_2 = saved[:7]
-        state_in = saved[7] if ctx.has_state else None
-        params = saved[8 if ctx.has_state else 7:]
+        k = 7
+        d_rows = state_in = None
+        if ctx.has_rows:
+            d_rows, k = saved[k], k + 1
+        if ctx.has_state:
+            state_in, k = saved[k], k + 1
+        params = saved[k:]
         mod = ctx.mod
         T, B, _ = xc.shape
         H1, H2 = mod.size_list
         dev = xc.device
         mod._check_unmodified(ctx.handle_key)
-        need = [ctx.needs_input_grad[4]] + list(ctx.needs_input_grad[5:12])
+        need = [ctx.needs_input_grad[5]] + list(ctx.needs_input_grad[6:13])
         if g_h1 is None and g_h2 is None and g_last is None:
-            return (None,) * 12
+            return (None,) * 13
         gp = lambda g: None if g is None else g.to(torch.float32).contiguous()
         g_h1, g_h2, g_last = gp(g_h1), gp(g_h2), gp(g_last)
         with torch.cuda.device(dev):
             dfs1 = torch.empty(T, B, 4 * H1 + 1, dtype=torch.float32, device=dev)
             dfs2 = torch.empty(T, B, 4 * H2 + 1, dtype=torch.float32, device=dev)
-            nat.check(nat.load().dsp_hmlstm_backward(mod._handle, T, B, ctx.a, d_len.data_ptr(), _ptr(state_in), tape.data_ptr(),
-                                                     ctx.tape_bytes, h_1.data_ptr(), h_2.data_ptr(), z_1.data_ptr(), z_2.data_ptr(),
-                                                     _ptr(g_h1), _ptr(g_h2), _ptr(g_last), dfs1.data_ptr(), dfs2.data_ptr(),
-                                                     torch.cuda.current_stream(dev).cuda_stream))
+            lib = nat.load()
+            call = lib.dsp_hmlstm_backward if d_rows is None else lib.dsp_hmlstm_backward_rows
+            rows = () if d_rows is None else (d_rows.data_ptr(),)
+            nat.check(call(mod._handle, T, B, ctx.a, d_len.data_ptr(), *rows, _ptr(state_in), tape.data_ptr(),
+                           ctx.tape_bytes, h_1.data_ptr(), h_2.data_ptr(), z_1.data_ptr(), z_2.data_ptr(),
+                           _ptr(g_h1), _ptr(g_h2), _ptr(g_last), dfs1.data_ptr(), dfs2.data_ptr(),
+                           torch.cuda.current_stream(dev).cuda_stream))
             grads = hm_param_grads([p.detach() for p in params], xc, state_in, h_1, h_2, z_1, dfs1, dfs2, need)
-        return (None, None, None, None) + grads
+        return (None, None, None, None, None) + grads
 
 
 class HMLSTMResult:
@@ -1364,11 +1377,12 @@ class HMLSTM(_NativeHandle, nn.Module):
         zf = lambda z: None if z is None else z.to(torch.float32).unsqueeze(2)
         return HMLSTMResult(h_1=h_1, h_2=h_2, z_1=zf(z_1), z_2=zf(z_2), hidden=hid, z_hat=z_hat, last_h2=last)
 
-    def _run_native_train(self, x, hidden, lens, d_len=None):
+    def _run_native_train(self, x, hidden, lens, d_len=None, d_rows=None):
         """The native training path: the same HMLSTMResult, h_1 / h_2 / last_h2 attached to the autograd graph.
         ``d_len`` (``device_grad=True``): the lengths as a [B] int32 tensor on x's device, read in place; ``last_h2`` is then
         the only field returned, and the handle survives an optimiser step (``refresh=True``).  All T rows run on this path
-        -- the forward-only ``last_only`` shortcut does not apply: the backward recurrence reads the tape of every row."""
+        -- the forward-only ``last_only`` shortcut does not apply: the backward recurrence reads the tape of every row it
+        runs -- unless ``d_rows`` (with ``d_len``) gives both passes one row bound to stop at (``_HMLSTMTrain``)."""
         T, B, _ = x.shape
         H1, H2 = self.size_list
         dev = x.device
@@ -1377,13 +1391,13 @@ class HMLSTM(_NativeHandle, nn.Module):
             f32 = dict(dtype=torch.float32, device=dev)
             state_in = None if hidden is None else _pack_state(hidden, H1, H2, B, **f32)
             if d_len is not None:
-                last = _HMLSTMTrain.apply(self, float(self.a), d_len, state_in, x, *self._params())[2]
+                last = _HMLSTMTrain.apply(self, float(self.a), d_len, d_rows, state_in, x, *self._params())[2]
                 return HMLSTMResult(last_h2=last)
             if lens is not None:
                 d_len = torch.as_tensor(_lengths(lens), dtype=torch.int32).to(dev)
             else:
                 d_len = torch.full((B,), T, dtype=torch.int32, device=dev)
-            h_1, h_2, last, z_1, z_2, z_hat, state_out = _HMLSTMTrain.apply(self, float(self.a), d_len, state_in, x, *self._params())
+            h_1, h_2, last, z_1, z_2, z_hat, state_out = _HMLSTMTrain.apply(self, float(self.a), d_len, None, state_in, x, *self._params())
         hid = _split_state(state_out, H1, H2, B)
         zf = lambda z: z.to(torch.float32).unsqueeze(2)
         return HMLSTMResult(h_1=h_1, h_2=h_2, z_1=zf(z_1), z_2=zf(z_2), hidden=hid, z_hat=z_hat, last_h2=last if lens is not None else None)
@@ -1412,16 +1426,25 @@ class HMLSTM(_NativeHandle, nn.Module):
         return HMLSTMResult(h_1=torch.stack(hs1, dim=1), h_2=h_2, z_1=torch.stack(zs1, dim=1), z_2=torch.stack(zs2, dim=1),
                             hidden=(h1, c1, z1, h2, c2, z2), z_hat=torch.stack(zh).detach(), last_h2=last)
 
-    def run(self, x, hidden=None, lens=None, native=None, device_len=False, device_grad=False):
+    def run(self, x, hidden=None, lens=None, native=None, device_len=False, device_grad=False, d_rows=None):
         """Everything the forward pass yields, as an HMLSTMResult.  x: [T, B, input_size].
         ``device_len=True``: ``lens`` is a [B] int32 tensor on x's device with entries in [1, T] and stays there; the native
         forward yields ``last_h2`` alone (every other field is None), which lets each 16-column slice stop at its longest
         length instead of running all T rows.
         Forward only: a required gradient, or anything else the native path cannot serve, raises -- unless
         ``device_grad=True`` is given as well: a required gradient then takes the native training path with the lengths read
-        on the device.  ``last_h2`` is still the only field returned, but ALL T rows run, because the backward recurrence
-        needs the tape of every row; the handle is refreshed in place after an optimiser step instead of rebuilt."""
+        on the device.  ``last_h2`` is still the only field returned; the handle is refreshed in place after an optimiser
+        step instead of rebuilt.  The per-slice stop does not apply there, because the forward and the backward recurrence
+        must agree on the rows the tape holds: without ``d_rows`` all T rows run, and with it -- a one-element int32 tensor on
+        x's device holding a row count no smaller than the longest length, such as ``head_length_info(...)[2][0:1]`` -- both
+        passes stop at clamp(d_rows[0], 1, T) rows, read on the device, with the same ``last_h2`` and the same gradients (a
+        smaller count cuts the lengths to it).  ``d_rows`` serves the training path only and needs ``device_grad=True``."""
         _check_device_grad('HMLSTM', device_len, device_grad)
+        if d_rows is not None:
+            if not device_grad:
+                raise ValueError('HMLSTM: d_rows needs device_len=True, device_grad=True (it bounds the native training path)')
+            if not (torch.is_tensor(d_rows) and d_rows.dtype == torch.int32 and d_rows.numel() == 1 and d_rows.device == x.device):
+                raise TypeError("HMLSTM: d_rows must be a one-element int32 tensor on the input's device")
         if device_len:
             needs_grad = _check_device_len('HMLSTM', x, lens, self, device_grad)
             if torch.is_grad_enabled() and hidden is not None and any(v.requires_grad for v in hidden):
@@ -1430,7 +1453,7 @@ class HMLSTM(_NativeHandle, nn.Module):
             if why is not None:
                 raise RuntimeError(f'HMLSTM: the native path cannot run: {why}')
             if needs_grad:
-                return self._run_native_train(x, hidden, None, d_len=lens.contiguous())
+                return self._run_native_train(x, hidden, None, d_len=lens.contiguous(), d_rows=d_rows)
             if device_grad:
                 self._native_handle(x.device, refresh=True)
             return self._run_native(x, hidden, None, d_len=lens.contiguous(), last_only=True)
@@ -1476,7 +1499,8 @@ class HMRNNHead(nn.Module):
             enc = self.enc1(inp, d_len, device_len=True, device_grad=device_grad)                        # [T, B, 200], zeros behind each end
             if dropout:
                 enc = torch.nn.functional.dropout(enc, 0.2)
-            last = self.enc2.run(enc, None, lens=d_len, device_len=True, device_grad=device_grad).last_h2
+            last = self.enc2.run(enc, None, lens=d_len, device_len=True, device_grad=device_grad,
+                                 d_rows=info[0:1] if device_grad else None).last_h2      # both passes stop at max(len0)
             feat = torch.cat([_pool_native(enc, d_len, info[0:1], grad=device_grad), last], dim=1)
             out = self.out(feat)
             return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat

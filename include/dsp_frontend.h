@@ -548,6 +548,17 @@ int dsp_hmlstm_forward(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t
  * Neither call differentiates with respect to the initial state, and z_1 / z_2 / z_hat / state_out are outputs only.
  * Both are one launch on `stream` without allocation (capturable); bad sizes, NULL or misaligned pointers and a short
  * tape are DSP_EINVAL, checked before any device call.
+ *
+ * dsp_hmlstm_forward_train_rows / dsp_hmlstm_backward_rows: the same pair under a row bound that lives in device memory.
+ * d_rows points at one int32 word r, read by the kernels when they run (never by the host, so a captured graph follows
+ * the word) and clamped there to [1, T]; d_rows == NULL is the plain call, bit for bit.  The contract: every buffer keeps
+ * its shape and strides of T (the tape and dsp_hmlstm_tape_bytes included), and on the rows t < r the call equals the
+ * plain call at T = r on the first r rows of d_x with d_len clamped to r -- d_state_out is the state behind step r - 1,
+ * d_last_h2 is h_2[b, min(len[b], r) - 1], steps t < r of the tape -- in every bit.  Behind it exact zeros are written:
+ * rows t >= r of d_h1, d_h2, d_z1, d_z2, d_zhat and of d_dfs1, d_dfs2, so every element of every output is still written
+ * on every call; the tape's steps t >= r are left alone, and d_x, d_g_h1 and d_g_h2 are not read there.  With r >= the
+ * longest length and no gradient behind it this is what the plain pair computes in front of r, without the steps behind.
+ * Both passes must be given the same word, unchanged in between.  Argument checks are those of the plain pair.
  */
 int dsp_hmlstm_tape_bytes(const dsp_hmlstm* h, int32_t T, int32_t B, int64_t* bytes);
 int dsp_hmlstm_forward_train(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
@@ -557,6 +568,14 @@ int dsp_hmlstm_backward(const dsp_hmlstm* h, int32_t T, int32_t B, float a, cons
                         const void* d_tape, int64_t tape_bytes, const float* d_h1, const float* d_h2, const uint8_t* d_z1,
                         const uint8_t* d_z2, const float* d_g_h1, const float* d_g_h2, const float* d_g_last, float* d_dfs1,
                         float* d_dfs2, void* stream);
+int dsp_hmlstm_forward_train_rows(const dsp_hmlstm* h, const float* d_x, int32_t T, int32_t B, float a, const int32_t* d_len,
+                                  const int32_t* d_rows, const float* d_state_in, float* d_state_out, float* d_h1, float* d_h2,
+                                  uint8_t* d_z1, uint8_t* d_z2, float* d_zhat, float* d_last_h2, void* d_tape, int64_t tape_bytes,
+                                  void* stream);
+int dsp_hmlstm_backward_rows(const dsp_hmlstm* h, int32_t T, int32_t B, float a, const int32_t* d_len, const int32_t* d_rows,
+                             const float* d_state_in, const void* d_tape, int64_t tape_bytes, const float* d_h1, const float* d_h2,
+                             const uint8_t* d_z1, const uint8_t* d_z2, const float* d_g_h1, const float* d_g_h2,
+                             const float* d_g_last, float* d_dfs1, float* d_dfs2, void* stream);
 
 /* ---- the classifiers' encoder (layers.DynamicEncoder, the first stage of every head in rnn_clf.py) --------- */
 /*

@@ -1,6 +1,6 @@
 // Stand-alone host check of the recurrent training entry points (include/dsp_frontend.h: dsp_bigru_tape_bytes,
 // dsp_bigru_tape_rows, dsp_bigru_forward_train, dsp_bigru_backward, dsp_hmlstm_tape_bytes, dsp_hmlstm_forward_train,
-// dsp_hmlstm_backward, and the NULL checks of dsp_bigru_refresh / dsp_hmlstm_refresh), whose argument checks are shared
+// dsp_hmlstm_backward, their twins under a row bound dsp_hmlstm_forward_train_rows / dsp_hmlstm_backward_rows, and the NULL checks of dsp_bigru_refresh / dsp_hmlstm_refresh), whose argument checks are shared
 // (csrc/dsp_rnn.hip): every argument error is DSP_EINVAL with a message, before any device call, so the program needs no GPU.  `make -C dsp-speech-recognition_amd/csrc asan-rnn` builds it
 // with AddressSanitizer + UBSan against the sanitized build of the library and runs it; it needs no preloaded runtime.
 #include <cstdint>
@@ -62,6 +62,11 @@ int main() {
     EXPECT(dsp_hmlstm_backward(nullptr, 4, 4, 1.0f, nullptr, nullptr, p, big, p, p, u, u, nullptr, nullptr, nullptr, p, p, nullptr), "no gradient");
     EXPECT(dsp_hmlstm_backward(nullptr, 4, 4, 1.0f, nullptr, nullptr, p, big, p, p, u, u, p, p, p, p, nullptr, nullptr), "NULL output");
     EXPECT(dsp_hmlstm_backward(nullptr, 4, 4, 1.0f, nullptr, nullptr, p, big, p, p, u, u, p, p, p, p, p, nullptr), "NULL handle");
+    // the pair under a row bound shares the plain pair's checks; d_rows itself may be NULL and is never followed by the host
+    EXPECT(dsp_hmlstm_forward_train_rows(nullptr, nullptr, 4, 4, 1.0f, nullptr, nullptr, nullptr, p, p, p, u, u, p, p, p, big, nullptr), "NULL input");
+    EXPECT(dsp_hmlstm_forward_train_rows(nullptr, p, 4, 4, 1.0f, nullptr, reinterpret_cast<int32_t*>(buf), nullptr, p, p, p, u, u, p, p, p, big, nullptr), "NULL handle");
+    EXPECT(dsp_hmlstm_backward_rows(nullptr, 4, 4, 1.0f, nullptr, nullptr, nullptr, p, big, p, p, u, u, p, p, p, p, nullptr, nullptr), "NULL output");
+    EXPECT(dsp_hmlstm_backward_rows(nullptr, 4, 4, 1.0f, nullptr, reinterpret_cast<int32_t*>(buf), nullptr, p, big, p, p, u, u, p, p, p, p, p, nullptr), "NULL handle");
     // refresh: a handle needs a device to exist, so what can be shown here is that neither NULL is followed (the size and
     // NULL-parameter checks against a real handle are in tests/test_gpu_head_train.py)
     dsp_bigru_desc gd = {};
