@@ -64,6 +64,10 @@ class AttnDesc(C.Structure):
     ]
 
 
+class RowsOperand(C.Structure):
+    _fields_ = [('d_ptr', c_vp), ('stride_t', c_i64), ('stride_b', c_i64), ('cols', c_i32), ('reserved', c_i32)]
+
+
 class EnsembleRule(C.Structure):
     _fields_ = [('label_a', c_i32), ('label_b', c_i32), ('threshold', c_f64), ('svm', c_vp)]
 
@@ -194,6 +198,10 @@ SIGNATURES = {
     'dsp_adam_set_step': (C.c_int, [c_vp, c_i64, c_vp]),
     'dsp_adam_get_state': (C.c_int, [c_vp, C.POINTER(c_i64), c_vp, c_vp]),
     'dsp_adam_step': (C.c_int, [c_vp, c_i32, c_vp]),
+    'dsp_rows_wgrad_scratch_bytes': (C.c_int, [c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i64)]),
+    'dsp_rows_wgrad': (C.c_int, [C.POINTER(RowsOperand), C.POINTER(RowsOperand), c_i32, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                 c_vp, c_i64, c_vp]),
+    'dsp_rows_product': (C.c_int, [C.POINTER(RowsOperand), c_vp, C.POINTER(RowsOperand), c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

@@ -55,6 +55,20 @@ def _check_device_grad(who, device_len, device_grad):
         raise ValueError(f'{who}: device_grad=True needs device_len=True (it is the training form of the device-length path)')
 
 
+def _want_wgrad(who, native_wgrad, default, train):
+    """``native_wgrad`` resolved.  The switch is valid wherever the native training path runs (``train``); anywhere else an
+    explicit True raises.  None takes the class default, which never raises."""
+    if native_wgrad and not train:
+        raise RuntimeError(f'{who}: native_wgrad=True cannot run: the native training path does not run here (no gradient is '
+                           'required, or another route was chosen)')
+    return bool(train and (default if native_wgrad is None else native_wgrad))
+
+
+def _check_rows_word(who, d_rows, x):
+    if not (torch.is_tensor(d_rows) and d_rows.dtype == torch.int32 and d_rows.numel() == 1 and d_rows.device == x.device):
+        raise TypeError(f"{who}: d_rows must be a one-element int32 tensor on the input's device")
+
+
 def _check_device_len(who, inp, len0, module, device_grad=False):
     """The conditions of ``device_len=True``: lengths as a [B] int32 tensor on ``inp``'s device, and no gradient required
     unless ``device_grad`` is given.  -> whether a gradient is required."""
@@ -240,6 +254,7 @@ class _DynEnc(_NativeHandle, nn.Module):
         ``native=None`` keeps ``nn.GRU`` whenever a gradient is required, unless ``native_train_default`` is set."""
     native_default = False         # what ``native=None`` picks where the native path can run: opt-in until DESIGN 7.3's timing shows it ahead
     native_train_default = False   # what ``native=None`` picks when a gradient is required: nn.GRU, until DESIGN 7.5's timing decides
+    native_wgrad_default = False   # what ``native_wgrad=None`` picks on the native training path: torch's GEMMs (DESIGN 7.14)
     _lib = 'dsp_bigru'
 
     def __init__(self, input_size, hidden_size, n_layers, dropout=0.0):
@@ -303,9 +318,10 @@ class _DynEnc(_NativeHandle, nn.Module):
                                             work.data_ptr(), nbytes.value, torch.cuda.current_stream(dev).cuda_stream))
         return y, hn
 
-    def _run_native_train(self, x, lens, drop=None):
+    def _run_native_train(self, x, lens, drop=None, wgrad=False):
         """The native training path: y and h_n attached to the autograd graph.  ``drop``: the inter-layer multipliers
-        [n_layers - 1, max(lens), B, 2 H] (0 or 1 / (1 - p)); drawn here in training mode when None."""
+        [n_layers - 1, max(lens), B, 2 H] (0 or 1 / (1 - p)); drawn here in training mode when None.  ``wgrad``: the products
+        behind the backward recurrence as native launches (features/wgrad.py) over the max(lens) rows."""
         B, H, dev, g = x.shape[1], self.hidden_size, x.device, self.gru
         T = int(lens.max())
         assert lens.numel() == B and int(lens.min()) >= 1 and T <= x.shape[0], 'lengths do not fit the input'
@@ -319,12 +335,15 @@ class _DynEnc(_NativeHandle, nn.Module):
             if drop is not None:
                 drop = drop.detach().to(torch.float32).contiguous()
                 assert tuple(drop.shape) == (g.num_layers - 1, T, B, 2 * H), 'drop does not fit [n_layers - 1, T, B, 2 H]'
+            if wgrad:
+                return _DynEncWgradTrain.apply(self, T, d_len, drop, x, None, *self._params())
             return _DynEncTrain.apply(self, T, d_len, drop, x, *self._params())
 
-    def _run_device_train(self, x, d_len, drop=None):
+    def _run_device_train(self, x, d_len, drop=None, wgrad=False, d_rows=None):
         """The native training path with the lengths on the device (``device_grad=True``): all x.shape[0] rows of the buffer
         are used -- max(len0) is not known here --, so the multipliers are drawn as [n_layers - 1, x.shape[0], B, 2 H].  The
-        handle survives an optimiser step (``refresh=True``)."""
+        handle survives an optimiser step (``refresh=True``).  ``wgrad``: the products behind the backward recurrence as
+        native launches that stop at clamp(d_rows[0], 1, T) rows, read on the device (all T rows without ``d_rows``)."""
         B, H, dev, g = x.shape[1], self.hidden_size, x.device, self.gru
         T = x.shape[0]
         with torch.cuda.device(dev):
@@ -335,6 +354,8 @@ class _DynEnc(_NativeHandle, nn.Module):
             if drop is not None:
                 drop = drop.detach().to(torch.float32).contiguous()
                 assert tuple(drop.shape) == (g.num_layers - 1, T, B, 2 * H), 'drop does not fit [n_layers - 1, T, B, 2 H]'
+            if wgrad:
+                return _DynEncWgradTrain.apply(self, T, d_len, drop, x, d_rows, *self._params())
             return _DynEncDeviceTrain.apply(self, T, d_len, drop, x, *self._params())
 
     # ---- nn.GRU path (layers.py:63-76) -----------------------------------------------------------------------------------
@@ -347,8 +368,15 @@ class _DynEnc(_NativeHandle, nn.Module):
         h = self.hidden_size
         return (y[:, :, :h] + y[:, :, h:])[:, unsort].contiguous(), hn[:, unsort].contiguous()
 
-    def run(self, x, lens, native=None, device_len=False, device_grad=False):
+    def run(self, x, lens, native=None, device_len=False, device_grad=False, native_wgrad=None, d_rows=None):
         """-> (y [max(lens), B, H], h_n [2 n_layers, B, H]), the reference's return value (layers.py:76).
+        ``native_wgrad=True``: on the native training path -- either route -- the products behind the backward recurrence
+        (``gru_param_grads``) run as native launches (features/wgrad.py) instead of torch's GEMMs, sums and ``cat`` copies;
+        anywhere else it raises.  ``native_wgrad=None`` takes ``native_wgrad_default``.  ``d_rows`` (with ``device_grad=True``): a
+        one-element int32 tensor on x's device holding a row count no smaller than the longest length, such as
+        ``head_length_info(...)[2][0:1]``: those launches stop at clamp(d_rows[0], 1, x.shape[0]) rows, read on the device.  It
+        is read on the device when the kernels run and must hold the same value at the backward call.  On the host-length
+        route the buffers already end at max(lens) rows and no bound is needed.
         ``device_len=True``: ``lens`` is a [B] int32 tensor on x's device with entries in [1, x.shape[0]] and stays there; the
         native forward runs over all x.shape[0] rows (y has that many, exact zero rows behind each end) and nothing is read
         back.  Forward only: a required gradient, or anything else the native path cannot serve, raises --
@@ -356,6 +384,10 @@ class _DynEnc(_NativeHandle, nn.Module):
         x.shape[0] rows (``_run_device_train``; training mode, as ``native=True``), and the handle is refreshed in place
         after an optimiser step instead of rebuilt."""
         _check_device_grad('_DynEnc', device_len, device_grad)
+        if d_rows is not None:
+            if not device_grad:
+                raise ValueError('_DynEnc: d_rows needs device_len=True, device_grad=True (it bounds the native training path)')
+            _check_rows_word('_DynEnc', d_rows, x)
         if device_len:
             needs_grad = _check_device_len('_DynEnc', x, lens, self, device_grad)
             if needs_grad and not self.training:
@@ -364,16 +396,19 @@ class _DynEnc(_NativeHandle, nn.Module):
                 why = self.native_supported(x, train=needs_grad)
             if why is not None:
                 raise RuntimeError(f'_DynEnc: the native path cannot run: {why}')
+            wgrad = _want_wgrad('_DynEnc', native_wgrad, self.native_wgrad_default, needs_grad)
             if needs_grad:
-                return self._run_device_train(x, lens.contiguous())
+                return self._run_device_train(x, lens.contiguous(), wgrad=wgrad, d_rows=d_rows)
             if device_grad:
                 self._native_handle(x.device, refresh=True)
             return self._launch_native(x, x.shape[0], lens.contiguous())
         lens = torch.as_tensor(_lengths(lens))
         if native is False:
+            _want_wgrad('_DynEnc', native_wgrad, False, False)
             return self._run_torch(x, lens)
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
         if native is None and not (self.native_train_default if needs_grad else self.native_default):
+            _want_wgrad('_DynEnc', native_wgrad, False, False)
             return self._run_torch(x, lens)                                     # (nothing to find out about the native path)
         if needs_grad and not self.training:                                    # eval mode keeps what it always did: no native gradient
             why = 'a gradient is required and the module is in eval mode (the native training path serves training mode)'
@@ -384,11 +419,13 @@ class _DynEnc(_NativeHandle, nn.Module):
         if native:
             if why is not None:
                 raise RuntimeError(f"_DynEnc: the native {'training path (a gradient is required)' if needs_grad else 'path'} cannot run: {why}")
-            return self._run_native_train(x, lens) if needs_grad else self._run_native(x, lens)
+            wgrad = _want_wgrad('_DynEnc', native_wgrad, self.native_wgrad_default, needs_grad)
+            return self._run_native_train(x, lens, wgrad=wgrad) if needs_grad else self._run_native(x, lens)
+        _want_wgrad('_DynEnc', native_wgrad, False, False)
         return self._run_torch(x, lens)
 
-    def forward(self, x, lens, native=None, device_len=False, device_grad=False):
-        return self.run(x, lens, native, device_len, device_grad)[0]
+    def forward(self, x, lens, native=None, device_len=False, device_grad=False, native_wgrad=None, d_rows=None):
+        return self.run(x, lens, native, device_len, device_grad, native_wgrad, d_rows)[0]
 
 
 def _ones_col_sum(a):
@@ -464,7 +501,23 @@ class _DynEncDeviceTrain(torch.autograd.Function):
         return _dynenc_train_backward(ctx, g_y, g_hn)
 
 
-def _dynenc_train_forward(ctx, col_sum, mod, T, d_len, drop, x, *params):
+class _DynEncWgradTrain(torch.autograd.Function):
+    """``_DynEncTrain`` with the products behind the backward recurrence as native launches (``native_wgrad=True``;
+    features/wgrad.py: ``gru_param_grads_native``) on either route.  Inputs: (module, T, d_len, drop or None, x, d_rows or None,
+    the parameters).  ``d_rows``: a one-element int32 tensor on x's device, the row bound of those launches: they stop at
+    clamp(d_rows[0], 1, T) rows.  It is read on the device when the kernels run and must hold the same value at the backward
+    call.  None (the host-length route, whose T is max(lens) already): all T rows."""
+
+    @staticmethod
+    def forward(ctx, mod, T, d_len, drop, x, d_rows, *params):
+        return _dynenc_train_forward(ctx, None, mod, T, d_len, drop, x, *params, wgrad=True, d_rows=d_rows)
+
+    @staticmethod
+    def backward(ctx, g_y, g_hn):
+        return _dynenc_train_backward(ctx, g_y, g_hn)
+
+
+def _dynenc_train_forward(ctx, col_sum, mod, T, d_len, drop, x, *params, wgrad=False, d_rows=None):
     from . import _native as nat
     ctx.set_materialize_grads(False)                     # an unused output hands None to backward, not a tensor of zeros
     B, H, L, dev = x.shape[1], mod.hidden_size, mod.gru.num_layers, x.device
@@ -480,7 +533,8 @@ def _dynenc_train_forward(ctx, col_sum, mod, T, d_len, drop, x, *params):
                                           torch.cuda.current_stream(dev).cuda_stream))
     ctx.mod, ctx.tape_bytes, ctx.handle_key, ctx.has_drop = mod, nbytes.value, mod._handle_key, drop is not None
     ctx.col_sum = col_sum
-    ctx.save_for_backward(xc, d_len, tape, *([drop] if drop is not None else []), *params)
+    ctx.wgrad, ctx.has_rows = wgrad, d_rows is not None                   # (wgrad: one more input, d_rows, in front of the parameters)
+    ctx.save_for_backward(xc, d_len, tape, *([drop] if drop is not None else []), *([d_rows] if ctx.has_rows else []), *params)
     return y, hn
 
 def _dynenc_train_backward(ctx, g_y, g_hn):
@@ -490,12 +544,16 @@ def _dynenc_train_backward(ctx, g_y, g_hn):
     saved = ctx.saved_tensors
     xc, d_len, tape = saved[:3]
     drop = saved[3] if ctx.has_drop else None
-    params = [p.detach() for p in saved[4 if ctx.has_drop else 3:]]
+    k = 4 if ctx.has_drop else 3
+    d_rows = saved[k] if ctx.has_rows else None
+    params = [p.detach() for p in saved[k + (1 if ctx.has_rows else 0):]]
     T, B, _ = xc.shape
     H, L, dev = mod.hidden_size, mod.gru.num_layers, xc.device
     grads = [None] * (1 + 8 * L)
+    p0 = 6 if ctx.wgrad else 5                                               # the first parameter among the inputs
+    pack = lambda: (None,) * 4 + (grads[0],) + (None,) * (p0 - 5) + tuple(grads[1:])
     if g_y is None and g_hn is None:
-        return (None,) * 4 + tuple(grads)
+        return pack()
     gp = lambda g: None if g is None else g.to(torch.float32).contiguous()
     g, g_hn = gp(g_y), gp(g_hn)
     lib = nat.load()
@@ -512,12 +570,16 @@ def _dynenc_train_backward(ctx, g_y, g_hn):
                                              torch.cuda.current_stream(dev).cuda_stream))
             dl = drop[l - 1] if (drop is not None and l > 0) else None
             x_l = xc if l == 0 else (rows[l - 1] if dl is None else rows[l - 1] * dl)
-            need = [l > 0 or ctx.needs_input_grad[4]] + list(ctx.needs_input_grad[5 + 8 * l:13 + 8 * l])
-            res = gru_param_grads(params[8 * l:8 * l + 8], x_l, rows[l], da, dl, need, ctx.col_sum)
+            need = [l > 0 or ctx.needs_input_grad[4]] + list(ctx.needs_input_grad[p0 + 8 * l:p0 + 8 + 8 * l])
+            if ctx.wgrad:
+                from .wgrad import gru_param_grads_native
+                res = gru_param_grads_native(params[8 * l:8 * l + 8], x_l, rows[l], da, dl, need, d_rows)
+            else:
+                res = gru_param_grads(params[8 * l:8 * l + 8], x_l, rows[l], da, dl, need, ctx.col_sum)
             grads[1 + 8 * l:9 + 8 * l] = res[1:]
             g = res[0]
         grads[0] = g
-    return (None,) * 4 + tuple(grads)
+    return pack()
 
 
 class RNNHead(nn.Module):
@@ -528,7 +590,7 @@ class RNNHead(nn.Module):
         self.enc = _DynEnc(feat_size, hidden, layers)
         self.out = nn.Linear(2 * hidden, classes)
 
-    def forward(self, inp, len0, native_enc=None, device_len=False, device_grad=False):
+    def forward(self, inp, len0, native_enc=None, device_len=False, device_grad=False, native_wgrad=None):
         """inp: [T, B, 39] (zero beyond each utterance's length), len0: lengths (numpy / list / tensor) -> [B, 20].
         ``device_len=True``: len0 is a [B] int32 tensor on inp's device and is never read from the host (module docstring);
         ``device_grad=True`` with it serves a required gradient on that path."""
@@ -536,10 +598,11 @@ class RNNHead(nn.Module):
         if device_len:
             _check_device_len('RNNHead', inp, len0, self, device_grad)
             d_len, _, info = head_length_info(len0, inp.shape[0], 1)
-            y = self.enc(inp, d_len, device_len=True, device_grad=device_grad)  # [T, B, H], zeros behind each end
+            y = self.enc(inp, d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad,
+                         d_rows=info[0:1] if device_grad else None)             # [T, B, H], zeros behind each end
             return self.out(_pool_native(y, d_len, info[0:1], grad=device_grad))
         lens = torch.as_tensor(_lengths(len0))
-        y = self.enc(inp, lens, native=native_enc)                          # [max(len0), B, H], zeros behind each end
+        y = self.enc(inp, lens, native=native_enc, native_wgrad=native_wgrad)    # [max(len0), B, H], zeros behind each end
         avg = y.sum(0) / lens.to(inp.device, inp.dtype).unsqueeze(1)        # rnn_clf.py:29-30
         mx = y.max(0).values                                                # rnn_clf.py:31 (over the padded rows too)
         return self.out(torch.cat([avg, mx], dim=1))
@@ -568,21 +631,22 @@ class HRNNHead(nn.Module):
         self.enc2 = _DynEnc(200, 200, 1)
         self.out = nn.Linear(400, 20)
 
-    def _levels(self, inp, len0, native_enc=None):
+    def _levels(self, inp, len0, native_enc=None, native_wgrad=None):
         len0 = _lengths(len0)
         len1 = (len0 + self.hir - 1) // self.hir                      # rnn_clf.py:52
-        y = self.enc1(inp, len0, native=native_enc)[:, :, -self.hidden_size:]            # rnn_clf.py:58
-        return self.enc2(y[0::self.hir], len1, native=native_enc), len1                  # rnn_clf.py:61-65
+        y = self.enc1(inp, len0, native=native_enc, native_wgrad=native_wgrad)[:, :, -self.hidden_size:]            # rnn_clf.py:58
+        return self.enc2(y[0::self.hir], len1, native=native_enc, native_wgrad=native_wgrad), len1                  # rnn_clf.py:61-65
 
-    def _levels_device(self, inp, len0, device_grad=False):
+    def _levels_device(self, inp, len0, device_grad=False, native_wgrad=None):
         """``_levels`` with the lengths on the device: all ceil(T / hir) picked rows go into enc2 -> (y2, len1, info)."""
         d_len, d_len1, info = head_length_info(len0, inp.shape[0], self.hir)
-        y = self.enc1(inp, d_len, device_len=True, device_grad=device_grad)[:, :, -self.hidden_size:]
-        return self.enc2(y[0::self.hir], d_len1, device_len=True, device_grad=device_grad), d_len1, info
+        rows0, rows1 = (info[0:1], info[1:2]) if device_grad else (None, None)   # max(len0) and ceil(max(len0) / hir), on the device
+        y = self.enc1(inp, d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad, d_rows=rows0)[:, :, -self.hidden_size:]
+        return self.enc2(y[0::self.hir], d_len1, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad, d_rows=rows1), d_len1, info
 
-    def _forward_device(self, inp, len0, dropout, attn=None, device_grad=False):
+    def _forward_device(self, inp, len0, dropout, attn=None, device_grad=False, native_wgrad=None):
         _check_device_len(type(self).__name__, inp, len0, self, device_grad)
-        y2, d_len1, info = self._levels_device(inp, len0, device_grad)
+        y2, d_len1, info = self._levels_device(inp, len0, device_grad, native_wgrad)
         rows = info[1:2]                                                        # ceil(max(len0) / hir), on the device
         if attn is None:
             feat = _pool_native(y2, d_len1, rows, grad=device_grad)
@@ -591,11 +655,11 @@ class HRNNHead(nn.Module):
         out = self.out(feat)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
 
-    def forward(self, inp, len0, dropout=True, native_enc=None, device_len=False, device_grad=False):
+    def forward(self, inp, len0, dropout=True, native_enc=None, device_len=False, device_grad=False, native_wgrad=None):
         _check_device_grad(type(self).__name__, device_len, device_grad)
         if device_len:
-            return self._forward_device(inp, len0, dropout, device_grad=device_grad)
-        y2, len1 = self._levels(inp, len0, native_enc)
+            return self._forward_device(inp, len0, dropout, device_grad=device_grad, native_wgrad=native_wgrad)
+        y2, len1 = self._levels(inp, len0, native_enc, native_wgrad)
         out, feat = _pool_head(y2, len1, self.out)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
 
@@ -795,11 +859,11 @@ class HRNNAttHead(HRNNHead):
         super().__init__(feat_size)
         self.attn = _SelfAttn(200)
 
-    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False, device_grad=False):
+    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False, device_grad=False, native_wgrad=None):
         _check_device_grad('HRNNAttHead', device_len, device_grad)
         if device_len:
-            return self._forward_device(inp, len0, dropout, self.attn, device_grad)
-        y2, len1 = self._levels(inp, len0, native_enc)
+            return self._forward_device(inp, len0, dropout, self.attn, device_grad, native_wgrad)
+        y2, len1 = self._levels(inp, len0, native_enc, native_wgrad)
         out, feat = _pool_head(y2, len1, self.out, self.attn, native_attn)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
 
@@ -1107,15 +1171,17 @@ class TransformerHead(nn.Module):
         self.out = nn.Linear(400, 20)
         self.hidden_size = 200
 
-    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False, device_grad=False):
+    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False, device_grad=False, native_wgrad=None):
         _check_device_grad('TransformerHead', device_len, device_grad)
         if device_len:
             _check_device_len('TransformerHead', inp, len0, self, device_grad)
             d_len, d_len1, info = head_length_info(len0, inp.shape[0], self.hir)
             attn_out = self.attn_enc(inp, native=True, refresh=device_grad)
             a = torch.nn.functional.dropout(attn_out, 0.5) if dropout else attn_out
-            y = self.rnn_enc_1(torch.cat([inp, a], 2), d_len, device_len=True, device_grad=device_grad)[:, :, -self.hidden_size:]
-            y2 = self.rnn_enc_2(y[0::self.hir], d_len1, device_len=True, device_grad=device_grad)
+            rows0, rows1 = (info[0:1], info[1:2]) if device_grad else (None, None)
+            y = self.rnn_enc_1(torch.cat([inp, a], 2), d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad,
+                               d_rows=rows0)[:, :, -self.hidden_size:]
+            y2 = self.rnn_enc_2(y[0::self.hir], d_len1, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad, d_rows=rows1)
             feat = _pool_native(y2, d_len1, info[1:2], grad=device_grad)
             out = self.out(feat)
             return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat, attn_out
@@ -1124,8 +1190,8 @@ class TransformerHead(nn.Module):
         attn_out = self.attn_enc(inp, native=native_attn)
         a = torch.nn.functional.dropout(attn_out, 0.5) if dropout else attn_out
         # (the reference concatenates all 200 padded rows; the packed GRU then reads max(len0) of them)
-        y = self.rnn_enc_1(torch.cat([inp, a], 2), len0, native=native_enc)[:, :, -self.hidden_size:]
-        y2 = self.rnn_enc_2(y[0::self.hir], len1, native=native_enc)
+        y = self.rnn_enc_1(torch.cat([inp, a], 2), len0, native=native_enc, native_wgrad=native_wgrad)[:, :, -self.hidden_size:]
+        y2 = self.rnn_enc_2(y[0::self.hir], len1, native=native_enc, native_wgrad=native_wgrad)
         out, feat = _pool_head(y2, len1, self.out)
         return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat, attn_out
 
@@ -1210,6 +1276,8 @@ class _HMLSTMTrain(torch.autograd.Function):
     dsp_hmlstm_backward_rows): the kernels stop at clamp(d_rows[0], 1, T) rows and leave exact zeros behind.  It is read on
     the device when the kernels run and must hold the same value at the backward call."""
 
+    wgrad = False
+
     @staticmethod
     def forward(ctx, mod, a, d_len, d_rows, state_in, x, *params):
         from . import _native as nat
@@ -1271,8 +1339,19 @@ class _HMLSTMTrain(torch.autograd.Function):
                            ctx.tape_bytes, h_1.data_ptr(), h_2.data_ptr(), z_1.data_ptr(), z_2.data_ptr(),
                            _ptr(g_h1), _ptr(g_h2), _ptr(g_last), dfs1.data_ptr(), dfs2.data_ptr(),
                            torch.cuda.current_stream(dev).cuda_stream))
-            grads = hm_param_grads([p.detach() for p in params], xc, state_in, h_1, h_2, z_1, dfs1, dfs2, need)
+            if ctx._forward_cls.wgrad:
+                from .wgrad import hm_param_grads_native
+                grads = hm_param_grads_native([p.detach() for p in params], xc, state_in, h_1, h_2, z_1, dfs1, dfs2, need, d_rows)
+            else:
+                grads = hm_param_grads([p.detach() for p in params], xc, state_in, h_1, h_2, z_1, dfs1, dfs2, need)
         return (None, None, None, None, None) + grads
+
+
+class _HMLSTMWgradTrain(_HMLSTMTrain):
+    """``_HMLSTMTrain`` with the products behind the backward recurrence as native launches (``native_wgrad=True``;
+    features/wgrad.py: ``hm_param_grads_native``).  With ``d_rows`` they stop at the same clamp(d_rows[0], 1, T) rows as the two
+    passes: it is read on the device when the kernels run and must hold the same value at the backward call."""
+    wgrad = True
 
 
 class HMLSTMResult:
@@ -1309,6 +1388,7 @@ class HMLSTM(_NativeHandle, nn.Module):
     hmrnn.py:53,121-122, so its ``HMRNN.adjust_param`` -- which adds to ``HM_LSTM.a`` only -- never reaches them; here the
     one attribute is what both cells use.)"""
     native_train_default = False   # what ``native=None`` picks when a gradient is required: the loop, until DESIGN 7.4's timing shows the native path ahead
+    native_wgrad_default = False   # what ``native_wgrad=None`` picks on the native training path: torch's GEMMs (DESIGN 7.14)
     _lib = 'dsp_hmlstm'
 
     def __init__(self, a, input_size, size_list):
@@ -1377,7 +1457,7 @@ class HMLSTM(_NativeHandle, nn.Module):
         zf = lambda z: None if z is None else z.to(torch.float32).unsqueeze(2)
         return HMLSTMResult(h_1=h_1, h_2=h_2, z_1=zf(z_1), z_2=zf(z_2), hidden=hid, z_hat=z_hat, last_h2=last)
 
-    def _run_native_train(self, x, hidden, lens, d_len=None, d_rows=None):
+    def _run_native_train(self, x, hidden, lens, d_len=None, d_rows=None, wgrad=False):
         """The native training path: the same HMLSTMResult, h_1 / h_2 / last_h2 attached to the autograd graph.
         ``d_len`` (``device_grad=True``): the lengths as a [B] int32 tensor on x's device, read in place; ``last_h2`` is then
         the only field returned, and the handle survives an optimiser step (``refresh=True``).  All T rows run on this path
@@ -1390,14 +1470,15 @@ class HMLSTM(_NativeHandle, nn.Module):
             self._native_handle(dev, refresh=d_len is not None)
             f32 = dict(dtype=torch.float32, device=dev)
             state_in = None if hidden is None else _pack_state(hidden, H1, H2, B, **f32)
+            train = _HMLSTMWgradTrain if wgrad else _HMLSTMTrain          # (``wgrad``: the products as native launches)
             if d_len is not None:
-                last = _HMLSTMTrain.apply(self, float(self.a), d_len, d_rows, state_in, x, *self._params())[2]
+                last = train.apply(self, float(self.a), d_len, d_rows, state_in, x, *self._params())[2]
                 return HMLSTMResult(last_h2=last)
             if lens is not None:
                 d_len = torch.as_tensor(_lengths(lens), dtype=torch.int32).to(dev)
             else:
                 d_len = torch.full((B,), T, dtype=torch.int32, device=dev)
-            h_1, h_2, last, z_1, z_2, z_hat, state_out = _HMLSTMTrain.apply(self, float(self.a), d_len, None, state_in, x, *self._params())
+            h_1, h_2, last, z_1, z_2, z_hat, state_out = train.apply(self, float(self.a), d_len, None, state_in, x, *self._params())
         hid = _split_state(state_out, H1, H2, B)
         zf = lambda z: z.to(torch.float32).unsqueeze(2)
         return HMLSTMResult(h_1=h_1, h_2=h_2, z_1=zf(z_1), z_2=zf(z_2), hidden=hid, z_hat=z_hat, last_h2=last if lens is not None else None)
@@ -1426,7 +1507,7 @@ class HMLSTM(_NativeHandle, nn.Module):
         return HMLSTMResult(h_1=torch.stack(hs1, dim=1), h_2=h_2, z_1=torch.stack(zs1, dim=1), z_2=torch.stack(zs2, dim=1),
                             hidden=(h1, c1, z1, h2, c2, z2), z_hat=torch.stack(zh).detach(), last_h2=last)
 
-    def run(self, x, hidden=None, lens=None, native=None, device_len=False, device_grad=False, d_rows=None):
+    def run(self, x, hidden=None, lens=None, native=None, device_len=False, device_grad=False, d_rows=None, native_wgrad=None):
         """Everything the forward pass yields, as an HMLSTMResult.  x: [T, B, input_size].
         ``device_len=True``: ``lens`` is a [B] int32 tensor on x's device with entries in [1, T] and stays there; the native
         forward yields ``last_h2`` alone (every other field is None), which lets each 16-column slice stop at its longest
@@ -1438,13 +1519,15 @@ class HMLSTM(_NativeHandle, nn.Module):
         must agree on the rows the tape holds: without ``d_rows`` all T rows run, and with it -- a one-element int32 tensor on
         x's device holding a row count no smaller than the longest length, such as ``head_length_info(...)[2][0:1]`` -- both
         passes stop at clamp(d_rows[0], 1, T) rows, read on the device, with the same ``last_h2`` and the same gradients (a
-        smaller count cuts the lengths to it).  ``d_rows`` serves the training path only and needs ``device_grad=True``."""
+        smaller count cuts the lengths to it).  ``d_rows`` serves the training path only and needs ``device_grad=True``.
+        ``native_wgrad=True``: on the native training path -- either route -- the products behind the backward recurrence
+        (``hm_param_grads``) run as native launches (features/wgrad.py), bounded by ``d_rows`` where it is given; anywhere else
+        it raises.  ``native_wgrad=None`` takes ``native_wgrad_default``."""
         _check_device_grad('HMLSTM', device_len, device_grad)
         if d_rows is not None:
             if not device_grad:
                 raise ValueError('HMLSTM: d_rows needs device_len=True, device_grad=True (it bounds the native training path)')
-            if not (torch.is_tensor(d_rows) and d_rows.dtype == torch.int32 and d_rows.numel() == 1 and d_rows.device == x.device):
-                raise TypeError("HMLSTM: d_rows must be a one-element int32 tensor on the input's device")
+            _check_rows_word('HMLSTM', d_rows, x)
         if device_len:
             needs_grad = _check_device_len('HMLSTM', x, lens, self, device_grad)
             if torch.is_grad_enabled() and hidden is not None and any(v.requires_grad for v in hidden):
@@ -1452,14 +1535,16 @@ class HMLSTM(_NativeHandle, nn.Module):
             why = self.native_supported(x)
             if why is not None:
                 raise RuntimeError(f'HMLSTM: the native path cannot run: {why}')
+            wgrad = _want_wgrad('HMLSTM', native_wgrad, self.native_wgrad_default, needs_grad)
             if needs_grad:
-                return self._run_native_train(x, hidden, None, d_len=lens.contiguous(), d_rows=d_rows)
+                return self._run_native_train(x, hidden, None, d_len=lens.contiguous(), d_rows=d_rows, wgrad=wgrad)
             if device_grad:
                 self._native_handle(x.device, refresh=True)
             return self._run_native(x, hidden, None, d_len=lens.contiguous(), last_only=True)
         hidden_grad = torch.is_grad_enabled() and hidden is not None and any(v.requires_grad for v in hidden)
         needs_grad = hidden_grad or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))
         if needs_grad and native is None and not self.native_train_default:
+            _want_wgrad('HMLSTM', native_wgrad, False, False)
             return self._run_torch(x, hidden, lens)
         why = 'the initial hidden requires a gradient' if hidden_grad else self.native_supported(x)
         if native is None:
@@ -1467,7 +1552,9 @@ class HMLSTM(_NativeHandle, nn.Module):
         if native:
             if why is not None:
                 raise RuntimeError(f'HMLSTM: the native path cannot run: {why}')
-            return self._run_native_train(x, hidden, lens) if needs_grad else self._run_native(x, hidden, lens)
+            wgrad = _want_wgrad('HMLSTM', native_wgrad, self.native_wgrad_default, needs_grad)
+            return self._run_native_train(x, hidden, lens, wgrad=wgrad) if needs_grad else self._run_native(x, hidden, lens)
+        _want_wgrad('HMLSTM', native_wgrad, False, False)
         return self._run_torch(x, hidden, lens)
 
     def forward(self, x, hidden=None, lens=None, native=None):
@@ -1491,24 +1578,25 @@ class HMRNNHead(nn.Module):
         self.enc2 = HMLSTM(1.0, 200, [200, 200])
         self.out = nn.Linear(600, 20)
 
-    def forward(self, inp, len0, dropout=True, native=None, native_enc=None, device_len=False, device_grad=False):
+    def forward(self, inp, len0, dropout=True, native=None, native_enc=None, device_len=False, device_grad=False, native_wgrad=None):
         _check_device_grad('HMRNNHead', device_len, device_grad)
         if device_len:
             _check_device_len('HMRNNHead', inp, len0, self, device_grad)
             d_len, _, info = head_length_info(len0, inp.shape[0], 1)
-            enc = self.enc1(inp, d_len, device_len=True, device_grad=device_grad)                        # [T, B, 200], zeros behind each end
+            enc = self.enc1(inp, d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad,
+                            d_rows=info[0:1] if device_grad else None)                                   # [T, B, 200], zeros behind each end
             if dropout:
                 enc = torch.nn.functional.dropout(enc, 0.2)
-            last = self.enc2.run(enc, None, lens=d_len, device_len=True, device_grad=device_grad,
+            last = self.enc2.run(enc, None, lens=d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad,
                                  d_rows=info[0:1] if device_grad else None).last_h2      # both passes stop at max(len0)
             feat = torch.cat([_pool_native(enc, d_len, info[0:1], grad=device_grad), last], dim=1)
             out = self.out(feat)
             return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
         len0 = _lengths(len0)
-        enc = self.enc1(inp, len0, native=native_enc)                                                    # [max(len0), B, 200]
+        enc = self.enc1(inp, len0, native=native_enc, native_wgrad=native_wgrad)                         # [max(len0), B, 200]
         if dropout:
             enc = torch.nn.functional.dropout(enc, 0.2)
-        last = self.enc2.run(enc, None, lens=len0, native=native).last_h2             # rnn_clf.py:139-143
+        last = self.enc2.run(enc, None, lens=len0, native=native, native_wgrad=native_wgrad).last_h2     # rnn_clf.py:139-143
         n = torch.as_tensor(len0, dtype=enc.dtype, device=enc.device)
         feat = torch.cat([enc.sum(0) / n.unsqueeze(1), enc.max(0).values, last], dim=1)
         out = self.out(feat)

@@ -1046,6 +1046,51 @@ int dsp_adam_set_step(dsp_adam* h, int64_t step, void* stream);
 int dsp_adam_get_state(const dsp_adam* h, int64_t* step, double* hyper, void* stream);
 int dsp_adam_step(dsp_adam* h, int32_t zero_grads, void* stream);
 
+/* ---- the products between the recurrent backward kernels, bounded by a row count read on the device (csrc/kernels_wgrad.h) ----
+ *
+ * The parameter and input gradients behind dsp_bigru_backward and dsp_hmlstm_backward are sums over the [T, B, ..] buffers those
+ * kernels leave.  A library GEMM takes its extents from the host; these take R = d_rows ? clamp(*d_rows, 1, T) : T from device
+ * memory when they RUN, read nothing at t >= R, and are fp32 on v_mfma_f32_16x16x4_f32 (exact f32: every element an fmaf chain
+ * in a fixed order).  No atomics, no memset, no grid barrier: the same bits on every run, capturable.
+ *
+ * An operand is a [T, B, cols] fp32 view with a unit column stride: element (t, b, c) at d_ptr[t stride_t + b stride_b + c],
+ * strides in floats and not negative (so da[:, :, d, :3 H] of a [T, B, 2, 4 H] buffer is d_ptr = da + d 4 H, stride_t = 8 H B,
+ * stride_b = 8 H, cols = 3 H, and a [B, T, H] buffer is stride_t = H, stride_b = T H).  reserved must be 0.
+ *
+ * dsp_rows_wgrad:   d_c[m, n] = sum_{t < R, b < B} s[t, b] a[t, b, m] xs[t, b, n]     m = a->cols, n = x->cols, d_c dense
+ *                   d_colsum[m] = sum_{t < R, b < B} a[t, b, m]                        unscaled; skipped when d_colsum is NULL
+ *   xs[t, b, :] = x[t + shift, b, :] where 0 <= t + shift < R; for t + shift < 0 the row d_x_init[b init_stride_b + ..] (zeros
+ *   when d_x_init is NULL; d_x_init needs shift = -1 and init_stride_b >= n); for t + shift >= R zeros, which is what a buffer
+ *   whose rows behind R are zero gives.  s = d_scale [T, B] dense, or 1 when NULL.  READ: rows t < R of a, x and d_scale, the
+ *   initial row, *d_rows.  NEVER READ: any row t >= R.  WRITTEN: every element of d_c (and d_colsum), and scratch.
+ *   Two launches: workgroups over (128 x 128 output tile) x (chunk of dsp-fixed whole time steps counted from t = 0, a function
+ *   of B alone) write partial tiles to d_scratch -- a chunk that starts at or behind R exits at once --, then one thread per
+ *   element adds the chunks below ceil(R / chunk) in index order.  The bits depend on (m, n, B, R) and the data, not on T: a
+ *   call bounded at R in a T-row buffer equals the unbounded call on the first R rows, bit for bit.
+ *   d_scratch: 16-byte aligned, at least the bytes dsp_rows_wgrad_scratch_bytes gives for (T, B, m, n).
+ *
+ * dsp_rows_product: d_y[t, b, :] = a0[t, b, :] d_w0 (+ a1[t, b, :] d_w1)   for t < R;   exact +0.0f for R <= t < T
+ *   d_w0 [a0->cols, n], d_w1 [a1->cols, n] dense; a1 and d_w1 both NULL for one product.  d_y [T, B, n] dense; EVERY element is
+ *   written on every call.  READ: rows t < R of a0 / a1, the matrices, *d_rows.  NEVER READ: any row t >= R.  One launch.
+ *
+ * 16-byte loads and stores are taken where a pointer and its strides allow them; a 4-byte-aligned view gives the same bits.
+ * LIMITS: T, B >= 1, T B < 2^31, at most 65535 chunks; cols and n in [1, 2048]; shift in {-1, 0, 1}; every pointer 4-byte
+ * aligned; outputs and scratch must not overlap anything read nor each other.  Anything else or a NULL mandatory pointer is
+ * DSP_EINVAL with a message before any launch.  Nothing is allocated or synchronised; everything runs on `stream`.
+ */
+typedef struct dsp_rows_operand {
+    const float* d_ptr;
+    int64_t stride_t, stride_b;
+    int32_t cols;
+    int32_t reserved;
+} dsp_rows_operand;
+int dsp_rows_wgrad_scratch_bytes(int32_t T, int32_t B, int32_t m, int32_t n, int64_t* out_bytes);
+int dsp_rows_wgrad(const dsp_rows_operand* a, const dsp_rows_operand* x, int32_t shift, const float* d_x_init, int64_t init_stride_b,
+                   const float* d_scale, int32_t T, int32_t B, const int32_t* d_rows, float* d_c, float* d_colsum, void* d_scratch,
+                   int64_t scratch_bytes, void* stream);
+int dsp_rows_product(const dsp_rows_operand* a0, const float* d_w0, const dsp_rows_operand* a1, const float* d_w1, int32_t n, int32_t T,
+                     int32_t B, const int32_t* d_rows, float* d_y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,9 @@ step -- of ``HMRNNHead`` and ``TransformerHead`` (seeded weights, training mode,
                Adam step behind it;
   (4) replay_adam  ``TrainBatch.capture(..., optimizer=DeviceAdam(...)).replay()``: the same graph with the native Adam step
                (csrc/kernels_optim.h) recorded behind the backward -- the whole step is one replay
+  (5) run_wgrad / replay_wgrad  routes (2) and (3) with ``native_wgrad=True``: the products behind the GRU and HM-LSTM backward
+               recurrences as native launches bounded by the row count on the device (csrc/kernels_wgrad.h) instead of torch's
+               GEMMs, sums and ``cat`` copies over all 200 rows; timed in the same rounds as their plain twins
 
 at B = 32 (the reference's cfg.batch_size) and B = 512, on the stored 16 kHz chirps of tests/ensemble_cases.py, repeated.
 
@@ -31,6 +34,7 @@ Every other figure is a host clock around --iters back-to-back steps that end in
 rounds are kept in the JSON).  Writes --out (default profiles/train_kbench.json) and prints it as one JSON line.
 
     python tools/kbench_train.py [--iters 20] [--warmup 3] [--rounds 3] [--batches 32,512] [--heads hmrnn,transformer]
+                                 [--routes host,host_keep,run,run_wgrad,replay,replay_wgrad,replay_adam,adam]
 """
 import argparse
 import json
@@ -116,6 +120,8 @@ def main():
     ap.add_argument('--adam-iters', type=int, default=200)
     ap.add_argument('--batches', default='32,512')
     ap.add_argument('--heads', default='hmrnn,transformer')
+    ap.add_argument('--routes', default='host,host_keep,run,run_wgrad,replay,replay_wgrad,replay_adam,adam',
+                    help='the routes to time (the others stay out of the JSON)')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'train_kbench.json'))
     args = ap.parse_args()
     import torch
@@ -128,6 +134,7 @@ def main():
     nat.require_device()
     dev = torch.device('cuda', nat.current_device())
     stored, rate = make_clips()
+    routes = set(args.routes.split(','))
     kinds = {'hmrnn': (HMRNNHead, dict(native=True, native_enc=True)), 'transformer': (TransformerHead, dict(native_enc=True, native_attn=True))}
     res = {'iters': args.iters, 'warmup': args.warmup, 'rounds': args.rounds, 'optimizer': 'torch.optim.Adam(lr=1e-4), eager',
            'clock': 'host clock around iters steps ending in a device synchronise; *_event_us and the adam section: device events',
@@ -135,10 +142,11 @@ def main():
     for kind in args.heads.split(','):
         cls, host_kw = kinds[kind]
         torch.manual_seed(0)
-        row = adam_alone(torch, dev, cls().to(dev), args.adam_iters, args.warmup, args.rounds)
-        res['adam'][kind] = row
-        print(f'{kind} Adam alone ({row["tensors"]} tensors, {row["parameters"]} parameters): '
-              + ', '.join(f'{k}={v:.1f}' for k, v in row.items() if k.endswith('_us')) + f', {row["device_adam_bytes_per_s"] / 1e12:.2f} TB/s eager, {row["device_adam_graph_bytes_per_s"] / 1e12:.2f} TB/s recorded', flush=True)
+        if 'adam' in routes:
+            row = adam_alone(torch, dev, cls().to(dev), args.adam_iters, args.warmup, args.rounds)
+            res['adam'][kind] = row
+            print(f'{kind} Adam alone ({row["tensors"]} tensors, {row["parameters"]} parameters): '
+                  + ', '.join(f'{k}={v:.1f}' for k, v in row.items() if k.endswith('_us')) + f', {row["device_adam_bytes_per_s"] / 1e12:.2f} TB/s eager, {row["device_adam_graph_bytes_per_s"] / 1e12:.2f} TB/s recorded', flush=True)
         for B in (int(v) for v in args.batches.split(',')):
             torch.manual_seed(0)
             head = cls().train()
@@ -168,44 +176,54 @@ def main():
                 else:
                     opt.step()
 
-            def run():
-                out = tb.run(buf, so, labels, d_jit)
+            def run(**kw):
+                out = tb.run(buf, so, labels, d_jit, **kw)
                 opt.zero_grad()
                 out.loss.backward()
                 opt.step()
 
-            rounds = {'host_us': [], 'host_keep_us': [], 'run_us': [], 'replay_us': [], 'replay_event_us': [], 'replay_adam_us': [],
-                      'replay_adam_event_us': []}
+            rounds = {}
+            timed = lambda name, clock, fn: rounds.setdefault(name, []).append(clock(torch, dev, fn, args.iters, args.warmup))
             for _ in range(args.rounds):
-                rounds['host_us'].append(per_step_us(torch, dev, host, args.iters, args.warmup))
-                rounds['host_keep_us'].append(per_step_us(torch, dev, lambda: host(True), args.iters, args.warmup))
-                rounds['run_us'].append(per_step_us(torch, dev, run, args.iters, args.warmup))
+                if 'host' in routes: timed('host_us', per_step_us, host)
+                if 'host_keep' in routes: timed('host_keep_us', per_step_us, lambda: host(True))
+                if 'run' in routes: timed('run_us', per_step_us, run)
+                if 'run_wgrad' in routes: timed('run_wgrad_us', per_step_us, lambda: run(native_wgrad=True))
             opt.zero_grad()
-            g = tb.capture(buf, so, labels, d_jit)
+            g = tb.capture(buf, so, labels, d_jit) if 'replay' in routes else None
+            gw = tb.capture(buf, so, labels, d_jit, native_wgrad=True) if 'replay_wgrad' in routes else None
 
-            def replay():
-                g.replay()
+            def replay(graph=None):
+                (g if graph is None else graph).replay()
                 opt.step()
 
             # the same head goes on training under the native optimiser: one replay is the whole step
-            dopt = DeviceAdam(params, lr=1e-4)
-            g2 = tb.capture(buf, so, labels, d_jit, optimizer=dopt)
+            g2 = tb.capture(buf, so, labels, d_jit, optimizer=DeviceAdam(params, lr=1e-4)) if 'replay_adam' in routes else None
             for _ in range(args.rounds):
-                rounds['replay_us'].append(per_step_us(torch, dev, replay, args.iters, args.warmup))
-                rounds['replay_event_us'].append(per_step_event_us(torch, dev, replay, args.iters, args.warmup))
-                rounds['replay_adam_us'].append(per_step_us(torch, dev, g2.replay, args.iters, args.warmup))
-                rounds['replay_adam_event_us'].append(per_step_event_us(torch, dev, g2.replay, args.iters, args.warmup))
+                if g is not None:
+                    timed('replay_us', per_step_us, replay)
+                    timed('replay_event_us', per_step_event_us, replay)
+                if gw is not None:
+                    timed('replay_wgrad_us', per_step_us, lambda: replay(gw))
+                    timed('replay_wgrad_event_us', per_step_event_us, lambda: replay(gw))
+                if g2 is not None:
+                    timed('replay_adam_us', per_step_us, g2.replay)
+                    timed('replay_adam_event_us', per_step_event_us, g2.replay)
             row = {k: float(np.median(v)) for k, v in rounds.items()}
-            row['handle_rebuild_us'] = row['host_us'] - row['host_keep_us']
-            row['host_over_run'] = row['host_us'] / row['run_us']
-            row['host_over_replay'] = row['host_us'] / row['replay_us']
-            row['replay_over_replay_adam'] = row['replay_us'] / row['replay_adam_us']
+            ratio = lambda a, b: row[a] / row[b] if a in row and b in row else None
+            if 'host_us' in row and 'host_keep_us' in row:
+                row['handle_rebuild_us'] = row['host_us'] - row['host_keep_us']
+            for name, (a, b) in {'host_over_run': ('host_us', 'run_us'), 'host_over_replay': ('host_us', 'replay_us'),
+                                 'replay_over_replay_adam': ('replay_us', 'replay_adam_us'), 'run_over_run_wgrad': ('run_us', 'run_wgrad_us'),
+                                 'replay_over_replay_wgrad': ('replay_us', 'replay_wgrad_us'), 'host_over_run_wgrad': ('host_us', 'run_wgrad_us')}.items():
+                if ratio(a, b) is not None:
+                    row[name] = ratio(a, b)
             row['spreads'] = {k: float(max(v) - min(v)) for k, v in rounds.items()}
             row['seconds_of_audio'] = float(so[-1]) / rate
             row['rounds'] = rounds
             res['steps'][f'{kind}_B{B}'] = row
             print(f'{kind} B={B}: ' + ', '.join(f'{k}={v:.0f}' for k, v in row.items() if k.endswith('_us')), flush=True)
-            del g, g2
+            del g, gw, g2
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as fh:
         json.dump(res, fh, indent=1)
