@@ -9,7 +9,8 @@ hand-written HIP kernels (gfx950) behind a ctypes C ABI (include/dsp_frontend.h)
 Unlike the reference's ``features/__init__.py`` this import has no side effects (no ./log/
 directory, no matplotlib / sklearn import).  Both pitch trackers (``pitch_detect_sr``, ``pitch_detect``) and
 ``pitch_feature`` are here, and ``features.ensemble`` evaluates the fitted pitch SVM and the ensemble's confidence gate
-(pitch_model.py:54-61, ensemble.py:44-67) on the device; fitting the SVM stays with sklearn.
+(pitch_model.py:54-61, ensemble.py:44-67) on the device; ``features.svmfit`` fits that scaler and SVM there as well
+(pitch_model.py:26-50: ``fit_pitch_svm``, ``grid_search``, ``PitchModelTrainer``).
 ``get_batch_full(feat)`` is RNNModel.get_batch_full (model.py:114-135) for the reference's list of (sig, rate) pairs, the
 rates mixed as reader.mini_batch_iterator yields them.  ``TrainBatch`` is the training step of model.py:137-147 on raw clips
 with the lengths kept on the device (features/train.py), and ``DeviceAdam`` its optimiser step (model.py:140-149) with the
@@ -24,10 +25,11 @@ from .pitch import (center_clip, max_pitch, pitch_detect_frame_sr, pitch_detect_
                     robust_max_pitch, smooth, window, pitch_detect, pitch_detect_frame, peak_score,
                     sub_endpoint_detect, find_smooth_subsequence, slope, quad_params, peakshift, pitch_feature,
                     pitch_feature_batch, pitch_features_device)
-from . import base, sigproc, endpoint, preprocess, pitch, batch, pipeline, ensemble, train, optim  # noqa: F401
+from . import base, sigproc, endpoint, preprocess, pitch, batch, pipeline, ensemble, train, optim, svmfit  # noqa: F401
 from .batch import FeaturePlan, EndpointPlan  # noqa: F401
 from .pipeline import VadMfccPipeline  # noqa: F401
 from .ensemble import PitchSVM, EnsembleBatch, MixedRateEnsembleBatch, ensemble_decide  # noqa: F401
 from .model_glue import MixedRateFeatureBatch, get_batch_full  # noqa: F401
+from .svmfit import fit_pitch_svm, grid_search, robust_scale_fit, svm_fit_problems, PitchModelTrainer  # noqa: F401
 from .train import TrainBatch  # noqa: F401
 from .optim import DeviceAdam  # noqa: F401

@@ -202,6 +202,11 @@ SIGNATURES = {
     'dsp_rows_wgrad': (C.c_int, [C.POINTER(RowsOperand), C.POINTER(RowsOperand), c_i32, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp,
                                  c_vp, c_i64, c_vp]),
     'dsp_rows_product': (C.c_int, [C.POINTER(RowsOperand), c_vp, C.POINTER(RowsOperand), c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'dsp_robust_scale_fit_batch': (C.c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_f64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'dsp_var_all': (C.c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'dsp_svm_fit_workspace_bytes': (C.c_int, [c_i32, c_i32, c_i32, C.POINTER(c_i64)]),
+    'dsp_svm_fit_batch': (C.c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_f64, c_i32, c_vp, c_i64,
+                                    c_vp, c_vp, c_vp, c_i64, c_vp]),
 }
 
 _lib = None

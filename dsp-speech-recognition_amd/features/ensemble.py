@@ -13,7 +13,9 @@ decides instead (pitch_model.py:54-61).
   ``run(sync_free=True)`` leaves them on the device (``device_len=True`` on the head), and ``capture()`` records that whole
   chain into ONE HIP graph whose ``replay()`` serves new clips written into the captured buffer.
 
-Training stays where it was: fit the scaler and the SVM with scikit-learn, then ``PitchSVM.from_sklearn(scaler, clf)``.
+Training (pitch_model.py:26-50) runs on the device too: ``PitchSVM.fit(X, y)`` fits the scaler and the SVM with the kernels
+of csrc/kernels_svmfit.h (features/svmfit.py: ``fit_pitch_svm``, ``grid_search``, ``PitchModelTrainer``).  A pair fitted with
+scikit-learn elsewhere still comes in through ``PitchSVM.from_sklearn(scaler, clf)``.
 """
 from __future__ import annotations
 
@@ -83,6 +85,13 @@ class PitchSVM:
         center = getattr(scaler, 'center_', None) if scaler is not None else None
         return cls(clf.support_vectors_, dual[0], np.asarray(clf.intercept_).reshape(-1)[0], float(gamma), classes,
                    scale=scale, center=center)
+
+    @classmethod
+    def fit(cls, X, y, **kwargs):
+        """``scaler.fit`` / ``scaler.transform`` / ``clf.fit`` of pitch_model.py:48-50 on the device: see
+        ``features.svmfit.fit_pitch_svm`` (classes, C, gamma, tol, max_iter, with_centering, quantile_range, valid, scaler)."""
+        from .svmfit import fit_pitch_svm
+        return fit_pitch_svm(X, y, **kwargs)
 
     def save(self, path):
         """The arrays as an .npz file (``load`` reads it back)."""
@@ -364,6 +373,34 @@ class EnsembleBatch(_EnsembleTail):
             return self._chain(clips, lay, self._m0(lay, clips.device), None, head_kwargs)
         inp, len0, endpoints = self.features.run(clips, layout=lay)
         return self._tail(inp, None, (len0, endpoints), [(lay, clips, self.rate, None)], head_kwargs)
+
+    def pitch_rows(self, waves, sample_offsets):
+        """The rows ``PitchModel.train`` collects (pitch_model.py:38-41) for a batch of raw clips -> (feat [B, 5] fp64, valid
+        [B] int32), device tensors, nothing synchronised: the front end's launches for the endpoints (its rows go to scratch;
+        no classifier input is laid out, no head is called), then the trim and the pitch features of ``_tail``."""
+        import torch
+        from .pitch import N_AUX, pitch_features_device
+        nat.require_device()
+        so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
+        if _is_device_tensor(waves):
+            clips = waves.reshape(-1).contiguous()
+        else:
+            host, _ = nat.as_wave(np.asarray(waves).reshape(-1))
+            clips = torch.from_numpy(host).to(torch.device('cuda', nat.current_device()))
+        dtype, dev = _wave_dtype_of(clips), clips.device
+        lay = self._layout(so)
+        m0 = self._m0(lay, dev)
+        stream = torch.cuda.current_stream(dev)
+        self.features.pipe.launch(clips.data_ptr(), dtype, lay, m0.data_ptr(), stream, None, defer_c0_shift=True)
+        st, B = _stream_ptr(stream), lay.n_utt
+        trim = torch.empty(max(lay.total_samples, 1), dtype=torch.float32, device=dev)
+        nat.check(nat.load().dsp_trim_preemph_batch(clips.data_ptr(), dtype, lay.vad.p_sample, lay.d_seg.ptr, lay.d_dst_off.ptr, B,
+                                                    self.coeff, trim.data_ptr(), st))
+        feat = torch.empty((B, 5), dtype=torch.float64, device=dev)
+        aux = torch.empty((B, N_AUX), dtype=torch.int32, device=dev)
+        pitch_features_device(trim.data_ptr(), lay.d_dst_off.ptr, B, lay.total_samples, self.rate, stream=st, d_feat=feat.data_ptr(),
+                              d_aux=aux.data_ptr())
+        return feat, aux[:, N_AUX - 1].contiguous()
 
     def _m0(self, lay, dev):
         """The front end's [frames_bound, C] scratch for ``_chain``; the layout's segment table becomes a torch tensor."""

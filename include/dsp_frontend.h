@@ -1091,6 +1091,62 @@ int dsp_rows_wgrad(const dsp_rows_operand* a, const dsp_rows_operand* x, int32_t
 int dsp_rows_product(const dsp_rows_operand* a0, const float* d_w0, const dsp_rows_operand* a1, const float* d_w1, int32_t n, int32_t T,
                      int32_t B, const int32_t* d_rows, float* d_y, void* stream);
 
+/* ---- fitting the pitch model: RobustScaler.fit and SVC(kernel='rbf').fit (PitchModel.train pitch_model.py:48-50; csrc/kernels_svmfit.h) ----
+ *
+ * Everything is fp64.  No atomics, no memset, no communication between workgroups, nothing allocated or synchronised: every
+ * launch goes to `stream` (capturable), every reduction is a fixed tree, the same arguments give the same bits on every call.
+ * A matrix d_X is [n, F] fp64 with row stride ld >= F doubles.  LIMITS: F in [1, 16]; n in [1, 8192] for the scaler and the
+ * variance, [2, 8192] for the solver; P in [1, 65535]; strides at most 2^32; every pointer aligned to its element size, the
+ * workspace to 16 bytes; outputs (and the workspace) must not overlap anything read nor each other.  Anything else or a NULL
+ * mandatory pointer is DSP_EINVAL with a message before any device call; under dsp_debug_host_dry_run(1) what passed every
+ * check is refused instead of launched.
+ *
+ * dsp_robust_scale_fit_batch: scaler.fit(X)                                                              pitch_model.py:48
+ *   d_valid: int32, element r * ld_valid says whether row r counts (dsp_pitch_feature_batch's d_aux[:, 8] with ld_valid = 9);
+ *   NULL = every row.  (q_lo, q_hi): the quantile pair in percent, 0 <= q_lo <= q_hi <= 100 (RobustScaler: 25, 75).
+ *   One workgroup per feature sorts the valid values in LDS and takes the percentiles as np.nanpercentile does (method
+ *   'linear': virtual index (m q + (1 - q)) - 1, the two-sided lerp a + (b - a) t below t = 0.5, b - (b - a)(1 - t) from
+ *   there, no contraction) and, with centering, np.nanmedian ((a + b) / 2 of the two middle values).
+ *   d_scale [F] = q_hi - q_lo value, 1 where that is below 10 DBL_EPSILON (sklearn's _handle_zeros_in_scale);
+ *   d_center [F]: written only with with_centering != 0 (may be NULL otherwise);
+ *   d_info [2] = {valid rows, status}: 0 = fitted; 1 = no valid row; 2 = a valid row holds a non-finite value.  With a
+ *   status other than 0 nothing but d_info is written.
+ *
+ * dsp_var_all: np.var of all entries of the rows (d_X - d_center) / d_scale (NULL: 0 / 1) that d_mask keeps (int8 [n],
+ *   non-zero = kept; NULL = every row), two passes: d_out[0] = the variance, d_out[1] = the number of entries.  It is what
+ *   SVC's gamma='scale' = 1 / (F var) needs.  One workgroup.
+ *
+ * dsp_svm_fit_batch: X = scaler.transform(X); clf.fit(X, y)                                              pitch_model.py:49-50
+ *   P independent two-class C-SVC duals with the RBF kernel over ONE matrix, one workgroup per problem:
+ *     min 1/2 a' Q a - e' a,  0 <= a <= C[p],  y' a = 0,   Q[s, t] = y_s y_t exp(-gamma[p] |x_s - x_t|^2)
+ *   on the rows x = (d_X - d_center) / d_scale (a true division, as dsp_svm_decision_batch; NULL: 0 / 1) whose label
+ *   d_Y[p, row] (int8, row stride ld_y >= n) is not 0: +1 / -1 are the classes, 0 takes the row out of problem p (label pairs,
+ *   folds and invalid rows alike).  The solver is libsvm's (working-set selection by second-order information, the
+ *   two-variable update with its four clipping cases, calculate_rho) without shrinking and without a kernel cache, in fp64,
+ *   on positions in the ascending list of the problem's rows: a masked problem is bit for bit the problem on the compacted
+ *   matrix.  Ties in both selections go to the lowest position.  It stops when m - M < tol (m = max of -y G over I_up, M =
+ *   min over I_low) or after max_iter updates (1 .. 10 000 000): the launch always ends.  d_C, d_gamma: [P] on the device.
+ *     d_coef [P, ld_coef >= n]  y a per row: exact +0 for rows outside the problem and non-support rows (SVC.dual_coef_ is
+ *                               its non-zero entries, class -1 rows first for classes_[0])
+ *     d_rho [P]                 SVC.intercept_ = -rho
+ *     d_info [P, 5]             n_iter, status, n_sv, n_bounded (a = C), n_active
+ *   status: 0 = converged; 1 = max_iter reached (the solution so far is written, as sklearn does under its
+ *   ConvergenceWarning); 2 = a row of the problem is not finite after scaling; 3 = fewer than one row in either class;
+ *   4 = C[p] or gamma[p] is not finite and positive.  Checked in the order 2, 4, 3.  With 2, 3 or 4 only d_info[p] is written.
+ *   d_work: at least dsp_svm_fit_workspace_bytes(n, F, P) bytes (the scaled matrix and the row lists).
+ */
+#define DSP_SVMFIT_MAX_ROWS 8192
+int dsp_robust_scale_fit_batch(const double* d_X, int64_t ld, int32_t n, int32_t F, const int32_t* d_valid, int64_t ld_valid,
+                               double q_lo, double q_hi, int32_t with_centering, double* d_scale, double* d_center, int32_t* d_info,
+                               void* stream);
+int dsp_var_all(const double* d_X, int64_t ld, int32_t n, int32_t F, const double* d_center, const double* d_scale,
+                const int8_t* d_mask, double* d_out, void* stream);
+int dsp_svm_fit_workspace_bytes(int32_t n, int32_t F, int32_t P, int64_t* out_bytes);
+int dsp_svm_fit_batch(const double* d_X, int64_t ld, int32_t n, int32_t F, const double* d_center, const double* d_scale,
+                      const int8_t* d_Y, int64_t ld_y, int32_t P, const double* d_C, const double* d_gamma, double tol,
+                      int32_t max_iter, double* d_coef, int64_t ld_coef, double* d_rho, int32_t* d_info, void* d_work,
+                      int64_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
