@@ -32,6 +32,8 @@ struct dsp_layout {
     int32_t* group_off2;   // tables of the int16 VAD kernel's 8-frame groups, where it uses them (vad_scan_frames8)
     int32_t* group_utt2;
     int device;
+    int capacity;          // dsp_layout_create_capacity: n_frames_total is a BOUND, the tables are rebuilt by dsp_layout_refresh
+    int dry_run;           // tables in HOST memory (dsp_debug_host_dry_run): the handle can be destroyed, nothing else
 };
 
 static thread_local std::string g_err;  // dsp_last_error
@@ -189,6 +191,91 @@ __global__ void offsets_view_kernel(const int64_t* __restrict__ src_sample, cons
     for (int b = blockIdx.x * blockDim.x + threadIdx.x; b <= n_utt; b += gridDim.x * blockDim.x) {
         sample_off[b] = (src_sample ? src_sample[b] : (int64_t)b * n) + shift;
         frame_off[b] = src_frame ? src_frame[b] : (int64_t)b * t;
+    }
+}
+
+// dsp_batch_offsets_batch: one workgroup.  Clip b (b = 1024 p + tid in pass p) reads in[b], in[b + 1]; the sanitised table is a
+// running maximum (out[b + 1] = clamp(in[b + 1], out[b], cap) = min(cap, max(0, in[1], .., in[b + 1]))), the frame offsets running
+// sums of T(out[b + 1] - out[b]); both scans run inside the waves with shuffles and across the 16 waves through LDS, and carry from
+// pass to pass.  Plain vector stores only; every word of every output is written.
+#define DSP_MAX_FRAMINGS 4
+struct BatchOffsetsArgs {
+    int32_t n_framings;
+    int32_t L[DSP_MAX_FRAMINGS], S[DSP_MAX_FRAMINGS];
+    int64_t* frame_off[DSP_MAX_FRAMINGS];
+};
+
+template <bool MAX>
+__device__ __forceinline__ int64_t block_scan_i64(int64_t v, int64_t* wtot) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int64_t t = __shfl_up(v, off, 64);
+        if (lane >= off) v = MAX ? (t > v ? t : v) : v + t;
+    }
+    if (lane == 63) wtot[w] = v;
+    __syncthreads();
+    for (int k = 0; k < w; ++k) {
+        const int64_t t = wtot[k];
+        v = MAX ? (t > v ? t : v) : v + t;
+    }
+    __syncthreads();       // wtot is free again
+    return v;
+}
+
+__global__ __launch_bounds__(1024) void batch_offsets_kernel(const int64_t* __restrict__ in, int32_t n_utt, int64_t cap,
+                                                             BatchOffsetsArgs A, int64_t* __restrict__ out,
+                                                             int32_t* __restrict__ status) {
+    __shared__ int64_t wtot[16];
+    __shared__ int64_t incl[1024];
+    __shared__ int64_t carry[1 + DSP_MAX_FRAMINGS];      // running maximum, running frame sums
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        out[0] = 0;
+        carry[0] = 0;
+        for (int f = 0; f < A.n_framings; ++f) { carry[1 + f] = 0; A.frame_off[f][0] = 0; }
+    }
+    int flags = 0;
+    __syncthreads();
+    for (int base = 0; base < n_utt; base += 1024) {
+        const int b = base + tid;
+        const bool live = b < n_utt;
+        const int64_t lo = live ? in[b] : 0, hi = live ? in[b + 1] : 0;
+        if (live) {
+            if (b == 0 && lo != 0) flags |= 1;
+            if (hi < lo) flags |= 2;
+            if (hi > cap || (b == 0 && lo > cap)) flags |= 4;
+            if (hi == lo) flags |= 8;
+        }
+        const int64_t before = carry[0];
+        int64_t m = block_scan_i64<true>(live ? hi : 0, wtot);      // max over this pass's in[base + 1 .. b + 1]
+        m = m > before ? m : before;
+        incl[tid] = m;
+        __syncthreads();
+        const int64_t mprev = tid == 0 ? before : incl[tid - 1];
+        const int64_t end = m < cap ? m : cap, start = mprev < cap ? mprev : cap;
+        if (live) out[b + 1] = end;
+        const int64_t n = end - start;
+        for (int f = 0; f < A.n_framings; ++f) {
+            const int64_t L = A.L[f], S = A.S[f];
+            const int64_t T = !live ? 0 : (n <= L ? 1 : 1 + (n - L + S - 1) / S);
+            const int64_t sum_before = carry[1 + f];
+            const int64_t sum = block_scan_i64<false>(T, wtot) + sum_before;
+            if (live) A.frame_off[f][b + 1] = sum;
+            if (tid == 1023) carry[1 + f] = sum;         // read by everyone above, before the scan's barriers
+        }
+        if (tid == 1023) carry[0] = m;
+        __syncthreads();
+    }
+    // the OR of every thread's bits: inside the waves with shuffles, across them through LDS
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) flags |= __shfl_xor(flags, off, 64);
+    if ((tid & 63) == 0) wtot[tid >> 6] = flags;
+    __syncthreads();
+    if (tid == 0) {
+        int all = 0;
+        for (int k = 0; k < 16; ++k) all |= (int)wtot[k];
+        *status = all;
     }
 }
 
@@ -488,11 +575,22 @@ int vad_features_impl(const dsp_layout* layout, const void* d_wave, int wave_dty
     BatchGeom bg = make_geom(d_sample_offsets, d_frame_offsets, n_utt, n_frames_total, uniform_samples, frame_len, frame_step);
     hipStream_t st = (hipStream_t)stream;
     const VadRoute route = vad_route(frame_len, frame_step, wave_dtype, use_sq, g_force_generic != 0);   // what dsp_debug_vad_route returns
+    // a capacity handle (dsp_layout_create_capacity) is served from its own tables alone: a recorded call must not touch the
+    // workspace pool, so what would need the shifted view or tables built on the fly is refused, never rerouted
+    const bool capacity = layout != nullptr && layout->capacity != 0;
     if (route.family != DSP_VAD_ROUTE_PER_FRAME) {
         BatchGeom fg = bg;
         const void* fw = d_wave;
-        DspWorkspace* view = fused_kernel_view(fg, fw, wave_dtype, st);
+        DspWorkspace* view = capacity ? nullptr : fused_kernel_view(fg, fw, wave_dtype, st);
         const bool ok = vad_tile_applicable(fg, fw, wave_dtype, route.fr);
+        if (capacity) {
+            if (!ok) return dsp_fail(DSP_EINVAL, "capacity layout: the wave buffer must start on a %d-byte boundary and the frame bound must fit 32-bit group counters",
+                                     wave_dtype == DSP_WAVE_I16 ? 8 : 16);
+            const int want = route.fr == 16 ? 4 : (route.fr == 8 ? 3 : 2);
+            const bool first = layout->group_off != nullptr && layout->shift == want;
+            const bool second = layout->group_off2 != nullptr && want == 3;
+            if (!first && !second) return dsp_fail(DSP_EINVAL, "capacity layout: no tables for %d-frame groups", route.fr);
+        }
         DspRaggedTables pre;
         const bool have_pre = layout != nullptr && layout->group_off != nullptr && view == nullptr;
         if (have_pre) {
@@ -1036,8 +1134,101 @@ int dsp_layout_create(const int64_t* d_frame_offsets, int32_t n_utt, int64_t n_f
 
 int dsp_layout_destroy(dsp_layout* layout) {
     if (!layout) return DSP_OK;
-    if (layout->group_off) (void)hipFree(layout->group_off);
+    dsp_table_free(layout->group_off, layout->dry_run);
     delete layout;
+    return DSP_OK;
+}
+
+int dsp_frames_bound(int64_t sample_capacity, int32_t n_utt, int32_t frame_len, int32_t frame_step, int64_t* n_frames_bound) {
+    if (!n_frames_bound) return dsp_fail(DSP_EINVAL, "dsp_frames_bound: n_frames_bound is NULL");
+    if (sample_capacity < 0 || n_utt <= 0 || frame_len <= 0 || frame_step <= 0)
+        return dsp_fail(DSP_EINVAL, "dsp_frames_bound: need sample_capacity >= 0, n_utt > 0, frame_len > 0, frame_step > 0");
+    // T(n) = 1 for n <= L, else 1 + ceil((n - L) / S).  L >= S: ceil((n - L) / S) <= ceil((n - S) / S) = ceil(n / S) - 1, so
+    // T(n) <= ceil(n / S) <= n / S + 1 (integer division).  Any L: ceil((n - L) / S) <= ceil(n / S), so T(n) <= n / S + 2.
+    // And sum_b (n_b / S) <= (sum_b n_b) / S <= sample_capacity / S.
+    const int64_t per_clip = frame_len >= frame_step ? 1 : 2;
+    if (sample_capacity / frame_step > INT64_MAX - per_clip * n_utt) return dsp_fail(DSP_EINVAL, "dsp_frames_bound: the bound overflows int64");
+    *n_frames_bound = sample_capacity / frame_step + per_clip * n_utt;
+    return DSP_OK;
+}
+
+int dsp_batch_offsets_batch(const int64_t* d_sample_offsets_in, int32_t n_utt, int64_t sample_capacity, int32_t n_framings,
+                            const int32_t* frame_len, const int32_t* frame_step, int64_t* d_sample_offsets,
+                            int64_t* const* d_frame_offsets, int32_t* d_status, void* stream) {
+    if (!d_sample_offsets_in || !d_sample_offsets || !d_status) return dsp_fail(DSP_EINVAL, "dsp_batch_offsets_batch: NULL argument");
+    if (n_utt <= 0) return dsp_fail(DSP_EINVAL, "dsp_batch_offsets_batch: n_utt %d must be >= 1", n_utt);
+    if (sample_capacity <= 0) return dsp_fail(DSP_EINVAL, "dsp_batch_offsets_batch: sample_capacity %lld must be >= 1", (long long)sample_capacity);
+    if (n_framings < 0 || n_framings > DSP_MAX_FRAMINGS)
+        return dsp_fail(DSP_EINVAL, "dsp_batch_offsets_batch: n_framings %d must be in [0, %d]", n_framings, DSP_MAX_FRAMINGS);
+    if (n_framings > 0 && (!frame_len || !frame_step || !d_frame_offsets)) return dsp_fail(DSP_EINVAL, "dsp_batch_offsets_batch: NULL argument");
+    if (d_sample_offsets == d_sample_offsets_in) return dsp_fail(DSP_EINVAL, "dsp_batch_offsets_batch: the sanitised table must not be the caller's (overlap)");
+    BatchOffsetsArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n_framings = n_framings;
+    for (int f = 0; f < n_framings; ++f) {
+        if (frame_len[f] <= 0 || frame_step[f] <= 0)
+            return dsp_fail(DSP_EINVAL, "dsp_batch_offsets_batch: framing %d: frame_len %d and frame_step %d must be > 0", f, frame_len[f], frame_step[f]);
+        if (!d_frame_offsets[f]) return dsp_fail(DSP_EINVAL, "dsp_batch_offsets_batch: framing %d: NULL frame offsets", f);
+        if (d_frame_offsets[f] == d_sample_offsets || d_frame_offsets[f] == d_sample_offsets_in)
+            return dsp_fail(DSP_EINVAL, "dsp_batch_offsets_batch: framing %d: the frame offsets overlap a sample table", f);
+        for (int g = 0; g < f; ++g)
+            if (d_frame_offsets[g] == d_frame_offsets[f]) return dsp_fail(DSP_EINVAL, "dsp_batch_offsets_batch: framings %d and %d share a table (overlap)", g, f);
+        A.L[f] = frame_len[f]; A.S[f] = frame_step[f]; A.frame_off[f] = d_frame_offsets[f];
+    }
+    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dsp_batch_offsets_batch: dry_run: launches are refused under dsp_debug_host_dry_run");
+    batch_offsets_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(d_sample_offsets_in, n_utt, sample_capacity, A, d_sample_offsets, d_status);
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+int dsp_layout_create_capacity(int32_t n_utt, int64_t n_frames_bound, int32_t frame_len, int32_t frame_step, dsp_layout** out) {
+    if (!out) return dsp_fail(DSP_EINVAL, "dsp_layout_create_capacity: out is NULL");
+    *out = nullptr;
+    if (n_utt <= 0 || n_frames_bound <= 0 || frame_len <= 0 || frame_step <= 0)
+        return dsp_fail(DSP_EINVAL, "dsp_layout_create_capacity: need n_utt > 0, n_frames_bound > 0, frame_len > 0, frame_step > 0");
+    if (n_frames_bound < n_utt) return dsp_fail(DSP_EINVAL, "dsp_layout_create_capacity: n_frames_bound %lld is below one frame per clip (%d)", (long long)n_frames_bound, n_utt);
+    const VadRoute r32 = vad_route(frame_len, frame_step, DSP_WAVE_F32, 0, false);       // as dsp_layout_create
+    const int tile = r32.family == DSP_VAD_ROUTE_PER_FRAME ? 0 : r32.fr;
+    const bool second = tile != 0 && vad_route(frame_len, frame_step, DSP_WAVE_I16, 0, false).fr == 8;
+    const int64_t bound = tile ? n_frames_bound / tile + n_utt : 0, bound2 = second ? n_frames_bound / 8 + n_utt : 0;
+    if (bound > 0x3fffffff || bound2 > 0x3fffffff) return dsp_fail(DSP_EINVAL, "dsp_layout_create_capacity: batch too large");
+    dsp_layout* l = new dsp_layout();
+    memset(l, 0, sizeof(*l));
+    l->n_utt = n_utt; l->frame_len = frame_len; l->frame_step = frame_step; l->n_frames_total = n_frames_bound;
+    l->capacity = 1;
+    l->dry_run = g_host_dry_run ? 1 : 0;
+    l->device = -1;
+    if (!l->dry_run && hipGetDevice(&l->device) != hipSuccess) { delete l; return dsp_fail(DSP_EHIP, "dsp_layout_create_capacity: hipGetDevice failed"); }
+    if (tile != 0) {
+        l->shift = tile == 16 ? 4 : 2;
+        const size_t n1 = (size_t)n_utt + 1 + (size_t)bound, n2 = second ? (size_t)n_utt + 1 + (size_t)bound2 : 0;
+        void* mem = nullptr;
+        if (l->dry_run) mem = malloc((n1 + n2) * sizeof(int32_t));
+        else if (hipMalloc(&mem, (n1 + n2) * sizeof(int32_t)) != hipSuccess) mem = nullptr;
+        if (!mem) { delete l; return dsp_fail(DSP_EHIP, "dsp_layout_create_capacity: allocation failed"); }
+        l->group_off = static_cast<int32_t*>(mem);
+        l->group_utt = l->group_off + n_utt + 1;
+        if (second) {
+            l->group_off2 = l->group_off + n1;
+            l->group_utt2 = l->group_off2 + n_utt + 1;
+        }
+    }
+    *out = l;
+    return DSP_OK;
+}
+
+int dsp_layout_refresh(dsp_layout* layout, const int64_t* d_frame_offsets, void* stream) {
+    if (!layout || !d_frame_offsets) return dsp_fail(DSP_EINVAL, "dsp_layout_refresh: NULL argument");
+    if (!layout->capacity) return dsp_fail(DSP_EINVAL, "dsp_layout_refresh: the handle is not from dsp_layout_create_capacity: its tables fit one batch shape");
+    if (g_host_dry_run || layout->dry_run) return dsp_fail(DSP_EINVAL, "dsp_layout_refresh: dry_run: launches are refused under dsp_debug_host_dry_run");
+    const int rc = check_owner_device(layout->device, false);
+    if (rc != DSP_OK) return rc;
+    if (layout->group_off != nullptr) {
+        f512_build_group_tables(d_frame_offsets, layout->n_utt, layout->shift, layout->group_off, layout->group_utt, (hipStream_t)stream);
+        if (layout->group_off2 != nullptr)
+            f512_build_group_tables(d_frame_offsets, layout->n_utt, 3, layout->group_off2, layout->group_utt2, (hipStream_t)stream);
+        HIP_TRY(hipGetLastError());
+    }
     return DSP_OK;
 }
 
@@ -1045,6 +1236,7 @@ int dsp_vad_features_layout_batch(const dsp_layout* layout, const void* d_wave, 
                                   const int64_t* d_sample_offsets, const int64_t* d_frame_offsets, int32_t use_sq,
                                   double* d_amp_sum, int32_t* d_zcr, void* stream) {
     if (!layout) return dsp_fail(DSP_EINVAL, "dsp_vad_features_layout_batch: layout is NULL");
+    if (layout->dry_run) return dsp_fail(DSP_EINVAL, "dsp_vad_features_layout_batch: dry_run: launches are refused under dsp_debug_host_dry_run");
     const int rc = check_owner_device(layout->device, false);
     if (rc != DSP_OK) return rc;
     return vad_features_impl(layout, d_wave, wave_dtype, d_sample_offsets, d_frame_offsets, layout->n_utt,

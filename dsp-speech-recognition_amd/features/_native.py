@@ -87,6 +87,10 @@ SIGNATURES = {
     'dsp_stream_synchronize': (C.c_int, [c_vp]),
     'dsp_frame_count': (C.c_int, [c_i64, c_i32, c_i32, C.POINTER(c_i64)]),
     'dsp_frame_offsets': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp]),
+    'dsp_frames_bound': (C.c_int, [c_i64, c_i32, c_i32, c_i32, C.POINTER(c_i64)]),
+    'dsp_batch_offsets_batch': (C.c_int, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'dsp_layout_create_capacity': (C.c_int, [c_i32, c_i64, c_i32, c_i32, C.POINTER(c_vp)]),
+    'dsp_layout_refresh': (C.c_int, [c_vp, c_vp, c_vp]),
     'dsp_plan_create': (C.c_int, [C.POINTER(PlanDesc), C.POINTER(c_vp)]),
     'dsp_plan_create_ex': (C.c_int, [C.POINTER(PlanDesc), C.c_uint32, C.POINTER(c_vp)]),
     'dsp_plan_transform': (C.c_int, [c_vp, C.POINTER(c_i32), C.POINTER(c_i32)]),
@@ -319,6 +323,13 @@ def frame_offsets(sample_offsets, L, S):
     fo = np.empty_like(so)
     check(load().dsp_frame_offsets(so.ctypes.data, len(so) - 1, int(L), int(S), fo.ctypes.data))
     return fo
+
+
+def frames_bound(sample_capacity, n_utt, L, S):
+    """dsp_frames_bound: an upper bound on the frame count of any ``n_utt`` clips whose lengths sum to ``sample_capacity``."""
+    out = c_i64(0)
+    check_value(load().dsp_frames_bound(int(sample_capacity), int(n_utt), int(L), int(S), C.byref(out)), 'invalid argument')
+    return out.value
 
 
 class DeviceBuffer:

@@ -58,6 +58,9 @@ class _CapturedGraph:
 
     def __init__(self, graph, waves, result, hold):
         self.graph, self.waves, self.result, self.hold = graph, waves, result, hold
+        # a capture with ``capacity=``: the int64 [B + 1] device tensor to write the next batch's offsets into before a
+        # replay, and the int32 [1] status word of the offsets kernel (0: a valid table); None otherwise
+        self.sample_offsets = self.status = None
 
     def replay(self):
         self.graph.replay()

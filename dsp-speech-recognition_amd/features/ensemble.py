@@ -348,8 +348,12 @@ class EnsembleBatch(_EnsembleTail):
         self._layouts[key] = lay
         return lay
 
-    def run(self, waves, sample_offsets, sync_free=False, **head_kwargs):
-        """``waves``: concatenated clips, a 1-D host array (int16 or float) or device tensor (int16 / float32);
+    def run(self, waves, sample_offsets, sync_free=False, capacity=None, **head_kwargs):
+        """``capacity=N``: the sync-free chain on a capacity layout cached per (B, N) -- the launches ``capture(...,
+        capacity=N)`` records, queued eagerly: ``waves`` is a contiguous device tensor of exactly N samples (ValueError
+        otherwise), ``sample_offsets`` ([B + 1], host array or device tensor) any B lengths >= 1 that sum to at most N; no
+        layout is built, uploaded or synchronised per batch shape.  ``status`` (int32 [1]) is added to the namespace.
+        ``waves``: concatenated clips, a 1-D host array (int16 or float) or device tensor (int16 / float32);
         ``sample_offsets`` [B + 1].  Returns a namespace of device tensors: pred int32 [B] (the ensemble's labels), prob fp32
         [B, C], used int32 [B], decision fp64 [B] (see ``ensemble_decide``), logits, feat fp64 [B, 5] and valid int32 [B]
         (the pitch features), endpoints int64 [B, 2] (host array, samples), len0 [B] (host array).  This call downloads len0
@@ -359,6 +363,16 @@ class EnsembleBatch(_EnsembleTail):
         the lengths the head had to clamp."""
         import torch
         nat.require_device()
+        if capacity is not None:
+            from .pipeline import check_capacity_wave
+            check_capacity_wave(waves, capacity)
+            _wave_dtype_of(waves)
+            B = int(sample_offsets.shape[0] if torch.is_tensor(sample_offsets) else len(sample_offsets)) - 1
+            lay = self.features.pipe._capacity_layout(B, capacity, 0)
+            lay.write_offsets(sample_offsets)
+            ns = self._chain(waves, lay, self._m0(lay, waves.device), None, head_kwargs)
+            ns.status = lay.status
+            return ns
         so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
         # ONE contiguous device copy of the clips, held until the call returns: endpointing, the feature kernels and the
         # pre-emphasised trim all read this buffer
@@ -421,24 +435,46 @@ class EnsembleBatch(_EnsembleTail):
                     torch.cuda.current_stream(dev))
         return self._tail(inp, len0, None, [(lay, clips, self.rate, None)], head_kwargs, None if arena is None else [arena])
 
-    def capture(self, waves, sample_offsets, **head_kwargs):
+    def capture(self, waves, sample_offsets, capacity=None, **head_kwargs):
         """ONE HIP graph of the whole path over device-resident ``waves`` (a contiguous tensor, int16 / float32):
-        ``g = eb.capture(waves, so, dropout=False)``; write new clips of the same lengths into ``waves`` and call
+        ``g = eb.capture(waves, so, dropout=False)``; write new clips into ``waves`` -- of the same lengths, unless the graph
+        was recorded with ``capacity=`` -- and call
         ``g.replay()`` -> the namespace of ``run(sync_free=True)``, every field a device tensor, valid after the current
         stream's work.  One eager call runs first (it builds the native handles and the layout's index tables and fills the
         graph's own arena).  The graph object owns every buffer its kernels touch -- the layout, the front end's scratch,
         the pitch chain's buffers and FIR taps -- so no later call of the library can free or overwrite what a replay reads.
         The graph reads ``waves`` at its address: a non-contiguous view raises ValueError; the head must accept
-        ``device_len=True``."""
+        ``device_len=True``.
+
+        ``capacity=N``: ``waves`` is a contiguous 1-D tensor of exactly N samples (ValueError otherwise) and ``so`` the offsets
+        of the batch it holds now.  The graph then serves ANY B = len(so) - 1 clips whose lengths are >= 1 and sum to at most
+        N: write the clips into ``waves`` and their [B + 1] offsets into ``g.sample_offsets`` (int64 device tensor), replay;
+        samples behind ``offsets[B]`` are ignored, ``g.status`` (int32 [1]) is 0 for a valid table.  The batch layout -- the
+        sanitised offsets, the frame offsets, the VAD kernel's index tables -- is rebuilt by two launches at the head of the
+        recorded sequence (``CapacityLayout``); every grid and buffer behind is sized by the capacity."""
+        box = []
+
         def prepare():
             nat.require_device()
-            clips = waves.reshape(-1)                          # a view: the same memory
-            _wave_dtype_of(clips)                              # TypeError for anything but int16 / float32
             so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
-            lay = self.features.pipe.prepare(so, 0)            # the graph's own: nothing else launches on its tables
+            if capacity is None:
+                clips = waves.reshape(-1)                      # a view: the same memory
+                _wave_dtype_of(clips)                          # TypeError for anything but int16 / float32
+                lay = self.features.pipe.prepare(so, 0)        # the graph's own: nothing else launches on its tables
+            else:
+                from .pipeline import check_capacity_wave
+                check_capacity_wave(waves, capacity)
+                clips = waves
+                _wave_dtype_of(clips)
+                lay = self.features.pipe.prepare_capacity(len(so) - 1, capacity, 0)
+                lay.write_offsets(so)
+                box.append(lay)
             m0, arena = self._m0(lay, waves.device), {}
             return (lambda: self._chain(clips, lay, m0, arena, head_kwargs)), [lay, m0, arena, clips, list(self.rules)]
-        return _capture(waves, prepare)
+        g = _capture(waves, prepare)
+        if box:
+            g.sample_offsets, g.status = box[0].sample_offsets_in, box[0].status
+        return g
 
 
 class MixedRateEnsembleBatch(_EnsembleTail):
@@ -452,10 +488,13 @@ class MixedRateEnsembleBatch(_EnsembleTail):
         self.head, self.rules, self.coeff = head, list(rules), float(coeff)
         self.features = MixedRateFeatureBatch(frame=frame, step=step)
 
-    def run(self, waves, sample_offsets=None, rates=None, sync_free=False, **head_kwargs):
-        """``waves`` / ``sample_offsets`` / ``rates`` as MixedRateFeatureBatch.run.  Returns the namespace of EnsembleBatch.run,
+    def run(self, waves, sample_offsets=None, rates=None, sync_free=False, capacity=None, **head_kwargs):
+        """``capacity=``: NotImplementedError (``MixedRateFeatureBatch.capture`` says why).
+        ``waves`` / ``sample_offsets`` / ``rates`` as MixedRateFeatureBatch.run.  Returns the namespace of EnsembleBatch.run,
         every row in batch order; ``sync_free=True`` as there (device input: no synchronisation once the plan of the batch
         shape exists)."""
+        from .model_glue import _no_mixed_capacity
+        _no_mixed_capacity(capacity)
         mr = self.features
         if sync_free:
             import torch
@@ -480,14 +519,17 @@ class MixedRateEnsembleBatch(_EnsembleTail):
             _segments_tensor(g.lay, dev)
         return self._after(self.features._launch(waves, so, rates, plan=plan), None, head_kwargs, arenas)
 
-    def capture(self, waves, sample_offsets, rates, **head_kwargs):
+    def capture(self, waves, sample_offsets, rates, capacity=None, **head_kwargs):
         """``EnsembleBatch.capture`` for a mixed-rate batch: ONE HIP graph of the front end's sub-pipelines (queued one after
         the other: a chain, no forked branches), the head with ``device_len=True``, and per rate group the trim and the pitch
         features, then the gate.  ``waves``: a contiguous 1-D device tensor (a non-contiguous one raises ValueError);
         ``replay()`` -> the namespace of ``run(sync_free=True)``, rows in batch order.  The graph object owns the plan, every
         group's layout and pitch arena, and the temporaries of the launches.  (The optional ``use_pitch`` / ``use_timefeat``
-        streams are not part of the capture.)"""
-        from .model_glue import _MixedPlan
+        streams are not part of the capture.)
+        ``capacity=`` raises NotImplementedError: the grouping by rate is host logic over the rates, so a mixed-rate graph
+        stays bound to its lengths and rates (``MixedRateFeatureBatch.capture``)."""
+        from .model_glue import _MixedPlan, _no_mixed_capacity
+        _no_mixed_capacity(capacity)
 
         def prepare():
             _, so, r = self.features._inputs(waves, sample_offsets, rates)

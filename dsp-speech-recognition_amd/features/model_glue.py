@@ -150,8 +150,11 @@ class ModelFeatureBatch:
         s_r, utterance by utterance)."""
         return MixedRateFeatureBatch.draw_jitter([self.rate] * n_utt, rng)
 
-    def run(self, waves, sample_offsets=None, jitter=None, layout=None, use_pitch=False, use_timefeat=False):
+    def run(self, waves, sample_offsets=None, jitter=None, layout=None, use_pitch=False, use_timefeat=False, capacity=None):
         """-> (inp [max_len, B, 39 (+2) (+2)] torch tensor on the library's device, len0 [B], endpoints [B, 2]).
+        ``capacity=N``: the eager, sync-free form on a capacity layout (``_run_capacity``): ``waves`` is a contiguous device
+        tensor of exactly N samples, ``sample_offsets`` ([B + 1], host array or device tensor) any B lengths >= 1 that sum to
+        at most N, and all three results stay on the device (len0 int32, endpoints int64).
         ``jitter``: int [B, 2] endpoint offsets (see draw_jitter) for the training path (augment=True);
         None = test path.  ``use_timefeat`` / ``use_pitch`` append the optional streams of model.py:125-128
         in the reference's order (pitch, then amplitude), both computed on the device from one trimmed, scaled
@@ -160,6 +163,10 @@ class ModelFeatureBatch:
         torch's current stream (the stream of every launch here), and that copy is held until the call's last kernel has
         finished.  torch only owns the result tensor."""
         import torch
+        if capacity is not None:
+            if layout is not None or use_pitch or use_timefeat:
+                raise NotImplementedError('run(capacity=) serves the default call: no layout=, no optional streams')
+            return self._run_capacity(waves, sample_offsets, jitter, capacity)
         dev = waves.device if _is_device_tensor(waves) else torch.device('cuda', nat.current_device())
         stream = torch.cuda.current_stream(dev)
         if layout is None:       # this call consumes the layout's tables before it returns: a cached one is safe
@@ -180,6 +187,34 @@ class ModelFeatureBatch:
         nat.check(nat.load().dsp_stream_synchronize(st))     # d_m0, its wave buffer and `hold` go on return: their consumers have finished
         del hold
         return inp, len0.cpu().numpy(), seg
+
+    def _run_capacity(self, waves, sample_offsets, jitter, capacity):
+        """``run(..., capacity=N)``: the launches ``capture(..., capacity=N)`` records, queued eagerly on torch's current
+        stream on a capacity layout cached per (B, N) -- no layout build, upload or synchronisation per batch shape.  The
+        padded grids make this a route of its own beside the exact-shape ``run``.  -> (inp, len0 int32 [B], endpoints int64
+        [B, 2]), device tensors, valid after the stream's work; ``self.capacity_status`` is the layout's status word."""
+        import torch
+        from .pipeline import check_capacity_wave
+        nat.require_device()
+        check_capacity_wave(waves, capacity)
+        dev, dtype = waves.device, _wave_dtype_of(waves)
+        B = int(sample_offsets.shape[0] if torch.is_tensor(sample_offsets) else len(sample_offsets)) - 1
+        lay = self.pipe._capacity_layout(B, capacity, 0)
+        lay.write_offsets(sample_offsets)
+        self.capacity_status = lay.status
+        C = self.pipe.features.C
+        m0 = torch.empty((max(lay.frames_bound, 1), C), dtype=torch.float32, device=dev)
+        inp = torch.empty((self.max_len, B, 3 * C), dtype=torch.float32, device=dev)
+        len0 = torch.empty(B, dtype=torch.int32, device=dev)
+        d_jit = None
+        if jitter is not None:
+            j = jitter if torch.is_tensor(jitter) else torch.from_numpy(np.ascontiguousarray(jitter, dtype=np.int64))
+            d_jit = j.to(device=dev, dtype=torch.int64).reshape(B, 2).contiguous()
+        from .ensemble import _segments_tensor
+        seg = _segments_tensor(lay, dev)          # the segment table as a torch tensor, swapped in BEFORE the launches write it
+        self.enqueue(waves.data_ptr(), dtype, lay, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(), torch.cuda.current_stream(dev),
+                     d_jitter=None if d_jit is None else d_jit.data_ptr())
+        return inp, len0, seg.clone()
 
     def enqueue(self, d_wave, wave_dtype, lay, d_m0, d_inp, d_len0, stream, d_jitter=None):
         """The default call (no optional streams) as launches only -- raw device pointers, nothing allocated,
@@ -222,28 +257,67 @@ class ModelFeatureBatch:
             hold += self._timefeat_streams(lay, st, dev, (d_inp, d_dst_col, n_cols, row_width, col))
         return hold
 
-    def capture(self, waves, layout):
+    def capture(self, waves, layout, capacity=None):
         """A HIP graph of ``enqueue`` over device-resident ``waves`` (torch tensor, int16 / float32) and a prepared layout:
-        ``g = mfb.capture(waves, lay)``; put new clips of the same lengths into ``waves`` and call ``g.replay()`` ->
+        ``g = mfb.capture(waves, lay)``; put new clips into ``waves`` -- of the same lengths, unless the layout is a capacity
+        layout -- and call ``g.replay()`` ->
         (inp [max_len, B, 39], len0 [B] int32), both on the device, valid after the current stream's work (no host
         synchronisation).  One eager call runs first (it builds the layout's long-lived index tables).
         The graph reads ``waves`` at its address, sample after sample: a non-contiguous view cannot be served (a copy
-        would not see what the caller writes later) and raises ValueError; a contiguous view at any offset is fine."""
+        would not see what the caller writes later) and raises ValueError; a contiguous view at any offset is fine.
 
-        def prepare():
+        ``capacity=N``: ``g = mfb.capture(waves, so, capacity=N)`` with ``waves`` a contiguous tensor of exactly N samples
+        (ValueError otherwise) and ``so`` the [B + 1] sample offsets of the batch it holds now (or a layout from
+        ``pipe.prepare_capacity(B, N, 0)``).  The graph then serves ANY B clips whose lengths are >= 1 and sum to at most N:
+        write the clips into ``waves`` and their offsets into ``g.sample_offsets`` (int64 [B + 1] device tensor), replay;
+        samples behind ``offsets[B]`` are ignored and ``g.status`` (int32 [1]) is 0 for a valid table (``CapacityLayout``).
+        The result also carries the endpoints: (inp, len0, endpoints int64 [B, 2])."""
+        if capacity is None and getattr(layout, 'capacity', None) is None:
+            def prepare():
+                import torch
+                dev, dtype = waves.device, _wave_dtype_of(waves)
+                C, B = self.pipe.features.C, layout.n_utt
+                m0 = torch.empty((max(layout.frames_bound, 1), C), dtype=torch.float32, device=dev)
+                inp = torch.empty((self.max_len, B, 3 * C), dtype=torch.float32, device=dev)
+                len0 = torch.empty(B, dtype=torch.int32, device=dev)
+
+                def queue():
+                    self.enqueue(waves.data_ptr(), dtype, layout, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(),
+                                 torch.cuda.current_stream(dev))
+                    return inp, len0
+                return queue, [m0, layout]
+            return _capture(waves, prepare)
+
+        from .pipeline import CapacityLayout, check_capacity_wave
+        lay_box = []
+
+        def prepare_capacity():
             import torch
+            from .ensemble import _segments_tensor
+            lay = layout
+            if not isinstance(lay, CapacityLayout):
+                so = np.ascontiguousarray(layout, dtype=np.int64).reshape(-1)
+                lay = self.pipe.prepare_capacity(len(so) - 1, capacity, 0)      # the graph's own
+                lay.write_offsets(so)
+            elif capacity is not None and int(capacity) != lay.capacity:
+                raise ValueError(f'capacity = {capacity}, the layout was prepared for {lay.capacity}')
+            check_capacity_wave(waves, lay.capacity)
+            lay_box.append(lay)
             dev, dtype = waves.device, _wave_dtype_of(waves)
-            C, B = self.pipe.features.C, layout.n_utt
-            m0 = torch.empty((max(layout.frames_bound, 1), C), dtype=torch.float32, device=dev)
+            C, B = self.pipe.features.C, lay.n_utt
+            m0 = torch.empty((max(lay.frames_bound, 1), C), dtype=torch.float32, device=dev)
             inp = torch.empty((self.max_len, B, 3 * C), dtype=torch.float32, device=dev)
             len0 = torch.empty(B, dtype=torch.int32, device=dev)
+            seg = _segments_tensor(lay, dev)
 
             def queue():
-                self.enqueue(waves.data_ptr(), dtype, layout, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(),
+                self.enqueue(waves.data_ptr(), dtype, lay, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(),
                              torch.cuda.current_stream(dev))
-                return inp, len0
-            return queue, [m0, layout]
-        return _capture(waves, prepare)
+                return inp, len0, seg
+            return queue, [m0, lay]
+        g = _capture(waves, prepare_capacity)
+        g.sample_offsets, g.status = lay_box[0].sample_offsets_in, lay_box[0].status
+        return g
 
     def _timefeat_streams(self, lay, st, dev, place):
         """Z-scored frame amplitude of the trimmed, scaled clips and its first difference (model.py:97-101), on the
@@ -318,6 +392,13 @@ def _as_rates(rates):
     if np.any(r <= 0):
         raise ValueError(f'sample rates must be positive, got {r[r <= 0].tolist()}')
     return r.astype(np.int64)
+
+
+def _no_mixed_capacity(capacity):
+    if capacity is not None:
+        raise NotImplementedError('capacity= is not served for mixed-rate batches: the grouping by rate is host logic over the rates '
+                                  '(group_by_rate), so the layout of a mixed batch cannot be rebuilt on the device; use the '
+                                  'single-rate classes')
 
 
 class _MixedPlan:
@@ -490,22 +571,28 @@ class MixedRateFeatureBatch:
         ctx.hold = []
         return len0, endpoints
 
-    def run(self, waves, sample_offsets=None, rates=None, jitter=None, use_pitch=False, use_timefeat=False):
-        """``waves``: concatenated clips as a host 1-D array or a 1-D device tensor (int16 / float32, any view) with
+    def run(self, waves, sample_offsets=None, rates=None, jitter=None, use_pitch=False, use_timefeat=False, capacity=None):
+        """``capacity=``: NotImplementedError -- see ``capture``.
+        ``waves``: concatenated clips as a host 1-D array or a 1-D device tensor (int16 / float32, any view) with
         ``sample_offsets`` [B + 1], or a list of B host arrays; ``rates``: [B] sample rates.  -> (inp [max_len, B, 39 (+2)
         (+2)] on the library's device, len0 [B], endpoints [B, 2]), all in batch order; ``jitter`` / ``use_pitch`` /
         ``use_timefeat`` as ModelFeatureBatch.run, each clip at its own rate's framings and decimation (model.py:90-101).
         A batch with a single rate is ModelFeatureBatch(rate).run."""
+        _no_mixed_capacity(capacity)
         ctx = self._launch(waves, sample_offsets, rates, jitter, use_pitch, use_timefeat)
         len0, endpoints = self._finish(ctx)
         return ctx.inp, len0, endpoints
 
-    def capture(self, waves, sample_offsets, rates):
+    def capture(self, waves, sample_offsets, rates, capacity=None):
         """A HIP graph of the default call over device-resident ``waves`` (contiguous 1-D tensor, int16 / float32):
         ``g = mr.capture(waves, so, rates)``; write new clips of the same lengths and rates into ``waves`` and call
         ``g.replay()`` -> (inp [max_len, B, 39], len0 [B] int32), on the device, valid after the current stream's work (no
         host synchronisation).  The sub-pipelines are queued one after the other on the capture stream: the graph is one
-        chain, no forked branches.  One eager call runs first (it builds the layouts' long-lived index tables)."""
+        chain, no forked branches.  One eager call runs first (it builds the layouts' long-lived index tables).
+        ``capacity=`` raises NotImplementedError: which clips form a rate group, each group's offsets and its share of the
+        samples are host logic over the rates (``group_by_rate``), so a mixed-rate graph stays bound to its lengths AND rates;
+        the single-rate classes take ``capacity=``."""
+        _no_mixed_capacity(capacity)
 
         def prepare():
             _, so, r = self._inputs(waves, sample_offsets, rates)

@@ -120,6 +120,124 @@ class PipelineLayout:
             self._d_trim = nat.DeviceBuffer(max(self.total_samples, 1) * 4)
         return self._d_trim
 
+    capacity = None                # a CapacityLayout's sample capacity; None: the offsets were baked in on the host
+
+
+class _CapacityVad:
+    """What ``EndpointPlan.run_raw`` needs of a batch layout (the surface of ``_BatchLayout``), with the offsets living only on
+    the device: ``d_sample`` is the SANITISED table dsp_batch_offsets_batch writes, ``d_frame`` the frame offsets of the
+    (L, S) framing it writes beside it, ``total_frames`` / ``total_samples`` are bounds, and the dsp_layout handle is a
+    capacity handle whose tables ``CapacityLayout.refresh`` rebuilds."""
+
+    uniform_samples = 0
+
+    def __init__(self, L, S, n_utt, sample_capacity):
+        import ctypes as C
+        self.n_utt, self.L, self.S = int(n_utt), int(L), int(S)
+        self.total_samples = int(sample_capacity)
+        self.total_frames = nat.frames_bound(sample_capacity, n_utt, L, S)
+        self.d_sample = nat.DeviceBuffer((self.n_utt + 1) * 8)
+        self.d_frame = nat.DeviceBuffer((self.n_utt + 1) * 8)
+        out = C.c_void_p(0)
+        nat.check(nat.load().dsp_layout_create_capacity(self.n_utt, self.total_frames, self.L, self.S, C.byref(out)))
+        from .batch import _LayoutHandle
+        self._handle = _LayoutHandle(out.value)
+
+    @property
+    def p_sample(self):
+        return self.d_sample.ptr
+
+    @property
+    def p_frame(self):
+        return self.d_frame.ptr
+
+    def vad_handle(self, L, S):
+        assert (int(L), int(S)) == (self.L, self.S), 'a capacity layout serves the framing it was prepared for'
+        return self._handle.handle
+
+
+class CapacityLayout(PipelineLayout):
+    """A ``PipelineLayout`` for ANY batch of ``n_utt`` clips whose lengths sum to at most ``sample_capacity``
+    (``VadMfccPipeline.prepare_capacity``).  Nothing about the clips' lengths is baked in on the host:
+
+    * ``sample_offsets_in``: torch int64 [n_utt + 1] on the device -- the caller writes the batch's offsets here (0, then the
+      running sum of the lengths) before a launch, or before a replay of a graph recorded on this layout;
+    * ``launch`` begins with dsp_batch_offsets_batch (the sanitised copy ``vad.d_sample``, which is all that later kernels
+      read, the frame offsets of the VAD framing ``vad.d_frame`` and of the feature framing ``d_frame_untrimmed``, and
+      ``status``) and dsp_layout_refresh (the VAD kernel's index tables), then runs the usual sequence;
+    * ``vad.total_frames``, ``frames_bound`` and ``total_samples`` are capacities (dsp_frames_bound): grids, tables and
+      buffers are sized by them, the kernels stop at the true counts in the device tables;
+    * ``status``: torch int32 [1], overwritten by every launch: 0, or bit 0 offsets[0] != 0, bit 1 a decreasing pair, bit 2 an
+      offset above the capacity, bit 3 a clip of 0 samples."""
+
+    def __init__(self, pipe, n_utt, sample_capacity, delta_n, device=None):
+        import ctypes as C
+        import torch
+        n_utt, cap = int(n_utt), int(sample_capacity)
+        if n_utt < 1 or cap < 1:
+            raise ValueError(f'prepare_capacity: need n_utt >= 1 and sample_capacity >= 1, got {n_utt}, {cap}')
+        dev = torch.device('cuda', nat.current_device()) if device is None else device
+        ep, fp = pipe.endpoint, pipe.features
+        self.capacity = cap
+        self.sample_offsets = None                   # no host copy: the truth is sample_offsets_in
+        self.n_utt = B = n_utt
+        self.sample_offsets_in = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.vad = _CapacityVad(ep.L, ep.S, B, cap)
+        self.frames_bound = nat.frames_bound(cap, B, fp.L, fp.S)        # trimming never lengthens a clip
+        self.total_samples = cap
+        self.delta_n = int(delta_n)
+        self.D = fp.width(delta_n)
+        nf = self.vad.total_frames
+        self.d_amp = nat.DeviceBuffer(nf * 8)
+        self.d_zcr = nat.DeviceBuffer(nf * 4)
+        self.d_ep = nat.DeviceBuffer(B * 8)
+        self.d_seg = nat.DeviceBuffer(B * 16)
+        self.d_dst_off = nat.DeviceBuffer((B + 1) * 8)
+        self.d_frame_off = nat.DeviceBuffer((B + 1) * 8)
+        self.d_frame_untrimmed = nat.DeviceBuffer((B + 1) * 8)
+        self._d_trim = None
+        self.features = _DeviceLayout(B, self.d_dst_off, self.d_frame_off, self.frames_bound)
+        self.d_work = None
+        self.c0_shift_pending = False
+        if delta_n >= 0:
+            nbytes = C.c_size_t(0)
+            nat.check(nat.load().dsp_segments_workspace_bytes(fp.plan.handle, B, max(self.frames_bound, 1), C.byref(nbytes)))
+            self.d_work = nat.DeviceBuffer(int(nbytes.value))
+        # host arguments of dsp_batch_offsets_batch, kept with the layout
+        self._frame_len = (C.c_int32 * 2)(ep.L, fp.L)
+        self._frame_step = (C.c_int32 * 2)(ep.S, fp.S)
+        self._frame_tables = (C.c_void_p * 2)(self.vad.d_frame.ptr, self.d_frame_untrimmed.ptr)
+
+    def refresh(self, st):
+        """The two launches in front of every sequence on this layout, on the raw stream ``st``: offsets, then the VAD
+        kernel's index tables.  No allocation, no synchronisation, capturable."""
+        lib = nat.load()
+        nat.check(lib.dsp_batch_offsets_batch(self.sample_offsets_in.data_ptr(), self.n_utt, self.capacity, 2, self._frame_len,
+                                              self._frame_step, self.vad.d_sample.ptr, self._frame_tables,
+                                              self.status.data_ptr(), st))
+        nat.check(lib.dsp_layout_refresh(self.vad.vad_handle(self.vad.L, self.vad.S), self.vad.d_frame.ptr, st))
+
+    def write_offsets(self, sample_offsets):
+        """Copy a batch's offsets ([n_utt + 1]: host array or device tensor) into ``sample_offsets_in`` on torch's current
+        stream; ValueError for a table of another length (the values are the device's to check: ``status``)."""
+        import torch
+        so = sample_offsets if torch.is_tensor(sample_offsets) else torch.from_numpy(np.ascontiguousarray(sample_offsets, dtype=np.int64))
+        if tuple(so.shape) != (self.n_utt + 1,):
+            raise ValueError(f'sample_offsets must be [n_utt + 1] = [{self.n_utt + 1}], got {tuple(so.shape)}')
+        self.sample_offsets_in.copy_(so)
+
+
+def check_capacity_wave(waves, capacity):
+    """The wave buffer of a capacity layout: a contiguous 1-D device tensor of exactly ``capacity`` samples (the sanitised
+    offsets keep every kernel inside that many samples, so that many must be there)."""
+    if not _is_device_tensor(waves):
+        raise TypeError('capacity= needs the clips in a device tensor')
+    if waves.dim() != 1 or waves.numel() != int(capacity):
+        raise ValueError(f'capacity = {int(capacity)} needs a 1-D wave tensor of exactly that many samples, got shape {tuple(waves.shape)}')
+    if not waves.is_contiguous():
+        raise ValueError('capacity= needs a contiguous waves tensor')
+
 
 class VadMfccPipeline:
     def __init__(self, rate=16000, frame=0.03, step=0.01, unit_variance=False, **mfcc_kwargs):
@@ -136,6 +254,28 @@ class VadMfccPipeline:
     def prepare(self, sample_offsets, delta_n=2):
         nat.require_device()
         return PipelineLayout(self, sample_offsets, delta_n)
+
+    def prepare_capacity(self, n_utt, sample_capacity, delta_n=2):
+        """A layout for ANY ``n_utt`` clips whose lengths are >= 1 and sum to at most ``sample_capacity`` (``CapacityLayout``):
+        write a batch's offsets into ``layout.sample_offsets_in`` and launch -- or replay a graph recorded on it.  The wave
+        buffer is a contiguous device tensor of exactly ``sample_capacity`` samples; what lies behind ``offsets[n_utt]`` is
+        ignored."""
+        nat.require_device()
+        return CapacityLayout(self, n_utt, sample_capacity, delta_n)
+
+    def _capacity_layout(self, n_utt, sample_capacity, delta_n):
+        """``run(..., capacity=)`` of the batch classes: one capacity layout per (device, n_utt, capacity, delta_n) and thread."""
+        cache = getattr(self._tls, 'capacity_layouts', None)
+        if cache is None:
+            cache = self._tls.capacity_layouts = {}
+        key = (nat.current_device(), int(n_utt), int(sample_capacity), int(delta_n))
+        lay = cache.pop(key, None)
+        if lay is None:
+            lay = self.prepare_capacity(n_utt, sample_capacity, delta_n)
+            while len(cache) >= 4:
+                cache.pop(next(iter(cache)))
+        cache[key] = lay
+        return lay
 
     def _cached_layout(self, sample_offsets, delta_n):
         """run(download=True) without an explicit layout: batches of a shape this thread has seen recently reuse
@@ -165,6 +305,8 @@ class VadMfccPipeline:
         lib = nat.load()
         st = _stream_ptr(stream)
         ep, fp = self.endpoint, self.features
+        if lay.capacity is not None:      # the batch layout itself is device work: sanitised offsets, frame offsets, index tables
+            lay.refresh(st)
         ep.run_raw(d_wave, wave_dtype, lay.vad, lay.d_amp.ptr, lay.d_zcr.ptr, lay.d_ep.ptr, st)
         lay.c0_shift_pending = False
         in_place = lay.d_work is not None and not self.copy_trimmed and \

@@ -45,6 +45,8 @@ class _CapturedStep:
 
     def __init__(self, graph, result, params, grads, hold, optimizer=None):
         self.graph, self.result, self.params, self.grads, self.hold, self.optimizer = graph, result, params, grads, hold, optimizer
+        # a capture with ``capacity=``: where the next batch's offsets go before a replay, and the offsets kernel's status word
+        self.sample_offsets = self.status = None
 
     def replay(self):
         self.graph.replay()
@@ -129,8 +131,12 @@ class TrainBatch:
         return types.SimpleNamespace(loss=loss, logits=logits, inp=inp, len0=len0, n_clamped=n_clamped,
                                      _hold=[clips, lay, m0, labels, d_jit])
 
-    def run(self, waves, sample_offsets, labels, jitter=None, **head_kwargs):
-        """``waves``: concatenated clips, a 1-D host array (int16 or float) or device tensor (int16 / float32);
+    def run(self, waves, sample_offsets, labels, jitter=None, capacity=None, **head_kwargs):
+        """``capacity=N``: the same chain on a capacity layout cached per (B, N) -- the launches ``capture(..., capacity=N)``
+        records: ``waves`` is a contiguous device tensor of exactly N samples (ValueError otherwise), ``sample_offsets``
+        ([B + 1], host array or device tensor) any B lengths >= 1 that sum to at most N; no layout is built or uploaded per
+        batch shape.  ``status`` (int32 [1]) is added to the namespace.
+        ``waves``: concatenated clips, a 1-D host array (int16 or float) or device tensor (int16 / float32);
         ``sample_offsets`` [B + 1]; ``labels`` [B] class indices; ``jitter``: int [B, 2] endpoint offsets (``draw_jitter``;
         model.py:144 trains with augment=True) or None.  Device tensors are read where they lie; host arrays are uploaded
         first.  -> a namespace (loss: the scalar ``F.cross_entropy(logits, labels)``, attached to the autograd graph; logits
@@ -139,6 +145,17 @@ class TrainBatch:
         its optimiser -- the head's native handles survive the step (they are repacked in place by the next call)."""
         import torch
         nat.require_device()
+        if capacity is not None:
+            from .pipeline import check_capacity_wave
+            check_capacity_wave(waves, capacity)
+            _wave_dtype_of(waves)
+            dev = waves.device
+            B = int(sample_offsets.shape[0] if torch.is_tensor(sample_offsets) else len(sample_offsets)) - 1
+            lay = self.features.pipe._capacity_layout(B, capacity, 0)
+            lay.write_offsets(sample_offsets)
+            ns = self._chain(waves, lay, self._m0(lay, dev), self._labels(labels, B, dev), self._jitter(jitter, B, dev), head_kwargs)
+            ns.status = lay.status
+            return ns
         so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
         if _is_device_tensor(waves):
             clips = waves.reshape(-1).contiguous()
@@ -150,14 +167,23 @@ class TrainBatch:
         lay = self._layout(so)
         return self._chain(clips, lay, self._m0(lay, dev), self._labels(labels, B, dev), self._jitter(jitter, B, dev), head_kwargs)
 
-    def capture(self, waves, sample_offsets, labels, jitter=None, optimizer=None, **head_kwargs):
+    def capture(self, waves, sample_offsets, labels, jitter=None, optimizer=None, capacity=None, **head_kwargs):
         """ONE HIP graph of a whole step; without ``optimizer`` all of it but the optimiser: ``g = tb.capture(waves, so, labels, jitter, dropout=False)``;
         ``g.replay()`` does, in order, (1) a refresh of every native handle of the head -- the repack of whatever the
         optimiser wrote since the last replay --, (2) the front end, (3) the forward, (4) the loss and (5) the backward into
         ``.grad`` tensors the graph owns (``g.grads``), which every replay overwrites.  It returns the namespace of ``run``.
         ``waves`` (contiguous device tensor, int16 / float32), ``labels`` (int64 [B] device tensor) and ``jitter`` (int64
-        [B, 2] device tensor, or None) are read at their addresses on every replay: write the next batch -- clips of the same
-        lengths -- into them.  With ``optimizer=None`` the optimiser step stays the caller's, eager, after ``replay()``.
+        [B, 2] device tensor, or None) are read at their addresses on every replay: write the next batch into them -- clips of
+        the same lengths, unless the step was recorded with ``capacity=``.  With ``optimizer=None`` the optimiser step stays
+        the caller's, eager, after ``replay()``.
+
+        ``capacity=N``: ``waves`` is a contiguous 1-D tensor of exactly N samples (ValueError otherwise) and ``sample_offsets``
+        the offsets of the batch it holds now.  The recorded step then serves ANY B clips whose lengths are >= 1 and sum to at
+        most N: write the clips, their [B + 1] offsets into ``g.sample_offsets`` (int64 device tensor), the labels and the
+        jitter, and replay; samples behind ``offsets[B]`` are ignored and ``g.status`` (int32 [1]) is 0 for a valid table.  The
+        batch layout is rebuilt by two launches at the head of the front end (``features.pipeline.CapacityLayout``).
+        ``CAPTURE_VERIFIED`` governs the head / B pairs as before; without ``capacity=`` exactly the same launches are
+        recorded as before.
 
         ``optimizer``: a ``features.optim.DeviceAdam`` over exactly the head's trainable parameters, in their order.  The
         recorded sequence then ends in (6) the binding of the optimiser to ``g.grads`` and its step -- three launches of the
@@ -202,7 +228,13 @@ class TrainBatch:
         if jitter is not None and not (_is_device_tensor(jitter) and jitter.dtype == torch.int64 and tuple(jitter.shape) == (B, 2)
                                        and jitter.is_contiguous()):
             raise TypeError('capture needs jitter as a contiguous [B, 2] int64 device tensor (or None): the graph reads it in place')
-        lay = self.features.pipe.prepare(so, 0)                # the graph's own: nothing else launches on its tables
+        if capacity is None:
+            lay = self.features.pipe.prepare(so, 0)            # the graph's own: nothing else launches on its tables
+        else:
+            from .pipeline import check_capacity_wave
+            check_capacity_wave(waves, capacity)
+            lay = self.features.pipe.prepare_capacity(B, capacity, 0)
+            lay.write_offsets(so)
         m0 = self._m0(lay, dev)
         names = [n for n, p in self.head.named_parameters() if p.requires_grad]
         params = [p for p in self.head.parameters() if p.requires_grad]
@@ -252,4 +284,7 @@ class TrainBatch:
             p.grad = None
         if optimizer is not None:
             optimizer._bound = bound                           # the recorded binding has not run yet
-        return _CapturedStep(graph, result, params, grads, [lay, m0, clips, labels, jitter, leaves], optimizer)
+        g = _CapturedStep(graph, result, params, grads, [lay, m0, clips, labels, jitter, leaves], optimizer)
+        if capacity is not None:
+            g.sample_offsets, g.status = lay.sample_offsets_in, lay.status
+        return g

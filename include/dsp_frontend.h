@@ -102,6 +102,11 @@ int dsp_frame_count(int64_t n_samples, int32_t frame_len, int32_t frame_step, in
 /* frame_offsets[0]=0, frame_offsets[b+1]=frame_offsets[b]+T_b      (h_ pointers)    */
 int dsp_frame_offsets(const int64_t* h_sample_offsets, int32_t n_utt, int32_t frame_len,
                       int32_t frame_step, int64_t* h_frame_offsets);
+/* An upper bound on sum_b T_b over EVERY batch of n_utt clips whose lengths sum to at most sample_capacity -- a function of
+ * (sample_capacity, n_utt, frame_len, frame_step) alone: sample_capacity / frame_step + n_utt where frame_len >= frame_step
+ * (T(n) <= n / S + 1 then), + 2 n_utt otherwise (T(n) <= n / S + 2 always).  What a capacity layout sizes its grids,
+ * tables and buffers by.  DSP_EINVAL where the bound does not fit int64. */
+int dsp_frames_bound(int64_t sample_capacity, int32_t n_utt, int32_t frame_len, int32_t frame_step, int64_t* n_frames_bound);
 
 /* ---- plans --------------------------------------------------------------------------------- */
 int dsp_plan_create(const dsp_plan_desc* desc, dsp_plan** plan);
@@ -265,6 +270,33 @@ int dsp_layout_destroy(dsp_layout* layout);
 int dsp_vad_features_layout_batch(const dsp_layout* layout, const void* d_wave, int wave_dtype,
                                   const int64_t* d_sample_offsets, const int64_t* d_frame_offsets, int32_t use_sq,
                                   double* d_amp_sum, int32_t* d_zcr, void* stream);
+
+/*
+ * A batch layout built ON THE DEVICE, so that a recorded launch sequence serves clips of any lengths.
+ *
+ * dsp_batch_offsets_batch (one launch, one workgroup, no atomics, no memset, capturable) reads the caller's [n_utt + 1]
+ * sample offsets from device memory and writes
+ *   d_sample_offsets   the sanitised copy: out[0] = 0, out[b + 1] = clamp(in[b + 1], out[b], sample_capacity) -- whatever
+ *                      the caller wrote, it is monotone and inside the sample_capacity samples of the wave buffer; later
+ *                      kernels read this table only (it must not be the caller's table);
+ *   d_frame_offsets[f] per framing f < n_framings <= 4 (frame_len / frame_step / d_frame_offsets are HOST arrays, the
+ *                      tables device memory): the exclusive prefix sum of dsp_frame_count over the sanitised lengths,
+ *                      equal to dsp_frame_offsets in every integer;
+ *   d_status           one int32, overwritten: bit 0 in[0] != 0, bit 1 a decreasing pair, bit 2 an offset above the
+ *                      capacity, bit 3 a clip of 0 samples (in[b + 1] == in[b]).
+ *
+ * dsp_layout_create_capacity allocates the index tables of a dsp_layout for ANY batch of n_utt clips with at most
+ * n_frames_bound frames (dsp_frames_bound) and builds nothing; dsp_layout_refresh rebuilds them on `stream` from the frame
+ * offsets dsp_batch_offsets_batch wrote for that framing (no allocation, no synchronisation, capturable; a handle from
+ * dsp_layout_create is refused).  dsp_vad_features_layout_batch on such a handle sizes its grid by the bound and stops at
+ * the true count in the tables; it never touches the pooled workspace, so what would need it -- a wave buffer that does
+ * not start on a vector (16 bytes, 8 for int16) where the framing takes a tile kernel -- is DSP_EINVAL.
+ */
+int dsp_batch_offsets_batch(const int64_t* d_sample_offsets_in, int32_t n_utt, int64_t sample_capacity, int32_t n_framings,
+                            const int32_t* frame_len, const int32_t* frame_step, int64_t* d_sample_offsets,
+                            int64_t* const* d_frame_offsets, int32_t* d_status, void* stream);
+int dsp_layout_create_capacity(int32_t n_utt, int64_t n_frames_bound, int32_t frame_len, int32_t frame_step, dsp_layout** out);
+int dsp_layout_refresh(dsp_layout* layout, const int64_t* d_frame_offsets, void* stream);
 
 /*
  * Endpoint-trimmed copy (fp32 out): utterance b keeps samples [segments[2b], segments[2b+1]) relative

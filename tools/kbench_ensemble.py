@@ -10,6 +10,11 @@ Both produce the same labels (checked).  Prints one JSON line; medians over --re
 route synchronised per call (it cannot be otherwise), the device call timed between two events around each group.
 
     python tools/kbench_ensemble.py [--batch 512] [--iters 200] [--repeats 7]
+
+``--capacity`` times something else instead: ``EnsembleBatch.capture(..., capacity=)`` against the exact-shape graph at B = 32 and
+512 with both heads, and an epoch of 8 length vectors through ONE capacity graph against the eager sync-free route
+(tools/kbench_capacity.py; device events, --capacity-iters replays, median of 3 rounds), merged into
+profiles/capacity_layout_kbench.json.
 """
 import argparse
 import json
@@ -29,7 +34,16 @@ def main():
     ap.add_argument('--batch', type=int, default=512)
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--repeats', type=int, default=7)
+    ap.add_argument('--capacity', action='store_true')
+    ap.add_argument('--capacity-iters', type=int, default=20)
+    ap.add_argument('--capacity-batches', default='32,512')
     args = ap.parse_args()
+    if args.capacity:
+        sys.path.insert(0, os.path.join(ROOT, 'tools'))
+        import kbench_capacity
+        rows = kbench_capacity.ensemble_section(tuple(int(v) for v in args.capacity_batches.split(',')), iters=args.capacity_iters)
+        print(json.dumps({'ensemble': kbench_capacity.merge('ensemble', rows)['ensemble']}))
+        return 0
     import torch
     import ensemble_ref as ref
     from ensemble_cases import N_CLASSES, PAIRS, THRESHOLDS

@@ -16,6 +16,10 @@ step -- of ``HMRNNHead`` and ``TransformerHead`` (seeded weights, training mode,
                recurrences as native launches bounded by the row count on the device (csrc/kernels_wgrad.h) instead of torch's
                GEMMs, sums and ``cat`` copies over all 200 rows; timed in the same rounds as their plain twins
 
+  (6) capacity  (``--routes capacity`` alone; not among the defaults) the recorded step with ``capacity=`` against the exact-shape
+               graph, and an epoch of 8 length vectors through ONE capacity graph against the eager route: tools/kbench_capacity.py,
+               merged into profiles/capacity_layout_kbench.json
+
 at B = 32 (the reference's cfg.batch_size) and B = 512, on the stored 16 kHz chirps of tests/ensemble_cases.py, repeated.
 
 The host route takes the jitter as a host array and uploads it on every step (16 bytes per clip, pageable memory), which is
@@ -135,6 +139,13 @@ def main():
     dev = torch.device('cuda', nat.current_device())
     stored, rate = make_clips()
     routes = set(args.routes.split(','))
+    if 'capacity' in routes:
+        sys.path.insert(0, os.path.join(ROOT, 'tools'))
+        import kbench_capacity
+        rows = kbench_capacity.train_section(tuple(int(v) for v in args.batches.split(',')), tuple(args.heads.split(',')), args.iters,
+                                             args.warmup, args.rounds)
+        print(json.dumps({'train': kbench_capacity.merge('train', rows)['train']}))
+        return
     kinds = {'hmrnn': (HMRNNHead, dict(native=True, native_enc=True)), 'transformer': (TransformerHead, dict(native_enc=True, native_attn=True))}
     res = {'iters': args.iters, 'warmup': args.warmup, 'rounds': args.rounds, 'optimizer': 'torch.optim.Adam(lr=1e-4), eager',
            'clock': 'host clock around iters steps ending in a device synchronise; *_event_us and the adam section: device events',
