@@ -92,7 +92,7 @@ struct BatchGeom {
 // pitchfeat_finalize_kernel) put utterance b: elements (t, col(b), col_offset + k) of a [max_len, n_cols, row_width] fp32
 // tensor.  dst_col == nullptr is the identity; the unplaced entry points pass (nullptr, n_utt, the stream's own width, 0).
 struct OutPlacement {
-    const int32_t* dst_col;     // [n_utt] distinct columns in [0, n_cols), or nullptr
+    const int32_t* dst_col;     // [n_utt] distinct columns in [0, n_cols), or nullptr; model_finalize_kernel skips a negative one
     int32_t n_cols, row_width, col_offset;
     __device__ __forceinline__ int32_t col(int32_t b) const { return dst_col ? dst_col[b] : b; }
     // first element of utterance column `c` in row t = 0; rows are stride() apart

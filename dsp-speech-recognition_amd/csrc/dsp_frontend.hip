@@ -279,6 +279,104 @@ __global__ __launch_bounds__(1024) void batch_offsets_kernel(const int64_t* __re
     }
 }
 
+// dsp_rate_groups_batch: one workgroup, built like batch_offsets_kernel.  Clip b (b = 1024 p + tid in pass p) is sanitised
+// as there (running maximum, clamped to the capacity), matched against the table of known rates (no match: group 0 and
+// status bit 4), and per group g two sum-scans over batch order -- of the flag "clip b is in g" and of flag * length -- give
+// its slot k and the rebased offset of that slot: a stable partition, group_by_rate's order (model_glue.py).  Both scans carry
+// from pass to pass.  Behind the real slots every group's tables are completed with pad slots (pick = dst_col = -1, a clip
+// of `pad` samples, zero jitter), so each table has n_utt slots whatever the rates are.  Plain vector stores and fixed
+// scans: no atomics, no memset, the same bits on every run; every word of every table is written.
+struct RateGroupsArgs {
+    int32_t n_groups;
+    int32_t rate[DSP_MAX_RATE_GROUPS];
+    int32_t* pick[DSP_MAX_RATE_GROUPS];
+    int32_t* dst_col[DSP_MAX_RATE_GROUPS];
+    int64_t* offsets[DSP_MAX_RATE_GROUPS];
+    int64_t* jitter[DSP_MAX_RATE_GROUPS];       // all NULL without a source jitter table
+};
+
+__global__ __launch_bounds__(1024) void rate_groups_kernel(const int32_t* __restrict__ rates, const int64_t* __restrict__ in,
+                                                           const int64_t* __restrict__ jitter, int32_t n_utt, int64_t cap,
+                                                           int64_t pad, RateGroupsArgs A, int64_t* __restrict__ out,
+                                                           int32_t* __restrict__ count, int32_t* __restrict__ status) {
+    __shared__ int64_t wtot[16];
+    __shared__ int64_t incl[1024];
+    __shared__ int64_t carry[1 + 2 * DSP_MAX_RATE_GROUPS];      // running maximum; per group: slots so far, samples so far
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        out[0] = 0;
+        for (int k = 0; k < 1 + 2 * DSP_MAX_RATE_GROUPS; ++k) carry[k] = 0;
+    }
+    int flags = 0;
+    __syncthreads();
+    for (int base = 0; base < n_utt; base += 1024) {
+        const int b = base + tid;
+        const bool live = b < n_utt;
+        const int64_t lo = live ? in[b] : 0, hi = live ? in[b + 1] : 0;
+        int grp = -1;
+        if (live) {
+            if (b == 0 && lo != 0) flags |= 1;
+            if (hi < lo) flags |= 2;
+            if (hi > cap || (b == 0 && lo > cap)) flags |= 4;
+            if (hi == lo) flags |= 8;
+            const int32_t r = rates[b];
+            for (int g = A.n_groups - 1; g >= 0; --g)
+                if (r == A.rate[g]) grp = g;
+            if (grp < 0) { flags |= 16; grp = 0; }                   // an unknown rate: defined and memory-safe, reported
+        }
+        const int64_t before = carry[0];
+        int64_t m = block_scan_i64<true>(live ? hi : 0, wtot);
+        m = m > before ? m : before;
+        incl[tid] = m;
+        __syncthreads();
+        const int64_t mprev = tid == 0 ? before : incl[tid - 1];
+        const int64_t end = m < cap ? m : cap, start = mprev < cap ? mprev : cap;
+        if (live) out[b + 1] = end;
+        const int64_t n = end - start;
+        for (int g = 0; g < A.n_groups; ++g) {
+            const bool mine = grp == g;
+            const int64_t k_before = carry[1 + 2 * g], s_before = carry[2 + 2 * g];
+            const int64_t k_incl = block_scan_i64<false>(mine ? 1 : 0, wtot) + k_before;
+            const int64_t s_incl = block_scan_i64<false>(mine ? n : 0, wtot) + s_before;
+            if (mine) {
+                const int64_t k = k_incl - 1;
+                A.pick[g][k] = b;
+                A.dst_col[g][k] = b;
+                A.offsets[g][k] = s_incl - n;
+                if (jitter != nullptr) {
+                    A.jitter[g][2 * k] = jitter[2 * (int64_t)b];
+                    A.jitter[g][2 * k + 1] = jitter[2 * (int64_t)b + 1];
+                }
+            }
+            if (tid == 1023) { carry[1 + 2 * g] = k_incl; carry[2 + 2 * g] = s_incl; }   // read by everyone above, before the scans' barriers
+        }
+        if (tid == 1023) carry[0] = m;
+        __syncthreads();
+    }
+    // pad slots: from the group's count up to n_utt; offsets[cnt] is the end of the real clips, offsets[n_utt] the group's total
+    for (int g = 0; g < A.n_groups; ++g) {
+        const int64_t cnt = carry[1 + 2 * g], tot = carry[2 + 2 * g];
+        for (int64_t k = cnt + tid; k <= n_utt; k += 1024) {
+            A.offsets[g][k] = tot + (k - cnt) * pad;
+            if (k < n_utt) {
+                A.pick[g][k] = -1;
+                A.dst_col[g][k] = -1;
+                if (jitter != nullptr) { A.jitter[g][2 * k] = 0; A.jitter[g][2 * k + 1] = 0; }
+            }
+        }
+        if (tid == 0) count[g] = (int32_t)cnt;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) flags |= __shfl_xor(flags, off, 64);
+    if ((tid & 63) == 0) wtot[tid >> 6] = flags;
+    __syncthreads();
+    if (tid == 0) {
+        int all = 0;
+        for (int k = 0; k < 16; ++k) all |= (int)wtot[k];
+        *status = all;
+    }
+}
+
 // Can the vector kernels (the NFFT = 512 and 1536 MFCC kernels, the VAD tile kernels) read this batch where it lies?
 // They load 16-byte vectors of four samples (8 bytes for int16), so the buffer must start on one; the dense
 // instantiations also need N % 4 == 0 (a vector must not straddle two utterances; ragged batches take any lengths and
@@ -1565,6 +1663,119 @@ int dsp_gather_clips_batch(const void* d_wave, int wave_dtype, const int64_t* d_
     else
         gather_clips_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(static_cast<const float*>(d_wave), d_sample_offsets,
                                                                           d_pick, d_dst_offsets, static_cast<float*>(d_out));
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+// Are two of these `n` table pointers the same, or one of them `other`?  (The tables of one kind have one size: equal start = overlap.)
+static bool tables_collide(const void* const* t, int n, const void* other) {
+    for (int g = 0; g < n; ++g) {
+        if (t[g] == other) return true;
+        for (int h = 0; h < g; ++h)
+            if (t[h] == t[g]) return true;
+    }
+    return false;
+}
+
+int dsp_rate_groups_batch(const int32_t* d_rates, const int64_t* d_sample_offsets_in, const int64_t* d_jitter, int32_t n_utt,
+                          int64_t sample_capacity, int32_t n_groups, const int32_t* group_rates, int64_t pad_len,
+                          int64_t* d_sample_offsets, int32_t* const* d_pick, int32_t* const* d_dst_col,
+                          int64_t* const* d_group_offsets, int64_t* const* d_group_jitter, int32_t* d_count, int32_t* d_status,
+                          void* stream) {
+    if (!d_rates || !d_sample_offsets_in || !group_rates || !d_sample_offsets || !d_pick || !d_dst_col || !d_group_offsets ||
+        !d_count || !d_status)
+        return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: NULL argument");
+    if ((d_jitter == nullptr) != (d_group_jitter == nullptr))
+        return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: d_jitter and d_group_jitter go together (both, or both NULL)");
+    if (n_utt <= 0) return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: n_utt %d must be >= 1", n_utt);
+    if (sample_capacity <= 0) return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: sample_capacity %lld must be >= 1", (long long)sample_capacity);
+    if (n_groups < 1 || n_groups > DSP_MAX_RATE_GROUPS)
+        return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: n_groups %d must be in [1, %d]", n_groups, DSP_MAX_RATE_GROUPS);
+    if (pad_len < 1) return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: pad_len %lld must be >= 1", (long long)pad_len);
+    if (pad_len > (INT64_MAX - sample_capacity) / n_utt)
+        return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: sample_capacity + n_utt * pad_len overflows int64");
+    if (d_sample_offsets == d_sample_offsets_in)
+        return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: the sanitised table must not be the caller's (overlap)");
+    RateGroupsArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n_groups = n_groups;
+    for (int g = 0; g < n_groups; ++g) {
+        if (group_rates[g] <= 0) return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: group %d: rate %d must be > 0", g, group_rates[g]);
+        for (int h = 0; h < g; ++h)
+            if (group_rates[h] == group_rates[g])
+                return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: groups %d and %d share the rate %d", h, g, group_rates[g]);
+        if (!d_pick[g] || !d_dst_col[g] || !d_group_offsets[g] || (d_group_jitter && !d_group_jitter[g]))
+            return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: group %d: NULL table", g);
+        A.rate[g] = group_rates[g]; A.pick[g] = d_pick[g]; A.dst_col[g] = d_dst_col[g]; A.offsets[g] = d_group_offsets[g];
+        A.jitter[g] = d_group_jitter ? d_group_jitter[g] : nullptr;
+    }
+    const void* i32_tabs[2 * DSP_MAX_RATE_GROUPS];
+    const void* i64_tabs[2 * DSP_MAX_RATE_GROUPS + 1];
+    int n32 = 0, n64 = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        i32_tabs[n32++] = d_pick[g]; i32_tabs[n32++] = d_dst_col[g];
+        i64_tabs[n64++] = d_group_offsets[g];
+        if (d_group_jitter) i64_tabs[n64++] = d_group_jitter[g];
+    }
+    i64_tabs[n64++] = d_sample_offsets;
+    if (tables_collide(i32_tabs, n32, d_rates) || tables_collide(i32_tabs, n32, d_count) || tables_collide(i32_tabs, n32, d_status) ||
+        tables_collide(i64_tabs, n64, d_sample_offsets_in) || tables_collide(i64_tabs, n64, d_jitter) || d_count == d_status)
+        return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: two tables share their memory (overlap)");
+    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: dry_run: launches are refused under dsp_debug_host_dry_run");
+    rate_groups_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(d_rates, d_sample_offsets_in, d_jitter, n_utt, sample_capacity, pad_len, A,
+                                                           d_sample_offsets, d_count, d_status);
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+int dsp_gather_groups_batch(const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets, int32_t n_utt, int32_t n_groups,
+                            const int32_t* const* d_pick, const int64_t* const* d_group_offsets, int64_t pad_len,
+                            void* const* d_out, void* stream) {
+    if (!d_wave || !d_sample_offsets || !d_pick || !d_group_offsets || !d_out)
+        return dsp_fail(DSP_EINVAL, "dsp_gather_groups_batch: NULL argument");
+    if (wave_dtype != DSP_WAVE_F32 && wave_dtype != DSP_WAVE_I16)
+        return dsp_fail(DSP_EINVAL, "dsp_gather_groups_batch: bad wave_dtype %d", wave_dtype);
+    if (n_utt < 1 || n_utt > 65535) return dsp_fail(DSP_EINVAL, "dsp_gather_groups_batch: n_utt %d must be in [1, 65535]", n_utt);
+    if (n_groups < 1 || n_groups > DSP_MAX_RATE_GROUPS)
+        return dsp_fail(DSP_EINVAL, "dsp_gather_groups_batch: n_groups %d must be in [1, %d]", n_groups, DSP_MAX_RATE_GROUPS);
+    if (pad_len < 1) return dsp_fail(DSP_EINVAL, "dsp_gather_groups_batch: pad_len %lld must be >= 1", (long long)pad_len);
+    GatherGroupsArgs A;
+    memset(&A, 0, sizeof(A));
+    for (int g = 0; g < n_groups; ++g) {
+        if (!d_pick[g] || !d_group_offsets[g] || !d_out[g]) return dsp_fail(DSP_EINVAL, "dsp_gather_groups_batch: group %d: NULL table or buffer", g);
+        if ((reinterpret_cast<uintptr_t>(d_out[g]) & 15) != 0)
+            return dsp_fail(DSP_EINVAL, "dsp_gather_groups_batch: group %d: the buffer does not start on a 16-byte vector (alignment)", g);
+        A.pick[g] = d_pick[g]; A.offsets[g] = d_group_offsets[g]; A.out[g] = d_out[g];
+    }
+    if (tables_collide(d_out, n_groups, d_wave))
+        return dsp_fail(DSP_EINVAL, "dsp_gather_groups_batch: two wave buffers share their memory (overlap)");
+    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dsp_gather_groups_batch: dry_run: launches are refused under dsp_debug_host_dry_run");
+    const dim3 grid(GATHER_CHUNKS, (unsigned)n_utt, (unsigned)n_groups);
+    if (wave_dtype == DSP_WAVE_I16)
+        gather_groups_kernel<int16_t><<<grid, 256, 0, (hipStream_t)stream>>>(static_cast<const int16_t*>(d_wave), d_sample_offsets, pad_len, A);
+    else
+        gather_groups_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(static_cast<const float*>(d_wave), d_sample_offsets, pad_len, A);
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
+int dsp_scatter_segments_batch(const int64_t* const* d_group_segments, const int32_t* const* d_dst_col, int32_t n_utt,
+                               int32_t n_groups, int64_t* d_endpoints, void* stream) {
+    if (!d_group_segments || !d_dst_col || !d_endpoints) return dsp_fail(DSP_EINVAL, "dsp_scatter_segments_batch: NULL argument");
+    if (n_utt < 1) return dsp_fail(DSP_EINVAL, "dsp_scatter_segments_batch: n_utt %d must be >= 1", n_utt);
+    if (n_groups < 1 || n_groups > DSP_MAX_RATE_GROUPS)
+        return dsp_fail(DSP_EINVAL, "dsp_scatter_segments_batch: n_groups %d must be in [1, %d]", n_groups, DSP_MAX_RATE_GROUPS);
+    ScatterSegmentsArgs A;
+    memset(&A, 0, sizeof(A));
+    for (int g = 0; g < n_groups; ++g) {
+        if (!d_group_segments[g] || !d_dst_col[g]) return dsp_fail(DSP_EINVAL, "dsp_scatter_segments_batch: group %d: NULL table", g);
+        A.seg[g] = d_group_segments[g]; A.dst_col[g] = d_dst_col[g];
+    }
+    if (tables_collide(reinterpret_cast<const void* const*>(d_group_segments), n_groups, d_endpoints))
+        return dsp_fail(DSP_EINVAL, "dsp_scatter_segments_batch: the endpoints must not be a group's segment table (overlap)");
+    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dsp_scatter_segments_batch: dry_run: launches are refused under dsp_debug_host_dry_run");
+    const dim3 grid((unsigned)((n_utt + 255) / 256), (unsigned)n_groups);
+    scatter_segments_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(A, n_utt, d_endpoints);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
 }

@@ -1220,6 +1220,8 @@ __global__ __launch_bounds__(256) void model_finalize_kernel(const float* __rest
     __shared__ double s_part[256];
     __shared__ double s_shift;
     const int b = blockIdx.x, tid = threadIdx.x;
+    const int32_t col = pl.col(b);
+    if (col < 0) return;             // a pad slot of a rate group (dsp_rate_groups_batch): no rows, no len0; the whole workgroup leaves
     const int64_t base = frame_off[b];
     const int T = (int)(frame_off[b + 1] - base);
     const int keep = T < max_len ? T : max_len;
@@ -1306,7 +1308,6 @@ __global__ __launch_bounds__(256) void model_finalize_kernel(const float* __rest
     }
     __syncthreads();
     auto dat = [&](int t, int c) { t = t < 0 ? 0 : (t >= T ? T - 1 : t); return sd1[t * C + c]; };
-    const int32_t col = pl.col(b);
     const int64_t row = pl.stride();
     float* ob = pl.base(out, col);
     for (int i = tid; i < max_len * C; i += 256) {
@@ -1358,4 +1359,72 @@ __global__ __launch_bounds__(256) void gather_clips_kernel(const T* __restrict__
     uint4* vd = reinterpret_cast<uint4*>(dst + head);
     for (int64_t k = tid; k < nvec; k += nthr) vd[k] = vs[k];
     for (int64_t k = head + nvec * V + tid; k < n; k += nthr) dst[k] = src[k];
+}
+
+// dsp_gather_groups_batch: gather_clips_kernel for every rate group of a mixed-rate batch in ONE launch, grid (GATHER_CHUNKS,
+// n_utt slots, n_groups).  Slot i of group g holds source clip pick_g[i], copied as above to out_g + offsets_g[i]; a pad slot
+// (pick_g[i] < 0, dsp_rate_groups_batch) is filled with `pad` samples of DSP_GROUP_PAD_VALUE, so every sample below
+// offsets_g[n_utt] of every group buffer is written by every launch.
+struct GatherGroupsArgs {
+    const int32_t* pick[DSP_MAX_RATE_GROUPS];
+    const int64_t* offsets[DSP_MAX_RATE_GROUPS];
+    void* out[DSP_MAX_RATE_GROUPS];
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void gather_groups_kernel(const T* __restrict__ wave, const int64_t* __restrict__ src_off,
+                                                            int64_t pad, GatherGroupsArgs A) {
+    constexpr int V = 16 / (int)sizeof(T);
+    const int i = blockIdx.y;
+    const int32_t* pick = A.pick[0];
+    const int64_t* dst_off = A.offsets[0];
+    T* out = static_cast<T*>(A.out[0]);
+#pragma unroll
+    for (int g = 1; g < DSP_MAX_RATE_GROUPS; ++g)
+        if ((int)blockIdx.z == g) { pick = A.pick[g]; dst_off = A.offsets[g]; out = static_cast<T*>(A.out[g]); }
+    const int32_t u = pick[i];
+    T* dst = out + dst_off[i];
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthr = (int64_t)gridDim.x * 256;
+    if (u < 0) {
+        for (int64_t k = tid; k < pad; k += nthr) dst[k] = (T)DSP_GROUP_PAD_VALUE;
+        return;
+    }
+    if (u >= (int32_t)gridDim.y) return;             // not a clip of this batch: nothing is read through it
+    const int64_t s0 = src_off[u], n = src_off[u + 1] - s0;
+    const T* src = wave + s0;
+    const uintptr_t mis_s = reinterpret_cast<uintptr_t>(src) & 15, mis_d = reinterpret_cast<uintptr_t>(dst) & 15;
+    if (mis_s != mis_d) {
+        for (int64_t k = tid; k < n; k += nthr) dst[k] = src[k];
+        return;
+    }
+    int64_t head = (int64_t)(((16 - mis_d) & 15) / sizeof(T));
+    if (head > n) head = n;
+    const int64_t nvec = (n - head) / V;
+    for (int64_t k = tid; k < head; k += nthr) dst[k] = src[k];
+    const uint4* vs = reinterpret_cast<const uint4*>(src + head);
+    uint4* vd = reinterpret_cast<uint4*>(dst + head);
+    for (int64_t k = tid; k < nvec; k += nthr) vd[k] = vs[k];
+    for (int64_t k = head + nvec * V + tid; k < n; k += nthr) dst[k] = src[k];
+}
+
+// dsp_scatter_segments_batch: the [n_utt, 2] segment tables the groups' endpoint kernels wrote in slot order, brought back to
+// batch order: endpoints[dst_col_g[k]] = seg_g[k] for every real slot, pad slots (dst_col_g[k] < 0) skipped.  The groups
+// partition the batch, so every row of `endpoints` is written exactly once.  Grid (ceil(n_utt / 256), n_groups).
+struct ScatterSegmentsArgs {
+    const int64_t* seg[DSP_MAX_RATE_GROUPS];
+    const int32_t* dst_col[DSP_MAX_RATE_GROUPS];
+};
+
+__global__ __launch_bounds__(256) void scatter_segments_kernel(ScatterSegmentsArgs A, int32_t n_utt, int64_t* __restrict__ endpoints) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n_utt) return;
+    const int64_t* seg = A.seg[0];
+    const int32_t* dst_col = A.dst_col[0];
+#pragma unroll
+    for (int g = 1; g < DSP_MAX_RATE_GROUPS; ++g)
+        if ((int)blockIdx.y == g) { seg = A.seg[g]; dst_col = A.dst_col[g]; }
+    const int32_t col = dst_col[k];
+    if (col < 0 || col >= n_utt) return;
+    endpoints[2 * (int64_t)col] = seg[2 * (int64_t)k];
+    endpoints[2 * (int64_t)col + 1] = seg[2 * (int64_t)k + 1];
 }

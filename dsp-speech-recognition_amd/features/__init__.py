@@ -14,7 +14,8 @@ directory, no matplotlib / sklearn import).  Both pitch trackers (``pitch_detect
 ``get_batch_full(feat)`` is RNNModel.get_batch_full (model.py:114-135) for the reference's list of (sig, rate) pairs, the
 rates mixed as reader.mini_batch_iterator yields them.  ``TrainBatch`` is the training step of model.py:137-147 on raw clips
 with the lengths kept on the device (features/train.py), and ``DeviceAdam`` its optimiser step (model.py:140-149) with the
-state on the device, recordable behind the backward (features/optim.py).
+state on the device, recordable behind the backward (features/optim.py).  ``MixedRateCapacityBatch`` and ``MixedRateTrainBatch``
+serve mixed-rate batches of any lengths and rate assignments through one recorded launch sequence: the grouping by rate is device work.
 There is no CPU fallback: without the built library or without a GPU every compute call raises.
 """
 from .base import *  # noqa: F401,F403
@@ -29,7 +30,7 @@ from . import base, sigproc, endpoint, preprocess, pitch, batch, pipeline, ensem
 from .batch import FeaturePlan, EndpointPlan  # noqa: F401
 from .pipeline import VadMfccPipeline  # noqa: F401
 from .ensemble import PitchSVM, EnsembleBatch, MixedRateEnsembleBatch, ensemble_decide  # noqa: F401
-from .model_glue import MixedRateFeatureBatch, get_batch_full  # noqa: F401
+from .model_glue import MixedRateFeatureBatch, MixedRateCapacityBatch, get_batch_full  # noqa: F401
 from .svmfit import fit_pitch_svm, grid_search, robust_scale_fit, svm_fit_problems, PitchModelTrainer  # noqa: F401
-from .train import TrainBatch  # noqa: F401
+from .train import TrainBatch, MixedRateTrainBatch  # noqa: F401
 from .optim import DeviceAdam  # noqa: F401

@@ -396,9 +396,10 @@ def _as_rates(rates):
 
 def _no_mixed_capacity(capacity):
     if capacity is not None:
-        raise NotImplementedError('capacity= is not served for mixed-rate batches: the grouping by rate is host logic over the rates '
-                                  '(group_by_rate), so the layout of a mixed batch cannot be rebuilt on the device; use the '
-                                  'single-rate classes')
+        raise NotImplementedError('capacity= is not served for mixed-rate batches by this class: its grouping by rate is host logic over '
+                                  'the rates (group_by_rate), so the layout of a mixed batch cannot be rebuilt on the device here; use '
+                                  'MixedRateCapacityBatch (features, default call) or train.MixedRateTrainBatch, which group on the '
+                                  'device, or the single-rate classes')
 
 
 class _MixedPlan:
@@ -572,7 +573,7 @@ class MixedRateFeatureBatch:
         return len0, endpoints
 
     def run(self, waves, sample_offsets=None, rates=None, jitter=None, use_pitch=False, use_timefeat=False, capacity=None):
-        """``capacity=``: NotImplementedError -- see ``capture``.
+        """``capacity=``: NotImplementedError -- see ``capture`` (``MixedRateCapacityBatch.run`` serves it).
         ``waves``: concatenated clips as a host 1-D array or a 1-D device tensor (int16 / float32, any view) with
         ``sample_offsets`` [B + 1], or a list of B host arrays; ``rates``: [B] sample rates.  -> (inp [max_len, B, 39 (+2)
         (+2)] on the library's device, len0 [B], endpoints [B, 2]), all in batch order; ``jitter`` / ``use_pitch`` /
@@ -590,8 +591,8 @@ class MixedRateFeatureBatch:
         host synchronisation).  The sub-pipelines are queued one after the other on the capture stream: the graph is one
         chain, no forked branches.  One eager call runs first (it builds the layouts' long-lived index tables).
         ``capacity=`` raises NotImplementedError: which clips form a rate group, each group's offsets and its share of the
-        samples are host logic over the rates (``group_by_rate``), so a mixed-rate graph stays bound to its lengths AND rates;
-        the single-rate classes take ``capacity=``."""
+        samples are host logic over the rates (``group_by_rate``), so a mixed-rate graph of THIS class stays bound to its lengths
+        AND rates; ``MixedRateCapacityBatch`` groups on the device and takes ``capacity=``, as the single-rate classes do."""
         _no_mixed_capacity(capacity)
 
         def prepare():
@@ -605,6 +606,209 @@ class MixedRateFeatureBatch:
                 return ctx.inp, ctx.len0
             return queue, hold
         return _capture(waves, prepare)
+
+
+# ---- mixed sample rates through one recorded launch sequence: the grouping itself on the device ------------------------
+# group_by_rate and _MixedPlan above are host logic over the rates, so a graph of MixedRateFeatureBatch is bound to its
+# lengths AND rates.  Here the stable partition, each group's rebased offsets, the gather, the placement columns and the
+# endpoints' way back to batch order are launches over device tables (dsp_rate_groups_batch, dsp_gather_groups_batch,
+# dsp_scatter_segments_batch): every rate of a fixed table gets a group of exactly B slots -- its clips, then pad clips of
+# PAD_SAMPLES samples that are computed and written nowhere -- on a capacity layout of its own.
+
+PAD_SAMPLES = 1      # the shortest clip a capacity layout declares valid (status 0): one VAD frame, one MFCC frame, zero variance
+MAX_RATE_GROUPS = 4  # DSP_MAX_RATE_GROUPS
+
+
+def _rate_table(rates):
+    """The table of known rates of a MixedRateCapacityBatch: 1 .. 4 distinct positive whole numbers; ValueError otherwise."""
+    table = tuple(int(r) for r in _as_rates(rates))
+    if not 1 <= len(table) <= MAX_RATE_GROUPS:
+        raise ValueError(f'a rate table holds 1 .. {MAX_RATE_GROUPS} rates, got {len(table)}')
+    if len(set(table)) != len(table):
+        raise ValueError(f'a rate table holds distinct rates, got {list(table)}')
+    if max(table) > 2 ** 31 - 1:
+        raise ValueError(f'sample rates must fit int32, got {list(table)}')
+    return table
+
+
+class _MixedCapacityArena:
+    """Everything one (B, N, sample type) of a MixedRateCapacityBatch launches on: the tensors the caller's batch is written
+    into (``sample_offsets``, ``rates``, ``jitter``), the sanitised source table, and per table rate a capacity layout for B
+    clips of N + B * PAD_SAMPLES samples, its wave buffer, cepstra and small tables.  The host arrays of table pointers the
+    three grouping entry points take are kept here too."""
+
+    def __init__(self, owner, B, N, dev, torch_dtype):
+        import ctypes as C
+        import torch
+        from .ensemble import _segments_tensor
+        self.B, self.N, self.dev = B, N, dev
+        G = self.G = len(owner.rates)
+        self.sample_offsets = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        self.rates = torch.full((B,), owner.rates[0], dtype=torch.int32, device=dev)
+        self.jitter = torch.zeros((B, 2), dtype=torch.int64, device=dev)
+        self.sanitised = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        self.count = torch.zeros(G, dtype=torch.int32, device=dev)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        cap = N + B * PAD_SAMPLES
+        self.lays, self.waves, self.m0, self.pick, self.dst_col, self.group_jitter, self.seg = [], [], [], [], [], [], []
+        for mfb in owner.groups:
+            lay = mfb.pipe.prepare_capacity(B, cap, 0)
+            self.lays.append(lay)
+            # whole 16-byte vectors, and one to spare behind the last sample: the vector kernels load aligned vectors that may
+            # reach past a clip's end (they mask what they loaded), and the capacity handles need the aligned start
+            self.waves.append(torch.zeros((cap + 15) // 8 * 8 + 8, dtype=torch_dtype, device=dev))
+            self.m0.append(torch.empty((max(lay.frames_bound, 1), mfb.pipe.features.C), dtype=torch.float32, device=dev))
+            self.pick.append(torch.full((B,), -1, dtype=torch.int32, device=dev))
+            self.dst_col.append(torch.full((B,), -1, dtype=torch.int32, device=dev))
+            self.group_jitter.append(torch.zeros((B, 2), dtype=torch.int64, device=dev))
+            self.seg.append(_segments_tensor(lay, dev))
+
+        def ptrs(tensors):
+            return (C.c_void_p * G)(*[t.data_ptr() for t in tensors])
+        self.h_rates = (C.c_int32 * G)(*owner.rates)
+        self.p_pick, self.p_dst_col, self.p_jitter = ptrs(self.pick), ptrs(self.dst_col), ptrs(self.group_jitter)
+        self.p_offsets = ptrs([lay.sample_offsets_in for lay in self.lays])
+        self.p_waves, self.p_seg = ptrs(self.waves), ptrs(self.seg)
+
+    def write(self, sample_offsets, rates, jitter):
+        """Copy a batch's tables ([B + 1] offsets, [B] rates, [B, 2] jitter or None: host arrays or device tensors) into the
+        tensors the launches read, on torch's current stream; ValueError for a table of another shape (the values are the
+        device's to check: ``status``)."""
+        import torch
+
+        def put(dst, src, np_dtype, what):
+            t = src if torch.is_tensor(src) else torch.from_numpy(np.ascontiguousarray(src, dtype=np_dtype))
+            if tuple(t.shape) != tuple(dst.shape):
+                raise ValueError(f'{what} must be {list(dst.shape)}, got {list(t.shape)}')
+            dst.copy_(t)
+        put(self.sample_offsets, sample_offsets, np.int64, 'sample_offsets')
+        put(self.rates, rates, np.int32, 'rates')
+        if jitter is not None:
+            put(self.jitter, jitter, np.int64, 'jitter')
+
+
+class MixedRateCapacityBatch:
+    """RNNModel.get_batch_full (model.py:113-135) for ANY batch of B clips at the rates of a fixed table (reader.py:80 yields
+    44.1 and 48 kHz files in shuffled order) whose lengths are >= 1 and sum to at most N, as one launch sequence that reads
+    lengths, rates and jitter from device memory -- the default call (no optional streams), capacity routes only:
+
+      dsp_rate_groups_batch     the source table sanitised, the stable partition by rate (``group_by_rate``'s order), each group's
+                                rebased offsets straight into its CapacityLayout.sample_offsets_in, pick / placement / jitter tables
+      dsp_gather_groups_batch   every clip to its group's wave buffer, pad slots filled; one launch for all groups
+      per table rate            ``ModelFeatureBatch.enqueue_placed`` unchanged, on the group's buffer, with its dst_col and jitter
+      dsp_scatter_segments_batch  the endpoints back to batch order
+
+    One chain, no forked branches, no memset, no pooled workspace, no scratch slot: ``capture`` records exactly what ``run``
+    queues.  A group has B slots whatever the rates are; the slots behind its clips hold pad clips of PAD_SAMPLES samples,
+    whose rows the finalize kernel skips (negative column).  ``status`` (int32 [1]): bits 0-3 as ``CapacityLayout.status``,
+    judged on the caller's table; bit 4: a rate outside the table -- that clip ran at ``rates[0]``."""
+
+    def __init__(self, rates=(44100, 48000), frame=0.03, step=0.01, nfft=1536, delta_n=3, max_len=200):
+        self.rates = _rate_table(rates)
+        self.groups = [ModelFeatureBatch(r, frame=frame, step=step, nfft=nfft, delta_n=delta_n, max_len=max_len) for r in self.rates]
+        self.max_len = max_len
+        self.C = self.groups[0].pipe.features.C
+        self._arenas = {}
+
+    draw_jitter = staticmethod(MixedRateFeatureBatch.draw_jitter)
+
+    def prepare(self, n_utt, capacity, waves):
+        """An arena of its own for (n_utt, capacity) and the sample type and device of ``waves``."""
+        nat.require_device()
+        _wave_dtype_of(waves)
+        n_utt, capacity = int(n_utt), int(capacity)
+        if n_utt < 1 or capacity < 1:
+            raise ValueError(f'need n_utt >= 1 and capacity >= 1, got {n_utt}, {capacity}')
+        return _MixedCapacityArena(self, n_utt, capacity, waves.device, waves.dtype)
+
+    def _arena(self, n_utt, capacity, waves):
+        """``run``: one arena per (device, B, N, sample type), a few kept, the most recently used last."""
+        key = (waves.device.index, int(n_utt), int(capacity), str(waves.dtype))
+        arena = self._arenas.pop(key, None)
+        if arena is None:
+            arena = self.prepare(n_utt, capacity, waves)
+            while len(self._arenas) >= 4:
+                self._arenas.pop(next(iter(self._arenas)))
+        self._arenas[key] = arena
+        return arena
+
+    @staticmethod
+    def _n_utt(sample_offsets):
+        import torch
+        n = int(sample_offsets.shape[0] if torch.is_tensor(sample_offsets) else len(sample_offsets)) - 1
+        if n < 1:
+            raise ValueError('an empty batch')
+        return n
+
+    def enqueue(self, waves, arena, inp, len0, endpoints, use_jitter, stream):
+        """The whole sequence as launches on ``stream`` (a torch stream): nothing allocated, nothing synchronised.  ``waves``:
+        the [N] source tensor; ``inp`` [max_len, B, 3 C] fp32, ``len0`` [B] int32, ``endpoints`` [B, 2] int64: every element
+        of all three is written, since the groups partition the batch."""
+        lib, st, B, G = nat.load(), _stream_ptr(stream), arena.B, arena.G
+        dtype = _wave_dtype_of(waves)
+        nat.check(lib.dsp_rate_groups_batch(arena.rates.data_ptr(), arena.sample_offsets.data_ptr(),
+                                            arena.jitter.data_ptr() if use_jitter else None, B, arena.N, G, arena.h_rates, PAD_SAMPLES,
+                                            arena.sanitised.data_ptr(), arena.p_pick, arena.p_dst_col, arena.p_offsets,
+                                            arena.p_jitter if use_jitter else None, arena.count.data_ptr(), arena.status.data_ptr(), st))
+        nat.check(lib.dsp_gather_groups_batch(waves.data_ptr(), dtype, arena.sanitised.data_ptr(), B, G, arena.p_pick, arena.p_offsets,
+                                              PAD_SAMPLES, arena.p_waves, st))
+        for g, mfb in enumerate(self.groups):
+            mfb.enqueue_placed(arena.waves[g].data_ptr(), dtype, arena.lays[g], arena.m0[g].data_ptr(), inp.data_ptr(), len0.data_ptr(),
+                               arena.dst_col[g].data_ptr(), B, 3 * self.C, stream, arena.dev,
+                               d_jitter=arena.group_jitter[g].data_ptr() if use_jitter else None)
+        nat.check(lib.dsp_scatter_segments_batch(arena.p_seg, arena.p_dst_col, B, G, endpoints.data_ptr(), st))
+
+    def _outputs(self, B, dev):
+        import torch
+        return (torch.empty((self.max_len, B, 3 * self.C), dtype=torch.float32, device=dev),
+                torch.empty(B, dtype=torch.int32, device=dev), torch.empty((B, 2), dtype=torch.int64, device=dev))
+
+    def run(self, waves, sample_offsets, rates, jitter=None, capacity=None):
+        """Eager and sync-free: ``waves`` a contiguous device tensor of exactly ``capacity`` = N samples (int16 / float32;
+        ValueError otherwise), ``sample_offsets`` [B + 1], ``rates`` [B] and ``jitter`` ([B, 2], ``draw_jitter``; None = the test
+        path) host arrays or device tensors.  -> (inp [max_len, B, 39], len0 int32 [B], endpoints int64 [B, 2], status int32
+        [1]): device tensors in batch order, valid after the current stream's work.  Exactly the launches ``capture`` records,
+        on an arena cached per (B, N)."""
+        import torch
+        from .pipeline import check_capacity_wave
+        if capacity is None:
+            raise ValueError('MixedRateCapacityBatch serves capacity routes only: pass capacity=N (MixedRateFeatureBatch.run takes exact shapes)')
+        check_capacity_wave(waves, capacity)
+        arena = self._arena(self._n_utt(sample_offsets), capacity, waves)
+        arena.write(sample_offsets, rates, jitter)
+        inp, len0, endpoints = self._outputs(arena.B, waves.device)
+        self.enqueue(waves, arena, inp, len0, endpoints, jitter is not None, torch.cuda.current_stream(waves.device))
+        return inp, len0, endpoints, arena.status
+
+    def capture(self, waves, sample_offsets, rates, jitter=None, capacity=None):
+        """A HIP graph of ``run``'s launches over ``waves`` (contiguous [N] device tensor) and the batch it holds now:
+        ``g = mc.capture(waves, so, rates, jitter, capacity=N)``.  Before a ``g.replay()`` write the next batch's clips into
+        ``waves``, its offsets into ``g.sample_offsets`` (int64 [B + 1]), its rates into ``g.rates`` (int32 [B]) and, if the
+        graph was recorded with jitter, its rows into ``g.jitter`` (int64 [B, 2]); ANY B clips at the table's rates whose
+        lengths are >= 1 and sum to at most N are served, in any order of rates.  ``replay()`` -> (inp, len0, endpoints) on
+        the device; ``g.status`` as ``run``'s."""
+        import torch
+        from .pipeline import check_capacity_wave
+        if capacity is None:
+            raise ValueError('MixedRateCapacityBatch serves capacity routes only: pass capacity=N')
+        box = []
+
+        def prepare():
+            check_capacity_wave(waves, capacity)
+            arena = self.prepare(self._n_utt(sample_offsets), capacity, waves)       # the graph's own
+            arena.write(sample_offsets, rates, jitter)
+            box.append(arena)
+            out = self._outputs(arena.B, waves.device)
+
+            def queue():
+                self.enqueue(waves, arena, *out, jitter is not None, torch.cuda.current_stream(waves.device))
+                return out
+            return queue, [arena]
+        g = _capture(waves, prepare)
+        arena = box[0]
+        g.sample_offsets, g.rates, g.status = arena.sample_offsets, arena.rates, arena.status
+        g.jitter = arena.jitter if jitter is not None else None
+        return g
 
 
 _DEFAULT_MIXED = None

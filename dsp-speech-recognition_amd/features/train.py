@@ -114,12 +114,17 @@ class TrainBatch:
         """Front end, head, loss: launches on torch's current stream, nothing synchronised, no device memory read from the
         host.  ``alias``: name -> tensor to stand in for the head's parameters during the call (``capture``)."""
         import torch
-        from .classifier import head_length_info
         mfb, dev, B = self.features, clips.device, lay.n_utt
         inp = torch.empty((mfb.max_len, B, 3 * mfb.pipe.features.C), dtype=torch.float32, device=dev)
         len0 = torch.empty(B, dtype=torch.int32, device=dev)
         mfb.enqueue(clips.data_ptr(), _wave_dtype_of(clips), lay, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(),
                     torch.cuda.current_stream(dev), d_jitter=None if d_jit is None else d_jit.data_ptr())
+        return self._head_loss(inp, len0, labels, head_kwargs, alias, [clips, lay, m0, labels, d_jit])
+
+    def _head_loss(self, inp, len0, labels, head_kwargs, alias, hold):
+        """The chain from ``inp`` / ``len0`` on: head, loss, the count of clamped lengths."""
+        import torch
+        from .classifier import head_length_info
         kw = dict(device_len=True, device_grad=True, **head_kwargs)
         if alias is None:
             out = self.head(inp, len0, **kw)
@@ -128,8 +133,7 @@ class TrainBatch:
         logits = _logits_of(out)
         loss = torch.nn.functional.cross_entropy(logits, labels)                        # model.py:141-147
         n_clamped = head_length_info(len0, inp.shape[0], 1)[2][2:3]
-        return types.SimpleNamespace(loss=loss, logits=logits, inp=inp, len0=len0, n_clamped=n_clamped,
-                                     _hold=[clips, lay, m0, labels, d_jit])
+        return types.SimpleNamespace(loss=loss, logits=logits, inp=inp, len0=len0, n_clamped=n_clamped, _hold=hold)
 
     def run(self, waves, sample_offsets, labels, jitter=None, capacity=None, **head_kwargs):
         """``capacity=N``: the same chain on a capacity layout cached per (B, N) -- the launches ``capture(..., capacity=N)``
@@ -207,18 +211,34 @@ class TrainBatch:
         has been seen to go wrong on replay on this stack, so a head / size pair is recorded only where
         tests/test_gpu_train_capture.py has compared a second replay with the eager step bit for bit.  Anything else raises
         NotImplementedError; ``run`` serves every head and size."""
+        so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
+        B = len(so) - 1
+        clips = self._check_capture(waves, B, labels, jitter)
+        dev = waves.device
+        if capacity is None:
+            lay = self.features.pipe.prepare(so, 0)            # the graph's own: nothing else launches on its tables
+        else:
+            from .pipeline import check_capacity_wave
+            check_capacity_wave(waves, capacity)
+            lay = self.features.pipe.prepare_capacity(B, capacity, 0)
+            lay.write_offsets(so)
+        m0 = self._m0(lay, dev)
+        g = self._record(dev, lambda alias: self._chain(clips, lay, m0, labels, jitter, head_kwargs, alias), optimizer,
+                         [lay, m0, clips, labels, jitter])
+        if capacity is not None:
+            g.sample_offsets, g.status = lay.sample_offsets_in, lay.status
+        return g
+
+    def _check_capture(self, waves, B, labels, jitter):
+        """The refusals of ``capture`` in front of its layout -> the clips as a flat view of ``waves``."""
         import torch
-        from .classifier import _NativeHandle
         if not _is_device_tensor(waves):
             raise TypeError('capture needs a device tensor')
         if not waves.is_contiguous():
             raise ValueError('capture needs a contiguous waves tensor: the graph reads it in place on every replay')
         nat.require_device()
-        dev = waves.device
         clips = waves.reshape(-1)                              # a view: the same memory
         _wave_dtype_of(clips)
-        so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
-        B = len(so) - 1
         kind = type(self.head).__name__
         if B not in CAPTURE_VERIFIED.get(kind, ()):
             raise NotImplementedError(f'capture: {kind} at B = {B} is not in CAPTURE_VERIFIED ({CAPTURE_VERIFIED}): a replay of this head '
@@ -228,14 +248,13 @@ class TrainBatch:
         if jitter is not None and not (_is_device_tensor(jitter) and jitter.dtype == torch.int64 and tuple(jitter.shape) == (B, 2)
                                        and jitter.is_contiguous()):
             raise TypeError('capture needs jitter as a contiguous [B, 2] int64 device tensor (or None): the graph reads it in place')
-        if capacity is None:
-            lay = self.features.pipe.prepare(so, 0)            # the graph's own: nothing else launches on its tables
-        else:
-            from .pipeline import check_capacity_wave
-            check_capacity_wave(waves, capacity)
-            lay = self.features.pipe.prepare_capacity(B, capacity, 0)
-            lay.write_offsets(so)
-        m0 = self._m0(lay, dev)
+        return clips
+
+    def _record(self, dev, chain, optimizer, hold):
+        """The check of ``optimizer`` and the recipe of ``capture``: ``chain(alias)`` queues front end, head and loss on torch's current
+        stream with the parameter aliases standing in, and returns the namespace of ``run``."""
+        import torch
+        from .classifier import _NativeHandle
         names = [n for n, p in self.head.named_parameters() if p.requires_grad]
         params = [p for p in self.head.parameters() if p.requires_grad]
         if optimizer is not None:
@@ -258,7 +277,7 @@ class TrainBatch:
                 for m in handles:
                     if m._handle is not None:
                         m._native_handle(dev, refresh='always')
-            out = self._chain(clips, lay, m0, labels, jitter, head_kwargs, alias)
+            out = chain(alias)
             with torch.autograd.set_multithreading_enabled(False):      # every recorded launch comes from the capturing thread
                 out.loss.backward()
             if record and optimizer is not None:               # the graph's own gradients: their addresses are known from here on
@@ -284,7 +303,68 @@ class TrainBatch:
             p.grad = None
         if optimizer is not None:
             optimizer._bound = bound                           # the recorded binding has not run yet
-        g = _CapturedStep(graph, result, params, grads, [lay, m0, clips, labels, jitter, leaves], optimizer)
-        if capacity is not None:
-            g.sample_offsets, g.status = lay.sample_offsets_in, lay.status
+        return _CapturedStep(graph, result, params, grads, list(hold) + [leaves], optimizer)
+
+
+class MixedRateTrainBatch(TrainBatch):
+    """model.py:137-147 for batches that mix the sample rates of a fixed table (reader.py:80 yields 44.1 and 48 kHz files in
+    shuffled order): ``TrainBatch``'s capacity routes over ``model_glue.MixedRateCapacityBatch``, whose front end groups the
+    clips by rate on the device.  From ``inp`` / ``len0`` on the chain is ``TrainBatch``'s.  Capacity routes only: ``run`` and
+    ``capture`` need ``capacity=N``; one recorded step then serves an epoch whose lengths AND rate assignments change from
+    batch to batch."""
+
+    def __init__(self, rates, head, frame=0.03, step=0.01):
+        from .model_glue import MixedRateCapacityBatch
+        self.features = MixedRateCapacityBatch(rates, frame=frame, step=step)     # ValueError for a bad table, before any device work
+        self.rates, self.head = self.features.rates, head
+
+    def draw_jitter(self, rates, rng):
+        """The endpoint offsets of model.py:54-60 for a batch with these [B] rates, in the reference's order: int64 [B, 2]."""
+        return self.features.draw_jitter(rates, rng)
+
+    def _mixed_chain(self, clips, arena, labels, use_jitter, head_kwargs, alias=None):
+        import torch
+        inp, len0, endpoints = self.features._outputs(arena.B, clips.device)
+        self.features.enqueue(clips, arena, inp, len0, endpoints, use_jitter, torch.cuda.current_stream(clips.device))
+        ns = self._head_loss(inp, len0, labels, head_kwargs, alias, [clips, arena, labels])
+        ns.endpoints, ns.status = endpoints, arena.status
+        return ns
+
+    def run(self, waves, sample_offsets, rates, labels, jitter=None, capacity=None, **head_kwargs):
+        """``TrainBatch.run(..., capacity=N)`` with ``rates`` [B] beside the offsets (host arrays or device tensors): the launches
+        ``capture`` records, on an arena cached per (B, N).  The namespace also carries ``endpoints`` (int64 [B, 2]) and
+        ``status`` (``MixedRateCapacityBatch``: bit 4 = a rate outside the table)."""
+        from .pipeline import check_capacity_wave
+        nat.require_device()
+        if capacity is None:
+            raise ValueError('MixedRateTrainBatch serves capacity routes only: pass capacity=N')
+        check_capacity_wave(waves, capacity)
+        _wave_dtype_of(waves)
+        fe = self.features
+        B = fe._n_utt(sample_offsets)
+        labels, jitter = self._labels(labels, B, waves.device), self._jitter(jitter, B, waves.device)
+        arena = fe._arena(B, capacity, waves)
+        arena.write(sample_offsets, rates, jitter)
+        return self._mixed_chain(waves, arena, labels, jitter is not None, head_kwargs)
+
+    def capture(self, waves, sample_offsets, rates, labels, jitter=None, optimizer=None, capacity=None, **head_kwargs):
+        """``TrainBatch.capture(..., capacity=N)`` for a mixed-rate batch: ONE HIP graph of the handle refresh, the grouping
+        front end, forward, loss, backward and -- with ``optimizer=`` -- the ``DeviceAdam`` step.  Before a ``replay()`` write
+        the next batch's clips into ``waves``, its offsets into ``g.sample_offsets`` (int64 [B + 1]), its rates into ``g.rates``
+        (int32 [B]), the labels into ``labels`` and -- if recorded with jitter -- its rows into ``g.jitter`` (int64 [B, 2]: the
+        graph's own table, a copy of ``jitter`` as given here).  ``CAPTURE_VERIFIED`` governs the head / B pairs as before."""
+        from .pipeline import check_capacity_wave
+        fe = self.features
+        B = fe._n_utt(sample_offsets)
+        clips = self._check_capture(waves, B, labels, jitter)
+        if capacity is None:
+            raise ValueError('MixedRateTrainBatch serves capacity routes only: pass capacity=N')
+        check_capacity_wave(waves, capacity)
+        arena = fe.prepare(B, capacity, waves)                 # the graph's own
+        arena.write(sample_offsets, rates, jitter)
+        use_jitter = jitter is not None
+        g = self._record(waves.device, lambda alias: self._mixed_chain(clips, arena, labels, use_jitter, head_kwargs, alias), optimizer,
+                         [arena, clips, labels])
+        g.sample_offsets, g.rates, g.status = arena.sample_offsets, arena.rates, arena.status
+        g.jitter = arena.jitter if use_jitter else None
         return g

@@ -796,6 +796,8 @@ int dsp_trim_preemph_batch(const void* d_wave, int wave_dtype, const int64_t* d_
  *
  * dsp_model_finalize_placed_batch covers both sources: d_segments / d_work NULL = dsp_model_finalize_batch, both set =
  * dsp_model_finalize_segments_batch.  d_len0 is [n_cols]: utterance b's min(T_b, max_len) goes to d_len0[dst_col[b]].
+ * An utterance with d_dst_col[b] < 0 is SKIPPED by this entry point: it writes no rows and no d_len0 entry (the pad slots of a
+ * rate group, dsp_rate_groups_batch below).  The two optional-stream entry points below take non-negative columns only.
  */
 int dsp_model_finalize_placed_batch(const float* d_mfcc, int64_t ld_in, const int64_t* d_frame_offsets,
                                     const int64_t* d_segments, const void* d_work, int32_t n_utt, int32_t C, int32_t N,
@@ -818,6 +820,50 @@ int dsp_model_pitchfeat_placed_batch(const double* d_pitch, const int64_t* d_fra
  */
 int dsp_gather_clips_batch(const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets, const int32_t* d_pick,
                            int32_t n_pick, const int64_t* d_dst_offsets, void* d_out, void* stream);
+
+/*
+ * The grouping by rate itself as device work, so that ONE recorded launch sequence serves a shuffled epoch of 44.1 / 48 kHz
+ * files (reader.py:80, model.py:114-135) whatever the lengths and the rate of each position are: the device form of
+ * group_by_rate and _MixedPlan in features/model_glue.py.  Every group g < n_groups <= DSP_MAX_RATE_GROUPS gets tables of
+ * n_utt SLOTS: its clips first, in batch order (a stable partition), then pad slots -- clips of pad_len samples of
+ * DSP_GROUP_PAD_VALUE that run through the group's pipeline and are written nowhere -- so that each group is a batch of
+ * exactly n_utt clips of at most sample_capacity + n_utt * pad_len samples, which is what a capacity layout serves.
+ *
+ * dsp_rate_groups_batch (one launch, one workgroup, plain stores and fixed scans: no atomics, no memset, the same bits on
+ * every run, capturable) reads d_rates [n_utt] (Hz), the caller's d_sample_offsets_in [n_utt + 1] and, unless NULL,
+ * d_jitter [n_utt, 2] (model.py:54-60) from device memory; group_rates [n_groups] (distinct, > 0) and the four arrays of
+ * n_groups table pointers are HOST arrays.  It writes, every word on every launch,
+ *   d_sample_offsets    the sanitised source table, by the rule of dsp_batch_offsets_batch: out[0] = 0, out[b + 1] =
+ *                       clamp(in[b + 1], out[b], sample_capacity); the gather reads this table only;
+ *   d_pick[g]           [n_utt] the source clip of each slot, -1 for a pad slot;  d_dst_col[g]: the same values, the
+ *                       placement columns of dsp_model_finalize_placed_batch;
+ *   d_group_offsets[g]  [n_utt + 1] the running sum of the group's sanitised clip lengths, then + pad_len per pad slot:
+ *                       the sample offsets of the group's own batch;
+ *   d_group_jitter[g]   [n_utt, 2] the jitter rows in slot order, zeros for pad slots (NULL together with d_jitter);
+ *   d_count             [n_groups] the clips of each group;
+ *   d_status            one int32: bits 0-3 as dsp_batch_offsets_batch, judged on the caller's table; bit 4: a rate that is
+ *                       not in group_rates -- that clip goes to group 0, which is defined and memory-safe.
+ *
+ * dsp_gather_groups_batch (one launch for all groups) copies slot i of group g, clip d_pick[g][i] of d_wave read through
+ * the SANITISED d_sample_offsets, to d_out[g] + d_group_offsets[g][i] as dsp_gather_clips_batch copies (sample type kept),
+ * and fills a pad slot with pad_len samples of DSP_GROUP_PAD_VALUE.  d_out[g]: that group's own buffer of at least
+ * sample_capacity + n_utt * pad_len samples, starting on a 16-byte vector, distinct from d_wave and from each other.
+ *
+ * dsp_scatter_segments_batch brings the groups' [n_utt, 2] segment tables (slot order, written by each group's endpoint
+ * kernels) back to batch order: d_endpoints[d_dst_col[g][k]] = d_group_segments[g][k], pad slots skipped; one launch.
+ */
+#define DSP_MAX_RATE_GROUPS 4
+#define DSP_GROUP_PAD_VALUE 1
+int dsp_rate_groups_batch(const int32_t* d_rates, const int64_t* d_sample_offsets_in, const int64_t* d_jitter, int32_t n_utt,
+                          int64_t sample_capacity, int32_t n_groups, const int32_t* group_rates, int64_t pad_len,
+                          int64_t* d_sample_offsets, int32_t* const* d_pick, int32_t* const* d_dst_col,
+                          int64_t* const* d_group_offsets, int64_t* const* d_group_jitter, int32_t* d_count, int32_t* d_status,
+                          void* stream);
+int dsp_gather_groups_batch(const void* d_wave, int wave_dtype, const int64_t* d_sample_offsets, int32_t n_utt, int32_t n_groups,
+                            const int32_t* const* d_pick, const int64_t* const* d_group_offsets, int64_t pad_len,
+                            void* const* d_out, void* stream);
+int dsp_scatter_segments_batch(const int64_t* const* d_group_segments, const int32_t* const* d_dst_col, int32_t n_utt,
+                               int32_t n_groups, int64_t* d_endpoints, void* stream);
 
 /* ---- the attention blocks: rnn_clf.Transformer's encoder layer and rnn_clf.HRNN_Att's pooling (forward, fp32) ------- */
 /*
