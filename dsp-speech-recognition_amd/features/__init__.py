@@ -16,6 +16,8 @@ rates mixed as reader.mini_batch_iterator yields them.  ``TrainBatch`` is the tr
 with the lengths kept on the device (features/train.py), and ``DeviceAdam`` its optimiser step (model.py:140-149) with the
 state on the device, recordable behind the backward (features/optim.py).  ``MixedRateCapacityBatch`` and ``MixedRateTrainBatch``
 serve mixed-rate batches of any lengths and rate assignments through one recorded launch sequence: the grouping by rate is device work.
+``DeviceRng`` and ``device_dropout`` (features/dropout.py) draw the heads' dropouts from a counter-based generator on the device:
+the heads' ``rng=`` keyword makes an eager step and a graph replay draw the same multipliers.
 There is no CPU fallback: without the built library or without a GPU every compute call raises.
 """
 from .base import *  # noqa: F401,F403
@@ -26,7 +28,7 @@ from .pitch import (center_clip, max_pitch, pitch_detect_frame_sr, pitch_detect_
                     robust_max_pitch, smooth, window, pitch_detect, pitch_detect_frame, peak_score,
                     sub_endpoint_detect, find_smooth_subsequence, slope, quad_params, peakshift, pitch_feature,
                     pitch_feature_batch, pitch_features_device)
-from . import base, sigproc, endpoint, preprocess, pitch, batch, pipeline, ensemble, train, optim, svmfit  # noqa: F401
+from . import base, sigproc, endpoint, preprocess, pitch, batch, pipeline, ensemble, train, optim, svmfit, dropout  # noqa: F401
 from .batch import FeaturePlan, EndpointPlan  # noqa: F401
 from .pipeline import VadMfccPipeline  # noqa: F401
 from .ensemble import PitchSVM, EnsembleBatch, MixedRateEnsembleBatch, ensemble_decide  # noqa: F401
@@ -34,3 +36,4 @@ from .model_glue import MixedRateFeatureBatch, MixedRateCapacityBatch, get_batch
 from .svmfit import fit_pitch_svm, grid_search, robust_scale_fit, svm_fit_problems, PitchModelTrainer  # noqa: F401
 from .train import TrainBatch, MixedRateTrainBatch  # noqa: F401
 from .optim import DeviceAdam  # noqa: F401
+from .dropout import DeviceRng, device_dropout  # noqa: F401

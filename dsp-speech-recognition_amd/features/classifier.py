@@ -39,6 +39,8 @@ import numpy as np
 import torch
 from torch import nn
 
+from .dropout import SITE_ATTN, SITE_GRU, SITE_HM_ENC, SITE_LOGITS, device_dropout, gru_site
+
 
 def _lengths(len0):
     """Lengths as a list, a NumPy array or a tensor (any device, any integer dtype) -> an int64 NumPy array."""
@@ -47,6 +49,14 @@ def _lengths(len0):
 
 def _ptr(t):
     return None if t is None else t.data_ptr()      # an optional tensor: None is a NULL argument
+
+
+def _dropout(x, p, rng, site):
+    """``F.dropout(x, p)`` in training mode: torch's draw, or with ``rng`` (a ``features.dropout.DeviceRng``) the device
+    generator's at ``site`` (features/dropout.py holds the table of sites)."""
+    if rng is None:
+        return torch.nn.functional.dropout(x, p)
+    return device_dropout(x, p, rng, site)
 
 
 def _check_device_grad(who, device_len, device_grad):
@@ -318,10 +328,11 @@ class _DynEnc(_NativeHandle, nn.Module):
                                             work.data_ptr(), nbytes.value, torch.cuda.current_stream(dev).cuda_stream))
         return y, hn
 
-    def _run_native_train(self, x, lens, drop=None, wgrad=False):
+    def _run_native_train(self, x, lens, drop=None, wgrad=False, rng=None, rng_site=SITE_GRU):
         """The native training path: y and h_n attached to the autograd graph.  ``drop``: the inter-layer multipliers
-        [n_layers - 1, max(lens), B, 2 H] (0 or 1 / (1 - p)); drawn here in training mode when None.  ``wgrad``: the products
-        behind the backward recurrence as native launches (features/wgrad.py) over the max(lens) rows."""
+        [n_layers - 1, max(lens), B, 2 H] (0 or 1 / (1 - p)); drawn here in training mode when None -- with torch, or, with
+        ``rng`` (a ``features.dropout.DeviceRng``), by ``dsp_dropout_multipliers`` at the sites ``rng_site + l``.  ``wgrad``: the
+        products behind the backward recurrence as native launches (features/wgrad.py) over the max(lens) rows."""
         B, H, dev, g = x.shape[1], self.hidden_size, x.device, self.gru
         T = int(lens.max())
         assert lens.numel() == B and int(lens.min()) >= 1 and T <= x.shape[0], 'lengths do not fit the input'
@@ -330,8 +341,11 @@ class _DynEnc(_NativeHandle, nn.Module):
             self._native_handle(dev)
             d_len = lens.to(torch.int32).to(dev)
             if drop is None and self.training and g.dropout > 0 and g.num_layers > 1:
-                keep = 1.0 - g.dropout
-                drop = (torch.rand(g.num_layers - 1, T, B, 2 * H, device=dev) < keep).to(torch.float32) / keep
+                if rng is not None:
+                    drop = rng.multipliers(g.num_layers - 1, T, B, 2 * H, g.dropout, rng_site)
+                else:
+                    keep = 1.0 - g.dropout
+                    drop = (torch.rand(g.num_layers - 1, T, B, 2 * H, device=dev) < keep).to(torch.float32) / keep
             if drop is not None:
                 drop = drop.detach().to(torch.float32).contiguous()
                 assert tuple(drop.shape) == (g.num_layers - 1, T, B, 2 * H), 'drop does not fit [n_layers - 1, T, B, 2 H]'
@@ -339,18 +353,23 @@ class _DynEnc(_NativeHandle, nn.Module):
                 return _DynEncWgradTrain.apply(self, T, d_len, drop, x, None, *self._params())
             return _DynEncTrain.apply(self, T, d_len, drop, x, *self._params())
 
-    def _run_device_train(self, x, d_len, drop=None, wgrad=False, d_rows=None):
+    def _run_device_train(self, x, d_len, drop=None, wgrad=False, d_rows=None, rng=None, rng_site=SITE_GRU):
         """The native training path with the lengths on the device (``device_grad=True``): all x.shape[0] rows of the buffer
         are used -- max(len0) is not known here --, so the multipliers are drawn as [n_layers - 1, x.shape[0], B, 2 H].  The
         handle survives an optimiser step (``refresh=True``).  ``wgrad``: the products behind the backward recurrence as
-        native launches that stop at clamp(d_rows[0], 1, T) rows, read on the device (all T rows without ``d_rows``)."""
+        native launches that stop at clamp(d_rows[0], 1, T) rows, read on the device (all T rows without ``d_rows``).
+        ``rng``: the multipliers come from ``dsp_dropout_multipliers`` at the sites ``rng_site + l``, drawn for the rows below
+        the same ``d_rows`` bound and exact zeros behind it (all rows without ``d_rows``)."""
         B, H, dev, g = x.shape[1], self.hidden_size, x.device, self.gru
         T = x.shape[0]
         with torch.cuda.device(dev):
             self._native_handle(dev, refresh=True)
             if drop is None and self.training and g.dropout > 0 and g.num_layers > 1:
-                keep = 1.0 - g.dropout
-                drop = (torch.rand(g.num_layers - 1, T, B, 2 * H, device=dev) < keep).to(torch.float32) / keep
+                if rng is not None:
+                    drop = rng.multipliers(g.num_layers - 1, T, B, 2 * H, g.dropout, rng_site, d_rows)
+                else:
+                    keep = 1.0 - g.dropout
+                    drop = (torch.rand(g.num_layers - 1, T, B, 2 * H, device=dev) < keep).to(torch.float32) / keep
             if drop is not None:
                 drop = drop.detach().to(torch.float32).contiguous()
                 assert tuple(drop.shape) == (g.num_layers - 1, T, B, 2 * H), 'drop does not fit [n_layers - 1, T, B, 2 H]'
@@ -359,7 +378,10 @@ class _DynEnc(_NativeHandle, nn.Module):
             return _DynEncDeviceTrain.apply(self, T, d_len, drop, x, *self._params())
 
     # ---- nn.GRU path (layers.py:63-76) -----------------------------------------------------------------------------------
-    def _run_torch(self, x, lens):
+    def _run_torch(self, x, lens, rng=None):
+        if rng is not None and self.training and self.gru.dropout > 0 and self.gru.num_layers > 1:
+            raise RuntimeError('_DynEnc: rng= needs the native training path (native=True or device_grad=True): nn.GRU draws its '
+                               'inter-layer dropout itself')
         order = torch.argsort(lens, descending=True, stable=True)
         unsort = torch.argsort(order).to(x.device)
         packed = nn.utils.rnn.pack_padded_sequence(x[:, order.to(x.device)], lens[order])
@@ -368,8 +390,11 @@ class _DynEnc(_NativeHandle, nn.Module):
         h = self.hidden_size
         return (y[:, :, :h] + y[:, :, h:])[:, unsort].contiguous(), hn[:, unsort].contiguous()
 
-    def run(self, x, lens, native=None, device_len=False, device_grad=False, native_wgrad=None, d_rows=None):
+    def run(self, x, lens, native=None, device_len=False, device_grad=False, native_wgrad=None, d_rows=None, rng=None, rng_site=SITE_GRU):
         """-> (y [max(lens), B, H], h_n [2 n_layers, B, H]), the reference's return value (layers.py:76).
+        ``rng`` (a ``features.dropout.DeviceRng``): the native training path draws its inter-layer multipliers with
+        ``dsp_dropout_multipliers`` at the sites ``rng_site + l`` instead of with torch; where inter-layer dropout is active and
+        the route is nn.GRU's it raises.  ``rng=None`` changes nothing.
         ``native_wgrad=True``: on the native training path -- either route -- the products behind the backward recurrence
         (``gru_param_grads``) run as native launches (features/wgrad.py) instead of torch's GEMMs, sums and ``cat`` copies;
         anywhere else it raises.  ``native_wgrad=None`` takes ``native_wgrad_default``.  ``d_rows`` (with ``device_grad=True``): a
@@ -384,6 +409,7 @@ class _DynEnc(_NativeHandle, nn.Module):
         x.shape[0] rows (``_run_device_train``; training mode, as ``native=True``), and the handle is refreshed in place
         after an optimiser step instead of rebuilt."""
         _check_device_grad('_DynEnc', device_len, device_grad)
+        draw = {} if rng is None else {'rng': rng, 'rng_site': rng_site}        # (without rng= the training paths are called as before)
         if d_rows is not None:
             if not device_grad:
                 raise ValueError('_DynEnc: d_rows needs device_len=True, device_grad=True (it bounds the native training path)')
@@ -398,18 +424,18 @@ class _DynEnc(_NativeHandle, nn.Module):
                 raise RuntimeError(f'_DynEnc: the native path cannot run: {why}')
             wgrad = _want_wgrad('_DynEnc', native_wgrad, self.native_wgrad_default, needs_grad)
             if needs_grad:
-                return self._run_device_train(x, lens.contiguous(), wgrad=wgrad, d_rows=d_rows)
+                return self._run_device_train(x, lens.contiguous(), wgrad=wgrad, d_rows=d_rows, **draw)
             if device_grad:
                 self._native_handle(x.device, refresh=True)
             return self._launch_native(x, x.shape[0], lens.contiguous())
         lens = torch.as_tensor(_lengths(lens))
         if native is False:
             _want_wgrad('_DynEnc', native_wgrad, False, False)
-            return self._run_torch(x, lens)
+            return self._run_torch(x, lens, rng)
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
         if native is None and not (self.native_train_default if needs_grad else self.native_default):
             _want_wgrad('_DynEnc', native_wgrad, False, False)
-            return self._run_torch(x, lens)                                     # (nothing to find out about the native path)
+            return self._run_torch(x, lens, rng)                                # (nothing to find out about the native path)
         if needs_grad and not self.training:                                    # eval mode keeps what it always did: no native gradient
             why = 'a gradient is required and the module is in eval mode (the native training path serves training mode)'
         else:
@@ -420,12 +446,12 @@ class _DynEnc(_NativeHandle, nn.Module):
             if why is not None:
                 raise RuntimeError(f"_DynEnc: the native {'training path (a gradient is required)' if needs_grad else 'path'} cannot run: {why}")
             wgrad = _want_wgrad('_DynEnc', native_wgrad, self.native_wgrad_default, needs_grad)
-            return self._run_native_train(x, lens, wgrad=wgrad) if needs_grad else self._run_native(x, lens)
+            return self._run_native_train(x, lens, wgrad=wgrad, **draw) if needs_grad else self._run_native(x, lens)
         _want_wgrad('_DynEnc', native_wgrad, False, False)
-        return self._run_torch(x, lens)
+        return self._run_torch(x, lens, rng)
 
-    def forward(self, x, lens, native=None, device_len=False, device_grad=False, native_wgrad=None, d_rows=None):
-        return self.run(x, lens, native, device_len, device_grad, native_wgrad, d_rows)[0]
+    def forward(self, x, lens, native=None, device_len=False, device_grad=False, native_wgrad=None, d_rows=None, rng=None, rng_site=SITE_GRU):
+        return self.run(x, lens, native, device_len, device_grad, native_wgrad, d_rows, rng, rng_site)[0]
 
 
 def _ones_col_sum(a):
@@ -590,8 +616,9 @@ class RNNHead(nn.Module):
         self.enc = _DynEnc(feat_size, hidden, layers)
         self.out = nn.Linear(2 * hidden, classes)
 
-    def forward(self, inp, len0, native_enc=None, device_len=False, device_grad=False, native_wgrad=None):
+    def forward(self, inp, len0, native_enc=None, device_len=False, device_grad=False, native_wgrad=None, rng=None):
         """inp: [T, B, 39] (zero beyond each utterance's length), len0: lengths (numpy / list / tensor) -> [B, 20].
+        ``rng`` is accepted and ignored: this head has no draw site.
         ``device_len=True``: len0 is a [B] int32 tensor on inp's device and is never read from the host (module docstring);
         ``device_grad=True`` with it serves a required gradient on that path."""
         _check_device_grad('RNNHead', device_len, device_grad)
@@ -621,7 +648,9 @@ class HRNNHead(nn.Module):
     """rnn_clf.HRNN (rnn_clf.py:36-77): 2-layer bidirectional GRU at the frame rate, every ``hir``-th output row
     (t = 0, hir, 2 hir, .. of max(len0) rows) into a 1-layer bidirectional GRU with lengths ceil(len0 / hir), pooled.
     The reference applies F.dropout(out, 0.2) to the logits in EVERY mode (training=True is F.dropout's default,
-    rnn_clf.py:73): ``dropout=True`` does the same, ``False`` returns the logits in front of it.  forward -> (logits, feat)."""
+    rnn_clf.py:73): ``dropout=True`` does the same, ``False`` returns the logits in front of it.  forward -> (logits, feat).
+    ``rng`` (a ``features.dropout.DeviceRng``): every draw -- the logits' and enc1's inter-layer one -- comes from the device
+    generator at its site (features/dropout.py) instead of from torch; enc1 then needs its native training path."""
     hir = 10
 
     def __init__(self, feat_size=39):
@@ -631,37 +660,39 @@ class HRNNHead(nn.Module):
         self.enc2 = _DynEnc(200, 200, 1)
         self.out = nn.Linear(400, 20)
 
-    def _levels(self, inp, len0, native_enc=None, native_wgrad=None):
+    def _levels(self, inp, len0, native_enc=None, native_wgrad=None, rng=None):
         len0 = _lengths(len0)
         len1 = (len0 + self.hir - 1) // self.hir                      # rnn_clf.py:52
-        y = self.enc1(inp, len0, native=native_enc, native_wgrad=native_wgrad)[:, :, -self.hidden_size:]            # rnn_clf.py:58
-        return self.enc2(y[0::self.hir], len1, native=native_enc, native_wgrad=native_wgrad), len1                  # rnn_clf.py:61-65
+        y = self.enc1(inp, len0, native=native_enc, native_wgrad=native_wgrad, rng=rng, rng_site=gru_site(0))[:, :, -self.hidden_size:]   # rnn_clf.py:58
+        return self.enc2(y[0::self.hir], len1, native=native_enc, native_wgrad=native_wgrad, rng=rng, rng_site=gru_site(1)), len1         # rnn_clf.py:61-65
 
-    def _levels_device(self, inp, len0, device_grad=False, native_wgrad=None):
+    def _levels_device(self, inp, len0, device_grad=False, native_wgrad=None, rng=None):
         """``_levels`` with the lengths on the device: all ceil(T / hir) picked rows go into enc2 -> (y2, len1, info)."""
         d_len, d_len1, info = head_length_info(len0, inp.shape[0], self.hir)
         rows0, rows1 = (info[0:1], info[1:2]) if device_grad else (None, None)   # max(len0) and ceil(max(len0) / hir), on the device
-        y = self.enc1(inp, d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad, d_rows=rows0)[:, :, -self.hidden_size:]
-        return self.enc2(y[0::self.hir], d_len1, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad, d_rows=rows1), d_len1, info
+        y = self.enc1(inp, d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad, d_rows=rows0, rng=rng,
+                      rng_site=gru_site(0))[:, :, -self.hidden_size:]
+        return self.enc2(y[0::self.hir], d_len1, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad, d_rows=rows1, rng=rng,
+                         rng_site=gru_site(1)), d_len1, info
 
-    def _forward_device(self, inp, len0, dropout, attn=None, device_grad=False, native_wgrad=None):
+    def _forward_device(self, inp, len0, dropout, attn=None, device_grad=False, native_wgrad=None, rng=None):
         _check_device_len(type(self).__name__, inp, len0, self, device_grad)
-        y2, d_len1, info = self._levels_device(inp, len0, device_grad, native_wgrad)
+        y2, d_len1, info = self._levels_device(inp, len0, device_grad, native_wgrad, rng)
         rows = info[1:2]                                                        # ceil(max(len0) / hir), on the device
         if attn is None:
             feat = _pool_native(y2, d_len1, rows, grad=device_grad)
         else:
             feat = torch.cat([attn(y2, native=True, d_rows=rows, device_grad=device_grad), _pool_native(y2, d_len1, rows, avg=False, grad=device_grad)], dim=1)
         out = self.out(feat)
-        return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
+        return (_dropout(out, 0.2, rng, SITE_LOGITS) if dropout else out), feat
 
-    def forward(self, inp, len0, dropout=True, native_enc=None, device_len=False, device_grad=False, native_wgrad=None):
+    def forward(self, inp, len0, dropout=True, native_enc=None, device_len=False, device_grad=False, native_wgrad=None, rng=None):
         _check_device_grad(type(self).__name__, device_len, device_grad)
         if device_len:
-            return self._forward_device(inp, len0, dropout, device_grad=device_grad, native_wgrad=native_wgrad)
-        y2, len1 = self._levels(inp, len0, native_enc, native_wgrad)
+            return self._forward_device(inp, len0, dropout, device_grad=device_grad, native_wgrad=native_wgrad, rng=rng)
+        y2, len1 = self._levels(inp, len0, native_enc, native_wgrad, rng)
         out, feat = _pool_head(y2, len1, self.out)
-        return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
+        return (_dropout(out, 0.2, rng, SITE_LOGITS) if dropout else out), feat
 
 
 def _attn_needs_grad(x, module):
@@ -859,13 +890,14 @@ class HRNNAttHead(HRNNHead):
         super().__init__(feat_size)
         self.attn = _SelfAttn(200)
 
-    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False, device_grad=False, native_wgrad=None):
+    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False, device_grad=False, native_wgrad=None,
+                rng=None):
         _check_device_grad('HRNNAttHead', device_len, device_grad)
         if device_len:
-            return self._forward_device(inp, len0, dropout, self.attn, device_grad, native_wgrad)
-        y2, len1 = self._levels(inp, len0, native_enc, native_wgrad)
+            return self._forward_device(inp, len0, dropout, self.attn, device_grad, native_wgrad, rng)
+        y2, len1 = self._levels(inp, len0, native_enc, native_wgrad, rng)
         out, feat = _pool_head(y2, len1, self.out, self.attn, native_attn)
-        return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
+        return (_dropout(out, 0.2, rng, SITE_LOGITS) if dropout else out), feat
 
 
 class _LayerNorm(nn.Module):
@@ -1160,7 +1192,8 @@ class _TransformerEncoder(_NativeHandle, nn.Module):
 class TransformerHead(nn.Module):
     """rnn_clf.Transformer (rnn_clf.py:166-203): one self-attention block over the [T, B, 39] input, its output -- behind an
     F.dropout(.., 0.5) that is active in every mode (rnn_clf.py:184) -- concatenated with the input into a bidirectional GRU,
-    every 5th row into a second one, pooled.  ``dropout=False`` leaves both F.dropout calls out.  -> (logits, feat, attn_out)."""
+    every 5th row into a second one, pooled.  ``dropout=False`` leaves both F.dropout calls out.  -> (logits, feat, attn_out).
+    ``rng`` (a ``features.dropout.DeviceRng``): both draws come from the device generator (sites 2 and 0, features/dropout.py)."""
     hir = 5
 
     def __init__(self):
@@ -1171,29 +1204,32 @@ class TransformerHead(nn.Module):
         self.out = nn.Linear(400, 20)
         self.hidden_size = 200
 
-    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False, device_grad=False, native_wgrad=None):
+    def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False, device_grad=False, native_wgrad=None,
+                rng=None):
         _check_device_grad('TransformerHead', device_len, device_grad)
         if device_len:
             _check_device_len('TransformerHead', inp, len0, self, device_grad)
             d_len, d_len1, info = head_length_info(len0, inp.shape[0], self.hir)
             attn_out = self.attn_enc(inp, native=True, refresh=device_grad)
-            a = torch.nn.functional.dropout(attn_out, 0.5) if dropout else attn_out
+            a = _dropout(attn_out, 0.5, rng, SITE_ATTN) if dropout else attn_out
             rows0, rows1 = (info[0:1], info[1:2]) if device_grad else (None, None)
             y = self.rnn_enc_1(torch.cat([inp, a], 2), d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad,
-                               d_rows=rows0)[:, :, -self.hidden_size:]
-            y2 = self.rnn_enc_2(y[0::self.hir], d_len1, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad, d_rows=rows1)
+                               d_rows=rows0, rng=rng, rng_site=gru_site(0))[:, :, -self.hidden_size:]
+            y2 = self.rnn_enc_2(y[0::self.hir], d_len1, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad, d_rows=rows1,
+                                rng=rng, rng_site=gru_site(1))
             feat = _pool_native(y2, d_len1, info[1:2], grad=device_grad)
             out = self.out(feat)
-            return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat, attn_out
+            return (_dropout(out, 0.2, rng, SITE_LOGITS) if dropout else out), feat, attn_out
         len0 = _lengths(len0)
         len1 = (len0 + self.hir - 1) // self.hir
         attn_out = self.attn_enc(inp, native=native_attn)
-        a = torch.nn.functional.dropout(attn_out, 0.5) if dropout else attn_out
+        a = _dropout(attn_out, 0.5, rng, SITE_ATTN) if dropout else attn_out
         # (the reference concatenates all 200 padded rows; the packed GRU then reads max(len0) of them)
-        y = self.rnn_enc_1(torch.cat([inp, a], 2), len0, native=native_enc, native_wgrad=native_wgrad)[:, :, -self.hidden_size:]
-        y2 = self.rnn_enc_2(y[0::self.hir], len1, native=native_enc, native_wgrad=native_wgrad)
+        y = self.rnn_enc_1(torch.cat([inp, a], 2), len0, native=native_enc, native_wgrad=native_wgrad, rng=rng,
+                           rng_site=gru_site(0))[:, :, -self.hidden_size:]
+        y2 = self.rnn_enc_2(y[0::self.hir], len1, native=native_enc, native_wgrad=native_wgrad, rng=rng, rng_site=gru_site(1))
         out, feat = _pool_head(y2, len1, self.out)
-        return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat, attn_out
+        return (_dropout(out, 0.2, rng, SITE_LOGITS) if dropout else out), feat, attn_out
 
 
 class _HMCell(nn.Module):
@@ -1568,7 +1604,8 @@ class HMRNNHead(nn.Module):
     wide), F.dropout(.., 0.2) on its output in EVERY mode (rnn_clf.py:138), the HM-LSTM over the max(len0) rows of it, and
     feat = [sum / len | max over those rows, zero rows included | h_2 at len - 1] -> Linear(600, 20) -> F.dropout(.., 0.2).
     ``dropout=False`` returns the values in front of both dropouts.  forward -> (logits, feat).  Parameter names and order
-    equal the real class's ``named_parameters()``."""
+    equal the real class's ``named_parameters()``.  ``rng`` (a ``features.dropout.DeviceRng``): both draws come from the device
+    generator (sites 1 and 0, features/dropout.py)."""
     hir = 5
 
     def __init__(self, feat_size=39):
@@ -1578,29 +1615,30 @@ class HMRNNHead(nn.Module):
         self.enc2 = HMLSTM(1.0, 200, [200, 200])
         self.out = nn.Linear(600, 20)
 
-    def forward(self, inp, len0, dropout=True, native=None, native_enc=None, device_len=False, device_grad=False, native_wgrad=None):
+    def forward(self, inp, len0, dropout=True, native=None, native_enc=None, device_len=False, device_grad=False, native_wgrad=None,
+                rng=None):
         _check_device_grad('HMRNNHead', device_len, device_grad)
         if device_len:
             _check_device_len('HMRNNHead', inp, len0, self, device_grad)
             d_len, _, info = head_length_info(len0, inp.shape[0], 1)
             enc = self.enc1(inp, d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad,
-                            d_rows=info[0:1] if device_grad else None)                                   # [T, B, 200], zeros behind each end
+                            d_rows=info[0:1] if device_grad else None, rng=rng, rng_site=gru_site(0))   # [T, B, 200], zeros behind each end
             if dropout:
-                enc = torch.nn.functional.dropout(enc, 0.2)
+                enc = _dropout(enc, 0.2, rng, SITE_HM_ENC)
             last = self.enc2.run(enc, None, lens=d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad,
                                  d_rows=info[0:1] if device_grad else None).last_h2      # both passes stop at max(len0)
             feat = torch.cat([_pool_native(enc, d_len, info[0:1], grad=device_grad), last], dim=1)
             out = self.out(feat)
-            return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
+            return (_dropout(out, 0.2, rng, SITE_LOGITS) if dropout else out), feat
         len0 = _lengths(len0)
-        enc = self.enc1(inp, len0, native=native_enc, native_wgrad=native_wgrad)                         # [max(len0), B, 200]
+        enc = self.enc1(inp, len0, native=native_enc, native_wgrad=native_wgrad, rng=rng, rng_site=gru_site(0))   # [max(len0), B, 200]
         if dropout:
-            enc = torch.nn.functional.dropout(enc, 0.2)
+            enc = _dropout(enc, 0.2, rng, SITE_HM_ENC)
         last = self.enc2.run(enc, None, lens=len0, native=native, native_wgrad=native_wgrad).last_h2     # rnn_clf.py:139-143
         n = torch.as_tensor(len0, dtype=enc.dtype, device=enc.device)
         feat = torch.cat([enc.sum(0) / n.unsqueeze(1), enc.max(0).values, last], dim=1)
         out = self.out(feat)
-        return (torch.nn.functional.dropout(out, 0.2) if dropout else out), feat
+        return (_dropout(out, 0.2, rng, SITE_LOGITS) if dropout else out), feat
 
     def adjust_param(self):
         """rnn_clf.py:163-164: the slope schedule, +0.5 per call (see HMLSTM on what the reference's own cells read)."""

@@ -11,6 +11,9 @@
   after ``replay()``: it writes the parameters in place, and the refresh at the head of the next replay repacks them.  With
   ``optimizer=`` a ``features.optim.DeviceAdam`` over the head's trainable parameters, its step is recorded behind the backward:
   the whole of model.py:137-149 is one replay.
+* With ``rng=`` a ``features.dropout.DeviceRng`` among the head's keywords the dropouts are drawn by the device generator, and
+  the chain begins with ``rng.advance()`` -- recorded too, so every replay draws a new step's multipliers, the ones an eager
+  ``run`` from the same state draws.  ``capture`` leaves the generator's state as it found it.
 """
 from __future__ import annotations
 
@@ -28,6 +31,13 @@ CAPTURE_VERIFIED = {'RNNHead': (32, 512), 'HRNNHead': (32, 512), 'HRNNAttHead': 
                     'HMRNNHead': (5, 32, 512)}
 
 
+def _advance_rng(head_kwargs):
+    """The head of every chain: with an ``rng`` among the head's keywords, one step of the generator (a launch, recordable)."""
+    rng = head_kwargs.get('rng')
+    if rng is not None:
+        rng.advance()
+
+
 def _logits_of(out):
     return out[0] if isinstance(out, (tuple, list)) else out
 
@@ -41,10 +51,12 @@ class _CapturedStep:
     that the result does not already keep alive.  ``optimizer``: the ``DeviceAdam`` whose step the graph carries, or None; with
     one, a replay also binds the optimiser to ``grads`` (a recorded launch in front of the step, so an eager ``step()`` on other
     gradients in between does not mislead it), updates the parameters and the optimiser's state, and ``replay()`` bumps the
-    parameters' version counters afterwards."""
+    parameters' version counters afterwards.  ``rng``: the ``DeviceRng`` whose state the recorded draws read (and whose
+    ``advance`` the graph carries), or None; kept alive here."""
 
-    def __init__(self, graph, result, params, grads, hold, optimizer=None):
+    def __init__(self, graph, result, params, grads, hold, optimizer=None, rng=None):
         self.graph, self.result, self.params, self.grads, self.hold, self.optimizer = graph, result, params, grads, hold, optimizer
+        self.rng = rng
         # a capture with ``capacity=``: where the next batch's offsets go before a replay, and the offsets kernel's status word
         self.sample_offsets = self.status = None
 
@@ -114,6 +126,7 @@ class TrainBatch:
         """Front end, head, loss: launches on torch's current stream, nothing synchronised, no device memory read from the
         host.  ``alias``: name -> tensor to stand in for the head's parameters during the call (``capture``)."""
         import torch
+        _advance_rng(head_kwargs)
         mfb, dev, B = self.features, clips.device, lay.n_utt
         inp = torch.empty((mfb.max_len, B, 3 * mfb.pipe.features.C), dtype=torch.float32, device=dev)
         len0 = torch.empty(B, dtype=torch.int32, device=dev)
@@ -224,7 +237,7 @@ class TrainBatch:
             lay.write_offsets(so)
         m0 = self._m0(lay, dev)
         g = self._record(dev, lambda alias: self._chain(clips, lay, m0, labels, jitter, head_kwargs, alias), optimizer,
-                         [lay, m0, clips, labels, jitter])
+                         [lay, m0, clips, labels, jitter], head_kwargs.get('rng'))
         if capacity is not None:
             g.sample_offsets, g.status = lay.sample_offsets_in, lay.status
         return g
@@ -250,9 +263,10 @@ class TrainBatch:
             raise TypeError('capture needs jitter as a contiguous [B, 2] int64 device tensor (or None): the graph reads it in place')
         return clips
 
-    def _record(self, dev, chain, optimizer, hold):
+    def _record(self, dev, chain, optimizer, hold, rng=None):
         """The check of ``optimizer`` and the recipe of ``capture``: ``chain(alias)`` queues front end, head and loss on torch's current
-        stream with the parameter aliases standing in, and returns the namespace of ``run``."""
+        stream with the parameter aliases standing in, and returns the namespace of ``run``.  ``rng``: the generator the chain
+        advances; the warm-up steps move it, so its state is put back behind them (recording runs nothing)."""
         import torch
         from .classifier import _NativeHandle
         names = [n for n, p in self.head.named_parameters() if p.requires_grad]
@@ -270,6 +284,7 @@ class TrainBatch:
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             leaves = [p.detach().requires_grad_(True) for p in params]      # aliases: the optimiser's writes to p are theirs
+            rng_state = None if rng is None else rng.state.clone()
         alias = dict(zip(names, leaves))
 
         def step(record):
@@ -291,6 +306,8 @@ class TrainBatch:
                     for v in leaves:
                         v.grad = None
                     warm = step(False)
+                if rng is not None:
+                    rng.state.copy_(rng_state)
             side.synchronize()
             del warm
             for v in leaves:
@@ -303,7 +320,7 @@ class TrainBatch:
             p.grad = None
         if optimizer is not None:
             optimizer._bound = bound                           # the recorded binding has not run yet
-        return _CapturedStep(graph, result, params, grads, list(hold) + [leaves], optimizer)
+        return _CapturedStep(graph, result, params, grads, list(hold) + [leaves], optimizer, rng)
 
 
 class MixedRateTrainBatch(TrainBatch):
@@ -324,6 +341,7 @@ class MixedRateTrainBatch(TrainBatch):
 
     def _mixed_chain(self, clips, arena, labels, use_jitter, head_kwargs, alias=None):
         import torch
+        _advance_rng(head_kwargs)
         inp, len0, endpoints = self.features._outputs(arena.B, clips.device)
         self.features.enqueue(clips, arena, inp, len0, endpoints, use_jitter, torch.cuda.current_stream(clips.device))
         ns = self._head_loss(inp, len0, labels, head_kwargs, alias, [clips, arena, labels])
@@ -364,7 +382,7 @@ class MixedRateTrainBatch(TrainBatch):
         arena.write(sample_offsets, rates, jitter)
         use_jitter = jitter is not None
         g = self._record(waves.device, lambda alias: self._mixed_chain(clips, arena, labels, use_jitter, head_kwargs, alias), optimizer,
-                         [arena, clips, labels])
+                         [arena, clips, labels], head_kwargs.get('rng'))
         g.sample_offsets, g.rates, g.status = arena.sample_offsets, arena.rates, arena.status
         g.jitter = arena.jitter if use_jitter else None
         return g

@@ -1225,6 +1225,45 @@ int dsp_svm_fit_batch(const double* d_X, int64_t ld, int32_t n, int32_t F, const
                       int32_t max_iter, double* d_coef, int64_t ld_coef, double* d_rho, int32_t* d_info, void* d_work,
                       int64_t work_bytes, void* stream);
 
+/* ---- reproducible dropout: the F.dropout calls and nn.GRU's inter-layer dropout of rnn_clf.py, drawn on the device (csrc/kernels_dropout.h) ----
+ *
+ * A counter-based generator whose whole state is d_state = {seed, step}: two int64 words in device memory, 8-byte aligned,
+ * read when a launch RUNS.  A multiplier is a pure function of (seed, step, site, element_index):
+ *   Philox4x32 with 10 rounds (Salmon et al., SC'11: multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85);
+ *   key = (seed_lo, seed_hi);  counter = (block, step_lo, step_hi, site),  block = element_index / 4;  the four output words
+ *   serve elements 4 block .. 4 block + 3 in order.  element_index is the row-major index into the logical tensor, whatever
+ *   the row bound, the alignment or the launch shape.  site: a small integer >= 0 that names the draw site.
+ *   An element is kept iff (word >> 8) < thr, thr = llrint((1 - p) 2^24) in double; a kept element is multiplied by
+ *   scale = (float)(1.0 / (1.0 - (double)p)), a dropped one becomes exact +0.0f.  p in [0, 1); p = 0 returns the input's bits.
+ * The eager step and a graph replay therefore draw the same bits, a backward regenerates the mask instead of storing it, and
+ * the state is 16 bytes of a checkpoint.  No atomics, no LDS, no memset, no allocation, nothing synchronised: every launch goes
+ * to `stream` and is capturable; every element belongs to exactly one lane.
+ *
+ * dsp_rng_advance:         one thread: step += 1.
+ * dsp_dropout_apply:       d_y[i] = d_x[i] * m[i], i < n.  16-byte accesses where d_x and d_y are both 16-byte aligned, 4-byte
+ *                          ones for any other view and for the tail n % 4: the route never changes the bits.  d_y == d_x is
+ *                          served; a partial overlap is refused.  d_key_out: NULL, or 16 bytes (8-byte aligned, apart from
+ *                          every other argument) that receive the {seed, step} the launch used.
+ * dsp_dropout_apply_key:   the same arithmetic keyed by a saved d_key (what d_key_out received): a backward multiplies the
+ *                          incoming gradient by the forward's mask even when the state has advanced since.
+ * dsp_dropout_multipliers: the fp32 multipliers d_m [L, T, B, C] (0 or scale) that dsp_bigru_forward_train takes as d_drop
+ *                          (L = n_layers - 1, C = 2 H): layer l draws at site site_base + l with element_index over [T, B, C].
+ *                          Rows t < R = clamp(d_rows[0], 1, T) are drawn (d_rows NULL: all T rows); every element of the rows
+ *                          behind is written as exact +0.0f by a plain store and draws nothing.  EVERY element of d_m is
+ *                          written on every call; the rows t < R are bit for bit those of the unbounded call.
+ *
+ * LIMITS: n in [0, 2^34) and T B C < 2^34 (block is one 32-bit word); L in [1, 64]; T, B, C >= 1; site and site_base + L below
+ * 2^31; tensors 4-byte aligned, d_state / d_key / d_key_out 8-byte aligned; an output must not overlap d_state or d_rows.
+ * Anything else or a NULL mandatory pointer is DSP_EINVAL with a message before any launch; under dsp_debug_host_dry_run(1)
+ * what passed every check is refused instead of launched.
+ */
+int dsp_rng_advance(int64_t* d_state, void* stream);
+int dsp_dropout_apply(const float* d_x, float* d_y, int64_t n, double p, int32_t site, const int64_t* d_state, int64_t* d_key_out,
+                      void* stream);
+int dsp_dropout_apply_key(const float* d_g, float* d_dx, int64_t n, double p, int32_t site, const int64_t* d_key, void* stream);
+int dsp_dropout_multipliers(float* d_m, int32_t L, int32_t T, int32_t B, int32_t C, double p, int32_t site_base, const int64_t* d_state,
+                            const int32_t* d_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
