@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "dsp_common.h"
+#include "softmax_row.h"
 
 #define SVM_MAX_FEATURES 16
 #define SVM_MAX_SV 65536
@@ -47,13 +48,6 @@ struct EnsParams {
     int32_t* used;
     double* decision;
 };
-
-// Sum over the 64 lanes in a fixed order (the xor butterfly: every lane ends with the same bits, on every call).
-__device__ __forceinline__ double ens_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // dec(x) = sum_i dual_i exp(-gamma |(x - center) / scale - sv_i|^2) + intercept for the row at `x`, by one whole wave:
 // every lane scales the row (a true division, as RobustScaler.transform), lanes stride over the support vectors -- the
@@ -105,14 +99,9 @@ __global__ __launch_bounds__(64 * ENS_ROWS_PER_BLOCK) void ensemble_decide_kerne
     if (b >= P.n_utt) return;
     const bool mine = lane < P.C;
     const float lf = mine ? P.logits[b * P.ld_logits + lane] : -INFINITY;
-    float mx = lf;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    const unsigned long long at_max = __ballot(mine && lf == mx);
-    const int pred = at_max ? __ffsll(at_max) - 1 : 0;          // (no lane compares equal only if a logit is NaN)
-    const double e = mine ? exp((double)lf - (double)mx) : 0.0;
-    const double s = ens_wave_sum(e);
-    const float p = (float)(e / s);
+    const RowSoftmax sm = row_softmax_wave(lf, mine);          // softmax_row.h: shared with the loss kernels, bit for bit
+    const int pred = sm.pred;
+    const float p = sm.p;
     if (P.prob != nullptr && mine) P.prob[b * P.C + lane] = p;
     const double p_pred = (double)__shfl(p, pred, 64);
     int fired = -1;

@@ -18,6 +18,8 @@ state on the device, recordable behind the backward (features/optim.py).  ``Mixe
 serve mixed-rate batches of any lengths and rate assignments through one recorded launch sequence: the grouping by rate is device work.
 ``DeviceRng`` and ``device_dropout`` (features/dropout.py) draw the heads' dropouts from a counter-based generator on the device:
 the heads' ``rng=`` keyword makes an eager step and a graph replay draw the same multipliers.
+``Metrics`` and ``cross_entropy`` (features/metrics.py) keep the loss, its gradient, the accuracy, the confusion matrix and the
+list of wrong clips on the device, and ``Trainer`` (features/fit.py) is model.py's ``train`` mode with one download per epoch.
 There is no CPU fallback: without the built library or without a GPU every compute call raises.
 """
 from .base import *  # noqa: F401,F403
@@ -28,7 +30,7 @@ from .pitch import (center_clip, max_pitch, pitch_detect_frame_sr, pitch_detect_
                     robust_max_pitch, smooth, window, pitch_detect, pitch_detect_frame, peak_score,
                     sub_endpoint_detect, find_smooth_subsequence, slope, quad_params, peakshift, pitch_feature,
                     pitch_feature_batch, pitch_features_device)
-from . import base, sigproc, endpoint, preprocess, pitch, batch, pipeline, ensemble, train, optim, svmfit, dropout  # noqa: F401
+from . import base, sigproc, endpoint, preprocess, pitch, batch, pipeline, ensemble, train, optim, svmfit, dropout, metrics, fit  # noqa: F401
 from .batch import FeaturePlan, EndpointPlan  # noqa: F401
 from .pipeline import VadMfccPipeline  # noqa: F401
 from .ensemble import PitchSVM, EnsembleBatch, MixedRateEnsembleBatch, ensemble_decide  # noqa: F401
@@ -37,3 +39,5 @@ from .svmfit import fit_pitch_svm, grid_search, robust_scale_fit, svm_fit_proble
 from .train import TrainBatch, MixedRateTrainBatch  # noqa: F401
 from .optim import DeviceAdam  # noqa: F401
 from .dropout import DeviceRng, device_dropout  # noqa: F401
+from .metrics import Metrics, cross_entropy  # noqa: F401
+from .fit import Trainer  # noqa: F401

@@ -218,6 +218,10 @@ SIGNATURES = {
     'dsp_dropout_apply': (C.c_int, [c_vp, c_vp, c_i64, c_f64, c_i32, c_vp, c_vp, c_vp]),
     'dsp_dropout_apply_key': (C.c_int, [c_vp, c_vp, c_i64, c_f64, c_i32, c_vp, c_vp]),
     'dsp_dropout_multipliers': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp]),
+    'dsp_metrics_bytes': (C.c_int, [c_i32, c_i32, C.POINTER(c_i64)]),
+    'dsp_metrics_reset': (C.c_int, [c_vp, c_i32, c_i32, c_vp]),
+    'dsp_xent_metrics_batch': (C.c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32,
+                                         c_vp]),
 }
 
 _lib = None

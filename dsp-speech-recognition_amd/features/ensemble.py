@@ -247,6 +247,16 @@ def ensemble_decide(logits, rules, feat=None, valid=None, stream=None):
     return pred, prob, used, dec
 
 
+def _capture_scored(waves, prepare, score):
+    """``_capture``; the warm call in front of the recording scores a batch, so the metrics block is put back behind it."""
+    if score is None:
+        return _capture(waves, prepare)
+    saved = score[1].state.clone()
+    g = _capture(waves, prepare)                          # (it synchronises its side stream behind the warm call)
+    score[1].state.copy_(saved)
+    return g
+
+
 def _segments_tensor(lay, dev):
     """The segment table [B, 2] int64 of a pipeline layout THIS module owns, as a torch tensor (swapped in on first use; no
     launch of the layout is in flight then: a fresh layout has none, a cached one is swapped before its first launch)."""
@@ -262,18 +272,38 @@ def _logits_of(out):
     return logits.detach().to(torch.float32)
 
 
+def _score_spec(labels, metrics, device_route):
+    """The ``labels=`` / ``metrics=`` keywords of ``run`` and ``capture`` -> (labels, metrics) or None; refusals need no device."""
+    if labels is None and metrics is None:
+        return None
+    if not device_route:
+        raise ValueError('labels= / metrics= are served by run(sync_free=True), run(capacity=) and capture(): the downloading run() '
+                         'has a host round trip already, score its result on the host')
+    if labels is None or metrics is None:
+        raise ValueError('labels= and metrics= go together: the labels to score against and the features.metrics.Metrics to update')
+    from .metrics import Metrics
+    if not isinstance(metrics, Metrics):
+        raise TypeError(f'metrics must be a features.metrics.Metrics, not {type(metrics).__name__}')
+    import torch
+    if not (_is_device_tensor(labels) and labels.dtype == torch.int64 and labels.dim() == 1 and labels.is_contiguous()):
+        raise TypeError('labels must be a contiguous [B] int64 device tensor: it is read in place (on every replay of a graph)')
+    return labels, metrics
+
+
 class _EnsembleTail:
     """What ``EnsembleBatch`` and ``MixedRateEnsembleBatch`` (``head``, ``rules``, ``coeff``) share: everything behind the
     front end's launches."""
 
-    def _tail(self, inp, d_len0, host, groups, head_kwargs, arenas=None):
+    def _tail(self, inp, d_len0, host, groups, head_kwargs, arenas=None, score=None):
         """The head, per rate group the pre-emphasised trim and the five pitch features, ONE gate launch over the batch, and
         the namespace of ``run`` -- launches on torch's current stream.  ``host``: the (len0, endpoints) arrays the front
         end downloaded, or None: they stay on the device -- the head is called with ``device_len=True`` on ``d_len0``,
         ``n_clamped`` counts what it had to clamp, and torch copies the endpoints from the groups' segment tables
         (``_segments_tensor``).  ``groups``: (layout, contiguous wave tensor, rate, d_index) per rate; ``d_index``: the
         group's batch positions (int32 device tensor), or None where the group is the whole batch and its rows are written
-        in place.  ``arenas``: one dict per group for the pitch chain's buffers, or None for library scratch."""
+        in place.  ``arenas``: one dict per group for the pitch chain's buffers, or None for library scratch.  ``score``:
+        ``_score_spec``'s pair or None: ONE more launch behind the gate scores ``pred`` -- the ensemble's label -- against the labels
+        and takes the loss from ``logits`` (``Metrics.update``)."""
         import torch
         from .pitch import N_AUX, pitch_features_device
         lib = nat.load()
@@ -310,6 +340,8 @@ class _EnsembleTail:
             trimmed.append(trim)
         valid = aux[:, N_AUX - 1]
         pred, prob, used, dec = ensemble_decide(logits, self.rules, feat, valid, stream=st)
+        if score is not None:
+            score[1].update(logits, score[0], pred)
         if host is None:
             endpoints = torch.empty((B, 2), dtype=torch.int64, device=dev)
             for lay, _, _, d_index in groups:
@@ -348,8 +380,10 @@ class EnsembleBatch(_EnsembleTail):
         self._layouts[key] = lay
         return lay
 
-    def run(self, waves, sample_offsets, sync_free=False, capacity=None, **head_kwargs):
-        """``capacity=N``: the sync-free chain on a capacity layout cached per (B, N) -- the launches ``capture(...,
+    def run(self, waves, sample_offsets, sync_free=False, capacity=None, labels=None, metrics=None, **head_kwargs):
+        """``labels=`` (int64 [B] device tensor) with ``metrics=`` (a ``features.metrics.Metrics``), on the sync-free routes only: one
+        more launch behind the gate scores ``pred`` against the labels and adds the loss of ``logits`` to the epoch state.
+        ``capacity=N``: the sync-free chain on a capacity layout cached per (B, N) -- the launches ``capture(...,
         capacity=N)`` records, queued eagerly: ``waves`` is a contiguous device tensor of exactly N samples (ValueError
         otherwise), ``sample_offsets`` ([B + 1], host array or device tensor) any B lengths >= 1 that sum to at most N; no
         layout is built, uploaded or synchronised per batch shape.  ``status`` (int32 [1]) is added to the namespace.
@@ -362,6 +396,7 @@ class EnsembleBatch(_EnsembleTail):
         features/classifier.py's), ``len0`` (int32) and ``endpoints`` are device tensors, and ``n_clamped`` (int32 [1]) counts
         the lengths the head had to clamp."""
         import torch
+        score = _score_spec(labels, metrics, sync_free or capacity is not None)
         nat.require_device()
         if capacity is not None:
             from .pipeline import check_capacity_wave
@@ -370,7 +405,7 @@ class EnsembleBatch(_EnsembleTail):
             B = int(sample_offsets.shape[0] if torch.is_tensor(sample_offsets) else len(sample_offsets)) - 1
             lay = self.features.pipe._capacity_layout(B, capacity, 0)
             lay.write_offsets(sample_offsets)
-            ns = self._chain(waves, lay, self._m0(lay, waves.device), None, head_kwargs)
+            ns = self._chain(waves, lay, self._m0(lay, waves.device), None, head_kwargs, score)
             ns.status = lay.status
             return ns
         so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
@@ -384,7 +419,7 @@ class EnsembleBatch(_EnsembleTail):
         _wave_dtype_of(clips)                              # TypeError for anything but int16 / float32
         lay = self._layout(so)
         if sync_free:
-            return self._chain(clips, lay, self._m0(lay, clips.device), None, head_kwargs)
+            return self._chain(clips, lay, self._m0(lay, clips.device), None, head_kwargs, score)
         inp, len0, endpoints = self.features.run(clips, layout=lay)
         return self._tail(inp, None, (len0, endpoints), [(lay, clips, self.rate, None)], head_kwargs)
 
@@ -422,7 +457,7 @@ class EnsembleBatch(_EnsembleTail):
         _segments_tensor(lay, dev)
         return torch.empty((max(lay.frames_bound, 1), self.features.pipe.features.C), dtype=torch.float32, device=dev)
 
-    def _chain(self, clips, lay, m0, arena, head_kwargs):
+    def _chain(self, clips, lay, m0, arena, head_kwargs, score=None):
         """The whole path as launches on torch's current stream, nothing synchronised, no device memory read from the host:
         front end (``ModelFeatureBatch.enqueue``), then ``_tail`` with the lengths on the device.  ``lay`` / ``m0``: a layout
         of this object and its scratch (``_m0``); ``arena``: the pitch chain's buffers (None: library scratch, for an eager
@@ -433,10 +468,12 @@ class EnsembleBatch(_EnsembleTail):
         len0 = torch.empty(B, dtype=torch.int32, device=dev)
         mfb.enqueue(clips.data_ptr(), _wave_dtype_of(clips), lay, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(),
                     torch.cuda.current_stream(dev))
-        return self._tail(inp, len0, None, [(lay, clips, self.rate, None)], head_kwargs, None if arena is None else [arena])
+        return self._tail(inp, len0, None, [(lay, clips, self.rate, None)], head_kwargs, None if arena is None else [arena], score)
 
-    def capture(self, waves, sample_offsets, capacity=None, **head_kwargs):
-        """ONE HIP graph of the whole path over device-resident ``waves`` (a contiguous tensor, int16 / float32):
+    def capture(self, waves, sample_offsets, capacity=None, labels=None, metrics=None, **head_kwargs):
+        """``labels=`` / ``metrics=`` as ``run``: the scoring launch is recorded behind the gate, ``labels`` is read in place on every
+        replay, and ``capture`` itself leaves the metrics block as it found it.
+        ONE HIP graph of the whole path over device-resident ``waves`` (a contiguous tensor, int16 / float32):
         ``g = eb.capture(waves, so, dropout=False)``; write new clips into ``waves`` -- of the same lengths, unless the graph
         was recorded with ``capacity=`` -- and call
         ``g.replay()`` -> the namespace of ``run(sync_free=True)``, every field a device tensor, valid after the current
@@ -453,6 +490,7 @@ class EnsembleBatch(_EnsembleTail):
         sanitised offsets, the frame offsets, the VAD kernel's index tables -- is rebuilt by two launches at the head of the
         recorded sequence (``CapacityLayout``); every grid and buffer behind is sized by the capacity."""
         box = []
+        score = _score_spec(labels, metrics, True)
 
         def prepare():
             nat.require_device()
@@ -470,8 +508,8 @@ class EnsembleBatch(_EnsembleTail):
                 lay.write_offsets(so)
                 box.append(lay)
             m0, arena = self._m0(lay, waves.device), {}
-            return (lambda: self._chain(clips, lay, m0, arena, head_kwargs)), [lay, m0, arena, clips, list(self.rules)]
-        g = _capture(waves, prepare)
+            return (lambda: self._chain(clips, lay, m0, arena, head_kwargs, score)), [lay, m0, arena, clips, list(self.rules), score]
+        g = _capture_scored(waves, prepare, score)
         if box:
             g.sample_offsets, g.status = box[0].sample_offsets_in, box[0].status
         return g
@@ -488,13 +526,15 @@ class MixedRateEnsembleBatch(_EnsembleTail):
         self.head, self.rules, self.coeff = head, list(rules), float(coeff)
         self.features = MixedRateFeatureBatch(frame=frame, step=step)
 
-    def run(self, waves, sample_offsets=None, rates=None, sync_free=False, capacity=None, **head_kwargs):
-        """``capacity=``: NotImplementedError (``MixedRateFeatureBatch.capture`` says why).
+    def run(self, waves, sample_offsets=None, rates=None, sync_free=False, capacity=None, labels=None, metrics=None, **head_kwargs):
+        """``labels=`` / ``metrics=`` as ``EnsembleBatch.run`` (with ``sync_free=True``).
+        ``capacity=``: NotImplementedError (``MixedRateFeatureBatch.capture`` says why).
         ``waves`` / ``sample_offsets`` / ``rates`` as MixedRateFeatureBatch.run.  Returns the namespace of EnsembleBatch.run,
         every row in batch order; ``sync_free=True`` as there (device input: no synchronisation once the plan of the batch
         shape exists)."""
         from .model_glue import _no_mixed_capacity
         _no_mixed_capacity(capacity)
+        score = _score_spec(labels, metrics, sync_free)
         mr = self.features
         if sync_free:
             import torch
@@ -502,25 +542,25 @@ class MixedRateEnsembleBatch(_EnsembleTail):
             on_device = _is_device_tensor(clips)
             dev = clips.device if on_device else torch.device('cuda', nat.current_device())
             plan = mr._plan(so, r, dev, on_device)       # this object's: its segment tables become torch's before the launches
-            return self._chain(waves, so, r, plan, dev, None, head_kwargs)
+            return self._chain(waves, so, r, plan, dev, None, head_kwargs, score)
         ctx = mr._launch(waves, sample_offsets, rates)
         return self._after(ctx, mr._finish(ctx), head_kwargs, None)
 
-    def _after(self, ctx, host, head_kwargs, arenas):
+    def _after(self, ctx, host, head_kwargs, arenas, score=None):
         """``_tail`` behind the launches of ``MixedRateFeatureBatch._launch``: one contiguous device buffer per rate."""
         groups = [(g.lay, wave, g.rate, g.d_index) for g, wave in zip(ctx.plan.groups, ctx.group_waves)]
-        ns = self._tail(ctx.inp, ctx.len0, host, groups, head_kwargs, arenas)
+        ns = self._tail(ctx.inp, ctx.len0, host, groups, head_kwargs, arenas, score)
         ns._hold = ctx.hold                       # the temporaries of the launches (torch tensors: released in stream order)
         return ns
 
-    def _chain(self, waves, so, rates, plan, dev, arenas, head_kwargs):
+    def _chain(self, waves, so, rates, plan, dev, arenas, head_kwargs, score=None):
         """The whole path on ``plan`` with nothing synchronised: the lengths and the endpoints stay on the device."""
         for g in plan.groups:
             _segments_tensor(g.lay, dev)
-        return self._after(self.features._launch(waves, so, rates, plan=plan), None, head_kwargs, arenas)
+        return self._after(self.features._launch(waves, so, rates, plan=plan), None, head_kwargs, arenas, score)
 
-    def capture(self, waves, sample_offsets, rates, capacity=None, **head_kwargs):
-        """``EnsembleBatch.capture`` for a mixed-rate batch: ONE HIP graph of the front end's sub-pipelines (queued one after
+    def capture(self, waves, sample_offsets, rates, capacity=None, labels=None, metrics=None, **head_kwargs):
+        """``labels=`` / ``metrics=`` as ``EnsembleBatch.capture``.  ``EnsembleBatch.capture`` for a mixed-rate batch: ONE HIP graph of the front end's sub-pipelines (queued one after
         the other: a chain, no forked branches), the head with ``device_len=True``, and per rate group the trim and the pitch
         features, then the gate.  ``waves``: a contiguous 1-D device tensor (a non-contiguous one raises ValueError);
         ``replay()`` -> the namespace of ``run(sync_free=True)``, rows in batch order.  The graph object owns the plan, every
@@ -530,10 +570,12 @@ class MixedRateEnsembleBatch(_EnsembleTail):
         stays bound to its lengths and rates (``MixedRateFeatureBatch.capture``)."""
         from .model_glue import _MixedPlan, _no_mixed_capacity
         _no_mixed_capacity(capacity)
+        score = _score_spec(labels, metrics, True)
 
         def prepare():
             _, so, r = self.features._inputs(waves, sample_offsets, rates)
             plan = _MixedPlan(self.features, so, r, waves.device, True)    # the graph's own: nothing else writes its tables
             arenas = [{} for _ in plan.groups]
-            return (lambda: self._chain(waves, so, r, plan, waves.device, arenas, head_kwargs)), [plan, arenas, list(self.rules)]
-        return _capture(waves, prepare)
+            return (lambda: self._chain(waves, so, r, plan, waves.device, arenas, head_kwargs, score)), [plan, arenas, list(self.rules),
+                                                                                                        score]
+        return _capture_scored(waves, prepare, score)

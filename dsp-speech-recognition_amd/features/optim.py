@@ -135,6 +135,16 @@ class DeviceAdam:
         device's copy, nothing else but this object's mirror."""
         self._set_hyper(lr, self.betas, self.eps)
 
+    def reset(self):
+        """A fresh Adam in place (model.py:140 makes a new one every epoch; a recorded step is bound to this one): the step
+        count to 0 and both moments to zero, on the current stream.  Addresses, hyper-parameters and the gradient binding stay,
+        so a recorded step goes on replaying, and the next step equals the first step of a new ``DeviceAdam``."""
+        import torch
+        with torch.cuda.device(self.device):
+            nat.check_value(nat.load().dsp_adam_set_step(self._handle, 0, self._stream()), 'dsp_adam_set_step')
+        with torch.no_grad():
+            torch._foreach_zero_(self.exp_avg + self.exp_avg_sq)
+
     def device_state(self):
         """-> (step, lr, beta1, beta2, eps) as the device holds them.  Synchronises the current stream."""
         import torch

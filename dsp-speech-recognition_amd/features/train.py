@@ -42,6 +42,19 @@ def _logits_of(out):
     return out[0] if isinstance(out, (tuple, list)) else out
 
 
+def _loss_spec(loss, metrics):
+    """The ``loss=`` / ``metrics=`` keywords of ``run`` and ``capture`` -> (native?, metrics); refusals need no device."""
+    if loss not in ('torch', 'native'):
+        raise ValueError(f"loss must be 'torch' or 'native', got {loss!r}")
+    if metrics is not None:
+        if loss != 'native':
+            raise ValueError("metrics= needs loss='native': the device metrics are updated by the native loss call")
+        from .metrics import Metrics
+        if not isinstance(metrics, Metrics):
+            raise TypeError(f'metrics must be a features.metrics.Metrics, not {type(metrics).__name__}')
+    return loss == 'native', metrics
+
+
 class _CapturedStep:
     """What ``TrainBatch.capture`` returns.  ``replay()`` re-runs the recorded step on whatever the captured buffers hold now
     and returns ``result`` (loss, logits, inp, len0, n_clamped: device tensors, valid after the current stream's work; nothing
@@ -122,7 +135,7 @@ class TrainBatch:
             raise ValueError(f'jitter must be [B, 2] = [{B}, 2], got {tuple(jitter.shape)}')
         return jitter
 
-    def _chain(self, clips, lay, m0, labels, d_jit, head_kwargs, alias=None):
+    def _chain(self, clips, lay, m0, labels, d_jit, head_kwargs, alias=None, spec=(False, None)):
         """Front end, head, loss: launches on torch's current stream, nothing synchronised, no device memory read from the
         host.  ``alias``: name -> tensor to stand in for the head's parameters during the call (``capture``)."""
         import torch
@@ -132,10 +145,10 @@ class TrainBatch:
         len0 = torch.empty(B, dtype=torch.int32, device=dev)
         mfb.enqueue(clips.data_ptr(), _wave_dtype_of(clips), lay, m0.data_ptr(), inp.data_ptr(), len0.data_ptr(),
                     torch.cuda.current_stream(dev), d_jitter=None if d_jit is None else d_jit.data_ptr())
-        return self._head_loss(inp, len0, labels, head_kwargs, alias, [clips, lay, m0, labels, d_jit])
+        return self._head_loss(inp, len0, labels, head_kwargs, alias, [clips, lay, m0, labels, d_jit], spec)
 
-    def _head_loss(self, inp, len0, labels, head_kwargs, alias, hold):
-        """The chain from ``inp`` / ``len0`` on: head, loss, the count of clamped lengths."""
+    def _head_loss(self, inp, len0, labels, head_kwargs, alias, hold, spec=(False, None)):
+        """The chain from ``inp`` / ``len0`` on: head, loss, the count of clamped lengths.  ``spec``: ``_loss_spec``'s pair."""
         import torch
         from .classifier import head_length_info
         kw = dict(device_len=True, device_grad=True, **head_kwargs)
@@ -144,12 +157,19 @@ class TrainBatch:
         else:
             out = torch.func.functional_call(self.head, alias, (inp, len0), kw)
         logits = _logits_of(out)
-        loss = torch.nn.functional.cross_entropy(logits, labels)                        # model.py:141-147
+        if spec[0]:                                                                     # one native call, the metrics with it
+            from .metrics import cross_entropy
+            loss = cross_entropy(logits, labels, spec[1])
+        else:
+            loss = torch.nn.functional.cross_entropy(logits, labels)                    # model.py:141-147
         n_clamped = head_length_info(len0, inp.shape[0], 1)[2][2:3]
         return types.SimpleNamespace(loss=loss, logits=logits, inp=inp, len0=len0, n_clamped=n_clamped, _hold=hold)
 
-    def run(self, waves, sample_offsets, labels, jitter=None, capacity=None, **head_kwargs):
-        """``capacity=N``: the same chain on a capacity layout cached per (B, N) -- the launches ``capture(..., capacity=N)``
+    def run(self, waves, sample_offsets, labels, jitter=None, capacity=None, loss='torch', metrics=None, **head_kwargs):
+        """``loss='native'``: the loss is ``features.metrics.cross_entropy`` -- one native call for the loss and its gradient -- in
+        place of ``F.cross_entropy``; ``metrics=`` (a ``features.metrics.Metrics``, with ``loss='native'`` only) is updated by the
+        same call.  ``loss='torch'``, the default, launches what it launched.
+        ``capacity=N``: the same chain on a capacity layout cached per (B, N) -- the launches ``capture(..., capacity=N)``
         records: ``waves`` is a contiguous device tensor of exactly N samples (ValueError otherwise), ``sample_offsets``
         ([B + 1], host array or device tensor) any B lengths >= 1 that sum to at most N; no layout is built or uploaded per
         batch shape.  ``status`` (int32 [1]) is added to the namespace.
@@ -161,6 +181,7 @@ class TrainBatch:
         Nothing is synchronised and no device memory is read from the host: the caller calls ``loss.backward()`` and then
         its optimiser -- the head's native handles survive the step (they are repacked in place by the next call)."""
         import torch
+        spec = _loss_spec(loss, metrics)
         nat.require_device()
         if capacity is not None:
             from .pipeline import check_capacity_wave
@@ -170,7 +191,8 @@ class TrainBatch:
             B = int(sample_offsets.shape[0] if torch.is_tensor(sample_offsets) else len(sample_offsets)) - 1
             lay = self.features.pipe._capacity_layout(B, capacity, 0)
             lay.write_offsets(sample_offsets)
-            ns = self._chain(waves, lay, self._m0(lay, dev), self._labels(labels, B, dev), self._jitter(jitter, B, dev), head_kwargs)
+            ns = self._chain(waves, lay, self._m0(lay, dev), self._labels(labels, B, dev), self._jitter(jitter, B, dev), head_kwargs,
+                             spec=spec)
             ns.status = lay.status
             return ns
         so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
@@ -182,10 +204,14 @@ class TrainBatch:
         _wave_dtype_of(clips)                              # TypeError for anything but int16 / float32
         dev, B = clips.device, len(so) - 1
         lay = self._layout(so)
-        return self._chain(clips, lay, self._m0(lay, dev), self._labels(labels, B, dev), self._jitter(jitter, B, dev), head_kwargs)
+        return self._chain(clips, lay, self._m0(lay, dev), self._labels(labels, B, dev), self._jitter(jitter, B, dev), head_kwargs,
+                           spec=spec)
 
-    def capture(self, waves, sample_offsets, labels, jitter=None, optimizer=None, capacity=None, **head_kwargs):
-        """ONE HIP graph of a whole step; without ``optimizer`` all of it but the optimiser: ``g = tb.capture(waves, so, labels, jitter, dropout=False)``;
+    def capture(self, waves, sample_offsets, labels, jitter=None, optimizer=None, capacity=None, loss='torch', metrics=None,
+                **head_kwargs):
+        """``loss='native'`` / ``metrics=`` as ``run``: the recorded loss is the native call, its backward launches nothing of its
+        own, and every replay updates ``metrics`` (``capture`` itself leaves the block as it found it).
+        ONE HIP graph of a whole step; without ``optimizer`` all of it but the optimiser: ``g = tb.capture(waves, so, labels, jitter, dropout=False)``;
         ``g.replay()`` does, in order, (1) a refresh of every native handle of the head -- the repack of whatever the
         optimiser wrote since the last replay --, (2) the front end, (3) the forward, (4) the loss and (5) the backward into
         ``.grad`` tensors the graph owns (``g.grads``), which every replay overwrites.  It returns the namespace of ``run``.
@@ -224,6 +250,7 @@ class TrainBatch:
         has been seen to go wrong on replay on this stack, so a head / size pair is recorded only where
         tests/test_gpu_train_capture.py has compared a second replay with the eager step bit for bit.  Anything else raises
         NotImplementedError; ``run`` serves every head and size."""
+        spec = _loss_spec(loss, metrics)
         so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
         B = len(so) - 1
         clips = self._check_capture(waves, B, labels, jitter)
@@ -236,8 +263,8 @@ class TrainBatch:
             lay = self.features.pipe.prepare_capacity(B, capacity, 0)
             lay.write_offsets(so)
         m0 = self._m0(lay, dev)
-        g = self._record(dev, lambda alias: self._chain(clips, lay, m0, labels, jitter, head_kwargs, alias), optimizer,
-                         [lay, m0, clips, labels, jitter], head_kwargs.get('rng'))
+        g = self._record(dev, lambda alias: self._chain(clips, lay, m0, labels, jitter, head_kwargs, alias, spec), optimizer,
+                         [lay, m0, clips, labels, jitter], head_kwargs.get('rng'), spec)
         if capacity is not None:
             g.sample_offsets, g.status = lay.sample_offsets_in, lay.status
         return g
@@ -263,10 +290,12 @@ class TrainBatch:
             raise TypeError('capture needs jitter as a contiguous [B, 2] int64 device tensor (or None): the graph reads it in place')
         return clips
 
-    def _record(self, dev, chain, optimizer, hold, rng=None):
+    def _record(self, dev, chain, optimizer, hold, rng=None, spec=(False, None)):
         """The check of ``optimizer`` and the recipe of ``capture``: ``chain(alias)`` queues front end, head and loss on torch's current
         stream with the parameter aliases standing in, and returns the namespace of ``run``.  ``rng``: the generator the chain
-        advances; the warm-up steps move it, so its state is put back behind them (recording runs nothing)."""
+        advances; the warm-up steps move it, so its state is put back behind them (recording runs nothing).  ``spec``:
+        ``_loss_spec``'s pair; the metrics block is put back like the generator, and a native loss is differentiated from
+        ``features.metrics.unit_grad``."""
         import torch
         from .classifier import _NativeHandle
         names = [n for n, p in self.head.named_parameters() if p.requires_grad]
@@ -285,6 +314,11 @@ class TrainBatch:
         with torch.cuda.stream(side):
             leaves = [p.detach().requires_grad_(True) for p in params]      # aliases: the optimiser's writes to p are theirs
             rng_state = None if rng is None else rng.state.clone()
+            native, metrics = spec
+            metrics_state = None if metrics is None else metrics.state.clone()
+            if native:
+                from .metrics import backward as native_backward, unit_grad
+                unit_grad(dev)                                 # (made here, not while recording)
         alias = dict(zip(names, leaves))
 
         def step(record):
@@ -294,7 +328,10 @@ class TrainBatch:
                         m._native_handle(dev, refresh='always')
             out = chain(alias)
             with torch.autograd.set_multithreading_enabled(False):      # every recorded launch comes from the capturing thread
-                out.loss.backward()
+                if native:
+                    native_backward(out.loss)
+                else:
+                    out.loss.backward()
             if record and optimizer is not None:               # the graph's own gradients: their addresses are known from here on
                 optimizer._launch([v.grad for v in leaves], False, rebind='always')
             out.loss, out.logits = out.loss.detach(), out.logits.detach()
@@ -308,6 +345,8 @@ class TrainBatch:
                     warm = step(False)
                 if rng is not None:
                     rng.state.copy_(rng_state)
+                if metrics is not None:
+                    metrics.state.copy_(metrics_state)
             side.synchronize()
             del warm
             for v in leaves:
@@ -320,7 +359,7 @@ class TrainBatch:
             p.grad = None
         if optimizer is not None:
             optimizer._bound = bound                           # the recorded binding has not run yet
-        return _CapturedStep(graph, result, params, grads, list(hold) + [leaves], optimizer, rng)
+        return _CapturedStep(graph, result, params, grads, list(hold) + [leaves, metrics], optimizer, rng)
 
 
 class MixedRateTrainBatch(TrainBatch):
@@ -339,20 +378,21 @@ class MixedRateTrainBatch(TrainBatch):
         """The endpoint offsets of model.py:54-60 for a batch with these [B] rates, in the reference's order: int64 [B, 2]."""
         return self.features.draw_jitter(rates, rng)
 
-    def _mixed_chain(self, clips, arena, labels, use_jitter, head_kwargs, alias=None):
+    def _mixed_chain(self, clips, arena, labels, use_jitter, head_kwargs, alias=None, spec=(False, None)):
         import torch
         _advance_rng(head_kwargs)
         inp, len0, endpoints = self.features._outputs(arena.B, clips.device)
         self.features.enqueue(clips, arena, inp, len0, endpoints, use_jitter, torch.cuda.current_stream(clips.device))
-        ns = self._head_loss(inp, len0, labels, head_kwargs, alias, [clips, arena, labels])
+        ns = self._head_loss(inp, len0, labels, head_kwargs, alias, [clips, arena, labels], spec)
         ns.endpoints, ns.status = endpoints, arena.status
         return ns
 
-    def run(self, waves, sample_offsets, rates, labels, jitter=None, capacity=None, **head_kwargs):
-        """``TrainBatch.run(..., capacity=N)`` with ``rates`` [B] beside the offsets (host arrays or device tensors): the launches
+    def run(self, waves, sample_offsets, rates, labels, jitter=None, capacity=None, loss='torch', metrics=None, **head_kwargs):
+        """``loss=`` / ``metrics=`` as ``TrainBatch.run``.  ``TrainBatch.run(..., capacity=N)`` with ``rates`` [B] beside the offsets (host arrays or device tensors): the launches
         ``capture`` records, on an arena cached per (B, N).  The namespace also carries ``endpoints`` (int64 [B, 2]) and
         ``status`` (``MixedRateCapacityBatch``: bit 4 = a rate outside the table)."""
         from .pipeline import check_capacity_wave
+        spec = _loss_spec(loss, metrics)
         nat.require_device()
         if capacity is None:
             raise ValueError('MixedRateTrainBatch serves capacity routes only: pass capacity=N')
@@ -363,15 +403,17 @@ class MixedRateTrainBatch(TrainBatch):
         labels, jitter = self._labels(labels, B, waves.device), self._jitter(jitter, B, waves.device)
         arena = fe._arena(B, capacity, waves)
         arena.write(sample_offsets, rates, jitter)
-        return self._mixed_chain(waves, arena, labels, jitter is not None, head_kwargs)
+        return self._mixed_chain(waves, arena, labels, jitter is not None, head_kwargs, spec=spec)
 
-    def capture(self, waves, sample_offsets, rates, labels, jitter=None, optimizer=None, capacity=None, **head_kwargs):
-        """``TrainBatch.capture(..., capacity=N)`` for a mixed-rate batch: ONE HIP graph of the handle refresh, the grouping
+    def capture(self, waves, sample_offsets, rates, labels, jitter=None, optimizer=None, capacity=None, loss='torch', metrics=None,
+                **head_kwargs):
+        """``loss=`` / ``metrics=`` as ``TrainBatch.capture``.  ``TrainBatch.capture(..., capacity=N)`` for a mixed-rate batch: ONE HIP graph of the handle refresh, the grouping
         front end, forward, loss, backward and -- with ``optimizer=`` -- the ``DeviceAdam`` step.  Before a ``replay()`` write
         the next batch's clips into ``waves``, its offsets into ``g.sample_offsets`` (int64 [B + 1]), its rates into ``g.rates``
         (int32 [B]), the labels into ``labels`` and -- if recorded with jitter -- its rows into ``g.jitter`` (int64 [B, 2]: the
         graph's own table, a copy of ``jitter`` as given here).  ``CAPTURE_VERIFIED`` governs the head / B pairs as before."""
         from .pipeline import check_capacity_wave
+        spec = _loss_spec(loss, metrics)
         fe = self.features
         B = fe._n_utt(sample_offsets)
         clips = self._check_capture(waves, B, labels, jitter)
@@ -381,8 +423,8 @@ class MixedRateTrainBatch(TrainBatch):
         arena = fe.prepare(B, capacity, waves)                 # the graph's own
         arena.write(sample_offsets, rates, jitter)
         use_jitter = jitter is not None
-        g = self._record(waves.device, lambda alias: self._mixed_chain(clips, arena, labels, use_jitter, head_kwargs, alias), optimizer,
-                         [arena, clips, labels], head_kwargs.get('rng'))
+        g = self._record(waves.device, lambda alias: self._mixed_chain(clips, arena, labels, use_jitter, head_kwargs, alias, spec),
+                         optimizer, [arena, clips, labels], head_kwargs.get('rng'), spec)
         g.sample_offsets, g.rates, g.status = arena.sample_offsets, arena.rates, arena.status
         g.jitter = arena.jitter if use_jitter else None
         return g

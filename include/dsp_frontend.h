@@ -1264,6 +1264,59 @@ int dsp_dropout_apply_key(const float* d_g, float* d_dx, int64_t n, double p, in
 int dsp_dropout_multipliers(float* d_m, int32_t L, int32_t T, int32_t B, int32_t C, double p, int32_t site_base, const int64_t* d_state,
                             const int32_t* d_rows, void* stream);
 
+/* ---- loss, its gradient and the epoch metrics on the device (csrc/kernels_loss.h) ----------------------------------------
+ *
+ * dsp_xent_metrics_batch turns [n_utt, n_classes] logits and labels into F.cross_entropy at its defaults (model.py:141-147),
+ * its gradient, the prediction of model.py:156-157 and the metrics RNNModel.test / EnsembleModel.test collect on the host
+ * (model.py:162-187, ensemble.py:44-64), accumulated in one caller-owned block.  At most TWO launches on `stream`: one wavefront
+ * per clip for the per-clip outputs (only if one of them is asked for), then one workgroup, one clip per thread, for d_loss and
+ * d_state (only if one of them is given; it forms the clips' values again, in the first launch's summation order).  n_scored is an integer count over the labels alone; every workgroup of the first launch counts it for itself,
+ * so it is known before d_dlogits is scaled and nothing is stored between the launches.  No atomics, no memset, no allocation,
+ * nothing synchronised: capturable.  The arithmetic is fp64 with the row maximum subtracted.
+ *
+ *   d_logits    fp32 [n_utt, n_classes], row stride ld_logits >= n_classes (finite; with a NaN the row's outputs are unspecified)
+ *   d_labels    int64 [n_utt].  -100 is ignored (torch's ignore_index); any other label outside [0, n_classes) is ignored too
+ *               and counted as bad_label.  A clip is SCORED iff its label lies in [0, n_classes).
+ *   d_pred_in   int32 [n_utt] or NULL: the labels to score (the ensemble's final pred); NULL scores the arg-max of the logits.
+ *               A value outside [0, n_classes) counts as wrong and is listed, but has no confusion cell.
+ *   d_grad_out  fp32 [1] or NULL (= 1): the upstream gradient of the loss.
+ * Per-call outputs, each may be NULL:
+ *   d_nll       fp32 [n_utt]             logsumexp(row) - row[label]; 0 where the clip is not scored
+ *   d_loss      fp32 [1]                 the sum of the unrounded fp64 nll over the scored clips -- thread t of the workgroup's
+ *                                        512 adds the clips t, t + 512, ... in ascending order, the 64 lanes of a wave are added by
+ *                                        a fixed butterfly and the 8 wave sums in order -- divided by n_scored and rounded once;
+ *                                        NaN when nothing is scored, as torch's
+ *   d_pred      int32 [n_utt]            the lowest index among the largest logits
+ *   d_prob      fp32 [n_utt, n_classes]  the softmax, dense.  d_pred and d_prob are dsp_ensemble_decide_batch's with
+ *                                        n_rules = 0 in every bit (one device function serves both)
+ *   d_dlogits   fp32 [n_utt, n_classes], row stride ld_dlogits: (softmax - onehot(label)) * grad_out / n_scored, formed in fp64
+ *               and rounded once; exact zeros in every clip that is not scored.  Only the n_classes columns are written.
+ *
+ * The epoch state, d_state or NULL: dsp_metrics_bytes(n_classes, wrong_capacity) bytes, 8-byte aligned, updated in place:
+ *   int64  counts[8]      seen, scored, correct, ignored, bad_label, wrong_total, calls, reserved
+ *                         (seen = scored + ignored; ignored counts the -100 labels AND the bad ones; correct + wrong_total = scored)
+ *   fp64   loss_sum       the sum of the unrounded nll
+ *   int64  confusion[n_classes][n_classes]   rows the true label, columns the scored label
+ *                                            (sklearn.metrics.confusion_matrix with labels=range(n_classes))
+ *   int32  wrong[wrong_capacity][3]          (index of the clip in the epoch = seen before this call + b, scored label, true
+ *                                            label), appended in clip order; entries behind the capacity are counted in
+ *                                            wrong_total and stored nowhere
+ * padded to a multiple of 8 bytes.  A clip that is not scored moves only seen, ignored and bad_label.  Every confusion cell is
+ * written by the one thread that owns it, the wrong list by a fixed prefix scan.  dsp_metrics_reset zeroes the block with a
+ * kernel (a recorded memset of more than 4 bytes is not relied upon).  The same wrong_capacity must be passed on every call.
+ *
+ * LIMITS: n_utt in [1, 16384]; n_classes in [2, 64]; wrong_capacity in [0, 2^24]; fp32 / int32 tensors 4-byte aligned, d_labels
+ * and d_state 8-byte aligned; no output (d_state included) may overlap another output or an input.  Anything else, NULL logits
+ * or labels, or a call with nothing to write is DSP_EINVAL with a message before any device call; under
+ * dsp_debug_host_dry_run(1) what passed every check is refused instead of launched.  The pointers carry no device: the caller
+ * makes the device of the tensors current (features/metrics.py does).
+ */
+int dsp_metrics_bytes(int32_t n_classes, int32_t wrong_capacity, int64_t* out_bytes);
+int dsp_metrics_reset(void* d_state, int32_t n_classes, int32_t wrong_capacity, void* stream);
+int dsp_xent_metrics_batch(const float* d_logits, int64_t ld_logits, int32_t n_utt, int32_t n_classes, const int64_t* d_labels,
+                           const int32_t* d_pred_in, const float* d_grad_out, float* d_nll, float* d_loss, int32_t* d_pred,
+                           float* d_prob, float* d_dlogits, int64_t ld_dlogits, void* d_state, int32_t wrong_capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,93 @@
+// Stand-alone host check of the scoring entry points (include/dsp_frontend.h: dsp_metrics_bytes, dsp_metrics_reset,
+// dsp_xent_metrics_batch; csrc/dsp_loss.hip): every argument check -- DSP_EINVAL with a message before any device call -- and,
+// under dsp_debug_host_dry_run(1), the refusal of what passed every check: the program needs no GPU.
+// `make -C dsp-speech-recognition_amd/csrc asan-loss` builds it with AddressSanitizer + UBSan against the sanitized build of the
+// library and runs it; it needs no preloaded runtime.
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "dsp_frontend.h"
+
+static int g_bad = 0;
+
+static void expect(int rc, const char* what, int line) {
+    const char* e = dsp_last_error();
+    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
+        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
+        ++g_bad;
+    }
+}
+#define EXPECT(call, what) expect((call), (what), __LINE__)
+
+int main() {
+    // never reached by a kernel: every call below returns before a launch
+    const int B = 5, C = 20, LD = 23, CAP = 4;
+    alignas(16) static float logits[B * LD], prob[B * C], dlogits[B * LD], nll[B], loss[2], go[1];
+    alignas(16) static int64_t labels[B + 1], state[9 + C * C + 8];
+    alignas(16) static int32_t pred[B], pred_in[B + 1];
+    float* odd_f = reinterpret_cast<float*>(reinterpret_cast<char*>(logits) + 2);
+    int32_t* odd_i = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(pred_in) + 2);
+    int64_t* odd_l = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(labels) + 4);
+    void* odd_s = reinterpret_cast<char*>(state) + 4;
+    float* fake = reinterpret_cast<float*>(uintptr_t(1) << 40);     // an address only: nothing is dereferenced
+    int64_t* fake_l = reinterpret_cast<int64_t*>(uintptr_t(1) << 41);
+    int64_t bytes = -1;
+
+    dsp_debug_host_dry_run(1);
+    const char* refused = "launches are refused under dsp_debug_host_dry_run";
+
+    EXPECT(dsp_metrics_bytes(C, CAP, nullptr), "NULL argument");
+    EXPECT(dsp_metrics_bytes(1, CAP, &bytes), "n_classes 1 must be in [2, 64]");
+    EXPECT(dsp_metrics_bytes(65, CAP, &bytes), "n_classes 65 must be in [2, 64]");
+    EXPECT(dsp_metrics_bytes(C, -1, &bytes), "wrong_capacity -1 must be in");
+    EXPECT(dsp_metrics_bytes(C, (1 << 24) + 1, &bytes), "wrong_capacity 16777217 must be in");
+    if (dsp_metrics_bytes(C, CAP, &bytes) != DSP_OK || bytes != 64 + 8 + 8 * C * C + 12 * CAP) { std::printf("bytes %lld\n", (long long)bytes); ++g_bad; }
+    if (dsp_metrics_bytes(2, 1, &bytes) != DSP_OK || bytes != 64 + 8 + 32 + 16) { std::printf("padded bytes %lld\n", (long long)bytes); ++g_bad; }
+    if (dsp_metrics_bytes(64, 1 << 24, &bytes) != DSP_OK || bytes != 72 + 8 * 4096 + 12LL * (1 << 24)) { std::printf("largest %lld\n", (long long)bytes); ++g_bad; }
+    if ((int64_t)sizeof(state) < 64 + 8 + 8 * C * C + 12 * CAP) { std::printf("the test's own state block is too small\n"); ++g_bad; }
+
+    EXPECT(dsp_metrics_reset(nullptr, C, CAP, nullptr), "NULL d_state");
+    EXPECT(dsp_metrics_reset(odd_s, C, CAP, nullptr), "d_state must be 8-byte aligned");
+    EXPECT(dsp_metrics_reset(state, 0, CAP, nullptr), "n_classes 0 must be in [2, 64]");
+    EXPECT(dsp_metrics_reset(state, C, -3, nullptr), "wrong_capacity -3 must be in");
+    EXPECT(dsp_metrics_reset(state, C, CAP, nullptr), refused);
+
+#define XENT(lg, ld, n, c, lab, pin, g, nl, ls, pr, pb, dl, ldd, st, cap) \
+    dsp_xent_metrics_batch((lg), (ld), (n), (c), (lab), (pin), (g), (nl), (ls), (pr), (pb), (dl), (ldd), (st), (cap), nullptr)
+    EXPECT(XENT(nullptr, LD, B, C, labels, pred_in, go, nll, loss, pred, prob, dlogits, LD, state, CAP), "NULL logits / labels");
+    EXPECT(XENT(logits, LD, B, C, nullptr, pred_in, go, nll, loss, pred, prob, dlogits, LD, state, CAP), "NULL logits / labels");
+    EXPECT(XENT(logits, LD, 0, C, labels, pred_in, go, nll, loss, pred, prob, dlogits, LD, state, CAP), "n_utt 0 must be in [1, 16384]");
+    EXPECT(XENT(fake, LD, 16385, C, fake_l, nullptr, nullptr, nullptr, loss, nullptr, nullptr, nullptr, 0, nullptr, 0), "n_utt 16385 must be in");
+    EXPECT(XENT(logits, LD, B, 1, labels, pred_in, go, nll, loss, pred, prob, dlogits, LD, state, CAP), "n_classes 1 must be in [2, 64]");
+    EXPECT(XENT(logits, 65, B, 65, labels, pred_in, go, nll, loss, pred, prob, dlogits, 65, state, CAP), "n_classes 65 must be in [2, 64]");
+    EXPECT(XENT(logits, C - 1, B, C, labels, pred_in, go, nll, loss, pred, prob, dlogits, LD, state, CAP), "ld_logits 19 is below n_classes 20");
+    EXPECT(XENT(logits, LD, B, C, labels, pred_in, go, nll, loss, pred, prob, dlogits, C - 1, state, CAP), "ld_dlogits 19 is below n_classes 20");
+    EXPECT(XENT(logits, LD, B, C, labels, pred_in, go, nll, loss, pred, prob, dlogits, LD, state, -1), "wrong_capacity -1 must be in");
+    EXPECT(XENT(logits, LD, B, C, labels, pred_in, go, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0), "nothing to write");
+    EXPECT(XENT(odd_f, LD, B, C, labels, pred_in, go, nll, loss, pred, prob, dlogits, LD, state, CAP), "4-byte aligned");
+    EXPECT(XENT(logits, LD, B, C, labels, odd_i, go, nll, loss, pred, prob, dlogits, LD, state, CAP), "4-byte aligned");
+    EXPECT(XENT(logits, LD, B, C, labels, pred_in, go, nll, loss, pred, prob, odd_f, LD, state, CAP), "4-byte aligned");
+    EXPECT(XENT(logits, LD, B, C, odd_l, pred_in, go, nll, loss, pred, prob, dlogits, LD, state, CAP), "d_labels must be 8-byte aligned");
+    EXPECT(XENT(logits, LD, B, C, labels, pred_in, go, nll, loss, pred, prob, dlogits, LD, odd_s, CAP), "d_state must be 8-byte aligned");
+    // an output on an input, an output on an output, a state block that reaches into a neighbour
+    EXPECT(XENT(logits, LD, B, C, labels, pred_in, go, nll, loss, pred, prob, logits, LD, state, CAP), "d_dlogits overlaps d_logits");
+    EXPECT(XENT(logits, LD, B, C, labels, pred_in, go, nll, loss, pred, logits + 4, dlogits, LD, state, CAP), "d_prob overlaps d_logits");
+    EXPECT(XENT(logits, LD, B, C, labels, pred_in, go, nll, nll + 1, pred, prob, dlogits, LD, state, CAP), "d_loss overlaps d_nll");
+    EXPECT(XENT(logits, LD, B, C, labels, pred_in, go, nll, loss, pred_in, prob, dlogits, LD, state, CAP), "d_pred overlaps d_pred_in");
+    EXPECT(XENT(logits, LD, B, C, labels, pred_in, loss, nll, loss, pred, prob, dlogits, LD, state, CAP), "d_loss overlaps d_grad_out");
+    EXPECT(XENT(logits, LD, B, C, labels, pred_in, go, nll, loss, pred, prob, dlogits, LD, labels, CAP), "d_state overlaps d_labels");
+    EXPECT(XENT(logits, LD, B, C, labels, pred_in, go, reinterpret_cast<float*>(state + 9), loss, pred, prob, dlogits, LD, state, CAP), "d_state overlaps d_nll");
+    // what passes: everything at once, a dense stride, inputs that share memory, every output alone, no state, the largest batch
+    EXPECT(XENT(logits, LD, B, C, labels, pred_in, go, nll, loss, pred, prob, dlogits, LD, state, CAP), refused);
+    EXPECT(XENT(logits, C, B, C, labels, nullptr, nullptr, nll, loss, pred, prob, dlogits, C, state, 0), refused);
+    EXPECT(XENT(logits, LD, B, C, labels, reinterpret_cast<int32_t*>(labels), logits, nullptr, loss, nullptr, nullptr, nullptr, 0, nullptr, -7), refused);
+    EXPECT(XENT(logits, LD, 1, 2, labels, nullptr, nullptr, nullptr, nullptr, pred, nullptr, nullptr, 0, nullptr, 0), refused);
+    EXPECT(XENT(logits, LD, B, C, labels, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, state, CAP), refused);
+    EXPECT(XENT(fake, 64, 16384, 64, fake_l, nullptr, nullptr, nullptr, loss, nullptr, nullptr, nullptr, 0, nullptr, 0), refused);
+    dsp_debug_host_dry_run(0);
+
+    if (g_bad) { std::printf("asan_loss_args: %d FAILED\n", g_bad); return 1; }
+    std::printf("asan_loss_args: ok\n");
+    return 0;
+}
