@@ -54,12 +54,7 @@ int check_operand(const char* who, const char* name, const dsp_rows_operand* op,
     return DSP_OK;
 }
 
-int64_t scratch_floats(int32_t T, int32_t B, int32_t m, int32_t n) {
-    const int steps = wgrad_chunk_steps(B);
-    const int64_t chunks = (T + steps - 1) / steps;
-    const int64_t tiles_m = (m + WGRAD_TILE - 1) / WGRAD_TILE, tiles_n = (n + WGRAD_TILE - 1) / WGRAD_TILE;
-    return chunks * tiles_m * (tiles_n * WGRAD_TILE * WGRAD_TILE + WGRAD_TILE);
-}
+int64_t scratch_floats(int32_t T, int32_t B, int32_t m, int32_t n) { return wgrad_scratch_floats(T, B, m, n); }
 
 }  // namespace
 

@@ -12,6 +12,7 @@
 //                       wave per clip here, as in the first launch, left fifteen of sixteen waves' worth of lanes idle and ran
 //                       the clips one behind the other: 63 us at 512 clips against 10 at 32.)
 // No atomics, no memset, no allocation; every store is a plain C++ assignment.  gfx950 only (wave64).
+// The kernels here are `static`: csrc/dsp_adv.hip launches them too, from a translation unit of its own.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -76,7 +77,7 @@ __device__ __forceinline__ XentRow xent_row_wave(const XentParams& P, int64_t b,
     return r;
 }
 
-__global__ __launch_bounds__(64 * XENT_ROWS_PER_BLOCK) void xent_rows_kernel(XentParams P) {
+static __global__ __launch_bounds__(64 * XENT_ROWS_PER_BLOCK) void xent_rows_kernel(XentParams P) {
     __shared__ int s_cnt[XENT_ROWS_PER_BLOCK];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t b = (int64_t)blockIdx.x * XENT_ROWS_PER_BLOCK + w;
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(64 * XENT_ROWS_PER_BLOCK) void xent_rows_kernel(Xen
 #define XR_WRONG 0x2000u
 #define XR_CELL 0x4000u                  // the scored label lies in [0, C): the clip has a confusion cell
 
-__global__ __launch_bounds__(XENT_REDUCE_THREADS) void xent_reduce_kernel(XentParams P) {
+static __global__ __launch_bounds__(XENT_REDUCE_THREADS) void xent_reduce_kernel(XentParams P) {
     __shared__ __attribute__((aligned(8))) uint16_t s_code[XENT_MAX_UTT];
     __shared__ double s_sum[XENT_REDUCE_WAVES];
     __shared__ int s_part[XENT_REDUCE_WAVES][5];      // scored, correct, ignored, bad_label, wrong
@@ -247,6 +248,6 @@ __global__ __launch_bounds__(XENT_REDUCE_THREADS) void xent_reduce_kernel(XentPa
 }
 
 // dsp_metrics_reset: every 32-bit word of the block becomes 0 (a recorded memset of more than 4 bytes replays wrong).
-__global__ __launch_bounds__(256) void xent_reset_kernel(int32_t* __restrict__ words, long long n_words) {
+static __global__ __launch_bounds__(256) void xent_reset_kernel(int32_t* __restrict__ words, long long n_words) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (long long)gridDim.x * 256) words[i] = 0;
 }

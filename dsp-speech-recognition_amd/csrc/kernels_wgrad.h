@@ -12,6 +12,7 @@
 // LIMITS (checked on the host, csrc/dsp_wgrad.hip): m, n, k in [1, 2048]; T B < 2^31; every address is formed in int64;
 // every pointer 4-byte aligned; operands have a unit column stride and non-negative t / b strides.  16-byte loads are
 // taken where the pointer and both strides of an operand allow them; the values loaded, and so the bits, are the same.
+// The kernels here are `static`: csrc/dsp_adv.hip launches the wgrad pair too, from a translation unit of its own.
 //
 // Tiling: 256 threads = 4 waves, each wave a 64 x 64 quarter of the tile as 4 x 4 MFMA tiles (64 accumulator registers).
 // Both operands of a stage of WGRAD_KT rows lie in LDS as [row][128 columns]; lane (i = l & 15, k = l >> 4) reads the four
@@ -38,6 +39,14 @@ __host__ __device__ inline int wgrad_chunk_steps(int B) {
 }
 
 typedef float wgrad_f4 __attribute__((ext_vector_type(4)));
+
+// The floats of scratch a dsp_rows_wgrad of these sizes needs: a partial tile per (chunk, tile) and the column-sum partials.
+inline int64_t wgrad_scratch_floats(int32_t T, int32_t B, int32_t m, int32_t n) {
+    const int steps = wgrad_chunk_steps(B);
+    const int64_t chunks = (T + steps - 1) / steps;
+    const int64_t tiles_m = (m + WGRAD_TILE - 1) / WGRAD_TILE, tiles_n = (n + WGRAD_TILE - 1) / WGRAD_TILE;
+    return chunks * tiles_m * (tiles_n * WGRAD_TILE * WGRAD_TILE + WGRAD_TILE);
+}
 
 struct RowsOp {          // one [T, B, cols] view: element (t, b, c) at p[t st + b sb + c]
     const float* p;
@@ -81,7 +90,7 @@ __device__ inline void rows_stage_mma(const float (*Ms)[WGRAD_TILE], const float
 }
 
 // grid (tiles_m * tiles_n, ceil(T / chunk)); part: [chunk][tile][128][128]; cpart: [chunk][tile_m][128] or NULL.
-__global__ __launch_bounds__(WGRAD_THREADS) void rows_wgrad_kernel(RowsOp A, RowsOp X, int shift, const float* __restrict__ init,
+static __global__ __launch_bounds__(WGRAD_THREADS) void rows_wgrad_kernel(RowsOp A, RowsOp X, int shift, const float* __restrict__ init,
                                                                    int64_t init_sb, const float* __restrict__ scale, int T, int B,
                                                                    const int32_t* __restrict__ d_rows, int tiles_n,
                                                                    float* __restrict__ part, float* __restrict__ cpart) {
@@ -159,7 +168,7 @@ __global__ __launch_bounds__(WGRAD_THREADS) void rows_wgrad_kernel(RowsOp A, Row
 }
 
 // One thread per element of C [m, n] and then of c [m]: the partials of the chunks below ceil(R / chunk), in index order.
-__global__ __launch_bounds__(256) void rows_wgrad_reduce_kernel(const float* __restrict__ part, const float* __restrict__ cpart, int m, int n,
+static __global__ __launch_bounds__(256) void rows_wgrad_reduce_kernel(const float* __restrict__ part, const float* __restrict__ cpart, int m, int n,
                                                                 int tiles_m, int tiles_n, int T, int B, const int32_t* __restrict__ d_rows,
                                                                 float* __restrict__ C, float* __restrict__ csum) {
     const int R = rows_bound(d_rows, T);
@@ -192,7 +201,7 @@ struct RowsTerm {        // one product A [T, B, k] W [k, n]
 };
 
 // grid (ceil(T B / 128), ceil(n / 128)); Y dense [T B, n].
-__global__ __launch_bounds__(WGRAD_THREADS) void rows_product_kernel(RowsTerm P0, RowsTerm P1, int nterms, int n, int T, int B,
+static __global__ __launch_bounds__(WGRAD_THREADS) void rows_product_kernel(RowsTerm P0, RowsTerm P1, int nterms, int n, int T, int B,
                                                                      const int32_t* __restrict__ d_rows, float* __restrict__ Y, int yvec) {
     __shared__ __attribute__((aligned(16))) float As[WGRAD_KT][WGRAD_TILE];   // [k][row of the tile]: transposed while staged
     __shared__ __attribute__((aligned(16))) float Ws[WGRAD_KT][WGRAD_TILE];   // [k][column]

@@ -36,7 +36,7 @@ from .pipeline import VadMfccPipeline  # noqa: F401
 from .ensemble import PitchSVM, EnsembleBatch, MixedRateEnsembleBatch, ensemble_decide  # noqa: F401
 from .model_glue import MixedRateFeatureBatch, MixedRateCapacityBatch, get_batch_full  # noqa: F401
 from .svmfit import fit_pitch_svm, grid_search, robust_scale_fit, svm_fit_problems, PitchModelTrainer  # noqa: F401
-from .train import TrainBatch, MixedRateTrainBatch  # noqa: F401
+from .train import TrainBatch, MixedRateTrainBatch, AdvTrainBatch  # noqa: F401
 from .optim import DeviceAdam  # noqa: F401
 from .dropout import DeviceRng, device_dropout  # noqa: F401
 from .metrics import Metrics, cross_entropy  # noqa: F401

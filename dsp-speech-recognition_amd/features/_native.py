@@ -222,6 +222,10 @@ SIGNATURES = {
     'dsp_metrics_reset': (C.c_int, [c_vp, c_i32, c_i32, c_vp]),
     'dsp_xent_metrics_batch': (C.c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32,
                                          c_vp]),
+    'dsp_adv_disc_work_bytes': (C.c_int, [c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i64)]),
+    'dsp_adv_disc_forward': (C.c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'dsp_adv_disc_train': (C.c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp,
+                                     c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
 }
 
 _lib = None

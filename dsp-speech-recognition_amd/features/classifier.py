@@ -1657,3 +1657,12 @@ def fill_parameters(module, seed):
             p.copy_(torch.from_numpy(v))
             names.append(name)
     return names
+
+
+def __getattr__(name):
+    """``AdvHRNNHead`` and ``gradient_reverse`` live in features/adversarial.py (which builds on ``HRNNHead`` above) and are
+    re-exported from here, resolved on first use so that either module may be imported first."""
+    if name in ('AdvHRNNHead', 'gradient_reverse'):
+        from . import adversarial
+        return getattr(adversarial, name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -11,6 +11,8 @@
   after ``replay()``: it writes the parameters in place, and the refresh at the head of the next replay repacks them.  With
   ``optimizer=`` a ``features.optim.DeviceAdam`` over the head's trainable parameters, its step is recorded behind the backward:
   the whole of model.py:137-149 is one replay.
+* ``AdvTrainBatch`` is the same step for ``features.adversarial.AdvHRNNHead`` (adv_model.py:33-48): speakers beside the labels,
+  ``loss = CE(labels) + CE(speakers)``, the discriminator optionally as one native call (``native_disc=True``).
 * With ``rng=`` a ``features.dropout.DeviceRng`` among the head's keywords the dropouts are drawn by the device generator, and
   the chain begins with ``rng.advance()`` -- recorded too, so every replay draws a new step's multipliers, the ones an eager
   ``run`` from the same state draws.  ``capture`` leaves the generator's state as it found it.
@@ -29,6 +31,11 @@ from .batch import _is_device_tensor, _wave_dtype_of
 # tests/test_gpu_device_train.py (B = 5) compare a second replay with the eager step, bit for bit.
 CAPTURE_VERIFIED = {'RNNHead': (32, 512), 'HRNNHead': (32, 512), 'HRNNAttHead': (32, 512), 'TransformerHead': (32, 512),
                     'HMRNNHead': (5, 32, 512)}
+# The same for ``AdvTrainBatch.capture``: the sizes at which tests/test_gpu_adv.py compares three replays with three eager steps.
+# A table of its own: every entry of CAPTURE_VERIFIED is a head that the label-only ``TrainBatch`` trains (and
+# tests/test_gpu_train_capture.py runs each of them through it), and under a label-only loss the discriminator's parameters
+# receive no gradient, so a ``TrainBatch`` over an ``AdvHRNNHead`` is refused by ``capture`` like any other unverified pair.
+ADV_CAPTURE_VERIFIED = {'AdvHRNNHead': (32, 512)}
 
 
 def _advance_rng(head_kwargs):
@@ -87,6 +94,8 @@ class TrainBatch:
 
     ``head``: one of features/classifier.py's heads in training mode (it is called with ``device_len=True,
     device_grad=True``; further keywords -- ``dropout=False`` and the like -- go through ``run`` / ``capture``)."""
+
+    _verified = CAPTURE_VERIFIED       # what ``capture`` serves: head class -> batch sizes
 
     def __init__(self, rate, head, frame=0.03, step=0.01):
         from .model_glue import ModelFeatureBatch
@@ -280,8 +289,8 @@ class TrainBatch:
         clips = waves.reshape(-1)                              # a view: the same memory
         _wave_dtype_of(clips)
         kind = type(self.head).__name__
-        if B not in CAPTURE_VERIFIED.get(kind, ()):
-            raise NotImplementedError(f'capture: {kind} at B = {B} is not in CAPTURE_VERIFIED ({CAPTURE_VERIFIED}): a replay of this head '
+        if B not in self._verified.get(kind, ()):
+            raise NotImplementedError(f'capture: {kind} at B = {B} is not in CAPTURE_VERIFIED ({self._verified}): a replay of this head '
                                       'and size has not been compared with the eager step; use run()')
         if not (_is_device_tensor(labels) and labels.dtype == torch.int64 and tuple(labels.shape) == (B,) and labels.is_contiguous()):
             raise TypeError('capture needs labels as a contiguous [B] int64 device tensor: the graph reads it in place')
@@ -289,6 +298,15 @@ class TrainBatch:
                                        and jitter.is_contiguous()):
             raise TypeError('capture needs jitter as a contiguous [B, 2] int64 device tensor (or None): the graph reads it in place')
         return clips
+
+    @staticmethod
+    def _backward(out, native):
+        """The backward of a recorded step: a native loss is differentiated from ``features.metrics.unit_grad``."""
+        if native:
+            from .metrics import backward as native_backward
+            native_backward(out.loss)
+        else:
+            out.loss.backward()
 
     def _record(self, dev, chain, optimizer, hold, rng=None, spec=(False, None)):
         """The check of ``optimizer`` and the recipe of ``capture``: ``chain(alias)`` queues front end, head and loss on torch's current
@@ -317,7 +335,7 @@ class TrainBatch:
             native, metrics = spec
             metrics_state = None if metrics is None else metrics.state.clone()
             if native:
-                from .metrics import backward as native_backward, unit_grad
+                from .metrics import unit_grad
                 unit_grad(dev)                                 # (made here, not while recording)
         alias = dict(zip(names, leaves))
 
@@ -328,10 +346,7 @@ class TrainBatch:
                         m._native_handle(dev, refresh='always')
             out = chain(alias)
             with torch.autograd.set_multithreading_enabled(False):      # every recorded launch comes from the capturing thread
-                if native:
-                    native_backward(out.loss)
-                else:
-                    out.loss.backward()
+                self._backward(out, native)
             if record and optimizer is not None:               # the graph's own gradients: their addresses are known from here on
                 optimizer._launch([v.grad for v in leaves], False, rebind='always')
             out.loss, out.logits = out.loss.detach(), out.logits.detach()
@@ -427,4 +442,122 @@ class MixedRateTrainBatch(TrainBatch):
                          optimizer, [arena, clips, labels], head_kwargs.get('rng'), spec)
         g.sample_offsets, g.rates, g.status = arena.sample_offsets, arena.rates, arena.status
         g.jitter = arena.jitter if use_jitter else None
+        return g
+
+
+class AdvTrainBatch(TrainBatch):
+    """adv_model.py:33-48 for a batch of raw clips of one sample rate: ``TrainBatch`` over a ``features.adversarial.AdvHRNNHead``
+    with the speakers beside the labels and ``loss = CE(logits, labels) + CE(logits2, speakers)`` (adv_model.py:45-47).
+
+    ``run(waves, sample_offsets, labels, speakers, ...)`` / ``capture(..., optimizer=)`` take ``TrainBatch``'s arguments plus
+    ``speakers`` (int64 [B]; for ``capture`` a contiguous device tensor that is read in place on every replay),
+    ``speaker_metrics`` (a ``features.metrics.Metrics`` over the head's n_speakers classes, updated by the native discriminator's
+    loss call: it needs ``native_disc=True``) and ``native_disc`` (None follows ``AdvHRNNHead.native_disc_default``): the
+    discriminator as ONE native call whose backward launches nothing (``dsp_adv_disc_train``).  The namespace gains
+    ``loss_label``, ``loss_speaker`` and ``logits2``; ``loss`` is their sum.  ``AdvTrainBatch.backward(ns)`` differentiates both
+    losses from ``features.metrics.unit_grad``, so neither native loss launches anything in backward; the recorded step does
+    the same.  ``MixedRateTrainBatch`` and ``features.fit.Trainer.fit`` over speakers are out of scope: mixed-rate batches and
+    the epoch schedule serve the five label-only heads."""
+
+    _verified = ADV_CAPTURE_VERIFIED
+
+    def __init__(self, rate, head, frame=0.03, step=0.01):
+        from .adversarial import AdvHRNNHead
+        if not isinstance(head, AdvHRNNHead):
+            raise TypeError(f'AdvTrainBatch needs a features.adversarial.AdvHRNNHead, not {type(head).__name__}')
+        super().__init__(rate, head, frame=frame, step=step)
+
+    @staticmethod
+    def _adv_spec(speakers, B, loss, speaker_metrics, native_disc, head, device_tensor=False):
+        """The refusals of the speaker arguments; they need no device."""
+        import torch
+        if loss not in ('torch', 'native'):
+            raise ValueError(f"loss must be 'torch' or 'native', got {loss!r}")
+        if speaker_metrics is not None:
+            if loss != 'native':
+                raise ValueError("speaker_metrics= needs loss='native': the device metrics are updated by the native loss calls")
+            from .metrics import Metrics
+            if not isinstance(speaker_metrics, Metrics):
+                raise TypeError(f'speaker_metrics must be a features.metrics.Metrics, not {type(speaker_metrics).__name__}')
+            if not (head.native_disc_default if native_disc is None else native_disc):
+                raise ValueError('speaker_metrics= needs native_disc=True: they are updated by the native discriminator call')
+        if not torch.is_tensor(speakers):
+            a = np.asarray(speakers)
+            if a.dtype.kind not in 'iu':
+                raise TypeError(f'speakers must be integers (int64 [B]), got {a.dtype}')
+            speakers = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64))
+        if speakers.dtype != torch.int64:
+            raise TypeError(f'speakers must be int64, got {speakers.dtype}')
+        if tuple(speakers.shape) != (B,):
+            raise ValueError(f'speakers must be [B] = [{B}], got {tuple(speakers.shape)}')
+        if device_tensor and not (speakers.is_cuda and speakers.is_contiguous()):
+            raise TypeError('capture needs speakers as a contiguous [B] int64 device tensor: the graph reads it in place')
+        return speakers
+
+    @staticmethod
+    def _n_utt(sample_offsets):
+        import torch
+        return int(sample_offsets.shape[0] if torch.is_tensor(sample_offsets) else len(sample_offsets)) - 1
+
+    def _head_loss(self, inp, len0, labels, head_kwargs, alias, hold, spec=(False, None)):
+        """``TrainBatch._head_loss`` with the second loss.  The speaker arguments travel from ``run`` / ``capture`` through the
+        base class's chain among the head's keywords, under the reserved key ``_adv``."""
+        import torch
+        from .classifier import head_length_info
+        head_kwargs = dict(head_kwargs)
+        speakers, speaker_metrics, native_disc = head_kwargs.pop('_adv')
+        speakers = speakers.to(inp.device)
+        kw = dict(device_len=True, device_grad=True, speakers=speakers, native_disc=native_disc, speaker_metrics=speaker_metrics,
+                  **head_kwargs)
+        if alias is None:
+            logits, logits2, loss_speaker = self.head(inp, len0, **kw)
+        else:
+            logits, logits2, loss_speaker = torch.func.functional_call(self.head, alias, (inp, len0), kw)
+        if spec[0]:
+            from .metrics import cross_entropy
+            loss_label = cross_entropy(logits, labels, spec[1])
+        else:
+            loss_label = torch.nn.functional.cross_entropy(logits, labels)
+        n_clamped = head_length_info(len0, inp.shape[0], 1)[2][2:3]
+        return types.SimpleNamespace(loss=(loss_label + loss_speaker).detach(), loss_label=loss_label, loss_speaker=loss_speaker,
+                                     logits=logits, logits2=logits2, inp=inp, len0=len0, n_clamped=n_clamped,
+                                     _hold=list(hold) + [speakers])
+
+    @staticmethod
+    def backward(ns):
+        """Differentiate both losses of a ``run`` namespace from ``unit_grad``: one autograd pass over both roots."""
+        import torch
+        from .metrics import unit_grad
+        u = unit_grad(ns.loss_label.device)
+        torch.autograd.backward([ns.loss_label, ns.loss_speaker], [u, u])
+
+    @staticmethod
+    def _backward(out, native):
+        AdvTrainBatch.backward(out)
+
+    def run(self, waves, sample_offsets, labels, speakers, jitter=None, capacity=None, loss='torch', metrics=None, speaker_metrics=None,
+            native_disc=None, **head_kwargs):
+        """``TrainBatch.run`` with ``speakers`` (class docstring).  ``loss`` in the namespace is the detached sum; call
+        ``AdvTrainBatch.backward(ns)`` (or ``(ns.loss_label + ns.loss_speaker).backward()``)."""
+        speakers = self._adv_spec(speakers, self._n_utt(sample_offsets), loss, speaker_metrics, native_disc, self.head)
+        return super().run(waves, sample_offsets, labels, jitter=jitter, capacity=capacity, loss=loss, metrics=metrics,
+                           _adv=(speakers, speaker_metrics, native_disc), **head_kwargs)
+
+    def capture(self, waves, sample_offsets, labels, speakers, jitter=None, optimizer=None, capacity=None, loss='torch', metrics=None,
+                speaker_metrics=None, native_disc=None, **head_kwargs):
+        """``TrainBatch.capture`` with ``speakers``: the recorded step reads them in place on every replay, and every replay
+        updates ``speaker_metrics`` (``capture`` itself leaves the block as it found it).  ``ADV_CAPTURE_VERIFIED['AdvHRNNHead']``
+        governs the batch sizes."""
+        import torch
+        speakers = self._adv_spec(speakers, self._n_utt(sample_offsets), loss, speaker_metrics, native_disc, self.head, device_tensor=True)
+        from .metrics import unit_grad
+        unit_grad(speakers.device)                             # (made here, not while recording)
+        saved = None if speaker_metrics is None else speaker_metrics.state.clone()
+        g = super().capture(waves, sample_offsets, labels, jitter=jitter, optimizer=optimizer, capacity=capacity, loss=loss,
+                            metrics=metrics, _adv=(speakers, speaker_metrics, native_disc), **head_kwargs)
+        if saved is not None:                                  # the warm-up steps moved it; recording ran nothing
+            speaker_metrics.state.copy_(saved)
+        g.hold.append((speakers, speaker_metrics, self.head.d_gamma))
+        g.result.loss_label, g.result.loss_speaker = g.result.loss_label.detach(), g.result.loss_speaker.detach()
+        g.result.logits2 = g.result.logits2.detach()
         return g

@@ -1317,6 +1317,52 @@ int dsp_xent_metrics_batch(const float* d_logits, int64_t ld_logits, int32_t n_u
                            const int32_t* d_pred_in, const float* d_grad_out, float* d_nll, float* d_loss, int32_t* d_pred,
                            float* d_prob, float* d_dlogits, int64_t ld_dlogits, void* d_state, int32_t wrong_capacity, void* stream);
 
+/* ---- the speaker discriminator of adv_clf.AdvHRNN: forward, loss and every gradient in one call (csrc/kernels_adv.h) ------
+ *
+ * adv_clf.py:34-38 behind the pooled feature: a gradient reversal (identity forward, -gamma times the gradient backward),
+ * a = tanh(feat W1^T + b1), z = a W2^T + b2, trained with F.cross_entropy(z, speakers) (adv_model.py:45-47).  The loss is
+ * terminal, so one call forms the forward, the loss and every gradient; an autograd node over it launches nothing in backward.
+ * All arithmetic is fp32 on v_mfma_f32_16x16x4_f32, every element an fmaf chain in a fixed order that does not depend on B; the
+ * loss and dz are dsp_xent_metrics_batch's in every bit (the same two kernels); dW / db come from the row-reduction kernels of
+ * dsp_rows_wgrad with T = 1.  No atomics, no memset, no grid barrier, no allocation, nothing synchronised: capturable, and the
+ * same arguments give the same bits on every run.
+ *
+ *   d_feat      fp32 [B, F], row stride ld_feat >= F        d_W1 [H, F], d_b1 [H], d_W2 [S, H], d_b2 [S]: dense
+ *   d_speakers  int64 [B]; -100 and labels outside [0, S) are ignored exactly as dsp_xent_metrics_batch ignores them
+ *   d_grad_out  fp32 [1] or NULL (= 1): the upstream gradient of the loss
+ *   gamma       the reversal's factor by value; d_gamma (fp32 [1], device) replaces it when not NULL, so a schedule can move it
+ *               between graph replays without a new capture.  By value it is rounded to fp32 once: both routes give the same bits.
+ *
+ * dsp_adv_disc_forward: ONE launch over tiles of 16 batch rows.  a -> d_a [B, H] (dense; may be NULL), z -> d_logits2 [B, S] with
+ * row stride ld_logits2.  a stays in LDS between the two products.
+ *
+ * dsp_adv_disc_train: at most EIGHT launches on `stream`:
+ *   1  the forward above (d_a is mandatory here; z goes to the workspace when d_logits2 is NULL);
+ *   2  the two scoring launches: d_loss2 [1], d_dz [B, S] dense = (softmax - onehot) grad_out / n_scored with exact zeros in
+ *      every row that is not scored, and the optional d_state metrics block (n_classes = S) with wrong_capacity;
+ *   1  the backward over the same row tiles: da = dz W2, dpre = da (1 - a^2) -> workspace [B, H],
+ *      d_dfeat [B, F] (row stride ld_dfeat) = -gamma (dpre W1) with gamma applied as one final multiply;
+ *   2 + 2  d_dW2 [S, H] = dz^T a with d_db2 [S] its column sum, d_dW1 [H, F] = dpre^T feat with d_db1 [H] its column sum.
+ * Every element of every output is written on every call.  Each of d_dW1, d_db1, d_dW2, d_db2, d_dfeat and d_logits2 may be NULL;
+ * a NULL output is skipped together with the launches only it needs, and the other outputs keep their bits.
+ * d_work: dsp_adv_disc_work_bytes(B, F, H, S) bytes, 16-byte aligned, contents unspecified before and after.
+ *
+ * LIMITS: B in [1, 16384], F in [1, 2048], H in [1, 512], S in [2, 64]; strides >= the columns; fp32 tensors 4-byte aligned,
+ * d_speakers and d_state 8-byte aligned, d_work 16-byte aligned; no output (d_state and d_work included) may overlap another
+ * output or anything that is read.  Anything else or a NULL mandatory pointer is DSP_EINVAL with a message before any device
+ * call; under dsp_debug_host_dry_run(1) what passed every check is refused instead of launched.  The pointers carry no device:
+ * the caller makes the device of the tensors current (features/adversarial.py does).
+ */
+int dsp_adv_disc_work_bytes(int32_t B, int32_t F, int32_t H, int32_t S, int64_t* out_bytes);
+int dsp_adv_disc_forward(const float* d_feat, int64_t ld_feat, int32_t B, int32_t F, int32_t H, int32_t S, const float* d_W1,
+                         const float* d_b1, const float* d_W2, const float* d_b2, float* d_a, float* d_logits2, int64_t ld_logits2,
+                         void* stream);
+int dsp_adv_disc_train(const float* d_feat, int64_t ld_feat, int32_t B, int32_t F, int32_t H, int32_t S, const float* d_W1,
+                       const float* d_b1, const float* d_W2, const float* d_b2, const int64_t* d_speakers, const float* d_grad_out,
+                       double gamma, const float* d_gamma, float* d_a, float* d_logits2, int64_t ld_logits2, float* d_loss2, float* d_dz,
+                       float* d_dfeat, int64_t ld_dfeat, float* d_dW1, float* d_db1, float* d_dW2, float* d_db2, void* d_state,
+                       int32_t wrong_capacity, void* d_work, int64_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

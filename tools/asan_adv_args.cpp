@@ -1,0 +1,161 @@
+// Stand-alone host check of the speaker-discriminator entry points (include/dsp_frontend.h: dsp_adv_disc_work_bytes,
+// dsp_adv_disc_forward, dsp_adv_disc_train; csrc/dsp_adv.hip): every argument check -- DSP_EINVAL with a message before any
+// device call -- and, under dsp_debug_host_dry_run(1), the refusal of what passed every check: the program needs no GPU.
+// `make -C dsp-speech-recognition_amd/csrc asan-adv` builds it with AddressSanitizer + UBSan against the sanitized build of the
+// library and runs it; it needs no preloaded runtime.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "dsp_frontend.h"
+
+static int g_bad = 0;
+
+static void expect(int rc, const char* what, int line) {
+    const char* e = dsp_last_error();
+    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
+        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
+        ++g_bad;
+    }
+}
+#define EXPECT(call, what) expect((call), (what), __LINE__)
+
+namespace {
+
+// never reached by a kernel: every call below returns before a launch
+constexpr int B = 5, F = 12, H = 7, S = 4, LDF = 13, LDZ = 6, LDD = 14, CAP = 3;
+alignas(16) float feat[B * LDF], W1[H * F], b1[H], W2[S * H], b2[S], go[1], gam[1];
+alignas(16) float a[B * H], z[B * LDZ], loss[2], dz[B * S], dfeat[B * LDD], dW1[H * F], db1[H], dW2[S * H], db2[S];
+alignas(16) int64_t spk[64], state[9 + S * S + 8];
+alignas(16) char work[1 << 20];
+
+struct Args {
+    const float* feat = ::feat;
+    int64_t ld_feat = LDF;
+    int32_t b = B, f = F, h = H, s = S;
+    const float *W1 = ::W1, *b1 = ::b1, *W2 = ::W2, *b2 = ::b2;
+    const int64_t* spk = ::spk;
+    const float* go = ::go;
+    double gamma = 0.01;
+    const float* d_gamma = gam;
+    float *a = ::a, *z = ::z;
+    int64_t ld_z = LDZ;
+    float *loss = ::loss, *dz = ::dz, *dfeat = ::dfeat;
+    int64_t ld_dfeat = LDD;
+    float *dW1 = ::dW1, *db1 = ::db1, *dW2 = ::dW2, *db2 = ::db2;
+    void* state = ::state;
+    int32_t cap = CAP;
+    void* work = ::work;
+    int64_t work_bytes = sizeof(::work);
+};
+
+int train(const Args& x) {
+    return dsp_adv_disc_train(x.feat, x.ld_feat, x.b, x.f, x.h, x.s, x.W1, x.b1, x.W2, x.b2, x.spk, x.go, x.gamma, x.d_gamma, x.a, x.z, x.ld_z,
+                              x.loss, x.dz, x.dfeat, x.ld_dfeat, x.dW1, x.db1, x.dW2, x.db2, x.state, x.cap, x.work, x.work_bytes, nullptr);
+}
+
+int forward(const Args& x) {
+    return dsp_adv_disc_forward(x.feat, x.ld_feat, x.b, x.f, x.h, x.s, x.W1, x.b1, x.W2, x.b2, x.a, x.z, x.ld_z, nullptr);
+}
+
+template <class T>
+T* odd(T* p, int bytes) { return reinterpret_cast<T*>(reinterpret_cast<char*>(p) + bytes); }
+
+}  // namespace
+
+#define TRAIN(what, ...) do { Args x; __VA_ARGS__; EXPECT(train(x), what); } while (0)
+#define FORWARD(what, ...) do { Args x; __VA_ARGS__; EXPECT(forward(x), what); } while (0)
+
+int main() {
+    float* fake = reinterpret_cast<float*>(uintptr_t(1) << 40);       // addresses only: nothing is dereferenced
+    int64_t bytes = -1, need = 0;
+
+    dsp_debug_host_dry_run(1);
+    const char* refused = "launches are refused under dsp_debug_host_dry_run";
+
+    EXPECT(dsp_adv_disc_work_bytes(B, F, H, S, nullptr), "NULL argument");
+    EXPECT(dsp_adv_disc_work_bytes(0, F, H, S, &bytes), "B 0 must be in [1, 16384]");
+    EXPECT(dsp_adv_disc_work_bytes(16385, F, H, S, &bytes), "B 16385 must be in [1, 16384]");
+    EXPECT(dsp_adv_disc_work_bytes(B, 0, H, S, &bytes), "F 0 must be in [1, 2048]");
+    EXPECT(dsp_adv_disc_work_bytes(B, 2049, H, S, &bytes), "F 2049 must be in [1, 2048]");
+    EXPECT(dsp_adv_disc_work_bytes(B, F, 513, S, &bytes), "H 513 must be in [1, 512]");
+    EXPECT(dsp_adv_disc_work_bytes(B, F, H, 1, &bytes), "S 1 must be in [2, 64]");
+    EXPECT(dsp_adv_disc_work_bytes(B, F, H, 65, &bytes), "S 65 must be in [2, 64]");
+    if (dsp_adv_disc_work_bytes(B, F, H, S, &need) != DSP_OK || need <= 0 || need % 16 || need > (int64_t)sizeof(work)) {
+        std::printf("work bytes %lld\n", (long long)need);
+        ++g_bad;
+    }
+    if (dsp_adv_disc_work_bytes(16384, 2048, 512, 64, &bytes) != DSP_OK || bytes < 16384LL * (512 + 64) * 4) {
+        std::printf("largest work bytes %lld\n", (long long)bytes);
+        ++g_bad;
+    }
+
+    // the forward
+    FORWARD("NULL feat / W1 / b1 / W2 / b2", x.feat = nullptr);
+    FORWARD("NULL feat / W1 / b1 / W2 / b2", x.b2 = nullptr);
+    FORWARD("B 0 must be in", x.b = 0);
+    FORWARD("H 513 must be in", x.h = 513);
+    FORWARD("ld_feat 11 is below the 12 columns", x.ld_feat = F - 1);
+    FORWARD("NULL output d_logits2", x.z = nullptr);
+    FORWARD("ld_logits2 3 is below the 4 columns", x.ld_z = S - 1);
+    FORWARD("4-byte aligned", x.feat = odd(feat, 2));
+    FORWARD("4-byte aligned", x.a = odd(a, 2));
+    FORWARD("d_logits2 overlaps d_feat", x.z = feat);
+    FORWARD("d_a overlaps d_W1", x.a = W1);
+    FORWARD("d_logits2 overlaps d_a", x.z = a + 3);
+    FORWARD(refused, (void)x);
+    FORWARD(refused, x.a = nullptr);
+    FORWARD(refused, x.feat = fake; x.b = 16384; x.a = nullptr; x.z = fake + (1 << 26); x.ld_z = S);
+
+    // the training step
+    TRAIN("NULL feat / W1 / b1 / W2 / b2", x.W1 = nullptr);
+    TRAIN("NULL d_speakers", x.spk = nullptr);
+    TRAIN("NULL output d_a / d_loss2 / d_dz", x.a = nullptr);
+    TRAIN("NULL output d_a / d_loss2 / d_dz", x.loss = nullptr);
+    TRAIN("NULL output d_a / d_loss2 / d_dz", x.dz = nullptr);
+    TRAIN("NULL workspace", x.work = nullptr);
+    TRAIN("B 16385 must be in", x.b = 16385);
+    TRAIN("F 0 must be in", x.f = 0);
+    TRAIN("S 65 must be in", x.s = 65);
+    TRAIN("gamma", x.gamma = NAN);
+    TRAIN("gamma", x.gamma = INFINITY);
+    TRAIN("ld_feat 11 is below the 12 columns", x.ld_feat = F - 1);
+    TRAIN("ld_logits2 3 is below the 4 columns", x.ld_z = S - 1);
+    TRAIN("ld_dfeat 11 is below the 12 columns", x.ld_dfeat = F - 1);
+    TRAIN("wrong_capacity -1 must be in", x.cap = -1);
+    TRAIN("wrong_capacity 16777217 must be in", x.cap = (1 << 24) + 1);
+    TRAIN("4-byte aligned", x.feat = odd(feat, 2));
+    TRAIN("4-byte aligned", x.d_gamma = odd(gam, 1));
+    TRAIN("4-byte aligned", x.go = odd(go, 2));
+    TRAIN("4-byte aligned", x.dW2 = odd(dW2, 2));
+    TRAIN("4-byte aligned", x.dfeat = odd(dfeat, 3));
+    TRAIN("d_speakers must be 8-byte aligned", x.spk = odd(spk, 4));
+    TRAIN("d_state must be 8-byte aligned", x.state = odd(state, 4));
+    TRAIN("the workspace must be 16-byte aligned", x.work = work + 8);
+    TRAIN("is short of the", x.work_bytes = need - 1);
+    // an output on an input, an output on an output, the workspace and the state on a neighbour
+    TRAIN("d_dfeat overlaps d_feat", x.dfeat = feat);
+    TRAIN("d_dW1 overlaps d_W1", x.dW1 = W1);
+    TRAIN("d_db2 overlaps d_b2", x.db2 = b2);
+    TRAIN("d_loss2 overlaps d_grad_out", x.loss = go);
+    TRAIN("d_loss2 overlaps d_gamma", x.loss = gam);
+    TRAIN("d_dz overlaps d_a", x.dz = a + 4);
+    TRAIN("d_dW2 overlaps d_logits2", x.dW2 = z);
+    TRAIN("d_state overlaps d_speakers", x.state = spk);
+    TRAIN("d_dz overlaps d_speakers", x.dz = reinterpret_cast<float*>(spk));
+    TRAIN("the workspace overlaps", x.work = reinterpret_cast<char*>(db1); x.work_bytes = 1 << 20);
+    TRAIN("the workspace overlaps d_feat", x.feat = reinterpret_cast<float*>(work + 64));
+    // what passes: everything at once, dense strides, every optional output NULL (its stride is then not looked at), no state
+    TRAIN(refused, (void)x);
+    TRAIN(refused, x.ld_feat = F; x.ld_z = S; x.ld_dfeat = F; x.go = nullptr; x.d_gamma = nullptr; x.gamma = -1.0);
+    TRAIN(refused, x.z = nullptr; x.ld_z = 0; x.dfeat = nullptr; x.ld_dfeat = -5; x.dW1 = x.db1 = x.dW2 = x.db2 = nullptr);
+    TRAIN(refused, x.state = nullptr; x.cap = -7);
+    TRAIN(refused, x.dW1 = nullptr);
+    TRAIN(refused, x.db2 = nullptr; x.work_bytes = need);
+    dsp_debug_host_dry_run(0);
+
+    if (g_bad) { std::printf("asan_adv_args: %d FAILED\n", g_bad); return 1; }
+    std::printf("asan_adv_args: ok\n");
+    return 0;
+}
