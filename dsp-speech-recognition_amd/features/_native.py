@@ -68,6 +68,12 @@ class RowsOperand(C.Structure):
     _fields_ = [('d_ptr', c_vp), ('stride_t', c_i64), ('stride_b', c_i64), ('cols', c_i32), ('reserved', c_i32)]
 
 
+class GraphCensus(C.Structure):
+    _fields_ = [('n_nodes', c_i32), ('n_kernel', c_i32), ('n_memset', c_i32), ('n_memcpy', c_i32), ('n_other', c_i32),
+                ('n_wide_memset', c_i32), ('n_roots', c_i32), ('max_fanout', c_i32), ('widest_memset_bytes', c_i64),
+                ('names_bytes', c_i64)]
+
+
 class EnsembleRule(C.Structure):
     _fields_ = [('label_a', c_i32), ('label_b', c_i32), ('threshold', c_f64), ('svm', c_vp)]
 
@@ -226,6 +232,9 @@ SIGNATURES = {
     'dsp_adv_disc_forward': (C.c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'dsp_adv_disc_train': (C.c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp,
                                      c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
+    'dsp_rows_colsum_scratch_bytes': (C.c_int, [c_i32, c_i32, c_i32, C.POINTER(c_i64)]),
+    'dsp_rows_colsum': (C.c_int, [C.POINTER(RowsOperand), C.POINTER(RowsOperand), c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'dsp_graph_census': (C.c_int, [c_vp, C.POINTER(GraphCensus), c_vp, C.c_size_t]),
 }
 
 _lib = None

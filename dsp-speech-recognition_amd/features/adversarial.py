@@ -175,7 +175,8 @@ class AdvHRNNHead(nn.Module):
 
     ``forward(inp, len0, **kw)`` -> (logits, logits2) as adv_clf.py:33-38; every keyword ``HRNNHead.forward`` takes goes to ``g``.
     With ``speakers=`` (int64 [B]) it returns (logits, logits2, loss_speaker) -- ``speaker_loss`` on g's feature, which is how
-    ``features.train.AdvTrainBatch`` calls it; ``native_disc`` / ``speaker_metrics`` are ``speaker_loss``'s ``native`` / ``metrics``."""
+    ``features.train.AdvTrainBatch`` calls it; ``native_disc`` / ``speaker_metrics`` are ``speaker_loss``'s ``native`` / ``metrics``.
+    ``native_sums=True`` (``HRNNHead.forward``) goes to ``g`` and needs the native discriminator."""
     native_disc_default = False    # what ``native=None`` picks: the torch chain, until profiles/adv_kbench.json decides otherwise
 
     def __init__(self, feat_size=39, n_speakers=35, gamma=0.01):
@@ -239,6 +240,9 @@ class AdvHRNNHead(nn.Module):
         return types.SimpleNamespace(loss=loss, logits2=logits2)
 
     def forward(self, inp, len0, speakers=None, native_disc=None, speaker_metrics=None, **kw):
+        if kw.get('native_sums') and not (speakers is not None and self._native(native_disc)):
+            raise RuntimeError('AdvHRNNHead: native_sums=True needs speakers= and native_disc=True: the torch discriminator forms its '
+                               'bias gradients and its loss with reductions of torch\'s')
         logits, feat = self.g(inp, len0, **kw)
         if speakers is None:
             return logits, self.discriminate(feat, native_disc)

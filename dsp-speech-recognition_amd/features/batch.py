@@ -61,19 +61,30 @@ class _CapturedGraph:
         # a capture with ``capacity=``: the int64 [B + 1] device tensor to write the next batch's offsets into before a
         # replay, and the int32 [1] status word of the offsets kernel (0: a valid table); None otherwise
         self.sample_offsets = self.status = None
+        self.census = None         # a capture with ``census=True``: the ``features.graphcheck.Census`` of the recorded graph
 
     def replay(self):
         self.graph.replay()
         return self.result
 
 
-def _capture(waves, prepare):
+def _kept_census(graph):
+    """The census of a graph recorded with ``keep_graph=True``; the graph is instantiated behind it, as a plain one is when its
+    recording ends."""
+    from .graphcheck import census
+    c = census(graph)
+    graph.instantiate()
+    return c
+
+
+def _capture(waves, prepare, census=False):
     """The capture recipe.  The graph reads ``waves`` at its address, sample after sample: a host array raises TypeError, a
     non-contiguous view (a copy would not see what the caller writes later) ValueError.  Then ``prepare()`` builds what
     the graph owns -- a layout, plan or arena of its own, so that nothing else launches on the graph's tables -- and
     returns ``(queue, hold)``: ``queue()`` puts the launches on torch's current stream and returns their result.  It runs
     twice on a side stream: one eager warm call (it builds handles, long-lived index tables and arenas), then under
-    ``torch.cuda.graph``."""
+    ``torch.cuda.graph``.  ``census=True``: the graph is recorded with ``keep_graph=True`` and its census attached as ``.census``
+    (features/graphcheck.py); False records exactly as before."""
     import torch
     if not _is_device_tensor(waves):
         raise TypeError('capture needs a device tensor')
@@ -87,10 +98,13 @@ def _capture(waves, prepare):
             warm = queue()
         side.synchronize()
         del warm
-        graph = torch.cuda.CUDAGraph()
+        graph = torch.cuda.CUDAGraph(keep_graph=True) if census else torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=side):
             result = queue()
-    return _CapturedGraph(graph, waves, result, hold)
+    g = _CapturedGraph(graph, waves, result, hold)
+    if census:
+        g.census = _kept_census(graph)
+    return g
 
 
 class _BatchLayout:

@@ -74,6 +74,46 @@ def _want_wgrad(who, native_wgrad, default, train):
     return bool(train and (default if native_wgrad is None else native_wgrad))
 
 
+def _want_sums(who, native_sums, default, train):
+    """``native_sums`` resolved, as ``_want_wgrad`` resolves its switch.  It is valid where the device-length training path runs
+    (``device_len=True, device_grad=True`` under a required gradient: ``train``); anywhere else an explicit True raises."""
+    if native_sums and not train:
+        raise RuntimeError(f'{who}: native_sums=True cannot run: it serves the device-length training path (device_len=True, '
+                           'device_grad=True with a gradient required)')
+    return bool(train and (default if native_sums is None else native_sums))
+
+
+class _LinearSums(torch.autograd.Function):
+    """An output layer ``F.linear(feat, W, b)`` whose backward records no reduction of torch's (``native_sums=True``): the forward
+    is the same addmm, so the logits keep their bits; backward: dfeat = g W as a GEMM, dW = g^T feat with db its column sums as
+    the two launches of ``dsp_rows_wgrad`` with T = 1 (features/wgrad.py: ``rows_gemm``)."""
+
+    @staticmethod
+    def forward(ctx, feat, W, b):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(feat, W)
+        return torch.nn.functional.linear(feat, W, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        from .wgrad import rows_gemm
+        if g is None:
+            return None, None, None
+        feat, W = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        need = ctx.needs_input_grad
+        d_feat = g @ W if need[0] else None
+        dW = db = None
+        if need[1] or need[2]:
+            dW, db = rows_gemm(g.unsqueeze(0), feat.detach().unsqueeze(0), colsum=True)
+        return d_feat, dW if need[1] else None, db if need[2] else None
+
+
+def _out_layer(linear, feat, sums):
+    """``linear(feat)``; with ``sums`` through ``_LinearSums``."""
+    return _LinearSums.apply(feat, linear.weight, linear.bias) if sums else linear(feat)
+
+
 def _check_rows_word(who, d_rows, x):
     if not (torch.is_tensor(d_rows) and d_rows.dtype == torch.int32 and d_rows.numel() == 1 and d_rows.device == x.device):
         raise TypeError(f"{who}: d_rows must be a one-element int32 tensor on the input's device")
@@ -616,18 +656,26 @@ class RNNHead(nn.Module):
         self.enc = _DynEnc(feat_size, hidden, layers)
         self.out = nn.Linear(2 * hidden, classes)
 
-    def forward(self, inp, len0, native_enc=None, device_len=False, device_grad=False, native_wgrad=None, rng=None):
+    native_sums_default = False    # what ``native_sums=None`` picks on the device-length training path
+
+    def forward(self, inp, len0, native_enc=None, device_len=False, device_grad=False, native_wgrad=None, rng=None, native_sums=None):
         """inp: [T, B, 39] (zero beyond each utterance's length), len0: lengths (numpy / list / tensor) -> [B, 20].
         ``rng`` is accepted and ignored: this head has no draw site.
         ``device_len=True``: len0 is a [B] int32 tensor on inp's device and is never read from the host (module docstring);
-        ``device_grad=True`` with it serves a required gradient on that path."""
+        ``device_grad=True`` with it serves a required gradient on that path.
+        ``native_sums=True`` (with ``device_len=True, device_grad=True`` under a required gradient; it raises elsewhere): the
+        whole backward off torch's reduction kernels -- ``native_wgrad`` on, the output layer's dW / db as native launches --
+        so that a recorded step holds none.  The logits keep their bits."""
         _check_device_grad('RNNHead', device_len, device_grad)
         if device_len:
-            _check_device_len('RNNHead', inp, len0, self, device_grad)
+            needs_grad = _check_device_len('RNNHead', inp, len0, self, device_grad)
+            sums = _want_sums('RNNHead', native_sums, self.native_sums_default, device_grad and needs_grad)
+            native_wgrad = True if sums else native_wgrad
             d_len, _, info = head_length_info(len0, inp.shape[0], 1)
             y = self.enc(inp, d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad,
                          d_rows=info[0:1] if device_grad else None)             # [T, B, H], zeros behind each end
-            return self.out(_pool_native(y, d_len, info[0:1], grad=device_grad))
+            return _out_layer(self.out, _pool_native(y, d_len, info[0:1], grad=device_grad), sums)
+        _want_sums('RNNHead', native_sums, False, False)
         lens = torch.as_tensor(_lengths(len0))
         y = self.enc(inp, lens, native=native_enc, native_wgrad=native_wgrad)    # [max(len0), B, H], zeros behind each end
         avg = y.sum(0) / lens.to(inp.device, inp.dtype).unsqueeze(1)        # rnn_clf.py:29-30
@@ -652,6 +700,7 @@ class HRNNHead(nn.Module):
     ``rng`` (a ``features.dropout.DeviceRng``): every draw -- the logits' and enc1's inter-layer one -- comes from the device
     generator at its site (features/dropout.py) instead of from torch; enc1 then needs its native training path."""
     hir = 10
+    native_sums_default = False    # what ``native_sums=None`` picks on the device-length training path (``RNNHead.forward``)
 
     def __init__(self, feat_size=39):
         super().__init__()
@@ -675,21 +724,27 @@ class HRNNHead(nn.Module):
         return self.enc2(y[0::self.hir], d_len1, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad, d_rows=rows1, rng=rng,
                          rng_site=gru_site(1)), d_len1, info
 
-    def _forward_device(self, inp, len0, dropout, attn=None, device_grad=False, native_wgrad=None, rng=None):
-        _check_device_len(type(self).__name__, inp, len0, self, device_grad)
+    def _forward_device(self, inp, len0, dropout, attn=None, device_grad=False, native_wgrad=None, rng=None, native_sums=None):
+        needs_grad = _check_device_len(type(self).__name__, inp, len0, self, device_grad)
+        sums = _want_sums(type(self).__name__, native_sums, self.native_sums_default, device_grad and needs_grad)
+        native_wgrad = True if sums else native_wgrad
         y2, d_len1, info = self._levels_device(inp, len0, device_grad, native_wgrad, rng)
         rows = info[1:2]                                                        # ceil(max(len0) / hir), on the device
         if attn is None:
             feat = _pool_native(y2, d_len1, rows, grad=device_grad)
         else:
-            feat = torch.cat([attn(y2, native=True, d_rows=rows, device_grad=device_grad), _pool_native(y2, d_len1, rows, avg=False, grad=device_grad)], dim=1)
-        out = self.out(feat)
+            feat = torch.cat([attn(y2, native=True, d_rows=rows, device_grad=device_grad, native_sums=sums),
+                              _pool_native(y2, d_len1, rows, avg=False, grad=device_grad)], dim=1)
+        out = _out_layer(self.out, feat, sums)
         return (_dropout(out, 0.2, rng, SITE_LOGITS) if dropout else out), feat
 
-    def forward(self, inp, len0, dropout=True, native_enc=None, device_len=False, device_grad=False, native_wgrad=None, rng=None):
+    def forward(self, inp, len0, dropout=True, native_enc=None, device_len=False, device_grad=False, native_wgrad=None, rng=None,
+                native_sums=None):
         _check_device_grad(type(self).__name__, device_len, device_grad)
         if device_len:
-            return self._forward_device(inp, len0, dropout, device_grad=device_grad, native_wgrad=native_wgrad, rng=rng)
+            return self._forward_device(inp, len0, dropout, device_grad=device_grad, native_wgrad=native_wgrad, rng=rng,
+                                        native_sums=native_sums)
+        _want_sums(type(self).__name__, native_sums, False, False)
         y2, len1 = self._levels(inp, len0, native_enc, native_wgrad, rng)
         out, feat = _pool_head(y2, len1, self.out)
         return (_dropout(out, 0.2, rng, SITE_LOGITS) if dropout else out), feat
@@ -755,9 +810,10 @@ def _selfattn_train_forward(ctx, y, W, bW, v, c, d_rows):
     return out
 
 
-def _selfattn_train_backward(ctx, g_out, need, d_rows):
+def _selfattn_train_backward(ctx, g_out, need, d_rows, sums=False):
     """The backward of both: -> the gradients of (y, W, bW, v, c); ``need``: which of the five are wanted.  With ``d_rows`` the
-    kernel leaves exact zeros behind the row count, so the sums over all T rows below are the sums over the block."""
+    kernel leaves exact zeros behind the row count, so the sums over all T rows below are the sums over the block.  ``sums``:
+    the four sums as native launches bounded by ``d_rows`` (features/wgrad.py) in place of torch's."""
     from . import _native as nat
     if g_out is None or not any(need):
         return (None,) * 5
@@ -777,6 +833,16 @@ def _selfattn_train_backward(ctx, g_out, need, d_rows):
             nat.check(lib.dsp_selfattn_pool_backward_batch(*args, st))
         else:
             nat.check(lib.dsp_selfattn_pool_rows_backward_batch(*args, d_rows.data_ptr(), st))
+        if sums:
+            from .wgrad import rows_colsum, rows_gemm
+            g_W = g_bW = None
+            if need[1]:
+                g_W, g_bW = rows_gemm(g_pre, yc, d_rows, colsum=True)
+            elif need[2]:
+                g_bW = rows_colsum(g_pre, None, d_rows)
+            return (g_y, g_W, g_bW if need[2] else None,
+                    rows_colsum(gv.unsqueeze(0)).reshape(1, H) if need[3] else None,
+                    rows_colsum(g_e.unsqueeze(2), None, d_rows) if need[4] else None)
         return (g_y,
                 _rows_gemm(g_pre, yc) if need[1] else None,
                 _rows_sum(g_pre) if need[2] else None,
@@ -788,6 +854,7 @@ class _SelfAttnRowsTrain(torch.autograd.Function):
     """``_SelfAttnTrain`` over the first clamp(*d_rows, 1, T) rows of y, the count read on the device
     (dsp_selfattn_pool_rows_train_batch / dsp_selfattn_pool_rows_backward_batch).  Inputs: (y, d_rows, attn.weight, attn.bias,
     v.weight, v.bias); the parameter gradients are computed as ``_SelfAttnTrain`` computes them."""
+    sums = False                   # ``_SelfAttnRowsSumsTrain``: the four sums of the backward as native launches
 
     @staticmethod
     def forward(ctx, y, d_rows, W, bW, v, c):
@@ -797,8 +864,13 @@ class _SelfAttnRowsTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_out):
         need = ctx.needs_input_grad
-        res = _selfattn_train_backward(ctx, g_out, (need[0],) + tuple(need[2:]), ctx.d_rows)
+        res = _selfattn_train_backward(ctx, g_out, (need[0],) + tuple(need[2:]), ctx.d_rows, ctx._forward_cls.sums)
         return (res[0], None) + tuple(res[1:])
+
+
+class _SelfAttnRowsSumsTrain(_SelfAttnRowsTrain):
+    """``_SelfAttnRowsTrain`` whose backward records no reduction of torch's (``native_sums=True``)."""
+    sums = True
 
 
 class _SelfAttn(nn.Module):
@@ -854,19 +926,24 @@ class _SelfAttn(nn.Module):
         w = torch.softmax(self.v(torch.tanh(self.attn(y))).squeeze(2), 1)       # [B, T]
         return torch.bmm(w.unsqueeze(1), y).squeeze(1)
 
-    def forward(self, y, native=None, d_rows=None, device_grad=False):
+    def forward(self, y, native=None, d_rows=None, device_grad=False, native_sums=False):
         """``d_rows``: a one-element int32 device tensor -- the softmax runs over the first min(*d_rows, T) rows of y only,
         the count read on the device (``dsp_selfattn_pool_rows_batch``); native, and forward only unless
-        ``device_grad=True`` is given: a required gradient then takes ``_SelfAttnRowsTrain``."""
+        ``device_grad=True`` is given: a required gradient then takes ``_SelfAttnRowsTrain``.  ``native_sums=True``: that
+        backward forms its four sums with native launches; it raises where that path does not run."""
         if device_grad and d_rows is None:
             raise ValueError('_SelfAttn: device_grad=True needs d_rows (it is the training form of the device-length path)')
+        if native_sums and not (d_rows is not None and device_grad and _attn_needs_grad(y, self)):
+            raise RuntimeError('_SelfAttn: native_sums=True cannot run: it serves the device-length training path (d_rows and '
+                               'device_grad=True with a gradient required)')
         if d_rows is not None:
             needs_grad = device_grad and _attn_needs_grad(y, self)
             why = self.native_supported(y, train=needs_grad)
             if why is not None:
                 raise RuntimeError(f'_SelfAttn: the native path cannot run: {why}')
             if needs_grad:
-                return _SelfAttnRowsTrain.apply(y, d_rows, self.attn.weight, self.attn.bias, self.v.weight, self.v.bias)
+                fn = _SelfAttnRowsSumsTrain if native_sums else _SelfAttnRowsTrain
+                return fn.apply(y, d_rows, self.attn.weight, self.attn.bias, self.v.weight, self.v.bias)
             return self._run_native(y, d_rows)
         if native is False:
             return self._run_torch(y)
@@ -891,10 +968,11 @@ class HRNNAttHead(HRNNHead):
         self.attn = _SelfAttn(200)
 
     def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False, device_grad=False, native_wgrad=None,
-                rng=None):
+                rng=None, native_sums=None):
         _check_device_grad('HRNNAttHead', device_len, device_grad)
         if device_len:
-            return self._forward_device(inp, len0, dropout, self.attn, device_grad, native_wgrad, rng)
+            return self._forward_device(inp, len0, dropout, self.attn, device_grad, native_wgrad, rng, native_sums)
+        _want_sums('HRNNAttHead', native_sums, False, False)
         y2, len1 = self._levels(inp, len0, native_enc, native_wgrad, rng)
         out, feat = _pool_head(y2, len1, self.out, self.attn, native_attn)
         return (_dropout(out, 0.2, rng, SITE_LOGITS) if dropout else out), feat
@@ -966,6 +1044,16 @@ def _ln_unit(r, eps):
     return (r - r.mean(-1, keepdim=True)) / (r.std(-1, keepdim=True) + eps)
 
 
+def _ln_unit_ones(r, eps):
+    """``_ln_unit`` with the two per-row statistics as products with a column of ones (library GEMMs) in place of torch's
+    reductions, which ``native_sums=True`` keeps out of a recorded step whatever their shape.  The same formula:
+    the mean, the unbiased variance of the centred row."""
+    d = r.shape[-1]
+    ones = r.new_ones(d, 1)
+    c = r - (r @ ones) / d
+    return c / (((c * c) @ ones / (d - 1)).sqrt() + eps)
+
+
 def _rows_gemm(a, b):
     """a [T, B, m], b [T, B, n] -> a^T b [m, n] over all T B rows.  With a wide batch the product is one GEMM per time step,
     summed over t afterwards: a single [m, T B] x [T B, n] product has m n / tile outputs and runs on a handful of workgroups
@@ -981,15 +1069,33 @@ def _rows_sum(a):
     return a.sum(0).sum(0)
 
 
-def attn_param_grads(params, x, M, g_y, da, need=None, eps=1e-3):
+def _rows_sum_torch(a, x=None):
+    """``_rows_sum`` of a, or of a * x."""
+    return _rows_sum(a if x is None else a * x)
+
+
+def _rows_gemm_native(a, b):
+    from .wgrad import rows_gemm
+    return rows_gemm(a, b)
+
+
+def _rows_sum_native(a, x=None):
+    from .wgrad import rows_colsum
+    return rows_colsum(a, x)
+
+
+def attn_param_grads(params, x, M, g_y, da, need=None, eps=1e-3, native=False):
     """The GEMMs and column sums behind the encoder layer's backward (include/dsp_frontend.h: dsp_attn_backward).  params: the
     13 tensors of ``_TransformerEncoder._params()``; x [T, B, d]: the layer's input; M [T, B, d]: the weighted sums
     sum_u A x_b[u] of the tape; g_y [T, B, d]: the gradient of the output; da: the seven row tensors g_r2, g_pre1, g_z1,
     g_r1, g_o, g_q', g_preQ, each [T, B, .].  The row-wise forward values (o, z1, h and the normalised rows) are recomputed
     from M and x; the B T T part is never run.  -> the 13 gradients in the order of ``params``; ``need`` (13 booleans) leaves
     out what is not wanted.  The gain and shift of a skipped LayerNorm (T == 1: the first, B == 1: the second) get None, as
-    they get no gradient from autograd."""
+    they get no gradient from autograd.  ``native``: every sum over the rows -- the products and the column sums -- as the native
+    launches of features/wgrad.py (``rows_gemm``, ``rows_colsum``) in place of torch's GEMMs and reductions, and the row
+    statistics of the two LayerNorms as products with ones (``_ln_unit_ones``); the recomputed forward values stay."""
     T, B, d = x.shape
+    gemm, rsum, ln_unit = (_rows_gemm_native, _rows_sum_native, _ln_unit_ones) if native else (_rows_gemm, _rows_sum_torch, _ln_unit)
     need = [True] * 13 if need is None else list(need)
     res = [None] * 13
     if not any(need):
@@ -997,31 +1103,31 @@ def attn_param_grads(params, x, M, g_y, da, need=None, eps=1e-3):
     wq, wk, wv, a1, b1, wp, bp, w1, c1, w2, c2, a2, b2 = params
     g_r2, g_pre1, g_z1, g_r1, g_o, g_q, g_preq = da
     ln1, ln2 = T > 1, B > 1
-    if need[0]: res[0] = _rows_gemm(x, g_preq).unsqueeze(0)
-    if need[1]: res[1] = (_rows_gemm(g_q, torch.tanh(x @ wq[0])) / float(np.power(d, 0.5))).unsqueeze(0)
-    if need[2]: res[2] = _rows_gemm(M, g_o).unsqueeze(0)
-    if need[4] and ln1: res[4] = _rows_sum(g_z1)
-    if need[6]: res[6] = _rows_sum(g_r1)
-    if need[8]: res[8] = _rows_sum(g_pre1)
-    if need[10]: res[10] = _rows_sum(g_r2)
-    if need[12] and ln2: res[12] = _rows_sum(g_y)
+    if need[0]: res[0] = gemm(x, g_preq).unsqueeze(0)
+    if need[1]: res[1] = (gemm(g_q, torch.tanh(x @ wq[0])) / float(np.power(d, 0.5))).unsqueeze(0)
+    if need[2]: res[2] = gemm(M, g_o).unsqueeze(0)
+    if need[4] and ln1: res[4] = rsum(g_z1)
+    if need[6]: res[6] = rsum(g_r1)
+    if need[8]: res[8] = rsum(g_pre1)
+    if need[10]: res[10] = rsum(g_r2)
+    if need[12] and ln2: res[12] = rsum(g_y)
     if not (need[5] or need[7] or need[9] or (need[3] and ln1) or (need[11] and ln2)):
         return tuple(res)
     o = M @ wv[0]
-    if need[5]: res[5] = _rows_gemm(g_r1, o)
+    if need[5]: res[5] = gemm(g_r1, o)
     if not (need[7] or need[9] or (need[3] and ln1) or (need[11] and ln2)):
         return tuple(res)
     z1 = o @ wp.t() + bp + x
     if ln1:
-        n1 = _ln_unit(z1, eps)
-        if need[3]: res[3] = _rows_sum(g_z1 * n1)
+        n1 = ln_unit(z1, eps)
+        if need[3]: res[3] = rsum(g_z1, n1)
         z1 = n1 * a1 + b1
-    if need[7]: res[7] = _rows_gemm(g_pre1, z1).unsqueeze(2)
+    if need[7]: res[7] = gemm(g_pre1, z1).unsqueeze(2)
     if need[9] or (need[11] and ln2):
         h = torch.relu(z1 @ w1[:, :, 0].t() + c1)
-        if need[9]: res[9] = _rows_gemm(g_r2, h).unsqueeze(2)
+        if need[9]: res[9] = gemm(g_r2, h).unsqueeze(2)
         if need[11] and ln2:
-            res[11] = _rows_sum(g_y * _ln_unit(h @ w2[:, :, 0].t() + c2 + z1, eps))
+            res[11] = rsum(g_y, ln_unit(h @ w2[:, :, 0].t() + c2 + z1, eps))
     return tuple(res)
 
 
@@ -1036,6 +1142,7 @@ class _AttnTrain(torch.autograd.Function):
     """_TransformerEncoder's native training path.  forward: dsp_attn_forward_train (the forward's three launches, which also
     save the tape); backward: dsp_attn_backward (four launches, three when x needs no gradient) and ``attn_param_grads``.
     Inputs: (module, x, the 13 parameters in module order); output: y [T, B, d_model]."""
+    sums = False                   # ``_AttnSumsTrain``: the sums of ``attn_param_grads`` as native launches
 
     @staticmethod
     def forward(ctx, mod, x, *params):
@@ -1082,8 +1189,13 @@ class _AttnTrain(torch.autograd.Function):
                                             torch.cuda.current_stream(dev).cuda_stream))
             a = mod.slf_attn
             rows = [v.view(T, B, n) for v, n in zip(torch.split(da, [T * B * n for n in mod._da_widths()]), mod._da_widths())]
-            grads = attn_param_grads(params, xc, attn_tape_views(tape, T, B, d), g, rows, need, a.layer_norm.eps)
+            grads = attn_param_grads(params, xc, attn_tape_views(tape, T, B, d), g, rows, need, a.layer_norm.eps, ctx._forward_cls.sums)
         return (None, g_x) + tuple(grads)
+
+
+class _AttnSumsTrain(_AttnTrain):
+    """``_AttnTrain`` whose backward records no reduction of torch's over the rows (``native_sums=True``)."""
+    sums = True
 
 
 class _TransformerEncoder(_NativeHandle, nn.Module):
@@ -1161,32 +1273,37 @@ class _TransformerEncoder(_NativeHandle, nn.Module):
                                            torch.cuda.current_stream(dev).cuda_stream))
         return y
 
-    def _run_native_train(self, x):
+    def _run_native_train(self, x, sums=False):
         """The native training path: y attached to the autograd graph.  (The handle is created here, outside any capture.)"""
-        return _AttnTrain.apply(self, x, *self._params())
+        return (_AttnSumsTrain if sums else _AttnTrain).apply(self, x, *self._params())
 
     def _run_torch(self, x):
         return self.pos_ffn(self.slf_attn(x))
 
-    def run(self, x, native=None, refresh=False):
+    def run(self, x, native=None, refresh=False, native_sums=False):
         """``refresh``: what ``_native_handle`` is told on the native paths -- True keeps the handle across an optimiser step and
-        repacks it in place (the ``device_grad=True`` path of ``TransformerHead``), 'always' repacks in any case."""
+        repacks it in place (the ``device_grad=True`` path of ``TransformerHead``), 'always' repacks in any case.
+        ``native_sums=True``: the native training path forms the sums of ``attn_param_grads`` with native launches; it raises
+        where that path does not run."""
+        needs_grad = _attn_needs_grad(x, self)
+        if native_sums and not (native and needs_grad):
+            raise RuntimeError('_TransformerEncoder: native_sums=True cannot run: it serves the native training path '
+                               '(native=True with a gradient required)')
         if native is False:
             return self._run_torch(x)
-        needs_grad = _attn_needs_grad(x, self)
         if native is None and not (self.native_train_default if needs_grad else self.native_default):
             return self._run_torch(x)                                           # (nothing to find out about the native path)
         why = self.native_supported(x, train=needs_grad)
         if why is None:
             if refresh:
                 self._native_handle(x.device, refresh=refresh)                  # (the paths' own call then finds an equal key)
-            return self._run_native_train(x) if needs_grad else self._run_native(x)
+            return self._run_native_train(x, native_sums) if needs_grad else self._run_native(x)
         if native:
             raise RuntimeError(f"_TransformerEncoder: the native {'training path (a gradient is required)' if needs_grad else 'path'} cannot run: {why}")
         return self._run_torch(x)
 
-    def forward(self, x, native=None, refresh=False):
-        return self.run(x, native, refresh)
+    def forward(self, x, native=None, refresh=False, native_sums=False):
+        return self.run(x, native, refresh, native_sums)
 
 
 class TransformerHead(nn.Module):
@@ -1195,6 +1312,7 @@ class TransformerHead(nn.Module):
     every 5th row into a second one, pooled.  ``dropout=False`` leaves both F.dropout calls out.  -> (logits, feat, attn_out).
     ``rng`` (a ``features.dropout.DeviceRng``): both draws come from the device generator (sites 2 and 0, features/dropout.py)."""
     hir = 5
+    native_sums_default = False    # what ``native_sums=None`` picks on the device-length training path (``RNNHead.forward``)
 
     def __init__(self):
         super().__init__()
@@ -1205,12 +1323,14 @@ class TransformerHead(nn.Module):
         self.hidden_size = 200
 
     def forward(self, inp, len0, dropout=True, native_enc=None, native_attn=None, device_len=False, device_grad=False, native_wgrad=None,
-                rng=None):
+                rng=None, native_sums=None):
         _check_device_grad('TransformerHead', device_len, device_grad)
         if device_len:
-            _check_device_len('TransformerHead', inp, len0, self, device_grad)
+            needs_grad = _check_device_len('TransformerHead', inp, len0, self, device_grad)
+            sums = _want_sums('TransformerHead', native_sums, self.native_sums_default, device_grad and needs_grad)
+            native_wgrad = True if sums else native_wgrad
             d_len, d_len1, info = head_length_info(len0, inp.shape[0], self.hir)
-            attn_out = self.attn_enc(inp, native=True, refresh=device_grad)
+            attn_out = self.attn_enc(inp, native=True, refresh=device_grad, native_sums=sums)
             a = _dropout(attn_out, 0.5, rng, SITE_ATTN) if dropout else attn_out
             rows0, rows1 = (info[0:1], info[1:2]) if device_grad else (None, None)
             y = self.rnn_enc_1(torch.cat([inp, a], 2), d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad,
@@ -1218,8 +1338,9 @@ class TransformerHead(nn.Module):
             y2 = self.rnn_enc_2(y[0::self.hir], d_len1, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad, d_rows=rows1,
                                 rng=rng, rng_site=gru_site(1))
             feat = _pool_native(y2, d_len1, info[1:2], grad=device_grad)
-            out = self.out(feat)
+            out = _out_layer(self.out, feat, sums)
             return (_dropout(out, 0.2, rng, SITE_LOGITS) if dropout else out), feat, attn_out
+        _want_sums('TransformerHead', native_sums, False, False)
         len0 = _lengths(len0)
         len1 = (len0 + self.hir - 1) // self.hir
         attn_out = self.attn_enc(inp, native=native_attn)
@@ -1607,6 +1728,7 @@ class HMRNNHead(nn.Module):
     equal the real class's ``named_parameters()``.  ``rng`` (a ``features.dropout.DeviceRng``): both draws come from the device
     generator (sites 1 and 0, features/dropout.py)."""
     hir = 5
+    native_sums_default = False    # what ``native_sums=None`` picks on the device-length training path (``RNNHead.forward``)
 
     def __init__(self, feat_size=39):
         super().__init__()
@@ -1616,10 +1738,12 @@ class HMRNNHead(nn.Module):
         self.out = nn.Linear(600, 20)
 
     def forward(self, inp, len0, dropout=True, native=None, native_enc=None, device_len=False, device_grad=False, native_wgrad=None,
-                rng=None):
+                rng=None, native_sums=None):
         _check_device_grad('HMRNNHead', device_len, device_grad)
         if device_len:
-            _check_device_len('HMRNNHead', inp, len0, self, device_grad)
+            needs_grad = _check_device_len('HMRNNHead', inp, len0, self, device_grad)
+            sums = _want_sums('HMRNNHead', native_sums, self.native_sums_default, device_grad and needs_grad)
+            native_wgrad = True if sums else native_wgrad
             d_len, _, info = head_length_info(len0, inp.shape[0], 1)
             enc = self.enc1(inp, d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad,
                             d_rows=info[0:1] if device_grad else None, rng=rng, rng_site=gru_site(0))   # [T, B, 200], zeros behind each end
@@ -1628,8 +1752,9 @@ class HMRNNHead(nn.Module):
             last = self.enc2.run(enc, None, lens=d_len, device_len=True, device_grad=device_grad, native_wgrad=native_wgrad,
                                  d_rows=info[0:1] if device_grad else None).last_h2      # both passes stop at max(len0)
             feat = torch.cat([_pool_native(enc, d_len, info[0:1], grad=device_grad), last], dim=1)
-            out = self.out(feat)
+            out = _out_layer(self.out, feat, sums)
             return (_dropout(out, 0.2, rng, SITE_LOGITS) if dropout else out), feat
+        _want_sums('HMRNNHead', native_sums, False, False)
         len0 = _lengths(len0)
         enc = self.enc1(inp, len0, native=native_enc, native_wgrad=native_wgrad, rng=rng, rng_site=gru_site(0))   # [max(len0), B, 200]
         if dropout:

@@ -247,12 +247,12 @@ def ensemble_decide(logits, rules, feat=None, valid=None, stream=None):
     return pred, prob, used, dec
 
 
-def _capture_scored(waves, prepare, score):
+def _capture_scored(waves, prepare, score, census=False):
     """``_capture``; the warm call in front of the recording scores a batch, so the metrics block is put back behind it."""
     if score is None:
-        return _capture(waves, prepare)
+        return _capture(waves, prepare, census)
     saved = score[1].state.clone()
-    g = _capture(waves, prepare)                          # (it synchronises its side stream behind the warm call)
+    g = _capture(waves, prepare, census)                       # (it synchronises its side stream behind the warm call)
     score[1].state.copy_(saved)
     return g
 
@@ -470,8 +470,9 @@ class EnsembleBatch(_EnsembleTail):
                     torch.cuda.current_stream(dev))
         return self._tail(inp, len0, None, [(lay, clips, self.rate, None)], head_kwargs, None if arena is None else [arena], score)
 
-    def capture(self, waves, sample_offsets, capacity=None, labels=None, metrics=None, **head_kwargs):
-        """``labels=`` / ``metrics=`` as ``run``: the scoring launch is recorded behind the gate, ``labels`` is read in place on every
+    def capture(self, waves, sample_offsets, capacity=None, labels=None, metrics=None, census=False, **head_kwargs):
+        """``census=True`` attaches ``g.census``, the node census of the recorded graph (features/graphcheck.py); the default records
+        exactly as before.  ``labels=`` / ``metrics=`` as ``run``: the scoring launch is recorded behind the gate, ``labels`` is read in place on every
         replay, and ``capture`` itself leaves the metrics block as it found it.
         ONE HIP graph of the whole path over device-resident ``waves`` (a contiguous tensor, int16 / float32):
         ``g = eb.capture(waves, so, dropout=False)``; write new clips into ``waves`` -- of the same lengths, unless the graph
@@ -509,7 +510,7 @@ class EnsembleBatch(_EnsembleTail):
                 box.append(lay)
             m0, arena = self._m0(lay, waves.device), {}
             return (lambda: self._chain(clips, lay, m0, arena, head_kwargs, score)), [lay, m0, arena, clips, list(self.rules), score]
-        g = _capture_scored(waves, prepare, score)
+        g = _capture_scored(waves, prepare, score, census)
         if box:
             g.sample_offsets, g.status = box[0].sample_offsets_in, box[0].status
         return g

@@ -58,10 +58,18 @@ class _Phase:
             raise ValueError(f'{what}: {len(self.clips)} clips with {len(self.labels)} labels (at least one clip is needed)')
         self.order = list(range(len(self.clips)))
         self.graph = self.buf = self.lab = self.jit = None
+        self.part = None           # the trailing partial batch's own buffers and graph (``fit(native_sums=True)``): a _Slot
 
     def batches(self, batch_size):
         for s in range(0, len(self.order), batch_size):
             yield self.order[s:s + batch_size]
+
+
+class _Slot:
+    """The capacity buffers and the recorded graph of one batch size."""
+
+    def __init__(self):
+        self.graph = self.buf = self.lab = self.jit = None
 
 
 class Trainer:
@@ -118,12 +126,26 @@ class Trainer:
         clips = [ph.clips[i] for i in idx]
         return np.concatenate(clips).astype(dtype, copy=False), _offsets(clips), ph.labels[idx]
 
-    def _train_step(self, ph, idx, B, capacity, np_dtype, torch_dtype, recordable):
+    def _train_step(self, ph, idx, B, capacity, np_dtype, torch_dtype, recordable, native_sums=False):
         import torch
         from . import metrics as M
         flat, so, labels = self._flat(ph, idx, np_dtype)
         jitter = self.tb.draw_jitter(len(idx), self.jitter_rng)
         m, kw = self.train_metrics, self.head_kwargs
+        if native_sums:                                    # any size records, the partial batch through a graph of its own
+            kw = dict(kw, native_sums=True)
+            slot = ph
+            if len(idx) != B:
+                slot = ph.part = ph.part or _Slot()
+            self._buffers(slot, len(idx), capacity, torch_dtype, True)
+            self._upload(slot, flat, labels, jitter)
+            if slot.graph is None:
+                slot.graph = self.tb.capture(slot.buf, so, slot.lab, slot.jit, optimizer=self.opt, capacity=capacity, loss='native',
+                                             metrics=m, **kw)
+                self.train_graphs += 1
+            slot.graph.sample_offsets.copy_(torch.from_numpy(so))
+            slot.graph.replay()
+            return
         if len(idx) == B:                                  # a full batch: the capacity layout, recorded where it may be
             self._buffers(ph, B, capacity, torch_dtype, True)
             self._upload(ph, flat, labels, jitter)
@@ -157,7 +179,8 @@ class Trainer:
             self.eb.run(flat, so, sync_free=True, labels=torch.from_numpy(labels).to(self.device), metrics=m, **kw)
 
     # ---- the run --------------------------------------------------------------------------------------------------
-    def fit(self, train, val, lr, epochs=10, early_stop=3, batch_size=32, capacity=None, on_improve=None, on_epoch=None):
+    def fit(self, train, val, lr, epochs=10, early_stop=3, batch_size=32, capacity=None, on_improve=None, on_epoch=None,
+            native_sums=False):
         """model.py:219-240.  ``train`` / ``val``: ``(feat, labels)`` with ``feat = [(sig, rate), ...]`` (reader.py:84) and one
         class index per clip.  Per epoch: ``optimizer.reset()`` and ``set_lr(lr)`` (model.py:140 makes a new Adam); the training
         list in ``epoch_order``; full batches through ONE capacity graph of the whole step -- recorded at the first full batch
@@ -170,6 +193,12 @@ class Trainer:
         ``lr *= 0.8``; otherwise ``lr *= 0.5`` and one life less, stopping at none; ``head.adjust_param()`` where there is one;
         the head back in ``train()``.  ``adjust_param`` changes a value the recorded launches took by value, so both graphs
         are recorded anew in the next epoch for such a head.
+
+        ``native_sums=True``: the head is trained with ``native_sums=True`` (features/classifier.py), with which ``capture`` serves
+        ANY batch size; every full batch goes through the capacity graph whatever ``batch_size`` is, and the trailing partial
+        batch -- whose size is the same in every epoch -- through a second capacity graph of its own.  Both are recorded anew
+        after ``adjust_param``.  ``train_graphs`` in each epoch's entry (and on the trainer) counts the training graphs recorded
+        so far.
 
         ``capacity``: samples of the capacity buffers; default: the sum of the ``batch_size`` longest clips of both sets.
         -> the history: per epoch a namespace (epoch, lr: the epoch's rate, train / val: ``Metrics.result()``, improved, stop,
@@ -191,6 +220,7 @@ class Trainer:
         if capacity is None:
             capacity = int(sum(sorted((len(c) for c in all_clips), reverse=True)[:B]))
         recordable = B in CAPTURE_VERIFIED.get(type(self.head).__name__, ())
+        self.train_graphs = 0
         sched = Schedule(lr, early_stop)
         history = []
         for epoch in range(int(epochs)):
@@ -201,7 +231,7 @@ class Trainer:
             self.train_metrics.reset()
             epoch_order(tr.order)
             for idx in tr.batches(B):
-                self._train_step(tr, idx, B, capacity, np_dtype, torch_dtype, recordable)
+                self._train_step(tr, idx, B, capacity, np_dtype, torch_dtype, recordable, native_sums)
             train_res = self.train_metrics.result()
             self.head.eval()
             self.val_metrics.reset()
@@ -214,7 +244,7 @@ class Trainer:
             if improved and on_improve is not None:
                 on_improve(epoch, val_res.accuracy)
             history.append(types.SimpleNamespace(epoch=epoch, lr=lr_now, train=train_res, val=val_res, improved=improved, stop=stop,
-                                                 train_order=list(tr.order), val_order=list(va.order)))
+                                                 train_order=list(tr.order), val_order=list(va.order), train_graphs=self.train_graphs))
             if on_epoch is not None:
                 on_epoch(history[-1])
             if stop:
@@ -223,5 +253,7 @@ class Trainer:
             if hasattr(self.head, 'adjust_param'):
                 self.head.adjust_param()
                 tr.graph = va.graph = None                 # the recorded launches hold the old value
+                if tr.part is not None:
+                    tr.part.graph = None
             self.head.train()
         return history

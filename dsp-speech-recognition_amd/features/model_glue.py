@@ -257,8 +257,9 @@ class ModelFeatureBatch:
             hold += self._timefeat_streams(lay, st, dev, (d_inp, d_dst_col, n_cols, row_width, col))
         return hold
 
-    def capture(self, waves, layout, capacity=None):
-        """A HIP graph of ``enqueue`` over device-resident ``waves`` (torch tensor, int16 / float32) and a prepared layout:
+    def capture(self, waves, layout, capacity=None, census=False):
+        """``census=True`` attaches ``g.census``, the node census of the recorded graph (features/graphcheck.py); the default records
+        exactly as before.  A HIP graph of ``enqueue`` over device-resident ``waves`` (torch tensor, int16 / float32) and a prepared layout:
         ``g = mfb.capture(waves, lay)``; put new clips into ``waves`` -- of the same lengths, unless the layout is a capacity
         layout -- and call ``g.replay()`` ->
         (inp [max_len, B, 39], len0 [B] int32), both on the device, valid after the current stream's work (no host
@@ -286,7 +287,7 @@ class ModelFeatureBatch:
                                  torch.cuda.current_stream(dev))
                     return inp, len0
                 return queue, [m0, layout]
-            return _capture(waves, prepare)
+            return _capture(waves, prepare, census)
 
         from .pipeline import CapacityLayout, check_capacity_wave
         lay_box = []
@@ -315,7 +316,7 @@ class ModelFeatureBatch:
                              torch.cuda.current_stream(dev))
                 return inp, len0, seg
             return queue, [m0, lay]
-        g = _capture(waves, prepare_capacity)
+        g = _capture(waves, prepare_capacity, census)
         g.sample_offsets, g.status = lay_box[0].sample_offsets_in, lay_box[0].status
         return g
 

@@ -79,6 +79,7 @@ class _CapturedStep:
         self.rng = rng
         # a capture with ``capacity=``: where the next batch's offsets go before a replay, and the offsets kernel's status word
         self.sample_offsets = self.status = None
+        self.census = None         # ``capture(..., census=True)`` or a capture outside the table: the recorded graph's census
 
     def replay(self):
         self.graph.replay()
@@ -217,8 +218,10 @@ class TrainBatch:
                            spec=spec)
 
     def capture(self, waves, sample_offsets, labels, jitter=None, optimizer=None, capacity=None, loss='torch', metrics=None,
-                **head_kwargs):
-        """``loss='native'`` / ``metrics=`` as ``run``: the recorded loss is the native call, its backward launches nothing of its
+                census=False, **head_kwargs):
+        """``census=True``: the graph is recorded with ``keep_graph=True`` and ``g.census`` is its node census
+        (features/graphcheck.py); the default records exactly as before.
+        ``loss='native'`` / ``metrics=`` as ``run``: the recorded loss is the native call, its backward launches nothing of its
         own, and every replay updates ``metrics`` (``capture`` itself leaves the block as it found it).
         ONE HIP graph of a whole step; without ``optimizer`` all of it but the optimiser: ``g = tb.capture(waves, so, labels, jitter, dropout=False)``;
         ``g.replay()`` does, in order, (1) a refresh of every native handle of the head -- the repack of whatever the
@@ -255,14 +258,18 @@ class TrainBatch:
         created by the warm-up on the capture stream whatever the caller still holds.  The returned ``loss`` and ``logits``
         are detached.
 
-        Only the heads and batch sizes of ``CAPTURE_VERIFIED`` are served: a recorded multi-workgroup reduction of torch's
-        has been seen to go wrong on replay on this stack, so a head / size pair is recorded only where
-        tests/test_gpu_train_capture.py has compared a second replay with the eager step bit for bit.  Anything else raises
-        NotImplementedError; ``run`` serves every head and size."""
+        A head / size pair of ``CAPTURE_VERIFIED`` is served as it always was: a recorded multi-workgroup reduction of torch's
+        has been seen to go wrong on replay on this stack, so those pairs are the ones where
+        tests/test_gpu_train_capture.py has compared a second replay with the eager step bit for bit.  ANY OTHER batch size of
+        the library's heads is served with ``native_sums=True`` among the head's keywords and ``loss='native'``: the step then
+        launches no reduction of torch's, and ``capture`` looks instead of trusting -- it records with ``keep_graph=True``, takes
+        the census, and raises RuntimeError carrying it (the graph is dropped) if the graph holds a memset node of more than 4
+        bytes or one of torch's reductions (``at::native::reduce_kernel``; DESIGN 7.21).  Without those keywords anything outside the
+        table raises NotImplementedError; ``run`` serves every head and size."""
         spec = _loss_spec(loss, metrics)
         so = np.ascontiguousarray(sample_offsets, dtype=np.int64)
         B = len(so) - 1
-        clips = self._check_capture(waves, B, labels, jitter)
+        clips, check = self._check_capture(waves, B, labels, jitter, head_kwargs, loss)
         dev = waves.device
         if capacity is None:
             lay = self.features.pipe.prepare(so, 0)            # the graph's own: nothing else launches on its tables
@@ -273,13 +280,14 @@ class TrainBatch:
             lay.write_offsets(so)
         m0 = self._m0(lay, dev)
         g = self._record(dev, lambda alias: self._chain(clips, lay, m0, labels, jitter, head_kwargs, alias, spec), optimizer,
-                         [lay, m0, clips, labels, jitter], head_kwargs.get('rng'), spec)
+                         [lay, m0, clips, labels, jitter], head_kwargs.get('rng'), spec, census, check)
         if capacity is not None:
             g.sample_offsets, g.status = lay.sample_offsets_in, lay.status
         return g
 
-    def _check_capture(self, waves, B, labels, jitter):
-        """The refusals of ``capture`` in front of its layout -> the clips as a flat view of ``waves``."""
+    def _check_capture(self, waves, B, labels, jitter, head_kwargs=None, loss='torch'):
+        """The refusals of ``capture`` in front of its layout -> (the clips as a flat view of ``waves``, whether the recorded
+        graph has to pass the census: a pair outside the table, served because of ``native_sums=True`` and ``loss='native'``)."""
         import torch
         if not _is_device_tensor(waves):
             raise TypeError('capture needs a device tensor')
@@ -289,7 +297,10 @@ class TrainBatch:
         clips = waves.reshape(-1)                              # a view: the same memory
         _wave_dtype_of(clips)
         kind = type(self.head).__name__
+        check = False
         if B not in self._verified.get(kind, ()):
+            check = kind in self._verified and (head_kwargs or {}).get('native_sums') is True and loss == 'native'
+        if B not in self._verified.get(kind, ()) and not check:
             raise NotImplementedError(f'capture: {kind} at B = {B} is not in CAPTURE_VERIFIED ({self._verified}): a replay of this head '
                                       'and size has not been compared with the eager step; use run()')
         if not (_is_device_tensor(labels) and labels.dtype == torch.int64 and tuple(labels.shape) == (B,) and labels.is_contiguous()):
@@ -297,7 +308,7 @@ class TrainBatch:
         if jitter is not None and not (_is_device_tensor(jitter) and jitter.dtype == torch.int64 and tuple(jitter.shape) == (B, 2)
                                        and jitter.is_contiguous()):
             raise TypeError('capture needs jitter as a contiguous [B, 2] int64 device tensor (or None): the graph reads it in place')
-        return clips
+        return clips, check
 
     @staticmethod
     def _backward(out, native):
@@ -308,12 +319,13 @@ class TrainBatch:
         else:
             out.loss.backward()
 
-    def _record(self, dev, chain, optimizer, hold, rng=None, spec=(False, None)):
+    def _record(self, dev, chain, optimizer, hold, rng=None, spec=(False, None), census=False, check=False):
         """The check of ``optimizer`` and the recipe of ``capture``: ``chain(alias)`` queues front end, head and loss on torch's current
         stream with the parameter aliases standing in, and returns the namespace of ``run``.  ``rng``: the generator the chain
         advances; the warm-up steps move it, so its state is put back behind them (recording runs nothing).  ``spec``:
         ``_loss_spec``'s pair; the metrics block is put back like the generator, and a native loss is differentiated from
-        ``features.metrics.unit_grad``."""
+        ``features.metrics.unit_grad``.  ``census``: record with ``keep_graph=True`` and attach the census; ``check``: the same, and
+        a graph with a memset node of more than 4 bytes or a reduction kernel of torch's is refused (``capture``)."""
         import torch
         from .classifier import _NativeHandle
         names = [n for n, p in self.head.named_parameters() if p.requires_grad]
@@ -366,7 +378,7 @@ class TrainBatch:
             del warm
             for v in leaves:
                 v.grad = None
-            graph = torch.cuda.CUDAGraph()
+            graph = torch.cuda.CUDAGraph(keep_graph=True) if (census or check) else torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=side):
                 result = step(True)
         grads = [v.grad for v in leaves]
@@ -374,7 +386,22 @@ class TrainBatch:
             p.grad = None
         if optimizer is not None:
             optimizer._bound = bound                           # the recorded binding has not run yet
-        return _CapturedStep(graph, result, params, grads, list(hold) + [leaves, metrics], optimizer, rng)
+        found = None
+        if census or check:
+            from .graphcheck import census as graph_census
+            found = graph_census(graph)
+            bad = found.torch_reductions()                 # (a '?' is a library GEMM launched from a code object: the runtime names none)
+            if check and (found.wide_memsets or bad):
+                del graph, result, grads                       # the recording is dropped: nothing of it ever runs
+                raise RuntimeError(f'capture: the recorded step holds {found.wide_memsets} memset node(s) of more than 4 bytes (the widest '
+                                   f'{found.widest_memset_bytes}) and {len(bad)} reduction kernel(s) of torch\'s {sorted(set(bad))[:4]}: such a '
+                                   f'graph has been seen to replay wrong here (DESIGN 7.12) and is not served.  Census: {found}')
+            graph.instantiate()
+        # (the head too: its modules own the native handles whose packed weights the recorded kernels read, and a module's
+        # ``__del__`` destroys its handle -- a step that outlived its head would replay on freed memory)
+        g = _CapturedStep(graph, result, params, grads, list(hold) + [leaves, metrics, self.head], optimizer, rng)
+        g.census = found
+        return g
 
 
 class MixedRateTrainBatch(TrainBatch):
@@ -421,8 +448,8 @@ class MixedRateTrainBatch(TrainBatch):
         return self._mixed_chain(waves, arena, labels, jitter is not None, head_kwargs, spec=spec)
 
     def capture(self, waves, sample_offsets, rates, labels, jitter=None, optimizer=None, capacity=None, loss='torch', metrics=None,
-                **head_kwargs):
-        """``loss=`` / ``metrics=`` as ``TrainBatch.capture``.  ``TrainBatch.capture(..., capacity=N)`` for a mixed-rate batch: ONE HIP graph of the handle refresh, the grouping
+                census=False, **head_kwargs):
+        """``census=``, ``loss=`` / ``metrics=`` and the batch sizes served as ``TrainBatch.capture``.  ``TrainBatch.capture(..., capacity=N)`` for a mixed-rate batch: ONE HIP graph of the handle refresh, the grouping
         front end, forward, loss, backward and -- with ``optimizer=`` -- the ``DeviceAdam`` step.  Before a ``replay()`` write
         the next batch's clips into ``waves``, its offsets into ``g.sample_offsets`` (int64 [B + 1]), its rates into ``g.rates``
         (int32 [B]), the labels into ``labels`` and -- if recorded with jitter -- its rows into ``g.jitter`` (int64 [B, 2]: the
@@ -431,7 +458,7 @@ class MixedRateTrainBatch(TrainBatch):
         spec = _loss_spec(loss, metrics)
         fe = self.features
         B = fe._n_utt(sample_offsets)
-        clips = self._check_capture(waves, B, labels, jitter)
+        clips, check = self._check_capture(waves, B, labels, jitter, head_kwargs, loss)
         if capacity is None:
             raise ValueError('MixedRateTrainBatch serves capacity routes only: pass capacity=N')
         check_capacity_wave(waves, capacity)
@@ -439,7 +466,7 @@ class MixedRateTrainBatch(TrainBatch):
         arena.write(sample_offsets, rates, jitter)
         use_jitter = jitter is not None
         g = self._record(waves.device, lambda alias: self._mixed_chain(clips, arena, labels, use_jitter, head_kwargs, alias, spec),
-                         optimizer, [arena, clips, labels], head_kwargs.get('rng'), spec)
+                         optimizer, [arena, clips, labels], head_kwargs.get('rng'), spec, census, check)
         g.sample_offsets, g.rates, g.status = arena.sample_offsets, arena.rates, arena.status
         g.jitter = arena.jitter if use_jitter else None
         return g
@@ -544,17 +571,18 @@ class AdvTrainBatch(TrainBatch):
                            _adv=(speakers, speaker_metrics, native_disc), **head_kwargs)
 
     def capture(self, waves, sample_offsets, labels, speakers, jitter=None, optimizer=None, capacity=None, loss='torch', metrics=None,
-                speaker_metrics=None, native_disc=None, **head_kwargs):
+                speaker_metrics=None, native_disc=None, census=False, **head_kwargs):
         """``TrainBatch.capture`` with ``speakers``: the recorded step reads them in place on every replay, and every replay
         updates ``speaker_metrics`` (``capture`` itself leaves the block as it found it).  ``ADV_CAPTURE_VERIFIED['AdvHRNNHead']``
-        governs the batch sizes."""
+        governs the batch sizes as ``CAPTURE_VERIFIED`` governs ``TrainBatch.capture``'s: any other size is served with
+        ``native_sums=True`` (which needs ``native_disc=True``) and ``loss='native'``, checked by the census.  ``census=`` as there."""
         import torch
         speakers = self._adv_spec(speakers, self._n_utt(sample_offsets), loss, speaker_metrics, native_disc, self.head, device_tensor=True)
         from .metrics import unit_grad
         unit_grad(speakers.device)                             # (made here, not while recording)
         saved = None if speaker_metrics is None else speaker_metrics.state.clone()
         g = super().capture(waves, sample_offsets, labels, jitter=jitter, optimizer=optimizer, capacity=capacity, loss=loss,
-                            metrics=metrics, _adv=(speakers, speaker_metrics, native_disc), **head_kwargs)
+                            metrics=metrics, census=census, _adv=(speakers, speaker_metrics, native_disc), **head_kwargs)
         if saved is not None:                                  # the warm-up steps moved it; recording ran nothing
             speaker_metrics.state.copy_(saved)
         g.hold.append((speakers, speaker_metrics, self.head.d_gamma))

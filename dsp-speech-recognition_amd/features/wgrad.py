@@ -200,3 +200,74 @@ def hm_param_grads_native(params, x, state_in, h_1, h_2, z_1, dfs1, dfs2, need=N
     """``classifier.hm_param_grads`` through the native launches, on torch's current stream."""
     plan = hm_wgrad_plan(params, x, state_in, h_1, h_2, z_1, dfs1, dfs2, need)
     return plan.finish(run_plan(plan, d_rows, torch.cuda.current_stream(x.device).cuda_stream))
+
+
+def rows_colsum(a, x=None, d_rows=None):
+    """``sum_{t < R, b} a[t, b, :] * (x[t, b, :] if x is given else 1)`` as the two native launches of ``dsp_rows_colsum``
+    (include/dsp_frontend.h; csrc/kernels_reduce.h) on torch's current stream -> a new [cols] tensor.
+
+    ``a`` (and ``x``, of the same shape): a float32 device tensor [T, B, cols] read through its strides -- any view with a unit
+    column stride is read where it lies (``da[:, :, d, :n]``), any other is copied first; a [B, cols] tensor is T = 1 and a
+    [T, B] tensor of scalars is ``a.unsqueeze(2)``.  ``d_rows``: a one-element int32 tensor on the same device, the row bound
+    R = clamp(d_rows[0], 1, T) read when the kernels run (rows behind it are never read), or None for R = T.  fp32 in a fixed
+    order: the same bits on every run; no atomics, no memset, nothing read back or synchronised, so the call can be captured.
+    The result and the scratch come from torch's allocator."""
+    from . import _native as nat
+    lib = nat.load()
+    for name, t in (('a', a), ('x', x)):
+        if t is None:
+            continue
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3):
+            raise TypeError(f'rows_colsum: {name} must be a float32 device tensor [T, B, cols]')
+    if x is not None and (x.shape != a.shape or x.device != a.device):
+        raise ValueError(f'rows_colsum: x {tuple(x.shape)} on {x.device} does not match a {tuple(a.shape)} on {a.device}')
+    if d_rows is not None and not (torch.is_tensor(d_rows) and d_rows.dtype == torch.int32 and d_rows.numel() == 1 and d_rows.device == a.device):
+        raise TypeError("rows_colsum: d_rows must be a one-element int32 tensor on a's device")
+    a, x = _rows_view(a), None if x is None else _rows_view(x)
+    T, B, cols = a.shape
+    nbytes = nat.c_i64(0)
+    nat.check_value(lib.dsp_rows_colsum_scratch_bytes(T, B, cols, nat.C.byref(nbytes)), 'rows_colsum: invalid sizes')
+    out = torch.empty(cols, dtype=torch.float32, device=a.device)
+    scratch = torch.empty(nbytes.value // 4, dtype=torch.float32, device=a.device)
+    op = lambda t: nat.RowsOperand(t.data_ptr(), t.stride(0), t.stride(1), cols, 0)
+    oa, ox = op(a), None if x is None else op(x)
+    with torch.cuda.device(a.device):
+        nat.check_value(lib.dsp_rows_colsum(nat.C.byref(oa), None if ox is None else nat.C.byref(ox), T, B,
+                                            None if d_rows is None else d_rows.data_ptr(), out.data_ptr(), scratch.data_ptr(),
+                                            nbytes.value, torch.cuda.current_stream(a.device).cuda_stream), 'rows_colsum: invalid argument')
+    return out
+
+
+def _rows_view(t):
+    """A [T, B, cols] float32 device tensor as the launches read it: itself where its column stride is 1, else a copy."""
+    return t if t.shape[2] == 1 or t.stride(2) == 1 else t.contiguous()
+
+
+def rows_gemm(a, x, d_rows=None, colsum=False):
+    """``a^T x`` over the rows: a [T, B, m], x [T, B, n] -> [m, n] = sum_{t < R, b} a[t, b, :]^T (x) x[t, b, :] as the two launches
+    of ``dsp_rows_wgrad`` (no shift, no scale) on torch's current stream; with ``colsum`` also a's column sums [m] from the same
+    launches -> (product, sums).  The operands are read through their strides (``rows_colsum`` has the rules); ``d_rows`` as
+    there.  ``nn.Linear``'s dW / db is ``rows_gemm(g.unsqueeze(0), feat.unsqueeze(0), colsum=True)``."""
+    from . import _native as nat
+    lib = nat.load()
+    for name, t in (('a', a), ('x', x)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3):
+            raise TypeError(f'rows_gemm: {name} must be a float32 device tensor [T, B, cols]')
+    if x.shape[:2] != a.shape[:2] or x.device != a.device:
+        raise ValueError(f'rows_gemm: x {tuple(x.shape)} on {x.device} does not match a {tuple(a.shape)} on {a.device}')
+    if d_rows is not None and not (torch.is_tensor(d_rows) and d_rows.dtype == torch.int32 and d_rows.numel() == 1 and d_rows.device == a.device):
+        raise TypeError("rows_gemm: d_rows must be a one-element int32 tensor on a's device")
+    a, x = _rows_view(a), _rows_view(x)
+    T, B, m = a.shape
+    n = x.shape[2]
+    f32 = dict(dtype=torch.float32, device=a.device)
+    nbytes = nat.c_i64(0)
+    nat.check_value(lib.dsp_rows_wgrad_scratch_bytes(T, B, m, n, nat.C.byref(nbytes)), 'rows_gemm: invalid sizes')
+    c, cs = torch.empty(m, n, **f32), torch.empty(m, **f32) if colsum else None
+    scratch = torch.empty(nbytes.value // 4, **f32)
+    oa, ox = nat.RowsOperand(a.data_ptr(), a.stride(0), a.stride(1), m, 0), nat.RowsOperand(x.data_ptr(), x.stride(0), x.stride(1), n, 0)
+    with torch.cuda.device(a.device):
+        nat.check_value(lib.dsp_rows_wgrad(nat.C.byref(oa), nat.C.byref(ox), 0, None, 0, None, T, B, None if d_rows is None else d_rows.data_ptr(),
+                                           c.data_ptr(), None if cs is None else cs.data_ptr(), scratch.data_ptr(), nbytes.value,
+                                           torch.cuda.current_stream(a.device).cuda_stream), 'rows_gemm: invalid argument')
+    return (c, cs) if colsum else c

@@ -1363,6 +1363,56 @@ int dsp_adv_disc_train(const float* d_feat, int64_t ld_feat, int32_t B, int32_t 
                        float* d_dfeat, int64_t ld_dfeat, float* d_dW1, float* d_db1, float* d_dW2, float* d_db2, void* d_state,
                        int32_t wrong_capacity, void* d_work, int64_t work_bytes, void* stream);
 
+/* ---- the column sums of the training step, bounded by a row count read on the device (csrc/kernels_reduce.h) --------------
+ *
+ * The sums over all rows that the heads' backward passes form beside their GEMMs: a.sum(0).sum(0) of a [T, B, n] buffer,
+ * (g * n1).sum(0).sum(0), g.sum(0) of a [B, n] buffer (T = 1), g.sum() of a [T, B] buffer (cols = 1, stride_t = B,
+ * stride_b = 1).  A library reduction of these shapes spreads one sum over workgroups that meet through counters a memset
+ * zeroes; these are two plain launches.  fp32, a fixed order.  No atomics, no memset, no grid barrier, nothing allocated or
+ * synchronised: the same bits on every run, capturable.
+ *
+ * dsp_rows_colsum:  d_out[c] = sum_{t < R, b < B} a[t, b, c] * (x ? x[t, b, c] : 1)     c < a->cols,
+ *                   R = d_rows ? clamp(*d_rows, 1, T) : T, read from device memory when the kernels RUN.
+ *   a and x are dsp_rows_operand views (above) with the same cols; x may be NULL.  With x, each product is rounded to fp32 and
+ *   then added (never fused).  READ: rows t < R of a and x, *d_rows.  NEVER READ: any row t >= R.  WRITTEN: every element of
+ *   d_out [cols], and scratch.
+ *   Two launches: workgroups over (column block) x (chunk of whole time steps counted from t = 0, the chunk of dsp_rows_wgrad: a
+ *   function of B alone) write one partial per (chunk, column) to d_scratch -- a chunk that starts at or behind R exits at
+ *   once --, then one thread per column adds the chunks below ceil(R / chunk) in index order.  cols >= 64: lanes along the
+ *   columns, 16 row groups added in index order; cols < 64: lanes along the rows, a fixed xor tree per wave, the 4 waves in
+ *   index order.  The partition is a function of (B, cols) alone, so the bits depend on (cols, B, R) and the data, not on T: a
+ *   call bounded at R in a T-row buffer equals the unbounded call on the first R rows, bit for bit.  tools/rows_sum_emul.py
+ *   restates partition and order in NumPy.
+ *   d_scratch: 16-byte aligned, at least the bytes dsp_rows_colsum_scratch_bytes gives for (T, B, cols).
+ *
+ * 16-byte loads are taken where a pointer and its strides allow them; a 4-byte-aligned view gives the same bits.
+ * LIMITS: T, B >= 1, T B < 2^31, at most 65535 chunks; cols in [1, 2048]; every pointer 4-byte aligned; the output and the
+ * scratch must not overlap anything read nor each other.  Anything else or a NULL mandatory pointer is DSP_EINVAL with a
+ * message before any launch; under dsp_debug_host_dry_run(1) what passed every check is refused instead of launched.
+ */
+int dsp_rows_colsum_scratch_bytes(int32_t T, int32_t B, int32_t cols, int64_t* out_bytes);
+int dsp_rows_colsum(const dsp_rows_operand* a, const dsp_rows_operand* x, int32_t T, int32_t B, const int32_t* d_rows, float* d_out,
+                    void* d_scratch, int64_t scratch_bytes, void* stream);
+
+/* ---- a census of a recorded graph (csrc/dsp_reduce.hip) -------------------------------------------------------------------
+ *
+ * Host only: walks a hipGraph_t (hipGraphGetNodes, hipGraphNodeGetType, hipGraphMemsetNodeGetParams, hipGraphGetRootNodes,
+ * hipGraphNodeGetDependentNodes) and launches nothing.  What a recorded step is made of can then be looked at, not assumed:
+ * n_roots = 1 and max_fanout = 1 is a chain; a memset node of more than 4 bytes (n_wide_memset) is what has been seen to replay
+ * wrong on this stack.  `names` (may be NULL with names_bytes 0) receives the kernel nodes' names as the runtime gives them
+ * (hipKernelNameRefByPtr on the node's function; "?" where it gives none), each followed by a newline, NUL-terminated; names
+ * that do not fit are left out whole, and names_bytes in the result is what all of them need.
+ * A NULL graph or result, or NULL names with a size, is DSP_EINVAL with a message.
+ */
+typedef struct dsp_graph_census_t {
+    int32_t n_nodes, n_kernel, n_memset, n_memcpy, n_other; /* n_other: every other node type */
+    int32_t n_wide_memset;                                  /* memset nodes of more than 4 bytes */
+    int32_t n_roots, max_fanout;                            /* nodes without a predecessor; the most successors of one node */
+    int64_t widest_memset_bytes;                            /* 0 without a memset node */
+    int64_t names_bytes;                                    /* bytes every kernel name needs, terminator included */
+} dsp_graph_census_t;
+int dsp_graph_census(void* hip_graph, dsp_graph_census_t* out, char* names, size_t names_bytes);
+
 #ifdef __cplusplus
 }
 #endif

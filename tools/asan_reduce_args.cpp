@@ -1,0 +1,138 @@
+// Stand-alone host check of the row-bounded column sums and the graph census (include/dsp_frontend.h:
+// dsp_rows_colsum_scratch_bytes, dsp_rows_colsum, dsp_graph_census; csrc/dsp_reduce.hip).  Every NULL, range, stride, overlap,
+// alignment and scratch-size error is DSP_EINVAL with a message before any launch, and under dsp_debug_host_dry_run(1) what passed
+// every check is refused instead of launched: the program needs no GPU.  dsp_graph_census is called with NULL arguments only.
+// `make -C dsp-speech-recognition_amd/csrc asan-reduce` builds it with AddressSanitizer + UBSan against the sanitized build of
+// the library and runs it; it needs no preloaded runtime.
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "dsp_frontend.h"
+
+static int g_bad = 0;
+
+static void expect(int rc, const char* what, int line) {
+    const char* e = dsp_last_error();
+    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
+        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
+        ++g_bad;
+    }
+}
+#define EXPECT(call, what) expect((call), (what), __LINE__)
+
+static dsp_rows_operand op(const float* p, int64_t st, int64_t sb, int32_t cols, int32_t reserved = 0) {
+    dsp_rows_operand o;
+    o.d_ptr = p;
+    o.stride_t = st;
+    o.stride_b = sb;
+    o.cols = cols;
+    o.reserved = reserved;
+    return o;
+}
+
+static void expect_bytes(int32_t T, int32_t B, int32_t cols, int64_t want, int line) {
+    int64_t n = -1;
+    if (dsp_rows_colsum_scratch_bytes(T, B, cols, &n) != DSP_OK || n != want) {
+        std::printf("line %d: scratch bytes %lld, expected %lld\n", line, (long long)n, (long long)want);
+        ++g_bad;
+    }
+}
+
+int main() {
+    dsp_debug_host_dry_run(1);
+    const char* refused = "dry_run: launches are refused";
+    // never reached by a kernel: every call below returns before a launch.  T = 2, B = 2 throughout: an operand with strides
+    // (8, 4) and 4 columns spans 16 floats; one chunk, so the scratch is 4 floats.
+    alignas(16) static float abuf[64], xbuf[64], out[8], scratch[16];
+    static int32_t rows[1] = {1};
+    const int64_t sb = 16;
+    const dsp_rows_operand a = op(abuf, 8, 4, 4), x = op(xbuf, 8, 4, 4);
+    int64_t n = 0;
+
+    expect_bytes(2, 2, 4, 16, __LINE__);
+    expect_bytes(2, 2, 1, 16, __LINE__);                               // rounded up to 16 bytes
+    expect_bytes(200, 512, 200, (int64_t)25 * 200 * 4, __LINE__);      // 8 time steps per chunk
+    expect_bytes(200, 32, 600, (int64_t)25 * 600 * 4, __LINE__);
+    expect_bytes(200, 8192, 1, (int64_t)200 * 4, __LINE__);            // one time step per chunk
+    expect_bytes(1, 17, 2048, (int64_t)2048 * 4, __LINE__);
+    EXPECT(dsp_rows_colsum_scratch_bytes(2, 2, 4, nullptr), "NULL argument");
+    EXPECT(dsp_rows_colsum_scratch_bytes(0, 2, 4, &n), "T 0 must be >= 1");
+    EXPECT(dsp_rows_colsum_scratch_bytes(2, 0, 4, &n), "B 0 must be >= 1");
+    EXPECT(dsp_rows_colsum_scratch_bytes(2, 2, 0, &n), "cols 0 must be in [1, 2048]");
+    EXPECT(dsp_rows_colsum_scratch_bytes(2, 2, 2049, &n), "cols 2049 must be in [1, 2048]");
+    EXPECT(dsp_rows_colsum_scratch_bytes(1 << 20, 1 << 12, 4, &n), "must be below 2^31");
+    EXPECT(dsp_rows_colsum_scratch_bytes(70000, 8192, 4, &n), "more than 65535 chunks");
+
+    dsp_rows_operand bad;
+    EXPECT(dsp_rows_colsum(&a, &x, 0, 2, nullptr, out, scratch, sb, nullptr), "T 0 must be >= 1");
+    EXPECT(dsp_rows_colsum(&a, &x, 2, -1, nullptr, out, scratch, sb, nullptr), "B -1 must be >= 1");
+    EXPECT(dsp_rows_colsum(&a, nullptr, 1 << 20, 1 << 12, nullptr, out, scratch, sb, nullptr), "must be below 2^31");
+    EXPECT(dsp_rows_colsum(nullptr, &x, 2, 2, nullptr, out, scratch, sb, nullptr), "NULL operand a");
+    bad = op(nullptr, 8, 4, 4);
+    EXPECT(dsp_rows_colsum(&bad, &x, 2, 2, nullptr, out, scratch, sb, nullptr), "NULL pointer in operand a");
+    EXPECT(dsp_rows_colsum(&a, &bad, 2, 2, nullptr, out, scratch, sb, nullptr), "NULL pointer in operand x");
+    bad = op(reinterpret_cast<const float*>(reinterpret_cast<const char*>(xbuf) + 2), 8, 4, 4);
+    EXPECT(dsp_rows_colsum(&a, &bad, 2, 2, nullptr, out, scratch, sb, nullptr), "operand x must be 4-byte aligned");
+    bad = op(abuf, 8, 4, 0);
+    EXPECT(dsp_rows_colsum(&bad, nullptr, 2, 2, nullptr, out, scratch, sb, nullptr), "operand a: cols 0 must be in [1, 2048]");
+    bad = op(abuf, 8, 4, 2049);
+    EXPECT(dsp_rows_colsum(&bad, nullptr, 2, 2, nullptr, out, scratch, sb, nullptr), "operand a: cols 2049 must be in [1, 2048]");
+    bad = op(xbuf, 8, 4, 3);
+    EXPECT(dsp_rows_colsum(&a, &bad, 2, 2, nullptr, out, scratch, sb, nullptr), "operand x has 3 columns, operand a 4");
+    bad = op(abuf, -8, 4, 4);
+    EXPECT(dsp_rows_colsum(&bad, &x, 2, 2, nullptr, out, scratch, sb, nullptr), "must not be negative");
+    bad = op(xbuf, 8, -4, 4);
+    EXPECT(dsp_rows_colsum(&a, &bad, 2, 2, nullptr, out, scratch, sb, nullptr), "must not be negative");
+    bad = op(abuf, (int64_t)1 << 40, 4, 4);
+    EXPECT(dsp_rows_colsum(&bad, &x, 2, 2, nullptr, out, scratch, sb, nullptr), "too large");
+    bad = op(abuf, 8, INT64_MAX, 4);
+    EXPECT(dsp_rows_colsum(&bad, &x, 2, 2, nullptr, out, scratch, sb, nullptr), "too large");
+    bad = op(abuf, 8, 4, 4, 7);
+    EXPECT(dsp_rows_colsum(&bad, &x, 2, 2, nullptr, out, scratch, sb, nullptr), "reserved must be 0");
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, nullptr, nullptr, scratch, sb, nullptr), "NULL output d_out");
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, nullptr, out, nullptr, sb, nullptr), "NULL scratch");
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, nullptr, reinterpret_cast<float*>(reinterpret_cast<char*>(out) + 2), scratch, sb, nullptr),
+           "every pointer must be 4-byte aligned");
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(rows) + 1), out, scratch, sb, nullptr),
+           "every pointer must be 4-byte aligned");
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, nullptr, out, scratch + 1, sb, nullptr), "scratch must be 16-byte aligned");
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, nullptr, out, scratch, sb - 4, nullptr), "is short of");
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, nullptr, out, scratch, 0, nullptr), "is short of");
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, nullptr, out, scratch, -16, nullptr), "is short of");
+    // overlaps: the output or the scratch against anything read, and against each other
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, nullptr, abuf + 8, scratch, sb, nullptr), "d_out overlaps operand a");
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, nullptr, xbuf + 15, scratch, sb, nullptr), "d_out overlaps operand x");
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, rows, reinterpret_cast<float*>(rows), scratch, sb, nullptr), "d_out overlaps d_rows");
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, nullptr, scratch + 3, scratch, sb, nullptr), "d_out overlaps scratch");
+    bad = op(scratch, 0, 0, 4);
+    EXPECT(dsp_rows_colsum(&bad, &x, 2, 2, nullptr, out, scratch, sb, nullptr), "scratch overlaps operand a");
+    bad = op(scratch, 0, 0, 4);
+    EXPECT(dsp_rows_colsum(&a, &bad, 2, 2, nullptr, out, scratch, sb, nullptr), "scratch overlaps operand x");
+    // what passes: with and without x and d_rows, a larger scratch, a 4-byte-aligned view, the view at the end of its buffer,
+    // zero strides, the output right behind the operand
+    EXPECT(dsp_rows_colsum(&a, nullptr, 2, 2, nullptr, out, scratch, sb, nullptr), refused);
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, rows, out, scratch, sb, nullptr), refused);
+    EXPECT(dsp_rows_colsum(&a, &x, 2, 2, rows, out + 1, scratch, sb + 64, nullptr), refused);
+    bad = op(abuf + 1, 9, 5, 3);
+    EXPECT(dsp_rows_colsum(&bad, nullptr, 2, 2, rows, out + 1, scratch, sb, nullptr), refused);
+    bad = op(abuf + 48, 8, 4, 4);                                   // the last element read is abuf[63]
+    EXPECT(dsp_rows_colsum(&bad, &x, 2, 2, nullptr, out, scratch, sb, nullptr), refused);
+    bad = op(abuf, 0, 0, 4);                                        // zero strides: every row the same four floats
+    EXPECT(dsp_rows_colsum(&bad, nullptr, 2, 2, nullptr, abuf + 4, scratch, sb, nullptr), refused);
+    bad = op(abuf, 2, 1, 1);                                        // a [T, B] view of scalars
+    EXPECT(dsp_rows_colsum(&bad, nullptr, 2, 2, nullptr, out, scratch, sb, nullptr), refused);
+
+    dsp_graph_census_t census;
+    char names[8];
+    EXPECT(dsp_graph_census(nullptr, &census, names, sizeof(names)), "NULL graph");
+    EXPECT(dsp_graph_census(nullptr, &census, nullptr, 0), "NULL graph");
+    EXPECT(dsp_graph_census(nullptr, nullptr, nullptr, 0), "NULL output");
+    EXPECT(dsp_graph_census(nullptr, nullptr, names, sizeof(names)), "NULL output");
+    EXPECT(dsp_graph_census(nullptr, &census, nullptr, 8), "NULL names with names_bytes 8");
+
+    dsp_debug_host_dry_run(0);
+    if (g_bad) { std::printf("asan_reduce_args: %d FAILED\n", g_bad); return 1; }
+    std::printf("asan_reduce_args: ok\n");
+    return 0;
+}

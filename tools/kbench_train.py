@@ -16,6 +16,8 @@ step -- of ``HMRNNHead`` and ``TransformerHead`` (seeded weights, training mode,
                recurrences as native launches bounded by the row count on the device (csrc/kernels_wgrad.h) instead of torch's
                GEMMs, sums and ``cat`` copies over all 200 rows; timed in the same rounds as their plain twins
 
+  (7) native_sums  (``--routes native_sums`` alone; not among the defaults) the whole recorded step with ``native_sums=True`` against
+      the default device route, both with their graph census (``native_sums_section``).
   (6) capacity  (``--routes capacity`` alone; not among the defaults) the recorded step with ``capacity=`` against the exact-shape
                graph, and an epoch of 8 length vectors through ONE capacity graph against the eager route: tools/kbench_capacity.py,
                merged into profiles/capacity_layout_kbench.json
@@ -116,6 +118,95 @@ def adam_alone(torch, dev, head, iters, warmup, rounds):
     return row
 
 
+def native_sums_section(torch, dev, stored, rate, args):
+    """``--routes native_sums`` (alone; not among the defaults): the whole recorded step -- ``DeviceAdam`` inside, ``loss='native'``,
+    dropout off -- on the device route as it is by default against the same step with ``native_sums=True``, at the sizes of
+    ``CAPTURE_VERIFIED`` so that both record; device events, the median of --rounds rounds with the spread.  Both graphs are recorded
+    with ``census=True``: the default route's census shows how many memset nodes and reductions of torch's the verified graphs
+    carry.  -> the section, also written to ``--out``."""
+    from features.classifier import HMRNNHead, TransformerHead, fill_parameters
+    from features.optim import DeviceAdam
+    from features.train import TrainBatch
+    kinds = {'hmrnn': HMRNNHead, 'transformer': TransformerHead}
+    res = {'iters': args.iters, 'warmup': args.warmup, 'rounds': args.rounds, 'clock': 'device events around iters replays', 'steps': {}}
+    brief = lambda c: {'kernels': c.kernels, 'memsets': c.memsets, 'wide_memsets': c.wide_memsets, 'widest_memset_bytes': c.widest_memset_bytes,
+                       'memcpys': c.memcpys, 'torch_reductions': len(c.torch_reductions()), 'roots': c.roots, 'max_fanout': c.max_fanout}
+    for kind in args.heads.split(','):
+        for B in (int(v) for v in args.batches.split(',')):
+            clips = [stored[i % len(stored)] for i in range(B)]
+            so = np.concatenate(([0], np.cumsum([len(c) for c in clips]))).astype(np.int64)
+            buf = torch.from_numpy(np.concatenate(clips)).to(dev)
+            labels = torch.from_numpy(np.random.default_rng(B).integers(0, 20, B).astype(np.int64)).to(dev)
+            graphs, row = {}, {}
+            for name, kw in (('default', {}), ('native_sums', {'native_sums': True})):
+                torch.manual_seed(0)
+                head = kinds[kind]().train()
+                fill_parameters(head, 3)
+                head = head.to(dev)
+                tb = TrainBatch(rate, head)
+                d_jit = torch.from_numpy(tb.draw_jitter(B, random.Random(B))).to(dev)
+                graphs[name] = tb.capture(buf, so, labels, d_jit, optimizer=DeviceAdam(list(head.parameters()), lr=1e-4), loss='native',
+                                          census=True, dropout=False, **kw)
+                row[f'{name}_census'] = brief(graphs[name].census)
+            rounds = {}
+            for _ in range(args.rounds):
+                for name, g in graphs.items():
+                    rounds.setdefault(name, []).append(per_step_event_us(torch, dev, g.replay, args.iters, args.warmup))
+            for name, v in rounds.items():
+                row[f'{name}_event_us'], row[f'{name}_spread_us'] = float(np.median(v)), float(max(v) - min(v))
+            gap = row['default_event_us'] - row['native_sums_event_us']
+            row['verdict'] = 'ahead' if gap > max(row['default_spread_us'], row['native_sums_spread_us']) else 'NOT ahead'
+            res['steps'][f'{kind}_B{B}'] = row
+            print(f'{kind} B={B}: default {row["default_event_us"]:.0f} us, native_sums {row["native_sums_event_us"]:.0f} us: {row["verdict"]}', flush=True)
+            del graphs
+    res['epoch_B48'] = epoch_section(torch, dev, stored, rate, args)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+    return res
+
+
+def epoch_section(torch, dev, stored, rate, args):
+    """An epoch of 8 batches at batch size 48 -- a size outside ``CAPTURE_VERIFIED`` -- through ``Trainer.fit``: with
+    ``native_sums=True`` (one recorded capacity graph) against the eager ``run(capacity=)`` fallback that size gets without it.  Host
+    clock around ``fit`` of one epoch, a first (recording) epoch left out; the median of --rounds epochs and the spread, in ms."""
+    from features.classifier import TransformerHead, fill_parameters
+    from features.ensemble import EnsembleBatch
+    from features.fit import Trainer
+    from features.optim import DeviceAdam
+    from features.train import TrainBatch
+    B, N = 48, 8 * 48
+    clips = [stored[i % len(stored)] for i in range(N)]
+    labels = np.random.default_rng(48).integers(0, 20, N).astype(np.int64)
+    feat = [(c, rate) for c in clips]
+    val = ([(c, rate) for c in clips[:B]], labels[:B])
+    out = {}
+    for name, sums in (('eager_fallback', False), ('native_sums_graph', True)):
+        torch.manual_seed(0)
+        head = TransformerHead().train()
+        fill_parameters(head, 3)
+        head = head.to(dev)
+        trainer = Trainer(TrainBatch(rate, head), EnsembleBatch(rate, head, []), DeviceAdam(list(head.parameters()), lr=1e-4), 20,
+                          head_kwargs={'dropout': False}, jitter_rng=random.Random(7))
+        times = []
+
+        def on_epoch(entry):
+            torch.cuda.synchronize(dev)
+            times.append(time.perf_counter())
+        torch.cuda.synchronize(dev)
+        times.append(time.perf_counter())
+        trainer.fit((feat, labels), val, 1e-4, epochs=args.rounds + 1, early_stop=args.rounds + 2, batch_size=B, on_epoch=on_epoch, native_sums=sums)
+        ms = [1e3 * (b - a) for a, b in zip(times[1:-1], times[2:])]        # (the first epoch records / warms up)
+        out[f'{name}_ms'], out[f'{name}_spread_ms'] = float(np.median(ms)), float(max(ms) - min(ms))
+        out[f'{name}_train_graphs'] = trainer.train_graphs
+    gap = out['eager_fallback_ms'] - out['native_sums_graph_ms']
+    out['verdict'] = 'ahead' if gap > max(out['eager_fallback_spread_ms'], out['native_sums_graph_spread_ms']) else 'NOT ahead'
+    out['note'] = 'TransformerHead, 8 batches of 48 stored clips and one validation batch per epoch'
+    print(f"epoch at B=48: eager fallback {out['eager_fallback_ms']:.1f} ms, native_sums graph {out['native_sums_graph_ms']:.1f} ms: {out['verdict']}", flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
@@ -145,6 +236,9 @@ def main():
         rows = kbench_capacity.train_section(tuple(int(v) for v in args.batches.split(',')), tuple(args.heads.split(',')), args.iters,
                                              args.warmup, args.rounds)
         print(json.dumps({'train': kbench_capacity.merge('train', rows)['train']}))
+        return
+    if 'native_sums' in routes:
+        print(json.dumps(native_sums_section(torch, dev, stored, rate, args), indent=1))
         return
     kinds = {'hmrnn': (HMRNNHead, dict(native=True, native_enc=True)), 'transformer': (TransformerHead, dict(native_enc=True, native_attn=True))}
     res = {'iters': args.iters, 'warmup': args.warmup, 'rounds': args.rounds, 'optimizer': 'torch.optim.Adam(lr=1e-4), eager',
