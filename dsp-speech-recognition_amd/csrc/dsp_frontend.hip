@@ -1780,6 +1780,41 @@ int dsp_scatter_segments_batch(const int64_t* const* d_group_segments, const int
     return DSP_OK;
 }
 
+// Do the byte ranges [a, a + na) and [b, b + nb) share a byte?
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return pa < pb + nb && pb < pa + na;
+}
+
+int dsp_scatter_group_rows_batch(const void* const* d_group_rows, const int32_t* const* d_dst_col, int32_t n_utt, int32_t n_groups,
+                                 int32_t row_bytes, void* d_out, void* stream) {
+    if (!d_group_rows || !d_dst_col || !d_out) return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: NULL argument");
+    if (n_utt < 1 || n_utt > 65535) return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: n_utt %d must be in [1, 65535]", n_utt);
+    if (n_groups < 1 || n_groups > DSP_MAX_RATE_GROUPS)
+        return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: n_groups %d must be in [1, %d]", n_groups, DSP_MAX_RATE_GROUPS);
+    if (row_bytes < 4 || row_bytes > 256 || (row_bytes & 3) != 0)
+        return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: row_bytes %d must be a multiple of 4 in [4, 256]", row_bytes);
+    if ((reinterpret_cast<uintptr_t>(d_out) & 3) != 0)
+        return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: the output does not start on a 4-byte word (alignment)");
+    const size_t table_bytes = (size_t)n_utt * (size_t)row_bytes, col_bytes = (size_t)n_utt * sizeof(int32_t);
+    ScatterRowsArgs A;
+    memset(&A, 0, sizeof(A));
+    for (int g = 0; g < n_groups; ++g) {
+        if (!d_group_rows[g] || !d_dst_col[g]) return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: group %d: NULL table", g);
+        if (((reinterpret_cast<uintptr_t>(d_group_rows[g]) | reinterpret_cast<uintptr_t>(d_dst_col[g])) & 3) != 0)
+            return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: group %d: a table does not start on a 4-byte word (alignment)", g);
+        if (ranges_overlap(d_out, table_bytes, d_group_rows[g], table_bytes) || ranges_overlap(d_out, table_bytes, d_dst_col[g], col_bytes))
+            return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: group %d: the output must not share memory with a group's table (overlap)", g);
+        A.rows[g] = static_cast<const uint32_t*>(d_group_rows[g]); A.dst_col[g] = d_dst_col[g];
+    }
+    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: dry_run: launches are refused under dsp_debug_host_dry_run");
+    const int32_t row_words = row_bytes / 4;                 // n_utt * row_words <= 65535 * 64: at most 16384 workgroups a group
+    const dim3 grid((unsigned)(((int64_t)n_utt * row_words + 255) / 256), (unsigned)n_groups);
+    scatter_group_rows_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(A, n_utt, row_words, static_cast<uint32_t*>(d_out));
+    HIP_TRY(hipGetLastError());
+    return DSP_OK;
+}
+
 int dsp_pitch_rows_batch(double* d_rows, const int64_t* d_frame_offsets, int32_t n_utt, int32_t n_lags, int32_t bias,
                          int32_t degree, int32_t flags, double* d_pitch, void* stream) {
     if (!d_rows || !d_frame_offsets || n_utt <= 0 || n_lags <= 0 || degree < 0)

@@ -1428,3 +1428,28 @@ __global__ __launch_bounds__(256) void scatter_segments_kernel(ScatterSegmentsAr
     endpoints[2 * (int64_t)col] = seg[2 * (int64_t)k];
     endpoints[2 * (int64_t)col + 1] = seg[2 * (int64_t)k + 1];
 }
+
+// dsp_scatter_group_rows_batch: the same way back for rows of row_words 4-byte words (the pitch tail's [n_utt, 5] fp64 features
+// and [n_utt, 9] int32 details, which each group computes over all its slots): out[dst_col_g[k]] = rows_g[k], a pad slot
+// (dst_col_g[k] < 0) or a column that is no row of the batch skipped WITHOUT reading its row -- a pad slot's row may be NaN.
+// One thread per word, so neighbouring lanes move neighbouring words; grid (ceil(n_utt * row_words / 256), n_groups).
+struct ScatterRowsArgs {
+    const uint32_t* rows[DSP_MAX_RATE_GROUPS];
+    const int32_t* dst_col[DSP_MAX_RATE_GROUPS];
+};
+
+__global__ __launch_bounds__(256) void scatter_group_rows_kernel(ScatterRowsArgs A, int32_t n_utt, int32_t row_words,
+                                                                 uint32_t* __restrict__ out) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t k = idx / row_words;
+    if (k >= n_utt) return;
+    const int64_t w = idx - k * row_words;
+    const uint32_t* rows = A.rows[0];
+    const int32_t* dst_col = A.dst_col[0];
+#pragma unroll
+    for (int g = 1; g < DSP_MAX_RATE_GROUPS; ++g)
+        if ((int)blockIdx.y == g) { rows = A.rows[g]; dst_col = A.dst_col[g]; }
+    const int32_t col = dst_col[k];
+    if (col < 0 || col >= n_utt) return;
+    out[(int64_t)col * row_words + w] = rows[k * row_words + w];
+}

@@ -180,6 +180,7 @@ SIGNATURES = {
     'dsp_rate_groups_batch': (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'dsp_gather_groups_batch': (C.c_int, [c_vp, C.c_int, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp]),
     'dsp_scatter_segments_batch': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    'dsp_scatter_group_rows_batch': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'dsp_attn_create': (C.c_int, [C.POINTER(AttnDesc), C.POINTER(c_vp)]),
     'dsp_attn_destroy': (C.c_int, [c_vp]),
     'dsp_attn_workspace_bytes': (C.c_int, [c_vp, c_i32, c_i32, C.POINTER(c_i64)]),

@@ -12,6 +12,9 @@ decides instead (pitch_model.py:54-61).
   ``run()`` downloads the lengths and the endpoints between the front end and the head (one synchronisation);
   ``run(sync_free=True)`` leaves them on the device (``device_len=True`` on the head), and ``capture()`` records that whole
   chain into ONE HIP graph whose ``replay()`` serves new clips written into the captured buffer.
+* ``MixedRateEnsembleBatch`` is the same for a batch that mixes sample rates, bound to the batch's lengths and rates;
+  ``MixedRateCapacityEnsembleBatch`` groups by rate on the device, so ONE recorded graph serves any lengths and any assignment
+  of a fixed table's rates (``dsp_scatter_group_rows_batch`` brings the groups' pitch rows back to batch order).
 
 Training (pitch_model.py:26-50) runs on the device too: ``PitchSVM.fit(X, y)`` fits the scaler and the SVM with the kernels
 of csrc/kernels_svmfit.h (features/svmfit.py: ``fit_pitch_svm``, ``grid_search``, ``PitchModelTrainer``).  A pair fitted with
@@ -580,3 +583,142 @@ class MixedRateEnsembleBatch(_EnsembleTail):
             return (lambda: self._chain(waves, so, r, plan, waves.device, arenas, head_kwargs, score)), [plan, arenas, list(self.rules),
                                                                                                         score]
         return _capture_scored(waves, prepare, score)
+
+
+# ---- the ensemble over mixed-rate capacity batches: one recorded chain for any lengths and any assignment of rates ----------
+# MixedRateEnsembleBatch above is bound to a batch's lengths AND rates (its plan is host logic).  Here the front end is
+# MixedRateCapacityBatch -- every table rate owns a group of exactly B slots, its clips first, then pad clips of PAD_SAMPLES
+# samples -- and the pitch tail runs per group over ALL B slots, pads included (DESIGN 7.22 reads every kernel of it at n = 1);
+# dsp_scatter_group_rows_batch then brings the rows of the real slots back to batch order, one launch for ``feat`` and one
+# for ``aux``, where the exact-shape route uses index_copy_.
+
+class _MixedEnsembleArena:
+    """What one (B, N, sample type) of a MixedRateCapacityEnsembleBatch launches on beside the front end's arena (``mixed``):
+    per table rate a pre-emphasised trim buffer of N + B * PAD_SAMPLES fp32, the group's ``feat_g`` [B, 5] fp64 and ``aux_g``
+    [B, 9] int32 and a dict for the pitch chain's buffers (features/pitch.py: ``_slot``), and the host arrays of table pointers
+    the two scatter launches take."""
+
+    def __init__(self, mixed):
+        import ctypes as C
+        import torch
+        from .model_glue import PAD_SAMPLES
+        from .pitch import N_AUX
+        self.mixed, dev, B, G = mixed, mixed.dev, mixed.B, mixed.G
+        cap = mixed.N + B * PAD_SAMPLES
+        self.trim = [torch.zeros(cap, dtype=torch.float32, device=dev) for _ in range(G)]
+        self.feat = [torch.zeros((B, 5), dtype=torch.float64, device=dev) for _ in range(G)]
+        self.aux = [torch.zeros((B, N_AUX), dtype=torch.int32, device=dev) for _ in range(G)]
+        self.pitch = [{} for _ in range(G)]
+        self.p_feat = (C.c_void_p * G)(*[t.data_ptr() for t in self.feat])
+        self.p_aux = (C.c_void_p * G)(*[t.data_ptr() for t in self.aux])
+
+
+class MixedRateCapacityEnsembleBatch:
+    """``EnsembleBatch``'s capacity route over a ``model_glue.MixedRateCapacityBatch``: ensemble.py:48-53 for ANY batch of B clips
+    at the rates of a fixed table whose lengths are >= 1 and sum to at most N, as ONE launch sequence that reads lengths and
+    rates from device memory.  Capacity routes only (``run`` and ``capture`` need ``capacity=N``); no jitter, no optional
+    streams.  The sequence, one chain:
+
+      MixedRateCapacityBatch.enqueue   grouping, gather, the groups' front ends, the endpoints back to batch order
+      head(inp, len0, device_len=True) ONE call on the whole batch
+      per table rate                   dsp_trim_preemph_batch on the group's wave buffer and capacity layout, then
+                                       pitch_features_device over all B slots of the group, pads included
+      dsp_scatter_group_rows_batch     twice: the groups' ``feat`` and ``aux`` rows to batch order, pad slots skipped
+      ensemble_decide                  the gate over the batch;  with ``labels=, metrics=`` the scoring launch behind it
+
+    No index_copy_, no memset, no library scratch slot.  ``status`` is ``MixedRateCapacityBatch``'s (bit 4: a rate outside the
+    table; that clip ran in group 0 and every result stays defined)."""
+
+    def __init__(self, rates=(44100, 48000), head=None, rules=(), frame=0.03, step=0.01, coeff=0.97):
+        from .model_glue import MixedRateCapacityBatch
+        self.features = MixedRateCapacityBatch(rates, frame=frame, step=step)     # ValueError for a bad table, before any device work
+        if head is None:
+            raise TypeError('MixedRateCapacityEnsembleBatch needs a head')
+        self.rates, self.head, self.rules, self.coeff = self.features.rates, head, list(rules), float(coeff)
+        self._arenas = {}
+
+    def _arena(self, n_utt, capacity, waves):
+        """``run``: one arena per (device, B, N, sample type), a few kept, the most recently used last."""
+        key = (waves.device.index, int(n_utt), int(capacity), str(waves.dtype))
+        arena = self._arenas.pop(key, None)
+        if arena is None:
+            arena = _MixedEnsembleArena(self.features.prepare(n_utt, capacity, waves))
+            while len(self._arenas) >= 4:
+                self._arenas.pop(next(iter(self._arenas)))
+        self._arenas[key] = arena
+        return arena
+
+    def _chain(self, waves, arena, head_kwargs, score=None):
+        """The whole path as launches on torch's current stream: nothing synchronised, no device memory read from the host."""
+        import torch
+        from .classifier import head_length_info
+        from .pitch import N_AUX, pitch_features_device
+        lib, mc, mixed = nat.load(), self.features, arena.mixed
+        dev, B, G = waves.device, mixed.B, mixed.G
+        stream = torch.cuda.current_stream(dev)
+        st, dtype = _stream_ptr(stream), _wave_dtype_of(waves)
+        inp, len0, endpoints = mc._outputs(B, dev)
+        mc.enqueue(waves, mixed, inp, len0, endpoints, False, stream)
+        logits = _logits_of(self.head(inp, len0, device_len=True, **head_kwargs))
+        n_clamped = head_length_info(len0, inp.shape[0], 1)[2][2:3]
+        for g, mfb in enumerate(mc.groups):
+            lay = mixed.lays[g]
+            nat.check(lib.dsp_trim_preemph_batch(mixed.waves[g].data_ptr(), dtype, lay.vad.p_sample, lay.d_seg.ptr, lay.d_dst_off.ptr,
+                                                 B, self.coeff, arena.trim[g].data_ptr(), st))
+            pitch_features_device(arena.trim[g].data_ptr(), lay.d_dst_off.ptr, B, lay.total_samples, mfb.rate, stream=st,
+                                  d_feat=arena.feat[g].data_ptr(), d_aux=arena.aux[g].data_ptr(), arena=arena.pitch[g])
+        feat = torch.empty((B, 5), dtype=torch.float64, device=dev)
+        aux = torch.empty((B, N_AUX), dtype=torch.int32, device=dev)
+        nat.check(lib.dsp_scatter_group_rows_batch(arena.p_feat, mixed.p_dst_col, B, G, 5 * 8, feat.data_ptr(), st))
+        nat.check(lib.dsp_scatter_group_rows_batch(arena.p_aux, mixed.p_dst_col, B, G, N_AUX * 4, aux.data_ptr(), st))
+        valid = aux[:, N_AUX - 1]
+        pred, prob, used, dec = ensemble_decide(logits, self.rules, feat, valid, stream=st)
+        if score is not None:
+            score[1].update(logits, score[0], pred)
+        return types.SimpleNamespace(pred=pred, prob=prob, used=used, decision=dec, logits=logits, feat=feat, valid=valid,
+                                     endpoints=endpoints, inp=inp, len0=len0, n_clamped=n_clamped, status=mixed.status)
+
+    def _check(self, waves, sample_offsets, capacity):
+        from .pipeline import check_capacity_wave
+        if capacity is None:
+            raise ValueError('MixedRateCapacityEnsembleBatch serves capacity routes only: pass capacity=N '
+                             '(MixedRateEnsembleBatch.run takes exact shapes)')
+        check_capacity_wave(waves, capacity)
+        _wave_dtype_of(waves)
+        return self.features._n_utt(sample_offsets)
+
+    def run(self, waves, sample_offsets, rates, capacity=None, labels=None, metrics=None, **head_kwargs):
+        """Eager and sync-free: ``waves`` a contiguous device tensor of exactly ``capacity`` = N samples (int16 / float32;
+        ValueError otherwise), ``sample_offsets`` [B + 1] and ``rates`` [B] host arrays or device tensors.  -> the namespace of
+        ``EnsembleBatch.run(sync_free=True)`` plus ``status``, every row in batch order: exactly the launches ``capture`` records,
+        on an arena cached per (device, B, N, sample type).  ``labels=`` / ``metrics=`` as ``EnsembleBatch.run``."""
+        score = _score_spec(labels, metrics, True)
+        B = self._check(waves, sample_offsets, capacity)      # (the refusals need no device)
+        nat.require_device()
+        arena = self._arena(B, capacity, waves)
+        arena.mixed.write(sample_offsets, rates, None)
+        return self._chain(waves, arena, head_kwargs, score)
+
+    def capture(self, waves, sample_offsets, rates, capacity=None, labels=None, metrics=None, census=False, **head_kwargs):
+        """ONE HIP graph of ``run``'s launches over ``waves`` (contiguous [N] device tensor) and the batch it holds now.  Before a
+        ``g.replay()`` write the next batch's clips into ``waves``, its offsets into ``g.sample_offsets`` (int64 [B + 1]) and its
+        rates into ``g.rates`` (int32 [B]): ANY B clips at the table's rates whose lengths are >= 1 and sum to at most N are
+        served, in any order of rates.  ``replay()`` -> the namespace of ``run``; ``g.status`` as there.  The graph owns every
+        buffer its launches touch: the front end's arena, the groups' trim buffers, rows and pitch arenas, and the batch-order
+        outputs.  ``labels=`` / ``metrics=`` / ``census=`` as ``EnsembleBatch.capture``."""
+        score = _score_spec(labels, metrics, True)
+        if capacity is None:
+            self._check(waves, sample_offsets, capacity)
+        box = []
+
+        def prepare():
+            nat.require_device()
+            B = self._check(waves, sample_offsets, capacity)
+            arena = _MixedEnsembleArena(self.features.prepare(B, capacity, waves))      # the graph's own
+            arena.mixed.write(sample_offsets, rates, None)
+            box.append(arena)
+            return (lambda: self._chain(waves, arena, head_kwargs, score)), [arena, list(self.rules), score, self.head]
+        g = _capture_scored(waves, prepare, score, census)
+        mixed = box[0].mixed
+        g.sample_offsets, g.rates, g.status = mixed.sample_offsets, mixed.rates, mixed.status
+        return g

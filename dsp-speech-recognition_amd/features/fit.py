@@ -7,7 +7,8 @@ schedule, saving on improvement, early stopping and ``adjust_param`` -- with ONE
 * ``epoch_order`` is reader.py:90: ``random.Random(0).shuffle`` of the list the iterator holds, in place, so the order is
   cumulative over epochs.
 * ``Trainer`` drives ``TrainBatch`` (``loss='native', metrics=``), ``DeviceAdam`` (``reset`` / ``set_lr``) and ``EnsembleBatch``
-  (``labels=, metrics=``).  Host arrays are uploaded batch by batch; nothing overlaps the upload with the step.
+  (``labels=, metrics=``) -- or, for the shuffled 44.1 / 48 kHz batches of reader.py:80, the mixed-rate pair ``MixedRateTrainBatch``
+  and ``MixedRateCapacityEnsembleBatch``.  Host arrays are uploaded batch by batch; nothing overlaps the upload with the step.
 """
 from __future__ import annotations
 
@@ -40,6 +41,16 @@ def epoch_order(order):
     """reader.py:90 on the list the caller holds: shuffled in place by a new ``random.Random(0)``; returns it."""
     random.Random(0).shuffle(order)
     return order
+
+
+def check_rates(rates, served, what='a clip'):
+    """ValueError for the first of ``rates`` that is not one of ``served`` (the batches' rate or rate table): on the host, before
+    any launch."""
+    served = tuple(int(r) for r in served)
+    for r in rates:
+        if int(r) not in served:
+            only = f'{served[0]} Hz only' if len(served) == 1 else f'the rate table {list(served)} only'
+            raise ValueError(f'{what} at {int(r)} Hz: this Trainer serves {only}')
 
 
 def _offsets(clips):
@@ -76,7 +87,9 @@ class Trainer:
     """``Trainer(train_batch, eval_batch, optimizer, n_classes)``: a ``features.train.TrainBatch`` over the head, a
     ``features.ensemble.EnsembleBatch`` over the SAME head (with its rules, or none) for validation, and a
     ``features.optim.DeviceAdam`` over the head's trainable parameters.  One sample rate: every clip's rate must be the
-    batches' (the mixed-rate classes are not driven here).
+    batches'.  Or the mixed-rate pair: a ``features.train.MixedRateTrainBatch`` with a
+    ``features.ensemble.MixedRateCapacityEnsembleBatch`` over the same head and the same rate table -- ``fit`` then serves clips
+    at any of the table's rates, in any order; any other pairing of a mixed-rate with a single-rate class is a TypeError.
 
     ``head_kwargs``: keywords of the head for both phases (``dropout=False``, ``rng=...``); ``eval_kwargs``: those of validation
     where they differ.  ``jitter_rng``: the ``random.Random`` the endpoint jitter of model.py:54-60 is drawn from
@@ -84,20 +97,30 @@ class Trainer:
 
     def __init__(self, train_batch, eval_batch, optimizer, n_classes, wrong_capacity=4096, head_kwargs=None, eval_kwargs=None,
                  jitter_rng=None):
-        from .ensemble import EnsembleBatch
+        from .ensemble import EnsembleBatch, MixedRateCapacityEnsembleBatch
         from .metrics import Metrics
         from .optim import DeviceAdam
         from .train import MixedRateTrainBatch, TrainBatch
-        if not isinstance(train_batch, TrainBatch) or isinstance(train_batch, MixedRateTrainBatch):
-            raise TypeError('Trainer drives a features.train.TrainBatch (one sample rate)')
-        if not isinstance(eval_batch, EnsembleBatch):
+        self.mixed = isinstance(train_batch, MixedRateTrainBatch) and isinstance(eval_batch, MixedRateCapacityEnsembleBatch)
+        if self.mixed:
+            if eval_batch.head is not train_batch.head:
+                raise ValueError('train_batch and eval_batch must share one head')
+            if tuple(eval_batch.rates) != tuple(train_batch.rates):
+                raise ValueError(f'train_batch is for the rate table {list(train_batch.rates)}, eval_batch for {list(eval_batch.rates)}')
+        elif isinstance(train_batch, MixedRateTrainBatch) or isinstance(eval_batch, MixedRateCapacityEnsembleBatch):
+            raise TypeError('a features.train.MixedRateTrainBatch goes with a features.ensemble.MixedRateCapacityEnsembleBatch, and '
+                            'only with it: a mixed-rate class is not paired with a single-rate one')
+        elif not isinstance(train_batch, TrainBatch):
+            raise TypeError('Trainer drives a features.train.TrainBatch (one sample rate) or a features.train.MixedRateTrainBatch')
+        elif not isinstance(eval_batch, EnsembleBatch):
             raise TypeError('Trainer validates through a features.ensemble.EnsembleBatch')
         if not isinstance(optimizer, DeviceAdam):
             raise TypeError('Trainer needs a features.optim.DeviceAdam: only its step can be recorded and reset in place')
-        if eval_batch.head is not train_batch.head:
-            raise ValueError('train_batch and eval_batch must share one head')
-        if eval_batch.rate != train_batch.rate:
-            raise ValueError(f'train_batch is for {train_batch.rate} Hz, eval_batch for {eval_batch.rate} Hz')
+        if not self.mixed:
+            if eval_batch.head is not train_batch.head:
+                raise ValueError('train_batch and eval_batch must share one head')
+            if eval_batch.rate != train_batch.rate:
+                raise ValueError(f'train_batch is for {train_batch.rate} Hz, eval_batch for {eval_batch.rate} Hz')
         self.tb, self.eb, self.opt, self.head = train_batch, eval_batch, optimizer, train_batch.head
         self.n_classes = int(n_classes)
         self.head_kwargs = dict(head_kwargs or {})
@@ -126,9 +149,69 @@ class Trainer:
         clips = [ph.clips[i] for i in idx]
         return np.concatenate(clips).astype(dtype, copy=False), _offsets(clips), ph.labels[idx]
 
+    # ---- one batch of the mixed-rate pair ----------------------------------------------------------------------------
+    @staticmethod
+    def _part(ph):
+        if ph.part is None:
+            ph.part = _Slot()
+        return ph.part
+
+    @staticmethod
+    def _replay_mixed(g, so, rates, jit=None):
+        """The next batch's tables into the graph's own tensors, then the replay."""
+        import torch
+        g.sample_offsets.copy_(torch.from_numpy(so))
+        g.rates.copy_(torch.from_numpy(rates))
+        if jit is not None:
+            g.jitter.copy_(jit)
+        g.replay()
+
+    def _train_step_mixed(self, ph, idx, B, capacity, np_dtype, torch_dtype, recordable, native_sums):
+        from . import metrics as M
+        flat, so, labels = self._flat(ph, idx, np_dtype)
+        rates = np.array([ph.rates[i] for i in idx], dtype=np.int32)
+        jitter = self.tb.draw_jitter(rates, self.jitter_rng)
+        m, kw = self.train_metrics, self.head_kwargs
+        full = len(idx) == B
+        slot = ph if full else self._part(ph)              # every size on capacity buffers of its own: an arena per (B, N)
+        self._buffers(slot, len(idx), capacity, torch_dtype, True)
+        self._upload(slot, flat, labels, jitter)
+        if native_sums:
+            kw = dict(kw, native_sums=True)
+        if native_sums or (full and recordable):
+            if slot.graph is None:
+                slot.graph = self.tb.capture(slot.buf, so, rates, slot.lab, slot.jit, optimizer=self.opt, capacity=capacity,
+                                             loss='native', metrics=m, **kw)
+                self.train_graphs += 1 if native_sums else 0
+            self._replay_mixed(slot.graph, so, rates, slot.jit)
+            return
+        out = self.tb.run(slot.buf, so, rates, slot.lab, slot.jit, capacity=capacity, loss='native', metrics=m, **kw)
+        for p in self.opt.params:
+            p.grad = None
+        M.backward(out.loss)
+        self.opt.step()
+
+    def _eval_step_mixed(self, ph, idx, B, capacity, np_dtype, torch_dtype):
+        flat, so, labels = self._flat(ph, idx, np_dtype)
+        rates = np.array([ph.rates[i] for i in idx], dtype=np.int32)
+        m, kw = self.val_metrics, self.eval_kwargs
+        full = len(idx) == B
+        slot = ph if full else self._part(ph)
+        self._buffers(slot, len(idx), capacity, torch_dtype, False)
+        self._upload(slot, flat, labels, None)
+        if full:
+            if ph.graph is None:
+                ph.graph = self.eb.capture(ph.buf, so, rates, capacity=capacity, labels=ph.lab, metrics=m, **kw)
+            self._replay_mixed(ph.graph, so, rates)
+        else:
+            self.eb.run(slot.buf, so, rates, capacity=capacity, labels=slot.lab, metrics=m, **kw)
+
+    # ---- one batch at one rate ------------------------------------------------------------------------------------
     def _train_step(self, ph, idx, B, capacity, np_dtype, torch_dtype, recordable, native_sums=False):
         import torch
         from . import metrics as M
+        if self.mixed:
+            return self._train_step_mixed(ph, idx, B, capacity, np_dtype, torch_dtype, recordable, native_sums)
         flat, so, labels = self._flat(ph, idx, np_dtype)
         jitter = self.tb.draw_jitter(len(idx), self.jitter_rng)
         m, kw = self.train_metrics, self.head_kwargs
@@ -166,6 +249,8 @@ class Trainer:
 
     def _eval_step(self, ph, idx, B, capacity, np_dtype, torch_dtype):
         import torch
+        if self.mixed:
+            return self._eval_step_mixed(ph, idx, B, capacity, np_dtype, torch_dtype)
         flat, so, labels = self._flat(ph, idx, np_dtype)
         m, kw = self.val_metrics, self.eval_kwargs
         if len(idx) == B:
@@ -200,6 +285,12 @@ class Trainer:
         after ``adjust_param``.  ``train_graphs`` in each epoch's entry (and on the trainer) counts the training graphs recorded
         so far.
 
+        The mixed-rate pair: the same decisions, every batch on capacity buffers.  Each batch also writes its ``rates`` (and its
+        jitter rows, drawn by ``MixedRateTrainBatch.draw_jitter(rates, rng)``) into the graph's own tensors, so ONE training graph
+        and ONE validation graph serve full batches whatever their lengths and rate assignments are; the trailing partial
+        batches go through ``run(..., capacity=)`` on an arena of their own size (training: with an eager ``optimizer.step()``, or
+        through the second graph with ``native_sums=True``).  A clip whose rate is not in the table is a ValueError before any launch.
+
         ``capacity``: samples of the capacity buffers; default: the sum of the ``batch_size`` longest clips of both sets.
         -> the history: per epoch a namespace (epoch, lr: the epoch's rate, train / val: ``Metrics.result()``, improved, stop,
         train_order / val_order: the epoch's orders, which the ``wrong`` lists index).  ``on_epoch(entry)``: called with each
@@ -211,9 +302,7 @@ class Trainer:
         if B < 1:
             raise ValueError(f'batch_size {batch_size} must be >= 1')
         for ph in (tr, va):
-            bad = [r for r in ph.rates if r != self.tb.rate]
-            if bad:
-                raise ValueError(f'a clip at {bad[0]} Hz: this Trainer serves {self.tb.rate} Hz only')
+            check_rates(ph.rates, self.tb.rates if self.mixed else (self.tb.rate,))
         all_clips = tr.clips + va.clips
         int16 = all(c.dtype == np.int16 for c in all_clips)
         np_dtype, torch_dtype = (np.int16, torch.int16) if int16 else (np.float32, torch.float32)
@@ -255,5 +344,7 @@ class Trainer:
                 tr.graph = va.graph = None                 # the recorded launches hold the old value
                 if tr.part is not None:
                     tr.part.graph = None
+                if va.part is not None:
+                    va.part.graph = None
             self.head.train()
         return history

@@ -399,8 +399,8 @@ def _no_mixed_capacity(capacity):
     if capacity is not None:
         raise NotImplementedError('capacity= is not served for mixed-rate batches by this class: its grouping by rate is host logic over '
                                   'the rates (group_by_rate), so the layout of a mixed batch cannot be rebuilt on the device here; use '
-                                  'MixedRateCapacityBatch (features, default call) or train.MixedRateTrainBatch, which group on the '
-                                  'device, or the single-rate classes')
+                                  'MixedRateCapacityBatch (features, default call), train.MixedRateTrainBatch or '
+                                  'ensemble.MixedRateCapacityEnsembleBatch, which group on the device, or the single-rate classes')
 
 
 class _MixedPlan:

@@ -864,6 +864,18 @@ int dsp_gather_groups_batch(const void* d_wave, int wave_dtype, const int64_t* d
                             void* const* d_out, void* stream);
 int dsp_scatter_segments_batch(const int64_t* const* d_group_segments, const int32_t* const* d_dst_col, int32_t n_utt,
                                int32_t n_groups, int64_t* d_endpoints, void* stream);
+/*
+ * dsp_scatter_group_rows_batch: the same way back for any small per-slot rows -- the pitch tail's [n_utt, 5] fp64 features (40
+ * bytes a row) and [n_utt, 9] int32 details (36 bytes, not 8-byte aligned), which every group computes over all its n_utt
+ * slots, pads included.  d_out[d_dst_col[g][k]] = d_group_rows[g][k] for g < n_groups, k < n_utt; rows are row_bytes bytes (a
+ * multiple of 4 in [4, 256]) and move as 4-byte words.  A slot whose column is negative (a pad slot) or >= n_utt is skipped
+ * WITHOUT reading its row, so the call is memory-safe on tables it did not write and a pad slot's NaN row goes nowhere.
+ * d_group_rows and d_dst_col are HOST arrays of n_groups device pointers, each on a 4-byte word, as d_out is; d_out
+ * [n_utt, row_bytes] shares no byte with a group's table.  n_utt in [1, 65535].  One launch for all groups, plain stores: no
+ * atomics, no memset, the same bits on every run; where the groups partition the batch every row of d_out is written.
+ */
+int dsp_scatter_group_rows_batch(const void* const* d_group_rows, const int32_t* const* d_dst_col, int32_t n_utt, int32_t n_groups,
+                                 int32_t row_bytes, void* d_out, void* stream);
 
 /* ---- the attention blocks: rnn_clf.Transformer's encoder layer and rnn_clf.HRNN_Att's pooling (forward, fp32) ------- */
 /*

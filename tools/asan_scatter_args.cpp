@@ -1,0 +1,81 @@
+// Stand-alone host check of dsp_scatter_group_rows_batch (include/dsp_frontend.h; csrc/dsp_frontend.hip): the launch that
+// brings the rate groups' pitch rows back to batch order.  Every NULL, range, row-size, alignment and overlap error is
+// DSP_EINVAL with a message before any device call, and under dsp_debug_host_dry_run(1) what passed every check is refused
+// instead of launched: the program needs no GPU.
+// `make -C dsp-speech-recognition_amd/csrc asan-scatter` builds it with AddressSanitizer + UBSan against the sanitized build of
+// the library and runs it; it needs no preloaded runtime.
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "dsp_frontend.h"
+
+static int g_bad = 0;
+
+static void expect(int rc, const char* what, int line) {
+    const char* e = dsp_last_error();
+    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
+        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
+        ++g_bad;
+    }
+}
+#define EXPECT(call, what) expect((call), (what), __LINE__)
+
+int main() {
+    dsp_debug_host_dry_run(1);
+    const char* refused = "dry_run: launches are refused";
+    // never reached by a kernel: every call below returns before a launch.  3 slots of at most 256 bytes a group.
+    alignas(8) static unsigned char rows[4][3 * 256], out[3 * 256 + 8];
+    static int32_t col[4][4];
+    const void* const tabs[4] = {rows[0], rows[1], rows[2], rows[3]};
+    const void* const tabs_null[2] = {rows[0], nullptr};
+    const void* const tabs_odd[2] = {rows[0], rows[1] + 2};
+    const void* const tabs_on_out[2] = {rows[0], out};
+    const void* const tabs_into_out[2] = {rows[0], out + 40};          // starts inside the output: a range test, not equal starts
+    const void* const tabs_behind_out[2] = {rows[0], out + 3 * 40};    // the first byte behind a [3, 40] output: no overlap
+    const int32_t* const cols[4] = {col[0], col[1], col[2], col[3]};
+    const int32_t* const cols_null[2] = {nullptr, col[1]};
+    const int32_t* const cols_odd[2] = {col[0], reinterpret_cast<const int32_t*>(reinterpret_cast<const unsigned char*>(col[1]) + 1)};
+    const int32_t* const cols_on_out[2] = {col[0], reinterpret_cast<const int32_t*>(out + 8)};
+
+    EXPECT(dsp_scatter_group_rows_batch(nullptr, cols, 3, 2, 40, out, nullptr), "NULL argument");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, nullptr, 3, 2, 40, out, nullptr), "NULL argument");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 3, 2, 40, nullptr, nullptr), "NULL argument");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 0, 2, 40, out, nullptr), "n_utt 0 must be in [1, 65535]");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, -1, 2, 40, out, nullptr), "n_utt -1 must be in [1, 65535]");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 65536, 2, 40, out, nullptr), "n_utt 65536 must be in [1, 65535]");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 3, 0, 40, out, nullptr), "n_groups 0 must be in [1, 4]");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 3, 5, 40, out, nullptr), "n_groups 5 must be in [1, 4]");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 3, 2, 0, out, nullptr), "row_bytes 0 must be a multiple of 4 in [4, 256]");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 3, 2, 2, out, nullptr), "row_bytes 2 must be a multiple of 4 in [4, 256]");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 3, 2, 38, out, nullptr), "row_bytes 38 must be a multiple of 4 in [4, 256]");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 3, 2, 260, out, nullptr), "row_bytes 260 must be a multiple of 4 in [4, 256]");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 3, 2, -4, out, nullptr), "row_bytes -4 must be a multiple of 4 in [4, 256]");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 3, 2, 40, out + 2, nullptr), "alignment");
+    EXPECT(dsp_scatter_group_rows_batch(tabs_null, cols, 3, 2, 40, out, nullptr), "group 1: NULL table");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols_null, 3, 2, 40, out, nullptr), "group 0: NULL table");
+    EXPECT(dsp_scatter_group_rows_batch(tabs_odd, cols, 3, 2, 40, out, nullptr), "group 1: a table does not start on a 4-byte word (alignment)");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols_odd, 3, 2, 40, out, nullptr), "group 1: a table does not start on a 4-byte word (alignment)");
+    EXPECT(dsp_scatter_group_rows_batch(tabs_on_out, cols, 3, 2, 40, out, nullptr), "overlap");
+    EXPECT(dsp_scatter_group_rows_batch(tabs_into_out, cols, 3, 2, 40, out, nullptr), "overlap");
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols_on_out, 3, 2, 40, out, nullptr), "overlap");
+    EXPECT(dsp_scatter_group_rows_batch(tabs_on_out, cols, 3, 1, 40, out, nullptr), refused);      // group 1 is not looked at
+    EXPECT(dsp_scatter_group_rows_batch(tabs_behind_out, cols, 3, 2, 40, out, nullptr), refused);
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 3, 2, 36, out + 4, nullptr), refused);         // int32 rows: 4-byte aligned is enough
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 3, 4, 256, out, nullptr), refused);
+    EXPECT(dsp_scatter_group_rows_batch(tabs, cols, 1, 1, 4, out, nullptr), refused);
+    // the largest tables: 65535 rows of 256 bytes a group, at addresses far enough apart (the host dereferences none of them)
+    const uintptr_t far = 0x10000000u, apart = 0x02000000u;
+    const void* const tabs_far[4] = {reinterpret_cast<const void*>(far), reinterpret_cast<const void*>(far + apart),
+                                     reinterpret_cast<const void*>(far + 2 * apart), reinterpret_cast<const void*>(far + 3 * apart)};
+    const int32_t* const cols_far[4] = {reinterpret_cast<const int32_t*>(far + 4 * apart), reinterpret_cast<const int32_t*>(far + 5 * apart),
+                                        reinterpret_cast<const int32_t*>(far + 6 * apart), reinterpret_cast<const int32_t*>(far + 7 * apart)};
+    EXPECT(dsp_scatter_group_rows_batch(tabs_far, cols_far, 65535, 4, 256, reinterpret_cast<void*>(far + 8 * apart), nullptr), refused);
+    EXPECT(dsp_scatter_group_rows_batch(tabs_far, cols_far, 65535, 4, 256, reinterpret_cast<void*>(far + 3 * apart + 65534u * 256u), nullptr),
+           "group 3: the output must not share memory");                                              // the last row of group 3
+
+    dsp_debug_host_dry_run(0);
+    if (g_bad) { std::printf("asan_scatter_args: %d FAILED\n", g_bad); return 1; }
+    std::printf("asan_scatter_args: ok\n");
+    return 0;
+}
