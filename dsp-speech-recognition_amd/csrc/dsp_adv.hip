@@ -14,32 +14,6 @@
 
 namespace {
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-struct Range {
-    const char* name;
-    uintptr_t lo, hi;       // [lo, hi)
-    bool output;
-};
-
-struct Ranges {
-    Range r[24];
-    int k = 0;
-    void add(const char* name, const void* p, int64_t bytes, bool output) {
-        if (!p) return;
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-        r[k++] = Range{name, lo, lo + (uintptr_t)bytes, output};
-    }
-    // the outputs must lie apart from each other and from everything that is read (inputs may share memory)
-    int check(const char* who) const {
-        for (int i = 0; i < k; ++i)
-            for (int j = i + 1; j < k; ++j)
-                if ((r[i].output || r[j].output) && r[i].lo < r[j].hi && r[j].lo < r[i].hi)
-                    return dsp_fail(DSP_EINVAL, "%s: %s overlaps %s", who, r[j].name, r[i].name);
-        return DSP_OK;
-    }
-};
-
 int check_sizes(const char* who, int32_t B, int32_t F, int32_t H, int32_t S) {
     if (B < 1 || B > ADV_MAX_B) return dsp_fail(DSP_EINVAL, "%s: B %d must be in [1, %d]", who, B, ADV_MAX_B);
     if (F < 1 || F > ADV_MAX_F) return dsp_fail(DSP_EINVAL, "%s: F %d must be in [1, %d]", who, F, ADV_MAX_F);
@@ -127,7 +101,7 @@ int dsp_adv_disc_forward(const float* d_feat, int64_t ld_feat, int32_t B, int32_
     rg.add("d_a", d_a, (int64_t)B * H * 4, true);
     rg.add("d_logits2", d_logits2, ((int64_t)(B - 1) * ld_logits2 + S) * 4, true);
     if (int rc = rg.check(who)) return rc;
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
 
     const AdvParams P = forward_params(d_feat, ld_feat, B, F, H, S, d_W1, d_b1, d_W2, d_b2, d_a, d_logits2, ld_logits2);
     adv_disc_fwd_kernel<<<(B + ADV_ROWS - 1) / ADV_ROWS, ADV_THREADS, 0, (hipStream_t)stream>>>(P);
@@ -169,18 +143,18 @@ int dsp_adv_disc_train(const float* d_feat, int64_t ld_feat, int32_t B, int32_t 
     rg.add("d_grad_out", d_grad_out, 4, false);
     rg.add("d_gamma", d_gamma, 4, false);
     rg.add("d_a", d_a, (int64_t)B * H * 4, true);
-    if (d_logits2) rg.add("d_logits2", d_logits2, ((int64_t)(B - 1) * ld_logits2 + S) * 4, true);
+    rg.add("d_logits2", d_logits2, ((int64_t)(B - 1) * ld_logits2 + S) * 4, true);
     rg.add("d_loss2", d_loss2, 4, true);
     rg.add("d_dz", d_dz, (int64_t)B * S * 4, true);
-    if (d_dfeat) rg.add("d_dfeat", d_dfeat, ((int64_t)(B - 1) * ld_dfeat + F) * 4, true);
+    rg.add("d_dfeat", d_dfeat, ((int64_t)(B - 1) * ld_dfeat + F) * 4, true);
     rg.add("d_dW1", d_dW1, (int64_t)H * F * 4, true);
     rg.add("d_db1", d_db1, (int64_t)H * 4, true);
     rg.add("d_dW2", d_dW2, (int64_t)S * H * 4, true);
     rg.add("d_db2", d_db2, (int64_t)S * 4, true);
-    if (d_state) rg.add("d_state", d_state, xent_state_bytes(S, cap), true);
+    rg.add("d_state", d_state, xent_state_bytes(S, cap), true);
     rg.add("the workspace", d_work, w.total, true);
     if (int rc = rg.check(who)) return rc;
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
 
     hipStream_t st = (hipStream_t)stream;
     char* base = static_cast<char*>(d_work);

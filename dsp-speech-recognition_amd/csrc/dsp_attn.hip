@@ -66,7 +66,7 @@ bool mult4_in(int32_t v, int32_t hi) { return v >= 4 && v <= hi && (v & 3) == 0;
 
 // A handle or call a launch may go ahead with: not under dry run, and on the handle's device.
 int attn_check_launch(const char* who, const dsp_attn* h) {
-    if (g_host_dry_run || (h && h->dry_run)) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (int rc = dsp_refuse_dry_run(who, h && h->dry_run)) return rc;
     if (!h) return DSP_OK;
     int dev = -1;
     HIP_TRY(hipGetDevice(&dev));

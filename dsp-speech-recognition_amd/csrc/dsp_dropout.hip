@@ -12,19 +12,6 @@ namespace {
 
 const int64_t kMaxElems = (int64_t)1 << 34;                      // element_index / 4 is one 32-bit counter word
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-struct Range {
-    uintptr_t lo, hi;
-};
-
-Range range_of(const void* p, int64_t bytes) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return Range{lo, lo + (uintptr_t)bytes};
-}
-
-bool overlap(Range a, Range b) { return a.lo < b.hi && b.lo < a.hi; }
-
 // p in [0, 1) -> the keep threshold and the scale of a kept element, both formed in double.
 int keep_rule(const char* who, double p, uint32_t* thr, float* scale) {
     if (!(p >= 0.0 && p < 1.0)) return dsp_fail(DSP_EINVAL, "%s: p %g must be in [0, 1)", who, p);
@@ -63,7 +50,7 @@ int apply(const char* who, const char* state_name, const float* d_x, float* d_y,
         const Range rk = range_of(d_key_out, 16);
         if (overlap(rk, rx) || overlap(rk, ry) || overlap(rk, rs)) return dsp_fail(DSP_EINVAL, "%s: d_key_out overlaps another argument", who);
     }
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
 
     const int grid = grid_for((n + 3) / 4, DROPOUT_THREADS);
     const long long* st = reinterpret_cast<const long long*>(d_state);
@@ -83,7 +70,7 @@ extern "C" {
 int dsp_rng_advance(int64_t* d_state, void* stream) {
     const char* who = "dsp_rng_advance";
     if (int rc = check_state(who, "d_state", d_state)) return rc;
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
     rng_advance_kernel<<<1, 1, 0, (hipStream_t)stream>>>(reinterpret_cast<long long*>(d_state));
     HIP_TRY(hipGetLastError());
     return DSP_OK;
@@ -115,8 +102,8 @@ int dsp_dropout_multipliers(float* d_m, int32_t L, int32_t T, int32_t B, int32_t
     if (int rc = check_site(who, site_base, L)) return rc;
     const Range rm = range_of(d_m, per_layer * L * 4);
     if (overlap(rm, range_of(d_state, 16))) return dsp_fail(DSP_EINVAL, "%s: d_m overlaps d_state", who);
-    if (d_rows && overlap(rm, range_of(d_rows, 4))) return dsp_fail(DSP_EINVAL, "%s: d_m overlaps d_rows", who);
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (overlap(rm, range_of(d_rows, 4))) return dsp_fail(DSP_EINVAL, "%s: d_m overlaps d_rows", who);
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
 
     const dim3 grid((unsigned)grid_for((per_layer + 3) / 4, DROPOUT_THREADS), (unsigned)L);
     const long long* st = reinterpret_cast<const long long*>(d_state);

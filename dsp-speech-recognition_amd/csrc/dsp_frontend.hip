@@ -737,8 +737,7 @@ int placement_check(const OutPlacement& pl, int32_t n_utt, int32_t width) {
     if (pl.col_offset < 0) return dsp_fail(DSP_EINVAL, "col_offset %d is negative", pl.col_offset);
     if ((int64_t)pl.col_offset + width > pl.row_width)
         return dsp_fail(DSP_EINVAL, "col_offset %d + %d columns do not fit row_width %d", pl.col_offset, width, pl.row_width);
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dry_run: launches are refused under dsp_debug_host_dry_run");
-    return DSP_OK;
+    return dsp_refuse_dry_run(nullptr);
 }
 
 // The argument checks the model-finalize entry points share (behind their own), and the launch.  pl.row_width == 0: the
@@ -1273,7 +1272,7 @@ int dsp_batch_offsets_batch(const int64_t* d_sample_offsets_in, int32_t n_utt, i
             if (d_frame_offsets[g] == d_frame_offsets[f]) return dsp_fail(DSP_EINVAL, "dsp_batch_offsets_batch: framings %d and %d share a table (overlap)", g, f);
         A.L[f] = frame_len[f]; A.S[f] = frame_step[f]; A.frame_off[f] = d_frame_offsets[f];
     }
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dsp_batch_offsets_batch: dry_run: launches are refused under dsp_debug_host_dry_run");
+    if (int rc = dsp_refuse_dry_run("dsp_batch_offsets_batch")) return rc;
     batch_offsets_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(d_sample_offsets_in, n_utt, sample_capacity, A, d_sample_offsets, d_status);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
@@ -1318,7 +1317,7 @@ int dsp_layout_create_capacity(int32_t n_utt, int64_t n_frames_bound, int32_t fr
 int dsp_layout_refresh(dsp_layout* layout, const int64_t* d_frame_offsets, void* stream) {
     if (!layout || !d_frame_offsets) return dsp_fail(DSP_EINVAL, "dsp_layout_refresh: NULL argument");
     if (!layout->capacity) return dsp_fail(DSP_EINVAL, "dsp_layout_refresh: the handle is not from dsp_layout_create_capacity: its tables fit one batch shape");
-    if (g_host_dry_run || layout->dry_run) return dsp_fail(DSP_EINVAL, "dsp_layout_refresh: dry_run: launches are refused under dsp_debug_host_dry_run");
+    if (int rc = dsp_refuse_dry_run("dsp_layout_refresh", layout->dry_run)) return rc;
     const int rc = check_owner_device(layout->device, false);
     if (rc != DSP_OK) return rc;
     if (layout->group_off != nullptr) {
@@ -1654,7 +1653,7 @@ int dsp_gather_clips_batch(const void* d_wave, int wave_dtype, const int64_t* d_
     if (n_pick < 0) return dsp_fail(DSP_EINVAL, "dsp_gather_clips_batch: n_pick %d is negative", n_pick);
     if (wave_dtype != DSP_WAVE_F32 && wave_dtype != DSP_WAVE_I16)
         return dsp_fail(DSP_EINVAL, "dsp_gather_clips_batch: bad wave_dtype %d", wave_dtype);
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dry_run: launches are refused under dsp_debug_host_dry_run");
+    if (int rc = dsp_refuse_dry_run(nullptr)) return rc;
     if (n_pick == 0) return DSP_OK;
     const dim3 grid(GATHER_CHUNKS, (unsigned)n_pick);
     if (wave_dtype == DSP_WAVE_I16)
@@ -1721,7 +1720,7 @@ int dsp_rate_groups_batch(const int32_t* d_rates, const int64_t* d_sample_offset
     if (tables_collide(i32_tabs, n32, d_rates) || tables_collide(i32_tabs, n32, d_count) || tables_collide(i32_tabs, n32, d_status) ||
         tables_collide(i64_tabs, n64, d_sample_offsets_in) || tables_collide(i64_tabs, n64, d_jitter) || d_count == d_status)
         return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: two tables share their memory (overlap)");
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dsp_rate_groups_batch: dry_run: launches are refused under dsp_debug_host_dry_run");
+    if (int rc = dsp_refuse_dry_run("dsp_rate_groups_batch")) return rc;
     rate_groups_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(d_rates, d_sample_offsets_in, d_jitter, n_utt, sample_capacity, pad_len, A,
                                                            d_sample_offsets, d_count, d_status);
     HIP_TRY(hipGetLastError());
@@ -1743,13 +1742,13 @@ int dsp_gather_groups_batch(const void* d_wave, int wave_dtype, const int64_t* d
     memset(&A, 0, sizeof(A));
     for (int g = 0; g < n_groups; ++g) {
         if (!d_pick[g] || !d_group_offsets[g] || !d_out[g]) return dsp_fail(DSP_EINVAL, "dsp_gather_groups_batch: group %d: NULL table or buffer", g);
-        if ((reinterpret_cast<uintptr_t>(d_out[g]) & 15) != 0)
+        if (!aligned(d_out[g], 16))
             return dsp_fail(DSP_EINVAL, "dsp_gather_groups_batch: group %d: the buffer does not start on a 16-byte vector (alignment)", g);
         A.pick[g] = d_pick[g]; A.offsets[g] = d_group_offsets[g]; A.out[g] = d_out[g];
     }
     if (tables_collide(d_out, n_groups, d_wave))
         return dsp_fail(DSP_EINVAL, "dsp_gather_groups_batch: two wave buffers share their memory (overlap)");
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dsp_gather_groups_batch: dry_run: launches are refused under dsp_debug_host_dry_run");
+    if (int rc = dsp_refuse_dry_run("dsp_gather_groups_batch")) return rc;
     const dim3 grid(GATHER_CHUNKS, (unsigned)n_utt, (unsigned)n_groups);
     if (wave_dtype == DSP_WAVE_I16)
         gather_groups_kernel<int16_t><<<grid, 256, 0, (hipStream_t)stream>>>(static_cast<const int16_t*>(d_wave), d_sample_offsets, pad_len, A);
@@ -1773,17 +1772,11 @@ int dsp_scatter_segments_batch(const int64_t* const* d_group_segments, const int
     }
     if (tables_collide(reinterpret_cast<const void* const*>(d_group_segments), n_groups, d_endpoints))
         return dsp_fail(DSP_EINVAL, "dsp_scatter_segments_batch: the endpoints must not be a group's segment table (overlap)");
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dsp_scatter_segments_batch: dry_run: launches are refused under dsp_debug_host_dry_run");
+    if (int rc = dsp_refuse_dry_run("dsp_scatter_segments_batch")) return rc;
     const dim3 grid((unsigned)((n_utt + 255) / 256), (unsigned)n_groups);
     scatter_segments_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(A, n_utt, d_endpoints);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
-}
-
-// Do the byte ranges [a, a + na) and [b, b + nb) share a byte?
-static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + nb && pb < pa + na;
 }
 
 int dsp_scatter_group_rows_batch(const void* const* d_group_rows, const int32_t* const* d_dst_col, int32_t n_utt, int32_t n_groups,
@@ -1794,20 +1787,21 @@ int dsp_scatter_group_rows_batch(const void* const* d_group_rows, const int32_t*
         return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: n_groups %d must be in [1, %d]", n_groups, DSP_MAX_RATE_GROUPS);
     if (row_bytes < 4 || row_bytes > 256 || (row_bytes & 3) != 0)
         return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: row_bytes %d must be a multiple of 4 in [4, 256]", row_bytes);
-    if ((reinterpret_cast<uintptr_t>(d_out) & 3) != 0)
+    if (!aligned(d_out, 4))
         return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: the output does not start on a 4-byte word (alignment)");
-    const size_t table_bytes = (size_t)n_utt * (size_t)row_bytes, col_bytes = (size_t)n_utt * sizeof(int32_t);
+    const int64_t table_bytes = (int64_t)n_utt * row_bytes, col_bytes = (int64_t)n_utt * 4;
+    const Range out = range_of(d_out, table_bytes);
     ScatterRowsArgs A;
     memset(&A, 0, sizeof(A));
     for (int g = 0; g < n_groups; ++g) {
         if (!d_group_rows[g] || !d_dst_col[g]) return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: group %d: NULL table", g);
-        if (((reinterpret_cast<uintptr_t>(d_group_rows[g]) | reinterpret_cast<uintptr_t>(d_dst_col[g])) & 3) != 0)
+        if (!aligned(d_group_rows[g], 4) || !aligned(d_dst_col[g], 4))
             return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: group %d: a table does not start on a 4-byte word (alignment)", g);
-        if (ranges_overlap(d_out, table_bytes, d_group_rows[g], table_bytes) || ranges_overlap(d_out, table_bytes, d_dst_col[g], col_bytes))
+        if (overlap(out, range_of(d_group_rows[g], table_bytes)) || overlap(out, range_of(d_dst_col[g], col_bytes)))
             return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: group %d: the output must not share memory with a group's table (overlap)", g);
         A.rows[g] = static_cast<const uint32_t*>(d_group_rows[g]); A.dst_col[g] = d_dst_col[g];
     }
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "dsp_scatter_group_rows_batch: dry_run: launches are refused under dsp_debug_host_dry_run");
+    if (int rc = dsp_refuse_dry_run("dsp_scatter_group_rows_batch")) return rc;
     const int32_t row_words = row_bytes / 4;                 // n_utt * row_words <= 65535 * 64: at most 16384 workgroups a group
     const dim3 grid((unsigned)(((int64_t)n_utt * row_words + 255) / 256), (unsigned)n_groups);
     scatter_group_rows_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(A, n_utt, row_words, static_cast<uint32_t*>(d_out));

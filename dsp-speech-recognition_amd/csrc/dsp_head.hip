@@ -19,7 +19,7 @@ int head_pool_check(const char* who, int32_t T, int32_t B, int32_t H, int64_t ld
         return dsp_fail(DSP_EINVAL, "%s: the columns of the average (%d) and of the maximum (%d) overlap", who, col_avg, col_max);
     const int64_t last = (int64_t)(col_avg > col_max ? col_avg : col_max) + H;
     if (ld < last) return dsp_fail(DSP_EINVAL, "%s: %s %lld is below the %lld columns %s", who, ld_name, (long long)ld, (long long)last, verb);
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
     return DSP_OK;
 }
 
@@ -52,7 +52,7 @@ int dsp_head_lengths_batch(const int32_t* d_len0, int32_t B, int32_t T, int32_t 
     if (B < 1 || B > HEAD_MAX_B) return dsp_fail(DSP_EINVAL, "%s: B %d must be in [1, %d]", who, B, HEAD_MAX_B);
     if (T < 1) return dsp_fail(DSP_EINVAL, "%s: T %d must be >= 1", who, T);
     if (hir < 1) return dsp_fail(DSP_EINVAL, "%s: hir %d must be >= 1", who, hir);
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
     head_lengths_kernel<<<1, HEAD_LEN_THREADS, 0, (hipStream_t)stream>>>(d_len0, B, T, hir, d_len0c, d_len1, d_info);
     HIP_TRY(hipGetLastError());
     return DSP_OK;

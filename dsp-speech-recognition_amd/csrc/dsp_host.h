@@ -1,4 +1,5 @@
-// Host-side plumbing shared by the translation units of libdsp_frontend.so (dsp_frontend.hip, dsp_rnn.hip, dsp_ensemble.hip).
+// Host-side plumbing shared by the twelve translation units of libdsp_frontend.so: the error string, HIP_TRY, the grid size,
+// and (host_checks.h) the vocabulary of the argument checks.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,6 +15,8 @@ __attribute__((visibility("hidden"))) int dsp_fail(int code, const char* fmt, ..
         hipError_t e_ = (expr);                                                                   \
         if (e_ != hipSuccess) return dsp_fail(DSP_EHIP, "%s: %s", #expr, hipGetErrorString(e_));  \
     } while (0)
+
+#include "host_checks.h"
 
 static inline int grid_for(int64_t work_items, int per_block) {
     int64_t blocks = (work_items + per_block - 1) / per_block;

@@ -8,19 +8,6 @@
 
 namespace {
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-struct Range {
-    const char* name;
-    uintptr_t lo, hi;       // [lo, hi)
-    bool output;
-};
-
-Range range_of(const char* name, const void* p, int64_t bytes, bool output) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return Range{name, lo, lo + (uintptr_t)bytes, output};
-}
-
 int check_sizes(const char* who, int32_t n_classes, int32_t wrong_capacity) {
     if (n_classes < 2 || n_classes > XENT_MAX_CLASSES)
         return dsp_fail(DSP_EINVAL, "%s: n_classes %d must be in [2, %d]", who, n_classes, XENT_MAX_CLASSES);
@@ -47,7 +34,7 @@ int dsp_metrics_reset(void* d_state, int32_t n_classes, int32_t wrong_capacity, 
     if (!d_state) return dsp_fail(DSP_EINVAL, "%s: NULL d_state", who);
     if (!aligned(d_state, 8)) return dsp_fail(DSP_EINVAL, "%s: d_state must be 8-byte aligned", who);
     if (int rc = check_sizes(who, n_classes, wrong_capacity)) return rc;
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
     const long long n_words = xent_state_bytes(n_classes, wrong_capacity) / 4;
     xent_reset_kernel<<<grid_for(n_words, 256), 256, 0, (hipStream_t)stream>>>(static_cast<int32_t*>(d_state), n_words);
     HIP_TRY(hipGetLastError());
@@ -75,23 +62,19 @@ int dsp_xent_metrics_batch(const float* d_logits, int64_t ld_logits, int32_t n_u
 
     // the outputs must lie apart from each other and from every input (inputs may share memory)
     const int64_t n = n_utt, C = n_classes;
-    Range r[10];
-    int k = 0;
-    r[k++] = range_of("d_logits", d_logits, ((n - 1) * ld_logits + C) * 4, false);
-    r[k++] = range_of("d_labels", d_labels, n * 8, false);
-    if (d_pred_in) r[k++] = range_of("d_pred_in", d_pred_in, n * 4, false);
-    if (d_grad_out) r[k++] = range_of("d_grad_out", d_grad_out, 4, false);
-    if (d_nll) r[k++] = range_of("d_nll", d_nll, n * 4, true);
-    if (d_loss) r[k++] = range_of("d_loss", d_loss, 4, true);
-    if (d_pred) r[k++] = range_of("d_pred", d_pred, n * 4, true);
-    if (d_prob) r[k++] = range_of("d_prob", d_prob, n * C * 4, true);
-    if (d_dlogits) r[k++] = range_of("d_dlogits", d_dlogits, ((n - 1) * ld_dlogits + C) * 4, true);
-    if (d_state) r[k++] = range_of("d_state", d_state, xent_state_bytes(n_classes, wrong_capacity), true);
-    for (int i = 0; i < k; ++i)
-        for (int j = i + 1; j < k; ++j)
-            if ((r[i].output || r[j].output) && r[i].lo < r[j].hi && r[j].lo < r[i].hi)
-                return dsp_fail(DSP_EINVAL, "%s: %s overlaps %s", who, r[j].name, r[i].name);
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    Ranges rg;
+    rg.add("d_logits", d_logits, ((n - 1) * ld_logits + C) * 4, false);
+    rg.add("d_labels", d_labels, n * 8, false);
+    rg.add("d_pred_in", d_pred_in, n * 4, false);
+    rg.add("d_grad_out", d_grad_out, 4, false);
+    rg.add("d_nll", d_nll, n * 4, true);
+    rg.add("d_loss", d_loss, 4, true);
+    rg.add("d_pred", d_pred, n * 4, true);
+    rg.add("d_prob", d_prob, n * C * 4, true);
+    rg.add("d_dlogits", d_dlogits, ((n - 1) * ld_dlogits + C) * 4, true);
+    rg.add("d_state", d_state, xent_state_bytes(n_classes, wrong_capacity), true);
+    if (int rc = rg.check(who)) return rc;
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
 
     XentParams P = {};
     P.logits = d_logits; P.ld_logits = ld_logits;

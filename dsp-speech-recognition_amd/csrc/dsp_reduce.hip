@@ -44,15 +44,15 @@ int dsp_rows_colsum(const dsp_rows_operand* a, const dsp_rows_operand* x, int32_
         return dsp_fail(DSP_EINVAL, "%s: scratch of %lld bytes is short of the %lld dsp_rows_colsum_scratch_bytes asks for", who,
                         (long long)scratch_bytes, (long long)need);
     // output and scratch against everything that is read, and against each other
-    const Range outs[2] = {range_of(d_out, cols), range_of(d_scratch, need / 4)};
+    const Range outs[2] = {range_of(d_out, cols * 4), range_of(d_scratch, need)};
     const char* out_names[2] = {"d_out", "scratch"};
-    const Range ins[3] = {ra, rx, d_rows ? range_of(d_rows, 1) : Range{0, 0}};
+    const Range ins[3] = {ra, rx, range_of(d_rows, 4)};
     const char* in_names[3] = {"operand a", "operand x", "d_rows"};
     for (int o = 0; o < 2; ++o)
         for (int i = 0; i < 3; ++i)
             if (overlap(outs[o], ins[i])) return dsp_fail(DSP_EINVAL, "%s: %s overlaps %s", who, out_names[o], in_names[i]);
     if (overlap(outs[0], outs[1])) return dsp_fail(DSP_EINVAL, "%s: d_out overlaps scratch", who);
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
 
     hipStream_t st = (hipStream_t)stream;
     const int steps = wgrad_chunk_steps(B);

@@ -10,31 +10,6 @@
 
 namespace {
 
-struct Range {
-    uintptr_t lo, hi;
-};
-
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-Range range_of(const void* p, int64_t bytes) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return p ? Range{lo, lo + (uintptr_t)bytes} : Range{0, 0};
-}
-
-bool overlap(Range a, Range b) { return a.lo < b.hi && b.lo < a.hi; }
-
-// Every output against every input and against the other outputs.
-int check_overlaps(const char* who, const Range* outs, const char* const* out_names, int n_out, const Range* ins,
-                   const char* const* in_names, int n_in) {
-    for (int o = 0; o < n_out; ++o) {
-        for (int i = 0; i < n_in; ++i)
-            if (overlap(outs[o], ins[i])) return dsp_fail(DSP_EINVAL, "%s: %s overlaps %s", who, out_names[o], in_names[i]);
-        for (int q = o + 1; q < n_out; ++q)
-            if (overlap(outs[o], outs[q])) return dsp_fail(DSP_EINVAL, "%s: %s overlaps %s", who, out_names[o], out_names[q]);
-    }
-    return DSP_OK;
-}
-
 int check_matrix(const char* who, const double* d_X, int64_t ld, int32_t n, int32_t n_min, int32_t F) {
     if (!d_X) return dsp_fail(DSP_EINVAL, "%s: NULL matrix d_X", who);
     if (!aligned(d_X, 8)) return dsp_fail(DSP_EINVAL, "%s: d_X must be 8-byte aligned", who);
@@ -91,7 +66,7 @@ int dsp_robust_scale_fit_batch(const double* d_X, int64_t ld, int32_t n, int32_t
     const Range ins[2] = {range_of(d_X, matrix_bytes(ld, n, F)), range_of(d_valid, d_valid ? ((int64_t)(n - 1) * ld_valid + 1) * 4 : 0)};
     const char* in_names[2] = {"d_X", "d_valid"};
     if (int rc = check_overlaps(who, outs, out_names, 3, ins, in_names, 2)) return rc;
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
 
     int32_t npad = 2;
     while (npad < n) npad <<= 1;
@@ -118,7 +93,7 @@ int dsp_var_all(const double* d_X, int64_t ld, int32_t n, int32_t F, const doubl
     const Range ins[4] = {range_of(d_X, matrix_bytes(ld, n, F)), range_of(d_center, F * 8), range_of(d_scale, F * 8), range_of(d_mask, n)};
     const char* in_names[4] = {"d_X", "d_center", "d_scale", "d_mask"};
     if (int rc = check_overlaps(who, outs, out_names, 1, ins, in_names, 4)) return rc;
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
     svmfit_var_all_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(d_X, ld, n, F, d_center, d_scale, d_mask, d_out);
     HIP_TRY(hipGetLastError());
     return DSP_OK;
@@ -162,7 +137,7 @@ int dsp_svm_fit_batch(const double* d_X, int64_t ld, int32_t n, int32_t F, const
                           range_of(d_gamma, (int64_t)P * 8), range_of(d_center, F * 8), range_of(d_scale, F * 8)};
     const char* in_names[6] = {"d_X", "d_Y", "d_C", "d_gamma", "d_center", "d_scale"};
     if (int rc = check_overlaps(who, outs, out_names, 4, ins, in_names, 6)) return rc;
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
 
     hipStream_t st = (hipStream_t)stream;
     double* xs = static_cast<double*>(d_work);

@@ -46,27 +46,22 @@ int dsp_rows_wgrad(const dsp_rows_operand* a, const dsp_rows_operand* x, int32_t
     if (scratch_bytes < need)
         return dsp_fail(DSP_EINVAL, "%s: scratch of %lld bytes is short of the %lld dsp_rows_wgrad_scratch_bytes asks for", who,
                         (long long)scratch_bytes, (long long)need);
-    Range ri{0, 0}, rs{0, 0};
+    Range ri{0, 0};
     if (d_x_init) {
         if (shift != -1) return dsp_fail(DSP_EINVAL, "%s: an initial row needs shift -1 (got %d)", who, shift);
         if (init_stride_b < n || init_stride_b > ((int64_t)1 << 40) / B)
             return dsp_fail(DSP_EINVAL, "%s: init_stride_b %lld must be in [%d, 2^40 / B]", who, (long long)init_stride_b, n);
-        ri = range_of(d_x_init, (int64_t)(B - 1) * init_stride_b + n);
+        ri = range_of(d_x_init, ((int64_t)(B - 1) * init_stride_b + n) * 4);
         if (!(aligned(d_x_init, 16) && (init_stride_b & 3) == 0)) X.vec = 0;
     }
-    if (d_scale) rs = range_of(d_scale, (int64_t)T * B);
+    const Range rs = range_of(d_scale, (int64_t)T * B * 4);
     // outputs and scratch against everything that is read, and against each other
-    const Range outs[3] = {range_of(d_c, (int64_t)m * n), d_colsum ? range_of(d_colsum, m) : Range{0, 0}, range_of(d_scratch, need / 4)};
+    const Range outs[3] = {range_of(d_c, (int64_t)m * n * 4), range_of(d_colsum, m * 4), range_of(d_scratch, need)};
     const char* out_names[3] = {"d_c", "d_colsum", "scratch"};
-    const Range ins[5] = {ra, rx, ri, rs, d_rows ? range_of(d_rows, 1) : Range{0, 0}};
+    const Range ins[5] = {ra, rx, ri, rs, range_of(d_rows, 4)};
     const char* in_names[5] = {"operand a", "operand x", "the initial row", "the scale", "d_rows"};
-    for (int o = 0; o < 3; ++o) {
-        for (int i = 0; i < 5; ++i)
-            if (overlap(outs[o], ins[i])) return dsp_fail(DSP_EINVAL, "%s: %s overlaps %s", who, out_names[o], in_names[i]);
-        for (int p = o + 1; p < 3; ++p)
-            if (overlap(outs[o], outs[p])) return dsp_fail(DSP_EINVAL, "%s: %s overlaps %s", who, out_names[o], out_names[p]);
-    }
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (int rc = check_overlaps(who, outs, out_names, 3, ins, in_names, 5)) return rc;
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
 
     hipStream_t st = (hipStream_t)stream;
     const int steps = wgrad_chunk_steps(B);
@@ -102,17 +97,17 @@ int dsp_rows_product(const dsp_rows_operand* a0, const float* d_w0, const dsp_ro
         if (!aligned(ws[p], 4)) return dsp_fail(DSP_EINVAL, "%s: every pointer must be 4-byte aligned", who);
         P[p].w = ws[p];
         P[p].wvec = aligned(ws[p], 16) && (n & 3) == 0;
-        rw[p] = range_of(ws[p], (int64_t)P[p].a.cols * n);
+        rw[p] = range_of(ws[p], (int64_t)P[p].a.cols * n * 4);
     }
     if (!d_y) return dsp_fail(DSP_EINVAL, "%s: NULL output d_y", who);
     if (!aligned(d_y, 4) || (d_rows && !aligned(d_rows, 4))) return dsp_fail(DSP_EINVAL, "%s: every pointer must be 4-byte aligned", who);
-    const Range ry = range_of(d_y, (int64_t)T * B * n);
+    const Range ry = range_of(d_y, (int64_t)T * B * n * 4);
     for (int p = 0; p < nterms; ++p) {
         if (overlap(ry, ra[p])) return dsp_fail(DSP_EINVAL, "%s: d_y overlaps operand %s", who, names[p]);
         if (overlap(ry, rw[p])) return dsp_fail(DSP_EINVAL, "%s: d_y overlaps d_w%d", who, p);
     }
-    if (d_rows && overlap(ry, range_of(d_rows, 1))) return dsp_fail(DSP_EINVAL, "%s: d_y overlaps d_rows", who);
-    if (g_host_dry_run) return dsp_fail(DSP_EINVAL, "%s: dry_run: launches are refused under dsp_debug_host_dry_run", who);
+    if (overlap(ry, range_of(d_rows, 4))) return dsp_fail(DSP_EINVAL, "%s: d_y overlaps d_rows", who);
+    if (int rc = dsp_refuse_dry_run(who)) return rc;
 
     const int64_t total = (int64_t)T * B;
     const dim3 grid((unsigned)((total + WGRAD_TILE - 1) / WGRAD_TILE), (n + WGRAD_TILE - 1) / WGRAD_TILE);

@@ -1,5 +1,5 @@
-// The argument checks shared by the row-bounded entry points (csrc/dsp_wgrad.hip, csrc/dsp_reduce.hip): sizes, one operand
-// view, address ranges.  Host only.
+// The argument checks shared by the row-bounded entry points (csrc/dsp_wgrad.hip, csrc/dsp_reduce.hip): sizes and one
+// operand view.  Host only.
 #pragma once
 
 #include <stdint.h>
@@ -9,19 +9,6 @@
 #include "kernels_wgrad.h"
 
 namespace {
-
-struct Range {
-    uintptr_t lo, hi;
-};
-
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-Range range_of(const void* p, int64_t floats) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return Range{lo, lo + (uintptr_t)floats * 4};
-}
-
-bool overlap(Range a, Range b) { return a.lo < b.hi && b.lo < a.hi; }
 
 int check_sizes(const char* who, int32_t T, int32_t B) {
     if (T < 1) return dsp_fail(DSP_EINVAL, "%s: T %d must be >= 1", who, T);
@@ -52,7 +39,7 @@ int check_operand(const char* who, const char* name, const dsp_rows_operand* op,
     out->sb = op->stride_b;
     out->cols = op->cols;
     out->vec = aligned(op->d_ptr, 16) && (op->stride_t & 3) == 0 && (op->stride_b & 3) == 0;
-    *span = range_of(op->d_ptr, (int64_t)(T - 1) * op->stride_t + (int64_t)(B - 1) * op->stride_b + op->cols);
+    *span = range_of(op->d_ptr, ((int64_t)(T - 1) * op->stride_t + (int64_t)(B - 1) * op->stride_b + op->cols) * 4);
     return DSP_OK;
 }
 

@@ -8,18 +8,8 @@
 #include <cstdio>
 #include <cstring>
 
+#include "asan_args.h"
 #include "dsp_frontend.h"
-
-static int g_bad = 0;
-
-static void expect(int rc, const char* what, int line) {
-    const char* e = dsp_last_error();
-    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
-        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
-        ++g_bad;
-    }
-}
-#define EXPECT(call, what) expect((call), (what), __LINE__)
 
 namespace {
 
@@ -155,7 +145,5 @@ int main() {
     TRAIN(refused, x.db2 = nullptr; x.work_bytes = need);
     dsp_debug_host_dry_run(0);
 
-    if (g_bad) { std::printf("asan_adv_args: %d FAILED\n", g_bad); return 1; }
-    std::printf("asan_adv_args: ok\n");
-    return 0;
+    return finish("asan_adv_args");
 }

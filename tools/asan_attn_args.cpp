@@ -12,26 +12,8 @@
 #include <limits>
 #include <vector>
 
+#include "asan_args.h"
 #include "dsp_frontend.h"
-
-static int g_bad = 0;
-
-static void expect(int rc, const char* what, int line) {
-    const char* e = dsp_last_error();
-    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
-        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
-        ++g_bad;
-    }
-}
-static void expect_ok(int rc, int line) {
-    if (rc != DSP_OK) {
-        const char* e = dsp_last_error();
-        std::printf("line %d: rc %d, message '%s', expected DSP_OK\n", line, rc, e ? e : "(none)");
-        ++g_bad;
-    }
-}
-#define EXPECT(call, what) expect((call), (what), __LINE__)
-#define EXPECT_OK(call) expect_ok((call), __LINE__)
 
 // The 13 parameters of a block as exact-size host arrays.
 struct Block {
@@ -229,7 +211,5 @@ int main() {
     EXPECT(dsp_selfattn_pool_backward_batch(yy, 1, 1, 4, W, bW, v, w1, go, nullptr, gp, ge, gv, nullptr), "dry_run: launches are refused");   // d_gy is optional
 
     dsp_debug_host_dry_run(0);
-    if (g_bad) { std::printf("asan_attn_args: %d FAILED\n", g_bad); return 1; }
-    std::printf("asan_attn_args: ok\n");
-    return 0;
+    return finish("asan_attn_args");
 }

@@ -11,26 +11,8 @@
 #include <limits>
 #include <vector>
 
+#include "asan_args.h"
 #include "dsp_frontend.h"
-
-static int g_bad = 0;
-
-static void expect(int rc, const char* what, int line) {
-    const char* e = dsp_last_error();
-    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
-        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
-        ++g_bad;
-    }
-}
-static void expect_ok(int rc, int line) {
-    if (rc != DSP_OK) {
-        const char* e = dsp_last_error();
-        std::printf("line %d: rc %d, message '%s', expected DSP_OK\n", line, rc, e ? e : "(none)");
-        ++g_bad;
-    }
-}
-#define EXPECT(call, what) expect((call), (what), __LINE__)
-#define EXPECT_OK(call) expect_ok((call), __LINE__)
 
 int main() {
     dsp_debug_host_dry_run(1);
@@ -143,6 +125,5 @@ int main() {
     EXPECT_OK(dsp_svm_destroy(c3));
     for (dsp_svm* m : made) EXPECT_OK(dsp_svm_destroy(m));
     dsp_debug_host_dry_run(0);
-    std::printf("asan_ensemble_args: %s\n", g_bad ? "FAILED" : "ok");
-    return g_bad ? 1 : 0;
+    return finish("asan_ensemble_args");
 }

@@ -7,18 +7,8 @@
 #include <cstdio>
 #include <cstring>
 
+#include "asan_args.h"
 #include "dsp_frontend.h"
-
-static int g_bad = 0;
-
-static void expect(int rc, const char* what, int line) {
-    const char* e = dsp_last_error();
-    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
-        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
-        ++g_bad;
-    }
-}
-#define EXPECT(call, what) expect((call), (what), __LINE__)
 
 int main() {
     // never reached by a kernel: every call below returns before a launch
@@ -87,7 +77,5 @@ int main() {
     EXPECT(XENT(fake, 64, 16384, 64, fake_l, nullptr, nullptr, nullptr, loss, nullptr, nullptr, nullptr, 0, nullptr, 0), refused);
     dsp_debug_host_dry_run(0);
 
-    if (g_bad) { std::printf("asan_loss_args: %d FAILED\n", g_bad); return 1; }
-    std::printf("asan_loss_args: ok\n");
-    return 0;
+    return finish("asan_loss_args");
 }

@@ -8,18 +8,8 @@
 #include <cstdio>
 #include <cstring>
 
+#include "asan_args.h"
 #include "dsp_frontend.h"
-
-static int g_bad = 0;
-
-static void expect(int rc, const char* what, int line) {
-    const char* e = dsp_last_error();
-    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
-        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
-        ++g_bad;
-    }
-}
-#define EXPECT(call, what) expect((call), (what), __LINE__)
 
 int main() {
     dsp_debug_host_dry_run(1);
@@ -92,6 +82,5 @@ int main() {
     EXPECT(dsp_gather_clips_batch(pcm, -1, offs, ints, 3, offs, pcm, nullptr), "wave_dtype");
 
     dsp_debug_host_dry_run(0);
-    std::printf("asan_mixed_args: %s\n", g_bad ? "FAILED" : "ok");
-    return g_bad ? 1 : 0;
+    return finish("asan_mixed_args");
 }

@@ -10,18 +10,8 @@
 #include <cstring>
 #include <vector>
 
+#include "asan_args.h"
 #include "dsp_frontend.h"
-
-static int g_bad = 0;
-
-static void expect_einval(int rc, const char* what, int line) {
-    const char* e = dsp_last_error();
-    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
-        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
-        ++g_bad;
-    }
-}
-#define EXPECT(call, what) expect_einval((call), (what), __LINE__)
 
 // exactly-sized tables (a read past any of them is an ASan report): M triangular filters over K bins, filter j = bins
 // [j * step + lo, ...) of width `w0 + j / grow`, so that the first ones have one and two taps
@@ -159,6 +149,5 @@ int main() {
         EXPECT(dsp_plan_create(&d, &p), "h_window");
     }
     dsp_debug_host_dry_run(0);
-    std::printf(g_bad ? "%d FAILED\n" : "plan descriptor: all checks passed\n", g_bad);
-    return g_bad ? 1 : 0;
+    return finish("asan_plan_args");
 }

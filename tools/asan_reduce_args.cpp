@@ -8,18 +8,8 @@
 #include <cstdio>
 #include <cstring>
 
+#include "asan_args.h"
 #include "dsp_frontend.h"
-
-static int g_bad = 0;
-
-static void expect(int rc, const char* what, int line) {
-    const char* e = dsp_last_error();
-    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
-        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
-        ++g_bad;
-    }
-}
-#define EXPECT(call, what) expect((call), (what), __LINE__)
 
 static dsp_rows_operand op(const float* p, int64_t st, int64_t sb, int32_t cols, int32_t reserved = 0) {
     dsp_rows_operand o;
@@ -132,7 +122,5 @@ int main() {
     EXPECT(dsp_graph_census(nullptr, &census, nullptr, 8), "NULL names with names_bytes 8");
 
     dsp_debug_host_dry_run(0);
-    if (g_bad) { std::printf("asan_reduce_args: %d FAILED\n", g_bad); return 1; }
-    std::printf("asan_reduce_args: ok\n");
-    return 0;
+    return finish("asan_reduce_args");
 }

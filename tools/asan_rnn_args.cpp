@@ -7,18 +7,8 @@
 #include <cstdio>
 #include <cstring>
 
+#include "asan_args.h"
 #include "dsp_frontend.h"
-
-static int g_bad = 0;
-
-static void expect(int rc, const char* what, int line) {
-    const char* e = dsp_last_error();
-    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
-        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
-        ++g_bad;
-    }
-}
-#define EXPECT(call, what) expect((call), (what), __LINE__)
 
 int main() {
     alignas(16) static float buf[64];                 // pointers that are only checked, never followed
@@ -75,6 +65,5 @@ int main() {
     EXPECT(dsp_bigru_refresh(reinterpret_cast<dsp_bigru*>(buf), nullptr, nullptr), "NULL argument");
     EXPECT(dsp_hmlstm_refresh(nullptr, &hd, nullptr), "NULL argument");
     EXPECT(dsp_hmlstm_refresh(reinterpret_cast<dsp_hmlstm*>(buf), nullptr, nullptr), "NULL argument");
-    std::printf("asan_rnn_args: %s\n", g_bad ? "FAILED" : "ok");
-    return g_bad ? 1 : 0;
+    return finish("asan_rnn_args");
 }

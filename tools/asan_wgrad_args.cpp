@@ -7,18 +7,8 @@
 #include <cstdio>
 #include <cstring>
 
+#include "asan_args.h"
 #include "dsp_frontend.h"
-
-static int g_bad = 0;
-
-static void expect(int rc, const char* what, int line) {
-    const char* e = dsp_last_error();
-    if (rc != DSP_EINVAL || !e || !std::strstr(e, what)) {
-        std::printf("line %d: rc %d, message '%s', expected DSP_EINVAL with '%s'\n", line, rc, e ? e : "(none)", what);
-        ++g_bad;
-    }
-}
-#define EXPECT(call, what) expect((call), (what), __LINE__)
 
 static dsp_rows_operand op(const float* p, int64_t st, int64_t sb, int32_t cols, int32_t reserved = 0) {
     dsp_rows_operand o;
@@ -138,7 +128,5 @@ int main() {
     EXPECT(dsp_rows_product(&a, w0, nullptr, nullptr, 4, 2, 2, nullptr, abuf + 16, nullptr), refused);   // right behind the operand
 
     dsp_debug_host_dry_run(0);
-    if (g_bad) { std::printf("asan_wgrad_args: %d FAILED\n", g_bad); return 1; }
-    std::printf("asan_wgrad_args: ok\n");
-    return 0;
+    return finish("asan_wgrad_args");
 }
